@@ -10,6 +10,11 @@ sub-steps (6x train_disc, 6x train_gen) with train-mode dropout, BCE, backward a
 IEMOCAP-schema batch of 32 dialogues per GPU padded to S = 94 (BASELINE.json configs[1]).  Weak scaling:
 every rank owns its own 32 dialogues; gradients are all-reduced (RCCL) per sub-step.
 Prints ONE JSON line on rank 0.
+
+The --warmup and --steps iterations start from the seeded initial training state (parameters, Adam state and dropout
+stream are restored after the timing-dependent pre-roll), so what they compute depends on the arguments only.
+`--dump-outputs DIR` writes what the last timed step computed (its losses and the networks' parameters after it; slabs
+larger than DUMP_SAMPLE floats as a fixed, seeded sample) to DIR/<name>.npy in float32, for comparing two builds.
 """
 import argparse
 import ctypes as C
@@ -29,6 +34,8 @@ L2_SERVED_GBS = 16800.0         # same guide, "Indexed rows: gather into LDS": r
 FP32_MFMA_PEAK = 157.3e12      # /opt/skills/guides/MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, 256 CU x 2.4 GHz
 # algorithmic FLOPs of one iteration per padded token at S = 94: fwd 409.5 + bwd 544.8 MFLOP
 FLOP_PER_TOKEN_ITER = 954.3e6
+DUMP_SAMPLE = 1 << 20           # --dump-outputs: floats kept per parameter slab
+DUMP_MAX_BYTES = 64 << 20       # --dump-outputs: all arrays together
 
 
 def flops_per_token(S, config="iemocap"):
@@ -430,6 +437,45 @@ def build_workload(config, dev):
     return engine.build_networks(device=dev, seed=3407)       # random init of the reference architecture
 
 
+def save_training_state(eng):
+    """host copy of everything a GanEngine iteration carries into the next one (every network's parameters, gradients, Adam
+    moments and step counter; the dropout stream's device offset and host counter) -> a function that puts it back.  On the
+    host, so that the engine's device buffers are allocated exactly as without it."""
+    tensors = [t for st in list(eng.G.values()) + list(eng.D.values())
+               for t in (st.slab, st.grad, st.exp_avg, st.exp_avg_sq, st.step)]
+    saved = [t.cpu() for t in tensors]
+    rng = eng.rng.state_dict()
+
+    def restore():
+        torch.cuda.synchronize()
+        for t, s in zip(tensors, saved):
+            t.copy_(s)
+        eng.rng.load_state_dict(rng)
+        torch.cuda.synchronize()
+    return restore
+
+
+def slab_sample(slab):
+    """a parameter slab as float32 on the host: whole up to DUMP_SAMPLE floats, else DUMP_SAMPLE of them at sorted indices
+    drawn from a generator seeded with the slab's length (the same indices on every run and every build)"""
+    n = slab.numel()
+    if n <= DUMP_SAMPLE:
+        return slab.detach().float().cpu().numpy()
+    idx = torch.randperm(n, generator=torch.Generator().manual_seed(n))[:DUMP_SAMPLE].sort().values
+    return slab.detach()[idx.to(slab.device)].float().cpu().numpy()
+
+
+def dump_outputs(out_dir, arrays):
+    """write {name: float32 array} as out_dir/<name>.npy (--dump-outputs)"""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, "outputs to dump: %d bytes, more than %d" % (total, DUMP_MAX_BYTES)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    print("[bench] %d arrays (%.1f MB) written to %s" % (len(arrays), total / 1e6, out_dir), file=sys.stderr, flush=True)
+
+
 DRNN_IN_STEP_FILE = "profiles/r05_drnn_by_launch_shape.txt"
 
 
@@ -497,7 +543,7 @@ def run_drnn(args, dev, pg, rank, world):
                             n_streams=int(os.environ.get("GANFFN_DRNN_STREAMS", "1")))
 
     def step():
-        return eng.step(batch, train=True)[0]
+        return eng.step(batch, train=True)
 
     def sync():
         torch.cuda.synchronize()
@@ -511,9 +557,15 @@ def run_drnn(args, dev, pg, rank, world):
     sync()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        loss = step()
+        loss, log_prob = step()
     sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        arrays = {"loss": loss.detach().float().cpu().numpy().reshape(-1), "log_prob": log_prob.detach().float().cpu().numpy()}
+        for k, st in eng.G.items():
+            arrays["params_G_" + k] = slab_sample(st.slab)
+        arrays["params_head"] = slab_sample(eng.h_slab)
+        dump_outputs(args.dump_outputs, arrays)
     utts = float(batch["umask"].sum())
     if pg is not None:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -911,7 +963,17 @@ def main():
     ap.add_argument("--replay-family", choices=["wgrad", "gemm_generic", "attention", "ffn_k100", "ffn_n100"], default=None,
                     help="only replay one kernel family's launch mix (warm-up pass + one timed pass): the command "
                          "tools/traffic_pmc.sh / tools/attention_pmc.sh profile with rocprofv3 --pmc, one counter set per pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (float32, <= 64 MB in all; "
+                         "rank 0): the losses and the networks' parameters after the step (a fixed, seeded sample of each "
+                         "slab larger than %d floats); --config drnn also the log-probabilities" % DUMP_SAMPLE)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs and args.replay_family:
+        ap.error("--dump-outputs needs the timed step; --replay-family does not run it")
     if args.seq is None:
         args.seq = 33 if args.config == "meld" else 94
     if args.config == "drnn" and args.batch == 32:
@@ -1000,10 +1062,13 @@ def main():
             torch.cuda.synchronize()
 
     heartbeat("rank %d: engine built (dp_mode %s, %d streams)" % (rank, engine.dp_mode() if pg is not None else "none", eng.n_streams), rank, every_rank=True)
+    restore_training_state = save_training_state(eng)
     # internal pre-roll (not counted in --warmup): until two consecutive 5-iteration windows agree within 0.3 %, <= 1.5 s —
     # so that the line does not depend on how many warm-up steps the caller asked for
     n_preroll = 0 if os.environ.get("GANFFN_BENCH_PREROLL", "1") == "0" else preroll(lambda: eng.iteration(batch), sync, pg, dev)
     heartbeat("rank %d: pre-roll %d iterations" % (rank, n_preroll), rank, every_rank=True)
+    # the pre-roll's length depends on timing: warm-up and timed steps start again from the seeded initial state
+    restore_training_state()
     for _ in range(args.warmup):
         eng.iteration(batch)
     sync()
@@ -1013,6 +1078,12 @@ def main():
     sync()
     dt = time.perf_counter() - t0
     losses = eng.loss_dict()
+    if args.dump_outputs and rank == 0:
+        arrays = {"losses": eng.losses.detach().float().cpu().numpy()}
+        for kind, nets in (("G", eng.G), ("D", eng.D)):
+            for k, st in nets.items():
+                arrays["params_%s_%s" % (kind, k)] = slab_sample(st.slab)
+        dump_outputs(args.dump_outputs, arrays)
     heartbeat("rank %d: %d timed steps, %.3f ms per step" % (rank, args.steps, dt / args.steps * 1e3), rank, every_rank=True)
     # second, separately timed block (median over >= 20 device-synchronised iterations): here every iteration
     # is bracketed by a device synchronisation (+ barrier), so consecutive iterations do NOT overlap as they do in the block

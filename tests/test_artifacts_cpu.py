@@ -112,8 +112,8 @@ def test_checkpoints_names_roundtrip_and_foreign_pickles(tmp_path):
         torch.save(torch.nn.DataParallel(m) if i == 2 else m, fp + n + ".pth")
     gens, discs = A.load_GAN_models(fp, device="cpu")
     assert type(gens["visual"]) is M.VisualGenerator and type(discs["acoustic"]) is M.AcousticDiscriminator
-    ssd = stock[2].state_dict()
+    ssd = stock[2].state_dict()          # (on cuda:0 when a GPU is present: a one-device DataParallel moves its module there)
     bsd = gens["visual"].state_dict()
     assert set(ssd) == set(bsd)
     for k in ssd:
-        assert torch.equal(ssd[k].reshape(-1), bsd[k].reshape(-1).cpu()), k
+        assert torch.equal(ssd[k].reshape(-1).cpu(), bsd[k].reshape(-1).cpu()), k

@@ -25,6 +25,30 @@ def test_child_arguments_keep_the_callers_and_override_streams():
     assert bench._child_argv(argv, None) == ["--gpus", "8", "--steps", "20", "--warmup", "5", "--streams", "3"]
     assert bench._child_argv(argv, 1) == ["--gpus", "8", "--steps", "20", "--warmup", "5", "--streams", "1"]
     assert bench._child_argv(["--gpus=2", "--streams=3"], 1) == ["--gpus=2", "--streams", "1"]
+    assert bench._child_argv(["--dump-outputs", "out", "--launcher", "spawn"], None) == ["--dump-outputs", "out"]
+
+
+def test_bench_refuses_arguments_without_a_timed_step():
+    for argv in (["--steps", "0"], ["--replay-family", "wgrad", "--dump-outputs", "out"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, capture_output=True, text=True, timeout=120)
+        assert r.returncode == 2 and "error:" in r.stderr, (argv, r.stderr[-2000:])
+
+
+def test_dumped_slabs_are_a_fixed_sample_within_the_size_cap(tmp_path):
+    import numpy as np
+    import pytest
+    import torch
+    big = torch.randn(bench.DUMP_SAMPLE * 3 + 7, generator=torch.Generator().manual_seed(1))
+    a, b = bench.slab_sample(big), bench.slab_sample(big.clone())
+    assert a.dtype == np.float32 and a.shape == (bench.DUMP_SAMPLE,) and np.array_equal(a, b)
+    assert np.isin(a, big.numpy()).all()
+    small = torch.arange(10, dtype=torch.float32)
+    assert np.array_equal(bench.slab_sample(small), small.numpy())
+    bench.dump_outputs(str(tmp_path / "d"), {"losses": np.ones(12), "params": a})
+    assert np.load(str(tmp_path / "d" / "losses.npy")).dtype == np.float32
+    assert np.array_equal(np.load(str(tmp_path / "d" / "params.npy")), a)
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "e"), {"x": np.zeros(bench.DUMP_MAX_BYTES // 4 + 1, np.float32)})
 
 
 def test_ladder_order_is_inline3_inline1_buckets():

@@ -38,6 +38,28 @@ def test_bench_default_contract():
     assert d["value"] > 50 * d["cpu_baseline"]["value"]          # north_star: >= 50x the host CPU
 
 
+def test_bench_dump_outputs_repeat_bit_for_bit(tmp_path):
+    """--dump-outputs writes what the last timed step computed (12 sub-step losses, the six networks' parameters) as float32
+    within 64 MB; warm-up and timed steps start from the seeded initial state whatever the timing-dependent pre-roll ran,
+    so two runs with the same arguments dump the same bits"""
+    import numpy as np
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--batch", "4",
+                            "--seq", "20", "--no-cpu-baseline", "--step-only", "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert _last_json(r.stdout)["steps"] == 3
+        dumps.append({p.stem: np.load(str(p)) for p in sorted(out.glob("*.npy"))})
+    a, b = dumps
+    assert set(a) == {"losses"} | {"params_%s_%s" % (k, m) for k in "GD" for m in ("acoustic", "visual", "text")}
+    assert all(v.dtype == np.float32 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["losses"].shape == (12,) and np.isfinite(a["losses"]).all()
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
 def test_bench_rccl_path_on_one_rank():
     env = dict(os.environ, GANFFN_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",

@@ -1,6 +1,8 @@
 """Pin the oracle (oracle/ganffn_oracle.py) and the stock re-declaration
 (oracle/stock_modules.py) against the golden fixtures that tests/golden/make_golden.py
 produced by running the reference itself.  CPU only."""
+import math
+
 import numpy as np
 import pytest
 import torch
@@ -41,10 +43,16 @@ def test_philox_mask_rate_and_layout():
 
 
 def test_pe_table():
+    """bit-equal on the CPU the fixture was made on; another CPU's vector math library (MKL picks its code path by processor)
+    rounds exp / sin / cos differently in the last place, and position p scales a rounding of div_term by p.  The bound is
+    4 fp32 ulps of the argument p * div_term (measured under other MKL code paths: 0.29 of it; a table shifted by one
+    position: 1.8e6 times it)"""
     g = golden("misc")
     for d in (100, 512):
-        pe = O.pe_table(d)[:, 0, :].numpy()
-        assert np.abs(pe - g["pe/%d" % d]).max() == 0.0
+        pe = O.pe_table(d)[:, 0, :].numpy().astype(np.float64)
+        ref = g["pe/%d" % d]
+        arg = np.arange(ref.shape[0])[:, None] * np.repeat(np.exp(np.arange(0, d, 2) * (-math.log(10000.0) / d)), 2)[None, :]
+        assert pe.shape == ref.shape and (np.abs(pe - ref) <= 4 * np.finfo(np.float32).eps * (1 + arg)).all()
 
 
 @pytest.mark.parametrize("case", [
@@ -239,16 +247,23 @@ def test_module_forward_backward_at_headline_size(case):
     assert n >= 12
 
 
+# The oracle runs this trajectory in fp64: in fp32 its own rounding depends on the CPU's BLAS / vector-math code path and
+# moved the sign flips of G_visual's layer-7 linear1 weight sample between 9.96 % and 10.16 % (one element of 1024 either
+# side of HEAD_DELTA_OUTLIERS).  In fp64 the flips are the reference fixture's own noise, the same on every code path
+# measured: 10.06 % there, every other first-update delta <= 5.4 %.
+HEAD_DELTA_OUTLIERS_FP64 = 0.11
+
+
 def test_gan_iteration_matches_reference_at_headline_size():
     """the 12 sub-steps of gan_steps_big.npz (the reference's train_disc / train_gen at (94, 32), dropout p = 0): losses
     (HEAD_LOSS_TOL above) and every network's first-update deltas"""
     g = golden("gan_steps_big")
     S, B = 94, 32
-    gens = {k: make_net(v) for k, v in GEN.items()}
-    discs = {k: make_net(v) for k, v in DISC.items()}
+    gens = {k: make_net(v, torch.float64) for k, v in GEN.items()}
+    discs = {k: make_net(v, torch.float64) for k, v in DISC.items()}
     opts = O.make_optimizers(gens, discs)
-    batch = {k: torch.from_numpy(F_.formula_input("ganbig." + k, S, B, DIN[k], pad_from=61)) for k in DIN}
-    valid = torch.ones(S, B, 1)
+    batch = {k: torch.from_numpy(F_.formula_input("ganbig." + k, S, B, DIN[k], pad_from=61)).double() for k in DIN}
+    valid = torch.ones(S, B, 1, dtype=torch.float64)
     fake = torch.zeros_like(valid)
     seen = set()
     for i, (kind, who, partner) in enumerate(O.SCHEDULE):
@@ -262,4 +277,5 @@ def test_gan_iteration_matches_reference_at_headline_size():
             net = (discs if kind == "D" else gens)[who]
             # (the visual generator's first update is sub-step 9: its gradient comes through a discriminator that has
             # already taken two sign-like steps, so a few % more of its own +-lr updates flip than at sub-steps 0-4)
-            check_first_update(g, kind, who, lambda k: net.P[k].detach().numpy(), outlier_frac=HEAD_DELTA_OUTLIERS, l2_rtol=2e-2)
+            check_first_update(g, kind, who, lambda k: net.P[k].detach().numpy(), outlier_frac=HEAD_DELTA_OUTLIERS_FP64,
+                               l2_rtol=2e-2)
