@@ -39,6 +39,13 @@ class DrnnPtrs(C.Structure):        # ganffn_drnn_params / ganffn_drnn_grads: 13
     _fields_ = [(n, C.c_void_p) for n in DRNN_PARAM_FIELDS]
 
 
+DRNN_LISTENER_FIELDS = ["l_wih", "l_whh", "l_bih", "l_bhh"]
+
+
+class DrnnListenerPtrs(C.Structure):    # ganffn_drnn_listener_params / ganffn_drnn_listener_grads: 4 pointers
+    _fields_ = [(n, C.c_void_p) for n in DRNN_LISTENER_FIELDS]
+
+
 _P = C.c_void_p
 _I, _L, _F, _U32, _U64 = C.c_int, C.c_int64, C.c_float, C.c_uint32, C.c_uint64
 _PE, _PH = C.POINTER(EncCfg), C.POINTER(HeadCfg)
@@ -105,6 +112,10 @@ SIGNATURES = {
     "ganffn_drnn_workspace_floats": (_L, [C.POINTER(DrnnCfg)]),
     "ganffn_drnn_fwd": (_I, [C.POINTER(DrnnCfg), _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, _P]),
     "ganffn_drnn_bwd": (_I, [C.POINTER(DrnnCfg), _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, _P]),
+    "ganffn_drnn_listener_saved_floats": (_L, [C.POINTER(DrnnCfg)]),
+    "ganffn_drnn_listener_workspace_floats": (_L, [C.POINTER(DrnnCfg)]),
+    "ganffn_drnn_listener_fwd": (_I, [C.POINTER(DrnnCfg), _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, _P]),
+    "ganffn_drnn_listener_bwd": (_I, [C.POINTER(DrnnCfg), _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, _P]),
     "ganffn_dropout": (_I, [_P, _P, _I, _I, _F, _U32, _P, _U64, _P]),
     "ganffn_seq_reverse": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "ganffn_drnn_join_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _U32, _U32, _P, _U64, _I, _P]),

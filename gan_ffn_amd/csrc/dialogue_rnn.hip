@@ -29,13 +29,15 @@
 //   * backward mirrors it step by step in reverse; all weight gradients are deferred: the per-step gate gradients are
 //     kept and ONE grouped TN GEMM launch (gemm.hip, owner-accumulated, no atomics) computes the 9 products at the end.
 // Everything is deterministic (no atomics).  Dropout follows the Philox contract of common.h with rows t*B + b.
+// listener_state = True (model.py:899-921, --active-listener) is a variant of the same driver (ganffn_drnn_listener_fwd /
+// _bwd): 4 launches per step each way instead of 2 — see "Listener state" below.
 #include "common.h"
 
 namespace ganffn {
 
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
-enum : uint32_t { SITE_DRNN_G = 8, SITE_DRNN_P = 9, SITE_DRNN_E = 10 };   // + 4 for the second direction
+enum : uint32_t { SITE_DRNN_G = 8, SITE_DRNN_P = 9, SITE_DRNN_E = 10, SITE_DRNN_L = 11 };   // + 4 for the second direction
 
 // ------------------------------------------------------------------------------------------
 // skinny products: M <= 32 rows of A (dialogues) against a weight matrix
@@ -267,8 +269,10 @@ __device__ __forceinline__ void gru_gate_fwd_body(const GateArgs& a, const GateD
     d.R[idx] = r; d.Z[idx] = z; d.N[idx] = n; d.HN[idx] = hn;
     const DropCtx dc = make_drop(a.rng, a.add, d.site, a.p, a.train);
     hnew *= drop_mult1(dc, (uint32_t)(a.row0 + b), (uint32_t)a.H, (uint32_t)u);
-    if (!PARTY) {
+    if (PARTY == 0) {
         d.hout[idx] = hnew;
+    } else if (PARTY == 2) {
+        d.QN[idx] = hnew;     // listener path: qs after its dropout (QSP[t]); drnn_listener_fwd_kernel blends and writes Q
     } else {
         // q_t[spk] = m ? qs : q_{t-1}[spk]; the other party keeps its state (listener_state False, model.py:888-893)
         const int s = d.spk[b];
@@ -312,7 +316,7 @@ __device__ __forceinline__ void gru_gate_bwd_body(const GateBwdArgs& a, const Ga
     if (idx >= a.B * a.H) return;
     const int b = idx / a.H, u = idx - b * a.H, H3 = 3 * a.H;
     float dout;
-    if (PARTY && d.pg_out != nullptr) {
+    if (PARTY == 1 && d.pg_out != nullptr) {
         const int sn = d.pg_spk[b];
         const size_t o0 = ((size_t)b * 2) * a.H + u, o1 = o0 + a.H;
         const float own = d.pg_dQSp[idx] + d.pg_dQSg[idx];
@@ -322,11 +326,11 @@ __device__ __forceinline__ void gru_gate_bwd_body(const GateBwdArgs& a, const Ga
         d.pg_out[o1] = v1;
         dout = d.spk[b] ? v1 : v0;
     } else {
-        dout = PARTY ? d.dh[((size_t)b * 2 + d.spk[b]) * a.H + u] : d.dh[idx];
+        dout = PARTY == 1 ? d.dh[((size_t)b * 2 + d.spk[b]) * a.H + u] : d.dh[idx];   // (PARTY 2, listener: dh = d qs [B x H])
     }
     if (d.dh2) dout += d.dh2[idx];
     float pass = 0.f;
-    if (PARTY) {
+    if (PARTY == 1) {
         const float m = d.mval[b];
         pass = m != 0.f ? 0.f : dout;      // padded step: q_t[spk] = q_{t-1}[spk]
         dout = m != 0.f ? dout : 0.f;
@@ -444,10 +448,12 @@ __global__ __launch_bounds__(DR_AT) void drnn_attn_fwd_kernel(AttnArgs a) { drnn
 // step.  Blocks [0, party_blocks) run the party gate body (1024 elements each); block party_blocks + b owns dialogue b:
 // its first H threads produce g_t[b], then the whole workgroup pools g_0 .. g_t[b] for step t + 1 (the newest history row
 // was written by this very workgroup: a workgroup-scope fence + barrier orders it).
+// (PARTY = 2: the listener path's party gate, which leaves the blend to drnn_listener_fwd_kernel)
 struct GateAttnArgs { GateArgs g, p; AttnArgs at; int party_blocks, has_attn; };
-__global__ __launch_bounds__(DR_AT) void drnn_gates_attn_fwd_kernel(GateAttnArgs a) {
+template <int PARTY>
+__device__ __forceinline__ void drnn_gates_attn_fwd_body(const GateAttnArgs& a) {
     if ((int)blockIdx.x < a.party_blocks) {
-        gru_gate_fwd_body<1>(a.p, a.p.d[blockIdx.z], blockIdx.x * DR_AT + threadIdx.x);
+        gru_gate_fwd_body<PARTY>(a.p, a.p.d[blockIdx.z], blockIdx.x * DR_AT + threadIdx.x);
         return;
     }
     const int b = blockIdx.x - a.party_blocks;
@@ -457,6 +463,8 @@ __global__ __launch_bounds__(DR_AT) void drnn_gates_attn_fwd_kernel(GateAttnArgs
     __syncthreads();
     drnn_attn_fwd_body(a.at, a.at.d[blockIdx.z], b);
 }
+__global__ __launch_bounds__(DR_AT) void drnn_gates_attn_fwd_kernel(GateAttnArgs a) { drnn_gates_attn_fwd_body<1>(a); }
+__global__ __launch_bounds__(DR_AT) void drnn_gates_attn_lfwd_kernel(GateAttnArgs a) { drnn_gates_attn_fwd_body<2>(a); }
 
 struct AttnBwdDir {
     const float* dCT;    // [B x H]
@@ -520,10 +528,12 @@ __global__ __launch_bounds__(DR_AT) void drnn_attn_bwd_kernel(AttnBwdArgs a) { d
 // First launch of a backward step t: the attention backward of step t + 1 (it completes dG row t + 1 of its dialogue),
 // then the global cell's gate gradient of step t on that row, in the workgroup that owns the dialogue; the party cell's
 // gate gradient (independent of both) in blocks [0, party_blocks).
+// (PARTY = 2: the listener path's party gate — dh = d qs assembled by drnn_listener_bwd_kernel, dh2 = d ss)
 struct GateAttnBwdArgs { GateBwdArgs g, p; AttnBwdArgs at; int party_blocks, has_attn; };
-__global__ __launch_bounds__(DR_AT) void drnn_gates_attn_bwd_kernel(GateAttnBwdArgs a) {
+template <int PARTY>
+__device__ __forceinline__ void drnn_gates_attn_bwd_body(const GateAttnBwdArgs& a) {
     if ((int)blockIdx.x < a.party_blocks) {
-        gru_gate_bwd_body<1>(a.p, a.p.d[blockIdx.z], blockIdx.x * DR_AT + threadIdx.x);
+        gru_gate_bwd_body<PARTY>(a.p, a.p.d[blockIdx.z], blockIdx.x * DR_AT + threadIdx.x);
         return;
     }
     const int b = blockIdx.x - a.party_blocks;
@@ -533,6 +543,119 @@ __global__ __launch_bounds__(DR_AT) void drnn_gates_attn_bwd_kernel(GateAttnBwdA
         __syncthreads();
     }
     if ((int)threadIdx.x < a.g.H) gru_gate_bwd_body<0>(a.g, a.g.d[blockIdx.z], b * a.g.H + threadIdx.x);
+}
+__global__ __launch_bounds__(DR_AT) void drnn_gates_attn_bwd_kernel(GateAttnBwdArgs a) { drnn_gates_attn_bwd_body<1>(a); }
+__global__ __launch_bounds__(DR_AT) void drnn_gates_attn_lbwd_kernel(GateAttnBwdArgs a) { drnn_gates_attn_bwd_body<2>(a); }
+
+// ------------------------------------------------------------------------------------------
+// Listener state (listener_state = True, model.py:899-921): every party row also takes a listener GRU step
+//     ql[p] = drop_L(GRU_l([U_t, qs], q_{t-1}[p]))      p = 0, 1; qs = the speaker's new state after its dropout
+//     q_t[p] = (m != 0 && p == spk) ? qs : ql[p]
+// The input side [U_t, qs] is the same for both party rows: its U part is one GEMM over all steps (XL, b_ih included), its
+// qs part one skinny product per step; the hidden side is one skinny product per party row (Q's [B x 2 x H] rows, lda 2H).
+// drnn_listener_fwd_kernel: the listener gates of both party rows + the blend (writes Q[t+1], QN[t], QS[t+1] — what the
+// party gate writes without the listener).  Dropout site SITE_DRNN_L (+4 per direction), row t*B + b, column p*H + u of
+// a width-2H row.
+// ------------------------------------------------------------------------------------------
+struct LGateDir {
+    const float* GI;          // [B x 3H] input pre-activations, shared by both party rows: XL[t] + QSP[t] W_ih_l[:, Dm:]^T
+    const float* GH;          // [B x 2 x 3H] hidden pre-activations per party row (b_hh included)
+    const float* Qprev;       // [B x 2 x H] Q[t]
+    const float* QSP;         // [B x H] qs of this step (after its dropout)
+    float* R; float* Z; float* N; float* HN;      // [B x 2 x H] saved listener gates of this step
+    const int* spk; const int* spk_next;          // spk_next NULL on the last step
+    const float* mval;
+    float* Qnext; float* QN; float* QSnext;       // as GateDir
+    uint32_t site;
+};
+struct LGateArgs {
+    LGateDir d[2];
+    int B, H, row0;
+    float p; int train;
+    const uint64_t* rng; uint64_t add;
+};
+__global__ __launch_bounds__(256) void drnn_listener_fwd_kernel(LGateArgs a) {
+    const LGateDir& d = a.d[blockIdx.z];
+    const int idx = blockIdx.x * 256 + threadIdx.x, H = a.H, H2 = 2 * a.H;
+    if (idx >= a.B * H2) return;
+    const int b = idx / H2, j = idx - b * H2, pa = j >= H ? 1 : 0, u = j - pa * H;
+    const float* gi = d.GI + (size_t)b * 3 * H;
+    const float* gh = d.GH + ((size_t)b * 2 + pa) * 3 * H;
+    const float h = d.Qprev[idx];
+    const float r = sigm(gi[u] + gh[u]);
+    const float z = sigm(gi[H + u] + gh[H + u]);
+    const float hn = gh[2 * H + u];
+    const float n = tanhf(gi[2 * H + u] + r * hn);
+    float hnew = (1.0f - z) * n + z * h;
+    d.R[idx] = r; d.Z[idx] = z; d.N[idx] = n; d.HN[idx] = hn;
+    const DropCtx dc = make_drop(a.rng, a.add, d.site, a.p, a.train);
+    hnew *= drop_mult1(dc, (uint32_t)(a.row0 + b), (uint32_t)H2, (uint32_t)j);
+    const int s = d.spk[b];
+    const float q = (d.mval[b] != 0.f && pa == s) ? d.QSP[(size_t)b * H + u] : hnew;
+    d.Qnext[idx] = q;
+    if (pa == s) d.QN[(size_t)b * H + u] = q;
+    if (d.spk_next && pa == d.spk_next[b]) d.QSnext[(size_t)b * H + u] = q;
+}
+
+// Backward of the listener and the blend at step t, one thread per (dialogue, column) covering both party rows (so the
+// party sum of the input-side gate gradient is formed in a fixed order, without atomics).  Gradient wrt Q[t+1][p]:
+//     dq[p] = dQl[p] + (p == spk_{t+1} ? dQSp + dQSg : 0) + (p == spk_t ? dQN[t] : 0)
+// (dQl = dGH_l[p] W_hh_l + dh' z of step t+1: the listener's hidden path; dQSp / dQSg: QS[t+1] = Q[t+1][spk_{t+1}] as the
+// party cell's hidden state and the global cell's input of step t+1; dQN: QN[t] = Q[t+1][spk_t] into the emotion cell).
+// The row the blend took from qs passes dq to d qs and its listener gets zero.
+struct LGateBwdDir {
+    const float* dQl;         // [B x 2 x H] NULL on the last step
+    const float* dQSp; const float* dQSg; const int* spk_next;
+    const float* dQN;         // [B x H]
+    const int* spk; const float* mval;
+    const float* R; const float* Z; const float* N; const float* HN;   // [B x 2 x H]
+    const float* Qprev;       // [B x 2 x H] Q[t]
+    float* dGI;               // [B x 3H] input-side gate gradient, summed over the two party rows
+    float* dGH;               // [B x 2 x 3H]
+    float* dhdir;             // [B x 2 x H] direct path to Q[t]: dh' z
+    float* dqs;               // [B x H] gradient wrt qs through the blend
+    uint32_t site;
+};
+struct LGateBwdArgs {
+    LGateBwdDir d[2];
+    int B, H, row0;
+    float p; int train;
+    const uint64_t* rng; uint64_t add;
+};
+__global__ __launch_bounds__(256) void drnn_listener_bwd_kernel(LGateBwdArgs a) {
+    const LGateBwdDir& d = a.d[blockIdx.z];
+    const int idx = blockIdx.x * 256 + threadIdx.x, H = a.H, H3 = 3 * a.H;
+    if (idx >= a.B * H) return;
+    const int b = idx / H, u = idx - b * H;
+    const int s = d.spk[b], sn = d.dQl ? d.spk_next[b] : -1;
+    const bool took_qs = d.mval[b] != 0.f;
+    const DropCtx dc = make_drop(a.rng, a.add, d.site, a.p, a.train);
+    float sr = 0.f, sz = 0.f, sn_ = 0.f, dqs = 0.f;
+#pragma unroll
+    for (int pa = 0; pa < 2; ++pa) {
+        const size_t o = ((size_t)b * 2 + pa) * H + u;
+        float dq = 0.f;
+        if (d.dQl) {
+            dq = d.dQl[o];
+            if (pa == sn) dq += d.dQSp[idx] + d.dQSg[idx];
+        }
+        if (pa == s) dq += d.dQN[idx];
+        if (took_qs && pa == s) { dqs = dq; dq = 0.f; }
+        const float dhn = dq * drop_mult1(dc, (uint32_t)(a.row0 + b), (uint32_t)(2 * H), (uint32_t)(pa * H + u));
+        const float r = d.R[o], z = d.Z[o], n = d.N[o], hn = d.HN[o], h = d.Qprev[o];
+        const float dn = dhn * (1.0f - z);
+        const float dz = dhn * (h - n);
+        const float dnp = dn * (1.0f - n * n);
+        const float drp = dnp * hn * r * (1.0f - r);
+        const float dzp = dz * z * (1.0f - z);
+        float* gh = d.dGH + ((size_t)b * 2 + pa) * H3;
+        gh[u] = drp; gh[H + u] = dzp; gh[2 * H + u] = dnp * r;
+        sr += drp; sz += dzp; sn_ += dnp;
+        d.dhdir[o] = dhn * z;
+    }
+    float* gi = d.dGI + (size_t)b * H3;
+    gi[u] = sr; gi[H + u] = sz; gi[2 * H + u] = sn_;
+    d.dqs[idx] = dqs;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -739,6 +862,32 @@ static DrnnWs drnn_ws(const ganffn_drnn_cfg* c) {
     return w;
 }
 
+// listener path: extra regions behind the listener-free ones (whose offsets do not move)
+struct DrnnLSaved { int64_t XL, QSP, Rl, Zl, Nl, HNl, total; };
+static DrnnLSaved drnn_lsaved(const ganffn_drnn_cfg* c) {
+    DrnnLSaved s;
+    const int64_t T = (int64_t)c->S * c->B, H = c->H;
+    int64_t p = drnn_saved(c).total;
+    auto take = [&](int64_t n) { int64_t r = p; p += (n + 3) & ~int64_t(3); return r; };
+    s.XL = take(T * 3 * H); s.QSP = take(T * H);
+    s.Rl = take(T * 2 * H); s.Zl = take(T * 2 * H); s.Nl = take(T * 2 * H); s.HNl = take(T * 2 * H);
+    s.total = p;
+    return s;
+}
+struct DrnnLWs { int64_t GIl, GHl, dGIl, dGHl, dss, dqs, dQl, dhdirl, WTl, total; };
+static DrnnLWs drnn_lws(const ganffn_drnn_cfg* c) {
+    DrnnLWs w;
+    const int64_t T = (int64_t)c->S * c->B, B = c->B, H = c->H;
+    int64_t p = drnn_ws(c).total;
+    auto take = [&](int64_t n) { int64_t r = p; p += (n + 3) & ~int64_t(3); return r; };
+    w.GIl = take(B * 3 * H); w.GHl = take(B * 2 * 3 * H);
+    w.dGIl = take(T * 3 * H); w.dGHl = take(T * 2 * 3 * H);
+    w.dss = take(B * H); w.dqs = take(B * H); w.dQl = take(B * 2 * H); w.dhdirl = take(B * 2 * H);
+    w.WTl = take(2 * H * 3 * H);                             // transposed l_wih[:, Dm:], l_whh (backward)
+    w.total = p;
+    return w;
+}
+
 static int check_drnn(const ganffn_drnn_cfg* c, int ndir) {
     GF_CHECK_ARG(c, "null drnn cfg");
     GF_CHECK_ARG(ndir == 1 || ndir == 2, "drnn: ndir=%d", ndir);
@@ -772,14 +921,17 @@ extern "C" int ganffn_drnn_skinny(int nn, int copies, const float* A, const floa
 
 extern "C" int64_t ganffn_drnn_saved_floats(const ganffn_drnn_cfg* c) { return check_drnn(c, 1) ? -1 : drnn_saved(c).total; }
 extern "C" int64_t ganffn_drnn_workspace_floats(const ganffn_drnn_cfg* c) { return check_drnn(c, 1) ? -1 : drnn_ws(c).total; }
+extern "C" int64_t ganffn_drnn_listener_saved_floats(const ganffn_drnn_cfg* c) { return check_drnn(c, 1) ? -1 : drnn_lsaved(c).total; }
+extern "C" int64_t ganffn_drnn_listener_workspace_floats(const ganffn_drnn_cfg* c) { return check_drnn(c, 1) ? -1 : drnn_lws(c).total; }
 
 // ------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------
-extern "C" int ganffn_drnn_fwd(const ganffn_drnn_cfg* c, int ndir, const float* const* U, const int32_t* const* spk,
-                               const float* const* mval, const ganffn_drnn_params* prm, float* const* e_out,
-                               float* const* alpha, float* const* saved, float* const* workspace, const uint64_t* rng,
-                               uint64_t add, void* stream) {
+// lp == NULL: listener_state False (ganffn_drnn_fwd); otherwise the listener path (ganffn_drnn_listener_fwd)
+static int drnn_fwd(const ganffn_drnn_cfg* c, int ndir, const float* const* U, const int32_t* const* spk,
+                    const float* const* mval, const ganffn_drnn_params* prm, const ganffn_drnn_listener_params* lp,
+                    float* const* e_out, float* const* alpha, float* const* saved, float* const* workspace,
+                    const uint64_t* rng, uint64_t add, void* stream) {
     GF_TRY(check_drnn(c, ndir));
     GF_CHECK_ARG(U && spk && mval && prm && e_out && alpha && saved && workspace, "drnn_fwd: null pointer");
     GF_CHECK_ARG(!(c->train && c->p > 0.f) || rng, "drnn_fwd: rng required in train mode");
@@ -787,6 +939,11 @@ extern "C" int ganffn_drnn_fwd(const ganffn_drnn_cfg* c, int ndir, const float* 
     const int S = c->S, B = c->B, Dm = c->Dm, H = c->H, He = c->He, T = S * B;
     const DrnnSaved so = drnn_saved(c);
     const DrnnWs wo = drnn_ws(c);
+    const DrnnLSaved sl = drnn_lsaved(c);
+    const DrnnLWs wl = drnn_lws(c);
+    if (lp)
+        for (int z = 0; z < ndir; ++z)
+            GF_CHECK_ARG(lp[z].l_wih && lp[z].l_whh && lp[z].l_bih && lp[z].l_bhh, "drnn_listener_fwd: direction %d: null listener parameter", z);
     for (int z = 0; z < ndir; ++z) {
         GF_CHECK_ARG(U[z] && spk[z] && mval[z] && e_out[z] && alpha[z] && saved[z] && workspace[z] && aligned16(U[z]) &&
                      aligned16(saved[z]) && aligned16(workspace[z]), "drnn_fwd: direction %d: null or misaligned buffer", z);
@@ -799,6 +956,11 @@ extern "C" int ganffn_drnn_fwd(const ganffn_drnn_cfg* c, int ndir, const float* 
         GF_TRY(launch_gemm_nt(U[z], Dm, prm[z].p_wih, Dm + H, sv + so.XP, 3 * H, T, 3 * H, Dm, EPI_NONE, e, st));
         e.bias = nullptr;
         GF_TRY(launch_gemm_nt(U[z], Dm, prm[z].att_w, Dm, sv + so.XA, H, T, H, Dm, EPI_NONE, e, st));
+        if (lp) {      // listener: XL = U Wih_l[:, :Dm]^T + bih_l
+            e.bias = lp[z].l_bih;
+            GF_TRY(launch_gemm_nt(U[z], Dm, lp[z].l_wih, Dm + H, sv + sl.XL, 3 * H, T, 3 * H, Dm, EPI_NONE, e, st));
+            e.bias = nullptr;
+        }
         // zero initial states: G[0], Q[0], E[0], QS[0], CT[0]; alpha (entries j >= t stay zero)
         GF_TRY(memset_f(sv + so.G, (int64_t)B * H, st));
         GF_TRY(memset_f(sv + so.Q, (int64_t)B * 2 * H, st));
@@ -837,6 +999,7 @@ extern "C" int ganffn_drnn_fwd(const ganffn_drnn_cfg* c, int ndir, const float* 
                               sv + so.HNp + r0 * H, nullptr, spk[z] + r0, t + 1 < S ? spk[z] + r1 : nullptr, mval[z] + r0,
                               sv + so.Q + r0 * 2 * H, sv + so.Q + r1 * 2 * H, sv + so.QN + r0 * H, sv + so.QS + r1 * H,
                               SITE_DRNN_P + 4u * z};
+            if (lp) gp.d[z].QN = sv + sl.QSP + r0 * H;       // qs only; the listener kernel below writes Q / QN / QS
         }
         GateAttnArgs gaa;
         gaa.g = ga; gaa.p = gp;
@@ -845,8 +1008,34 @@ extern "C" int ganffn_drnn_fwd(const ganffn_drnn_cfg* c, int ndir, const float* 
         gaa.at.B = B; gaa.at.H = H; gaa.at.S = S; gaa.at.t = t + 1;
         for (int z = 0; z < ndir; ++z)
             gaa.at.d[z] = AttnDir{saved[z] + so.XA + r1 * H, saved[z] + so.G, saved[z] + so.CT + r1 * H, alpha[z]};
-        hipLaunchKernelGGL(drnn_gates_attn_fwd_kernel, dim3(gaa.party_blocks + B, 1, ndir), dim3(DR_AT), 0, st, gaa);
-        GF_LAUNCH_CHECK();
+        if (!lp) {
+            hipLaunchKernelGGL(drnn_gates_attn_fwd_kernel, dim3(gaa.party_blocks + B, 1, ndir), dim3(DR_AT), 0, st, gaa);
+            GF_LAUNCH_CHECK();
+        } else {
+            hipLaunchKernelGGL(drnn_gates_attn_lfwd_kernel, dim3(gaa.party_blocks + B, 1, ndir), dim3(DR_AT), 0, st, gaa);
+            GF_LAUNCH_CHECK();
+            // ---- listener: GI_l = XL[t] + QSP[t] Wih_l[:, Dm:]^T ; GH_l[p] = Q[t][p] Whh_l^T + bhh_l (p = 0, 1)
+            for (int z = 0; z < ndir; ++z) {
+                float* sv = saved[z]; float* ws = workspace[z];
+                sg.p[3 * z] = SkinnyProb{sv + sl.QSP + r0 * H, H, lp[z].l_wih + Dm, Dm + H, sv + sl.XL + r0 * 3 * H, 3 * H, nullptr, nullptr,
+                                         ws + wl.GIl, 3 * H, B, 3 * H, H};
+                for (int pa = 0; pa < 2; ++pa)
+                    sg.p[3 * z + 1 + pa] = SkinnyProb{sv + so.Q + r0 * 2 * H + pa * H, 2 * H, lp[z].l_whh, H, nullptr, 0, nullptr, lp[z].l_bhh,
+                                                      ws + wl.GHl + pa * 3 * H, 6 * H, B, 3 * H, H};
+            }
+            GF_TRY(launch_skinny(sg, 3 * ndir, false, st));
+            LGateArgs la;
+            la.B = B; la.H = H; la.row0 = (int)r0; la.p = c->p; la.train = c->train; la.rng = rng; la.add = add;
+            for (int z = 0; z < ndir; ++z) {
+                float* sv = saved[z]; float* ws = workspace[z];
+                la.d[z] = LGateDir{ws + wl.GIl, ws + wl.GHl, sv + so.Q + r0 * 2 * H, sv + sl.QSP + r0 * H, sv + sl.Rl + r0 * 2 * H,
+                                   sv + sl.Zl + r0 * 2 * H, sv + sl.Nl + r0 * 2 * H, sv + sl.HNl + r0 * 2 * H, spk[z] + r0,
+                                   t + 1 < S ? spk[z] + r1 : nullptr, mval[z] + r0, sv + so.Q + r1 * 2 * H, sv + so.QN + r0 * H,
+                                   sv + so.QS + r1 * H, SITE_DRNN_L + 4u * z};
+            }
+            hipLaunchKernelGGL(drnn_listener_fwd_kernel, dim3((B * 2 * H + 255) / 256, 1, ndir), dim3(256), 0, st, la);
+            GF_LAUNCH_CHECK();
+        }
         if (echain) continue;
         // ---- emotion cell: GI = QN[t] Wih_e^T + bih_e ; GH = E[t] Whh_e^T + bhh_e
         for (int z = 0; z < ndir; ++z) {
@@ -886,14 +1075,30 @@ extern "C" int ganffn_drnn_fwd(const ganffn_drnn_cfg* c, int ndir, const float* 
     return 0;
 }
 
+extern "C" int ganffn_drnn_fwd(const ganffn_drnn_cfg* c, int ndir, const float* const* U, const int32_t* const* spk,
+                               const float* const* mval, const ganffn_drnn_params* prm, float* const* e_out,
+                               float* const* alpha, float* const* saved, float* const* workspace, const uint64_t* rng,
+                               uint64_t add, void* stream) {
+    return drnn_fwd(c, ndir, U, spk, mval, prm, nullptr, e_out, alpha, saved, workspace, rng, add, stream);
+}
+extern "C" int ganffn_drnn_listener_fwd(const ganffn_drnn_cfg* c, int ndir, const float* const* U, const int32_t* const* spk,
+                                        const float* const* mval, const ganffn_drnn_params* prm,
+                                        const ganffn_drnn_listener_params* lprm, float* const* e_out, float* const* alpha,
+                                        float* const* saved, float* const* workspace, const uint64_t* rng, uint64_t add,
+                                        void* stream) {
+    GF_CHECK_ARG(lprm, "drnn_listener_fwd: null listener parameters");
+    return drnn_fwd(c, ndir, U, spk, mval, prm, lprm, e_out, alpha, saved, workspace, rng, add, stream);
+}
+
 // ------------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------------
-extern "C" int ganffn_drnn_bwd(const ganffn_drnn_cfg* c, int ndir, const float* const* d_e, const float* const* U,
-                               const int32_t* const* spk, const float* const* mval, const ganffn_drnn_params* prm,
-                               const ganffn_drnn_grads* grd, float* const* dU, const float* const* alpha,
-                               const float* const* saved, float* const* workspace, const uint64_t* rng, uint64_t add,
-                               void* stream) {
+// lp == NULL: listener_state False (ganffn_drnn_bwd); otherwise the listener path (ganffn_drnn_listener_bwd, lg may be NULL)
+static int drnn_bwd(const ganffn_drnn_cfg* c, int ndir, const float* const* d_e, const float* const* U,
+                    const int32_t* const* spk, const float* const* mval, const ganffn_drnn_params* prm,
+                    const ganffn_drnn_listener_params* lp, const ganffn_drnn_grads* grd, const ganffn_drnn_listener_grads* lg,
+                    float* const* dU, const float* const* alpha, const float* const* saved, float* const* workspace,
+                    const uint64_t* rng, uint64_t add, void* stream) {
     GF_TRY(check_drnn(c, ndir));
     GF_CHECK_ARG(d_e && U && spk && mval && prm && grd && dU && alpha && saved && workspace, "drnn_bwd: null pointer");
     GF_CHECK_ARG(!(c->train && c->p > 0.f) || rng, "drnn_bwd: rng required in train mode");
@@ -901,6 +1106,11 @@ extern "C" int ganffn_drnn_bwd(const ganffn_drnn_cfg* c, int ndir, const float* 
     const int S = c->S, B = c->B, Dm = c->Dm, H = c->H, He = c->He, T = S * B;
     const DrnnSaved so = drnn_saved(c);
     const DrnnWs wo = drnn_ws(c);
+    const DrnnLSaved sl = drnn_lsaved(c);
+    const DrnnLWs wl = drnn_lws(c);
+    if (lp)
+        for (int z = 0; z < ndir; ++z)
+            GF_CHECK_ARG(lp[z].l_wih && lp[z].l_whh && lp[z].l_bih && lp[z].l_bhh, "drnn_listener_bwd: direction %d: null listener parameter", z);
     for (int z = 0; z < ndir; ++z) {
         GF_CHECK_ARG(d_e[z] && U[z] && dU[z] && saved[z] && workspace[z] && alpha[z], "drnn_bwd: direction %d: null buffer", z);
         float* ws = workspace[z];
@@ -924,6 +1134,15 @@ extern "C" int ganffn_drnn_bwd(const ganffn_drnn_cfg* c, int ndir, const float* 
         }
         hipLaunchKernelGGL(drnn_transpose_kernel, dim3((H + 31) / 32, (3 * H + 31) / 32, 4 * ndir), dim3(256), 0, st, tr);
         GF_LAUNCH_CHECK();
+        if (lp) {      // listener: l_wih[:, Dm:], l_whh
+            for (int z = 0; z < ndir; ++z) {
+                float* wt = workspace[z] + wl.WTl;
+                tr.in[2 * z] = lp[z].l_wih + Dm; tr.ld_in[2 * z] = Dm + H; tr.out[2 * z] = wt;
+                tr.in[2 * z + 1] = lp[z].l_whh; tr.ld_in[2 * z + 1] = H; tr.out[2 * z + 1] = wt + (int64_t)H * 3 * H;
+            }
+            hipLaunchKernelGGL(drnn_transpose_kernel, dim3((H + 31) / 32, (3 * H + 31) / 32, 2 * ndir), dim3(256), 0, st, tr);
+            GF_LAUNCH_CHECK();
+        }
     }
     if (echain) {
         // emotion chain first (it depends on nothing else): gate gradients of all steps, then dQN of all steps in one GEMM
@@ -973,6 +1192,32 @@ extern "C" int ganffn_drnn_bwd(const ganffn_drnn_cfg* c, int ndir, const float* 
         // inside the kernel).  Global cell: dg_t = dG[t+1] — the attention uses of g_t at later steps and the recurrent path
         // were all added by the steps already done.
         gb.H = H;
+        if (lp) {
+            // ---- listener + blend backward: dGI_l (party sum), dGH_l, dh' z of both party rows, d qs through the blend
+            LGateBwdArgs lb;
+            lb.B = B; lb.H = H; lb.row0 = (int)r0; lb.p = c->p; lb.train = c->train; lb.rng = rng; lb.add = add;
+            for (int z = 0; z < ndir; ++z) {
+                const float* sv = saved[z]; float* ws = workspace[z];
+                const bool last = t == S - 1;
+                lb.d[z] = LGateBwdDir{last ? nullptr : ws + wl.dQl, ws + wo.dQSp, ws + wo.dQSg, last ? nullptr : spk[z] + r1,
+                                      echain ? ws + wo.dQNall + r0 * H : ws + wo.dQN, spk[z] + r0, mval[z] + r0,
+                                      sv + sl.Rl + r0 * 2 * H, sv + sl.Zl + r0 * 2 * H, sv + sl.Nl + r0 * 2 * H, sv + sl.HNl + r0 * 2 * H,
+                                      sv + so.Q + r0 * 2 * H, ws + wl.dGIl + r0 * 3 * H, ws + wl.dGHl + r0 * 6 * H, ws + wl.dhdirl,
+                                      ws + wl.dqs, SITE_DRNN_L + 4u * z};
+            }
+            hipLaunchKernelGGL(drnn_listener_bwd_kernel, dim3((B * H + 255) / 256, 1, ndir), dim3(256), 0, st, lb);
+            GF_LAUNCH_CHECK();
+            // ---- d ss = dGI_l Wih_l[:, Dm:] ; dQl[p] = dGH_l[p] Whh_l + dh' z (gradient wrt Q[t] through the listener)
+            for (int z = 0; z < ndir; ++z) {
+                float* ws = workspace[z];
+                const float* wt = ws + wl.WTl;
+                sg.p[3 * z] = SkinnyProb{ws + wl.dGIl + r0 * 3 * H, 3 * H, wt, 3 * H, nullptr, 0, nullptr, nullptr, ws + wl.dss, H, B, H, 3 * H};
+                for (int pa = 0; pa < 2; ++pa)
+                    sg.p[3 * z + 1 + pa] = SkinnyProb{ws + wl.dGHl + r0 * 6 * H + pa * 3 * H, 6 * H, wt + (int64_t)H * 3 * H, 3 * H,
+                                                      ws + wl.dhdirl + pa * H, 2 * H, nullptr, nullptr, ws + wl.dQl + pa * H, 2 * H, B, H, 3 * H};
+            }
+            GF_TRY(launch_skinny(sg, 3 * ndir, false, st));
+        }
         GateBwdArgs gg = gb;
         for (int z = 0; z < ndir; ++z) {
             const float* sv = saved[z]; float* ws = workspace[z];
@@ -984,6 +1229,10 @@ extern "C" int ganffn_drnn_bwd(const ganffn_drnn_cfg* c, int ndir, const float* 
                 gb.d[z].pg_dQ = ws + (even1 ? wo.dQa : wo.dQb);
                 gb.d[z].pg_out = ws + dQin;
                 gb.d[z].pg_dQSp = ws + wo.dQSp; gb.d[z].pg_dQSg = ws + wo.dQSg; gb.d[z].pg_spk = spk[z] + r1;
+            }
+            if (lp) {             // listener: the party cell's output qs gets d qs (blend) + d ss (listener input); no pass-through
+                gb.d[z].dh = ws + wl.dqs; gb.d[z].dh2 = ws + wl.dss;
+                gb.d[z].pg_out = nullptr;
             }
             gg.d[z] = GateBwdDir{ws + wo.dG + r1 * H, nullptr, sv + so.Rg + r0 * H, sv + so.Zg + r0 * H, sv + so.Ng + r0 * H, sv + so.HNg + r0 * H,
                                  sv + so.G + r0 * H, ws + wo.dGIg + r0 * 3 * H, ws + wo.dGHg + r0 * 3 * H, ws + wo.dhdirG, nullptr,
@@ -997,7 +1246,8 @@ extern "C" int ganffn_drnn_bwd(const ganffn_drnn_cfg* c, int ndir, const float* 
         for (int z = 0; z < ndir; ++z)
             gab.at.d[z] = AttnBwdDir{workspace[z] + wo.dCT, saved[z] + so.XA + r1 * H, saved[z] + so.G, alpha[z], workspace[z] + wo.dG,
                                      workspace[z] + wo.dXA + r1 * H};
-        hipLaunchKernelGGL(drnn_gates_attn_bwd_kernel, dim3(gab.party_blocks + B, 1, ndir), dim3(DR_AT), 0, st, gab);
+        if (!lp) hipLaunchKernelGGL(drnn_gates_attn_bwd_kernel, dim3(gab.party_blocks + B, 1, ndir), dim3(DR_AT), 0, st, gab);
+        else hipLaunchKernelGGL(drnn_gates_attn_lbwd_kernel, dim3(gab.party_blocks + B, 1, ndir), dim3(DR_AT), 0, st, gab);
         GF_LAUNCH_CHECK();
         // ---- the four dgrad products of the step in one launch
         for (int z = 0; z < ndir; ++z) {
@@ -1023,6 +1273,7 @@ extern "C" int ganffn_drnn_bwd(const ganffn_drnn_cfg* c, int ndir, const float* 
         e1.aux_in = dU[z];
         GF_TRY(launch_gemm_nn(ws + wo.dGIp, 3 * H, prm[z].p_wih, Dm + H, dU[z], Dm, T, Dm, 3 * H, EPI_NONE, e1, st));
         GF_TRY(launch_gemm_nn(ws + wo.dXA, H, prm[z].att_w, Dm, dU[z], Dm, T, Dm, H, EPI_NONE, e1, st));
+        if (lp) GF_TRY(launch_gemm_nn(ws + wl.dGIl, 3 * H, lp[z].l_wih, Dm + H, dU[z], Dm, T, Dm, 3 * H, EPI_NONE, e1, st));
         if (g.g_wih) {
             TnDesc tn[12];
             int n = 0;
@@ -1035,8 +1286,32 @@ extern "C" int ganffn_drnn_bwd(const ganffn_drnn_cfg* c, int ndir, const float* 
             tn[n++] = TnDesc{ws + wo.dGIe, 3 * He, sv + so.QN, H, g.e_wih, H, g.e_bih, 3 * He, H, T};
             tn[n++] = TnDesc{ws + wo.dGHe, 3 * He, sv + so.E, He, g.e_whh, He, g.e_bhh, 3 * He, He, T};
             tn[n++] = TnDesc{ws + wo.dXA, H, U[z], Dm, g.att_w, Dm, nullptr, H, Dm, T};
+            if (lp && lg && lg[z].l_wih) {
+                // listener: input side against [U, qs] (party-summed dGI_l), hidden side against Q[t][p] (2T rows)
+                const ganffn_drnn_listener_grads& l = lg[z];
+                tn[n++] = TnDesc{ws + wl.dGIl, 3 * H, U[z], Dm, l.l_wih, Dm + H, l.l_bih, 3 * H, Dm, T};
+                tn[n++] = TnDesc{ws + wl.dGIl, 3 * H, sv + sl.QSP, H, l.l_wih + Dm, Dm + H, nullptr, 3 * H, H, T};
+                tn[n++] = TnDesc{ws + wl.dGHl, 3 * H, sv + so.Q, H, l.l_whh, H, l.l_bhh, 3 * H, H, 2 * T};
+            }
             GF_TRY(launch_gemm_tn_grouped(tn, n, st));
         }
     }
     return 0;
+}
+
+extern "C" int ganffn_drnn_bwd(const ganffn_drnn_cfg* c, int ndir, const float* const* d_e, const float* const* U,
+                               const int32_t* const* spk, const float* const* mval, const ganffn_drnn_params* prm,
+                               const ganffn_drnn_grads* grd, float* const* dU, const float* const* alpha,
+                               const float* const* saved, float* const* workspace, const uint64_t* rng, uint64_t add,
+                               void* stream) {
+    return drnn_bwd(c, ndir, d_e, U, spk, mval, prm, nullptr, grd, nullptr, dU, alpha, saved, workspace, rng, add, stream);
+}
+extern "C" int ganffn_drnn_listener_bwd(const ganffn_drnn_cfg* c, int ndir, const float* const* d_e, const float* const* U,
+                                        const int32_t* const* spk, const float* const* mval, const ganffn_drnn_params* prm,
+                                        const ganffn_drnn_listener_params* lprm, const ganffn_drnn_grads* grd,
+                                        const ganffn_drnn_listener_grads* lgrd, float* const* dU, const float* const* alpha,
+                                        const float* const* saved, float* const* workspace, const uint64_t* rng, uint64_t add,
+                                        void* stream) {
+    GF_CHECK_ARG(lprm, "drnn_listener_bwd: null listener parameters");
+    return drnn_bwd(c, ndir, d_e, U, spk, mval, prm, lprm, grd, lgrd, dU, alpha, saved, workspace, rng, add, stream);
 }

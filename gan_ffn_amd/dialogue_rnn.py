@@ -5,10 +5,11 @@ Mirrors the module interface of /root/reference/model.py:134-194 (MatchingAttent
 (DialogueRNNCell, DialogueRNN, BiModel) and :1465-1528 (GAN_FFN_DialogueRNN): same constructor arguments, same
 parameter names and shapes (reference state_dicts load), same forward signatures and return tuples.
 
-On the GPU, in the configuration the reference script runs (general context attention, no listener), the recurrence is
-the HIP path of csrc/dialogue_rnn.hip (ops.DialogueRNNFn: both directions of BiModel through one chain of launches, forward
-and backward); other configurations (simple attention, listener state) and CPU tensors take the torch-op restatement
-below, which is also what the reference-fixture parity tests pin.  The pieces with no sequential dependence are batched:
+On the GPU, with general or simple context attention, with or without listener state (the reference script's
+--active-listener), the recurrence is the HIP path of csrc/dialogue_rnn.hip (ops.DialogueRNNFn: both directions of BiModel
+through one chain of launches, forward and backward; ops.dialogue_rnn_supported / dialogue_rnn_listener_supported say
+when); the other attention types (dot, general2, concat) and CPU tensors take the torch-op restatement below, which is
+also what the reference-fixture parity tests pin.  The pieces with no sequential dependence are batched:
   * party selection is a gather, sequence reversal one index gather per tensor (the reference loops over dialogues),
   * BiModel's second attention — one masked `general2` MatchingAttention query per time step in the reference — is ONE
     batched masked attention over all (dialogue, query step) pairs (`general2_all_queries`).
@@ -148,7 +149,7 @@ class DialogueRNN(nn.Module):
     def forward(self, U, qmask):
         """U (S, B, D_m), qmask (S, B, P) -> emotions (S, B, D_e), [alpha_t (B, t)] for t >= 1"""
         from . import ops
-        if ops.dialogue_rnn_supported(self.dialogue_cell, U, qmask):
+        if _hip_recurrence(ops, self.dialogue_cell, U, qmask):
             # the HIP recurrence (csrc/dialogue_rnn.hip): the configuration train_IEMOCAP_DialogueRNN.py runs
             return ops.dialogue_rnn_run([self.dialogue_cell], [U], [qmask], self.training)[0]
         S, B, P = qmask.shape
@@ -163,6 +164,13 @@ class DialogueRNN(nn.Module):
             if a_ is not None:
                 alpha.append(a_[:, 0, :])
         return torch.stack(e_steps, 0), alpha
+
+
+def _hip_recurrence(ops, cell, U, qmask):
+    """whether the HIP recurrence runs this cell: the listener-free path or the listener path"""
+    if cell.listener_state:
+        return ops.dialogue_rnn_listener_supported(cell, U, qmask)
+    return ops.dialogue_rnn_supported(cell, U, qmask)
 
 
 def reverse_valid_prefix(X, mask):
@@ -203,7 +211,8 @@ class BiModel(nn.Module):
         from . import ops
         rev_U, rev_qmask = self._reverse_seq(U, umask), self._reverse_seq(qmask, umask)
         cf, cr = self.dialog_rnn_f.dialogue_cell, self.dialog_rnn_r.dialogue_cell
-        if ops.dialogue_rnn_supported(cf, U, qmask) and ops.dialogue_rnn_supported(cr, rev_U, rev_qmask) and rev_U.shape == U.shape:
+        if (cf.listener_state == cr.listener_state and _hip_recurrence(ops, cf, U, qmask) and _hip_recurrence(ops, cr, rev_U, rev_qmask)
+                and rev_U.shape == U.shape):
             # both directions through the same chain of launches (csrc/dialogue_rnn.hip)
             (emotions_f, alpha_f), (emotions_b, alpha_b) = ops.dialogue_rnn_run([cf, cr], [U, rev_U], [qmask, rev_qmask],
                                                                                 self.training)

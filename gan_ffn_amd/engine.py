@@ -1008,8 +1008,9 @@ class DrnnEngine(GanEngine):
     (lr, L2-coupled weight decay; train_IEMOCAP_DialogueRNN.py:746) on flat slabs: one fused launch per generator and one
     for the whole head.  Data-parallel: the generators' gradients go through the bucketed GradReducer (all-reduce of a
     bucket overlaps the rest of that generator's backward, Adam per bucket), the head's slab is one more bucket.
-    Supports the configuration the reference script trains (general context attention, no listener, two parties); the
-    module path (model.GAN_FFN_DialogueRNN.forward under autograd) stays available for everything else."""
+    Supports the configuration the reference script trains (general context attention, two parties), with or without
+    listener state (--active-listener: ganffn_drnn_listener_fwd / _bwd, the 4 l_cell tensors per direction at the end of the
+    head slab); the module path (model.GAN_FFN_DialogueRNN.forward under autograd) stays available for everything else."""
 
     def __init__(self, net, lr=1e-4, weight_decay=1e-5, class_weights=CLASS_WEIGHTS, process_group=None, n_buckets=3,
                  n_streams=1):
@@ -1017,9 +1018,10 @@ class DrnnEngine(GanEngine):
         self.module = net
         bm = net.bi_model
         cf, cr = bm.dialog_rnn_f.dialogue_cell, bm.dialog_rnn_r.dialogue_cell
-        if cf.listener_state or getattr(cf.attention, "att_type", None) != "general" or cf.D_g != cf.D_p or cf.D_g > 512:
-            raise ValueError("DrnnEngine runs the trained configuration only (general context attention, no listener, "
-                             "D_g = D_p <= 512); use the module path for the other variants")
+        if getattr(cf.attention, "att_type", None) != "general" or cf.D_g != cf.D_p or cf.D_g > 512:
+            raise ValueError("DrnnEngine runs general context attention with D_g = D_p <= 512 only (with or without listener "
+                             "state); use the module path for the other variants")
+        self.listener = bool(cf.listener_state)
         gens = {"acoustic": net.acoustic_generator, "visual": net.visual_generator, "text": net.text_generator}
         self.G = {k: NetState(m, lr, (0.9, 0.999), weight_decay) for k, m in gens.items()}
         self.D = {}
@@ -1036,6 +1038,10 @@ class DrnnEngine(GanEngine):
             plist += [sd[k] for k in ops.DRNN_KEYS]
         plist += [bm.matchatt.transform.weight, bm.matchatt.transform.bias, bm.linear.weight, bm.linear.bias,
                   bm.smax_fc.weight, bm.smax_fc.bias]
+        if self.listener:                    # behind the head tensors: the listener-free slab layout does not move
+            for cell in (cf, cr):
+                sd = dict(cell.named_parameters())
+                plist += [sd[k] for k in ops.DRNN_LISTENER_KEYS]
         offs, total = [], 0
         for p_ in plist:
             offs.append(total)
@@ -1084,7 +1090,11 @@ class DrnnEngine(GanEngine):
             self.ws3 = {k: torch.empty(p_.n_ws, **f32) for k, p_ in self.pass_G.items()}     # one workspace per generator stream
             cfgc = _lib.DrnnCfg(cS, cB, self.Dm, self.H, self.He, self.p_rec, 1)
             lib = _lib.load()
-            n_saved, n_ws = int(lib.ganffn_drnn_saved_floats(C.byref(cfgc))), int(lib.ganffn_drnn_workspace_floats(C.byref(cfgc)))
+            if self.listener:
+                n_saved = int(lib.ganffn_drnn_listener_saved_floats(C.byref(cfgc)))
+                n_ws = int(lib.ganffn_drnn_listener_workspace_floats(C.byref(cfgc)))
+            else:
+                n_saved, n_ws = int(lib.ganffn_drnn_saved_floats(C.byref(cfgc))), int(lib.ganffn_drnn_workspace_floats(C.byref(cfgc)))
             if n_saved < 0 or n_ws < 0:
                 _lib.check(-1, "ganffn_drnn_*_floats")
             T, D2, Cn = cS * cB, 2 * self.He, self.n_classes
@@ -1124,6 +1134,15 @@ class DrnnEngine(GanEngine):
                 setattr(s, name, self._hp(13 * z + j, grad).data_ptr())
             out.append(s)
         return (_lib.DrnnPtrs * 2)(*out)
+
+    def _drnn_listener_ptrs(self, grad):
+        out = []
+        for z in range(2):
+            s = _lib.DrnnListenerPtrs()
+            for j, name in enumerate(_lib.DRNN_LISTENER_FIELDS):
+                setattr(s, name, self._hp(32 + 4 * z + j, grad).data_ptr())
+            out.append(s)
+        return (_lib.DrnnListenerPtrs * 2)(*out)
 
     def step(self, batch, train=True):
         """batch: acoustic/visual/text (S,B,.), qmask (S,B,2) one-hot (zero rows on padding), umask (B,S), label (B,S) int64.
@@ -1213,7 +1232,12 @@ class DrnnEngine(GanEngine):
         U_, spk_, mval_ = arr([f["fusion"], f["rev_U"]]), arr([spk_f, spk_b]), arr([mval_f, mval_b])
         e_, al_, sv_, ws_ = arr([f["e_f"], f["e_b"]]), arr([f["alpha_f"], f["alpha_b"]]), arr([f["saved_f"], f["saved_b"]]), arr([f["ws_f"], f["ws_b"]])
         Pp = self._drnn_ptrs(False)
-        _lib.call("ganffn_drnn_fwd", C.byref(cfg), 2, U_, spk_, mval_, Pp, e_, al_, sv_, ws_, P(rng), C.c_uint64(a_rec), st)
+        if self.listener:
+            LPp = self._drnn_listener_ptrs(False)
+            _lib.call("ganffn_drnn_listener_fwd", C.byref(cfg), 2, U_, spk_, mval_, Pp, LPp, e_, al_, sv_, ws_, P(rng),
+                      C.c_uint64(a_rec), st)
+        else:
+            _lib.call("ganffn_drnn_fwd", C.byref(cfg), 2, U_, spk_, mval_, Pp, e_, al_, sv_, ws_, P(rng), C.c_uint64(a_rec), st)
         # ---- head: emotions -> matching attention -> linear/relu/dropout -> classes -> loss
         tr = 1 if train else 0
         _lib.call("ganffn_drnn_join_fwd", P(f["e_f"]), P(f["e_b"]), P(lens), P(f["emotions"]), S, B, He, C.c_float(self.p_join),
@@ -1246,7 +1270,11 @@ class DrnnEngine(GanEngine):
         # ---- the recurrence backward (weight gradients accumulate into the zeroed head slab)
         Gp = self._drnn_ptrs(True)
         de_, dU_ = arr([f["d_e_f"], f["d_e_b"]]), arr([f["dU_f"], f["dU_b"]])
-        _lib.call("ganffn_drnn_bwd", C.byref(cfg), 2, de_, U_, spk_, mval_, Pp, Gp, dU_, al_, sv_, ws_, P(rng), C.c_uint64(a_rec), st)
+        if self.listener:
+            _lib.call("ganffn_drnn_listener_bwd", C.byref(cfg), 2, de_, U_, spk_, mval_, Pp, LPp, Gp, self._drnn_listener_ptrs(True),
+                      dU_, al_, sv_, ws_, P(rng), C.c_uint64(a_rec), st)
+        else:
+            _lib.call("ganffn_drnn_bwd", C.byref(cfg), 2, de_, U_, spk_, mval_, Pp, Gp, dU_, al_, sv_, ws_, P(rng), C.c_uint64(a_rec), st)
         # d fusion = dU_f + reverse(dU_b)
         _lib.call("ganffn_seq_reverse", P(f["dU_b"]), P(lens), P(f["dU_f"]), S, B, Dm, 1, st)
         d_fusion = f["dU_f"][:T * Dm].view(S, B, Dm)

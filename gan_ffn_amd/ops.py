@@ -463,39 +463,49 @@ class General2AttnFn(torch.autograd.Function):
 DRNN_KEYS = ["g_cell.weight_ih", "g_cell.weight_hh", "g_cell.bias_ih", "g_cell.bias_hh",
              "p_cell.weight_ih", "p_cell.weight_hh", "p_cell.bias_ih", "p_cell.bias_hh",
              "e_cell.weight_ih", "e_cell.weight_hh", "e_cell.bias_ih", "e_cell.bias_hh", "attention.transform.weight"]
+DRNN_LISTENER_KEYS = ["l_cell.weight_ih", "l_cell.weight_hh", "l_cell.bias_ih", "l_cell.bias_hh"]
 
 
 def _ptr_array(tensors):
     return (C.c_void_p * len(tensors))(*[t.data_ptr() if t is not None else None for t in tensors])
 
 
-def _drnn_ptrs(tensors):
-    s = _lib.DrnnPtrs()
-    for name, t in zip(_lib.DRNN_PARAM_FIELDS, tensors):
+def _drnn_ptrs(tensors, cls=_lib.DrnnPtrs):
+    s = cls()
+    for (name, _), t in zip(cls._fields_, tensors):
         setattr(s, name, t.data_ptr() if t is not None else None)
     return s
 
 
 class DialogueRNNFn(torch.autograd.Function):
-    """ndir (1 or 2) DialogueRNNs (general attention, no listener) through one chain of launches.
+    """ndir (1 or 2) DialogueRNNs (general attention) through one chain of launches.
     apply(cfg_dict, U_0, spk_0, mval_0, *13 params_0 [, U_1, spk_1, mval_1, *13 params_1]) ->
-    (e_0 (S,B,D_e), alpha_0 (B,S,S) [, e_1, alpha_1]).  alpha is an inspection output (non-differentiable)."""
+    (e_0 (S,B,D_e), alpha_0 (B,S,S) [, e_1, alpha_1]).  alpha is an inspection output (non-differentiable).
+    cfg_dict["listener"] true: listener_state = True (ganffn_drnn_listener_*); every direction then takes 17 parameter tensors,
+    the 13 above followed by l_cell's weight_ih, weight_hh, bias_ih, bias_hh (DRNN_LISTENER_KEYS)."""
 
     @staticmethod
     def forward(ctx, meta, *args):
-        ndir = len(args) // 16
-        assert len(args) == 16 * ndir and ndir in (1, 2)
-        U = [_f32c(args[16 * z]) for z in range(ndir)]
-        spk = [args[16 * z + 1].to(torch.int32).contiguous() for z in range(ndir)]
-        mval = [_f32c(args[16 * z + 2]) for z in range(ndir)]
-        prm = [[_f32c(p) for p in args[16 * z + 3:16 * z + 16]] for z in range(ndir)]
+        listener = bool(meta.get("listener", False))
+        na = 20 if listener else 16
+        ndir = len(args) // na
+        assert len(args) == na * ndir and ndir in (1, 2)
+        U = [_f32c(args[na * z]) for z in range(ndir)]
+        spk = [args[na * z + 1].to(torch.int32).contiguous() for z in range(ndir)]
+        mval = [_f32c(args[na * z + 2]) for z in range(ndir)]
+        prm = [[_f32c(p) for p in args[na * z + 3:na * z + 16]] for z in range(ndir)]
+        lprm = [[_f32c(p) for p in args[na * z + 16:na * z + 20]] for z in range(ndir)] if listener else None
         _need_gpu(*U)
         S, B, Dm = U[0].shape
         H, He = prm[0][1].shape[1], prm[0][9].shape[1]
         train = bool(meta["train"]) and meta["p"] > 0.0
         cfg = _lib.DrnnCfg(S, B, Dm, H, He, float(meta["p"]), 1 if train else 0)
         lib = _lib.load()
-        n_saved, n_ws = int(lib.ganffn_drnn_saved_floats(C.byref(cfg))), int(lib.ganffn_drnn_workspace_floats(C.byref(cfg)))
+        if listener:
+            n_saved = int(lib.ganffn_drnn_listener_saved_floats(C.byref(cfg)))
+            n_ws = int(lib.ganffn_drnn_listener_workspace_floats(C.byref(cfg)))
+        else:
+            n_saved, n_ws = int(lib.ganffn_drnn_saved_floats(C.byref(cfg))), int(lib.ganffn_drnn_workspace_floats(C.byref(cfg)))
         if n_saved < 0 or n_ws < 0:
             _lib.check(-1, "ganffn_drnn_*_floats")
         dev = U[0].device
@@ -506,10 +516,16 @@ class DialogueRNNFn(torch.autograd.Function):
         rng = DeviceRng.get(dev)
         add = rng.next_add() if train else 0
         P = (_lib.DrnnPtrs * ndir)(*[_drnn_ptrs(p) for p in prm])
-        _lib.call("ganffn_drnn_fwd", C.byref(cfg), ndir, _ptr_array(U), _ptr_array(spk), _ptr_array(mval), P, _ptr_array(e),
-                  _ptr_array(alpha), _ptr_array(saved), _ptr_array(ws), _ptr(rng.state), C.c_uint64(add), _stream())
+        if listener:
+            LP = (_lib.DrnnListenerPtrs * ndir)(*[_drnn_ptrs(p, _lib.DrnnListenerPtrs) for p in lprm])
+            _lib.call("ganffn_drnn_listener_fwd", C.byref(cfg), ndir, _ptr_array(U), _ptr_array(spk), _ptr_array(mval), P, LP,
+                      _ptr_array(e), _ptr_array(alpha), _ptr_array(saved), _ptr_array(ws), _ptr(rng.state), C.c_uint64(add),
+                      _stream())
+        else:
+            _lib.call("ganffn_drnn_fwd", C.byref(cfg), ndir, _ptr_array(U), _ptr_array(spk), _ptr_array(mval), P, _ptr_array(e),
+                      _ptr_array(alpha), _ptr_array(saved), _ptr_array(ws), _ptr(rng.state), C.c_uint64(add), _stream())
         ctx.cfg, ctx.ndir, ctx.add, ctx.rng_state = cfg, ndir, add, rng.state
-        ctx.keep = (U, spk, mval, prm, alpha, saved, ws)
+        ctx.keep = (U, spk, mval, prm, lprm, alpha, saved, ws)
         out = []
         for z in range(ndir):
             out += [e[z], alpha[z]]
@@ -518,19 +534,28 @@ class DialogueRNNFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *douts):
-        U, spk, mval, prm, alpha, saved, ws = ctx.keep
+        U, spk, mval, prm, lprm, alpha, saved, ws = ctx.keep
         ndir, cfg = ctx.ndir, ctx.cfg
         d_e = [_f32c(douts[2 * z]) if douts[2 * z] is not None else torch.zeros_like(U[z][..., :cfg.He]) for z in range(ndir)]
         dU = [torch.empty_like(U[z]) for z in range(ndir)]
         grads = [[torch.zeros_like(p) for p in prm[z]] for z in range(ndir)]
         P = (_lib.DrnnPtrs * ndir)(*[_drnn_ptrs(p) for p in prm])
         G = (_lib.DrnnPtrs * ndir)(*[_drnn_ptrs(g) for g in grads])
-        _lib.call("ganffn_drnn_bwd", C.byref(cfg), ndir, _ptr_array(d_e), _ptr_array(U), _ptr_array(spk), _ptr_array(mval), P, G,
-                  _ptr_array(dU), _ptr_array(alpha), _ptr_array(saved), _ptr_array(ws), _ptr(ctx.rng_state), C.c_uint64(ctx.add),
-                  _stream())
+        if lprm is not None:
+            lgrads = [[torch.zeros_like(p) for p in lprm[z]] for z in range(ndir)]
+            LP = (_lib.DrnnListenerPtrs * ndir)(*[_drnn_ptrs(p, _lib.DrnnListenerPtrs) for p in lprm])
+            LG = (_lib.DrnnListenerPtrs * ndir)(*[_drnn_ptrs(g, _lib.DrnnListenerPtrs) for g in lgrads])
+            _lib.call("ganffn_drnn_listener_bwd", C.byref(cfg), ndir, _ptr_array(d_e), _ptr_array(U), _ptr_array(spk),
+                      _ptr_array(mval), P, LP, G, LG, _ptr_array(dU), _ptr_array(alpha), _ptr_array(saved), _ptr_array(ws),
+                      _ptr(ctx.rng_state), C.c_uint64(ctx.add), _stream())
+        else:
+            lgrads = [[] for _ in range(ndir)]
+            _lib.call("ganffn_drnn_bwd", C.byref(cfg), ndir, _ptr_array(d_e), _ptr_array(U), _ptr_array(spk), _ptr_array(mval), P,
+                      G, _ptr_array(dU), _ptr_array(alpha), _ptr_array(saved), _ptr_array(ws), _ptr(ctx.rng_state),
+                      C.c_uint64(ctx.add), _stream())
         out = [None]
         for z in range(ndir):
-            out += [dU[z], None, None] + grads[z]
+            out += [dU[z], None, None] + grads[z] + lgrads[z]
         return tuple(out)
 
 
@@ -544,8 +569,18 @@ def dialogue_rnn_supported(cell, U, qmask):
     PRECONDITION (not tested here: the test would be a device->host sync in front of ~760 latency-sized launches): every
     qmask row is one-hot or all zero, as the reference's loaders produce (dataloader.py:41-50) — the gate kernels use
     (argmax, value at argmax) only.  GANFFN_CHECK_QMASK=1 verifies it on every call."""
+    return not cell.listener_state and _drnn_limits_hold(cell, U, qmask)
+
+
+def dialogue_rnn_listener_supported(cell, U, qmask):
+    """dialogue_rnn_supported's limits for a cell WITH listener state (listener_state = True, model.py:899-921): the HIP
+    recurrence's listener path (ganffn_drnn_listener_fwd / _bwd).  Same qmask precondition."""
+    return bool(cell.listener_state) and _drnn_limits_hold(cell, U, qmask)
+
+
+def _drnn_limits_hold(cell, U, qmask):
     simple = type(cell.attention).__name__ == "SimpleAttention"          # softmax over time of a learned scalar score (model.py:117-131)
-    ok = (U.is_cuda and not cell.listener_state and (getattr(cell.attention, "att_type", None) == "general" or simple)
+    ok = (U.is_cuda and (getattr(cell.attention, "att_type", None) == "general" or simple)
           and qmask.size(2) == 2 and cell.D_g == cell.D_p and cell.D_g <= 512 and cell.D_m % 4 == 0 and cell.D_g % 4 == 0
           and cell.D_e % 4 == 0 and U.size(0) <= 112)
     if ok and _CHECK_QMASK:
@@ -554,7 +589,8 @@ def dialogue_rnn_supported(cell, U, qmask):
 
 
 def _drnn_cell_args(cell, U):
-    """(U, the 13 parameter tensors) the recurrence kernels take for one DialogueRNNCell.
+    """(U, the 13 parameter tensors — 17 with the listener's, DRNN_LISTENER_KEYS) the recurrence kernels take for one
+    DialogueRNNCell.
     general attention (model.py:160-166): as they are.
     simple attention (model.py:117-131): alpha = softmax_s(w . g_s) is general attention with the CONSTANT query w (general:
     alpha = softmax_s(q_t . g_s), q_t = W_att U_t).  A constant cannot come out of W_att U_t, so the utterance features get one
@@ -563,8 +599,9 @@ def _drnn_cell_args(cell, U):
     All of it is torch.cat on the way in, so autograd carries dU and d(w) back out; the recurrence itself is the same HIP launch
     chain.  (The scalar score has no bias in the reference; a bias would cancel in the softmax anyway.)"""
     sd = dict(cell.named_parameters())
+    keys = DRNN_KEYS + (DRNN_LISTENER_KEYS if cell.listener_state else [])
     if type(cell.attention).__name__ != "SimpleAttention":
-        return U, [sd[k] for k in DRNN_KEYS]
+        return U, [sd[k] for k in keys]
     S, B, Dm = U.shape
     H = cell.D_g
     Ux = torch.cat([U, U.new_ones(S, B, 1), U.new_zeros(S, B, 3)], 2)
@@ -576,7 +613,10 @@ def _drnn_cell_args(cell, U):
     params = []
     for k in DRNN_KEYS[:-1]:
         params.append(pad_ih(sd[k]) if k in ("g_cell.weight_ih", "p_cell.weight_ih") else sd[k])
-    return Ux, params + [att]
+    params.append(att)
+    if cell.listener_state:            # the listener's input side takes U too: the same zero columns
+        params += [pad_ih(sd[k]) if k == "l_cell.weight_ih" else sd[k] for k in DRNN_LISTENER_KEYS]
+    return Ux, params
 
 
 def dialogue_rnn_run(cells, Us, qmasks, training):
@@ -594,7 +634,7 @@ def dialogue_rnn_run(cells, Us, qmasks, training):
             mval = qm.gather(2, spk.unsqueeze(2)).squeeze(2)
             Ux, params = _drnn_cell_args(cells[z], Us[z][:, b0:b1])
             args += [Ux.contiguous(), spk, mval] + params
-        meta = {"p": float(cells[0].dropout.p), "train": bool(training)}
+        meta = {"p": float(cells[0].dropout.p), "train": bool(training), "listener": bool(cells[0].listener_state)}
         out = DialogueRNNFn.apply(meta, *args)
         for z in range(ndir):
             e_parts[z].append(out[2 * z])

@@ -243,7 +243,8 @@ int ganffn_general2_attention_bwd(const float* d_att, const float* x, const floa
  *   spk [S x B] int32 = argmax(qmask, party), mval [S x B] = qmask[s, b, spk] (0 on padded steps),
  *   e_out [S x B x D_e] emotion states (after dropout), alpha [B x S x S]: row t = attention weights of step t over the
  *   global history g_0 .. g_{t-1} (zero elsewhere; the reference's per-step alpha list is alpha[:, t, :t]).
- * Dropout (p = dropout_rec, train != 0) on g, the speaker's party state and e, Philox rows t*B + b. */
+ * Dropout (p = dropout_rec, train != 0) on g, the speaker's party state and e, Philox rows t*B + b, sites 8, 9, 10
+ * (+ 4 for the second direction); the listener variant below adds site 11 (+ 4). */
 typedef struct ganffn_drnn_cfg {
     int32_t S, B;        /* steps (<= 112), dialogues (<= 32) */
     int32_t Dm, H, He;   /* D_m, D_g = D_p, D_e  (100, 500, 100; multiples of 4) */
@@ -272,6 +273,33 @@ int ganffn_drnn_bwd(const ganffn_drnn_cfg* cfg, int ndir, const float* const* d_
                     const ganffn_drnn_grads* grads, float* const* dU, const float* const* alpha,
                     const float* const* saved, float* const* workspace, const uint64_t* rng,
                     uint64_t rng_offset_add, void* stream);
+/* The same recurrence with listener_state = True (model.py:899-921; train_IEMOCAP_DialogueRNN.py --active-listener): every
+ * party row also takes a listener GRU step ql[p] = drop(l_cell([U_t, qs], q_{t-1}[p])), p = 0, 1, with qs the speaker's new
+ * state after its dropout, and q_t[p] = (m != 0 && p == spk) ? qs : ql[p] — on padded steps (m = 0) both rows take ql.
+ * Same cfg, same arguments plus the 4 l_cell tensors per direction: weight_ih [3H x (D_m+H)], weight_hh [3H x H], bias_ih,
+ * bias_hh.  saved / workspace are sized by the _listener_ functions (per direction; larger than the listener-free sizes).
+ * Listener dropout (train != 0): Philox site 11 + 4 * direction, row t*B + b, column p*H + u of a width-2H row, i.e. on the
+ * CPU keep_mask(S*B, 2*H, p, 11 + 4*z, seed, offset).view(S, B, 2, H).  lgrads (ndir entries, accumulated into) may be
+ * NULL, or have NULL members: no l_cell weight gradients. */
+typedef struct ganffn_drnn_listener_params {
+    const float *l_wih, *l_whh, *l_bih, *l_bhh;
+} ganffn_drnn_listener_params;
+typedef struct ganffn_drnn_listener_grads {
+    float *l_wih, *l_whh, *l_bih, *l_bhh;
+} ganffn_drnn_listener_grads;
+int64_t ganffn_drnn_listener_saved_floats(const ganffn_drnn_cfg* cfg);      /* per direction */
+int64_t ganffn_drnn_listener_workspace_floats(const ganffn_drnn_cfg* cfg);  /* per direction; fwd and bwd */
+int ganffn_drnn_listener_fwd(const ganffn_drnn_cfg* cfg, int ndir, const float* const* U, const int32_t* const* spk,
+                             const float* const* mval, const ganffn_drnn_params* params,
+                             const ganffn_drnn_listener_params* lparams, float* const* e_out, float* const* alpha,
+                             float* const* saved, float* const* workspace, const uint64_t* rng, uint64_t rng_offset_add,
+                             void* stream);
+int ganffn_drnn_listener_bwd(const ganffn_drnn_cfg* cfg, int ndir, const float* const* d_e, const float* const* U,
+                             const int32_t* const* spk, const float* const* mval, const ganffn_drnn_params* params,
+                             const ganffn_drnn_listener_params* lparams, const ganffn_drnn_grads* grads,
+                             const ganffn_drnn_listener_grads* lgrads, float* const* dU, const float* const* alpha,
+                             const float* const* saved, float* const* workspace, const uint64_t* rng,
+                             uint64_t rng_offset_add, void* stream);
 
 /* Data movement of BiModel.forward around the recurrence (model.py:1008-1062), one launch each (csrc/drnn_head.hip):
  * ganffn_seq_reverse: out[s, b, :] (+)= s < lens[b] ? x[lens[b]-1-s, b, :] : 0 — BiModel._reverse_seq and, being its own
