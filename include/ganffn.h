@@ -306,7 +306,10 @@ int ganffn_drnn_listener_bwd(const ganffn_drnn_cfg* cfg, int ndir, const float* 
  *   transpose, its gradient (accumulate != 0 adds into out); x, out [S x B x D], D % 4 == 0.
  * ganffn_drnn_join_fwd: emotions [S x B x 2 D_e] = cat(dropout(e_f), dropout(reverse(e_b))) with p = dropout_rec + ...
  *   (BiModel.dropout_rec), two dropout sites; ganffn_drnn_join_bwd: the gradients of e_f and of e_b (in the reverse
- *   direction's own order) from d_emotions, same masks.
+ *   direction's own order) from d_emotions, same masks.  Mask layout: both halves are [S*B x D_e] Philox masks at the
+ *   FORWARD-time token row t = s*B + b, column c < D_e, one (seed, offset + rng_offset_add); the first half at site_f, the
+ *   second at site_b.  The second half's mask applies after the reversal: the element of e_b at reverse step len_b-1-s
+ *   lands on row s*B + b and takes that row's mask, as the reference applies dropout_rec to reverse(e_b).
  * ganffn_mask_pos_inplace: d[i] = aux[i] > 0 ? d[i] * mscale : 0 — backward through dropout(relu(.)) from the saved output. */
 int ganffn_seq_reverse(const float* x, const int32_t* lens, float* out, int S, int B, int D, int accumulate, void* stream);
 int ganffn_drnn_join_fwd(const float* e_f, const float* e_b, const int32_t* lens, float* emotions, int S, int B, int De,

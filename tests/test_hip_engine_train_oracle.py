@@ -17,15 +17,13 @@ of the sub-steps can be compared on its own.  Per compared sub-step:
   * the partner is bit-unchanged (its slab, moments and step).
 GANFFN_ADAM_PARTS=0 keeps the summed gradient in net.grad; that the unreduced-chunk path gives the same bits is
 tests/test_hip_engine.py::test_unreduced_weight_gradient_chunks_give_the_reduce_launchs_bits."""
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
 import engine_oracle as EO
 import formula as F_
-from util import DIN, DISC, GEN, MELD_DIN, MELD_DISC, MELD_GEN, _assert_close, formula_sd
+from util import DIN, DISC, GEN, MELD_DIN, MELD_DISC, MELD_GEN, _assert_close, formula_sd, relu_masks
 
 pytestmark = pytest.mark.gpu
 
@@ -78,21 +76,6 @@ def _networks(gen_table, disc_table):
     return out
 
 
-def _relu_masks(ps, cfg, S, B):
-    """the 0/1 ReLU(+dropout) pattern of every layer of a pass, read from its saved hidden activations at the offsets of the
-    config the pass ran with (dropped units read 0: their gradient is 0 whatever the pattern)"""
-    from gan_ffn_amd import _lib
-    lib = _lib.load()
-    assert (cfg.S, cfg.B) == (S, B)
-    n = S * B * cfg.F
-    masks = []
-    for l in range(cfg.L):
-        off = int(lib.ganffn_encoder_saved_hidden_offset(C.byref(cfg), l))
-        assert off >= 0 and off + n <= ps.saved.numel(), (off, n, ps.saved.numel())
-        masks.append((ps.saved[off:off + n] != 0).view(S, B, cfg.F).cpu())
-    return masks
-
-
 def _host(st):
     return dict(slab=st.slab.cpu().clone(), m=st.exp_avg.cpu().clone(), v=st.exp_avg_sq.cpu().clone(), t=int(st.step.item()))
 
@@ -143,13 +126,13 @@ class _Harness:
         self.sub = None
         if kind == "D":
             pd = eng.pass_D2[who]
-            masks = _relu_masks(pd, pd.cfg_train, S, 2 * B)
+            masks = relu_masks(pd, pd.cfg_train, S, 2 * B)
             fake = eng.pass_G_nosave[partner].out.cpu().double()
             self._check_disc(tr, pa, xs[who], xs[partner], b, i, pre, pre_p, post, loss, masks, fake, _ref_lr(kind, who))
         else:
             pg, pd = eng.pass_G[who], eng.pass_D1[partner]
-            masks_g = _relu_masks(pg, pg.cfg_train, S, B)
-            masks_d = _relu_masks(pd, pd.cfg_eval, S, B)        # the frozen discriminator ran in eval mode
+            masks_g = relu_masks(pg, pg.cfg_train, S, B)
+            masks_d = relu_masks(pd, pd.cfg_eval, S, B)        # the frozen discriminator ran in eval mode
             out = pg.out.cpu().double()
             self._check_gen(tr, pa, xs[who], b, i, pre, pre_p, post, loss, masks_g, masks_d, out, _ref_lr(kind, who))
         # the partner only lends its parameters: bit-unchanged

@@ -1,4 +1,5 @@
 """Shared helpers for the test-suite: golden loading, formula weights, comparisons."""
+import ctypes as C
 import os
 
 import numpy as np
@@ -109,3 +110,19 @@ def check_summary(g, prefix, t, rtol=1e-4, atol=1e-5, what="", strict=False, out
     l2 = float(g[prefix + "/l2"])
     assert abs(np.sqrt((flat ** 2).sum()) - l2) <= l2_rtol * max(l2, 1e-30) + atol, (what, prefix, "l2")
     return r
+
+
+def relu_masks(ps, cfg, S, B):
+    """the 0/1 ReLU(+dropout) pattern of every encoder layer of an engine pass (engine._Pass), read from its saved hidden
+    activations at the offsets of the config the pass ran with (dropped units read 0: their gradient is 0 whatever the
+    pattern) -> [(S, B, F) bool] on the host"""
+    from gan_ffn_amd import _lib
+    lib = _lib.load()
+    assert (cfg.S, cfg.B) == (S, B)
+    n = S * B * cfg.F
+    masks = []
+    for l in range(cfg.L):
+        off = int(lib.ganffn_encoder_saved_hidden_offset(C.byref(cfg), l))
+        assert off >= 0 and off + n <= ps.saved.numel(), (off, n, ps.saved.numel())
+        masks.append((ps.saved[off:off + n] != 0).view(S, B, cfg.F).cpu())
+    return masks
