@@ -15,6 +15,10 @@ The --warmup and --steps iterations start from the seeded initial training state
 stream are restored after the timing-dependent pre-roll), so what they compute depends on the arguments only.
 `--dump-outputs DIR` writes what the last timed step computed (its losses and the networks' parameters after it; slabs
 larger than DUMP_SAMPLE floats as a fixed, seeded sample) to DIR/<name>.npy in float32, for comparing two builds.
+
+A plain run does only what the headline needs: set up, pre-roll and warm up, time --steps iterations, dump, print the line.
+`--full` adds what takes runs of its own: the device-synchronised per-iteration block, the live kernel-family replays and
+the roofline figures built on them, and (one rank) the stock-PyTorch CPU baselines.
 """
 import argparse
 import ctypes as C
@@ -574,9 +578,7 @@ def run_drnn(args, dev, pg, rank, world):
         dist.all_reduce(u)
         dt, utts = float(t), float(u)
     if rank == 0:
-        kt, kbytes = time_skinny_kernel(B)
-        in_step = drnn_in_step_us("skinny_nt_kernel<12>")
-        print(json.dumps({
+        out = {
             "metric": "utterances/sec per phase-2 train step, IEMOCAP GAN-FFN + DialogueRNN", "value": round(utts * args.steps / dt, 2),
             "unit": "utterances/s", "n_gpus": world, "steps": args.steps, "warmup": n_warm,
             "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -586,24 +588,27 @@ def run_drnn(args, dev, pg, rank, world):
                                    "6-class head, forward + MaskedNLLLoss + backward + Adam, batch=%d per GPU fp32 on "
                                    "%dxMI355X" % (B, world),
                        "dialogues_per_gpu": B, "seq_len": S, "parallelism": "dp%d" % world, "launch": "eager",
-                       "last_loss": round(float(loss.detach()), 4)},
-            "roofline": {"bound": "hbm", "kernel": "skinny_nt_kernel<12> (the four dgrad products of one backward step of the "
-                                                   "recurrence, both directions: 8 x ([B x 1500] x [1500 x 500]) on transposed "
-                                                   "weights; the skinny products are the kernel family with the largest share of "
-                                                   "GPU time in " + DRNN_IN_STEP_FILE + ")",
-                         "achieved": round(kbytes / kt / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(kbytes / kt / 1e9 / HBM_PEAK_GBS, 4), "traffic": None,
-                         "algorithmic_bytes_per_launch": round(kbytes), "avg_kernel_us": round(kt * 1e6, 2),
-                         "in_step_avg_us": in_step, "frac_in_step": round(kbytes / (in_step * 1e-6) / 1e9 / HBM_PEAK_GBS, 4) if in_step else None,
-                         "l2_served_peak": L2_SERVED_GBS, "frac_of_l2_served_peak": round(kbytes / kt / 1e9 / L2_SERVED_GBS, 4),
-                         "frac_of_l2_served_peak_in_step": round(kbytes / (in_step * 1e-6) / 1e9 / L2_SERVED_GBS, 4) if in_step else None,
-                         "how": "HIP events around 20 back-to-back launches on the launch stream (in_step_avg_us: the same "
-                                "kernel inside the step, from the committed rocprofv3 summary).  The 24 MB of recurrent weights are "
-                                "re-read every step by the same workgroup ids, i.e. each XCD re-reads its own 3 MB eighth out of its "
-                                "4 MiB L2: the roof that applies is the L2 -> CU path (MI355X_MICROARCH.md 'Indexed rows': 16.8-18.8 "
-                                "TB/s chip-wide for rows served from L2) — frac_of_l2_served_peak; `frac` against the HBM peak is "
-                                "what the contract's bound key offers.  Either way the launch is latency-sized (one link of a "
-                                "serial chain of ~400)"}}), flush=True)
+                       "last_loss": round(float(loss.detach()), 4)}}
+        if args.full:
+            kt, kbytes = time_skinny_kernel(B)
+            in_step = drnn_in_step_us("skinny_nt_kernel<12>")
+            out["roofline"] = {
+                "bound": "hbm", "kernel": "skinny_nt_kernel<12> (the four dgrad products of one backward step of the recurrence, "
+                                          "both directions: 8 x ([B x 1500] x [1500 x 500]) on transposed weights; the skinny "
+                                          "products are the kernel family with the largest share of GPU time in " + DRNN_IN_STEP_FILE + ")",
+                "achieved": round(kbytes / kt / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(kbytes / kt / 1e9 / HBM_PEAK_GBS, 4), "traffic": None,
+                "algorithmic_bytes_per_launch": round(kbytes), "avg_kernel_us": round(kt * 1e6, 2),
+                "in_step_avg_us": in_step, "frac_in_step": round(kbytes / (in_step * 1e-6) / 1e9 / HBM_PEAK_GBS, 4) if in_step else None,
+                "l2_served_peak": L2_SERVED_GBS, "frac_of_l2_served_peak": round(kbytes / kt / 1e9 / L2_SERVED_GBS, 4),
+                "frac_of_l2_served_peak_in_step": round(kbytes / (in_step * 1e-6) / 1e9 / L2_SERVED_GBS, 4) if in_step else None,
+                "how": "HIP events around 20 back-to-back launches on the launch stream (in_step_avg_us: the same kernel inside "
+                       "the step, from the committed rocprofv3 summary).  The 24 MB of recurrent weights are re-read every step "
+                       "by the same workgroup ids, i.e. each XCD re-reads its own 3 MB eighth out of its 4 MiB L2: the roof that "
+                       "applies is the L2 -> CU path (16.8-18.8 TB/s chip-wide for rows served from L2, L2_SERVED_GBS) — "
+                       "frac_of_l2_served_peak; `frac` against the HBM peak is what the contract's bound key offers.  Either "
+                       "way the launch is latency-sized (one link of a serial chain of ~400)"}
+        print(json.dumps(out), flush=True)
 
 
 def host_threads():
@@ -949,7 +954,10 @@ def main():
                          "has no GAN path for MELD); drnn = configs[4], the phase-2 GAN-FFN + DialogueRNN "
                          "classifier step at batch 30")
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own: the device-synchronised per-iteration "
+                         "block, the live kernel-family replays with the roofline figures, and (one rank) the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--step-only", action="store_true",
                     help="time the step and print the line without the isolated kernel replays (roofline / roofline_worst) and "
                          "without the CPU baseline: what tools/gpu_round.sh profiles, so that the rocprofv3 summaries hold the "
@@ -974,6 +982,8 @@ def main():
         ap.error("--warmup must not be negative")
     if args.dump_outputs and args.replay_family:
         ap.error("--dump-outputs needs the timed step; --replay-family does not run it")
+    if args.full and args.step_only:
+        ap.error("--step-only and --full contradict each other")
     if args.seq is None:
         args.seq = 33 if args.config == "meld" else 94
     if args.config == "drnn" and args.batch == 32:
@@ -1087,9 +1097,9 @@ def main():
     heartbeat("rank %d: %d timed steps, %.3f ms per step" % (rank, args.steps, dt / args.steps * 1e3), rank, every_rank=True)
     # second, separately timed block (median over >= 20 device-synchronised iterations): here every iteration
     # is bracketed by a device synchronisation (+ barrier), so consecutive iterations do NOT overlap as they do in the block
-    # above — it reads a little slower and is reported beside the headline, never instead of it
+    # above — it reads a little slower and is reported beside the headline, never instead of it (--full)
     per_iter = []
-    for _ in range(0 if args.step_only else max(20, min(args.steps, 60))):
+    for _ in range(max(20, min(args.steps, 60)) if args.full else 0):
         sync()
         t1 = time.perf_counter()
         eng.iteration(batch)
@@ -1131,8 +1141,6 @@ def main():
                           "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
                           "config": dict({"workload": cfgname, "streams": eng.n_streams, "preroll_iterations": n_preroll}, **dist_info)}), flush=True)
     elif rank == 0:
-        sys.path.insert(0, os.path.join(ROOT, "tools"))
-        import roofline_model as RM
         fpt = flops_per_token(S, cfgname)
         step_tflops = fpt * S * B * world * args.steps / dt / 1e12
         out = {
@@ -1158,16 +1166,19 @@ def main():
                        "step_tflops_executed": round(step_tflops * (1.0 - frozen_wgrad_flops_per_token(cfgname) / fpt), 2),
                        "step_frac_executed": round(step_tflops * (1.0 - frozen_wgrad_flops_per_token(cfgname) / fpt) * 1e12 / (FP32_MFMA_PEAK * world), 4),
                        "preroll_iterations": n_preroll,
-                       "median_ms_per_step_synchronised": round(per_iter[len(per_iter) // 2], 3) if per_iter else None,
-                       "min_max_ms_per_step_synchronised": [round(per_iter[0], 3), round(per_iter[-1], 3)] if per_iter else None,
-                       "synchronised_iterations": len(per_iter),
                        "timing": "ms_per_step / value: EXACTLY --steps iterations between two barrier + device-synchronise points "
-                                 "(consecutive iterations overlap on the three streams, as in training); median_ms_per_step_synchronised: "
-                                 "a second block, device-synchronised at every iteration boundary (SURVEY.md 8d)",
+                                 "(consecutive iterations overlap on the three streams, as in training)",
                        **dist_info,
                        "last_losses": {k: round(v, 4) for k, v in losses.items()}},
         }
-        if cfgname != "iemocap":
+        if per_iter:
+            out["config"].update({
+                "median_ms_per_step_synchronised": round(per_iter[len(per_iter) // 2], 3),
+                "min_max_ms_per_step_synchronised": [round(per_iter[0], 3), round(per_iter[-1], 3)],
+                "synchronised_iterations": len(per_iter)})
+            out["config"]["timing"] += ("; median_ms_per_step_synchronised: a second block, device-synchronised at every "
+                                        "iteration boundary (SURVEY.md 8d)")
+        if args.full and cfgname != "iemocap":
             # extension workload: the weight-gradient launch (its heaviest family; no committed single-stream profile of it)
             kt, kflop, klaunch = time_dominant_kernel(S, B, config=cfgname)
             out["roofline"] = {"bound": "mfma", "kernel": "the grouped weight-gradient launch (all 32 weight + bias gradients of one encoder "
@@ -1177,7 +1188,9 @@ def main():
                                "algorithmic_bytes_per_launch": round(wgrad_algorithmic_bytes(S, B, cfgname)),
                                "avg_kernel_us": round(kt * 1e6, 2), "avg_gflop_per_launch": round(kflop / 1e9, 4),
                                "how": "HIP events around one iteration's launch mix of this launch replayed in isolation on the launch stream"}
-        else:
+        elif args.full:
+            sys.path.insert(0, os.path.join(ROOT, "tools"))
+            import roofline_model as RM
             # ---- the bench line FOLLOWS the committed single-stream profile: every kernel family with >= 5 % of the step's
             # kernel time is listed with its in-step roofline fraction (tools/roofline_model.py: family table + algorithmic
             # work per iteration), each is also replayed live (HIP events on the launch stream); `roofline` is the family with
@@ -1265,7 +1278,7 @@ def main():
                 if d["family"] == "wgrad":
                     d["traffic"] = wtraffic
                     d["algorithmic_bytes_per_launch"] = round(wgrad_algorithmic_bytes(S, B, cfgname))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             threads = host_threads()
             print("[bench] cpu_baseline on %d host threads (affinity / cgroup share)" % threads, file=sys.stderr, flush=True)
             cv, cdt, cutts = cpu_baseline(S, args.cpu_sample_batch, threads, config=cfgname)

@@ -34,6 +34,16 @@ def test_bench_refuses_arguments_without_a_timed_step():
         assert r.returncode == 2 and "error:" in r.stderr, (argv, r.stderr[-2000:])
 
 
+def test_bench_refuses_full_with_step_only():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--step-only"], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 2 and "--step-only and --full" in r.stderr, r.stderr[-2000:]
+
+
+def test_full_is_passed_on_to_the_ranks():
+    assert bench._child_argv(["--gpus", "2", "--full", "--launcher", "spawn"], 1) == ["--gpus", "2", "--full", "--streams", "1"]
+
+
 def test_dumped_slabs_are_a_fixed_sample_within_the_size_cap(tmp_path):
     import numpy as np
     import pytest

@@ -1,4 +1,4 @@
-"""GPU: bench.py contract (one JSON line with roofline + cpu_baseline) and the RCCL code path exercised on
+"""GPU: bench.py contract (one JSON line; with --full also roofline + cpu_baseline) and the RCCL code path exercised on
 a single GPU (1-rank nccl group, launched exactly as the driver launches N > 1)."""
 import json
 import os
@@ -24,8 +24,25 @@ def _last_json(out):
     return json.loads(lines[0])
 
 
+def test_bench_plain_run_is_the_headline_only():
+    """a plain run sets up, warms up, times the steps and prints the line: none of what --full adds"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1"],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _last_json(r.stdout)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config"):
+        assert k in d, k
+    assert d["metric"] == "utterances/sec per GAN train step, IEMOCAP tri-modal" and d["unit"] == "utterances/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "f32" and d["steps"] == 3 and d["value"] > 0
+    for k in ("roofline", "roofline_families", "roofline_worst", "cpu_baseline", "profile"):
+        assert k not in d, k
+    assert "median_ms_per_step_synchronised" not in d["config"] and "gpu_over_cpu" not in d["config"]
+    assert "cpu_baseline" not in r.stderr
+
+
 def test_bench_default_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1",
                         "--cpu-sample-batch", "2"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)
@@ -36,6 +53,7 @@ def test_bench_default_contract():
     assert d["roofline"]["bound"] == "mfma" and 0 < d["roofline"]["frac"] < 1
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["cores"] >= 1
     assert d["value"] > 50 * d["cpu_baseline"]["value"]          # north_star: >= 50x the host CPU
+    assert d["config"]["synchronised_iterations"] == 20 and d["config"]["median_ms_per_step_synchronised"] > 0
 
 
 def test_bench_dump_outputs_repeat_bit_for_bit(tmp_path):
@@ -75,12 +93,12 @@ def test_bench_rccl_path_on_one_rank():
 @pytest.mark.parametrize("config", ["meld", "drnn"])
 def test_bench_other_configs_on_the_rccl_path(config):
     """configs[2] (MELD widths) and configs[4] (GAN-FFN + DialogueRNN) through the same launcher and the 1-rank nccl
-    group: the line keeps the contract's keys and a roofline object"""
+    group: the line keeps the contract's keys and, with --full, a roofline object"""
     env = dict(os.environ, GANFFN_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                         "--master-addr", "127.0.0.1", "--master-port", _free_port(),
-                        os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                        "--config", config], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                        os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full",
+                        "--no-cpu-baseline", "--config", config], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _last_json(r.stdout)
     for k in ("metric", "value", "unit", "n_gpus", "steps", "ms_per_step", "scaling", "dtype", "config", "roofline"):

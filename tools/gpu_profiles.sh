@@ -28,9 +28,9 @@ for fam in attention ffn_k100 ffn_n100; do bash tools/family_pmc.sh $fam r05 > $
 python3 tools/general2_line.py $(ls $O/prof_g2/*/*kernel_stats.csv | head -1) > $O/r05_general2_line.txt
 rm -rf $O/prof_g2
 unset GANFFN_BENCH_PREROLL
-timeout -k 10 600 python bench.py > $O/r05_bench_default.json 2> $O/r05_bench_default.err || { tail -20 $O/r05_bench_default.err; exit 1; }
-timeout -k 10 300 python bench.py --config meld --no-cpu-baseline > $O/r05_bench_meld.json 2> $O/r05_bench_meld.err || { tail -20 $O/r05_bench_meld.err; exit 1; }
-timeout -k 10 300 python bench.py --config drnn --no-cpu-baseline > $O/r05_bench_drnn.json 2> $O/r05_bench_drnn.err || { tail -20 $O/r05_bench_drnn.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/r05_bench_default.json 2> $O/r05_bench_default.err || { tail -20 $O/r05_bench_default.err; exit 1; }
+timeout -k 10 300 python bench.py --config meld --full --no-cpu-baseline > $O/r05_bench_meld.json 2> $O/r05_bench_meld.err || { tail -20 $O/r05_bench_meld.err; exit 1; }
+timeout -k 10 300 python bench.py --config drnn --full --no-cpu-baseline > $O/r05_bench_drnn.json 2> $O/r05_bench_drnn.err || { tail -20 $O/r05_bench_drnn.err; exit 1; }
 python3 - <<'PY'
 import json
 d = json.loads([l for l in open("gpurun_out/r05_bench_default.json") if l.startswith("{")][0])

@@ -10,7 +10,7 @@ rc=$?
 tail -5 $O/r05_gputest.log
 [ $rc -ne 0 ] && { grep -E "^(FAILED|ERROR)|Error|assert" $O/r05_gputest.log | head -30; exit $rc; }
 for c in iemocap meld drnn; do
-  timeout -k 10 300 python bench.py --config $c --no-cpu-baseline > $O/r05_bench_${c}_quick.json 2> $O/r05_bench_${c}_quick.err || { tail -20 $O/r05_bench_${c}_quick.err; exit 1; }
+  timeout -k 10 300 python bench.py --config $c --full --no-cpu-baseline > $O/r05_bench_${c}_quick.json 2> $O/r05_bench_${c}_quick.err || { tail -20 $O/r05_bench_${c}_quick.err; exit 1; }
   cat $O/r05_bench_${c}_quick.json
 done
 cd /tmp && export TMPDIR=/tmp
