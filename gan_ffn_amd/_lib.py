@@ -46,6 +46,18 @@ class DrnnListenerPtrs(C.Structure):    # ganffn_drnn_listener_params / ganffn_d
     _fields_ = [(n, C.c_void_p) for n in DRNN_LISTENER_FIELDS]
 
 
+class DrnnAtt(C.Structure):        # ganffn_drnn_att: context attention type + D_a
+    _fields_ = [("type", C.c_int32), ("Da", C.c_int32)]
+
+
+DRNN_ATT_TYPES = {"general": 0, "simple": 1, "dot": 2, "general2": 3, "concat": 4}     # GANFFN_DRNN_ATT_*
+DRNN_ATT_FIELDS = ["w", "b", "v"]
+
+
+class DrnnAttPtrs(C.Structure):     # ganffn_drnn_att_params / ganffn_drnn_att_grads: 3 pointers
+    _fields_ = [(n, C.c_void_p) for n in DRNN_ATT_FIELDS]
+
+
 _P = C.c_void_p
 _I, _L, _F, _U32, _U64 = C.c_int, C.c_int64, C.c_float, C.c_uint32, C.c_uint64
 _PE, _PH = C.POINTER(EncCfg), C.POINTER(HeadCfg)
@@ -116,6 +128,10 @@ SIGNATURES = {
     "ganffn_drnn_listener_workspace_floats": (_L, [C.POINTER(DrnnCfg)]),
     "ganffn_drnn_listener_fwd": (_I, [C.POINTER(DrnnCfg), _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, _P]),
     "ganffn_drnn_listener_bwd": (_I, [C.POINTER(DrnnCfg), _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, _P]),
+    "ganffn_drnn_att_saved_floats": (_L, [C.POINTER(DrnnCfg), C.POINTER(DrnnAtt), _I]),
+    "ganffn_drnn_att_workspace_floats": (_L, [C.POINTER(DrnnCfg), C.POINTER(DrnnAtt), _I]),
+    "ganffn_drnn_att_fwd": (_I, [C.POINTER(DrnnCfg), C.POINTER(DrnnAtt), _I] + [_P] * 11 + [_U64, _P]),
+    "ganffn_drnn_att_bwd": (_I, [C.POINTER(DrnnCfg), C.POINTER(DrnnAtt), _I] + [_P] * 15 + [_U64, _P]),
     "ganffn_dropout": (_I, [_P, _P, _I, _I, _F, _U32, _P, _U64, _P]),
     "ganffn_seq_reverse": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "ganffn_drnn_join_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _U32, _U32, _P, _U64, _I, _P]),

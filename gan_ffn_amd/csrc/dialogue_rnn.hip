@@ -31,6 +31,9 @@
 // Everything is deterministic (no atomics).  Dropout follows the Philox contract of common.h with rows t*B + b.
 // listener_state = True (model.py:899-921, --active-listener) is a variant of the same driver (ganffn_drnn_listener_fwd /
 // _bwd): 4 launches per step each way instead of 2 — see "Listener state" below.
+// The other context attention types (--attention simple / dot / general2 / concat, model.py:117-194) run through
+// ganffn_drnn_att_fwd / _bwd with the same launches per step: their extra work sits in the gate + attention launches (see
+// "Other context attention types" below).
 #include "common.h"
 
 namespace ganffn {
@@ -398,15 +401,104 @@ __device__ __forceinline__ void drnn_scores(const float* __restrict__ q, const f
     }
 }
 
-__device__ __forceinline__ void drnn_attn_fwd_body(const AttnArgs& a, const AttnDir& d, const int b) {
+// Other context attention types (ganffn_drnn_att_*; model.py:134-194).  "simple" and "dot" are general attention with
+// another hoisted query (the constant w, resp. U_t itself), so they run the bodies above as they are; "general2" takes a
+// tanh on the scores, "concat" scores s_j = v . tanh(W_g g_j + W_u U_t) from P_j = W_g g_j, computed right after g_j in
+// the workgroup that owns the dialogue, and X_t = U_t W_u^T (hoisted).
+enum : int { ATT_GENERAL = GANFFN_DRNN_ATT_GENERAL, ATT_SIMPLE = GANFFN_DRNN_ATT_SIMPLE, ATT_DOT = GANFFN_DRNN_ATT_DOT,
+             ATT_GENERAL2 = GANFFN_DRNN_ATT_GENERAL2, ATT_CONCAT = GANFFN_DRNN_ATT_CONCAT };
+constexpr int DR_MAXDA = 512;
+struct AttnXDir {
+    float* TS;           // general2: [B x S x S] tanh scores, row t (saved for backward)
+    float* P;            // concat: [S B x D_a] P_j = W_g g_j, row j B + b
+    const float* XC;     // concat: [S B x D_a] X_t = W_u U_t, row t B + b
+    const float* Wg;     // concat: W_g = transform.weight[:, :D_g], leading dimension ldw = D_g + D_m
+    const float* v;      // concat: vector_prod.weight [D_a]
+    float* dP;           // concat, backward: [S B x D_a] accumulated gradient wrt P_j
+    float* dXC;          // concat, backward: [S B x D_a] gradient wrt X_t
+    float* dVp;          // concat, backward: [S B x D_a] per-step partials of the gradient wrt v (reduced after the loop)
+};
+struct AttnX { AttnXDir d[2]; int ldw, Da; };
+
+// concat: P_j[b] = W_g g_j[b] (g_j = G block j + 1); wave w takes rows w, w + 16, ... two at a time, lanes split D_g
+__device__ __forceinline__ void drnn_concat_project(const AttnX& x, const AttnXDir& xd, const float* __restrict__ G, int B, int H,
+                                                    int b, int j, int lane, int w) {
+    const float* g = G + ((size_t)(j + 1) * B + b) * H;
+    float gr[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) gr[i] = lane + 64 * i < H ? g[lane + 64 * i] : 0.f;
+    for (int a0 = w; a0 < x.Da; a0 += 32) {
+        const int a1 = min(a0 + 16, x.Da - 1);
+        const float* w0 = xd.Wg + (size_t)a0 * x.ldw;
+        const float* w1 = xd.Wg + (size_t)a1 * x.ldw;
+        float v0[8], v1[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int k = min(lane + 64 * i, H - 1);
+            v0[i] = w0[k];
+            v1[i] = w1[k];
+        }
+        float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { s0 += gr[i] * v0[i]; s1 += gr[i] * v1[i]; }
+        s0 = wave_sum(s0);
+        s1 = wave_sum(s1);
+        if (lane == 0) {
+            xd.P[((size_t)j * B + b) * x.Da + a0] = s0;
+            if (a0 + 16 < x.Da) xd.P[((size_t)j * B + b) * x.Da + a0 + 16] = s1;
+        }
+    }
+}
+
+// concat scores of step t: s_j = sum_a v_a tanh(P_j[a] + X_t[a]), j < t; wave per history step (two at a time), lanes split D_a
+__device__ __forceinline__ void drnn_concat_scores(const AttnX& x, const AttnXDir& xd, int B, int b, int t, float* __restrict__ out,
+                                                   int lane, int w) {
+    const float* X = xd.XC + ((size_t)t * B + b) * x.Da;
+    float xr[8], vr[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int a = lane + 64 * i;
+        xr[i] = a < x.Da ? X[a] : 0.f;
+        vr[i] = a < x.Da ? xd.v[a] : 0.f;
+    }
+    for (int j0 = w; j0 < t; j0 += 32) {
+        const int j1 = min(j0 + 16, t - 1);
+        const float* p0 = xd.P + ((size_t)j0 * B + b) * x.Da;
+        const float* p1 = xd.P + ((size_t)j1 * B + b) * x.Da;
+        float v0[8], v1[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const int a = min(lane + 64 * i, x.Da - 1);
+            v0[i] = p0[a];
+            v1[i] = p1[a];
+        }
+        float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { s0 += vr[i] * tanhf(v0[i] + xr[i]); s1 += vr[i] * tanhf(v1[i] + xr[i]); }
+        s0 = wave_sum(s0);
+        s1 = wave_sum(s1);
+        if (lane == 0) {
+            out[j0] = s0;
+            if (j0 + 16 < t) out[j0 + 16] = s1;
+        }
+    }
+}
+
+template <int ATT>
+__device__ __forceinline__ void drnn_attn_fwd_body(const AttnArgs& a, const AttnDir& d, const int b, const AttnX* x = nullptr) {
     __shared__ float sc[DR_MAXS + 16];
     __shared__ float red[2];
     __shared__ float part[512];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, t = a.t;
-    drnn_scores(d.XA + (size_t)b * a.H, d.G, a.B, a.H, b, t, sc, lane, w);     // H <= 512 (checked on the host)
+    if constexpr (ATT == ATT_CONCAT) drnn_concat_scores(*x, x->d[blockIdx.z], a.B, b, t, sc, lane, w);     // D_a <= 512 (host)
+    else drnn_scores(d.XA + (size_t)b * a.H, d.G, a.B, a.H, b, t, sc, lane, w);     // H <= 512 (checked on the host)
     __syncthreads();
     // softmax over t <= 112 scores: the first two waves
     float v = tid < t ? sc[tid] : -INFINITY;
+    if (ATT == ATT_GENERAL2 && tid < t) {         // s_j = tanh(<W U_t + b, g_j>) (model.py:169-182 with an all-ones mask)
+        v = tanhf(v);
+        x->d[blockIdx.z].TS[((size_t)b * a.S + t) * a.S + tid] = v;
+    }
     float m = wave_max(v);
     if (tid < 128 && lane == 0) red[w] = m;
     __syncthreads();
@@ -442,7 +534,7 @@ __device__ __forceinline__ void drnn_attn_fwd_body(const AttnArgs& a, const Attn
     __syncthreads();
     if (!half && k < a.H) d.CT[(size_t)b * a.H + k] = c + part[k];
 }
-__global__ __launch_bounds__(DR_AT) void drnn_attn_fwd_kernel(AttnArgs a) { drnn_attn_fwd_body(a, a.d[blockIdx.z], blockIdx.x); }
+__global__ __launch_bounds__(DR_AT) void drnn_attn_fwd_kernel(AttnArgs a) { drnn_attn_fwd_body<ATT_GENERAL>(a, a.d[blockIdx.z], blockIdx.x); }
 
 // Second launch of a forward step: both cells' gate math and, behind the global cell's, the context attention of the NEXT
 // step.  Blocks [0, party_blocks) run the party gate body (1024 elements each); block party_blocks + b owns dialogue b:
@@ -450,8 +542,8 @@ __global__ __launch_bounds__(DR_AT) void drnn_attn_fwd_kernel(AttnArgs a) { drnn
 // was written by this very workgroup: a workgroup-scope fence + barrier orders it).
 // (PARTY = 2: the listener path's party gate, which leaves the blend to drnn_listener_fwd_kernel)
 struct GateAttnArgs { GateArgs g, p; AttnArgs at; int party_blocks, has_attn; };
-template <int PARTY>
-__device__ __forceinline__ void drnn_gates_attn_fwd_body(const GateAttnArgs& a) {
+template <int PARTY, int ATT = ATT_GENERAL>
+__device__ __forceinline__ void drnn_gates_attn_fwd_body(const GateAttnArgs& a, const AttnX* x = nullptr) {
     if ((int)blockIdx.x < a.party_blocks) {
         gru_gate_fwd_body<PARTY>(a.p, a.p.d[blockIdx.z], blockIdx.x * DR_AT + threadIdx.x);
         return;
@@ -461,10 +553,19 @@ __device__ __forceinline__ void drnn_gates_attn_fwd_body(const GateAttnArgs& a) 
     if (!a.has_attn) return;
     __threadfence_block();
     __syncthreads();
-    drnn_attn_fwd_body(a.at, a.at.d[blockIdx.z], b);
+    if constexpr (ATT == ATT_CONCAT) {      // P_{t-1} = W_g g_{t-1} of the row just written, before the scores of step t read it
+        drnn_concat_project(*x, x->d[blockIdx.z], a.at.d[blockIdx.z].G, a.at.B, a.at.H, b, a.at.t - 1, threadIdx.x & 63, threadIdx.x >> 6);
+        __threadfence_block();
+        __syncthreads();
+    }
+    drnn_attn_fwd_body<ATT>(a.at, a.at.d[blockIdx.z], b, x);
 }
 __global__ __launch_bounds__(DR_AT) void drnn_gates_attn_fwd_kernel(GateAttnArgs a) { drnn_gates_attn_fwd_body<1>(a); }
 __global__ __launch_bounds__(DR_AT) void drnn_gates_attn_lfwd_kernel(GateAttnArgs a) { drnn_gates_attn_fwd_body<2>(a); }
+// general2 / concat: the same launch with the attention type's own arguments (PARTY 1: listener-free, 2: listener)
+struct GateAttnXArgs { GateAttnArgs a; AttnX x; };
+template <int PARTY, int ATT>
+__global__ __launch_bounds__(DR_AT) void drnn_gates_attnx_fwd_kernel(GateAttnXArgs a) { drnn_gates_attn_fwd_body<PARTY, ATT>(a.a, &a.x); }
 
 struct AttnBwdDir {
     const float* dCT;    // [B x H]
@@ -476,7 +577,8 @@ struct AttnBwdDir {
 };
 struct AttnBwdArgs { AttnBwdDir d[2]; int B, H, S, t; };
 
-__device__ __forceinline__ void drnn_attn_bwd_body(const AttnBwdArgs& a, const AttnBwdDir& d, const int b) {
+template <int ATT>
+__device__ __forceinline__ void drnn_attn_bwd_body(const AttnBwdArgs& a, const AttnBwdDir& d, const int b, const AttnX* x = nullptr) {
     __shared__ float da[DR_MAXS + 16];
     __shared__ float al[DR_MAXS + 16];
     __shared__ float red[2];
@@ -485,6 +587,8 @@ __device__ __forceinline__ void drnn_attn_bwd_body(const AttnBwdArgs& a, const A
     const float* dc = d.dCT + (size_t)b * a.H;
     drnn_scores(dc, d.G, a.B, a.H, b, t, da, lane, w);                 // d alpha_j = <dc, g_j>
     if (tid < t) al[tid] = d.alpha[((size_t)b * a.S + t) * a.S + tid];
+    float ts = 0.f;
+    if (ATT == ATT_GENERAL2 && tid < t) ts = x->d[blockIdx.z].TS[((size_t)b * a.S + t) * a.S + tid];
     __syncthreads();
     float dot = tid < t ? al[tid] * da[tid] : 0.f;
     dot = wave_sum(dot);
@@ -492,53 +596,123 @@ __device__ __forceinline__ void drnn_attn_bwd_body(const AttnBwdArgs& a, const A
     __syncthreads();
     const float tot = red[0] + red[1];
     __syncthreads();
-    if (tid < t) da[tid] = al[tid] * (da[tid] - tot);                  // d score_j
+    if (tid < t) {
+        if (ATT == ATT_GENERAL2) da[tid] = al[tid] * (da[tid] - tot) * (1.0f - ts * ts);      // through the tanh
+        else da[tid] = al[tid] * (da[tid] - tot);                      // d score_j
+    }
     __syncthreads();
     // dXA_k = sum_j dscore_j g_j[k];  dG[j][k] += alpha_j dc_k + dscore_j x_k.  Thread (k, half) owns column k of its half of
-    // the history: no other thread touches those dG elements (no race, no atomics).
+    // the history: no other thread touches those dG elements (no race, no atomics).  (concat: the score path goes through P)
     const int k = tid & 511, half = tid >> 9, jmid = (t + 1) >> 1;
     const int jb = half ? jmid : 0, je = half ? t : jmid;
     float dx = 0.f;
     if (k < a.H) {
-        const float dck = dc[k], xk = d.XA[(size_t)b * a.H + k];
+        const float dck = dc[k], xk = ATT == ATT_CONCAT ? 0.f : d.XA[(size_t)b * a.H + k];
         const size_t st = (size_t)a.B * a.H, base = ((size_t)a.B + b) * a.H + k;
         for (int j = jb; j < je; j += 8) {
             float g[8], og[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const size_t o = base + (size_t)min(j + u, je - 1) * st;
-                g[u] = d.G[o];
+                if (ATT != ATT_CONCAT) g[u] = d.G[o];
                 og[u] = d.dG[o];
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 if (j + u < je) {
-                    dx += da[j + u] * g[u];
-                    d.dG[base + (size_t)(j + u) * st] = og[u] + al[j + u] * dck + da[j + u] * xk;
+                    if (ATT == ATT_CONCAT) {
+                        d.dG[base + (size_t)(j + u) * st] = og[u] + al[j + u] * dck;
+                    } else {
+                        dx += da[j + u] * g[u];
+                        d.dG[base + (size_t)(j + u) * st] = og[u] + al[j + u] * dck + da[j + u] * xk;
+                    }
                 }
             }
         }
     }
-    if (half) part[k] = dx;
-    __syncthreads();
-    if (!half && k < a.H) d.dXA[(size_t)b * a.H + k] = dx + part[k];
+    if constexpr (ATT != ATT_CONCAT) {
+        if (half) part[k] = dx;
+        __syncthreads();
+        if (!half && k < a.H) d.dXA[(size_t)b * a.H + k] = dx + part[k];
+    } else {
+        // concat: thread (k, half) owns column k of the D_a-wide rows and its half of the history.
+        //   dz_{j,k} = dscore_j v_k (1 - tanh^2),  dX_t[k] = sum_j dz_{j,k},  dP_j[k] += dz_{j,k},  dv partial[k] = sum_j dscore_j tanh
+        __shared__ float dpt[DR_MAXDA];
+        __shared__ float partv[DR_MAXDA];
+        const AttnXDir& xd = x->d[blockIdx.z];
+        const int Da = x->Da;
+        float dv = 0.f;
+        if (k < Da) {
+            const float xc = xd.XC[((size_t)t * a.B + b) * Da + k], vc = xd.v[k];
+            const size_t st = (size_t)a.B * Da, base = (size_t)b * Da + k;
+            for (int j = jb; j < je; j += 8) {
+                float pv[8], op[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    const size_t o = base + (size_t)min(j + u, je - 1) * st;
+                    pv[u] = xd.P[o];
+                    op[u] = xd.dP[o];
+                }
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    if (j + u < je) {
+                        const float th = tanhf(pv[u] + xc);
+                        const float dz = da[j + u] * vc * (1.0f - th * th);
+                        dx += dz;
+                        dv += da[j + u] * th;
+                        const float np = op[u] + dz;
+                        xd.dP[base + (size_t)(j + u) * st] = np;
+                        if (j + u == t - 1) dpt[k] = np;               // dP_{t-1} is complete: step t is the last reader of g_{t-1}
+                    }
+                }
+            }
+        }
+        if (half && k < Da) { part[k] = dx; partv[k] = dv; }
+        __threadfence_block();
+        __syncthreads();
+        if (!half && k < Da) {
+            xd.dXC[((size_t)t * a.B + b) * Da + k] = dx + part[k];
+            xd.dVp[((size_t)t * a.B + b) * Da + k] = dv + partv[k];
+        }
+        __syncthreads();
+        // dG[g_{t-1}] += W_g^T dP_{t-1} (before the global gate gradient of step t - 1 reads it): thread (k, half) sums its half
+        // of the D_a rows, the halves are added in a fixed order
+        const int amid = (Da + 1) >> 1, ab = half ? amid : 0, ae = half ? Da : amid;
+        float s = 0.f;
+        if (k < a.H) {
+            const float* wk = xd.Wg + k;
+            for (int c = ab; c < ae; c += 8) {
+                float wv[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) wv[u] = wk[(size_t)min(c + u, ae - 1) * x->ldw];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) s += c + u < ae ? wv[u] * dpt[c + u] : 0.f;
+            }
+        }
+        if (half && k < a.H) part[k] = s;
+        __syncthreads();
+        if (!half && k < a.H) {
+            float* dg = d.dG + ((size_t)t * a.B + b) * a.H + k;
+            *dg = *dg + (s + part[k]);
+        }
+    }
 }
-__global__ __launch_bounds__(DR_AT) void drnn_attn_bwd_kernel(AttnBwdArgs a) { drnn_attn_bwd_body(a, a.d[blockIdx.z], blockIdx.x); }
+__global__ __launch_bounds__(DR_AT) void drnn_attn_bwd_kernel(AttnBwdArgs a) { drnn_attn_bwd_body<ATT_GENERAL>(a, a.d[blockIdx.z], blockIdx.x); }
 
 // First launch of a backward step t: the attention backward of step t + 1 (it completes dG row t + 1 of its dialogue),
 // then the global cell's gate gradient of step t on that row, in the workgroup that owns the dialogue; the party cell's
 // gate gradient (independent of both) in blocks [0, party_blocks).
 // (PARTY = 2: the listener path's party gate — dh = d qs assembled by drnn_listener_bwd_kernel, dh2 = d ss)
 struct GateAttnBwdArgs { GateBwdArgs g, p; AttnBwdArgs at; int party_blocks, has_attn; };
-template <int PARTY>
-__device__ __forceinline__ void drnn_gates_attn_bwd_body(const GateAttnBwdArgs& a) {
+template <int PARTY, int ATT = ATT_GENERAL>
+__device__ __forceinline__ void drnn_gates_attn_bwd_body(const GateAttnBwdArgs& a, const AttnX* x = nullptr) {
     if ((int)blockIdx.x < a.party_blocks) {
         gru_gate_bwd_body<PARTY>(a.p, a.p.d[blockIdx.z], blockIdx.x * DR_AT + threadIdx.x);
         return;
     }
     const int b = blockIdx.x - a.party_blocks;
     if (a.has_attn) {
-        drnn_attn_bwd_body(a.at, a.at.d[blockIdx.z], b);
+        drnn_attn_bwd_body<ATT>(a.at, a.at.d[blockIdx.z], b, x);
         __threadfence_block();
         __syncthreads();
     }
@@ -546,6 +720,38 @@ __device__ __forceinline__ void drnn_gates_attn_bwd_body(const GateAttnBwdArgs& 
 }
 __global__ __launch_bounds__(DR_AT) void drnn_gates_attn_bwd_kernel(GateAttnBwdArgs a) { drnn_gates_attn_bwd_body<1>(a); }
 __global__ __launch_bounds__(DR_AT) void drnn_gates_attn_lbwd_kernel(GateAttnBwdArgs a) { drnn_gates_attn_bwd_body<2>(a); }
+struct GateAttnXBwdArgs { GateAttnBwdArgs a; AttnX x; };
+template <int PARTY, int ATT>
+__global__ __launch_bounds__(DR_AT) void drnn_gates_attnx_bwd_kernel(GateAttnXBwdArgs a) { drnn_gates_attn_bwd_body<PARTY, ATT>(a.a, &a.x); }
+
+// small helpers of the other attention types (once per call, outside the step chain)
+// simple: the constant query w in every row of XA
+__global__ __launch_bounds__(256) void drnn_bcast_row_kernel(const float* __restrict__ w, float* __restrict__ out, int64_t rows, int cols) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < rows * cols) out[i] = w[i % cols];
+}
+// dot: dU += dXA (the query is U_t itself)
+__global__ __launch_bounds__(256) void drnn_add_kernel(float* __restrict__ dst, const float* __restrict__ src, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) dst[i] += src[i];
+}
+// out[c] += sum_r A[r][c] in a fixed order (16 waves take rows w, w + 16, ...; the waves are added in order): simple's dw,
+// concat's dv
+__global__ __launch_bounds__(1024) void drnn_colsum_kernel(const float* __restrict__ A, int rows, int cols, float* __restrict__ out) {
+    __shared__ float part[16][64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = blockIdx.x * 64 + lane;
+    float s = 0.f;
+    if (c < cols)
+        for (int r = w; r < rows; r += 16) s += A[(size_t)r * cols + c];
+    part[w][lane] = s;
+    __syncthreads();
+    if (w == 0 && c < cols) {
+        float o = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) o += part[i][lane];
+        out[c] += o;
+    }
+}
 
 // ------------------------------------------------------------------------------------------
 // Listener state (listener_state = True, model.py:899-921): every party row also takes a listener GRU step
@@ -888,6 +1094,29 @@ static DrnnLWs drnn_lws(const ganffn_drnn_cfg* c) {
     return w;
 }
 
+// other attention types: regions behind the listener-free (or listener) ones, whose offsets do not move
+struct DrnnASaved { int64_t TS, XC, P, total; };
+static DrnnASaved drnn_asaved(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, bool listener) {
+    DrnnASaved s{-1, -1, -1, 0};
+    const int64_t T = (int64_t)c->S * c->B, Da = at->Da;
+    int64_t p = listener ? drnn_lsaved(c).total : drnn_saved(c).total;
+    auto take = [&](int64_t n) { int64_t r = p; p += (n + 3) & ~int64_t(3); return r; };
+    if (at->type == GANFFN_DRNN_ATT_GENERAL2) s.TS = take((int64_t)c->B * c->S * c->S);
+    if (at->type == GANFFN_DRNN_ATT_CONCAT) { s.XC = take(T * Da); s.P = take(T * Da); }
+    s.total = p;
+    return s;
+}
+struct DrnnAWs { int64_t dXC, dP, dVp, total; };
+static DrnnAWs drnn_aws(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, bool listener) {
+    DrnnAWs w{-1, -1, -1, 0};
+    const int64_t T = (int64_t)c->S * c->B, Da = at->Da;
+    int64_t p = listener ? drnn_lws(c).total : drnn_ws(c).total;
+    auto take = [&](int64_t n) { int64_t r = p; p += (n + 3) & ~int64_t(3); return r; };
+    if (at->type == GANFFN_DRNN_ATT_CONCAT) { w.dXC = take(T * Da); w.dP = take(T * Da); w.dVp = take(T * Da); }
+    w.total = p;
+    return w;
+}
+
 static int check_drnn(const ganffn_drnn_cfg* c, int ndir) {
     GF_CHECK_ARG(c, "null drnn cfg");
     GF_CHECK_ARG(ndir == 1 || ndir == 2, "drnn: ndir=%d", ndir);
@@ -896,6 +1125,26 @@ static int check_drnn(const ganffn_drnn_cfg* c, int ndir) {
                  "drnn: D_m=%d, D_g=D_p=%d, D_e=%d must be multiples of 4", c->Dm, c->H, c->He);
     GF_CHECK_ARG(c->H <= 512, "drnn: D_g = D_p = %d > 512 (attention kernels hold one column per thread)", c->H);
     GF_CHECK_ARG(c->p >= 0.f && c->p < 1.f, "drnn: dropout p out of [0,1)");
+    return 0;
+}
+
+static int check_att(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at) {
+    GF_CHECK_ARG(at, "drnn_att: null attention descriptor");
+    GF_CHECK_ARG(at->type >= GANFFN_DRNN_ATT_GENERAL && at->type <= GANFFN_DRNN_ATT_CONCAT,
+                 "drnn_att: unknown attention type %d (0 general, 1 simple, 2 dot, 3 general2, 4 concat)", at->type);
+    GF_CHECK_ARG(at->type != GANFFN_DRNN_ATT_CONCAT || (at->Da >= 4 && at->Da <= DR_MAXDA && (at->Da & 3) == 0),
+                 "drnn_att: concat needs D_a a multiple of 4 in [4, %d], got D_a=%d", DR_MAXDA, at->Da);
+    GF_CHECK_ARG(at->type != GANFFN_DRNN_ATT_DOT || c->Dm == c->H, "drnn_att: dot attention needs D_m == D_g, got D_m=%d D_g=%d",
+                 c->Dm, c->H);
+    return 0;
+}
+static int check_att_params(const ganffn_drnn_att* at, const ganffn_drnn_att_params* ap, int ndir) {
+    GF_CHECK_ARG(ap || at->type == GANFFN_DRNN_ATT_DOT, "drnn_att: null attention parameters");
+    for (int z = 0; z < ndir && at->type != GANFFN_DRNN_ATT_DOT; ++z) {
+        GF_CHECK_ARG(ap[z].w && aligned16(ap[z].w), "drnn_att: direction %d: null or misaligned attention weight", z);
+        GF_CHECK_ARG(at->type != GANFFN_DRNN_ATT_GENERAL2 || ap[z].b, "drnn_att: direction %d: general2 needs transform.bias", z);
+        GF_CHECK_ARG(at->type != GANFFN_DRNN_ATT_CONCAT || ap[z].v, "drnn_att: direction %d: concat needs vector_prod.weight", z);
+    }
     return 0;
 }
 
@@ -923,16 +1172,32 @@ extern "C" int64_t ganffn_drnn_saved_floats(const ganffn_drnn_cfg* c) { return c
 extern "C" int64_t ganffn_drnn_workspace_floats(const ganffn_drnn_cfg* c) { return check_drnn(c, 1) ? -1 : drnn_ws(c).total; }
 extern "C" int64_t ganffn_drnn_listener_saved_floats(const ganffn_drnn_cfg* c) { return check_drnn(c, 1) ? -1 : drnn_lsaved(c).total; }
 extern "C" int64_t ganffn_drnn_listener_workspace_floats(const ganffn_drnn_cfg* c) { return check_drnn(c, 1) ? -1 : drnn_lws(c).total; }
+extern "C" int64_t ganffn_drnn_att_saved_floats(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int listener) {
+    return check_drnn(c, 1) || check_att(c, at) ? -1 : drnn_asaved(c, at, listener != 0).total;
+}
+extern "C" int64_t ganffn_drnn_att_workspace_floats(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int listener) {
+    return check_drnn(c, 1) || check_att(c, at) ? -1 : drnn_aws(c, at, listener != 0).total;
+}
 
 // ------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------
 // lp == NULL: listener_state False (ganffn_drnn_fwd); otherwise the listener path (ganffn_drnn_listener_fwd)
+// at == NULL: general attention with prm[z].att_w (ganffn_drnn_fwd / _listener_fwd); otherwise ganffn_drnn_att_fwd
 static int drnn_fwd(const ganffn_drnn_cfg* c, int ndir, const float* const* U, const int32_t* const* spk,
                     const float* const* mval, const ganffn_drnn_params* prm, const ganffn_drnn_listener_params* lp,
                     float* const* e_out, float* const* alpha, float* const* saved, float* const* workspace,
-                    const uint64_t* rng, uint64_t add, void* stream) {
+                    const uint64_t* rng, uint64_t add, void* stream, const ganffn_drnn_att* at = nullptr,
+                    const ganffn_drnn_att_params* ap = nullptr) {
     GF_TRY(check_drnn(c, ndir));
+    const int att = at ? at->type : ATT_GENERAL;
+    if (at) {
+        GF_TRY(check_att(c, at));
+        GF_TRY(check_att_params(at, ap, ndir));
+    }
+    const ganffn_drnn_att gen{ATT_GENERAL, 0};
+    const DrnnASaved sa = drnn_asaved(c, at ? at : &gen, lp != nullptr);
+    const int Da = at ? at->Da : 0;
     GF_CHECK_ARG(U && spk && mval && prm && e_out && alpha && saved && workspace, "drnn_fwd: null pointer");
     GF_CHECK_ARG(!(c->train && c->p > 0.f) || rng, "drnn_fwd: rng required in train mode");
     hipStream_t st = (hipStream_t)stream;
@@ -955,7 +1220,22 @@ static int drnn_fwd(const ganffn_drnn_cfg* c, int ndir, const float* const* U, c
         e.bias = prm[z].p_bih;
         GF_TRY(launch_gemm_nt(U[z], Dm, prm[z].p_wih, Dm + H, sv + so.XP, 3 * H, T, 3 * H, Dm, EPI_NONE, e, st));
         e.bias = nullptr;
-        GF_TRY(launch_gemm_nt(U[z], Dm, prm[z].att_w, Dm, sv + so.XA, H, T, H, Dm, EPI_NONE, e, st));
+        const float* aw = at ? (ap ? ap[z].w : nullptr) : prm[z].att_w;
+        if (att == ATT_GENERAL) {
+            GF_TRY(launch_gemm_nt(U[z], Dm, aw, Dm, sv + so.XA, H, T, H, Dm, EPI_NONE, e, st));
+        } else if (att == ATT_GENERAL2) {          // query W U_t + b
+            e.bias = ap[z].b;
+            GF_TRY(launch_gemm_nt(U[z], Dm, aw, Dm, sv + so.XA, H, T, H, Dm, EPI_NONE, e, st));
+            e.bias = nullptr;
+        } else if (att == ATT_DOT) {               // query U_t itself (D_m == D_g)
+            hipError_t er = hipMemcpyAsync(sv + so.XA, U[z], (size_t)T * H * sizeof(float), hipMemcpyDeviceToDevice, st);
+            if (er != hipSuccess) return fail((int)er, "drnn_fwd: memcpy failed: %s", hipGetErrorString(er));
+        } else if (att == ATT_SIMPLE) {            // constant query w
+            hipLaunchKernelGGL(drnn_bcast_row_kernel, dim3((unsigned)(((int64_t)T * H + 255) / 256)), dim3(256), 0, st, aw, sv + so.XA, (int64_t)T, H);
+            GF_LAUNCH_CHECK();
+        } else {                                   // concat: X = U W_u^T, W_u = transform.weight[:, D_g:]
+            GF_TRY(launch_gemm_nt(U[z], Dm, aw + H, H + Dm, sv + sa.XC, Da, T, Da, Dm, EPI_NONE, e, st));
+        }
         if (lp) {      // listener: XL = U Wih_l[:, :Dm]^T + bih_l
             e.bias = lp[z].l_bih;
             GF_TRY(launch_gemm_nt(U[z], Dm, lp[z].l_wih, Dm + H, sv + sl.XL, 3 * H, T, 3 * H, Dm, EPI_NONE, e, st));
@@ -1008,12 +1288,27 @@ static int drnn_fwd(const ganffn_drnn_cfg* c, int ndir, const float* const* U, c
         gaa.at.B = B; gaa.at.H = H; gaa.at.S = S; gaa.at.t = t + 1;
         for (int z = 0; z < ndir; ++z)
             gaa.at.d[z] = AttnDir{saved[z] + so.XA + r1 * H, saved[z] + so.G, saved[z] + so.CT + r1 * H, alpha[z]};
-        if (!lp) {
+        const dim3 gA(gaa.party_blocks + B, 1, ndir);
+        if (att == ATT_GENERAL2 || att == ATT_CONCAT) {
+            GateAttnXArgs gx;
+            gx.a = gaa;
+            gx.x.ldw = H + Dm; gx.x.Da = Da;
+            for (int z = 0; z < ndir; ++z)
+                gx.x.d[z] = AttnXDir{att == ATT_GENERAL2 ? saved[z] + sa.TS : nullptr, att == ATT_CONCAT ? saved[z] + sa.P : nullptr,
+                                     att == ATT_CONCAT ? saved[z] + sa.XC : nullptr, ap[z].w, ap[z].v, nullptr, nullptr, nullptr};
+            if (att == ATT_GENERAL2 && !lp) hipLaunchKernelGGL((drnn_gates_attnx_fwd_kernel<1, ATT_GENERAL2>), gA, dim3(DR_AT), 0, st, gx);
+            else if (att == ATT_GENERAL2) hipLaunchKernelGGL((drnn_gates_attnx_fwd_kernel<2, ATT_GENERAL2>), gA, dim3(DR_AT), 0, st, gx);
+            else if (!lp) hipLaunchKernelGGL((drnn_gates_attnx_fwd_kernel<1, ATT_CONCAT>), gA, dim3(DR_AT), 0, st, gx);
+            else hipLaunchKernelGGL((drnn_gates_attnx_fwd_kernel<2, ATT_CONCAT>), gA, dim3(DR_AT), 0, st, gx);
+            GF_LAUNCH_CHECK();
+        } else if (!lp) {
             hipLaunchKernelGGL(drnn_gates_attn_fwd_kernel, dim3(gaa.party_blocks + B, 1, ndir), dim3(DR_AT), 0, st, gaa);
             GF_LAUNCH_CHECK();
         } else {
             hipLaunchKernelGGL(drnn_gates_attn_lfwd_kernel, dim3(gaa.party_blocks + B, 1, ndir), dim3(DR_AT), 0, st, gaa);
             GF_LAUNCH_CHECK();
+        }
+        if (lp) {
             // ---- listener: GI_l = XL[t] + QSP[t] Wih_l[:, Dm:]^T ; GH_l[p] = Q[t][p] Whh_l^T + bhh_l (p = 0, 1)
             for (int z = 0; z < ndir; ++z) {
                 float* sv = saved[z]; float* ws = workspace[z];
@@ -1098,8 +1393,18 @@ static int drnn_bwd(const ganffn_drnn_cfg* c, int ndir, const float* const* d_e,
                     const int32_t* const* spk, const float* const* mval, const ganffn_drnn_params* prm,
                     const ganffn_drnn_listener_params* lp, const ganffn_drnn_grads* grd, const ganffn_drnn_listener_grads* lg,
                     float* const* dU, const float* const* alpha, const float* const* saved, float* const* workspace,
-                    const uint64_t* rng, uint64_t add, void* stream) {
+                    const uint64_t* rng, uint64_t add, void* stream, const ganffn_drnn_att* at = nullptr,
+                    const ganffn_drnn_att_params* ap = nullptr, const ganffn_drnn_att_grads* ag = nullptr) {
     GF_TRY(check_drnn(c, ndir));
+    const int att = at ? at->type : ATT_GENERAL;
+    if (at) {
+        GF_TRY(check_att(c, at));
+        GF_TRY(check_att_params(at, ap, ndir));
+    }
+    const ganffn_drnn_att gen{ATT_GENERAL, 0};
+    const DrnnASaved sa = drnn_asaved(c, at ? at : &gen, lp != nullptr);
+    const DrnnAWs wa = drnn_aws(c, at ? at : &gen, lp != nullptr);
+    const int Da = at ? at->Da : 0;
     GF_CHECK_ARG(d_e && U && spk && mval && prm && grd && dU && alpha && saved && workspace, "drnn_bwd: null pointer");
     GF_CHECK_ARG(!(c->train && c->p > 0.f) || rng, "drnn_bwd: rng required in train mode");
     hipStream_t st = (hipStream_t)stream;
@@ -1118,6 +1423,11 @@ static int drnn_bwd(const ganffn_drnn_cfg* c, int ndir, const float* const* d_e,
         GF_TRY(memset_f(ws + wo.dQa, (int64_t)B * 2 * H, st));
         GF_TRY(memset_f(ws + wo.dEa, (int64_t)B * He, st));
         GF_TRY(memset_f(ws + wo.dXA, (int64_t)B * H, st));          // step 0 has no attention: dXA[0] = 0
+        if (att == ATT_CONCAT) {            // dX (row block 0 stays zero), dP (accumulated), v partials (row block 0 stays zero)
+            GF_TRY(memset_f(ws + wa.dXC, (int64_t)T * Da, st));
+            GF_TRY(memset_f(ws + wa.dP, (int64_t)T * Da, st));
+            GF_TRY(memset_f(ws + wa.dVp, (int64_t)T * Da, st));
+        }
     }
     const dim3 gH((B * H + 255) / 256, 1, ndir), gHe((B * He + 255) / 256, 1, ndir);
     const bool echain = He <= EC_MAXHE;
@@ -1246,7 +1556,22 @@ static int drnn_bwd(const ganffn_drnn_cfg* c, int ndir, const float* const* d_e,
         for (int z = 0; z < ndir; ++z)
             gab.at.d[z] = AttnBwdDir{workspace[z] + wo.dCT, saved[z] + so.XA + r1 * H, saved[z] + so.G, alpha[z], workspace[z] + wo.dG,
                                      workspace[z] + wo.dXA + r1 * H};
-        if (!lp) hipLaunchKernelGGL(drnn_gates_attn_bwd_kernel, dim3(gab.party_blocks + B, 1, ndir), dim3(DR_AT), 0, st, gab);
+        if (att == ATT_GENERAL2 || att == ATT_CONCAT) {
+            const dim3 gA(gab.party_blocks + B, 1, ndir);
+            GateAttnXBwdArgs gx;
+            gx.a = gab;
+            gx.x.ldw = H + Dm; gx.x.Da = Da;
+            for (int z = 0; z < ndir; ++z) {
+                float* sv = const_cast<float*>(saved[z]); float* ws = workspace[z];
+                const bool cc = att == ATT_CONCAT;
+                gx.x.d[z] = AttnXDir{cc ? nullptr : sv + sa.TS, cc ? sv + sa.P : nullptr, cc ? sv + sa.XC : nullptr, ap[z].w, ap[z].v,
+                                     cc ? ws + wa.dP : nullptr, cc ? ws + wa.dXC : nullptr, cc ? ws + wa.dVp : nullptr};
+            }
+            if (att == ATT_GENERAL2 && !lp) hipLaunchKernelGGL((drnn_gates_attnx_bwd_kernel<1, ATT_GENERAL2>), gA, dim3(DR_AT), 0, st, gx);
+            else if (att == ATT_GENERAL2) hipLaunchKernelGGL((drnn_gates_attnx_bwd_kernel<2, ATT_GENERAL2>), gA, dim3(DR_AT), 0, st, gx);
+            else if (!lp) hipLaunchKernelGGL((drnn_gates_attnx_bwd_kernel<1, ATT_CONCAT>), gA, dim3(DR_AT), 0, st, gx);
+            else hipLaunchKernelGGL((drnn_gates_attnx_bwd_kernel<2, ATT_CONCAT>), gA, dim3(DR_AT), 0, st, gx);
+        } else if (!lp) hipLaunchKernelGGL(drnn_gates_attn_bwd_kernel, dim3(gab.party_blocks + B, 1, ndir), dim3(DR_AT), 0, st, gab);
         else hipLaunchKernelGGL(drnn_gates_attn_lbwd_kernel, dim3(gab.party_blocks + B, 1, ndir), dim3(DR_AT), 0, st, gab);
         GF_LAUNCH_CHECK();
         // ---- the four dgrad products of the step in one launch
@@ -1272,28 +1597,54 @@ static int drnn_bwd(const ganffn_drnn_cfg* c, int ndir, const float* const* d_e,
         GF_TRY(launch_gemm_nn(ws + wo.dGIg, 3 * H, prm[z].g_wih, Dm + H, dU[z], Dm, T, Dm, 3 * H, EPI_NONE, e0, st));
         e1.aux_in = dU[z];
         GF_TRY(launch_gemm_nn(ws + wo.dGIp, 3 * H, prm[z].p_wih, Dm + H, dU[z], Dm, T, Dm, 3 * H, EPI_NONE, e1, st));
-        GF_TRY(launch_gemm_nn(ws + wo.dXA, H, prm[z].att_w, Dm, dU[z], Dm, T, Dm, H, EPI_NONE, e1, st));
+        const float* aw = at ? (ap ? ap[z].w : nullptr) : prm[z].att_w;
+        if (att == ATT_GENERAL || att == ATT_GENERAL2) {
+            GF_TRY(launch_gemm_nn(ws + wo.dXA, H, aw, Dm, dU[z], Dm, T, Dm, H, EPI_NONE, e1, st));
+        } else if (att == ATT_DOT) {
+            hipLaunchKernelGGL(drnn_add_kernel, dim3((unsigned)(((int64_t)T * Dm + 255) / 256)), dim3(256), 0, st, dU[z], ws + wo.dXA, (int64_t)T * Dm);
+            GF_LAUNCH_CHECK();
+        } else if (att == ATT_CONCAT) {         // dU += dX W_u
+            GF_TRY(launch_gemm_nn(ws + wa.dXC, Da, aw + H, H + Dm, dU[z], Dm, T, Dm, Da, EPI_NONE, e1, st));
+        }
         if (lp) GF_TRY(launch_gemm_nn(ws + wl.dGIl, 3 * H, lp[z].l_wih, Dm + H, dU[z], Dm, T, Dm, 3 * H, EPI_NONE, e1, st));
-        if (g.g_wih) {
-            TnDesc tn[12];
+        float* agw = at ? (ag ? ag[z].w : nullptr) : g.att_w;
+        if (at && agw && att == ATT_SIMPLE) {   // dw = column sum of dXA (the constant query)
+            hipLaunchKernelGGL(drnn_colsum_kernel, dim3((H + 63) / 64), dim3(1024), 0, st, ws + wo.dXA, T, H, agw);
+            GF_LAUNCH_CHECK();
+        }
+        if (at && ag && ag[z].v && att == ATT_CONCAT) {   // dv: the per-step partials in a fixed order
+            hipLaunchKernelGGL(drnn_colsum_kernel, dim3((Da + 63) / 64), dim3(1024), 0, st, ws + wa.dVp, T, Da, ag[z].v);
+            GF_LAUNCH_CHECK();
+        }
+        if (g.g_wih || (at && agw)) {
+            TnDesc tn[16];
             int n = 0;
-            tn[n++] = TnDesc{ws + wo.dGIg, 3 * H, U[z], Dm, g.g_wih, Dm + H, g.g_bih, 3 * H, Dm, T};
-            tn[n++] = TnDesc{ws + wo.dGIg, 3 * H, sv + so.QS, H, g.g_wih + Dm, Dm + H, nullptr, 3 * H, H, T};
-            tn[n++] = TnDesc{ws + wo.dGHg, 3 * H, sv + so.G, H, g.g_whh, H, g.g_bhh, 3 * H, H, T};
-            tn[n++] = TnDesc{ws + wo.dGIp, 3 * H, U[z], Dm, g.p_wih, Dm + H, g.p_bih, 3 * H, Dm, T};
-            tn[n++] = TnDesc{ws + wo.dGIp, 3 * H, sv + so.CT, H, g.p_wih + Dm, Dm + H, nullptr, 3 * H, H, T};
-            tn[n++] = TnDesc{ws + wo.dGHp, 3 * H, sv + so.QS, H, g.p_whh, H, g.p_bhh, 3 * H, H, T};
-            tn[n++] = TnDesc{ws + wo.dGIe, 3 * He, sv + so.QN, H, g.e_wih, H, g.e_bih, 3 * He, H, T};
-            tn[n++] = TnDesc{ws + wo.dGHe, 3 * He, sv + so.E, He, g.e_whh, He, g.e_bhh, 3 * He, He, T};
-            tn[n++] = TnDesc{ws + wo.dXA, H, U[z], Dm, g.att_w, Dm, nullptr, H, Dm, T};
-            if (lp && lg && lg[z].l_wih) {
+            if (g.g_wih) {
+                tn[n++] = TnDesc{ws + wo.dGIg, 3 * H, U[z], Dm, g.g_wih, Dm + H, g.g_bih, 3 * H, Dm, T};
+                tn[n++] = TnDesc{ws + wo.dGIg, 3 * H, sv + so.QS, H, g.g_wih + Dm, Dm + H, nullptr, 3 * H, H, T};
+                tn[n++] = TnDesc{ws + wo.dGHg, 3 * H, sv + so.G, H, g.g_whh, H, g.g_bhh, 3 * H, H, T};
+                tn[n++] = TnDesc{ws + wo.dGIp, 3 * H, U[z], Dm, g.p_wih, Dm + H, g.p_bih, 3 * H, Dm, T};
+                tn[n++] = TnDesc{ws + wo.dGIp, 3 * H, sv + so.CT, H, g.p_wih + Dm, Dm + H, nullptr, 3 * H, H, T};
+                tn[n++] = TnDesc{ws + wo.dGHp, 3 * H, sv + so.QS, H, g.p_whh, H, g.p_bhh, 3 * H, H, T};
+                tn[n++] = TnDesc{ws + wo.dGIe, 3 * He, sv + so.QN, H, g.e_wih, H, g.e_bih, 3 * He, H, T};
+                tn[n++] = TnDesc{ws + wo.dGHe, 3 * He, sv + so.E, He, g.e_whh, He, g.e_bhh, 3 * He, He, T};
+            }
+            if (att == ATT_GENERAL && (at ? agw != nullptr : g.g_wih != nullptr))
+                tn[n++] = TnDesc{ws + wo.dXA, H, U[z], Dm, agw, Dm, nullptr, H, Dm, T};
+            if (att == ATT_GENERAL2 && agw)             // transform.bias: the column sum of dXA
+                tn[n++] = TnDesc{ws + wo.dXA, H, U[z], Dm, agw, Dm, ag[z].b, H, Dm, T};
+            if (att == ATT_CONCAT && agw) {            // dW_g = sum dP^T g, dW_u = sum dX^T U: the two column blocks of transform.weight
+                tn[n++] = TnDesc{ws + wa.dP, Da, saved[z] + so.G + (int64_t)B * H, H, agw, H + Dm, nullptr, Da, H, T};
+                tn[n++] = TnDesc{ws + wa.dXC, Da, U[z], Dm, agw + H, H + Dm, nullptr, Da, Dm, T};
+            }
+            if (g.g_wih && lp && lg && lg[z].l_wih) {
                 // listener: input side against [U, qs] (party-summed dGI_l), hidden side against Q[t][p] (2T rows)
                 const ganffn_drnn_listener_grads& l = lg[z];
                 tn[n++] = TnDesc{ws + wl.dGIl, 3 * H, U[z], Dm, l.l_wih, Dm + H, l.l_bih, 3 * H, Dm, T};
                 tn[n++] = TnDesc{ws + wl.dGIl, 3 * H, sv + sl.QSP, H, l.l_wih + Dm, Dm + H, nullptr, 3 * H, H, T};
                 tn[n++] = TnDesc{ws + wl.dGHl, 3 * H, sv + so.Q, H, l.l_whh, H, l.l_bhh, 3 * H, H, 2 * T};
             }
-            GF_TRY(launch_gemm_tn_grouped(tn, n, st));
+            if (n) GF_TRY(launch_gemm_tn_grouped(tn, n, st));
         }
     }
     return 0;
@@ -1314,4 +1665,24 @@ extern "C" int ganffn_drnn_listener_bwd(const ganffn_drnn_cfg* c, int ndir, cons
                                         void* stream) {
     GF_CHECK_ARG(lprm, "drnn_listener_bwd: null listener parameters");
     return drnn_bwd(c, ndir, d_e, U, spk, mval, prm, lprm, grd, lgrd, dU, alpha, saved, workspace, rng, add, stream);
+}
+
+// other context attention types (general, simple, dot, general2, concat), with (lprm != NULL) or without listener state
+extern "C" int ganffn_drnn_att_fwd(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int ndir, const float* const* U,
+                                   const int32_t* const* spk, const float* const* mval, const ganffn_drnn_params* prm,
+                                   const ganffn_drnn_listener_params* lprm, const ganffn_drnn_att_params* aprm,
+                                   float* const* e_out, float* const* alpha, float* const* saved, float* const* workspace,
+                                   const uint64_t* rng, uint64_t add, void* stream) {
+    GF_CHECK_ARG(at, "drnn_att_fwd: null attention descriptor");
+    return drnn_fwd(c, ndir, U, spk, mval, prm, lprm, e_out, alpha, saved, workspace, rng, add, stream, at, aprm);
+}
+extern "C" int ganffn_drnn_att_bwd(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int ndir, const float* const* d_e,
+                                   const float* const* U, const int32_t* const* spk, const float* const* mval,
+                                   const ganffn_drnn_params* prm, const ganffn_drnn_listener_params* lprm,
+                                   const ganffn_drnn_att_params* aprm, const ganffn_drnn_grads* grd,
+                                   const ganffn_drnn_listener_grads* lgrd, const ganffn_drnn_att_grads* agrd, float* const* dU,
+                                   const float* const* alpha, const float* const* saved, float* const* workspace,
+                                   const uint64_t* rng, uint64_t add, void* stream) {
+    GF_CHECK_ARG(at, "drnn_att_bwd: null attention descriptor");
+    return drnn_bwd(c, ndir, d_e, U, spk, mval, prm, lprm, grd, lgrd, dU, alpha, saved, workspace, rng, add, stream, at, aprm, agrd);
 }

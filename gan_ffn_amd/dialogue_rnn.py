@@ -5,11 +5,12 @@ Mirrors the module interface of /root/reference/model.py:134-194 (MatchingAttent
 (DialogueRNNCell, DialogueRNN, BiModel) and :1465-1528 (GAN_FFN_DialogueRNN): same constructor arguments, same
 parameter names and shapes (reference state_dicts load), same forward signatures and return tuples.
 
-On the GPU, with general or simple context attention, with or without listener state (the reference script's
---active-listener), the recurrence is the HIP path of csrc/dialogue_rnn.hip (ops.DialogueRNNFn: both directions of BiModel
-through one chain of launches, forward and backward; ops.dialogue_rnn_supported / dialogue_rnn_listener_supported say
-when); the other attention types (dot, general2, concat) and CPU tensors take the torch-op restatement below, which is
-also what the reference-fixture parity tests pin.  The pieces with no sequential dependence are batched:
+On the GPU, with every context attention type (general, simple, dot, general2, concat — the reference script's
+--attention), with or without listener state (--active-listener), the recurrence is the HIP path of csrc/dialogue_rnn.hip
+(ops.DialogueRNNFn: both directions of BiModel through one chain of launches, forward and backward;
+ops.dialogue_rnn_supported / dialogue_rnn_listener_supported say when: D_g = D_p <= 512, dot with D_m = D_g, concat with
+D_a % 4 == 0 and D_a <= 512, at most 112 steps); CPU tensors and shapes outside those limits take the torch-op
+restatement below, which is also what the reference-fixture parity tests pin.  The pieces with no sequential dependence are batched:
   * party selection is a gather, sequence reversal one index gather per tensor (the reference loops over dialogues),
   * BiModel's second attention — one masked `general2` MatchingAttention query per time step in the reference — is ONE
     batched masked attention over all (dialogue, query step) pairs (`general2_all_queries`).
@@ -150,7 +151,7 @@ class DialogueRNN(nn.Module):
         """U (S, B, D_m), qmask (S, B, P) -> emotions (S, B, D_e), [alpha_t (B, t)] for t >= 1"""
         from . import ops
         if _hip_recurrence(ops, self.dialogue_cell, U, qmask):
-            # the HIP recurrence (csrc/dialogue_rnn.hip): the configuration train_IEMOCAP_DialogueRNN.py runs
+            # the HIP recurrence (csrc/dialogue_rnn.hip): every attention type, with or without listener state
             return ops.dialogue_rnn_run([self.dialogue_cell], [U], [qmask], self.training)[0]
         S, B, P = qmask.shape
         g_steps, e_steps, alpha = [], [], []

@@ -1008,9 +1008,12 @@ class DrnnEngine(GanEngine):
     (lr, L2-coupled weight decay; train_IEMOCAP_DialogueRNN.py:746) on flat slabs: one fused launch per generator and one
     for the whole head.  Data-parallel: the generators' gradients go through the bucketed GradReducer (all-reduce of a
     bucket overlaps the rest of that generator's backward, Adam per bucket), the head's slab is one more bucket.
-    Supports the configuration the reference script trains (general context attention, two parties), with or without
-    listener state (--active-listener: ganffn_drnn_listener_fwd / _bwd, the 4 l_cell tensors per direction at the end of the
-    head slab); the module path (model.GAN_FFN_DialogueRNN.forward under autograd) stays available for everything else."""
+    Supports every context attention type of the reference script's --attention (general — the trained configuration —,
+    simple, dot, general2, concat; two parties), with or without listener state (--active-listener: ganffn_drnn_listener_fwd /
+    _bwd, the 4 l_cell tensors per direction at the end of the head slab).  general runs ganffn_drnn_fwd / _bwd with the slab
+    layout it always had; the other types run ganffn_drnn_att_fwd / _bwd with their attention tensors in the cell block
+    (ops.DRNN_ATT_KEYS: named_parameters order).  The module path (model.GAN_FFN_DialogueRNN.forward under autograd) stays
+    available for what the kernels cannot run (D_g != D_p, D_g > 512, dot with D_m != D_g, concat D_a limits)."""
 
     def __init__(self, net, lr=1e-4, weight_decay=1e-5, class_weights=CLASS_WEIGHTS, process_group=None, n_buckets=3,
                  n_streams=1):
@@ -1018,10 +1021,17 @@ class DrnnEngine(GanEngine):
         self.module = net
         bm = net.bi_model
         cf, cr = bm.dialog_rnn_f.dialogue_cell, bm.dialog_rnn_r.dialogue_cell
-        if getattr(cf.attention, "att_type", None) != "general" or cf.D_g != cf.D_p or cf.D_g > 512:
-            raise ValueError("DrnnEngine runs general context attention with D_g = D_p <= 512 only (with or without listener "
-                             "state); use the module path for the other variants")
+        if cf.D_g != cf.D_p or cf.D_g > 512 or cf.D_g % 4 or not ops.drnn_att_limits_hold(cf):
+            raise ValueError("DrnnEngine runs every context attention type (general, simple, dot, general2, concat) within the "
+                             "recurrence kernels' limits: D_g = D_p <= 512 (multiples of 4), dot only with D_m = D_g, concat "
+                             "only with D_a a multiple of 4 and <= 512; got %s attention, D_m = %d, D_g = %d, D_p = %d — use "
+                             "the module path for the rest" % (ops.drnn_att_type(cf), cf.D_m, cf.D_g, cf.D_p))
         self.listener = bool(cf.listener_state)
+        self.att = ops.drnn_att_type(cf)
+        self.att_keys = ops.DRNN_ATT_KEYS[self.att]
+        self.ncell = 12 + len(self.att_keys)                 # tensors per cell in the slab (13 for general: layout unchanged)
+        self.acfg = _lib.DrnnAtt(_lib.DRNN_ATT_TYPES[self.att],
+                                 int(cf.attention.transform.weight.shape[0]) if self.att == "concat" else 0)
         gens = {"acoustic": net.acoustic_generator, "visual": net.visual_generator, "text": net.text_generator}
         self.G = {k: NetState(m, lr, (0.9, 0.999), weight_decay) for k, m in gens.items()}
         self.D = {}
@@ -1035,7 +1045,7 @@ class DrnnEngine(GanEngine):
         plist = []
         for cell in (cf, cr):
             sd = dict(cell.named_parameters())
-            plist += [sd[k] for k in ops.DRNN_KEYS]
+            plist += [sd[k] for k in ops.DRNN_KEYS[:12] + self.att_keys]
         plist += [bm.matchatt.transform.weight, bm.matchatt.transform.bias, bm.linear.weight, bm.linear.bias,
                   bm.smax_fc.weight, bm.smax_fc.bias]
         if self.listener:                    # behind the head tensors: the listener-free slab layout does not move
@@ -1090,7 +1100,10 @@ class DrnnEngine(GanEngine):
             self.ws3 = {k: torch.empty(p_.n_ws, **f32) for k, p_ in self.pass_G.items()}     # one workspace per generator stream
             cfgc = _lib.DrnnCfg(cS, cB, self.Dm, self.H, self.He, self.p_rec, 1)
             lib = _lib.load()
-            if self.listener:
+            if self.att != "general":
+                n_saved = int(lib.ganffn_drnn_att_saved_floats(C.byref(cfgc), C.byref(self.acfg), int(self.listener)))
+                n_ws = int(lib.ganffn_drnn_att_workspace_floats(C.byref(cfgc), C.byref(self.acfg), int(self.listener)))
+            elif self.listener:
                 n_saved = int(lib.ganffn_drnn_listener_saved_floats(C.byref(cfgc)))
                 n_ws = int(lib.ganffn_drnn_listener_workspace_floats(C.byref(cfgc)))
             else:
@@ -1130,17 +1143,22 @@ class DrnnEngine(GanEngine):
         out = []
         for z in range(2):
             s = _lib.DrnnPtrs()
-            for j, name in enumerate(_lib.DRNN_PARAM_FIELDS):
-                setattr(s, name, self._hp(13 * z + j, grad).data_ptr())
+            for j, name in enumerate(_lib.DRNN_PARAM_FIELDS[:self.ncell]):       # (other types: att_w stays NULL)
+                setattr(s, name, self._hp(self.ncell * z + j, grad).data_ptr())
             out.append(s)
         return (_lib.DrnnPtrs * 2)(*out)
+
+    def _drnn_att_ptrs(self, grad):
+        n = len(self.att_keys)
+        return (_lib.DrnnAttPtrs * 2)(*[ops._att_ptrs(self.att, [self._hp(self.ncell * z + 12 + i, grad) for i in range(n)])
+                                        for z in range(2)])
 
     def _drnn_listener_ptrs(self, grad):
         out = []
         for z in range(2):
             s = _lib.DrnnListenerPtrs()
             for j, name in enumerate(_lib.DRNN_LISTENER_FIELDS):
-                setattr(s, name, self._hp(32 + 4 * z + j, grad).data_ptr())
+                setattr(s, name, self._hp(2 * self.ncell + 6 + 4 * z + j, grad).data_ptr())
             out.append(s)
         return (_lib.DrnnListenerPtrs * 2)(*out)
 
@@ -1232,7 +1250,11 @@ class DrnnEngine(GanEngine):
         U_, spk_, mval_ = arr([f["fusion"], f["rev_U"]]), arr([spk_f, spk_b]), arr([mval_f, mval_b])
         e_, al_, sv_, ws_ = arr([f["e_f"], f["e_b"]]), arr([f["alpha_f"], f["alpha_b"]]), arr([f["saved_f"], f["saved_b"]]), arr([f["ws_f"], f["ws_b"]])
         Pp = self._drnn_ptrs(False)
-        if self.listener:
+        if self.att != "general":
+            LPp = self._drnn_listener_ptrs(False) if self.listener else None
+            _lib.call("ganffn_drnn_att_fwd", C.byref(cfg), C.byref(self.acfg), 2, U_, spk_, mval_, Pp, LPp, self._drnn_att_ptrs(False),
+                      e_, al_, sv_, ws_, P(rng), C.c_uint64(a_rec), st)
+        elif self.listener:
             LPp = self._drnn_listener_ptrs(False)
             _lib.call("ganffn_drnn_listener_fwd", C.byref(cfg), 2, U_, spk_, mval_, Pp, LPp, e_, al_, sv_, ws_, P(rng),
                       C.c_uint64(a_rec), st)
@@ -1242,7 +1264,7 @@ class DrnnEngine(GanEngine):
         tr = 1 if train else 0
         _lib.call("ganffn_drnn_join_fwd", P(f["e_f"]), P(f["e_b"]), P(lens), P(f["emotions"]), S, B, He, C.c_float(self.p_join),
                   C.c_uint32(SITE_JOIN_F), C.c_uint32(SITE_JOIN_B), P(rng), C.c_uint64(a_head), tr, st)
-        w_t, b_t, w_l, b_l, w_s, b_s = (self._hp(26 + j) for j in range(6))
+        w_t, b_t, w_l, b_l, w_s, b_s = (self._hp(2 * self.ncell + j) for j in range(6))
         ops.linear_fwd_raw(f["emotions"], w_t, b_t, f["xq"], T, D2, D2)
         _lib.call("ganffn_general2_attention_fwd", P(f["xq"]), P(f["emotions"]), P(umask), P(f["att"]), P(f["alpha2"]), P(f["tanh_s"]),
                   S, B, D2, st)
@@ -1256,7 +1278,7 @@ class DrnnEngine(GanEngine):
             return self.loss, log_prob
         # ---- backward through the head
         self.h_grad.zero_()
-        g_t, gb_t, g_l, gb_l, g_s, gb_s = (self._hp(26 + j, True) for j in range(6))
+        g_t, gb_t, g_l, gb_l, g_s, gb_s = (self._hp(2 * self.ncell + j, True) for j in range(6))
         ops.linear_bwd_raw(f["dlogits"], f["hidden"], w_s, f["d_hidden"], g_s, gb_s, T, self.Dh2, Cn, f["lin_ws"])
         mscale = 1.0 / (1.0 - self.p_hid) if self.p_hid > 0 else 1.0
         _lib.call("ganffn_mask_pos_inplace", P(f["d_hidden"]), P(f["hidden"]), C.c_float(mscale), C.c_int64(T * self.Dh2), st)
@@ -1270,7 +1292,11 @@ class DrnnEngine(GanEngine):
         # ---- the recurrence backward (weight gradients accumulate into the zeroed head slab)
         Gp = self._drnn_ptrs(True)
         de_, dU_ = arr([f["d_e_f"], f["d_e_b"]]), arr([f["dU_f"], f["dU_b"]])
-        if self.listener:
+        if self.att != "general":
+            _lib.call("ganffn_drnn_att_bwd", C.byref(cfg), C.byref(self.acfg), 2, de_, U_, spk_, mval_, Pp, LPp,
+                      self._drnn_att_ptrs(False), Gp, self._drnn_listener_ptrs(True) if self.listener else None,
+                      self._drnn_att_ptrs(True), dU_, al_, sv_, ws_, P(rng), C.c_uint64(a_rec), st)
+        elif self.listener:
             _lib.call("ganffn_drnn_listener_bwd", C.byref(cfg), 2, de_, U_, spk_, mval_, Pp, LPp, Gp, self._drnn_listener_ptrs(True),
                       dU_, al_, sv_, ws_, P(rng), C.c_uint64(a_rec), st)
         else:

@@ -477,31 +477,62 @@ def _drnn_ptrs(tensors, cls=_lib.DrnnPtrs):
     return s
 
 
+# context attention parameters per type (named_parameters order under attention.), besides general's transform.weight
+DRNN_ATT_KEYS = {"general": ["attention.transform.weight"], "dot": [],
+                 "general2": ["attention.transform.weight", "attention.transform.bias"],
+                 "concat": ["attention.transform.weight", "attention.vector_prod.weight"],
+                 "simple": ["attention.scalar.weight"]}
+
+
+def _att_ptrs(att, tensors):
+    """ganffn_drnn_att_params / _grads of one direction from the type's tensors (DRNN_ATT_KEYS order)"""
+    s = _lib.DrnnAttPtrs()
+    names = {"general": ["w"], "simple": ["w"], "dot": [], "general2": ["w", "b"], "concat": ["w", "v"]}[att]
+    for n, t in zip(names, tensors):
+        setattr(s, n, t.data_ptr() if t is not None else None)
+    return s
+
+
 class DialogueRNNFn(torch.autograd.Function):
-    """ndir (1 or 2) DialogueRNNs (general attention) through one chain of launches.
+    """ndir (1 or 2) DialogueRNNs through one chain of launches.
     apply(cfg_dict, U_0, spk_0, mval_0, *13 params_0 [, U_1, spk_1, mval_1, *13 params_1]) ->
     (e_0 (S,B,D_e), alpha_0 (B,S,S) [, e_1, alpha_1]).  alpha is an inspection output (non-differentiable).
     cfg_dict["listener"] true: listener_state = True (ganffn_drnn_listener_*); every direction then takes 17 parameter tensors,
-    the 13 above followed by l_cell's weight_ih, weight_hh, bias_ih, bias_hh (DRNN_LISTENER_KEYS)."""
+    the 13 above followed by l_cell's weight_ih, weight_hh, bias_ih, bias_hh (DRNN_LISTENER_KEYS).
+    cfg_dict["att"] (default "general"): the context attention type.  Other than general, the 13th tensor (general's
+    transform.weight) is replaced by the type's own DRNN_ATT_KEYS tensors (none for dot, two for general2 and concat) and
+    the call goes through ganffn_drnn_att_* (cfg_dict["Da"]: concat's D_a)."""
 
     @staticmethod
     def forward(ctx, meta, *args):
         listener = bool(meta.get("listener", False))
-        na = 20 if listener else 16
+        att = meta.get("att", "general")
+        n_att = len(DRNN_ATT_KEYS[att])
+        na = 15 + n_att + (4 if listener else 0)
         ndir = len(args) // na
         assert len(args) == na * ndir and ndir in (1, 2)
         U = [_f32c(args[na * z]) for z in range(ndir)]
         spk = [args[na * z + 1].to(torch.int32).contiguous() for z in range(ndir)]
         mval = [_f32c(args[na * z + 2]) for z in range(ndir)]
-        prm = [[_f32c(p) for p in args[na * z + 3:na * z + 16]] for z in range(ndir)]
-        lprm = [[_f32c(p) for p in args[na * z + 16:na * z + 20]] for z in range(ndir)] if listener else None
+        if att == "general":
+            prm = [[_f32c(p) for p in args[na * z + 3:na * z + 16]] for z in range(ndir)]
+            aprm = None
+        else:
+            prm = [[_f32c(p) for p in args[na * z + 3:na * z + 15]] + [None] for z in range(ndir)]
+            aprm = [[_f32c(p) for p in args[na * z + 15:na * z + 15 + n_att]] for z in range(ndir)]
+        l0 = 15 + n_att
+        lprm = [[_f32c(p) for p in args[na * z + l0:na * z + l0 + 4]] for z in range(ndir)] if listener else None
         _need_gpu(*U)
         S, B, Dm = U[0].shape
         H, He = prm[0][1].shape[1], prm[0][9].shape[1]
         train = bool(meta["train"]) and meta["p"] > 0.0
         cfg = _lib.DrnnCfg(S, B, Dm, H, He, float(meta["p"]), 1 if train else 0)
         lib = _lib.load()
-        if listener:
+        acfg = _lib.DrnnAtt(_lib.DRNN_ATT_TYPES[att], int(meta.get("Da", 0)))
+        if aprm is not None:
+            n_saved = int(lib.ganffn_drnn_att_saved_floats(C.byref(cfg), C.byref(acfg), int(listener)))
+            n_ws = int(lib.ganffn_drnn_att_workspace_floats(C.byref(cfg), C.byref(acfg), int(listener)))
+        elif listener:
             n_saved = int(lib.ganffn_drnn_listener_saved_floats(C.byref(cfg)))
             n_ws = int(lib.ganffn_drnn_listener_workspace_floats(C.byref(cfg)))
         else:
@@ -516,7 +547,13 @@ class DialogueRNNFn(torch.autograd.Function):
         rng = DeviceRng.get(dev)
         add = rng.next_add() if train else 0
         P = (_lib.DrnnPtrs * ndir)(*[_drnn_ptrs(p) for p in prm])
-        if listener:
+        if aprm is not None:
+            LP = (_lib.DrnnListenerPtrs * ndir)(*[_drnn_ptrs(p, _lib.DrnnListenerPtrs) for p in lprm]) if listener else None
+            AP = (_lib.DrnnAttPtrs * ndir)(*[_att_ptrs(att, a) for a in aprm])
+            _lib.call("ganffn_drnn_att_fwd", C.byref(cfg), C.byref(acfg), ndir, _ptr_array(U), _ptr_array(spk), _ptr_array(mval), P,
+                      LP, AP, _ptr_array(e), _ptr_array(alpha), _ptr_array(saved), _ptr_array(ws), _ptr(rng.state),
+                      C.c_uint64(add), _stream())
+        elif listener:
             LP = (_lib.DrnnListenerPtrs * ndir)(*[_drnn_ptrs(p, _lib.DrnnListenerPtrs) for p in lprm])
             _lib.call("ganffn_drnn_listener_fwd", C.byref(cfg), ndir, _ptr_array(U), _ptr_array(spk), _ptr_array(mval), P, LP,
                       _ptr_array(e), _ptr_array(alpha), _ptr_array(saved), _ptr_array(ws), _ptr(rng.state), C.c_uint64(add),
@@ -525,6 +562,7 @@ class DialogueRNNFn(torch.autograd.Function):
             _lib.call("ganffn_drnn_fwd", C.byref(cfg), ndir, _ptr_array(U), _ptr_array(spk), _ptr_array(mval), P, _ptr_array(e),
                       _ptr_array(alpha), _ptr_array(saved), _ptr_array(ws), _ptr(rng.state), C.c_uint64(add), _stream())
         ctx.cfg, ctx.ndir, ctx.add, ctx.rng_state = cfg, ndir, add, rng.state
+        ctx.att, ctx.acfg, ctx.aprm = att, acfg, aprm
         ctx.keep = (U, spk, mval, prm, lprm, alpha, saved, ws)
         out = []
         for z in range(ndir):
@@ -538,9 +576,26 @@ class DialogueRNNFn(torch.autograd.Function):
         ndir, cfg = ctx.ndir, ctx.cfg
         d_e = [_f32c(douts[2 * z]) if douts[2 * z] is not None else torch.zeros_like(U[z][..., :cfg.He]) for z in range(ndir)]
         dU = [torch.empty_like(U[z]) for z in range(ndir)]
-        grads = [[torch.zeros_like(p) for p in prm[z]] for z in range(ndir)]
+        grads = [[torch.zeros_like(p) if p is not None else None for p in prm[z]] for z in range(ndir)]
         P = (_lib.DrnnPtrs * ndir)(*[_drnn_ptrs(p) for p in prm])
         G = (_lib.DrnnPtrs * ndir)(*[_drnn_ptrs(g) for g in grads])
+        if ctx.aprm is not None:
+            agrads = [[torch.zeros_like(p) for p in ctx.aprm[z]] for z in range(ndir)]
+            AP = (_lib.DrnnAttPtrs * ndir)(*[_att_ptrs(ctx.att, a) for a in ctx.aprm])
+            AG = (_lib.DrnnAttPtrs * ndir)(*[_att_ptrs(ctx.att, a) for a in agrads])
+            if lprm is not None:
+                lgrads = [[torch.zeros_like(p) for p in lprm[z]] for z in range(ndir)]
+                LP = (_lib.DrnnListenerPtrs * ndir)(*[_drnn_ptrs(p, _lib.DrnnListenerPtrs) for p in lprm])
+                LG = (_lib.DrnnListenerPtrs * ndir)(*[_drnn_ptrs(g, _lib.DrnnListenerPtrs) for g in lgrads])
+            else:
+                lgrads, LP, LG = [[] for _ in range(ndir)], None, None
+            _lib.call("ganffn_drnn_att_bwd", C.byref(cfg), C.byref(ctx.acfg), ndir, _ptr_array(d_e), _ptr_array(U), _ptr_array(spk),
+                      _ptr_array(mval), P, LP, AP, G, LG, AG, _ptr_array(dU), _ptr_array(alpha), _ptr_array(saved), _ptr_array(ws),
+                      _ptr(ctx.rng_state), C.c_uint64(ctx.add), _stream())
+            out = [None]
+            for z in range(ndir):
+                out += [dU[z], None, None] + grads[z][:12] + agrads[z] + lgrads[z]
+            return tuple(out)
         if lprm is not None:
             lgrads = [[torch.zeros_like(p) for p in lprm[z]] for z in range(ndir)]
             LP = (_lib.DrnnListenerPtrs * ndir)(*[_drnn_ptrs(p, _lib.DrnnListenerPtrs) for p in lprm])
@@ -563,9 +618,10 @@ _CHECK_QMASK = __import__("os").environ.get("GANFFN_CHECK_QMASK", "0") == "1"
 
 
 def dialogue_rnn_supported(cell, U, qmask):
-    """the configurations the HIP recurrence implements: general attention (the trained configuration) or simple attention
-    (DialogueRNNCell's constructor default; run as general attention with a constant query: _drnn_cell_args), no listener, two parties, dims % 4,
-    D_g = D_p <= 512 (the attention kernels keep one state column per thread), on a GPU.
+    """the configurations the HIP recurrence implements: every context attention type — general (the trained
+    configuration), simple (DialogueRNNCell's constructor default; run as general attention with a constant query:
+    _drnn_cell_args), dot (D_m = D_g), general2, concat (D_a % 4 == 0, D_a <= 512) — no listener, two parties, dims % 4,
+    D_g = D_p <= 512 (the attention kernels keep one state column per thread), at most 112 steps, on a GPU.
     PRECONDITION (not tested here: the test would be a device->host sync in front of ~760 latency-sized launches): every
     qmask row is one-hot or all zero, as the reference's loaders produce (dataloader.py:41-50) — the gate kernels use
     (argmax, value at argmax) only.  GANFFN_CHECK_QMASK=1 verifies it on every call."""
@@ -578,9 +634,26 @@ def dialogue_rnn_listener_supported(cell, U, qmask):
     return bool(cell.listener_state) and _drnn_limits_hold(cell, U, qmask)
 
 
+def drnn_att_type(cell):
+    """the cell's context attention type: simple / general / dot / general2 / concat"""
+    if type(cell.attention).__name__ == "SimpleAttention":            # softmax over time of a learned scalar score (model.py:117-131)
+        return "simple"
+    return cell.attention.att_type
+
+
+def drnn_att_limits_hold(cell):
+    """the attention type's own limits on the HIP recurrence: dot needs D_m = D_g, concat D_a % 4 == 0 and D_a <= 512"""
+    att = drnn_att_type(cell)
+    if att == "dot":
+        return cell.D_m == cell.D_g
+    if att == "concat":
+        Da = cell.attention.transform.weight.shape[0]
+        return Da % 4 == 0 and 4 <= Da <= 512
+    return att in ("general", "general2", "simple")
+
+
 def _drnn_limits_hold(cell, U, qmask):
-    simple = type(cell.attention).__name__ == "SimpleAttention"          # softmax over time of a learned scalar score (model.py:117-131)
-    ok = (U.is_cuda and (getattr(cell.attention, "att_type", None) == "general" or simple)
+    ok = (U.is_cuda and drnn_att_limits_hold(cell)
           and qmask.size(2) == 2 and cell.D_g == cell.D_p and cell.D_g <= 512 and cell.D_m % 4 == 0 and cell.D_g % 4 == 0
           and cell.D_e % 4 == 0 and U.size(0) <= 112)
     if ok and _CHECK_QMASK:
@@ -592,6 +665,8 @@ def _drnn_cell_args(cell, U):
     """(U, the 13 parameter tensors — 17 with the listener's, DRNN_LISTENER_KEYS) the recurrence kernels take for one
     DialogueRNNCell.
     general attention (model.py:160-166): as they are.
+    dot / general2 / concat: the 12 cell tensors, then the type's own (DRNN_ATT_KEYS: none / transform weight and bias /
+    transform.weight and vector_prod.weight), then the listener's; DialogueRNNFn passes them to ganffn_drnn_att_*.
     simple attention (model.py:117-131): alpha = softmax_s(w . g_s) is general attention with the CONSTANT query w (general:
     alpha = softmax_s(q_t . g_s), q_t = W_att U_t).  A constant cannot come out of W_att U_t, so the utterance features get one
     more column that is always 1 (and three zero columns: the kernels want widths in multiples of 4), the input-side weights of
@@ -599,8 +674,11 @@ def _drnn_cell_args(cell, U):
     All of it is torch.cat on the way in, so autograd carries dU and d(w) back out; the recurrence itself is the same HIP launch
     chain.  (The scalar score has no bias in the reference; a bias would cancel in the softmax anyway.)"""
     sd = dict(cell.named_parameters())
+    att = drnn_att_type(cell)
+    if att not in ("general", "simple"):     # dot / general2 / concat: the 12 cell tensors, the type's own, the listener's
+        return U, [sd[k] for k in DRNN_KEYS[:12] + DRNN_ATT_KEYS[att] + (DRNN_LISTENER_KEYS if cell.listener_state else [])]
     keys = DRNN_KEYS + (DRNN_LISTENER_KEYS if cell.listener_state else [])
-    if type(cell.attention).__name__ != "SimpleAttention":
+    if att == "general":
         return U, [sd[k] for k in keys]
     S, B, Dm = U.shape
     H = cell.D_g
@@ -635,6 +713,10 @@ def dialogue_rnn_run(cells, Us, qmasks, training):
             Ux, params = _drnn_cell_args(cells[z], Us[z][:, b0:b1])
             args += [Ux.contiguous(), spk, mval] + params
         meta = {"p": float(cells[0].dropout.p), "train": bool(training), "listener": bool(cells[0].listener_state)}
+        att = drnn_att_type(cells[0])
+        if att not in ("general", "simple"):
+            meta["att"] = att
+            meta["Da"] = int(cells[0].attention.transform.weight.shape[0]) if att == "concat" else 0
         out = DialogueRNNFn.apply(meta, *args)
         for z in range(ndir):
             e_parts[z].append(out[2 * z])

@@ -236,7 +236,8 @@ int ganffn_general2_attention_bwd(const float* d_att, const float* x, const floa
 
 /* ---- N2 (config 5): the DialogueRNN recurrence ------------------------------------------ */
 /* Replaces DialogueRNN.forward / DialogueRNNCell.forward (model.py:828-972) in the configuration
- * train_IEMOCAP_DialogueRNN.py runs: context_attention = "general" (:586), listener_state = False (:595), two parties.
+ * train_IEMOCAP_DialogueRNN.py runs: context_attention = "general" (:586), listener_state = False (:595), two parties
+ * (listener state: ganffn_drnn_listener_*; the other attention types, with or without it: ganffn_drnn_att_* below).
  * One call runs ndir (1 or 2) independent DialogueRNNs — BiModel's forward and reverse directions (model.py:1025-1033)
  * — through the same launches.  Per direction:
  *   U [S x B x D_m] (the reverse direction gets the reversed sequences, as BiModel._reverse_seq builds them),
@@ -300,6 +301,48 @@ int ganffn_drnn_listener_bwd(const ganffn_drnn_cfg* cfg, int ndir, const float* 
                              const ganffn_drnn_listener_grads* lgrads, float* const* dU, const float* const* alpha,
                              const float* const* saved, float* const* workspace, const uint64_t* rng,
                              uint64_t rng_offset_add, void* stream);
+
+/* The other context attention types of DialogueRNNCell (model.py:856-859, MatchingAttention :134-194, SimpleAttention
+ * :117-131; train_IEMOCAP_DialogueRNN.py --attention, :586): the same recurrence, the same launches per step (2 + 2
+ * without listener state, 4 + 4 with it), one attention descriptor for both directions.  At step t >= 1 the memory is
+ * g_0 .. g_{t-1} (after dropout), alpha = softmax_j(s_j), c_t = sum_j alpha_j g_j; s_j per type:
+ *   general  <W U_t, g_j>                 w = transform.weight [D_g x D_m]
+ *   simple   <w, g_j>                     w = scalar.weight [1 x D_g]
+ *   dot      <U_t, g_j>                   no parameters; D_m == D_g
+ *   general2 tanh(<W U_t + b, g_j>)       w = transform.weight [D_g x D_m], b = transform.bias [D_g] (the cell passes
+ *                                         no mask: masking and re-normalisation are the identity)
+ *   concat   v . tanh(W [g_j ; U_t])      w = transform.weight [D_a x (D_g + D_m)] (memory columns first),
+ *                                         v = vector_prod.weight [1 x D_a]; D_a a multiple of 4, <= 512
+ * params.att_w (and grads.att_w) are ignored: the attention's parameters are aparams (ndir entries; NULL for dot).
+ * lparams == NULL: listener_state False, else the listener path above (lgrads as there).  saved / workspace are sized by
+ * ganffn_drnn_att_saved_floats / _workspace_floats(cfg, att, listener) (per direction).  agrads (ndir entries or NULL;
+ * members NULL = not wanted) are accumulated into.  No dropout of its own; deterministic (no atomics). */
+enum { GANFFN_DRNN_ATT_GENERAL = 0, GANFFN_DRNN_ATT_SIMPLE = 1, GANFFN_DRNN_ATT_DOT = 2, GANFFN_DRNN_ATT_GENERAL2 = 3,
+       GANFFN_DRNN_ATT_CONCAT = 4 };
+typedef struct ganffn_drnn_att {
+    int32_t type;        /* GANFFN_DRNN_ATT_* */
+    int32_t Da;          /* concat: D_a (train_IEMOCAP_DialogueRNN.py:641: 100); ignored otherwise */
+} ganffn_drnn_att;
+typedef struct ganffn_drnn_att_params {
+    const float *w, *b, *v;
+} ganffn_drnn_att_params;
+typedef struct ganffn_drnn_att_grads {
+    float *w, *b, *v;
+} ganffn_drnn_att_grads;
+int64_t ganffn_drnn_att_saved_floats(const ganffn_drnn_cfg* cfg, const ganffn_drnn_att* att, int listener);
+int64_t ganffn_drnn_att_workspace_floats(const ganffn_drnn_cfg* cfg, const ganffn_drnn_att* att, int listener);
+int ganffn_drnn_att_fwd(const ganffn_drnn_cfg* cfg, const ganffn_drnn_att* att, int ndir, const float* const* U,
+                        const int32_t* const* spk, const float* const* mval, const ganffn_drnn_params* params,
+                        const ganffn_drnn_listener_params* lparams, const ganffn_drnn_att_params* aparams,
+                        float* const* e_out, float* const* alpha, float* const* saved, float* const* workspace,
+                        const uint64_t* rng, uint64_t rng_offset_add, void* stream);
+int ganffn_drnn_att_bwd(const ganffn_drnn_cfg* cfg, const ganffn_drnn_att* att, int ndir, const float* const* d_e,
+                        const float* const* U, const int32_t* const* spk, const float* const* mval,
+                        const ganffn_drnn_params* params, const ganffn_drnn_listener_params* lparams,
+                        const ganffn_drnn_att_params* aparams, const ganffn_drnn_grads* grads,
+                        const ganffn_drnn_listener_grads* lgrads, const ganffn_drnn_att_grads* agrads, float* const* dU,
+                        const float* const* alpha, const float* const* saved, float* const* workspace,
+                        const uint64_t* rng, uint64_t rng_offset_add, void* stream);
 
 /* Data movement of BiModel.forward around the recurrence (model.py:1008-1062), one launch each (csrc/drnn_head.hip):
  * ganffn_seq_reverse: out[s, b, :] (+)= s < lens[b] ? x[lens[b]-1-s, b, :] : 0 — BiModel._reverse_seq and, being its own
