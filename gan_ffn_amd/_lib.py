@@ -132,6 +132,10 @@ SIGNATURES = {
     "ganffn_drnn_att_workspace_floats": (_L, [C.POINTER(DrnnCfg), C.POINTER(DrnnAtt), _I]),
     "ganffn_drnn_att_fwd": (_I, [C.POINTER(DrnnCfg), C.POINTER(DrnnAtt), _I] + [_P] * 11 + [_U64, _P]),
     "ganffn_drnn_att_bwd": (_I, [C.POINTER(DrnnCfg), C.POINTER(DrnnAtt), _I] + [_P] * 15 + [_U64, _P]),
+    "ganffn_drnn_party_saved_floats": (_L, [C.POINTER(DrnnCfg), C.POINTER(DrnnAtt), _I, _I]),
+    "ganffn_drnn_party_workspace_floats": (_L, [C.POINTER(DrnnCfg), C.POINTER(DrnnAtt), _I, _I]),
+    "ganffn_drnn_party_fwd": (_I, [C.POINTER(DrnnCfg), C.POINTER(DrnnAtt), _I, _I] + [_P] * 11 + [_U64, _P]),
+    "ganffn_drnn_party_bwd": (_I, [C.POINTER(DrnnCfg), C.POINTER(DrnnAtt), _I, _I] + [_P] * 15 + [_U64, _P]),
     "ganffn_dropout": (_I, [_P, _P, _I, _I, _F, _U32, _P, _U64, _P]),
     "ganffn_seq_reverse": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "ganffn_drnn_join_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _U32, _U32, _P, _U64, _I, _P]),

@@ -58,9 +58,8 @@ enum : uint32_t { SITE_DRNN_G = 8, SITE_DRNN_P = 9, SITE_DRNN_E = 10, SITE_DRNN_
 // L2-bandwidth-sized; fewer, fatter waves lengthen the one round trip it consists of.)
 constexpr int SK_NT = 8;
 template <int NW>
-__global__ __launch_bounds__(64 * NW) void skinny_nt_kernel(SkinnyGroup grp) {
+__device__ __forceinline__ void skinny_nt_body(const SkinnyProb& q) {
     __shared__ __attribute__((aligned(16))) float red[NW][2][4][64];
-    const SkinnyProb& q = grp.p[blockIdx.z];
     const int n0 = blockIdx.x * 16;
     if (n0 >= q.N) return;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
@@ -139,6 +138,19 @@ __global__ __launch_bounds__(64 * NW) void skinny_nt_kernel(SkinnyGroup grp) {
         }
     }
 }
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void skinny_nt_kernel(SkinnyGroup grp) { skinny_nt_body<NW>(grp.p[blockIdx.z]); }
+
+// More than 8 NT problems in one launch: the listener's products of one step with P > 3 parties (one input-side product and
+// one hidden-side product per party row, per direction: 2 (1 + P)).  A separate kernel, so that the 8-problem launches of
+// the two-party recurrence and of lstm.hip keep their kernel and argument block.
+constexpr int DR_MAXP = GANFFN_DRNN_MAX_PARTIES;
+struct SkinnyGroupWide {
+    SkinnyProb p[2 * (1 + DR_MAXP)];
+};
+static_assert(sizeof(SkinnyGroupWide) <= 4096, "the wide skinny group is passed as a kernel argument (4 KB at most)");
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void skinny_nt_wide_kernel(SkinnyGroupWide grp) { skinny_nt_body<NW>(grp.p[blockIdx.z]); }
 
 // out[c][r] = in[r][c] for up to 8 matrices [rows x cols] (leading dimension ld_in) -> [cols x rows]: the recurrent
 // weights in the orientation the backward step's products read row-wise (once per backward call)
@@ -232,6 +244,30 @@ int launch_skinny(const SkinnyGroup& grp, int nprob, bool nn, hipStream_t st) {
     GF_LAUNCH_CHECK();
     return 0;
 }
+// n NT problems in one launch: up to 8 through launch_skinny (the same launch as before parties were general), more through
+// the wide group
+static int launch_skinny_nt(const SkinnyProb* pr, int n, hipStream_t st) {
+    if (n <= 8) {
+        SkinnyGroup sg;
+        for (int i = 0; i < n; ++i) sg.p[i] = pr[i];
+        return launch_skinny(sg, n, false, st);
+    }
+    GF_CHECK_ARG(n <= 2 * (1 + DR_MAXP), "drnn skinny product: %d problems in one launch (<= %d)", n, 2 * (1 + DR_MAXP));
+    SkinnyGroupWide wg;
+    int maxN = 0, maxK = 0;
+    for (int i = 0; i < n; ++i) {
+        const SkinnyProb& q = pr[i];
+        GF_CHECK_ARG(q.M >= 1 && q.M <= 32 && (q.K & 3) == 0 && (q.lda & 3) == 0 && aligned16(q.A) && (q.ldw & 3) == 0 && aligned16(q.W),
+                     "drnn skinny product: M=%d K=%d lda=%d ldw=%d unsupported", q.M, q.K, q.lda, q.ldw);
+        wg.p[i] = q;
+        maxN = q.N > maxN ? q.N : maxN;
+        maxK = q.K > maxK ? q.K : maxK;
+    }
+    if (maxK > 4 * 16 * SK_NT) hipLaunchKernelGGL(skinny_nt_wide_kernel<12>, dim3((maxN + 15) / 16, 1, n), dim3(768), 0, st, wg);
+    else hipLaunchKernelGGL(skinny_nt_wide_kernel<4>, dim3((maxN + 15) / 16, 1, n), dim3(256), 0, st, wg);
+    GF_LAUNCH_CHECK();
+    return 0;
+}
 
 // ------------------------------------------------------------------------------------------
 // GRU gate math (torch.nn.GRUCell: r, z, n row blocks; n = tanh(i_n + r * h_n); h' = (1 - z) n + z h)
@@ -244,7 +280,7 @@ struct GateDir {
     // party cell only:
     const int* spk; const int* spk_next;  // [B] speaker of this / the next step (spk_next NULL on the last step)
     const float* mval;                    // [B] 1 on valid steps, 0 on padding
-    const float* Qprev; float* Qnext;     // [B x 2 x H] party states before / after this step
+    const float* Qprev; float* Qnext;     // [B x P x H] party states before / after this step
     float* QN; float* QSnext;             // [B x H] q_t[spk_t]; q_t[spk_{t+1}] (next step's g / p cell input)
     uint32_t site;
 };
@@ -252,6 +288,7 @@ struct GateArgs {
     GateDir d[2];
     int B, H, row0;        // row0 = t * B: dropout row of dialogue 0
     float p; int train;
+    int P;                 // parties (party cell; 1 <= P <= DR_MAXP)
     const uint64_t* rng; uint64_t add;
 };
 
@@ -277,15 +314,17 @@ __device__ __forceinline__ void gru_gate_fwd_body(const GateArgs& a, const GateD
     } else if (PARTY == 2) {
         d.QN[idx] = hnew;     // listener path: qs after its dropout (QSP[t]); drnn_listener_fwd_kernel blends and writes Q
     } else {
-        // q_t[spk] = m ? qs : q_{t-1}[spk]; the other party keeps its state (listener_state False, model.py:888-893)
+        // q_t[spk] = m ? qs : q_{t-1}[spk]; the other P - 1 parties keep their state (listener_state False, model.py:888-893)
         const int s = d.spk[b];
         const float m = d.mval[b];
         const float qs = m != 0.f ? hnew : h;
-        const float other = d.Qprev[((size_t)b * 2 + (1 - s)) * a.H + u];
-        d.Qnext[((size_t)b * 2 + s) * a.H + u] = qs;
-        d.Qnext[((size_t)b * 2 + (1 - s)) * a.H + u] = other;
+        const size_t q0 = (size_t)b * a.P * a.H + u;
+        for (int pa = 0; pa < a.P; ++pa) d.Qnext[q0 + (size_t)pa * a.H] = pa == s ? qs : d.Qprev[q0 + (size_t)pa * a.H];
         d.QN[idx] = qs;
-        if (d.spk_next) d.QSnext[idx] = d.spk_next[b] == s ? qs : other;
+        if (d.spk_next) {
+            const int sn = d.spk_next[b];
+            d.QSnext[idx] = sn == s ? qs : d.Qprev[q0 + (size_t)sn * a.H];
+        }
     }
 }
 template <int PARTY>
@@ -300,7 +339,7 @@ struct GateBwdDir {
     float* dGI; float* dGH; // [B x 3H] gate gradients (kept for the weight-gradient GEMMs)
     float* dhdir;           // [B x H] direct path to hprev: dh' * z (+ (1 - m) dq for the party cell)
     const float* mval;      // party cell: [B]
-    const int* spk;         // party cell: [B]; dh is then the [B x 2 x H] gradient wrt Q[t+1], read at party spk[b]
+    const int* spk;         // party cell: [B]; dh is then the [B x P x H] gradient wrt Q[t+1], read at party spk[b]
     uint32_t site;
     // party cell, optional: the previous (later-in-time) step's party-gradient assembly done here instead of in its own
     // launch — dQ[t+1][b][p] = p == spk_{t+1}[b] ? dQSp + dQSg : dQ[t+2][b][p]; written to pg_out (= dh) and used directly
@@ -311,6 +350,7 @@ struct GateBwdArgs {
     GateBwdDir d[2];
     int B, H, row0;
     float p; int train;
+    int P;                 // parties (party cell)
     const uint64_t* rng; uint64_t add;
 };
 
@@ -320,16 +360,18 @@ __device__ __forceinline__ void gru_gate_bwd_body(const GateBwdArgs& a, const Ga
     const int b = idx / a.H, u = idx - b * a.H, H3 = 3 * a.H;
     float dout;
     if (PARTY == 1 && d.pg_out != nullptr) {
-        const int sn = d.pg_spk[b];
-        const size_t o0 = ((size_t)b * 2) * a.H + u, o1 = o0 + a.H;
+        const int sn = d.pg_spk[b], s = d.spk[b];
+        const size_t o0 = (size_t)b * a.P * a.H + u;
         const float own = d.pg_dQSp[idx] + d.pg_dQSg[idx];
-        const float v0 = sn == 0 ? own : d.pg_dQ[o0];
-        const float v1 = sn == 1 ? own : d.pg_dQ[o1];
-        d.pg_out[o0] = v0;
-        d.pg_out[o1] = v1;
-        dout = d.spk[b] ? v1 : v0;
+        dout = 0.f;
+        for (int pa = 0; pa < a.P; ++pa) {
+            const size_t o = o0 + (size_t)pa * a.H;
+            const float v = pa == sn ? own : d.pg_dQ[o];
+            d.pg_out[o] = v;
+            if (pa == s) dout = v;
+        }
     } else {
-        dout = PARTY == 1 ? d.dh[((size_t)b * 2 + d.spk[b]) * a.H + u] : d.dh[idx];   // (PARTY 2, listener: dh = d qs [B x H])
+        dout = PARTY == 1 ? d.dh[((size_t)b * a.P + d.spk[b]) * a.H + u] : d.dh[idx];   // (PARTY 2, listener: dh = d qs [B x H])
     }
     if (d.dh2) dout += d.dh2[idx];
     float pass = 0.f;
@@ -755,20 +797,21 @@ __global__ __launch_bounds__(1024) void drnn_colsum_kernel(const float* __restri
 
 // ------------------------------------------------------------------------------------------
 // Listener state (listener_state = True, model.py:899-921): every party row also takes a listener GRU step
-//     ql[p] = drop_L(GRU_l([U_t, qs], q_{t-1}[p]))      p = 0, 1; qs = the speaker's new state after its dropout
+//     ql[p] = drop_L(GRU_l([U_t, qs], q_{t-1}[p]))      p = 0 .. P-1; qs = the speaker's new state after its dropout
 //     q_t[p] = (m != 0 && p == spk) ? qs : ql[p]
-// The input side [U_t, qs] is the same for both party rows: its U part is one GEMM over all steps (XL, b_ih included), its
-// qs part one skinny product per step; the hidden side is one skinny product per party row (Q's [B x 2 x H] rows, lda 2H).
-// drnn_listener_fwd_kernel: the listener gates of both party rows + the blend (writes Q[t+1], QN[t], QS[t+1] — what the
+// The input side [U_t, qs] is the same for every party row: its U part is one GEMM over all steps (XL, b_ih included), its
+// qs part one skinny product per step; the hidden side is one skinny product per party row (Q's [B x P x H] rows, lda PH),
+// all of them in one launch (launch_skinny_nt: the wide group beyond 8 problems, i.e. P > 3 with both directions).
+// drnn_listener_fwd_kernel: the listener gates of every party row + the blend (writes Q[t+1], QN[t], QS[t+1] — what the
 // party gate writes without the listener).  Dropout site SITE_DRNN_L (+4 per direction), row t*B + b, column p*H + u of
-// a width-2H row.
+// a width-PH row.
 // ------------------------------------------------------------------------------------------
 struct LGateDir {
-    const float* GI;          // [B x 3H] input pre-activations, shared by both party rows: XL[t] + QSP[t] W_ih_l[:, Dm:]^T
-    const float* GH;          // [B x 2 x 3H] hidden pre-activations per party row (b_hh included)
-    const float* Qprev;       // [B x 2 x H] Q[t]
+    const float* GI;          // [B x 3H] input pre-activations, shared by every party row: XL[t] + QSP[t] W_ih_l[:, Dm:]^T
+    const float* GH;          // [B x P x 3H] hidden pre-activations per party row (b_hh included)
+    const float* Qprev;       // [B x P x H] Q[t]
     const float* QSP;         // [B x H] qs of this step (after its dropout)
-    float* R; float* Z; float* N; float* HN;      // [B x 2 x H] saved listener gates of this step
+    float* R; float* Z; float* N; float* HN;      // [B x P x H] saved listener gates of this step
     const int* spk; const int* spk_next;          // spk_next NULL on the last step
     const float* mval;
     float* Qnext; float* QN; float* QSnext;       // as GateDir
@@ -778,15 +821,16 @@ struct LGateArgs {
     LGateDir d[2];
     int B, H, row0;
     float p; int train;
+    int P;
     const uint64_t* rng; uint64_t add;
 };
 __global__ __launch_bounds__(256) void drnn_listener_fwd_kernel(LGateArgs a) {
     const LGateDir& d = a.d[blockIdx.z];
-    const int idx = blockIdx.x * 256 + threadIdx.x, H = a.H, H2 = 2 * a.H;
-    if (idx >= a.B * H2) return;
-    const int b = idx / H2, j = idx - b * H2, pa = j >= H ? 1 : 0, u = j - pa * H;
+    const int idx = blockIdx.x * 256 + threadIdx.x, H = a.H, HP = a.P * a.H;
+    if (idx >= a.B * HP) return;
+    const int b = idx / HP, j = idx - b * HP, pa = j / H, u = j - pa * H;
     const float* gi = d.GI + (size_t)b * 3 * H;
-    const float* gh = d.GH + ((size_t)b * 2 + pa) * 3 * H;
+    const float* gh = d.GH + ((size_t)b * a.P + pa) * 3 * H;
     const float h = d.Qprev[idx];
     const float r = sigm(gi[u] + gh[u]);
     const float z = sigm(gi[H + u] + gh[H + u]);
@@ -795,7 +839,7 @@ __global__ __launch_bounds__(256) void drnn_listener_fwd_kernel(LGateArgs a) {
     float hnew = (1.0f - z) * n + z * h;
     d.R[idx] = r; d.Z[idx] = z; d.N[idx] = n; d.HN[idx] = hn;
     const DropCtx dc = make_drop(a.rng, a.add, d.site, a.p, a.train);
-    hnew *= drop_mult1(dc, (uint32_t)(a.row0 + b), (uint32_t)H2, (uint32_t)j);
+    hnew *= drop_mult1(dc, (uint32_t)(a.row0 + b), (uint32_t)HP, (uint32_t)j);
     const int s = d.spk[b];
     const float q = (d.mval[b] != 0.f && pa == s) ? d.QSP[(size_t)b * H + u] : hnew;
     d.Qnext[idx] = q;
@@ -803,22 +847,22 @@ __global__ __launch_bounds__(256) void drnn_listener_fwd_kernel(LGateArgs a) {
     if (d.spk_next && pa == d.spk_next[b]) d.QSnext[(size_t)b * H + u] = q;
 }
 
-// Backward of the listener and the blend at step t, one thread per (dialogue, column) covering both party rows (so the
-// party sum of the input-side gate gradient is formed in a fixed order, without atomics).  Gradient wrt Q[t+1][p]:
+// Backward of the listener and the blend at step t, one thread per (dialogue, column) covering every party row (so the
+// party sum of the input-side gate gradient is formed in a fixed order, p = 0 .. P-1, without atomics).  Gradient wrt Q[t+1][p]:
 //     dq[p] = dQl[p] + (p == spk_{t+1} ? dQSp + dQSg : 0) + (p == spk_t ? dQN[t] : 0)
 // (dQl = dGH_l[p] W_hh_l + dh' z of step t+1: the listener's hidden path; dQSp / dQSg: QS[t+1] = Q[t+1][spk_{t+1}] as the
 // party cell's hidden state and the global cell's input of step t+1; dQN: QN[t] = Q[t+1][spk_t] into the emotion cell).
 // The row the blend took from qs passes dq to d qs and its listener gets zero.
 struct LGateBwdDir {
-    const float* dQl;         // [B x 2 x H] NULL on the last step
+    const float* dQl;         // [B x P x H] NULL on the last step
     const float* dQSp; const float* dQSg; const int* spk_next;
     const float* dQN;         // [B x H]
     const int* spk; const float* mval;
-    const float* R; const float* Z; const float* N; const float* HN;   // [B x 2 x H]
-    const float* Qprev;       // [B x 2 x H] Q[t]
-    float* dGI;               // [B x 3H] input-side gate gradient, summed over the two party rows
-    float* dGH;               // [B x 2 x 3H]
-    float* dhdir;             // [B x 2 x H] direct path to Q[t]: dh' z
+    const float* R; const float* Z; const float* N; const float* HN;   // [B x P x H]
+    const float* Qprev;       // [B x P x H] Q[t]
+    float* dGI;               // [B x 3H] input-side gate gradient, summed over the party rows
+    float* dGH;               // [B x P x 3H]
+    float* dhdir;             // [B x P x H] direct path to Q[t]: dh' z
     float* dqs;               // [B x H] gradient wrt qs through the blend
     uint32_t site;
 };
@@ -826,6 +870,7 @@ struct LGateBwdArgs {
     LGateBwdDir d[2];
     int B, H, row0;
     float p; int train;
+    int P;
     const uint64_t* rng; uint64_t add;
 };
 __global__ __launch_bounds__(256) void drnn_listener_bwd_kernel(LGateBwdArgs a) {
@@ -837,9 +882,8 @@ __global__ __launch_bounds__(256) void drnn_listener_bwd_kernel(LGateBwdArgs a) 
     const bool took_qs = d.mval[b] != 0.f;
     const DropCtx dc = make_drop(a.rng, a.add, d.site, a.p, a.train);
     float sr = 0.f, sz = 0.f, sn_ = 0.f, dqs = 0.f;
-#pragma unroll
-    for (int pa = 0; pa < 2; ++pa) {
-        const size_t o = ((size_t)b * 2 + pa) * H + u;
+    for (int pa = 0; pa < a.P; ++pa) {
+        const size_t o = ((size_t)b * a.P + pa) * H + u;
         float dq = 0.f;
         if (d.dQl) {
             dq = d.dQl[o];
@@ -847,14 +891,14 @@ __global__ __launch_bounds__(256) void drnn_listener_bwd_kernel(LGateBwdArgs a) 
         }
         if (pa == s) dq += d.dQN[idx];
         if (took_qs && pa == s) { dqs = dq; dq = 0.f; }
-        const float dhn = dq * drop_mult1(dc, (uint32_t)(a.row0 + b), (uint32_t)(2 * H), (uint32_t)(pa * H + u));
+        const float dhn = dq * drop_mult1(dc, (uint32_t)(a.row0 + b), (uint32_t)(a.P * H), (uint32_t)(pa * H + u));
         const float r = d.R[o], z = d.Z[o], n = d.N[o], hn = d.HN[o], h = d.Qprev[o];
         const float dn = dhn * (1.0f - z);
         const float dz = dhn * (h - n);
         const float dnp = dn * (1.0f - n * n);
         const float drp = dnp * hn * r * (1.0f - r);
         const float dzp = dz * z * (1.0f - z);
-        float* gh = d.dGH + ((size_t)b * 2 + pa) * H3;
+        float* gh = d.dGH + ((size_t)b * a.P + pa) * H3;
         gh[u] = drp; gh[H + u] = dzp; gh[2 * H + u] = dnp * r;
         sr += drp; sz += dzp; sn_ += dnp;
         d.dhdir[o] = dhn * z;
@@ -1029,18 +1073,20 @@ __global__ __launch_bounds__(EC_NT) void drnn_echain_bwd_kernel(EchainBwdArgs a)
 }
 
 // ------------------------------------------------------------------------------------------
-// layouts of the saved-for-backward block and of the workspace (floats; every region 16-byte aligned)
+// layouts of the saved-for-backward block and of the workspace (floats; every region 16-byte aligned).  P = parties: the
+// party states Q, their gradients dQ and the listener's per-party-row regions are [.. x P x ..]; P = 2 gives the sizes and
+// offsets the two-party entry points always had.
 // ------------------------------------------------------------------------------------------
 struct DrnnSaved {
     int64_t XG, XP, XA, G, Q, E, QS, CT, QN, Rg, Zg, Ng, HNg, Rp, Zp, Np, HNp, Re, Ze, Ne, HNe, total;
 };
-static DrnnSaved drnn_saved(const ganffn_drnn_cfg* c) {
+static DrnnSaved drnn_saved(const ganffn_drnn_cfg* c, int P) {
     DrnnSaved s;
     const int64_t T = (int64_t)c->S * c->B, T1 = (int64_t)(c->S + 1) * c->B, H = c->H, He = c->He;
     int64_t p = 0;
     auto take = [&](int64_t n) { int64_t r = p; p += (n + 3) & ~int64_t(3); return r; };
     s.XG = take(T * 3 * H); s.XP = take(T * 3 * H); s.XA = take(T * H);
-    s.G = take(T1 * H); s.Q = take(T1 * 2 * H); s.E = take(T1 * He);
+    s.G = take(T1 * H); s.Q = take(T1 * P * H); s.E = take(T1 * He);
     s.QS = take(T1 * H); s.CT = take(T * H); s.QN = take(T * H);
     s.Rg = take(T * H); s.Zg = take(T * H); s.Ng = take(T * H); s.HNg = take(T * H);
     s.Rp = take(T * H); s.Zp = take(T * H); s.Np = take(T * H); s.HNp = take(T * H);
@@ -1051,7 +1097,7 @@ static DrnnSaved drnn_saved(const ganffn_drnn_cfg* c) {
 struct DrnnWs {
     int64_t GI, GH, GIp, GHp, dGIg, dGHg, dGIp, dGHp, dGIe, dGHe, dXA, dCT, dG, dQa, dQb, dEa, dEb, dQsel, dQSp, dQSg, dhdir, dhdirG, dQN, GIe, dQNall, WT, total;
 };
-static DrnnWs drnn_ws(const ganffn_drnn_cfg* c) {
+static DrnnWs drnn_ws(const ganffn_drnn_cfg* c, int P) {
     DrnnWs w;
     const int64_t T = (int64_t)c->S * c->B, T1 = (int64_t)(c->S + 1) * c->B, B = c->B, H = c->H, He = c->He;
     int64_t p = 0;
@@ -1060,7 +1106,7 @@ static DrnnWs drnn_ws(const ganffn_drnn_cfg* c) {
     w.dGIg = take(T * 3 * H); w.dGHg = take(T * 3 * H); w.dGIp = take(T * 3 * H); w.dGHp = take(T * 3 * H);
     w.dGIe = take(T * 3 * He); w.dGHe = take(T * 3 * He);
     w.dXA = take(T * H); w.dCT = take(B * H); w.dG = take(T1 * H);
-    w.dQa = take(B * 2 * H); w.dQb = take(B * 2 * H); w.dEa = take(B * He); w.dEb = take(B * He);
+    w.dQa = take(B * P * H); w.dQb = take(B * P * H); w.dEa = take(B * He); w.dEb = take(B * He);
     w.dQsel = take(B * H); w.dQSp = take(B * H); w.dQSg = take(B * H); w.dhdir = take(B * H); w.dhdirG = take(B * H); w.dQN = take(B * H);
     w.GIe = take(T * 3 * He); w.dQNall = take(T * H);       // emotion chain: input pre-activations / dQN of all steps
     w.WT = take(4 * H * 3 * H);                              // transposed recurrent weights (backward): 4 x [H x 3H]
@@ -1070,25 +1116,25 @@ static DrnnWs drnn_ws(const ganffn_drnn_cfg* c) {
 
 // listener path: extra regions behind the listener-free ones (whose offsets do not move)
 struct DrnnLSaved { int64_t XL, QSP, Rl, Zl, Nl, HNl, total; };
-static DrnnLSaved drnn_lsaved(const ganffn_drnn_cfg* c) {
+static DrnnLSaved drnn_lsaved(const ganffn_drnn_cfg* c, int P) {
     DrnnLSaved s;
     const int64_t T = (int64_t)c->S * c->B, H = c->H;
-    int64_t p = drnn_saved(c).total;
+    int64_t p = drnn_saved(c, P).total;
     auto take = [&](int64_t n) { int64_t r = p; p += (n + 3) & ~int64_t(3); return r; };
     s.XL = take(T * 3 * H); s.QSP = take(T * H);
-    s.Rl = take(T * 2 * H); s.Zl = take(T * 2 * H); s.Nl = take(T * 2 * H); s.HNl = take(T * 2 * H);
+    s.Rl = take(T * P * H); s.Zl = take(T * P * H); s.Nl = take(T * P * H); s.HNl = take(T * P * H);
     s.total = p;
     return s;
 }
 struct DrnnLWs { int64_t GIl, GHl, dGIl, dGHl, dss, dqs, dQl, dhdirl, WTl, total; };
-static DrnnLWs drnn_lws(const ganffn_drnn_cfg* c) {
+static DrnnLWs drnn_lws(const ganffn_drnn_cfg* c, int P) {
     DrnnLWs w;
     const int64_t T = (int64_t)c->S * c->B, B = c->B, H = c->H;
-    int64_t p = drnn_ws(c).total;
+    int64_t p = drnn_ws(c, P).total;
     auto take = [&](int64_t n) { int64_t r = p; p += (n + 3) & ~int64_t(3); return r; };
-    w.GIl = take(B * 3 * H); w.GHl = take(B * 2 * 3 * H);
-    w.dGIl = take(T * 3 * H); w.dGHl = take(T * 2 * 3 * H);
-    w.dss = take(B * H); w.dqs = take(B * H); w.dQl = take(B * 2 * H); w.dhdirl = take(B * 2 * H);
+    w.GIl = take(B * 3 * H); w.GHl = take(B * P * 3 * H);
+    w.dGIl = take(T * 3 * H); w.dGHl = take(T * P * 3 * H);
+    w.dss = take(B * H); w.dqs = take(B * H); w.dQl = take(B * P * H); w.dhdirl = take(B * P * H);
     w.WTl = take(2 * H * 3 * H);                             // transposed l_wih[:, Dm:], l_whh (backward)
     w.total = p;
     return w;
@@ -1096,10 +1142,10 @@ static DrnnLWs drnn_lws(const ganffn_drnn_cfg* c) {
 
 // other attention types: regions behind the listener-free (or listener) ones, whose offsets do not move
 struct DrnnASaved { int64_t TS, XC, P, total; };
-static DrnnASaved drnn_asaved(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, bool listener) {
+static DrnnASaved drnn_asaved(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, bool listener, int P) {
     DrnnASaved s{-1, -1, -1, 0};
     const int64_t T = (int64_t)c->S * c->B, Da = at->Da;
-    int64_t p = listener ? drnn_lsaved(c).total : drnn_saved(c).total;
+    int64_t p = listener ? drnn_lsaved(c, P).total : drnn_saved(c, P).total;
     auto take = [&](int64_t n) { int64_t r = p; p += (n + 3) & ~int64_t(3); return r; };
     if (at->type == GANFFN_DRNN_ATT_GENERAL2) s.TS = take((int64_t)c->B * c->S * c->S);
     if (at->type == GANFFN_DRNN_ATT_CONCAT) { s.XC = take(T * Da); s.P = take(T * Da); }
@@ -1107,10 +1153,10 @@ static DrnnASaved drnn_asaved(const ganffn_drnn_cfg* c, const ganffn_drnn_att* a
     return s;
 }
 struct DrnnAWs { int64_t dXC, dP, dVp, total; };
-static DrnnAWs drnn_aws(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, bool listener) {
+static DrnnAWs drnn_aws(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, bool listener, int P) {
     DrnnAWs w{-1, -1, -1, 0};
     const int64_t T = (int64_t)c->S * c->B, Da = at->Da;
-    int64_t p = listener ? drnn_lws(c).total : drnn_ws(c).total;
+    int64_t p = listener ? drnn_lws(c, P).total : drnn_ws(c, P).total;
     auto take = [&](int64_t n) { int64_t r = p; p += (n + 3) & ~int64_t(3); return r; };
     if (at->type == GANFFN_DRNN_ATT_CONCAT) { w.dXC = take(T * Da); w.dP = take(T * Da); w.dVp = take(T * Da); }
     w.total = p;
@@ -1148,6 +1194,11 @@ static int check_att_params(const ganffn_drnn_att* at, const ganffn_drnn_att_par
     return 0;
 }
 
+static int check_parties(int P) {
+    GF_CHECK_ARG(P >= 1 && P <= DR_MAXP, "drnn_party: parties=%d outside [1, %d] (GANFFN_DRNN_MAX_PARTIES)", P, DR_MAXP);
+    return 0;
+}
+
 static int memset_f(float* p, int64_t n, hipStream_t st) {
     hipError_t e = hipMemsetAsync(p, 0, (size_t)n * sizeof(float), st);
     if (e != hipSuccess) return fail((int)e, "drnn: memset failed: %s", hipGetErrorString(e));
@@ -1168,15 +1219,21 @@ extern "C" int ganffn_drnn_skinny(int nn, int copies, const float* A, const floa
     return launch_skinny(sg, copies, nn != 0, (hipStream_t)stream);
 }
 
-extern "C" int64_t ganffn_drnn_saved_floats(const ganffn_drnn_cfg* c) { return check_drnn(c, 1) ? -1 : drnn_saved(c).total; }
-extern "C" int64_t ganffn_drnn_workspace_floats(const ganffn_drnn_cfg* c) { return check_drnn(c, 1) ? -1 : drnn_ws(c).total; }
-extern "C" int64_t ganffn_drnn_listener_saved_floats(const ganffn_drnn_cfg* c) { return check_drnn(c, 1) ? -1 : drnn_lsaved(c).total; }
-extern "C" int64_t ganffn_drnn_listener_workspace_floats(const ganffn_drnn_cfg* c) { return check_drnn(c, 1) ? -1 : drnn_lws(c).total; }
+extern "C" int64_t ganffn_drnn_saved_floats(const ganffn_drnn_cfg* c) { return check_drnn(c, 1) ? -1 : drnn_saved(c, 2).total; }
+extern "C" int64_t ganffn_drnn_workspace_floats(const ganffn_drnn_cfg* c) { return check_drnn(c, 1) ? -1 : drnn_ws(c, 2).total; }
+extern "C" int64_t ganffn_drnn_listener_saved_floats(const ganffn_drnn_cfg* c) { return check_drnn(c, 1) ? -1 : drnn_lsaved(c, 2).total; }
+extern "C" int64_t ganffn_drnn_listener_workspace_floats(const ganffn_drnn_cfg* c) { return check_drnn(c, 1) ? -1 : drnn_lws(c, 2).total; }
 extern "C" int64_t ganffn_drnn_att_saved_floats(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int listener) {
-    return check_drnn(c, 1) || check_att(c, at) ? -1 : drnn_asaved(c, at, listener != 0).total;
+    return check_drnn(c, 1) || check_att(c, at) ? -1 : drnn_asaved(c, at, listener != 0, 2).total;
 }
 extern "C" int64_t ganffn_drnn_att_workspace_floats(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int listener) {
-    return check_drnn(c, 1) || check_att(c, at) ? -1 : drnn_aws(c, at, listener != 0).total;
+    return check_drnn(c, 1) || check_att(c, at) ? -1 : drnn_aws(c, at, listener != 0, 2).total;
+}
+extern "C" int64_t ganffn_drnn_party_saved_floats(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int listener, int parties) {
+    return check_drnn(c, 1) || check_att(c, at) || check_parties(parties) ? -1 : drnn_asaved(c, at, listener != 0, parties).total;
+}
+extern "C" int64_t ganffn_drnn_party_workspace_floats(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int listener, int parties) {
+    return check_drnn(c, 1) || check_att(c, at) || check_parties(parties) ? -1 : drnn_aws(c, at, listener != 0, parties).total;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1188,24 +1245,25 @@ static int drnn_fwd(const ganffn_drnn_cfg* c, int ndir, const float* const* U, c
                     const float* const* mval, const ganffn_drnn_params* prm, const ganffn_drnn_listener_params* lp,
                     float* const* e_out, float* const* alpha, float* const* saved, float* const* workspace,
                     const uint64_t* rng, uint64_t add, void* stream, const ganffn_drnn_att* at = nullptr,
-                    const ganffn_drnn_att_params* ap = nullptr) {
+                    const ganffn_drnn_att_params* ap = nullptr, int P = 2) {
     GF_TRY(check_drnn(c, ndir));
+    GF_TRY(check_parties(P));
     const int att = at ? at->type : ATT_GENERAL;
     if (at) {
         GF_TRY(check_att(c, at));
         GF_TRY(check_att_params(at, ap, ndir));
     }
     const ganffn_drnn_att gen{ATT_GENERAL, 0};
-    const DrnnASaved sa = drnn_asaved(c, at ? at : &gen, lp != nullptr);
+    const DrnnASaved sa = drnn_asaved(c, at ? at : &gen, lp != nullptr, P);
     const int Da = at ? at->Da : 0;
     GF_CHECK_ARG(U && spk && mval && prm && e_out && alpha && saved && workspace, "drnn_fwd: null pointer");
     GF_CHECK_ARG(!(c->train && c->p > 0.f) || rng, "drnn_fwd: rng required in train mode");
     hipStream_t st = (hipStream_t)stream;
     const int S = c->S, B = c->B, Dm = c->Dm, H = c->H, He = c->He, T = S * B;
-    const DrnnSaved so = drnn_saved(c);
-    const DrnnWs wo = drnn_ws(c);
-    const DrnnLSaved sl = drnn_lsaved(c);
-    const DrnnLWs wl = drnn_lws(c);
+    const DrnnSaved so = drnn_saved(c, P);
+    const DrnnWs wo = drnn_ws(c, P);
+    const DrnnLSaved sl = drnn_lsaved(c, P);
+    const DrnnLWs wl = drnn_lws(c, P);
     if (lp)
         for (int z = 0; z < ndir; ++z)
             GF_CHECK_ARG(lp[z].l_wih && lp[z].l_whh && lp[z].l_bih && lp[z].l_bhh, "drnn_listener_fwd: direction %d: null listener parameter", z);
@@ -1243,7 +1301,7 @@ static int drnn_fwd(const ganffn_drnn_cfg* c, int ndir, const float* const* U, c
         }
         // zero initial states: G[0], Q[0], E[0], QS[0], CT[0]; alpha (entries j >= t stay zero)
         GF_TRY(memset_f(sv + so.G, (int64_t)B * H, st));
-        GF_TRY(memset_f(sv + so.Q, (int64_t)B * 2 * H, st));
+        GF_TRY(memset_f(sv + so.Q, (int64_t)B * P * H, st));
         GF_TRY(memset_f(sv + so.E, (int64_t)B * He, st));
         GF_TRY(memset_f(sv + so.QS, (int64_t)B * H, st));
         GF_TRY(memset_f(sv + so.CT, (int64_t)B * H, st));
@@ -1268,7 +1326,7 @@ static int drnn_fwd(const ganffn_drnn_cfg* c, int ndir, const float* const* U, c
         }
         GF_TRY(launch_skinny(sg, 4 * ndir, false, st));
         GateArgs ga, gp;
-        ga.B = B; ga.H = H; ga.row0 = (int)r0; ga.p = c->p; ga.train = c->train; ga.rng = rng; ga.add = add;
+        ga.B = B; ga.H = H; ga.row0 = (int)r0; ga.p = c->p; ga.train = c->train; ga.P = P; ga.rng = rng; ga.add = add;
         gp = ga;
         for (int z = 0; z < ndir; ++z) {
             float* sv = saved[z]; float* ws = workspace[z];
@@ -1277,7 +1335,7 @@ static int drnn_fwd(const ganffn_drnn_cfg* c, int ndir, const float* const* U, c
                               SITE_DRNN_G + 4u * z};
             gp.d[z] = GateDir{ws + wo.GIp, ws + wo.GHp, sv + so.QS + r0 * H, sv + so.Rp + r0 * H, sv + so.Zp + r0 * H, sv + so.Np + r0 * H,
                               sv + so.HNp + r0 * H, nullptr, spk[z] + r0, t + 1 < S ? spk[z] + r1 : nullptr, mval[z] + r0,
-                              sv + so.Q + r0 * 2 * H, sv + so.Q + r1 * 2 * H, sv + so.QN + r0 * H, sv + so.QS + r1 * H,
+                              sv + so.Q + r0 * P * H, sv + so.Q + r1 * P * H, sv + so.QN + r0 * H, sv + so.QS + r1 * H,
                               SITE_DRNN_P + 4u * z};
             if (lp) gp.d[z].QN = sv + sl.QSP + r0 * H;       // qs only; the listener kernel below writes Q / QN / QS
         }
@@ -1309,26 +1367,27 @@ static int drnn_fwd(const ganffn_drnn_cfg* c, int ndir, const float* const* U, c
             GF_LAUNCH_CHECK();
         }
         if (lp) {
-            // ---- listener: GI_l = XL[t] + QSP[t] Wih_l[:, Dm:]^T ; GH_l[p] = Q[t][p] Whh_l^T + bhh_l (p = 0, 1)
+            // ---- listener: GI_l = XL[t] + QSP[t] Wih_l[:, Dm:]^T ; GH_l[p] = Q[t][p] Whh_l^T + bhh_l (p = 0 .. P-1)
+            SkinnyProb lpr[2 * (1 + DR_MAXP)];
             for (int z = 0; z < ndir; ++z) {
                 float* sv = saved[z]; float* ws = workspace[z];
-                sg.p[3 * z] = SkinnyProb{sv + sl.QSP + r0 * H, H, lp[z].l_wih + Dm, Dm + H, sv + sl.XL + r0 * 3 * H, 3 * H, nullptr, nullptr,
-                                         ws + wl.GIl, 3 * H, B, 3 * H, H};
-                for (int pa = 0; pa < 2; ++pa)
-                    sg.p[3 * z + 1 + pa] = SkinnyProb{sv + so.Q + r0 * 2 * H + pa * H, 2 * H, lp[z].l_whh, H, nullptr, 0, nullptr, lp[z].l_bhh,
-                                                      ws + wl.GHl + pa * 3 * H, 6 * H, B, 3 * H, H};
+                lpr[(1 + P) * z] = SkinnyProb{sv + sl.QSP + r0 * H, H, lp[z].l_wih + Dm, Dm + H, sv + sl.XL + r0 * 3 * H, 3 * H, nullptr, nullptr,
+                                              ws + wl.GIl, 3 * H, B, 3 * H, H};
+                for (int pa = 0; pa < P; ++pa)
+                    lpr[(1 + P) * z + 1 + pa] = SkinnyProb{sv + so.Q + r0 * P * H + pa * H, P * H, lp[z].l_whh, H, nullptr, 0, nullptr,
+                                                           lp[z].l_bhh, ws + wl.GHl + pa * 3 * H, P * 3 * H, B, 3 * H, H};
             }
-            GF_TRY(launch_skinny(sg, 3 * ndir, false, st));
+            GF_TRY(launch_skinny_nt(lpr, (1 + P) * ndir, st));
             LGateArgs la;
-            la.B = B; la.H = H; la.row0 = (int)r0; la.p = c->p; la.train = c->train; la.rng = rng; la.add = add;
+            la.B = B; la.H = H; la.row0 = (int)r0; la.p = c->p; la.train = c->train; la.P = P; la.rng = rng; la.add = add;
             for (int z = 0; z < ndir; ++z) {
                 float* sv = saved[z]; float* ws = workspace[z];
-                la.d[z] = LGateDir{ws + wl.GIl, ws + wl.GHl, sv + so.Q + r0 * 2 * H, sv + sl.QSP + r0 * H, sv + sl.Rl + r0 * 2 * H,
-                                   sv + sl.Zl + r0 * 2 * H, sv + sl.Nl + r0 * 2 * H, sv + sl.HNl + r0 * 2 * H, spk[z] + r0,
-                                   t + 1 < S ? spk[z] + r1 : nullptr, mval[z] + r0, sv + so.Q + r1 * 2 * H, sv + so.QN + r0 * H,
+                la.d[z] = LGateDir{ws + wl.GIl, ws + wl.GHl, sv + so.Q + r0 * P * H, sv + sl.QSP + r0 * H, sv + sl.Rl + r0 * P * H,
+                                   sv + sl.Zl + r0 * P * H, sv + sl.Nl + r0 * P * H, sv + sl.HNl + r0 * P * H, spk[z] + r0,
+                                   t + 1 < S ? spk[z] + r1 : nullptr, mval[z] + r0, sv + so.Q + r1 * P * H, sv + so.QN + r0 * H,
                                    sv + so.QS + r1 * H, SITE_DRNN_L + 4u * z};
             }
-            hipLaunchKernelGGL(drnn_listener_fwd_kernel, dim3((B * 2 * H + 255) / 256, 1, ndir), dim3(256), 0, st, la);
+            hipLaunchKernelGGL(drnn_listener_fwd_kernel, dim3((B * P * H + 255) / 256, 1, ndir), dim3(256), 0, st, la);
             GF_LAUNCH_CHECK();
         }
         if (echain) continue;
@@ -1394,25 +1453,26 @@ static int drnn_bwd(const ganffn_drnn_cfg* c, int ndir, const float* const* d_e,
                     const ganffn_drnn_listener_params* lp, const ganffn_drnn_grads* grd, const ganffn_drnn_listener_grads* lg,
                     float* const* dU, const float* const* alpha, const float* const* saved, float* const* workspace,
                     const uint64_t* rng, uint64_t add, void* stream, const ganffn_drnn_att* at = nullptr,
-                    const ganffn_drnn_att_params* ap = nullptr, const ganffn_drnn_att_grads* ag = nullptr) {
+                    const ganffn_drnn_att_params* ap = nullptr, const ganffn_drnn_att_grads* ag = nullptr, int P = 2) {
     GF_TRY(check_drnn(c, ndir));
+    GF_TRY(check_parties(P));
     const int att = at ? at->type : ATT_GENERAL;
     if (at) {
         GF_TRY(check_att(c, at));
         GF_TRY(check_att_params(at, ap, ndir));
     }
     const ganffn_drnn_att gen{ATT_GENERAL, 0};
-    const DrnnASaved sa = drnn_asaved(c, at ? at : &gen, lp != nullptr);
-    const DrnnAWs wa = drnn_aws(c, at ? at : &gen, lp != nullptr);
+    const DrnnASaved sa = drnn_asaved(c, at ? at : &gen, lp != nullptr, P);
+    const DrnnAWs wa = drnn_aws(c, at ? at : &gen, lp != nullptr, P);
     const int Da = at ? at->Da : 0;
     GF_CHECK_ARG(d_e && U && spk && mval && prm && grd && dU && alpha && saved && workspace, "drnn_bwd: null pointer");
     GF_CHECK_ARG(!(c->train && c->p > 0.f) || rng, "drnn_bwd: rng required in train mode");
     hipStream_t st = (hipStream_t)stream;
     const int S = c->S, B = c->B, Dm = c->Dm, H = c->H, He = c->He, T = S * B;
-    const DrnnSaved so = drnn_saved(c);
-    const DrnnWs wo = drnn_ws(c);
-    const DrnnLSaved sl = drnn_lsaved(c);
-    const DrnnLWs wl = drnn_lws(c);
+    const DrnnSaved so = drnn_saved(c, P);
+    const DrnnWs wo = drnn_ws(c, P);
+    const DrnnLSaved sl = drnn_lsaved(c, P);
+    const DrnnLWs wl = drnn_lws(c, P);
     if (lp)
         for (int z = 0; z < ndir; ++z)
             GF_CHECK_ARG(lp[z].l_wih && lp[z].l_whh && lp[z].l_bih && lp[z].l_bhh, "drnn_listener_bwd: direction %d: null listener parameter", z);
@@ -1420,7 +1480,7 @@ static int drnn_bwd(const ganffn_drnn_cfg* c, int ndir, const float* const* d_e,
         GF_CHECK_ARG(d_e[z] && U[z] && dU[z] && saved[z] && workspace[z] && alpha[z], "drnn_bwd: direction %d: null buffer", z);
         float* ws = workspace[z];
         GF_TRY(memset_f(ws + wo.dG, (int64_t)(S + 1) * B * H, st));
-        GF_TRY(memset_f(ws + wo.dQa, (int64_t)B * 2 * H, st));
+        GF_TRY(memset_f(ws + wo.dQa, (int64_t)B * P * H, st));
         GF_TRY(memset_f(ws + wo.dEa, (int64_t)B * He, st));
         GF_TRY(memset_f(ws + wo.dXA, (int64_t)B * H, st));          // step 0 has no attention: dXA[0] = 0
         if (att == ATT_CONCAT) {            // dX (row block 0 stays zero), dP (accumulated), v partials (row block 0 stays zero)
@@ -1478,7 +1538,7 @@ static int drnn_bwd(const ganffn_drnn_cfg* c, int ndir, const float* const* d_e,
         const int64_t dEin = even ? wo.dEa : wo.dEb, dEout = even ? wo.dEb : wo.dEa;
         SkinnyGroup sg;
         GateBwdArgs gb;
-        gb.B = B; gb.row0 = (int)r0; gb.p = c->p; gb.train = c->train; gb.rng = rng; gb.add = add;
+        gb.B = B; gb.row0 = (int)r0; gb.p = c->p; gb.train = c->train; gb.P = P; gb.rng = rng; gb.add = add;
         // ---- emotion cell (per step only when the chain kernels do not apply)
         gb.H = He;
         if (!echain) {
@@ -1505,28 +1565,30 @@ static int drnn_bwd(const ganffn_drnn_cfg* c, int ndir, const float* const* d_e,
         if (lp) {
             // ---- listener + blend backward: dGI_l (party sum), dGH_l, dh' z of both party rows, d qs through the blend
             LGateBwdArgs lb;
-            lb.B = B; lb.H = H; lb.row0 = (int)r0; lb.p = c->p; lb.train = c->train; lb.rng = rng; lb.add = add;
+            lb.B = B; lb.H = H; lb.row0 = (int)r0; lb.p = c->p; lb.train = c->train; lb.P = P; lb.rng = rng; lb.add = add;
             for (int z = 0; z < ndir; ++z) {
                 const float* sv = saved[z]; float* ws = workspace[z];
                 const bool last = t == S - 1;
                 lb.d[z] = LGateBwdDir{last ? nullptr : ws + wl.dQl, ws + wo.dQSp, ws + wo.dQSg, last ? nullptr : spk[z] + r1,
                                       echain ? ws + wo.dQNall + r0 * H : ws + wo.dQN, spk[z] + r0, mval[z] + r0,
-                                      sv + sl.Rl + r0 * 2 * H, sv + sl.Zl + r0 * 2 * H, sv + sl.Nl + r0 * 2 * H, sv + sl.HNl + r0 * 2 * H,
-                                      sv + so.Q + r0 * 2 * H, ws + wl.dGIl + r0 * 3 * H, ws + wl.dGHl + r0 * 6 * H, ws + wl.dhdirl,
+                                      sv + sl.Rl + r0 * P * H, sv + sl.Zl + r0 * P * H, sv + sl.Nl + r0 * P * H, sv + sl.HNl + r0 * P * H,
+                                      sv + so.Q + r0 * P * H, ws + wl.dGIl + r0 * 3 * H, ws + wl.dGHl + r0 * P * 3 * H, ws + wl.dhdirl,
                                       ws + wl.dqs, SITE_DRNN_L + 4u * z};
             }
             hipLaunchKernelGGL(drnn_listener_bwd_kernel, dim3((B * H + 255) / 256, 1, ndir), dim3(256), 0, st, lb);
             GF_LAUNCH_CHECK();
             // ---- d ss = dGI_l Wih_l[:, Dm:] ; dQl[p] = dGH_l[p] Whh_l + dh' z (gradient wrt Q[t] through the listener)
+            SkinnyProb lpr[2 * (1 + DR_MAXP)];
             for (int z = 0; z < ndir; ++z) {
                 float* ws = workspace[z];
                 const float* wt = ws + wl.WTl;
-                sg.p[3 * z] = SkinnyProb{ws + wl.dGIl + r0 * 3 * H, 3 * H, wt, 3 * H, nullptr, 0, nullptr, nullptr, ws + wl.dss, H, B, H, 3 * H};
-                for (int pa = 0; pa < 2; ++pa)
-                    sg.p[3 * z + 1 + pa] = SkinnyProb{ws + wl.dGHl + r0 * 6 * H + pa * 3 * H, 6 * H, wt + (int64_t)H * 3 * H, 3 * H,
-                                                      ws + wl.dhdirl + pa * H, 2 * H, nullptr, nullptr, ws + wl.dQl + pa * H, 2 * H, B, H, 3 * H};
+                lpr[(1 + P) * z] = SkinnyProb{ws + wl.dGIl + r0 * 3 * H, 3 * H, wt, 3 * H, nullptr, 0, nullptr, nullptr, ws + wl.dss, H, B, H, 3 * H};
+                for (int pa = 0; pa < P; ++pa)
+                    lpr[(1 + P) * z + 1 + pa] = SkinnyProb{ws + wl.dGHl + r0 * P * 3 * H + pa * 3 * H, P * 3 * H, wt + (int64_t)H * 3 * H, 3 * H,
+                                                           ws + wl.dhdirl + pa * H, P * H, nullptr, nullptr, ws + wl.dQl + pa * H, P * H,
+                                                           B, H, 3 * H};
             }
-            GF_TRY(launch_skinny(sg, 3 * ndir, false, st));
+            GF_TRY(launch_skinny_nt(lpr, (1 + P) * ndir, st));
         }
         GateBwdArgs gg = gb;
         for (int z = 0; z < ndir; ++z) {
@@ -1638,11 +1700,11 @@ static int drnn_bwd(const ganffn_drnn_cfg* c, int ndir, const float* const* d_e,
                 tn[n++] = TnDesc{ws + wa.dXC, Da, U[z], Dm, agw + H, H + Dm, nullptr, Da, Dm, T};
             }
             if (g.g_wih && lp && lg && lg[z].l_wih) {
-                // listener: input side against [U, qs] (party-summed dGI_l), hidden side against Q[t][p] (2T rows)
+                // listener: input side against [U, qs] (party-summed dGI_l), hidden side against Q[t][p] (P T rows)
                 const ganffn_drnn_listener_grads& l = lg[z];
                 tn[n++] = TnDesc{ws + wl.dGIl, 3 * H, U[z], Dm, l.l_wih, Dm + H, l.l_bih, 3 * H, Dm, T};
                 tn[n++] = TnDesc{ws + wl.dGIl, 3 * H, sv + sl.QSP, H, l.l_wih + Dm, Dm + H, nullptr, 3 * H, H, T};
-                tn[n++] = TnDesc{ws + wl.dGHl, 3 * H, sv + so.Q, H, l.l_whh, H, l.l_bhh, 3 * H, H, 2 * T};
+                tn[n++] = TnDesc{ws + wl.dGHl, 3 * H, sv + so.Q, H, l.l_whh, H, l.l_bhh, 3 * H, H, P * T};
             }
             if (n) GF_TRY(launch_gemm_tn_grouped(tn, n, st));
         }
@@ -1685,4 +1747,28 @@ extern "C" int ganffn_drnn_att_bwd(const ganffn_drnn_cfg* c, const ganffn_drnn_a
                                    const uint64_t* rng, uint64_t add, void* stream) {
     GF_CHECK_ARG(at, "drnn_att_bwd: null attention descriptor");
     return drnn_bwd(c, ndir, d_e, U, spk, mval, prm, lprm, grd, lgrd, dU, alpha, saved, workspace, rng, add, stream, at, aprm, agrd);
+}
+
+// any party count 1 <= parties <= GANFFN_DRNN_MAX_PARTIES, every attention type, with or without listener state: the driver
+// above with P = parties (ganffn_drnn_att_* are its parties = 2 case)
+extern "C" int ganffn_drnn_party_fwd(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int parties, int ndir, const float* const* U,
+                                     const int32_t* const* spk, const float* const* mval, const ganffn_drnn_params* prm,
+                                     const ganffn_drnn_listener_params* lprm, const ganffn_drnn_att_params* aprm,
+                                     float* const* e_out, float* const* alpha, float* const* saved, float* const* workspace,
+                                     const uint64_t* rng, uint64_t add, void* stream) {
+    GF_CHECK_ARG(at, "drnn_party_fwd: null attention descriptor");
+    GF_TRY(check_parties(parties));
+    return drnn_fwd(c, ndir, U, spk, mval, prm, lprm, e_out, alpha, saved, workspace, rng, add, stream, at, aprm, parties);
+}
+extern "C" int ganffn_drnn_party_bwd(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int parties, int ndir, const float* const* d_e,
+                                     const float* const* U, const int32_t* const* spk, const float* const* mval,
+                                     const ganffn_drnn_params* prm, const ganffn_drnn_listener_params* lprm,
+                                     const ganffn_drnn_att_params* aprm, const ganffn_drnn_grads* grd,
+                                     const ganffn_drnn_listener_grads* lgrd, const ganffn_drnn_att_grads* agrd, float* const* dU,
+                                     const float* const* alpha, const float* const* saved, float* const* workspace,
+                                     const uint64_t* rng, uint64_t add, void* stream) {
+    GF_CHECK_ARG(at, "drnn_party_bwd: null attention descriptor");
+    GF_TRY(check_parties(parties));
+    return drnn_bwd(c, ndir, d_e, U, spk, mval, prm, lprm, grd, lgrd, dU, alpha, saved, workspace, rng, add, stream, at, aprm, agrd,
+                    parties);
 }

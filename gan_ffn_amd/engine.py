@@ -1009,7 +1009,8 @@ class DrnnEngine(GanEngine):
     for the whole head.  Data-parallel: the generators' gradients go through the bucketed GradReducer (all-reduce of a
     bucket overlaps the rest of that generator's backward, Adam per bucket), the head's slab is one more bucket.
     Supports every context attention type of the reference script's --attention (general — the trained configuration —,
-    simple, dot, general2, concat; two parties), with or without listener state (--active-listener: ganffn_drnn_listener_fwd /
+    simple, dot, general2, concat), 1 to ops.DRNN_MAX_PARTIES parties (qmask (S, B, P): P = 2 runs the two-party entry points
+    named here, any other P ganffn_drnn_party_fwd / _bwd; the slab does not depend on P), with or without listener state (--active-listener: ganffn_drnn_listener_fwd /
     _bwd, the 4 l_cell tensors per direction at the end of the head slab).  general runs ganffn_drnn_fwd / _bwd with the slab
     layout it always had; the other types run ganffn_drnn_att_fwd / _bwd with their attention tensors in the cell block
     (ops.DRNN_ATT_KEYS: named_parameters order).  The module path (model.GAN_FFN_DialogueRNN.forward under autograd) stays
@@ -1073,6 +1074,7 @@ class DrnnEngine(GanEngine):
         self.loss = torch.zeros(1, device=dev)
         self._shape = None
         self._cap_S = self._cap_B = 0
+        self._alloc_P = 0
         self._adds = 0
         self._base_add = 0
 
@@ -1083,24 +1085,28 @@ class DrnnEngine(GanEngine):
     def reserve(self, S, B):
         self._cap_S, self._cap_B = max(self._cap_S, S), max(self._cap_B, B)
 
-    def _prepare5(self, S, B):
-        if self._shape == (S, B):
+    def _prepare5(self, S, B, P=2):
+        if self._shape == (S, B, P):
             return
         if B > 32 or S > 112:
             raise ValueError("DrnnEngine: at most 32 dialogues of at most 112 utterances per step (the recurrence's tile and the "
                              "attention kernels' sequence limit); got S = %d, B = %d — split the batch, or run the module path "
                              "(model.GAN_FFN_DialogueRNN under autograd, which chunks by itself)" % (S, B))
-        if self._shape is None or S > self._alloc_S or B > self._alloc_B:
+        if self._shape is None or S > self._alloc_S or B > self._alloc_B or P > self._alloc_P:
             cS = self._cap_S = max(self._cap_S, S)
             cB = self._cap_B = max(self._cap_B, B)
-            self._alloc_S, self._alloc_B = cS, cB
+            cP = max(self._alloc_P, P)
+            self._alloc_S, self._alloc_B, self._alloc_P = cS, cB, cP
             dev = self.dev
             self.pass_G = {k: _Pass(n, cS, cB, dev, True) for k, n in self.G.items()}
             f32 = dict(device=dev, dtype=torch.float32)
             self.ws3 = {k: torch.empty(p_.n_ws, **f32) for k, p_ in self.pass_G.items()}     # one workspace per generator stream
             cfgc = _lib.DrnnCfg(cS, cB, self.Dm, self.H, self.He, self.p_rec, 1)
             lib = _lib.load()
-            if self.att != "general":
+            if cP != 2:          # (the recurrence's buffers grow with the party count: sized for the widest batch so far)
+                n_saved = int(lib.ganffn_drnn_party_saved_floats(C.byref(cfgc), C.byref(self.acfg), int(self.listener), cP))
+                n_ws = int(lib.ganffn_drnn_party_workspace_floats(C.byref(cfgc), C.byref(self.acfg), int(self.listener), cP))
+            elif self.att != "general":
                 n_saved = int(lib.ganffn_drnn_att_saved_floats(C.byref(cfgc), C.byref(self.acfg), int(self.listener)))
                 n_ws = int(lib.ganffn_drnn_att_workspace_floats(C.byref(cfgc), C.byref(self.acfg), int(self.listener)))
             elif self.listener:
@@ -1120,7 +1126,7 @@ class DrnnEngine(GanEngine):
                            dU_f=z(T * self.Dm), dU_b=z(T * self.Dm), saved_f=z(n_saved), saved_b=z(n_saved), ws_f=z(n_ws),
                            ws_b=z(n_ws), lin_ws=z(int(lib.ganffn_linear_bwd_workspace_floats(T, D2, D2)) + 64))
             self.ws2 = torch.zeros(4, **f32)
-        self._shape = (S, B)
+        self._shape = (S, B, P)
         for p_ in self.pass_G.values():
             p_.resize(S, B)
         self.cfg_train = _lib.DrnnCfg(S, B, self.Dm, self.H, self.He, self.p_rec, 1)
@@ -1132,7 +1138,7 @@ class DrnnEngine(GanEngine):
     def _tune_slot(self, i):
         k = ("acoustic", "visual", "text")[i % 3]
         if getattr(self, "_tune_x", (None, None))[0] != self._shape:
-            S, B = self._shape
+            S, B = self._shape[:2]
             self._tune_x = (self._shape, {m: torch.zeros(S, B, self.G[m].E, device=self.dev) for m in self.G})
         self.ws = self.ws3[k]
         # (save=True: these pass buffers and their workspace were sized for the saving mode; the next real forward overwrites)
@@ -1163,10 +1169,15 @@ class DrnnEngine(GanEngine):
         return (_lib.DrnnListenerPtrs * 2)(*out)
 
     def step(self, batch, train=True):
-        """batch: acoustic/visual/text (S,B,.), qmask (S,B,2) one-hot (zero rows on padding), umask (B,S), label (B,S) int64.
-        Returns (loss tensor, log_prob (S,B,C)).  train=False: forward + loss only (model.eval())."""
+        """batch: acoustic/visual/text (S,B,.), qmask (S,B,P) one-hot (zero rows on padding; 1 <= P <= ops.DRNN_MAX_PARTIES),
+        umask (B,S), label (B,S) int64.  Returns (loss tensor, log_prob (S,B,C)).  train=False: forward + loss only
+        (model.eval())."""
         S, B = batch["text"].shape[:2]
-        self._prepare5(S, B)
+        P = batch["qmask"].size(2)
+        if not 1 <= P <= ops.DRNN_MAX_PARTIES:
+            raise ValueError("DrnnEngine: qmask has %d parties; the recurrence kernels take 1 to %d (ops.DRNN_MAX_PARTIES) — run "
+                             "the module path (model.GAN_FFN_DialogueRNN under autograd) for more" % (P, ops.DRNN_MAX_PARTIES))
+        self._prepare5(S, B, P)
         if self.streams is None:
             return self._step(batch, train)
         # n_streams = 3: the WHOLE step runs on the tuned streams — the visual generator's stream carries the recurrence and
@@ -1250,7 +1261,12 @@ class DrnnEngine(GanEngine):
         U_, spk_, mval_ = arr([f["fusion"], f["rev_U"]]), arr([spk_f, spk_b]), arr([mval_f, mval_b])
         e_, al_, sv_, ws_ = arr([f["e_f"], f["e_b"]]), arr([f["alpha_f"], f["alpha_b"]]), arr([f["saved_f"], f["saved_b"]]), arr([f["ws_f"], f["ws_b"]])
         Pp = self._drnn_ptrs(False)
-        if self.att != "general":
+        parties = self._shape[2]
+        if parties != 2:
+            LPp = self._drnn_listener_ptrs(False) if self.listener else None
+            _lib.call("ganffn_drnn_party_fwd", C.byref(cfg), C.byref(self.acfg), parties, 2, U_, spk_, mval_, Pp, LPp,
+                      self._drnn_att_ptrs(False), e_, al_, sv_, ws_, P(rng), C.c_uint64(a_rec), st)
+        elif self.att != "general":
             LPp = self._drnn_listener_ptrs(False) if self.listener else None
             _lib.call("ganffn_drnn_att_fwd", C.byref(cfg), C.byref(self.acfg), 2, U_, spk_, mval_, Pp, LPp, self._drnn_att_ptrs(False),
                       e_, al_, sv_, ws_, P(rng), C.c_uint64(a_rec), st)
@@ -1292,7 +1308,11 @@ class DrnnEngine(GanEngine):
         # ---- the recurrence backward (weight gradients accumulate into the zeroed head slab)
         Gp = self._drnn_ptrs(True)
         de_, dU_ = arr([f["d_e_f"], f["d_e_b"]]), arr([f["dU_f"], f["dU_b"]])
-        if self.att != "general":
+        if parties != 2:
+            _lib.call("ganffn_drnn_party_bwd", C.byref(cfg), C.byref(self.acfg), parties, 2, de_, U_, spk_, mval_, Pp, LPp,
+                      self._drnn_att_ptrs(False), Gp, self._drnn_listener_ptrs(True) if self.listener else None,
+                      self._drnn_att_ptrs(True), dU_, al_, sv_, ws_, P(rng), C.c_uint64(a_rec), st)
+        elif self.att != "general":
             _lib.call("ganffn_drnn_att_bwd", C.byref(cfg), C.byref(self.acfg), 2, de_, U_, spk_, mval_, Pp, LPp,
                       self._drnn_att_ptrs(False), Gp, self._drnn_listener_ptrs(True) if self.listener else None,
                       self._drnn_att_ptrs(True), dU_, al_, sv_, ws_, P(rng), C.c_uint64(a_rec), st)

@@ -464,6 +464,7 @@ DRNN_KEYS = ["g_cell.weight_ih", "g_cell.weight_hh", "g_cell.bias_ih", "g_cell.b
              "p_cell.weight_ih", "p_cell.weight_hh", "p_cell.bias_ih", "p_cell.bias_hh",
              "e_cell.weight_ih", "e_cell.weight_hh", "e_cell.bias_ih", "e_cell.bias_hh", "attention.transform.weight"]
 DRNN_LISTENER_KEYS = ["l_cell.weight_ih", "l_cell.weight_hh", "l_cell.bias_ih", "l_cell.bias_hh"]
+DRNN_MAX_PARTIES = 16      # GANFFN_DRNN_MAX_PARTIES: qmask's party axis on the HIP recurrence is 1 .. 16 wide
 
 
 def _ptr_array(tensors):
@@ -501,7 +502,10 @@ class DialogueRNNFn(torch.autograd.Function):
     the 13 above followed by l_cell's weight_ih, weight_hh, bias_ih, bias_hh (DRNN_LISTENER_KEYS).
     cfg_dict["att"] (default "general"): the context attention type.  Other than general, the 13th tensor (general's
     transform.weight) is replaced by the type's own DRNN_ATT_KEYS tensors (none for dot, two for general2 and concat) and
-    the call goes through ganffn_drnn_att_* (cfg_dict["Da"]: concat's D_a)."""
+    the call goes through ganffn_drnn_att_* (cfg_dict["Da"]: concat's D_a).
+    cfg_dict["parties"] (default 2): the width P of qmask's party axis.  P = 2 makes the calls above; any other P (1 ..
+    DRNN_MAX_PARTIES) goes through ganffn_drnn_party_*, general attention included (its transform.weight as the attention
+    parameter), with the same arguments and gradients."""
 
     @staticmethod
     def forward(ctx, meta, *args):
@@ -529,7 +533,11 @@ class DialogueRNNFn(torch.autograd.Function):
         cfg = _lib.DrnnCfg(S, B, Dm, H, He, float(meta["p"]), 1 if train else 0)
         lib = _lib.load()
         acfg = _lib.DrnnAtt(_lib.DRNN_ATT_TYPES[att], int(meta.get("Da", 0)))
-        if aprm is not None:
+        parties = int(meta.get("parties", 2))
+        if parties != 2:
+            n_saved = int(lib.ganffn_drnn_party_saved_floats(C.byref(cfg), C.byref(acfg), int(listener), parties))
+            n_ws = int(lib.ganffn_drnn_party_workspace_floats(C.byref(cfg), C.byref(acfg), int(listener), parties))
+        elif aprm is not None:
             n_saved = int(lib.ganffn_drnn_att_saved_floats(C.byref(cfg), C.byref(acfg), int(listener)))
             n_ws = int(lib.ganffn_drnn_att_workspace_floats(C.byref(cfg), C.byref(acfg), int(listener)))
         elif listener:
@@ -547,7 +555,13 @@ class DialogueRNNFn(torch.autograd.Function):
         rng = DeviceRng.get(dev)
         add = rng.next_add() if train else 0
         P = (_lib.DrnnPtrs * ndir)(*[_drnn_ptrs(p) for p in prm])
-        if aprm is not None:
+        if parties != 2:
+            LP = (_lib.DrnnListenerPtrs * ndir)(*[_drnn_ptrs(p, _lib.DrnnListenerPtrs) for p in lprm]) if listener else None
+            AP = (_lib.DrnnAttPtrs * ndir)(*[_att_ptrs(att, a) for a in (aprm or [[p[12]] for p in prm])])
+            _lib.call("ganffn_drnn_party_fwd", C.byref(cfg), C.byref(acfg), parties, ndir, _ptr_array(U), _ptr_array(spk),
+                      _ptr_array(mval), P, LP, AP, _ptr_array(e), _ptr_array(alpha), _ptr_array(saved), _ptr_array(ws),
+                      _ptr(rng.state), C.c_uint64(add), _stream())
+        elif aprm is not None:
             LP = (_lib.DrnnListenerPtrs * ndir)(*[_drnn_ptrs(p, _lib.DrnnListenerPtrs) for p in lprm]) if listener else None
             AP = (_lib.DrnnAttPtrs * ndir)(*[_att_ptrs(att, a) for a in aprm])
             _lib.call("ganffn_drnn_att_fwd", C.byref(cfg), C.byref(acfg), ndir, _ptr_array(U), _ptr_array(spk), _ptr_array(mval), P,
@@ -562,7 +576,7 @@ class DialogueRNNFn(torch.autograd.Function):
             _lib.call("ganffn_drnn_fwd", C.byref(cfg), ndir, _ptr_array(U), _ptr_array(spk), _ptr_array(mval), P, _ptr_array(e),
                       _ptr_array(alpha), _ptr_array(saved), _ptr_array(ws), _ptr(rng.state), C.c_uint64(add), _stream())
         ctx.cfg, ctx.ndir, ctx.add, ctx.rng_state = cfg, ndir, add, rng.state
-        ctx.att, ctx.acfg, ctx.aprm = att, acfg, aprm
+        ctx.att, ctx.acfg, ctx.aprm, ctx.parties = att, acfg, aprm, parties
         ctx.keep = (U, spk, mval, prm, lprm, alpha, saved, ws)
         out = []
         for z in range(ndir):
@@ -579,6 +593,25 @@ class DialogueRNNFn(torch.autograd.Function):
         grads = [[torch.zeros_like(p) if p is not None else None for p in prm[z]] for z in range(ndir)]
         P = (_lib.DrnnPtrs * ndir)(*[_drnn_ptrs(p) for p in prm])
         G = (_lib.DrnnPtrs * ndir)(*[_drnn_ptrs(g) for g in grads])
+        if ctx.parties != 2:
+            general = ctx.aprm is None        # (general: transform.weight and its gradient are the attention's own parameter)
+            aprm = [[p[12]] for p in prm] if general else ctx.aprm
+            agrads = [[g[12]] for g in grads] if general else [[torch.zeros_like(p) for p in aprm[z]] for z in range(ndir)]
+            AP = (_lib.DrnnAttPtrs * ndir)(*[_att_ptrs(ctx.att, a) for a in aprm])
+            AG = (_lib.DrnnAttPtrs * ndir)(*[_att_ptrs(ctx.att, a) for a in agrads])
+            if lprm is not None:
+                lgrads = [[torch.zeros_like(p) for p in lprm[z]] for z in range(ndir)]
+                LP = (_lib.DrnnListenerPtrs * ndir)(*[_drnn_ptrs(p, _lib.DrnnListenerPtrs) for p in lprm])
+                LG = (_lib.DrnnListenerPtrs * ndir)(*[_drnn_ptrs(g, _lib.DrnnListenerPtrs) for g in lgrads])
+            else:
+                lgrads, LP, LG = [[] for _ in range(ndir)], None, None
+            _lib.call("ganffn_drnn_party_bwd", C.byref(cfg), C.byref(ctx.acfg), ctx.parties, ndir, _ptr_array(d_e), _ptr_array(U),
+                      _ptr_array(spk), _ptr_array(mval), P, LP, AP, G, LG, AG, _ptr_array(dU), _ptr_array(alpha), _ptr_array(saved),
+                      _ptr_array(ws), _ptr(ctx.rng_state), C.c_uint64(ctx.add), _stream())
+            out = [None]
+            for z in range(ndir):
+                out += [dU[z], None, None] + (grads[z] if general else grads[z][:12] + agrads[z]) + lgrads[z]
+            return tuple(out)
         if ctx.aprm is not None:
             agrads = [[torch.zeros_like(p) for p in ctx.aprm[z]] for z in range(ndir)]
             AP = (_lib.DrnnAttPtrs * ndir)(*[_att_ptrs(ctx.att, a) for a in ctx.aprm])
@@ -620,8 +653,9 @@ _CHECK_QMASK = __import__("os").environ.get("GANFFN_CHECK_QMASK", "0") == "1"
 def dialogue_rnn_supported(cell, U, qmask):
     """the configurations the HIP recurrence implements: every context attention type — general (the trained
     configuration), simple (DialogueRNNCell's constructor default; run as general attention with a constant query:
-    _drnn_cell_args), dot (D_m = D_g), general2, concat (D_a % 4 == 0, D_a <= 512) — no listener, two parties, dims % 4,
-    D_g = D_p <= 512 (the attention kernels keep one state column per thread), at most 112 steps, on a GPU.
+    _drnn_cell_args), dot (D_m = D_g), general2, concat (D_a % 4 == 0, D_a <= 512) — no listener, 1 to DRNN_MAX_PARTIES
+    parties (qmask.size(2)), dims % 4, D_g = D_p <= 512 (the attention kernels keep one state column per thread), at most
+    112 steps, on a GPU.
     PRECONDITION (not tested here: the test would be a device->host sync in front of ~760 latency-sized launches): every
     qmask row is one-hot or all zero, as the reference's loaders produce (dataloader.py:41-50) — the gate kernels use
     (argmax, value at argmax) only.  GANFFN_CHECK_QMASK=1 verifies it on every call."""
@@ -654,7 +688,7 @@ def drnn_att_limits_hold(cell):
 
 def _drnn_limits_hold(cell, U, qmask):
     ok = (U.is_cuda and drnn_att_limits_hold(cell)
-          and qmask.size(2) == 2 and cell.D_g == cell.D_p and cell.D_g <= 512 and cell.D_m % 4 == 0 and cell.D_g % 4 == 0
+          and 1 <= qmask.size(2) <= DRNN_MAX_PARTIES and cell.D_g == cell.D_p and cell.D_g <= 512 and cell.D_m % 4 == 0 and cell.D_g % 4 == 0
           and cell.D_e % 4 == 0 and U.size(0) <= 112)
     if ok and _CHECK_QMASK:
         ok = bool((((qmask == 0) | (qmask == 1)).all() & (qmask.sum(2) <= 1).all()).item())
@@ -712,7 +746,8 @@ def dialogue_rnn_run(cells, Us, qmasks, training):
             mval = qm.gather(2, spk.unsqueeze(2)).squeeze(2)
             Ux, params = _drnn_cell_args(cells[z], Us[z][:, b0:b1])
             args += [Ux.contiguous(), spk, mval] + params
-        meta = {"p": float(cells[0].dropout.p), "train": bool(training), "listener": bool(cells[0].listener_state)}
+        meta = {"p": float(cells[0].dropout.p), "train": bool(training), "listener": bool(cells[0].listener_state),
+                "parties": int(qmasks[0].size(2))}
         att = drnn_att_type(cells[0])
         if att not in ("general", "simple"):
             meta["att"] = att

@@ -237,7 +237,9 @@ int ganffn_general2_attention_bwd(const float* d_att, const float* x, const floa
 /* ---- N2 (config 5): the DialogueRNN recurrence ------------------------------------------ */
 /* Replaces DialogueRNN.forward / DialogueRNNCell.forward (model.py:828-972) in the configuration
  * train_IEMOCAP_DialogueRNN.py runs: context_attention = "general" (:586), listener_state = False (:595), two parties
- * (listener state: ganffn_drnn_listener_*; the other attention types, with or without it: ganffn_drnn_att_* below).
+ * (listener state: ganffn_drnn_listener_*; the other attention types, with or without it: ganffn_drnn_att_* below; any
+ * party count from 1 to GANFFN_DRNN_MAX_PARTIES, every attention type, with or without listener state:
+ * ganffn_drnn_party_* at the end of this section, of which the two-party entry points are the parties = 2 case).
  * One call runs ndir (1 or 2) independent DialogueRNNs — BiModel's forward and reverse directions (model.py:1025-1033)
  * — through the same launches.  Per direction:
  *   U [S x B x D_m] (the reverse direction gets the reversed sequences, as BiModel._reverse_seq builds them),
@@ -343,6 +345,35 @@ int ganffn_drnn_att_bwd(const ganffn_drnn_cfg* cfg, const ganffn_drnn_att* att, 
                         const ganffn_drnn_listener_grads* lgrads, const ganffn_drnn_att_grads* agrads, float* const* dU,
                         const float* const* alpha, const float* const* saved, float* const* workspace,
                         const uint64_t* rng, uint64_t rng_offset_add, void* stream);
+
+/* Any number of parties (DialogueRNNCell with qmask [S x B x P], model.py:861-926; MELD's speaker one-hots are 9 wide):
+ * ganffn_drnn_att_* with one more argument, parties = P, 1 <= P <= GANFFN_DRNN_MAX_PARTIES (anything else is an argument
+ * error reported through ganffn_last_error).  spk (argmax over the P columns) must be < P, as it is < 2 above.  The party
+ * states are [B x P x H]: the speaker's row takes the party cell's step, the other P - 1 rows keep their state (with
+ * listener state every row takes the listener step, then the blend).  general attention goes through it like the
+ * others: aparams[z].w = transform.weight.  saved / workspace are sized by ganffn_drnn_party_saved_floats /
+ * _workspace_floats(cfg, att, listener, parties) (per direction); at parties = 2 they equal the _att_ sizes and every
+ * call is the same launch sequence as ganffn_drnn_att_*, bit for bit.
+ * Dropout: the party cell's site 9 (+ 4) mask is one row of width H per (t, b), shared by all party rows (only the
+ * speaker's row is used); the listener's site 11 (+ 4) mask is row t*B + b, column p*H + u of a width-P*H row, i.e.
+ * keep_mask(S*B, P*H, p, 11 + 4*z, seed, offset).view(S, B, P, H) — the two-party layout above at P = 2.
+ * Launches per step: 2 + 2 without listener state for any P; 4 + 4 with it (the listener's products of a step are one
+ * launch of 2 (1 + P) skinny problems: the bound on P is what that launch's argument block holds). */
+#define GANFFN_DRNN_MAX_PARTIES 16
+int64_t ganffn_drnn_party_saved_floats(const ganffn_drnn_cfg* cfg, const ganffn_drnn_att* att, int listener, int parties);
+int64_t ganffn_drnn_party_workspace_floats(const ganffn_drnn_cfg* cfg, const ganffn_drnn_att* att, int listener, int parties);
+int ganffn_drnn_party_fwd(const ganffn_drnn_cfg* cfg, const ganffn_drnn_att* att, int parties, int ndir, const float* const* U,
+                          const int32_t* const* spk, const float* const* mval, const ganffn_drnn_params* params,
+                          const ganffn_drnn_listener_params* lparams, const ganffn_drnn_att_params* aparams,
+                          float* const* e_out, float* const* alpha, float* const* saved, float* const* workspace,
+                          const uint64_t* rng, uint64_t rng_offset_add, void* stream);
+int ganffn_drnn_party_bwd(const ganffn_drnn_cfg* cfg, const ganffn_drnn_att* att, int parties, int ndir, const float* const* d_e,
+                          const float* const* U, const int32_t* const* spk, const float* const* mval,
+                          const ganffn_drnn_params* params, const ganffn_drnn_listener_params* lparams,
+                          const ganffn_drnn_att_params* aparams, const ganffn_drnn_grads* grads,
+                          const ganffn_drnn_listener_grads* lgrads, const ganffn_drnn_att_grads* agrads, float* const* dU,
+                          const float* const* alpha, const float* const* saved, float* const* workspace,
+                          const uint64_t* rng, uint64_t rng_offset_add, void* stream);
 
 /* Data movement of BiModel.forward around the recurrence (model.py:1008-1062), one launch each (csrc/drnn_head.hip):
  * ganffn_seq_reverse: out[s, b, :] (+)= s < lens[b] ? x[lens[b]-1-s, b, :] : 0 — BiModel._reverse_seq and, being its own
