@@ -21,6 +21,12 @@ class LstmCfg(C.Structure):
     _fields_ = [("S", C.c_int32), ("B", C.c_int32), ("In", C.c_int32), ("H", C.c_int32)]
 
 
+class LstmStackCfg(C.Structure):
+    """ganffn_lstm_stack_cfg"""
+    _fields_ = [("S", C.c_int32), ("B", C.c_int32), ("In", C.c_int32), ("H", C.c_int32), ("L", C.c_int32), ("p", C.c_float),
+                ("train", C.c_int32)]
+
+
 class HeadCfg(C.Structure):
     _fields_ = [("T", C.c_int32), ("E", C.c_int32), ("D1", C.c_int32), ("D2", C.c_int32), ("kind", C.c_int32),
                 ("p", C.c_float), ("train", C.c_int32)]
@@ -92,6 +98,13 @@ SIGNATURES = {
     "ganffn_lstm_workspace_floats": (_L, [C.POINTER(LstmCfg)]),
     "ganffn_lstm_layer_fwd": (_I, [C.POINTER(LstmCfg), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ganffn_lstm_layer_bwd": (_I, [C.POINTER(LstmCfg), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ganffn_lstm_stack_saved_floats": (_L, [C.POINTER(LstmStackCfg)]),
+    "ganffn_lstm_stack_workspace_floats": (_L, [C.POINTER(LstmStackCfg)]),
+    "ganffn_lstm_stack_fwd": (_I, [C.POINTER(LstmStackCfg)] + [_P] * 9 + [_U64, _P]),
+    "ganffn_lstm_stack_bwd": (_I, [C.POINTER(LstmStackCfg)] + [_P] * 13 + [_U64, _P]),
+    "ganffn_meld_head_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "ganffn_meld_head_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "ganffn_zero_floats": (_I, [_P, _L, _P]),
     "ganffn_adam_step_parts": (_I, [_P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _P, _L, _I, _L, _L, _L, _P]),
     "ganffn_encoder_bwd_parts_supported": (_I, [_PE]),
     "ganffn_encoder_bwd_parts_covered": (_L, [_I, _I]),

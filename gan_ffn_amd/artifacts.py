@@ -158,14 +158,18 @@ def write_test_report(best_loss, labels, preds, masks, g_epochs, out_dir="./outp
 # ------------------------------------------------------------------------------------------------
 # phase-2 epoch loop (counterpart of train_or_eval_model, with the :679 argument slip fixed)
 # ------------------------------------------------------------------------------------------------
-def train_or_eval_model(engine, loader, train=False, device="cuda"):
+def train_or_eval_model(engine, loader, train=False, device="cuda", to_batch=None):
     """One epoch of the classifier over `loader` (batches as data.get_IEMOCAP_loaders yields them) through
     engine.Phase2Engine.  Returns (avg_loss, avg_accuracy, labels, preds, masks, avg_fscore, [[], [], [], vids]) like
-    train_IEMOCAP.py:189-197 (GAN_FFN has no attention weights: the alpha lists stay empty)."""
+    train_IEMOCAP.py:189-197 (GAN_FFN has no attention weights: the alpha lists stay empty).
+    to_batch: collated batch -> engine batch (default data.to_batch, the IEMOCAP one).  With engine.MeldEngine and
+    data.to_meld_batch this is train_MELD.py:50-104: an engine that has `.alpha` (the (B, S, S) attention weights of its last
+    step) fills the first list, on eval batches, with one (B, S) tensor per query step like the script's `alphas += alpha`."""
     from . import data as D
-    losses, preds, labels, masks, vids = [], [], [], [], []
+    to_batch = to_batch or D.to_batch
+    losses, preds, labels, masks, vids, alphas = [], [], [], [], [], []
     for collated in loader:
-        batch = D.to_batch(collated, device)
+        batch = to_batch(collated, device)
         loss, log_prob = engine.step(batch, train=train)
         pred = engine.predictions(log_prob)
         m = batch["umask"].reshape(-1).cpu().numpy()
@@ -175,11 +179,14 @@ def train_or_eval_model(engine, loader, train=False, device="cuda"):
         losses.append(float(loss) * m.sum())
         if not train and batch.get("vids"):
             vids += batch["vids"]
+        if not train and getattr(engine, "alpha", None) is not None:
+            a = engine.alpha.clone()                     # (the engine's buffer is overwritten by the next step)
+            alphas += [a[:, t, :] for t in range(a.size(1))]
     if not preds:
         return float("nan"), float("nan"), [], [], [], float("nan"), []
     preds, labels, masks = np.concatenate(preds), np.concatenate(labels), np.concatenate(masks)
     avg_loss, avg_acc, avg_f = epoch_metrics(losses, labels, preds, masks)
-    return avg_loss, avg_acc, labels, preds, masks, avg_f, [[], [], [], vids]
+    return avg_loss, avg_acc, labels, preds, masks, avg_f, [alphas, [], [], vids]
 
 
 def run_training(dataset_path, g_epochs=150, n_epochs=160, lr=1e-4, l2=0.008, batch_size=32, out_dir="./output/",
@@ -216,6 +223,33 @@ def run_training(dataset_path, g_epochs=150, n_epochs=160, lr=1e-4, l2=0.008, ba
                                                                  te[0], te[1], te[5]))
     file_name, f1 = write_test_report(best[0], best[2], best[3], best[4], g_epochs, out_dir)
     return file_name, f1, df
+
+
+def run_meld_training(pickle_path, n_epochs=50, lr=3e-4, l2=1e-4, dropout=0.6, batch_size=32, classify="emotion", device="cuda",
+                      seed=None, log=print):
+    """The __main__ flow of train_MELD.py:143-195 on the HIP path: MELDLSTMModel(600, 300, 600) through engine.MeldEngine,
+    MaskedNLLLoss without class weights, Adam(lr, weight_decay = l2), loaders with valid = 0.0, the per-epoch line, and the
+    test epoch with the best F-score kept.  Returns (best_loss, best_fscore, labels, preds, masks, attentions)."""
+    from . import data as D, engine as E, dialogue_rnn as DR
+    if seed is not None:
+        torch.manual_seed(seed)
+    n_classes = 7 if classify == "emotion" else 3                                 # train_MELD.py:138-141
+    model = DR.MELDLSTMModel(600, 300, 600, n_classes=n_classes, dropout=dropout).to(device)
+    eng = E.MeldEngine(model, lr=lr, weight_decay=l2)
+    train_loader, valid_loader, test_loader = D.get_MELD_loaders(pickle_path, batch_size=batch_size, valid=0.0, classify=classify)
+    eng.reserve(33, batch_size)                      # MELD's longest dialogue
+    best = None
+    for e in range(n_epochs):
+        tr = train_or_eval_model(eng, train_loader, True, device, D.to_meld_batch)
+        va = train_or_eval_model(eng, valid_loader, False, device, D.to_meld_batch)
+        te = train_or_eval_model(eng, test_loader, False, device, D.to_meld_batch)
+        if best is None or best[5] < te[5]:                                       # train_MELD.py:175: best TEST F-score
+            best = te
+        if log:
+            log("epoch {} train_loss {} train_acc {} train_fscore {} valid_loss {} valid_acc {} val_fscore {} "
+                "test_loss {} test_acc {} test_fscore {}".format(e + 1, tr[0], tr[1], tr[5], va[0], va[1], va[5],
+                                                                 te[0], te[1], te[5]))
+    return best[0], best[5], best[2], best[3], best[4], best[6]
 
 
 class _DeviceBatches:

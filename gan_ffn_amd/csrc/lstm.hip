@@ -20,6 +20,9 @@
 //     is kept and four TN GEMMs after the loop compute dW_ih = dG^T x and dW_hh = dG^T h_prev over all tokens (owner-accumulated or
 //     slab + ordered reduce: no atomics), the bias gradients are fixed-order column sums, dx = sum_d dG_d W_ih_d two NN GEMMs.
 // Deterministic: no atomics anywhere.  B <= 32 per call (the skinny kernels' dialogue tile); the Python side chunks larger batches.
+// ganffn_lstm_stack_fwd / _bwd (end of the file) chain the L layers of the stack in one call, with nn.LSTM's inter-layer dropout
+// (Philox site 64 + l, offset base + l) between them: the same launches as L per-layer calls and L - 1 ganffn_dropout calls, so
+// the same bits — what engine.MeldEngine runs instead of ops.lstm_forward's autograd chain.
 #include "common.h"
 
 namespace ganffn {
@@ -112,11 +115,47 @@ int64_t lstm_ws(const ganffn_lstm_cfg* c) {
     return (fwd > bwd ? fwd : bwd) + 64;
 }
 
+// ---- the whole stack (ganffn_lstm_stack_*): L layers chained, nn.LSTM's inter-layer dropout between them
+constexpr uint32_t SITE_LSTM0 = 64;                      // + layer (ops.SITE_LSTM): the dropout behind every layer but the last
+
+inline ganffn_lstm_cfg stack_layer_cfg(const ganffn_lstm_stack_cfg* c, int l) {
+    return ganffn_lstm_cfg{c->S, c->B, l == 0 ? c->In : 2 * c->H, c->H};
+}
+// saved: per layer the layer's own block (gates | c: 10 T H floats whatever its input width), then per layer but the last
+// its output [T x 2H] and the dropped output [T x 2H] the next layer reads (unused when no dropout is active)
+struct LstmStackOff { int64_t layer_stride, outs, total; };
+LstmStackOff lstm_stack_saved(const ganffn_lstm_stack_cfg* c) {
+    const int64_t T = (int64_t)c->S * c->B, H = c->H;
+    LstmStackOff o;
+    o.layer_stride = 10 * T * H;
+    o.outs = c->L * o.layer_stride;
+    o.total = o.outs + (int64_t)(c->L - 1) * 2 * T * 2 * H;
+    return o;
+}
+// workspace: the widest layer's own workspace (16-byte rounded) | two [T x 2H] gradient buffers the backward alternates between
+int64_t lstm_stack_layer_ws(const ganffn_lstm_stack_cfg* c) {
+    int64_t m = 0;
+    for (int l = 0; l < c->L; ++l) {
+        const ganffn_lstm_cfg lc = stack_layer_cfg(c, l);
+        const int64_t w = lstm_ws(&lc);
+        m = w > m ? w : m;
+    }
+    return (m + 3) & ~(int64_t)3;
+}
+
 int check_lstm(const ganffn_lstm_cfg* c) {
     GF_CHECK_ARG(c, "null lstm cfg");
     GF_CHECK_ARG(c->S >= 1 && c->B >= 1 && c->B <= 32, "lstm: S=%d B=%d (B <= 32 per call)", c->S, c->B);
     GF_CHECK_ARG(c->In >= 4 && (c->In & 3) == 0 && c->H >= 4 && (c->H & 3) == 0, "lstm: In=%d H=%d must be multiples of 4", c->In, c->H);
     return 0;
+}
+
+int check_lstm_stack(const ganffn_lstm_stack_cfg* c) {
+    GF_CHECK_ARG(c, "null lstm stack cfg");
+    GF_CHECK_ARG(c->L >= 1 && c->L <= 16, "lstm stack: L=%d (1 .. 16 layers)", c->L);
+    GF_CHECK_ARG(c->p >= 0.f && c->p < 1.f, "lstm stack: dropout p=%g must be in [0, 1)", (double)c->p);
+    const ganffn_lstm_cfg l0 = stack_layer_cfg(c, 0);
+    return check_lstm(&l0);
 }
 
 }  // namespace
@@ -242,6 +281,70 @@ extern "C" int ganffn_lstm_layer_bwd(const ganffn_lstm_cfg* c, const float* d_ou
         EpiArgs e1;
         e1.aux_in = dx;                              // + the reverse direction's share (each element read and written by one thread)
         GF_TRY(launch_gemm_nn(dG + T * 4 * H, 4 * H, w_ih[1], In, dx, In, (int)T, In, 4 * H, EPI_NONE, e1, st));
+    }
+    return 0;
+}
+
+// ---- L layers in one call -------------------------------------------------------------------------------------------
+extern "C" int64_t ganffn_lstm_stack_saved_floats(const ganffn_lstm_stack_cfg* c) { return check_lstm_stack(c) ? -1 : lstm_stack_saved(c).total; }
+extern "C" int64_t ganffn_lstm_stack_workspace_floats(const ganffn_lstm_stack_cfg* c) {
+    return check_lstm_stack(c) ? -1 : lstm_stack_layer_ws(c) + 2 * (int64_t)c->S * c->B * 2 * c->H;
+}
+
+// The per-layer entry points above, chained (same launches, same bits), with nn.LSTM(dropout = p)'s dropout on the output of every
+// layer but the last: site SITE_LSTM0 + l, offset rng_offset_add + l — what ops.lstm_forward issues as separate calls.
+extern "C" int ganffn_lstm_stack_fwd(const ganffn_lstm_stack_cfg* c, const float* x, const float* const* w_ih, const float* const* w_hh,
+                                     const float* const* b_ih, const float* const* b_hh, float* out, float* saved, float* workspace,
+                                     const uint64_t* rng, uint64_t rng_offset_add, void* stream) {
+    GF_TRY(check_lstm_stack(c));
+    GF_CHECK_ARG(x && w_ih && w_hh && b_ih && b_hh && out && saved && workspace, "lstm_stack_fwd: null pointer");
+    const bool drop = c->train && c->p > 0.f && c->L > 1;
+    GF_CHECK_ARG(!drop || rng, "lstm_stack_fwd: rng required in train mode");
+    const int64_t T = (int64_t)c->S * c->B, H = c->H;
+    const LstmStackOff so = lstm_stack_saved(c);
+    const float* in = x;
+    for (int l = 0; l < c->L; ++l) {
+        const ganffn_lstm_cfg lc = stack_layer_cfg(c, l);
+        const bool last = l + 1 == c->L;
+        float* o = last ? out : saved + so.outs + (int64_t)l * 2 * T * 2 * H;
+        GF_TRY(ganffn_lstm_layer_fwd(&lc, in, w_ih + 2 * l, w_hh + 2 * l, b_ih + 2 * l, b_hh + 2 * l, o, saved + l * so.layer_stride,
+                                     workspace, stream));
+        in = o;
+        if (!last && drop) {
+            float* dr = o + T * 2 * H;
+            GF_TRY(launch_dropout(o, dr, (int)T, 2 * (int)H, c->p, SITE_LSTM0 + l, rng, rng_offset_add + l, 1, (hipStream_t)stream));
+            in = dr;
+        }
+    }
+    return 0;
+}
+
+// x, out: the forward's; gw_* / gb_*: arrays of [L][2] pointers, ACCUMULATED into like the per-layer backward (NULL arrays or
+// entries: not wanted); dx [S x B x In] may be NULL.  The dropout masks are regenerated from {rng, rng_offset_add}.
+extern "C" int ganffn_lstm_stack_bwd(const ganffn_lstm_stack_cfg* c, const float* d_out, const float* x, const float* out,
+                                     const float* const* w_ih, const float* const* w_hh, float* dx, float* const* gw_ih,
+                                     float* const* gw_hh, float* const* gb_ih, float* const* gb_hh, const float* saved,
+                                     float* workspace, const uint64_t* rng, uint64_t rng_offset_add, void* stream) {
+    GF_TRY(check_lstm_stack(c));
+    GF_CHECK_ARG(d_out && x && out && w_ih && w_hh && saved && workspace, "lstm_stack_bwd: null pointer");
+    const bool drop = c->train && c->p > 0.f && c->L > 1;
+    GF_CHECK_ARG(!drop || rng, "lstm_stack_bwd: rng required in train mode");
+    const int64_t T = (int64_t)c->S * c->B, H = c->H;
+    const LstmStackOff so = lstm_stack_saved(c);
+    float* dbuf = workspace + lstm_stack_layer_ws(c);          // [2][T x 2H]
+    const float* d = d_out;
+    for (int l = c->L - 1; l >= 0; --l) {
+        const ganffn_lstm_cfg lc = stack_layer_cfg(c, l);
+        const float* o = l + 1 == c->L ? out : saved + so.outs + (int64_t)l * 2 * T * 2 * H;
+        const float* prev = l == 0 ? nullptr : saved + so.outs + (int64_t)(l - 1) * 2 * T * 2 * H;
+        const float* in = l == 0 ? x : drop ? prev + T * 2 * H : prev;
+        float* dxl = l == 0 ? dx : dbuf + (int64_t)(l & 1) * T * 2 * H;
+        GF_TRY(ganffn_lstm_layer_bwd(&lc, d, in, o, w_ih + 2 * l, w_hh + 2 * l, dxl, gw_ih ? gw_ih + 2 * l : nullptr,
+                                     gw_hh ? gw_hh + 2 * l : nullptr, gb_ih ? gb_ih + 2 * l : nullptr, gb_hh ? gb_hh + 2 * l : nullptr,
+                                     saved + l * so.layer_stride, workspace, stream));
+        if (l > 0 && drop)
+            GF_TRY(launch_dropout(dxl, dxl, (int)T, 2 * (int)H, c->p, SITE_LSTM0 + (l - 1), rng, rng_offset_add + (l - 1), 1, (hipStream_t)stream));
+        d = dxl;
     }
     return 0;
 }

@@ -169,6 +169,39 @@ def to_batch(collated, device="cuda"):
             "label": mv(label.long()).contiguous(), "vids": collated[6] if len(collated) > 6 else None}
 
 
+def to_meld_batch(collated, device="cuda"):
+    """one collated MELD batch (text, audio, qmask, umask, label, vids — MELDDataset.collate_fn, unpacked at
+    train_MELD.py:65-66) -> the dict engine.MeldEngine takes, moved to `device` once.  The model reads the text features
+    alone (train_MELD.py:71); `acoustic` and `qmask` are carried along."""
+    textf, acouf, qmask, umask, label = collated[:5]
+    mv = lambda t: t.to(device, non_blocking=True)
+    return {"text": mv(textf.float()).contiguous(), "acoustic": mv(acouf.float()).contiguous(), "qmask": mv(qmask),
+            "umask": mv(umask.float()).contiguous(), "label": mv(label.long()).contiguous(),
+            "vids": collated[5] if len(collated) > 5 else None}
+
+
+def write_synthetic_meld_pickle(path, n_train=12, n_test=5, seed=3407, lo=3, hi=33, dtype=np.float32):
+    """A small pickle with the 9-tuple MELD schema MELDDataset unpickles (dataloader.py:93-95) and seeded content: text 600
+    and audio 300 wide, 9 speakers one-hot, 7 emotion / 3 sentiment labels, ragged lengths lo .. hi <= 33 (tests, smoke runs;
+    the real MELD_features_raw.pkl is not shipped)."""
+    import pickle
+    rng = np.random.default_rng(seed)
+    ids, spk, emo, txt, aud, sen, sent = {}, {}, {}, {}, {}, {}, {}
+    names = list(range(n_train + n_test))                # MELD's dialogue ids are integers
+    for n in names:
+        L = int(rng.integers(lo, hi + 1))
+        ids[n] = ["dia%d_utt%d" % (n, j) for j in range(L)]
+        spk[n] = np.eye(9, dtype=np.float32)[rng.integers(0, 9, L)].tolist()
+        emo[n] = [int(x) for x in rng.integers(0, 7, L)]
+        sent[n] = [int(x) for x in rng.integers(0, 3, L)]
+        txt[n] = (rng.standard_normal((L, MELD_DIMS["text"])) * 0.5).astype(dtype)
+        aud[n] = (rng.standard_normal((L, MELD_DIMS["acoustic"])) * 0.5).astype(dtype)
+        sen[n] = ["utt %d" % j for j in range(L)]
+    with open(path, "wb") as f:
+        pickle.dump((ids, spk, emo, txt, aud, sen, names[:n_train], names[n_train:], sent), f)
+    return names[:n_train], names[n_train:]
+
+
 def write_synthetic_iemocap_pickle(path, n_train=12, n_test=5, seed=3407, lo=4, hi=23, dtype=np.float64):
     """A small pickle with the IEMOCAP schema and seeded content (tests, smoke runs; the real one is not shipped)."""
     import pickle

@@ -1368,3 +1368,172 @@ class DrnnEngine(GanEngine):
     @staticmethod
     def predictions(log_prob):
         return log_prob.transpose(0, 1).reshape(-1, log_prob.shape[2]).argmax(1)
+
+
+# ================================================================================================
+# MELD: MELDLSTMModel classifier step     (/root/reference/train_MELD.py:50-104,147-157, model.py:520-562)
+# ================================================================================================
+class MeldEngine(_Runner):
+    """One train / eval step of MELDLSTMModel (the att2 = True branch train_MELD.py:71 runs) on the C ABI, no autograd graph:
+    the 4-layer bidirectional LSTM with its inter-layer dropout as ONE library call (ganffn_lstm_stack_fwd / _bwd), matchatt's
+    transform (ganffn_linear_*), the masked general2 attention (ganffn_general2_attention_*), hardswish(emotions + hardswish(att))
+    and smax_fc as one launch each way (ganffn_meld_head_*), log-softmax + MaskedNLLLoss — without class weights by default, as
+    train_MELD.py:154 — and Adam (lr 3e-4, L2 1e-4: train_MELD.py:111-112,155-157) as ONE fused launch over one parameter slab:
+    the LSTM's 32 tensors in named_parameters() order, matchatt.transform.{weight, bias}, smax_fc.{weight, bias}.
+    `linear.{weight, bias}` serve the att2 = False branch only: their .grad is None in the reference, torch.optim.Adam skips such
+    parameters entirely (no weight decay either), so they stay off the slab and are never touched.
+    Limits (ValueError; MELDLSTMModel under autograd — the module path — runs the rest): at most 32 dialogues of at most 128
+    utterances per step, 2 D_e <= 1024, D_m and D_e multiples of 4, at most 16 classes.
+    Data-parallel over dialogues like Phase2Engine: the gradient slab is all-reduced in-line on the step's stream (through
+    GradReducer under GANFFN_DP_MODE=buckets), Adam divides by the world size."""
+
+    def __init__(self, model, lr=3e-4, weight_decay=1e-4, class_weights=None, process_group=None):
+        self.module = model
+        lstm = model.lstm
+        if not (lstm.bidirectional and not lstm.batch_first and lstm.proj_size == 0 and lstm.bias):
+            raise ValueError("MeldEngine: MELDLSTMModel's LSTM configuration only (bidirectional, sequence-first, biases, no "
+                             "projection) — run the module path for anything else")
+        self.Dm, self.He, self.L = int(lstm.input_size), int(lstm.hidden_size), int(lstm.num_layers)
+        self.D2 = 2 * self.He
+        self.n_classes = int(model.smax_fc.weight.shape[0])
+        self.p_lstm = float(lstm.dropout)
+        if (self.Dm % 4 or self.He % 4 or self.D2 > 1024 or self.n_classes > 16 or model.smax_fc.weight.shape[1] != self.D2
+                or model.matchatt.att_type != "general2" or tuple(model.matchatt.transform.weight.shape) != (self.D2, self.D2)):
+            raise ValueError("MeldEngine: D_m and D_e must be multiples of 4, 2 D_e <= 1024 (the general2 attention kernel), at most "
+                             "16 classes, smax_fc and matchatt 2 D_e wide; got D_m = %d, D_e = %d, %d classes, smax_fc over %d — use "
+                             "the module path (MELDLSTMModel under autograd) for the rest"
+                             % (self.Dm, self.He, self.n_classes, model.smax_fc.weight.shape[1]))
+        names = dict(lstm.named_parameters())
+        plist = [names[k] for k in names]                     # weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0, *_l0_reverse, ...
+        assert len(plist) == 8 * self.L and list(names)[4] == "weight_ih_l0_reverse", list(names)[:8]
+        plist += [model.matchatt.transform.weight, model.matchatt.transform.bias, model.smax_fc.weight, model.smax_fc.bias]
+        self._init_common(plist[0].device, process_group, 1)
+        dev = self.dev
+        assert dev.type == "cuda", "MeldEngine needs the module on the GPU"
+        offs, total = [], 0
+        for p_ in plist:
+            offs.append(total)
+            total += (p_.numel() + 3) & ~3
+        self.slab = torch.zeros(total, device=dev)
+        with torch.no_grad():
+            for p_, o in zip(plist, offs):
+                self.slab[o:o + p_.numel()].copy_(p_.detach().reshape(-1))
+                p_.data = self.slab[o:o + p_.numel()].view_as(p_)
+        self._params, self._offs, self.total = plist, offs, total
+        self.grad = torch.zeros_like(self.slab)
+        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.slab), torch.zeros_like(self.slab)
+        self.step_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.lr, self.wd = lr, weight_decay
+        self.class_w = torch.tensor(class_weights, device=dev, dtype=torch.float32) if class_weights is not None else None
+        # the stack entry points' pointer arrays [L][2] (the slabs never move: built once)
+        def arrays(slab):
+            base = slab.data_ptr()
+            return [(C.c_void_p * (2 * self.L))(*[base + 4 * offs[4 * i + j] for i in range(2 * self.L)]) for j in range(4)]
+        self._w, self._g = arrays(self.slab), arrays(self.grad)
+        self.n_adds = max(1, self.L - 1)                      # one Philox offset per inter-layer dropout call
+        self.loss = torch.zeros(1, device=dev)
+        self.alpha = None
+        self._shape = None
+        self._cap_S = self._cap_B = 0
+        self._base_add = 0
+
+    def _p(self, i, grad=False):
+        o, n = self._offs[i], self._params[i].numel()
+        return (self.grad if grad else self.slab)[o:o + n]
+
+    def reserve(self, S, B):
+        """size every step buffer once for batches of up to (S, B): train / valid / test loaders then never re-allocate"""
+        self._cap_S, self._cap_B = max(self._cap_S, S), max(self._cap_B, B)
+
+    def _prepare(self, S, B):
+        if self._shape == (S, B):
+            return
+        if B > 32 or S > 128:
+            raise ValueError("MeldEngine: at most 32 dialogues of at most 128 utterances per step (the LSTM kernels' dialogue tile and "
+                             "the general2 attention kernel's sequence limit); got S = %d, B = %d — split the batch, or run the "
+                             "module path (MELDLSTMModel under autograd, which chunks by itself)" % (S, B))
+        if self._shape is None or S > self._alloc_S or B > self._alloc_B:
+            cS = self._cap_S = max(self._cap_S, S)
+            cB = self._cap_B = max(self._cap_B, B)
+            self._alloc_S, self._alloc_B = cS, cB
+            lib = _lib.load()
+            cfgc = _lib.LstmStackCfg(cS, cB, self.Dm, self.He, self.L, self.p_lstm, 1)
+            n_saved, n_ws = int(lib.ganffn_lstm_stack_saved_floats(C.byref(cfgc))), int(lib.ganffn_lstm_stack_workspace_floats(C.byref(cfgc)))
+            if n_saved < 0 or n_ws < 0:
+                _lib.check(-1, "ganffn_lstm_stack_*_floats")
+            T, D2, Cn = cS * cB, self.D2, self.n_classes
+            z = lambda n: torch.empty(n, device=self.dev, dtype=torch.float32)
+            self._f = dict(emotions=z(T * D2), xq=z(T * D2), att=z(T * D2), alpha=z(cB * cS * cS), tanh_s=z(cB * cS * cS),
+                           du=z(cB * cS * cS), hidden=z(T * D2), logits=z(T * Cn), log_prob=z(T * Cn), dlogits=z(T * Cn),
+                           d_res=z(T * D2), d_att=z(T * D2), d_xq=z(T * D2), d_mem=z(T * D2), d_tr=z(T * D2), d_em=z(T * D2),
+                           saved=z(n_saved), ws=z(n_ws), lin_ws=z(int(lib.ganffn_linear_bwd_workspace_floats(T, D2, D2)) + 64))
+            self.ws2 = torch.zeros(4, device=self.dev, dtype=torch.float32)
+        self._shape = (S, B)
+        self.cfg_train = _lib.LstmStackCfg(S, B, self.Dm, self.He, self.L, self.p_lstm, 1)
+        self.cfg_eval = _lib.LstmStackCfg(S, B, self.Dm, self.He, self.L, self.p_lstm, 0)
+        self.alpha = self._f["alpha"][:B * S * S].view(B, S, S)
+
+    def step(self, batch, train=True):
+        """batch: text (S,B,D_m) float32, umask (B,S) float, label (B,S) int64 (qmask / acoustic are not read:
+        train_MELD.py:71 feeds the text features alone).  Returns (loss tensor, log_prob (S,B,C)); the attention weights of the
+        step are `self.alpha` (B,S,S).  train=False: forward + loss only (model.eval()): no parameter, moment or step-count change."""
+        text, umask, label = batch["text"], batch["umask"], batch["label"]
+        S, B = text.shape[:2]
+        if text.shape[2] != self.Dm or text.dtype != torch.float32 or not text.is_contiguous() or not text.is_cuda:
+            raise ValueError("MeldEngine: text must be a contiguous float32 (S, B, %d) tensor on the GPU (data.to_meld_batch makes "
+                             "it so); got %s %s" % (self.Dm, tuple(text.shape), text.dtype))
+        self._prepare(S, B)
+        for p_, o in zip(self._params, self._offs):
+            if p_.data_ptr() != self.slab.data_ptr() + 4 * o:
+                raise RuntimeError("a MELDLSTMModel parameter was re-allocated after the engine was built (.to() / "
+                                   "flatten_parameters): build MeldEngine after the last .to()")
+        P, st = ops._ptr, ops._stream()
+        T, D2, Cn = S * B, self.D2, self.n_classes
+        f = self._f
+        self._base_add = base = self.rng.next_add(self.n_adds)        # SITE_LSTM + l draws offset base + l
+        rng = self.rng.state
+        cfg = self.cfg_train if train else self.cfg_eval
+        w_ih, w_hh, b_ih, b_hh = self._w
+        n_t = 8 * self.L
+        w_t, b_t, w_s, b_s = (self._p(n_t + j) for j in range(4))
+        # ---- forward: LSTM stack -> transform -> general2 attention -> hardswish head -> loss       (model.py:546-560)
+        _lib.call("ganffn_lstm_stack_fwd", C.byref(cfg), P(text), w_ih, w_hh, b_ih, b_hh, P(f["emotions"]), P(f["saved"]), P(f["ws"]),
+                  P(rng), C.c_uint64(base), st)
+        ops.linear_fwd_raw(f["emotions"], w_t, b_t, f["xq"], T, D2, D2)
+        _lib.call("ganffn_general2_attention_fwd", P(f["xq"]), P(f["emotions"]), P(umask), P(f["att"]), P(f["alpha"]), P(f["tanh_s"]),
+                  S, B, D2, st)
+        _lib.call("ganffn_meld_head_fwd", P(f["emotions"]), P(f["att"]), P(w_s), P(b_s), P(f["hidden"]), P(f["logits"]), T, D2, Cn, st)
+        log_prob = f["log_prob"][:T * Cn].view(S, B, Cn)
+        ops.logsoftmax_nll_raw(f["logits"], label, umask, self.class_w, log_prob, self.loss, f["dlogits"] if train else None,
+                               self.ws2, S, B, Cn)                                             # train_MELD.py:72-74, model.py:62-81
+        if not train:
+            return self.loss, log_prob
+        # ---- backward (the LSTM's weight gradients accumulate: the slab is zeroed first)
+        _lib.call("ganffn_zero_floats", P(self.grad), C.c_int64(self.total), st)
+        g_t, gb_t, g_s, gb_s = (self._p(n_t + j, True) for j in range(4))
+        _lib.call("ganffn_meld_head_bwd", P(f["dlogits"]), P(f["emotions"]), P(f["att"]), P(f["hidden"]), P(w_s), P(f["d_res"]),
+                  P(f["d_att"]), P(g_s), P(gb_s), T, D2, Cn, st)
+        _lib.call("ganffn_general2_attention_bwd", P(f["d_att"]), P(f["xq"]), P(f["emotions"]), P(umask), P(f["alpha"]), P(f["tanh_s"]),
+                  P(f["du"]), P(f["d_xq"]), P(f["d_mem"]), S, B, D2, st)
+        ops.linear_bwd_raw(f["d_xq"], f["emotions"], w_t, f["d_tr"], g_t, gb_t, T, D2, D2, f["lin_ws"])
+        # d emotions = the residual + the attention's memory side + its query side through transform
+        _lib.call("ganffn_add3", P(f["d_res"]), P(f["d_mem"]), P(f["d_tr"]), P(f["d_em"]), C.c_int64(T * D2), st)
+        g_ih, g_hh, gb_ih, gb_hh = self._g
+        _lib.call("ganffn_lstm_stack_bwd", C.byref(cfg), P(f["d_em"]), P(text), P(f["emotions"]), w_ih, w_hh, None, g_ih, g_hh, gb_ih,
+                  gb_hh, P(f["saved"]), P(f["ws"]), P(rng), C.c_uint64(base), st)
+        if self.pg is not None:
+            if dp_mode() == "inline":
+                import torch.distributed as dist
+                dist.all_reduce(self.grad, op=dist.ReduceOp.SUM, group=self.pg, async_op=False)
+            else:
+                red = GradReducer(self.pg)
+                red.reduce_async(self.grad)
+                red.finish()
+        ops.adam_step_raw(self.slab, self.grad, self.exp_avg, self.exp_avg_sq, self.step_count, self.total, self.lr, 0.9, 0.999,
+                          1e-8, self.wd, 1.0 / self.world)
+        return self.loss, log_prob
+
+    @staticmethod
+    def predictions(log_prob):
+        """argmax over classes in the reference's batch-major flattening (train_MELD.py:72,76)"""
+        return log_prob.transpose(0, 1).reshape(-1, log_prob.shape[2]).argmax(1)

@@ -495,6 +495,48 @@ int ganffn_lstm_layer_bwd(const ganffn_lstm_cfg* cfg, const float* d_out, const 
                           float* const* gw_hh, float* const* gb_ih, float* const* gb_hh, const float* saved,
                           float* workspace, void* stream);
 
+/* ---- N4: the whole LSTM stack in one call (csrc/lstm.hip) ---------------------------------------------------------------
+ * `nn.LSTM(In, H, num_layers = L, bidirectional = True, dropout = p)` of MELDLSTMModel (/root/reference/model.py:531,546; built
+ * at /root/reference/train_MELD.py:147-151 with L = 4): the L per-layer bodies above chained, with the dropout nn.LSTM applies to
+ * the output of every layer but the last (train != 0, p > 0) inside the library: Philox {seed, offset} contract, one call per
+ * layer l with site 64 + l and offset rng_offset_add + l, rows = tokens, columns = 2H — the same launches, hence the same
+ * bits, as ganffn_lstm_layer_* and ganffn_dropout issued one by one.  Weight and gradient pointers are arrays of [L][2]
+ * (layer-major; d = 0 forward, 1 reverse): w_ih[2 l + d] is [4H x In] for l = 0 and [4H x 2H] above.  saved
+ * (ganffn_lstm_stack_saved_floats) holds every layer's gates and cell states and the outputs between the layers; workspace
+ * (ganffn_lstm_stack_workspace_floats) is scratch.  The backward regenerates the masks from the same {rng, rng_offset_add},
+ * ACCUMULATES (+=) into gw_* / gb_* (arrays or entries may be NULL) and writes dx [S x B x In] (NULL: not wanted). */
+typedef struct ganffn_lstm_stack_cfg {
+    int32_t S, B, In, H, L;
+    float p;
+    int32_t train;
+} ganffn_lstm_stack_cfg;
+int64_t ganffn_lstm_stack_saved_floats(const ganffn_lstm_stack_cfg* cfg);
+int64_t ganffn_lstm_stack_workspace_floats(const ganffn_lstm_stack_cfg* cfg);
+int ganffn_lstm_stack_fwd(const ganffn_lstm_stack_cfg* cfg, const float* x, const float* const* w_ih, const float* const* w_hh,
+                          const float* const* b_ih, const float* const* b_hh, float* out, float* saved, float* workspace,
+                          const uint64_t* rng, uint64_t rng_offset_add, void* stream);
+int ganffn_lstm_stack_bwd(const ganffn_lstm_stack_cfg* cfg, const float* d_out, const float* x, const float* out,
+                          const float* const* w_ih, const float* const* w_hh, float* dx, float* const* gw_ih,
+                          float* const* gw_hh, float* const* gb_ih, float* const* gb_hh, const float* saved,
+                          float* workspace, const uint64_t* rng, uint64_t rng_offset_add, void* stream);
+
+/* ---- N4: the MELD classifier's head (csrc/meld_head.hip) ------------------------------------------------------------------
+ * Replaces `hidden = F.hardswish(emotions + F.hardswish(att_emotions))` and `self.smax_fc(hidden)` of MELDLSTMModel.forward
+ * (/root/reference/model.py:553-560, the att2 branch /root/reference/train_MELD.py:71 runs) and autograd's backward of them.
+ * emotions, att [T x D] (token t = s*B+b), w_fc [C x D], b_fc [C]; D a multiple of 4 and <= 1024, C <= 16.
+ * fwd writes hidden [T x D] (the weight gradient reads it) and logits [T x C].
+ * bwd: d_emotions = dlogits w_fc * hsw'(u) (the residual path alone: the attention's paths are the caller's), d_att = that *
+ * hsw'(att), u recomputed from emotions and att; gw_fc / gb_fc are ACCUMULATED (+=) in a fixed order (gb_fc may be NULL).
+ * hsw' as torch: 0 for x <= -3, 1 for x >= 3, x / 3 + 0.5 between.  One launch each; deterministic, no atomics. */
+int ganffn_meld_head_fwd(const float* emotions, const float* att, const float* w_fc, const float* b_fc, float* hidden,
+                         float* logits, int T, int D, int C, void* stream);
+int ganffn_meld_head_bwd(const float* dlogits, const float* emotions, const float* att, const float* hidden, const float* w_fc,
+                         float* d_emotions, float* d_att, float* gw_fc, float* gb_fc, int T, int D, int C, void* stream);
+
+/* n floats of zeros, in stream order: the gradient slab of a step runner before a backward that accumulates into it (the
+ * `optimizer.zero_grad()` of /root/reference/train_MELD.py:63 for engine.MeldEngine's slab). */
+int ganffn_zero_floats(float* p, int64_t n, void* stream);
+
 /* Measurement hook: the K = 100 -> 2048 products of the d_model-100 feed-forward block (csrc/gemm.hip gemm_wres_kernel) with the
  * arguments ganffn_encoder_fwd / _bwd give them (linear1 / linear2 of nn.TransformerEncoderLayer, call sites model.py:1210,1307).
  * which 0: out[T x 2048] = dropout_p(relu(a[T x 100] w[2048 x 100]^T + bias)); hmask != NULL: also the 1-bit [out > 0] pattern
