@@ -102,6 +102,14 @@ SIGNATURES = {
     "ganffn_lstm_stack_workspace_floats": (_L, [C.POINTER(LstmStackCfg)]),
     "ganffn_lstm_stack_fwd": (_I, [C.POINTER(LstmStackCfg)] + [_P] * 9 + [_U64, _P]),
     "ganffn_lstm_stack_bwd": (_I, [C.POINTER(LstmStackCfg)] + [_P] * 13 + [_U64, _P]),
+    "ganffn_lstm_batch_saved_floats": (_L, [C.POINTER(LstmCfg)]),
+    "ganffn_lstm_batch_workspace_floats": (_L, [C.POINTER(LstmCfg)]),
+    "ganffn_lstm_batch_layer_fwd": (_I, [C.POINTER(LstmCfg), _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ganffn_lstm_batch_layer_bwd": (_I, [C.POINTER(LstmCfg), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ganffn_lstm_stack_batch_saved_floats": (_L, [C.POINTER(LstmStackCfg)]),
+    "ganffn_lstm_stack_batch_workspace_floats": (_L, [C.POINTER(LstmStackCfg)]),
+    "ganffn_lstm_stack_batch_fwd": (_I, [C.POINTER(LstmStackCfg)] + [_P] * 9 + [_U64, _P]),
+    "ganffn_lstm_stack_batch_bwd": (_I, [C.POINTER(LstmStackCfg)] + [_P] * 13 + [_U64, _P]),
     "ganffn_meld_head_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ganffn_meld_head_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ganffn_zero_floats": (_I, [_P, _L, _P]),
@@ -133,6 +141,7 @@ SIGNATURES = {
     "ganffn_gemm_n100": (_I, [_P, _P, _I, _P, _P, _L, _I, _I, _I, C.POINTER(C.c_int), _P]),
     "ganffn_debug_set_ffn_mode": (_I, [_I]),
     "ganffn_drnn_skinny": (_I, [_I, _I, _P, _P, _P, _I, _I, _I, _P]),
+    "ganffn_drnn_skinny_batch": (_I, [_I, _I, _P, _P, _P, _I, _I, _I, _P]),
     "ganffn_drnn_saved_floats": (_L, [C.POINTER(DrnnCfg)]),
     "ganffn_drnn_workspace_floats": (_L, [C.POINTER(DrnnCfg)]),
     "ganffn_drnn_fwd": (_I, [C.POINTER(DrnnCfg), _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, _P]),
@@ -149,6 +158,10 @@ SIGNATURES = {
     "ganffn_drnn_party_workspace_floats": (_L, [C.POINTER(DrnnCfg), C.POINTER(DrnnAtt), _I, _I]),
     "ganffn_drnn_party_fwd": (_I, [C.POINTER(DrnnCfg), C.POINTER(DrnnAtt), _I, _I] + [_P] * 11 + [_U64, _P]),
     "ganffn_drnn_party_bwd": (_I, [C.POINTER(DrnnCfg), C.POINTER(DrnnAtt), _I, _I] + [_P] * 15 + [_U64, _P]),
+    "ganffn_drnn_batch_saved_floats": (_L, [C.POINTER(DrnnCfg), C.POINTER(DrnnAtt), _I, _I]),
+    "ganffn_drnn_batch_workspace_floats": (_L, [C.POINTER(DrnnCfg), C.POINTER(DrnnAtt), _I, _I]),
+    "ganffn_drnn_batch_fwd": (_I, [C.POINTER(DrnnCfg), C.POINTER(DrnnAtt), _I, _I] + [_P] * 11 + [_U64, _P]),
+    "ganffn_drnn_batch_bwd": (_I, [C.POINTER(DrnnCfg), C.POINTER(DrnnAtt), _I, _I] + [_P] * 15 + [_U64, _P]),
     "ganffn_dropout": (_I, [_P, _P, _I, _I, _F, _U32, _P, _U64, _P]),
     "ganffn_seq_reverse": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "ganffn_drnn_join_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _U32, _U32, _P, _U64, _I, _P]),

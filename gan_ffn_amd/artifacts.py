@@ -235,7 +235,7 @@ def run_meld_training(pickle_path, n_epochs=50, lr=3e-4, l2=1e-4, dropout=0.6, b
         torch.manual_seed(seed)
     n_classes = 7 if classify == "emotion" else 3                                 # train_MELD.py:138-141
     model = DR.MELDLSTMModel(600, 300, 600, n_classes=n_classes, dropout=dropout).to(device)
-    eng = E.MeldEngine(model, lr=lr, weight_decay=l2)
+    eng = E.MeldEngine(model, lr=lr, weight_decay=l2, max_dialogues=max(32, batch_size))      # train_MELD.py:114 --batch-size
     train_loader, valid_loader, test_loader = D.get_MELD_loaders(pickle_path, batch_size=batch_size, valid=0.0, classify=classify)
     eng.reserve(33, batch_size)                      # MELD's longest dialogue
     best = None

@@ -43,7 +43,8 @@ typedef float floatx4 __attribute__((ext_vector_type(4)));
 enum : uint32_t { SITE_DRNN_G = 8, SITE_DRNN_P = 9, SITE_DRNN_E = 10, SITE_DRNN_L = 11 };   // + 4 for the second direction
 
 // ------------------------------------------------------------------------------------------
-// skinny products: M <= 32 rows of A (dialogues) against a weight matrix
+// skinny products: M <= 32 rows of A (dialogues) against a weight matrix; up to GANFFN_MAX_DIALOGUES rows in tiles of 32
+// ("Dialogue-tile axis" below)
 // ------------------------------------------------------------------------------------------
 // (SkinnyProb / SkinnyGroup: common.h — lstm.hip runs its recurrent products through the same kernels)
 
@@ -174,9 +175,8 @@ __global__ __launch_bounds__(256) void drnn_transpose_kernel(TrGroup t) {
 // NN: C[b][n] = sum_k A[b][k] W[k][n] (+ Cin).  Workgroup = 16 output columns x 32 dialogues, 8 waves split K.
 // MFMA tile D[m = dialogue][n' = column]: A-operand = A rows (float4 along k), B-operand = W[k][n0 + n'] (one dword per
 // step: 16 consecutive columns of a row = 64 contiguous bytes).
-__global__ __launch_bounds__(512) void skinny_nn_kernel(SkinnyGroup grp) {
+__device__ __forceinline__ void skinny_nn_body(const SkinnyProb& q) {
     __shared__ __attribute__((aligned(16))) float red[8][2][4][64];
-    const SkinnyProb& q = grp.p[blockIdx.z];
     const int n0 = blockIdx.x * 16;
     if (n0 >= q.N) return;
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, c = lane & 15, g = lane >> 4;
@@ -228,15 +228,58 @@ __global__ __launch_bounds__(512) void skinny_nn_kernel(SkinnyGroup grp) {
         }
     }
 }
+__global__ __launch_bounds__(512) void skinny_nn_kernel(SkinnyGroup grp) { skinny_nn_body(grp.p[blockIdx.z]); }
+
+// Dialogue-tile axis: 32 < M <= GANFFN_MAX_DIALOGUES.  blockIdx.y = y is a tile of 32 dialogues: the workgroup is exactly the
+// workgroup of the kernels above on rows 32 y .. 32 y + 31 of A, Cin, Cin2 and C (M clipped to the rows left), so with the K
+// split unchanged every row's sum is formed in the order the one-tile launch forms it: row b of an M-row product has the bits
+// of the same row in any other product over the same W, whatever tile it falls in.  The weight rows are re-read per tile
+// (from L2 / MALL after the first); a launch stays one memory round trip + one LDS reduction long, which is what a link of
+// the chain costs — the alternative, a loop over the tiles inside the workgroup with wv[] kept in registers, makes each of
+// the workgroup's waves M / 32 times as long and was not kept (DESIGN.md "Dialogue tiles").  Separate kernels, so that launches
+// with M <= 32 keep their kernel, grid and argument block.
+__device__ __forceinline__ SkinnyProb skinny_tile(const SkinnyProb& q) {
+    SkinnyProb t = q;
+    const int m0 = 32 * (int)blockIdx.y;
+    t.A = q.A + (size_t)m0 * q.lda;
+    t.Cin = q.Cin ? q.Cin + (size_t)m0 * q.ldcin : nullptr;
+    t.Cin2 = q.Cin2 ? q.Cin2 + (size_t)m0 * q.ldc : nullptr;
+    t.C = q.C + (size_t)m0 * q.ldc;
+    t.M = min(32, q.M - m0);
+    return t;
+}
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void skinny_nt_tiled_kernel(SkinnyGroup grp) {
+    if (32 * (int)blockIdx.y >= grp.p[blockIdx.z].M) return;
+    skinny_nt_body<NW>(skinny_tile(grp.p[blockIdx.z]));
+}
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void skinny_nt_wide_tiled_kernel(SkinnyGroupWide grp) {
+    if (32 * (int)blockIdx.y >= grp.p[blockIdx.z].M) return;
+    skinny_nt_body<NW>(skinny_tile(grp.p[blockIdx.z]));
+}
+__global__ __launch_bounds__(512) void skinny_nn_tiled_kernel(SkinnyGroup grp) {
+    if (32 * (int)blockIdx.y >= grp.p[blockIdx.z].M) return;
+    skinny_nn_body(skinny_tile(grp.p[blockIdx.z]));
+}
 
 int launch_skinny(const SkinnyGroup& grp, int nprob, bool nn, hipStream_t st) {
-    int maxN = 0, maxK = 0;
+    int maxN = 0, maxK = 0, maxM = 0;
     for (int i = 0; i < nprob; ++i) {
         const SkinnyProb& q = grp.p[i];
-        GF_CHECK_ARG(q.M >= 1 && q.M <= 32 && (q.K & 3) == 0 && (q.lda & 3) == 0 && aligned16(q.A) && (nn || ((q.ldw & 3) == 0 && aligned16(q.W))),
+        GF_CHECK_ARG(q.M >= 1 && q.M <= GANFFN_MAX_DIALOGUES && (q.K & 3) == 0 && (q.lda & 3) == 0 && aligned16(q.A) && (nn || ((q.ldw & 3) == 0 && aligned16(q.W))),
                      "drnn skinny product: M=%d K=%d lda=%d ldw=%d unsupported", q.M, q.K, q.lda, q.ldw);
         maxN = q.N > maxN ? q.N : maxN;
         maxK = q.K > maxK ? q.K : maxK;
+        maxM = q.M > maxM ? q.M : maxM;
+    }
+    if (maxM > 32) {          // dialogue tiles on grid.y: the same launch count, (maxM + 31) / 32 times the workgroups
+        const dim3 grid((maxN + 15) / 16, (maxM + 31) / 32, nprob);
+        if (nn) hipLaunchKernelGGL(skinny_nn_tiled_kernel, grid, dim3(512), 0, st, grp);
+        else if (maxK > 4 * 16 * SK_NT) hipLaunchKernelGGL(skinny_nt_tiled_kernel<12>, grid, dim3(768), 0, st, grp);
+        else hipLaunchKernelGGL(skinny_nt_tiled_kernel<4>, grid, dim3(256), 0, st, grp);
+        GF_LAUNCH_CHECK();
+        return 0;
     }
     if (nn) hipLaunchKernelGGL(skinny_nn_kernel, dim3((maxN + 15) / 16, 1, nprob), dim3(512), 0, st, grp);
     else if (maxK > 4 * 16 * SK_NT) hipLaunchKernelGGL(skinny_nt_kernel<12>, dim3((maxN + 15) / 16, 1, nprob), dim3(768), 0, st, grp);
@@ -254,14 +297,22 @@ static int launch_skinny_nt(const SkinnyProb* pr, int n, hipStream_t st) {
     }
     GF_CHECK_ARG(n <= 2 * (1 + DR_MAXP), "drnn skinny product: %d problems in one launch (<= %d)", n, 2 * (1 + DR_MAXP));
     SkinnyGroupWide wg;
-    int maxN = 0, maxK = 0;
+    int maxN = 0, maxK = 0, maxM = 0;
     for (int i = 0; i < n; ++i) {
         const SkinnyProb& q = pr[i];
-        GF_CHECK_ARG(q.M >= 1 && q.M <= 32 && (q.K & 3) == 0 && (q.lda & 3) == 0 && aligned16(q.A) && (q.ldw & 3) == 0 && aligned16(q.W),
+        GF_CHECK_ARG(q.M >= 1 && q.M <= GANFFN_MAX_DIALOGUES && (q.K & 3) == 0 && (q.lda & 3) == 0 && aligned16(q.A) && (q.ldw & 3) == 0 && aligned16(q.W),
                      "drnn skinny product: M=%d K=%d lda=%d ldw=%d unsupported", q.M, q.K, q.lda, q.ldw);
         wg.p[i] = q;
         maxN = q.N > maxN ? q.N : maxN;
         maxK = q.K > maxK ? q.K : maxK;
+        maxM = q.M > maxM ? q.M : maxM;
+    }
+    if (maxM > 32) {
+        const dim3 grid((maxN + 15) / 16, (maxM + 31) / 32, n);
+        if (maxK > 4 * 16 * SK_NT) hipLaunchKernelGGL(skinny_nt_wide_tiled_kernel<12>, grid, dim3(768), 0, st, wg);
+        else hipLaunchKernelGGL(skinny_nt_wide_tiled_kernel<4>, grid, dim3(256), 0, st, wg);
+        GF_LAUNCH_CHECK();
+        return 0;
     }
     if (maxK > 4 * 16 * SK_NT) hipLaunchKernelGGL(skinny_nt_wide_kernel<12>, dim3((maxN + 15) / 16, 1, n), dim3(768), 0, st, wg);
     else hipLaunchKernelGGL(skinny_nt_wide_kernel<4>, dim3((maxN + 15) / 16, 1, n), dim3(256), 0, st, wg);
@@ -1163,10 +1214,12 @@ static DrnnAWs drnn_aws(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, boo
     return w;
 }
 
-static int check_drnn(const ganffn_drnn_cfg* c, int ndir) {
+// maxB: 32 behind the entry points that always had that limit (they keep refusing 33 dialogues), GANFFN_MAX_DIALOGUES behind
+// ganffn_drnn_batch_*
+static int check_drnn(const ganffn_drnn_cfg* c, int ndir, int maxB = 32) {
     GF_CHECK_ARG(c, "null drnn cfg");
     GF_CHECK_ARG(ndir == 1 || ndir == 2, "drnn: ndir=%d", ndir);
-    GF_CHECK_ARG(c->S >= 1 && c->S <= DR_MAXS && c->B >= 1 && c->B <= 32, "drnn: S=%d (<= %d), B=%d (<= 32)", c->S, DR_MAXS, c->B);
+    GF_CHECK_ARG(c->S >= 1 && c->S <= DR_MAXS && c->B >= 1 && c->B <= maxB, "drnn: S=%d (<= %d), B=%d (<= %d)", c->S, DR_MAXS, c->B, maxB);
     GF_CHECK_ARG(c->Dm >= 4 && (c->Dm & 3) == 0 && c->H >= 4 && (c->H & 3) == 0 && c->He >= 4 && (c->He & 3) == 0,
                  "drnn: D_m=%d, D_g=D_p=%d, D_e=%d must be multiples of 4", c->Dm, c->H, c->He);
     GF_CHECK_ARG(c->H <= 512, "drnn: D_g = D_p = %d > 512 (attention kernels hold one column per thread)", c->H);
@@ -1212,7 +1265,18 @@ using namespace ganffn;
 // test / measurement hook: one skinny product C[M x N] = A[M x K] W^T (nn = 0, W [N x K]) or A W (nn = 1, W [K x N]),
 // replicated `copies` (<= 8) times in one launch like a step of the recurrence (2 directions x 2 cells x 2 products)
 extern "C" int ganffn_drnn_skinny(int nn, int copies, const float* A, const float* W, float* C, int M, int N, int K, void* stream) {
+    GF_CHECK_ARG(M >= 1 && M <= 32, "drnn_skinny: M=%d (1 .. 32; ganffn_drnn_skinny_batch takes more)", M);
     GF_CHECK_ARG(A && W && C && copies >= 1 && copies <= 8, "drnn_skinny: bad arguments");
+    SkinnyGroup sg;
+    for (int i = 0; i < copies; ++i)
+        sg.p[i] = SkinnyProb{A, K, W + (size_t)i * N * K, nn ? N : K, nullptr, 0, nullptr, nullptr, C + (size_t)i * M * N, N, M, N, K};
+    return launch_skinny(sg, copies, nn != 0, (hipStream_t)stream);
+}
+
+// the same with the dialogue-tile axis: M <= GANFFN_MAX_DIALOGUES (M <= 32 is the launch above)
+extern "C" int ganffn_drnn_skinny_batch(int nn, int copies, const float* A, const float* W, float* C, int M, int N, int K, void* stream) {
+    GF_CHECK_ARG(A && W && C && copies >= 1 && copies <= 8, "drnn_skinny_batch: bad arguments");
+    GF_CHECK_ARG(M >= 1 && M <= GANFFN_MAX_DIALOGUES && N >= 1 && K >= 4, "drnn_skinny_batch: M=%d (1 .. %d) N=%d K=%d", M, GANFFN_MAX_DIALOGUES, N, K);
     SkinnyGroup sg;
     for (int i = 0; i < copies; ++i)
         sg.p[i] = SkinnyProb{A, K, W + (size_t)i * N * K, nn ? N : K, nullptr, 0, nullptr, nullptr, C + (size_t)i * M * N, N, M, N, K};
@@ -1245,8 +1309,8 @@ static int drnn_fwd(const ganffn_drnn_cfg* c, int ndir, const float* const* U, c
                     const float* const* mval, const ganffn_drnn_params* prm, const ganffn_drnn_listener_params* lp,
                     float* const* e_out, float* const* alpha, float* const* saved, float* const* workspace,
                     const uint64_t* rng, uint64_t add, void* stream, const ganffn_drnn_att* at = nullptr,
-                    const ganffn_drnn_att_params* ap = nullptr, int P = 2) {
-    GF_TRY(check_drnn(c, ndir));
+                    const ganffn_drnn_att_params* ap = nullptr, int P = 2, int maxB = 32) {
+    GF_TRY(check_drnn(c, ndir, maxB));
     GF_TRY(check_parties(P));
     const int att = at ? at->type : ATT_GENERAL;
     if (at) {
@@ -1453,8 +1517,8 @@ static int drnn_bwd(const ganffn_drnn_cfg* c, int ndir, const float* const* d_e,
                     const ganffn_drnn_listener_params* lp, const ganffn_drnn_grads* grd, const ganffn_drnn_listener_grads* lg,
                     float* const* dU, const float* const* alpha, const float* const* saved, float* const* workspace,
                     const uint64_t* rng, uint64_t add, void* stream, const ganffn_drnn_att* at = nullptr,
-                    const ganffn_drnn_att_params* ap = nullptr, const ganffn_drnn_att_grads* ag = nullptr, int P = 2) {
-    GF_TRY(check_drnn(c, ndir));
+                    const ganffn_drnn_att_params* ap = nullptr, const ganffn_drnn_att_grads* ag = nullptr, int P = 2, int maxB = 32) {
+    GF_TRY(check_drnn(c, ndir, maxB));
     GF_TRY(check_parties(P));
     const int att = at ? at->type : ATT_GENERAL;
     if (at) {
@@ -1771,4 +1835,35 @@ extern "C" int ganffn_drnn_party_bwd(const ganffn_drnn_cfg* c, const ganffn_drnn
     GF_TRY(check_parties(parties));
     return drnn_bwd(c, ndir, d_e, U, spk, mval, prm, lprm, grd, lgrd, dU, alpha, saved, workspace, rng, add, stream, at, aprm, agrd,
                     parties);
+}
+
+// 1 <= B <= GANFFN_MAX_DIALOGUES dialogues per call: the driver above with the skinny products' dialogue-tile axis (B <= 32 is
+// the launch sequence of ganffn_drnn_party_*, bit for bit; above it the same number of launches per step)
+extern "C" int64_t ganffn_drnn_batch_saved_floats(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int listener, int parties) {
+    return check_drnn(c, 1, GANFFN_MAX_DIALOGUES) || check_att(c, at) || check_parties(parties) ? -1 : drnn_asaved(c, at, listener != 0, parties).total;
+}
+extern "C" int64_t ganffn_drnn_batch_workspace_floats(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int listener, int parties) {
+    return check_drnn(c, 1, GANFFN_MAX_DIALOGUES) || check_att(c, at) || check_parties(parties) ? -1 : drnn_aws(c, at, listener != 0, parties).total;
+}
+extern "C" int ganffn_drnn_batch_fwd(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int parties, int ndir, const float* const* U,
+                                     const int32_t* const* spk, const float* const* mval, const ganffn_drnn_params* prm,
+                                     const ganffn_drnn_listener_params* lprm, const ganffn_drnn_att_params* aprm,
+                                     float* const* e_out, float* const* alpha, float* const* saved, float* const* workspace,
+                                     const uint64_t* rng, uint64_t add, void* stream) {
+    GF_CHECK_ARG(at, "drnn_batch_fwd: null attention descriptor");
+    GF_TRY(check_parties(parties));
+    return drnn_fwd(c, ndir, U, spk, mval, prm, lprm, e_out, alpha, saved, workspace, rng, add, stream, at, aprm, parties,
+                    GANFFN_MAX_DIALOGUES);
+}
+extern "C" int ganffn_drnn_batch_bwd(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int parties, int ndir, const float* const* d_e,
+                                     const float* const* U, const int32_t* const* spk, const float* const* mval,
+                                     const ganffn_drnn_params* prm, const ganffn_drnn_listener_params* lprm,
+                                     const ganffn_drnn_att_params* aprm, const ganffn_drnn_grads* grd,
+                                     const ganffn_drnn_listener_grads* lgrd, const ganffn_drnn_att_grads* agrd, float* const* dU,
+                                     const float* const* alpha, const float* const* saved, float* const* workspace,
+                                     const uint64_t* rng, uint64_t add, void* stream) {
+    GF_CHECK_ARG(at, "drnn_batch_bwd: null attention descriptor");
+    GF_TRY(check_parties(parties));
+    return drnn_bwd(c, ndir, d_e, U, spk, mval, prm, lprm, grd, lgrd, dU, alpha, saved, workspace, rng, add, stream, at, aprm, agrd,
+                    parties, GANFFN_MAX_DIALOGUES);
 }

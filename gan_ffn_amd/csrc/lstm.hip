@@ -19,7 +19,9 @@
 //     (dh_{t-1} = d_out[t-1] + dG_t W_hh, the weight read row-wise as stored); every weight gradient is DEFERRED: dG of all steps
 //     is kept and four TN GEMMs after the loop compute dW_ih = dG^T x and dW_hh = dG^T h_prev over all tokens (owner-accumulated or
 //     slab + ordered reduce: no atomics), the bias gradients are fixed-order column sums, dx = sum_d dG_d W_ih_d two NN GEMMs.
-// Deterministic: no atomics anywhere.  B <= 32 per call (the skinny kernels' dialogue tile); the Python side chunks larger batches.
+// Deterministic: no atomics anywhere.  B <= 32 per call behind ganffn_lstm_* / ganffn_lstm_stack_*; ganffn_lstm_batch_* /
+// ganffn_lstm_stack_batch_* take up to GANFFN_MAX_DIALOGUES dialogues through the skinny kernels' dialogue-tile axis (still 2 + 2
+// launches per step); the Python side chunks larger batches.
 // ganffn_lstm_stack_fwd / _bwd (end of the file) chain the L layers of the stack in one call, with nn.LSTM's inter-layer dropout
 // (Philox site 64 + l, offset base + l) between them: the same launches as L per-layer calls and L - 1 ganffn_dropout calls, so
 // the same bits — what engine.MeldEngine runs instead of ops.lstm_forward's autograd chain.
@@ -143,19 +145,19 @@ int64_t lstm_stack_layer_ws(const ganffn_lstm_stack_cfg* c) {
     return (m + 3) & ~(int64_t)3;
 }
 
-int check_lstm(const ganffn_lstm_cfg* c) {
+int check_lstm(const ganffn_lstm_cfg* c, int maxB = 32) {
     GF_CHECK_ARG(c, "null lstm cfg");
-    GF_CHECK_ARG(c->S >= 1 && c->B >= 1 && c->B <= 32, "lstm: S=%d B=%d (B <= 32 per call)", c->S, c->B);
+    GF_CHECK_ARG(c->S >= 1 && c->B >= 1 && c->B <= maxB, "lstm: S=%d B=%d (B <= %d per call)", c->S, c->B, maxB);
     GF_CHECK_ARG(c->In >= 4 && (c->In & 3) == 0 && c->H >= 4 && (c->H & 3) == 0, "lstm: In=%d H=%d must be multiples of 4", c->In, c->H);
     return 0;
 }
 
-int check_lstm_stack(const ganffn_lstm_stack_cfg* c) {
+int check_lstm_stack(const ganffn_lstm_stack_cfg* c, int maxB = 32) {
     GF_CHECK_ARG(c, "null lstm stack cfg");
     GF_CHECK_ARG(c->L >= 1 && c->L <= 16, "lstm stack: L=%d (1 .. 16 layers)", c->L);
     GF_CHECK_ARG(c->p >= 0.f && c->p < 1.f, "lstm stack: dropout p=%g must be in [0, 1)", (double)c->p);
     const ganffn_lstm_cfg l0 = stack_layer_cfg(c, 0);
-    return check_lstm(&l0);
+    return check_lstm(&l0, maxB);
 }
 
 }  // namespace
@@ -166,10 +168,11 @@ using namespace ganffn;
 extern "C" int64_t ganffn_lstm_saved_floats(const ganffn_lstm_cfg* c) { return check_lstm(c) ? -1 : lstm_saved(c).total; }
 extern "C" int64_t ganffn_lstm_workspace_floats(const ganffn_lstm_cfg* c) { return check_lstm(c) ? -1 : lstm_ws(c); }
 
-extern "C" int ganffn_lstm_layer_fwd(const ganffn_lstm_cfg* c, const float* x, const float* const* w_ih, const float* const* w_hh,
-                                     const float* const* b_ih, const float* const* b_hh, float* out, float* saved, float* workspace,
-                                     void* stream) {
-    GF_TRY(check_lstm(c));
+// maxB: 32 behind the entry points that always had that limit, GANFFN_MAX_DIALOGUES behind the _batch_ ones
+static int lstm_layer_fwd(const ganffn_lstm_cfg* c, const float* x, const float* const* w_ih, const float* const* w_hh,
+                          const float* const* b_ih, const float* const* b_hh, float* out, float* saved, float* workspace,
+                          void* stream, int maxB) {
+    GF_TRY(check_lstm(c, maxB));
     GF_CHECK_ARG(x && w_ih && w_hh && b_ih && b_hh && out && saved && workspace, "lstm_layer_fwd: null pointer");
     GF_CHECK_ARG(aligned16(x) && aligned16(out) && aligned16(saved) && aligned16(workspace), "lstm_layer_fwd: buffers must be 16-byte aligned");
     for (int d = 0; d < 2; ++d)
@@ -215,11 +218,17 @@ extern "C" int ganffn_lstm_layer_fwd(const ganffn_lstm_cfg* c, const float* x, c
     return 0;
 }
 
-extern "C" int ganffn_lstm_layer_bwd(const ganffn_lstm_cfg* c, const float* d_out, const float* x, const float* out,
-                                     const float* const* w_ih, const float* const* w_hh, float* dx, float* const* gw_ih,
-                                     float* const* gw_hh, float* const* gb_ih, float* const* gb_hh, const float* saved,
-                                     float* workspace, void* stream) {
-    GF_TRY(check_lstm(c));
+extern "C" int ganffn_lstm_layer_fwd(const ganffn_lstm_cfg* c, const float* x, const float* const* w_ih, const float* const* w_hh,
+                                     const float* const* b_ih, const float* const* b_hh, float* out, float* saved, float* workspace,
+                                     void* stream) {
+    return lstm_layer_fwd(c, x, w_ih, w_hh, b_ih, b_hh, out, saved, workspace, stream, 32);
+}
+
+static int lstm_layer_bwd(const ganffn_lstm_cfg* c, const float* d_out, const float* x, const float* out,
+                          const float* const* w_ih, const float* const* w_hh, float* dx, float* const* gw_ih,
+                          float* const* gw_hh, float* const* gb_ih, float* const* gb_hh, const float* saved,
+                          float* workspace, void* stream, int maxB) {
+    GF_TRY(check_lstm(c, maxB));
     GF_CHECK_ARG(d_out && x && out && w_ih && w_hh && saved && workspace, "lstm_layer_bwd: null pointer");
     GF_CHECK_ARG(aligned16(d_out) && aligned16(x) && aligned16(out) && aligned16(saved) && aligned16(workspace) && (!dx || aligned16(dx)),
                  "lstm_layer_bwd: buffers must be 16-byte aligned");
@@ -285,6 +294,13 @@ extern "C" int ganffn_lstm_layer_bwd(const ganffn_lstm_cfg* c, const float* d_ou
     return 0;
 }
 
+extern "C" int ganffn_lstm_layer_bwd(const ganffn_lstm_cfg* c, const float* d_out, const float* x, const float* out,
+                                     const float* const* w_ih, const float* const* w_hh, float* dx, float* const* gw_ih,
+                                     float* const* gw_hh, float* const* gb_ih, float* const* gb_hh, const float* saved,
+                                     float* workspace, void* stream) {
+    return lstm_layer_bwd(c, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, workspace, stream, 32);
+}
+
 // ---- L layers in one call -------------------------------------------------------------------------------------------
 extern "C" int64_t ganffn_lstm_stack_saved_floats(const ganffn_lstm_stack_cfg* c) { return check_lstm_stack(c) ? -1 : lstm_stack_saved(c).total; }
 extern "C" int64_t ganffn_lstm_stack_workspace_floats(const ganffn_lstm_stack_cfg* c) {
@@ -293,10 +309,10 @@ extern "C" int64_t ganffn_lstm_stack_workspace_floats(const ganffn_lstm_stack_cf
 
 // The per-layer entry points above, chained (same launches, same bits), with nn.LSTM(dropout = p)'s dropout on the output of every
 // layer but the last: site SITE_LSTM0 + l, offset rng_offset_add + l — what ops.lstm_forward issues as separate calls.
-extern "C" int ganffn_lstm_stack_fwd(const ganffn_lstm_stack_cfg* c, const float* x, const float* const* w_ih, const float* const* w_hh,
-                                     const float* const* b_ih, const float* const* b_hh, float* out, float* saved, float* workspace,
-                                     const uint64_t* rng, uint64_t rng_offset_add, void* stream) {
-    GF_TRY(check_lstm_stack(c));
+static int lstm_stack_fwd(const ganffn_lstm_stack_cfg* c, const float* x, const float* const* w_ih, const float* const* w_hh,
+                          const float* const* b_ih, const float* const* b_hh, float* out, float* saved, float* workspace,
+                          const uint64_t* rng, uint64_t rng_offset_add, void* stream, int maxB) {
+    GF_TRY(check_lstm_stack(c, maxB));
     GF_CHECK_ARG(x && w_ih && w_hh && b_ih && b_hh && out && saved && workspace, "lstm_stack_fwd: null pointer");
     const bool drop = c->train && c->p > 0.f && c->L > 1;
     GF_CHECK_ARG(!drop || rng, "lstm_stack_fwd: rng required in train mode");
@@ -307,8 +323,8 @@ extern "C" int ganffn_lstm_stack_fwd(const ganffn_lstm_stack_cfg* c, const float
         const ganffn_lstm_cfg lc = stack_layer_cfg(c, l);
         const bool last = l + 1 == c->L;
         float* o = last ? out : saved + so.outs + (int64_t)l * 2 * T * 2 * H;
-        GF_TRY(ganffn_lstm_layer_fwd(&lc, in, w_ih + 2 * l, w_hh + 2 * l, b_ih + 2 * l, b_hh + 2 * l, o, saved + l * so.layer_stride,
-                                     workspace, stream));
+        GF_TRY(lstm_layer_fwd(&lc, in, w_ih + 2 * l, w_hh + 2 * l, b_ih + 2 * l, b_hh + 2 * l, o, saved + l * so.layer_stride,
+                              workspace, stream, maxB));
         in = o;
         if (!last && drop) {
             float* dr = o + T * 2 * H;
@@ -319,13 +335,19 @@ extern "C" int ganffn_lstm_stack_fwd(const ganffn_lstm_stack_cfg* c, const float
     return 0;
 }
 
+extern "C" int ganffn_lstm_stack_fwd(const ganffn_lstm_stack_cfg* c, const float* x, const float* const* w_ih, const float* const* w_hh,
+                                     const float* const* b_ih, const float* const* b_hh, float* out, float* saved, float* workspace,
+                                     const uint64_t* rng, uint64_t rng_offset_add, void* stream) {
+    return lstm_stack_fwd(c, x, w_ih, w_hh, b_ih, b_hh, out, saved, workspace, rng, rng_offset_add, stream, 32);
+}
+
 // x, out: the forward's; gw_* / gb_*: arrays of [L][2] pointers, ACCUMULATED into like the per-layer backward (NULL arrays or
 // entries: not wanted); dx [S x B x In] may be NULL.  The dropout masks are regenerated from {rng, rng_offset_add}.
-extern "C" int ganffn_lstm_stack_bwd(const ganffn_lstm_stack_cfg* c, const float* d_out, const float* x, const float* out,
-                                     const float* const* w_ih, const float* const* w_hh, float* dx, float* const* gw_ih,
-                                     float* const* gw_hh, float* const* gb_ih, float* const* gb_hh, const float* saved,
-                                     float* workspace, const uint64_t* rng, uint64_t rng_offset_add, void* stream) {
-    GF_TRY(check_lstm_stack(c));
+static int lstm_stack_bwd(const ganffn_lstm_stack_cfg* c, const float* d_out, const float* x, const float* out,
+                          const float* const* w_ih, const float* const* w_hh, float* dx, float* const* gw_ih,
+                          float* const* gw_hh, float* const* gb_ih, float* const* gb_hh, const float* saved,
+                          float* workspace, const uint64_t* rng, uint64_t rng_offset_add, void* stream, int maxB) {
+    GF_TRY(check_lstm_stack(c, maxB));
     GF_CHECK_ARG(d_out && x && out && w_ih && w_hh && saved && workspace, "lstm_stack_bwd: null pointer");
     const bool drop = c->train && c->p > 0.f && c->L > 1;
     GF_CHECK_ARG(!drop || rng, "lstm_stack_bwd: rng required in train mode");
@@ -339,12 +361,53 @@ extern "C" int ganffn_lstm_stack_bwd(const ganffn_lstm_stack_cfg* c, const float
         const float* prev = l == 0 ? nullptr : saved + so.outs + (int64_t)(l - 1) * 2 * T * 2 * H;
         const float* in = l == 0 ? x : drop ? prev + T * 2 * H : prev;
         float* dxl = l == 0 ? dx : dbuf + (int64_t)(l & 1) * T * 2 * H;
-        GF_TRY(ganffn_lstm_layer_bwd(&lc, d, in, o, w_ih + 2 * l, w_hh + 2 * l, dxl, gw_ih ? gw_ih + 2 * l : nullptr,
-                                     gw_hh ? gw_hh + 2 * l : nullptr, gb_ih ? gb_ih + 2 * l : nullptr, gb_hh ? gb_hh + 2 * l : nullptr,
-                                     saved + l * so.layer_stride, workspace, stream));
+        GF_TRY(lstm_layer_bwd(&lc, d, in, o, w_ih + 2 * l, w_hh + 2 * l, dxl, gw_ih ? gw_ih + 2 * l : nullptr,
+                              gw_hh ? gw_hh + 2 * l : nullptr, gb_ih ? gb_ih + 2 * l : nullptr, gb_hh ? gb_hh + 2 * l : nullptr,
+                              saved + l * so.layer_stride, workspace, stream, maxB));
         if (l > 0 && drop)
             GF_TRY(launch_dropout(dxl, dxl, (int)T, 2 * (int)H, c->p, SITE_LSTM0 + (l - 1), rng, rng_offset_add + (l - 1), 1, (hipStream_t)stream));
         d = dxl;
     }
     return 0;
+}
+extern "C" int ganffn_lstm_stack_bwd(const ganffn_lstm_stack_cfg* c, const float* d_out, const float* x, const float* out,
+                                     const float* const* w_ih, const float* const* w_hh, float* dx, float* const* gw_ih,
+                                     float* const* gw_hh, float* const* gb_ih, float* const* gb_hh, const float* saved,
+                                     float* workspace, const uint64_t* rng, uint64_t rng_offset_add, void* stream) {
+    return lstm_stack_bwd(c, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, workspace, rng, rng_offset_add, stream, 32);
+}
+
+// ---- 1 <= B <= GANFFN_MAX_DIALOGUES dialogues per call ---------------------------------------------------------------------
+// The bodies above with the skinny products' dialogue-tile axis (dialogue_rnn.hip): the same layouts and sizes as functions of
+// B, the same launches per step; B <= 32 is the launch sequence of the entry points above, bit for bit.
+extern "C" int64_t ganffn_lstm_batch_saved_floats(const ganffn_lstm_cfg* c) { return check_lstm(c, GANFFN_MAX_DIALOGUES) ? -1 : lstm_saved(c).total; }
+extern "C" int64_t ganffn_lstm_batch_workspace_floats(const ganffn_lstm_cfg* c) { return check_lstm(c, GANFFN_MAX_DIALOGUES) ? -1 : lstm_ws(c); }
+extern "C" int ganffn_lstm_batch_layer_fwd(const ganffn_lstm_cfg* c, const float* x, const float* const* w_ih, const float* const* w_hh,
+                                           const float* const* b_ih, const float* const* b_hh, float* out, float* saved,
+                                           float* workspace, void* stream) {
+    return lstm_layer_fwd(c, x, w_ih, w_hh, b_ih, b_hh, out, saved, workspace, stream, GANFFN_MAX_DIALOGUES);
+}
+extern "C" int ganffn_lstm_batch_layer_bwd(const ganffn_lstm_cfg* c, const float* d_out, const float* x, const float* out,
+                                           const float* const* w_ih, const float* const* w_hh, float* dx, float* const* gw_ih,
+                                           float* const* gw_hh, float* const* gb_ih, float* const* gb_hh, const float* saved,
+                                           float* workspace, void* stream) {
+    return lstm_layer_bwd(c, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, workspace, stream, GANFFN_MAX_DIALOGUES);
+}
+extern "C" int64_t ganffn_lstm_stack_batch_saved_floats(const ganffn_lstm_stack_cfg* c) {
+    return check_lstm_stack(c, GANFFN_MAX_DIALOGUES) ? -1 : lstm_stack_saved(c).total;
+}
+extern "C" int64_t ganffn_lstm_stack_batch_workspace_floats(const ganffn_lstm_stack_cfg* c) {
+    return check_lstm_stack(c, GANFFN_MAX_DIALOGUES) ? -1 : lstm_stack_layer_ws(c) + 2 * (int64_t)c->S * c->B * 2 * c->H;
+}
+extern "C" int ganffn_lstm_stack_batch_fwd(const ganffn_lstm_stack_cfg* c, const float* x, const float* const* w_ih,
+                                           const float* const* w_hh, const float* const* b_ih, const float* const* b_hh, float* out,
+                                           float* saved, float* workspace, const uint64_t* rng, uint64_t rng_offset_add, void* stream) {
+    return lstm_stack_fwd(c, x, w_ih, w_hh, b_ih, b_hh, out, saved, workspace, rng, rng_offset_add, stream, GANFFN_MAX_DIALOGUES);
+}
+extern "C" int ganffn_lstm_stack_batch_bwd(const ganffn_lstm_stack_cfg* c, const float* d_out, const float* x, const float* out,
+                                           const float* const* w_ih, const float* const* w_hh, float* dx, float* const* gw_ih,
+                                           float* const* gw_hh, float* const* gb_ih, float* const* gb_hh, const float* saved,
+                                           float* workspace, const uint64_t* rng, uint64_t rng_offset_add, void* stream) {
+    return lstm_stack_bwd(c, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, workspace, rng, rng_offset_add, stream,
+                          GANFFN_MAX_DIALOGUES);
 }

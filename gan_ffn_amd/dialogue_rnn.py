@@ -10,7 +10,7 @@ On the GPU, with every context attention type (general, simple, dot, general2, c
 (ops.DialogueRNNFn: both directions of BiModel through one chain of launches, forward and backward;
 ops.dialogue_rnn_supported / dialogue_rnn_listener_supported say when: D_g = D_p <= 512, dot with D_m = D_g, concat with
 D_a % 4 == 0 and D_a <= 512, at most 112 steps, 1 to ops.DRNN_MAX_PARTIES = 16 parties — qmask's width: IEMOCAP's 2,
-MELD's 9); CPU tensors and shapes outside those limits take the torch-op
+MELD's 9; any batch size, one native call per ops.MAX_DIALOGUES = 256 dialogues); CPU tensors and shapes outside those limits take the torch-op
 restatement below, which is also what the reference-fixture parity tests pin.  The pieces with no sequential dependence are batched:
   * party selection is a gather, sequence reversal one index gather per tensor (the reference loops over dialogues),
   * BiModel's second attention — one masked `general2` MatchingAttention query per time step in the reference — is ONE

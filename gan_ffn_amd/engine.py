@@ -997,6 +997,19 @@ class Phase2Engine(GanEngine):
 SITE_JOIN_F, SITE_JOIN_B, SITE_HIDDEN = 5, 6, 7       # dropout sites of the head (the recurrence uses 8..14, the encoders 16+)
 
 
+_MAX_DIALOGUES_HINT = " (max_dialogues: the constructor takes up to %d)" % ops.MAX_DIALOGUES
+
+
+def _check_max_dialogues(who, n):
+    """a step runner's dialogue capacity: 32 (the default: one tile of the recurrences' products) .. ops.MAX_DIALOGUES"""
+    n = int(n)
+    if not 32 <= n <= ops.MAX_DIALOGUES:
+        raise ValueError("%s: max_dialogues = %d outside [32, %d] (ops.MAX_DIALOGUES: the most dialogues a native call of the "
+                         "recurrence takes) — split the batch, or run the module path, which chunks by itself"
+                         % (who, n, ops.MAX_DIALOGUES))
+    return n
+
+
 class DrnnEngine(GanEngine):
     """One train / eval step of GAN_FFN_DialogueRNN on the C ABI, no autograd graph: the three generators (n_streams = 3
     runs their forward and backward passes on three HIP streams chosen like GanEngine's; measured NOT faster than one
@@ -1014,11 +1027,15 @@ class DrnnEngine(GanEngine):
     _bwd, the 4 l_cell tensors per direction at the end of the head slab).  general runs ganffn_drnn_fwd / _bwd with the slab
     layout it always had; the other types run ganffn_drnn_att_fwd / _bwd with their attention tensors in the cell block
     (ops.DRNN_ATT_KEYS: named_parameters order).  The module path (model.GAN_FFN_DialogueRNN.forward under autograd) stays
-    available for what the kernels cannot run (D_g != D_p, D_g > 512, dot with D_m != D_g, concat D_a limits)."""
+    available for what the kernels cannot run (D_g != D_p, D_g > 512, dot with D_m != D_g, concat D_a limits).
+    max_dialogues (32 .. ops.MAX_DIALOGUES; default 32): the most dialogues a step takes.  It is a capacity, not a switch: a
+    batch of at most 32 dialogues runs the entry points named above whatever the capacity is, a larger one ganffn_drnn_batch_fwd /
+    _bwd (the same step with the dialogues in tiles of 32 inside every launch), decided from B alone."""
 
     def __init__(self, net, lr=1e-4, weight_decay=1e-5, class_weights=CLASS_WEIGHTS, process_group=None, n_buckets=3,
-                 n_streams=1):
+                 n_streams=1, max_dialogues=32):
         from . import dialogue_rnn as DR
+        self.max_dialogues = _check_max_dialogues("DrnnEngine", max_dialogues)
         self.module = net
         bm = net.bi_model
         cf, cr = bm.dialog_rnn_f.dialogue_cell, bm.dialog_rnn_r.dialogue_cell
@@ -1083,15 +1100,20 @@ class DrnnEngine(GanEngine):
         return (self.h_grad if grad else self.h_slab)[o:o + n]
 
     def reserve(self, S, B):
+        self._check_SB(S, B)
         self._cap_S, self._cap_B = max(self._cap_S, S), max(self._cap_B, B)
+
+    def _check_SB(self, S, B):
+        if B > self.max_dialogues or S > 112:
+            raise ValueError("DrnnEngine: at most %d dialogues%s of at most 112 utterances per step (the recurrence's tile and the "
+                             "attention kernels' sequence limit); got S = %d, B = %d — split the batch, or run the module path "
+                             "(model.GAN_FFN_DialogueRNN under autograd, which chunks by itself)"
+                             % (self.max_dialogues, _MAX_DIALOGUES_HINT if self.max_dialogues < ops.MAX_DIALOGUES else "", S, B))
 
     def _prepare5(self, S, B, P=2):
         if self._shape == (S, B, P):
             return
-        if B > 32 or S > 112:
-            raise ValueError("DrnnEngine: at most 32 dialogues of at most 112 utterances per step (the recurrence's tile and the "
-                             "attention kernels' sequence limit); got S = %d, B = %d — split the batch, or run the module path "
-                             "(model.GAN_FFN_DialogueRNN under autograd, which chunks by itself)" % (S, B))
+        self._check_SB(S, B)
         if self._shape is None or S > self._alloc_S or B > self._alloc_B or P > self._alloc_P:
             cS = self._cap_S = max(self._cap_S, S)
             cB = self._cap_B = max(self._cap_B, B)
@@ -1103,7 +1125,10 @@ class DrnnEngine(GanEngine):
             self.ws3 = {k: torch.empty(p_.n_ws, **f32) for k, p_ in self.pass_G.items()}     # one workspace per generator stream
             cfgc = _lib.DrnnCfg(cS, cB, self.Dm, self.H, self.He, self.p_rec, 1)
             lib = _lib.load()
-            if cP != 2:          # (the recurrence's buffers grow with the party count: sized for the widest batch so far)
+            if cB > 32:          # (the same layouts as functions of B; the entry points below refuse more than 32 dialogues)
+                n_saved = int(lib.ganffn_drnn_batch_saved_floats(C.byref(cfgc), C.byref(self.acfg), int(self.listener), cP))
+                n_ws = int(lib.ganffn_drnn_batch_workspace_floats(C.byref(cfgc), C.byref(self.acfg), int(self.listener), cP))
+            elif cP != 2:        # (the recurrence's buffers grow with the party count: sized for the widest batch so far)
                 n_saved = int(lib.ganffn_drnn_party_saved_floats(C.byref(cfgc), C.byref(self.acfg), int(self.listener), cP))
                 n_ws = int(lib.ganffn_drnn_party_workspace_floats(C.byref(cfgc), C.byref(self.acfg), int(self.listener), cP))
             elif self.att != "general":
@@ -1262,9 +1287,10 @@ class DrnnEngine(GanEngine):
         e_, al_, sv_, ws_ = arr([f["e_f"], f["e_b"]]), arr([f["alpha_f"], f["alpha_b"]]), arr([f["saved_f"], f["saved_b"]]), arr([f["ws_f"], f["ws_b"]])
         Pp = self._drnn_ptrs(False)
         parties = self._shape[2]
-        if parties != 2:
+        wide = B > 32            # more than one tile of dialogues: ganffn_drnn_batch_* (the _party_ argument lists)
+        if wide or parties != 2:
             LPp = self._drnn_listener_ptrs(False) if self.listener else None
-            _lib.call("ganffn_drnn_party_fwd", C.byref(cfg), C.byref(self.acfg), parties, 2, U_, spk_, mval_, Pp, LPp,
+            _lib.call("ganffn_drnn_batch_fwd" if wide else "ganffn_drnn_party_fwd", C.byref(cfg), C.byref(self.acfg), parties, 2, U_, spk_, mval_, Pp, LPp,
                       self._drnn_att_ptrs(False), e_, al_, sv_, ws_, P(rng), C.c_uint64(a_rec), st)
         elif self.att != "general":
             LPp = self._drnn_listener_ptrs(False) if self.listener else None
@@ -1308,8 +1334,8 @@ class DrnnEngine(GanEngine):
         # ---- the recurrence backward (weight gradients accumulate into the zeroed head slab)
         Gp = self._drnn_ptrs(True)
         de_, dU_ = arr([f["d_e_f"], f["d_e_b"]]), arr([f["dU_f"], f["dU_b"]])
-        if parties != 2:
-            _lib.call("ganffn_drnn_party_bwd", C.byref(cfg), C.byref(self.acfg), parties, 2, de_, U_, spk_, mval_, Pp, LPp,
+        if wide or parties != 2:
+            _lib.call("ganffn_drnn_batch_bwd" if wide else "ganffn_drnn_party_bwd", C.byref(cfg), C.byref(self.acfg), parties, 2, de_, U_, spk_, mval_, Pp, LPp,
                       self._drnn_att_ptrs(False), Gp, self._drnn_listener_ptrs(True) if self.listener else None,
                       self._drnn_att_ptrs(True), dU_, al_, sv_, ws_, P(rng), C.c_uint64(a_rec), st)
         elif self.att != "general":
@@ -1382,12 +1408,14 @@ class MeldEngine(_Runner):
     the LSTM's 32 tensors in named_parameters() order, matchatt.transform.{weight, bias}, smax_fc.{weight, bias}.
     `linear.{weight, bias}` serve the att2 = False branch only: their .grad is None in the reference, torch.optim.Adam skips such
     parameters entirely (no weight decay either), so they stay off the slab and are never touched.
-    Limits (ValueError; MELDLSTMModel under autograd — the module path — runs the rest): at most 32 dialogues of at most 128
-    utterances per step, 2 D_e <= 1024, D_m and D_e multiples of 4, at most 16 classes.
+    Limits (ValueError; MELDLSTMModel under autograd — the module path — runs the rest): at most max_dialogues dialogues (32 ..
+    ops.MAX_DIALOGUES, default 32: a capacity — up to 32 dialogues run ganffn_lstm_stack_*, more ganffn_lstm_stack_batch_*, decided
+    from B alone) of at most 128 utterances per step, 2 D_e <= 1024, D_m and D_e multiples of 4, at most 16 classes.
     Data-parallel over dialogues like Phase2Engine: the gradient slab is all-reduced in-line on the step's stream (through
     GradReducer under GANFFN_DP_MODE=buckets), Adam divides by the world size."""
 
-    def __init__(self, model, lr=3e-4, weight_decay=1e-4, class_weights=None, process_group=None):
+    def __init__(self, model, lr=3e-4, weight_decay=1e-4, class_weights=None, process_group=None, max_dialogues=32):
+        self.max_dialogues = _check_max_dialogues("MeldEngine", max_dialogues)
         self.module = model
         lstm = model.lstm
         if not (lstm.bidirectional and not lstm.batch_first and lstm.proj_size == 0 and lstm.bias):
@@ -1443,22 +1471,28 @@ class MeldEngine(_Runner):
 
     def reserve(self, S, B):
         """size every step buffer once for batches of up to (S, B): train / valid / test loaders then never re-allocate"""
+        self._check_SB(S, B)
         self._cap_S, self._cap_B = max(self._cap_S, S), max(self._cap_B, B)
+
+    def _check_SB(self, S, B):
+        if B > self.max_dialogues or S > 128:
+            raise ValueError("MeldEngine: at most %d dialogues%s of at most 128 utterances per step (the LSTM kernels' dialogue tile and "
+                             "the general2 attention kernel's sequence limit); got S = %d, B = %d — split the batch, or run the "
+                             "module path (MELDLSTMModel under autograd, which chunks by itself)"
+                             % (self.max_dialogues, _MAX_DIALOGUES_HINT if self.max_dialogues < ops.MAX_DIALOGUES else "", S, B))
 
     def _prepare(self, S, B):
         if self._shape == (S, B):
             return
-        if B > 32 or S > 128:
-            raise ValueError("MeldEngine: at most 32 dialogues of at most 128 utterances per step (the LSTM kernels' dialogue tile and "
-                             "the general2 attention kernel's sequence limit); got S = %d, B = %d — split the batch, or run the "
-                             "module path (MELDLSTMModel under autograd, which chunks by itself)" % (S, B))
+        self._check_SB(S, B)
         if self._shape is None or S > self._alloc_S or B > self._alloc_B:
             cS = self._cap_S = max(self._cap_S, S)
             cB = self._cap_B = max(self._cap_B, B)
             self._alloc_S, self._alloc_B = cS, cB
             lib = _lib.load()
             cfgc = _lib.LstmStackCfg(cS, cB, self.Dm, self.He, self.L, self.p_lstm, 1)
-            n_saved, n_ws = int(lib.ganffn_lstm_stack_saved_floats(C.byref(cfgc))), int(lib.ganffn_lstm_stack_workspace_floats(C.byref(cfgc)))
+            fam = "ganffn_lstm_stack_batch_" if cB > 32 else "ganffn_lstm_stack_"       # (the same sizes as functions of B)
+            n_saved, n_ws = int(getattr(lib, fam + "saved_floats")(C.byref(cfgc))), int(getattr(lib, fam + "workspace_floats")(C.byref(cfgc)))
             if n_saved < 0 or n_ws < 0:
                 _lib.check(-1, "ganffn_lstm_stack_*_floats")
             T, D2, Cn = cS * cB, self.D2, self.n_classes
@@ -1497,7 +1531,8 @@ class MeldEngine(_Runner):
         n_t = 8 * self.L
         w_t, b_t, w_s, b_s = (self._p(n_t + j) for j in range(4))
         # ---- forward: LSTM stack -> transform -> general2 attention -> hardswish head -> loss       (model.py:546-560)
-        _lib.call("ganffn_lstm_stack_fwd", C.byref(cfg), P(text), w_ih, w_hh, b_ih, b_hh, P(f["emotions"]), P(f["saved"]), P(f["ws"]),
+        fam = "ganffn_lstm_stack_batch_" if B > 32 else "ganffn_lstm_stack_"
+        _lib.call(fam + "fwd", C.byref(cfg), P(text), w_ih, w_hh, b_ih, b_hh, P(f["emotions"]), P(f["saved"]), P(f["ws"]),
                   P(rng), C.c_uint64(base), st)
         ops.linear_fwd_raw(f["emotions"], w_t, b_t, f["xq"], T, D2, D2)
         _lib.call("ganffn_general2_attention_fwd", P(f["xq"]), P(f["emotions"]), P(umask), P(f["att"]), P(f["alpha"]), P(f["tanh_s"]),
@@ -1519,7 +1554,7 @@ class MeldEngine(_Runner):
         # d emotions = the residual + the attention's memory side + its query side through transform
         _lib.call("ganffn_add3", P(f["d_res"]), P(f["d_mem"]), P(f["d_tr"]), P(f["d_em"]), C.c_int64(T * D2), st)
         g_ih, g_hh, gb_ih, gb_hh = self._g
-        _lib.call("ganffn_lstm_stack_bwd", C.byref(cfg), P(f["d_em"]), P(text), P(f["emotions"]), w_ih, w_hh, None, g_ih, g_hh, gb_ih,
+        _lib.call(fam + "bwd", C.byref(cfg), P(f["d_em"]), P(text), P(f["emotions"]), w_ih, w_hh, None, g_ih, g_hh, gb_ih,
                   gb_hh, P(f["saved"]), P(f["ws"]), P(rng), C.c_uint64(base), st)
         if self.pg is not None:
             if dp_mode() == "inline":

@@ -465,6 +465,7 @@ DRNN_KEYS = ["g_cell.weight_ih", "g_cell.weight_hh", "g_cell.bias_ih", "g_cell.b
              "e_cell.weight_ih", "e_cell.weight_hh", "e_cell.bias_ih", "e_cell.bias_hh", "attention.transform.weight"]
 DRNN_LISTENER_KEYS = ["l_cell.weight_ih", "l_cell.weight_hh", "l_cell.bias_ih", "l_cell.bias_hh"]
 DRNN_MAX_PARTIES = 16      # GANFFN_DRNN_MAX_PARTIES: qmask's party axis on the HIP recurrence is 1 .. 16 wide
+MAX_DIALOGUES = 256        # GANFFN_MAX_DIALOGUES: dialogues per native call of either recurrence (ganffn_drnn_batch_* / ganffn_lstm_batch_*)
 
 
 def _ptr_array(tensors):
@@ -505,7 +506,9 @@ class DialogueRNNFn(torch.autograd.Function):
     the call goes through ganffn_drnn_att_* (cfg_dict["Da"]: concat's D_a).
     cfg_dict["parties"] (default 2): the width P of qmask's party axis.  P = 2 makes the calls above; any other P (1 ..
     DRNN_MAX_PARTIES) goes through ganffn_drnn_party_*, general attention included (its transform.weight as the attention
-    parameter), with the same arguments and gradients."""
+    parameter), with the same arguments and gradients.
+    More than 32 dialogues (up to MAX_DIALOGUES; decided from B alone): ganffn_drnn_batch_*, whatever the attention type,
+    listener flag and party count — the _party_ argument lists."""
 
     @staticmethod
     def forward(ctx, meta, *args):
@@ -534,7 +537,11 @@ class DialogueRNNFn(torch.autograd.Function):
         lib = _lib.load()
         acfg = _lib.DrnnAtt(_lib.DRNN_ATT_TYPES[att], int(meta.get("Da", 0)))
         parties = int(meta.get("parties", 2))
-        if parties != 2:
+        batch = B > 32
+        if batch:
+            n_saved = int(lib.ganffn_drnn_batch_saved_floats(C.byref(cfg), C.byref(acfg), int(listener), parties))
+            n_ws = int(lib.ganffn_drnn_batch_workspace_floats(C.byref(cfg), C.byref(acfg), int(listener), parties))
+        elif parties != 2:
             n_saved = int(lib.ganffn_drnn_party_saved_floats(C.byref(cfg), C.byref(acfg), int(listener), parties))
             n_ws = int(lib.ganffn_drnn_party_workspace_floats(C.byref(cfg), C.byref(acfg), int(listener), parties))
         elif aprm is not None:
@@ -555,10 +562,10 @@ class DialogueRNNFn(torch.autograd.Function):
         rng = DeviceRng.get(dev)
         add = rng.next_add() if train else 0
         P = (_lib.DrnnPtrs * ndir)(*[_drnn_ptrs(p) for p in prm])
-        if parties != 2:
+        if batch or parties != 2:
             LP = (_lib.DrnnListenerPtrs * ndir)(*[_drnn_ptrs(p, _lib.DrnnListenerPtrs) for p in lprm]) if listener else None
             AP = (_lib.DrnnAttPtrs * ndir)(*[_att_ptrs(att, a) for a in (aprm or [[p[12]] for p in prm])])
-            _lib.call("ganffn_drnn_party_fwd", C.byref(cfg), C.byref(acfg), parties, ndir, _ptr_array(U), _ptr_array(spk),
+            _lib.call("ganffn_drnn_batch_fwd" if batch else "ganffn_drnn_party_fwd", C.byref(cfg), C.byref(acfg), parties, ndir, _ptr_array(U), _ptr_array(spk),
                       _ptr_array(mval), P, LP, AP, _ptr_array(e), _ptr_array(alpha), _ptr_array(saved), _ptr_array(ws),
                       _ptr(rng.state), C.c_uint64(add), _stream())
         elif aprm is not None:
@@ -576,7 +583,7 @@ class DialogueRNNFn(torch.autograd.Function):
             _lib.call("ganffn_drnn_fwd", C.byref(cfg), ndir, _ptr_array(U), _ptr_array(spk), _ptr_array(mval), P, _ptr_array(e),
                       _ptr_array(alpha), _ptr_array(saved), _ptr_array(ws), _ptr(rng.state), C.c_uint64(add), _stream())
         ctx.cfg, ctx.ndir, ctx.add, ctx.rng_state = cfg, ndir, add, rng.state
-        ctx.att, ctx.acfg, ctx.aprm, ctx.parties = att, acfg, aprm, parties
+        ctx.att, ctx.acfg, ctx.aprm, ctx.parties, ctx.batch = att, acfg, aprm, parties, batch
         ctx.keep = (U, spk, mval, prm, lprm, alpha, saved, ws)
         out = []
         for z in range(ndir):
@@ -593,7 +600,7 @@ class DialogueRNNFn(torch.autograd.Function):
         grads = [[torch.zeros_like(p) if p is not None else None for p in prm[z]] for z in range(ndir)]
         P = (_lib.DrnnPtrs * ndir)(*[_drnn_ptrs(p) for p in prm])
         G = (_lib.DrnnPtrs * ndir)(*[_drnn_ptrs(g) for g in grads])
-        if ctx.parties != 2:
+        if ctx.batch or ctx.parties != 2:
             general = ctx.aprm is None        # (general: transform.weight and its gradient are the attention's own parameter)
             aprm = [[p[12]] for p in prm] if general else ctx.aprm
             agrads = [[g[12]] for g in grads] if general else [[torch.zeros_like(p) for p in aprm[z]] for z in range(ndir)]
@@ -605,7 +612,7 @@ class DialogueRNNFn(torch.autograd.Function):
                 LG = (_lib.DrnnListenerPtrs * ndir)(*[_drnn_ptrs(g, _lib.DrnnListenerPtrs) for g in lgrads])
             else:
                 lgrads, LP, LG = [[] for _ in range(ndir)], None, None
-            _lib.call("ganffn_drnn_party_bwd", C.byref(cfg), C.byref(ctx.acfg), ctx.parties, ndir, _ptr_array(d_e), _ptr_array(U),
+            _lib.call("ganffn_drnn_batch_bwd" if ctx.batch else "ganffn_drnn_party_bwd", C.byref(cfg), C.byref(ctx.acfg), ctx.parties, ndir, _ptr_array(d_e), _ptr_array(U),
                       _ptr_array(spk), _ptr_array(mval), P, LP, AP, G, LG, AG, _ptr_array(dU), _ptr_array(alpha), _ptr_array(saved),
                       _ptr_array(ws), _ptr(ctx.rng_state), C.c_uint64(ctx.add), _stream())
             out = [None]
@@ -733,12 +740,13 @@ def _drnn_cell_args(cell, U):
 
 def dialogue_rnn_run(cells, Us, qmasks, training):
     """cells / Us / qmasks: one entry per direction.  -> [(emotions (S,B,D_e), [alpha_t (B,t)] for t >= 1)] per direction.
-    Dialogues run in chunks of 32 (the kernels' tile); chunks are independent."""
+    One native call for B <= MAX_DIALOGUES (at most 32 dialogues: the entry points that always took them; more: ganffn_drnn_batch_*,
+    the dialogues in tiles of 32 inside every launch); beyond that, chunks of MAX_DIALOGUES (chunks are independent)."""
     ndir = len(cells)
     S, B = Us[0].shape[:2]
     e_parts, a_parts = [[] for _ in range(ndir)], [[] for _ in range(ndir)]
-    for b0 in range(0, B, 32):
-        b1 = min(B, b0 + 32)
+    for b0 in range(0, B, MAX_DIALOGUES):
+        b1 = min(B, b0 + MAX_DIALOGUES)
         args = []
         for z in range(ndir):
             qm = qmasks[z][:, b0:b1]
@@ -773,8 +781,9 @@ SITE_LSTM = 64          # + layer: the dropout nn.LSTM(dropout=p) applies to the
 
 class LstmLayerFn(torch.autograd.Function):
     """one bidirectional LSTM layer: x (S, B, In) -> (S, B, 2H) = [h forward | h reverse]; torch's parameters
-    weight_ih [4H x In], weight_hh [4H x H], bias_ih, bias_hh [4H] per direction (gate order i, f, g, o).  The kernels take at
-    most 32 dialogues per call: bigger batches run in chunks (dialogues are independent)."""
+    weight_ih [4H x In], weight_hh [4H x H], bias_ih, bias_hh [4H] per direction (gate order i, f, g, o).  One native call for
+    B <= MAX_DIALOGUES (at most 32 dialogues: ganffn_lstm_layer_*; more: ganffn_lstm_batch_layer_*); bigger batches run in chunks of
+    MAX_DIALOGUES (dialogues are independent)."""
 
     @staticmethod
     def forward(ctx, x, *params):
@@ -785,16 +794,19 @@ class LstmLayerFn(torch.autograd.Function):
         H = p[1].shape[1]
         out = torch.empty(S, B, 2 * H, device=x.device, dtype=torch.float32)
         chunks = []
-        for b0 in range(0, B, 32):
-            b1 = min(B, b0 + 32)
+        for b0 in range(0, B, MAX_DIALOGUES):
+            b1 = min(B, b0 + MAX_DIALOGUES)
             cfg = _lib.LstmCfg(S, b1 - b0, In, H)
-            n_saved = int(_lib.load().ganffn_lstm_saved_floats(C.byref(cfg)))
-            n_ws = int(_lib.load().ganffn_lstm_workspace_floats(C.byref(cfg)))
+            fam = "ganffn_lstm_batch_" if b1 - b0 > 32 else "ganffn_lstm_"
+            n_saved = int(getattr(_lib.load(), fam + "saved_floats")(C.byref(cfg)))
+            n_ws = int(getattr(_lib.load(), fam + "workspace_floats")(C.byref(cfg)))
+            if n_saved < 0 or n_ws < 0:
+                _lib.check(-1, fam + "*_floats")
             xc = x if (b0, b1) == (0, B) else x[:, b0:b1].contiguous()
             oc = out if (b0, b1) == (0, B) else torch.empty(S, b1 - b0, 2 * H, device=x.device, dtype=torch.float32)
             saved = torch.empty(n_saved, device=x.device, dtype=torch.float32)
             ws = torch.empty(n_ws, device=x.device, dtype=torch.float32)
-            _lib.call("ganffn_lstm_layer_fwd", C.byref(cfg), _ptr(xc), _ptr_array([p[0], p[4]]), _ptr_array([p[1], p[5]]),
+            _lib.call(fam + "layer_fwd", C.byref(cfg), _ptr(xc), _ptr_array([p[0], p[4]]), _ptr_array([p[1], p[5]]),
                       _ptr_array([p[2], p[6]]), _ptr_array([p[3], p[7]]), _ptr(oc), _ptr(saved), _ptr(ws), _stream())
             if oc is not out:
                 out[:, b0:b1] = oc
@@ -813,13 +825,14 @@ class LstmLayerFn(torch.autograd.Function):
         grads = [torch.zeros_like(t) if ctx.needs_input_grad[1 + i] else None for i, t in enumerate(p)]
         for (b0, b1, xc, oc, saved) in ctx.chunks:
             cfg = _lib.LstmCfg(S, b1 - b0, In, H)
-            n_ws = int(_lib.load().ganffn_lstm_workspace_floats(C.byref(cfg)))
+            fam = "ganffn_lstm_batch_" if b1 - b0 > 32 else "ganffn_lstm_"
+            n_ws = int(getattr(_lib.load(), fam + "workspace_floats")(C.byref(cfg)))
             ws = torch.empty(n_ws, device=d_out.device, dtype=torch.float32)
             dc = d_out if (b0, b1) == (0, B) else d_out[:, b0:b1].contiguous()
             dxc = None
             if need_dx:
                 dxc = dx if (b0, b1) == (0, B) else torch.empty(S, b1 - b0, In, device=d_out.device, dtype=torch.float32)
-            _lib.call("ganffn_lstm_layer_bwd", C.byref(cfg), _ptr(dc), _ptr(xc), _ptr(oc), _ptr_array([p[0], p[4]]), _ptr_array([p[1], p[5]]),
+            _lib.call(fam + "layer_bwd", C.byref(cfg), _ptr(dc), _ptr(xc), _ptr(oc), _ptr_array([p[0], p[4]]), _ptr_array([p[1], p[5]]),
                       _ptr(dxc), _ptr_array([grads[0], grads[4]]), _ptr_array([grads[1], grads[5]]), _ptr_array([grads[2], grads[6]]),
                       _ptr_array([grads[3], grads[7]]), _ptr(saved), _ptr(ws), _stream())
             if need_dx and dxc is not dx:

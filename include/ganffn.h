@@ -375,6 +375,30 @@ int ganffn_drnn_party_bwd(const ganffn_drnn_cfg* cfg, const ganffn_drnn_att* att
                           const float* const* alpha, const float* const* saved, float* const* workspace,
                           const uint64_t* rng, uint64_t rng_offset_add, void* stream);
 
+/* Any batch size up to GANFFN_MAX_DIALOGUES (every reference trainer has --batch-size: train_IEMOCAP_DialogueRNN.py:580,
+ * train_MELD.py:114; BASELINE.json configs[3] names a global batch of 256): ganffn_drnn_party_* with 1 <= cfg->B <=
+ * GANFFN_MAX_DIALOGUES (anything else is an argument error reported through ganffn_last_error; the entry points above keep
+ * their B <= 32).  The skinny products of a step take the dialogues in tiles of 32 on a grid axis, so a step is still 2 + 2
+ * launches (4 + 4 with listener state) whatever B is, and every dialogue's sums are formed in the order of a 32-dialogue
+ * call: in eval mode row b of the outputs does not depend on which other dialogues share the call.  Sizes, layouts
+ * (functions of B as documented above) and arguments are those of ganffn_drnn_party_*; at B <= 32 every call is the same
+ * launch sequence, bit for bit.  Dropout rows are t*B + b with B the whole batch of the call. */
+#define GANFFN_MAX_DIALOGUES 256
+int64_t ganffn_drnn_batch_saved_floats(const ganffn_drnn_cfg* cfg, const ganffn_drnn_att* att, int listener, int parties);
+int64_t ganffn_drnn_batch_workspace_floats(const ganffn_drnn_cfg* cfg, const ganffn_drnn_att* att, int listener, int parties);
+int ganffn_drnn_batch_fwd(const ganffn_drnn_cfg* cfg, const ganffn_drnn_att* att, int parties, int ndir, const float* const* U,
+                          const int32_t* const* spk, const float* const* mval, const ganffn_drnn_params* params,
+                          const ganffn_drnn_listener_params* lparams, const ganffn_drnn_att_params* aparams,
+                          float* const* e_out, float* const* alpha, float* const* saved, float* const* workspace,
+                          const uint64_t* rng, uint64_t rng_offset_add, void* stream);
+int ganffn_drnn_batch_bwd(const ganffn_drnn_cfg* cfg, const ganffn_drnn_att* att, int parties, int ndir, const float* const* d_e,
+                          const float* const* U, const int32_t* const* spk, const float* const* mval,
+                          const ganffn_drnn_params* params, const ganffn_drnn_listener_params* lparams,
+                          const ganffn_drnn_att_params* aparams, const ganffn_drnn_grads* grads,
+                          const ganffn_drnn_listener_grads* lgrads, const ganffn_drnn_att_grads* agrads, float* const* dU,
+                          const float* const* alpha, const float* const* saved, float* const* workspace,
+                          const uint64_t* rng, uint64_t rng_offset_add, void* stream);
+
 /* Data movement of BiModel.forward around the recurrence (model.py:1008-1062), one launch each (csrc/drnn_head.hip):
  * ganffn_seq_reverse: out[s, b, :] (+)= s < lens[b] ? x[lens[b]-1-s, b, :] : 0 — BiModel._reverse_seq and, being its own
  *   transpose, its gradient (accumulate != 0 adds into out); x, out [S x B x D], D % 4 == 0.
@@ -398,6 +422,8 @@ int ganffn_mask_pos_inplace(float* d, const float* aux, float mscale, int64_t n,
  * W_i^T (nn = 0, W_i [N x K]) or A W_i (nn = 1, W_i [K x N]); W / C hold the copies back to back; M <= 32 (unit tests and
  * the roofline leg of bench.py --config drnn) */
 int ganffn_drnn_skinny(int nn, int copies, const float* A, const float* W, float* C, int M, int N, int K, void* stream);
+/* the same with M <= GANFFN_MAX_DIALOGUES: above 32 rows the launch takes them in tiles of 32 on a grid axis (unit tests) */
+int ganffn_drnn_skinny_batch(int nn, int copies, const float* A, const float* W, float* C, int M, int N, int K, void* stream);
 
 /* ---- building blocks exported for unit tests ----------------------------------------- */
 /* C[M x N] = A[M x K] * W[N x K]^T + bias (bias may be NULL) */
@@ -519,6 +545,31 @@ int ganffn_lstm_stack_bwd(const ganffn_lstm_stack_cfg* cfg, const float* d_out, 
                           const float* const* w_ih, const float* const* w_hh, float* dx, float* const* gw_ih,
                           float* const* gw_hh, float* const* gb_ih, float* const* gb_hh, const float* saved,
                           float* workspace, const uint64_t* rng, uint64_t rng_offset_add, void* stream);
+
+/* ---- N4: the LSTM recurrence on up to GANFFN_MAX_DIALOGUES dialogues per call (csrc/lstm.hip) -------------------------------
+ * The four ganffn_lstm_* and the four ganffn_lstm_stack_* entry points above (nn.LSTM of MELDLSTMModel, /root/reference/model.py:
+ * 531,546, under train_MELD.py:114's --batch-size) with 1 <= cfg->B <= GANFFN_MAX_DIALOGUES instead of 32: same arguments, same
+ * layouts and sizes as functions of B, still one product launch and one gate launch per step and direction pair.  At B <= 32
+ * every call is the same launch sequence as its namesake above, bit for bit; B = 0 or B > GANFFN_MAX_DIALOGUES is an argument
+ * error reported through ganffn_last_error (the size functions return a negative value). */
+int64_t ganffn_lstm_batch_saved_floats(const ganffn_lstm_cfg* cfg);
+int64_t ganffn_lstm_batch_workspace_floats(const ganffn_lstm_cfg* cfg);
+int ganffn_lstm_batch_layer_fwd(const ganffn_lstm_cfg* cfg, const float* x, const float* const* w_ih, const float* const* w_hh,
+                                const float* const* b_ih, const float* const* b_hh, float* out, float* saved, float* workspace,
+                                void* stream);
+int ganffn_lstm_batch_layer_bwd(const ganffn_lstm_cfg* cfg, const float* d_out, const float* x, const float* out,
+                                const float* const* w_ih, const float* const* w_hh, float* dx, float* const* gw_ih,
+                                float* const* gw_hh, float* const* gb_ih, float* const* gb_hh, const float* saved,
+                                float* workspace, void* stream);
+int64_t ganffn_lstm_stack_batch_saved_floats(const ganffn_lstm_stack_cfg* cfg);
+int64_t ganffn_lstm_stack_batch_workspace_floats(const ganffn_lstm_stack_cfg* cfg);
+int ganffn_lstm_stack_batch_fwd(const ganffn_lstm_stack_cfg* cfg, const float* x, const float* const* w_ih, const float* const* w_hh,
+                                const float* const* b_ih, const float* const* b_hh, float* out, float* saved, float* workspace,
+                                const uint64_t* rng, uint64_t rng_offset_add, void* stream);
+int ganffn_lstm_stack_batch_bwd(const ganffn_lstm_stack_cfg* cfg, const float* d_out, const float* x, const float* out,
+                                const float* const* w_ih, const float* const* w_hh, float* dx, float* const* gw_ih,
+                                float* const* gw_hh, float* const* gb_ih, float* const* gb_hh, const float* saved,
+                                float* workspace, const uint64_t* rng, uint64_t rng_offset_add, void* stream);
 
 /* ---- N4: the MELD classifier's head (csrc/meld_head.hip) ------------------------------------------------------------------
  * Replaces `hidden = F.hardswish(emotions + F.hardswish(att_emotions))` and `self.smax_fc(hidden)` of MELDLSTMModel.forward
