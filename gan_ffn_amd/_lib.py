@@ -64,6 +64,13 @@ class DrnnAttPtrs(C.Structure):     # ganffn_drnn_att_params / ganffn_drnn_att_g
     _fields_ = [(n, C.c_void_p) for n in DRNN_ATT_FIELDS]
 
 
+BATCH_MAX_COLS = 4                 # GANFFN_BATCH_MAX_COLS
+
+
+class BatchCol(C.Structure):        # ganffn_batch_col: one column of the packed corpus and where its padded batch goes
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("width", C.c_int32)]
+
+
 _P = C.c_void_p
 _I, _L, _F, _U32, _U64 = C.c_int, C.c_int64, C.c_float, C.c_uint32, C.c_uint64
 _PE, _PH = C.POINTER(EncCfg), C.POINTER(HeadCfg)
@@ -167,6 +174,8 @@ SIGNATURES = {
     "ganffn_drnn_join_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _U32, _U32, _P, _U64, _I, _P]),
     "ganffn_drnn_join_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _U32, _U32, _P, _U64, _I, _P]),
     "ganffn_mask_pos_inplace": (_I, [_P, _P, _F, _L, _P]),
+    "ganffn_batch_gather": (_I, [_P, _I, _P, _P, _L, _P, _P, _P, _I, _I, _I, _P]),
+    "ganffn_epoch_record": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _L, _L, _P, _P, _I, _I, _P]),
 }
 
 _lib = None

@@ -164,8 +164,12 @@ def train_or_eval_model(engine, loader, train=False, device="cuda", to_batch=Non
     train_IEMOCAP.py:189-197 (GAN_FFN has no attention weights: the alpha lists stay empty).
     to_batch: collated batch -> engine batch (default data.to_batch, the IEMOCAP one).  With engine.MeldEngine and
     data.to_meld_batch this is train_MELD.py:50-104: an engine that has `.alpha` (the (B, S, S) attention weights of its last
-    step) fills the first list, on eval batches, with one (B, S) tensor per query step like the script's `alphas += alpha`."""
+    step) fills the first list, on eval batches, with one (B, S) tensor per query step like the script's `alphas += alpha`.
+    loader: a data.DeviceLoader (the corpus packed on the GPU) takes the device path (_device_epoch): same tuple, one
+    device-to-host read per epoch instead of four per batch; `device` and `to_batch` are then not used."""
     from . import data as D
+    if isinstance(loader, D.DeviceLoader):
+        return _device_epoch(engine, loader, train)
     to_batch = to_batch or D.to_batch
     losses, preds, labels, masks, vids, alphas = [], [], [], [], [], []
     for collated in loader:
@@ -189,16 +193,47 @@ def train_or_eval_model(engine, loader, train=False, device="cuda", to_batch=Non
     return avg_loss, avg_acc, labels, preds, masks, avg_f, [alphas, [], [], vids]
 
 
+def _device_epoch(engine, loader, train):
+    """train_or_eval_model over a data.DeviceLoader: the same steps and the same returned tuple, with no device-to-host read
+    inside the loop — one ganffn_epoch_record launch per step keeps predictions, labels, masks, loss and the count of real
+    utterances on the device, and the host reads them once, after the last step."""
+    from . import ops
+    ep = loader.epoch()
+    if not len(ep):
+        return float("nan"), float("nan"), [], [], [], float("nan"), []
+    rec = ops.EpochRecord(ep.total, len(ep), loader.corpus.device)
+    vids, alphas = [], []
+    for i, (batch, (_, _, offset)) in enumerate(zip(ep, ep.batches)):
+        loss, log_prob = engine.step(batch, train=train)
+        rec.record(i, offset, log_prob, batch["label"], batch["umask"], loss)
+        if not train and batch.get("vids"):
+            vids += batch["vids"]
+        if not train and getattr(engine, "alpha", None) is not None:
+            a = engine.alpha.clone()                     # (the engine's buffer is overwritten by the next step)
+            alphas += [a[:, t, :] for t in range(a.size(1))]
+    preds, labels, masks, loss_h, count_h = rec.host()
+    losses = [float(l_) * c_ for l_, c_ in zip(loss_h, count_h)]          # float(loss) * m.sum(), m float32, as the host path
+    avg_loss, avg_acc, avg_f = epoch_metrics(losses, labels, preds, masks)
+    return avg_loss, avg_acc, labels, preds, masks, avg_f, [alphas, [], [], vids]
+
+
 def run_training(dataset_path, g_epochs=150, n_epochs=160, lr=1e-4, l2=0.008, batch_size=32, out_dir="./output/",
-                 model_save_path="./GAN_save/", device="cuda", seed=None, log=print):
+                 model_save_path="./GAN_save/", device="cuda", seed=None, log=print, device_corpus=False):
     """The reference's __main__ flow on the HIP path: GAN phase (lr 1e-4, betas (0.5, 0.6), batch 32 whatever
     `batch_size` says — train_IEMOCAP.py:595-607) -> GAN_loss.csv + six checkpoints -> GAN_FFN phase for `n_epochs`
-    -> test_out_*.txt from the epoch with the best test loss.  Returns (report file, final F1, loss table)."""
+    -> test_out_*.txt from the epoch with the best test loss.  Returns (report file, final F1, loss table).
+    device_corpus: pack both splits on the GPU once per phase and draw every batch from there (data.DeviceLoader) instead of
+    collating on the host; same batches, same RNG draws, same results."""
     from . import data as D, engine as E, model as M
     gens, discs = E.build_networks(100, 0.2, device, seed)
-    train_loader, _, _ = D.get_IEMOCAP_loaders(dataset_path, batch_size=32, valid=0.1)
-    rows = E.train_GAN(gens, discs, _DeviceBatches(train_loader, device), epochs=g_epochs, lr=1e-4, b1=0.5, b2=0.6,
-                       reserve_S=110)
+    if device_corpus:
+        loaders = lambda bs: D.get_device_loaders(D.IEMOCAPDataset(dataset_path, True), D.IEMOCAPDataset(dataset_path, False),
+                                                  bs, 0.1, device)
+        batches = loaders(32)[0]
+    else:
+        loaders = lambda bs: D.get_IEMOCAP_loaders(dataset_path, batch_size=bs, valid=0.1)
+        batches = _DeviceBatches(loaders(32)[0], device)
+    rows = E.train_GAN(gens, discs, batches, epochs=g_epochs, lr=1e-4, b1=0.5, b2=0.6, reserve_S=110)
     df = loss_table(rows)
     save_GAN_loss(df, os.path.join(out_dir, "GAN_loss.csv"))
     if not os.path.exists(model_save_path):
@@ -209,7 +244,7 @@ def run_training(dataset_path, g_epochs=150, n_epochs=160, lr=1e-4, l2=0.008, ba
     net = M.GAN_FFN(gens["acoustic"], gens["visual"], gens["text"], n_classes=6).to(device)
     eng = E.Phase2Engine(net, lr=lr, weight_decay=l2)
     eng.reserve(110, batch_size)                     # PositionalEncoding caps a dialogue at 110 utterances
-    train_loader, valid_loader, test_loader = D.get_IEMOCAP_loaders(dataset_path, batch_size=batch_size, valid=0.1)
+    train_loader, valid_loader, test_loader = loaders(batch_size)
     best = None
     for e in range(n_epochs):
         tr = train_or_eval_model(eng, train_loader, True, device)
@@ -226,17 +261,22 @@ def run_training(dataset_path, g_epochs=150, n_epochs=160, lr=1e-4, l2=0.008, ba
 
 
 def run_meld_training(pickle_path, n_epochs=50, lr=3e-4, l2=1e-4, dropout=0.6, batch_size=32, classify="emotion", device="cuda",
-                      seed=None, log=print):
+                      seed=None, log=print, device_corpus=False):
     """The __main__ flow of train_MELD.py:143-195 on the HIP path: MELDLSTMModel(600, 300, 600) through engine.MeldEngine,
     MaskedNLLLoss without class weights, Adam(lr, weight_decay = l2), loaders with valid = 0.0, the per-epoch line, and the
-    test epoch with the best F-score kept.  Returns (best_loss, best_fscore, labels, preds, masks, attentions)."""
+    test epoch with the best F-score kept.  Returns (best_loss, best_fscore, labels, preds, masks, attentions).
+    device_corpus: as in run_training."""
     from . import data as D, engine as E, dialogue_rnn as DR
     if seed is not None:
         torch.manual_seed(seed)
     n_classes = 7 if classify == "emotion" else 3                                 # train_MELD.py:138-141
     model = DR.MELDLSTMModel(600, 300, 600, n_classes=n_classes, dropout=dropout).to(device)
     eng = E.MeldEngine(model, lr=lr, weight_decay=l2, max_dialogues=max(32, batch_size))      # train_MELD.py:114 --batch-size
-    train_loader, valid_loader, test_loader = D.get_MELD_loaders(pickle_path, batch_size=batch_size, valid=0.0, classify=classify)
+    if device_corpus:
+        train_loader, valid_loader, test_loader = D.get_device_loaders(D.MELDDataset(pickle_path, classify, True),
+                                                                       D.MELDDataset(pickle_path, classify, False), batch_size, 0.0, device)
+    else:
+        train_loader, valid_loader, test_loader = D.get_MELD_loaders(pickle_path, batch_size=batch_size, valid=0.0, classify=classify)
     eng.reserve(33, batch_size)                      # MELD's longest dialogue
     best = None
     for e in range(n_epochs):

@@ -254,3 +254,147 @@ def collate(items, device="cpu"):
         out["umask"][b, :n] = 1
         out["label"][b, :n] = torch.from_numpy(y)
     return {k: v.to(device) for k, v in out.items()}
+
+
+# ------------------------------------------------------------------------------------------------
+# the corpus on the device: one split packed once, batches gathered by one launch each (csrc/batch.hip)
+# ------------------------------------------------------------------------------------------------
+FEATURE_NAMES = {3: ("text", "visual", "acoustic"), 2: ("text", "acoustic")}     # IEMOCAPDataset / MELDDataset item layouts
+
+
+class DeviceCorpus:
+    """One split of a dataset packed on `device`: per feature column one fp32 matrix [N_utt x width] with the dialogues back to
+    back in `dataset.keys` order, the speaker one-hots [N_utt x P] fp32, labels [N_utt] int64 and row0 [N_dial + 1] int64
+    prefix offsets; the lengths and keys stay on the host as well.  Every dialogue goes through the dataset's own __getitem__
+    once — item = (features..., speakers, umask, labels, vid), IEMOCAPDataset's or MELDDataset's — so normalisation and the
+    float64 -> float32 conversion are the host path's.  `device` may be "cpu" for host-side logic (packing, index streams);
+    batches are gathered on the GPU only."""
+
+    def __init__(self, dataset, device="cuda"):
+        self.device = torch.device(device)
+        n = len(dataset)
+        if n < 1:
+            raise ValueError("DeviceCorpus: the dataset has no dialogue")
+        items = [dataset[i] for i in range(n)]
+        n_feat = len(items[0]) - 4
+        if n_feat not in FEATURE_NAMES:
+            raise ValueError("DeviceCorpus: items of %d fields; expected (text, visual, audio, speakers, umask, labels, vid) or "
+                             "(text, audio, speakers, umask, labels, vid)" % len(items[0]))
+        self.names = FEATURE_NAMES[n_feat]
+        self.keys = [it[-1] for it in items]
+        self.lengths = [int(it[-2].shape[0]) for it in items]
+        for it, L in zip(items, self.lengths):
+            if L < 1 or any(int(it[j].shape[0]) != L for j in range(n_feat + 1)):
+                raise ValueError("DeviceCorpus: dialogue %r: every field needs the same number (>= 1) of utterances" % (it[-1],))
+        self.n_dialogues, self.n_rows = n, int(sum(self.lengths))
+        pack = lambda j, dt: torch.cat([it[j].to(dt).reshape(it[j].shape[0], -1) for it in items]).contiguous().to(self.device)
+        self.features = {k: pack(j, torch.float32) for j, k in enumerate(self.names)}
+        self.qmask = pack(n_feat, torch.float32)
+        self.labels = torch.cat([it[-2].long() for it in items]).contiguous().to(self.device)
+        off = [0]
+        for L in self.lengths:
+            off.append(off[-1] + L)
+        self.row0 = torch.tensor(off, dtype=torch.int64).to(self.device)
+        self.widths = {k: int(v.shape[1]) for k, v in self.features.items()}
+        self.n_parties = int(self.qmask.shape[1])
+
+    def __len__(self):
+        return self.n_dialogues
+
+    def gather(self, idx_dev, S):
+        """idx_dev: int32 [B] on the device, S: the padded length -> the dict the engines take (without vids): one launch"""
+        from . import ops
+        B = int(idx_dev.numel())
+        dev = idx_dev.device
+        out = {k: torch.empty(S, B, w, dtype=torch.float32, device=dev) for k, w in self.widths.items()}
+        out["qmask"] = torch.empty(S, B, self.n_parties, dtype=torch.float32, device=dev)
+        out["umask"] = torch.empty(B, S, dtype=torch.float32, device=dev)
+        out["label"] = torch.empty(B, S, dtype=torch.int64, device=dev)
+        cols = [(self.features[k], out[k], self.widths[k]) for k in self.names] + [(self.qmask, out["qmask"], self.n_parties)]
+        ops.batch_gather_raw(cols, self.labels, self.row0, self.n_rows, idx_dev, out["umask"], out["label"], S, B, self.n_dialogues)
+        return out
+
+
+class _Indices(torch.utils.data.Dataset):
+    def __init__(self, n):
+        self.n = n
+
+    def __getitem__(self, i):
+        return int(i)
+
+    def __len__(self):
+        return self.n
+
+
+class _DeviceEpoch:
+    """one pass of a DeviceLoader: `batches` = [(dialogue indices of this rank, S, offset into the epoch buffers)], `total` =
+    the epoch's (step, dialogue) cells; iterating yields the engine batches"""
+
+    def __init__(self, loader, index_batches):
+        self.corpus = loader.corpus
+        L = self.corpus.lengths
+        self.batches, self.total = [], 0
+        for full in index_batches:
+            S = max(L[i] for i in full)                    # the FULL batch pads to its longest dialogue, whichever rank holds it
+            if loader.world > 1:
+                assert len(full) % loader.world == 0, "global batch %d not divisible by world %d" % (len(full), loader.world)
+                n = len(full) // loader.world
+                full = full[loader.rank * n:(loader.rank + 1) * n]
+            self.batches.append((full, S, self.total))
+            self.total += S * len(full)
+
+    def __len__(self):
+        return len(self.batches)
+
+    def __iter__(self):
+        c = self.corpus
+        if not self.batches:
+            return
+        if c.device.type != "cuda":
+            from ._lib import GanffnError
+            raise GanffnError("DeviceLoader gathers batches on an MI355X (HIP) device only; the corpus is on %s. There is no CPU "
+                              "fallback." % c.device)
+        flat = torch.tensor([i for b, _, _ in self.batches for i in b], dtype=torch.int32).to(c.device)      # one copy per epoch
+        at = 0
+        for idx, S, _ in self.batches:
+            batch = c.gather(flat[at:at + len(idx)], S)
+            at += len(idx)
+            batch["vids"] = [c.keys[i] for i in idx]
+            yield batch
+
+
+class DeviceLoader:
+    """Re-iterable counterpart of DataLoader(dataset, sampler=sampler, batch_size=batch_size, collate_fn=dataset.collate_fn) +
+    to_batch / to_meld_batch over a DeviceCorpus: yields the dicts the engines take (features, qmask, umask, label, vids), each
+    built by one gather launch from the packed corpus — ordinary tensors allocated per batch on the current stream.
+    The index stream is a DataLoader's own, over an index-only dataset with the same sampler and batch size: the same draws
+    from the global RNG in the same order as the host loader's.  The epoch's index lists are materialised when iteration
+    starts (`epoch()`), which fixes every batch's S and its offset into an epoch-sized result buffer beforehand.
+    world > 1: only this rank's slice of every index batch is gathered — what shard_batch(full batch, rank, world) holds."""
+
+    def __init__(self, corpus, sampler=None, batch_size=32, rank=0, world=1):
+        from torch.utils.data import DataLoader
+        assert 0 <= rank < world
+        self.corpus, self.sampler, self.batch_size, self.rank, self.world = corpus, sampler, batch_size, rank, world
+        self._index_loader = DataLoader(_Indices(len(corpus)), sampler=sampler, batch_size=batch_size, collate_fn=list)
+
+    def index_batches(self):
+        """the index lists of one epoch (draws from the global RNG exactly what one pass over the host loader draws)"""
+        return [list(b) for b in self._index_loader]
+
+    def epoch(self):
+        return _DeviceEpoch(self, self.index_batches())
+
+    def __iter__(self):
+        return iter(self.epoch())
+
+    def __len__(self):
+        return len(self._index_loader)
+
+
+def get_device_loaders(trainset, testset, batch_size=32, valid=0.1, device="cuda", rank=0, world=1):
+    """(train, valid, test) DeviceLoaders with the samplers of get_IEMOCAP_loaders / get_MELD_loaders"""
+    ts, vs = get_train_valid_sampler(trainset, valid)
+    train_c, test_c = DeviceCorpus(trainset, device), DeviceCorpus(testset, device)
+    return (DeviceLoader(train_c, ts, batch_size, rank, world), DeviceLoader(train_c, vs, batch_size, rank, world),
+            DeviceLoader(test_c, None, batch_size, rank, world))

@@ -850,19 +850,27 @@ def train_GAN(gens, discs, batches, epochs=1, lr=1e-4, b1=0.5, b2=0.6, process_g
     """Counterpart of train_GAN (train_IEMOCAP.py:255-393) over an iterable of batches per epoch.
     Returns rows of the GAN_loss table (columns train_IEMOCAP.py:308-316): last batch of each epoch.
     reserve_S: size the step buffers once for dialogues up to this length (PositionalEncoding allows 110), so that
-    batches of varying length never re-allocate."""
+    batches of varying length never re-allocate.
+    The losses are read on the host per batch only when `log` wants them; otherwise once per epoch (the last batch's)."""
     eng = GanEngine(gens, discs, lr, b1, b2, process_group, use_graph=use_graph, n_streams=n_streams)
     rows = []
     for epoch in range(epochs):
-        last = None
+        last = kept = None
         for batch in batches:
             if reserve_S and eng._shape is None:
                 S0, B0 = batch["text"].shape[:2]
                 eng.reserve(max(reserve_S, S0), B0)
             eng.iteration(batch)
-            last = eng.loss_dict()
             if log:
+                last = eng.loss_dict()
                 log(epoch, last)
+            else:
+                # nobody reads this batch's losses on the host: keep a device-side copy (the next iteration overwrites
+                # eng.losses) and read the last one once, after the epoch — the host runs ahead of the GPU meanwhile
+                eng.synchronize()
+                kept = eng.losses.clone()
+        if kept is not None:
+            last = {"%s_%s_loss" % (who, kind): x for (kind, who, _), x in zip(eng.schedule, kept.tolist())}
         if last is not None:
             rows.append(dict(epoch=epoch, **{c: last[c] for c in LOSS_COLUMNS}))
     return rows

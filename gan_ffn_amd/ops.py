@@ -853,3 +853,54 @@ def lstm_forward(x, lstm, training):
         if l + 1 < lstm.num_layers and lstm.dropout > 0.0:
             h = DropoutFn.apply(h, float(lstm.dropout), training, SITE_LSTM + l)
     return h
+
+
+# ----------------------------------------------------------------------------------------------
+# the epoch loop with the corpus on the device (csrc/batch.hip; data.DeviceLoader, artifacts.train_or_eval_model)
+# ----------------------------------------------------------------------------------------------
+def batch_gather_raw(cols, labels_src, row0, n_rows, idx, umask, label, S, B, n_dialogues):
+    """cols: [(src [n_rows x width], dst [S x B x width], width)], at most _lib.BATCH_MAX_COLS; idx int32 [B] on the device.
+    One launch writes every dst, umask (B, S) and label (B, S)."""
+    _need_gpu(labels_src, row0, idx, umask, label, *[t for c in cols for t in c[:2]])
+    arr = (_lib.BatchCol * max(1, len(cols)))()
+    for a, (src, dst, width) in zip(arr, cols):
+        a.src, a.dst, a.width = src.data_ptr(), dst.data_ptr(), int(width)
+    _lib.call("ganffn_batch_gather", C.cast(arr, C.c_void_p), len(cols), _ptr(labels_src), _ptr(row0), C.c_int64(n_rows), _ptr(idx),
+              _ptr(umask), _ptr(label), S, B, n_dialogues, _stream())
+
+
+class EpochRecord:
+    """An epoch's results on the device — predictions, labels and masks of `capacity` (step, dialogue) cells and the loss and
+    real-utterance count of `n_steps` steps — written by one ganffn_epoch_record launch per step and read once by `host()`."""
+
+    def __init__(self, capacity, n_steps, device):
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise GanffnError("EpochRecord keeps an epoch's results on an MI355X (HIP) device; got %s. There is no CPU fallback." % dev)
+        self.capacity, self.n_steps = int(capacity), int(n_steps)
+        n, k = max(1, self.capacity), max(1, self.n_steps)
+        self.preds = torch.empty(n, dtype=torch.int64, device=dev)
+        self.labels = torch.empty(n, dtype=torch.int64, device=dev)
+        self.masks = torch.empty(n, dtype=torch.float32, device=dev)
+        self.loss = torch.empty(k, dtype=torch.float32, device=dev)
+        self.count = torch.empty(k, dtype=torch.float32, device=dev)
+
+    def record(self, step, offset, log_prob, label, umask, loss):
+        """log_prob (S, B, C), label (B, S) int64, umask (B, S) float32, loss: the step's scalar — as the step runners return them"""
+        _need_gpu(log_prob, label, umask, loss)
+        S, B, Cn = log_prob.shape
+        if (log_prob.dtype != torch.float32 or umask.dtype != torch.float32 or label.dtype != torch.int64 or loss.dtype != torch.float32
+                or not (log_prob.is_contiguous() and label.is_contiguous() and umask.is_contiguous())
+                or label.numel() != S * B or umask.numel() != S * B or loss.numel() < 1):
+            raise GanffnError("EpochRecord.record: contiguous float32 log_prob (S, B, C), float32 umask (B, S), int64 label (B, S) and "
+                              "a float32 loss; got %s %s, %s %s, %s %s, %s" % (tuple(log_prob.shape), log_prob.dtype, tuple(umask.shape),
+                                                                             umask.dtype, tuple(label.shape), label.dtype, loss.dtype))
+        _lib.call("ganffn_epoch_record", _ptr(log_prob), _ptr(label), _ptr(umask), _ptr(loss), S, B, Cn, _ptr(self.preds),
+                  _ptr(self.labels), _ptr(self.masks), C.c_int64(offset), C.c_int64(self.capacity), _ptr(self.loss), _ptr(self.count),
+                  int(step), self.n_steps, _stream())
+
+    def host(self):
+        """-> numpy (preds, labels, masks, loss, count): one synchronise, one copy each"""
+        torch.cuda.current_stream().synchronize()
+        return tuple(t.cpu().numpy() for t in (self.preds[:self.capacity], self.labels[:self.capacity], self.masks[:self.capacity],
+                                               self.loss[:self.n_steps], self.count[:self.n_steps]))

@@ -630,6 +630,35 @@ int ganffn_ffn_k100_hook(int which, const float* a, const float* w, const float*
  * the backward pass that consumes its saved block. */
 int ganffn_debug_set_ffn_mode(int bits);
 
+/* ---- the epoch loop with the corpus resident on the device (csrc/batch.hip) ---------------------------------------------------
+ * The packed corpus of one split: per feature column (and the speaker one-hots) one fp32 matrix [n_rows x width], the
+ * dialogues back to back; labels_src [n_rows] int64; row0 [n_dialogues + 1] int64, dialogue d owning rows row0[d] .. row0[d+1]-1.
+ *
+ * ganffn_batch_gather: ONE launch builds the padded batch of the dialogues idx[0 .. B-1] (int32, on the device), what
+ *   dataloader.py:55-58's pad_sequence collate builds on the host: every column k seq-first cols[k].dst [S x B x width],
+ *   umask [B x S] fp32 (1 on real utterances), label [B x S] int64.  Every output element is written: steps s >= the dialogue's
+ *   length are zeros.  A dialogue longer than S gives its first S rows; an index outside [0, n_dialogues), or a row range of
+ *   row0 outside [0, n_rows], is an empty dialogue — nothing outside the operands is read or written, whatever idx holds.
+ *   `cols` is a HOST array of n_cols (1 .. GANFFN_BATCH_MAX_COLS) descriptors, copied into the launch; a column whose width is a
+ *   multiple of 4 moves 16 bytes per lane and needs 16-byte aligned src and dst, any other width moves single floats.
+ *   1 <= S <= 4096, 1 <= B <= GANFFN_MAX_DIALOGUES.
+ * ganffn_epoch_record: ONE launch per step appends the step's results to the epoch buffers at `offset` (elements; offset +
+ *   B S <= capacity): preds_out = argmax over the C (<= 16) classes of log_prob [S x B x C] in the batch-major flattening
+ *   i = b S + s of train_IEMOCAP.py:154,158 (ties: the lowest class), labels_out / masks_out = label / umask [B x S] as they are;
+ *   and loss_out[step] = loss[0], count_out[step] = the sum of umask (exact in any order: zeros and ones below 2^24; added in a
+ *   fixed order, no atomics), 0 <= step < n_steps.  The host reads the five buffers once per epoch. */
+#define GANFFN_BATCH_MAX_COLS 4
+typedef struct ganffn_batch_col {
+    const float* src;    /* [n_rows x width] */
+    float* dst;          /* [S x B x width] */
+    int32_t width;
+} ganffn_batch_col;
+int ganffn_batch_gather(const ganffn_batch_col* cols, int n_cols, const int64_t* labels_src, const int64_t* row0, int64_t n_rows,
+                        const int32_t* idx, float* umask, int64_t* label, int S, int B, int n_dialogues, void* stream);
+int ganffn_epoch_record(const float* log_prob, const int64_t* label, const float* umask, const float* loss, int S, int B, int C,
+                        int64_t* preds_out, int64_t* labels_out, float* masks_out, int64_t offset, int64_t capacity,
+                        float* loss_out, float* count_out, int step, int n_steps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
