@@ -84,6 +84,63 @@ class NetState:
         return bucket_ranges(self.enc_floats, self.obj_floats, self.total, self.layer_floats, self.L, n_buckets)
 
 
+class _ParamSlab:
+    """Module parameters that belong to no generator (a classifier head, an LSTM) packed into one slab: every tensor starts
+    on a multiple of 4 floats, the parameters become views of the slab, and gradient, Adam moments and step count sit
+    beside it — what NetState is for a generator."""
+
+    def __init__(self, params, device):
+        self.params = list(params)
+        self.offs, total = [], 0
+        for p_ in self.params:
+            self.offs.append(total)
+            total += (p_.numel() + 3) & ~3
+        self.total = total
+        self.slab = torch.zeros(total, device=device)
+        with torch.no_grad():
+            for i, p_ in enumerate(self.params):
+                self.view(i).copy_(p_.detach().reshape(-1))
+                p_.data = self.view(i).view_as(p_)
+        self.grad = torch.zeros_like(self.slab)
+        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.slab), torch.zeros_like(self.slab)
+        self.step = torch.zeros(1, dtype=torch.int32, device=device)
+
+    def view(self, i, grad=False):
+        o, n = self.offs[i], self.params[i].numel()
+        return (self.grad if grad else self.slab)[o:o + n]
+
+    def in_place(self):
+        """every parameter is still the view at its offset (a .to() / flatten_parameters since then gave it new storage, and
+        the engine would silently stop following)"""
+        base = self.slab.data_ptr()
+        return all(p_.data_ptr() == base + 4 * o for p_, o in zip(self.params, self.offs))
+
+    def all_reduce(self, pg, wait=True):
+        """sum the gradient slab over the ranks of pg (None: nothing to do): in-line on the current stream (dp_mode()), or
+        through a GradReducer — wait=False returns it unfinished, for the caller to finish() after more work is enqueued"""
+        if pg is None:
+            return None
+        if dp_mode() == "inline":
+            import torch.distributed as dist
+            dist.all_reduce(self.grad, op=dist.ReduceOp.SUM, group=pg, async_op=False)
+            return None
+        red = GradReducer(pg)
+        red.reduce_async(self.grad)
+        if not wait:
+            return red
+        red.finish()
+        return None
+
+    def adam(self, lr, wd, world):
+        ops.adam_step_raw(self.slab, self.grad, self.exp_avg, self.exp_avg_sq, self.step, self.total, lr, 0.9, 0.999, 1e-8,
+                          wd, 1.0 / world)
+
+
+def predictions(log_prob):
+    """argmax over classes in the reference's batch-major flattening (train_IEMOCAP.py:154,158; train_MELD.py:72,76)"""
+    return log_prob.transpose(0, 1).reshape(-1, log_prob.shape[2]).argmax(1)
+
+
 def dp_mode():
     """how gradients cross the ranks (GANFFN_DP_MODE):
     "inline" (default, round 4): ONE all-reduce of the network's whole gradient slab per sub-step, issued as a synchronous
@@ -238,8 +295,9 @@ def _side_streams(dev, prios, tuner=None, work=1):
 
 
 class _Runner:
-    """network-level forward / backward / Adam on preallocated buffers — shared by the GAN step runner and the
-    phase-2 (classifier) step runner"""
+    """what every step runner shares: the device, its RNG, the process group, and the check that no network re-packed its
+    slab.  (The network-level forward / backward / Adam on preallocated buffers live in GanEngine, which the classifier step
+    runners over generators derive from.)"""
     n_streams = 1
     early_gen = False
     _cur_stream = None
@@ -900,18 +958,9 @@ class Phase2Engine(GanEngine):
         dev = self.dev
         # fc (100 -> n_classes) parameters as one small slab [weight | bias], 16-byte aligned pieces
         self.fc_w, self.fc_b = ffn_module.fc.weight, ffn_module.fc.bias
-        nw = self.fc_w.numel()
-        self.fc_off_b = (nw + 3) & ~3
-        self.fc_total = self.fc_off_b + ((self.fc_b.numel() + 3) & ~3)
-        self.fc_slab = torch.zeros(self.fc_total, device=dev)
-        with torch.no_grad():
-            self.fc_slab[:nw].copy_(self.fc_w.detach().reshape(-1))
-            self.fc_slab[self.fc_off_b:self.fc_off_b + self.fc_b.numel()].copy_(self.fc_b.detach())
-            self.fc_w.data = self.fc_slab[:nw].view_as(self.fc_w)
-            self.fc_b.data = self.fc_slab[self.fc_off_b:self.fc_off_b + self.fc_b.numel()]
-        self.fc_grad = torch.zeros_like(self.fc_slab)
-        self.fc_m, self.fc_v = torch.zeros_like(self.fc_slab), torch.zeros_like(self.fc_slab)
-        self.fc_step = torch.zeros(1, dtype=torch.int32, device=dev)
+        fc = self.fc = _ParamSlab([self.fc_w, self.fc_b], dev)
+        self.fc_slab, self.fc_grad, self.fc_m, self.fc_v, self.fc_step = fc.slab, fc.grad, fc.exp_avg, fc.exp_avg_sq, fc.step
+        self.fc_off_b, self.fc_total = fc.offs[1], fc.total
         self.lr, self.wd = lr, weight_decay
         self.class_w = torch.tensor(class_weights, device=dev, dtype=torch.float32) if class_weights is not None else None
         self._shape = None
@@ -956,7 +1005,7 @@ class Phase2Engine(GanEngine):
         S, B = batch["text"].shape[:2]
         self._prepare2(S, B)
         self._check_slabs()
-        if self.fc_w.data_ptr() != self.fc_slab.data_ptr():
+        if not self.fc.in_place():
             raise RuntimeError("GAN_FFN.fc was re-allocated after the engine was built: build Phase2Engine after the last .to()")
         T, C_ = S * B, self.n_classes
         self._adds = 0
@@ -979,23 +1028,12 @@ class Phase2Engine(GanEngine):
                 cb, finish = self._make_reducer(net)
                 self._net_bwd(net, self.pass_G[k], self.d_fusion, True, adds[k], True, cb)
                 finish(("G", k))
-            if self.pg is not None:
-                if dp_mode() == "inline":
-                    import torch.distributed as dist
-                    dist.all_reduce(self.fc_grad, op=dist.ReduceOp.SUM, group=self.pg, async_op=False)
-                else:
-                    red = GradReducer(self.pg)
-                    red.reduce_async(self.fc_grad)
-                    red.finish()
-            ops.adam_step_raw(self.fc_slab, self.fc_grad, self.fc_m, self.fc_v, self.fc_step, self.fc_total, self.lr,
-                              0.9, 0.999, 1e-8, self.wd, 1.0 / self.world)
+            self.fc.all_reduce(self.pg)
+            self.fc.adam(self.lr, self.wd, self.world)
         assert self._adds <= 8, self._adds
         return self.loss, self.log_prob
 
-    @staticmethod
-    def predictions(log_prob):
-        """argmax over classes in the reference's batch-major flattening (train_IEMOCAP.py:154,158)"""
-        return log_prob.transpose(0, 1).reshape(-1, log_prob.shape[2]).argmax(1)
+    predictions = staticmethod(predictions)
 
 
 # ================================================================================================
@@ -1024,21 +1062,21 @@ class DrnnEngine(GanEngine):
     stream on this workload — 15.0-16.5 against 14.9-15.0 ms per step: kernels of different streams do not run side by
     side, only the dead time between launches overlaps, and the run-to-run spread grows —
     so one stream is the default), fusion = their sum, BiModel's two
-    DialogueRNN directions through one chain of launches (ganffn_drnn_fwd / _bwd), the matching attention
+    DialogueRNN directions through one chain of launches (ops.drnn_fwd_raw / drnn_bwd_raw), the matching attention
     (ganffn_general2_attention_*), linear + ReLU + dropout, the class head, MaskedNLLLoss with class weights, and Adam
     (lr, L2-coupled weight decay; train_IEMOCAP_DialogueRNN.py:746) on flat slabs: one fused launch per generator and one
     for the whole head.  Data-parallel: the generators' gradients go through the bucketed GradReducer (all-reduce of a
     bucket overlaps the rest of that generator's backward, Adam per bucket), the head's slab is one more bucket.
     Supports every context attention type of the reference script's --attention (general — the trained configuration —,
-    simple, dot, general2, concat), 1 to ops.DRNN_MAX_PARTIES parties (qmask (S, B, P): P = 2 runs the two-party entry points
-    named here, any other P ganffn_drnn_party_fwd / _bwd; the slab does not depend on P), with or without listener state (--active-listener: ganffn_drnn_listener_fwd /
-    _bwd, the 4 l_cell tensors per direction at the end of the head slab).  general runs ganffn_drnn_fwd / _bwd with the slab
-    layout it always had; the other types run ganffn_drnn_att_fwd / _bwd with their attention tensors in the cell block
-    (ops.DRNN_ATT_KEYS: named_parameters order).  The module path (model.GAN_FFN_DialogueRNN.forward under autograd) stays
-    available for what the kernels cannot run (D_g != D_p, D_g > 512, dot with D_m != D_g, concat D_a limits).
-    max_dialogues (32 .. ops.MAX_DIALOGUES; default 32): the most dialogues a step takes.  It is a capacity, not a switch: a
-    batch of at most 32 dialogues runs the entry points named above whatever the capacity is, a larger one ganffn_drnn_batch_fwd /
-    _bwd (the same step with the dialogues in tiles of 32 inside every launch), decided from B alone."""
+    simple (passed on as its own type), dot, general2, concat), 1 to ops.DRNN_MAX_PARTIES parties (qmask (S, B, P); the slab
+    does not depend on P), with or without listener state (--active-listener: the 4 l_cell tensors per direction at the end
+    of the head slab).  Which entry points of the recurrence a step reaches: ops.drnn_family.  general keeps the slab layout
+    it always had; the other types have their attention tensors in the cell block (ops.DRNN_ATT_KEYS: named_parameters
+    order).  The module path (model.GAN_FFN_DialogueRNN.forward under autograd) stays available for what the kernels cannot
+    run (D_g != D_p, D_g > 512, dot with D_m != D_g, concat D_a limits).
+    max_dialogues (32 .. ops.MAX_DIALOGUES; default 32): the most dialogues a step takes.  It is a capacity, not a switch: the
+    family is decided from the batch's own B (more than 32 dialogues: the same step with the dialogues in tiles of 32 inside
+    every launch)."""
 
     def __init__(self, net, lr=1e-4, weight_decay=1e-5, class_weights=CLASS_WEIGHTS, process_group=None, n_buckets=3,
                  n_streams=1, max_dialogues=32):
@@ -1078,19 +1116,9 @@ class DrnnEngine(GanEngine):
             for cell in (cf, cr):
                 sd = dict(cell.named_parameters())
                 plist += [sd[k] for k in ops.DRNN_LISTENER_KEYS]
-        offs, total = [], 0
-        for p_ in plist:
-            offs.append(total)
-            total += (p_.numel() + 3) & ~3
-        self.h_slab = torch.zeros(total, device=dev)
-        with torch.no_grad():
-            for p_, o in zip(plist, offs):
-                self.h_slab[o:o + p_.numel()].copy_(p_.detach().reshape(-1))
-                p_.data = self.h_slab[o:o + p_.numel()].view_as(p_)
-        self._hparams, self._hoffs, self.h_total = plist, offs, total
-        self.h_grad = torch.zeros_like(self.h_slab)
-        self.h_m, self.h_v = torch.zeros_like(self.h_slab), torch.zeros_like(self.h_slab)
-        self.h_step = torch.zeros(1, dtype=torch.int32, device=dev)
+        head = self.head = _ParamSlab(plist, dev)
+        self.h_slab, self.h_grad, self.h_m, self.h_v, self.h_step = head.slab, head.grad, head.exp_avg, head.exp_avg_sq, head.step
+        self._hparams, self._hoffs, self.h_total, self._hp = head.params, head.offs, head.total, head.view
         self.class_w = torch.tensor(class_weights, device=dev, dtype=torch.float32) if class_weights is not None else None
         self.n_streams = max(1, min(3, n_streams))
         if process_group is not None:
@@ -1102,10 +1130,6 @@ class DrnnEngine(GanEngine):
         self._alloc_P = 0
         self._adds = 0
         self._base_add = 0
-
-    def _hp(self, i, grad=False):
-        o, n = self._hoffs[i], self._hparams[i].numel()
-        return (self.h_grad if grad else self.h_slab)[o:o + n]
 
     def reserve(self, S, B):
         self._check_SB(S, B)
@@ -1133,22 +1157,9 @@ class DrnnEngine(GanEngine):
             self.ws3 = {k: torch.empty(p_.n_ws, **f32) for k, p_ in self.pass_G.items()}     # one workspace per generator stream
             cfgc = _lib.DrnnCfg(cS, cB, self.Dm, self.H, self.He, self.p_rec, 1)
             lib = _lib.load()
-            if cB > 32:          # (the same layouts as functions of B; the entry points below refuse more than 32 dialogues)
-                n_saved = int(lib.ganffn_drnn_batch_saved_floats(C.byref(cfgc), C.byref(self.acfg), int(self.listener), cP))
-                n_ws = int(lib.ganffn_drnn_batch_workspace_floats(C.byref(cfgc), C.byref(self.acfg), int(self.listener), cP))
-            elif cP != 2:        # (the recurrence's buffers grow with the party count: sized for the widest batch so far)
-                n_saved = int(lib.ganffn_drnn_party_saved_floats(C.byref(cfgc), C.byref(self.acfg), int(self.listener), cP))
-                n_ws = int(lib.ganffn_drnn_party_workspace_floats(C.byref(cfgc), C.byref(self.acfg), int(self.listener), cP))
-            elif self.att != "general":
-                n_saved = int(lib.ganffn_drnn_att_saved_floats(C.byref(cfgc), C.byref(self.acfg), int(self.listener)))
-                n_ws = int(lib.ganffn_drnn_att_workspace_floats(C.byref(cfgc), C.byref(self.acfg), int(self.listener)))
-            elif self.listener:
-                n_saved = int(lib.ganffn_drnn_listener_saved_floats(C.byref(cfgc)))
-                n_ws = int(lib.ganffn_drnn_listener_workspace_floats(C.byref(cfgc)))
-            else:
-                n_saved, n_ws = int(lib.ganffn_drnn_saved_floats(C.byref(cfgc))), int(lib.ganffn_drnn_workspace_floats(C.byref(cfgc)))
-            if n_saved < 0 or n_ws < 0:
-                _lib.check(-1, "ganffn_drnn_*_floats")
+            # (the capacity's family: the layouts are the same functions of B in every family, and the recurrence's buffers grow
+            # with the party count — sized for the widest batch so far)
+            n_saved, n_ws = ops.drnn_floats(cfgc, self.acfg, self.listener, cP)
             T, D2, Cn = cS * cB, 2 * self.He, self.n_classes
             z = lambda n: torch.empty(n, **f32)
             self._f = dict(fusion=z(T * self.Dm), rev_U=z(T * self.Dm), e_f=z(T * self.He), e_b=z(T * self.He),
@@ -1234,7 +1245,7 @@ class DrnnEngine(GanEngine):
     def _step(self, batch, train=True):
         S, B = batch["text"].shape[:2]
         self._check_slabs()
-        if self._hparams[0].data_ptr() != self.h_slab.data_ptr():
+        if not self.head.in_place():
             raise RuntimeError("the DialogueRNN head was re-allocated after the engine was built: build DrnnEngine after the last .to()")
         P, st_ = ops._ptr, ops._stream
         T, Dm, He, D2, Cn = S * B, self.Dm, self.He, 2 * self.He, self.n_classes
@@ -1293,23 +1304,10 @@ class DrnnEngine(GanEngine):
         arr = lambda ts: (C.c_void_p * 2)(*[t.data_ptr() for t in ts])
         U_, spk_, mval_ = arr([f["fusion"], f["rev_U"]]), arr([spk_f, spk_b]), arr([mval_f, mval_b])
         e_, al_, sv_, ws_ = arr([f["e_f"], f["e_b"]]), arr([f["alpha_f"], f["alpha_b"]]), arr([f["saved_f"], f["saved_b"]]), arr([f["ws_f"], f["ws_b"]])
-        Pp = self._drnn_ptrs(False)
+        Pp, APp = self._drnn_ptrs(False), self._drnn_att_ptrs(False)
+        LPp = self._drnn_listener_ptrs(False) if self.listener else None
         parties = self._shape[2]
-        wide = B > 32            # more than one tile of dialogues: ganffn_drnn_batch_* (the _party_ argument lists)
-        if wide or parties != 2:
-            LPp = self._drnn_listener_ptrs(False) if self.listener else None
-            _lib.call("ganffn_drnn_batch_fwd" if wide else "ganffn_drnn_party_fwd", C.byref(cfg), C.byref(self.acfg), parties, 2, U_, spk_, mval_, Pp, LPp,
-                      self._drnn_att_ptrs(False), e_, al_, sv_, ws_, P(rng), C.c_uint64(a_rec), st)
-        elif self.att != "general":
-            LPp = self._drnn_listener_ptrs(False) if self.listener else None
-            _lib.call("ganffn_drnn_att_fwd", C.byref(cfg), C.byref(self.acfg), 2, U_, spk_, mval_, Pp, LPp, self._drnn_att_ptrs(False),
-                      e_, al_, sv_, ws_, P(rng), C.c_uint64(a_rec), st)
-        elif self.listener:
-            LPp = self._drnn_listener_ptrs(False)
-            _lib.call("ganffn_drnn_listener_fwd", C.byref(cfg), 2, U_, spk_, mval_, Pp, LPp, e_, al_, sv_, ws_, P(rng),
-                      C.c_uint64(a_rec), st)
-        else:
-            _lib.call("ganffn_drnn_fwd", C.byref(cfg), 2, U_, spk_, mval_, Pp, e_, al_, sv_, ws_, P(rng), C.c_uint64(a_rec), st)
+        ops.drnn_fwd_raw(cfg, self.acfg, parties, 2, U_, spk_, mval_, Pp, LPp, APp, e_, al_, sv_, ws_, P(rng), a_rec)
         # ---- head: emotions -> matching attention -> linear/relu/dropout -> classes -> loss
         tr = 1 if train else 0
         _lib.call("ganffn_drnn_join_fwd", P(f["e_f"]), P(f["e_b"]), P(lens), P(f["emotions"]), S, B, He, C.c_float(self.p_join),
@@ -1342,33 +1340,16 @@ class DrnnEngine(GanEngine):
         # ---- the recurrence backward (weight gradients accumulate into the zeroed head slab)
         Gp = self._drnn_ptrs(True)
         de_, dU_ = arr([f["d_e_f"], f["d_e_b"]]), arr([f["dU_f"], f["dU_b"]])
-        if wide or parties != 2:
-            _lib.call("ganffn_drnn_batch_bwd" if wide else "ganffn_drnn_party_bwd", C.byref(cfg), C.byref(self.acfg), parties, 2, de_, U_, spk_, mval_, Pp, LPp,
-                      self._drnn_att_ptrs(False), Gp, self._drnn_listener_ptrs(True) if self.listener else None,
-                      self._drnn_att_ptrs(True), dU_, al_, sv_, ws_, P(rng), C.c_uint64(a_rec), st)
-        elif self.att != "general":
-            _lib.call("ganffn_drnn_att_bwd", C.byref(cfg), C.byref(self.acfg), 2, de_, U_, spk_, mval_, Pp, LPp,
-                      self._drnn_att_ptrs(False), Gp, self._drnn_listener_ptrs(True) if self.listener else None,
-                      self._drnn_att_ptrs(True), dU_, al_, sv_, ws_, P(rng), C.c_uint64(a_rec), st)
-        elif self.listener:
-            _lib.call("ganffn_drnn_listener_bwd", C.byref(cfg), 2, de_, U_, spk_, mval_, Pp, LPp, Gp, self._drnn_listener_ptrs(True),
-                      dU_, al_, sv_, ws_, P(rng), C.c_uint64(a_rec), st)
-        else:
-            _lib.call("ganffn_drnn_bwd", C.byref(cfg), 2, de_, U_, spk_, mval_, Pp, Gp, dU_, al_, sv_, ws_, P(rng), C.c_uint64(a_rec), st)
+        ops.drnn_bwd_raw(cfg, self.acfg, parties, 2, de_, U_, spk_, mval_, Pp, LPp, APp, Gp,
+                         self._drnn_listener_ptrs(True) if self.listener else None, self._drnn_att_ptrs(True), dU_, al_, sv_, ws_,
+                         P(rng), a_rec)
         # d fusion = dU_f + reverse(dU_b)
         _lib.call("ganffn_seq_reverse", P(f["dU_b"]), P(lens), P(f["dU_f"]), S, B, Dm, 1, st)
         d_fusion = f["dU_f"][:T * Dm].view(S, B, Dm)
         # ---- head optimizer step (its all-reduce, when data-parallel, runs beside the generators' backward)
-        red_h = None
-        if self.pg is not None:
-            if dp_mode() == "inline":
-                # in-line on this stream (a communicator never carries two collectives at once: the generators' all-reduces
-                # below use the same one)
-                import torch.distributed as dist
-                dist.all_reduce(self.h_grad, op=dist.ReduceOp.SUM, group=self.pg, async_op=False)
-            else:
-                red_h = GradReducer(self.pg)
-                red_h.reduce_async(self.h_grad)
+        # (in-line mode: on this stream — a communicator never carries two collectives at once, and the generators' all-reduces
+        # below use the same one; bucket mode: finished after the generators' backward)
+        red_h = self.head.all_reduce(self.pg, wait=False)
         # ---- three generator backward passes + Adam, concurrently
         if self.streams is not None:
             fork = torch.cuda.Event()
@@ -1390,8 +1371,7 @@ class DrnnEngine(GanEngine):
                 bwd()
         if red_h is not None:
             red_h.finish()
-        ops.adam_step_raw(self.h_slab, self.h_grad, self.h_m, self.h_v, self.h_step, self.h_total, self.lr, 0.9, 0.999, 1e-8,
-                          self.wd, 1.0 / self.world)
+        self.head.adam(self.lr, self.wd, self.world)
         if self.streams is not None:
             for s_ in self.streams:
                 if s_.cuda_stream != cur.cuda_stream:
@@ -1399,9 +1379,7 @@ class DrnnEngine(GanEngine):
         assert self._adds <= 6, self._adds
         return self.loss, log_prob
 
-    @staticmethod
-    def predictions(log_prob):
-        return log_prob.transpose(0, 1).reshape(-1, log_prob.shape[2]).argmax(1)
+    predictions = staticmethod(predictions)
 
 
 # ================================================================================================
@@ -1446,19 +1424,10 @@ class MeldEngine(_Runner):
         self._init_common(plist[0].device, process_group, 1)
         dev = self.dev
         assert dev.type == "cuda", "MeldEngine needs the module on the GPU"
-        offs, total = [], 0
-        for p_ in plist:
-            offs.append(total)
-            total += (p_.numel() + 3) & ~3
-        self.slab = torch.zeros(total, device=dev)
-        with torch.no_grad():
-            for p_, o in zip(plist, offs):
-                self.slab[o:o + p_.numel()].copy_(p_.detach().reshape(-1))
-                p_.data = self.slab[o:o + p_.numel()].view_as(p_)
-        self._params, self._offs, self.total = plist, offs, total
-        self.grad = torch.zeros_like(self.slab)
-        self.exp_avg, self.exp_avg_sq = torch.zeros_like(self.slab), torch.zeros_like(self.slab)
-        self.step_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        ps = self.params = _ParamSlab(plist, dev)
+        self.slab, self.grad, self.exp_avg, self.exp_avg_sq, self.step_count = ps.slab, ps.grad, ps.exp_avg, ps.exp_avg_sq, ps.step
+        self._params, self._offs, self.total, self._p = ps.params, ps.offs, ps.total, ps.view
+        offs = ps.offs
         self.lr, self.wd = lr, weight_decay
         self.class_w = torch.tensor(class_weights, device=dev, dtype=torch.float32) if class_weights is not None else None
         # the stack entry points' pointer arrays [L][2] (the slabs never move: built once)
@@ -1472,10 +1441,6 @@ class MeldEngine(_Runner):
         self._shape = None
         self._cap_S = self._cap_B = 0
         self._base_add = 0
-
-    def _p(self, i, grad=False):
-        o, n = self._offs[i], self._params[i].numel()
-        return (self.grad if grad else self.slab)[o:o + n]
 
     def reserve(self, S, B):
         """size every step buffer once for batches of up to (S, B): train / valid / test loaders then never re-allocate"""
@@ -1525,10 +1490,9 @@ class MeldEngine(_Runner):
             raise ValueError("MeldEngine: text must be a contiguous float32 (S, B, %d) tensor on the GPU (data.to_meld_batch makes "
                              "it so); got %s %s" % (self.Dm, tuple(text.shape), text.dtype))
         self._prepare(S, B)
-        for p_, o in zip(self._params, self._offs):
-            if p_.data_ptr() != self.slab.data_ptr() + 4 * o:
-                raise RuntimeError("a MELDLSTMModel parameter was re-allocated after the engine was built (.to() / "
-                                   "flatten_parameters): build MeldEngine after the last .to()")
+        if not self.params.in_place():
+            raise RuntimeError("a MELDLSTMModel parameter was re-allocated after the engine was built (.to() / "
+                               "flatten_parameters): build MeldEngine after the last .to()")
         P, st = ops._ptr, ops._stream()
         T, D2, Cn = S * B, self.D2, self.n_classes
         f = self._f
@@ -1564,19 +1528,8 @@ class MeldEngine(_Runner):
         g_ih, g_hh, gb_ih, gb_hh = self._g
         _lib.call(fam + "bwd", C.byref(cfg), P(f["d_em"]), P(text), P(f["emotions"]), w_ih, w_hh, None, g_ih, g_hh, gb_ih,
                   gb_hh, P(f["saved"]), P(f["ws"]), P(rng), C.c_uint64(base), st)
-        if self.pg is not None:
-            if dp_mode() == "inline":
-                import torch.distributed as dist
-                dist.all_reduce(self.grad, op=dist.ReduceOp.SUM, group=self.pg, async_op=False)
-            else:
-                red = GradReducer(self.pg)
-                red.reduce_async(self.grad)
-                red.finish()
-        ops.adam_step_raw(self.slab, self.grad, self.exp_avg, self.exp_avg_sq, self.step_count, self.total, self.lr, 0.9, 0.999,
-                          1e-8, self.wd, 1.0 / self.world)
+        self.params.all_reduce(self.pg)
+        self.params.adam(self.lr, self.wd, self.world)
         return self.loss, log_prob
 
-    @staticmethod
-    def predictions(log_prob):
-        """argmax over classes in the reference's batch-major flattening (train_MELD.py:72,76)"""
-        return log_prob.transpose(0, 1).reshape(-1, log_prob.shape[2]).argmax(1)
+    predictions = staticmethod(predictions)

@@ -495,20 +495,85 @@ def _att_ptrs(att, tensors):
     return s
 
 
+def _ptr_structs(cls, rows, fill=_drnn_ptrs):
+    """one ctypes array of `cls` pointer structs, one per direction (None when there are no rows)"""
+    return (cls * len(rows))(*[fill(r, cls) for r in rows]) if rows is not None else None
+
+
+def drnn_family(B, parties, att_type, listener):
+    """THE rule for which entry-point family of the recurrence a call takes (every family is a thin wrapper over the one
+    drnn_fwd / drnn_bwd driver in csrc/dialogue_rnn.hip):
+      "batch"     B > 32 dialogues (up to MAX_DIALOGUES), whatever the rest      ganffn_drnn_batch_*
+      "party"     otherwise a party axis other than 2 wide                       ganffn_drnn_party_*
+      "att"       otherwise a context attention type other than general          ganffn_drnn_att_*
+      "listener"  otherwise listener state                                       ganffn_drnn_listener_*
+      ""          otherwise                                                      ganffn_drnn_*
+    att_type: the _lib.DrnnAtt.type value or its name, as the caller has it.  The rule only sees what it is given: the module
+    path runs simple attention as general (_drnn_cell_args), DrnnEngine passes simple as its own type."""
+    if B > 32:
+        return "batch"
+    if parties != 2:
+        return "party"
+    if att_type not in ("general", _lib.DRNN_ATT_TYPES["general"]):
+        return "att"
+    return "listener" if listener else ""
+
+
+def _drnn_entry(family, what):
+    return "ganffn_drnn_%s%s" % (family + "_" if family else "", what)
+
+
+def drnn_floats(cfg, acfg, listener, parties):
+    """(n_saved, n_ws) floats per direction, from the size functions of the family cfg.B and the rest select (drnn_family)"""
+    lib = _lib.load()
+    fam = drnn_family(cfg.B, parties, acfg.type, listener)
+    args = {"": (cfg,), "listener": (cfg,), "att": (cfg, acfg, int(listener))}.get(fam, (cfg, acfg, int(listener), parties))
+    n_saved, n_ws = (int(getattr(lib, _drnn_entry(fam, w))(*args)) for w in ("saved_floats", "workspace_floats"))
+    if n_saved < 0 or n_ws < 0:
+        _lib.check(-1, "ganffn_drnn_*_floats")
+    return n_saved, n_ws
+
+
+# what each family's argument list leaves out of the party family's (the full) one
+_DRNN_OMIT = {"": ("acfg", "parties", "LP", "AP", "LG", "AG"), "listener": ("acfg", "parties", "AP", "AG"), "att": ("parties",),
+              "party": (), "batch": ()}
+
+
+def _drnn_call(what, named, rng, add):
+    a = dict(named)
+    fam = drnn_family(a["cfg"].B, a["parties"], a["acfg"].type, a["LP"] is not None)
+    _lib.call(_drnn_entry(fam, what), *[v for k, v in named if k not in _DRNN_OMIT[fam]], rng, C.c_uint64(add), _stream())
+
+
+def drnn_fwd_raw(cfg, acfg, parties, ndir, U, spk, mval, P, LP, AP, e, alpha, saved, ws, rng, add):
+    """the recurrence forward of ndir directions: ONE call of ganffn_drnn_<family>_fwd (drnn_family; listener = LP is given)
+    with that family's argument list — the full one here, in this order, less what the family does not take.  cfg / acfg:
+    _lib.DrnnCfg / _lib.DrnnAtt; P / LP / AP: arrays of ndir pointer structs (AP always given: general's is the 13th cell
+    tensor); the rest: arrays of ndir device pointers, rng the Philox state's pointer, add the offset."""
+    _drnn_call("fwd", [("cfg", cfg), ("acfg", acfg), ("parties", parties), ("ndir", ndir), ("U", U), ("spk", spk), ("mval", mval),
+                       ("P", P), ("LP", LP), ("AP", AP), ("e", e), ("alpha", alpha), ("saved", saved), ("ws", ws)], rng, add)
+
+
+def drnn_bwd_raw(cfg, acfg, parties, ndir, d_e, U, spk, mval, P, LP, AP, G, LG, AG, dU, alpha, saved, ws, rng, add):
+    """drnn_fwd_raw's backward: ONE call of ganffn_drnn_<family>_bwd; G / LG / AG: the gradients' pointer structs (weight
+    gradients accumulate), d_e / dU: arrays of ndir device pointers."""
+    _drnn_call("bwd", [("cfg", cfg), ("acfg", acfg), ("parties", parties), ("ndir", ndir), ("d_e", d_e), ("U", U), ("spk", spk),
+                       ("mval", mval), ("P", P), ("LP", LP), ("AP", AP), ("G", G), ("LG", LG), ("AG", AG), ("dU", dU),
+                       ("alpha", alpha), ("saved", saved), ("ws", ws)], rng, add)
+
+
 class DialogueRNNFn(torch.autograd.Function):
-    """ndir (1 or 2) DialogueRNNs through one chain of launches.
+    """ndir (1 or 2) DialogueRNNs through one chain of launches (drnn_fwd_raw / drnn_bwd_raw; which entry points they reach:
+    drnn_family).
     apply(cfg_dict, U_0, spk_0, mval_0, *13 params_0 [, U_1, spk_1, mval_1, *13 params_1]) ->
     (e_0 (S,B,D_e), alpha_0 (B,S,S) [, e_1, alpha_1]).  alpha is an inspection output (non-differentiable).
-    cfg_dict["listener"] true: listener_state = True (ganffn_drnn_listener_*); every direction then takes 17 parameter tensors,
-    the 13 above followed by l_cell's weight_ih, weight_hh, bias_ih, bias_hh (DRNN_LISTENER_KEYS).
+    cfg_dict["listener"] true: listener_state = True; every direction then takes 17 parameter tensors, the 13 above followed
+    by l_cell's weight_ih, weight_hh, bias_ih, bias_hh (DRNN_LISTENER_KEYS).
     cfg_dict["att"] (default "general"): the context attention type.  Other than general, the 13th tensor (general's
-    transform.weight) is replaced by the type's own DRNN_ATT_KEYS tensors (none for dot, two for general2 and concat) and
-    the call goes through ganffn_drnn_att_* (cfg_dict["Da"]: concat's D_a).
-    cfg_dict["parties"] (default 2): the width P of qmask's party axis.  P = 2 makes the calls above; any other P (1 ..
-    DRNN_MAX_PARTIES) goes through ganffn_drnn_party_*, general attention included (its transform.weight as the attention
-    parameter), with the same arguments and gradients.
-    More than 32 dialogues (up to MAX_DIALOGUES; decided from B alone): ganffn_drnn_batch_*, whatever the attention type,
-    listener flag and party count — the _party_ argument lists."""
+    transform.weight) is replaced by the type's own DRNN_ATT_KEYS tensors (none for dot, two for general2 and concat;
+    cfg_dict["Da"]: concat's D_a).
+    cfg_dict["parties"] (default 2): the width P of qmask's party axis, 1 .. DRNN_MAX_PARTIES.
+    At most MAX_DIALOGUES dialogues.  Arguments and gradients are the same whichever family runs."""
 
     @staticmethod
     def forward(ctx, meta, *args):
@@ -534,26 +599,9 @@ class DialogueRNNFn(torch.autograd.Function):
         H, He = prm[0][1].shape[1], prm[0][9].shape[1]
         train = bool(meta["train"]) and meta["p"] > 0.0
         cfg = _lib.DrnnCfg(S, B, Dm, H, He, float(meta["p"]), 1 if train else 0)
-        lib = _lib.load()
         acfg = _lib.DrnnAtt(_lib.DRNN_ATT_TYPES[att], int(meta.get("Da", 0)))
         parties = int(meta.get("parties", 2))
-        batch = B > 32
-        if batch:
-            n_saved = int(lib.ganffn_drnn_batch_saved_floats(C.byref(cfg), C.byref(acfg), int(listener), parties))
-            n_ws = int(lib.ganffn_drnn_batch_workspace_floats(C.byref(cfg), C.byref(acfg), int(listener), parties))
-        elif parties != 2:
-            n_saved = int(lib.ganffn_drnn_party_saved_floats(C.byref(cfg), C.byref(acfg), int(listener), parties))
-            n_ws = int(lib.ganffn_drnn_party_workspace_floats(C.byref(cfg), C.byref(acfg), int(listener), parties))
-        elif aprm is not None:
-            n_saved = int(lib.ganffn_drnn_att_saved_floats(C.byref(cfg), C.byref(acfg), int(listener)))
-            n_ws = int(lib.ganffn_drnn_att_workspace_floats(C.byref(cfg), C.byref(acfg), int(listener)))
-        elif listener:
-            n_saved = int(lib.ganffn_drnn_listener_saved_floats(C.byref(cfg)))
-            n_ws = int(lib.ganffn_drnn_listener_workspace_floats(C.byref(cfg)))
-        else:
-            n_saved, n_ws = int(lib.ganffn_drnn_saved_floats(C.byref(cfg))), int(lib.ganffn_drnn_workspace_floats(C.byref(cfg)))
-        if n_saved < 0 or n_ws < 0:
-            _lib.check(-1, "ganffn_drnn_*_floats")
+        n_saved, n_ws = drnn_floats(cfg, acfg, listener, parties)
         dev = U[0].device
         saved = [torch.empty(n_saved, device=dev) for _ in range(ndir)]
         ws = [torch.empty(n_ws, device=dev) for _ in range(ndir)]
@@ -561,29 +609,13 @@ class DialogueRNNFn(torch.autograd.Function):
         alpha = [torch.empty(B, S, S, device=dev) for _ in range(ndir)]
         rng = DeviceRng.get(dev)
         add = rng.next_add() if train else 0
-        P = (_lib.DrnnPtrs * ndir)(*[_drnn_ptrs(p) for p in prm])
-        if batch or parties != 2:
-            LP = (_lib.DrnnListenerPtrs * ndir)(*[_drnn_ptrs(p, _lib.DrnnListenerPtrs) for p in lprm]) if listener else None
-            AP = (_lib.DrnnAttPtrs * ndir)(*[_att_ptrs(att, a) for a in (aprm or [[p[12]] for p in prm])])
-            _lib.call("ganffn_drnn_batch_fwd" if batch else "ganffn_drnn_party_fwd", C.byref(cfg), C.byref(acfg), parties, ndir, _ptr_array(U), _ptr_array(spk),
-                      _ptr_array(mval), P, LP, AP, _ptr_array(e), _ptr_array(alpha), _ptr_array(saved), _ptr_array(ws),
-                      _ptr(rng.state), C.c_uint64(add), _stream())
-        elif aprm is not None:
-            LP = (_lib.DrnnListenerPtrs * ndir)(*[_drnn_ptrs(p, _lib.DrnnListenerPtrs) for p in lprm]) if listener else None
-            AP = (_lib.DrnnAttPtrs * ndir)(*[_att_ptrs(att, a) for a in aprm])
-            _lib.call("ganffn_drnn_att_fwd", C.byref(cfg), C.byref(acfg), ndir, _ptr_array(U), _ptr_array(spk), _ptr_array(mval), P,
-                      LP, AP, _ptr_array(e), _ptr_array(alpha), _ptr_array(saved), _ptr_array(ws), _ptr(rng.state),
-                      C.c_uint64(add), _stream())
-        elif listener:
-            LP = (_lib.DrnnListenerPtrs * ndir)(*[_drnn_ptrs(p, _lib.DrnnListenerPtrs) for p in lprm])
-            _lib.call("ganffn_drnn_listener_fwd", C.byref(cfg), ndir, _ptr_array(U), _ptr_array(spk), _ptr_array(mval), P, LP,
-                      _ptr_array(e), _ptr_array(alpha), _ptr_array(saved), _ptr_array(ws), _ptr(rng.state), C.c_uint64(add),
-                      _stream())
-        else:
-            _lib.call("ganffn_drnn_fwd", C.byref(cfg), ndir, _ptr_array(U), _ptr_array(spk), _ptr_array(mval), P, _ptr_array(e),
-                      _ptr_array(alpha), _ptr_array(saved), _ptr_array(ws), _ptr(rng.state), C.c_uint64(add), _stream())
+        # (general: transform.weight, the 13th cell tensor, is the attention's own parameter)
+        AP = _ptr_structs(_lib.DrnnAttPtrs, aprm or [[p[12]] for p in prm], lambda a, _: _att_ptrs(att, a))
+        drnn_fwd_raw(cfg, acfg, parties, ndir, _ptr_array(U), _ptr_array(spk), _ptr_array(mval), _ptr_structs(_lib.DrnnPtrs, prm),
+                     _ptr_structs(_lib.DrnnListenerPtrs, lprm), AP, _ptr_array(e), _ptr_array(alpha), _ptr_array(saved),
+                     _ptr_array(ws), _ptr(rng.state), add)
         ctx.cfg, ctx.ndir, ctx.add, ctx.rng_state = cfg, ndir, add, rng.state
-        ctx.att, ctx.acfg, ctx.aprm, ctx.parties, ctx.batch = att, acfg, aprm, parties, batch
+        ctx.att, ctx.acfg, ctx.aprm, ctx.parties = att, acfg, aprm, parties
         ctx.keep = (U, spk, mval, prm, lprm, alpha, saved, ws)
         out = []
         for z in range(ndir):
@@ -598,59 +630,20 @@ class DialogueRNNFn(torch.autograd.Function):
         d_e = [_f32c(douts[2 * z]) if douts[2 * z] is not None else torch.zeros_like(U[z][..., :cfg.He]) for z in range(ndir)]
         dU = [torch.empty_like(U[z]) for z in range(ndir)]
         grads = [[torch.zeros_like(p) if p is not None else None for p in prm[z]] for z in range(ndir)]
-        P = (_lib.DrnnPtrs * ndir)(*[_drnn_ptrs(p) for p in prm])
-        G = (_lib.DrnnPtrs * ndir)(*[_drnn_ptrs(g) for g in grads])
-        if ctx.batch or ctx.parties != 2:
-            general = ctx.aprm is None        # (general: transform.weight and its gradient are the attention's own parameter)
-            aprm = [[p[12]] for p in prm] if general else ctx.aprm
-            agrads = [[g[12]] for g in grads] if general else [[torch.zeros_like(p) for p in aprm[z]] for z in range(ndir)]
-            AP = (_lib.DrnnAttPtrs * ndir)(*[_att_ptrs(ctx.att, a) for a in aprm])
-            AG = (_lib.DrnnAttPtrs * ndir)(*[_att_ptrs(ctx.att, a) for a in agrads])
-            if lprm is not None:
-                lgrads = [[torch.zeros_like(p) for p in lprm[z]] for z in range(ndir)]
-                LP = (_lib.DrnnListenerPtrs * ndir)(*[_drnn_ptrs(p, _lib.DrnnListenerPtrs) for p in lprm])
-                LG = (_lib.DrnnListenerPtrs * ndir)(*[_drnn_ptrs(g, _lib.DrnnListenerPtrs) for g in lgrads])
-            else:
-                lgrads, LP, LG = [[] for _ in range(ndir)], None, None
-            _lib.call("ganffn_drnn_batch_bwd" if ctx.batch else "ganffn_drnn_party_bwd", C.byref(cfg), C.byref(ctx.acfg), ctx.parties, ndir, _ptr_array(d_e), _ptr_array(U),
-                      _ptr_array(spk), _ptr_array(mval), P, LP, AP, G, LG, AG, _ptr_array(dU), _ptr_array(alpha), _ptr_array(saved),
-                      _ptr_array(ws), _ptr(ctx.rng_state), C.c_uint64(ctx.add), _stream())
-            out = [None]
-            for z in range(ndir):
-                out += [dU[z], None, None] + (grads[z] if general else grads[z][:12] + agrads[z]) + lgrads[z]
-            return tuple(out)
-        if ctx.aprm is not None:
-            agrads = [[torch.zeros_like(p) for p in ctx.aprm[z]] for z in range(ndir)]
-            AP = (_lib.DrnnAttPtrs * ndir)(*[_att_ptrs(ctx.att, a) for a in ctx.aprm])
-            AG = (_lib.DrnnAttPtrs * ndir)(*[_att_ptrs(ctx.att, a) for a in agrads])
-            if lprm is not None:
-                lgrads = [[torch.zeros_like(p) for p in lprm[z]] for z in range(ndir)]
-                LP = (_lib.DrnnListenerPtrs * ndir)(*[_drnn_ptrs(p, _lib.DrnnListenerPtrs) for p in lprm])
-                LG = (_lib.DrnnListenerPtrs * ndir)(*[_drnn_ptrs(g, _lib.DrnnListenerPtrs) for g in lgrads])
-            else:
-                lgrads, LP, LG = [[] for _ in range(ndir)], None, None
-            _lib.call("ganffn_drnn_att_bwd", C.byref(cfg), C.byref(ctx.acfg), ndir, _ptr_array(d_e), _ptr_array(U), _ptr_array(spk),
-                      _ptr_array(mval), P, LP, AP, G, LG, AG, _ptr_array(dU), _ptr_array(alpha), _ptr_array(saved), _ptr_array(ws),
-                      _ptr(ctx.rng_state), C.c_uint64(ctx.add), _stream())
-            out = [None]
-            for z in range(ndir):
-                out += [dU[z], None, None] + grads[z][:12] + agrads[z] + lgrads[z]
-            return tuple(out)
-        if lprm is not None:
-            lgrads = [[torch.zeros_like(p) for p in lprm[z]] for z in range(ndir)]
-            LP = (_lib.DrnnListenerPtrs * ndir)(*[_drnn_ptrs(p, _lib.DrnnListenerPtrs) for p in lprm])
-            LG = (_lib.DrnnListenerPtrs * ndir)(*[_drnn_ptrs(g, _lib.DrnnListenerPtrs) for g in lgrads])
-            _lib.call("ganffn_drnn_listener_bwd", C.byref(cfg), ndir, _ptr_array(d_e), _ptr_array(U), _ptr_array(spk),
-                      _ptr_array(mval), P, LP, G, LG, _ptr_array(dU), _ptr_array(alpha), _ptr_array(saved), _ptr_array(ws),
-                      _ptr(ctx.rng_state), C.c_uint64(ctx.add), _stream())
-        else:
-            lgrads = [[] for _ in range(ndir)]
-            _lib.call("ganffn_drnn_bwd", C.byref(cfg), ndir, _ptr_array(d_e), _ptr_array(U), _ptr_array(spk), _ptr_array(mval), P,
-                      G, _ptr_array(dU), _ptr_array(alpha), _ptr_array(saved), _ptr_array(ws), _ptr(ctx.rng_state),
-                      C.c_uint64(ctx.add), _stream())
+        general = ctx.aprm is None        # (general: transform.weight and its gradient are the attention's own parameter)
+        aprm = [[p[12]] for p in prm] if general else ctx.aprm
+        agrads = [[g[12]] for g in grads] if general else [[torch.zeros_like(p) for p in aprm[z]] for z in range(ndir)]
+        lgrads = [[torch.zeros_like(p) for p in lprm[z]] for z in range(ndir)] if lprm is not None else None
+        att_ptrs = lambda a, _: _att_ptrs(ctx.att, a)
+        drnn_bwd_raw(cfg, ctx.acfg, ctx.parties, ndir, _ptr_array(d_e), _ptr_array(U), _ptr_array(spk), _ptr_array(mval),
+                     _ptr_structs(_lib.DrnnPtrs, prm), _ptr_structs(_lib.DrnnListenerPtrs, lprm),
+                     _ptr_structs(_lib.DrnnAttPtrs, aprm, att_ptrs), _ptr_structs(_lib.DrnnPtrs, grads),
+                     _ptr_structs(_lib.DrnnListenerPtrs, lgrads), _ptr_structs(_lib.DrnnAttPtrs, agrads, att_ptrs),
+                     _ptr_array(dU), _ptr_array(alpha), _ptr_array(saved), _ptr_array(ws), _ptr(ctx.rng_state), ctx.add)
         out = [None]
         for z in range(ndir):
-            out += [dU[z], None, None] + grads[z] + lgrads[z]
+            # the 13th slot is general's transform.weight; any other type's own tensors follow the 12 cell gradients
+            out += [dU[z], None, None] + (grads[z] if general else grads[z][:12] + agrads[z]) + (lgrads[z] if lgrads else [])
         return tuple(out)
 
 
@@ -707,7 +700,7 @@ def _drnn_cell_args(cell, U):
     DialogueRNNCell.
     general attention (model.py:160-166): as they are.
     dot / general2 / concat: the 12 cell tensors, then the type's own (DRNN_ATT_KEYS: none / transform weight and bias /
-    transform.weight and vector_prod.weight), then the listener's; DialogueRNNFn passes them to ganffn_drnn_att_*.
+    transform.weight and vector_prod.weight), then the listener's; DialogueRNNFn passes them on as the attention's own.
     simple attention (model.py:117-131): alpha = softmax_s(w . g_s) is general attention with the CONSTANT query w (general:
     alpha = softmax_s(q_t . g_s), q_t = W_att U_t).  A constant cannot come out of W_att U_t, so the utterance features get one
     more column that is always 1 (and three zero columns: the kernels want widths in multiples of 4), the input-side weights of
@@ -740,8 +733,8 @@ def _drnn_cell_args(cell, U):
 
 def dialogue_rnn_run(cells, Us, qmasks, training):
     """cells / Us / qmasks: one entry per direction.  -> [(emotions (S,B,D_e), [alpha_t (B,t)] for t >= 1)] per direction.
-    One native call for B <= MAX_DIALOGUES (at most 32 dialogues: the entry points that always took them; more: ganffn_drnn_batch_*,
-    the dialogues in tiles of 32 inside every launch); beyond that, chunks of MAX_DIALOGUES (chunks are independent)."""
+    One native call for B <= MAX_DIALOGUES (which entry points: drnn_family; more than 32 dialogues run in tiles of 32 inside
+    every launch); beyond that, chunks of MAX_DIALOGUES (chunks are independent)."""
     ndir = len(cells)
     S, B = Us[0].shape[:2]
     e_parts, a_parts = [[] for _ in range(ndir)], [[] for _ in range(ndir)]
