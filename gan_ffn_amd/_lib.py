@@ -89,6 +89,9 @@ SIGNATURES = {
     "ganffn_rng_advance": (_I, [_P, _U64, _P]),
     "ganffn_pe_table": (_I, [_P, _I, _I, _P]),
     "ganffn_encoder_fwd": (_I, [_PE, _P, _P, _P, _P, _P, _P, _P, _U64, _P]),
+    "ganffn_encoder_fwd_pair_supported": (_I, [_PE]),
+    "ganffn_encoder_fwd_pair_workspace_floats": (_L, [_PE]),
+    "ganffn_encoder_fwd_pair": (_I, [_PE, _P, _P, _P, _P, _P, _P, _P, _P, _U64, _P]),
     "ganffn_encoder_bwd": (_I, [_PE, _I, _I, _P, _P, _P, _P, _P, _P, _U64, _P]),
     "ganffn_encoder_bwd2": (_I, [_PE, _I, _I, _P, _P, _P, _P, _P, _P, _U64, _I, _P]),
     "ganffn_head_fwd": (_I, [_PH, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, _P]),

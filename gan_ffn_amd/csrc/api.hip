@@ -281,6 +281,143 @@ extern "C" int ganffn_encoder_fwd(const ganffn_enc_cfg* c, const float* x_in, co
 }
 
 // ------------------------------------------------------------------------------------------
+// encoder stack forward over two row segments: the eval-mode pass (nothing kept) and the train-mode pass (saved for the
+// backward) of ONE stack over the SAME input.  In the GAN schedule every discriminator sub-step runs its partner generator
+// in eval mode and the next sub-step runs that generator in train mode on the same batch with the same parameters; here the
+// two passes share their launches.  Every forward kernel has a two-segment form (rowchain.hip, attention16.hip,
+// attention.hip, gemm.hip's generic and weight-resident kernels, gemm_n100.hip, elementwise.hip's PE and LayerNorm
+// kernels) in which a workgroup picks its segment from its index and then does what a workgroup of the single-segment launch
+// does, so each output has the bits ganffn_encoder_fwd gives it.  The launch sequence is ganffn_encoder_fwd's; every rule
+// that picks a summation order (split-K factors, K chunks of gemm_n100) is evaluated for T = S B, one segment's rows.
+// ------------------------------------------------------------------------------------------
+static bool pair_supported(const ganffn_enc_cfg* c, const Mode md) {
+    // every width has its segment forms; of gemm_n100's variants only the product one (eight waves, 4x4x1 tail), not the lab ones
+    if (n100_supported(c->E, c->F) && !md.n100_off() && (md.n100_pad7() || md.n100_force_kw() == 1)) return false;
+    return true;
+}
+// eval segment: the unsaved forward's workspace layout (X ping-pong | one layer's saved set | slabs); then the train segment's slabs
+static int64_t pair_eval_ws_floats(const ganffn_enc_cfg* c) {
+    const int64_t TE = (int64_t)c->S * c->B * c->E;
+    return 2 * TE + saved_off(c).per_layer + MAX_SPLITS * TE;
+}
+extern "C" int ganffn_encoder_fwd_pair_supported(const ganffn_enc_cfg* c) {
+    if (check_cfg(c) != 0) return 0;
+    return pair_supported(c, mode()) ? 1 : 0;
+}
+extern "C" int64_t ganffn_encoder_fwd_pair_workspace_floats(const ganffn_enc_cfg* c) {
+    if (check_cfg(c) != 0) return -1;
+    return pair_eval_ws_floats(c) + (int64_t)MAX_SPLITS * c->S * c->B * c->E + 64;
+}
+extern "C" int ganffn_encoder_fwd_pair(const ganffn_enc_cfg* c, const float* x_in, const float* pe, const float* params,
+                                       float* out_eval, float* out_train, float* saved_train, float* workspace,
+                                       const uint64_t* rng, uint64_t add_train, void* stream) {
+    const Mode md = mode();
+    GF_TRY(check_cfg(c));
+    GF_CHECK_ARG(pair_supported(c, md), "encoder_fwd_pair: no two-segment form for E=%d H=%d F=%d S=%d (ganffn_encoder_fwd_pair_supported)",
+                 c->E, c->H, c->F, c->S);
+    GF_CHECK_ARG(x_in && pe && params && out_eval && out_train && saved_train && workspace, "encoder_fwd_pair: null pointer");
+    GF_CHECK_ARG(aligned16(x_in) && aligned16(params) && aligned16(out_eval) && aligned16(out_train) && aligned16(saved_train) &&
+                     aligned16(workspace), "encoder_fwd_pair: buffers must be 16-byte aligned");
+    const int train = c->train;
+    GF_CHECK_ARG(!(train && (c->p_pe > 0.f || c->p_enc > 0.f)) || rng, "encoder_fwd_pair: rng required in train mode");
+    hipStream_t st = (hipStream_t)stream;
+    const int S = c->S, B = c->B, E = c->E, H = c->H, F = c->F, L = c->L, T = S * B;
+    const int64_t TE = (int64_t)T * E;
+    const LayerOff lo = layer_off(E, F);
+    const SavedOff so = saved_off(c);
+    const uint64_t add = add_train;
+
+    // segment 0 (eval, train flag 0 in every launch) lives in the workspace as in the unsaved ganffn_encoder_fwd, segment 1
+    // (train) in its saved buffer; tmp0 / tmp1: the GEMM output slabs before a LayerNorm
+    float* const tmp0 = workspace + 2 * TE + so.per_layer;
+    float* const tmp1 = workspace + pair_eval_ws_floats(c);
+    float* const sv0 = workspace + 2 * TE;
+    auto sv1 = [&](int l) { return saved_train + so.layers + (int64_t)l * so.per_layer; };
+    float* X0 = workspace;
+    float* X1 = saved_train + so.X;
+    const bool rc = rc_supported(E) && !md.rc_off();
+    if (rc && !md.pe_off()) {
+        RcFwdSeg1 s1{};
+        s1.y = pe; s1.x = x_in; s1.out = X1; s1.post_out = sv1(0) + so.qkv; s1.train = train;
+        GF_TRY(launch_rc_pe_inproj_fwd(x_in, pe, X0, params + lo.in_w, params + lo.in_b, sv0 + so.qkv, T, B, c->p_pe, rng, add, 0, st,
+                                       &s1));
+    } else {
+        GF_TRY(launch_pe_dropout(x_in, pe, X0, S, B, E, c->p_pe, rng, add, 0, st, X1, train));
+        if (rc) {
+            EpiArgs e0;
+            e0.bias = params + lo.in_b;
+            const GemmSeg1 g1{X1, sv1(0) + so.qkv, nullptr, train};
+            GF_TRY(launch_gemm_nt_pair(X0, E, params + lo.in_w, E, sv0 + so.qkv, 3 * E, T, 3 * E, E, EPI_NONE, e0, g1, st));
+        }
+    }
+    for (int l = 0; l < L; ++l) {
+        const float* P = params + (int64_t)l * lo.total;
+        float* const s1v = sv1(l);
+        float* Xn0 = (l == L - 1) ? out_eval : workspace + ((l & 1) ? 0 : TE);
+        float* Xn1 = (l == L - 1) ? out_train : saved_train + so.X + (int64_t)(l + 1) * TE;
+        const uint32_t site = SITE_LAYER0 + 4 * l;
+        EpiArgs ea;
+        ea.bias = P + lo.in_b;
+        if (!rc) {
+            const GemmSeg1 g1{X1, s1v + so.qkv, nullptr, train};
+            GF_TRY(launch_gemm_nt_pair(X0, E, P + lo.in_w, E, sv0 + so.qkv, 3 * E, T, 3 * E, E, EPI_NONE, ea, g1, st));
+        }
+        {
+            const AttnFwdSeg1 a1{s1v + so.qkv, s1v + so.attn_o, s1v + so.lse, reinterpret_cast<uint32_t*>(s1v + so.keep), train};
+            GF_TRY(launch_attention_fwd(sv0 + so.qkv, sv0 + so.attn_o, sv0 + so.lse, nullptr, S, B, E, H, c->p_enc, site + 0, rng, add, 0,
+                                        st, &a1));
+        }
+        if (rc) {
+            RcFwdSeg1 s1{};
+            s1.pre_a = s1v + so.attn_o; s1.x = X1; s1.out = s1v + so.x1; s1.xhat = s1v + so.xhat1; s1.rstd = s1v + so.rstd1;
+            s1.train = train;
+            GF_TRY(launch_rc_outproj_ln_fwd(sv0 + so.attn_o, P + lo.out_w, P + lo.out_b, X0, P + lo.n1w, P + lo.n1b, sv0 + so.x1,
+                                            sv0 + so.xhat1, sv0 + so.rstd1, T, c->ln_eps, c->p_enc, site + 1, rng, add, 0, st, &s1));
+        } else {
+            ea.bias = P + lo.out_b;
+            int osplits = md.outproj_nosplit() ? 1 : gemm_splitk_factor(T, E, E);      // (T: one segment's rows)
+            const GemmSeg1 g1{s1v + so.attn_o, tmp1, nullptr, train};
+            GF_TRY(launch_gemm_nt_pair(sv0 + so.attn_o, E, P + lo.out_w, E, tmp0, E, T, E, E, EPI_NONE, ea, g1, st, &osplits, TE));
+            const LnFwdSeg1 n1{X1, tmp1, s1v + so.x1, s1v + so.xhat1, s1v + so.rstd1, train};
+            GF_TRY(launch_add_drop_ln_fwd(X0, tmp0, P + lo.n1w, P + lo.n1b, sv0 + so.x1, sv0 + so.xhat1, sv0 + so.rstd1, T, E, c->ln_eps,
+                                          c->p_enc, site + 1, rng, add, 0, st, osplits, TE, &n1));
+        }
+        int splits = 1;
+        {
+            EpiArgs e1;
+            e1.bias = P + lo.b1; e1.p = c->p_enc; e1.site = site + 2; e1.rng = rng; e1.rng_add = add; e1.train = 0;
+            const GemmSeg1 g1{s1v + so.x1, s1v + so.h, reinterpret_cast<uint16_t*>(s1v + so.hmask), train};
+            GF_TRY(launch_gemm_nt_pair(sv0 + so.x1, E, P + lo.w1, E, sv0 + so.h, F, T, F, E, EPI_RELU_DROP, e1, g1, st));
+            if (n100_supported(E, F) && !md.n100_off()) {
+                splits = MAX_SPLITS;
+                GF_TRY(launch_gemm_n100(sv0 + so.h, F, P + lo.w2, F, 0, P + lo.b2, tmp0, TE, T, F, &splits, st, s1v + so.h, tmp1));
+            } else {
+                ea.bias = P + lo.b2;
+                splits = gemm_splitk_factor(T, E, F);
+                const GemmSeg1 g2{s1v + so.h, tmp1, nullptr, train};
+                GF_TRY(launch_gemm_nt_pair(sv0 + so.h, F, P + lo.w2, F, tmp0, E, T, E, F, EPI_NONE, ea, g2, st, &splits, TE));
+            }
+        }
+        if (rc) {
+            const float* Pn = (l + 1 < L) ? P + lo.total : nullptr;
+            RcFwdSeg1 s1{};
+            s1.y = tmp1; s1.x = s1v + so.x1; s1.out = Xn1; s1.xhat = s1v + so.xhat2; s1.rstd = s1v + so.rstd2;
+            s1.post_out = Pn ? sv1(l + 1) + so.qkv : nullptr; s1.train = train;
+            GF_TRY(launch_rc_ln_inproj_fwd(tmp0, splits, TE, sv0 + so.x1, P + lo.n2w, P + lo.n2b, Xn0, sv0 + so.xhat2, sv0 + so.rstd2,
+                                           Pn ? Pn + lo.in_w : nullptr, Pn ? Pn + lo.in_b : nullptr, Pn ? sv0 + so.qkv : nullptr, T,
+                                           c->ln_eps, c->p_enc, site + 3, rng, add, 0, st, &s1));
+        } else {
+            const LnFwdSeg1 n2{s1v + so.x1, tmp1, Xn1, s1v + so.xhat2, s1v + so.rstd2, train};
+            GF_TRY(launch_add_drop_ln_fwd(sv0 + so.x1, tmp0, P + lo.n2w, P + lo.n2b, Xn0, sv0 + so.xhat2, sv0 + so.rstd2, T, E, c->ln_eps,
+                                          c->p_enc, site + 3, rng, add, 0, st, splits, TE, &n2));
+        }
+        X0 = Xn0;
+        X1 = Xn1;
+    }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
 // encoder stack backward over layers [lo_l, hi_l)
 // ------------------------------------------------------------------------------------------
 extern "C" int ganffn_encoder_bwd2(const ganffn_enc_cfg* c, int layer_lo, int layer_hi, float* dx, const float* params,

@@ -311,14 +311,25 @@ __device__ __forceinline__ bool kept(const unsigned long long (&mq)[4], int c, i
 // ------------------------------------------------------------------------------------------
 // forward: one wave per 32 queries, blockDim = 64 * NT
 // ------------------------------------------------------------------------------------------
-template <int HD, int NT>
+// PAIR: two batches of the same shape in one launch (the eval-mode and the train-mode pass of one generator): workgroups
+// 0 .. B H - 1 are the first batch's, the rest the second's with its own qkv / o and train flag.  Wave-uniform, chosen once;
+// (dialogue, head) indices and the Philox counters are local to the batch: each batch gets the bits of its own launch.
+template <int HD, int NT, bool PAIR = false>
 __global__ __launch_bounds__(64 * NT) void attention_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ o, AttnGeom g,
                                                                 float p, uint32_t site, const uint64_t* __restrict__ rng,
-                                                                uint64_t add, int train) {
+                                                                uint64_t add, int train, const float* qkv1, float* o1,
+                                                                int train1) {
     constexpr int NTD = HD ? (HD + 31) / 32 : 2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
-    const int bh = blockIdx.x, b = bh / g.H, head = bh % g.H;
+    int bh = blockIdx.x;
+    if constexpr (PAIR) {
+        if (bh >= g.B * g.H) {
+            bh -= g.B * g.H;
+            qkv = qkv1; o = o1; train = train1;
+        }
+    }
+    const int b = bh / g.H, head = bh % g.H;
     const size_t HM = (size_t)g.ROWS * g.LDH + 64;
     float* Qs = smem;
     float* Ks = Qs + HM;
@@ -555,9 +566,16 @@ static int check_attn(int S, int B, int E, int H) {
 
 template <int HD, int NT>
 static int launch_fwd_t(const float* qkv, float* o, const AttnGeom& g, size_t lds, float p, uint32_t site, const uint64_t* rng,
-                        uint64_t add, int train, hipStream_t st) {
-    GF_TRY((lds_optin<attention_fwd_kernel<HD, NT>>(lds, "attention_fwd")));
-    hipLaunchKernelGGL((attention_fwd_kernel<HD, NT>), dim3(g.B * g.H), dim3(64 * NT), lds, st, qkv, o, g, p, site, rng, add, train);
+                        uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1) {
+    if (seg1) {
+        GF_TRY((lds_optin<attention_fwd_kernel<HD, NT, true>>(lds, "attention_fwd")));
+        hipLaunchKernelGGL((attention_fwd_kernel<HD, NT, true>), dim3(2 * g.B * g.H), dim3(64 * NT), lds, st, qkv, o, g, p, site, rng,
+                           add, train, seg1->qkv, seg1->o, seg1->train);
+    } else {
+        GF_TRY((lds_optin<attention_fwd_kernel<HD, NT>>(lds, "attention_fwd")));
+        hipLaunchKernelGGL((attention_fwd_kernel<HD, NT>), dim3(g.B * g.H), dim3(64 * NT), lds, st, qkv, o, g, p, site, rng, add, train,
+                           (const float*)nullptr, (float*)nullptr, 0);
+    }
     GF_LAUNCH_CHECK();
     return 0;
 }
@@ -580,17 +598,18 @@ static int launch_bwd_t(const float* qkv, const float* d_o, float* d_qkv, const 
     }
 
 int launch_attention_fwd(const float* qkv, float* o, float* lse, uint32_t* keep, int S, int B, int E, int H, float p, uint32_t site,
-                         const uint64_t* rng, uint64_t add, int train, hipStream_t st) {
+                         const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1) {
     GF_TRY(check_attn(S, B, E, H));
     GF_CHECK_ARG(qkv && o, "attention_fwd: null pointer");
-    GF_CHECK_ARG(!(train && p > 0.f) || rng, "attention_fwd: rng required when dropout is active");
-    if (attn16_supported(E, H, S)) return launch_attn16_fwd(qkv, o, lse, keep, S, B, E, H, p, site, rng, add, train, st);
+    GF_CHECK_ARG(!seg1 || (seg1->qkv && seg1->o), "attention_fwd: bad second batch");
+    GF_CHECK_ARG(!((train || (seg1 && seg1->train)) && p > 0.f) || rng, "attention_fwd: rng required when dropout is active");
+    if (attn16_supported(E, H, S)) return launch_attn16_fwd(qkv, o, lse, keep, S, B, E, H, p, site, rng, add, train, st, seg1);
     const AttnGeom g = make_geom(S, B, E, H);
     const size_t lds = 3 * hd_mat_floats(g) * sizeof(float);
     GF_CHECK_ARG(lds <= 160 * 1024, "attention_fwd: LDS need %zu > 160 KiB", lds);
-    if (g.hd == 64) { NT_SWITCH(launch_fwd_t, 64, qkv, o, g, lds, p, site, rng, add, train, st) }
-    if (g.hd == 60) { NT_SWITCH(launch_fwd_t, 60, qkv, o, g, lds, p, site, rng, add, train, st) }
-    NT_SWITCH(launch_fwd_t, 0, qkv, o, g, lds, p, site, rng, add, train, st)
+    if (g.hd == 64) { NT_SWITCH(launch_fwd_t, 64, qkv, o, g, lds, p, site, rng, add, train, st, seg1) }
+    if (g.hd == 60) { NT_SWITCH(launch_fwd_t, 60, qkv, o, g, lds, p, site, rng, add, train, st, seg1) }
+    NT_SWITCH(launch_fwd_t, 0, qkv, o, g, lds, p, site, rng, add, train, st, seg1)
 }
 
 int launch_attention_bwd(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keep, float* d_qkv,

@@ -174,17 +174,32 @@ __device__ __forceinline__ void store4(float* __restrict__ row, int d0, const fl
 // (dialogue, head) problem into NT / WPB workgroups that each stage the head's K and V again (a few KB out of L2) — the
 // 320 problems of a d_model-100 pass are 1.25 per CU as whole workgroups (64 CUs hold two), finer workgroups spread evenly
 // ------------------------------------------------------------------------------------------
-template <int HD, int NT, int WPB>
+// PAIR: two batches of the same shape in one launch (the eval-mode and the train-mode pass of one generator): workgroups
+// 0 .. nb0 - 1 are the first batch's, the rest the second's with its own qkv / o / lse / keep words and train flag (s1).  The
+// choice is wave-uniform and made once; (dialogue, head) indices and with them the Philox row groups are local to the batch,
+// so each batch gets the bits of its own launch.
+struct Attn16Seg1 {
+    const float* qkv; float* o; float* lse; uint32_t* keepw; int train;
+};
+template <int HD, int NT, int WPB, bool PAIR = false>
 __global__ __launch_bounds__(64 * WPB) void attn16_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ o,
                                                              float* __restrict__ lse, uint32_t* __restrict__ keepw, int S, int B,
                                                              int E, int H, float p, uint32_t site,
-                                                             const uint64_t* __restrict__ rng, uint64_t add, int train) {
+                                                             const uint64_t* __restrict__ rng, uint64_t add, int train,
+                                                             Attn16Seg1 s1, int nb0) {
+    unsigned bid = blockIdx.x;
+    if constexpr (PAIR) {
+        if (bid >= (unsigned)nb0) {
+            bid -= (unsigned)nb0;
+            qkv = s1.qkv; o = s1.o; lse = s1.lse; keepw = s1.keepw; train = s1.train;
+        }
+    }
     constexpr int LD = A16<HD>::LD, NTD = A16<HD>::NTD, MAT = 16 * NT * LD + A16<HD>::TAIL;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     static_assert(NT % WPB == 0, "query tiles per workgroup must divide the tile count");
     constexpr int NQB = NT / WPB;
     const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, g = lane >> 4;
-    const int bh = blockIdx.x / NQB, w = (blockIdx.x - bh * NQB) * WPB + (tid >> 6);     // w: query tile of this wave
+    const int bh = bid / NQB, w = (bid - bh * NQB) * WPB + (tid >> 6);     // w: query tile of this wave
     const int b = bh / H, head = bh - b * H;
     float* Qs = smem;
     float* Ks = Qs + MAT;
@@ -489,9 +504,24 @@ static size_t bwd_lds(int nt) {
 
 template <int HD, int NT>
 static int launch16_fwd(const float* qkv, float* o, float* lse, uint32_t* keepw, int S, int B, int E, int H, float p, uint32_t site,
-                        const uint64_t* rng, uint64_t add, int train, hipStream_t st) {
+                        const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1) {
     const size_t lds = fwd_lds<HD>(NT);
     if (!attn16_use_keep(B, H)) keepw = nullptr;
+    if (seg1) {
+        // the workgroup cut and the keep-word rule are those of ONE batch of B dialogues: what a single launch would choose
+        Attn16Seg1 s1{seg1->qkv, seg1->o, seg1->lse, attn16_use_keep(B, H) ? seg1->keep : nullptr, seg1->train};
+#define GF_A16_FWD2(W)                                                                                              \
+    {                                                                                                               \
+        GF_TRY((lds_optin<attn16_fwd_kernel<HD, NT, W, true>>(lds, "attention_fwd")));                              \
+        hipLaunchKernelGGL((attn16_fwd_kernel<HD, NT, W, true>), dim3(2 * B * H * (NT / W)), dim3(64 * W), lds, st, qkv, o, lse, keepw, \
+                           S, B, E, H, p, site, rng, add, train, s1, B * H * (NT / W));                              \
+    }
+        if ((long)B * H < 512 && NT % 2 == 0 && NT > 2) GF_A16_FWD2((NT % 2 == 0 ? 2 : NT))
+        else GF_A16_FWD2(NT)
+#undef GF_A16_FWD2
+        GF_LAUNCH_CHECK();
+        return 0;
+    }
     // query tiles per workgroup: measured at hd = 10, S = 94 (tools/lab/attn_wpb.py, lab build): 320 problems 11.1 us as
     // whole workgroups, 10.1 / 9.9 / 11.5 us cut in 2 / 3 / 6; 640 problems 15.0 us whole, 16.4 / 17.9 / 21.5 us cut —
     // the cut pays while the problems do not fill the chip, then the repeated K / V staging costs more than the balance gains
@@ -499,7 +529,7 @@ static int launch16_fwd(const float* qkv, float* o, float* lse, uint32_t* keepw,
     {                                                                                                               \
         GF_TRY((lds_optin<attn16_fwd_kernel<HD, NT, W>>(lds, "attention_fwd")));                                    \
         hipLaunchKernelGGL((attn16_fwd_kernel<HD, NT, W>), dim3(B * H * (NT / W)), dim3(64 * W), lds, st, qkv, o, lse, keepw, S, \
-                           B, E, H, p, site, rng, add, train);                                                          \
+                           B, E, H, p, site, rng, add, train, Attn16Seg1{}, 0);                                         \
     }
     if ((long)B * H < 512 && NT % 2 == 0 && NT > 2) GF_A16_FWD((NT % 2 == 0 ? 2 : NT))
     else GF_A16_FWD(NT)
@@ -543,13 +573,14 @@ static int launch16_bwd(const float* qkv, const float* o, const float* lse, cons
     }
 
 int launch_attn16_fwd(const float* qkv, float* o, float* lse, uint32_t* keepw, int S, int B, int E, int H, float p, uint32_t site,
-                      const uint64_t* rng, uint64_t add, int train, hipStream_t st) {
+                      const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1) {
+    GF_CHECK_ARG(!seg1 || (seg1->qkv && seg1->o), "attn16_fwd: bad second batch");
     GF_CHECK_ARG(attn16_supported(E, H, S) && S >= 1 && S <= GANFFN_MAX_SEQ, "attn16_fwd: unsupported E=%d H=%d S=%d", E, H, S);
     GF_CHECK_ARG((long)B * H * 28 * 128 < (1l << 32), "attention: B*H too large for the Philox counter");
-    if (E / H == 64) { NT16_SWITCH3(launch16_fwd, 64, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st) }
-    if (E / H == 60) { NT16_SWITCH3(launch16_fwd, 60, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st) }
-    if (E / H == 10) { NT16_SWITCH(launch16_fwd, 10, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st) }
-    NT16_SWITCH(launch16_fwd, 30, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st)
+    if (E / H == 64) { NT16_SWITCH3(launch16_fwd, 64, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st, seg1) }
+    if (E / H == 60) { NT16_SWITCH3(launch16_fwd, 60, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st, seg1) }
+    if (E / H == 10) { NT16_SWITCH(launch16_fwd, 10, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st, seg1) }
+    NT16_SWITCH(launch16_fwd, 30, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st, seg1)
 }
 
 int launch_attn16_bwd(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keepw, float* d_qkv,

@@ -268,6 +268,13 @@ inline long epi_mask_words(long M, long N) { return ((M + 31) / 32) * N * 2; }
 int launch_gemm_nt(const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N, int K,
                    int epi, const EpiArgs& ea, hipStream_t st, int* splits_io = nullptr, long slab_stride = 0);
 int gemm_splitk_factor(int M, int N, int K);
+// second row segment of a two-segment launch_gemm_nt (EPI_NONE, also split-K, or EPI_RELU_DROP): its input rows, output (slabs
+// at the same stride), pattern words (may be null) and train flag
+struct GemmSeg1 {
+    const float* A; float* C; uint16_t* mask_out; int train;
+};
+int launch_gemm_nt_pair(const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N, int K, int epi,
+                        const EpiArgs& ea, const GemmSeg1& s1, hipStream_t st, int* splits_io = nullptr, long slab_stride = 0);
 // C[MxN] = A[MxK] * B[KxN] (NN)
 int launch_gemm_nn(const float* A, int lda, const float* Bm, int ldb, float* C, int ldc, int M, int N, int K,
                    int epi, const EpiArgs& ea, hipStream_t st, int* splits_io = nullptr, long slab_stride = 0);
@@ -328,29 +335,40 @@ long gemm_tn_grouped_part_floats();
 // small-head forward and read back by its backward instead of recomputing the Philox calls (attention16.hip; the
 // head_dim 60/64 kernels ignore it).  Same bits either way.
 constexpr int ATTN_KEEP_WORDS = 28 * 16;
+// seg1 (optional): a second batch of the same shape in the same launch, with its own buffers and train flag
+struct AttnFwdSeg1 {
+    const float* qkv; float* o; float* lse; uint32_t* keep; int train;
+};
 int launch_attention_fwd(const float* qkv, float* o, float* lse, uint32_t* keep, int S, int B, int E, int H, float p, uint32_t site,
-                         const uint64_t* rng, uint64_t add, int train, hipStream_t st);
+                         const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1 = nullptr);
 int launch_attention_bwd(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keep, float* d_qkv,
                          int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train,
                          hipStream_t st);
 bool attn16_supported(int E, int H, int S);
 int launch_attn16_fwd(const float* qkv, float* o, float* lse, uint32_t* keepw, int S, int B, int E, int H, float p, uint32_t site,
-                      const uint64_t* rng, uint64_t add, int train, hipStream_t st);
+                      const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1 = nullptr);
 int launch_attn16_bwd(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keepw, float* d_qkv,
                       int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train,
                       hipStream_t st);
 
+// out1 (optional): a second segment over the same x in the same launch, with its own output and train flag
 int launch_pe_dropout(const float* x, const float* pe, float* out, int S, int B, int E, float p,
-                      const uint64_t* rng, uint64_t add, int train, hipStream_t st);
+                      const uint64_t* rng, uint64_t add, int train, hipStream_t st, float* out1 = nullptr, int train1 = 0);
 int launch_dropout_bwd_inplace(float* dx, int R, int C, float p, uint32_t site, const uint64_t* rng, uint64_t add,
                                int train, hipStream_t st);
 int launch_dropout(const float* x, float* out, int R, int C, float p, uint32_t site, const uint64_t* rng,
                    uint64_t add, int train, hipStream_t st);
 // y / d_out may be given as `nslab` partial slabs `slab_stride` floats apart (split-K GEMM output): they are summed
 // on the fly; d_out additionally takes an optional addend (the residual-branch gradient).
+// s1 (optional): a second row segment of T rows in the same launch (same parameters, nslab and slab_stride), with its own
+// operands and train flag
+struct LnFwdSeg1 {
+    const float* x; const float* y; float* out; float* xhat; float* rstd; int train;
+};
 int launch_add_drop_ln_fwd(const float* x, const float* y, const float* w, const float* b, float* out, float* xhat,
                            float* rstd, int T, int E, float eps, float p, uint32_t site, const uint64_t* rng,
-                           uint64_t add, int train, hipStream_t st, int nslab = 1, long slab_stride = 0);
+                           uint64_t add, int train, hipStream_t st, int nslab = 1, long slab_stride = 0,
+                           const LnFwdSeg1* s1 = nullptr);
 // gw / gb: per-block partial sums go to gpart (ln_bwd_blocks(T) * 2 * E floats), to be added by launch_ln_param_reduce;
 // gpart == NULL runs one workgroup that adds its sums directly.  No atomics either way.
 int ln_bwd_blocks(int T);
@@ -366,8 +384,9 @@ int launch_add_inplace(float* a, const float* b, int64_t n, hipStream_t st);
 // gemm_n100.hip — [T x K] x [K x 100] with a long K on 16x16x4 MFMAs (112-wide feature tile), K cut into output slabs
 bool n100_supported(int N, int K);
 int n100_splits(int T, int K, int max_splits, int w_kmajor);
+// A1 / C1 (optional, both or neither; rows-of-K weights only): a second row segment [T x K] -> slabs at C1 in the same launch
 int launch_gemm_n100(const float* A, int lda, const float* W, int ldw, int w_kmajor, const float* bias, float* C, long slab_stride,
-                     int T, int K, int* splits_io, hipStream_t st);
+                     int T, int K, int* splits_io, hipStream_t st, const float* A1 = nullptr, float* C1 = nullptr);
 
 // rowchain.hip — d_model 100: out-proj + residual + dropout + LayerNorm1, LayerNorm2 + the next layer's in-proj, and the
 // mirror-image backward chains, one kernel each (16 token rows per workgroup)
@@ -375,14 +394,24 @@ bool rc_supported(int E);
 long rc_pack_floats();          // floats of one layer's transposed {in-proj, out-proj} weights (backward)
 int rc_blocks(int T);           // workgroups = partial rows of the LayerNorm parameter gradients per launch
 int launch_rc_pack(const float* params, long layer_stride, long off_in, long off_out, float* wt, int nl, hipStream_t st);
+// s1 (forward launchers, optional): a SECOND row segment of the same T rows with the same weights in the same launch — its
+// per-segment operands (named as in the kernel: pre_a = attn_o, y = slabs / PE table, x = residual, post_out = qkv) and its
+// train flag; the arguments proper describe segment 0.  Each segment gets the bits of its own single-segment launch.
+struct RcFwdSeg1 {
+    const float* pre_a; const float* y; const float* x;
+    float* out; float* xhat; float* rstd; float* post_out;
+    int train;
+};
 int launch_rc_outproj_ln_fwd(const float* attn_o, const float* wo, const float* bo, const float* x, const float* gamma,
                              const float* beta, float* out, float* xhat, float* rstd, int T, float eps, float p, uint32_t site,
-                             const uint64_t* rng, uint64_t add, int train, hipStream_t st);
+                             const uint64_t* rng, uint64_t add, int train, hipStream_t st, const RcFwdSeg1* s1 = nullptr);
 int launch_rc_pe_inproj_fwd(const float* x_in, const float* pe, float* out, const float* w_in, const float* b_in, float* qkv, int T,
-                            int B, float p, const uint64_t* rng, uint64_t add, int train, hipStream_t st);
+                            int B, float p, const uint64_t* rng, uint64_t add, int train, hipStream_t st,
+                            const RcFwdSeg1* s1 = nullptr);
 int launch_rc_ln_inproj_fwd(const float* y, int nslab, long slab_stride, const float* x, const float* gamma, const float* beta,
                             float* out, float* xhat, float* rstd, const float* w_in, const float* b_in, float* qkv, int T,
-                            float eps, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train, hipStream_t st);
+                            float eps, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train, hipStream_t st,
+                            const RcFwdSeg1* s1 = nullptr);
 int launch_rc_ln_bwd(const float* d_qkv, const float* w_in_t, const float* d_out, int nslab, long slab_stride, const float* addend,
                      const float* xhat, const float* rstd, const float* gamma, float* dz, float* dy, float* gpart,
                      const float* wo_t, float* d_attn, int T, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train,

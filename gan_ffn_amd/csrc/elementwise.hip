@@ -16,11 +16,21 @@ namespace ganffn {
 // A1: out = dropout_p(x + pe[s])        /root/reference/model.py:1196-1197
 // one thread per (row group of 4, column)
 // ------------------------------------------------------------------------------------------
+// PAIR: two segments of T rows in one launch (the eval-mode and the train-mode pass over the same x): workgroups 0 .. nb0 - 1 do
+// segment 0, the rest segment 1 (out1, train1) — row groups of 4 are counted inside the segment
+template <bool PAIR>
 __global__ void pe_dropout_kernel(const float* __restrict__ x, const float* __restrict__ pe, float* __restrict__ out,
                                   int T, int B, int E, float p, const uint64_t* __restrict__ rng, uint64_t add,
-                                  int train) {
+                                  int train, float* out1, int train1, int nb0) {
     const int G = (T + 3) >> 2;
-    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    int bid = blockIdx.x;
+    if constexpr (PAIR) {
+        if (bid >= nb0) {
+            bid -= nb0;
+            out = out1; train = train1;
+        }
+    }
+    const long idx = (long)bid * blockDim.x + threadIdx.x;
     if (idx >= (long)G * E) return;
     const int rg = (int)(idx / E), c = (int)(idx - (long)rg * E);
     const DropCtx dc = make_drop(rng, add, SITE_PE, p, train);
@@ -85,15 +95,23 @@ constexpr int LN_MAXSLAB = 16;  // split-K / split-F slabs summed on the fly (ap
 // NC = column chunks of 64 per lane (E <= 64 NC); NSB = slabs loaded per batch.  Every global load is issued from a
 // clamped (always valid) address and masked afterwards by a select: a load under a branch makes hipcc wait for it
 // (s_waitcnt vmcnt(0)) before the next one is issued, which serialised ~100 loads per lane in the first version.
-template <int NC, int NSB>
+template <int NC, int NSB, bool PAIR = false>
 __global__ __launch_bounds__(256) void add_drop_ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                               const float* __restrict__ w, const float* __restrict__ b,
                                                               float* __restrict__ out, float* __restrict__ xhat,
                                                               float* __restrict__ rstd, int T, int E, float eps, float p,
                                                               uint32_t site, const uint64_t* __restrict__ rng,
-                                                              uint64_t add, int train, int nslab, long slab_stride) {
+                                                              uint64_t add, int train, int nslab, long slab_stride, LnFwdSeg1 s1,
+                                                              int nb0) {
     const int lane = threadIdx.x & 63;
-    const int rg = blockIdx.x * 4 + (threadIdx.x >> 6);
+    int bid = blockIdx.x;
+    if constexpr (PAIR) {           // second row segment (same T, same parameters): its own operands, row groups counted inside it
+        if (bid >= nb0) {
+            bid -= nb0;
+            x = s1.x; y = s1.y; out = s1.out; xhat = s1.xhat; rstd = s1.rstd; train = s1.train;
+        }
+    }
+    const int rg = bid * 4 + (threadIdx.x >> 6);
     if (rg * 4 >= T) return;
     const DropCtx dc = make_drop(rng, add, site, p, train);
     size_t off[NC][4];      // element offsets (clamped)
@@ -672,10 +690,12 @@ __global__ __launch_bounds__(1024) void small_linear_dw_kernel(const float* __re
 static inline int nblk(long n, int bs) { return (int)((n + bs - 1) / bs); }
 
 int launch_pe_dropout(const float* x, const float* pe, float* out, int S, int B, int E, float p,
-                      const uint64_t* rng, uint64_t add, int train, hipStream_t st) {
+                      const uint64_t* rng, uint64_t add, int train, hipStream_t st, float* out1, int train1) {
     const int T = S * B;
     const long n = (long)((T + 3) / 4) * E;
-    hipLaunchKernelGGL(pe_dropout_kernel, dim3(nblk(n, 256)), dim3(256), 0, st, x, pe, out, T, B, E, p, rng, add, train);
+    const int nb = nblk(n, 256);
+    if (out1) hipLaunchKernelGGL(pe_dropout_kernel<true>, dim3(2 * nb), dim3(256), 0, st, x, pe, out, T, B, E, p, rng, add, train, out1, train1, nb);
+    else hipLaunchKernelGGL(pe_dropout_kernel<false>, dim3(nb), dim3(256), 0, st, x, pe, out, T, B, E, p, rng, add, train, (float*)nullptr, 0, 0);
     GF_LAUNCH_CHECK();
     return 0;
 }
@@ -716,14 +736,19 @@ int launch_add_inplace(float* a, const float* b, int64_t n, hipStream_t st) {
 
 int launch_add_drop_ln_fwd(const float* x, const float* y, const float* w, const float* b, float* out, float* xhat,
                            float* rstd, int T, int E, float eps, float p, uint32_t site, const uint64_t* rng,
-                           uint64_t add, int train, hipStream_t st, int nslab, long slab_stride) {
+                           uint64_t add, int train, hipStream_t st, int nslab, long slab_stride, const LnFwdSeg1* s1) {
     GF_CHECK_ARG(E <= 64 * LN_MAXC, "layernorm: E=%d > %d", E, 64 * LN_MAXC);
     GF_CHECK_ARG(nslab >= 1 && nslab <= LN_MAXSLAB, "layernorm: nslab=%d out of [1,%d]", nslab, LN_MAXSLAB);
+    GF_CHECK_ARG(!s1 || (s1->x && s1->y && s1->out), "layernorm: bad second segment");
     const int G = (T + 3) / 4;
-    const dim3 grid((G + 3) / 4), blk(256);
+    const dim3 grid((G + 3) / 4), grid2(2 * ((G + 3) / 4)), blk(256);
 #define GF_LN_FWD(NC, NSB)                                                                                              \
-    hipLaunchKernelGGL((add_drop_ln_fwd_kernel<NC, NSB>), grid, blk, 0, st, x, y, w, b, out, xhat, rstd, T, E, eps, p, \
-                       site, rng, add, train, nslab, slab_stride)
+    do {                                                                                                                \
+        if (s1) hipLaunchKernelGGL((add_drop_ln_fwd_kernel<NC, NSB, true>), grid2, blk, 0, st, x, y, w, b, out, xhat, rstd, T, E, eps, \
+                                   p, site, rng, add, train, nslab, slab_stride, *s1, (int)grid.x);                      \
+        else hipLaunchKernelGGL((add_drop_ln_fwd_kernel<NC, NSB>), grid, blk, 0, st, x, y, w, b, out, xhat, rstd, T, E, eps, p, \
+                                site, rng, add, train, nslab, slab_stride, LnFwdSeg1{}, 0);                              \
+    } while (0)
     if (E <= 64) GF_LN_FWD(1, 8);
     else if (E <= 128) GF_LN_FWD(2, 8);
     else if (E <= 256) GF_LN_FWD(4, 4);

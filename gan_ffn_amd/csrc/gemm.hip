@@ -779,6 +779,26 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_kernel(GemmArgs g) {
     gemm_body<MODE, BM, BN, BK, EPI, WGM, WGN>(g, bx, by, bz);
 }
 
+// Two row segments of M rows each against the same B operand in one launch (the eval-mode and the train-mode pass of one
+// generator): the grid has 2 * gy0 row tiles per K split; row tiles gy0 .. 2 gy0 - 1 are segment 1 — g with s1's A, C, pattern
+// words and train flag — at row tile by - gy0.  The choice is wave-uniform and made once; tiles, Philox row groups, split-K
+// slabs and the clamps at the last row are the segment's own, so each segment gets the bits of its own launch.
+template <int MODE, int BM, int BN, int BK, int EPI, int WGM = 2, int WGN = 2, int SHORTK = 0>
+__global__ __launch_bounds__(64 * WGM * WGN) void gemm_pair_kernel(GemmArgs g, GemmSeg1 s1, int gy0) {
+    const int gx = gridDim.x, gy = gridDim.y, per = gx * gy, nwg = per * gridDim.z;       // (tile order: gemm_kernel's)
+    const int lin = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
+    const int q8 = nwg >> 3, r8 = nwg & 7, xl = lin & 7;
+    const int b = (xl < r8 ? xl * (q8 + 1) : r8 * (q8 + 1) + (xl - r8) * q8) + (lin >> 3);
+    const int bz = b / per, t = b - bz * per;
+    int by = t / gx;
+    const int bx = t - by * gx;
+    if (by >= gy0) {
+        by -= gy0;
+        g.A = s1.A; g.C = s1.C; g.ea.mask_out = s1.mask_out; g.ea.train = s1.train;
+    }
+    gemm_body<MODE, BM, BN, BK, EPI, WGM, WGN>(g, bx, by, bz);
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // Weight-resident short-K GEMM (K = KC = 100: linear1 forward and linear2's dgrad of the d_model-100 feed-forward block,
 // the two [T x 100] -> [T x 2048] products with fused epilogues; /root/reference/model.py:1210 -> torch _ff_block).
@@ -803,8 +823,15 @@ __global__ __launch_bounds__(64 * WGM * WGN) void gemm_kernel(GemmArgs g) {
 // Same MFMA (v_mfma_f32_32x32x2_f32, exact fp32) and the same epilogue formulas as gemm_body.
 GF_LAB_ONLY(unsigned long long* g_wres_stamps = nullptr;)    // lab builds only (make LAB=1): 4 x uint64 of in-kernel time stamps per workgroup
 
-template <int MODE, int EPI, int KC>
-__global__ __launch_bounds__(256) void gemm_wres_kernel(GemmArgs g, int mtiles, int wg_per_panel GF_LAB_ONLY(, unsigned long long* stamps)) {
+// PAIR: two row segments of M rows each against the same weight panel in one launch (the eval-mode and the train-mode linear1
+// of one generator): the workgroup walks the 2 * mtiles token tiles of both — tiles 0 .. mtiles - 1 are segment 0 (g as given),
+// the rest segment 1 (g with s1's A, C, pattern words and train flag) — so the weight fragments and the first load are paid
+// once for both.  A tile belongs to ONE segment: its rows, Philox row groups and out-of-range rows are counted inside the
+// segment, and the segment choice is wave-uniform scalar work (pointers, one descriptor, the dropout switch) per tile; the
+// MFMA chain and the epilogue are the single-segment ones, so each segment gets the bits of its own launch.
+template <int MODE, int EPI, int KC, bool PAIR>
+__device__ __forceinline__ void gemm_wres_body(const GemmArgs& g, const int mtiles, const int wg_per_panel, const GemmSeg1& s1
+                                               GF_LAB_ONLY(, unsigned long long* stamps)) {
     static_assert(KC % 4 == 0 && KC <= 128, "short K only");
     constexpr int BM = 64, BN = 64;
     constexpr int G8 = (KC + 7) / 8;                              // groups of 8 along k; k >= KC carries zero weights
@@ -867,27 +894,38 @@ __global__ __launch_bounds__(256) void gemm_wres_kernel(GemmArgs g, int mtiles, 
     // token-tile loads through a buffer descriptor (round 5): the lane's offset inside a tile is loop-invariant, the tile's first
     // row is one 32-bit add, and rows past M are out of the descriptor's range — the hardware returns zeros for them (they feed
     // output rows that are never stored) instead of a per-lane min() + 64-bit address per load
-    const __amdgpu_buffer_rsrc_t rsA = buf_rsrc(g.A, (uint32_t)(((size_t)(g.M - 1) * g.lda + KC) * sizeof(float)));
+    const uint32_t abytes = (uint32_t)(((size_t)(g.M - 1) * g.lda + KC) * sizeof(float));
+    const __amdgpu_buffer_rsrc_t rsA = buf_rsrc(g.A, abytes);
+    const int vtiles = PAIR ? 2 * mtiles : mtiles;              // tiles walked: of both segments
     // (the tile's first row is added to the LANE offset, one v_add per load: the range check covers the lane offset only, a
     //  scalar offset would slip past it)
     const uint32_t ldab = (uint32_t)g.lda * 4u;
 #define GF_WRES_VOFF(J) const uint32_t tvo##J = ((uint32_t)trow##J * (uint32_t)g.lda + (uint32_t)tcol##J) * 4u;
     GF_REP7(GF_WRES_VOFF)
-#define GF_WRES_GLOAD1(J) ta##J = buf_load_f4(rsA, tvo##J + so_, 0u);
-#define GF_WRES_GLOAD(MT) { const uint32_t so_ = (uint32_t)((MT) * BM) * ldab; GF_REP7(GF_WRES_GLOAD1) }
+#define GF_WRES_GLOAD1(J) ta##J = buf_load_f4(rs_, tvo##J + so_, 0u);
+#define GF_WRES_GLOAD(MT)                                                                                   \
+    {                                                                                                       \
+        const int vt_ = (MT);                                                                               \
+        const bool sg_ = PAIR && vt_ >= mtiles;                 /* the tile's segment: scalar */            \
+        const __amdgpu_buffer_rsrc_t rs_ = PAIR ? buf_rsrc(sg_ ? s1.A : g.A, abytes) : rsA;                 \
+        const uint32_t so_ = (uint32_t)((sg_ ? vt_ - mtiles : vt_) * BM) * ldab;                            \
+        GF_REP7(GF_WRES_GLOAD1)                                                                             \
+    }
 #define GF_WRES_SSTORE1(J) *reinterpret_cast<float4*>(sdst + soff##J) = ta##J;
 #define GF_WRES_SSTORE(BUF) { float* const sdst = smem + (BUF) * (BM * LD); GF_REP7(GF_WRES_SSTORE1) }
 
     DropCtx dc;
     if (epi_has_dropout<EPI>()) dc = make_drop(g.ea.rng, g.ea.rng_add, g.ea.site, g.ea.p, g.ea.train);
     else dc.on = 0;
+    DropCtx dc1 = dc;                                           // PAIR: segment 1's (its own train flag)
+    if (PAIR && epi_has_dropout<EPI>()) dc1 = make_drop(g.ea.rng, g.ea.rng_add, g.ea.site, g.ea.p, s1.train);
     const int nbase = n0 + wn * 32;
     float bias = 0.f;                                           // the wave's columns never change: one load per workgroup
     if (EPI == EPI_NONE || EPI == EPI_RELU_DROP || EPI == EPI_DROP_GELU)
         if (g.ea.bias != nullptr) bias = g.ea.bias[min(nbase + r, g.N - 1)];
 
     int mt = j0;
-    if (mt >= mtiles) return;                                   // (the host never launches such a workgroup)
+    if (mt >= vtiles) return;                                   // (the host never launches such a workgroup)
     GF_WRES_GLOAD(mt)
     GF_WRES_SSTORE(0)
     __syncthreads();
@@ -917,35 +955,48 @@ __global__ __launch_bounds__(256) void gemm_wres_kernel(GemmArgs g, int mtiles, 
     // one tile from LDS stage BUF (a compile-time constant: the loop below is unrolled by two)
 #define GF_WRES_TILE(BUF)                                                                                   \
     {                                                                                                       \
-        const int mbase = mt * BM + wm * 32;                                                                \
-        const int mload = min(mt + wg_per_panel, mtiles - 1);   /* unconditional (clamped): no load under a branch */ \
+        const bool seg = PAIR && mt >= mtiles;                                                              \
+        const int mbase = (seg ? mt - mtiles : mt) * BM + wm * 32;   /* row inside the tile's segment */    \
+        const int mload = min(mt + wg_per_panel, vtiles - 1);   /* unconditional (clamped): no load under a branch */ \
         GF_WRES_GLOAD(mload)                                                                                \
+        GemmArgs gp;                                                                                        \
+        DropCtx dcp;                                                                                        \
+        if constexpr (PAIR) {                                                                               \
+            gp = g;                                                                                         \
+            gp.A = seg ? s1.A : g.A; gp.C = seg ? s1.C : g.C; gp.ea.mask_out = seg ? s1.mask_out : g.ea.mask_out; \
+            dcp = dc;                                                                                       \
+            dcp.on = seg ? dc1.on : dc.on; dcp.scale = seg ? dc1.scale : dc.scale;                          \
+            dcp.k0 = seg ? dc1.k0 : dc.k0; dcp.k1 = seg ? dc1.k1 : dc.k1;                                   \
+            dcp.o0 = seg ? dc1.o0 : dc.o0; dcp.o1 = seg ? dc1.o1 : dc.o1;                                   \
+        }                                                                                                   \
+        const GemmArgs& gs = PAIR ? gp : g;                                                                 \
+        const DropCtx& dcs = PAIR ? dcp : dc;                                                               \
         float aux[1][1][16];                                                                                \
-        gemm_load_aux<EPI, 1, 1>(g, aux, mbase, nbase, 0, r, h);                                            \
+        gemm_load_aux<EPI, 1, 1>(gs, aux, mbase, nbase, 0, r, h);                                           \
         __builtin_amdgcn_sched_barrier(0);                                                                  \
         uint32_t keep[1][1];                                                                                \
-        gemm_keep_bits<EPI, 1, 1>(g, dc, keep, mbase, nbase, r, h);                                         \
+        gemm_keep_bits<EPI, 1, 1>(gs, dcs, keep, mbase, nbase, r, h);                                       \
         floatx16 acc[1][1];                                                                                 \
         GF_WRES_MFMA(acc[0][0], BUF)                                                                        \
         __builtin_amdgcn_sched_barrier(0);                                                                  \
         GF_WRES_SSTORE((BUF) ^ 1)                                                                           \
         if (mbase + 32 <= g.M && nbase + 32 <= g.N) {           /* wave-uniform */                          \
-            gemm_apply_store_full<EPI>(g, acc[0][0], aux[0][0], bias, mbase, nbase, r, h, dc, keep[0][0]);  \
+            gemm_apply_store_full<EPI>(gs, acc[0][0], aux[0][0], bias, mbase, nbase, r, h, dcs, keep[0][0]); \
         } else {                                                                                            \
-            gemm_apply_store<EPI, 1, 1>(g, acc, aux, mbase, nbase, 0, r, h, dc, keep);                      \
+            gemm_apply_store<EPI, 1, 1>(gs, acc, aux, mbase, nbase, 0, r, h, dcs, keep);                    \
         }                                                                                                   \
         __syncthreads();                                                                                    \
     }
 #pragma unroll 1
-    for (; mt < mtiles; mt += wg_per_panel) {
+    for (; mt < vtiles; mt += wg_per_panel) {
         GF_WRES_TILE(0)
         mt += wg_per_panel;
-        if (mt >= mtiles) break;
+        if (mt >= vtiles) break;
         GF_WRES_TILE(1)
     }
 #undef GF_WRES_TILE
 #undef GF_WRES_MFMA1
-    GF_LAB_ONLY(if (stamp) { stamp[2] = __builtin_amdgcn_s_memtime(); stamp[3] = (unsigned long long)((mtiles - j0 + wg_per_panel - 1) / wg_per_panel); })
+    GF_LAB_ONLY(if (stamp) { stamp[2] = __builtin_amdgcn_s_memtime(); stamp[3] = (unsigned long long)((vtiles - j0 + wg_per_panel - 1) / wg_per_panel); })
 #undef GF_WRES_MFMA
 #undef GF_WRES_GLOAD
 #undef GF_WRES_SSTORE
@@ -956,11 +1007,22 @@ __global__ __launch_bounds__(256) void gemm_wres_kernel(GemmArgs g, int mtiles, 
 #undef GF_REP7
 }
 
-template <int MODE, int EPI>
-static int launch_wres(const GemmArgs& g, hipStream_t st) {
+template <int MODE, int EPI, int KC>
+__global__ __launch_bounds__(256) void gemm_wres_kernel(GemmArgs g, int mtiles, int wg_per_panel GF_LAB_ONLY(, unsigned long long* stamps)) {
+    gemm_wres_body<MODE, EPI, KC, false>(g, mtiles, wg_per_panel, GemmSeg1{} GF_LAB_ONLY(, stamps));
+}
+template <int MODE, int EPI, int KC>
+__global__ __launch_bounds__(256) void gemm_wres_pair_kernel(GemmArgs g, GemmSeg1 s1, int mtiles, int wg_per_panel) {
+    gemm_wres_body<MODE, EPI, KC, true>(g, mtiles, wg_per_panel, s1 GF_LAB_ONLY(, nullptr));
+}
+
+// PAIR (with s1): the two-segment launch (gemm_wres_pair_kernel) over 2 * mtiles token tiles
+template <int MODE, int EPI, bool PAIR = false>
+static int launch_wres(const GemmArgs& g, hipStream_t st, const GemmSeg1* s1 = nullptr) {
     constexpr int KC = 100;
     constexpr size_t lds = 2 * 64 * 4 * ((KC / 4) | 1) * sizeof(float);
     const int panels = (g.N + 63) / 64, mtiles = (g.M + 63) / 64;
+    if constexpr (PAIR) GF_TRY((lds_optin<gemm_wres_pair_kernel<MODE, EPI, KC>>(lds, "gemm_wres")));
     GF_TRY((lds_optin<gemm_wres_kernel<MODE, EPI, KC>>(lds, "gemm_wres")));
     // persistent grid = exactly the workgroups the device holds at once (queried once per kernel and device)
     static thread_local int resident[16] = {0};
@@ -978,6 +1040,12 @@ static int launch_wres(const GemmArgs& g, hipStream_t st) {
     }
     int per = res / panels;
     if (per < 1) per = 1;
+    if constexpr (PAIR) {
+        if (per > 2 * mtiles) per = 2 * mtiles;
+        hipLaunchKernelGGL((gemm_wres_pair_kernel<MODE, EPI, KC>), dim3(panels * per), dim3(256), lds, st, g, *s1, mtiles, per);
+        GF_LAUNCH_CHECK();
+        return 0;
+    }
     if (per > mtiles) per = mtiles;
     hipLaunchKernelGGL((gemm_wres_kernel<MODE, EPI, KC>), dim3(panels * per), dim3(256), lds, st, g, mtiles, per GF_LAB_ONLY(, g_wres_stamps));
     GF_LAUNCH_CHECK();
@@ -1077,6 +1145,29 @@ static int launch_cfg(const GemmArgs& g, int splits, hipStream_t st) {
     return 0;
 }
 
+template <int MODE, int BM, int BN, int BK, int EPI, int WGM = 2, int WGN = 2, int SHORTK = 0>
+static int launch_cfg_pair(const GemmArgs& g, const GemmSeg1& s1, int splits, hipStream_t st) {
+    const int gy0 = (g.M + BM - 1) / BM;
+    dim3 grid((g.N + BN - 1) / BN, 2 * gy0, splits);
+    constexpr size_t lds = Smem<MODE, BM, BN, BK>::TOTAL * sizeof(float);
+    GF_TRY((lds_optin<gemm_pair_kernel<MODE, BM, BN, BK, EPI, WGM, WGN, SHORTK>>(lds, "gemm")));
+    hipLaunchKernelGGL((gemm_pair_kernel<MODE, BM, BN, BK, EPI, WGM, WGN, SHORTK>), grid, dim3(64 * WGM * WGN), lds, st, g, s1, gy0);
+    GF_LAUNCH_CHECK();
+    return 0;
+}
+
+// the two-segment launch of the kernel launch_pick takes for one segment's shape
+template <int EPI>
+static int launch_pick_pair(const GemmArgs& g, const GemmSeg1& s1, int splits, hipStream_t st) {
+    if (g.K == 100 && g.N >= 1024 && splits == 1 && (g.lda & 3) == 0 && (g.ldb & 3) == 0 &&
+        (size_t)g.M * g.lda * 4 < (size_t(1) << 31) && (size_t)g.M * g.ldc * 4 < (size_t(1) << 31)) {
+        if constexpr (EPI == EPI_RELU_DROP) return launch_wres<MODE_NT, EPI, true>(g, st, &s1);
+        else return fail(-1, "gemm_nt_pair: no two-segment form of the weight-resident kernel for epilogue %d", EPI);
+    }
+    if (g.K <= 128) return launch_cfg_pair<MODE_NT, 64, 64, 16, EPI, 2, 2, 1>(g, s1, splits, st);
+    return launch_cfg_pair<MODE_NT, 64, 64, 16, EPI>(g, s1, splits, st);
+}
+
 template <int MODE, int EPI>
 static int launch_pick(const GemmArgs& g, int splits, hipStream_t st) {
     // measured on MI355X (tools/gemm_bench.py, M = 3008 / 6016, N = 100 .. 2048, K = 100 .. 2048): with the
@@ -1147,6 +1238,23 @@ int launch_gemm_nt(const float* A, int lda, const float* W, int ldw, float* C, i
     set_split(g, splits, slab_stride);
     if (splits_io) *splits_io = splits;
     EPI_SWITCH(MODE_NT, g, st)
+}
+
+// launch_gemm_nt for two row segments [M x K] against the same weight in one launch (plain / split-K product and linear1's
+// epilogue): segment 0 as given, segment 1 with s1's operands; the same kernel, K split and slab layout as for one segment
+int launch_gemm_nt_pair(const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N, int K, int epi,
+                        const EpiArgs& ea, const GemmSeg1& s1, hipStream_t st, int* splits_io, long slab_stride) {
+    GF_CHECK_ARG(epi == EPI_RELU_DROP || epi == EPI_NONE, "gemm_nt_pair: epilogue %d has no two-segment form", epi);
+    GF_TRY(check_common(A, lda, W, ldw, C, M, N, K));
+    GF_CHECK_ARG(s1.A && s1.C && aligned16(s1.A) && ea.aux_in == nullptr, "gemm_nt_pair: bad second segment");
+    GF_CHECK_ARG((K & 3) == 0, "gemm_nt: K=%d must be a multiple of 4", K);
+    GF_CHECK_ARG(fits32(M, lda) && fits32(N, ldw), "gemm_nt: an operand of 4 GiB or more is not supported");
+    GemmArgs g{A, lda, W, ldw, C, ldc, nullptr, M, N, K, K, 0, ea};
+    int splits = (splits_io && epi == EPI_NONE) ? *splits_io : 1;
+    set_split(g, splits, slab_stride);
+    if (splits_io) *splits_io = splits;
+    if (epi == EPI_RELU_DROP) return launch_pick_pair<EPI_RELU_DROP>(g, s1, 1, st);
+    return launch_pick_pair<EPI_NONE>(g, s1, splits, st);
 }
 
 int launch_gemm_nn(const float* A, int lda, const float* Bm, int ldb, float* C, int ldc, int M, int N, int K,

@@ -50,8 +50,9 @@ struct N100Args {
 // that is three quarters padding (32 cycles): block b = 4 g + c / 4 holds (tokens 4 (c / 4) .. + 3) x (features 96 .. 99) for
 // the k values of lane group g — exactly what lane (c, g) already supplies as the token operand — so a 16-wide k group costs
 // 24 x 32 + 4 x 8 = 800 MFMA cycles instead of 896; the four lane groups' partial sums meet in the epilogue (two shuffles).
+// (bx: the workgroup's 64-token tile — blockIdx.x, or its index inside its own segment in a two-segment launch)
 template <bool WKMAJOR, int KW, bool TAIL4>
-__global__ __launch_bounds__(256 * KW) void gemm_n100_kernel(N100Args a) {
+__device__ __forceinline__ void gemm_n100_body(const N100Args& a, const int bx) {
     static_assert(KW == 1 || KW == 2, "one or two waves per token group along K");
     constexpr int NTHR = 256 * KW;
     constexpr int WT = WKMAJOR ? NBK * LDWK : 112 * NBK;          // weight tile floats
@@ -61,7 +62,7 @@ __global__ __launch_bounds__(256 * KW) void gemm_n100_kernel(N100Args a) {
     static_assert(KW == 1 || 2 * STAGE >= NBM * 116, "the K-half exchange image [64 tokens][116] re-uses the stage buffers");
     const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, g = lane >> 4;
     const int wave = (tid >> 6) & 3, khalf = tid >> 8;             // token group of 16; which 16-wide half of a K tile (KW == 2)
-    const int m0 = blockIdx.x * NBM, z = blockIdx.y;
+    const int m0 = bx * NBM, z = blockIdx.y;
     const int kbeg = z * a.kchunk, kend = min(a.K, kbeg + a.kchunk);
     const int nt = (kend - kbeg) / NBK;                           // K, kchunk multiples of 32
     GF_LAB_ONLY(unsigned long long* const stamp = (a.stamps && tid == 0) ? a.stamps + 5 * (size_t)(blockIdx.y * gridDim.x + blockIdx.x) : nullptr;
@@ -248,6 +249,26 @@ __global__ __launch_bounds__(256 * KW) void gemm_n100_kernel(N100Args a) {
     GF_LAB_ONLY(if (stamp) stamp[4] = __builtin_amdgcn_s_memtime();)
 }
 
+template <bool WKMAJOR, int KW, bool TAIL4>
+__global__ __launch_bounds__(256 * KW) void gemm_n100_kernel(N100Args a) {
+    gemm_n100_body<WKMAJOR, KW, TAIL4>(a, blockIdx.x);
+}
+
+// Two row segments with the same weight in one launch: token tiles 0 .. tiles0 - 1 are segment 0 (A, C as given), the rest
+// segment 1 (A1, C1; same T, same leading dimensions and slab stride).  Wave-uniform choice, made once; tiles and the clamp at
+// the last row are local to the segment, so each segment gets the bits of its own launch.
+template <bool WKMAJOR, int KW, bool TAIL4>
+__global__ __launch_bounds__(256 * KW) void gemm_n100_pair_kernel(N100Args a, const float* A1, float* C1, int tiles0) {
+    int bx = blockIdx.x;
+    if (bx >= tiles0) {
+        bx -= tiles0;
+        a.A = A1;
+        a.C = C1;
+    }
+    GF_LAB_ONLY(a.stamps = nullptr;)
+    gemm_n100_body<WKMAJOR, KW, TAIL4>(a, bx);
+}
+
 }  // namespace
 
 // lab knobs of the mode word (common.h `Mode`): bits 8..15 force the K-chunk count, bit 23 = features 96..99 on a padded seventh
@@ -293,8 +314,9 @@ static int n100_kw(int T, int splits) {
 
 // C slabs = A[T x K] . W^T (w_kmajor == 0: W [100 x K]) or A . W (w_kmajor == 1: W [K x 100]); *splits_io: in = cap, out = slabs written
 int launch_gemm_n100(const float* A, int lda, const float* W, int ldw, int w_kmajor, const float* bias, float* C, long slab_stride,
-                     int T, int K, int* splits_io, hipStream_t st) {
+                     int T, int K, int* splits_io, hipStream_t st, const float* A1, float* C1) {
     GF_CHECK_ARG(A && W && C && splits_io && T > 0 && n100_supported(NE, K), "gemm_n100: bad arguments (K=%d)", K);
+    GF_CHECK_ARG((A1 == nullptr) == (C1 == nullptr) && aligned16(A1) && aligned16(C1), "gemm_n100: bad second segment");
     GF_CHECK_ARG(aligned16(A) && aligned16(W) && aligned16(C) && (lda & 3) == 0 && (ldw & 3) == 0 && (slab_stride & 3) == 0 &&
                      (!bias || aligned16(bias)), "gemm_n100: operands must be 16-byte aligned");
     GF_CHECK_ARG((unsigned long long)T * (unsigned long long)lda * 4ull < (1ull << 32) &&
@@ -309,7 +331,12 @@ int launch_gemm_n100(const float* A, int lda, const float* W, int ldw, int w_kma
     const dim3 grid((T + NBM - 1) / NBM, s);
     const Mode md = mode();
     const int kw = md.n100_force_kw() ? md.n100_force_kw() : n100_kw(T, s);
-    if (kw == 2 && !md.n100_pad7()) {
+    if (A1) {
+        // second segment: the product form only (eight waves, 4x4x1 tail, weight as rows of K); the chunk count above is the
+        // single-segment launch's (T, not 2 T: the slab order is part of the result)
+        GF_CHECK_ARG(kw == 2 && !md.n100_pad7() && !w_kmajor, "gemm_n100: no two-segment form of this variant");
+        hipLaunchKernelGGL((gemm_n100_pair_kernel<false, 2, true>), dim3(2 * grid.x, s), dim3(512), 0, st, a, A1, C1, (int)grid.x);
+    } else if (kw == 2 && !md.n100_pad7()) {
         if (w_kmajor) hipLaunchKernelGGL((gemm_n100_kernel<true, 2, true>), grid, dim3(512), 0, st, a);
         else hipLaunchKernelGGL((gemm_n100_kernel<false, 2, true>), grid, dim3(512), 0, st, a);
     } else if (kw == 2) {

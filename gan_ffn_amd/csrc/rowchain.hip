@@ -133,13 +133,14 @@ struct RcFwdArgs {
 };
 
 // z = x + dropout(y); out = LayerNorm(z); optionally the next layer's in-proj on the fresh rows
+// (bid: the workgroup's 16-row tile — blockIdx.x, or its index inside its own segment in a two-segment launch)
 template <int PRE, bool POST_GEMM>
-__global__ __launch_bounds__(256) void rc_fwd_kernel(RcFwdArgs a) {
+__device__ __forceinline__ void rc_fwd_body(const RcFwdArgs& a, const int bid) {
     constexpr int NP = 3 * RE, PT = (NP + 15) / 16;     // in-proj: 300 output features, 19 tiles
     __shared__ __attribute__((aligned(16))) float red[2 * 64];
     __shared__ __attribute__((aligned(16))) float xs[POST_GEMM ? 16 * LDX : 4];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, g = lane >> 4, ql = c & 3;
-    const int t0 = blockIdx.x * 16, T = a.T;
+    const int t0 = bid * 16, T = a.T;
     const bool tok = t0 + c < T;
     const size_t trow = (size_t)min(t0 + c, T - 1);
     const DropCtx dc = make_drop(a.rng, a.add, a.site, a.p, a.train);
@@ -298,6 +299,26 @@ __global__ __launch_bounds__(256) void rc_fwd_kernel(RcFwdArgs a) {
                     make_float4(r4[0] + pb[j].x, r4[1] + pb[j].y, r4[2] + pb[j].z, r4[3] + pb[j].w);
         }
     }
+}
+
+template <int PRE, bool POST_GEMM>
+__global__ __launch_bounds__(256) void rc_fwd_kernel(RcFwdArgs a) {
+    rc_fwd_body<PRE, POST_GEMM>(a, blockIdx.x);
+}
+
+// Two row segments in one launch (the eval-mode and the train-mode pass of one generator over the same input: same weights,
+// same T): workgroups 0 .. nb0 - 1 run segment 0 = `a` as given, the rest segment 1 = `a` with the per-segment operands of s1.
+// The choice is wave-uniform and made once; from there a workgroup is a workgroup of the single-segment launch — tiles,
+// Philox row groups and the clamps at the last row are local to its segment, so both segments get the single launch's bits.
+template <int PRE, bool POST_GEMM>
+__global__ __launch_bounds__(256) void rc_fwd_pair_kernel(RcFwdArgs a, RcFwdSeg1 s1, int nb0) {
+    int bid = blockIdx.x;
+    if (bid >= nb0) {
+        bid -= nb0;
+        a.pre_a = s1.pre_a; a.y = s1.y; a.x = s1.x; a.out = s1.out; a.xhat = s1.xhat; a.rstd = s1.rstd; a.post_out = s1.post_out;
+        a.train = s1.train;
+    }
+    rc_fwd_body<PRE, POST_GEMM>(a, bid);
 }
 
 struct RcBwdArgs {
@@ -536,14 +557,17 @@ int launch_rc_pack(const float* params, long layer_stride, long off_in, long off
 // forward A: x1 = LayerNorm1(x + dropout(attn_o . Wo^T + bo))
 int launch_rc_outproj_ln_fwd(const float* attn_o, const float* wo, const float* bo, const float* x, const float* gamma,
                              const float* beta, float* out, float* xhat, float* rstd, int T, float eps, float p, uint32_t site,
-                             const uint64_t* rng, uint64_t add, int train, hipStream_t st) {
+                             const uint64_t* rng, uint64_t add, int train, hipStream_t st, const RcFwdSeg1* s1) {
     GF_CHECK_ARG(attn_o && wo && bo && x && gamma && beta && out && T > 0, "rc_outproj_ln_fwd: bad arguments");
+    GF_CHECK_ARG(!s1 || (s1->pre_a && s1->x && s1->out && aligned16(s1->pre_a) && aligned16(s1->x) && aligned16(s1->out) &&
+                         (!s1->xhat || aligned16(s1->xhat))), "rc_outproj_ln_fwd: bad second segment");
     GF_CHECK_ARG(aligned16(attn_o) && aligned16(wo) && aligned16(bo) && aligned16(x) && aligned16(gamma) && aligned16(beta) &&
                      aligned16(out) && (!xhat || aligned16(xhat)), "rc_outproj_ln_fwd: operands must be 16-byte aligned");
     RcFwdArgs a{};
     a.pre_a = attn_o; a.pre_w = wo; a.pre_b = bo; a.x = x; a.gamma = gamma; a.beta = beta; a.out = out; a.xhat = xhat; a.rstd = rstd;
     a.T = T; a.eps = eps; a.p = p; a.site = site; a.rng = rng; a.add = add; a.train = train;
-    hipLaunchKernelGGL((rc_fwd_kernel<1, false>), dim3(rc_blocks(T)), dim3(256), 0, st, a);
+    if (s1) hipLaunchKernelGGL((rc_fwd_pair_kernel<1, false>), dim3(2 * rc_blocks(T)), dim3(256), 0, st, a, *s1, rc_blocks(T));
+    else hipLaunchKernelGGL((rc_fwd_kernel<1, false>), dim3(rc_blocks(T)), dim3(256), 0, st, a);
     GF_LAUNCH_CHECK();
     return 0;
 }
@@ -551,8 +575,12 @@ int launch_rc_outproj_ln_fwd(const float* attn_o, const float* wo, const float* 
 // forward B: out = LayerNorm2(x + dropout(sum of slabs)); with w_in: qkv = out . w_in^T + b_in (the next layer's in-proj)
 int launch_rc_ln_inproj_fwd(const float* y, int nslab, long slab_stride, const float* x, const float* gamma, const float* beta,
                             float* out, float* xhat, float* rstd, const float* w_in, const float* b_in, float* qkv, int T,
-                            float eps, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train, hipStream_t st) {
+                            float eps, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train, hipStream_t st,
+                            const RcFwdSeg1* s1) {
     GF_CHECK_ARG(y && x && gamma && beta && out && T > 0 && nslab >= 1, "rc_ln_inproj_fwd: bad arguments");
+    GF_CHECK_ARG(!s1 || (s1->y && s1->x && s1->out && aligned16(s1->y) && aligned16(s1->x) && aligned16(s1->out) &&
+                         (!s1->xhat || aligned16(s1->xhat)) && (!w_in || (s1->post_out && aligned16(s1->post_out)))),
+                 "rc_ln_inproj_fwd: bad second segment");
     GF_CHECK_ARG(aligned16(y) && (slab_stride & 3) == 0 && aligned16(x) && aligned16(gamma) && aligned16(beta) && aligned16(out) &&
                      (!xhat || aligned16(xhat)), "rc_ln_inproj_fwd: operands must be 16-byte aligned");
     GF_CHECK_ARG(!w_in || (b_in && qkv && aligned16(w_in) && aligned16(b_in) && aligned16(qkv)),
@@ -561,22 +589,28 @@ int launch_rc_ln_inproj_fwd(const float* y, int nslab, long slab_stride, const f
     a.y = y; a.nslab = nslab; a.slab_stride = slab_stride; a.x = x; a.gamma = gamma; a.beta = beta; a.out = out; a.xhat = xhat;
     a.rstd = rstd; a.post_w = w_in; a.post_b = b_in; a.post_out = qkv;
     a.T = T; a.eps = eps; a.p = p; a.site = site; a.rng = rng; a.add = add; a.train = train;
-    if (w_in) hipLaunchKernelGGL((rc_fwd_kernel<0, true>), dim3(rc_blocks(T)), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((rc_fwd_kernel<0, false>), dim3(rc_blocks(T)), dim3(256), 0, st, a);
+    const int nb = rc_blocks(T);
+    if (s1 && w_in) hipLaunchKernelGGL((rc_fwd_pair_kernel<0, true>), dim3(2 * nb), dim3(256), 0, st, a, *s1, nb);
+    else if (s1) hipLaunchKernelGGL((rc_fwd_pair_kernel<0, false>), dim3(2 * nb), dim3(256), 0, st, a, *s1, nb);
+    else if (w_in) hipLaunchKernelGGL((rc_fwd_kernel<0, true>), dim3(nb), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((rc_fwd_kernel<0, false>), dim3(nb), dim3(256), 0, st, a);
     GF_LAUNCH_CHECK();
     return 0;
 }
 
 // forward 0: x0 = dropout(x_in + pe[s]) and qkv of layer 0 = x0 . w_in^T + b_in — the head of an encoder stack as one launch
 int launch_rc_pe_inproj_fwd(const float* x_in, const float* pe, float* out, const float* w_in, const float* b_in, float* qkv, int T,
-                            int B, float p, const uint64_t* rng, uint64_t add, int train, hipStream_t st) {
+                            int B, float p, const uint64_t* rng, uint64_t add, int train, hipStream_t st, const RcFwdSeg1* s1) {
     GF_CHECK_ARG(x_in && pe && out && w_in && b_in && qkv && T > 0 && B > 0, "rc_pe_inproj_fwd: bad arguments");
+    GF_CHECK_ARG(!s1 || (s1->y && s1->x && s1->out && s1->post_out && aligned16(s1->y) && aligned16(s1->x) && aligned16(s1->out) &&
+                         aligned16(s1->post_out)), "rc_pe_inproj_fwd: bad second segment");
     GF_CHECK_ARG(aligned16(x_in) && aligned16(pe) && aligned16(out) && aligned16(w_in) && aligned16(b_in) && aligned16(qkv),
                  "rc_pe_inproj_fwd: operands must be 16-byte aligned");
     RcFwdArgs a{};
     a.y = pe; a.x = x_in; a.out = out; a.post_w = w_in; a.post_b = b_in; a.post_out = qkv;
     a.T = T; a.B = B; a.p = p; a.site = SITE_PE; a.rng = rng; a.add = add; a.train = train;
-    hipLaunchKernelGGL((rc_fwd_kernel<2, true>), dim3(rc_blocks(T)), dim3(256), 0, st, a);
+    if (s1) hipLaunchKernelGGL((rc_fwd_pair_kernel<2, true>), dim3(2 * rc_blocks(T)), dim3(256), 0, st, a, *s1, rc_blocks(T));
+    else hipLaunchKernelGGL((rc_fwd_kernel<2, true>), dim3(rc_blocks(T)), dim3(256), 0, st, a);
     GF_LAUNCH_CHECK();
     return 0;
 }

@@ -217,6 +217,8 @@ class _Pass:
         self._out = torch.empty(Tc * (net.D2 if net.kind == 0 else 1), **f32)
         self._dx = torch.empty(Tc * E, **f32) if need_bwd else None
         self.n_ws = max(n_ws, h_ws)          # at capacity: workspace needs grow with S
+        if ops.encoder_fwd_pair_supported(cfg):
+            self.n_ws = max(self.n_ws, ops.encoder_fwd_pair_workspace_floats(cfg))
         self.resize(S)
 
     def resize(self, S, B=None):
@@ -228,6 +230,7 @@ class _Pass:
         self.S, self.T = S, S * B
         self.cfg_train = ops.enc_cfg(S, B, E, net.H, net.L, train=True, p_pe=net.p_pe, p_enc=net.p_enc)
         self.cfg_eval = ops.enc_cfg(S, B, E, net.H, net.L, train=False, p_pe=net.p_pe, p_enc=net.p_enc)
+        self.pair_ok = ops.encoder_fwd_pair_supported(self.cfg_train)     # eval + train forward as one two-segment pass
         n_saved, _ = ops.enc_sizes(self.cfg_train)
         self.hcfg_train = HeadCfg(self.T, E, net.D1, net.D2, net.kind, net.p_head, 1)
         self.hcfg_eval = HeadCfg(self.T, E, net.D1, net.D2, net.kind, net.p_head, 0)
@@ -261,6 +264,21 @@ STREAM_MAP = {1: [0] * 12,
 ADDS_PER_SUBSTEP = 4     # dropout-bearing launches of one sub-step (two encoder passes and two heads)
 SCHEDULE_BIMODAL = [s for s in SCHEDULE if "visual" not in s[1:]]
 STREAM_MAP_BIMODAL = {1: [0, 0, 0, 0], 2: [0, 0, 1, 1]}
+
+
+# Widths up to this stay unpaired by default (GANFFN_GEN_PAIR=all pairs them too): the d_model-100 generators' sub-steps are not
+# on the iteration's longest chain, and their paired launches measured slower in the three-stream step (DESIGN.md section 6,
+# profiles/gen_pair_ab.txt); the 512-wide generator's chain is the longest, and its pairing shortens it.
+GEN_PAIR_MAX_UNPAIRED_E = 128
+
+
+def find_gen_pairs(schedule, stream_map):
+    """sub-steps i whose generator forward can carry the next sub-step's: i = (D, ., p) runs generator p in eval mode on
+    batch[p], i + 1 = (G, p, .) runs it in train mode on the same input, and only a discriminator is updated in between, so
+    both passes see the same parameters.  Both sub-steps must be on the same stream.  -> sorted list of such i"""
+    return [i for i in range(len(schedule) - 1)
+            if schedule[i][0] == "D" and schedule[i + 1][0] == "G" and schedule[i + 1][1] == schedule[i][2]
+            and stream_map[i] == stream_map[i + 1]]
 
 
 _STREAMS = {}
@@ -300,6 +318,9 @@ class _Runner:
     runners over generators derive from.)"""
     n_streams = 1
     early_gen = False
+    gen_pair = False
+    gen_pair_mode = "0"
+    _gen_pairs = frozenset()
     _cur_stream = None
     _base_add = 0
     _adds = 0
@@ -360,6 +381,15 @@ class GanEngine(_Runner):
         if os.environ.get("GANFFN_STREAM_MAP"):
             self.stream_map = [int(x) for x in os.environ["GANFFN_STREAM_MAP"].split(",")]
             assert len(self.stream_map) == len(self.schedule) and max(self.stream_map) < self.n_streams
+        # eval + train generator forward of a (D, G) sub-step pair as one two-segment pass (ganffn_encoder_fwd_pair): on unless
+        # GANFFN_GEN_PAIR=0, or the early generator forward (which issues the same pass elsewhere) is asked for.
+        # GANFFN_GEN_PAIR=all pairs every stack that has a pair pass, 1 those that gained from it (_pair_slot).  Unset: 1 in the
+        # multi-stream runner (the product's and the benchmark's mode, where the gain was measured), 0 on one stream — there
+        # every sub-step issues its own generator forward with its own offsets, the launch sequence the fp64 train-step oracle
+        # test walks sub-step by sub-step (tests/test_hip_engine_train_oracle.py); ask for 1 or all to pair there too
+        self.gen_pair_mode = os.environ.get("GANFFN_GEN_PAIR") or ("1" if self.n_streams > 1 else "0")
+        self.gen_pair = self.gen_pair_mode != "0" and os.environ.get("GANFFN_EARLY_GEN", "0") != "1"
+        self._gen_pairs = frozenset(find_gen_pairs(self.schedule, self.stream_map))
         self.streams = None
         self._res = {}
         self._base_add = 0
@@ -691,8 +721,33 @@ class GanEngine(_Runner):
         return cb, finish_and_step
 
     # ------------------------------------------------------------------------------------------
-    def train_disc(self, who, partner, batch, loss_slot):
-        """train_IEMOCAP.py:200-227."""
+    def _gen_pair_fwd(self, net, ps_eval, ps_train, x, adds_eval, adds_train):
+        """the eval-mode forward (into ps_eval, nothing saved) and the train-mode forward (into ps_train, saved) of one
+        generator over x: one two-segment encoder pass, then the two heads; -> the train pass's (enc_add, head_add)"""
+        a0, a1 = self._base_add + adds_train[0], self._base_add + adds_train[1]
+        ops.encoder_fwd_pair_raw(ps_train.cfg_train, x, net.pe, net.slab, ps_eval.enc_out, ps_train.enc_out, ps_train.saved,
+                                 self.ws, self.rng.state, a0)
+        w = net.w
+        w3 = w("fc3.weight") if net.kind == 1 else None
+        b3 = w("fc3.bias") if net.kind == 1 else None
+        for hcfg, ps, add in ((ps_eval.hcfg_eval, ps_eval, self._base_add + adds_eval[1]), (ps_train.hcfg_train, ps_train, a1)):
+            ops.head_fwd_raw(hcfg, ps.enc_out, w("fc1.weight"), w("fc1.bias"), w("fc2.weight"), w("fc2.bias"), w3, b3,
+                             ps.out, ps.hsaved, self.ws, self.rng.state, add)
+        return a0, a1
+
+    def _pair_slot(self, i):
+        """the sub-step whose train-mode generator forward sub-step i (a discriminator step) issues with its own eval-mode
+        one, or None"""
+        if not self.gen_pair or i not in self._gen_pairs:
+            return None
+        ps = self.pass_G[self.schedule[i][2]]
+        if not ps.pair_ok or (self.gen_pair_mode != "all" and ps.net.E <= GEN_PAIR_MAX_UNPAIRED_E):
+            return None
+        return i + 1
+
+    def train_disc(self, who, partner, batch, loss_slot, pair_slot=None):
+        """train_IEMOCAP.py:200-227.  pair_slot: the next sub-step trains `partner` on the same input — its train-mode forward
+        is issued here, in the launches of the eval-mode one, with that sub-step's dropout offsets; -> its g_adds (else None)"""
         S, B = batch[who].shape[:2]
         Dn, Gn = self.D[who], self.G[partner]
         pg_, pd = self.pass_G_nosave[partner], self.pass_D2[who]
@@ -700,7 +755,12 @@ class GanEngine(_Runner):
         # they do not depend on the order in which streams issue their launches
         a = ADDS_PER_SUBSTEP * loss_slot
         # fusion = G(real_gen) in eval mode, nothing saved (detach(), :218-219)
-        self._net_fwd(Gn, pg_, batch[partner], train=False, save=False, adds=(a, a + 1))
+        g_adds = None
+        if pair_slot is not None:
+            ap = ADDS_PER_SUBSTEP * pair_slot
+            g_adds = self._gen_pair_fwd(Gn, pg_, self.pass_G[partner], batch[partner], (a, a + 1), (ap, ap + 1))
+        else:
+            self._net_fwd(Gn, pg_, batch[partner], train=False, save=False, adds=(a, a + 1))
         # real input of D_m is raw modality m; VisualDiscriminator maps 512 -> 100 first (model.py:1355-1356)
         x_real = batch[who]
         if Dn.has_obj:
@@ -726,6 +786,7 @@ class GanEngine(_Runner):
             if cb is not None:
                 cb(Dn.enc_floats, Dn.enc_floats + Dn.obj_floats, last=True)
         finish(("D", who), parts)
+        return g_adds
 
     def train_gen_forward(self, who, batch, loss_slot):
         """the generator's own forward of train_gen (train mode, saved for backward): it reads nothing but the generator's
@@ -769,8 +830,17 @@ class GanEngine(_Runner):
             self._base_add = self.rng.next_add(ADDS_PER_SUBSTEP * len(self.schedule))
         self._adds = ADDS_PER_SUBSTEP * len(self.schedule)       # (offsets are assigned by sub-step: train_disc / train_gen)
         if self.n_streams == 1:
+            paired = {}                  # sub-step -> (enc_add, head_add) of its generator forward, issued by the sub-step before
             for i, (kind, who, partner) in enumerate(self.schedule):
-                (self.train_disc if kind == "D" else self.train_gen)(who, partner, batch, i)
+                j = self._pair_slot(i) if kind == "D" else None
+                if j is not None:
+                    paired[j] = self.train_disc(who, partner, batch, i, pair_slot=j)
+                elif kind == "D":
+                    self.train_disc(who, partner, batch, i)
+                elif i in paired:
+                    self.train_gen(who, partner, batch, i, g_adds=paired[i])
+                else:
+                    self.train_gen(who, partner, batch, i)
         else:
             origin = torch.cuda.current_stream()
             fork = torch.cuda.Event()
@@ -813,8 +883,11 @@ class GanEngine(_Runner):
                 trained = (kind, who)
                 other = ("G" if kind == "D" else "D", partner)
                 # pass buffers are resources too (same (net, role) buffer reused by a later sub-step)
+                pj = self._pair_slot(i) if kind == "D" else None
                 if kind == "D":
                     bufs = [("buf", "G_nosave", partner), ("buf", "D2", who)]
+                    if pj is not None:
+                        bufs.append(("buf", "G", partner))      # the paired pass writes the next sub-step's generator buffers
                 else:
                     bufs = [("buf", "G", who), ("buf", "D1", partner)]
                 self._use_scratch(smap[i])
@@ -824,7 +897,9 @@ class GanEngine(_Runner):
                     self._wait_writers(st, [trained, other] + bufs)
                     self._wait_readers(st, bufs)
                     if kind == "D":
-                        self.train_disc(who, partner, batch, i)
+                        g_adds = self.train_disc(who, partner, batch, i, pair_slot=pj)
+                        if pj is not None:
+                            early[pj] = g_adds
                     else:
                         self.train_gen(who, partner, batch, i, g_adds=early.get(i))
                     self._done(st, reads=[other], writes=[trained] + bufs)

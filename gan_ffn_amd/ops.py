@@ -138,6 +138,25 @@ def encoder_fwd_raw(cfg, x, pe, slab, out, saved, ws, rng, add):
               _ptr(rng), C.c_uint64(add), _stream())
 
 
+def encoder_fwd_pair_supported(cfg):
+    """can the eval-mode and the train-mode forward of this configuration share their launches (ganffn_encoder_fwd_pair)?"""
+    return int(_lib.load().ganffn_encoder_fwd_pair_supported(C.byref(cfg))) == 1
+
+
+def encoder_fwd_pair_workspace_floats(cfg):
+    w = int(_lib.load().ganffn_encoder_fwd_pair_workspace_floats(C.byref(cfg)))
+    if w < 0:
+        _lib.check(-1, "ganffn_encoder_fwd_pair_workspace_floats")
+    return w
+
+
+def encoder_fwd_pair_raw(cfg, x, pe, slab, out_eval, out_train, saved_train, ws, rng, add_train):
+    """cfg: the train-mode cfg.  out_eval = the eval-mode forward of x (nothing kept), out_train / saved_train = the
+    train-mode forward with its saved set — one pass, the bits of the two encoder_fwd_raw calls."""
+    _lib.call("ganffn_encoder_fwd_pair", C.byref(cfg), _ptr(x), _ptr(pe), _ptr(slab), _ptr(out_eval), _ptr(out_train),
+              _ptr(saved_train), _ptr(ws), _ptr(rng), C.c_uint64(add_train), _stream())
+
+
 def encoder_bwd_raw(cfg, lo, hi, dx, slab, gslab, saved, ws, rng, add, need_dx_in=True):
     """need_dx_in=False: the stack's input needs no gradient — with lo == 0 the bottom in-proj dgrad and the PE dropout
     backward are skipped (as autograd skips them) and dx is undefined afterwards."""

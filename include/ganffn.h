@@ -112,6 +112,20 @@ int ganffn_encoder_fwd(const ganffn_enc_cfg* cfg, const float* x_in, const float
                        const float* params, float* out, float* saved, float* workspace,
                        const uint64_t* rng, uint64_t rng_offset_add, void* stream);
 
+/* The eval-mode and the train-mode forward of ONE stack over the SAME input as one pass over two row segments (the GAN
+ * schedule runs a generator in eval mode in a discriminator sub-step and in train mode, on the same batch with the same
+ * parameters, in the sub-step after it).  cfg is the train-mode cfg; segment 0 runs it with train = 0 and keeps nothing
+ * (out_eval), segment 1 runs it as given (out_train, saved_train: what ganffn_encoder_fwd would save).  Every launch covers
+ * both segments; each output has the bits of the corresponding ganffn_encoder_fwd call (eval: saved = NULL; train: the same
+ * rng_offset_add).  workspace: ganffn_encoder_fwd_pair_workspace_floats floats.  _supported: 1 when every kernel on the
+ * stack's path has a two-segment form (today: every valid cfg, unless the debug mode word selects a lab variant of the
+ * 2048 -> 100 product), else 0 — ganffn_encoder_fwd_pair then fails and the caller issues the two passes itself. */
+int ganffn_encoder_fwd_pair_supported(const ganffn_enc_cfg* cfg);
+int64_t ganffn_encoder_fwd_pair_workspace_floats(const ganffn_enc_cfg* cfg);
+int ganffn_encoder_fwd_pair(const ganffn_enc_cfg* cfg, const float* x_in, const float* pe, const float* params,
+                            float* out_eval, float* out_train, float* saved_train, float* workspace,
+                            const uint64_t* rng, uint64_t rng_offset_add_train, void* stream);
+
 /* Backward through layers [layer_lo, layer_hi) in reverse order.  dx [T x E] is in/out: on entry
  * dL/d(output of layer layer_hi-1), on exit dL/d(input of layer layer_lo); when layer_lo == 0 the
  * PE dropout backward is applied too, so dx is then dL/d(x_in).  grads (same layout as params)

@@ -1,0 +1,142 @@
+"""The eval-mode and the train-mode forward of one generator as ONE two-segment encoder pass (ganffn_encoder_fwd_pair) against
+the two ganffn_encoder_fwd calls it replaces, and GanEngine with the pairing on against GANFFN_GEN_PAIR=0 — bit for bit."""
+import pytest
+import torch
+
+from test_hip_engine import build_all, gan_batch
+
+pytestmark = pytest.mark.gpu
+
+# (S, B): T = 14 is no multiple of 4 (a Philox row group of a joint [2 T] matrix would straddle the segments), 36 is a
+# multiple of 4 but not of 16 (the row chain's tile), 64 is tile-aligned, 282 is the workload's S with every key tile in use
+SHAPES = [(7, 2), (9, 4), (16, 4), (94, 3)]
+# (E, H), L = 2: "LayerNorm2 carries the next in-proj" and the last-layer path both run.  (120, 4): 30-wide heads on the generic
+# GEMM path (the 16-row attention kernels' third head shape)
+WIDTHS = [(100, 10), (512, 8), (120, 4)]
+
+
+def _case(S, B, E, H, L=2):
+    from gan_ffn_amd import ops
+    g = torch.Generator().manual_seed(1000 * S + 10 * B + E)
+    cfg = ops.enc_cfg(S, B, E, H, L, train=True)
+    cfg_eval = ops.enc_cfg(S, B, E, H, L, train=False)
+    per, _ = ops.layer_layout(E)
+    params = ((torch.rand(L * per, generator=g) - 0.5) * 0.2).cuda()
+    x = torch.rand(S, B, E, generator=g).cuda()
+    pe = torch.rand(S, E, generator=g).cuda()
+    return cfg, cfg_eval, params, x, pe
+
+
+@pytest.mark.parametrize("E,H", WIDTHS)
+@pytest.mark.parametrize("S,B", SHAPES)
+def test_pair_pass_equals_the_two_single_passes(S, B, E, H):
+    from gan_ffn_amd import ops
+    cfg, cfg_eval, params, x, pe = _case(S, B, E, H)
+    n_saved, n_ws = ops.enc_sizes(cfg)
+    ops.manual_seed(4321)
+    rng, add = ops.DeviceRng.get("cuda").state, 17
+    f32 = dict(device="cuda", dtype=torch.float32)
+    # reference: eval unsaved, then train saved with the same offset; buffers start from the same fill on both sides, so the
+    # WHOLE saved buffer compares (words no launch writes included)
+    out_e, out_t = torch.zeros(S * B * E, **f32), torch.zeros(S * B * E, **f32)
+    saved = torch.full((n_saved,), -7.0, **f32)
+    ws = torch.zeros(n_ws, **f32)
+    ops.encoder_fwd_raw(cfg_eval, x, pe, params, out_e, None, ws, rng, add)
+    ops.encoder_fwd_raw(cfg, x, pe, params, out_t, saved, ws, rng, add)
+    assert ops.encoder_fwd_pair_supported(cfg)
+    p_e, p_t = torch.zeros(S * B * E, **f32), torch.zeros(S * B * E, **f32)
+    p_saved = torch.full((n_saved,), -7.0, **f32)
+    p_ws = torch.zeros(ops.encoder_fwd_pair_workspace_floats(cfg), **f32)
+    ops.encoder_fwd_pair_raw(cfg, x, pe, params, p_e, p_t, p_saved, p_ws, rng, add)
+    torch.cuda.synchronize()
+    assert torch.isfinite(out_e).all() and torch.isfinite(out_t).all() and not torch.equal(out_e, out_t)
+    assert torch.equal(p_e, out_e)
+    assert torch.equal(p_t, out_t)
+    assert torch.equal(p_saved.view(torch.int32), saved.view(torch.int32))
+
+
+def test_a_lab_variant_without_a_segment_form_is_reported_and_refused():
+    """every width has its segment forms (WIDTHS above: row chain + 16-row attention; generic GEMMs + 16-row attention at
+    S <= 48 / the 32-row kernel above; 30-wide heads) — only a lab variant of the 2048 -> 100 product selected through the debug
+    mode word has none: _supported answers 0 and the entry point fails instead of computing something else"""
+    from gan_ffn_amd import _lib, ops
+    S, B, E, H = 9, 4, 100, 10
+    cfg, _, params, x, pe = _case(S, B, E, H)
+    assert ops.encoder_fwd_pair_supported(cfg)
+    n_saved, n_ws = ops.enc_sizes(cfg)
+    f32 = dict(device="cuda", dtype=torch.float32)
+    out_e, out_t = torch.zeros(S * B * E, **f32), torch.zeros(S * B * E, **f32)
+    saved = torch.zeros(n_saved, **f32)
+    ws = torch.zeros(max(n_ws, ops.encoder_fwd_pair_workspace_floats(cfg)), **f32)
+    lib = _lib.load()
+    lib.ganffn_debug_set_ffn_mode(1 << 23)          # the padded seventh tile instead of the 4x4x1 tail
+    try:
+        assert not ops.encoder_fwd_pair_supported(cfg)
+        with pytest.raises(_lib.GanffnError):
+            ops.encoder_fwd_pair_raw(cfg, x, pe, params, out_e, out_t, saved, ws, ops.DeviceRng.get("cuda").state, 0)
+    finally:
+        lib.ganffn_debug_set_ffn_mode(0)
+    torch.cuda.synchronize()
+    assert not out_e.any() and not out_t.any() and not saved.any()
+
+
+def _run_engine(S, B, n_streams, use_graph, pair, monkeypatch, iters=2):
+    """pair: "all" = every (D, G) sub-step pair whose generator has a pair pass, "1" = those that gained from it, "0" = none,
+    None = GANFFN_GEN_PAIR unset: 1 in the multi-stream runner, 0 on one stream"""
+    from gan_ffn_amd import engine, ops
+    if pair is None:
+        monkeypatch.delenv("GANFFN_GEN_PAIR", raising=False)
+        pair = "1" if n_streams > 1 else "0"
+    else:
+        monkeypatch.setenv("GANFFN_GEN_PAIR", pair)
+    gens, discs = build_all(zero_dropout=False)
+    ops.manual_seed(99)
+    eng = engine.GanEngine(gens, discs, n_streams=n_streams, use_graph=use_graph)
+    assert eng.gen_pair == (pair != "0") and eng.gen_pair_mode == pair
+    batch = gan_batch(S=S, B=B)
+    losses = []
+    for _ in range(iters):
+        ls = eng.iteration(batch)
+        eng.synchronize()
+        losses.append(ls.clone())
+    torch.cuda.synchronize()
+    # every (D, G) sub-step pair of the reference schedule is on one stream and has a pair pass; by default the two of the
+    # 512-wide visual generator are taken (engine.GEN_PAIR_MAX_UNPAIRED_E)
+    paired = [i for i in range(12) if eng._pair_slot(i) is not None]
+    assert paired == {"all": [0, 2, 4, 6, 8, 10], "1": [8, 10], "0": []}[pair], paired
+    state = {}
+    for grp, nets in (("G", eng.G), ("D", eng.D)):
+        for k, st in nets.items():
+            for name in ("slab", "grad", "exp_avg", "exp_avg_sq"):
+                state[(grp, k, name)] = getattr(st, name).detach().clone()
+    return torch.stack(losses), state
+
+
+def _compare(a, b):
+    assert torch.isfinite(a[0]).all() and a[0].shape == (2, 12)
+    assert torch.equal(a[0], b[0]), (a[0] - b[0]).abs().max()
+    for k in a[1]:
+        assert torch.equal(a[1][k], b[1][k]), k
+
+
+@pytest.mark.parametrize("n_streams", [1, 3])
+@pytest.mark.parametrize("S,B", [(9, 4), (94, 4)])
+def test_engine_with_pairing_equals_engine_without(S, B, n_streams, monkeypatch):
+    on = _run_engine(S, B, n_streams, False, "all", monkeypatch)
+    off = _run_engine(S, B, n_streams, False, "0", monkeypatch)
+    _compare(on, off)
+
+
+def test_engine_with_default_pairing_equals_engine_without(monkeypatch):
+    on = _run_engine(9, 4, 3, False, None, monkeypatch)          # three streams, nothing set: the 512-wide generator's two pairs
+    off = _run_engine(9, 4, 3, False, "0", monkeypatch)
+    _compare(on, off)
+    one = _run_engine(9, 4, 1, False, "1", monkeypatch)          # the same choice asked for on one stream
+    _compare(one, _run_engine(9, 4, 1, False, None, monkeypatch))    # ... against one stream's default: unpaired
+    _compare(one, off)
+
+
+def test_engine_with_pairing_equals_engine_without_under_graph_replay(monkeypatch):
+    on = _run_engine(9, 4, 1, True, "all", monkeypatch)
+    off = _run_engine(9, 4, 1, True, "0", monkeypatch)
+    _compare(on, off)

@@ -84,20 +84,21 @@ def family_table(S, B):
     ffn100 = 2.0 * 100 * F                                         # one K = 100 <-> 2048 product, per token
     l5 = _layer512(T1)
     fams = []
+    # (the *_pair_kernel symbols are the two-segment launches of a paired eval + train generator forward: the same work)
     # generic 64 x 64-tile GEMM: every nn.Linear of the d_model-512 generator (forward + dgrad) and the generator heads /
     # `object` of all networks (the d_model-100 layers have their own kernels below)
     g_fwd = 4 * L * (l5["inp"] + l5["out"] + l5["l1"] + l5["l2"])
     g_bwd = 2 * L * (l5["out"] + l5["l1"] + l5["l2"]) + 2 * (L - 1) * l5["inp"]       # the bottom layer's in-proj dgrad is skipped
     heads = 4 * (2.0 * T1 * 512 * 1024 + 2.0 * T1 * 1024 * 100) + 2 * (2.0 * T1 * 100 * 1024 + 2.0 * T1 * 1024 * 512) \
         + (8 + 4) * (2.0 * T1 * 100 * 512 + 2.0 * T1 * 512 * 100) + 2 * 2.0 * T1 * 512 * 100
-    fams.append(dict(key="gemm_generic", bound="mfma", prefixes=["gemm_kernel<0", "gemm_kernel<1"], flops=g_fwd + g_bwd + heads,
+    fams.append(dict(key="gemm_generic", bound="mfma", prefixes=["gemm_kernel<0", "gemm_kernel<1", "gemm_pair_kernel<0"], flops=g_fwd + g_bwd + heads,
                      title="generic 64x64-tile GEMM (gemm_kernel<NT|NN,...>): the d_model-512 generator's in-proj / out-proj / "
                            "linear1 / linear2 forward and dgrad, generator heads, `object`"))
-    fams.append(dict(key="ffn_k100", bound="mfma", prefixes=["gemm_wres_kernel"], flops=ffn100 * L * (fwd100 + bwd100),
+    fams.append(dict(key="ffn_k100", bound="mfma", prefixes=["gemm_wres_kernel", "gemm_wres_pair_kernel"], flops=ffn100 * L * (fwd100 + bwd100),
                      launches=L * (14 + 6 + 10 + 6),
                      title="gemm_wres_kernel: the K = 100 -> 2048 products of the d_model-100 feed-forward block (linear1 forward "
                            "with bias + ReLU + dropout, linear2 dgrad with the ReLU/dropout mask); persistent, weights register-resident"))
-    fams.append(dict(key="ffn_n100", bound="mfma", prefixes=["gemm_n100_kernel"], flops=ffn100 * L * (fwd100 + bwd100),
+    fams.append(dict(key="ffn_n100", bound="mfma", prefixes=["gemm_n100_kernel", "gemm_n100_pair_kernel"], flops=ffn100 * L * (fwd100 + bwd100),
                      launches=L * (14 + 6 + 10 + 6),
                      title="gemm_n100_kernel: the 2048 -> 100 products of the d_model-100 feed-forward block (linear2 forward, "
                            "linear1 dgrad) on 112-wide 16x16x4 tiles, K-chunk slabs"))
@@ -117,7 +118,7 @@ def family_table(S, B):
     # reads attn_o, x, writes x1, xhat1 (4 E); LN2 + next in-proj reads 5 slabs + x1, writes x, xhat2, qkv (11 E); backward
     # mirrors them (LN backward reads dy, xhat, writes dx: + the slabs of the dgrad products): ~ 15 E + 15 E floats
     rc_bytes = 4.0 * 100 * L * (15 * fwd100 + 15 * bwd100)
-    fams.append(dict(key="rowchain", bound="hbm", prefixes=["rc_fwd_kernel", "rc_bwd_kernel"], bytes=rc_bytes,
+    fams.append(dict(key="rowchain", bound="hbm", prefixes=["rc_fwd_kernel", "rc_fwd_pair_kernel", "rc_bwd_kernel"], bytes=rc_bytes,
                      title="rowchain (rc_fwd/bwd_kernel): out-proj + residual + dropout + LN1, LN2 + next in-proj and their backward "
                            "mirrors for d_model 100, 16 token rows per workgroup — latency-sized (5-17 us) kernels, priced on their "
                            "operand bytes against HBM"))
