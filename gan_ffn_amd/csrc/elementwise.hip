@@ -579,13 +579,15 @@ __global__ __launch_bounds__(1024) void logsoftmax_nll_kernel(const float* __res
         for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
         float sum = 0.f;
         for (int c = 0; c < C; ++c) sum += expf(x[c] - m);
-        const float lse = m + logf(sum);
-        for (int c = 0; c < C; ++c) logp[(size_t)t * C + c] = x[c] - lse;
+        // (x - m) - log(sum), not x - (m + log(sum)): the latter rounds at the magnitude of m, which a common shift of the
+        // logits sets (1.5e-5 at |m| = 160) and which would then be the error of every log-probability near 0
+        const float ls = logf(sum);
+        for (int c = 0; c < C; ++c) logp[(size_t)t * C + c] = (x[c] - m) - ls;
         if (labels) {
             const int y = (int)labels[(size_t)b * S + s];
             const float mk = umask[(size_t)b * S + s];
             const float wy = cw ? cw[y] : 1.f;
-            num += wy * mk * (x[y] - lse);
+            num += wy * mk * ((x[y] - m) - ls);
             den += wy * mk;
         }
     }
@@ -605,7 +607,10 @@ __global__ __launch_bounds__(1024) void logsoftmax_nll_kernel(const float* __res
         }
     }
 }
-__global__ void nll_finish_kernel(const float* __restrict__ acc2, float* __restrict__ loss) { loss[0] = -acc2[0] / acc2[1]; }
+// den == 0 (every token masked out): nothing was asked for — the loss and its gradient are 0, not 0 / 0
+__global__ void nll_finish_kernel(const float* __restrict__ acc2, float* __restrict__ loss) {
+    loss[0] = acc2[1] != 0.f ? -acc2[0] / acc2[1] : 0.f;
+}
 // dlogits[t,c] = -(w[y] m / den) * (1[c==y] - softmax[t,c])
 __global__ void nll_bwd_kernel(const float* __restrict__ logp, const int64_t* __restrict__ labels,
                                const float* __restrict__ umask, const float* __restrict__ cw, const float* __restrict__ acc2,
@@ -614,7 +619,7 @@ __global__ void nll_bwd_kernel(const float* __restrict__ logp, const int64_t* __
     if (t >= S * B) return;
     const int s = t / B, b = t - s * B;
     const int y = (int)labels[(size_t)b * S + s];
-    const float coef = (cw ? cw[y] : 1.f) * umask[(size_t)b * S + s] / acc2[1];
+    const float coef = acc2[1] != 0.f ? (cw ? cw[y] : 1.f) * umask[(size_t)b * S + s] / acc2[1] : 0.f;
     for (int c = 0; c < C; ++c) {
         const float sm = expf(logp[(size_t)t * C + c]);
         dlogits[(size_t)t * C + c] = -coef * ((c == y ? 1.f : 0.f) - sm);

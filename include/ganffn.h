@@ -53,7 +53,10 @@ extern "C" {
 #define GANFFN_MAX_SEQ 112 /* PositionalEncoding(max_len=110), model.py:1179, rounded up to 4 */
 
 /* Encoder-stack configuration: PositionalEncoding + L post-LN nn.TransformerEncoderLayer
- * (model.py:1178-1197, 1210-1213).  p_* = 0 or train = 0 disables that dropout site. */
+ * (model.py:1178-1197, 1210-1213).  p_* = 0 or train = 0 disables that dropout site.
+ * Accepted: 1 <= S <= 110; E a multiple of 4, 4 <= E <= 640; H dividing E with an even head_dim E / H <= 64; F a multiple
+ * of 4; 1 <= L <= 64.  Anything else is refused with a message.  Widths off the workload's (100, 512, 600, 300) run on the
+ * generic kernels and are checked against the fp64 oracle by tests/test_hip_dispatch_range.py. */
 typedef struct ganffn_enc_cfg {
     int32_t S, B;       /* sequence length (<= 110) and batch (dialogues) */
     int32_t E, H, F, L; /* d_model, heads, dim_feedforward (2048), layers (8) */
@@ -229,7 +232,9 @@ int ganffn_add3(const float* a, const float* b, const float* c, float* out, int6
 /* logits [T x C] (token t = s*B+b) -> log_prob [T x C]; loss_out[0] = masked weighted NLL:
  * -sum_t w[y_t] m_t lp[t,y_t] / sum_t w[y_t] m_t, labels/umask are batch-major [B x S] as the
  * reference's collate makes them (dataloader.py:55-58); class_w may be NULL (unweighted).
- * dlogits (may be NULL) receives dL/dlogits. */
+ * dlogits (may be NULL) receives dL/dlogits.  log_prob = (x - max) - log(sum exp(x - max)): a common shift of a token's
+ * logits does not change it.  When every token is masked out (sum_t w[y_t] m_t = 0) the loss and dlogits are 0 (the
+ * reference divides 0 by 0 there). */
 int ganffn_logsoftmax_nll(const float* logits, const int64_t* labels, const float* umask,
                           const float* class_w, float* log_prob, float* loss_out, float* dlogits,
                           float* workspace2, int S, int B, int C, void* stream);
@@ -464,8 +469,12 @@ int ganffn_gemm_tn_grouped(int n, const float* const* At, const float* const* Bm
                            int64_t workspace_floats, void* stream);
 /* Attention core of nn.MultiheadAttention (call sites model.py:1210,1244,1276,1307,1340,1377):
  * qkv [T x 3E] -> o [T x E]; site = dropout site id; p = 0 disables dropout.  lse [B*H x S] receives the log-sum-exp of
- * every score row (may be NULL when no backward follows).  The backward takes the forward's o and lse back (head_dim
- * <= 32 uses them instead of recomputing the softmax statistics; larger heads ignore them, NULL allowed there). */
+ * every score row (may be NULL when no backward follows).  The backward takes the forward's o and lse back: the 16-row
+ * kernels (head_dim 10 and 30 at any S, 60 and 64 at S <= 48) use them instead of recomputing the softmax statistics;
+ * every other case recomputes, writes no lse and ignores both (NULL allowed there).
+ * Accepted: 1 <= S <= GANFFN_MAX_SEQ, H dividing E, head_dim E / H even and <= 64 (E need not be a multiple of 4),
+ * B * H < 2^32 / 3584; anything else is refused with a message and nothing is written.  head_dim 10, 30, 60, 64 have
+ * kernels of their own, every other one runs a kernel with a run-time head_dim. */
 int ganffn_attention_fwd(const float* qkv, float* o, float* lse, int S, int B, int E, int H, float p,
                          uint32_t site, const uint64_t* rng, uint64_t rng_offset_add, void* stream);
 int ganffn_attention_bwd(const float* qkv, const float* o, const float* lse, const float* d_o, float* d_qkv,
@@ -481,7 +490,9 @@ int ganffn_attention_fwd_keep(const float* qkv, float* o, float* lse, uint32_t* 
 int ganffn_attention_bwd_keep(const float* qkv, const float* o, const float* lse, const float* d_o,
                               const uint32_t* keep, float* d_qkv, int S, int B, int E, int H, float p, uint32_t site,
                               const uint64_t* rng, uint64_t rng_offset_add, void* stream);
-/* z = x + drop(y); xhat = (z-mean)*rstd; out = xhat*w + b   (norm1/norm2 of the encoder layer) */
+/* z = x + drop(y); xhat = (z-mean)*rstd; out = xhat*w + b   (norm1/norm2 of the encoder layer).  Accepted: T >= 1 and
+ * 1 <= E <= 640, a multiple of 4 or not; a wider row is refused with a message.  The variance is the two-pass one (mean
+ * of the squared deviations), so a row mean far above the row's spread costs no more than fp32 rounding of z itself. */
 int ganffn_add_dropout_layernorm_fwd(const float* x, const float* y, const float* w, const float* b,
                                      float* out, float* xhat, float* rstd, int T, int E, float eps,
                                      float p, uint32_t site, const uint64_t* rng,

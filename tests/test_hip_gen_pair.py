@@ -11,8 +11,9 @@ pytestmark = pytest.mark.gpu
 # multiple of 4 but not of 16 (the row chain's tile), 64 is tile-aligned, 282 is the workload's S with every key tile in use
 SHAPES = [(7, 2), (9, 4), (16, 4), (94, 3)]
 # (E, H), L = 2: "LayerNorm2 carries the next in-proj" and the last-layer path both run.  (120, 4): 30-wide heads on the generic
-# GEMM path (the 16-row attention kernels' third head shape)
-WIDTHS = [(100, 10), (512, 8), (120, 4)]
+# GEMM path (the 16-row attention kernels' third head shape); (64, 4) and (248, 4): head_dim 16 and 62 on the 32-row attention
+# kernel's run-time head_dim form, whose two-segment instantiation no workload width reaches
+WIDTHS = [(100, 10), (512, 8), (120, 4), (64, 4), (248, 4)]
 
 
 def _case(S, B, E, H, L=2):
@@ -43,10 +44,12 @@ def test_pair_pass_equals_the_two_single_passes(S, B, E, H):
     ws = torch.zeros(n_ws, **f32)
     ops.encoder_fwd_raw(cfg_eval, x, pe, params, out_e, None, ws, rng, add)
     ops.encoder_fwd_raw(cfg, x, pe, params, out_t, saved, ws, rng, add)
-    assert ops.encoder_fwd_pair_supported(cfg)
     p_e, p_t = torch.zeros(S * B * E, **f32), torch.zeros(S * B * E, **f32)
     p_saved = torch.full((n_saved,), -7.0, **f32)
     p_ws = torch.zeros(ops.encoder_fwd_pair_workspace_floats(cfg), **f32)
+    # every width here has its two-segment forms under the default mode word (a width that lost them would have to be refused:
+    # test_a_lab_variant_without_a_segment_form_is_reported_and_refused) — asserted, so that none drops out of this comparison
+    assert ops.encoder_fwd_pair_supported(cfg)
     ops.encoder_fwd_pair_raw(cfg, x, pe, params, p_e, p_t, p_saved, p_ws, rng, add)
     torch.cuda.synchronize()
     assert torch.isfinite(out_e).all() and torch.isfinite(out_t).all() and not torch.equal(out_e, out_t)

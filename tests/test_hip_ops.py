@@ -176,40 +176,62 @@ ATTN_CASES = [(7, 2, 100, 10), (110, 3, 100, 10), (94, 4, 512, 8), (33, 2, 100, 
               (48, 2, 600, 10), (49, 2, 600, 10), (40, 3, 512, 8), (16, 2, 512, 8), (5, 1, 600, 10)]
 
 
-@pytest.mark.parametrize("S,B,E,H", ATTN_CASES)
-@pytest.mark.parametrize("p", [0.0, 0.1])
-def test_attention_fwd_bwd(lib, S, B, E, H, p):
+ATTN_SEED, ATTN_OFF, ATTN_ADD, ATTN_LAYER = 777, 11, 4, 2
+
+
+def attention_inputs(S, B, E, H, qk_scale=1.0):
+    """seeded qkv (S, B, 3E) and d_o (S, B, E); qk_scale multiplies the q and k parts (score range: tests/test_hip_dispatch_range.py)"""
     g = torch.Generator().manual_seed(S * 131 + B * 17 + E)
     qkv = torch.randn(S, B, 3 * E, generator=g) * 1.5
     do = torch.randn(S, B, E, generator=g)
-    seed, off, add, layer = 777, 11, 4, 2
-    site = O.SITE_LAYER0 + 4 * layer
-    # oracle (float64 for a tight reference; same Philox mask)
-    q64 = qkv.double().requires_grad_(True)
+    if qk_scale != 1.0:
+        qkv[..., :2 * E] *= qk_scale
+    return qkv, do
+
+
+def attention_oracle(qkv, do, B, H, p, dtype=torch.float64):
+    """O.attention and its gradient in `dtype` on the CPU with the Philox masks of the launches of attention_case"""
+    q = qkv.detach().clone().to(dtype).requires_grad_(True)
     saved = O.ENC_DROPOUT
     O.ENC_DROPOUT = p
     try:
-        o_ref = O.attention(q64, B, H, layer, O.Rng(seed, off + add, train=p > 0))
+        o_ref = O.attention(q, B, H, ATTN_LAYER, O.Rng(ATTN_SEED, ATTN_OFF + ATTN_ADD, train=p > 0))
     finally:
         O.ENC_DROPOUT = saved
-    (o_ref * do.double()).sum().backward()
+    (o_ref * do.to(dtype)).sum().backward()
+    return o_ref.detach(), q.grad
+
+
+def attention_case(lib, S, B, E, H, p, qk_scale=1.0):
+    """ganffn_attention_fwd / _bwd on seeded inputs against the fp64 oracle with the same Philox mask -> the errors
+    {"o", "dq", "lse"} for the caller to bound ("lse" only where the 16-row kernels of head_dim 10 / 30 run: they keep the
+    log-sum-exp of every (dialogue, head, query) score row; the 32-row kernels neither write nor read it).  Asserted here:
+    the pair that hands the dropout keep bits from the forward to the backward gives the same bits.  Every output starts
+    as NaN, so an element no launch writes fails its comparison."""
+    qkv, do = attention_inputs(S, B, E, H, qk_scale)
+    seed, off, add = ATTN_SEED, ATTN_OFF, ATTN_ADD
+    site = O.SITE_LAYER0 + 4 * ATTN_LAYER
+    # oracle (float64 for a tight reference; same Philox mask)
+    o_ref, dq_ref = attention_oracle(qkv, do, B, H, p)
+    err = {}
     rng = torch.tensor([seed, off], dtype=torch.int64, device="cuda")
     qd, dod = dev(qkv), dev(do)
     od = torch.full((S, B, E), float("nan"), device="cuda")
     lse = torch.full((B * H, S), float("nan"), device="cuda")
     lib.call("ganffn_attention_fwd", ptr(qd), ptr(od), ptr(lse), S, B, E, H, C.c_float(p), C.c_uint32(site), ptr(rng),
              C.c_uint64(add), stream())
-    assert rel_err(od, o_ref.detach()) < 2e-5
-    if E // H <= 32:   # small-head kernels keep the log-sum-exp of every (dialogue, head, query) score row
+    err["o"] = rel_err(od, o_ref)
+    keeps_lse = E // H in (10, 30)
+    if keeps_lse:
         hd = E // H
         q = qkv[..., :E].double().reshape(S, B * H, hd).transpose(0, 1)
         k = qkv[..., E:2 * E].double().reshape(S, B * H, hd).transpose(0, 1)
         lse_ref = torch.logsumexp(q @ k.transpose(1, 2) / hd ** 0.5, dim=-1)
-        assert float((lse.double().cpu() - lse_ref).abs().max()) < 2e-5
+        err["lse"] = float((lse.double().cpu() - lse_ref).abs().max())
     dq = torch.full((S, B, 3 * E), float("nan"), device="cuda")
     lib.call("ganffn_attention_bwd", ptr(qd), ptr(od), ptr(lse), ptr(dod), ptr(dq), S, B, E, H, C.c_float(p),
              C.c_uint32(site), ptr(rng), C.c_uint64(add), stream())
-    assert rel_err(dq, q64.grad) < 5e-5
+    err["dq"] = rel_err(dq, dq_ref)
     # the pair that hands the dropout keep bits from the forward to the backward (what the encoder stack runs): the
     # same bits, so output, log-sum-exp and gradient are IDENTICAL to the Philox-recomputing pair above
     nk = int(lib.load().ganffn_attention_keep_words(B, H))
@@ -221,44 +243,91 @@ def test_attention_fwd_bwd(lib, S, B, E, H, p):
     lib.call("ganffn_attention_bwd_keep", ptr(qd), ptr(od2), ptr(lse2), ptr(dod), ptr(keep), ptr(dq2), S, B, E, H, C.c_float(p),
              C.c_uint32(site), ptr(rng), C.c_uint64(add), stream())
     assert torch.equal(od2, od) and torch.equal(dq2, dq)
-    if E // H <= 32:
+    if keeps_lse:
         assert torch.equal(lse2, lse)
         if p > 0 and B * H <= 384:
             assert int((keep != 0).sum()) > 0        # the forward did store its keep words (small launches only: see attn16_use_keep)
+    # a second launch of the plain pair: the same bits
+    od3, dq3 = torch.full_like(od, float("nan")), torch.full_like(dq, float("nan"))
+    lib.call("ganffn_attention_fwd", ptr(qd), ptr(od3), ptr(lse2), S, B, E, H, C.c_float(p), C.c_uint32(site), ptr(rng),
+             C.c_uint64(add), stream())
+    lib.call("ganffn_attention_bwd", ptr(qd), ptr(od3), ptr(lse2), ptr(dod), ptr(dq3), S, B, E, H, C.c_float(p),
+             C.c_uint32(site), ptr(rng), C.c_uint64(add), stream())
+    assert torch.equal(od3, od) and torch.equal(dq3, dq)
+    return err
+
+
+@pytest.mark.parametrize("S,B,E,H", ATTN_CASES)
+@pytest.mark.parametrize("p", [0.0, 0.1])
+def test_attention_fwd_bwd(lib, S, B, E, H, p):
+    err = attention_case(lib, S, B, E, H, p)
+    assert err["o"] < 2e-5
+    assert err["dq"] < 5e-5
+    if E // H in (10, 30):   # every head_dim <= 32 of ATTN_CASES: the 16-row kernels
+        assert err["lse"] < 2e-5
+
+
+LN_SEED, LN_OFF, LN_ADD, LN_SITE = 99, 3, 7, 21
+
+
+def layernorm_inputs(T, E, mean=0.3, spread=2.0, y_scale=1.0, g0_scale=0.0):
+    """seeded x, y, w, b, d_out and the values gw / gb hold before the backward (zeros unless g0_scale is set)"""
+    g = torch.Generator().manual_seed(T + E)
+    x, y = torch.randn(T, E, generator=g) * spread + mean, torch.randn(T, E, generator=g) * y_scale
+    w, b = 1 + 0.1 * torch.randn(E, generator=g), 0.1 * torch.randn(E, generator=g)
+    dout = torch.randn(T, E, generator=g)
+    gw0, gb0 = torch.randn(E, generator=g) * g0_scale, torch.randn(E, generator=g) * g0_scale
+    return x, y, w, b, dout, gw0, gb0
+
+
+def layernorm_oracle(inputs, p, dtype=torch.float64):
+    """O.layer_norm(x + dropout(y)) and its gradients in `dtype` on the CPU -> {out, dz, dy, gw, gb}, gw / gb with their
+    initial values added; the Philox mask of the launches of layernorm_case"""
+    x, y, w, b, dout, gw0, gb0 = inputs
+    T, E = x.shape
+    keep = torch.from_numpy(philox.keep_mask(T, E, p, LN_SITE, LN_SEED, LN_OFF + LN_ADD)).to(dtype) / (1 - p)
+    xr, yr, wr, br = (t.detach().clone().to(dtype).requires_grad_(True) for t in (x, y, w, b))
+    out_ref = O.layer_norm(xr + yr * keep, wr, br)
+    (out_ref * dout.to(dtype)).sum().backward()
+    return {"out": out_ref.detach(), "dz": xr.grad, "dy": yr.grad, "gw": gw0.to(dtype) + wr.grad, "gb": gb0.to(dtype) + br.grad}
+
+
+def layernorm_case(lib, T, E, p, **kw):
+    """ganffn_add_dropout_layernorm_fwd / _bwd on seeded inputs against the fp64 oracle -> the errors {out, dz, dy, gw, gb}
+    for the caller to bound.  gw / gb are accumulated: each run starts them from the same values and the reference is
+    initial + gradient.  Asserted here: a second forward and backward launch gives the same bits.  Outputs start as NaN."""
+    inputs = layernorm_inputs(T, E, **kw)
+    x, y, w, b, dout, gw0, gb0 = inputs
+    ref = layernorm_oracle(inputs, p)
+    seed, off, add, site = LN_SEED, LN_OFF, LN_ADD, LN_SITE
+    rng = torch.tensor([seed, off], dtype=torch.int64, device="cuda")
+    wd, bd, xd, yd, doutd = dev(w), dev(b), dev(x), dev(y), dev(dout)
+
+    def run():
+        nan = lambda *s: torch.full(s, float("nan"), device="cuda")
+        out, xhat, rstd = nan(T, E), nan(T, E), nan(T)
+        lib.call("ganffn_add_dropout_layernorm_fwd", ptr(xd), ptr(yd), ptr(wd), ptr(bd), ptr(out), ptr(xhat), ptr(rstd),
+                 T, E, C.c_float(1e-5), C.c_float(p), C.c_uint32(site), ptr(rng), C.c_uint64(add), stream())
+        dz, dy = nan(T, E), nan(T, E)
+        gw, gb = dev(gw0.clone()), dev(gb0.clone())
+        lib.call("ganffn_add_dropout_layernorm_bwd", ptr(doutd), ptr(xhat), ptr(rstd), ptr(wd), ptr(dz), ptr(dy), ptr(gw),
+                 ptr(gb), T, E, C.c_float(p), C.c_uint32(site), ptr(rng), C.c_uint64(add), stream())
+        return {"out": out, "dz": dz, "dy": dy, "gw": gw, "gb": gb}
+    got, again = run(), run()
+    for k in got:
+        assert torch.equal(got[k], again[k]), k
+    return {k: rel_err(got[k], ref[k]) for k in got}
 
 
 @pytest.mark.parametrize("T,E", [(3008, 100), (3008, 512), (14, 100), (5, 512), (331, 100)])
 @pytest.mark.parametrize("p", [0.0, 0.1])
 def test_add_dropout_layernorm(lib, T, E, p):
-    g = torch.Generator().manual_seed(T + E)
-    x, y = torch.randn(T, E, generator=g) * 2 + 0.3, torch.randn(T, E, generator=g)
-    w, b = 1 + 0.1 * torch.randn(E, generator=g), 0.1 * torch.randn(E, generator=g)
-    dout = torch.randn(T, E, generator=g)
-    seed, off, add, site = 99, 3, 7, 21
-    keep = torch.from_numpy(philox.keep_mask(T, E, p, site, seed, off + add)).double() / (1 - p)
-    y64 = y.double().requires_grad_(True)
-    x64 = x.double().requires_grad_(True)
-    w64, b64 = w.double().requires_grad_(True), b.double().requires_grad_(True)
-    out_ref = O.layer_norm(x64 + y64 * keep, w64, b64)
-    (out_ref * dout.double()).sum().backward()
-    rng = torch.tensor([seed, off], dtype=torch.int64, device="cuda")
-    out = torch.empty(T, E, device="cuda")
-    xhat = torch.empty(T, E, device="cuda")
-    rstd = torch.empty(T, device="cuda")
-    wd, bd, xd, yd, doutd = dev(w), dev(b), dev(x), dev(y), dev(dout)
-    lib.call("ganffn_add_dropout_layernorm_fwd", ptr(xd), ptr(yd), ptr(wd), ptr(bd), ptr(out), ptr(xhat), ptr(rstd),
-             T, E, C.c_float(1e-5), C.c_float(p), C.c_uint32(site), ptr(rng), C.c_uint64(add), stream())
-    assert rel_err(out, out_ref.detach()) < 5e-6
-    dz = torch.empty(T, E, device="cuda")
-    dy = torch.empty(T, E, device="cuda")
-    gw = torch.zeros(E, device="cuda")
-    gb = torch.zeros(E, device="cuda")
-    lib.call("ganffn_add_dropout_layernorm_bwd", ptr(doutd), ptr(xhat), ptr(rstd), ptr(wd), ptr(dz), ptr(dy), ptr(gw),
-             ptr(gb), T, E, C.c_float(p), C.c_uint32(site), ptr(rng), C.c_uint64(add), stream())
-    assert rel_err(dz, x64.grad) < 2e-5
-    assert rel_err(dy, y64.grad) < 2e-5
-    assert rel_err(gw, w64.grad) < 2e-5
-    assert rel_err(gb, b64.grad) < 2e-5
+    err = layernorm_case(lib, T, E, p)
+    assert err["out"] < 5e-6
+    assert err["dz"] < 2e-5
+    assert err["dy"] < 2e-5
+    assert err["gw"] < 2e-5
+    assert err["gb"] < 2e-5
 
 
 def test_pe_table(lib):
