@@ -291,9 +291,9 @@ def _side_streams(dev, prios, tuner=None, work=1):
     (torch's pools, RCCL, other engines), and with it how well kernels of different streams overlap: the same three
     sub-step chains ran at 34.7, 37.1, 40.5, 43.5 or 54 ms per iteration depending on nothing but that
     (tools/lab/stream_order.py; 1-workgroup spin kernels overlap on every pair — only real launch mixes tell the pairs
-    apart).  `tuner(prios)` picks the streams by timing a probe workload on fresh candidates (GanEngine._tune_streams);
-    without it, or with GANFFN_STREAM_TUNE=0, fresh streams are taken as they come; `work` = tokens per pass of the engine
-    that asks (the choice is re-timed when a much bigger engine comes along).
+    apart).  `tuner(prios)` picks the streams by timing the asking engine's probe work (its _tune_slot) on fresh candidates
+    (_NetRunner._tune_streams); without it, or with GANFFN_STREAM_TUNE=0, fresh streams are taken as they come; `work` =
+    tokens per pass of the engine that asks (the choice is re-timed when a much bigger engine comes along).
     Sharing the streams between the engines of one process is safe for engines over DIFFERENT networks and buffers (each
     engine orders its own sub-steps with its own events).  Two engines over the SAME networks see only their own dependency
     records: DrnnEngine joins its streams at the end of every step, but an eager multi-stream GanEngine does not (consecutive
@@ -313,28 +313,14 @@ def _side_streams(dev, prios, tuner=None, work=1):
 
 
 class _Runner:
-    """what every step runner shares: the device, its RNG, the process group, and the check that no network re-packed its
-    slab.  (The network-level forward / backward / Adam on preallocated buffers live in GanEngine, which the classifier step
-    runners over generators derive from.)"""
-    n_streams = 1
-    early_gen = False
-    gen_pair = False
-    gen_pair_mode = "0"
-    _gen_pairs = frozenset()
-    _cur_stream = None
-    _base_add = 0
-    _adds = 0
+    """what all four step runners share: the device, its RNG, the process group, the grow-only capacity of the step buffers
+    (reserve / _fit), the check that no network re-packed its slab, and predictions.
+      _Runner -> MeldEngine                                    (one slab, no generator)
+      _Runner -> _NetRunner -> GanEngine, Phase2Engine, DrnnEngine
+    _NetRunner holds the forward / backward / Adam of one network on preallocated pass buffers; the sub-step schedule, the
+    stream map and the cross-stream dependency records are GanEngine's alone."""
 
-    def _check_slabs(self):
-        """the engine trains the slab it captured at construction; a module that re-packed into a NEW slab since then
-        (`.to(other device)`, `.double()`, load into fresh parameters) would silently stop following — refuse instead"""
-        for group in (getattr(self, "G", {}), getattr(self, "D", {})):
-            for k, st in group.items():
-                if st.m.slab.data_ptr() != st.slab.data_ptr():
-                    raise RuntimeError("network %r re-packed its parameters after the engine was built (module.slab moved): "
-                                       "build the engine after the last .to()/.cuda()/dtype change" % k)
-
-    def _init_common(self, device, process_group, n_buckets):
+    def _init_common(self, device, process_group, n_buckets, nets=()):
         self.dev = device
         self.rng = ops.DeviceRng.get(device)
         self.pg = process_group
@@ -343,274 +329,73 @@ class _Runner:
             import torch.distributed as dist
             self.world = dist.get_world_size(process_group)
         self.n_buckets = n_buckets
-
-
-class GanEngine(_Runner):
-    """train_GAN's inner loop (train_IEMOCAP.py:320-382) for a fixed batch shape.
-
-    n_streams > 1: independent sub-steps run concurrently on several HIP streams.  The 12 sub-steps form a
-    DAG over the six networks (e.g. (D_t|G_a) only needs G_a from sub-step 2 and can run beside
-    (D_v|G_t)/(G_t|D_v)); every sub-step waits for the writers of what it reads and, before its Adam, for
-    the readers of what it writes — so each one sees exactly the parameter versions of the sequential
-    schedule.  Most kernels of this workload fill a fraction of the 256 CUs, so overlapping them is free."""
-
-    def __init__(self, gens, discs, lr=1e-4, b1=0.5, b2=0.6, process_group=None, n_buckets=3, use_graph=False,
-                 n_streams=1, schedule=None):
-        # optimizers: train_IEMOCAP.py:292-297 (G lr, text-G 1.1*lr, every D lr/2); call site :603-606
-        self.G = {k: NetState(m, lr * (1.1 if k == "text" else 1.0), (b1, b2)) for k, m in gens.items()}
-        self.D = {k: NetState(m, lr / 2, (b1, b2)) for k, m in discs.items()}
-        self._init_common(next(iter(self.G.values())).slab.device, process_group, n_buckets)
-        self.modalities = list(self.G.keys())
-        if schedule is None:
-            schedule = SCHEDULE if set(self.modalities) == {"acoustic", "visual", "text"} else \
-                [s_ for s_ in SCHEDULE if s_[1] in self.G and s_[2] in self.G]
-        self.schedule = list(schedule)
-        self.D_h = next(iter(self.G.values())).D2          # width of the fused feature = every discriminator's d_model
-        stream_maps = STREAM_MAP if len(self.schedule) == 12 else \
-            {1: [0] * len(self.schedule), 2: [(i // 2) % 2 for i in range(len(self.schedule))]}
-        self.use_graph = use_graph
-        if n_streams not in stream_maps:
-            n_streams = max(k for k in stream_maps if k <= max(1, n_streams))
-        self.n_streams = n_streams
-        if use_graph and self.n_streams > 1:
-            # multi-stream capture is not used: replay == eager here (the step is GPU-bound, not launch-bound), and
-            # eager streams additionally overlap consecutive iterations
-            self.use_graph = use_graph = False
-        self.stream_map = stream_maps[self.n_streams]
-        self.early_gen = self.n_streams > 1 and os.environ.get("GANFFN_EARLY_GEN", "0") == "1"
-        if os.environ.get("GANFFN_STREAM_MAP"):
-            self.stream_map = [int(x) for x in os.environ["GANFFN_STREAM_MAP"].split(",")]
-            assert len(self.stream_map) == len(self.schedule) and max(self.stream_map) < self.n_streams
-        # eval + train generator forward of a (D, G) sub-step pair as one two-segment pass (ganffn_encoder_fwd_pair): on unless
-        # GANFFN_GEN_PAIR=0, or the early generator forward (which issues the same pass elsewhere) is asked for.
-        # GANFFN_GEN_PAIR=all pairs every stack that has a pair pass, 1 those that gained from it (_pair_slot).  Unset: 1 in the
-        # multi-stream runner (the product's and the benchmark's mode, where the gain was measured), 0 on one stream — there
-        # every sub-step issues its own generator forward with its own offsets, the launch sequence the fp64 train-step oracle
-        # test walks sub-step by sub-step (tests/test_hip_engine_train_oracle.py); ask for 1 or all to pair there too
-        self.gen_pair_mode = os.environ.get("GANFFN_GEN_PAIR") or ("1" if self.n_streams > 1 else "0")
-        self.gen_pair = self.gen_pair_mode != "0" and os.environ.get("GANFFN_EARLY_GEN", "0") != "1"
-        self._gen_pairs = frozenset(find_gen_pairs(self.schedule, self.stream_map))
-        self.streams = None
-        self._res = {}
-        self._base_add = 0
-        # One communicator per sub-step stream (default in the in-line mode, see dp_mode(); GANFFN_COMM_PER_STREAM overrides).
-        self.pgs = [process_group]
-        per_stream = os.environ.get("GANFFN_COMM_PER_STREAM", "1" if dp_mode() == "inline" else "0") == "1"
-        if process_group is not None and self.n_streams > 1 and not per_stream and dp_mode() == "inline":
-            import torch.distributed as dist
-            if dist.get_backend(process_group) == "nccl":
-                # in-line collectives of different sub-step streams would share ONE RCCL communicator and may be in flight
-                # together: RCCL (like NCCL) does not support that.  (gloo reduces on the host, synchronously: no such limit.)
-                raise RuntimeError("GANFFN_DP_MODE=inline with %d sub-step streams needs one communicator per stream: "
-                                   "leave GANFFN_COMM_PER_STREAM at 1, or use n_streams=1, or GANFFN_DP_MODE=buckets" % self.n_streams)
-        # Ordering assumption of the in-line mode (DESIGN.md section 7): every rank runs the SAME host program, so the
-        # collectives of the three communicators are issued in the same host order on every rank; whatever order a rank's
-        # hardware queues impose is a sub-order of that one, so no two ranks can wait on each other's collectives in a cycle.
-        # Never measured on more than one rank (no multi-GPU node was available): `python bench.py --gpus N` therefore runs
-        # under a watchdog that falls back to one stream / one communicator and then to the bucket mode.
-        if process_group is not None and self.n_streams > 1 and per_stream:
-            # in-line collectives run on the sub-step streams themselves; two of them may be in flight at once, and one
-            # communicator must never carry two collectives concurrently: one communicator per sub-step stream (every rank
-            # creates them here, in the same order; each stream's collectives are ordered by the stream)
-            import torch.distributed as dist
-            ranks = list(range(dist.get_world_size(process_group)))
-            self.pgs += [dist.new_group(ranks=ranks) for _ in range(self.n_streams - 1)]
-        self._cur_pg = process_group
+        self._nets = list(nets)                  # [(name, NetState)]: what _check_slabs watches
         self._shape = None
-        self._graph = None
-        self.losses = torch.zeros(len(self.schedule), device=self.dev)
+        self._cap_S = self._cap_B = 0            # asked for (reserve) or seen so far
+        self._alloc_S = self._alloc_B = 0        # what the buffers are sized for
+        self._base_add = 0
         self._adds = 0
-        self._cap_S = self._cap_B = 0
 
-    # ------------------------------------------------------------------------------------------
+    def _check_slabs(self):
+        """the engine trains the slab it captured at construction; a module that re-packed into a NEW slab since then
+        (`.to(other device)`, `.double()`, load into fresh parameters) would silently stop following — refuse instead"""
+        for k, st in self._nets:
+            if st.m.slab.data_ptr() != st.slab.data_ptr():
+                raise RuntimeError("network %r re-packed its parameters after the engine was built (module.slab moved): "
+                                   "build the engine after the last .to()/.cuda()/dtype change" % k)
+
+    def _check_SB(self, S, B):
+        """engines with limits on a step's shape raise ValueError here"""
+
     def reserve(self, S, B):
         """size every step buffer once for dialogues of up to S utterances and batches of up to B dialogues, so that
-        the varying (S, B) of real loaders (no drop_last: every epoch ends on a short batch, train_IEMOCAP.py:62-100)
-        never touches the allocator again"""
+        the varying (S, B) of real loaders (no drop_last: every epoch ends on a short batch, train_IEMOCAP.py:62-100;
+        train / valid / test loaders differ) never touches the allocator again"""
+        self._check_SB(S, B)
         self._cap_S, self._cap_B = max(self._cap_S, S), max(self._cap_B, B)
 
-    def _prepare(self, S, B):
-        if self._shape == (S, B):
-            return
-        if self._shape is not None and S <= self._alloc_S and B <= self._alloc_B:
-            # within what the buffers were sized for: new views, no allocation, no sync.  (A pass of fewer dialogues uses
-            # a prefix of the flat storage; layouts are derived from (S, B) alone.)
-            self._resize_passes(S, B)
-            self._shape = (S, B)
-            self._graph = None
-            self.static_batch = None
-            self._view_scratch(S, B)
-            return
-        if self._shape is not None and self.n_streams > 1:
-            # the buffers about to be dropped may still be in use by sub-steps queued on the side streams (eager
-            # iterations overlap); the caching allocator only tracks the allocating stream
-            torch.cuda.synchronize(self.dev)
-        # capacity only ever grows (ADVICE r1: a short last batch must not shrink it)
-        cS = self._cap_S = max(self._cap_S, S)
-        cB = self._cap_B = max(self._cap_B, B)
-        self._alloc_S, self._alloc_B = cS, cB
-        self._shape = (S, B)
-        self._graph = None
-        dev = self.dev
-        self.pass_G_nosave = {k: _Pass(n, cS, cB, dev, False) for k, n in self.G.items()}
-        self.pass_G = {k: _Pass(n, cS, cB, dev, True) for k, n in self.G.items()}
-        self.pass_D2 = {k: _Pass(n, cS, 2 * cB, dev, True) for k, n in self.D.items()}   # [real | fake]
-        self.pass_D1 = {k: _Pass(n, cS, cB, dev, True) for k, n in self.D.items()}       # frozen D in train_gen
-        n_ws = max(p.n_ws for d in (self.pass_G, self.pass_D2, self.pass_D1, self.pass_G_nosave) for p in d.values())
-        f32 = dict(device=dev, dtype=torch.float32)
-        Dh = self.D_h
-        # scratch is per stream (sub-steps on different streams run concurrently); flat, viewed per (S, B)
-        self._scratch_flat = [dict(ws=torch.empty(n_ws, **f32), x_cat=torch.empty(cS * 2 * cB * Dh, **f32),
-                                   obj_out=torch.empty(cS * cB * Dh, **f32), dprob2=torch.empty(cS * 2 * cB, **f32),
-                                   dprob1=torch.empty(cS * cB, **f32), d_real=torch.empty(cS * cB * Dh, **f32))
-                              for _ in range(self.n_streams * (2 if self.early_gen else 1))]
-        if (S, B) != (cS, cB):
-            self._resize_passes(S, B)
-        self._view_scratch(S, B)
-        if self.n_streams > 1 and self.streams is None:
-            # stream priorities: the visual generator's chain (stream 2 of the 3-stream map: its four sub-steps are a cycle
-            # through G_v's parameters and pace the iteration) gets the high priority — measured 35.34 -> 34.90 ms per step
-            # (GANFFN_STREAM_PRIO="0,0,0" restores equal priorities; "-1,-1,0" measured 35.6)
-            default_prio = "0,0,-1" if (self.n_streams == 3 and len(self.schedule) == 12) else ""
-            prio = [int(x) for x in os.environ.get("GANFFN_STREAM_PRIO", default_prio).split(",") if x.strip()]
-            prio = (prio + [0] * self.n_streams)[:self.n_streams]
-            # main streams, then (early generator forward) one helper stream per main stream
-            self.streams = list(_side_streams(dev, prio + (prio if self.early_gen else []), self._tune_streams, S * B))
-            self._tune_x, self._tune_pass = (None, None), {}
-            self._use_scratch(0)
-        self._res = {}
-        self.static_batch = None
+    def _fit(self, *shape, grow=False):
+        """the capacity rule of every engine's prepare, for the step shape (S, B, ...) -> "same": the shape of the last step,
+        nothing to do; "fits": within what the buffers were sized for — the caller takes new views, no allocation, no sync;
+        "grow": the caller allocates for (_alloc_S, _alloc_B), which is the largest S and the largest B reserved or seen so
+        far — capacity only ever grows (a short last batch must not shrink it).  grow=True: the caller outgrew a dimension
+        of its own (DrnnEngine's party count).
+        The new shape and allocation are recorded HERE, before the caller allocates (as GanEngine always did): an engine whose
+        allocation raised (out of memory) is not fit to step again — build a new one."""
+        if self._shape == shape:
+            return "same"
+        S, B = shape[:2]
+        self._check_SB(S, B)
+        self._shape = shape
+        if not grow and S <= self._alloc_S and B <= self._alloc_B:
+            return "fits"
+        self._alloc_S = self._cap_S = max(self._cap_S, S)
+        self._alloc_B = self._cap_B = max(self._cap_B, B)
+        return "grow"
 
-    def _tune_slot(self, i):
-        """the probe work of stream slot i for _tune_streams: eval-mode forwards of one generator into its no-save pass
-        buffers with the slot's scratch (nothing else is written: no parameter, gradient or RNG state changes)"""
-        k = self.modalities[i % len(self.modalities)]
-        if getattr(self, "_tune_x", (None, None))[0] != self._shape:
-            S, B = self._shape
-            self._tune_x = (self._shape, {m: torch.zeros(S, B, self.G[m].E, device=self.dev) for m in self.modalities})
-            self._tune_pass = {}
-        # slots beyond the modalities (the early-generator helper streams) probe the same networks: every such slot gets pass
-        # buffers of its own, so that concurrent probes never write the same memory (ADVICE r3)
-        if i < len(self.modalities):
-            ps = self.pass_G_nosave[k]
-        else:
-            if i not in self._tune_pass:
-                self._tune_pass[i] = _Pass(self.G[k], self._shape[0], self._shape[1], self.dev, False)
-            ps = self._tune_pass[i]
-        self._use_scratch(i)
-        for _ in range(1 if self.G[k].E > 256 else 3):                      # (the 512-wide generator is ~3x a 100-wide one)
-            self._net_fwd(self.G[k], ps, self._tune_x[1][k], train=False, save=False, adds=(0, 1))
+    predictions = staticmethod(predictions)
 
-    def _tune_streams(self, prios, n_cand=6, reps=2):
-        """choose one stream per entry of `prios` among n_cand fresh candidates per priority by TIMING them on this engine's
-        own kernels: slot i runs _tune_slot(i) beside the slots already chosen; the first two slots are chosen jointly over
-        all candidate pairs, every further slot greedily.  ~0.15 s, once per process and device."""
-        dev = self.dev
-        n_cand = int(os.environ.get("GANFFN_STREAM_CAND", n_cand))
-        cands = {p_: [torch.cuda.Stream(device=dev, priority=p_) for _ in range(n_cand)] for p_ in sorted(set(prios))}
-        cur = torch.cuda.current_stream(dev)
 
-        def probe(streams):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(cur)
-            for i, st in enumerate(streams):
-                st.wait_event(e0)
-                with torch.cuda.stream(st):
-                    self._tune_slot(i)
-            for st in streams:
-                cur.wait_stream(st)
-            e1.record(cur)
-            e1.synchronize()
-            return e0.elapsed_time(e1)
+class _NetRunner(_Runner):
+    """the network-level operations GanEngine, Phase2Engine and DrnnEngine share: forward, backward, all-reduce and Adam of ONE
+    network (a NetState) on preallocated pass buffers (_Pass) with the workspace `self.ws`, dropout offsets relative to
+    `_base_add`, and the timing of candidate side streams on the engine's own `_tune_slot`.  One stream and one communicator
+    are the defaults here; GanEngine, whose sub-steps run on several streams, overrides `_cur_pg`, `_communicators` and
+    `_pre_write`."""
+    _cur_pg = None               # the communicator of the sub-step being issued (None: self.pg)
 
-        def best(fixed, pool):
-            timed = []
-            for c_ in pool:
-                group = fixed + (list(c_) if isinstance(c_, tuple) else [c_])
-                timed.append((min(probe(group) for _ in range(reps)), c_))
-            return min(timed, key=lambda t_: t_[0])[1]
+    def _communicators(self):
+        """every communicator the engine issues collectives on"""
+        return [self.pg]
 
-        if self.pg is not None:
-            # RCCL creates its internal stream(s) at the first collective of a communicator; a stream that appears AFTER the
-            # choice below can land on a hardware queue one of the chosen streams uses.  Issue one tiny all-reduce per
-            # communicator first, so that the candidates are timed with RCCL's queue already taken.
-            for g_ in getattr(self, "pgs", [self.pg]):
-                if g_ is not None:
-                    self.dist_warm = torch.zeros(8, device=dev)
-                    import torch.distributed as dist
-                    dist.all_reduce(self.dist_warm, group=g_, async_op=(dp_mode() != "inline"))
-                    if dp_mode() != "inline":
-                        torch.cuda.synchronize(dev)
-        torch.cuda.synchronize(dev)
-        saved_add = self._base_add
-        self._base_add = 0
-        try:
-            probe([cands[prios[0]][0]])                                      # warm-up (lazy module / allocator state)
-            if prios[0] == prios[1]:
-                pool = [(a_, b_) for i, a_ in enumerate(cands[prios[0]]) for b_ in cands[prios[0]][i + 1:]]
-            else:
-                pool = [(a_, b_) for a_ in cands[prios[0]] for b_ in cands[prios[1]]]
-            chosen = list(best([], pool))
-            for p_ in prios[2:]:
-                chosen.append(best(chosen, [c_ for c_ in cands[p_] if c_ not in chosen]))
-        finally:
-            self._base_add = saved_add
-            torch.cuda.synchronize(dev)
-        return chosen
-
-    def _resize_passes(self, S, B):
-        for d in (self.pass_G_nosave, self.pass_G, self.pass_D1):
-            for p_ in d.values():
-                p_.resize(S, B)
-        for p_ in self.pass_D2.values():
-            p_.resize(S, 2 * B)
-
-    def _view_scratch(self, S, B):
-        Dh = self.D_h
-        self.scratch = [dict(ws=f["ws"], x_cat=f["x_cat"][:S * 2 * B * Dh].view(S, 2 * B, Dh),
-                             obj_out=f["obj_out"][:S * B * Dh].view(S, B, Dh),
-                             dprob2=f["dprob2"][:S * 2 * B].view(S, 2 * B, 1), dprob1=f["dprob1"][:S * B].view(S, B, 1),
-                             d_real=f["d_real"][:S * B * Dh].view(S, B, Dh)) for f in self._scratch_flat]
-        self._use_scratch(0)
-
-    def _use_scratch(self, i):
-        sc = self.scratch[i]
-        self.ws, self.x_cat, self.obj_out = sc["ws"], sc["x_cat"], sc["obj_out"]
-        self.dprob2, self.dprob1, self.d_real = sc["dprob2"], sc["dprob1"], sc["d_real"]
-
-    # ---- cross-stream dependencies -------------------------------------------------------------
-    def _r(self, key):
-        r = self._res.get(key)
-        if r is None:
-            r = self._res[key] = _Res()
-        return r
-
-    def _wait_writers(self, stream, keys):
-        for k in keys:
-            ev = self._r(k).last_write
-            if ev is not None:
-                stream.wait_event(ev)
-
-    def _wait_readers(self, stream, keys):
-        for k in keys:
-            for ev in self._r(k).reads:
-                stream.wait_event(ev)
-
-    def _done(self, stream, reads, writes):
-        ev = torch.cuda.Event()
-        ev.record(stream)
-        for k in reads:
-            self._r(k).reads.append(ev)
-        for k in writes:
-            r = self._r(k)
-            r.last_write, r.reads = ev, []
+    def _pre_write(self, net_key):
+        """called right before a network's Adam; one stream: nothing to wait for"""
 
     def _next_add(self):
         v = self._adds
         self._adds += 1
         return self._base_add + v
 
-    # ------------------------------------------------------------------------------------------
     def _net_fwd(self, net, ps, x, train, save, adds=None):
         """encoder + head forward into ps.out; returns (enc_add, head_add) rng offsets used.  adds: the two dropout
         offsets (relative to the iteration's block) when the caller assigns them by sub-step; else the next two."""
@@ -671,6 +456,10 @@ class GanEngine(_Runner):
         ops.adam_step_raw(net.slab, net.grad, net.exp_avg, net.exp_avg_sq, net.step, net.total, net.lr,
                           net.betas[0], net.betas[1], 1e-8, net.wd, 1.0 / self.world)
 
+    def _adam_slice(self, net, lo, hi):
+        ops.adam_update_raw(net.slab[lo:hi], net.grad[lo:hi], net.exp_avg[lo:hi], net.exp_avg_sq[lo:hi], net.step, hi - lo,
+                            net.lr, net.betas[0], net.betas[1], 1e-8, net.wd, 1.0 / self.world)
+
     def _parts_ok(self, net, ps):
         """single GPU, d_model 100: leave the weight gradients of this backward pass as token-chunk slabs and let Adam add them
         (ganffn_encoder_bwd_parts / ganffn_adam_step_parts): no reduce launch, no zero-fill of the encoder region of net.grad.
@@ -685,10 +474,6 @@ class GanEngine(_Runner):
         else:
             net.grad.zero_()
 
-    def _adam_slice(self, net, lo, hi):
-        ops.adam_update_raw(net.slab[lo:hi], net.grad[lo:hi], net.exp_avg[lo:hi], net.exp_avg_sq[lo:hi], net.step, hi - lo,
-                            net.lr, net.betas[0], net.betas[1], 1e-8, net.wd, 1.0 / self.world)
-
     def _make_reducer(self, net):
         """returns (callback, finish_and_step): async all-reduce (sum) of grad-slab slices on RCCL's own stream,
         overlapping the rest of backward.  finish_and_step(net_key) waits bucket by bucket and applies Adam (which
@@ -701,7 +486,7 @@ class GanEngine(_Runner):
             return None, plain
         if dp_mode() == "inline":
             import torch.distributed as dist
-            group = getattr(self, "_cur_pg", None) or self.pg
+            group = self._cur_pg or self.pg
 
             def inline(net_key, parts=None):
                 # on the CURRENT stream (the sub-step's own): sum over ranks, then Adam divides by world (grad_scale)
@@ -709,7 +494,7 @@ class GanEngine(_Runner):
                 self._pre_write(net_key)
                 self._adam(net)
             return None, inline
-        red = GradReducer(getattr(self, "_cur_pg", None) or self.pg)
+        red = GradReducer(self._cur_pg or self.pg)
 
         def cb(lo, hi, last):
             red.reduce_async(net.grad[lo:hi], lo, hi)
@@ -719,6 +504,246 @@ class GanEngine(_Runner):
             red.finish(lambda lo, hi: self._adam_slice(net, lo, hi) if hi > lo else None)
             ops.adam_bump_raw(net.step)
         return cb, finish_and_step
+
+    def _tune_streams(self, prios, n_cand=6, reps=2):
+        """choose one stream per entry of `prios` among n_cand fresh candidates per priority by TIMING them on this engine's
+        own kernels: slot i runs _tune_slot(i) beside the slots already chosen; the first two slots are chosen jointly over
+        all candidate pairs, every further slot greedily.  ~0.15 s, once per process and device."""
+        dev = self.dev
+        n_cand = int(os.environ.get("GANFFN_STREAM_CAND", n_cand))
+        cands = {p_: [torch.cuda.Stream(device=dev, priority=p_) for _ in range(n_cand)] for p_ in sorted(set(prios))}
+        cur = torch.cuda.current_stream(dev)
+
+        def probe(streams):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(cur)
+            for i, st in enumerate(streams):
+                st.wait_event(e0)
+                with torch.cuda.stream(st):
+                    self._tune_slot(i)
+            for st in streams:
+                cur.wait_stream(st)
+            e1.record(cur)
+            e1.synchronize()
+            return e0.elapsed_time(e1)
+
+        def best(fixed, pool):
+            timed = []
+            for c_ in pool:
+                group = fixed + (list(c_) if isinstance(c_, tuple) else [c_])
+                timed.append((min(probe(group) for _ in range(reps)), c_))
+            return min(timed, key=lambda t_: t_[0])[1]
+
+        if self.pg is not None:
+            # RCCL creates its internal stream(s) at the first collective of a communicator; a stream that appears AFTER the
+            # choice below can land on a hardware queue one of the chosen streams uses.  Issue one tiny all-reduce per
+            # communicator first, so that the candidates are timed with RCCL's queue already taken.
+            for g_ in self._communicators():
+                if g_ is not None:
+                    self.dist_warm = torch.zeros(8, device=dev)
+                    import torch.distributed as dist
+                    dist.all_reduce(self.dist_warm, group=g_, async_op=(dp_mode() != "inline"))
+                    if dp_mode() != "inline":
+                        torch.cuda.synchronize(dev)
+        torch.cuda.synchronize(dev)
+        saved_add = self._base_add
+        self._base_add = 0
+        try:
+            probe([cands[prios[0]][0]])                                      # warm-up (lazy module / allocator state)
+            if prios[0] == prios[1]:
+                pool = [(a_, b_) for i, a_ in enumerate(cands[prios[0]]) for b_ in cands[prios[0]][i + 1:]]
+            else:
+                pool = [(a_, b_) for a_ in cands[prios[0]] for b_ in cands[prios[1]]]
+            chosen = list(best([], pool))
+            for p_ in prios[2:]:
+                chosen.append(best(chosen, [c_ for c_ in cands[p_] if c_ not in chosen]))
+        finally:
+            self._base_add = saved_add
+            torch.cuda.synchronize(dev)
+        return chosen
+
+
+class GanEngine(_NetRunner):
+    """train_GAN's inner loop (train_IEMOCAP.py:320-382) for a fixed batch shape.
+
+    n_streams > 1: independent sub-steps run concurrently on several HIP streams.  The 12 sub-steps form a
+    DAG over the six networks (e.g. (D_t|G_a) only needs G_a from sub-step 2 and can run beside
+    (D_v|G_t)/(G_t|D_v)); every sub-step waits for the writers of what it reads and, before its Adam, for
+    the readers of what it writes — so each one sees exactly the parameter versions of the sequential
+    schedule.  Most kernels of this workload fill a fraction of the 256 CUs, so overlapping them is free."""
+
+    def __init__(self, gens, discs, lr=1e-4, b1=0.5, b2=0.6, process_group=None, n_buckets=3, use_graph=False,
+                 n_streams=1, schedule=None):
+        # optimizers: train_IEMOCAP.py:292-297 (G lr, text-G 1.1*lr, every D lr/2); call site :603-606
+        self.G = {k: NetState(m, lr * (1.1 if k == "text" else 1.0), (b1, b2)) for k, m in gens.items()}
+        self.D = {k: NetState(m, lr / 2, (b1, b2)) for k, m in discs.items()}
+        self._init_common(next(iter(self.G.values())).slab.device, process_group, n_buckets,
+                          list(self.G.items()) + list(self.D.items()))
+        self.modalities = list(self.G.keys())
+        if schedule is None:
+            schedule = SCHEDULE if set(self.modalities) == {"acoustic", "visual", "text"} else \
+                [s_ for s_ in SCHEDULE if s_[1] in self.G and s_[2] in self.G]
+        self.schedule = list(schedule)
+        self.D_h = next(iter(self.G.values())).D2          # width of the fused feature = every discriminator's d_model
+        stream_maps = STREAM_MAP if len(self.schedule) == 12 else \
+            {1: [0] * len(self.schedule), 2: [(i // 2) % 2 for i in range(len(self.schedule))]}
+        self.use_graph = use_graph
+        if n_streams not in stream_maps:
+            n_streams = max(k for k in stream_maps if k <= max(1, n_streams))
+        self.n_streams = n_streams
+        if use_graph and self.n_streams > 1:
+            # multi-stream capture is not used: replay == eager here (the step is GPU-bound, not launch-bound), and
+            # eager streams additionally overlap consecutive iterations
+            self.use_graph = use_graph = False
+        self.stream_map = stream_maps[self.n_streams]
+        if os.environ.get("GANFFN_STREAM_MAP"):
+            self.stream_map = [int(x) for x in os.environ["GANFFN_STREAM_MAP"].split(",")]
+            assert len(self.stream_map) == len(self.schedule) and max(self.stream_map) < self.n_streams
+        # eval + train generator forward of a (D, G) sub-step pair as one two-segment pass (ganffn_encoder_fwd_pair): on unless
+        # GANFFN_GEN_PAIR=0.  GANFFN_GEN_PAIR=all pairs every stack that has a pair pass, 1 those that gained from it
+        # (_pair_slot).  Unset: 1 in the multi-stream runner (the product's and the benchmark's mode, where the gain was
+        # measured), 0 on one stream — there every sub-step issues its own generator forward with its own offsets, the launch
+        # sequence the fp64 train-step oracle test walks sub-step by sub-step (tests/test_hip_engine_train_oracle.py); ask for
+        # 1 or all to pair there too
+        self.gen_pair_mode = os.environ.get("GANFFN_GEN_PAIR") or ("1" if self.n_streams > 1 else "0")
+        self.gen_pair = self.gen_pair_mode != "0"
+        self._gen_pairs = frozenset(find_gen_pairs(self.schedule, self.stream_map))
+        self.streams = None
+        self._cur_stream = None              # the stream of the sub-step being issued (multi-stream loop of _iteration_body)
+        self._tune_x = (None, None)          # (shape, inputs) of _tune_slot's probe work
+        self._res = {}
+        # One communicator per sub-step stream (default in the in-line mode, see dp_mode(); GANFFN_COMM_PER_STREAM overrides).
+        self.pgs = [process_group]
+        per_stream = os.environ.get("GANFFN_COMM_PER_STREAM", "1" if dp_mode() == "inline" else "0") == "1"
+        if process_group is not None and self.n_streams > 1 and not per_stream and dp_mode() == "inline":
+            import torch.distributed as dist
+            if dist.get_backend(process_group) == "nccl":
+                # in-line collectives of different sub-step streams would share ONE RCCL communicator and may be in flight
+                # together: RCCL (like NCCL) does not support that.  (gloo reduces on the host, synchronously: no such limit.)
+                raise RuntimeError("GANFFN_DP_MODE=inline with %d sub-step streams needs one communicator per stream: "
+                                   "leave GANFFN_COMM_PER_STREAM at 1, or use n_streams=1, or GANFFN_DP_MODE=buckets" % self.n_streams)
+        # Ordering assumption of the in-line mode (DESIGN.md section 7): every rank runs the SAME host program, so the
+        # collectives of the three communicators are issued in the same host order on every rank; whatever order a rank's
+        # hardware queues impose is a sub-order of that one, so no two ranks can wait on each other's collectives in a cycle.
+        # Never measured on more than one rank (no multi-GPU node was available): `python bench.py --gpus N` therefore runs
+        # under a watchdog that falls back to one stream / one communicator and then to the bucket mode.
+        if process_group is not None and self.n_streams > 1 and per_stream:
+            # in-line collectives run on the sub-step streams themselves; two of them may be in flight at once, and one
+            # communicator must never carry two collectives concurrently: one communicator per sub-step stream (every rank
+            # creates them here, in the same order; each stream's collectives are ordered by the stream)
+            import torch.distributed as dist
+            ranks = list(range(dist.get_world_size(process_group)))
+            self.pgs += [dist.new_group(ranks=ranks) for _ in range(self.n_streams - 1)]
+        self._cur_pg = process_group
+        self._graph = None
+        self.losses = torch.zeros(len(self.schedule), device=self.dev)
+
+    def _communicators(self):
+        return self.pgs
+
+    # ------------------------------------------------------------------------------------------
+    def _prepare(self, S, B):
+        first = self._shape is None
+        fit = self._fit(S, B)
+        if fit == "same":
+            return
+        self._graph = None
+        self.static_batch = None
+        if fit == "fits":
+            # new views, no allocation, no sync.  (A pass of fewer dialogues uses a prefix of the flat storage; layouts are
+            # derived from (S, B) alone.)
+            self._resize_passes(S, B)
+            self._view_scratch(S, B)
+            return
+        if not first and self.n_streams > 1:
+            # the buffers about to be dropped may still be in use by sub-steps queued on the side streams (eager
+            # iterations overlap); the caching allocator only tracks the allocating stream
+            torch.cuda.synchronize(self.dev)
+        cS, cB, dev = self._alloc_S, self._alloc_B, self.dev
+        self.pass_G_nosave = {k: _Pass(n, cS, cB, dev, False) for k, n in self.G.items()}
+        self.pass_G = {k: _Pass(n, cS, cB, dev, True) for k, n in self.G.items()}
+        self.pass_D2 = {k: _Pass(n, cS, 2 * cB, dev, True) for k, n in self.D.items()}   # [real | fake]
+        self.pass_D1 = {k: _Pass(n, cS, cB, dev, True) for k, n in self.D.items()}       # frozen D in train_gen
+        n_ws = max(p.n_ws for d in (self.pass_G, self.pass_D2, self.pass_D1, self.pass_G_nosave) for p in d.values())
+        f32 = dict(device=dev, dtype=torch.float32)
+        Dh = self.D_h
+        # scratch is per stream (sub-steps on different streams run concurrently); flat, viewed per (S, B)
+        self._scratch_flat = [dict(ws=torch.empty(n_ws, **f32), x_cat=torch.empty(cS * 2 * cB * Dh, **f32),
+                                   obj_out=torch.empty(cS * cB * Dh, **f32), dprob2=torch.empty(cS * 2 * cB, **f32),
+                                   dprob1=torch.empty(cS * cB, **f32), d_real=torch.empty(cS * cB * Dh, **f32))
+                              for _ in range(self.n_streams)]
+        if (S, B) != (cS, cB):
+            self._resize_passes(S, B)
+        self._view_scratch(S, B)
+        if self.n_streams > 1 and self.streams is None:
+            # stream priorities: the visual generator's chain (stream 2 of the 3-stream map: its four sub-steps are a cycle
+            # through G_v's parameters and pace the iteration) gets the high priority — measured 35.34 -> 34.90 ms per step
+            # (GANFFN_STREAM_PRIO="0,0,0" restores equal priorities; "-1,-1,0" measured 35.6)
+            default_prio = "0,0,-1" if (self.n_streams == 3 and len(self.schedule) == 12) else ""
+            prio = [int(x) for x in os.environ.get("GANFFN_STREAM_PRIO", default_prio).split(",") if x.strip()]
+            prio = (prio + [0] * self.n_streams)[:self.n_streams]
+            self.streams = list(_side_streams(dev, prio, self._tune_streams, S * B))
+            self._tune_x = (None, None)
+            self._use_scratch(0)
+        self._res = {}
+
+    def _tune_slot(self, i):
+        """the probe work of stream slot i for _tune_streams: eval-mode forwards of one generator into its no-save pass
+        buffers with the slot's scratch (nothing else is written: no parameter, gradient or RNG state changes)"""
+        k = self.modalities[i % len(self.modalities)]
+        if self._tune_x[0] != self._shape:
+            S, B = self._shape
+            self._tune_x = (self._shape, {m: torch.zeros(S, B, self.G[m].E, device=self.dev) for m in self.modalities})
+        self._use_scratch(i)
+        for _ in range(1 if self.G[k].E > 256 else 3):                      # (the 512-wide generator is ~3x a 100-wide one)
+            self._net_fwd(self.G[k], self.pass_G_nosave[k], self._tune_x[1][k], train=False, save=False, adds=(0, 1))
+
+    def _resize_passes(self, S, B):
+        for d in (self.pass_G_nosave, self.pass_G, self.pass_D1):
+            for p_ in d.values():
+                p_.resize(S, B)
+        for p_ in self.pass_D2.values():
+            p_.resize(S, 2 * B)
+
+    def _view_scratch(self, S, B):
+        Dh = self.D_h
+        self.scratch = [dict(ws=f["ws"], x_cat=f["x_cat"][:S * 2 * B * Dh].view(S, 2 * B, Dh),
+                             obj_out=f["obj_out"][:S * B * Dh].view(S, B, Dh),
+                             dprob2=f["dprob2"][:S * 2 * B].view(S, 2 * B, 1), dprob1=f["dprob1"][:S * B].view(S, B, 1),
+                             d_real=f["d_real"][:S * B * Dh].view(S, B, Dh)) for f in self._scratch_flat]
+        self._use_scratch(0)
+
+    def _use_scratch(self, i):
+        sc = self.scratch[i]
+        self.ws, self.x_cat, self.obj_out = sc["ws"], sc["x_cat"], sc["obj_out"]
+        self.dprob2, self.dprob1, self.d_real = sc["dprob2"], sc["dprob1"], sc["d_real"]
+
+    # ---- cross-stream dependencies -------------------------------------------------------------
+    def _r(self, key):
+        r = self._res.get(key)
+        if r is None:
+            r = self._res[key] = _Res()
+        return r
+
+    def _wait_writers(self, stream, keys):
+        for k in keys:
+            ev = self._r(k).last_write
+            if ev is not None:
+                stream.wait_event(ev)
+
+    def _wait_readers(self, stream, keys):
+        for k in keys:
+            for ev in self._r(k).reads:
+                stream.wait_event(ev)
+
+    def _done(self, stream, reads, writes):
+        ev = torch.cuda.Event()
+        ev.record(stream)
+        for k in reads:
+            self._r(k).reads.append(ev)
+        for k in writes:
+            r = self._r(k)
+            r.last_write, r.reads = ev, []
 
     # ------------------------------------------------------------------------------------------
     def _gen_pair_fwd(self, net, ps_eval, ps_train, x, adds_eval, adds_train):
@@ -790,7 +815,7 @@ class GanEngine(_Runner):
 
     def train_gen_forward(self, who, batch, loss_slot):
         """the generator's own forward of train_gen (train mode, saved for backward): it reads nothing but the generator's
-        parameters and the batch, so the multi-stream scheduler may issue it ahead of the sub-step"""
+        parameters and the batch (a paired discriminator sub-step issues it instead, with its own eval-mode one: _gen_pair_fwd)"""
         a = ADDS_PER_SUBSTEP * loss_slot
         return self._net_fwd(self.G[who], self.pass_G[who], batch[who], train=True, save=True, adds=(a, a + 1))
 
@@ -815,12 +840,10 @@ class GanEngine(_Runner):
 
     def _pre_write(self, net_key):
         """called right before a sub-step's Adam: wait for other streams' readers of that network (WAR)"""
-        if self.n_streams > 1 and self._cur_stream is not None:
+        if self._cur_stream is not None:
             self._wait_readers(self._cur_stream, [net_key])
 
     # ------------------------------------------------------------------------------------------
-    _cur_stream = None
-
     def _iteration_body(self, batch, device_rng_advance):
         self._adds = 0
         self._check_slabs()
@@ -829,8 +852,8 @@ class GanEngine(_Runner):
             # module path and every other engine); iterations may overlap, the offsets are host-side arguments
             self._base_add = self.rng.next_add(ADDS_PER_SUBSTEP * len(self.schedule))
         self._adds = ADDS_PER_SUBSTEP * len(self.schedule)       # (offsets are assigned by sub-step: train_disc / train_gen)
+        paired = {}                      # sub-step -> (enc_add, head_add) of its generator forward, issued by the sub-step before
         if self.n_streams == 1:
-            paired = {}                  # sub-step -> (enc_add, head_add) of its generator forward, issued by the sub-step before
             for i, (kind, who, partner) in enumerate(self.schedule):
                 j = self._pair_slot(i) if kind == "D" else None
                 if j is not None:
@@ -853,33 +876,8 @@ class GanEngine(_Runner):
                 for k in self.modalities:
                     if batch[k].is_cuda:
                         batch[k].record_stream(st)
-            early = {}
-            nsub = len(self.schedule)
             for i, (kind, who, partner) in enumerate(self.schedule):
                 st = self.streams[smap[i]]
-                # Early generator forward: the train-mode forward of the NEXT sub-step's generator reads only that generator's
-                # parameters (which this sub-step does not write) and the batch, so it is issued now, on this stream's helper
-                # stream, and runs beside this sub-step instead of after it.  (The visual generator's four sub-steps are a
-                # cycle — each needs the parameters the previous one wrote: its two train-mode forwards leave that chain.)
-                # Results do not change: same parameters, same dropout offsets (the multi-stream tests pass bit for bit with
-                # it on).  NO GAIN, therefore OFF by default (GANFFN_EARLY_GEN=1 enables it): 35.4 against 35.3 ms per step with
-                # its six streams chosen by _tune_streams (37.8 and 47 ms before that: helper streams that shared a hardware
-                # queue with a main stream).
-                j = i + 1
-                if self.early_gen and j < nsub and self.schedule[j][0] == "G" and smap[j] == smap[i] and \
-                        (kind, who) != ("G", self.schedule[j][1]):
-                    gwho = self.schedule[j][1]
-                    hs = self.streams[self.n_streams + smap[j]]
-                    self._use_scratch(self.n_streams + smap[j])
-                    with torch.cuda.stream(hs):
-                        self._wait_writers(hs, [("G", gwho), ("buf", "G", gwho)])
-                        self._wait_readers(hs, [("buf", "G", gwho)])
-                        early[j] = self.train_gen_forward(gwho, batch, j)
-                        ev = torch.cuda.Event()
-                        ev.record(hs)
-                        self._r(("G", gwho)).reads.append(ev)        # a later writer of these parameters waits for this read
-                        rb = self._r(("buf", "G", gwho))
-                        rb.last_write, rb.reads = ev, []             # (the sub-step itself waits for it as the buffer's writer)
                 trained = (kind, who)
                 other = ("G" if kind == "D" else "D", partner)
                 # pass buffers are resources too (same (net, role) buffer reused by a later sub-step)
@@ -899,9 +897,9 @@ class GanEngine(_Runner):
                     if kind == "D":
                         g_adds = self.train_disc(who, partner, batch, i, pair_slot=pj)
                         if pj is not None:
-                            early[pj] = g_adds
+                            paired[pj] = g_adds
                     else:
-                        self.train_gen(who, partner, batch, i, g_adds=early.get(i))
+                        self.train_gen(who, partner, batch, i, g_adds=paired.get(i))
                     self._done(st, reads=[other], writes=[trained] + bufs)
                 self._cur_stream = None
             self._cur_pg = self.pg
@@ -1015,20 +1013,32 @@ def train_GAN(gens, discs, batches, epochs=1, lr=1e-4, b1=0.5, b2=0.6, process_g
 CLASS_WEIGHTS = [1.2, 0.60072, 0.38066, 0.94019, 0.67924, 0.34332]   # train_IEMOCAP.py:653
 
 
-class Phase2Engine(GanEngine):
+def _module_generators(module, lr, weight_decay):
+    """the three generators of a classifier module as NetStates under its Adam(0.9, 0.999, L2), in the order the module runs them
+    (model.py:1441-1443, 1521-1523)"""
+    return {k: NetState(getattr(module, k + "_generator"), lr, (0.9, 0.999), weight_decay)
+            for k in ("acoustic", "visual", "text")}
+
+
+def _generator_bwd(eng, k, d_out, adds):
+    """one generator's backward from d_out, its all-reduce and its Adam, on the current stream with the workspace eng.ws"""
+    net = eng.G[k]
+    net.grad.zero_()
+    cb, finish = eng._make_reducer(net)
+    eng._net_bwd(net, eng.pass_G[k], d_out, True, adds, True, cb)
+    finish(("G", k))
+
+
+class Phase2Engine(_NetRunner):
     """One step of train_or_eval_model on GAN_FFN: log_softmax(fc(G_a(a) + G_v(v) + G_t(t))), MaskedNLLLoss with
     class weights, backward through the three generators, Adam(lr, weight_decay=l2) on everything.
     The reference re-creates a LambdaLR every batch, which pins the effective lr to its base value."""
 
     def __init__(self, ffn_module, lr=1e-4, weight_decay=0.008, class_weights=CLASS_WEIGHTS, process_group=None,
                  n_buckets=3):
-        gens = {"acoustic": ffn_module.acoustic_generator, "visual": ffn_module.visual_generator,
-                "text": ffn_module.text_generator}
         self.module = ffn_module
-        self.G = {k: NetState(m, lr, (0.9, 0.999), weight_decay) for k, m in gens.items()}
-        self.D = {}
-        self._init_common(next(iter(self.G.values())).slab.device, process_group, n_buckets)
-        self.n_streams, self.use_graph = 1, False
+        self.G = _module_generators(ffn_module, lr, weight_decay)
+        self._init_common(next(iter(self.G.values())).slab.device, process_group, n_buckets, self.G.items())
         self.n_classes = ffn_module.fc.weight.shape[0]
         dev = self.dev
         # fc (100 -> n_classes) parameters as one small slab [weight | bias], 16-byte aligned pieces
@@ -1038,24 +1048,15 @@ class Phase2Engine(GanEngine):
         self.fc_off_b, self.fc_total = fc.offs[1], fc.total
         self.lr, self.wd = lr, weight_decay
         self.class_w = torch.tensor(class_weights, device=dev, dtype=torch.float32) if class_weights is not None else None
-        self._shape = None
         self.loss = torch.zeros(1, device=dev)
-        self._adds = 0
-        self._base_add = 0
-
-    def reserve(self, S, B):
-        """size the pass buffers once for batches of up to (S, B): train / valid / test loaders then never re-allocate"""
-        self._cap_S, self._cap_B = max(getattr(self, "_cap_S", 0), S), max(getattr(self, "_cap_B", 0), B)
 
     def _prepare2(self, S, B):
-        if self._shape == (S, B):
+        fit = self._fit(S, B)
+        if fit == "same":
             return
         C_ = self.n_classes
-        if self._shape is None or S > self._alloc_S or B > self._alloc_B:
-            cS = self._cap_S = max(getattr(self, "_cap_S", 0), S)
-            cB = self._cap_B = max(getattr(self, "_cap_B", 0), B)
-            self._alloc_S, self._alloc_B = cS, cB
-            dev = self.dev
+        if fit == "grow":
+            cS, cB, dev = self._alloc_S, self._alloc_B, self.dev
             self.pass_G = {k: _Pass(n, cS, cB, dev, True) for k, n in self.G.items()}
             n_ws = max(p.n_ws for p in self.pass_G.values())
             f32 = dict(device=dev, dtype=torch.float32)
@@ -1064,7 +1065,6 @@ class Phase2Engine(GanEngine):
                               log_prob=torch.empty(cS * cB * C_, **f32), dlogits=torch.empty(cS * cB * C_, **f32),
                               d_fusion=torch.empty(cS * cB * 100, **f32))
             self.ws2 = torch.zeros(4, **f32)
-        self._shape = (S, B)
         for p_ in self.pass_G.values():
             p_.resize(S, B)
         f = self._flat
@@ -1098,17 +1098,11 @@ class Phase2Engine(GanEngine):
             ops.linear_bwd_raw(self.dlogits, self.fusion, self.fc_w, self.d_fusion, self.fc_grad[:self.fc_w.numel()],
                                self.fc_grad[self.fc_off_b:], T, 100, C_, self.ws)
             for k in ("acoustic", "visual", "text"):
-                net = self.G[k]
-                net.grad.zero_()
-                cb, finish = self._make_reducer(net)
-                self._net_bwd(net, self.pass_G[k], self.d_fusion, True, adds[k], True, cb)
-                finish(("G", k))
+                _generator_bwd(self, k, self.d_fusion, adds[k])
             self.fc.all_reduce(self.pg)
             self.fc.adam(self.lr, self.wd, self.world)
         assert self._adds <= 8, self._adds
         return self.loss, self.log_prob
-
-    predictions = staticmethod(predictions)
 
 
 # ================================================================================================
@@ -1131,12 +1125,12 @@ def _check_max_dialogues(who, n):
     return n
 
 
-class DrnnEngine(GanEngine):
+class DrnnEngine(_NetRunner):
     """One train / eval step of GAN_FFN_DialogueRNN on the C ABI, no autograd graph: the three generators (n_streams = 3
-    runs their forward and backward passes on three HIP streams chosen like GanEngine's; measured NOT faster than one
-    stream on this workload — 15.0-16.5 against 14.9-15.0 ms per step: kernels of different streams do not run side by
-    side, only the dead time between launches overlaps, and the run-to-run spread grows —
-    so one stream is the default), fusion = their sum, BiModel's two
+    runs their forward and backward passes on three HIP streams chosen by _side_streams with its own _tune_slot as probe;
+    measured NOT faster than one stream on this workload — 15.0-16.5 against 14.9-15.0 ms per step: kernels of different
+    streams do not run side by side, only the dead time between launches overlaps, and the run-to-run
+    spread grows — so one stream is the default), fusion = their sum, BiModel's two
     DialogueRNN directions through one chain of launches (ops.drnn_fwd_raw / drnn_bwd_raw), the matching attention
     (ganffn_general2_attention_*), linear + ReLU + dropout, the class head, MaskedNLLLoss with class weights, and Adam
     (lr, L2-coupled weight decay; train_IEMOCAP_DialogueRNN.py:746) on flat slabs: one fused launch per generator and one
@@ -1171,10 +1165,8 @@ class DrnnEngine(GanEngine):
         self.ncell = 12 + len(self.att_keys)                 # tensors per cell in the slab (13 for general: layout unchanged)
         self.acfg = _lib.DrnnAtt(_lib.DRNN_ATT_TYPES[self.att],
                                  int(cf.attention.transform.weight.shape[0]) if self.att == "concat" else 0)
-        gens = {"acoustic": net.acoustic_generator, "visual": net.visual_generator, "text": net.text_generator}
-        self.G = {k: NetState(m, lr, (0.9, 0.999), weight_decay) for k, m in gens.items()}
-        self.D = {}
-        self._init_common(next(iter(self.G.values())).slab.device, process_group, n_buckets)
+        self.G = _module_generators(net, lr, weight_decay)
+        self._init_common(next(iter(self.G.values())).slab.device, process_group, n_buckets, self.G.items())
         dev = self.dev
         self.lr, self.wd = lr, weight_decay
         self.Dm, self.H, self.He, self.Dh2 = cf.D_m, cf.D_g, cf.D_e, bm.linear.weight.shape[0]
@@ -1199,16 +1191,9 @@ class DrnnEngine(GanEngine):
         if process_group is not None:
             self.n_streams = 1           # (one communicator: its in-line collectives must not run on several streams at once)
         self.streams = None                                  # (n_streams > 1: chosen in _prepare5, once the buffers exist)
+        self._tune_x = (None, None)                          # (shape, inputs) of _tune_slot's probe work
         self.loss = torch.zeros(1, device=dev)
-        self._shape = None
-        self._cap_S = self._cap_B = 0
-        self._alloc_P = 0
-        self._adds = 0
-        self._base_add = 0
-
-    def reserve(self, S, B):
-        self._check_SB(S, B)
-        self._cap_S, self._cap_B = max(self._cap_S, S), max(self._cap_B, B)
+        self._alloc_P = 0                                    # parties the recurrence's buffers are sized for
 
     def _check_SB(self, S, B):
         if B > self.max_dialogues or S > 112:
@@ -1218,15 +1203,12 @@ class DrnnEngine(GanEngine):
                              % (self.max_dialogues, _MAX_DIALOGUES_HINT if self.max_dialogues < ops.MAX_DIALOGUES else "", S, B))
 
     def _prepare5(self, S, B, P=2):
-        if self._shape == (S, B, P):
+        fit = self._fit(S, B, P, grow=P > self._alloc_P)
+        if fit == "same":
             return
-        self._check_SB(S, B)
-        if self._shape is None or S > self._alloc_S or B > self._alloc_B or P > self._alloc_P:
-            cS = self._cap_S = max(self._cap_S, S)
-            cB = self._cap_B = max(self._cap_B, B)
-            cP = max(self._alloc_P, P)
-            self._alloc_S, self._alloc_B, self._alloc_P = cS, cB, cP
-            dev = self.dev
+        if fit == "grow":
+            cS, cB, dev = self._alloc_S, self._alloc_B, self.dev
+            cP = self._alloc_P = max(self._alloc_P, P)
             self.pass_G = {k: _Pass(n, cS, cB, dev, True) for k, n in self.G.items()}
             f32 = dict(device=dev, dtype=torch.float32)
             self.ws3 = {k: torch.empty(p_.n_ws, **f32) for k, p_ in self.pass_G.items()}     # one workspace per generator stream
@@ -1245,7 +1227,6 @@ class DrnnEngine(GanEngine):
                            dU_f=z(T * self.Dm), dU_b=z(T * self.Dm), saved_f=z(n_saved), saved_b=z(n_saved), ws_f=z(n_ws),
                            ws_b=z(n_ws), lin_ws=z(int(lib.ganffn_linear_bwd_workspace_floats(T, D2, D2)) + 64))
             self.ws2 = torch.zeros(4, **f32)
-        self._shape = (S, B, P)
         for p_ in self.pass_G.values():
             p_.resize(S, B)
         self.cfg_train = _lib.DrnnCfg(S, B, self.Dm, self.H, self.He, self.p_rec, 1)
@@ -1256,7 +1237,7 @@ class DrnnEngine(GanEngine):
 
     def _tune_slot(self, i):
         k = ("acoustic", "visual", "text")[i % 3]
-        if getattr(self, "_tune_x", (None, None))[0] != self._shape:
+        if self._tune_x[0] != self._shape:
             S, B = self._shape[:2]
             self._tune_x = (self._shape, {m: torch.zeros(S, B, self.G[m].E, device=self.dev) for m in self.G})
         self.ws = self.ws3[k]
@@ -1430,20 +1411,13 @@ class DrnnEngine(GanEngine):
             fork = torch.cuda.Event()
             fork.record(cur)
         for i, k in enumerate(keys):
-            net = self.G[k]
             self.ws = self.ws3[k]
-
-            def bwd():
-                net.grad.zero_()
-                cb, finish = self._make_reducer(net)
-                self._net_bwd(net, self.pass_G[k], d_fusion, True, adds[k], True, cb)
-                finish(("G", k))
             if self.streams is not None and self.streams[i].cuda_stream != cur.cuda_stream:
                 self.streams[i].wait_event(fork)
                 with torch.cuda.stream(self.streams[i]):
-                    bwd()
+                    _generator_bwd(self, k, d_fusion, adds[k])
             else:
-                bwd()
+                _generator_bwd(self, k, d_fusion, adds[k])
         if red_h is not None:
             red_h.finish()
         self.head.adam(self.lr, self.wd, self.world)
@@ -1453,8 +1427,6 @@ class DrnnEngine(GanEngine):
                     cur.wait_stream(s_)
         assert self._adds <= 6, self._adds
         return self.loss, log_prob
-
-    predictions = staticmethod(predictions)
 
 
 # ================================================================================================
@@ -1513,14 +1485,6 @@ class MeldEngine(_Runner):
         self.n_adds = max(1, self.L - 1)                      # one Philox offset per inter-layer dropout call
         self.loss = torch.zeros(1, device=dev)
         self.alpha = None
-        self._shape = None
-        self._cap_S = self._cap_B = 0
-        self._base_add = 0
-
-    def reserve(self, S, B):
-        """size every step buffer once for batches of up to (S, B): train / valid / test loaders then never re-allocate"""
-        self._check_SB(S, B)
-        self._cap_S, self._cap_B = max(self._cap_S, S), max(self._cap_B, B)
 
     def _check_SB(self, S, B):
         if B > self.max_dialogues or S > 128:
@@ -1530,13 +1494,11 @@ class MeldEngine(_Runner):
                              % (self.max_dialogues, _MAX_DIALOGUES_HINT if self.max_dialogues < ops.MAX_DIALOGUES else "", S, B))
 
     def _prepare(self, S, B):
-        if self._shape == (S, B):
+        fit = self._fit(S, B)
+        if fit == "same":
             return
-        self._check_SB(S, B)
-        if self._shape is None or S > self._alloc_S or B > self._alloc_B:
-            cS = self._cap_S = max(self._cap_S, S)
-            cB = self._cap_B = max(self._cap_B, B)
-            self._alloc_S, self._alloc_B = cS, cB
+        if fit == "grow":
+            cS, cB = self._alloc_S, self._alloc_B
             lib = _lib.load()
             cfgc = _lib.LstmStackCfg(cS, cB, self.Dm, self.He, self.L, self.p_lstm, 1)
             fam = "ganffn_lstm_stack_batch_" if cB > 32 else "ganffn_lstm_stack_"       # (the same sizes as functions of B)
@@ -1550,7 +1512,6 @@ class MeldEngine(_Runner):
                            d_res=z(T * D2), d_att=z(T * D2), d_xq=z(T * D2), d_mem=z(T * D2), d_tr=z(T * D2), d_em=z(T * D2),
                            saved=z(n_saved), ws=z(n_ws), lin_ws=z(int(lib.ganffn_linear_bwd_workspace_floats(T, D2, D2)) + 64))
             self.ws2 = torch.zeros(4, device=self.dev, dtype=torch.float32)
-        self._shape = (S, B)
         self.cfg_train = _lib.LstmStackCfg(S, B, self.Dm, self.He, self.L, self.p_lstm, 1)
         self.cfg_eval = _lib.LstmStackCfg(S, B, self.Dm, self.He, self.L, self.p_lstm, 0)
         self.alpha = self._f["alpha"][:B * S * S].view(B, S, S)
@@ -1606,5 +1567,3 @@ class MeldEngine(_Runner):
         self.params.all_reduce(self.pg)
         self.params.adam(self.lr, self.wd, self.world)
         return self.loss, log_prob
-
-    predictions = staticmethod(predictions)

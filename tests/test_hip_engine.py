@@ -342,11 +342,10 @@ def test_engines_of_one_process_share_their_side_streams():
         eng.iteration(gan_batch(S=S, B=B))
         eng.synchronize()
         torch.cuda.synchronize()
-        # (three sub-step streams; with the early generator forward on, three helper streams follow them in the list)
-        assert len(eng.streams) in (3, 6) and len({s.cuda_stream for s in eng.streams}) == len(eng.streams)
+        assert len(eng.streams) == 3 and len({s.cuda_stream for s in eng.streams}) == len(eng.streams)
         handles.append([s.cuda_stream for s in eng.streams])
     assert handles[0] == handles[1]
-    key = (str(eng.dev), (0, 0, -1) * (2 if eng.early_gen else 1))
+    key = (str(eng.dev), (0, 0, -1))
     assert engine._STREAMS[key][1] >= 94 * 8 or handles[2] == handles[0]
 
 
