@@ -120,6 +120,10 @@ SIGNATURES = {
     "ganffn_lstm_stack_batch_workspace_floats": (_L, [C.POINTER(LstmStackCfg)]),
     "ganffn_lstm_stack_batch_fwd": (_I, [C.POINTER(LstmStackCfg)] + [_P] * 9 + [_U64, _P]),
     "ganffn_lstm_stack_batch_bwd": (_I, [C.POINTER(LstmStackCfg)] + [_P] * 13 + [_U64, _P]),
+    "ganffn_lstm_packed_layer_fwd": (_I, [C.POINTER(LstmCfg)] + [_P] * 10),
+    "ganffn_lstm_packed_layer_bwd": (_I, [C.POINTER(LstmCfg)] + [_P] * 14),
+    "ganffn_lstm_stack_packed_fwd": (_I, [C.POINTER(LstmStackCfg)] + [_P] * 10 + [_U64, _P]),
+    "ganffn_lstm_stack_packed_bwd": (_I, [C.POINTER(LstmStackCfg)] + [_P] * 14 + [_U64, _P]),
     "ganffn_meld_head_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ganffn_meld_head_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ganffn_zero_floats": (_I, [_P, _L, _P]),

@@ -25,6 +25,14 @@
 // ganffn_lstm_stack_fwd / _bwd (end of the file) chain the L layers of the stack in one call, with nn.LSTM's inter-layer dropout
 // (Philox site 64 + l, offset base + l) between them: the same launches as L per-layer calls and L - 1 ganffn_dropout calls, so
 // the same bits — what engine.MeldEngine runs instead of ops.lstm_forward's autograd chain.
+//
+// PACKED form (ganffn_lstm_packed_* / ganffn_lstm_stack_packed_*; an extension: the reference never packs): lengths[b] (int32, on
+// the device, only ever compared with a time index) is the number of real steps of dialogue b.  At a time index tm >= lengths[b]
+// the gate kernels SELECT zeros, in both directions: forward c_t = 0, h_t = 0 (into out[tm]) and zero saved gates, whatever the
+// products computed for that row; backward dG = 0 for the four gates and a zero dc for the earlier step, whatever dh / d_out hold
+// there.  That is pack_padded_sequence -> nn.LSTM -> pad_packed_sequence(total_length = S): the reverse direction enters step
+// len - 1 with zero state (out[tm + 1] and c[tm + 1] are zero), the outputs past the end are zero, and the deferred GEMMs see
+// zero dG rows at padded tokens, so nothing else changes — the same launches as the unpacked step, no host read of lengths.
 #include "common.h"
 
 namespace ganffn {
@@ -39,9 +47,12 @@ struct LstmGateDir {
     float* c;              // [B x H]
     float* h_out;          // h_t into out[t][:, d H .. (d + 1) H): leading dimension 2H
     float* gates;          // [B x 4H] activated i | f | g | o, kept for the backward
+    int tm;                // this step's time index (read by the packed form only)
 };
-struct LstmGateArgs { LstmGateDir d[2]; int B, H; };
+struct LstmGateArgs { LstmGateDir d[2]; int B, H; const int* lengths; };
 
+// PACKED: dialogue b at a time index tm >= lengths[b] gets c = h = gates = 0 by a select (the row's products are discarded)
+template <bool PACKED>
 __global__ __launch_bounds__(256) void lstm_gate_fwd_kernel(LstmGateArgs a) {
     const LstmGateDir& q = a.d[blockIdx.y];
     const int idx = blockIdx.x * 256 + threadIdx.x;
@@ -51,10 +62,18 @@ __global__ __launch_bounds__(256) void lstm_gate_fwd_kernel(LstmGateArgs a) {
     const float i = sigmoidf_(G[j]), f = sigmoidf_(G[H + j]), g = tanhf(G[2 * H + j]), o = sigmoidf_(G[3 * H + j]);
     const float cp = q.c_prev ? q.c_prev[(size_t)b * H + j] : 0.f;
     const float c = f * cp + i * g;
-    q.c[(size_t)b * H + j] = c;
-    q.h_out[(size_t)b * 2 * H + j] = o * tanhf(c);
+    const float h = o * tanhf(c);
     float* S = q.gates + (size_t)b * 4 * H;
-    S[j] = i; S[H + j] = f; S[2 * H + j] = g; S[3 * H + j] = o;
+    if (PACKED) {
+        const bool valid = q.tm < a.lengths[b];
+        q.c[(size_t)b * H + j] = valid ? c : 0.f;
+        q.h_out[(size_t)b * 2 * H + j] = valid ? h : 0.f;
+        S[j] = valid ? i : 0.f; S[H + j] = valid ? f : 0.f; S[2 * H + j] = valid ? g : 0.f; S[3 * H + j] = valid ? o : 0.f;
+    } else {
+        q.c[(size_t)b * H + j] = c;
+        q.h_out[(size_t)b * 2 * H + j] = h;
+        S[j] = i; S[H + j] = f; S[2 * H + j] = g; S[3 * H + j] = o;
+    }
 }
 
 struct LstmGateBwdDir {
@@ -64,9 +83,13 @@ struct LstmGateBwdDir {
     const float* gates;           // activated i | f | g | o of this step
     const float* c; const float* c_prev;   // c_t, c_{t-1} (null: zeros)
     float* dG;                    // [B x 4H] gradient wrt the pre-activations of this step
+    int tm;                       // this step's time index (read by the packed form only)
 };
-struct LstmGateBwdArgs { LstmGateBwdDir d[2]; int B, H; };
+struct LstmGateBwdArgs { LstmGateBwdDir d[2]; int B, H; const int* lengths; };
 
+// PACKED: dialogue b at a time index tm >= lengths[b] gets dG = 0 and hands dc = 0 to the earlier step, by a select and not a
+// product with 0: whatever d_out / dh hold at a padded position (NaN included) cannot spread
+template <bool PACKED>
 __global__ __launch_bounds__(256) void lstm_gate_bwd_kernel(LstmGateBwdArgs a) {
     const LstmGateBwdDir& q = a.d[blockIdx.y];
     const int idx = blockIdx.x * 256 + threadIdx.x;
@@ -79,11 +102,16 @@ __global__ __launch_bounds__(256) void lstm_gate_bwd_kernel(LstmGateBwdArgs a) {
     const float dh = q.dh[(size_t)b * q.ld_dh + j];
     const float dc = dh * o * (1.f - tc * tc) + (q.dc_zero ? 0.f : q.dc[(size_t)b * H + j]);
     float* dG = q.dG + (size_t)b * 4 * H;
-    dG[j] = dc * g * i * (1.f - i);
-    dG[H + j] = dc * cp * f * (1.f - f);
-    dG[2 * H + j] = dc * i * (1.f - g * g);
-    dG[3 * H + j] = dh * tc * o * (1.f - o);
-    q.dc[(size_t)b * H + j] = dc * f;
+    const float di = dc * g * i * (1.f - i), df = dc * cp * f * (1.f - f), dg = dc * i * (1.f - g * g), dO = dh * tc * o * (1.f - o);
+    const float dcp = dc * f;
+    if (PACKED) {
+        const bool valid = q.tm < a.lengths[b];
+        dG[j] = valid ? di : 0.f; dG[H + j] = valid ? df : 0.f; dG[2 * H + j] = valid ? dg : 0.f; dG[3 * H + j] = valid ? dO : 0.f;
+        q.dc[(size_t)b * H + j] = valid ? dcp : 0.f;
+    } else {
+        dG[j] = di; dG[H + j] = df; dG[2 * H + j] = dg; dG[3 * H + j] = dO;
+        q.dc[(size_t)b * H + j] = dcp;
+    }
 }
 
 // out[n] += sum over rows of X[row][n], rows in order (the two bias gradients of a direction are this same sum)
@@ -168,10 +196,11 @@ using namespace ganffn;
 extern "C" int64_t ganffn_lstm_saved_floats(const ganffn_lstm_cfg* c) { return check_lstm(c) ? -1 : lstm_saved(c).total; }
 extern "C" int64_t ganffn_lstm_workspace_floats(const ganffn_lstm_cfg* c) { return check_lstm(c) ? -1 : lstm_ws(c); }
 
-// maxB: 32 behind the entry points that always had that limit, GANFFN_MAX_DIALOGUES behind the _batch_ ones
+// maxB: 32 behind the entry points that always had that limit, GANFFN_MAX_DIALOGUES behind the _batch_ and _packed_ ones;
+// lengths: null behind every entry point but the _packed_ ones (which refuse a null one themselves)
 static int lstm_layer_fwd(const ganffn_lstm_cfg* c, const float* x, const float* const* w_ih, const float* const* w_hh,
                           const float* const* b_ih, const float* const* b_hh, float* out, float* saved, float* workspace,
-                          void* stream, int maxB) {
+                          void* stream, int maxB, const int* lengths = nullptr) {
     GF_TRY(check_lstm(c, maxB));
     GF_CHECK_ARG(x && w_ih && w_hh && b_ih && b_hh && out && saved && workspace, "lstm_layer_fwd: null pointer");
     GF_CHECK_ARG(aligned16(x) && aligned16(out) && aligned16(saved) && aligned16(workspace), "lstm_layer_fwd: buffers must be 16-byte aligned");
@@ -192,7 +221,7 @@ static int lstm_layer_fwd(const ganffn_lstm_cfg* c, const float* x, const float*
     for (int t = 0; t < S; ++t) {
         SkinnyGroup sg;
         LstmGateArgs ga;
-        ga.B = B; ga.H = H;
+        ga.B = B; ga.H = H; ga.lengths = lengths;
         for (int d = 0; d < 2; ++d) {
             const int64_t tm = d == 0 ? t : S - 1 - t, tp = d == 0 ? tm - 1 : tm + 1;      // this step's / the previous step's time index
             float* Gd = G + (int64_t)d * B * 4 * H;
@@ -202,7 +231,7 @@ static int lstm_layer_fwd(const ganffn_lstm_cfg* c, const float* x, const float*
             // (first step: h_{-1} = 0 — the product runs on this step's own, still unwritten, c slot, zeroed below)
             sg.p[d] = SkinnyProb{t == 0 ? cS + tm * B * H : out + tp * B * 2 * H + d * H, t == 0 ? H : 2 * H, w_hh[d], H, xgt, 4 * H, nullptr,
                                  b_hh[d], Gd, 4 * H, B, 4 * H, H};
-            ga.d[d] = LstmGateDir{Gd, t == 0 ? nullptr : cS + tp * B * H, cS + tm * B * H, out + tm * B * 2 * H + d * H, gS + tm * B * 4 * H};
+            ga.d[d] = LstmGateDir{Gd, t == 0 ? nullptr : cS + tp * B * H, cS + tm * B * H, out + tm * B * 2 * H + d * H, gS + tm * B * 4 * H, (int)tm};
         }
         if (t == 0) {
             // the first step's h_prev operand: this step's own (not yet written) c slot, zeroed — h_{-1} = 0 without a special kernel
@@ -212,7 +241,8 @@ static int lstm_layer_fwd(const ganffn_lstm_cfg* c, const float* x, const float*
             }
         }
         GF_TRY(launch_skinny(sg, 2, false, st));
-        hipLaunchKernelGGL(lstm_gate_fwd_kernel, ggrid, dim3(256), 0, st, ga);
+        if (lengths) hipLaunchKernelGGL(lstm_gate_fwd_kernel<true>, ggrid, dim3(256), 0, st, ga);
+        else hipLaunchKernelGGL(lstm_gate_fwd_kernel<false>, ggrid, dim3(256), 0, st, ga);
         GF_LAUNCH_CHECK();
     }
     return 0;
@@ -227,7 +257,7 @@ extern "C" int ganffn_lstm_layer_fwd(const ganffn_lstm_cfg* c, const float* x, c
 static int lstm_layer_bwd(const ganffn_lstm_cfg* c, const float* d_out, const float* x, const float* out,
                           const float* const* w_ih, const float* const* w_hh, float* dx, float* const* gw_ih,
                           float* const* gw_hh, float* const* gb_ih, float* const* gb_hh, const float* saved,
-                          float* workspace, void* stream, int maxB) {
+                          float* workspace, void* stream, int maxB, const int* lengths = nullptr) {
     GF_TRY(check_lstm(c, maxB));
     GF_CHECK_ARG(d_out && x && out && w_ih && w_hh && saved && workspace, "lstm_layer_bwd: null pointer");
     GF_CHECK_ARG(aligned16(d_out) && aligned16(x) && aligned16(out) && aligned16(saved) && aligned16(workspace) && (!dx || aligned16(dx)),
@@ -244,7 +274,7 @@ static int lstm_layer_bwd(const ganffn_lstm_cfg* c, const float* d_out, const fl
     const dim3 ggrid((B * H + 255) / 256, 2);
     for (int t = S - 1; t >= 0; --t) {              // step index of the forward loop, walked backwards
         LstmGateBwdArgs gb;
-        gb.B = B; gb.H = H;
+        gb.B = B; gb.H = H; gb.lengths = lengths;
         for (int d = 0; d < 2; ++d) {
             const int64_t tm = d == 0 ? t : S - 1 - t, tp = d == 0 ? tm - 1 : tm + 1;
             const float* cS = saved + so.c + d * T * H;
@@ -252,9 +282,10 @@ static int lstm_layer_bwd(const ganffn_lstm_cfg* c, const float* d_out, const fl
             const bool first = t == S - 1;          // first backward step: no later step feeds dh / dc
             gb.d[d] = LstmGateBwdDir{first ? d_out + tm * B * 2 * H + d * H : dh + (int64_t)d * B * H, first ? 2 * H : H, dc + (int64_t)d * B * H,
                                      first ? 1 : 0, gS + tm * B * 4 * H, cS + tm * B * H, t == 0 ? nullptr : cS + tp * B * H,
-                                     dG + d * T * 4 * H + tm * B * 4 * H};
+                                     dG + d * T * 4 * H + tm * B * 4 * H, (int)tm};
         }
-        hipLaunchKernelGGL(lstm_gate_bwd_kernel, ggrid, dim3(256), 0, st, gb);
+        if (lengths) hipLaunchKernelGGL(lstm_gate_bwd_kernel<true>, ggrid, dim3(256), 0, st, gb);
+        else hipLaunchKernelGGL(lstm_gate_bwd_kernel<false>, ggrid, dim3(256), 0, st, gb);
         GF_LAUNCH_CHECK();
         if (t > 0) {
             // dh_{t-1} = d_out[t-1]'s half + dG_t W_hh   ([B x 4H] x [4H x H], the weight row-wise as stored)
@@ -311,7 +342,7 @@ extern "C" int64_t ganffn_lstm_stack_workspace_floats(const ganffn_lstm_stack_cf
 // layer but the last: site SITE_LSTM0 + l, offset rng_offset_add + l — what ops.lstm_forward issues as separate calls.
 static int lstm_stack_fwd(const ganffn_lstm_stack_cfg* c, const float* x, const float* const* w_ih, const float* const* w_hh,
                           const float* const* b_ih, const float* const* b_hh, float* out, float* saved, float* workspace,
-                          const uint64_t* rng, uint64_t rng_offset_add, void* stream, int maxB) {
+                          const uint64_t* rng, uint64_t rng_offset_add, void* stream, int maxB, const int* lengths = nullptr) {
     GF_TRY(check_lstm_stack(c, maxB));
     GF_CHECK_ARG(x && w_ih && w_hh && b_ih && b_hh && out && saved && workspace, "lstm_stack_fwd: null pointer");
     const bool drop = c->train && c->p > 0.f && c->L > 1;
@@ -324,7 +355,7 @@ static int lstm_stack_fwd(const ganffn_lstm_stack_cfg* c, const float* x, const 
         const bool last = l + 1 == c->L;
         float* o = last ? out : saved + so.outs + (int64_t)l * 2 * T * 2 * H;
         GF_TRY(lstm_layer_fwd(&lc, in, w_ih + 2 * l, w_hh + 2 * l, b_ih + 2 * l, b_hh + 2 * l, o, saved + l * so.layer_stride,
-                              workspace, stream, maxB));
+                              workspace, stream, maxB, lengths));
         in = o;
         if (!last && drop) {
             float* dr = o + T * 2 * H;
@@ -346,7 +377,8 @@ extern "C" int ganffn_lstm_stack_fwd(const ganffn_lstm_stack_cfg* c, const float
 static int lstm_stack_bwd(const ganffn_lstm_stack_cfg* c, const float* d_out, const float* x, const float* out,
                           const float* const* w_ih, const float* const* w_hh, float* dx, float* const* gw_ih,
                           float* const* gw_hh, float* const* gb_ih, float* const* gb_hh, const float* saved,
-                          float* workspace, const uint64_t* rng, uint64_t rng_offset_add, void* stream, int maxB) {
+                          float* workspace, const uint64_t* rng, uint64_t rng_offset_add, void* stream, int maxB,
+                          const int* lengths = nullptr) {
     GF_TRY(check_lstm_stack(c, maxB));
     GF_CHECK_ARG(d_out && x && out && w_ih && w_hh && saved && workspace, "lstm_stack_bwd: null pointer");
     const bool drop = c->train && c->p > 0.f && c->L > 1;
@@ -363,7 +395,7 @@ static int lstm_stack_bwd(const ganffn_lstm_stack_cfg* c, const float* d_out, co
         float* dxl = l == 0 ? dx : dbuf + (int64_t)(l & 1) * T * 2 * H;
         GF_TRY(lstm_layer_bwd(&lc, d, in, o, w_ih + 2 * l, w_hh + 2 * l, dxl, gw_ih ? gw_ih + 2 * l : nullptr,
                               gw_hh ? gw_hh + 2 * l : nullptr, gb_ih ? gb_ih + 2 * l : nullptr, gb_hh ? gb_hh + 2 * l : nullptr,
-                              saved + l * so.layer_stride, workspace, stream, maxB));
+                              saved + l * so.layer_stride, workspace, stream, maxB, lengths));
         if (l > 0 && drop)
             GF_TRY(launch_dropout(dxl, dxl, (int)T, 2 * (int)H, c->p, SITE_LSTM0 + (l - 1), rng, rng_offset_add + (l - 1), 1, (hipStream_t)stream));
         d = dxl;
@@ -410,4 +442,38 @@ extern "C" int ganffn_lstm_stack_batch_bwd(const ganffn_lstm_stack_cfg* c, const
                                            float* workspace, const uint64_t* rng, uint64_t rng_offset_add, void* stream) {
     return lstm_stack_bwd(c, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, workspace, rng, rng_offset_add, stream,
                           GANFFN_MAX_DIALOGUES);
+}
+
+// ---- packed sequences: lengths[b] real steps per dialogue ------------------------------------------------------------------
+// The _batch_ bodies with the length-aware gate kernels (the rule: top of the file): same layouts, sizes (ganffn_lstm_batch_*_floats /
+// ganffn_lstm_stack_batch_*_floats) and launches.  lengths: int32 [B] on the device, never read by the host.
+extern "C" int ganffn_lstm_packed_layer_fwd(const ganffn_lstm_cfg* c, const int32_t* lengths, const float* x, const float* const* w_ih,
+                                            const float* const* w_hh, const float* const* b_ih, const float* const* b_hh, float* out,
+                                            float* saved, float* workspace, void* stream) {
+    GF_CHECK_ARG(lengths, "lstm_packed_layer_fwd: null lengths");
+    return lstm_layer_fwd(c, x, w_ih, w_hh, b_ih, b_hh, out, saved, workspace, stream, GANFFN_MAX_DIALOGUES, lengths);
+}
+extern "C" int ganffn_lstm_packed_layer_bwd(const ganffn_lstm_cfg* c, const int32_t* lengths, const float* d_out, const float* x,
+                                            const float* out, const float* const* w_ih, const float* const* w_hh, float* dx,
+                                            float* const* gw_ih, float* const* gw_hh, float* const* gb_ih, float* const* gb_hh,
+                                            const float* saved, float* workspace, void* stream) {
+    GF_CHECK_ARG(lengths, "lstm_packed_layer_bwd: null lengths");
+    return lstm_layer_bwd(c, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, workspace, stream, GANFFN_MAX_DIALOGUES,
+                          lengths);
+}
+extern "C" int ganffn_lstm_stack_packed_fwd(const ganffn_lstm_stack_cfg* c, const int32_t* lengths, const float* x,
+                                            const float* const* w_ih, const float* const* w_hh, const float* const* b_ih,
+                                            const float* const* b_hh, float* out, float* saved, float* workspace, const uint64_t* rng,
+                                            uint64_t rng_offset_add, void* stream) {
+    GF_CHECK_ARG(lengths, "lstm_stack_packed_fwd: null lengths");
+    return lstm_stack_fwd(c, x, w_ih, w_hh, b_ih, b_hh, out, saved, workspace, rng, rng_offset_add, stream, GANFFN_MAX_DIALOGUES, lengths);
+}
+extern "C" int ganffn_lstm_stack_packed_bwd(const ganffn_lstm_stack_cfg* c, const int32_t* lengths, const float* d_out, const float* x,
+                                            const float* out, const float* const* w_ih, const float* const* w_hh, float* dx,
+                                            float* const* gw_ih, float* const* gw_hh, float* const* gb_ih, float* const* gb_hh,
+                                            const float* saved, float* workspace, const uint64_t* rng, uint64_t rng_offset_add,
+                                            void* stream) {
+    GF_CHECK_ARG(lengths, "lstm_stack_packed_bwd: null lengths");
+    return lstm_stack_bwd(c, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, workspace, rng, rng_offset_add, stream,
+                          GANFFN_MAX_DIALOGUES, lengths);
 }

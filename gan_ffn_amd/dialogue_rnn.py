@@ -264,11 +264,17 @@ class MELDLSTMModel(nn.Module):
     branch / exist on the reference object.  On the GPU the LSTM recurrence runs on the build's own kernels (csrc/lstm.hip
     through ops.lstm_forward: hoisted input products, one skinny MFMA product + one gate launch per step for both directions,
     deferred weight gradients) with `self.lstm`'s parameters — round 5; until then MIOpen's; the attention is the batched
-    general2 kernel used by BiModel."""
+    general2 kernel used by BiModel.
+    packed (default False: the reference's padded run, model.py:546) is an extension the reference does not have: the LSTM runs
+    on packed sequences — every dialogue for its own umask.sum(1) steps, zero output past its end, the reverse direction starting
+    at its last real utterance — so a dialogue's prediction no longer depends on how far its batch is padded.  `umask` must then be
+    a PREFIX mask (ones for the real utterances, then zeros: what every loader of the project produces).  A plain attribute, not a
+    parameter or buffer: the state_dict is the same either way."""
 
-    def __init__(self, D_m, D_e, D_h, n_classes=7, dropout=0.5):
+    def __init__(self, D_m, D_e, D_h, n_classes=7, dropout=0.5, packed=False):
         super().__init__()
         self.n_classes = n_classes
+        self.packed = bool(packed)
         self.dropout = nn.Dropout(dropout)
         self.lstm = nn.LSTM(input_size=D_m, hidden_size=D_e, num_layers=4, bidirectional=True, dropout=dropout)
         self.matchatt = MatchingAttention(2 * D_e, 2 * D_e, att_type="general2")
@@ -279,7 +285,12 @@ class MELDLSTMModel(nn.Module):
         if U.is_cuda:
             # the recurrence on the HIP kernels (csrc/lstm.hip), with self.lstm's own parameters (same state_dict keys)
             from . import ops
-            emotions = ops.lstm_forward(U, self.lstm, self.training)
+            lengths = umask.sum(1).to(torch.int32) if self.packed else None       # on the device: no host read
+            emotions = ops.lstm_forward(U, self.lstm, self.training, lengths=lengths)
+        elif self.packed:
+            # CPU tensors: torch's own packing (pack_padded_sequence wants its lengths on the host)
+            seq = nn.utils.rnn.pack_padded_sequence(U, umask.sum(1).to(torch.int64).cpu(), enforce_sorted=False)
+            emotions, _ = nn.utils.rnn.pad_packed_sequence(self.lstm(seq)[0], total_length=U.shape[0])
         else:
             emotions, _ = self.lstm(U)      # CPU tensors: stock torch (the fixtures' CPU check; the product path is the GPU one)
         alpha, alpha_f, alpha_b = [], [], []

@@ -1444,11 +1444,15 @@ class MeldEngine(_Runner):
     Limits (ValueError; MELDLSTMModel under autograd — the module path — runs the rest): at most max_dialogues dialogues (32 ..
     ops.MAX_DIALOGUES, default 32: a capacity — up to 32 dialogues run ganffn_lstm_stack_*, more ganffn_lstm_stack_batch_*, decided
     from B alone) of at most 128 utterances per step, 2 D_e <= 1024, D_m and D_e multiples of 4, at most 16 classes.
+    packed = True (default False; an extension the reference does not have, MELDLSTMModel(packed=True)'s step): the LSTM runs on
+    packed sequences — lengths = umask.sum(1) as int32, derived on the device every step (umask must be a prefix mask), through
+    ganffn_lstm_stack_packed_* for any B <= max_dialogues: the same launches; everything else in the step is unchanged.
     Data-parallel over dialogues like Phase2Engine: the gradient slab is all-reduced in-line on the step's stream (through
     GradReducer under GANFFN_DP_MODE=buckets), Adam divides by the world size."""
 
-    def __init__(self, model, lr=3e-4, weight_decay=1e-4, class_weights=None, process_group=None, max_dialogues=32):
+    def __init__(self, model, lr=3e-4, weight_decay=1e-4, class_weights=None, process_group=None, max_dialogues=32, packed=False):
         self.max_dialogues = _check_max_dialogues("MeldEngine", max_dialogues)
+        self.packed = bool(packed)
         self.module = model
         lstm = model.lstm
         if not (lstm.bidirectional and not lstm.batch_first and lstm.proj_size == 0 and lstm.bias):
@@ -1539,8 +1543,12 @@ class MeldEngine(_Runner):
         n_t = 8 * self.L
         w_t, b_t, w_s, b_s = (self._p(n_t + j) for j in range(4))
         # ---- forward: LSTM stack -> transform -> general2 attention -> hardswish head -> loss       (model.py:546-560)
-        fam = "ganffn_lstm_stack_batch_" if B > 32 else "ganffn_lstm_stack_"
-        _lib.call(fam + "fwd", C.byref(cfg), P(text), w_ih, w_hh, b_ih, b_hh, P(f["emotions"]), P(f["saved"]), P(f["ws"]),
+        if self.packed:
+            lengths = umask.sum(1).to(torch.int32)          # on the device, no host read; alive until the backward is enqueued
+            fam, head = "ganffn_lstm_stack_packed_", (C.byref(cfg), P(lengths))
+        else:
+            fam, head = "ganffn_lstm_stack_batch_" if B > 32 else "ganffn_lstm_stack_", (C.byref(cfg),)
+        _lib.call(fam + "fwd", *head, P(text), w_ih, w_hh, b_ih, b_hh, P(f["emotions"]), P(f["saved"]), P(f["ws"]),
                   P(rng), C.c_uint64(base), st)
         ops.linear_fwd_raw(f["emotions"], w_t, b_t, f["xq"], T, D2, D2)
         _lib.call("ganffn_general2_attention_fwd", P(f["xq"]), P(f["emotions"]), P(umask), P(f["att"]), P(f["alpha"]), P(f["tanh_s"]),
@@ -1562,7 +1570,7 @@ class MeldEngine(_Runner):
         # d emotions = the residual + the attention's memory side + its query side through transform
         _lib.call("ganffn_add3", P(f["d_res"]), P(f["d_mem"]), P(f["d_tr"]), P(f["d_em"]), C.c_int64(T * D2), st)
         g_ih, g_hh, gb_ih, gb_hh = self._g
-        _lib.call(fam + "bwd", C.byref(cfg), P(f["d_em"]), P(text), P(f["emotions"]), w_ih, w_hh, None, g_ih, g_hh, gb_ih,
+        _lib.call(fam + "bwd", *head, P(f["d_em"]), P(text), P(f["emotions"]), w_ih, w_hh, None, g_ih, g_hh, gb_ih,
                   gb_hh, P(f["saved"]), P(f["ws"]), P(rng), C.c_uint64(base), st)
         self.params.all_reduce(self.pg)
         self.params.adam(self.lr, self.wd, self.world)

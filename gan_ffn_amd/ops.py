@@ -791,6 +791,71 @@ def dialogue_rnn_run(cells, Us, qmasks, training):
 SITE_LSTM = 64          # + layer: the dropout nn.LSTM(dropout=p) applies to the output of every layer but the last
 
 
+def _lstm_layer_fwd(ctx, x, lengths, params):
+    """the forward of LstmLayerFn (lengths None) and LstmPackedLayerFn: chunks of MAX_DIALOGUES, lengths sliced with the batch"""
+    _need_gpu(x, *params)
+    x = _f32c(x)
+    p = [_f32c(t.detach()) for t in params]          # w_ih0, w_hh0, b_ih0, b_hh0, w_ih1, w_hh1, b_ih1, b_hh1
+    S, B, In = x.shape
+    H = p[1].shape[1]
+    if lengths is not None:
+        _need_gpu(lengths)
+        if lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,):
+            raise ValueError("lstm: lengths must be an int32 tensor of shape (%d,) on the device; got %s %s"
+                             % (B, lengths.dtype, tuple(lengths.shape)))
+        lengths = lengths.contiguous()
+    out = torch.empty(S, B, 2 * H, device=x.device, dtype=torch.float32)
+    chunks = []
+    for b0 in range(0, B, MAX_DIALOGUES):
+        b1 = min(B, b0 + MAX_DIALOGUES)
+        cfg = _lib.LstmCfg(S, b1 - b0, In, H)
+        fam = "ganffn_lstm_batch_" if b1 - b0 > 32 or lengths is not None else "ganffn_lstm_"
+        n_saved = int(getattr(_lib.load(), fam + "saved_floats")(C.byref(cfg)))
+        n_ws = int(getattr(_lib.load(), fam + "workspace_floats")(C.byref(cfg)))
+        if n_saved < 0 or n_ws < 0:
+            _lib.check(-1, fam + "*_floats")
+        xc = x if (b0, b1) == (0, B) else x[:, b0:b1].contiguous()
+        oc = out if (b0, b1) == (0, B) else torch.empty(S, b1 - b0, 2 * H, device=x.device, dtype=torch.float32)
+        saved = torch.empty(n_saved, device=x.device, dtype=torch.float32)
+        ws = torch.empty(n_ws, device=x.device, dtype=torch.float32)
+        lc = None if lengths is None else lengths[b0:b1]          # (a slice of a contiguous vector: contiguous, 4-byte aligned)
+        head = (fam + "layer_fwd", C.byref(cfg)) if lc is None else ("ganffn_lstm_packed_layer_fwd", C.byref(cfg), _ptr(lc))
+        _lib.call(*head, _ptr(xc), _ptr_array([p[0], p[4]]), _ptr_array([p[1], p[5]]),
+                  _ptr_array([p[2], p[6]]), _ptr_array([p[3], p[7]]), _ptr(oc), _ptr(saved), _ptr(ws), _stream())
+        if oc is not out:
+            out[:, b0:b1] = oc
+        chunks.append((b0, b1, xc, oc, saved, lc))
+    ctx.chunks, ctx.p, ctx.shape = chunks, p, (S, B, In, H)
+    ctx.need_x = x.requires_grad if hasattr(x, "requires_grad") else False
+    return out
+
+
+def _lstm_layer_bwd(ctx, d_out, i_x, i_p):
+    """-> (dx, parameter gradients); i_x / i_p: where x / the first parameter sit among the Function's inputs"""
+    S, B, In, H = ctx.shape
+    p = ctx.p
+    d_out = _f32c(d_out)
+    need_dx = ctx.needs_input_grad[i_x]
+    dx = torch.empty(S, B, In, device=d_out.device, dtype=torch.float32) if need_dx else None
+    grads = [torch.zeros_like(t) if ctx.needs_input_grad[i_p + i] else None for i, t in enumerate(p)]
+    for (b0, b1, xc, oc, saved, lc) in ctx.chunks:
+        cfg = _lib.LstmCfg(S, b1 - b0, In, H)
+        fam = "ganffn_lstm_batch_" if b1 - b0 > 32 or lc is not None else "ganffn_lstm_"
+        n_ws = int(getattr(_lib.load(), fam + "workspace_floats")(C.byref(cfg)))
+        ws = torch.empty(n_ws, device=d_out.device, dtype=torch.float32)
+        dc = d_out if (b0, b1) == (0, B) else d_out[:, b0:b1].contiguous()
+        dxc = None
+        if need_dx:
+            dxc = dx if (b0, b1) == (0, B) else torch.empty(S, b1 - b0, In, device=d_out.device, dtype=torch.float32)
+        head = (fam + "layer_bwd", C.byref(cfg)) if lc is None else ("ganffn_lstm_packed_layer_bwd", C.byref(cfg), _ptr(lc))
+        _lib.call(*head, _ptr(dc), _ptr(xc), _ptr(oc), _ptr_array([p[0], p[4]]), _ptr_array([p[1], p[5]]),
+                  _ptr(dxc), _ptr_array([grads[0], grads[4]]), _ptr_array([grads[1], grads[5]]), _ptr_array([grads[2], grads[6]]),
+                  _ptr_array([grads[3], grads[7]]), _ptr(saved), _ptr(ws), _stream())
+        if need_dx and dxc is not dx:
+            dx[:, b0:b1] = dxc
+    return dx, grads
+
+
 class LstmLayerFn(torch.autograd.Function):
     """one bidirectional LSTM layer: x (S, B, In) -> (S, B, 2H) = [h forward | h reverse]; torch's parameters
     weight_ih [4H x In], weight_hh [4H x H], bias_ih, bias_hh [4H] per direction (gate order i, f, g, o).  One native call for
@@ -799,69 +864,43 @@ class LstmLayerFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, *params):
-        _need_gpu(x, *params)
-        x = _f32c(x)
-        p = [_f32c(t.detach()) for t in params]          # w_ih0, w_hh0, b_ih0, b_hh0, w_ih1, w_hh1, b_ih1, b_hh1
-        S, B, In = x.shape
-        H = p[1].shape[1]
-        out = torch.empty(S, B, 2 * H, device=x.device, dtype=torch.float32)
-        chunks = []
-        for b0 in range(0, B, MAX_DIALOGUES):
-            b1 = min(B, b0 + MAX_DIALOGUES)
-            cfg = _lib.LstmCfg(S, b1 - b0, In, H)
-            fam = "ganffn_lstm_batch_" if b1 - b0 > 32 else "ganffn_lstm_"
-            n_saved = int(getattr(_lib.load(), fam + "saved_floats")(C.byref(cfg)))
-            n_ws = int(getattr(_lib.load(), fam + "workspace_floats")(C.byref(cfg)))
-            if n_saved < 0 or n_ws < 0:
-                _lib.check(-1, fam + "*_floats")
-            xc = x if (b0, b1) == (0, B) else x[:, b0:b1].contiguous()
-            oc = out if (b0, b1) == (0, B) else torch.empty(S, b1 - b0, 2 * H, device=x.device, dtype=torch.float32)
-            saved = torch.empty(n_saved, device=x.device, dtype=torch.float32)
-            ws = torch.empty(n_ws, device=x.device, dtype=torch.float32)
-            _lib.call(fam + "layer_fwd", C.byref(cfg), _ptr(xc), _ptr_array([p[0], p[4]]), _ptr_array([p[1], p[5]]),
-                      _ptr_array([p[2], p[6]]), _ptr_array([p[3], p[7]]), _ptr(oc), _ptr(saved), _ptr(ws), _stream())
-            if oc is not out:
-                out[:, b0:b1] = oc
-            chunks.append((b0, b1, xc, oc, saved))
-        ctx.chunks, ctx.p, ctx.shape = chunks, p, (S, B, In, H)
-        ctx.need_x = x.requires_grad if hasattr(x, "requires_grad") else False
-        return out
+        return _lstm_layer_fwd(ctx, x, None, params)
 
     @staticmethod
     def backward(ctx, d_out):
-        S, B, In, H = ctx.shape
-        p = ctx.p
-        d_out = _f32c(d_out)
-        need_dx = ctx.needs_input_grad[0]
-        dx = torch.empty(S, B, In, device=d_out.device, dtype=torch.float32) if need_dx else None
-        grads = [torch.zeros_like(t) if ctx.needs_input_grad[1 + i] else None for i, t in enumerate(p)]
-        for (b0, b1, xc, oc, saved) in ctx.chunks:
-            cfg = _lib.LstmCfg(S, b1 - b0, In, H)
-            fam = "ganffn_lstm_batch_" if b1 - b0 > 32 else "ganffn_lstm_"
-            n_ws = int(getattr(_lib.load(), fam + "workspace_floats")(C.byref(cfg)))
-            ws = torch.empty(n_ws, device=d_out.device, dtype=torch.float32)
-            dc = d_out if (b0, b1) == (0, B) else d_out[:, b0:b1].contiguous()
-            dxc = None
-            if need_dx:
-                dxc = dx if (b0, b1) == (0, B) else torch.empty(S, b1 - b0, In, device=d_out.device, dtype=torch.float32)
-            _lib.call(fam + "layer_bwd", C.byref(cfg), _ptr(dc), _ptr(xc), _ptr(oc), _ptr_array([p[0], p[4]]), _ptr_array([p[1], p[5]]),
-                      _ptr(dxc), _ptr_array([grads[0], grads[4]]), _ptr_array([grads[1], grads[5]]), _ptr_array([grads[2], grads[6]]),
-                      _ptr_array([grads[3], grads[7]]), _ptr(saved), _ptr(ws), _stream())
-            if need_dx and dxc is not dx:
-                dx[:, b0:b1] = dxc
+        dx, grads = _lstm_layer_bwd(ctx, d_out, 0, 1)
         return (dx, *grads)
 
 
-def lstm_forward(x, lstm, training):
+class LstmPackedLayerFn(torch.autograd.Function):
+    """LstmLayerFn on packed sequences (ganffn_lstm_packed_layer_*; an extension the reference does not have): lengths int32 (B,)
+    on the device, lengths[b] real steps of dialogue b — what pack_padded_sequence -> one nn.LSTM layer ->
+    pad_packed_sequence(total_length = S) gives: zero output past a dialogue's end, the reverse direction starting at its last
+    real step, zero dx at padded positions, upstream gradients at padded positions ignored.  x must be finite at padded
+    positions; its values there change nothing.  The same chunking at MAX_DIALOGUES, lengths sliced alongside the batch."""
+
+    @staticmethod
+    def forward(ctx, x, lengths, *params):
+        return _lstm_layer_fwd(ctx, x, lengths, params)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        dx, grads = _lstm_layer_bwd(ctx, d_out, 0, 2)
+        return (dx, None, *grads)
+
+
+def lstm_forward(x, lstm, training, lengths=None):
     """nn.LSTM(..., bidirectional=True, dropout=p).forward(x)[0] for a padded (S, B, In) CUDA batch, on the HIP kernels, with the
     module's own parameters (state_dict keys unchanged: lstm.weight_ih_l{k}[_reverse], ...).  Inter-layer dropout (every layer but
-    the last, train mode only) follows the Philox contract (site SITE_LSTM + layer)."""
+    the last, train mode only) follows the Philox contract (site SITE_LSTM + layer).
+    lengths (int32 (B,) on the device; default None: the padded run above, as the reference): the packed run —
+    pack_padded_sequence(x, lengths, enforce_sorted=False) -> lstm -> pad_packed_sequence(total_length=S)[0] (LstmPackedLayerFn)."""
     assert lstm.bidirectional and not lstm.batch_first and lstm.proj_size == 0 and lstm.bias, "lstm_forward: the MELDLSTMModel configuration only"
     h = x
     for l in range(lstm.num_layers):
         names = ["weight_ih_l%d", "weight_hh_l%d", "bias_ih_l%d", "bias_hh_l%d"]
         params = [getattr(lstm, n % l) for n in names] + [getattr(lstm, (n % l) + "_reverse") for n in names]
-        h = LstmLayerFn.apply(h, *params)
+        h = LstmLayerFn.apply(h, *params) if lengths is None else LstmPackedLayerFn.apply(h, lengths, *params)
         if l + 1 < lstm.num_layers and lstm.dropout > 0.0:
             h = DropoutFn.apply(h, float(lstm.dropout), training, SITE_LSTM + l)
     return h

@@ -596,6 +596,40 @@ int ganffn_lstm_stack_batch_bwd(const ganffn_lstm_stack_cfg* cfg, const float* d
                                 float* const* gw_hh, float* const* gb_ih, float* const* gb_hh, const float* saved,
                                 float* workspace, const uint64_t* rng, uint64_t rng_offset_add, void* stream);
 
+/* ---- N4: the LSTM recurrence on packed sequences (csrc/lstm.hip) -------------------------------------------------------------
+ * An extension the reference does not have (model.py:546 hands nn.LSTM the padded batch): what
+ * pack_padded_sequence -> nn.LSTM -> pad_packed_sequence(total_length = S) computes, on the padded layout.  The arguments are
+ * those of ganffn_lstm_batch_layer_* / ganffn_lstm_stack_batch_* with `lengths` after cfg: int32 [B] on the device, lengths[b] =
+ * the number of real steps of dialogue b (<= 0: an empty dialogue; > S: taken as S).  It is only ever compared with a time index,
+ * never used as an index, and never read by the host.  The rule, in BOTH directions, for dialogue b at time index tm >= lengths[b]:
+ *   forward:  c_t = 0; h_t = 0, written into out[tm]; the saved activated gates are 0 — whatever the products computed for that
+ *             row is discarded by a select;
+ *   backward: dG = 0 for all four gates and the dc handed to the earlier step is 0, whatever dh / d_out hold there — a select,
+ *             not a product with 0, so junk (NaN included) in d_out at padded positions cannot spread.
+ * At tm < lengths[b] the arithmetic is that of the unpacked entry points.  So the reverse direction enters step lengths[b] - 1
+ * with zero state, out is 0 past a dialogue's end, the inter-layer dropout of those rows is 0, the weight, bias and input
+ * gradients see zero dG rows at padded tokens (dx is 0 there), and with every length >= S the results are the unpacked entry
+ * points' bit for bit.  Contract on x: FINITE at padded positions (the project's collate and ganffn_batch_gather write zeros);
+ * its values there change no result.  1 <= cfg->B <= GANFFN_MAX_DIALOGUES; sizes from ganffn_lstm_batch_*_floats /
+ * ganffn_lstm_stack_batch_*_floats, layouts unchanged; the same launches per step as the unpacked calls.  A null `lengths` is an
+ * argument error reported through ganffn_last_error. */
+int ganffn_lstm_packed_layer_fwd(const ganffn_lstm_cfg* cfg, const int32_t* lengths, const float* x, const float* const* w_ih,
+                                 const float* const* w_hh, const float* const* b_ih, const float* const* b_hh, float* out,
+                                 float* saved, float* workspace, void* stream);
+int ganffn_lstm_packed_layer_bwd(const ganffn_lstm_cfg* cfg, const int32_t* lengths, const float* d_out, const float* x,
+                                 const float* out, const float* const* w_ih, const float* const* w_hh, float* dx,
+                                 float* const* gw_ih, float* const* gw_hh, float* const* gb_ih, float* const* gb_hh,
+                                 const float* saved, float* workspace, void* stream);
+int ganffn_lstm_stack_packed_fwd(const ganffn_lstm_stack_cfg* cfg, const int32_t* lengths, const float* x,
+                                 const float* const* w_ih, const float* const* w_hh, const float* const* b_ih,
+                                 const float* const* b_hh, float* out, float* saved, float* workspace, const uint64_t* rng,
+                                 uint64_t rng_offset_add, void* stream);
+int ganffn_lstm_stack_packed_bwd(const ganffn_lstm_stack_cfg* cfg, const int32_t* lengths, const float* d_out, const float* x,
+                                 const float* out, const float* const* w_ih, const float* const* w_hh, float* dx,
+                                 float* const* gw_ih, float* const* gw_hh, float* const* gb_ih, float* const* gb_hh,
+                                 const float* saved, float* workspace, const uint64_t* rng, uint64_t rng_offset_add,
+                                 void* stream);
+
 /* ---- N4: the MELD classifier's head (csrc/meld_head.hip) ------------------------------------------------------------------
  * Replaces `hidden = F.hardswish(emotions + F.hardswish(att_emotions))` and `self.smax_fc(hidden)` of MELDLSTMModel.forward
  * (/root/reference/model.py:553-560, the att2 branch /root/reference/train_MELD.py:71 runs) and autograd's backward of them.
