@@ -2,7 +2,8 @@
 //
 // Replaces the attention core of torch's nn.MultiheadAttention as used by the reference's
 // nn.TransformerEncoderLayer stacks (/root/reference/model.py:1210,1244,1276,1307,1340,1377):
-//   P = softmax(q k^T / sqrt(hd)) over keys, NO masks (padded utterances attend and are attended to),
+//   P = softmax(q k^T / sqrt(hd)) over keys, NO masks (padded utterances attend and are attended to) unless the caller
+//   gives key lengths: keys at or past a dialogue's length then get probability 0 (an extension: ganffn_attention_fwd_len),
 //   dropout(0.1) on P in train mode, O = P v.
 // The sequence is one dialogue (S <= 110 utterances), so one workgroup owns one (b, h) problem with
 // q, k, v resident in LDS; nothing S x S ever touches HBM, and the backward recomputes P (and the
@@ -57,6 +58,7 @@ struct HeadSrc {
     const float* src;
     int ld_src;
     float scale;
+    int rows;      // rows < rows are staged, the rest zero: S for q and dO, the dialogue's key length for k and v
 };
 
 template <int NM>
@@ -73,7 +75,7 @@ __device__ __forceinline__ void load_heads_generic(const HeadSrc (&m)[NM], const
                 const int i = min(base + u * nthreads, per - 1);
                 const int s = i / hd2, d = (i - s * hd2) * 2;
                 const float2 q = *reinterpret_cast<const float2*>(m[mi].src + (size_t)(min(s, g.S - 1) * g.B + b) * m[mi].ld_src + d);
-                v[u] = s < g.S ? q : make_float2(0.f, 0.f);
+                v[u] = s < m[mi].rows ? q : make_float2(0.f, 0.f);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -130,7 +132,7 @@ __device__ __forceinline__ void load_heads(const HeadSrc (&m)[NM], const AttnGeo
                 const int i = tid + u * NTH;
                 if (PER % NTH == 0 || i < PER) {
                     const int s = i / PR, d = (i - s * PR) * VEC;
-                    const float f = (s < g.S ? one : 0.f) * m[mi].scale;      // rows >= S: zero (finite operand x 0)
+                    const float f = (s < m[mi].rows ? one : 0.f) * m[mi].scale;      // rows past the limit: zero (finite operand x 0)
 #pragma unroll
                     for (int e = 0; e < VEC; ++e) m[mi].dst[s * g.LDH + d + e] = v[mi][u][e] * f;
                 }
@@ -314,11 +316,13 @@ __device__ __forceinline__ bool kept(const unsigned long long (&mq)[4], int c, i
 // PAIR: two batches of the same shape in one launch (the eval-mode and the train-mode pass of one generator): workgroups
 // 0 .. B H - 1 are the first batch's, the rest the second's with its own qkv / o and train flag.  Wave-uniform, chosen once;
 // (dialogue, head) indices and the Philox counters are local to the batch: each batch gets the bits of its own launch.
-template <int HD, int NT, bool PAIR = false>
+// LEN: per-dialogue key lengths (key_len, device int32 [B]; never together with PAIR) — a template flag, so that the
+// instantiations without lengths keep the instructions they had (see attention16.hip)
+template <int HD, int NT, bool PAIR = false, bool LEN = false>
 __global__ __launch_bounds__(64 * NT) void attention_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ o, AttnGeom g,
                                                                 float p, uint32_t site, const uint64_t* __restrict__ rng,
                                                                 uint64_t add, int train, const float* qkv1, float* o1,
-                                                                int train1) {
+                                                                int train1, const int32_t* __restrict__ key_len) {
     constexpr int NTD = HD ? (HD + 31) / 32 : 2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
@@ -330,6 +334,7 @@ __global__ __launch_bounds__(64 * NT) void attention_fwd_kernel(const float* __r
         }
     }
     const int b = bh / g.H, head = bh % g.H;
+    const int n = LEN ? attn_key_len(key_len, b, g.S) : g.S;      // keys < n take part (workgroup-uniform)
     const size_t HM = (size_t)g.ROWS * g.LDH + 64;
     float* Qs = smem;
     float* Ks = Qs + HM;
@@ -337,8 +342,8 @@ __global__ __launch_bounds__(64 * NT) void attention_fwd_kernel(const float* __r
     const int ld3 = 3 * g.E;
     const float scale = rsqrtf((float)g.hd);
     {
-        const HeadSrc m3[3] = {{Qs, qkv + head * g.hd, ld3, scale}, {Ks, qkv + g.E + head * g.hd, ld3, 1.f},
-                               {Vs, qkv + 2 * g.E + head * g.hd, ld3, 1.f}};
+        const HeadSrc m3[3] = {{Qs, qkv + head * g.hd, ld3, scale, g.S}, {Ks, qkv + g.E + head * g.hd, ld3, 1.f, n},
+                               {Vs, qkv + 2 * g.E + head * g.hd, ld3, 1.f, n}};
         load_heads<HD, NT, 3>(m3, g, b, tid);
     }
     __syncthreads();
@@ -349,7 +354,7 @@ __global__ __launch_bounds__(64 * NT) void attention_fwd_kernel(const float* __r
 #pragma unroll
         for (int i = 0; i < 16; ++i) pr[c][i] = 0.f;
     scores_T<HD, NT>(pr, Ks, Qs, g.LDH, g.hd, 32 * w, r, h);
-    softmax_T<NT>(pr, g.S, h);
+    softmax_T<NT>(pr, n, h);
 
     const DropCtx dc = make_drop(rng, add, site, p, train);
     if (dc.on) {
@@ -386,14 +391,18 @@ __global__ __launch_bounds__(64 * NT) void attention_fwd_kernel(const float* __r
 // ------------------------------------------------------------------------------------------
 // backward: d_qkv from d_o, recomputing P^T and the dropout mask
 // ------------------------------------------------------------------------------------------
-template <int HD, int NT>
+template <int HD, int NT, bool LEN = false>
 __global__ __launch_bounds__(64 * NT) void attention_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ d_o,
                                                                 float* __restrict__ d_qkv, AttnGeom g, float p, uint32_t site,
-                                                                const uint64_t* __restrict__ rng, uint64_t add, int train) {
+                                                                const uint64_t* __restrict__ rng, uint64_t add, int train,
+                                                                const int32_t* __restrict__ key_len) {
     constexpr int NTD = HD ? (HD + 31) / 32 : 2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, r = lane & 31, h = lane >> 5;
     const int bh = blockIdx.x, b = bh / g.H, head = bh % g.H;
+    // keys < n take part (workgroup-uniform).  Past n the recomputed softmax gives P = 0 exactly (score -inf), V is staged as
+    // zeros, so P~, dP and dS are 0 there and the dK, dV rows n .. S-1 are written as zeros
+    const int n = LEN ? attn_key_len(key_len, b, g.S) : g.S;
     const size_t HM = (size_t)g.ROWS * g.LDH + 64;
     // All four operand matrices stay resident in LDS when they fit (one global-load round trip, one barrier fewer);
     // otherwise dO overwrites Q and the re-loaded Q overwrites V (ALIAS).  Same rule on the host: launch_attention_bwd().
@@ -408,12 +417,12 @@ __global__ __launch_bounds__(64 * NT) void attention_bwd_kernel(const float* __r
     const float scale = rsqrtf((float)g.hd);
 
     if constexpr (ALIAS) {
-        const HeadSrc m3[3] = {{RA, qkv + head * g.hd, ld3, scale}, {RB, qkv + g.E + head * g.hd, ld3, 1.f},
-                               {RC, qkv + 2 * g.E + head * g.hd, ld3, 1.f}};
+        const HeadSrc m3[3] = {{RA, qkv + head * g.hd, ld3, scale, g.S}, {RB, qkv + g.E + head * g.hd, ld3, 1.f, n},
+                               {RC, qkv + 2 * g.E + head * g.hd, ld3, 1.f, n}};
         load_heads<HD, NT, 3>(m3, g, b, tid);
     } else {
-        const HeadSrc m4[4] = {{RA, qkv + head * g.hd, ld3, scale}, {RB, qkv + g.E + head * g.hd, ld3, 1.f},
-                               {RC, qkv + 2 * g.E + head * g.hd, ld3, 1.f}, {RD, d_o + head * g.hd, g.E, 1.f}};
+        const HeadSrc m4[4] = {{RA, qkv + head * g.hd, ld3, scale, g.S}, {RB, qkv + g.E + head * g.hd, ld3, 1.f, n},
+                               {RC, qkv + 2 * g.E + head * g.hd, ld3, 1.f, n}, {RD, d_o + head * g.hd, g.E, 1.f, g.S}};
         load_heads<HD, NT, 4>(m4, g, b, tid);
     }
     __syncthreads();
@@ -426,7 +435,7 @@ __global__ __launch_bounds__(64 * NT) void attention_bwd_kernel(const float* __r
         for (int i = 0; i < 16; ++i) { pr[c][i] = 0.f; dp[c][i] = 0.f; }
 
     scores_T<HD, NT>(pr, RB, RA, g.LDH, g.hd, 32 * w, r, h);
-    softmax_T<NT>(pr, g.S, h);
+    softmax_T<NT>(pr, n, h);
     const DropCtx dc = make_drop(rng, add, site, p, train);
     unsigned long long mq[4];
     keep_masks<NT>(mq, dc, bh, w, lane);
@@ -444,7 +453,7 @@ __global__ __launch_bounds__(64 * NT) void attention_bwd_kernel(const float* __r
     }
     __syncthreads();                                           // all waves are done with Q; P~^T complete
     if constexpr (ALIAS) {
-        const HeadSrc m1[1] = {{RA, d_o + head * g.hd, g.E, 1.f}};   // dO over Q
+        const HeadSrc m1[1] = {{RA, d_o + head * g.hd, g.E, 1.f, g.S}};   // dO over Q
         load_heads<HD, NT, 1>(m1, g, b, tid);
         __syncthreads();
     }
@@ -526,7 +535,7 @@ __global__ __launch_bounds__(64 * NT) void attention_bwd_kernel(const float* __r
         }
     }
     if constexpr (ALIAS) {
-        const HeadSrc m1[1] = {{RC, qkv + head * g.hd, ld3, scale}};  // scaled Q over V
+        const HeadSrc m1[1] = {{RC, qkv + head * g.hd, ld3, scale, g.S}};  // scaled Q over V
         load_heads<HD, NT, 1>(m1, g, b, tid);
     }
     __syncthreads();
@@ -566,25 +575,35 @@ static int check_attn(int S, int B, int E, int H) {
 
 template <int HD, int NT>
 static int launch_fwd_t(const float* qkv, float* o, const AttnGeom& g, size_t lds, float p, uint32_t site, const uint64_t* rng,
-                        uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1) {
+                        uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1, const int32_t* key_len) {
     if (seg1) {
         GF_TRY((lds_optin<attention_fwd_kernel<HD, NT, true>>(lds, "attention_fwd")));
         hipLaunchKernelGGL((attention_fwd_kernel<HD, NT, true>), dim3(2 * g.B * g.H), dim3(64 * NT), lds, st, qkv, o, g, p, site, rng,
-                           add, train, seg1->qkv, seg1->o, seg1->train);
+                           add, train, seg1->qkv, seg1->o, seg1->train, (const int32_t*)nullptr);
+    } else if (key_len) {
+        GF_TRY((lds_optin<attention_fwd_kernel<HD, NT, false, true>>(lds, "attention_fwd")));
+        hipLaunchKernelGGL((attention_fwd_kernel<HD, NT, false, true>), dim3(g.B * g.H), dim3(64 * NT), lds, st, qkv, o, g, p, site, rng,
+                           add, train, (const float*)nullptr, (float*)nullptr, 0, key_len);
     } else {
         GF_TRY((lds_optin<attention_fwd_kernel<HD, NT>>(lds, "attention_fwd")));
         hipLaunchKernelGGL((attention_fwd_kernel<HD, NT>), dim3(g.B * g.H), dim3(64 * NT), lds, st, qkv, o, g, p, site, rng, add, train,
-                           (const float*)nullptr, (float*)nullptr, 0);
+                           (const float*)nullptr, (float*)nullptr, 0, key_len);
     }
     GF_LAUNCH_CHECK();
     return 0;
 }
 template <int HD, int NT>
 static int launch_bwd_t(const float* qkv, const float* d_o, float* d_qkv, const AttnGeom& g, size_t lds, float p, uint32_t site,
-                        const uint64_t* rng, uint64_t add, int train, hipStream_t st) {
-    GF_TRY((lds_optin<attention_bwd_kernel<HD, NT>>(lds, "attention_bwd")));
-    hipLaunchKernelGGL((attention_bwd_kernel<HD, NT>), dim3(g.B * g.H), dim3(64 * NT), lds, st, qkv, d_o, d_qkv, g, p, site, rng,
-                       add, train);
+                        const uint64_t* rng, uint64_t add, int train, hipStream_t st, const int32_t* key_len) {
+    if (key_len) {
+        GF_TRY((lds_optin<attention_bwd_kernel<HD, NT, true>>(lds, "attention_bwd")));
+        hipLaunchKernelGGL((attention_bwd_kernel<HD, NT, true>), dim3(g.B * g.H), dim3(64 * NT), lds, st, qkv, d_o, d_qkv, g, p, site,
+                           rng, add, train, key_len);
+    } else {
+        GF_TRY((lds_optin<attention_bwd_kernel<HD, NT>>(lds, "attention_bwd")));
+        hipLaunchKernelGGL((attention_bwd_kernel<HD, NT>), dim3(g.B * g.H), dim3(64 * NT), lds, st, qkv, d_o, d_qkv, g, p, site, rng,
+                           add, train, key_len);
+    }
     GF_LAUNCH_CHECK();
     return 0;
 }
@@ -598,35 +617,37 @@ static int launch_bwd_t(const float* qkv, const float* d_o, float* d_qkv, const 
     }
 
 int launch_attention_fwd(const float* qkv, float* o, float* lse, uint32_t* keep, int S, int B, int E, int H, float p, uint32_t site,
-                         const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1) {
+                         const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1,
+                         const int32_t* key_len) {
     GF_TRY(check_attn(S, B, E, H));
+    GF_CHECK_ARG(!(seg1 && key_len), "attention_fwd: key lengths are not taken together with a second batch");
     GF_CHECK_ARG(qkv && o, "attention_fwd: null pointer");
     GF_CHECK_ARG(!seg1 || (seg1->qkv && seg1->o), "attention_fwd: bad second batch");
     GF_CHECK_ARG(!((train || (seg1 && seg1->train)) && p > 0.f) || rng, "attention_fwd: rng required when dropout is active");
-    if (attn16_supported(E, H, S)) return launch_attn16_fwd(qkv, o, lse, keep, S, B, E, H, p, site, rng, add, train, st, seg1);
+    if (attn16_supported(E, H, S)) return launch_attn16_fwd(qkv, o, lse, keep, S, B, E, H, p, site, rng, add, train, st, seg1, key_len);
     const AttnGeom g = make_geom(S, B, E, H);
     const size_t lds = 3 * hd_mat_floats(g) * sizeof(float);
     GF_CHECK_ARG(lds <= 160 * 1024, "attention_fwd: LDS need %zu > 160 KiB", lds);
-    if (g.hd == 64) { NT_SWITCH(launch_fwd_t, 64, qkv, o, g, lds, p, site, rng, add, train, st, seg1) }
-    if (g.hd == 60) { NT_SWITCH(launch_fwd_t, 60, qkv, o, g, lds, p, site, rng, add, train, st, seg1) }
-    NT_SWITCH(launch_fwd_t, 0, qkv, o, g, lds, p, site, rng, add, train, st, seg1)
+    if (g.hd == 64) { NT_SWITCH(launch_fwd_t, 64, qkv, o, g, lds, p, site, rng, add, train, st, seg1, key_len) }
+    if (g.hd == 60) { NT_SWITCH(launch_fwd_t, 60, qkv, o, g, lds, p, site, rng, add, train, st, seg1, key_len) }
+    NT_SWITCH(launch_fwd_t, 0, qkv, o, g, lds, p, site, rng, add, train, st, seg1, key_len)
 }
 
 int launch_attention_bwd(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keep, float* d_qkv,
                          int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train,
-                         hipStream_t st) {
+                         hipStream_t st, const int32_t* key_len) {
     GF_TRY(check_attn(S, B, E, H));
     GF_CHECK_ARG(qkv && d_o && d_qkv, "attention_bwd: null pointer");
     GF_CHECK_ARG(!(train && p > 0.f) || rng, "attention_bwd: rng required when dropout is active");
-    if (attn16_supported(E, H, S)) return launch_attn16_bwd(qkv, o, lse, d_o, keep, d_qkv, S, B, E, H, p, site, rng, add, train, st);
+    if (attn16_supported(E, H, S)) return launch_attn16_bwd(qkv, o, lse, d_o, keep, d_qkv, S, B, E, H, p, site, rng, add, train, st, key_len);
     const AttnGeom g = make_geom(S, B, E, H);
     const int hdt = (g.hd == 60 || g.hd == 64) ? g.hd : 0;      // kernel template head_dim (0 = generic)
     const bool alias = hdt == 0 || hdt * g.NT > 192;            // == attention_bwd_kernel::ALIAS
     const size_t lds = ((alias ? 3 : 4) * hd_mat_floats(g) + ss_mat_floats(g)) * sizeof(float);
     GF_CHECK_ARG(lds <= 160 * 1024, "attention_bwd: LDS need %zu > 160 KiB", lds);
-    if (g.hd == 64) { NT_SWITCH(launch_bwd_t, 64, qkv, d_o, d_qkv, g, lds, p, site, rng, add, train, st) }
-    if (g.hd == 60) { NT_SWITCH(launch_bwd_t, 60, qkv, d_o, d_qkv, g, lds, p, site, rng, add, train, st) }
-    NT_SWITCH(launch_bwd_t, 0, qkv, d_o, d_qkv, g, lds, p, site, rng, add, train, st)
+    if (g.hd == 64) { NT_SWITCH(launch_bwd_t, 64, qkv, d_o, d_qkv, g, lds, p, site, rng, add, train, st, key_len) }
+    if (g.hd == 60) { NT_SWITCH(launch_bwd_t, 60, qkv, d_o, d_qkv, g, lds, p, site, rng, add, train, st, key_len) }
+    NT_SWITCH(launch_bwd_t, 0, qkv, d_o, d_qkv, g, lds, p, site, rng, add, train, st, key_len)
 }
 
 }  // namespace ganffn

@@ -3,7 +3,8 @@
 // v_mfma_f32_16x16x4_f32 (exact fp32).
 //
 // Replaces the attention core of torch's nn.MultiheadAttention inside nn.TransformerEncoderLayer
-// (/root/reference/model.py:1210,1276,1307,1340,1377): P = softmax(q k^T / sqrt(hd)) over keys, NO masks, dropout(0.1)
+// (/root/reference/model.py:1210,1276,1307,1340,1377): P = softmax(q k^T / sqrt(hd)) over keys, NO masks (unless the caller gives key
+// lengths: keys at or past a dialogue's length then get probability 0 — an extension, see ganffn_attention_fwd_len), dropout(0.1)
 // on P in train mode, O = P v.
 //
 // Why a second kernel family (attention.hip keeps head_dim 60/64): with hd = 10 a 32x32x2 MFMA product that has the head
@@ -48,6 +49,7 @@ struct HeadSrc16 {
     const float* src;
     int ld_src;
     float scale;
+    int key;       // 1: a k or v matrix, staged up to the dialogue's key length; 0: q or dO, staged up to S (the rest zero)
 };
 
 // Stage NM [S x HD] head slices into LDS images [16 NT rows][LD] (rows >= S and columns >= HD zero), in two phases so that
@@ -75,16 +77,17 @@ struct HeadStage {
         }
         __builtin_amdgcn_sched_barrier(0);
     }
-    __device__ __forceinline__ void store(const HeadSrc16 (&m)[NM], int S, int tid) const {
+    __device__ __forceinline__ void store(const HeadSrc16 (&m)[NM], int S, int n, int tid) const {
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int i = tid + u * NTH;
             if (PER % NTH == 0 || i < PER) {
                 const int s = i / PR, j = i - s * PR;
                 const float in = (s < S && 2 * j < HD) ? 1.f : 0.f;
+                const float ink = (s < n && 2 * j < HD) ? 1.f : 0.f;      // (without lengths n is S: the same value)
 #pragma unroll
                 for (int mi = 0; mi < NM; ++mi) {
-                    const float f = in * m[mi].scale;
+                    const float f = (m[mi].key ? ink : in) * m[mi].scale;
                     *reinterpret_cast<float2*>(m[mi].dst + s * LD + 2 * j) = make_float2(v[mi][u].x * f, v[mi][u].y * f);
                 }
             }
@@ -181,12 +184,16 @@ __device__ __forceinline__ void store4(float* __restrict__ row, int d0, const fl
 struct Attn16Seg1 {
     const float* qkv; float* o; float* lse; uint32_t* keepw; int train;
 };
-template <int HD, int NT, int WPB, bool PAIR = false>
+// LEN: per-dialogue key lengths (key_len, device int32 [B]; never together with PAIR).  A template flag and not a test of the
+// pointer: the instantiations without lengths (every launch of the GAN step) keep the instructions they had — no scalar load, no
+// uniform branch (the listings compared: profiles/attention_key_len_ab.txt).
+template <int HD, int NT, int WPB, bool PAIR = false, bool LEN = false>
 __global__ __launch_bounds__(64 * WPB) void attn16_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ o,
                                                              float* __restrict__ lse, uint32_t* __restrict__ keepw, int S, int B,
                                                              int E, int H, float p, uint32_t site,
                                                              const uint64_t* __restrict__ rng, uint64_t add, int train,
-                                                             Attn16Seg1 s1, int nb0) {
+                                                             Attn16Seg1 s1, int nb0,
+                                                             const int32_t* __restrict__ key_len) {
     unsigned bid = blockIdx.x;
     if constexpr (PAIR) {
         if (bid >= (unsigned)nb0) {
@@ -201,6 +208,7 @@ __global__ __launch_bounds__(64 * WPB) void attn16_fwd_kernel(const float* __res
     const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, g = lane >> 4;
     const int bh = bid / NQB, w = (bid - bh * NQB) * WPB + (tid >> 6);     // w: query tile of this wave
     const int b = bh / H, head = bh - b * H;
+    const int n = LEN ? attn_key_len(key_len, b, S) : S;      // keys < n take part (workgroup-uniform)
     float* Qs = smem;
     float* Ks = Qs + MAT;
     float* Vs = Ks + MAT;
@@ -208,8 +216,8 @@ __global__ __launch_bounds__(64 * WPB) void attn16_fwd_kernel(const float* __res
     const DropCtx dc = make_drop(rng, add, site, p, train);
     uint32_t mine = 0;
     {
-        const HeadSrc16 m3[3] = {{Qs, qkv + head * HD, ld3, rsqrtf((float)HD)}, {Ks, qkv + E + head * HD, ld3, 1.f},
-                                 {Vs, qkv + 2 * E + head * HD, ld3, 1.f}};
+        const HeadSrc16 m3[3] = {{Qs, qkv + head * HD, ld3, rsqrtf((float)HD), 0}, {Ks, qkv + E + head * HD, ld3, 1.f, 1},
+                                 {Vs, qkv + 2 * E + head * HD, ld3, 1.f, 1}};
         HeadStage<HD, NT, 3, WPB> stg;
         stg.load(m3, S, B, b, tid);
         if (dc.on) {
@@ -230,7 +238,7 @@ __global__ __launch_bounds__(64 * WPB) void attn16_fwd_kernel(const float* __res
             // backward then needs no Philox call at all (its lane (key 16w' + c', group g') reads word [4t + g'][c'])
             if (keepw != nullptr) keepw[(size_t)rowgroup * 16 + 4 * g + ql] = mine;
         }
-        stg.store(m3, S, tid);
+        stg.store(m3, S, n, tid);
     }
     __syncthreads();
 
@@ -245,7 +253,7 @@ __global__ __launch_bounds__(64 * WPB) void attn16_fwd_kernel(const float* __res
     for (int t = 0; t < NT; ++t)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            if (16 * t + 4 * g + r >= S) pr[t][r] = -INFINITY;
+            if (16 * t + 4 * g + r >= n) pr[t][r] = -INFINITY;
             m = fmaxf(m, pr[t][r]);
         }
     m = fmaxf(m, __shfl_xor(m, 16, 64));
@@ -297,17 +305,19 @@ __global__ __launch_bounds__(64 * WPB) void attn16_fwd_kernel(const float* __res
 // ------------------------------------------------------------------------------------------
 // SAVED: the dropout keep bits come from the words the forward stored (keepw) instead of Philox calls — the same bits, so
 // both forms give identical results (tests/test_hip_ops.py::test_attention_fwd_bwd compares them with torch.equal)
-template <int HD, int NT, bool SAVED>
+template <int HD, int NT, bool SAVED, bool LEN = false>
 __global__ __launch_bounds__(64 * NT) void attn16_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
                                                              const float* __restrict__ lse, const float* __restrict__ d_o,
                                                              const uint32_t* __restrict__ keepw, float* __restrict__ d_qkv,
                                                              int S, int B, int E, int H, float p, uint32_t site,
-                                                             const uint64_t* __restrict__ rng, uint64_t add, int train) {
+                                                             const uint64_t* __restrict__ rng, uint64_t add, int train,
+                                                             const int32_t* __restrict__ key_len) {
     constexpr int LD = A16<HD>::LD, NTD = A16<HD>::NTD, KS = A16<HD>::KS, ROWS = 16 * NT, MAT = ROWS * LD + A16<HD>::TAIL;
     constexpr int LDS_S = ROWS + 4;                      // dS image [query][key]: rows 4 apart sit 16 banks apart
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, g = lane >> 4;
     const int bh = blockIdx.x, b = bh / H, head = bh - b * H;
+    const int n = LEN ? attn_key_len(key_len, b, S) : S;      // keys < n take part (workgroup-uniform)
     // K, LSE and D live for the whole kernel; scaled q, V and dO are dead once dV / dK are accumulated, and the dS image
     // takes their place (one more barrier) — at S = 94 that is 43 KB instead of 57 KB a workgroup: three per CU, not two
     float* Ks = smem;
@@ -326,8 +336,8 @@ __global__ __launch_bounds__(64 * NT) void attn16_bwd_kernel(const float* __rest
 #pragma unroll
     for (int t = 0; t < NT; ++t) wdt[t][0] = wdt[t][1] = wdt[t][2] = wdt[t][3] = 0xFFFFFFFFu;
     {
-        const HeadSrc16 m4[4] = {{Qs, qkv + head * HD, ld3, scale}, {Ks, qkv + E + head * HD, ld3, 1.f},
-                                 {Vs, qkv + 2 * E + head * HD, ld3, 1.f}, {Os, d_o + head * HD, E, 1.f}};
+        const HeadSrc16 m4[4] = {{Qs, qkv + head * HD, ld3, scale, 0}, {Ks, qkv + E + head * HD, ld3, 1.f, 1},
+                                 {Vs, qkv + 2 * E + head * HD, ld3, 1.f, 1}, {Os, d_o + head * HD, E, 1.f, 0}};
         // D and LSE of this wave's 16 query rows, straight from global memory (issued with the staging loads)
         const int qi = 16 * w + c;
         const size_t rowo = (size_t)(min(qi, S - 1) * B + b) * E + head * HD;
@@ -356,7 +366,7 @@ __global__ __launch_bounds__(64 * NT) void attn16_bwd_kernel(const float* __rest
             for (int t = 0; t < NT; ++t)
                 philox4((uint32_t)(bh * 28 + 4 * t + g) * 128u + (uint32_t)(16 * w + c), dc.site, dc.o0, dc.o1, dc.k0, dc.k1, wdt[t]);
         }
-        stg.store(m4, S, tid);
+        stg.store(m4, S, n, tid);
         if (SAVED) Wk[tid] = kw1;
 #pragma unroll
         for (int kk = 0; kk < KS; ++kk) part += (4 * kk + g < HD && qi < S) ? ov[kk] * dv[kk] : 0.f;
@@ -391,7 +401,8 @@ __global__ __launch_bounds__(64 * NT) void attn16_bwd_kernel(const float* __rest
     dot_tiles<HD, NT>(ps, Qs, Ks + kj * LD + g, c, g);      // S[query 16t+4g+reg][key kj] - LSE
     dot_tiles<HD, NT>(dp, Os, Vs + kj * LD + g, c, g);      // dP~[query][key] = dO . V
 
-    const bool keyok = kj < S;
+    // a key past the dialogue's length has P = 0 (and with it dS = 0): its dK and dV rows are written as zeros
+    const bool keyok = kj < n;
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
         const float4 d4 = *reinterpret_cast<const float4*>(Ds + 16 * t + 4 * g);
@@ -436,7 +447,7 @@ __global__ __launch_bounds__(64 * NT) void attn16_bwd_kernel(const float* __rest
                     ak[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a2[t & 1][r][dt], dp[t][r], ak[dt], 0, 0, 0);
                 }
         }
-        if (keyok) {
+        if (kj < S) {
             float* row = d_qkv + (size_t)(kj * B + b) * ld3 + head * HD;
 #pragma unroll
             for (int dt = 0; dt < NTD; ++dt) {
@@ -504,7 +515,8 @@ static size_t bwd_lds(int nt) {
 
 template <int HD, int NT>
 static int launch16_fwd(const float* qkv, float* o, float* lse, uint32_t* keepw, int S, int B, int E, int H, float p, uint32_t site,
-                        const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1) {
+                        const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1,
+                        const int32_t* key_len) {
     const size_t lds = fwd_lds<HD>(NT);
     if (!attn16_use_keep(B, H)) keepw = nullptr;
     if (seg1) {
@@ -514,7 +526,7 @@ static int launch16_fwd(const float* qkv, float* o, float* lse, uint32_t* keepw,
     {                                                                                                               \
         GF_TRY((lds_optin<attn16_fwd_kernel<HD, NT, W, true>>(lds, "attention_fwd")));                              \
         hipLaunchKernelGGL((attn16_fwd_kernel<HD, NT, W, true>), dim3(2 * B * H * (NT / W)), dim3(64 * W), lds, st, qkv, o, lse, keepw, \
-                           S, B, E, H, p, site, rng, add, train, s1, B * H * (NT / W));                              \
+                           S, B, E, H, p, site, rng, add, train, s1, B * H * (NT / W), (const int32_t*)nullptr);     \
     }
         if ((long)B * H < 512 && NT % 2 == 0 && NT > 2) GF_A16_FWD2((NT % 2 == 0 ? 2 : NT))
         else GF_A16_FWD2(NT)
@@ -525,14 +537,20 @@ static int launch16_fwd(const float* qkv, float* o, float* lse, uint32_t* keepw,
     // query tiles per workgroup: measured at hd = 10, S = 94 (tools/lab/attn_wpb.py, lab build): 320 problems 11.1 us as
     // whole workgroups, 10.1 / 9.9 / 11.5 us cut in 2 / 3 / 6; 640 problems 15.0 us whole, 16.4 / 17.9 / 21.5 us cut —
     // the cut pays while the problems do not fill the chip, then the repeated K / V staging costs more than the balance gains
-#define GF_A16_FWD(W)                                                                                               \
+#define GF_A16_FWD(W, LEN)                                                                                          \
     {                                                                                                               \
-        GF_TRY((lds_optin<attn16_fwd_kernel<HD, NT, W>>(lds, "attention_fwd")));                                    \
-        hipLaunchKernelGGL((attn16_fwd_kernel<HD, NT, W>), dim3(B * H * (NT / W)), dim3(64 * W), lds, st, qkv, o, lse, keepw, S, \
-                           B, E, H, p, site, rng, add, train, Attn16Seg1{}, 0);                                         \
+        GF_TRY((lds_optin<attn16_fwd_kernel<HD, NT, W, false, LEN>>(lds, "attention_fwd")));                        \
+        hipLaunchKernelGGL((attn16_fwd_kernel<HD, NT, W, false, LEN>), dim3(B * H * (NT / W)), dim3(64 * W), lds, st, qkv, o, lse, keepw, S, \
+                           B, E, H, p, site, rng, add, train, Attn16Seg1{}, 0, key_len);                                \
     }
-    if ((long)B * H < 512 && NT % 2 == 0 && NT > 2) GF_A16_FWD((NT % 2 == 0 ? 2 : NT))
-    else GF_A16_FWD(NT)
+    const bool cut = (long)B * H < 512 && NT % 2 == 0 && NT > 2;
+    if (key_len) {
+        if (cut) GF_A16_FWD((NT % 2 == 0 ? 2 : NT), true)
+        else GF_A16_FWD(NT, true)
+    } else {
+        if (cut) GF_A16_FWD((NT % 2 == 0 ? 2 : NT), false)
+        else GF_A16_FWD(NT, false)
+    }
 #undef GF_A16_FWD
     GF_LAUNCH_CHECK();
     return 0;
@@ -540,17 +558,23 @@ static int launch16_fwd(const float* qkv, float* o, float* lse, uint32_t* keepw,
 template <int HD, int NT>
 static int launch16_bwd(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keepw, float* d_qkv,
                         int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train,
-                        hipStream_t st) {
+                        hipStream_t st, const int32_t* key_len) {
     const size_t lds = bwd_lds<HD>(NT);
-    if (keepw != nullptr && train && p > 0.f && attn16_use_keep(B, H)) {          // the forward of this pass stored its keep words
-        GF_TRY((lds_optin<attn16_bwd_kernel<HD, NT, true>>(lds, "attention_bwd")));
-        hipLaunchKernelGGL((attn16_bwd_kernel<HD, NT, true>), dim3(B * H), dim3(64 * NT), lds, st, qkv, o, lse, d_o, keepw, d_qkv, S,
-                           B, E, H, p, site, rng, add, train);
-    } else {
-        GF_TRY((lds_optin<attn16_bwd_kernel<HD, NT, false>>(lds, "attention_bwd")));
-        hipLaunchKernelGGL((attn16_bwd_kernel<HD, NT, false>), dim3(B * H), dim3(64 * NT), lds, st, qkv, o, lse, d_o, keepw, d_qkv, S,
-                           B, E, H, p, site, rng, add, train);
+#define GF_A16_BWD(SAVED, LEN)                                                                                      \
+    {                                                                                                               \
+        GF_TRY((lds_optin<attn16_bwd_kernel<HD, NT, SAVED, LEN>>(lds, "attention_bwd")));                           \
+        hipLaunchKernelGGL((attn16_bwd_kernel<HD, NT, SAVED, LEN>), dim3(B * H), dim3(64 * NT), lds, st, qkv, o, lse, d_o, keepw, d_qkv, \
+                           S, B, E, H, p, site, rng, add, train, key_len);                                              \
     }
+    const bool saved = keepw != nullptr && train && p > 0.f && attn16_use_keep(B, H);      // the forward of this pass stored its keep words
+    if (key_len) {
+        if (saved) GF_A16_BWD(true, true)
+        else GF_A16_BWD(false, true)
+    } else {
+        if (saved) GF_A16_BWD(true, false)
+        else GF_A16_BWD(false, false)
+    }
+#undef GF_A16_BWD
     GF_LAUNCH_CHECK();
     return 0;
 }
@@ -573,26 +597,28 @@ static int launch16_bwd(const float* qkv, const float* o, const float* lse, cons
     }
 
 int launch_attn16_fwd(const float* qkv, float* o, float* lse, uint32_t* keepw, int S, int B, int E, int H, float p, uint32_t site,
-                      const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1) {
+                      const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1,
+                      const int32_t* key_len) {
     GF_CHECK_ARG(!seg1 || (seg1->qkv && seg1->o), "attn16_fwd: bad second batch");
+    GF_CHECK_ARG(!(seg1 && key_len), "attn16_fwd: key lengths are not taken together with a second batch");
     GF_CHECK_ARG(attn16_supported(E, H, S) && S >= 1 && S <= GANFFN_MAX_SEQ, "attn16_fwd: unsupported E=%d H=%d S=%d", E, H, S);
     GF_CHECK_ARG((long)B * H * 28 * 128 < (1l << 32), "attention: B*H too large for the Philox counter");
-    if (E / H == 64) { NT16_SWITCH3(launch16_fwd, 64, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st, seg1) }
-    if (E / H == 60) { NT16_SWITCH3(launch16_fwd, 60, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st, seg1) }
-    if (E / H == 10) { NT16_SWITCH(launch16_fwd, 10, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st, seg1) }
-    NT16_SWITCH(launch16_fwd, 30, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st, seg1)
+    if (E / H == 64) { NT16_SWITCH3(launch16_fwd, 64, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st, seg1, key_len) }
+    if (E / H == 60) { NT16_SWITCH3(launch16_fwd, 60, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st, seg1, key_len) }
+    if (E / H == 10) { NT16_SWITCH(launch16_fwd, 10, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st, seg1, key_len) }
+    NT16_SWITCH(launch16_fwd, 30, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st, seg1, key_len)
 }
 
 int launch_attn16_bwd(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keepw, float* d_qkv,
                       int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train,
-                      hipStream_t st) {
+                      hipStream_t st, const int32_t* key_len) {
     GF_CHECK_ARG(attn16_supported(E, H, S) && S >= 1 && S <= GANFFN_MAX_SEQ, "attn16_bwd: unsupported E=%d H=%d S=%d", E, H, S);
     GF_CHECK_ARG(o && lse, "attention_bwd: head_dim %d needs the forward's output and log-sum-exp", E / H);
     GF_CHECK_ARG((long)B * H * 28 * 128 < (1l << 32), "attention: B*H too large for the Philox counter");
-    if (E / H == 64) { NT16_SWITCH3(launch16_bwd, 64, qkv, o, lse, d_o, keepw, d_qkv, S, B, E, H, p, site, rng, add, train, st) }
-    if (E / H == 60) { NT16_SWITCH3(launch16_bwd, 60, qkv, o, lse, d_o, keepw, d_qkv, S, B, E, H, p, site, rng, add, train, st) }
-    if (E / H == 10) { NT16_SWITCH(launch16_bwd, 10, qkv, o, lse, d_o, keepw, d_qkv, S, B, E, H, p, site, rng, add, train, st) }
-    NT16_SWITCH(launch16_bwd, 30, qkv, o, lse, d_o, keepw, d_qkv, S, B, E, H, p, site, rng, add, train, st)
+    if (E / H == 64) { NT16_SWITCH3(launch16_bwd, 64, qkv, o, lse, d_o, keepw, d_qkv, S, B, E, H, p, site, rng, add, train, st, key_len) }
+    if (E / H == 60) { NT16_SWITCH3(launch16_bwd, 60, qkv, o, lse, d_o, keepw, d_qkv, S, B, E, H, p, site, rng, add, train, st, key_len) }
+    if (E / H == 10) { NT16_SWITCH(launch16_bwd, 10, qkv, o, lse, d_o, keepw, d_qkv, S, B, E, H, p, site, rng, add, train, st, key_len) }
+    NT16_SWITCH(launch16_bwd, 30, qkv, o, lse, d_o, keepw, d_qkv, S, B, E, H, p, site, rng, add, train, st, key_len)
 }
 
 }  // namespace ganffn

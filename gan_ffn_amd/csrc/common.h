@@ -339,17 +339,26 @@ constexpr int ATTN_KEEP_WORDS = 28 * 16;
 struct AttnFwdSeg1 {
     const float* qkv; float* o; float* lse; uint32_t* keep; int train;
 };
+// key_len (optional, device int32 [B]): dialogue b attends over keys j < clamp(key_len[b], 1, S) only (probability 0 past it,
+// dK and dV rows written as zeros); null = all S keys, today's bits.  Not taken together with seg1.
 int launch_attention_fwd(const float* qkv, float* o, float* lse, uint32_t* keep, int S, int B, int E, int H, float p, uint32_t site,
-                         const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1 = nullptr);
+                         const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1 = nullptr,
+                         const int32_t* key_len = nullptr);
 int launch_attention_bwd(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keep, float* d_qkv,
                          int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train,
-                         hipStream_t st);
+                         hipStream_t st, const int32_t* key_len = nullptr);
+// the key length of dialogue b inside a kernel instantiated for lengths: one scalar load per workgroup (b is workgroup-uniform),
+// clamped here so that a bad length can neither empty a softmax nor move a read out of range
+__device__ __forceinline__ int attn_key_len(const int32_t* __restrict__ key_len, int b, int S) {
+    return key_len ? min(max(key_len[b], 1), S) : S;
+}
 bool attn16_supported(int E, int H, int S);
 int launch_attn16_fwd(const float* qkv, float* o, float* lse, uint32_t* keepw, int S, int B, int E, int H, float p, uint32_t site,
-                      const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1 = nullptr);
+                      const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1 = nullptr,
+                      const int32_t* key_len = nullptr);
 int launch_attn16_bwd(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keepw, float* d_qkv,
                       int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train,
-                      hipStream_t st);
+                      hipStream_t st, const int32_t* key_len = nullptr);
 
 // out1 (optional): a second segment over the same x in the same launch, with its own output and train flag
 int launch_pe_dropout(const float* x, const float* pe, float* out, int S, int B, int E, float p,

@@ -237,11 +237,15 @@ class BiModel(nn.Module):
 
 class GAN_FFN_DialogueRNN(nn.Module):
     """fusion = G_a(acoustic) + G_v(visual) + G_t(text) -> BiModel (model.py:1465-1528).  `gelu`, `relu`, `dropout`
-    and `fc1` exist on the reference object without taking part in forward; they are kept so state_dicts match."""
+    and `fc1` exist on the reference object without taking part in forward; they are kept so state_dicts match.
+    mask_padding (default False: the reference passes no mask) is an extension: the generators' self-attention ignores the padded
+    utterances of every dialogue (key lengths umask.sum(1), derived on the device), the one place where padding reached a real
+    utterance's prediction.  `umask` must then be a PREFIX mask.  A plain attribute: the state_dict is the same either way."""
 
     def __init__(self, acoustic_generator, visual_generator, text_generator, D_m, D_g, D_p, D_e, D_h, D_a, n_classes,
-                 listener_state, context_attention, dropout_rec, dropout):
+                 listener_state, context_attention, dropout_rec, dropout, mask_padding=False):
         super().__init__()
+        self.mask_padding = bool(mask_padding)
         self.n_classes = n_classes
         self.acoustic_generator = acoustic_generator
         self.visual_generator = visual_generator
@@ -253,7 +257,9 @@ class GAN_FFN_DialogueRNN(nn.Module):
         self.fc1 = nn.Linear(100, n_classes)
 
     def forward(self, acoustic, visual, text, qmask, umask):
-        fusion = self.acoustic_generator(acoustic) + self.visual_generator(visual) + self.text_generator(text)
+        from . import ops
+        kl = ops.key_lengths_from_umask(umask) if self.mask_padding else None
+        fusion = self.acoustic_generator(acoustic, kl) + self.visual_generator(visual, kl) + self.text_generator(text, kl)
         return self.bi_model(fusion, qmask, umask)
 
 

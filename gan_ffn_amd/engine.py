@@ -383,6 +383,10 @@ class _NetRunner(_Runner):
     are the defaults here; GanEngine, whose sub-steps run on several streams, overrides `_cur_pg`, `_communicators` and
     `_pre_write`."""
     _cur_pg = None               # the communicator of the sub-step being issued (None: self.pg)
+    # int32 [B] key lengths of the step being issued (Phase2Engine / DrnnEngine with mask_padding: the generators' self-attention
+    # ignores padded utterances), or None: the plain encoder calls.  Held here until the next step replaces it, so the tensor
+    # outlives the backward that reads it.  GanEngine never sets it.
+    _key_len = None
 
     def _communicators(self):
         """every communicator the engine issues collectives on"""
@@ -405,7 +409,8 @@ class _NetRunner(_Runner):
             a0, a1 = self._next_add(), self._next_add()
         else:
             a0, a1 = self._base_add + adds[0], self._base_add + adds[1]
-        ops.encoder_fwd_raw(cfg, x, net.pe, net.slab, ps.enc_out, ps.saved if save else None, self.ws, self.rng.state, a0)
+        ops.encoder_fwd_raw(cfg, x, net.pe, net.slab, ps.enc_out, ps.saved if save else None, self.ws, self.rng.state, a0,
+                            key_len=self._key_len)
         w = net.w
         w3 = w("fc3.weight") if net.kind == 1 else None
         b3 = w("fc3.bias") if net.kind == 1 else None
@@ -437,14 +442,16 @@ class _NetRunner(_Runner):
             # caller did not zero the encoder region of net.grad) -> (parts view of self.ws, stride, chunks)
             return ops.encoder_bwd_parts_raw(cfg, ps.dx, net.slab, gslab, ps.saved, self.ws, self.rng.state, a0, need_dx)
         if reduce_cb is None or not want_wgrad:
-            ops.encoder_bwd_raw(cfg, 0, net.L, ps.dx, net.slab, gslab, ps.saved, self.ws, self.rng.state, a0, need_dx)
+            ops.encoder_bwd_raw(cfg, 0, net.L, ps.dx, net.slab, gslab, ps.saved, self.ws, self.rng.state, a0, need_dx,
+                                key_len=self._key_len)
         else:
             # bucketed: backward a group of layers, then hand that slice of the grad slab to the all-reduce
             bks = net.buckets(self.n_buckets)
             reduce_cb(*bks[0], last=False)                       # head (+object handled by caller before this)
             for i, (lo_f, hi_f) in enumerate(bks[1:]):
                 lo, hi = lo_f // net.layer_floats, hi_f // net.layer_floats
-                ops.encoder_bwd_raw(cfg, lo, hi, ps.dx, net.slab, gslab, ps.saved, self.ws, self.rng.state, a0, need_dx)
+                ops.encoder_bwd_raw(cfg, lo, hi, ps.dx, net.slab, gslab, ps.saved, self.ws, self.rng.state, a0, need_dx,
+                                    key_len=self._key_len)
                 reduce_cb(lo_f, hi_f, last=(i == len(bks) - 2))
 
     def _adam(self, net, parts=None):
@@ -1032,10 +1039,14 @@ def _generator_bwd(eng, k, d_out, adds):
 class Phase2Engine(_NetRunner):
     """One step of train_or_eval_model on GAN_FFN: log_softmax(fc(G_a(a) + G_v(v) + G_t(t))), MaskedNLLLoss with
     class weights, backward through the three generators, Adam(lr, weight_decay=l2) on everything.
-    The reference re-creates a LambdaLR every batch, which pins the effective lr to its base value."""
+    The reference re-creates a LambdaLR every batch, which pins the effective lr to its base value.
+    mask_padding (default False: the reference passes no mask) is an extension: the three generators' self-attention sees only the
+    first umask.sum(1) utterances of every dialogue (ganffn_encoder_fwd_len / _bwd_len), so a dialogue's prediction does not depend
+    on how far its batch is padded.  umask must then be a prefix mask.  False issues exactly the calls it always did."""
 
     def __init__(self, ffn_module, lr=1e-4, weight_decay=0.008, class_weights=CLASS_WEIGHTS, process_group=None,
-                 n_buckets=3):
+                 n_buckets=3, mask_padding=False):
+        self.mask_padding = bool(mask_padding)
         self.module = ffn_module
         self.G = _module_generators(ffn_module, lr, weight_decay)
         self._init_common(next(iter(self.G.values())).slab.device, process_group, n_buckets, self.G.items())
@@ -1085,6 +1096,9 @@ class Phase2Engine(_NetRunner):
         T, C_ = S * B, self.n_classes
         self._adds = 0
         self._base_add = self.rng.next_add(8)      # 3 generators x (encoder, head): one block from the device allocator
+        if self.mask_padding and ops._CHECK_QMASK:
+            ops.check_prefix_mask(batch["umask"], "Phase2Engine")
+        self._key_len = ops.key_lengths_from_umask(batch["umask"]) if self.mask_padding else None   # on the device: no host read
         adds = {}
         for k in ("acoustic", "visual", "text"):                    # model.py:1441-1443
             adds[k] = self._net_fwd(self.G[k], self.pass_G[k], batch[k], train=train, save=train)
@@ -1145,11 +1159,15 @@ class DrnnEngine(_NetRunner):
     run (D_g != D_p, D_g > 512, dot with D_m != D_g, concat D_a limits).
     max_dialogues (32 .. ops.MAX_DIALOGUES; default 32): the most dialogues a step takes.  It is a capacity, not a switch: the
     family is decided from the batch's own B (more than 32 dialogues: the same step with the dialogues in tiles of 32 inside
-    every launch)."""
+    every launch).
+    mask_padding (default False: the reference passes no mask) is an extension: the generators' self-attention sees only the first
+    umask.sum(1) utterances of every dialogue — the lengths tensor the recurrence already uses, so the step has no launch more —
+    and with that no part of the step lets padding reach a real utterance.  False issues exactly the calls it always did."""
 
     def __init__(self, net, lr=1e-4, weight_decay=1e-5, class_weights=CLASS_WEIGHTS, process_group=None, n_buckets=3,
-                 n_streams=1, max_dialogues=32):
+                 n_streams=1, max_dialogues=32, mask_padding=False):
         from . import dialogue_rnn as DR
+        self.mask_padding = bool(mask_padding)
         self.max_dialogues = _check_max_dialogues("DrnnEngine", max_dialogues)
         self.module = net
         bm = net.bi_model
@@ -1241,6 +1259,8 @@ class DrnnEngine(_NetRunner):
             S, B = self._shape[:2]
             self._tune_x = (self._shape, {m: torch.zeros(S, B, self.G[m].E, device=self.dev) for m in self.G})
         self.ws = self.ws3[k]
+        if self.mask_padding and (self._key_len is None or self._key_len.numel() != self._shape[1]):
+            self._key_len = torch.full((self._shape[1],), self._shape[0], device=self.dev, dtype=torch.int32)     # the probe: full lengths
         # (save=True: these pass buffers and their workspace were sized for the saving mode; the next real forward overwrites)
         self._net_fwd(self.G[k], self.pass_G[k], self._tune_x[1][k], train=False, save=True, adds=(0, 1))
 
@@ -1317,11 +1337,10 @@ class DrnnEngine(_NetRunner):
             row = qmask.sum(2)
             if not bool((((row == 1) & (qmask.max(2).values == 1)) | (row == 0)).all()):
                 raise ValueError("DrnnEngine: qmask rows must be one-hot (or all zero on padding)")
-            L_ = umask.sum(1).long()
-            if not bool((umask == (torch.arange(S, device=umask.device).unsqueeze(0) < L_.unsqueeze(1)).to(umask.dtype)).all()):
-                raise ValueError("DrnnEngine: umask rows must be prefixes (1 .. 1 0 .. 0)")
+            ops.check_prefix_mask(umask, "DrnnEngine")
         # per-batch index data (tiny): dialogue lengths, speaker index / value per step, in both directions
         lens = umask.sum(1).to(torch.int32)
+        self._key_len = lens if self.mask_padding else None
         spk_f = torch.argmax(qmask, 2).to(torch.int32).contiguous()
         mval_f = qmask.max(2).values.contiguous()
         t_idx = torch.arange(S, device=self.dev).unsqueeze(1)
@@ -1343,6 +1362,8 @@ class DrnnEngine(_NetRunner):
                 self.streams[i].wait_event(fork)
                 if batch[k].is_cuda:
                     batch[k].record_stream(self.streams[i])      # the caller may drop the batch while this stream still reads it
+                if self._key_len is not None:
+                    self._key_len.record_stream(self.streams[i])
                 with torch.cuda.stream(self.streams[i]):
                     adds[k] = self._net_fwd(self.G[k], self.pass_G[k], batch[k], train=train, save=train)
             else:

@@ -133,9 +133,38 @@ def head_sizes(cfg):
 # ----------------------------------------------------------------------------------------------
 # raw calls (no autograd) — used by the autograd Functions below and by engine.py
 # ----------------------------------------------------------------------------------------------
-def encoder_fwd_raw(cfg, x, pe, slab, out, saved, ws, rng, add):
-    _lib.call("ganffn_encoder_fwd", C.byref(cfg), _ptr(x), _ptr(pe), _ptr(slab), _ptr(out), _ptr(saved), _ptr(ws),
-              _ptr(rng), C.c_uint64(add), _stream())
+def key_lengths_from_umask(umask):
+    """int32 [batch] utterance counts of a prefix mask [batch, seq_len], computed where umask lives (no host read): the key
+    lengths of a mask_padding forward"""
+    if umask is None:
+        raise ValueError("mask_padding=True needs umask (batch, seq_len) to know every dialogue's length")
+    return umask.sum(1).to(torch.int32)
+
+
+def check_prefix_mask(umask, who):
+    """GANFFN_CHECK_QMASK=1 (one host sync per batch): lengths are umask.sum(1) — a mask with holes would silently mask the
+    wrong keys / steps"""
+    S = umask.shape[1]
+    L_ = umask.sum(1).long()
+    if not bool((umask == (torch.arange(S, device=umask.device).unsqueeze(0) < L_.unsqueeze(1)).to(umask.dtype)).all()):
+        raise ValueError("%s: umask rows must be prefixes (1 .. 1 0 .. 0)" % who)
+
+
+def _check_key_len(key_len, cfg):
+    if key_len.dtype != torch.int32 or not key_len.is_cuda or not key_len.is_contiguous() or key_len.numel() != cfg.B:
+        raise ValueError("key_len must be a contiguous int32 device tensor with one entry per dialogue (%d)" % cfg.B)
+
+
+def encoder_fwd_raw(cfg, x, pe, slab, out, saved, ws, rng, add, key_len=None):
+    """key_len (int32 device tensor [B], or None): the attention of every layer sees keys j < key_len[b] of dialogue b only
+    (ganffn_encoder_fwd_len); None is the plain call."""
+    if key_len is None:
+        _lib.call("ganffn_encoder_fwd", C.byref(cfg), _ptr(x), _ptr(pe), _ptr(slab), _ptr(out), _ptr(saved), _ptr(ws),
+                  _ptr(rng), C.c_uint64(add), _stream())
+        return
+    _check_key_len(key_len, cfg)
+    _lib.call("ganffn_encoder_fwd_len", C.byref(cfg), _ptr(key_len), _ptr(x), _ptr(pe), _ptr(slab), _ptr(out), _ptr(saved),
+              _ptr(ws), _ptr(rng), C.c_uint64(add), _stream())
 
 
 def encoder_fwd_pair_supported(cfg):
@@ -157,9 +186,14 @@ def encoder_fwd_pair_raw(cfg, x, pe, slab, out_eval, out_train, saved_train, ws,
               _ptr(saved_train), _ptr(ws), _ptr(rng), C.c_uint64(add_train), _stream())
 
 
-def encoder_bwd_raw(cfg, lo, hi, dx, slab, gslab, saved, ws, rng, add, need_dx_in=True):
+def encoder_bwd_raw(cfg, lo, hi, dx, slab, gslab, saved, ws, rng, add, need_dx_in=True, key_len=None):
     """need_dx_in=False: the stack's input needs no gradient — with lo == 0 the bottom in-proj dgrad and the PE dropout
-    backward are skipped (as autograd skips them) and dx is undefined afterwards."""
+    backward are skipped (as autograd skips them) and dx is undefined afterwards.  key_len: the lengths the forward was given."""
+    if key_len is not None:
+        _check_key_len(key_len, cfg)
+        _lib.call("ganffn_encoder_bwd_len", C.byref(cfg), _ptr(key_len), lo, hi, _ptr(dx), _ptr(slab), _ptr(gslab), _ptr(saved),
+                  _ptr(ws), _ptr(rng), C.c_uint64(add), 1 if need_dx_in else 0, _stream())
+        return
     _lib.call("ganffn_encoder_bwd2", C.byref(cfg), lo, hi, _ptr(dx), _ptr(slab), _ptr(gslab), _ptr(saved), _ptr(ws),
               _ptr(rng), C.c_uint64(add), 1 if need_dx_in else 0, _stream())
 
@@ -282,7 +316,9 @@ class EncoderFn(torch.autograd.Function):
         out = torch.empty(S, B, E, device=x.device, dtype=torch.float32)
         rng = DeviceRng.get(x.device)
         add = rng.next_add() if train else 0
-        encoder_fwd_raw(cfg, xc, pe, slab, out, saved, ws, rng.state, add)
+        key_len = meta.get("key_len")
+        encoder_fwd_raw(cfg, xc, pe, slab, out, saved, ws, rng.state, add, key_len=key_len)
+        ctx.key_len = key_len          # (kept alive for the backward)
         ctx.cfg, ctx.add, ctx.rng_state = cfg, add, rng.state
         ctx.slab, ctx.saved = slab, saved
         ctx.param_meta = meta
@@ -297,7 +333,7 @@ class EncoderFn(torch.autograd.Function):
         want_w = any(ctx.needs_input_grad[4:])
         gslab = torch.zeros_like(ctx.slab) if want_w else None
         encoder_bwd_raw(cfg, 0, cfg.L, dx, ctx.slab, gslab, ctx.saved, ws, ctx.rng_state, ctx.add,
-                        need_dx_in=ctx.needs_input_grad[0])
+                        need_dx_in=ctx.needs_input_grad[0], key_len=ctx.key_len)
         grads = [None] * len(meta["views"])
         if want_w:
             for i, (off, shape) in enumerate(meta["views"]):

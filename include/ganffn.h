@@ -490,6 +490,40 @@ int ganffn_attention_fwd_keep(const float* qkv, float* o, float* lse, uint32_t* 
 int ganffn_attention_bwd_keep(const float* qkv, const float* o, const float* lse, const float* d_o,
                               const uint32_t* keep, float* d_qkv, int S, int B, int E, int H, float p, uint32_t site,
                               const uint64_t* rng, uint64_t rng_offset_add, void* stream);
+/* ---- key-length attention: padded utterances are not attended to -----------------------------------------------------------
+ * An extension the reference does not have (its nn.TransformerEncoder calls pass no mask, so a generator's output for a real
+ * utterance depends on how far the batch was padded): what nn.TransformerEncoder(..., src_key_padding_mask = mask) computes
+ * when mask[b][j] = (j >= key_len[b]), on the same padded layout.  key_len is DEVICE int32 [B], never read by the host; a
+ * kernel reads its dialogue's entry once per workgroup and clamps it to [1, S], so a bad length can neither empty a softmax
+ * nor move a read out of range (the kernels behind the calls without lengths are instantiations of their own: they do not pay for
+ * it).  With n = clamp(key_len[b], 1, S):
+ *   forward   for every query row i < S (padded query rows are computed too) P[i][j] = softmax over j < n of q_i k_j / sqrt(hd)
+ *             and 0 for j >= n; lse is over j < n; the dropout keep bits are those of the calls above (the Philox indexing
+ *             does not depend on lengths); o_i = sum_j P~[i][j] v_j.
+ *   backward  the gradient of that forward; keys j >= n get P = 0 explicitly in the recompute, and the k and v parts of d_qkv at
+ *             rows n .. S-1 are WRITTEN as exact zeros.
+ *   padding   finite values of k and v at rows >= n change no bit of any output (those rows are staged with a 0 factor).
+ * keep may be NULL (as ganffn_attention_fwd / _bwd) or the keep words of ganffn_attention_fwd_keep.  key_len == NULL is exactly
+ * the calls above, with the same bits, and so is key_len[b] >= S for every b.
+ * ganffn_encoder_fwd_len / _bwd_len: ganffn_encoder_fwd / ganffn_encoder_bwd2 with the lengths handed to the attention core of
+ * every layer — the only place of a layer where rows of a dialogue meet; everything else in a stack is row-wise.  Saved and
+ * workspace sizes and layouts are those of ganffn_encoder_saved_floats / _workspace_floats, unchanged; the same launches.
+ * The forward and the backward of one pass must be given the same lengths.
+ * NOT covered: the two-segment forward (ganffn_encoder_fwd_pair), ganffn_encoder_bwd_parts and the BCE calls take no lengths, so
+ * the GAN step (GanEngine) attends over padding as the reference does; the classifier step runners and the module path use
+ * these entry points when asked to (mask_padding). */
+int ganffn_attention_fwd_len(const float* qkv, float* o, float* lse, uint32_t* keep, const int32_t* key_len, int S, int B,
+                             int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t rng_offset_add,
+                             void* stream);
+int ganffn_attention_bwd_len(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keep,
+                             const int32_t* key_len, float* d_qkv, int S, int B, int E, int H, float p, uint32_t site,
+                             const uint64_t* rng, uint64_t rng_offset_add, void* stream);
+int ganffn_encoder_fwd_len(const ganffn_enc_cfg* cfg, const int32_t* key_len, const float* x_in, const float* pe,
+                           const float* params, float* out, float* saved, float* workspace, const uint64_t* rng,
+                           uint64_t rng_offset_add, void* stream);
+int ganffn_encoder_bwd_len(const ganffn_enc_cfg* cfg, const int32_t* key_len, int layer_lo, int layer_hi, float* dx,
+                           const float* params, float* grads, const float* saved, float* workspace, const uint64_t* rng,
+                           uint64_t rng_offset_add, int need_dx_in, void* stream);
 /* z = x + drop(y); xhat = (z-mean)*rstd; out = xhat*w + b   (norm1/norm2 of the encoder layer).  Accepted: T >= 1 and
  * 1 <= E <= 640, a multiple of 4 or not; a wider row is refused with a message.  The variance is the two-pass one (mean
  * of the squared deviations), so a row mean far above the row's spread costs no more than fp32 rounding of z itself. */
