@@ -630,7 +630,7 @@ static int check_head(const ganffn_head_cfg* c) {
     GF_CHECK_ARG(c->D1 >= 4 && (c->D1 & 3) == 0 && c->D2 >= 4 && (c->D2 & 3) == 0, "head: D1=%d D2=%d must be multiples of 4", c->D1, c->D2);
     GF_CHECK_ARG(c->kind == 0 || c->kind == 1, "head: kind=%d", c->kind);
     GF_CHECK_ARG(c->kind == 0 || c->D2 <= 32, "disc head: D2=%d > 32", c->D2);
-    GF_CHECK_ARG(c->p >= 0.f && c->p < 1.f, "head: p out of [0,1)");
+    GF_CHECK_ARG(c->p >= 0.f && c->p < 1.f, "head: p=%g out of [0,1)", (double)c->p);
     return 0;
 }
 extern "C" int64_t ganffn_head_saved_floats(const ganffn_head_cfg* c) {
@@ -703,6 +703,12 @@ extern "C" int ganffn_head_bwd(const ganffn_head_cfg* c, const float* d_out, con
     GF_CHECK_ARG(aligned16(workspace), "head_bwd: workspace must be 16-byte aligned");
     GF_CHECK_ARG(c->kind == 0 || w3, "head_bwd: disc needs fc3");
     GF_CHECK_ARG(!(c->train && c->p > 0.f) || rng, "head_bwd: rng required in train mode");
+    // gradient pointers come in pairs: the bias gradient is the column sum of the weight-gradient launch, and the fc3 reduce
+    // writes both — refused here, before the first launch, so that nothing is written
+    GF_CHECK_ARG(gw1 || !gb1, "head_bwd: gb1 given without gw1 (a bias gradient needs its weight gradient)");
+    GF_CHECK_ARG(gw2 || !gb2, "head_bwd: gb2 given without gw2 (a bias gradient needs its weight gradient)");
+    GF_CHECK_ARG(gw3 || !gb3, "head_bwd: gb3 given without gw3 (a bias gradient needs its weight gradient)");
+    GF_CHECK_ARG(!gw3 || gb3, "head_bwd: gw3 given without gb3 (the fc3 gradients are reduced together)");
     hipStream_t st = (hipStream_t)stream;
     const int T = c->T, E = c->E, D1 = c->D1, D2 = c->D2, train = c->train;
     const float* s0 = saved;

@@ -121,6 +121,11 @@ def enc_sizes(cfg):
     return s, w
 
 
+def head_cfg(T, E, D1, D2, kind, p=0.2, train=False):
+    """kind 0: generator head, 1: discriminator head (include/ganffn.h ganffn_head_cfg)"""
+    return HeadCfg(T, E, D1, D2, kind, p, 1 if train else 0)
+
+
 def head_sizes(cfg):
     lib = _lib.load()
     s = int(lib.ganffn_head_saved_floats(C.byref(cfg)))

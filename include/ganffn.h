@@ -173,7 +173,10 @@ int ganffn_head_fwd(const ganffn_head_cfg* cfg, const float* x, const float* w1,
                     const float* w2, const float* b2, const float* w3, const float* b3, float* out,
                     float* saved, float* workspace, const uint64_t* rng, uint64_t rng_offset_add,
                     void* stream);
-/* d_out: gen [T x D2], disc [T x 1].  dx [T x E] written.  g* accumulated (+=) when non-NULL. */
+/* d_out: gen [T x D2], disc [T x 1].  dx [T x E] written.  g* accumulated (+=) when non-NULL.
+ * The gradient pointers come in pairs: a bias gradient without its weight gradient (gbK != NULL, gwK == NULL, K = 1, 2, 3)
+ * is refused, and so is gw3 without gb3 (the fc3 reduce writes both); gw1 / gw2 without gb1 / gb2 are legal, and all NULL
+ * computes dx alone (the pass through a frozen discriminator).  A refused call names the pair and writes nothing. */
 int ganffn_head_bwd(const ganffn_head_cfg* cfg, const float* d_out, const float* x,
                     const float* w1, const float* w2, const float* w3, float* gw1, float* gb1,
                     float* gw2, float* gb2, float* gw3, float* gb3, float* dx, const float* saved,
