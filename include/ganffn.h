@@ -430,7 +430,11 @@ int ganffn_drnn_batch_bwd(const ganffn_drnn_cfg* cfg, const ganffn_drnn_att* att
  *   FORWARD-time token row t = s*B + b, column c < D_e, one (seed, offset + rng_offset_add); the first half at site_f, the
  *   second at site_b.  The second half's mask applies after the reversal: the element of e_b at reverse step len_b-1-s
  *   lands on row s*B + b and takes that row's mask, as the reference applies dropout_rec to reverse(e_b).
- * ganffn_mask_pos_inplace: d[i] = aux[i] > 0 ? d[i] * mscale : 0 — backward through dropout(relu(.)) from the saved output. */
+ * lens [B] (ganffn_seq_reverse, ganffn_drnn_join_*): 0 <= lens[b] <= S.  The kernels do not clamp it — a length outside that
+ *   range indexes outside the buffers — so the range is the caller's contract.  Rows s >= lens[b] of a reversed tensor are
+ *   exact zeros (accumulate: left as they are).
+ * ganffn_mask_pos_inplace: d[i] = aux[i] > 0 ? d[i] * mscale : 0 — backward through dropout(relu(.)) from the saved output.
+ *   The predicate is IEEE's: a positive subnormal passes, +0 and -0 mask; a masked element is +0. */
 int ganffn_seq_reverse(const float* x, const int32_t* lens, float* out, int S, int B, int D, int accumulate, void* stream);
 int ganffn_drnn_join_fwd(const float* e_f, const float* e_b, const int32_t* lens, float* emotions, int S, int B, int De,
                          float p, uint32_t site_f, uint32_t site_b, const uint64_t* rng, uint64_t rng_offset_add, int train,
@@ -555,8 +559,12 @@ int ganffn_gemm_n100(const float* A, const float* W, int w_kmajor, const float* 
  * have no specialised kernel (the d_model-512 generator, nn.Linear call sites model.py:1244-1252 via torch's
  * TransformerEncoderLayer).  mode 0: C = A[M x K] W[N x K]^T, mode 1: C = A[M x K] W[K x N].  epi 0: + bias; 1: bias + ReLU +
  * dropout (linear1); 3: C = acc * (aux > 0 ? 1/(1-p) : 0) (dgrad through ReLU + dropout, aux = the saved activation [M x N]).
+ * epi 0 with aux != NULL: C = A W + bias + aux, aux [M x N] — the fused residual / branch add that ganffn_encoder_bwd, the
+ * LSTM and the DialogueRNN backward rely on.  epi 3 tests aux > 0 as IEEE does (a positive subnormal counts as positive, +0 and
+ * -0 do not), the same predicate as the 1-bit pattern of ganffn_ffn_k100_hook, which is taken from the bits of the activation.
  * max_slabs > 1 with epi 0: K is split the way the encoder splits few-tile long-K products, slab z at C + z * slab_stride,
- * *n_slabs = slabs written (their sum is the product).  bench.py replays one iteration's launch mix through it. */
+ * *n_slabs = slabs written (their sum is the product; bias and aux are added into slab 0 only; slabs at index *n_slabs and
+ * above are not touched).  bench.py replays one iteration's launch mix through it. */
 int ganffn_gemm_hook(int mode, int epi, const float* A, const float* W, const float* bias, const float* aux, float* C,
                      int64_t slab_stride, int M, int N, int K, float p, uint32_t site, const uint64_t* rng,
                      uint64_t rng_offset_add, int train, int max_slabs, int* n_slabs, void* stream);
@@ -687,7 +695,8 @@ int ganffn_zero_floats(float* p, int64_t n, void* stream);
 /* Measurement hook: the K = 100 -> 2048 products of the d_model-100 feed-forward block (csrc/gemm.hip gemm_wres_kernel) with the
  * arguments ganffn_encoder_fwd / _bwd give them (linear1 / linear2 of nn.TransformerEncoderLayer, call sites model.py:1210,1307).
  * which 0: out[T x 2048] = dropout_p(relu(a[T x 100] w[2048 x 100]^T + bias)); hmask != NULL: also the 1-bit [out > 0] pattern
- *          (ceil(T/32) * 2048 floats) a saved pass leaves for the backward.
+ *          (ceil(T/32) * 2048 floats) a saved pass leaves for the backward.  Only the bits of rows < T are specified: when
+ *          T % 32 != 0 the bits of rows >= T in the last row tile hold whatever the padded rows computed.
  * which 1: out[T x 2048] = (a[T x 100] w[100 x 2048]) * pattern / (1-p) — the linear2 dgrad; pattern from hmask when given,
  *          else from h_saved [T x 2048] > 0. */
 int ganffn_ffn_k100_hook(int which, const float* a, const float* w, const float* bias, float* out, void* hmask,
