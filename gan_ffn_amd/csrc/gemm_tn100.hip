@@ -504,9 +504,11 @@ int launch_gemm_tn100_grouped(const TnDesc* d, int n, hipStream_t st, float* par
         if (splits > WMAXSPLIT) splits = WMAXSPLIT;
         if (splits > kmax / 256) splits = kmax / 256;
         if (md.tn100_force_splits() > 0) splits = md.tn100_force_splits() < WMAXSPLIT ? md.tn100_force_splits() : WMAXSPLIT;
-        if (slabs != nullptr) {
-            if ((long)(splits - 1) * slabs->range_floats > part_floats) splits = 1 + (int)(part_floats / slabs->range_floats);
-        } else if ((long)splits * per_split > part_floats) splits = (int)(part_floats / per_split);
+        // the reduce launch's clamp holds for unreduced slabs too, although they need one slab less: the chunk count decides the
+        // association of the sum, and ganffn_adam_step_parts promises the reduce launch's (a 9- or 10-layer stack from 768
+        // tokens on: 3 chunks of the whole group do not fit, 2 gradient-shaped slabs would)
+        if ((long)splits * per_split > part_floats) splits = (int)(part_floats / per_split);
+        if (slabs != nullptr && (long)(splits - 1) * slabs->range_floats > part_floats) splits = 1 + (int)(part_floats / slabs->range_floats);
         if (splits < 2) splits = 1;
     }
     grp.splits = splits;

@@ -135,7 +135,13 @@ int ganffn_encoder_fwd_pair(const ganffn_enc_cfg* cfg, const float* x_in, const 
  * is ACCUMULATED into (+=) when non-NULL; NULL skips every weight gradient (train_gen's pass
  * through the frozen discriminator, train_IEMOCAP.py:245-250: those grads are never used).
  * Splitting the range lets the caller start a layer's gradient all-reduce while earlier layers
- * are still in backward. */
+ * are still in backward.
+ * A sequence of range calls (top range first, the same dx and grads) computes what the whole-range
+ * call computes, to rounding and NOT to the bit: the layer below a boundary reads dx from a plain
+ * unsplit GEMM where the whole-range pass forms that product inside the next LayerNorm backward
+ * (d_model 100) or as split-K slabs (other widths), and a smaller group of weight-gradient problems
+ * may cut its token range into another number of chunks (from 512 tokens on).  Every call is
+ * bit-reproducible in itself; the workspace carries nothing from one call to the next. */
 int ganffn_encoder_bwd(const ganffn_enc_cfg* cfg, int layer_lo, int layer_hi, float* dx,
                        const float* params, float* grads, const float* saved, float* workspace,
                        const uint64_t* rng, uint64_t rng_offset_add, void* stream);
@@ -156,7 +162,8 @@ int ganffn_encoder_bwd2(const ganffn_enc_cfg* cfg, int layer_lo, int layer_hi, f
  * like that region; the LayerNorm parameter gradients are written too.  So grads' encoder region [0, L * layer floats) need
  * NOT be zeroed by the caller (everything behind it — heads, `object` — still accumulates).  ganffn_adam_step_parts then adds
  * the chunks in order: exactly the sum, in exactly the association, that ganffn_encoder_bwd2's reduce launch forms — the
- * update is bit-identical.  The workspace must stay untouched between the two calls.
+ * update is bit-identical (*n_parts is the chunk count the reduce launch chooses for the same pass, also where the
+ * unreduced form alone would have room for more).  The workspace must stay untouched between the two calls.
  * ganffn_encoder_bwd_parts_supported(cfg): 1 when this form exists for cfg (d_model 100, default kernel paths), else 0;
  * ganffn_encoder_bwd_parts_covered(E, F): floats at the head of each layer block that the chunks cover (weights and biases of
  * in-proj, out-proj, linear1, linear2; the LayerNorm parameters behind them are not chunked). */
