@@ -318,9 +318,10 @@ extern "C" int64_t ganffn_encoder_fwd_pair_workspace_floats(const ganffn_enc_cfg
     if (check_cfg(c) != 0) return -1;
     return pair_eval_ws_floats(c) + (int64_t)MAX_SPLITS * c->S * c->B * c->E + 64;
 }
-extern "C" int ganffn_encoder_fwd_pair(const ganffn_enc_cfg* c, const float* x_in, const float* pe, const float* params,
-                                       float* out_eval, float* out_train, float* saved_train, float* workspace,
-                                       const uint64_t* rng, uint64_t add_train, void* stream) {
+// key_len (or null): handed to the attention of every layer; both segments are the same B dialogues, so one [B] array serves both
+static int encoder_fwd_pair_impl(const ganffn_enc_cfg* c, const int32_t* key_len, const float* x_in, const float* pe,
+                                 const float* params, float* out_eval, float* out_train, float* saved_train, float* workspace,
+                                 const uint64_t* rng, uint64_t add_train, void* stream) {
     const Mode md = mode();
     GF_TRY(check_cfg(c));
     GF_CHECK_ARG(pair_supported(c, md), "encoder_fwd_pair: no two-segment form for E=%d H=%d F=%d S=%d (ganffn_encoder_fwd_pair_supported)",
@@ -375,7 +376,7 @@ extern "C" int ganffn_encoder_fwd_pair(const ganffn_enc_cfg* c, const float* x_i
         {
             const AttnFwdSeg1 a1{s1v + so.qkv, s1v + so.attn_o, s1v + so.lse, reinterpret_cast<uint32_t*>(s1v + so.keep), train};
             GF_TRY(launch_attention_fwd(sv0 + so.qkv, sv0 + so.attn_o, sv0 + so.lse, nullptr, S, B, E, H, c->p_enc, site + 0, rng, add, 0,
-                                        st, &a1));
+                                        st, &a1, key_len));
         }
         if (rc) {
             RcFwdSeg1 s1{};
@@ -427,6 +428,17 @@ extern "C" int ganffn_encoder_fwd_pair(const ganffn_enc_cfg* c, const float* x_i
     return 0;
 }
 
+extern "C" int ganffn_encoder_fwd_pair(const ganffn_enc_cfg* c, const float* x_in, const float* pe, const float* params,
+                                       float* out_eval, float* out_train, float* saved_train, float* workspace,
+                                       const uint64_t* rng, uint64_t add_train, void* stream) {
+    return encoder_fwd_pair_impl(c, nullptr, x_in, pe, params, out_eval, out_train, saved_train, workspace, rng, add_train, stream);
+}
+extern "C" int ganffn_encoder_fwd_pair_len(const ganffn_enc_cfg* c, const int32_t* key_len, const float* x_in, const float* pe,
+                                           const float* params, float* out_eval, float* out_train, float* saved_train,
+                                           float* workspace, const uint64_t* rng, uint64_t add_train, void* stream) {
+    return encoder_fwd_pair_impl(c, key_len, x_in, pe, params, out_eval, out_train, saved_train, workspace, rng, add_train, stream);
+}
+
 // ------------------------------------------------------------------------------------------
 // encoder stack backward over layers [lo_l, hi_l)
 // ------------------------------------------------------------------------------------------
@@ -462,18 +474,24 @@ extern "C" int ganffn_encoder_bwd_parts_supported(const ganffn_enc_cfg* c) {
     return bwd_parts_supported(c, mode()) ? 1 : 0;
 }
 extern "C" int64_t ganffn_encoder_bwd_parts_covered(int E, int F) { return layer_off(E, F).n1w; }
-extern "C" int ganffn_encoder_bwd_parts(const ganffn_enc_cfg* c, float* dx, const float* params, float* grads, const float* saved,
-                                        float* workspace, const uint64_t* rng, uint64_t add, int need_dx_in, int64_t* part_offset,
-                                        int64_t* part_stride, int* n_parts, void* stream) {
+extern "C" int ganffn_encoder_bwd_parts_len(const ganffn_enc_cfg* c, const int32_t* key_len, float* dx, const float* params,
+                                            float* grads, const float* saved, float* workspace, const uint64_t* rng, uint64_t add,
+                                            int need_dx_in, int64_t* part_offset, int64_t* part_stride, int* n_parts, void* stream) {
     GF_TRY(check_cfg(c));
     GF_CHECK_ARG(grads && part_offset && part_stride && n_parts, "encoder_bwd_parts: null pointer");
     GF_CHECK_ARG(bwd_parts_supported(c, mode()), "encoder_bwd_parts: this stack's weight gradients are reduced in the launch (ask ganffn_encoder_bwd_parts_supported)");
     TnSlabs sl{grads, (long)c->L * layer_off(c->E, c->F).total, 1, nullptr, 0};
-    GF_TRY(encoder_bwd_impl(c, 0, c->L, dx, params, grads, saved, workspace, rng, add, need_dx_in, stream, &sl));
+    GF_TRY(encoder_bwd_impl(c, 0, c->L, dx, params, grads, saved, workspace, rng, add, need_dx_in, stream, &sl, key_len));
     *n_parts = sl.n_parts;
     *part_offset = sl.part ? sl.part - workspace : 0;
     *part_stride = sl.part_stride;
     return 0;
+}
+extern "C" int ganffn_encoder_bwd_parts(const ganffn_enc_cfg* c, float* dx, const float* params, float* grads, const float* saved,
+                                        float* workspace, const uint64_t* rng, uint64_t add, int need_dx_in, int64_t* part_offset,
+                                        int64_t* part_stride, int* n_parts, void* stream) {
+    return ganffn_encoder_bwd_parts_len(c, nullptr, dx, params, grads, saved, workspace, rng, add, need_dx_in, part_offset, part_stride,
+                                        n_parts, stream);
 }
 static int encoder_bwd_impl(const ganffn_enc_cfg* c, int layer_lo, int layer_hi, float* dx, const float* params,
                             float* grads, const float* saved, float* workspace, const uint64_t* rng, uint64_t add,

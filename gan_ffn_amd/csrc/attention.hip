@@ -316,7 +316,8 @@ __device__ __forceinline__ bool kept(const unsigned long long (&mq)[4], int c, i
 // PAIR: two batches of the same shape in one launch (the eval-mode and the train-mode pass of one generator): workgroups
 // 0 .. B H - 1 are the first batch's, the rest the second's with its own qkv / o and train flag.  Wave-uniform, chosen once;
 // (dialogue, head) indices and the Philox counters are local to the batch: each batch gets the bits of its own launch.
-// LEN: per-dialogue key lengths (key_len, device int32 [B]; never together with PAIR) — a template flag, so that the
+// LEN: per-dialogue key lengths (key_len, device int32 [B]; with PAIR the two batches are the same B dialogues and b is local
+// to the batch, so key_len[b] serves both) — a template flag, so that the
 // instantiations without lengths keep the instructions they had (see attention16.hip)
 template <int HD, int NT, bool PAIR = false, bool LEN = false>
 __global__ __launch_bounds__(64 * NT) void attention_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ o, AttnGeom g,
@@ -576,7 +577,11 @@ static int check_attn(int S, int B, int E, int H) {
 template <int HD, int NT>
 static int launch_fwd_t(const float* qkv, float* o, const AttnGeom& g, size_t lds, float p, uint32_t site, const uint64_t* rng,
                         uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1, const int32_t* key_len) {
-    if (seg1) {
+    if (seg1 && key_len) {
+        GF_TRY((lds_optin<attention_fwd_kernel<HD, NT, true, true>>(lds, "attention_fwd")));
+        hipLaunchKernelGGL((attention_fwd_kernel<HD, NT, true, true>), dim3(2 * g.B * g.H), dim3(64 * NT), lds, st, qkv, o, g, p, site,
+                           rng, add, train, seg1->qkv, seg1->o, seg1->train, key_len);
+    } else if (seg1) {
         GF_TRY((lds_optin<attention_fwd_kernel<HD, NT, true>>(lds, "attention_fwd")));
         hipLaunchKernelGGL((attention_fwd_kernel<HD, NT, true>), dim3(2 * g.B * g.H), dim3(64 * NT), lds, st, qkv, o, g, p, site, rng,
                            add, train, seg1->qkv, seg1->o, seg1->train, (const int32_t*)nullptr);
@@ -620,7 +625,6 @@ int launch_attention_fwd(const float* qkv, float* o, float* lse, uint32_t* keep,
                          const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1,
                          const int32_t* key_len) {
     GF_TRY(check_attn(S, B, E, H));
-    GF_CHECK_ARG(!(seg1 && key_len), "attention_fwd: key lengths are not taken together with a second batch");
     GF_CHECK_ARG(qkv && o, "attention_fwd: null pointer");
     GF_CHECK_ARG(!seg1 || (seg1->qkv && seg1->o), "attention_fwd: bad second batch");
     GF_CHECK_ARG(!((train || (seg1 && seg1->train)) && p > 0.f) || rng, "attention_fwd: rng required when dropout is active");

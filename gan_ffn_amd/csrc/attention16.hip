@@ -184,7 +184,8 @@ __device__ __forceinline__ void store4(float* __restrict__ row, int d0, const fl
 struct Attn16Seg1 {
     const float* qkv; float* o; float* lse; uint32_t* keepw; int train;
 };
-// LEN: per-dialogue key lengths (key_len, device int32 [B]; never together with PAIR).  A template flag and not a test of the
+// LEN: per-dialogue key lengths (key_len, device int32 [B]; with PAIR both batches are the same B dialogues and b is already
+// local to the batch, so key_len[b] serves both).  A template flag and not a test of the
 // pointer: the instantiations without lengths (every launch of the GAN step) keep the instructions they had — no scalar load, no
 // uniform branch (the listings compared: profiles/attention_key_len_ab.txt).
 template <int HD, int NT, int WPB, bool PAIR = false, bool LEN = false>
@@ -522,14 +523,20 @@ static int launch16_fwd(const float* qkv, float* o, float* lse, uint32_t* keepw,
     if (seg1) {
         // the workgroup cut and the keep-word rule are those of ONE batch of B dialogues: what a single launch would choose
         Attn16Seg1 s1{seg1->qkv, seg1->o, seg1->lse, attn16_use_keep(B, H) ? seg1->keep : nullptr, seg1->train};
-#define GF_A16_FWD2(W)                                                                                              \
+#define GF_A16_FWD2(W, LEN)                                                                                         \
     {                                                                                                               \
-        GF_TRY((lds_optin<attn16_fwd_kernel<HD, NT, W, true>>(lds, "attention_fwd")));                              \
-        hipLaunchKernelGGL((attn16_fwd_kernel<HD, NT, W, true>), dim3(2 * B * H * (NT / W)), dim3(64 * W), lds, st, qkv, o, lse, keepw, \
-                           S, B, E, H, p, site, rng, add, train, s1, B * H * (NT / W), (const int32_t*)nullptr);     \
+        GF_TRY((lds_optin<attn16_fwd_kernel<HD, NT, W, true, LEN>>(lds, "attention_fwd")));                         \
+        hipLaunchKernelGGL((attn16_fwd_kernel<HD, NT, W, true, LEN>), dim3(2 * B * H * (NT / W)), dim3(64 * W), lds, st, qkv, o, lse, keepw, \
+                           S, B, E, H, p, site, rng, add, train, s1, B * H * (NT / W), key_len);                     \
     }
-        if ((long)B * H < 512 && NT % 2 == 0 && NT > 2) GF_A16_FWD2((NT % 2 == 0 ? 2 : NT))
-        else GF_A16_FWD2(NT)
+        const bool cut2 = (long)B * H < 512 && NT % 2 == 0 && NT > 2;
+        if (key_len) {
+            if (cut2) GF_A16_FWD2((NT % 2 == 0 ? 2 : NT), true)
+            else GF_A16_FWD2(NT, true)
+        } else {
+            if (cut2) GF_A16_FWD2((NT % 2 == 0 ? 2 : NT), false)
+            else GF_A16_FWD2(NT, false)
+        }
 #undef GF_A16_FWD2
         GF_LAUNCH_CHECK();
         return 0;
@@ -600,7 +607,6 @@ int launch_attn16_fwd(const float* qkv, float* o, float* lse, uint32_t* keepw, i
                       const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1,
                       const int32_t* key_len) {
     GF_CHECK_ARG(!seg1 || (seg1->qkv && seg1->o), "attn16_fwd: bad second batch");
-    GF_CHECK_ARG(!(seg1 && key_len), "attn16_fwd: key lengths are not taken together with a second batch");
     GF_CHECK_ARG(attn16_supported(E, H, S) && S >= 1 && S <= GANFFN_MAX_SEQ, "attn16_fwd: unsupported E=%d H=%d S=%d", E, H, S);
     GF_CHECK_ARG((long)B * H * 28 * 128 < (1l << 32), "attention: B*H too large for the Philox counter");
     if (E / H == 64) { NT16_SWITCH3(launch16_fwd, 64, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st, seg1, key_len) }

@@ -340,7 +340,7 @@ struct AttnFwdSeg1 {
     const float* qkv; float* o; float* lse; uint32_t* keep; int train;
 };
 // key_len (optional, device int32 [B]): dialogue b attends over keys j < clamp(key_len[b], 1, S) only (probability 0 past it,
-// dK and dV rows written as zeros); null = all S keys, today's bits.  Not taken together with seg1.
+// dK and dV rows written as zeros); null = all S keys, today's bits.  With seg1 the lengths serve both batches (the same B dialogues).
 int launch_attention_fwd(const float* qkv, float* o, float* lse, uint32_t* keep, int S, int B, int E, int H, float p, uint32_t site,
                          const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1 = nullptr,
                          const int32_t* key_len = nullptr);

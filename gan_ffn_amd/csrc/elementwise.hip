@@ -465,6 +465,70 @@ __global__ void bce_bwd_kernel(const float* __restrict__ prob, float target_a, f
     dprob[i] = scale / (float)n * (p - target) / fmaxf(p * (1.0f - p), 1e-12f);
 }
 
+// The BCE pair with per-dialogue lengths: prob is [S x Bt] (element i = s * Bt + c), column c holds a dialogue of
+// n_c = clamp(key_len[c % n_len], 1, S) real utterances (the clamp of attn_key_len; key_len null: n_c = S) and the mean runs over
+// the count = sum_c n_c positions s < n_c only.  Lengths and count are integers, set up in LDS by every workgroup (Bt <= 512), so
+// no launch depends on another.  Loop stride, tree and the `scale / (float)count` expressions are bce_fwd_kernel's and
+// bce_bwd_kernel's: with every n_c = S the results have the bits of ganffn_bce2 with period = Bt.
+constexpr int BCE_LEN_MAX_COLS = 512;
+__device__ __forceinline__ int bce_len_setup(const int32_t* __restrict__ key_len, int n_len, int S, int Bt, int* nlen, int* count) {
+    if (threadIdx.x == 0) *count = 0;
+    __syncthreads();
+    for (int c = threadIdx.x; c < Bt; c += blockDim.x) {
+        const int nc = attn_key_len(key_len, key_len ? c % n_len : 0, S);
+        nlen[c] = nc;
+        atomicAdd(count, nc);
+    }
+    __syncthreads();
+    return *count;
+}
+__global__ __launch_bounds__(1024) void bce_len_fwd_kernel(const float* __restrict__ prob, const int32_t* __restrict__ key_len,
+                                                           int n_len, float target_a, float target_b, int S, int Bt, int split,
+                                                           float scale, float* __restrict__ loss, int accumulate) {
+    __shared__ float red[16];
+    __shared__ int nlen[BCE_LEN_MAX_COLS];
+    __shared__ int count_s;
+    const int count = bce_len_setup(key_len, n_len, S, Bt, nlen, &count_s);
+    const int n = S * Bt;
+    float s = 0.f;
+    for (int i = threadIdx.x; i < n; i += 1024) {
+        const int row = i / Bt, c = i - row * Bt;
+        if (row >= nlen[c]) continue;
+        const float target = (c >= split) ? target_b : target_a;
+        const float p = prob[i];
+        const float lp = fmaxf(logf(p), -100.f);
+        const float l1p = fmaxf(logf(1.0f - p), -100.f);
+        s -= target * lp + (1.0f - target) * l1p;
+    }
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = 0.f;
+        for (int w = 0; w < 16; ++w) t += red[w];
+        t = t * scale / (float)count;
+        loss[0] = accumulate ? loss[0] + t : t;
+    }
+}
+
+__global__ __launch_bounds__(256) void bce_len_bwd_kernel(const float* __restrict__ prob, const int32_t* __restrict__ key_len,
+                                                          int n_len, float target_a, float target_b, int S, int Bt, int split,
+                                                          float scale, float* __restrict__ dprob) {
+    __shared__ int nlen[BCE_LEN_MAX_COLS];
+    __shared__ int count_s;
+    const int count = bce_len_setup(key_len, n_len, S, Bt, nlen, &count_s);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= S * Bt) return;
+    const int row = i / Bt, c = i - row * Bt;
+    if (row >= nlen[c]) {
+        dprob[i] = 0.0f;
+        return;
+    }
+    const float target = (c >= split) ? target_b : target_a;
+    const float p = prob[i];
+    dprob[i] = scale / (float)count * (p - target) / fmaxf(p * (1.0f - p), 1e-12f);
+}
+
 // ------------------------------------------------------------------------------------------
 // A10: Adam, flat slab.  t = *step + 1 (the counter is bumped by adam_step_inc afterwards)
 // ------------------------------------------------------------------------------------------
@@ -905,6 +969,32 @@ extern "C" int ganffn_bce2_bwd(const float* prob, float target_a, float target_b
                                float* dprob, void* stream) {
     GF_CHECK_ARG(prob && dprob && n > 0 && period >= 0 && split >= 0, "bce_bwd: bad arguments");
     hipLaunchKernelGGL(bce_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, prob, target_a, target_b, period, split, n, scale, dprob);
+    GF_LAUNCH_CHECK();
+    return 0;
+}
+
+static int check_bce_len(const char* who, const void* prob, const void* out, const int32_t* key_len, int n_len, int S, int Bt,
+                         int split) {
+    GF_CHECK_ARG(prob && out, "%s: null pointer", who);
+    GF_CHECK_ARG(S >= 1 && Bt >= 1 && Bt <= BCE_LEN_MAX_COLS && (long)S * Bt < (1l << 31), "%s: bad S=%d Bt=%d (Bt <= %d)", who, S, Bt,
+                 BCE_LEN_MAX_COLS);
+    GF_CHECK_ARG(split >= 0 && split <= Bt, "%s: split=%d outside [0, Bt=%d]", who, split, Bt);
+    GF_CHECK_ARG(!key_len || (n_len >= 1 && n_len <= Bt), "%s: n_len=%d outside [1, Bt=%d]", who, n_len, Bt);
+    return 0;
+}
+extern "C" int ganffn_bce_len_fwd(const float* prob, const int32_t* key_len, int n_len, float target_a, float target_b, int S,
+                                  int Bt, int split, float scale, float* loss_out, int accumulate, void* stream) {
+    GF_TRY(check_bce_len("bce_len_fwd", prob, loss_out, key_len, n_len, S, Bt, split));
+    hipLaunchKernelGGL(bce_len_fwd_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, prob, key_len, n_len, target_a, target_b, S, Bt,
+                       split, scale, loss_out, accumulate);
+    GF_LAUNCH_CHECK();
+    return 0;
+}
+extern "C" int ganffn_bce_len_bwd(const float* prob, const int32_t* key_len, int n_len, float target_a, float target_b, int S,
+                                  int Bt, int split, float scale, float* dprob, void* stream) {
+    GF_TRY(check_bce_len("bce_len_bwd", prob, dprob, key_len, n_len, S, Bt, split));
+    hipLaunchKernelGGL(bce_len_bwd_kernel, dim3((S * Bt + 255) / 256), dim3(256), 0, (hipStream_t)stream, prob, key_len, n_len, target_a,
+                       target_b, S, Bt, split, scale, dprob);
     GF_LAUNCH_CHECK();
     return 0;
 }

@@ -385,8 +385,12 @@ class _NetRunner(_Runner):
     _cur_pg = None               # the communicator of the sub-step being issued (None: self.pg)
     # int32 [B] key lengths of the step being issued (Phase2Engine / DrnnEngine with mask_padding: the generators' self-attention
     # ignores padded utterances), or None: the plain encoder calls.  Held here until the next step replaces it, so the tensor
-    # outlives the backward that reads it.  GanEngine never sets it.
+    # outlives the backward that reads it.  GanEngine, whose passes have two batch widths, overrides _pass_key_len instead.
     _key_len = None
+
+    def _pass_key_len(self, ps):
+        """the key lengths of a forward / backward on the pass buffers ps (None: the plain encoder calls)"""
+        return self._key_len
 
     def _communicators(self):
         """every communicator the engine issues collectives on"""
@@ -410,7 +414,7 @@ class _NetRunner(_Runner):
         else:
             a0, a1 = self._base_add + adds[0], self._base_add + adds[1]
         ops.encoder_fwd_raw(cfg, x, net.pe, net.slab, ps.enc_out, ps.saved if save else None, self.ws, self.rng.state, a0,
-                            key_len=self._key_len)
+                            key_len=self._pass_key_len(ps))
         w = net.w
         w3 = w("fc3.weight") if net.kind == 1 else None
         b3 = w("fc3.bias") if net.kind == 1 else None
@@ -440,10 +444,11 @@ class _NetRunner(_Runner):
         if parts and want_wgrad and reduce_cb is None:
             # single GPU, d_model 100: the weight gradients stay as token-chunk slabs for Adam to add (no reduce launch, and the
             # caller did not zero the encoder region of net.grad) -> (parts view of self.ws, stride, chunks)
-            return ops.encoder_bwd_parts_raw(cfg, ps.dx, net.slab, gslab, ps.saved, self.ws, self.rng.state, a0, need_dx)
+            return ops.encoder_bwd_parts_raw(cfg, ps.dx, net.slab, gslab, ps.saved, self.ws, self.rng.state, a0, need_dx,
+                                             key_len=self._pass_key_len(ps))
         if reduce_cb is None or not want_wgrad:
             ops.encoder_bwd_raw(cfg, 0, net.L, ps.dx, net.slab, gslab, ps.saved, self.ws, self.rng.state, a0, need_dx,
-                                key_len=self._key_len)
+                                key_len=self._pass_key_len(ps))
         else:
             # bucketed: backward a group of layers, then hand that slice of the grad slab to the all-reduce
             bks = net.buckets(self.n_buckets)
@@ -451,7 +456,7 @@ class _NetRunner(_Runner):
             for i, (lo_f, hi_f) in enumerate(bks[1:]):
                 lo, hi = lo_f // net.layer_floats, hi_f // net.layer_floats
                 ops.encoder_bwd_raw(cfg, lo, hi, ps.dx, net.slab, gslab, ps.saved, self.ws, self.rng.state, a0, need_dx,
-                                    key_len=self._key_len)
+                                    key_len=self._pass_key_len(ps))
                 reduce_cb(lo_f, hi_f, last=(i == len(bks) - 2))
 
     def _adam(self, net, parts=None):
@@ -577,10 +582,22 @@ class GanEngine(_NetRunner):
     DAG over the six networks (e.g. (D_t|G_a) only needs G_a from sub-step 2 and can run beside
     (D_v|G_t)/(G_t|D_v)); every sub-step waits for the writers of what it reads and, before its Adam, for
     the readers of what it writes — so each one sees exactly the parameter versions of the sequential
-    schedule.  Most kernels of this workload fill a fraction of the 256 CUs, so overlapping them is free."""
+    schedule.  Most kernels of this workload fill a fraction of the 256 CUs, so overlapping them is free.
+
+    mask_padding (default False: the reference passes no mask and averages its losses over every padded position) is an
+    extension: iteration(batch) reads batch["umask"] [B, S]; every generator and discriminator pass of every sub-step attends
+    over the real utterances of its dialogue only (key lengths = umask.sum(1), computed and kept on the device; a discriminator's
+    [real | fake] pass of 2B dialogues gets them twice), and both losses are means over the real utterances (ganffn_bce_len).
+    Padded rows then get a loss gradient of exactly 0, so finite values at padded positions of the batch change no bit of any
+    loss, gradient or updated parameter.  Under a process group each rank divides by its OWN count of real utterances: the
+    all-reduced gradient is the mean of the ranks' masked means (as the reference's is the mean of their padded means), not the
+    mean over all ranks' utterances.  GANFFN_CHECK_QMASK=1 checks that umask rows are prefixes (one host sync per batch).  Off,
+    the engine issues exactly the calls it issued before the option existed."""
 
     def __init__(self, gens, discs, lr=1e-4, b1=0.5, b2=0.6, process_group=None, n_buckets=3, use_graph=False,
-                 n_streams=1, schedule=None):
+                 n_streams=1, schedule=None, mask_padding=False):
+        self.mask_padding = bool(mask_padding)
+        self._kl1 = self._kl2 = None         # int32 key lengths of the iteration being issued: [B], and [2B] = the same twice
         # optimizers: train_IEMOCAP.py:292-297 (G lr, text-G 1.1*lr, every D lr/2); call site :603-606
         self.G = {k: NetState(m, lr * (1.1 if k == "text" else 1.0), (b1, b2)) for k, m in gens.items()}
         self.D = {k: NetState(m, lr / 2, (b1, b2)) for k, m in discs.items()}
@@ -647,6 +664,11 @@ class GanEngine(_NetRunner):
 
     def _communicators(self):
         return self.pgs
+
+    def _pass_key_len(self, ps):
+        if self._kl1 is None:
+            return None
+        return self._kl2 if ps.B == self._kl2.numel() else self._kl1
 
     # ------------------------------------------------------------------------------------------
     def _prepare(self, S, B):
@@ -758,7 +780,7 @@ class GanEngine(_NetRunner):
         generator over x: one two-segment encoder pass, then the two heads; -> the train pass's (enc_add, head_add)"""
         a0, a1 = self._base_add + adds_train[0], self._base_add + adds_train[1]
         ops.encoder_fwd_pair_raw(ps_train.cfg_train, x, net.pe, net.slab, ps_eval.enc_out, ps_train.enc_out, ps_train.saved,
-                                 self.ws, self.rng.state, a0)
+                                 self.ws, self.rng.state, a0, key_len=self._pass_key_len(ps_train))
         w = net.w
         w3 = w("fc3.weight") if net.kind == 1 else None
         b3 = w("fc3.bias") if net.kind == 1 else None
@@ -801,10 +823,15 @@ class GanEngine(_NetRunner):
         torch.cat((x_real, pg_.out), dim=1, out=self.x_cat)
         adds = self._net_fwd(Dn, pd, self.x_cat, train=True, save=True, adds=(a + 2, a + 3))
         n = S * 2 * B
-        ops._lib.call("ganffn_bce2_fwd", ops._ptr(pd.out), C.c_float(1.0), C.c_float(0.0), 2 * B, B, n, C.c_float(1.0),
-                      ops._ptr(self.losses[loss_slot:loss_slot + 1]), 0, ops._stream())
-        ops._lib.call("ganffn_bce2_bwd", ops._ptr(pd.out), C.c_float(1.0), C.c_float(0.0), 2 * B, B, n, C.c_float(1.0),
-                      ops._ptr(self.dprob2), ops._stream())
+        if self._kl1 is not None:
+            # the mean over real utterances only; the real and the fake half have the same lengths (key_len[c % B])
+            ops.bce_len_fwd_raw(pd.out, self._kl1, B, 1.0, 0.0, S, 2 * B, B, 1.0, self.losses[loss_slot:loss_slot + 1], False)
+            ops.bce_len_bwd_raw(pd.out, self._kl1, B, 1.0, 0.0, S, 2 * B, B, 1.0, self.dprob2)
+        else:
+            ops._lib.call("ganffn_bce2_fwd", ops._ptr(pd.out), C.c_float(1.0), C.c_float(0.0), 2 * B, B, n, C.c_float(1.0),
+                          ops._ptr(self.losses[loss_slot:loss_slot + 1]), 0, ops._stream())
+            ops._lib.call("ganffn_bce2_bwd", ops._ptr(pd.out), C.c_float(1.0), C.c_float(0.0), 2 * B, B, n, C.c_float(1.0),
+                          ops._ptr(self.dprob2), ops._stream())
         parts_mode = self._parts_ok(Dn, pd)
         self._zero_grad(Dn, parts_mode)                              # opt.zero_grad(), :216
         cb, finish = self._make_reducer(Dn)
@@ -836,8 +863,12 @@ class GanEngine(_NetRunner):
             g_adds = self.train_gen_forward(who, batch, loss_slot)
         d_adds = self._net_fwd(Dn, pd, pg_.out, train=False, save=True, adds=(a + 2, a + 3))       # disc.eval(), :243
         n = S * B
-        ops.bce_fwd_raw(pd.out, 1.0, n, 1.0, self.losses[loss_slot:loss_slot + 1], False)
-        ops.bce_bwd_raw(pd.out, 1.0, n, 1.0, self.dprob1)
+        if self._kl1 is not None:
+            ops.bce_len_fwd_raw(pd.out, self._kl1, B, 1.0, 1.0, S, B, B, 1.0, self.losses[loss_slot:loss_slot + 1], False)
+            ops.bce_len_bwd_raw(pd.out, self._kl1, B, 1.0, 1.0, S, B, B, 1.0, self.dprob1)
+        else:
+            ops.bce_fwd_raw(pd.out, 1.0, n, 1.0, self.losses[loss_slot:loss_slot + 1], False)
+            ops.bce_bwd_raw(pd.out, 1.0, n, 1.0, self.dprob1)
         self._net_bwd(Dn, pd, self.dprob1, False, d_adds, False)             # through the frozen D: dgrad only
         parts_mode = self._parts_ok(Gn, pg_)
         self._zero_grad(Gn, parts_mode)
@@ -851,9 +882,11 @@ class GanEngine(_NetRunner):
             self._wait_readers(self._cur_stream, [net_key])
 
     # ------------------------------------------------------------------------------------------
-    def _iteration_body(self, batch, device_rng_advance):
+    def _iteration_body(self, batch, device_rng_advance, lens=None):
+        """lens: (int32 [B], int32 [2B]) key lengths of this batch on the device (mask_padding), or None"""
         self._adds = 0
         self._check_slabs()
+        self._kl1, self._kl2 = lens if lens is not None else (None, None)
         if not device_rng_advance:
             # eager: this iteration's block of dropout offsets comes from the device's one allocator (shared with the
             # module path and every other engine); iterations may overlap, the offsets are host-side arguments
@@ -883,6 +916,8 @@ class GanEngine(_NetRunner):
                 for k in self.modalities:
                     if batch[k].is_cuda:
                         batch[k].record_stream(st)
+                for t_ in lens or ():
+                    t_.record_stream(st)                     # computed on the caller's stream, read by every sub-step stream
             for i, (kind, who, partner) in enumerate(self.schedule):
                 st = self.streams[smap[i]]
                 trained = (kind, who)
@@ -932,28 +967,49 @@ class GanEngine(_NetRunner):
         """One batch = 12 sub-steps.  Returns the device tensor of the 12 sub-step losses (no host sync).
         With n_streams > 1 call synchronize() (or loss_dict()) before reading it on the current stream."""
         S, B = batch[self.modalities[0]].shape[:2]
+        self._kl1 = self._kl2 = None             # (the stream probe of _prepare runs plain forwards)
         self._prepare(S, B)
+        lens = self._batch_lens(batch, S, B) if self.mask_padding else None
         if not self.use_graph:
-            self._iteration_body(batch, device_rng_advance=False)
+            self._iteration_body(batch, device_rng_advance=False, lens=lens)
             return self.losses
         if self.static_batch is None:
             self.static_batch = {k: batch[k].clone() for k in self.modalities}
+            if lens is not None:
+                self.static_batch["key_len"], self.static_batch["key_len2"] = lens[0].clone(), lens[1].clone()
         else:
-            for k in self.static_batch:
+            for k in self.modalities:
                 self.static_batch[k].copy_(batch[k])
+            if lens is not None:
+                self.static_batch["key_len"].copy_(lens[0])
+                self.static_batch["key_len2"].copy_(lens[1])
+        if lens is not None:
+            lens = (self.static_batch["key_len"], self.static_batch["key_len2"])     # the addresses the graph was captured on
         if self._graph is None:
             # warm up on a side stream (allocations, lazy module init), then capture
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
-                self._iteration_body(self.static_batch, device_rng_advance=True)
+                self._iteration_body(self.static_batch, device_rng_advance=True, lens=lens)
             torch.cuda.current_stream().wait_stream(s)
             torch.cuda.synchronize()
             self._graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self._graph):
-                self._iteration_body(self.static_batch, device_rng_advance=True)
+                self._iteration_body(self.static_batch, device_rng_advance=True, lens=lens)
         self._graph.replay()
         return self.losses
+
+    def _batch_lens(self, batch, S, B):
+        """mask_padding: (key lengths [B], the same twice [2B]) from batch["umask"] [B, S], on the device, no host read"""
+        umask = batch.get("umask") if hasattr(batch, "get") else None
+        if umask is None:
+            raise ValueError('GanEngine(mask_padding=True) needs batch["umask"] (batch, seq_len) to know every dialogue\'s length')
+        if tuple(umask.shape) != (B, S):
+            raise ValueError('batch["umask"] must be [%d, %d] (batch, seq_len), got %s' % (B, S, tuple(umask.shape)))
+        if ops._CHECK_QMASK:
+            ops.check_prefix_mask(umask, "GanEngine")
+        kl = ops.key_lengths_from_umask(umask.to(self.dev)).contiguous()
+        return kl, torch.cat((kl, kl))
 
     def loss_dict(self):
         """host copy of the last iteration's losses under the reference's column names (last value per key,
@@ -984,13 +1040,14 @@ def build_networks(D_h=100, dropout=0.2, device="cuda", seed=None):
 
 
 def train_GAN(gens, discs, batches, epochs=1, lr=1e-4, b1=0.5, b2=0.6, process_group=None, use_graph=False, log=None,
-              n_streams=3, reserve_S=None):
+              n_streams=3, reserve_S=None, mask_padding=False):
     """Counterpart of train_GAN (train_IEMOCAP.py:255-393) over an iterable of batches per epoch.
     Returns rows of the GAN_loss table (columns train_IEMOCAP.py:308-316): last batch of each epoch.
     reserve_S: size the step buffers once for dialogues up to this length (PositionalEncoding allows 110), so that
     batches of varying length never re-allocate.
-    The losses are read on the host per batch only when `log` wants them; otherwise once per epoch (the last batch's)."""
-    eng = GanEngine(gens, discs, lr, b1, b2, process_group, use_graph=use_graph, n_streams=n_streams)
+    The losses are read on the host per batch only when `log` wants them; otherwise once per epoch (the last batch's).
+    mask_padding: every batch carries "umask" [B, S]; attention and losses ignore padded utterances (GanEngine)."""
+    eng = GanEngine(gens, discs, lr, b1, b2, process_group, use_graph=use_graph, n_streams=n_streams, mask_padding=mask_padding)
     rows = []
     for epoch in range(epochs):
         last = kept = None

@@ -184,11 +184,17 @@ def encoder_fwd_pair_workspace_floats(cfg):
     return w
 
 
-def encoder_fwd_pair_raw(cfg, x, pe, slab, out_eval, out_train, saved_train, ws, rng, add_train):
+def encoder_fwd_pair_raw(cfg, x, pe, slab, out_eval, out_train, saved_train, ws, rng, add_train, key_len=None):
     """cfg: the train-mode cfg.  out_eval = the eval-mode forward of x (nothing kept), out_train / saved_train = the
-    train-mode forward with its saved set — one pass, the bits of the two encoder_fwd_raw calls."""
-    _lib.call("ganffn_encoder_fwd_pair", C.byref(cfg), _ptr(x), _ptr(pe), _ptr(slab), _ptr(out_eval), _ptr(out_train),
-              _ptr(saved_train), _ptr(ws), _ptr(rng), C.c_uint64(add_train), _stream())
+    train-mode forward with its saved set — one pass, the bits of the two encoder_fwd_raw calls.  key_len (int32 device
+    tensor [B], or None): the lengths of the B dialogues, for both segments (ganffn_encoder_fwd_pair_len)."""
+    if key_len is None:
+        _lib.call("ganffn_encoder_fwd_pair", C.byref(cfg), _ptr(x), _ptr(pe), _ptr(slab), _ptr(out_eval), _ptr(out_train),
+                  _ptr(saved_train), _ptr(ws), _ptr(rng), C.c_uint64(add_train), _stream())
+        return
+    _check_key_len(key_len, cfg)
+    _lib.call("ganffn_encoder_fwd_pair_len", C.byref(cfg), _ptr(key_len), _ptr(x), _ptr(pe), _ptr(slab), _ptr(out_eval),
+              _ptr(out_train), _ptr(saved_train), _ptr(ws), _ptr(rng), C.c_uint64(add_train), _stream())
 
 
 def encoder_bwd_raw(cfg, lo, hi, dx, slab, gslab, saved, ws, rng, add, need_dx_in=True, key_len=None):
@@ -208,12 +214,18 @@ def encoder_bwd_parts_supported(cfg):
     return int(_lib.load().ganffn_encoder_bwd_parts_supported(C.byref(cfg))) == 1
 
 
-def encoder_bwd_parts_raw(cfg, dx, slab, gslab, saved, ws, rng, add, need_dx_in=True):
+def encoder_bwd_parts_raw(cfg, dx, slab, gslab, saved, ws, rng, add, need_dx_in=True, key_len=None):
     """whole-stack backward with unreduced weight gradients -> (parts tensor view into ws or None, part_stride, n_parts, offset
-    of the parts in ws): hand them to adam_step_parts_raw before anything else touches ws[offset:]"""
+    of the parts in ws): hand them to adam_step_parts_raw before anything else touches ws[offset:].  key_len: the lengths the
+    forward was given (ganffn_encoder_bwd_parts_len)."""
     off, stride, n = C.c_int64(0), C.c_int64(0), C.c_int(0)
-    _lib.call("ganffn_encoder_bwd_parts", C.byref(cfg), _ptr(dx), _ptr(slab), _ptr(gslab), _ptr(saved), _ptr(ws), _ptr(rng),
-              C.c_uint64(add), 1 if need_dx_in else 0, C.byref(off), C.byref(stride), C.byref(n), _stream())
+    if key_len is not None:
+        _check_key_len(key_len, cfg)
+        _lib.call("ganffn_encoder_bwd_parts_len", C.byref(cfg), _ptr(key_len), _ptr(dx), _ptr(slab), _ptr(gslab), _ptr(saved),
+                  _ptr(ws), _ptr(rng), C.c_uint64(add), 1 if need_dx_in else 0, C.byref(off), C.byref(stride), C.byref(n), _stream())
+    else:
+        _lib.call("ganffn_encoder_bwd_parts", C.byref(cfg), _ptr(dx), _ptr(slab), _ptr(gslab), _ptr(saved), _ptr(ws), _ptr(rng),
+                  C.c_uint64(add), 1 if need_dx_in else 0, C.byref(off), C.byref(stride), C.byref(n), _stream())
     return (ws[off.value:] if n.value > 1 else None), stride.value, n.value, off.value
 
 
@@ -252,6 +264,27 @@ def bce_fwd_raw(prob, target, n, scale, loss, accumulate):
 
 def bce_bwd_raw(prob, target, n, scale, dprob):
     _lib.call("ganffn_bce_bwd", _ptr(prob), C.c_float(target), n, C.c_float(scale), _ptr(dprob), _stream())
+
+
+def _check_bce_len(key_len, n_len):
+    if key_len is not None and (key_len.dtype != torch.int32 or not key_len.is_cuda or not key_len.is_contiguous()
+                                or key_len.numel() != n_len):
+        raise ValueError("key_len must be a contiguous int32 device tensor with n_len (%d) entries" % n_len)
+
+
+def bce_len_fwd_raw(prob, key_len, n_len, target_a, target_b, S, Bt, split, scale, loss, accumulate):
+    """BCELoss(mean) over the real utterances of prob [S x Bt]: column c has target_a if c < split else target_b and
+    clamp(key_len[c % n_len], 1, S) real rows (ganffn_bce_len_fwd); key_len None = ganffn_bce2_fwd with period Bt"""
+    _check_bce_len(key_len, n_len)
+    _lib.call("ganffn_bce_len_fwd", _ptr(prob), _ptr(key_len), n_len, C.c_float(target_a), C.c_float(target_b), S, Bt, split,
+              C.c_float(scale), _ptr(loss), 1 if accumulate else 0, _stream())
+
+
+def bce_len_bwd_raw(prob, key_len, n_len, target_a, target_b, S, Bt, split, scale, dprob):
+    """d loss / d prob of bce_len_fwd_raw; padded entries are written as exact zeros"""
+    _check_bce_len(key_len, n_len)
+    _lib.call("ganffn_bce_len_bwd", _ptr(prob), _ptr(key_len), n_len, C.c_float(target_a), C.c_float(target_b), S, Bt, split,
+              C.c_float(scale), _ptr(dprob), _stream())
 
 
 def adam_step_raw(p, g, m, v, step, n, lr, b1, b2, eps=1e-8, wd=0.0, gscale=1.0):

@@ -523,9 +523,35 @@ int ganffn_attention_bwd_keep(const float* qkv, const float* o, const float* lse
  * every layer — the only place of a layer where rows of a dialogue meet; everything else in a stack is row-wise.  Saved and
  * workspace sizes and layouts are those of ganffn_encoder_saved_floats / _workspace_floats, unchanged; the same launches.
  * The forward and the backward of one pass must be given the same lengths.
- * NOT covered: the two-segment forward (ganffn_encoder_fwd_pair), ganffn_encoder_bwd_parts and the BCE calls take no lengths, so
- * the GAN step (GanEngine) attends over padding as the reference does; the classifier step runners and the module path use
- * these entry points when asked to (mask_padding). */
+ * The GAN step has its forms too (GanEngine(mask_padding = True); the classifier step runners and the module path use the
+ * entry points above when asked to):
+ * ganffn_encoder_fwd_pair_len: ganffn_encoder_fwd_pair with the lengths handed to the attention of every layer in BOTH
+ * segments (both are the same B dialogues, so one key_len[B] serves them).  The eval output has the bits of
+ * ganffn_encoder_fwd_len(..., saved = NULL), the train output and the saved block those of ganffn_encoder_fwd_len with the same
+ * rng_offset_add; key_len == NULL is ganffn_encoder_fwd_pair.  _pair_supported and _pair_workspace_floats are unchanged.
+ * ganffn_encoder_bwd_parts_len: ganffn_encoder_bwd_parts with the lengths handed on; followed by ganffn_adam_step_parts the
+ * update has the bits of ganffn_encoder_bwd_len + ganffn_adam_step.
+ * ganffn_bce_len_fwd / _bwd: BCELoss over the real utterances only.  prob is [S x Bt] (row t = s * Bt + c); column c has target
+ * target_a if c < split, else target_b, and n_c = clamp(key_len[c % n_len], 1, S) real rows (the attention clamp; a length of 0
+ * or above S is clamped, not refused).  count = sum_c n_c, an integer summed on the device.
+ *   forward   loss = scale * sum over s < n_c of l(s, c) / count, logs clamped at -100 as in ganffn_bce_fwd; one workgroup and a
+ *             fixed-order tree, so the value is bit-reproducible.
+ *   backward  dprob = scale / count * (p - y) / max(p (1 - p), 1e-12) where s < n_c; every other entry is written as +0.0f.
+ * key_len == NULL, or every length >= S, gives the bits of ganffn_bce2_fwd / _bwd with period = Bt, n = S * Bt.  Refused:
+ * Bt > 512, split outside [0, Bt], n_len outside [1, Bt].  Bt = 2B, split = B, n_len = B is the discriminator loss over
+ * [real | fake] (both halves have the same lengths, so the one masked mean is (BCE(real, 1) + BCE(fake, 0)) / 2 over real
+ * utterances); split = Bt is the generator loss. */
+int ganffn_encoder_fwd_pair_len(const ganffn_enc_cfg* cfg, const int32_t* key_len, const float* x_in, const float* pe,
+                                const float* params, float* out_eval, float* out_train, float* saved_train, float* workspace,
+                                const uint64_t* rng, uint64_t rng_offset_add_train, void* stream);
+int ganffn_encoder_bwd_parts_len(const ganffn_enc_cfg* cfg, const int32_t* key_len, float* dx, const float* params,
+                                 float* grads, const float* saved, float* workspace, const uint64_t* rng,
+                                 uint64_t rng_offset_add, int need_dx_in, int64_t* part_offset, int64_t* part_stride,
+                                 int* n_parts, void* stream);
+int ganffn_bce_len_fwd(const float* prob, const int32_t* key_len, int n_len, float target_a, float target_b, int S, int Bt,
+                       int split, float scale, float* loss_out, int accumulate, void* stream);
+int ganffn_bce_len_bwd(const float* prob, const int32_t* key_len, int n_len, float target_a, float target_b, int S, int Bt,
+                       int split, float scale, float* dprob, void* stream);
 int ganffn_attention_fwd_len(const float* qkv, float* o, float* lse, uint32_t* keep, const int32_t* key_len, int S, int B,
                              int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t rng_offset_add,
                              void* stream);
