@@ -219,7 +219,7 @@ def _device_epoch(engine, loader, train):
 
 def run_training(dataset_path, g_epochs=150, n_epochs=160, lr=1e-4, l2=0.008, batch_size=32, out_dir="./output/",
                  model_save_path="./GAN_save/", device="cuda", seed=None, log=print, device_corpus=False, mask_padding=False,
-                 mask_padding_gan=False):
+                 mask_padding_gan=False, causal=False):
     """The reference's __main__ flow on the HIP path: GAN phase (lr 1e-4, betas (0.5, 0.6), batch 32 whatever
     `batch_size` says — train_IEMOCAP.py:595-607) -> GAN_loss.csv + six checkpoints -> GAN_FFN phase for `n_epochs`
     -> test_out_*.txt from the epoch with the best test loss.  Returns (report file, final F1, loss table).
@@ -228,7 +228,11 @@ def run_training(dataset_path, g_epochs=150, n_epochs=160, lr=1e-4, l2=0.008, ba
     mask_padding (an extension the reference does not have): the classifier phase's generators ignore padded utterances in their
     self-attention, in the module and in the engine alike (GAN_FFN / Phase2Engine `mask_padding`); it says nothing about the GAN phase.
     mask_padding_gan (an extension too, independent of mask_padding): the GAN phase's six networks attend over real utterances
-    only and their losses are means over real utterances (GanEngine `mask_padding`, from every batch's umask)."""
+    only and their losses are means over real utterances (GanEngine `mask_padding`, from every batch's umask).
+    causal (an extension, independent of both): in the classifier phase the generators' self-attention never looks ahead, in the
+    module and in the engine alike (GAN_FFN / Phase2Engine `causal`), so the trained classifier labels utterance t from utterances
+    0 .. t.  It applies to the classifier phase only: the GAN phase still trains bidirectional generators, which phase 2 then
+    fine-tunes under the causal mask.  A causal GanEngine is the follow-up."""
     from . import data as D, engine as E, model as M
     gens, discs = E.build_networks(100, 0.2, device, seed)
     if device_corpus:
@@ -246,8 +250,9 @@ def run_training(dataset_path, g_epochs=150, n_epochs=160, lr=1e-4, l2=0.008, ba
     save_GAN_models({"gens": gens, "discs": discs}, model_save_path)
     for m in list(gens.values()) + list(discs.values()):
         m.eval()
-    net = M.GAN_FFN(gens["acoustic"], gens["visual"], gens["text"], n_classes=6, mask_padding=mask_padding).to(device)
-    eng = E.Phase2Engine(net, lr=lr, weight_decay=l2, mask_padding=mask_padding)
+    net = M.GAN_FFN(gens["acoustic"], gens["visual"], gens["text"], n_classes=6, mask_padding=mask_padding,
+                    causal=causal).to(device)
+    eng = E.Phase2Engine(net, lr=lr, weight_decay=l2, mask_padding=mask_padding, causal=causal)
     eng.reserve(110, batch_size)                     # PositionalEncoding caps a dialogue at 110 utterances
     train_loader, valid_loader, test_loader = loaders(batch_size)
     best = None

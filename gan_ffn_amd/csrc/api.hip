@@ -181,10 +181,13 @@ extern "C" int64_t ganffn_encoder_workspace_floats(const ganffn_enc_cfg* c) {
 // encoder stack forward
 // ------------------------------------------------------------------------------------------
 // key_len (or null): per-dialogue key lengths of the attention core, the one place of a layer where rows of a dialogue meet
-static int encoder_fwd_impl(const ganffn_enc_cfg* c, const int32_t* key_len, const float* x_in, const float* pe, const float* params,
-                            float* out, float* saved, float* workspace, const uint64_t* rng, uint64_t add, void* stream) {
+// flags: GANFFN_ATTN_* bits for the same place (0 = none; an unknown bit is refused before anything is launched)
+static int encoder_fwd_impl(const ganffn_enc_cfg* c, const int32_t* key_len, uint32_t flags, const float* x_in, const float* pe,
+                            const float* params, float* out, float* saved, float* workspace, const uint64_t* rng, uint64_t add,
+                            void* stream) {
     const Mode md = mode();
     GF_TRY(check_cfg(c));
+    GF_CHECK_ARG((flags & ~GANFFN_ATTN_CAUSAL) == 0, "encoder_fwd: unknown flag bits 0x%x", flags & ~GANFFN_ATTN_CAUSAL);
     GF_CHECK_ARG(x_in && pe && params && out && workspace, "encoder_fwd: null pointer");
     GF_CHECK_ARG(aligned16(x_in) && aligned16(params) && aligned16(out) && aligned16(workspace) && (!saved || aligned16(saved)),
                  "encoder_fwd: buffers must be 16-byte aligned");
@@ -235,7 +238,7 @@ static int encoder_fwd_impl(const ganffn_enc_cfg* c, const int32_t* key_len, con
         // attention core
         // (keep words only when a backward will follow: saved != null)
         GF_TRY(launch_attention_fwd(sv + so.qkv, sv + so.attn_o, sv + so.lse, saved ? reinterpret_cast<uint32_t*>(sv + so.keep) : nullptr, S, B, E,
-                                    H, c->p_enc, site + 0, rng, add, train, st, nullptr, key_len));
+                                    H, c->p_enc, site + 0, rng, add, train, st, nullptr, key_len, flags));
         // out-proj, residual + dropout + LN1
         if (rc) {
             GF_TRY(launch_rc_outproj_ln_fwd(sv + so.attn_o, P + lo.out_w, P + lo.out_b, Xcur, P + lo.n1w, P + lo.n1b, sv + so.x1,
@@ -282,12 +285,17 @@ static int encoder_fwd_impl(const ganffn_enc_cfg* c, const int32_t* key_len, con
 extern "C" int ganffn_encoder_fwd(const ganffn_enc_cfg* c, const float* x_in, const float* pe, const float* params,
                                   float* out, float* saved, float* workspace, const uint64_t* rng, uint64_t add,
                                   void* stream) {
-    return encoder_fwd_impl(c, nullptr, x_in, pe, params, out, saved, workspace, rng, add, stream);
+    return encoder_fwd_impl(c, nullptr, 0, x_in, pe, params, out, saved, workspace, rng, add, stream);
 }
 extern "C" int ganffn_encoder_fwd_len(const ganffn_enc_cfg* c, const int32_t* key_len, const float* x_in, const float* pe,
                                       const float* params, float* out, float* saved, float* workspace, const uint64_t* rng,
                                       uint64_t add, void* stream) {
-    return encoder_fwd_impl(c, key_len, x_in, pe, params, out, saved, workspace, rng, add, stream);
+    return encoder_fwd_impl(c, key_len, 0, x_in, pe, params, out, saved, workspace, rng, add, stream);
+}
+extern "C" int ganffn_encoder_fwd_mask(const ganffn_enc_cfg* c, const int32_t* key_len, uint32_t flags, const float* x_in,
+                                       const float* pe, const float* params, float* out, float* saved, float* workspace,
+                                       const uint64_t* rng, uint64_t add, void* stream) {
+    return encoder_fwd_impl(c, key_len, flags, x_in, pe, params, out, saved, workspace, rng, add, stream);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -452,7 +460,7 @@ extern "C" int ganffn_encoder_bwd(const ganffn_enc_cfg* c, int layer_lo, int lay
 }
 static int encoder_bwd_impl(const ganffn_enc_cfg* c, int layer_lo, int layer_hi, float* dx, const float* params,
                             float* grads, const float* saved, float* workspace, const uint64_t* rng, uint64_t add,
-                            int need_dx_in, void* stream, TnSlabs* slabs, const int32_t* key_len = nullptr);
+                            int need_dx_in, void* stream, TnSlabs* slabs, const int32_t* key_len = nullptr, uint32_t flags = 0);
 extern "C" int ganffn_encoder_bwd2(const ganffn_enc_cfg* c, int layer_lo, int layer_hi, float* dx, const float* params,
                                    float* grads, const float* saved, float* workspace, const uint64_t* rng, uint64_t add,
                                    int need_dx_in, void* stream) {
@@ -462,6 +470,12 @@ extern "C" int ganffn_encoder_bwd_len(const ganffn_enc_cfg* c, const int32_t* ke
                                       const float* params, float* grads, const float* saved, float* workspace, const uint64_t* rng,
                                       uint64_t add, int need_dx_in, void* stream) {
     return encoder_bwd_impl(c, layer_lo, layer_hi, dx, params, grads, saved, workspace, rng, add, need_dx_in, stream, nullptr, key_len);
+}
+extern "C" int ganffn_encoder_bwd_mask(const ganffn_enc_cfg* c, const int32_t* key_len, uint32_t flags, int layer_lo, int layer_hi,
+                                       float* dx, const float* params, float* grads, const float* saved, float* workspace,
+                                       const uint64_t* rng, uint64_t add, int need_dx_in, void* stream) {
+    return encoder_bwd_impl(c, layer_lo, layer_hi, dx, params, grads, saved, workspace, rng, add, need_dx_in, stream, nullptr, key_len,
+                            flags);
 }
 // does ganffn_encoder_bwd_parts leave the weight gradients of this stack unreduced?  (d_model 100 on the rowchain / tn100 kernels,
 // at most 10 layers: one grouped weight-gradient launch for the whole pass)
@@ -495,9 +509,10 @@ extern "C" int ganffn_encoder_bwd_parts(const ganffn_enc_cfg* c, float* dx, cons
 }
 static int encoder_bwd_impl(const ganffn_enc_cfg* c, int layer_lo, int layer_hi, float* dx, const float* params,
                             float* grads, const float* saved, float* workspace, const uint64_t* rng, uint64_t add,
-                            int need_dx_in, void* stream, TnSlabs* slabs, const int32_t* key_len) {
+                            int need_dx_in, void* stream, TnSlabs* slabs, const int32_t* key_len, uint32_t flags) {
     const Mode md = mode();
     GF_TRY(check_cfg(c));
+    GF_CHECK_ARG((flags & ~GANFFN_ATTN_CAUSAL) == 0, "encoder_bwd: unknown flag bits 0x%x", flags & ~GANFFN_ATTN_CAUSAL);
     GF_CHECK_ARG(dx && params && saved && workspace, "encoder_bwd: null pointer");
     GF_CHECK_ARG(0 <= layer_lo && layer_lo < layer_hi && layer_hi <= c->L, "encoder_bwd: bad layer range [%d,%d)", layer_lo, layer_hi);
     GF_CHECK_ARG(aligned16(dx) && aligned16(params) && aligned16(saved) && aligned16(workspace) && (!grads || aligned16(grads)),
@@ -609,7 +624,7 @@ static int encoder_bwd_impl(const ganffn_enc_cfg* c, int layer_lo, int layer_hi,
         if (!rc) GF_TRY(launch_gemm_nn(dyB, E, P + lo.out_w, E, d_attn, E, T, E, E, EPI_NONE, none, st));
         // attention core backward
         GF_TRY(launch_attention_bwd(sv + so.qkv, sv + so.attn_o, sv + so.lse, d_attn, reinterpret_cast<const uint32_t*>(sv + so.keep), d_qkv, S, B, E,
-                                    H, c->p_enc, site + 0, rng, add, train, st, key_len));
+                                    H, c->p_enc, site + 0, rng, add, train, st, key_len, flags));
         // in-proj wgrad + dgrad; dX[l] = d_qkv W_in + dz1
         if (G) tn[ntn++] = TnDesc{d_qkv, 3 * E, Xl, E, G + lo.in_w, E, G + lo.in_b, 3 * E, E, T};
         if (ntn == 40 || (l == layer_lo && ntn > 0)) {
@@ -932,4 +947,15 @@ extern "C" int ganffn_attention_bwd_len(const float* qkv, const float* o, const 
                                         const int32_t* key_len, float* d_qkv, int S, int B, int E, int H, float p, uint32_t site,
                                         const uint64_t* rng, uint64_t add, void* stream) {
     return launch_attention_bwd(qkv, o, lse, d_o, keep, d_qkv, S, B, E, H, p, site, rng, add, 1, (hipStream_t)stream, key_len);
+}
+// the same pair with a flags word (GANFFN_ATTN_CAUSAL; 0 = the _len pair, an unknown bit is refused before any launch)
+extern "C" int ganffn_attention_fwd_mask(const float* qkv, float* o, float* lse, uint32_t* keep, const int32_t* key_len, uint32_t flags,
+                                         int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add,
+                                         void* stream) {
+    return launch_attention_fwd(qkv, o, lse, keep, S, B, E, H, p, site, rng, add, 1, (hipStream_t)stream, nullptr, key_len, flags);
+}
+extern "C" int ganffn_attention_bwd_mask(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keep,
+                                         const int32_t* key_len, uint32_t flags, float* d_qkv, int S, int B, int E, int H, float p,
+                                         uint32_t site, const uint64_t* rng, uint64_t add, void* stream) {
+    return launch_attention_bwd(qkv, o, lse, d_o, keep, d_qkv, S, B, E, H, p, site, rng, add, 1, (hipStream_t)stream, key_len, flags);
 }

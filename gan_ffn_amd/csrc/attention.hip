@@ -319,7 +319,9 @@ __device__ __forceinline__ bool kept(const unsigned long long (&mq)[4], int c, i
 // LEN: per-dialogue key lengths (key_len, device int32 [B]; with PAIR the two batches are the same B dialogues and b is local
 // to the batch, so key_len[b] serves both) — a template flag, so that the
 // instantiations without lengths keep the instructions they had (see attention16.hip)
-template <int HD, int NT, bool PAIR = false, bool LEN = false>
+// CAUSAL (only with LEN; a null key_len reads as S): the lane's key limit in the softmax is min(n, query + 1).  At most 4 key
+// tiles here, so the mask is all: no tile is skipped.
+template <int HD, int NT, bool PAIR = false, bool LEN = false, bool CAUSAL = false>
 __global__ __launch_bounds__(64 * NT) void attention_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ o, AttnGeom g,
                                                                 float p, uint32_t site, const uint64_t* __restrict__ rng,
                                                                 uint64_t add, int train, const float* qkv1, float* o1,
@@ -355,7 +357,8 @@ __global__ __launch_bounds__(64 * NT) void attention_fwd_kernel(const float* __r
 #pragma unroll
         for (int i = 0; i < 16; ++i) pr[c][i] = 0.f;
     scores_T<HD, NT>(pr, Ks, Qs, g.LDH, g.hd, 32 * w, r, h);
-    softmax_T<NT>(pr, n, h);
+    static_assert(!CAUSAL || LEN, "the causal instantiations are those with lengths");
+    softmax_T<NT>(pr, CAUSAL ? min(n, 32 * w + r + 1) : n, h);
 
     const DropCtx dc = make_drop(rng, add, site, p, train);
     if (dc.on) {
@@ -392,7 +395,7 @@ __global__ __launch_bounds__(64 * NT) void attention_fwd_kernel(const float* __r
 // ------------------------------------------------------------------------------------------
 // backward: d_qkv from d_o, recomputing P^T and the dropout mask
 // ------------------------------------------------------------------------------------------
-template <int HD, int NT, bool LEN = false>
+template <int HD, int NT, bool LEN = false, bool CAUSAL = false>
 __global__ __launch_bounds__(64 * NT) void attention_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ d_o,
                                                                 float* __restrict__ d_qkv, AttnGeom g, float p, uint32_t site,
                                                                 const uint64_t* __restrict__ rng, uint64_t add, int train,
@@ -436,7 +439,9 @@ __global__ __launch_bounds__(64 * NT) void attention_bwd_kernel(const float* __r
         for (int i = 0; i < 16; ++i) { pr[c][i] = 0.f; dp[c][i] = 0.f; }
 
     scores_T<HD, NT>(pr, RB, RA, g.LDH, g.hd, 32 * w, r, h);
-    softmax_T<NT>(pr, n, h);
+    static_assert(!CAUSAL || LEN, "the causal instantiations are those with lengths");
+    // causal: the recomputed softmax gives P = 0 exactly for keys past the query as well, and dS = P (dP - D) with it
+    softmax_T<NT>(pr, CAUSAL ? min(n, 32 * w + r + 1) : n, h);
     const DropCtx dc = make_drop(rng, add, site, p, train);
     unsigned long long mq[4];
     keep_masks<NT>(mq, dc, bh, w, lane);
@@ -576,8 +581,12 @@ static int check_attn(int S, int B, int E, int H) {
 
 template <int HD, int NT>
 static int launch_fwd_t(const float* qkv, float* o, const AttnGeom& g, size_t lds, float p, uint32_t site, const uint64_t* rng,
-                        uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1, const int32_t* key_len) {
-    if (seg1 && key_len) {
+                        uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1, const int32_t* key_len, bool causal) {
+    if (causal) {      // never with seg1 (refused by the caller); a null key_len reads as S in the kernel
+        GF_TRY((lds_optin<attention_fwd_kernel<HD, NT, false, true, true>>(lds, "attention_fwd")));
+        hipLaunchKernelGGL((attention_fwd_kernel<HD, NT, false, true, true>), dim3(g.B * g.H), dim3(64 * NT), lds, st, qkv, o, g, p, site,
+                           rng, add, train, (const float*)nullptr, (float*)nullptr, 0, key_len);
+    } else if (seg1 && key_len) {
         GF_TRY((lds_optin<attention_fwd_kernel<HD, NT, true, true>>(lds, "attention_fwd")));
         hipLaunchKernelGGL((attention_fwd_kernel<HD, NT, true, true>), dim3(2 * g.B * g.H), dim3(64 * NT), lds, st, qkv, o, g, p, site,
                            rng, add, train, seg1->qkv, seg1->o, seg1->train, key_len);
@@ -599,8 +608,12 @@ static int launch_fwd_t(const float* qkv, float* o, const AttnGeom& g, size_t ld
 }
 template <int HD, int NT>
 static int launch_bwd_t(const float* qkv, const float* d_o, float* d_qkv, const AttnGeom& g, size_t lds, float p, uint32_t site,
-                        const uint64_t* rng, uint64_t add, int train, hipStream_t st, const int32_t* key_len) {
-    if (key_len) {
+                        const uint64_t* rng, uint64_t add, int train, hipStream_t st, const int32_t* key_len, bool causal) {
+    if (causal) {
+        GF_TRY((lds_optin<attention_bwd_kernel<HD, NT, true, true>>(lds, "attention_bwd")));
+        hipLaunchKernelGGL((attention_bwd_kernel<HD, NT, true, true>), dim3(g.B * g.H), dim3(64 * NT), lds, st, qkv, d_o, d_qkv, g, p,
+                           site, rng, add, train, key_len);
+    } else if (key_len) {
         GF_TRY((lds_optin<attention_bwd_kernel<HD, NT, true>>(lds, "attention_bwd")));
         hipLaunchKernelGGL((attention_bwd_kernel<HD, NT, true>), dim3(g.B * g.H), dim3(64 * NT), lds, st, qkv, d_o, d_qkv, g, p, site,
                            rng, add, train, key_len);
@@ -623,35 +636,40 @@ static int launch_bwd_t(const float* qkv, const float* d_o, float* d_qkv, const 
 
 int launch_attention_fwd(const float* qkv, float* o, float* lse, uint32_t* keep, int S, int B, int E, int H, float p, uint32_t site,
                          const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1,
-                         const int32_t* key_len) {
+                         const int32_t* key_len, uint32_t flags) {
     GF_TRY(check_attn(S, B, E, H));
+    GF_CHECK_ARG((flags & ~GANFFN_ATTN_CAUSAL) == 0, "attention_fwd: unknown flag bits 0x%x", flags & ~GANFFN_ATTN_CAUSAL);
+    const bool causal = (flags & GANFFN_ATTN_CAUSAL) != 0;
+    GF_CHECK_ARG(!(seg1 && causal), "attention_fwd: the two-batch launch has no causal form");
     GF_CHECK_ARG(qkv && o, "attention_fwd: null pointer");
     GF_CHECK_ARG(!seg1 || (seg1->qkv && seg1->o), "attention_fwd: bad second batch");
     GF_CHECK_ARG(!((train || (seg1 && seg1->train)) && p > 0.f) || rng, "attention_fwd: rng required when dropout is active");
-    if (attn16_supported(E, H, S)) return launch_attn16_fwd(qkv, o, lse, keep, S, B, E, H, p, site, rng, add, train, st, seg1, key_len);
+    if (attn16_supported(E, H, S)) return launch_attn16_fwd(qkv, o, lse, keep, S, B, E, H, p, site, rng, add, train, st, seg1, key_len, flags);
     const AttnGeom g = make_geom(S, B, E, H);
     const size_t lds = 3 * hd_mat_floats(g) * sizeof(float);
     GF_CHECK_ARG(lds <= 160 * 1024, "attention_fwd: LDS need %zu > 160 KiB", lds);
-    if (g.hd == 64) { NT_SWITCH(launch_fwd_t, 64, qkv, o, g, lds, p, site, rng, add, train, st, seg1, key_len) }
-    if (g.hd == 60) { NT_SWITCH(launch_fwd_t, 60, qkv, o, g, lds, p, site, rng, add, train, st, seg1, key_len) }
-    NT_SWITCH(launch_fwd_t, 0, qkv, o, g, lds, p, site, rng, add, train, st, seg1, key_len)
+    if (g.hd == 64) { NT_SWITCH(launch_fwd_t, 64, qkv, o, g, lds, p, site, rng, add, train, st, seg1, key_len, causal) }
+    if (g.hd == 60) { NT_SWITCH(launch_fwd_t, 60, qkv, o, g, lds, p, site, rng, add, train, st, seg1, key_len, causal) }
+    NT_SWITCH(launch_fwd_t, 0, qkv, o, g, lds, p, site, rng, add, train, st, seg1, key_len, causal)
 }
 
 int launch_attention_bwd(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keep, float* d_qkv,
                          int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train,
-                         hipStream_t st, const int32_t* key_len) {
+                         hipStream_t st, const int32_t* key_len, uint32_t flags) {
     GF_TRY(check_attn(S, B, E, H));
+    GF_CHECK_ARG((flags & ~GANFFN_ATTN_CAUSAL) == 0, "attention_bwd: unknown flag bits 0x%x", flags & ~GANFFN_ATTN_CAUSAL);
+    const bool causal = (flags & GANFFN_ATTN_CAUSAL) != 0;
     GF_CHECK_ARG(qkv && d_o && d_qkv, "attention_bwd: null pointer");
     GF_CHECK_ARG(!(train && p > 0.f) || rng, "attention_bwd: rng required when dropout is active");
-    if (attn16_supported(E, H, S)) return launch_attn16_bwd(qkv, o, lse, d_o, keep, d_qkv, S, B, E, H, p, site, rng, add, train, st, key_len);
+    if (attn16_supported(E, H, S)) return launch_attn16_bwd(qkv, o, lse, d_o, keep, d_qkv, S, B, E, H, p, site, rng, add, train, st, key_len, flags);
     const AttnGeom g = make_geom(S, B, E, H);
     const int hdt = (g.hd == 60 || g.hd == 64) ? g.hd : 0;      // kernel template head_dim (0 = generic)
     const bool alias = hdt == 0 || hdt * g.NT > 192;            // == attention_bwd_kernel::ALIAS
     const size_t lds = ((alias ? 3 : 4) * hd_mat_floats(g) + ss_mat_floats(g)) * sizeof(float);
     GF_CHECK_ARG(lds <= 160 * 1024, "attention_bwd: LDS need %zu > 160 KiB", lds);
-    if (g.hd == 64) { NT_SWITCH(launch_bwd_t, 64, qkv, d_o, d_qkv, g, lds, p, site, rng, add, train, st, key_len) }
-    if (g.hd == 60) { NT_SWITCH(launch_bwd_t, 60, qkv, d_o, d_qkv, g, lds, p, site, rng, add, train, st, key_len) }
-    NT_SWITCH(launch_bwd_t, 0, qkv, d_o, d_qkv, g, lds, p, site, rng, add, train, st, key_len)
+    if (g.hd == 64) { NT_SWITCH(launch_bwd_t, 64, qkv, d_o, d_qkv, g, lds, p, site, rng, add, train, st, key_len, causal) }
+    if (g.hd == 60) { NT_SWITCH(launch_bwd_t, 60, qkv, d_o, d_qkv, g, lds, p, site, rng, add, train, st, key_len, causal) }
+    NT_SWITCH(launch_bwd_t, 0, qkv, d_o, d_qkv, g, lds, p, site, rng, add, train, st, key_len, causal)
 }
 
 }  // namespace ganffn

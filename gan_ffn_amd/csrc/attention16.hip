@@ -26,6 +26,7 @@
 //     no reduction across waves, no atomics);  only dS crosses LDS once, for dQ = dS K.
 // Layout: qkv [T x 3E] packed q|k|v per token (t = s*B + b), head h = columns h*hd .. h*hd+hd-1; lse [B*H x S].
 #include "common.h"
+#include <type_traits>
 
 namespace ganffn {
 
@@ -157,6 +158,30 @@ __device__ __forceinline__ void apply_tiles(floatx4 (&out)[A16<HD>::NTD], const 
     for (int dt = 0; dt < NTD; ++dt) out[dt] += alt[dt];
 }
 
+// Causal forms: a wave needs only the tiles on its side of the diagonal.  The number of live tiles is wave-uniform (w is taken
+// through readfirstlane: an SGPR), and tile_dispatch turns it into a COMPILE-TIME count once: a chain of scalar compares calls
+// f(integral_constant<I>) for I == w, and the body behind each arm is straight-line code over exactly its live tiles, with the
+// batched operand loads of dot_tiles / apply_tiles.  (The first version guarded every tile of every loop with `if (t <= w)`:
+// correct, but hipcc copied the accumulator tiles at each of the ~40 merges — 327 v_mov against 32 and 147 VGPRs against 65 in
+// the 7-tile forward.)
+// -DGANFFN_CAUSAL_MASK_ONLY builds the causal kernels with the mask alone (every tile computed): the other side of the measurement
+// in profiles/attention_causal_ab.txt, not a product configuration.
+#ifdef GANFFN_CAUSAL_MASK_ONLY
+constexpr bool CAUSAL_SKIP = false;
+#else
+constexpr bool CAUSAL_SKIP = true;
+#endif
+
+template <int NT, int I = 0, class F>
+__device__ __forceinline__ void tile_dispatch(int w, F&& f) {
+    if constexpr (I + 1 >= NT) {
+        f(std::integral_constant<int, I>{});
+    } else {
+        if (w == I) f(std::integral_constant<int, I>{});
+        else tile_dispatch<NT, I + 1>(w, f);
+    }
+}
+
 // value of lane r of this lane's quad (DPP quad_perm broadcast)
 template <int R>
 __device__ __forceinline__ uint32_t quad_bcast(uint32_t v) {
@@ -188,7 +213,10 @@ struct Attn16Seg1 {
 // local to the batch, so key_len[b] serves both).  A template flag and not a test of the
 // pointer: the instantiations without lengths (every launch of the GAN step) keep the instructions they had — no scalar load, no
 // uniform branch (the listings compared: profiles/attention_key_len_ab.txt).
-template <int HD, int NT, int WPB, bool PAIR = false, bool LEN = false>
+// CAUSAL (only with LEN; a null key_len reads as S): query i attends to keys j <= i, i.e. the lane's key limit is
+// min(n, query + 1).  Wave w owns query tile w, so key tiles t > w are dead: the wave runs the tail of the kernel compiled for
+// w + 1 key tiles (tile_dispatch) — no score MFMAs, exp / sum work or P V products for the rest, and no Philox calls.
+template <int HD, int NT, int WPB, bool PAIR = false, bool LEN = false, bool CAUSAL = false>
 __global__ __launch_bounds__(64 * WPB) void attn16_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ o,
                                                              float* __restrict__ lse, uint32_t* __restrict__ keepw, int S, int B,
                                                              int E, int H, float p, uint32_t site,
@@ -207,7 +235,10 @@ __global__ __launch_bounds__(64 * WPB) void attn16_fwd_kernel(const float* __res
     static_assert(NT % WPB == 0, "query tiles per workgroup must divide the tile count");
     constexpr int NQB = NT / WPB;
     const int tid = threadIdx.x, lane = tid & 63, c = lane & 15, g = lane >> 4;
-    const int bh = bid / NQB, w = (bid - bh * NQB) * WPB + (tid >> 6);     // w: query tile of this wave
+    static_assert(!CAUSAL || LEN, "the causal instantiations are those with lengths");
+    const int bh = bid / NQB;
+    const int w0 = (bid - bh * NQB) * WPB + (tid >> 6);
+    const int w = CAUSAL ? __builtin_amdgcn_readfirstlane(w0) : w0;      // w: query tile of this wave
     const int b = bh / H, head = bh - b * H;
     const int n = LEN ? attn_key_len(key_len, b, S) : S;      // keys < n take part (workgroup-uniform)
     float* Qs = smem;
@@ -229,6 +260,7 @@ __global__ __launch_bounds__(64 * WPB) void attn16_fwd_kernel(const float* __res
             const uint32_t rowgroup = (uint32_t)(bh * 28 + 4 * w + (c >> 2));
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
+                if (CAUSAL && CAUSAL_SKIP && t > w) continue;      // dead key tile: its keep bits are never read
                 uint32_t wd[4];
                 philox4(rowgroup * 128u + (uint32_t)(16 * t + 4 * g + ql), dc.site, dc.o0, dc.o1, dc.k0, dc.k1, wd);
 #pragma unroll
@@ -243,6 +275,74 @@ __global__ __launch_bounds__(64 * WPB) void attn16_fwd_kernel(const float* __res
     }
     __syncthreads();
 
+    // CAUSAL: the rest of the kernel over the first NL = w + 1 key tiles, then return.  (One algorithm written twice: the code below
+    // is that of the kernels without the flag, left where and as it was so that they keep their instructions — sharing one body
+    // with the causal form, or only moving it into a block of its own, changed their listings.)
+    if constexpr (CAUSAL) {
+        auto tail = [&](auto nl_) {
+            constexpr int NL = decltype(nl_)::value + 1;
+            // S^T tiles: pr[t][reg] = score(key 16t + 4g + reg, query 16w + c)
+            floatx4 pr[NL];
+#pragma unroll
+            for (int t = 0; t < NL; ++t) pr[t] = floatx4{0.f, 0.f, 0.f, 0.f};
+            dot_tiles<HD, NL>(pr, Ks, Qs + (16 * w + c) * LD + g, c, g);
+
+            const int lim = min(n, 16 * w + c + 1);     // this lane's query sees keys < lim (>= 1, ghost queries too)
+            float m = -INFINITY;
+#pragma unroll
+            for (int t = 0; t < NL; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    if (16 * t + 4 * g + r >= lim) pr[t][r] = -INFINITY;
+                    m = fmaxf(m, pr[t][r]);
+                }
+            m = fmaxf(m, __shfl_xor(m, 16, 64));
+            m = fmaxf(m, __shfl_xor(m, 32, 64));
+            float sum = 0.f;
+#pragma unroll
+            for (int t = 0; t < NL; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float e = __expf(pr[t][r] - m);     // exp(-inf) = 0 for padded keys
+                    pr[t][r] = e;
+                    sum += e;
+                }
+            sum += __shfl_xor(sum, 16, 64);
+            sum += __shfl_xor(sum, 32, 64);
+            const float inv = 1.0f / sum;
+            const int qi = 16 * w + c;
+            if (lse != nullptr && g == 0 && qi < S) lse[(size_t)bh * S + qi] = m + __logf(sum);
+
+            if (dc.on) {
+                const int ql = c & 3;
+                const uint32_t mq[4] = {quad_bcast<0>(mine), quad_bcast<1>(mine), quad_bcast<2>(mine), quad_bcast<3>(mine)};
+                const float ps = inv * dc.scale;
+#pragma unroll
+                for (int t = 0; t < NL; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) pr[t][r] = ((mq[r] >> (4 * t + ql)) & 1u) ? pr[t][r] * ps : 0.f;
+            } else {
+#pragma unroll
+                for (int t = 0; t < NL; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) pr[t][r] *= inv;
+            }
+
+            // O^T[d][query] = sum_key V[key][d] P~^T[key][query]
+            floatx4 oacc[NTD];
+#pragma unroll
+            for (int dt = 0; dt < NTD; ++dt) oacc[dt] = floatx4{0.f, 0.f, 0.f, 0.f};
+            apply_tiles<HD, NL>(oacc, pr, Vs, c, g);
+            if (qi < S) {
+                float* orow = o + (size_t)(qi * B + b) * E + head * HD;
+#pragma unroll
+                for (int dt = 0; dt < NTD; ++dt) store4<HD>(orow, 16 * dt + 4 * g, oacc[dt], 1.f);
+            }
+        };
+        if constexpr (CAUSAL_SKIP) tile_dispatch<NT>(w, tail);      // key tiles 0 .. w
+        else tail(std::integral_constant<int, NT - 1>{});
+        return;
+    }
     // S^T tiles: pr[t][reg] = score(key 16t + 4g + reg, query 16w + c)
     floatx4 pr[NT];
 #pragma unroll
@@ -306,7 +406,12 @@ __global__ __launch_bounds__(64 * WPB) void attn16_fwd_kernel(const float* __res
 // ------------------------------------------------------------------------------------------
 // SAVED: the dropout keep bits come from the words the forward stored (keepw) instead of Philox calls — the same bits, so
 // both forms give identical results (tests/test_hip_ops.py::test_attention_fwd_bwd compares them with torch.equal)
-template <int HD, int NT, bool SAVED, bool LEN = false>
+// CAUSAL (only with LEN): P = 0 for keys past the query, set explicitly (exp(s - lse) is not 0 there).  Wave w owns keys
+// 16w .. 16w+15 and needs query tiles t >= w only: it runs the products compiled for NT - w query tiles (tile_dispatch) — no score /
+// dP MFMAs, Philox calls (or keep-word unpacking), exp work or dV / dK products for tiles t < w — and their dS is neither
+// written to LDS nor read: the dQ product of query tile w reads key tiles t <= w, which are exactly the ones key-wave t wrote
+// for query tile w >= t.  Every wave reaches both barriers: they stand outside the dispatched parts.
+template <int HD, int NT, bool SAVED, bool LEN = false, bool CAUSAL = false>
 __global__ __launch_bounds__(64 * NT) void attn16_bwd_kernel(const float* __restrict__ qkv, const float* __restrict__ o,
                                                              const float* __restrict__ lse, const float* __restrict__ d_o,
                                                              const uint32_t* __restrict__ keepw, float* __restrict__ d_qkv,
@@ -316,7 +421,9 @@ __global__ __launch_bounds__(64 * NT) void attn16_bwd_kernel(const float* __rest
     constexpr int LD = A16<HD>::LD, NTD = A16<HD>::NTD, KS = A16<HD>::KS, ROWS = 16 * NT, MAT = ROWS * LD + A16<HD>::TAIL;
     constexpr int LDS_S = ROWS + 4;                      // dS image [query][key]: rows 4 apart sit 16 banks apart
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 15, g = lane >> 4;
+    static_assert(!CAUSAL || LEN, "the causal instantiations are those with lengths");
+    const int tid = threadIdx.x, lane = tid & 63, w0 = tid >> 6, c = lane & 15, g = lane >> 4;
+    const int w = CAUSAL ? __builtin_amdgcn_readfirstlane(w0) : w0;      // causal: an SGPR, so the tile skips are scalar branches
     const int bh = blockIdx.x, b = bh / H, head = bh - b * H;
     const int n = LEN ? attn_key_len(key_len, b, S) : S;      // keys < n take part (workgroup-uniform)
     // K, LSE and D live for the whole kernel; scaled q, V and dO are dead once dV / dK are accumulated, and the dS image
@@ -364,8 +471,10 @@ __global__ __launch_bounds__(64 * NT) void attn16_bwd_kernel(const float* __rest
             // the keep words of this lane's (key, 4-query group) pairs: exactly one Philox call per accumulator tile, and
             // data-independent — evaluated while the global loads are in flight
 #pragma unroll
-            for (int t = 0; t < NT; ++t)
+            for (int t = 0; t < NT; ++t) {
+                if (CAUSAL && CAUSAL_SKIP && t < w) continue;      // dead query tile
                 philox4((uint32_t)(bh * 28 + 4 * t + g) * 128u + (uint32_t)(16 * w + c), dc.site, dc.o0, dc.o1, dc.k0, dc.k1, wdt[t]);
+            }
         }
         stg.store(m4, S, n, tid);
         if (SAVED) Wk[tid] = kw1;
@@ -379,6 +488,130 @@ __global__ __launch_bounds__(64 * NT) void attn16_bwd_kernel(const float* __rest
         }
     }
     __syncthreads();
+    // CAUSAL: the rest of the kernel over the live tiles only, then return (the code below is the kernels' without the flag: see
+    // the forward)
+    if constexpr (CAUSAL) {
+        const int kj = 16 * w + c;                     // this lane's key
+        floatx4 ds[NT];                                // dS of this lane's key, query tiles F .. NT-1 (handed to LDS below)
+        // scores, P~, dS and the dV / dK products over the query tiles F .. NT-1 (F = the wave's own tile w, a compile-time value)
+        auto products = [&](auto f_) {
+            constexpr int F = decltype(f_)::value, NL = NT - F;
+            if (SAVED) {
+                // the same registers the Philox form fills: all-ones (kept) or zero (dropped: 0 < thr) — the rest of the kernel is
+                // one code path (a separate bit-test path compiled to 82 VGPRs and ran SLOWER than the Philox calls at 640 problems)
+#pragma unroll
+                for (int t = F; t < NT; ++t) {
+                    const uint32_t nib = Wk[64 * t + lane] >> (4 * w);
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) wdt[t][r] = ((nib >> r) & 1u) ? 0xFFFFFFFFu : 0u;
+                }
+            }
+
+            floatx4 ps[NL], dp[NL];
+            // initial accumulators: -LSE[query] for the scores (P = exp(acc) needs no subtraction), 0 for dP
+#pragma unroll
+            for (int t = 0; t < NL; ++t) {
+                const float4 l4 = *reinterpret_cast<const float4*>(Ls + 16 * (F + t) + 4 * g);
+                ps[t] = floatx4{-l4.x, -l4.y, -l4.z, -l4.w};
+                dp[t] = floatx4{0.f, 0.f, 0.f, 0.f};
+            }
+            dot_tiles<HD, NL>(ps, Qs + F * 16 * LD, Ks + kj * LD + g, c, g);      // S[query 16t+4g+reg][key kj] - LSE
+            dot_tiles<HD, NL>(dp, Os + F * 16 * LD, Vs + kj * LD + g, c, g);      // dP~[query][key] = dO . V
+
+            // a key past the dialogue's length has P = 0 (and with it dS = 0): its dK and dV rows are written as zeros
+            const bool keyok = kj < n;
+#pragma unroll
+            for (int t = 0; t < NL; ++t) {
+                const float4 d4 = *reinterpret_cast<const float4*>(Ds + 16 * (F + t) + 4 * g);
+                const float dd[4] = {d4.x, d4.y, d4.z, d4.w};
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const bool ok = keyok && kj <= 16 * (F + t) + 4 * g + r;      // the key is not past the query
+                    const float pv = ok ? __expf(ps[t][r]) : 0.f;                // probability (pre-dropout)
+                    const bool keep = !dc.on || wdt[F + t][r] >= dc.thr;
+                    const float dpk = keep ? dp[t][r] * dc.scale : 0.f;          // dP = keep * scale * dP~
+                    ps[t][r] = keep ? pv * dc.scale : 0.f;                       // P~
+                    dp[t][r] = pv * (dpk - dd[r]);                               // dS
+                }
+            }
+
+            // dV^T[d][key] = sum_q dO[q][d] P~[q][key];  dK^T[d][key] = sum_q (scale Q)[q][d] dS[q][key]
+            floatx4 av[NTD], ak[NTD];
+#pragma unroll
+            for (int dt = 0; dt < NTD; ++dt) { av[dt] = floatx4{0.f, 0.f, 0.f, 0.f}; ak[dt] = floatx4{0.f, 0.f, 0.f, 0.f}; }
+            const float* pv_ = Os + (F * 16 + 4 * g) * LD + c;
+            const float* pk_ = Qs + (F * 16 + 4 * g) * LD + c;
+            float a1[2][4][NTD], a2[2][4][NTD];
+            auto fetch = [&](int t, float (&d1)[4][NTD], float (&d2)[4][NTD]) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int dt = 0; dt < NTD; ++dt) {
+                        d1[r][dt] = pv_[(16 * t + r) * LD + 16 * dt];
+                        d2[r][dt] = pk_[(16 * t + r) * LD + 16 * dt];
+                    }
+            };
+            fetch(0, a1[0], a2[0]);
+#pragma unroll
+            for (int t = 0; t < NL; ++t) {
+                if (t + 1 < NL) fetch(t + 1, a1[(t + 1) & 1], a2[(t + 1) & 1]);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+#pragma unroll
+                    for (int dt = 0; dt < NTD; ++dt) {
+                        av[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[t & 1][r][dt], ps[t][r], av[dt], 0, 0, 0);
+                        ak[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a2[t & 1][r][dt], dp[t][r], ak[dt], 0, 0, 0);
+                    }
+            }
+            if (kj < S) {
+                float* row = d_qkv + (size_t)(kj * B + b) * ld3 + head * HD;
+#pragma unroll
+                for (int dt = 0; dt < NTD; ++dt) {
+                    store4<HD>(row + 2 * E, 16 * dt + 4 * g, av[dt], 1.f);
+                    store4<HD>(row + E, 16 * dt + 4 * g, ak[dt], 1.f);
+                }
+            }
+#pragma unroll
+            for (int t = 0; t < NL; ++t) ds[F + t] = dp[t];
+        };
+        if constexpr (CAUSAL_SKIP) tile_dispatch<NT>(w, products);      // query tiles w .. NT-1
+        else products(std::integral_constant<int, 0>{});
+        // dS -> LDS [query][key], over the operands every wave has finished reading
+        __syncthreads();
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            if (CAUSAL_SKIP && t < w) continue;      // never computed, never read: query tile t takes key tiles <= t only
+#pragma unroll
+            for (int r = 0; r < 4; ++r) SS[(16 * t + 4 * g + r) * LDS_S + kj] = ds[t][r];
+        }
+        __syncthreads();
+
+        // dQ^T[d][query 16w + c] = scale * sum_key K[key][d] dS[query][key], over the key tiles 0 .. w
+        auto dq = [&](auto nl_) {
+            constexpr int NL = decltype(nl_)::value + 1;
+            floatx4 pq[NL];
+            const float* ss = SS + (16 * w + c) * LDS_S + 4 * g;
+#pragma unroll
+            for (int t = 0; t < NL; ++t) {
+                const float4 q4 = *reinterpret_cast<const float4*>(ss + 16 * t);
+                pq[t] = floatx4{q4.x, q4.y, q4.z, q4.w};
+            }
+            floatx4 aq[NTD];
+#pragma unroll
+            for (int dt = 0; dt < NTD; ++dt) aq[dt] = floatx4{0.f, 0.f, 0.f, 0.f};
+            apply_tiles<HD, NL>(aq, pq, Ks, c, g);
+            const int qi = 16 * w + c;
+            if (qi < S) {
+                float* row = d_qkv + (size_t)(qi * B + b) * ld3 + head * HD;
+#pragma unroll
+                for (int dt = 0; dt < NTD; ++dt) store4<HD>(row, 16 * dt + 4 * g, aq[dt], scale);
+            }
+        };
+        if constexpr (CAUSAL_SKIP) tile_dispatch<NT>(w, dq);
+        else dq(std::integral_constant<int, NT - 1>{});
+        return;
+    }
     if (SAVED) {
         // the same registers the Philox form fills: all-ones (kept) or zero (dropped: 0 < thr) — the rest of the kernel is
         // one code path (a separate bit-test path compiled to 82 VGPRs and ran SLOWER than the Philox calls at 640 problems)
@@ -493,12 +726,24 @@ __global__ __launch_bounds__(64 * NT) void attn16_bwd_kernel(const float* __rest
 // head_dim 10 / 30: always.  head_dim 60 / 64: short sequences only — measured against attention.hip (tools/lab/attn_big.py,
 // B = 32): S = 33, hd 60: forward 17.1 -> 9.6 us, backward 30.4 -> 19.4 us; S = 94, hd 64: forward 17.2 -> 36.9 us
 // (16 k-steps per score tile on 16-wide tiles), backward 34.1 -> 32.2 us.
+#ifndef GANFFN_A16_CAUSAL_TU
 bool attn16_supported(int E, int H, int S) {
     const int hd = H > 0 ? E / H : 0;
     if (!(H > 0 && E % H == 0)) return false;
     if (hd == 10 || hd == 30) return true;
     return (hd == 60 || hd == 64) && S <= 48;
 }
+#endif
+// The CAUSAL instantiations live in a translation unit of their own: attention16_causal.hip is this file compiled with
+// GANFFN_A16_CAUSAL_TU, which keeps the causal launches (as launch_attn16_fwd_causal / _bwd_causal) and nothing else, and this
+// file without it keeps everything else.  Measured, not a matter of taste: with both in one module 52 of the 176 kernels without
+// the flag (the head_dim 10 backward among them) came out of hipcc with another schedule and register assignment than the
+// parent's, although their source had not changed; apart, all 176 are the parent's instruction for instruction.
+#ifdef GANFFN_A16_CAUSAL_TU
+#define A16_ENTRY(name) name##_causal
+#else
+#define A16_ENTRY(name) name
+#endif
 
 // Hand the dropout keep bits from the forward to the backward (instead of re-evaluating the Philox calls there) only while
 // the launch leaves most CUs with ONE backward workgroup: measured (tools/lab/attn_ab.py, S = 94, head_dim 10, p = 0.1)
@@ -520,6 +765,7 @@ static int launch16_fwd(const float* qkv, float* o, float* lse, uint32_t* keepw,
                         const int32_t* key_len) {
     const size_t lds = fwd_lds<HD>(NT);
     if (!attn16_use_keep(B, H)) keepw = nullptr;
+#ifndef GANFFN_A16_CAUSAL_TU
     if (seg1) {
         // the workgroup cut and the keep-word rule are those of ONE batch of B dialogues: what a single launch would choose
         Attn16Seg1 s1{seg1->qkv, seg1->o, seg1->lse, attn16_use_keep(B, H) ? seg1->keep : nullptr, seg1->train};
@@ -541,16 +787,22 @@ static int launch16_fwd(const float* qkv, float* o, float* lse, uint32_t* keepw,
         GF_LAUNCH_CHECK();
         return 0;
     }
+#endif
     // query tiles per workgroup: measured at hd = 10, S = 94 (tools/lab/attn_wpb.py, lab build): 320 problems 11.1 us as
     // whole workgroups, 10.1 / 9.9 / 11.5 us cut in 2 / 3 / 6; 640 problems 15.0 us whole, 16.4 / 17.9 / 21.5 us cut —
     // the cut pays while the problems do not fill the chip, then the repeated K / V staging costs more than the balance gains
-#define GF_A16_FWD(W, LEN)                                                                                          \
+#define GF_A16_FWD(W, LEN, ...)                                                                                     \
     {                                                                                                               \
-        GF_TRY((lds_optin<attn16_fwd_kernel<HD, NT, W, false, LEN>>(lds, "attention_fwd")));                        \
-        hipLaunchKernelGGL((attn16_fwd_kernel<HD, NT, W, false, LEN>), dim3(B * H * (NT / W)), dim3(64 * W), lds, st, qkv, o, lse, keepw, S, \
+        GF_TRY((lds_optin<attn16_fwd_kernel<HD, NT, W, false, LEN, ##__VA_ARGS__>>(lds, "attention_fwd")));         \
+        hipLaunchKernelGGL((attn16_fwd_kernel<HD, NT, W, false, LEN, ##__VA_ARGS__>), dim3(B * H * (NT / W)), dim3(64 * W), lds, st, qkv, o, lse, keepw, S, \
                            B, E, H, p, site, rng, add, train, Attn16Seg1{}, 0, key_len);                                \
     }
     const bool cut = (long)B * H < 512 && NT % 2 == 0 && NT > 2;
+#ifdef GANFFN_A16_CAUSAL_TU
+    // the causal instantiations are LEN ones; a null key_len reads as S in the kernel
+    if (cut) GF_A16_FWD((NT % 2 == 0 ? 2 : NT), true, true)
+    else GF_A16_FWD(NT, true, true)
+#else
     if (key_len) {
         if (cut) GF_A16_FWD((NT % 2 == 0 ? 2 : NT), true)
         else GF_A16_FWD(NT, true)
@@ -558,6 +810,7 @@ static int launch16_fwd(const float* qkv, float* o, float* lse, uint32_t* keepw,
         if (cut) GF_A16_FWD((NT % 2 == 0 ? 2 : NT), false)
         else GF_A16_FWD(NT, false)
     }
+#endif
 #undef GF_A16_FWD
     GF_LAUNCH_CHECK();
     return 0;
@@ -567,13 +820,17 @@ static int launch16_bwd(const float* qkv, const float* o, const float* lse, cons
                         int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train,
                         hipStream_t st, const int32_t* key_len) {
     const size_t lds = bwd_lds<HD>(NT);
-#define GF_A16_BWD(SAVED, LEN)                                                                                      \
+#define GF_A16_BWD(SAVED, LEN, ...)                                                                                 \
     {                                                                                                               \
-        GF_TRY((lds_optin<attn16_bwd_kernel<HD, NT, SAVED, LEN>>(lds, "attention_bwd")));                           \
-        hipLaunchKernelGGL((attn16_bwd_kernel<HD, NT, SAVED, LEN>), dim3(B * H), dim3(64 * NT), lds, st, qkv, o, lse, d_o, keepw, d_qkv, \
+        GF_TRY((lds_optin<attn16_bwd_kernel<HD, NT, SAVED, LEN, ##__VA_ARGS__>>(lds, "attention_bwd")));            \
+        hipLaunchKernelGGL((attn16_bwd_kernel<HD, NT, SAVED, LEN, ##__VA_ARGS__>), dim3(B * H), dim3(64 * NT), lds, st, qkv, o, lse, d_o, keepw, d_qkv, \
                            S, B, E, H, p, site, rng, add, train, key_len);                                              \
     }
     const bool saved = keepw != nullptr && train && p > 0.f && attn16_use_keep(B, H);      // the forward of this pass stored its keep words
+#ifdef GANFFN_A16_CAUSAL_TU
+    if (saved) GF_A16_BWD(true, true, true)
+    else GF_A16_BWD(false, true, true)
+#else
     if (key_len) {
         if (saved) GF_A16_BWD(true, true)
         else GF_A16_BWD(false, true)
@@ -581,6 +838,7 @@ static int launch16_bwd(const float* qkv, const float* o, const float* lse, cons
         if (saved) GF_A16_BWD(true, false)
         else GF_A16_BWD(false, false)
     }
+#endif
 #undef GF_A16_BWD
     GF_LAUNCH_CHECK();
     return 0;
@@ -603,24 +861,33 @@ static int launch16_bwd(const float* qkv, const float* o, const float* lse, cons
         default: return FN<HD, 7>(__VA_ARGS__);             \
     }
 
-int launch_attn16_fwd(const float* qkv, float* o, float* lse, uint32_t* keepw, int S, int B, int E, int H, float p, uint32_t site,
+int A16_ENTRY(launch_attn16_fwd)(const float* qkv, float* o, float* lse, uint32_t* keepw, int S, int B, int E, int H, float p, uint32_t site,
                       const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1,
-                      const int32_t* key_len) {
+                      const int32_t* key_len, uint32_t flags) {
+    const bool causal = (flags & GANFFN_ATTN_CAUSAL) != 0;
     GF_CHECK_ARG(!seg1 || (seg1->qkv && seg1->o), "attn16_fwd: bad second batch");
+    GF_CHECK_ARG(!(seg1 && causal), "attn16_fwd: the two-batch launch has no causal form");
     GF_CHECK_ARG(attn16_supported(E, H, S) && S >= 1 && S <= GANFFN_MAX_SEQ, "attn16_fwd: unsupported E=%d H=%d S=%d", E, H, S);
     GF_CHECK_ARG((long)B * H * 28 * 128 < (1l << 32), "attention: B*H too large for the Philox counter");
+#ifndef GANFFN_A16_CAUSAL_TU
+    if (causal) return launch_attn16_fwd_causal(qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st, seg1, key_len, flags);
+#endif
     if (E / H == 64) { NT16_SWITCH3(launch16_fwd, 64, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st, seg1, key_len) }
     if (E / H == 60) { NT16_SWITCH3(launch16_fwd, 60, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st, seg1, key_len) }
     if (E / H == 10) { NT16_SWITCH(launch16_fwd, 10, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st, seg1, key_len) }
     NT16_SWITCH(launch16_fwd, 30, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st, seg1, key_len)
 }
 
-int launch_attn16_bwd(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keepw, float* d_qkv,
+int A16_ENTRY(launch_attn16_bwd)(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keepw, float* d_qkv,
                       int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train,
-                      hipStream_t st, const int32_t* key_len) {
+                      hipStream_t st, const int32_t* key_len, uint32_t flags) {
+    [[maybe_unused]] const bool causal = (flags & GANFFN_ATTN_CAUSAL) != 0;
     GF_CHECK_ARG(attn16_supported(E, H, S) && S >= 1 && S <= GANFFN_MAX_SEQ, "attn16_bwd: unsupported E=%d H=%d S=%d", E, H, S);
     GF_CHECK_ARG(o && lse, "attention_bwd: head_dim %d needs the forward's output and log-sum-exp", E / H);
     GF_CHECK_ARG((long)B * H * 28 * 128 < (1l << 32), "attention: B*H too large for the Philox counter");
+#ifndef GANFFN_A16_CAUSAL_TU
+    if (causal) return launch_attn16_bwd_causal(qkv, o, lse, d_o, keepw, d_qkv, S, B, E, H, p, site, rng, add, train, st, key_len, flags);
+#endif
     if (E / H == 64) { NT16_SWITCH3(launch16_bwd, 64, qkv, o, lse, d_o, keepw, d_qkv, S, B, E, H, p, site, rng, add, train, st, key_len) }
     if (E / H == 60) { NT16_SWITCH3(launch16_bwd, 60, qkv, o, lse, d_o, keepw, d_qkv, S, B, E, H, p, site, rng, add, train, st, key_len) }
     if (E / H == 10) { NT16_SWITCH(launch16_bwd, 10, qkv, o, lse, d_o, keepw, d_qkv, S, B, E, H, p, site, rng, add, train, st, key_len) }

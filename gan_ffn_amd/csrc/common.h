@@ -341,24 +341,33 @@ struct AttnFwdSeg1 {
 };
 // key_len (optional, device int32 [B]): dialogue b attends over keys j < clamp(key_len[b], 1, S) only (probability 0 past it,
 // dK and dV rows written as zeros); null = all S keys, today's bits.  With seg1 the lengths serve both batches (the same B dialogues).
+// flags: GANFFN_ATTN_CAUSAL = query i attends to keys j <= i as well (key limit min(n, i + 1)); kernels of their own, instantiated
+// only in the form with lengths (a null key_len reads as S there) and not for seg1.  0 = the launches and bits without it.
 int launch_attention_fwd(const float* qkv, float* o, float* lse, uint32_t* keep, int S, int B, int E, int H, float p, uint32_t site,
                          const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1 = nullptr,
-                         const int32_t* key_len = nullptr);
+                         const int32_t* key_len = nullptr, uint32_t flags = 0);
 int launch_attention_bwd(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keep, float* d_qkv,
                          int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train,
-                         hipStream_t st, const int32_t* key_len = nullptr);
+                         hipStream_t st, const int32_t* key_len = nullptr, uint32_t flags = 0);
 // the key length of dialogue b inside a kernel instantiated for lengths: one scalar load per workgroup (b is workgroup-uniform),
 // clamped here so that a bad length can neither empty a softmax nor move a read out of range
 __device__ __forceinline__ int attn_key_len(const int32_t* __restrict__ key_len, int b, int S) {
     return key_len ? min(max(key_len[b], 1), S) : S;
 }
 bool attn16_supported(int E, int H, int S);
+// the causal launches of the same family (attention16_causal.hip); reached through launch_attn16_fwd / _bwd with the flag set
+int launch_attn16_fwd_causal(const float* qkv, float* o, float* lse, uint32_t* keepw, int S, int B, int E, int H, float p,
+                             uint32_t site, const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1,
+                             const int32_t* key_len, uint32_t flags);
+int launch_attn16_bwd_causal(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keepw,
+                             float* d_qkv, int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add,
+                             int train, hipStream_t st, const int32_t* key_len, uint32_t flags);
 int launch_attn16_fwd(const float* qkv, float* o, float* lse, uint32_t* keepw, int S, int B, int E, int H, float p, uint32_t site,
                       const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1 = nullptr,
-                      const int32_t* key_len = nullptr);
+                      const int32_t* key_len = nullptr, uint32_t flags = 0);
 int launch_attn16_bwd(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keepw, float* d_qkv,
                       int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train,
-                      hipStream_t st, const int32_t* key_len = nullptr);
+                      hipStream_t st, const int32_t* key_len = nullptr, uint32_t flags = 0);
 
 // out1 (optional): a second segment over the same x in the same launch, with its own output and train flag
 int launch_pe_dropout(const float* x, const float* pe, float* out, int S, int B, int E, float p,

@@ -387,6 +387,9 @@ class _NetRunner(_Runner):
     # ignores padded utterances), or None: the plain encoder calls.  Held here until the next step replaces it, so the tensor
     # outlives the backward that reads it.  GanEngine, whose passes have two batch widths, overrides _pass_key_len instead.
     _key_len = None
+    # causal self-attention in every encoder call of _net_fwd / _net_bwd (Phase2Engine(causal=True)); False: the calls without it.
+    # GanEngine has no causal form yet (its paired forward and parts backward have none in the library) and leaves this False.
+    _causal = False
 
     def _pass_key_len(self, ps):
         """the key lengths of a forward / backward on the pass buffers ps (None: the plain encoder calls)"""
@@ -414,7 +417,7 @@ class _NetRunner(_Runner):
         else:
             a0, a1 = self._base_add + adds[0], self._base_add + adds[1]
         ops.encoder_fwd_raw(cfg, x, net.pe, net.slab, ps.enc_out, ps.saved if save else None, self.ws, self.rng.state, a0,
-                            key_len=self._pass_key_len(ps))
+                            key_len=self._pass_key_len(ps), causal=self._causal)
         w = net.w
         w3 = w("fc3.weight") if net.kind == 1 else None
         b3 = w("fc3.bias") if net.kind == 1 else None
@@ -441,6 +444,8 @@ class _NetRunner(_Runner):
         # train_gen passes its input gradient on to the generator
         if need_dx is None:
             need_dx = not want_wgrad
+        if parts and self._causal:
+            raise NotImplementedError("the parts backward has no causal form")
         if parts and want_wgrad and reduce_cb is None:
             # single GPU, d_model 100: the weight gradients stay as token-chunk slabs for Adam to add (no reduce launch, and the
             # caller did not zero the encoder region of net.grad) -> (parts view of self.ws, stride, chunks)
@@ -448,7 +453,7 @@ class _NetRunner(_Runner):
                                              key_len=self._pass_key_len(ps))
         if reduce_cb is None or not want_wgrad:
             ops.encoder_bwd_raw(cfg, 0, net.L, ps.dx, net.slab, gslab, ps.saved, self.ws, self.rng.state, a0, need_dx,
-                                key_len=self._pass_key_len(ps))
+                                key_len=self._pass_key_len(ps), causal=self._causal)
         else:
             # bucketed: backward a group of layers, then hand that slice of the grad slab to the all-reduce
             bks = net.buckets(self.n_buckets)
@@ -456,7 +461,7 @@ class _NetRunner(_Runner):
             for i, (lo_f, hi_f) in enumerate(bks[1:]):
                 lo, hi = lo_f // net.layer_floats, hi_f // net.layer_floats
                 ops.encoder_bwd_raw(cfg, lo, hi, ps.dx, net.slab, gslab, ps.saved, self.ws, self.rng.state, a0, need_dx,
-                                    key_len=self._pass_key_len(ps))
+                                    key_len=self._pass_key_len(ps), causal=self._causal)
                 reduce_cb(lo_f, hi_f, last=(i == len(bks) - 2))
 
     def _adam(self, net, parts=None):
@@ -1099,11 +1104,16 @@ class Phase2Engine(_NetRunner):
     The reference re-creates a LambdaLR every batch, which pins the effective lr to its base value.
     mask_padding (default False: the reference passes no mask) is an extension: the three generators' self-attention sees only the
     first umask.sum(1) utterances of every dialogue (ganffn_encoder_fwd_len / _bwd_len), so a dialogue's prediction does not depend
-    on how far its batch is padded.  umask must then be a prefix mask.  False issues exactly the calls it always did."""
+    on how far its batch is padded.  umask must then be a prefix mask.  False issues exactly the calls it always did.
+    causal (default False: the reference's generators are bidirectional) is an extension too: in the three generators utterance i
+    attends to utterances j <= i only (ganffn_encoder_fwd_mask / _bwd_mask with GANFFN_ATTN_CAUSAL), so log_prob[t] is a function
+    of utterances 0 .. t — a classifier that can run while the dialogue is spoken.  It composes with mask_padding and alone needs
+    no lengths.  False issues exactly the calls it always did."""
 
     def __init__(self, ffn_module, lr=1e-4, weight_decay=0.008, class_weights=CLASS_WEIGHTS, process_group=None,
-                 n_buckets=3, mask_padding=False):
+                 n_buckets=3, mask_padding=False, causal=False):
         self.mask_padding = bool(mask_padding)
+        self._causal = self.causal = bool(causal)
         self.module = ffn_module
         self.G = _module_generators(ffn_module, lr, weight_decay)
         self._init_common(next(iter(self.G.values())).slab.device, process_group, n_buckets, self.G.items())

@@ -210,9 +210,11 @@ class _Net(nn.Module):
         return self._slab
 
     # ---- forward ---------------------------------------------------------------------------
-    def forward(self, x, key_lengths=None):
+    def forward(self, x, key_lengths=None, causal=False):
         """key_lengths (int32 device tensor [batch], or None): an extension — self-attention sees only the first
-        key_lengths[b] utterances of dialogue b (nn.TransformerEncoder's src_key_padding_mask for a prefix mask)."""
+        key_lengths[b] utterances of dialogue b (nn.TransformerEncoder's src_key_padding_mask for a prefix mask).
+        causal=True (an extension too): utterance i attends to utterances j <= i only (nn.TransformerEncoder's
+        mask = triu(-inf, 1)); everything else in the network is row-wise, so row t of the output is a function of rows 0 .. t."""
         self._ensure_packed()
         if self.HAS_OBJECT and x.size(-1) == self.OBJECT_IN:      # model.py:1355-1356
             x = ops.LinearFn.apply(x, self.object.weight, self.object.bias)
@@ -227,6 +229,8 @@ class _Net(nn.Module):
                 "views": self._views[:n_enc]}
         if key_lengths is not None:
             meta["key_len"] = key_lengths.to(device=x.device, dtype=torch.int32).contiguous()
+        if causal:
+            meta["causal"] = True
         enc_params = self._slab_params()[:n_enc]
         h = ops.EncoderFn.apply(x, self.position_encoding.pe, self._slab, meta, *enc_params)
         fc3 = getattr(self, "fc3", None)
@@ -300,9 +304,11 @@ class GAN_FFN(nn.Module):
     """model.py:1405-1462: log_softmax(fc(G_a(a) + G_v(v) + G_t(t)), 2).  `lstm`, `smax_fc`, dropout are
     constructed-but-unused members of the reference (model.py:1425-1430) kept for parameter-count parity."""
 
-    def __init__(self, acoustic_generator, visual_generator, text_generator, n_classes=6, dropout=0.2, mask_padding=False):
+    def __init__(self, acoustic_generator, visual_generator, text_generator, n_classes=6, dropout=0.2, mask_padding=False,
+                 causal=False):
         super().__init__()
         self.mask_padding = bool(mask_padding)      # extension (plain attribute: the state_dict is the reference's)
+        self.causal = bool(causal)                  # extension (plain attribute too)
         self.n_classes = n_classes
         self.acoustic_generator = acoustic_generator
         self.visual_generator = visual_generator
@@ -317,10 +323,14 @@ class GAN_FFN(nn.Module):
     def forward(self, acoustic, visual, text, umask=None):
         """mask_padding=True (an extension; the reference passes no mask): the generators' self-attention ignores the padded
         utterances of every dialogue, so a dialogue is predicted as if it were alone in the batch.  umask [batch, seq_len] must
-        be a prefix mask (ones, then zeros)."""
+        be a prefix mask (ones, then zeros).
+        causal=True (an extension; every generator of the reference is bidirectional): the generators' self-attention never
+        looks ahead, and since the rest of the classifier is row-wise, log_prob[t] depends on utterances 0 .. t only — the
+        classifier can label a dialogue as it is spoken.  It composes with mask_padding; alone it needs no umask."""
         kl = ops.key_lengths_from_umask(umask) if self.mask_padding else None
-        fusion = ops.Add3Fn.apply(self.acoustic_generator(acoustic, kl), self.visual_generator(visual, kl),
-                                  self.text_generator(text, kl))
+        c = self.causal
+        fusion = ops.Add3Fn.apply(self.acoustic_generator(acoustic, kl, c), self.visual_generator(visual, kl, c),
+                                  self.text_generator(text, kl, c))
         logits = ops.LinearFn.apply(fusion, self.fc.weight, self.fc.bias)
         log_prob = ops.LogSoftmaxFn.apply(logits)
         return log_prob, [], [], []

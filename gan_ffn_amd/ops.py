@@ -160,9 +160,19 @@ def _check_key_len(key_len, cfg):
         raise ValueError("key_len must be a contiguous int32 device tensor with one entry per dialogue (%d)" % cfg.B)
 
 
-def encoder_fwd_raw(cfg, x, pe, slab, out, saved, ws, rng, add, key_len=None):
+ATTN_CAUSAL = 1                    # GANFFN_ATTN_CAUSAL
+
+
+def encoder_fwd_raw(cfg, x, pe, slab, out, saved, ws, rng, add, key_len=None, causal=False):
     """key_len (int32 device tensor [B], or None): the attention of every layer sees keys j < key_len[b] of dialogue b only
-    (ganffn_encoder_fwd_len); None is the plain call."""
+    (ganffn_encoder_fwd_len); None is the plain call.  causal=True: query i sees keys j <= i as well, with or without lengths
+    (ganffn_encoder_fwd_mask with GANFFN_ATTN_CAUSAL) — row t of the output then depends on rows 0 .. t of x alone."""
+    if causal:
+        if key_len is not None:
+            _check_key_len(key_len, cfg)
+        _lib.call("ganffn_encoder_fwd_mask", C.byref(cfg), _ptr(key_len), C.c_uint32(ATTN_CAUSAL), _ptr(x), _ptr(pe), _ptr(slab),
+                  _ptr(out), _ptr(saved), _ptr(ws), _ptr(rng), C.c_uint64(add), _stream())
+        return
     if key_len is None:
         _lib.call("ganffn_encoder_fwd", C.byref(cfg), _ptr(x), _ptr(pe), _ptr(slab), _ptr(out), _ptr(saved), _ptr(ws),
                   _ptr(rng), C.c_uint64(add), _stream())
@@ -197,9 +207,15 @@ def encoder_fwd_pair_raw(cfg, x, pe, slab, out_eval, out_train, saved_train, ws,
               _ptr(out_train), _ptr(saved_train), _ptr(ws), _ptr(rng), C.c_uint64(add_train), _stream())
 
 
-def encoder_bwd_raw(cfg, lo, hi, dx, slab, gslab, saved, ws, rng, add, need_dx_in=True, key_len=None):
+def encoder_bwd_raw(cfg, lo, hi, dx, slab, gslab, saved, ws, rng, add, need_dx_in=True, key_len=None, causal=False):
     """need_dx_in=False: the stack's input needs no gradient — with lo == 0 the bottom in-proj dgrad and the PE dropout
-    backward are skipped (as autograd skips them) and dx is undefined afterwards.  key_len: the lengths the forward was given."""
+    backward are skipped (as autograd skips them) and dx is undefined afterwards.  key_len, causal: what the forward was given."""
+    if causal:
+        if key_len is not None:
+            _check_key_len(key_len, cfg)
+        _lib.call("ganffn_encoder_bwd_mask", C.byref(cfg), _ptr(key_len), C.c_uint32(ATTN_CAUSAL), lo, hi, _ptr(dx), _ptr(slab),
+                  _ptr(gslab), _ptr(saved), _ptr(ws), _ptr(rng), C.c_uint64(add), 1 if need_dx_in else 0, _stream())
+        return
     if key_len is not None:
         _check_key_len(key_len, cfg)
         _lib.call("ganffn_encoder_bwd_len", C.byref(cfg), _ptr(key_len), lo, hi, _ptr(dx), _ptr(slab), _ptr(gslab), _ptr(saved),
@@ -355,8 +371,10 @@ class EncoderFn(torch.autograd.Function):
         rng = DeviceRng.get(x.device)
         add = rng.next_add() if train else 0
         key_len = meta.get("key_len")
-        encoder_fwd_raw(cfg, xc, pe, slab, out, saved, ws, rng.state, add, key_len=key_len)
+        causal = bool(meta.get("causal", False))
+        encoder_fwd_raw(cfg, xc, pe, slab, out, saved, ws, rng.state, add, key_len=key_len, causal=causal)
         ctx.key_len = key_len          # (kept alive for the backward)
+        ctx.causal = causal
         ctx.cfg, ctx.add, ctx.rng_state = cfg, add, rng.state
         ctx.slab, ctx.saved = slab, saved
         ctx.param_meta = meta
@@ -371,7 +389,7 @@ class EncoderFn(torch.autograd.Function):
         want_w = any(ctx.needs_input_grad[4:])
         gslab = torch.zeros_like(ctx.slab) if want_w else None
         encoder_bwd_raw(cfg, 0, cfg.L, dx, ctx.slab, gslab, ctx.saved, ws, ctx.rng_state, ctx.add,
-                        need_dx_in=ctx.needs_input_grad[0], key_len=ctx.key_len)
+                        need_dx_in=ctx.needs_input_grad[0], key_len=ctx.key_len, causal=ctx.causal)
         grads = [None] * len(meta["views"])
         if want_w:
             for i, (off, shape) in enumerate(meta["views"]):

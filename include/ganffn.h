@@ -564,6 +564,32 @@ int ganffn_encoder_fwd_len(const ganffn_enc_cfg* cfg, const int32_t* key_len, co
 int ganffn_encoder_bwd_len(const ganffn_enc_cfg* cfg, const int32_t* key_len, int layer_lo, int layer_hi, float* dx,
                            const float* params, float* grads, const float* saved, float* workspace, const uint64_t* rng,
                            uint64_t rng_offset_add, int need_dx_in, void* stream);
+/* ---- causal self-attention: a query never looks ahead -------------------------------------------------------------------------
+ * The _len calls above with a flags word after key_len.  GANFFN_ATTN_CAUSAL: what nn.TransformerEncoder(src, mask = triu(-inf, 1),
+ * src_key_padding_mask = pad) computes.  In every layer, query row i of dialogue b attends to keys j <= i and, when lengths are
+ * given, j < clamp(key_len[b], 1, S): the key limit of a query is min(n, i + 1) >= 1, so no softmax is ever empty; lse is over
+ * the allowed keys; the Philox indexing of the dropout is that of the calls above (it does not depend on the mask).  The
+ * backward is the gradient of that forward, with P = 0 set explicitly for masked keys; the k and v parts of d_qkv at rows >= n
+ * are written as exact zeros, as above.  Keep words at masked (query, key) positions are unspecified: nothing reads them.
+ * Everything else of a stack is row-wise, so with the flag row t of the output of ganffn_encoder_fwd_mask is a function of input
+ * rows 0 .. t alone, and finite values at later rows change no bit of it.
+ * flags == 0 is exactly the _len call (same launches, same bits); key_len may be NULL with any flags; a bit other than
+ * GANFFN_ATTN_CAUSAL is refused with a message and nothing is written.  Saved and workspace sizes and layouts are unchanged.  The
+ * forward and the backward of one pass must be given the same flags (and lengths).  The causal kernels are instantiations of
+ * their own; in the head_dim 10 / 30 family (and 60 / 64 at S <= 48) they also skip the key tiles above the diagonal. */
+#define GANFFN_ATTN_CAUSAL 1u
+int ganffn_attention_fwd_mask(const float* qkv, float* o, float* lse, uint32_t* keep, const int32_t* key_len, uint32_t flags,
+                              int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng,
+                              uint64_t rng_offset_add, void* stream);
+int ganffn_attention_bwd_mask(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keep,
+                              const int32_t* key_len, uint32_t flags, float* d_qkv, int S, int B, int E, int H, float p,
+                              uint32_t site, const uint64_t* rng, uint64_t rng_offset_add, void* stream);
+int ganffn_encoder_fwd_mask(const ganffn_enc_cfg* cfg, const int32_t* key_len, uint32_t flags, const float* x_in,
+                            const float* pe, const float* params, float* out, float* saved, float* workspace,
+                            const uint64_t* rng, uint64_t rng_offset_add, void* stream);
+int ganffn_encoder_bwd_mask(const ganffn_enc_cfg* cfg, const int32_t* key_len, uint32_t flags, int layer_lo, int layer_hi,
+                            float* dx, const float* params, float* grads, const float* saved, float* workspace,
+                            const uint64_t* rng, uint64_t rng_offset_add, int need_dx_in, void* stream);
 /* z = x + drop(y); xhat = (z-mean)*rstd; out = xhat*w + b   (norm1/norm2 of the encoder layer).  Accepted: T >= 1 and
  * 1 <= E <= 640, a multiple of 4 or not; a wider row is refused with a message.  The variance is the two-pass one (mean
  * of the squared deviations), so a row mean far above the row's spread costs no more than fp32 rounding of z itself. */
