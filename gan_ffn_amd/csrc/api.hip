@@ -180,8 +180,146 @@ extern "C" int64_t ganffn_encoder_workspace_floats(const ganffn_enc_cfg* c) {
 // ------------------------------------------------------------------------------------------
 // encoder stack forward
 // ------------------------------------------------------------------------------------------
-// key_len (or null): per-dialogue key lengths of the attention core, the one place of a layer where rows of a dialogue meet
-// flags: GANFFN_ATTN_* bits for the same place (0 = none; an unknown bit is refused before anything is launched)
+// One row segment of a forward pass: T = S B rows that go through the stack with their own buffers and train flag.  A pass
+// has one segment or two (the second over the same input, in the same launches: every forward kernel has a two-segment form).
+struct FwdSeg {
+    float* X;          // the running activation: X[0] = PE output, X[l + 1] = output of layer l (the last one goes to `out`)
+    float* layers;     // layer l's saved set (SavedOff: qkv, attn_o, x1, xhat1, xhat2, h, rstd1, rstd2, lse, keep, hmask)
+    float* tmp;        // [MAX_SPLITS][T x E] GEMM output (partial slabs) before residual + LayerNorm
+    float* out;        // the stack's output
+    int64_t TE, per_layer;
+    int L, train;
+    bool keeps;        // a backward will follow: every X[l] and layer set has its own place, keep words and hmask are written
+    float* x(int l) const { return l == L ? out : X + (keeps ? l : (l & 1)) * TE; }
+    float* layer(int l) const { return layers + (keeps ? l : 0) * per_layer; }
+};
+// nothing kept: X ping-pongs at workspace + 0 / + TE | one layer's saved set, reused by every layer | slabs
+static FwdSeg unsaved_seg(const ganffn_enc_cfg* c, const SavedOff& so, float* workspace, float* out, int train) {
+    const int64_t TE = (int64_t)c->S * c->B * c->E;
+    return FwdSeg{workspace, workspace + 2 * TE, workspace + 2 * TE + so.per_layer, out, TE, so.per_layer, c->L, train, false};
+}
+// everything kept in `saved` (SavedOff); the slabs are the caller's
+static FwdSeg saved_seg(const ganffn_enc_cfg* c, const SavedOff& so, float* saved, float* tmp, float* out, int train) {
+    const int64_t TE = (int64_t)c->S * c->B * c->E;
+    return FwdSeg{saved + so.X, saved + so.layers, tmp, out, TE, so.per_layer, c->L, train, true};
+}
+
+// The launch sequence of the stack, once.  s1 (or null): the second segment; every launcher takes it as its optional trailing
+// operand set, built here from s1 and null without one.  Every rule that picks a summation order (split-K factors, K chunks of
+// gemm_n100) is evaluated for T = S B, one segment's rows, so a segment has the bits of a pass of its own.
+// key_len (or null): per-dialogue key lengths of the attention core, the one place of a layer where rows of a dialogue meet;
+// both segments are the same B dialogues, so one [B] array serves both
+// flags: GANFFN_ATTN_* bits for the same place (0 = none); the causal kernels have no two-segment form
+static int encoder_fwd_walk(const ganffn_enc_cfg* c, const int32_t* key_len, uint32_t flags, const Mode md, const FwdSeg& s0,
+                            const FwdSeg* s1, const float* pe, const float* x_in, const float* params, const uint64_t* rng,
+                            uint64_t add, hipStream_t st) {
+    GF_CHECK_ARG(!s1 || flags == 0, "encoder_fwd_pair: flags 0x%x have no two-segment form", flags);
+    const int S = c->S, B = c->B, E = c->E, H = c->H, F = c->F, L = c->L, T = S * B;
+    const int64_t TE = (int64_t)T * E;
+    const LayerOff lo = layer_off(E, F);
+    const SavedOff so = saved_off(c);
+    // t1's addresses are only handed on where s1 is: without a second segment the adapters below give the launchers null
+    const FwdSeg& t1 = s1 ? *s1 : s0;
+    const int train0 = s0.train, train1 = s1 ? s1->train : 0;
+    auto keep_words = [&](const FwdSeg& s, float* sv) { return s.keeps ? reinterpret_cast<uint32_t*>(sv + so.keep) : nullptr; };
+    // [T x K] x W[N x K]^T of both segments in one launch; splits (or null): split-K slabs TE apart, summed by the LayerNorm kernel
+    auto nt = [&](const float* A0, const float* A1, int K, const float* W, float* C0, float* C1, int N, int epi, const EpiArgs& ea,
+                  uint16_t* mask1 = nullptr, int* splits = nullptr) {
+        const GemmSeg1 g1{A1, C1, mask1, train1};
+        return launch_gemm_nt(A0, K, W, K, C0, N, T, N, K, epi, ea, st, splits, splits ? TE : 0, s1 ? &g1 : nullptr);
+    };
+    auto ln = [&](const float* x0, const float* x1, const float* w, const float* b, float* out0, float* out1, float* xhat0,
+                  float* xhat1, float* rstd0, float* rstd1, uint32_t site, int nslab) {
+        const LnFwdSeg1 n1{x1, t1.tmp, out1, xhat1, rstd1, train1};
+        return launch_add_drop_ln_fwd(x0, s0.tmp, w, b, out0, xhat0, rstd0, T, E, c->ln_eps, c->p_enc, site, rng, add, train0, st,
+                                      nslab, TE, s1 ? &n1 : nullptr);
+    };
+
+    // d_model 100: out-proj + residual + dropout + LN1 is one kernel, and LN2 carries the NEXT layer's in-proj (rowchain.hip);
+    // the positional encoding + dropout at the head of the stack carries layer 0's
+    const bool rc = rc_supported(E) && !md.rc_off();
+    if (rc && !md.pe_off()) {
+        RcFwdSeg1 r1{};
+        r1.y = pe; r1.x = x_in; r1.out = t1.x(0); r1.post_out = t1.layer(0) + so.qkv; r1.train = train1;
+        GF_TRY(launch_rc_pe_inproj_fwd(x_in, pe, s0.x(0), params + lo.in_w, params + lo.in_b, s0.layer(0) + so.qkv, T, B, c->p_pe, rng,
+                                       add, train0, st, s1 ? &r1 : nullptr));
+    } else {
+        GF_TRY(launch_pe_dropout(x_in, pe, s0.x(0), S, B, E, c->p_pe, rng, add, train0, st, s1 ? s1->x(0) : nullptr, train1));
+        if (rc) {
+            EpiArgs e0;
+            e0.bias = params + lo.in_b;
+            GF_TRY(nt(s0.x(0), t1.x(0), E, params + lo.in_w, s0.layer(0) + so.qkv, t1.layer(0) + so.qkv, 3 * E, EPI_NONE, e0));
+        }
+    }
+
+    for (int l = 0; l < L; ++l) {
+        const float* P = params + (int64_t)l * lo.total;
+        float* const v0 = s0.layer(l);
+        float* const v1 = t1.layer(l);
+        const uint32_t site = SITE_LAYER0 + 4 * l;
+        EpiArgs ea;
+        // qkv = X W_in^T + b_in
+        ea.bias = P + lo.in_b;
+        if (!rc) GF_TRY(nt(s0.x(l), t1.x(l), E, P + lo.in_w, v0 + so.qkv, v1 + so.qkv, 3 * E, EPI_NONE, ea));
+        // attention core (keep words only when a backward will follow)
+        {
+            const AttnFwdSeg1 a1{v1 + so.qkv, v1 + so.attn_o, v1 + so.lse, keep_words(t1, v1), train1};
+            GF_TRY(launch_attention_fwd(v0 + so.qkv, v0 + so.attn_o, v0 + so.lse, keep_words(s0, v0), S, B, E, H, c->p_enc, site + 0, rng,
+                                        add, train0, st, s1 ? &a1 : nullptr, key_len, flags));
+        }
+        // out-proj, residual + dropout + LN1
+        if (rc) {
+            RcFwdSeg1 r1{};
+            r1.pre_a = v1 + so.attn_o; r1.x = t1.x(l); r1.out = v1 + so.x1; r1.xhat = v1 + so.xhat1; r1.rstd = v1 + so.rstd1;
+            r1.train = train1;
+            GF_TRY(launch_rc_outproj_ln_fwd(v0 + so.attn_o, P + lo.out_w, P + lo.out_b, s0.x(l), P + lo.n1w, P + lo.n1b, v0 + so.x1,
+                                            v0 + so.xhat1, v0 + so.rstd1, T, c->ln_eps, c->p_enc, site + 1, rng, add, train0, st,
+                                            s1 ? &r1 : nullptr));
+        } else {
+            ea.bias = P + lo.out_b;
+            // (the 512-wide out-proj is 376 output tiles on 256 CUs: K in two halves, summed by the LayerNorm kernel)
+            int osplits = md.outproj_nosplit() ? 1 : gemm_splitk_factor(T, E, E);
+            GF_TRY(nt(v0 + so.attn_o, v1 + so.attn_o, E, P + lo.out_w, s0.tmp, t1.tmp, E, EPI_NONE, ea, nullptr, &osplits));
+            GF_TRY(ln(s0.x(l), t1.x(l), P + lo.n1w, P + lo.n1b, v0 + so.x1, v1 + so.x1, v0 + so.xhat1, v1 + so.xhat1, v0 + so.rstd1,
+                      v1 + so.rstd1, site + 1, osplits));
+        }
+        // FFN: h = drop(relu(x1 W1^T + b1)); y = h W2^T + b2
+        int splits = 1;
+        {
+            EpiArgs e1;
+            e1.bias = P + lo.b1; e1.p = c->p_enc; e1.site = site + 2; e1.rng = rng; e1.rng_add = add; e1.train = train0;
+            // hmask: the pattern the linear2 dgrad will ask for
+            if (s0.keeps) e1.mask_out = reinterpret_cast<uint16_t*>(v0 + so.hmask);
+            uint16_t* const mask1 = t1.keeps ? reinterpret_cast<uint16_t*>(v1 + so.hmask) : nullptr;
+            GF_TRY(nt(v0 + so.x1, v1 + so.x1, E, P + lo.w1, v0 + so.h, v1 + so.h, F, EPI_RELU_DROP, e1, mask1));
+            if (n100_supported(E, F) && !md.n100_off()) {
+                splits = MAX_SPLITS;                   // K chunks = output slabs, summed by the LayerNorm kernel
+                GF_TRY(launch_gemm_n100(v0 + so.h, F, P + lo.w2, F, 0, P + lo.b2, s0.tmp, TE, T, F, &splits, st,
+                                        s1 ? v1 + so.h : nullptr, s1 ? s1->tmp : nullptr));
+            } else {
+                ea.bias = P + lo.b2;
+                splits = gemm_splitk_factor(T, E, F);      // few output tiles, K = 2048: split K, LN sums the slabs
+                GF_TRY(nt(v0 + so.h, v1 + so.h, F, P + lo.w2, s0.tmp, t1.tmp, E, EPI_NONE, ea, nullptr, &splits));
+            }
+        }
+        if (rc) {
+            // LN2, then (all but the last layer) qkv of layer l + 1 from the fresh rows while they are in the workgroup
+            const float* Pn = (l + 1 < L) ? P + lo.total : nullptr;
+            RcFwdSeg1 r1{};
+            r1.y = t1.tmp; r1.x = v1 + so.x1; r1.out = t1.x(l + 1); r1.xhat = v1 + so.xhat2; r1.rstd = v1 + so.rstd2;
+            r1.post_out = Pn ? t1.layer(l + 1) + so.qkv : nullptr; r1.train = train1;
+            GF_TRY(launch_rc_ln_inproj_fwd(s0.tmp, splits, TE, v0 + so.x1, P + lo.n2w, P + lo.n2b, s0.x(l + 1), v0 + so.xhat2,
+                                           v0 + so.rstd2, Pn ? Pn + lo.in_w : nullptr, Pn ? Pn + lo.in_b : nullptr,
+                                           Pn ? s0.layer(l + 1) + so.qkv : nullptr, T, c->ln_eps, c->p_enc, site + 3, rng, add, train0,
+                                           st, s1 ? &r1 : nullptr));
+        } else {
+            GF_TRY(ln(v0 + so.x1, v1 + so.x1, P + lo.n2w, P + lo.n2b, s0.x(l + 1), t1.x(l + 1), v0 + so.xhat2, v1 + so.xhat2,
+                      v0 + so.rstd2, v1 + so.rstd2, site + 3, splits));
+        }
+    }
+    return 0;
+}
+
 static int encoder_fwd_impl(const ganffn_enc_cfg* c, const int32_t* key_len, uint32_t flags, const float* x_in, const float* pe,
                             const float* params, float* out, float* saved, float* workspace, const uint64_t* rng, uint64_t add,
                             void* stream) {
@@ -193,94 +331,9 @@ static int encoder_fwd_impl(const ganffn_enc_cfg* c, const int32_t* key_len, uin
                  "encoder_fwd: buffers must be 16-byte aligned");
     const bool drop = c->train && (c->p_pe > 0.f || c->p_enc > 0.f);
     GF_CHECK_ARG(!drop || rng, "encoder_fwd: rng required in train mode");
-    hipStream_t st = (hipStream_t)stream;
-    const int S = c->S, B = c->B, E = c->E, H = c->H, F = c->F, L = c->L, T = S * B;
-    const int64_t TE = (int64_t)T * E;
-    const LayerOff lo = layer_off(E, F);
     const SavedOff so = saved_off(c);
-    const int train = c->train;
-
-    float* tmp;      // [MAX_SPLITS][T x E] GEMM output (partial slabs) before residual+LN
-    float* Xcur;
-    if (saved) {
-        tmp = workspace;
-        Xcur = saved + so.X;
-    } else {
-        tmp = workspace + 2 * TE + so.per_layer;
-        Xcur = workspace;
-    }
-    // d_model 100: out-proj + residual + dropout + LN1 is one kernel, and LN2 carries the NEXT layer's in-proj (rowchain.hip);
-    // the positional encoding + dropout at the head of the stack carries layer 0's
-    const bool rc = rc_supported(E) && !md.rc_off();
-    auto layer_saved = [&](int l) { return saved ? saved + so.layers + (int64_t)l * so.per_layer : workspace + 2 * TE; };
-    if (rc && !md.pe_off()) {
-        GF_TRY(launch_rc_pe_inproj_fwd(x_in, pe, Xcur, params + lo.in_w, params + lo.in_b, layer_saved(0) + so.qkv, T, B, c->p_pe, rng,
-                                       add, train, st));
-    } else {
-        GF_TRY(launch_pe_dropout(x_in, pe, Xcur, S, B, E, c->p_pe, rng, add, train, st));
-        if (rc) {
-            EpiArgs e0;
-            e0.bias = params + lo.in_b;
-            GF_TRY(launch_gemm_nt(Xcur, E, params + lo.in_w, E, layer_saved(0) + so.qkv, 3 * E, T, 3 * E, E, EPI_NONE, e0, st));
-        }
-    }
-
-    for (int l = 0; l < L; ++l) {
-        const float* P = params + (int64_t)l * lo.total;
-        float* sv = layer_saved(l);
-        float* Xnext = saved ? saved + so.X + (int64_t)(l + 1) * TE : workspace + ((l & 1) ? 0 : TE);
-        if (l == L - 1) Xnext = out;
-        const uint32_t site = SITE_LAYER0 + 4 * l;
-        EpiArgs ea;
-        // qkv = X W_in^T + b_in
-        ea.bias = P + lo.in_b;
-        if (!rc) GF_TRY(launch_gemm_nt(Xcur, E, P + lo.in_w, E, sv + so.qkv, 3 * E, T, 3 * E, E, EPI_NONE, ea, st));
-        // attention core
-        // (keep words only when a backward will follow: saved != null)
-        GF_TRY(launch_attention_fwd(sv + so.qkv, sv + so.attn_o, sv + so.lse, saved ? reinterpret_cast<uint32_t*>(sv + so.keep) : nullptr, S, B, E,
-                                    H, c->p_enc, site + 0, rng, add, train, st, nullptr, key_len, flags));
-        // out-proj, residual + dropout + LN1
-        if (rc) {
-            GF_TRY(launch_rc_outproj_ln_fwd(sv + so.attn_o, P + lo.out_w, P + lo.out_b, Xcur, P + lo.n1w, P + lo.n1b, sv + so.x1,
-                                            sv + so.xhat1, sv + so.rstd1, T, c->ln_eps, c->p_enc, site + 1, rng, add, train, st));
-        } else {
-            ea.bias = P + lo.out_b;
-            // (the 512-wide out-proj is 376 output tiles on 256 CUs: K in two halves, summed by the LayerNorm kernel)
-            int osplits = md.outproj_nosplit() ? 1 : gemm_splitk_factor(T, E, E);
-            GF_TRY(launch_gemm_nt(sv + so.attn_o, E, P + lo.out_w, E, tmp, E, T, E, E, EPI_NONE, ea, st, &osplits, TE));
-            GF_TRY(launch_add_drop_ln_fwd(Xcur, tmp, P + lo.n1w, P + lo.n1b, sv + so.x1, sv + so.xhat1, sv + so.rstd1, T, E,
-                                          c->ln_eps, c->p_enc, site + 1, rng, add, train, st, osplits, TE));
-        }
-        // FFN: h = drop(relu(x1 W1^T + b1)); y = h W2^T + b2
-        int splits = 1;
-        {
-            EpiArgs e1;
-            e1.bias = P + lo.b1; e1.p = c->p_enc; e1.site = site + 2; e1.rng = rng; e1.rng_add = add; e1.train = train;
-            if (saved) e1.mask_out = reinterpret_cast<uint16_t*>(sv + so.hmask);     // the pattern the linear2 dgrad will ask for
-            GF_TRY(launch_gemm_nt(sv + so.x1, E, P + lo.w1, E, sv + so.h, F, T, F, E, EPI_RELU_DROP, e1, st));
-            if (n100_supported(E, F) && !md.n100_off()) {
-                splits = MAX_SPLITS;                   // K chunks = output slabs, summed by the LayerNorm kernel
-                GF_TRY(launch_gemm_n100(sv + so.h, F, P + lo.w2, F, 0, P + lo.b2, tmp, TE, T, F, &splits, st));
-            } else {
-                ea.bias = P + lo.b2;
-                splits = gemm_splitk_factor(T, E, F);      // few output tiles, K = 2048: split K, LN sums the slabs
-                GF_TRY(launch_gemm_nt(sv + so.h, F, P + lo.w2, F, tmp, E, T, E, F, EPI_NONE, ea, st, &splits, TE));
-            }
-        }
-        if (rc) {
-            // LN2, then (all but the last layer) qkv of layer l + 1 from the fresh rows while they are in the workgroup
-            const float* Pn = (l + 1 < L) ? P + lo.total : nullptr;
-            GF_TRY(launch_rc_ln_inproj_fwd(tmp, splits, TE, sv + so.x1, P + lo.n2w, P + lo.n2b, Xnext, sv + so.xhat2, sv + so.rstd2,
-                                           Pn ? Pn + lo.in_w : nullptr, Pn ? Pn + lo.in_b : nullptr,
-                                           Pn ? layer_saved(l + 1) + so.qkv : nullptr, T, c->ln_eps, c->p_enc, site + 3, rng, add,
-                                           train, st));
-        } else {
-            GF_TRY(launch_add_drop_ln_fwd(sv + so.x1, tmp, P + lo.n2w, P + lo.n2b, Xnext, sv + so.xhat2, sv + so.rstd2, T, E,
-                                          c->ln_eps, c->p_enc, site + 3, rng, add, train, st, splits, TE));
-        }
-        Xcur = Xnext;
-    }
-    return 0;
+    const FwdSeg s0 = saved ? saved_seg(c, so, saved, workspace, out, c->train) : unsaved_seg(c, so, workspace, out, c->train);
+    return encoder_fwd_walk(c, key_len, flags, md, s0, nullptr, pe, x_in, params, rng, add, (hipStream_t)stream);
 }
 extern "C" int ganffn_encoder_fwd(const ganffn_enc_cfg* c, const float* x_in, const float* pe, const float* params,
                                   float* out, float* saved, float* workspace, const uint64_t* rng, uint64_t add,
@@ -302,18 +355,17 @@ extern "C" int ganffn_encoder_fwd_mask(const ganffn_enc_cfg* c, const int32_t* k
 // encoder stack forward over two row segments: the eval-mode pass (nothing kept) and the train-mode pass (saved for the
 // backward) of ONE stack over the SAME input.  In the GAN schedule every discriminator sub-step runs its partner generator
 // in eval mode and the next sub-step runs that generator in train mode on the same batch with the same parameters; here the
-// two passes share their launches.  Every forward kernel has a two-segment form (rowchain.hip, attention16.hip,
-// attention.hip, gemm.hip's generic and weight-resident kernels, gemm_n100.hip, elementwise.hip's PE and LayerNorm
-// kernels) in which a workgroup picks its segment from its index and then does what a workgroup of the single-segment launch
-// does, so each output has the bits ganffn_encoder_fwd gives it.  The launch sequence is ganffn_encoder_fwd's; every rule
-// that picks a summation order (split-K factors, K chunks of gemm_n100) is evaluated for T = S B, one segment's rows.
+// two passes are the two segments of one encoder_fwd_walk.  Segment 0 is the unsaved segment of ganffn_encoder_fwd at the
+// head of the workspace with train = 0, segment 1 the saved segment over saved_train with its slabs behind segment 0's
+// workspace.  In a two-segment kernel a workgroup picks its segment from its index and then does what a workgroup of the
+// single-segment launch does, so each output has the bits ganffn_encoder_fwd gives it.
 // ------------------------------------------------------------------------------------------
 static bool pair_supported(const ganffn_enc_cfg* c, const Mode md) {
     // every width has its segment forms; of gemm_n100's variants only the product one (eight waves, 4x4x1 tail), not the lab ones
     if (n100_supported(c->E, c->F) && !md.n100_off() && (md.n100_pad7() || md.n100_force_kw() == 1)) return false;
     return true;
 }
-// eval segment: the unsaved forward's workspace layout (X ping-pong | one layer's saved set | slabs); then the train segment's slabs
+// segment 0's part of the workspace (unsaved_seg: X ping-pong | one layer's saved set | slabs); then segment 1's slabs
 static int64_t pair_eval_ws_floats(const ganffn_enc_cfg* c) {
     const int64_t TE = (int64_t)c->S * c->B * c->E;
     return 2 * TE + saved_off(c).per_layer + MAX_SPLITS * TE;
@@ -326,7 +378,6 @@ extern "C" int64_t ganffn_encoder_fwd_pair_workspace_floats(const ganffn_enc_cfg
     if (check_cfg(c) != 0) return -1;
     return pair_eval_ws_floats(c) + (int64_t)MAX_SPLITS * c->S * c->B * c->E + 64;
 }
-// key_len (or null): handed to the attention of every layer; both segments are the same B dialogues, so one [B] array serves both
 static int encoder_fwd_pair_impl(const ganffn_enc_cfg* c, const int32_t* key_len, const float* x_in, const float* pe,
                                  const float* params, float* out_eval, float* out_train, float* saved_train, float* workspace,
                                  const uint64_t* rng, uint64_t add_train, void* stream) {
@@ -337,103 +388,11 @@ static int encoder_fwd_pair_impl(const ganffn_enc_cfg* c, const int32_t* key_len
     GF_CHECK_ARG(x_in && pe && params && out_eval && out_train && saved_train && workspace, "encoder_fwd_pair: null pointer");
     GF_CHECK_ARG(aligned16(x_in) && aligned16(params) && aligned16(out_eval) && aligned16(out_train) && aligned16(saved_train) &&
                      aligned16(workspace), "encoder_fwd_pair: buffers must be 16-byte aligned");
-    const int train = c->train;
-    GF_CHECK_ARG(!(train && (c->p_pe > 0.f || c->p_enc > 0.f)) || rng, "encoder_fwd_pair: rng required in train mode");
-    hipStream_t st = (hipStream_t)stream;
-    const int S = c->S, B = c->B, E = c->E, H = c->H, F = c->F, L = c->L, T = S * B;
-    const int64_t TE = (int64_t)T * E;
-    const LayerOff lo = layer_off(E, F);
+    GF_CHECK_ARG(!(c->train && (c->p_pe > 0.f || c->p_enc > 0.f)) || rng, "encoder_fwd_pair: rng required in train mode");
     const SavedOff so = saved_off(c);
-    const uint64_t add = add_train;
-
-    // segment 0 (eval, train flag 0 in every launch) lives in the workspace as in the unsaved ganffn_encoder_fwd, segment 1
-    // (train) in its saved buffer; tmp0 / tmp1: the GEMM output slabs before a LayerNorm
-    float* const tmp0 = workspace + 2 * TE + so.per_layer;
-    float* const tmp1 = workspace + pair_eval_ws_floats(c);
-    float* const sv0 = workspace + 2 * TE;
-    auto sv1 = [&](int l) { return saved_train + so.layers + (int64_t)l * so.per_layer; };
-    float* X0 = workspace;
-    float* X1 = saved_train + so.X;
-    const bool rc = rc_supported(E) && !md.rc_off();
-    if (rc && !md.pe_off()) {
-        RcFwdSeg1 s1{};
-        s1.y = pe; s1.x = x_in; s1.out = X1; s1.post_out = sv1(0) + so.qkv; s1.train = train;
-        GF_TRY(launch_rc_pe_inproj_fwd(x_in, pe, X0, params + lo.in_w, params + lo.in_b, sv0 + so.qkv, T, B, c->p_pe, rng, add, 0, st,
-                                       &s1));
-    } else {
-        GF_TRY(launch_pe_dropout(x_in, pe, X0, S, B, E, c->p_pe, rng, add, 0, st, X1, train));
-        if (rc) {
-            EpiArgs e0;
-            e0.bias = params + lo.in_b;
-            const GemmSeg1 g1{X1, sv1(0) + so.qkv, nullptr, train};
-            GF_TRY(launch_gemm_nt_pair(X0, E, params + lo.in_w, E, sv0 + so.qkv, 3 * E, T, 3 * E, E, EPI_NONE, e0, g1, st));
-        }
-    }
-    for (int l = 0; l < L; ++l) {
-        const float* P = params + (int64_t)l * lo.total;
-        float* const s1v = sv1(l);
-        float* Xn0 = (l == L - 1) ? out_eval : workspace + ((l & 1) ? 0 : TE);
-        float* Xn1 = (l == L - 1) ? out_train : saved_train + so.X + (int64_t)(l + 1) * TE;
-        const uint32_t site = SITE_LAYER0 + 4 * l;
-        EpiArgs ea;
-        ea.bias = P + lo.in_b;
-        if (!rc) {
-            const GemmSeg1 g1{X1, s1v + so.qkv, nullptr, train};
-            GF_TRY(launch_gemm_nt_pair(X0, E, P + lo.in_w, E, sv0 + so.qkv, 3 * E, T, 3 * E, E, EPI_NONE, ea, g1, st));
-        }
-        {
-            const AttnFwdSeg1 a1{s1v + so.qkv, s1v + so.attn_o, s1v + so.lse, reinterpret_cast<uint32_t*>(s1v + so.keep), train};
-            GF_TRY(launch_attention_fwd(sv0 + so.qkv, sv0 + so.attn_o, sv0 + so.lse, nullptr, S, B, E, H, c->p_enc, site + 0, rng, add, 0,
-                                        st, &a1, key_len));
-        }
-        if (rc) {
-            RcFwdSeg1 s1{};
-            s1.pre_a = s1v + so.attn_o; s1.x = X1; s1.out = s1v + so.x1; s1.xhat = s1v + so.xhat1; s1.rstd = s1v + so.rstd1;
-            s1.train = train;
-            GF_TRY(launch_rc_outproj_ln_fwd(sv0 + so.attn_o, P + lo.out_w, P + lo.out_b, X0, P + lo.n1w, P + lo.n1b, sv0 + so.x1,
-                                            sv0 + so.xhat1, sv0 + so.rstd1, T, c->ln_eps, c->p_enc, site + 1, rng, add, 0, st, &s1));
-        } else {
-            ea.bias = P + lo.out_b;
-            int osplits = md.outproj_nosplit() ? 1 : gemm_splitk_factor(T, E, E);      // (T: one segment's rows)
-            const GemmSeg1 g1{s1v + so.attn_o, tmp1, nullptr, train};
-            GF_TRY(launch_gemm_nt_pair(sv0 + so.attn_o, E, P + lo.out_w, E, tmp0, E, T, E, E, EPI_NONE, ea, g1, st, &osplits, TE));
-            const LnFwdSeg1 n1{X1, tmp1, s1v + so.x1, s1v + so.xhat1, s1v + so.rstd1, train};
-            GF_TRY(launch_add_drop_ln_fwd(X0, tmp0, P + lo.n1w, P + lo.n1b, sv0 + so.x1, sv0 + so.xhat1, sv0 + so.rstd1, T, E, c->ln_eps,
-                                          c->p_enc, site + 1, rng, add, 0, st, osplits, TE, &n1));
-        }
-        int splits = 1;
-        {
-            EpiArgs e1;
-            e1.bias = P + lo.b1; e1.p = c->p_enc; e1.site = site + 2; e1.rng = rng; e1.rng_add = add; e1.train = 0;
-            const GemmSeg1 g1{s1v + so.x1, s1v + so.h, reinterpret_cast<uint16_t*>(s1v + so.hmask), train};
-            GF_TRY(launch_gemm_nt_pair(sv0 + so.x1, E, P + lo.w1, E, sv0 + so.h, F, T, F, E, EPI_RELU_DROP, e1, g1, st));
-            if (n100_supported(E, F) && !md.n100_off()) {
-                splits = MAX_SPLITS;
-                GF_TRY(launch_gemm_n100(sv0 + so.h, F, P + lo.w2, F, 0, P + lo.b2, tmp0, TE, T, F, &splits, st, s1v + so.h, tmp1));
-            } else {
-                ea.bias = P + lo.b2;
-                splits = gemm_splitk_factor(T, E, F);
-                const GemmSeg1 g2{s1v + so.h, tmp1, nullptr, train};
-                GF_TRY(launch_gemm_nt_pair(sv0 + so.h, F, P + lo.w2, F, tmp0, E, T, E, F, EPI_NONE, ea, g2, st, &splits, TE));
-            }
-        }
-        if (rc) {
-            const float* Pn = (l + 1 < L) ? P + lo.total : nullptr;
-            RcFwdSeg1 s1{};
-            s1.y = tmp1; s1.x = s1v + so.x1; s1.out = Xn1; s1.xhat = s1v + so.xhat2; s1.rstd = s1v + so.rstd2;
-            s1.post_out = Pn ? sv1(l + 1) + so.qkv : nullptr; s1.train = train;
-            GF_TRY(launch_rc_ln_inproj_fwd(tmp0, splits, TE, sv0 + so.x1, P + lo.n2w, P + lo.n2b, Xn0, sv0 + so.xhat2, sv0 + so.rstd2,
-                                           Pn ? Pn + lo.in_w : nullptr, Pn ? Pn + lo.in_b : nullptr, Pn ? sv0 + so.qkv : nullptr, T,
-                                           c->ln_eps, c->p_enc, site + 3, rng, add, 0, st, &s1));
-        } else {
-            const LnFwdSeg1 n2{s1v + so.x1, tmp1, Xn1, s1v + so.xhat2, s1v + so.rstd2, train};
-            GF_TRY(launch_add_drop_ln_fwd(sv0 + so.x1, tmp0, P + lo.n2w, P + lo.n2b, Xn0, sv0 + so.xhat2, sv0 + so.rstd2, T, E, c->ln_eps,
-                                          c->p_enc, site + 3, rng, add, 0, st, splits, TE, &n2));
-        }
-        X0 = Xn0;
-        X1 = Xn1;
-    }
-    return 0;
+    const FwdSeg s0 = unsaved_seg(c, so, workspace, out_eval, 0);
+    const FwdSeg s1 = saved_seg(c, so, saved_train, workspace + pair_eval_ws_floats(c), out_train, c->train);
+    return encoder_fwd_walk(c, key_len, 0, md, s0, &s1, pe, x_in, params, rng, add_train, (hipStream_t)stream);
 }
 
 extern "C" int ganffn_encoder_fwd_pair(const ganffn_enc_cfg* c, const float* x_in, const float* pe, const float* params,
@@ -450,66 +409,9 @@ extern "C" int ganffn_encoder_fwd_pair_len(const ganffn_enc_cfg* c, const int32_
 // ------------------------------------------------------------------------------------------
 // encoder stack backward over layers [lo_l, hi_l)
 // ------------------------------------------------------------------------------------------
-extern "C" int ganffn_encoder_bwd2(const ganffn_enc_cfg* c, int layer_lo, int layer_hi, float* dx, const float* params,
-                                   float* grads, const float* saved, float* workspace, const uint64_t* rng, uint64_t add,
-                                   int need_dx_in, void* stream);
-extern "C" int ganffn_encoder_bwd(const ganffn_enc_cfg* c, int layer_lo, int layer_hi, float* dx, const float* params,
-                                  float* grads, const float* saved, float* workspace, const uint64_t* rng, uint64_t add,
-                                  void* stream) {
-    return ganffn_encoder_bwd2(c, layer_lo, layer_hi, dx, params, grads, saved, workspace, rng, add, 1, stream);
-}
 static int encoder_bwd_impl(const ganffn_enc_cfg* c, int layer_lo, int layer_hi, float* dx, const float* params,
                             float* grads, const float* saved, float* workspace, const uint64_t* rng, uint64_t add,
-                            int need_dx_in, void* stream, TnSlabs* slabs, const int32_t* key_len = nullptr, uint32_t flags = 0);
-extern "C" int ganffn_encoder_bwd2(const ganffn_enc_cfg* c, int layer_lo, int layer_hi, float* dx, const float* params,
-                                   float* grads, const float* saved, float* workspace, const uint64_t* rng, uint64_t add,
-                                   int need_dx_in, void* stream) {
-    return encoder_bwd_impl(c, layer_lo, layer_hi, dx, params, grads, saved, workspace, rng, add, need_dx_in, stream, nullptr);
-}
-extern "C" int ganffn_encoder_bwd_len(const ganffn_enc_cfg* c, const int32_t* key_len, int layer_lo, int layer_hi, float* dx,
-                                      const float* params, float* grads, const float* saved, float* workspace, const uint64_t* rng,
-                                      uint64_t add, int need_dx_in, void* stream) {
-    return encoder_bwd_impl(c, layer_lo, layer_hi, dx, params, grads, saved, workspace, rng, add, need_dx_in, stream, nullptr, key_len);
-}
-extern "C" int ganffn_encoder_bwd_mask(const ganffn_enc_cfg* c, const int32_t* key_len, uint32_t flags, int layer_lo, int layer_hi,
-                                       float* dx, const float* params, float* grads, const float* saved, float* workspace,
-                                       const uint64_t* rng, uint64_t add, int need_dx_in, void* stream) {
-    return encoder_bwd_impl(c, layer_lo, layer_hi, dx, params, grads, saved, workspace, rng, add, need_dx_in, stream, nullptr, key_len,
-                            flags);
-}
-// does ganffn_encoder_bwd_parts leave the weight gradients of this stack unreduced?  (d_model 100 on the rowchain / tn100 kernels,
-// at most 10 layers: one grouped weight-gradient launch for the whole pass)
-static bool bwd_parts_supported(const ganffn_enc_cfg* c, const Mode md) {
-    return rc_supported(c->E) && !md.rc_off() && !md.tn100_off() && !md.tn100_in_kernel_sum() && !md.adam_slabs_off() && c->F == 2048 &&
-           4 * c->L <= 40;
-}
-extern "C" int ganffn_encoder_bwd_parts_supported(const ganffn_enc_cfg* c) {
-    if (check_cfg(c) != 0) return -1;
-    return bwd_parts_supported(c, mode()) ? 1 : 0;
-}
-extern "C" int64_t ganffn_encoder_bwd_parts_covered(int E, int F) { return layer_off(E, F).n1w; }
-extern "C" int ganffn_encoder_bwd_parts_len(const ganffn_enc_cfg* c, const int32_t* key_len, float* dx, const float* params,
-                                            float* grads, const float* saved, float* workspace, const uint64_t* rng, uint64_t add,
-                                            int need_dx_in, int64_t* part_offset, int64_t* part_stride, int* n_parts, void* stream) {
-    GF_TRY(check_cfg(c));
-    GF_CHECK_ARG(grads && part_offset && part_stride && n_parts, "encoder_bwd_parts: null pointer");
-    GF_CHECK_ARG(bwd_parts_supported(c, mode()), "encoder_bwd_parts: this stack's weight gradients are reduced in the launch (ask ganffn_encoder_bwd_parts_supported)");
-    TnSlabs sl{grads, (long)c->L * layer_off(c->E, c->F).total, 1, nullptr, 0};
-    GF_TRY(encoder_bwd_impl(c, 0, c->L, dx, params, grads, saved, workspace, rng, add, need_dx_in, stream, &sl, key_len));
-    *n_parts = sl.n_parts;
-    *part_offset = sl.part ? sl.part - workspace : 0;
-    *part_stride = sl.part_stride;
-    return 0;
-}
-extern "C" int ganffn_encoder_bwd_parts(const ganffn_enc_cfg* c, float* dx, const float* params, float* grads, const float* saved,
-                                        float* workspace, const uint64_t* rng, uint64_t add, int need_dx_in, int64_t* part_offset,
-                                        int64_t* part_stride, int* n_parts, void* stream) {
-    return ganffn_encoder_bwd_parts_len(c, nullptr, dx, params, grads, saved, workspace, rng, add, need_dx_in, part_offset, part_stride,
-                                        n_parts, stream);
-}
-static int encoder_bwd_impl(const ganffn_enc_cfg* c, int layer_lo, int layer_hi, float* dx, const float* params,
-                            float* grads, const float* saved, float* workspace, const uint64_t* rng, uint64_t add,
-                            int need_dx_in, void* stream, TnSlabs* slabs, const int32_t* key_len, uint32_t flags) {
+                            int need_dx_in, void* stream, TnSlabs* slabs, const int32_t* key_len = nullptr, uint32_t flags = 0) {
     const Mode md = mode();
     GF_TRY(check_cfg(c));
     GF_CHECK_ARG((flags & ~GANFFN_ATTN_CAUSAL) == 0, "encoder_bwd: unknown flag bits 0x%x", flags & ~GANFFN_ATTN_CAUSAL);
@@ -650,6 +552,57 @@ static int encoder_bwd_impl(const ganffn_enc_cfg* c, int layer_lo, int layer_hi,
     if (nred > 0) GF_TRY(launch_ln_param_reduce(nred, r_gw, r_gb, r_part, r_nb, E, st, slabs != nullptr));
     if (layer_lo == 0 && need_dx_in) GF_TRY(launch_dropout_bwd_inplace(dx, T, E, c->p_pe, SITE_PE, rng, add, train, st));
     return 0;
+}
+extern "C" int ganffn_encoder_bwd2(const ganffn_enc_cfg* c, int layer_lo, int layer_hi, float* dx, const float* params,
+                                   float* grads, const float* saved, float* workspace, const uint64_t* rng, uint64_t add,
+                                   int need_dx_in, void* stream) {
+    return encoder_bwd_impl(c, layer_lo, layer_hi, dx, params, grads, saved, workspace, rng, add, need_dx_in, stream, nullptr);
+}
+extern "C" int ganffn_encoder_bwd(const ganffn_enc_cfg* c, int layer_lo, int layer_hi, float* dx, const float* params,
+                                  float* grads, const float* saved, float* workspace, const uint64_t* rng, uint64_t add,
+                                  void* stream) {
+    return ganffn_encoder_bwd2(c, layer_lo, layer_hi, dx, params, grads, saved, workspace, rng, add, 1, stream);
+}
+extern "C" int ganffn_encoder_bwd_len(const ganffn_enc_cfg* c, const int32_t* key_len, int layer_lo, int layer_hi, float* dx,
+                                      const float* params, float* grads, const float* saved, float* workspace, const uint64_t* rng,
+                                      uint64_t add, int need_dx_in, void* stream) {
+    return encoder_bwd_impl(c, layer_lo, layer_hi, dx, params, grads, saved, workspace, rng, add, need_dx_in, stream, nullptr, key_len);
+}
+extern "C" int ganffn_encoder_bwd_mask(const ganffn_enc_cfg* c, const int32_t* key_len, uint32_t flags, int layer_lo, int layer_hi,
+                                       float* dx, const float* params, float* grads, const float* saved, float* workspace,
+                                       const uint64_t* rng, uint64_t add, int need_dx_in, void* stream) {
+    return encoder_bwd_impl(c, layer_lo, layer_hi, dx, params, grads, saved, workspace, rng, add, need_dx_in, stream, nullptr, key_len,
+                            flags);
+}
+// does ganffn_encoder_bwd_parts leave the weight gradients of this stack unreduced?  (d_model 100 on the rowchain / tn100 kernels,
+// at most 10 layers: one grouped weight-gradient launch for the whole pass)
+static bool bwd_parts_supported(const ganffn_enc_cfg* c, const Mode md) {
+    return rc_supported(c->E) && !md.rc_off() && !md.tn100_off() && !md.tn100_in_kernel_sum() && !md.adam_slabs_off() && c->F == 2048 &&
+           4 * c->L <= 40;
+}
+extern "C" int ganffn_encoder_bwd_parts_supported(const ganffn_enc_cfg* c) {
+    if (check_cfg(c) != 0) return -1;
+    return bwd_parts_supported(c, mode()) ? 1 : 0;
+}
+extern "C" int64_t ganffn_encoder_bwd_parts_covered(int E, int F) { return layer_off(E, F).n1w; }
+extern "C" int ganffn_encoder_bwd_parts_len(const ganffn_enc_cfg* c, const int32_t* key_len, float* dx, const float* params,
+                                            float* grads, const float* saved, float* workspace, const uint64_t* rng, uint64_t add,
+                                            int need_dx_in, int64_t* part_offset, int64_t* part_stride, int* n_parts, void* stream) {
+    GF_TRY(check_cfg(c));
+    GF_CHECK_ARG(grads && part_offset && part_stride && n_parts, "encoder_bwd_parts: null pointer");
+    GF_CHECK_ARG(bwd_parts_supported(c, mode()), "encoder_bwd_parts: this stack's weight gradients are reduced in the launch (ask ganffn_encoder_bwd_parts_supported)");
+    TnSlabs sl{grads, (long)c->L * layer_off(c->E, c->F).total, 1, nullptr, 0};
+    GF_TRY(encoder_bwd_impl(c, 0, c->L, dx, params, grads, saved, workspace, rng, add, need_dx_in, stream, &sl, key_len));
+    *n_parts = sl.n_parts;
+    *part_offset = sl.part ? sl.part - workspace : 0;
+    *part_stride = sl.part_stride;
+    return 0;
+}
+extern "C" int ganffn_encoder_bwd_parts(const ganffn_enc_cfg* c, float* dx, const float* params, float* grads, const float* saved,
+                                        float* workspace, const uint64_t* rng, uint64_t add, int need_dx_in, int64_t* part_offset,
+                                        int64_t* part_stride, int* n_parts, void* stream) {
+    return ganffn_encoder_bwd_parts_len(c, nullptr, dx, params, grads, saved, workspace, rng, add, need_dx_in, part_offset, part_stride,
+                                        n_parts, stream);
 }
 
 // ------------------------------------------------------------------------------------------

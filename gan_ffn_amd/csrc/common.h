@@ -264,17 +264,16 @@ struct EpiArgs {
 
 inline long epi_mask_words(long M, long N) { return ((M + 31) / 32) * N * 2; }
 
-// C[MxN] = A[MxK] * W[NxK]^T (NT)
-int launch_gemm_nt(const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N, int K,
-                   int epi, const EpiArgs& ea, hipStream_t st, int* splits_io = nullptr, long slab_stride = 0);
-int gemm_splitk_factor(int M, int N, int K);
 // second row segment of a two-segment launch_gemm_nt (EPI_NONE, also split-K, or EPI_RELU_DROP): its input rows, output (slabs
 // at the same stride), pattern words (may be null) and train flag
 struct GemmSeg1 {
     const float* A; float* C; uint16_t* mask_out; int train;
 };
-int launch_gemm_nt_pair(const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N, int K, int epi,
-                        const EpiArgs& ea, const GemmSeg1& s1, hipStream_t st, int* splits_io = nullptr, long slab_stride = 0);
+// C[MxN] = A[MxK] * W[NxK]^T (NT); s1 (optional): the same product for a second row segment in the same launch
+int launch_gemm_nt(const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N, int K,
+                   int epi, const EpiArgs& ea, hipStream_t st, int* splits_io = nullptr, long slab_stride = 0,
+                   const GemmSeg1* s1 = nullptr);
+int gemm_splitk_factor(int M, int N, int K);
 // C[MxN] = A[MxK] * B[KxN] (NN)
 int launch_gemm_nn(const float* A, int lda, const float* Bm, int ldb, float* C, int ldc, int M, int N, int K,
                    int epi, const EpiArgs& ea, hipStream_t st, int* splits_io = nullptr, long slab_stride = 0);

@@ -1135,53 +1135,51 @@ __global__ __launch_bounds__(256) void gemm_tn_grouped_kernel(TnGroup grp) {
     gemm_body<MODE_TN, 64, BN, 16, EPI_NONE, 2, 2>(g, nt, mt, bz);
 }
 
+// the kernels with a two-segment form (gemm_pair_kernel; of the weight-resident kernel, linear1's epilogue only)
+template <int MODE, int EPI>
+constexpr bool HAS_PAIR = MODE == MODE_NT && (EPI == EPI_NONE || EPI == EPI_RELU_DROP);
+
+// s1 (or null): the second row segment — the same tiles again along grid y, for s1's operands
 template <int MODE, int BM, int BN, int BK, int EPI, int WGM = 2, int WGN = 2, int SHORTK = 0>
-static int launch_cfg(const GemmArgs& g, int splits, hipStream_t st) {
-    dim3 grid((g.N + BN - 1) / BN, (g.M + BM - 1) / BM, splits);
+static int launch_cfg(const GemmArgs& g, int splits, hipStream_t st, const GemmSeg1* s1 = nullptr) {
+    const int gy0 = (g.M + BM - 1) / BM;
+    dim3 grid((g.N + BN - 1) / BN, gy0, splits);
     constexpr size_t lds = Smem<MODE, BM, BN, BK>::TOTAL * sizeof(float);
+    if constexpr (HAS_PAIR<MODE, EPI>) {
+        if (s1) {
+            grid.y = 2 * gy0;
+            GF_TRY((lds_optin<gemm_pair_kernel<MODE, BM, BN, BK, EPI, WGM, WGN, SHORTK>>(lds, "gemm")));
+            hipLaunchKernelGGL((gemm_pair_kernel<MODE, BM, BN, BK, EPI, WGM, WGN, SHORTK>), grid, dim3(64 * WGM * WGN), lds, st, g, *s1, gy0);
+            GF_LAUNCH_CHECK();
+            return 0;
+        }
+    }
     GF_TRY((lds_optin<gemm_kernel<MODE, BM, BN, BK, EPI, WGM, WGN, SHORTK>>(lds, "gemm")));
     hipLaunchKernelGGL((gemm_kernel<MODE, BM, BN, BK, EPI, WGM, WGN, SHORTK>), grid, dim3(64 * WGM * WGN), lds, st, g);
     GF_LAUNCH_CHECK();
     return 0;
 }
 
-template <int MODE, int BM, int BN, int BK, int EPI, int WGM = 2, int WGN = 2, int SHORTK = 0>
-static int launch_cfg_pair(const GemmArgs& g, const GemmSeg1& s1, int splits, hipStream_t st) {
-    const int gy0 = (g.M + BM - 1) / BM;
-    dim3 grid((g.N + BN - 1) / BN, 2 * gy0, splits);
-    constexpr size_t lds = Smem<MODE, BM, BN, BK>::TOTAL * sizeof(float);
-    GF_TRY((lds_optin<gemm_pair_kernel<MODE, BM, BN, BK, EPI, WGM, WGN, SHORTK>>(lds, "gemm")));
-    hipLaunchKernelGGL((gemm_pair_kernel<MODE, BM, BN, BK, EPI, WGM, WGN, SHORTK>), grid, dim3(64 * WGM * WGN), lds, st, g, s1, gy0);
-    GF_LAUNCH_CHECK();
-    return 0;
-}
-
-// the two-segment launch of the kernel launch_pick takes for one segment's shape
-template <int EPI>
-static int launch_pick_pair(const GemmArgs& g, const GemmSeg1& s1, int splits, hipStream_t st) {
-    if (g.K == 100 && g.N >= 1024 && splits == 1 && (g.lda & 3) == 0 && (g.ldb & 3) == 0 &&
-        (size_t)g.M * g.lda * 4 < (size_t(1) << 31) && (size_t)g.M * g.ldc * 4 < (size_t(1) << 31)) {
-        if constexpr (EPI == EPI_RELU_DROP) return launch_wres<MODE_NT, EPI, true>(g, st, &s1);
-        else return fail(-1, "gemm_nt_pair: no two-segment form of the weight-resident kernel for epilogue %d", EPI);
-    }
-    if (g.K <= 128) return launch_cfg_pair<MODE_NT, 64, 64, 16, EPI, 2, 2, 1>(g, s1, splits, st);
-    return launch_cfg_pair<MODE_NT, 64, 64, 16, EPI>(g, s1, splits, st);
-}
-
+// s1 (or null): the second segment goes to the two-segment form of the kernel that one segment's shape takes
 template <int MODE, int EPI>
-static int launch_pick(const GemmArgs& g, int splits, hipStream_t st) {
+static int launch_pick(const GemmArgs& g, int splits, hipStream_t st, const GemmSeg1* s1 = nullptr) {
+    if constexpr (!HAS_PAIR<MODE, EPI>)
+        if (s1) return fail(-1, "gemm_nt_pair: epilogue %d has no two-segment form", EPI);
     // measured on MI355X (tools/gemm_bench.py, M = 3008 / 6016, N = 100 .. 2048, K = 100 .. 2048): with the
     // straight-line K loop the 4-wave 64x64x16 block is the fastest or within 2 % of the fastest of every block /
     // wave-tile shape tried (64x64x32, 128x64, 64x128, 128x128 with 2, 4, 8 or 16 waves), so it is the only one used.
     if constexpr (MODE != MODE_TN)
         if (g.K == 100 && g.N >= 1024 && splits == 1 && (g.lda & 3) == 0 && ((MODE == MODE_NT) ? (g.ldb & 3) == 0 : true) &&
-            (size_t)g.M * g.lda * 4 < (size_t(1) << 31) && (size_t)g.M * g.ldc * 4 < (size_t(1) << 31))   // 32-bit buffer offsets
-            return launch_wres<MODE, EPI>(g, st);
-    if (g.K <= 128) return launch_cfg<MODE, 64, 64, 16, EPI, 2, 2, 1>(g, splits, st);
+            (size_t)g.M * g.lda * 4 < (size_t(1) << 31) && (size_t)g.M * g.ldc * 4 < (size_t(1) << 31)) {   // 32-bit buffer offsets
+            if (!s1) return launch_wres<MODE, EPI>(g, st);
+            if constexpr (MODE == MODE_NT && EPI == EPI_RELU_DROP) return launch_wres<MODE, EPI, true>(g, st, s1);
+            else return fail(-1, "gemm_nt_pair: no two-segment form of the weight-resident kernel for epilogue %d", EPI);
+        }
+    if (g.K <= 128) return launch_cfg<MODE, 64, 64, 16, EPI, 2, 2, 1>(g, splits, st, s1);
     // (64 x 128 tiles for the N = 2048, K = 512 products: 5-9 % faster in isolation, round 2; in the 3-stream step 35.9 against
     // 35.7 ms with 64 x 64 — fewer, fatter workgroups co-run worse — so they are not used; round 3, tools/lab/mode_ab.py;
     // re-measured in round 4 with tuned streams and the XCD-aware tile order: 34.71 against 34.43 ms, three interleaved runs each)
-    return launch_cfg<MODE, 64, 64, 16, EPI>(g, splits, st);
+    return launch_cfg<MODE, 64, 64, 16, EPI>(g, splits, st, s1);
 }
 
 // the K loop reads its operands through buffer descriptors with 32-bit byte offsets (round 5): an operand must span < 4 GiB
@@ -1195,15 +1193,15 @@ static int check_common(const float* A, int lda, const float* B, int ldb, const 
     return 0;
 }
 
-#define EPI_SWITCH(MODE, g, st)                                                            \
+#define EPI_SWITCH(MODE, g, st, s1)                                                        \
     switch (epi) {                                                                         \
-        case EPI_NONE: return launch_pick<MODE, EPI_NONE>(g, splits, st);                  \
-        case EPI_RELU_DROP: return launch_pick<MODE, EPI_RELU_DROP>(g, 1, st);             \
-        case EPI_DROP_GELU: return launch_pick<MODE, EPI_DROP_GELU>(g, 1, st);             \
-        case EPI_MASK_POS: return launch_pick<MODE, EPI_MASK_POS>(g, 1, st);               \
+        case EPI_NONE: return launch_pick<MODE, EPI_NONE>(g, splits, st, s1);              \
+        case EPI_RELU_DROP: return launch_pick<MODE, EPI_RELU_DROP>(g, 1, st, s1);         \
+        case EPI_DROP_GELU: return launch_pick<MODE, EPI_DROP_GELU>(g, 1, st, s1);         \
+        case EPI_MASK_POS: return launch_pick<MODE, EPI_MASK_POS>(g, 1, st, s1);           \
         case EPI_GELU_BWD_DROP:                                                            \
-        case EPI_GELU_BWD_DROP0: return launch_pick<MODE, EPI_GELU_BWD_DROP>(g, 1, st);    \
-        case EPI_GELU_BWD: return launch_pick<MODE, EPI_GELU_BWD>(g, 1, st);               \
+        case EPI_GELU_BWD_DROP0: return launch_pick<MODE, EPI_GELU_BWD_DROP>(g, 1, st, s1);\
+        case EPI_GELU_BWD: return launch_pick<MODE, EPI_GELU_BWD>(g, 1, st, s1);           \
         default: return fail(-1, "gemm: unknown epilogue %d", epi);                        \
     }
 
@@ -1228,33 +1226,20 @@ static void set_split(GemmArgs& g, int& splits, long slab_stride) {
 
 // splits > 1 (EPI_NONE only): split z writes its partial to C + z*slab_stride; the consumer sums the slabs.
 // *splits_io returns the number of slabs actually written.
-int launch_gemm_nt(const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N, int K,
-                   int epi, const EpiArgs& ea, hipStream_t st, int* splits_io, long slab_stride) {
-    GF_TRY(check_common(A, lda, W, ldw, C, M, N, K));
-    GF_CHECK_ARG((K & 3) == 0, "gemm_nt: K=%d must be a multiple of 4", K);
-    GF_CHECK_ARG(fits32(M, lda) && fits32(N, ldw), "gemm_nt: an operand of 4 GiB or more is not supported");
-    GemmArgs g{A, lda, W, ldw, C, ldc, nullptr, M, N, K, K, 0, ea};
-    int splits = (splits_io && epi == EPI_NONE) ? *splits_io : 1;
-    set_split(g, splits, slab_stride);
-    if (splits_io) *splits_io = splits;
-    EPI_SWITCH(MODE_NT, g, st)
-}
-
-// launch_gemm_nt for two row segments [M x K] against the same weight in one launch (plain / split-K product and linear1's
+// s1 (or null): a second row segment [M x K] against the same weight in the same launch (plain / split-K product and linear1's
 // epilogue): segment 0 as given, segment 1 with s1's operands; the same kernel, K split and slab layout as for one segment
-int launch_gemm_nt_pair(const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N, int K, int epi,
-                        const EpiArgs& ea, const GemmSeg1& s1, hipStream_t st, int* splits_io, long slab_stride) {
-    GF_CHECK_ARG(epi == EPI_RELU_DROP || epi == EPI_NONE, "gemm_nt_pair: epilogue %d has no two-segment form", epi);
+int launch_gemm_nt(const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N, int K,
+                   int epi, const EpiArgs& ea, hipStream_t st, int* splits_io, long slab_stride, const GemmSeg1* s1) {
+    GF_CHECK_ARG(!s1 || epi == EPI_RELU_DROP || epi == EPI_NONE, "gemm_nt_pair: epilogue %d has no two-segment form", epi);
     GF_TRY(check_common(A, lda, W, ldw, C, M, N, K));
-    GF_CHECK_ARG(s1.A && s1.C && aligned16(s1.A) && ea.aux_in == nullptr, "gemm_nt_pair: bad second segment");
+    GF_CHECK_ARG(!s1 || (s1->A && s1->C && aligned16(s1->A) && ea.aux_in == nullptr), "gemm_nt_pair: bad second segment");
     GF_CHECK_ARG((K & 3) == 0, "gemm_nt: K=%d must be a multiple of 4", K);
     GF_CHECK_ARG(fits32(M, lda) && fits32(N, ldw), "gemm_nt: an operand of 4 GiB or more is not supported");
     GemmArgs g{A, lda, W, ldw, C, ldc, nullptr, M, N, K, K, 0, ea};
     int splits = (splits_io && epi == EPI_NONE) ? *splits_io : 1;
     set_split(g, splits, slab_stride);
     if (splits_io) *splits_io = splits;
-    if (epi == EPI_RELU_DROP) return launch_pick_pair<EPI_RELU_DROP>(g, s1, 1, st);
-    return launch_pick_pair<EPI_NONE>(g, s1, splits, st);
+    EPI_SWITCH(MODE_NT, g, st, s1)
 }
 
 int launch_gemm_nn(const float* A, int lda, const float* Bm, int ldb, float* C, int ldc, int M, int N, int K,
@@ -1266,7 +1251,7 @@ int launch_gemm_nn(const float* A, int lda, const float* Bm, int ldb, float* C, 
     int splits = (splits_io && epi == EPI_NONE) ? *splits_io : 1;
     set_split(g, splits, slab_stride);
     if (splits_io) *splits_io = splits;
-    EPI_SWITCH(MODE_NN, g, st)
+    EPI_SWITCH(MODE_NN, g, st, nullptr)
 }
 
 // A one- or two-tile gradient (the discriminator head's fc1 [64 x 100] / fc2 [16 x 64]) used to be cut into K / 64 = 94

@@ -28,10 +28,9 @@ def _case(S, B, E, H, L=2):
     return cfg, cfg_eval, params, x, pe
 
 
-@pytest.mark.parametrize("E,H", WIDTHS)
-@pytest.mark.parametrize("S,B", SHAPES)
-def test_pair_pass_equals_the_two_single_passes(S, B, E, H):
-    from gan_ffn_amd import ops
+def _pair_against_the_two_single_passes(S, B, E, H, mode=0, key_len=None):
+    """mode: the debug mode word (ganffn_debug_set_ffn_mode) all three calls run under; key_len: handed to all three"""
+    from gan_ffn_amd import _lib, ops
     cfg, cfg_eval, params, x, pe = _case(S, B, E, H)
     n_saved, n_ws = ops.enc_sizes(cfg)
     ops.manual_seed(4321)
@@ -42,20 +41,49 @@ def test_pair_pass_equals_the_two_single_passes(S, B, E, H):
     out_e, out_t = torch.zeros(S * B * E, **f32), torch.zeros(S * B * E, **f32)
     saved = torch.full((n_saved,), -7.0, **f32)
     ws = torch.zeros(n_ws, **f32)
-    ops.encoder_fwd_raw(cfg_eval, x, pe, params, out_e, None, ws, rng, add)
-    ops.encoder_fwd_raw(cfg, x, pe, params, out_t, saved, ws, rng, add)
     p_e, p_t = torch.zeros(S * B * E, **f32), torch.zeros(S * B * E, **f32)
     p_saved = torch.full((n_saved,), -7.0, **f32)
     p_ws = torch.zeros(ops.encoder_fwd_pair_workspace_floats(cfg), **f32)
-    # every width here has its two-segment forms under the default mode word (a width that lost them would have to be refused:
-    # test_a_lab_variant_without_a_segment_form_is_reported_and_refused) — asserted, so that none drops out of this comparison
-    assert ops.encoder_fwd_pair_supported(cfg)
-    ops.encoder_fwd_pair_raw(cfg, x, pe, params, p_e, p_t, p_saved, p_ws, rng, add)
-    torch.cuda.synchronize()
+    lib = _lib.load()
+    lib.ganffn_debug_set_ffn_mode(mode)
+    try:
+        ops.encoder_fwd_raw(cfg_eval, x, pe, params, out_e, None, ws, rng, add, key_len=key_len)
+        ops.encoder_fwd_raw(cfg, x, pe, params, out_t, saved, ws, rng, add, key_len=key_len)
+        # every width here has its two-segment forms under these mode words (a width that lost them would have to be refused:
+        # test_a_lab_variant_without_a_segment_form_is_reported_and_refused) — asserted, so that none drops out of this comparison
+        assert ops.encoder_fwd_pair_supported(cfg)
+        ops.encoder_fwd_pair_raw(cfg, x, pe, params, p_e, p_t, p_saved, p_ws, rng, add, key_len=key_len)
+        torch.cuda.synchronize()
+    finally:
+        lib.ganffn_debug_set_ffn_mode(0)
     assert torch.isfinite(out_e).all() and torch.isfinite(out_t).all() and not torch.equal(out_e, out_t)
     assert torch.equal(p_e, out_e)
     assert torch.equal(p_t, out_t)
     assert torch.equal(p_saved.view(torch.int32), saved.view(torch.int32))
+
+
+@pytest.mark.parametrize("E,H", WIDTHS)
+@pytest.mark.parametrize("S,B", SHAPES)
+def test_pair_pass_equals_the_two_single_passes(S, B, E, H):
+    _pair_against_the_two_single_passes(S, B, E, H)
+
+
+# the older launch sequences of the mode word (include/ganffn.h: bit 1 separate GEMM + LayerNorm launches, bit 2 generic tiles
+# for the 2048 -> 100 product, bit 6 PE and layer 0's in-proj as two launches, bit 24 the wide out-proj unsplit), each at the
+# width whose walk it changes; mode 0 at 512 is the split out-proj that bit 24 turns off
+OLDER_SEQUENCES = [(2, 100, 10), (4, 100, 10), (6, 100, 10), (64, 100, 10), (2 | 64, 100, 10), (1 << 24, 512, 8), (0, 512, 8)]
+
+
+@pytest.mark.parametrize("ragged", [False, True])
+@pytest.mark.parametrize("mode,E,H", OLDER_SEQUENCES)
+@pytest.mark.parametrize("S,B", [(7, 2), (9, 4)])
+def test_pair_pass_equals_the_two_single_passes_under_older_launch_sequences(S, B, mode, E, H, ragged):
+    """the pair pass and the two single passes take the same branches of the one forward walk.  T = 14: a Philox row group of a
+    joint [2 T] matrix would straddle the segments; T = 36: gemm_splitk_factor gives 8 slabs for the 2048 -> 100 product and 2
+    for the 512-wide out-proj, so the split and the unsplit out-proj differ.  ragged: key lengths [S, 1] / [S, 1, S // 2, 2]
+    through the _len entry points."""
+    key_len = torch.tensor([S, 1, S // 2, 2][:B], dtype=torch.int32, device="cuda") if ragged else None
+    _pair_against_the_two_single_passes(S, B, E, H, mode, key_len)
 
 
 def test_a_lab_variant_without_a_segment_form_is_reported_and_refused():
