@@ -156,6 +156,10 @@ SIGNATURES = {
     "ganffn_attention_bwd_mask": (_I, [_P, _P, _P, _P, _P, _P, _U32, _P, _I, _I, _I, _I, _F, _U32, _P, _U64, _P]),
     "ganffn_encoder_fwd_mask": (_I, [_PE, _P, _U32, _P, _P, _P, _P, _P, _P, _P, _U64, _P]),
     "ganffn_encoder_bwd_mask": (_I, [_PE, _P, _U32, _I, _I, _P, _P, _P, _P, _P, _P, _U64, _I, _P]),
+    "ganffn_stream_cache_floats": (_L, [_PE]),
+    "ganffn_stream_workspace_floats": (_L, [_PE, _I]),
+    "ganffn_encoder_stream_step": (_I, [_PE, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ganffn_stream_attention": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "ganffn_encoder_fwd_pair_len":(_I, [_PE, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, _P]),
     "ganffn_encoder_bwd_parts_len": (_I, [_PE, _P, _P, _P, _P, _P, _P, _P, _U64, _I, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int), _P]),
     "ganffn_bce_len_fwd": (_I, [_P, _P, _I, _F, _F, _I, _I, _I, _F, _P, _I, _P]),

@@ -210,10 +210,14 @@ static FwdSeg saved_seg(const ganffn_enc_cfg* c, const SavedOff& so, float* save
 // key_len (or null): per-dialogue key lengths of the attention core, the one place of a layer where rows of a dialogue meet;
 // both segments are the same B dialogues, so one [B] array serves both
 // flags: GANFFN_ATTN_* bits for the same place (0 = none); the causal kernels have no two-segment form
+// sa (or null): the pass is a streaming step (ganffn_encoder_stream_step) — c is S = 1, B = n, eval; the positional encoding is
+// the gather by per-dialogue position followed by layer 0's in-proj GEMM, and the attention core is the single-query step over
+// layer l's K/V cache (stream.hip).  Every other launch is the one a pass over T = n rows issues; null changes no call.
 static int encoder_fwd_walk(const ganffn_enc_cfg* c, const int32_t* key_len, uint32_t flags, const Mode md, const FwdSeg& s0,
                             const FwdSeg* s1, const float* pe, const float* x_in, const float* params, const uint64_t* rng,
-                            uint64_t add, hipStream_t st) {
+                            uint64_t add, hipStream_t st, const StreamArgs* sa = nullptr) {
     GF_CHECK_ARG(!s1 || flags == 0, "encoder_fwd_pair: flags 0x%x have no two-segment form", flags);
+    GF_CHECK_ARG(!sa || (!s1 && !key_len && flags == 0 && !s0.train), "encoder_stream_step: one eval segment, no lengths, no flags");
     const int S = c->S, B = c->B, E = c->E, H = c->H, F = c->F, L = c->L, T = S * B;
     const int64_t TE = (int64_t)T * E;
     const LayerOff lo = layer_off(E, F);
@@ -238,13 +242,16 @@ static int encoder_fwd_walk(const ganffn_enc_cfg* c, const int32_t* key_len, uin
     // d_model 100: out-proj + residual + dropout + LN1 is one kernel, and LN2 carries the NEXT layer's in-proj (rowchain.hip);
     // the positional encoding + dropout at the head of the stack carries layer 0's
     const bool rc = rc_supported(E) && !md.rc_off();
-    if (rc && !md.pe_off()) {
+    if (rc && !md.pe_off() && !sa) {
         RcFwdSeg1 r1{};
         r1.y = pe; r1.x = x_in; r1.out = t1.x(0); r1.post_out = t1.layer(0) + so.qkv; r1.train = train1;
         GF_TRY(launch_rc_pe_inproj_fwd(x_in, pe, s0.x(0), params + lo.in_w, params + lo.in_b, s0.layer(0) + so.qkv, T, B, c->p_pe, rng,
                                        add, train0, st, s1 ? &r1 : nullptr));
     } else {
-        GF_TRY(launch_pe_dropout(x_in, pe, s0.x(0), S, B, E, c->p_pe, rng, add, train0, st, s1 ? s1->x(0) : nullptr, train1));
+        if (sa)
+            GF_TRY(launch_stream_pe(x_in, pe, sa->slot, sa->pos, s0.x(0), T, sa->capacity, sa->max_len, E, st));
+        else
+            GF_TRY(launch_pe_dropout(x_in, pe, s0.x(0), S, B, E, c->p_pe, rng, add, train0, st, s1 ? s1->x(0) : nullptr, train1));
         if (rc) {
             EpiArgs e0;
             e0.bias = params + lo.in_b;
@@ -262,7 +269,10 @@ static int encoder_fwd_walk(const ganffn_enc_cfg* c, const int32_t* key_len, uin
         ea.bias = P + lo.in_b;
         if (!rc) GF_TRY(nt(s0.x(l), t1.x(l), E, P + lo.in_w, v0 + so.qkv, v1 + so.qkv, 3 * E, EPI_NONE, ea));
         // attention core (keep words only when a backward will follow)
-        {
+        if (sa) {
+            GF_TRY(launch_stream_attention(v0 + so.qkv, sa->cache + (int64_t)l * sa->layer_stride, sa->slot, sa->pos, v0 + so.attn_o, T,
+                                           sa->capacity, sa->max_len, E, H, st));
+        } else {
             const AttnFwdSeg1 a1{v1 + so.qkv, v1 + so.attn_o, v1 + so.lse, keep_words(t1, v1), train1};
             GF_TRY(launch_attention_fwd(v0 + so.qkv, v0 + so.attn_o, v0 + so.lse, keep_words(s0, v0), S, B, E, H, c->p_enc, site + 0, rng,
                                         add, train0, st, s1 ? &a1 : nullptr, key_len, flags));
@@ -349,6 +359,59 @@ extern "C" int ganffn_encoder_fwd_mask(const ganffn_enc_cfg* c, const int32_t* k
                                        const float* pe, const float* params, float* out, float* saved, float* workspace,
                                        const uint64_t* rng, uint64_t add, void* stream) {
     return encoder_fwd_impl(c, key_len, flags, x_in, pe, params, out, saved, workspace, rng, add, stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// streaming step: n new rows, one per active dialogue, through the whole stack against per-layer K/V caches
+//   cache: L layers, stream_layer_floats apart, each [capacity][2 (K, V)][H][max_len][E / H]   (c->B = capacity, c->S = max_len)
+//   workspace: the unsaved segment of a forward over T = n_max rows
+// ------------------------------------------------------------------------------------------
+static int check_stream_cfg(const ganffn_enc_cfg* c) {
+    GF_TRY(check_cfg(c));
+    GF_CHECK_ARG(c->B <= GANFFN_MAX_DIALOGUES, "stream: capacity B=%d out of range [1,%d]", c->B, GANFFN_MAX_DIALOGUES);
+    GF_CHECK_ARG(c->train == 0, "stream: train=%d (streaming is inference: train must be 0)", c->train);
+    GF_CHECK_ARG(((c->E / c->H) & 1) == 0 && c->E / c->H <= 64, "stream: head_dim %d must be even and <= 64", c->E / c->H);
+    return 0;
+}
+static int64_t stream_layer_floats(const ganffn_enc_cfg* c) { return a4((int64_t)c->B * 2 * c->S * c->E); }
+static ganffn_enc_cfg stream_rows_cfg(const ganffn_enc_cfg* c, int n) {
+    ganffn_enc_cfg r = *c;
+    r.S = 1;
+    r.B = n;
+    r.train = 0;
+    return r;
+}
+extern "C" int64_t ganffn_stream_cache_floats(const ganffn_enc_cfg* c) {
+    if (check_stream_cfg(c) != 0) return -1;
+    return (int64_t)c->L * stream_layer_floats(c);
+}
+extern "C" int64_t ganffn_stream_workspace_floats(const ganffn_enc_cfg* c, int n_max) {
+    if (check_stream_cfg(c) != 0) return -1;
+    if (n_max < 1 || n_max > c->B) {
+        fail(-1, "stream_workspace_floats: n_max=%d out of range [1,%d]", n_max, c->B);
+        return -1;
+    }
+    const ganffn_enc_cfg r = stream_rows_cfg(c, n_max);
+    return enc_ws_floats(&r);
+}
+extern "C" int ganffn_encoder_stream_step(const ganffn_enc_cfg* c, int n, const int32_t* slot, const int32_t* pos, const float* x,
+                                          const float* pe, const float* params, float* cache, float* out, float* workspace,
+                                          void* stream) {
+    const Mode md = mode();
+    GF_TRY(check_stream_cfg(c));
+    GF_CHECK_ARG(n >= 1 && n <= c->B, "encoder_stream_step: n=%d out of range [1,%d]", n, c->B);
+    GF_CHECK_ARG(slot && pos && x && pe && params && cache && out && workspace, "encoder_stream_step: null pointer");
+    GF_CHECK_ARG(aligned16(x) && aligned16(pe) && aligned16(params) && aligned16(cache) && aligned16(out) && aligned16(workspace),
+                 "encoder_stream_step: buffers must be 16-byte aligned");
+    const ganffn_enc_cfg r = stream_rows_cfg(c, n);
+    const SavedOff so = saved_off(&r);
+    const FwdSeg s0 = unsaved_seg(&r, so, workspace, out, 0);
+    const StreamArgs sa{slot, pos, cache, stream_layer_floats(c), c->B, c->S};
+    return encoder_fwd_walk(&r, nullptr, 0, md, s0, nullptr, pe, x, params, nullptr, 0, (hipStream_t)stream, &sa);
+}
+extern "C" int ganffn_stream_attention(const float* qkv, float* cache_layer, const int32_t* slot, const int32_t* pos, float* o, int n,
+                                       int capacity, int max_len, int E, int H, void* stream) {
+    return launch_stream_attention(qkv, cache_layer, slot, pos, o, n, capacity, max_len, E, H, (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------

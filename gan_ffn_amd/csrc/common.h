@@ -368,6 +368,19 @@ int launch_attn16_bwd(const float* qkv, const float* o, const float* lse, const 
                       int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train,
                       hipStream_t st, const int32_t* key_len = nullptr, uint32_t flags = 0);
 
+// stream.hip — streaming causal attention over per-layer K/V caches (layout: include/ganffn.h, "streaming"): per row i, slot
+// s = slot[i] at position t = pos[s], append the row's K / V at t and attend with its Q over keys 0 .. t; a row with s outside
+// [0, capacity) or t outside [0, max_len) gives a zero row and touches nothing
+int launch_stream_attention(const float* qkv, float* cache_layer, const int32_t* slot, const int32_t* pos, float* o, int n,
+                            int capacity, int max_len, int E, int H, hipStream_t st);
+// x0[i] = x[i] + pe[pos[slot[i]]] (eval mode); a skipped row gives a zero row
+int launch_stream_pe(const float* x, const float* pe, const int32_t* slot, const int32_t* pos, float* x0, int n, int capacity,
+                     int max_len, int E, hipStream_t st);
+// what encoder_fwd_walk (api.hip) needs to run a stack as a streaming step: layer l's cache is cache + l * layer_stride
+struct StreamArgs {
+    const int32_t* slot; const int32_t* pos; float* cache; int64_t layer_stride; int capacity, max_len;
+};
+
 // out1 (optional): a second segment over the same x in the same launch, with its own output and train flag
 int launch_pe_dropout(const float* x, const float* pe, float* out, int S, int B, int E, float p,
                       const uint64_t* rng, uint64_t add, int train, hipStream_t st, float* out1 = nullptr, int train1 = 0);

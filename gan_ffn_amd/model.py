@@ -335,6 +335,14 @@ class GAN_FFN(nn.Module):
         log_prob = ops.LogSoftmaxFn.apply(logits)
         return log_prob, [], [], []
 
+    def stream(self, capacity=1, max_len=MAX_LEN, use_graph=False):
+        """(an extension, causal=True only) a streaming.StreamSession over this classifier: per-layer K/V caches for up to
+        `capacity` concurrent dialogues of up to `max_len` utterances, and `step(acoustic, visual, text, slots)`, which labels the
+        next utterance of each from the caches instead of running the whole prefix again.  use_graph=True replays one captured
+        graph per distinct row count.  Raises ValueError for a bidirectional classifier (causal=False)."""
+        from .streaming import StreamSession
+        return StreamSession(self, capacity=capacity, max_len=max_len, use_graph=use_graph)
+
 
 # configuration 5 (train_IEMOCAP_DialogueRNN.py:705-720): the DialogueRNN head lives in dialogue_rnn.py; re-exported so
 # that `from model import GAN_FFN_DialogueRNN, BiModel, ...` keeps working for code written against the reference

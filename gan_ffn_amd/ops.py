@@ -182,6 +182,30 @@ def encoder_fwd_raw(cfg, x, pe, slab, out, saved, ws, rng, add, key_len=None, ca
               _ptr(ws), _ptr(rng), C.c_uint64(add), _stream())
 
 
+def stream_sizes(cfg, n_max):
+    """(K/V cache floats, workspace floats for steps of up to n_max rows) of a streamed stack; cfg describes the cache:
+    cfg.S = positions per slot, cfg.B = slots, eval (ganffn_stream_cache_floats / ganffn_stream_workspace_floats)"""
+    lib = _lib.load()
+    c = int(lib.ganffn_stream_cache_floats(C.byref(cfg)))
+    w = int(lib.ganffn_stream_workspace_floats(C.byref(cfg), n_max)) if c >= 0 else -1
+    if c < 0 or w < 0:
+        _lib.check(-1, "ganffn_stream_*_floats")
+    return c, w
+
+
+def encoder_stream_step_raw(cfg, n, slot, pos, x, pe, slab, cache, out, ws):
+    """one streaming step of an encoder stack (ganffn_encoder_stream_step; no autograd, eval math): row i of x [n x E] is the
+    next utterance of the dialogue in cache slot slot[i] (int32 device tensor [n], distinct), at position pos[slot[i]] (int32
+    device tensor [cfg.B], read only: the caller advances it).  Appends the row's K / V to every layer's cache and writes the
+    stack's output for the row to out [n x E]."""
+    for t, k in ((slot, n), (pos, cfg.B)):
+        if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.numel() < k:
+            raise ValueError("slot / pos must be contiguous int32 device tensors with %d / %d entries" % (n, cfg.B))
+    _need_gpu(x, pe, slab, cache, out, ws)
+    _lib.call("ganffn_encoder_stream_step", C.byref(cfg), n, _ptr(slot), _ptr(pos), _ptr(x), _ptr(pe), _ptr(slab), _ptr(cache),
+              _ptr(out), _ptr(ws), _stream())
+
+
 def encoder_fwd_pair_supported(cfg):
     """can the eval-mode and the train-mode forward of this configuration share their launches (ganffn_encoder_fwd_pair)?"""
     return int(_lib.load().ganffn_encoder_fwd_pair_supported(C.byref(cfg))) == 1

@@ -590,6 +590,33 @@ int ganffn_encoder_fwd_mask(const ganffn_enc_cfg* cfg, const int32_t* key_len, u
 int ganffn_encoder_bwd_mask(const ganffn_enc_cfg* cfg, const int32_t* key_len, uint32_t flags, int layer_lo, int layer_hi,
                             float* dx, const float* params, float* grads, const float* saved, float* workspace,
                             const uint64_t* rng, uint64_t rng_offset_add, int need_dx_in, void* stream);
+/* ---- streaming: a causal stack one utterance at a time, from per-layer K/V caches (csrc/stream.hip) ----------------------------
+ * Under the causal mask the K and V of a past utterance never change and everything else of a stack is row-wise, so row t of a
+ * dialogue needs only its own input row and the cached K / V of rows 0 .. t-1 in every layer.  A step takes n new rows, one per
+ * active dialogue: row i belongs to cache slot slot[i] and is that dialogue's utterance number pos[slot[i]].
+ * cfg here describes the CACHE: cfg->S = positions per slot (max_len, 1 .. 110), cfg->B = slots (capacity, 1 ..
+ * GANFFN_MAX_DIALOGUES), cfg->train must be 0 (streaming is inference: no dropout, nothing saved), head_dim E / H even and <= 64.
+ * Cache layout (the caller owns it; tests fill it directly): L layers, a4(capacity * 2 * max_len * E) floats apart (a4 = rounded
+ * up to a multiple of 4), each layer [capacity][2 (K, V)][H][max_len][hd] floats with hd = E / H: the key (kv = 0) or value
+ * (kv = 1) of slot s, head h, position j is the hd contiguous floats at (((s * 2 + kv) * H + h) * max_len + j) * hd.  Positions at
+ * or above pos[s] are never read, so the cache needs no initialisation and a slot is reset by setting its position to 0.
+ * slot [n] and pos [capacity] are int32 on the device; pos is READ ONLY here — advancing it (pos[slot[i]] += 1 after the last stack
+ * of a step) is the caller's job, so several stacks can step from the same positions.  The slots of one call must be distinct.
+ * A row whose slot is outside [0, capacity) or whose position is outside [0, max_len) is skipped by the attention step (its
+ * attention output is a zero row, its positional-encoding sum a zero row, the cache is untouched) and nothing is accessed out of
+ * range; its `out` row is then meaningless.
+ * The step is the launch sequence of the forward at T = n rows with two launches swapped: the positional encoding is a gather by
+ * position (plus layer 0's in-proj GEMM), the attention core is the single-query kernel.  Every rule that picks a summation
+ * order (split-K factors, K chunks of the 2048 -> 100 product) is evaluated for T = n, so a step's values agree with the rows of
+ * the full causal forward over the dialogue to rounding, NOT bit for bit.  The bits of a row depend on no other row of the call.
+ * x, out [n x E]; pe [>= max_len x E]; workspace: the _workspace_floats of n_max >= n.  The attention call alone (a unit-test
+ * hook) takes one layer's cache and this step's in-proj output qkv [n x 3E], and writes o [n x E]. */
+int64_t ganffn_stream_cache_floats(const ganffn_enc_cfg* cfg);
+int64_t ganffn_stream_workspace_floats(const ganffn_enc_cfg* cfg, int n_max);
+int ganffn_encoder_stream_step(const ganffn_enc_cfg* cfg, int n, const int32_t* slot, const int32_t* pos, const float* x,
+                               const float* pe, const float* params, float* cache, float* out, float* workspace, void* stream);
+int ganffn_stream_attention(const float* qkv, float* cache_layer, const int32_t* slot, const int32_t* pos, float* o, int n,
+                            int capacity, int max_len, int E, int H, void* stream);
 /* z = x + drop(y); xhat = (z-mean)*rstd; out = xhat*w + b   (norm1/norm2 of the encoder layer).  Accepted: T >= 1 and
  * 1 <= E <= 640, a multiple of 4 or not; a wider row is refused with a message.  The variance is the two-pass one (mean
  * of the squared deviations), so a row mean far above the row's spread costs no more than fp32 rounding of z itself. */
