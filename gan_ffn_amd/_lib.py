@@ -160,6 +160,9 @@ SIGNATURES = {
     "ganffn_stream_workspace_floats": (_L, [_PE, _I]),
     "ganffn_encoder_stream_step": (_I, [_PE, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ganffn_stream_attention": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "ganffn_stream_extend_workspace_floats": (_L, [_PE, _I]),
+    "ganffn_encoder_stream_extend": (_I, [_PE, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "ganffn_stream_attention_chunk": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ganffn_encoder_fwd_pair_len":(_I, [_PE, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, _P]),
     "ganffn_encoder_bwd_parts_len": (_I, [_PE, _P, _P, _P, _P, _P, _P, _P, _U64, _I, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int), _P]),
     "ganffn_bce_len_fwd": (_I, [_P, _P, _I, _F, _F, _I, _I, _I, _F, _P, _I, _P]),

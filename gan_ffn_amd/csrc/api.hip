@@ -213,6 +213,8 @@ static FwdSeg saved_seg(const ganffn_enc_cfg* c, const SavedOff& so, float* save
 // sa (or null): the pass is a streaming step (ganffn_encoder_stream_step) — c is S = 1, B = n, eval; the positional encoding is
 // the gather by per-dialogue position followed by layer 0's in-proj GEMM, and the attention core is the single-query step over
 // layer l's K/V cache (stream.hip).  Every other launch is the one a pass over T = n rows issues; null changes no call.
+// With sa->count (ganffn_encoder_stream_extend) the T = m * n rows are n chunks of up to m rows, time-major, and the two launches
+// are the chunk forms of the same file; without it they are the step's, as before.
 static int encoder_fwd_walk(const ganffn_enc_cfg* c, const int32_t* key_len, uint32_t flags, const Mode md, const FwdSeg& s0,
                             const FwdSeg* s1, const float* pe, const float* x_in, const float* params, const uint64_t* rng,
                             uint64_t add, hipStream_t st, const StreamArgs* sa = nullptr) {
@@ -248,7 +250,10 @@ static int encoder_fwd_walk(const ganffn_enc_cfg* c, const int32_t* key_len, uin
         GF_TRY(launch_rc_pe_inproj_fwd(x_in, pe, s0.x(0), params + lo.in_w, params + lo.in_b, s0.layer(0) + so.qkv, T, B, c->p_pe, rng,
                                        add, train0, st, s1 ? &r1 : nullptr));
     } else {
-        if (sa)
+        if (sa && sa->count)
+            GF_TRY(launch_stream_pe_chunk(x_in, pe, sa->slot, sa->count, sa->pos, s0.x(0), T / sa->m, sa->m, sa->capacity, sa->max_len,
+                                          E, st));
+        else if (sa)
             GF_TRY(launch_stream_pe(x_in, pe, sa->slot, sa->pos, s0.x(0), T, sa->capacity, sa->max_len, E, st));
         else
             GF_TRY(launch_pe_dropout(x_in, pe, s0.x(0), S, B, E, c->p_pe, rng, add, train0, st, s1 ? s1->x(0) : nullptr, train1));
@@ -269,7 +274,10 @@ static int encoder_fwd_walk(const ganffn_enc_cfg* c, const int32_t* key_len, uin
         ea.bias = P + lo.in_b;
         if (!rc) GF_TRY(nt(s0.x(l), t1.x(l), E, P + lo.in_w, v0 + so.qkv, v1 + so.qkv, 3 * E, EPI_NONE, ea));
         // attention core (keep words only when a backward will follow)
-        if (sa) {
+        if (sa && sa->count) {
+            GF_TRY(launch_stream_attention_chunk(v0 + so.qkv, sa->cache + (int64_t)l * sa->layer_stride, sa->slot, sa->count, sa->pos,
+                                                 v0 + so.attn_o, T / sa->m, sa->m, sa->capacity, sa->max_len, E, H, st));
+        } else if (sa) {
             GF_TRY(launch_stream_attention(v0 + so.qkv, sa->cache + (int64_t)l * sa->layer_stride, sa->slot, sa->pos, v0 + so.attn_o, T,
                                            sa->capacity, sa->max_len, E, H, st));
         } else {
@@ -408,6 +416,50 @@ extern "C" int ganffn_encoder_stream_step(const ganffn_enc_cfg* c, int n, const 
     const FwdSeg s0 = unsaved_seg(&r, so, workspace, out, 0);
     const StreamArgs sa{slot, pos, cache, stream_layer_floats(c), c->B, c->S};
     return encoder_fwd_walk(&r, nullptr, 0, md, s0, nullptr, pe, x, params, nullptr, 0, (hipStream_t)stream, &sa);
+}
+
+// ------------------------------------------------------------------------------------------
+// stream prefill: n chunks of up to m new rows each (time-major [m][n][E]) through the whole stack against the same caches
+//   workspace: the unsaved segment of a forward over T = rows_max rows (nothing of a backward: streaming is inference)
+// ------------------------------------------------------------------------------------------
+static int64_t stream_extend_ws(const ganffn_enc_cfg* c, int rows) {
+    const ganffn_enc_cfg r = stream_rows_cfg(c, rows);
+    return 2 * (int64_t)rows * c->E + saved_off(&r).per_layer + (int64_t)MAX_SPLITS * rows * c->E + 64;
+}
+extern "C" int64_t ganffn_stream_extend_workspace_floats(const ganffn_enc_cfg* c, int rows_max) {
+    if (check_stream_cfg(c) != 0) return -1;
+    if (rows_max < 1 || rows_max > c->S * c->B) {
+        fail(-1, "stream_extend_workspace_floats: rows_max=%d out of range [1,%d] (max_len * capacity)", rows_max, c->S * c->B);
+        return -1;
+    }
+    return stream_extend_ws(c, rows_max);
+}
+extern "C" int ganffn_encoder_stream_extend(const ganffn_enc_cfg* c, int n, int m, const int32_t* slot, const int32_t* count,
+                                            const int32_t* pos, const float* x, const float* pe, const float* params, float* cache,
+                                            float* out, float* workspace, int64_t workspace_floats, void* stream) {
+    const Mode md = mode();
+    GF_TRY(check_stream_cfg(c));
+    GF_CHECK_ARG(n >= 1 && n <= c->B, "encoder_stream_extend: n=%d out of range [1,%d]", n, c->B);
+    GF_CHECK_ARG(m >= 1 && m <= c->S, "encoder_stream_extend: m=%d out of range [1,%d]", m, c->S);
+    GF_CHECK_ARG(slot && count && pos && x && pe && params && cache && out && workspace, "encoder_stream_extend: null pointer");
+    GF_CHECK_ARG(aligned16(x) && aligned16(pe) && aligned16(params) && aligned16(cache) && aligned16(out) && aligned16(workspace),
+                 "encoder_stream_extend: buffers must be 16-byte aligned");
+    const int rows = m * n;
+    GF_CHECK_ARG(workspace_floats >= stream_extend_ws(c, rows),
+                 "encoder_stream_extend: m*n=%d rows need a workspace of %lld floats (rows_max >= %d), got %lld", rows,
+                 (long long)stream_extend_ws(c, rows), rows, (long long)workspace_floats);
+    const ganffn_enc_cfg r = stream_rows_cfg(c, rows);
+    const SavedOff so = saved_off(&r);
+    const FwdSeg s0 = unsaved_seg(&r, so, workspace, out, 0);
+    StreamArgs sa{slot, pos, cache, stream_layer_floats(c), c->B, c->S};
+    sa.count = count;
+    sa.m = m;
+    return encoder_fwd_walk(&r, nullptr, 0, md, s0, nullptr, pe, x, params, nullptr, 0, (hipStream_t)stream, &sa);
+}
+extern "C" int ganffn_stream_attention_chunk(const float* qkv, float* cache_layer, const int32_t* slot, const int32_t* count,
+                                             const int32_t* pos, float* o, int n, int m, int capacity, int max_len, int E, int H,
+                                             void* stream) {
+    return launch_stream_attention_chunk(qkv, cache_layer, slot, count, pos, o, n, m, capacity, max_len, E, H, (hipStream_t)stream);
 }
 extern "C" int ganffn_stream_attention(const float* qkv, float* cache_layer, const int32_t* slot, const int32_t* pos, float* o, int n,
                                        int capacity, int max_len, int E, int H, void* stream) {

@@ -376,9 +376,21 @@ int launch_stream_attention(const float* qkv, float* cache_layer, const int32_t*
 // x0[i] = x[i] + pe[pos[slot[i]]] (eval mode); a skipped row gives a zero row
 int launch_stream_pe(const float* x, const float* pe, const int32_t* slot, const int32_t* pos, float* x0, int n, int capacity,
                      int max_len, int E, hipStream_t st);
-// what encoder_fwd_walk (api.hip) needs to run a stack as a streaming step: layer l's cache is cache + l * layer_stride
+// the chunk form (ganffn_stream_attention_chunk): qkv [m][n][3E] and o [m][n][E] time-major; chunk i holds c = count[i] new rows
+// of slot s = slot[i] at positions t .. t+c-1, t = pos[s]; row j < c attends over cached keys 0 .. t-1 and the chunk's keys
+// 0 .. j, and the rows' K / V go to the cache at t .. t+c-1.  A chunk with s outside [0, capacity), t < 0, c < 0, c > m or
+// t + c > max_len is skipped whole (cache untouched); o rows j >= c are zeros for every chunk, qkv rows j >= c are never read
+int launch_stream_attention_chunk(const float* qkv, float* cache_layer, const int32_t* slot, const int32_t* count,
+                                  const int32_t* pos, float* o, int n, int m, int capacity, int max_len, int E, int H,
+                                  hipStream_t st);
+// x0[j, i] = x[j, i] + pe[pos[slot[i]] + j] for j < count[i] of a chunk that is not skipped; every other row is a zero row
+int launch_stream_pe_chunk(const float* x, const float* pe, const int32_t* slot, const int32_t* count, const int32_t* pos,
+                           float* x0, int n, int m, int capacity, int max_len, int E, hipStream_t st);
+// what encoder_fwd_walk (api.hip) needs to run a stack as a streaming step: layer l's cache is cache + l * layer_stride.
+// count (or null = the one-row step) and m: the chunk form over m * n time-major rows (ganffn_encoder_stream_extend)
 struct StreamArgs {
     const int32_t* slot; const int32_t* pos; float* cache; int64_t layer_stride; int capacity, max_len;
+    const int32_t* count = nullptr; int m = 1;
 };
 
 // out1 (optional): a second segment over the same x in the same launch, with its own output and train flag

@@ -206,6 +206,33 @@ def encoder_stream_step_raw(cfg, n, slot, pos, x, pe, slab, cache, out, ws):
               _ptr(out), _ptr(ws), _stream())
 
 
+STREAM_EXTEND_MAX_ROWS = 110 * 32      # rows of one ganffn_encoder_stream_extend call from StreamSession.extend: the flagship
+                                       # training shape's row count, for which the row-wise kernels are exercised
+
+
+def stream_extend_sizes(cfg, rows_max):
+    """workspace floats of ganffn_encoder_stream_extend calls of up to rows_max = m * n rows (cfg describes the cache, as for
+    stream_sizes; ganffn_stream_extend_workspace_floats)"""
+    w = int(_lib.load().ganffn_stream_extend_workspace_floats(C.byref(cfg), int(rows_max)))
+    if w < 0:
+        _lib.check(-1, "ganffn_stream_extend_workspace_floats")
+    return w
+
+
+def encoder_stream_extend_raw(cfg, n, m, slot, count, pos, x, pe, slab, cache, out, ws):
+    """several new utterances per dialogue through an encoder stack (ganffn_encoder_stream_extend; no autograd, eval math):
+    x [m x n x E], time-major — chunk i holds count[i] <= m new rows of the dialogue in cache slot slot[i] (int32 device tensors
+    [n]; slots distinct), at positions pos[slot[i]] .. + count[i] - 1 (pos: int32 device tensor [cfg.B], read only: the caller
+    advances it by count).  Appends the rows' K / V to every layer's cache and writes the stack's output to out [m x n x E]; rows
+    j >= count[i] of x must be finite and their out rows are meaningless.  ws: stream_extend_sizes(cfg, rows_max >= m * n)."""
+    for t, k in ((slot, n), (count, n), (pos, cfg.B)):
+        if t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous() or t.numel() < k:
+            raise ValueError("slot / count / pos must be contiguous int32 device tensors with %d / %d / %d entries" % (n, n, cfg.B))
+    _need_gpu(x, pe, slab, cache, out, ws)
+    _lib.call("ganffn_encoder_stream_extend", C.byref(cfg), n, m, _ptr(slot), _ptr(count), _ptr(pos), _ptr(x), _ptr(pe), _ptr(slab),
+              _ptr(cache), _ptr(out), _ptr(ws), C.c_int64(ws.numel()), _stream())
+
+
 def encoder_fwd_pair_supported(cfg):
     """can the eval-mode and the train-mode forward of this configuration share their launches (ganffn_encoder_fwd_pair)?"""
     return int(_lib.load().ganffn_encoder_fwd_pair_supported(C.byref(cfg))) == 1

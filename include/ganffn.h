@@ -617,6 +617,35 @@ int ganffn_encoder_stream_step(const ganffn_enc_cfg* cfg, int n, const int32_t* 
                                const float* pe, const float* params, float* cache, float* out, float* workspace, void* stream);
 int ganffn_stream_attention(const float* qkv, float* cache_layer, const int32_t* slot, const int32_t* pos, float* o, int n,
                             int capacity, int max_len, int E, int H, void* stream);
+/* ---- stream prefill: several new utterances per dialogue in one call (csrc/stream.hip) ---------------------------------------
+ * The same caches, slots and positions as the step above, but chunk i of a call holds count[i] new rows of the dialogue in slot
+ * slot[i], at positions t .. t + count[i] - 1 with t = pos[slot[i]]: a dialogue joined under way, caches rebuilt after the
+ * weights changed, utterances that arrive in bursts.  x and out are [m][n][E], TIME-MAJOR (row j of chunk i is row j * n + i), so
+ * a padded [S, B, E] batch passes straight in; m is the longest chunk's room, 1 <= m <= max_len, and count[i] <= m.
+ * Row j < count[i] attends with its Q over the cached keys 0 .. t-1 and the chunk's own keys 0 .. j (scale 1 / sqrt(hd), softmax,
+ * P V): what j + 1 consecutive steps compute.  The K and V of rows 0 .. count[i]-1 are written to every layer's cache at
+ * t .. t + count[i] - 1 as bit copies; new keys and values are taken from the call's own rows, never read back from the cache.
+ * slot, count [n] and pos [capacity] are int32 on the device; pos is READ ONLY — pos[slot[i]] += count[i] after the last stack of a
+ * call is the caller's job.  The slots of one call must be distinct.
+ * SKIP: a chunk whose slot is outside [0, capacity), whose position is negative, whose count is negative or above m, or with
+ * pos + count > max_len is skipped WHOLE: the cache is untouched.  count = 0 writes nothing either.  For every chunk the attention
+ * output and the positional-encoding sum of rows j >= count[i] (all m rows of a skipped chunk) are zero rows; their x rows are
+ * read by no launch that could carry them into a valid row or into the cache, but they run through the row-wise launches
+ * (LayerNorm, FFN), so x must be FINITE there and their `out` rows are meaningless.  Cache words at or above a position are never
+ * read, and nothing is accessed out of range whatever slot / count / pos hold.
+ * The call is the launch sequence of the forward at T = m * n rows with the same two launches swapped, so its values agree with
+ * consecutive steps and with the full causal forward to rounding, NOT bit for bit.  The bits of a chunk's rows depend neither on
+ * the other chunks of the call nor on the chunk's column i.  No atomics; every summation order is fixed.
+ * Workspace: ganffn_stream_extend_workspace_floats(cfg, rows_max) serves every call with m * n <= rows_max (rows_max >= 1); a
+ * call with more rows, or with workspace_floats below what its rows_max = m * n needs, is refused with a message that names the
+ * number.  The attention call alone (a unit-test hook) takes one layer's cache, qkv [m][n][3E] and writes o [m][n][E]. */
+int64_t ganffn_stream_extend_workspace_floats(const ganffn_enc_cfg* cfg, int rows_max);
+int ganffn_encoder_stream_extend(const ganffn_enc_cfg* cfg, int n, int m, const int32_t* slot, const int32_t* count,
+                                 const int32_t* pos, const float* x, const float* pe, const float* params, float* cache,
+                                 float* out, float* workspace, int64_t workspace_floats, void* stream);
+int ganffn_stream_attention_chunk(const float* qkv, float* cache_layer, const int32_t* slot, const int32_t* count,
+                                  const int32_t* pos, float* o, int n, int m, int capacity, int max_len, int E, int H,
+                                  void* stream);
 /* z = x + drop(y); xhat = (z-mean)*rstd; out = xhat*w + b   (norm1/norm2 of the encoder layer).  Accepted: T >= 1 and
  * 1 <= E <= 640, a multiple of 4 or not; a wider row is refused with a message.  The variance is the two-pass one (mean
  * of the squared deviations), so a row mean far above the row's spread costs no more than fp32 rounding of z itself. */

@@ -14,7 +14,18 @@ condition "the total of (b) or (c) at B = 32 is lower than (a) by more than the 
 heads: 320 problems) and head_dim 64 (E = 512, 8 heads: 256 problems); device events around `--launches` launches captured into one
 graph, microseconds per launch.
 
+--extend: reaching utterance 94 of a dialogue that is already under way (a session that joins late, or whose caches are stale
+after the weights changed), at B = 1, 8 and 32 concurrent dialogues, the same protocol (one process, the same generators and
+inputs, two warm-up rounds, the variants alternating block by block):
+  (a) steps  : sess.reset(), then 94 x sess.step — all a tree without StreamSession.extend offers;
+  (b) extend : sess.reset(), then sess.extend over the first 93 utterances and sess.step on the 94th.
+One block = reset to the label of utterance 94 between two device synchronisations.  The JSON carries every block, median and
+[min, max], the largest difference between the two variants' log_prob of utterance 94, and the condition "(b) at B = 32 is lower
+than (a) by more than the larger of the two min-max spreads".  With --kernels the chunk attention kernel alone
+(ganffn_stream_attention_chunk) is timed too: 32 chunks of 94 rows at position 0 and of 47 rows at position 47.
+
     python tools/stream_time.py [--repeats 5] [--root DIR]
+    python tools/stream_time.py --extend [--repeats 5]
     python tools/stream_time.py --kernels [--launches 200] [--repeats 5]
 
 --root DIR imports the package from another checkout (with its own built library), e.g. the parent commit's: a tree without
@@ -113,6 +124,96 @@ def sessions(args, torch):
     return out
 
 
+def extend(args, torch):
+    from gan_ffn_amd import engine, model as M
+    gens, _ = engine.build_networks(device="cuda", seed=3407)
+    net = M.GAN_FFN(gens["acoustic"], gens["visual"], gens["text"], n_classes=6, causal=True).cuda().eval()
+    out = {"root": os.path.abspath(args.root), "S": S, "repeats": args.repeats, "totals_ms": {}, "blocks": {}, "warmup_blocks": {},
+           "last_label_max_abs_diff": {}}
+    for B in (1, 8, 32):
+        g = torch.Generator().manual_seed(B)
+        a, v, t = (torch.rand(S, B, w, generator=g).cuda() for w in (100, 512, 100))
+        sess = net.stream(capacity=B)
+        lengths = [S - 1] * B
+
+        def steps():
+            for u in range(S):
+                lp = sess.step(a[u], v[u], t[u])
+            return lp
+
+        def chunk():
+            sess.extend(a[:S - 1], v[:S - 1], t[:S - 1], lengths)
+            return sess.step(a[S - 1], v[S - 1], t[S - 1])
+
+        variants = {"steps": steps, "extend": chunk}
+
+        def whole(name):
+            sess.reset()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            lp = variants[name]()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3, lp.clone()
+
+        runs = {k: [] for k in variants}
+        last = {}
+        for r in range(args.repeats + WARMUP_ROUNDS):
+            for k in variants:
+                ms, last[k] = whole(k)
+                runs[k].append(ms)
+        out["last_label_max_abs_diff"]["B%d" % B] = float((last["steps"] - last["extend"]).abs().max())
+        for k, vals in runs.items():
+            key = "B%d_%s" % (B, k)
+            out["blocks"][key] = [round(x, 3) for x in vals[WARMUP_ROUNDS:]]
+            out["warmup_blocks"][key] = [round(x, 3) for x in vals[:WARMUP_ROUNDS]]
+            out["totals_ms"][key] = summary(vals[WARMUP_ROUNDS:])
+        del sess
+    a_, b_ = out["totals_ms"]["B32_steps"], out["totals_ms"]["B32_extend"]
+    margin = max(a_["spread"], b_["spread"])
+    out["condition_B32"] = {"steps_median_ms": a_["median"], "extend_median_ms": b_["median"], "larger_spread_ms": margin,
+                            "holds": bool(a_["median"] - b_["median"] > margin)}
+    return out
+
+
+def chunk_kernels(args, torch, out):
+    """the chunk attention kernel alone: 32 chunks, (count, pos) = (94, 0) and (47, 47), head_dim 10 and 64"""
+    from gan_ffn_amd import _lib
+    p = lambda x: C.c_void_p(x.data_ptr())
+    n = cap = 32
+    max_len = 110
+    for name, E, H in (("hd10", 100, 10), ("hd64", 512, 8)):
+        for count, at in ((S, 0), (S // 2, S // 2)):
+            g = torch.Generator().manual_seed(5)
+            qkv = (torch.randn(count, n, 3 * E, generator=g) * 1.5).cuda()
+            cache = torch.randn(cap * 2 * max_len * E, generator=g).cuda()
+            slot = torch.arange(n, dtype=torch.int32, device="cuda")
+            cnt = torch.full((n,), count, dtype=torch.int32, device="cuda")
+            pos = torch.full((cap,), at, dtype=torch.int32, device="cuda")
+            o = torch.empty(count, n, E, device="cuda")
+
+            def launch():
+                _lib.call("ganffn_stream_attention_chunk", p(qkv), p(cache), p(slot), p(cnt), p(pos), p(o), n, count, cap, max_len, E,
+                          H, C.c_void_p(torch.cuda.current_stream().cuda_stream))
+
+            launch()
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                for _ in range(args.launches):
+                    launch()
+            runs = []
+            for _ in range(args.repeats + 1):             # the first round is the warm-up
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                graph.replay()
+                e1.record()
+                torch.cuda.synchronize()
+                runs.append(round(e0.elapsed_time(e1) * 1e3 / args.launches, 3))
+            key = "chunk_%s_count%d_pos%d_us" % (name, count, at)
+            out["blocks"][key] = runs[1:]
+            out[key] = summary(runs[1:])
+
+
 def kernels(args, torch):
     from gan_ffn_amd import _lib
     _lib.load()
@@ -151,6 +252,8 @@ def kernels(args, torch):
         out["blocks"][name + "_us"] = runs[1:]
         out[name + "_us"] = summary(runs[1:])
         out[name + "_problems"] = n * H
+    if hasattr(_lib.load(), "ganffn_stream_attention_chunk"):
+        chunk_kernels(args, torch, out)
     return out
 
 
@@ -159,11 +262,12 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--kernels", action="store_true")
+    ap.add_argument("--extend", action="store_true")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     args = ap.parse_args()
     sys.path.insert(0, os.path.abspath(args.root))
     import torch
-    print(json.dumps((kernels if args.kernels else sessions)(args, torch)), flush=True)
+    print(json.dumps((kernels if args.kernels else extend if args.extend else sessions)(args, torch)), flush=True)
 
 
 if __name__ == "__main__":
