@@ -1124,94 +1124,58 @@ __global__ __launch_bounds__(EC_NT) void drnn_echain_bwd_kernel(EchainBwdArgs a)
 }
 
 // ------------------------------------------------------------------------------------------
-// layouts of the saved-for-backward block and of the workspace (floats; every region 16-byte aligned).  P = parties: the
-// party states Q, their gradients dQ and the listener's per-party-row regions are [.. x P x ..]; P = 2 gives the sizes and
-// offsets the two-party entry points always had.
+// Host side.  Every entry point of the recurrence fills one DrnnCall and runs drnn_fwd / drnn_bwd on it; one DrnnLayout per
+// call says where every region of the saved-for-backward block and of the workspace lies.
+// Layout (floats; every region 16-byte aligned): a function of (cfg, attention, listener, parties).  P = parties: the party
+// states Q, their gradients dQ and the listener's per-party-row regions are [.. x P x ..]; P = 2 gives the sizes and offsets
+// the two-party entry points always had.  The listener's regions lie behind the listener-free ones and general2's / concat's
+// behind those, so a region's offset does not depend on what follows it; a region the configuration does not use is -1.
 // ------------------------------------------------------------------------------------------
-struct DrnnSaved {
-    int64_t XG, XP, XA, G, Q, E, QS, CT, QN, Rg, Zg, Ng, HNg, Rp, Zp, Np, HNp, Re, Ze, Ne, HNe, total;
+struct DrnnLayout {
+    // saved: U-only products, states ((S + 1) blocks of B rows; block 0 = zeros), per-step inputs, gates of the g / p / e cells
+    int64_t XG, XP, XA, G, Q, E, QS, CT, QN, Rg, Zg, Ng, HNg, Rp, Zp, Np, HNp, Re, Ze, Ne, HNe;
+    int64_t XL = -1, QSP = -1, Rl = -1, Zl = -1, Nl = -1, HNl = -1;        // listener
+    int64_t TS = -1, XC = -1, PC = -1;         // general2: tanh scores; concat: X_t = W_u U_t, P_j = W_g g_j
+    int64_t saved_total;
+    // workspace: pre-activations of a step, gate gradients of all steps, recurrent gradients (a / b: ping-pong)
+    int64_t GI, GH, GIp, GHp, dGIg, dGHg, dGIp, dGHp, dGIe, dGHe, dXA, dCT, dG, dQa, dQb, dEa, dEb, dQsel, dQSp, dQSg, dhdir, dhdirG, dQN;
+    int64_t GIe, dQNall, WT;      // emotion chain: input pre-activations / dQN of all steps; transposed recurrent weights (backward): 4 x [H x 3H]
+    int64_t GIl = -1, GHl = -1, dGIl = -1, dGHl = -1, dss = -1, dqs = -1, dQl = -1, dhdirl = -1, WTl = -1;     // listener (WTl: transposed l_wih[:, Dm:], l_whh)
+    int64_t dXC = -1, dP = -1, dVp = -1;       // concat
+    int64_t ws_total;
 };
-static DrnnSaved drnn_saved(const ganffn_drnn_cfg* c, int P) {
-    DrnnSaved s;
-    const int64_t T = (int64_t)c->S * c->B, T1 = (int64_t)(c->S + 1) * c->B, H = c->H, He = c->He;
+static DrnnLayout drnn_layout(const ganffn_drnn_cfg* c, const ganffn_drnn_att& at, bool listener, int P) {
+    DrnnLayout L;
+    const int64_t T = (int64_t)c->S * c->B, T1 = (int64_t)(c->S + 1) * c->B, B = c->B, H = c->H, He = c->He, Da = at.Da;
     int64_t p = 0;
     auto take = [&](int64_t n) { int64_t r = p; p += (n + 3) & ~int64_t(3); return r; };
-    s.XG = take(T * 3 * H); s.XP = take(T * 3 * H); s.XA = take(T * H);
-    s.G = take(T1 * H); s.Q = take(T1 * P * H); s.E = take(T1 * He);
-    s.QS = take(T1 * H); s.CT = take(T * H); s.QN = take(T * H);
-    s.Rg = take(T * H); s.Zg = take(T * H); s.Ng = take(T * H); s.HNg = take(T * H);
-    s.Rp = take(T * H); s.Zp = take(T * H); s.Np = take(T * H); s.HNp = take(T * H);
-    s.Re = take(T * He); s.Ze = take(T * He); s.Ne = take(T * He); s.HNe = take(T * He);
-    s.total = p;
-    return s;
-}
-struct DrnnWs {
-    int64_t GI, GH, GIp, GHp, dGIg, dGHg, dGIp, dGHp, dGIe, dGHe, dXA, dCT, dG, dQa, dQb, dEa, dEb, dQsel, dQSp, dQSg, dhdir, dhdirG, dQN, GIe, dQNall, WT, total;
-};
-static DrnnWs drnn_ws(const ganffn_drnn_cfg* c, int P) {
-    DrnnWs w;
-    const int64_t T = (int64_t)c->S * c->B, T1 = (int64_t)(c->S + 1) * c->B, B = c->B, H = c->H, He = c->He;
-    int64_t p = 0;
-    auto take = [&](int64_t n) { int64_t r = p; p += (n + 3) & ~int64_t(3); return r; };
-    w.GI = take(B * 3 * H); w.GH = take(B * 3 * H); w.GIp = take(B * 3 * H); w.GHp = take(B * 3 * H);
-    w.dGIg = take(T * 3 * H); w.dGHg = take(T * 3 * H); w.dGIp = take(T * 3 * H); w.dGHp = take(T * 3 * H);
-    w.dGIe = take(T * 3 * He); w.dGHe = take(T * 3 * He);
-    w.dXA = take(T * H); w.dCT = take(B * H); w.dG = take(T1 * H);
-    w.dQa = take(B * P * H); w.dQb = take(B * P * H); w.dEa = take(B * He); w.dEb = take(B * He);
-    w.dQsel = take(B * H); w.dQSp = take(B * H); w.dQSg = take(B * H); w.dhdir = take(B * H); w.dhdirG = take(B * H); w.dQN = take(B * H);
-    w.GIe = take(T * 3 * He); w.dQNall = take(T * H);       // emotion chain: input pre-activations / dQN of all steps
-    w.WT = take(4 * H * 3 * H);                              // transposed recurrent weights (backward): 4 x [H x 3H]
-    w.total = p;
-    return w;
-}
+    L.XG = take(T * 3 * H); L.XP = take(T * 3 * H); L.XA = take(T * H);
+    L.G = take(T1 * H); L.Q = take(T1 * P * H); L.E = take(T1 * He);
+    L.QS = take(T1 * H); L.CT = take(T * H); L.QN = take(T * H);
+    L.Rg = take(T * H); L.Zg = take(T * H); L.Ng = take(T * H); L.HNg = take(T * H);
+    L.Rp = take(T * H); L.Zp = take(T * H); L.Np = take(T * H); L.HNp = take(T * H);
+    L.Re = take(T * He); L.Ze = take(T * He); L.Ne = take(T * He); L.HNe = take(T * He);
+    if (listener) { L.XL = take(T * 3 * H); L.QSP = take(T * H); L.Rl = take(T * P * H); L.Zl = take(T * P * H); L.Nl = take(T * P * H); L.HNl = take(T * P * H); }
+    if (at.type == ATT_GENERAL2) L.TS = take(B * c->S * c->S);
+    if (at.type == ATT_CONCAT) { L.XC = take(T * Da); L.PC = take(T * Da); }
+    L.saved_total = p;
 
-// listener path: extra regions behind the listener-free ones (whose offsets do not move)
-struct DrnnLSaved { int64_t XL, QSP, Rl, Zl, Nl, HNl, total; };
-static DrnnLSaved drnn_lsaved(const ganffn_drnn_cfg* c, int P) {
-    DrnnLSaved s;
-    const int64_t T = (int64_t)c->S * c->B, H = c->H;
-    int64_t p = drnn_saved(c, P).total;
-    auto take = [&](int64_t n) { int64_t r = p; p += (n + 3) & ~int64_t(3); return r; };
-    s.XL = take(T * 3 * H); s.QSP = take(T * H);
-    s.Rl = take(T * P * H); s.Zl = take(T * P * H); s.Nl = take(T * P * H); s.HNl = take(T * P * H);
-    s.total = p;
-    return s;
-}
-struct DrnnLWs { int64_t GIl, GHl, dGIl, dGHl, dss, dqs, dQl, dhdirl, WTl, total; };
-static DrnnLWs drnn_lws(const ganffn_drnn_cfg* c, int P) {
-    DrnnLWs w;
-    const int64_t T = (int64_t)c->S * c->B, B = c->B, H = c->H;
-    int64_t p = drnn_ws(c, P).total;
-    auto take = [&](int64_t n) { int64_t r = p; p += (n + 3) & ~int64_t(3); return r; };
-    w.GIl = take(B * 3 * H); w.GHl = take(B * P * 3 * H);
-    w.dGIl = take(T * 3 * H); w.dGHl = take(T * P * 3 * H);
-    w.dss = take(B * H); w.dqs = take(B * H); w.dQl = take(B * P * H); w.dhdirl = take(B * P * H);
-    w.WTl = take(2 * H * 3 * H);                             // transposed l_wih[:, Dm:], l_whh (backward)
-    w.total = p;
-    return w;
-}
-
-// other attention types: regions behind the listener-free (or listener) ones, whose offsets do not move
-struct DrnnASaved { int64_t TS, XC, P, total; };
-static DrnnASaved drnn_asaved(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, bool listener, int P) {
-    DrnnASaved s{-1, -1, -1, 0};
-    const int64_t T = (int64_t)c->S * c->B, Da = at->Da;
-    int64_t p = listener ? drnn_lsaved(c, P).total : drnn_saved(c, P).total;
-    auto take = [&](int64_t n) { int64_t r = p; p += (n + 3) & ~int64_t(3); return r; };
-    if (at->type == GANFFN_DRNN_ATT_GENERAL2) s.TS = take((int64_t)c->B * c->S * c->S);
-    if (at->type == GANFFN_DRNN_ATT_CONCAT) { s.XC = take(T * Da); s.P = take(T * Da); }
-    s.total = p;
-    return s;
-}
-struct DrnnAWs { int64_t dXC, dP, dVp, total; };
-static DrnnAWs drnn_aws(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, bool listener, int P) {
-    DrnnAWs w{-1, -1, -1, 0};
-    const int64_t T = (int64_t)c->S * c->B, Da = at->Da;
-    int64_t p = listener ? drnn_lws(c, P).total : drnn_ws(c, P).total;
-    auto take = [&](int64_t n) { int64_t r = p; p += (n + 3) & ~int64_t(3); return r; };
-    if (at->type == GANFFN_DRNN_ATT_CONCAT) { w.dXC = take(T * Da); w.dP = take(T * Da); w.dVp = take(T * Da); }
-    w.total = p;
-    return w;
+    p = 0;
+    L.GI = take(B * 3 * H); L.GH = take(B * 3 * H); L.GIp = take(B * 3 * H); L.GHp = take(B * 3 * H);
+    L.dGIg = take(T * 3 * H); L.dGHg = take(T * 3 * H); L.dGIp = take(T * 3 * H); L.dGHp = take(T * 3 * H);
+    L.dGIe = take(T * 3 * He); L.dGHe = take(T * 3 * He);
+    L.dXA = take(T * H); L.dCT = take(B * H); L.dG = take(T1 * H);
+    L.dQa = take(B * P * H); L.dQb = take(B * P * H); L.dEa = take(B * He); L.dEb = take(B * He);
+    L.dQsel = take(B * H); L.dQSp = take(B * H); L.dQSg = take(B * H); L.dhdir = take(B * H); L.dhdirG = take(B * H); L.dQN = take(B * H);
+    L.GIe = take(T * 3 * He); L.dQNall = take(T * H);
+    L.WT = take(4 * H * 3 * H);
+    if (listener) {
+        L.GIl = take(B * 3 * H); L.GHl = take(B * P * 3 * H); L.dGIl = take(T * 3 * H); L.dGHl = take(T * P * 3 * H);
+        L.dss = take(B * H); L.dqs = take(B * H); L.dQl = take(B * P * H); L.dhdirl = take(B * P * H); L.WTl = take(2 * H * 3 * H);
+    }
+    if (at.type == ATT_CONCAT) { L.dXC = take(T * Da); L.dP = take(T * Da); L.dVp = take(T * Da); }
+    L.ws_total = p;
+    return L;
 }
 
 // maxB: 32 behind the entry points that always had that limit (they keep refusing 33 dialogues), GANFFN_MAX_DIALOGUES behind
@@ -1258,120 +1222,221 @@ static int memset_f(float* p, int64_t n, hipStream_t st) {
     return 0;
 }
 
+// What a forward or a backward call needs; the entry-point families differ only in what they put here.  Arrays have ndir entries.
+struct DrnnCall {
+    const ganffn_drnn_cfg* c; int ndir;
+    const float* const* U; const int32_t* const* spk; const float* const* mval;
+    const ganffn_drnn_params* prm; const ganffn_drnn_listener_params* lp;        // lp NULL: listener_state False
+    float* const* alpha; float* const* saved; float* const* workspace;           // (the backward only reads alpha and saved)
+    float* const* e_out;                                                         // forward
+    const float* const* d_e; float* const* dU; const ganffn_drnn_grads* grd; const ganffn_drnn_listener_grads* lg;   // backward; lg may be NULL
+    // context attention: always a descriptor and, per direction, its parameters and gradient pointers (a NULL member: the type
+    // has no such tensor / that gradient is not wanted).  ap[z].w and ag[z].w are THE attention weight and its gradient.
+    ganffn_drnn_att att; ganffn_drnn_att_params ap[2]; ganffn_drnn_att_grads ag[2];
+    bool general_dw[2];                         // general attention: ag[z].w is produced (each entry point has its rule)
+    int P = 2, maxB = 32;                       // parties; dialogue limit (GANFFN_MAX_DIALOGUES behind ganffn_drnn_batch_*)
+    const uint64_t* rng; uint64_t add; hipStream_t st;
+    // how the entry points fill it: one group of their arguments per setter
+    DrnnCall& inputs(const float* const* U_, const int32_t* const* spk_, const float* const* mval_) { U = U_; spk = spk_; mval = mval_; return *this; }
+    DrnnCall& cells(const ganffn_drnn_params* prm_, const ganffn_drnn_listener_params* lp_) { prm = prm_; lp = lp_; return *this; }
+    DrnnCall& grads(const ganffn_drnn_grads* grd_, const ganffn_drnn_listener_grads* lg_) { grd = grd_; lg = lg_; return *this; }
+    DrnnCall& limits(int parties, int max_dialogues) { P = parties; maxB = max_dialogues; return *this; }
+    DrnnCall& forward(float* const* e, float* const* al, float* const* sv, float* const* ws) { e_out = e; alpha = al; saved = sv; workspace = ws; return *this; }
+    DrnnCall& backward(const float* const* de, float* const* du, const float* const* al, const float* const* sv, float* const* ws) {
+        d_e = de; dU = du; alpha = const_cast<float* const*>(al); saved = const_cast<float* const*>(sv); workspace = ws;
+        return *this;
+    }
+};
+static inline DrnnCall drnn_call(const ganffn_drnn_cfg* c, int ndir, const uint64_t* rng, uint64_t add, void* stream) {
+    DrnnCall k{};
+    k.c = c; k.ndir = ndir; k.rng = rng; k.add = add; k.st = (hipStream_t)stream;
+    return k;
+}
+static int check_call(const DrnnCall& k) { return check_drnn(k.c, k.ndir, k.maxB) || check_parties(k.P) ? -1 : 0; }
+// what both drivers refuse before their first launch; pass = "fwd" | "bwd", arrays_given: none of the pass's arguments is NULL
+static int check_pass(const DrnnCall& k, const char* pass, bool arrays_given) {
+    GF_TRY(check_call(k));
+    GF_CHECK_ARG(arrays_given, "drnn_%s: null pointer", pass);
+    GF_CHECK_ARG(!(k.c->train && k.c->p > 0.f) || k.rng, "drnn_%s: rng required in train mode", pass);
+    for (int z = 0; k.lp && z < k.ndir; ++z)
+        GF_CHECK_ARG(k.lp[z].l_wih && k.lp[z].l_whh && k.lp[z].l_bih && k.lp[z].l_bhh, "drnn_listener_%s: direction %d: null listener parameter", pass, z);
+    return 0;
+}
+// the attention of the entry points without a descriptor (ganffn_drnn_fwd / _bwd, _listener_*): general, on the 13th cell tensor
+static inline void att_of_cell(DrnnCall& k) {
+    k.att = ganffn_drnn_att{ATT_GENERAL, 0};
+    for (int z = 0; z < 2 && z < k.ndir; ++z) {             // (nothing is checked yet: the driver refuses a null prm / grd)
+        if (k.prm) k.ap[z].w = k.prm[z].att_w;
+        if (k.grd) { k.ag[z].w = k.grd[z].att_w; k.general_dw[z] = k.grd[z].g_wih != nullptr; }      // produced iff g_wih's is given
+    }
+}
+// ... and of those with one (ganffn_drnn_att_* / _party_* / _batch_*): checked here, behind the call's own limits (the driver sees copies)
+static int att_of_descriptor(DrnnCall& k, const ganffn_drnn_att* at, const ganffn_drnn_att_params* ap, const ganffn_drnn_att_grads* ag) {
+    GF_TRY(check_call(k));
+    GF_TRY(check_att(k.c, at));
+    GF_TRY(check_att_params(at, ap, k.ndir));
+    k.att = *at;
+    for (int z = 0; z < k.ndir; ++z) {
+        if (ap) k.ap[z] = ap[z];
+        if (ag) { k.ag[z] = ag[z]; k.general_dw[z] = ag[z].w != nullptr; }      // produced iff agrads[z].w is given
+    }
+    return 0;
+}
+
+// One skinny product by name: out[M x N] = A[M x K] . W^T (NT launches, W [N x K]; NN launches: A . W, W [K x N])
+// (+ addend[M x N]) (+ bias[N]); out_acc: added into out (the second addend is the output block itself)
+struct Prod : SkinnyProb {
+    Prod& a(const float* p, int ld) { A = p; lda = ld; return *this; }
+    Prod& w(const float* p, int ld) { W = p; ldw = ld; return *this; }
+    Prod& plus(const float* p, int ld) { Cin = p; ldcin = ld; return *this; }
+    Prod& plus_bias(const float* b) { bias = b; return *this; }
+    Prod& out(float* p, int ld) { C = p; ldc = ld; return *this; }
+    Prod& out_acc(float* p, int ld) { Cin2 = p; return out(p, ld); }
+};
+static inline Prod prod(int M, int N, int K) { Prod q{}; q.M = M; q.N = N; q.K = K; return q; }
+
+// what every gate kernel's argument block starts with: Hc = the cell's width, r0 = t * B
+template <class Args> static inline void step_header(Args& a, const DrnnCall& k, int Hc, int64_t r0) {
+    a.B = k.c->B; a.H = Hc; a.row0 = (int)r0; a.p = k.c->p; a.train = k.c->train; a.P = k.P; a.rng = k.rng; a.add = k.add;
+}
+// ... and what the attention half of the gate + attention launch of step t starts with (the attention is that of step t + 1)
+template <class Args> static inline void attn_header(Args& a, const ganffn_drnn_cfg* c, int t) {
+    a.party_blocks = (c->B * c->H + DR_AT - 1) / DR_AT;
+    a.has_attn = t + 1 < c->S;
+    a.at.B = c->B; a.at.H = c->H; a.at.S = c->S; a.at.t = t + 1;
+}
+
+// The gate + attention launch of a step: THE choice of its kernel <PARTY, ATT>, for both passes.  PARTY = 2 with listener state
+// (the listener kernel then writes Q / QN / QS); general, simple and dot score <query, g_j> and run the plain kernels, general2
+// and concat the x kernels with their own arguments (AttnX) behind the plain ones.  (PARTY = 1 and general2 are named first: the kernels
+// lie in the code object in the order they are instantiated in.)
+struct StepFwd {
+    typedef GateAttnArgs Args; typedef GateAttnXArgs XArgs; static constexpr bool bwd = false;
+    static auto plain(bool listener) { return !listener ? drnn_gates_attn_fwd_kernel : drnn_gates_attn_lfwd_kernel; }
+    template <int ATT> static auto extra(bool listener) { return !listener ? drnn_gates_attnx_fwd_kernel<1, ATT> : drnn_gates_attnx_fwd_kernel<2, ATT>; }
+};
+struct StepBwd {
+    typedef GateAttnBwdArgs Args; typedef GateAttnXBwdArgs XArgs; static constexpr bool bwd = true;
+    static auto plain(bool listener) { return !listener ? drnn_gates_attn_bwd_kernel : drnn_gates_attn_lbwd_kernel; }
+    template <int ATT> static auto extra(bool listener) { return !listener ? drnn_gates_attnx_bwd_kernel<1, ATT> : drnn_gates_attnx_bwd_kernel<2, ATT>; }
+};
+template <class Step> static inline void launch_gates_attn(const typename Step::Args& a, const DrnnCall& k, const DrnnLayout& L) {
+    const bool listener = k.lp != nullptr, cc = k.att.type == ATT_CONCAT;
+    const dim3 grid(a.party_blocks + a.at.B, 1, k.ndir);
+    if (k.att.type == ATT_GENERAL2 || cc) {
+        typename Step::XArgs gx;
+        gx.a = a;
+        gx.x.ldw = k.c->H + k.c->Dm; gx.x.Da = k.att.Da;
+        for (int z = 0; z < k.ndir; ++z) {
+            float* sv = k.saved[z]; float* ws = k.workspace[z];
+            gx.x.d[z] = AttnXDir{cc ? nullptr : sv + L.TS, cc ? sv + L.PC : nullptr, cc ? sv + L.XC : nullptr, k.ap[z].w, k.ap[z].v,
+                                 cc && Step::bwd ? ws + L.dP : nullptr, cc && Step::bwd ? ws + L.dXC : nullptr, cc && Step::bwd ? ws + L.dVp : nullptr};
+        }
+        auto kern = k.att.type == ATT_GENERAL2 ? Step::template extra<ATT_GENERAL2>(listener) : Step::template extra<ATT_CONCAT>(listener);
+        hipLaunchKernelGGL(kern, grid, dim3(DR_AT), 0, k.st, gx);
+    } else {
+        auto kern = Step::plain(listener);
+        hipLaunchKernelGGL(kern, grid, dim3(DR_AT), 0, k.st, a);
+    }
+}
+
 }  // namespace ganffn
 
 using namespace ganffn;
 
+static int skinny_copies(bool nn, int copies, const SkinnyProb& q, hipStream_t st) {      // copy i: weight i, output i
+    SkinnyGroup sg;
+    for (int i = 0; i < copies; ++i) sg.p[i] = Prod{q}.w(q.W + (size_t)i * q.N * q.K, q.ldw).out(q.C + (size_t)i * q.M * q.N, q.ldc);
+    return launch_skinny(sg, copies, nn, st);
+}
 // test / measurement hook: one skinny product C[M x N] = A[M x K] W^T (nn = 0, W [N x K]) or A W (nn = 1, W [K x N]),
 // replicated `copies` (<= 8) times in one launch like a step of the recurrence (2 directions x 2 cells x 2 products)
 extern "C" int ganffn_drnn_skinny(int nn, int copies, const float* A, const float* W, float* C, int M, int N, int K, void* stream) {
     GF_CHECK_ARG(M >= 1 && M <= 32, "drnn_skinny: M=%d (1 .. 32; ganffn_drnn_skinny_batch takes more)", M);
     GF_CHECK_ARG(A && W && C && copies >= 1 && copies <= 8, "drnn_skinny: bad arguments");
-    SkinnyGroup sg;
-    for (int i = 0; i < copies; ++i)
-        sg.p[i] = SkinnyProb{A, K, W + (size_t)i * N * K, nn ? N : K, nullptr, 0, nullptr, nullptr, C + (size_t)i * M * N, N, M, N, K};
-    return launch_skinny(sg, copies, nn != 0, (hipStream_t)stream);
+    return skinny_copies(nn != 0, copies, prod(M, N, K).a(A, K).w(W, nn ? N : K).out(C, N), (hipStream_t)stream);
 }
 
 // the same with the dialogue-tile axis: M <= GANFFN_MAX_DIALOGUES (M <= 32 is the launch above)
 extern "C" int ganffn_drnn_skinny_batch(int nn, int copies, const float* A, const float* W, float* C, int M, int N, int K, void* stream) {
     GF_CHECK_ARG(A && W && C && copies >= 1 && copies <= 8, "drnn_skinny_batch: bad arguments");
     GF_CHECK_ARG(M >= 1 && M <= GANFFN_MAX_DIALOGUES && N >= 1 && K >= 4, "drnn_skinny_batch: M=%d (1 .. %d) N=%d K=%d", M, GANFFN_MAX_DIALOGUES, N, K);
-    SkinnyGroup sg;
-    for (int i = 0; i < copies; ++i)
-        sg.p[i] = SkinnyProb{A, K, W + (size_t)i * N * K, nn ? N : K, nullptr, 0, nullptr, nullptr, C + (size_t)i * M * N, N, M, N, K};
-    return launch_skinny(sg, copies, nn != 0, (hipStream_t)stream);
+    return skinny_copies(nn != 0, copies, prod(M, N, K).a(A, K).w(W, nn ? N : K).out(C, N), (hipStream_t)stream);
 }
 
-extern "C" int64_t ganffn_drnn_saved_floats(const ganffn_drnn_cfg* c) { return check_drnn(c, 1) ? -1 : drnn_saved(c, 2).total; }
-extern "C" int64_t ganffn_drnn_workspace_floats(const ganffn_drnn_cfg* c) { return check_drnn(c, 1) ? -1 : drnn_ws(c, 2).total; }
-extern "C" int64_t ganffn_drnn_listener_saved_floats(const ganffn_drnn_cfg* c) { return check_drnn(c, 1) ? -1 : drnn_lsaved(c, 2).total; }
-extern "C" int64_t ganffn_drnn_listener_workspace_floats(const ganffn_drnn_cfg* c) { return check_drnn(c, 1) ? -1 : drnn_lws(c, 2).total; }
+// sizes per direction: the layout's two totals (no descriptor: general attention; no party count: two parties)
+static const ganffn_drnn_att ATT_OF_CELL{ATT_GENERAL, 0};
+extern "C" int64_t ganffn_drnn_saved_floats(const ganffn_drnn_cfg* c) { return check_drnn(c, 1) ? -1 : drnn_layout(c, ATT_OF_CELL, false, 2).saved_total; }
+extern "C" int64_t ganffn_drnn_workspace_floats(const ganffn_drnn_cfg* c) { return check_drnn(c, 1) ? -1 : drnn_layout(c, ATT_OF_CELL, false, 2).ws_total; }
+extern "C" int64_t ganffn_drnn_listener_saved_floats(const ganffn_drnn_cfg* c) { return check_drnn(c, 1) ? -1 : drnn_layout(c, ATT_OF_CELL, true, 2).saved_total; }
+extern "C" int64_t ganffn_drnn_listener_workspace_floats(const ganffn_drnn_cfg* c) { return check_drnn(c, 1) ? -1 : drnn_layout(c, ATT_OF_CELL, true, 2).ws_total; }
 extern "C" int64_t ganffn_drnn_att_saved_floats(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int listener) {
-    return check_drnn(c, 1) || check_att(c, at) ? -1 : drnn_asaved(c, at, listener != 0, 2).total;
+    return check_drnn(c, 1) || check_att(c, at) ? -1 : drnn_layout(c, *at, listener != 0, 2).saved_total;
 }
 extern "C" int64_t ganffn_drnn_att_workspace_floats(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int listener) {
-    return check_drnn(c, 1) || check_att(c, at) ? -1 : drnn_aws(c, at, listener != 0, 2).total;
+    return check_drnn(c, 1) || check_att(c, at) ? -1 : drnn_layout(c, *at, listener != 0, 2).ws_total;
 }
 extern "C" int64_t ganffn_drnn_party_saved_floats(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int listener, int parties) {
-    return check_drnn(c, 1) || check_att(c, at) || check_parties(parties) ? -1 : drnn_asaved(c, at, listener != 0, parties).total;
+    return check_drnn(c, 1) || check_att(c, at) || check_parties(parties) ? -1 : drnn_layout(c, *at, listener != 0, parties).saved_total;
 }
 extern "C" int64_t ganffn_drnn_party_workspace_floats(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int listener, int parties) {
-    return check_drnn(c, 1) || check_att(c, at) || check_parties(parties) ? -1 : drnn_aws(c, at, listener != 0, parties).total;
+    return check_drnn(c, 1) || check_att(c, at) || check_parties(parties) ? -1 : drnn_layout(c, *at, listener != 0, parties).ws_total;
+}
+// 1 <= B <= GANFFN_MAX_DIALOGUES dialogues (ganffn_drnn_batch_*): the same functions of B
+extern "C" int64_t ganffn_drnn_batch_saved_floats(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int listener, int parties) {
+    return check_drnn(c, 1, GANFFN_MAX_DIALOGUES) || check_att(c, at) || check_parties(parties) ? -1 : drnn_layout(c, *at, listener != 0, parties).saved_total;
+}
+extern "C" int64_t ganffn_drnn_batch_workspace_floats(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int listener, int parties) {
+    return check_drnn(c, 1, GANFFN_MAX_DIALOGUES) || check_att(c, at) || check_parties(parties) ? -1 : drnn_layout(c, *at, listener != 0, parties).ws_total;
 }
 
 // ------------------------------------------------------------------------------------------
 // forward
 // ------------------------------------------------------------------------------------------
-// lp == NULL: listener_state False (ganffn_drnn_fwd); otherwise the listener path (ganffn_drnn_listener_fwd)
-// at == NULL: general attention with prm[z].att_w (ganffn_drnn_fwd / _listener_fwd); otherwise ganffn_drnn_att_fwd
-static int drnn_fwd(const ganffn_drnn_cfg* c, int ndir, const float* const* U, const int32_t* const* spk,
-                    const float* const* mval, const ganffn_drnn_params* prm, const ganffn_drnn_listener_params* lp,
-                    float* const* e_out, float* const* alpha, float* const* saved, float* const* workspace,
-                    const uint64_t* rng, uint64_t add, void* stream, const ganffn_drnn_att* at = nullptr,
-                    const ganffn_drnn_att_params* ap = nullptr, int P = 2, int maxB = 32) {
-    GF_TRY(check_drnn(c, ndir, maxB));
-    GF_TRY(check_parties(P));
-    const int att = at ? at->type : ATT_GENERAL;
-    if (at) {
-        GF_TRY(check_att(c, at));
-        GF_TRY(check_att_params(at, ap, ndir));
-    }
-    const ganffn_drnn_att gen{ATT_GENERAL, 0};
-    const DrnnASaved sa = drnn_asaved(c, at ? at : &gen, lp != nullptr, P);
-    const int Da = at ? at->Da : 0;
-    GF_CHECK_ARG(U && spk && mval && prm && e_out && alpha && saved && workspace, "drnn_fwd: null pointer");
-    GF_CHECK_ARG(!(c->train && c->p > 0.f) || rng, "drnn_fwd: rng required in train mode");
-    hipStream_t st = (hipStream_t)stream;
-    const int S = c->S, B = c->B, Dm = c->Dm, H = c->H, He = c->He, T = S * B;
-    const DrnnSaved so = drnn_saved(c, P);
-    const DrnnWs wo = drnn_ws(c, P);
-    const DrnnLSaved sl = drnn_lsaved(c, P);
-    const DrnnLWs wl = drnn_lws(c, P);
-    if (lp)
-        for (int z = 0; z < ndir; ++z)
-            GF_CHECK_ARG(lp[z].l_wih && lp[z].l_whh && lp[z].l_bih && lp[z].l_bhh, "drnn_listener_fwd: direction %d: null listener parameter", z);
+static int drnn_fwd(const DrnnCall& k) {
+    const ganffn_drnn_cfg* c = k.c;
+    const ganffn_drnn_params* prm = k.prm;
+    const ganffn_drnn_listener_params* lp = k.lp;
+    const float* const* U = k.U; const int32_t* const* spk = k.spk; const float* const* mval = k.mval;
+    float* const* alpha = k.alpha; float* const* saved = k.saved; float* const* workspace = k.workspace;
+    GF_TRY(check_pass(k, "fwd", U && spk && mval && prm && k.e_out && alpha && saved && workspace));
+    const int ndir = k.ndir, P = k.P, att = k.att.type, Da = k.att.Da, S = c->S, B = c->B, Dm = c->Dm, H = c->H, He = c->He, T = S * B;
+    const DrnnLayout L = drnn_layout(c, k.att, lp != nullptr, P);
+    hipStream_t st = k.st;
     for (int z = 0; z < ndir; ++z) {
-        GF_CHECK_ARG(U[z] && spk[z] && mval[z] && e_out[z] && alpha[z] && saved[z] && workspace[z] && aligned16(U[z]) &&
+        GF_CHECK_ARG(U[z] && spk[z] && mval[z] && k.e_out[z] && alpha[z] && saved[z] && workspace[z] && aligned16(U[z]) &&
                      aligned16(saved[z]) && aligned16(workspace[z]), "drnn_fwd: direction %d: null or misaligned buffer", z);
         float* sv = saved[z];
-        // U-only terms for all steps: XG = U Wih_g[:, :Dm]^T + bih_g, XP likewise, XA = U Watt^T
-        EpiArgs e;
-        e.bias = prm[z].g_bih;
-        GF_TRY(launch_gemm_nt(U[z], Dm, prm[z].g_wih, Dm + H, sv + so.XG, 3 * H, T, 3 * H, Dm, EPI_NONE, e, st));
-        e.bias = prm[z].p_bih;
-        GF_TRY(launch_gemm_nt(U[z], Dm, prm[z].p_wih, Dm + H, sv + so.XP, 3 * H, T, 3 * H, Dm, EPI_NONE, e, st));
-        e.bias = nullptr;
-        const float* aw = at ? (ap ? ap[z].w : nullptr) : prm[z].att_w;
-        if (att == ATT_GENERAL) {
-            GF_TRY(launch_gemm_nt(U[z], Dm, aw, Dm, sv + so.XA, H, T, H, Dm, EPI_NONE, e, st));
-        } else if (att == ATT_GENERAL2) {          // query W U_t + b
-            e.bias = ap[z].b;
-            GF_TRY(launch_gemm_nt(U[z], Dm, aw, Dm, sv + so.XA, H, T, H, Dm, EPI_NONE, e, st));
-            e.bias = nullptr;
+        const float* aw = k.ap[z].w;
+        // U-only terms for all steps, out[T x N] = U W[:, :Dm]^T (+ bias): XG (with bih_g), XP likewise, XA = the attention's query
+        auto u_term = [&](const float* W, int ldw, const float* bias, float* out, int N) {
+            EpiArgs e;
+            e.bias = bias;
+            return launch_gemm_nt(U[z], Dm, W, ldw, out, N, T, N, Dm, EPI_NONE, e, st);
+        };
+        GF_TRY(u_term(prm[z].g_wih, Dm + H, prm[z].g_bih, sv + L.XG, 3 * H));
+        GF_TRY(u_term(prm[z].p_wih, Dm + H, prm[z].p_bih, sv + L.XP, 3 * H));
+        if (att == ATT_GENERAL || att == ATT_GENERAL2) {      // query W U_t, general2: + b
+            GF_TRY(u_term(aw, Dm, att == ATT_GENERAL2 ? k.ap[z].b : nullptr, sv + L.XA, H));
         } else if (att == ATT_DOT) {               // query U_t itself (D_m == D_g)
-            hipError_t er = hipMemcpyAsync(sv + so.XA, U[z], (size_t)T * H * sizeof(float), hipMemcpyDeviceToDevice, st);
+            hipError_t er = hipMemcpyAsync(sv + L.XA, U[z], (size_t)T * H * sizeof(float), hipMemcpyDeviceToDevice, st);
             if (er != hipSuccess) return fail((int)er, "drnn_fwd: memcpy failed: %s", hipGetErrorString(er));
         } else if (att == ATT_SIMPLE) {            // constant query w
-            hipLaunchKernelGGL(drnn_bcast_row_kernel, dim3((unsigned)(((int64_t)T * H + 255) / 256)), dim3(256), 0, st, aw, sv + so.XA, (int64_t)T, H);
+            hipLaunchKernelGGL(drnn_bcast_row_kernel, dim3((unsigned)(((int64_t)T * H + 255) / 256)), dim3(256), 0, st, aw, sv + L.XA, (int64_t)T, H);
             GF_LAUNCH_CHECK();
         } else {                                   // concat: X = U W_u^T, W_u = transform.weight[:, D_g:]
-            GF_TRY(launch_gemm_nt(U[z], Dm, aw + H, H + Dm, sv + sa.XC, Da, T, Da, Dm, EPI_NONE, e, st));
+            GF_TRY(u_term(aw + H, H + Dm, nullptr, sv + L.XC, Da));
         }
-        if (lp) {      // listener: XL = U Wih_l[:, :Dm]^T + bih_l
-            e.bias = lp[z].l_bih;
-            GF_TRY(launch_gemm_nt(U[z], Dm, lp[z].l_wih, Dm + H, sv + sl.XL, 3 * H, T, 3 * H, Dm, EPI_NONE, e, st));
-            e.bias = nullptr;
-        }
+        if (lp) GF_TRY(u_term(lp[z].l_wih, Dm + H, lp[z].l_bih, sv + L.XL, 3 * H));      // listener: XL, with bih_l
         // zero initial states: G[0], Q[0], E[0], QS[0], CT[0]; alpha (entries j >= t stay zero)
-        GF_TRY(memset_f(sv + so.G, (int64_t)B * H, st));
-        GF_TRY(memset_f(sv + so.Q, (int64_t)B * P * H, st));
-        GF_TRY(memset_f(sv + so.E, (int64_t)B * He, st));
-        GF_TRY(memset_f(sv + so.QS, (int64_t)B * H, st));
-        GF_TRY(memset_f(sv + so.CT, (int64_t)B * H, st));
+        GF_TRY(memset_f(sv + L.G, (int64_t)B * H, st));
+        GF_TRY(memset_f(sv + L.Q, (int64_t)B * P * H, st));
+        GF_TRY(memset_f(sv + L.E, (int64_t)B * He, st));
+        GF_TRY(memset_f(sv + L.QS, (int64_t)B * H, st));
+        GF_TRY(memset_f(sv + L.CT, (int64_t)B * H, st));
         GF_TRY(memset_f(alpha[z], (int64_t)B * S * S, st));
     }
-    const dim3 gH((B * H + 255) / 256, 1, ndir), gHe((B * He + 255) / 256, 1, ndir);
+    const dim3 gHe((B * He + 255) / 256, 1, ndir);
     const bool echain = He <= EC_MAXHE;          // emotion cell as one chain per dialogue after the main loop
     // A step is two launches: the four products of the global and the party cell (the party cell needs c_t but not g_t, the
     // global cell neither: they are independent within a step), then both cells' gate math with the context attention of
@@ -1379,396 +1444,299 @@ static int drnn_fwd(const ganffn_drnn_cfg* c, int ndir, const float* const* U, c
     for (int t = 0; t < S; ++t) {
         const int64_t r0 = (int64_t)t * B, r1 = (int64_t)(t + 1) * B;
         SkinnyGroup sg;
-        // ---- global cell: GI = XG[t] + QS[t] Wih_g[:, Dm:]^T ; GH = G[t] Whh_g^T + bhh_g
-        // ---- party cell (speaker): GI = XP[t] + CT[t] Wih_p[:, Dm:]^T ; GH = QS[t] Whh_p^T + bhh_p
         for (int z = 0; z < ndir; ++z) {
             float* sv = saved[z]; float* ws = workspace[z];
-            sg.p[4 * z] = SkinnyProb{sv + so.QS + r0 * H, H, prm[z].g_wih + Dm, Dm + H, sv + so.XG + r0 * 3 * H, 3 * H, nullptr, nullptr, ws + wo.GI, 3 * H, B, 3 * H, H};
-            sg.p[4 * z + 1] = SkinnyProb{sv + so.G + r0 * H, H, prm[z].g_whh, H, nullptr, 0, nullptr, prm[z].g_bhh, ws + wo.GH, 3 * H, B, 3 * H, H};
-            sg.p[4 * z + 2] = SkinnyProb{sv + so.CT + r0 * H, H, prm[z].p_wih + Dm, Dm + H, sv + so.XP + r0 * 3 * H, 3 * H, nullptr, nullptr, ws + wo.GIp, 3 * H, B, 3 * H, H};
-            sg.p[4 * z + 3] = SkinnyProb{sv + so.QS + r0 * H, H, prm[z].p_whh, H, nullptr, 0, nullptr, prm[z].p_bhh, ws + wo.GHp, 3 * H, B, 3 * H, H};
+            // ---- global cell: GI = QS[t] Wih_g[:, Dm:]^T + XG[t] ; GH = G[t] Whh_g^T + bhh_g
+            sg.p[4 * z] = prod(B, 3 * H, H).a(sv + L.QS + r0 * H, H).w(prm[z].g_wih + Dm, Dm + H).plus(sv + L.XG + r0 * 3 * H, 3 * H).out(ws + L.GI, 3 * H);
+            sg.p[4 * z + 1] = prod(B, 3 * H, H).a(sv + L.G + r0 * H, H).w(prm[z].g_whh, H).plus_bias(prm[z].g_bhh).out(ws + L.GH, 3 * H);
+            // ---- party cell (speaker): GI = CT[t] Wih_p[:, Dm:]^T + XP[t] ; GH = QS[t] Whh_p^T + bhh_p
+            sg.p[4 * z + 2] = prod(B, 3 * H, H).a(sv + L.CT + r0 * H, H).w(prm[z].p_wih + Dm, Dm + H).plus(sv + L.XP + r0 * 3 * H, 3 * H).out(ws + L.GIp, 3 * H);
+            sg.p[4 * z + 3] = prod(B, 3 * H, H).a(sv + L.QS + r0 * H, H).w(prm[z].p_whh, H).plus_bias(prm[z].p_bhh).out(ws + L.GHp, 3 * H);
         }
         GF_TRY(launch_skinny(sg, 4 * ndir, false, st));
-        GateArgs ga, gp;
-        ga.B = B; ga.H = H; ga.row0 = (int)r0; ga.p = c->p; ga.train = c->train; ga.P = P; ga.rng = rng; ga.add = add;
-        gp = ga;
+        GateAttnArgs gaa;
+        GateArgs &ga = gaa.g, &gp = gaa.p;
+        step_header(ga, k, H, r0);
+        step_header(gp, k, H, r0);
+        attn_header(gaa, c, t);
         for (int z = 0; z < ndir; ++z) {
             float* sv = saved[z]; float* ws = workspace[z];
-            ga.d[z] = GateDir{ws + wo.GI, ws + wo.GH, sv + so.G + r0 * H, sv + so.Rg + r0 * H, sv + so.Zg + r0 * H, sv + so.Ng + r0 * H,
-                              sv + so.HNg + r0 * H, sv + so.G + r1 * H, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+            ga.d[z] = GateDir{ws + L.GI, ws + L.GH, sv + L.G + r0 * H, sv + L.Rg + r0 * H, sv + L.Zg + r0 * H, sv + L.Ng + r0 * H,
+                              sv + L.HNg + r0 * H, sv + L.G + r1 * H, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                               SITE_DRNN_G + 4u * z};
-            gp.d[z] = GateDir{ws + wo.GIp, ws + wo.GHp, sv + so.QS + r0 * H, sv + so.Rp + r0 * H, sv + so.Zp + r0 * H, sv + so.Np + r0 * H,
-                              sv + so.HNp + r0 * H, nullptr, spk[z] + r0, t + 1 < S ? spk[z] + r1 : nullptr, mval[z] + r0,
-                              sv + so.Q + r0 * P * H, sv + so.Q + r1 * P * H, sv + so.QN + r0 * H, sv + so.QS + r1 * H,
+            gp.d[z] = GateDir{ws + L.GIp, ws + L.GHp, sv + L.QS + r0 * H, sv + L.Rp + r0 * H, sv + L.Zp + r0 * H, sv + L.Np + r0 * H,
+                              sv + L.HNp + r0 * H, nullptr, spk[z] + r0, t + 1 < S ? spk[z] + r1 : nullptr, mval[z] + r0,
+                              sv + L.Q + r0 * P * H, sv + L.Q + r1 * P * H, sv + L.QN + r0 * H, sv + L.QS + r1 * H,
                               SITE_DRNN_P + 4u * z};
-            if (lp) gp.d[z].QN = sv + sl.QSP + r0 * H;       // qs only; the listener kernel below writes Q / QN / QS
+            if (lp) gp.d[z].QN = sv + L.QSP + r0 * H;       // qs only; the listener kernel below writes Q / QN / QS
+            gaa.at.d[z] = AttnDir{sv + L.XA + r1 * H, sv + L.G, sv + L.CT + r1 * H, alpha[z]};
         }
-        GateAttnArgs gaa;
-        gaa.g = ga; gaa.p = gp;
-        gaa.party_blocks = (B * H + DR_AT - 1) / DR_AT;
-        gaa.has_attn = t + 1 < S;
-        gaa.at.B = B; gaa.at.H = H; gaa.at.S = S; gaa.at.t = t + 1;
-        for (int z = 0; z < ndir; ++z)
-            gaa.at.d[z] = AttnDir{saved[z] + so.XA + r1 * H, saved[z] + so.G, saved[z] + so.CT + r1 * H, alpha[z]};
-        const dim3 gA(gaa.party_blocks + B, 1, ndir);
-        if (att == ATT_GENERAL2 || att == ATT_CONCAT) {
-            GateAttnXArgs gx;
-            gx.a = gaa;
-            gx.x.ldw = H + Dm; gx.x.Da = Da;
-            for (int z = 0; z < ndir; ++z)
-                gx.x.d[z] = AttnXDir{att == ATT_GENERAL2 ? saved[z] + sa.TS : nullptr, att == ATT_CONCAT ? saved[z] + sa.P : nullptr,
-                                     att == ATT_CONCAT ? saved[z] + sa.XC : nullptr, ap[z].w, ap[z].v, nullptr, nullptr, nullptr};
-            if (att == ATT_GENERAL2 && !lp) hipLaunchKernelGGL((drnn_gates_attnx_fwd_kernel<1, ATT_GENERAL2>), gA, dim3(DR_AT), 0, st, gx);
-            else if (att == ATT_GENERAL2) hipLaunchKernelGGL((drnn_gates_attnx_fwd_kernel<2, ATT_GENERAL2>), gA, dim3(DR_AT), 0, st, gx);
-            else if (!lp) hipLaunchKernelGGL((drnn_gates_attnx_fwd_kernel<1, ATT_CONCAT>), gA, dim3(DR_AT), 0, st, gx);
-            else hipLaunchKernelGGL((drnn_gates_attnx_fwd_kernel<2, ATT_CONCAT>), gA, dim3(DR_AT), 0, st, gx);
-            GF_LAUNCH_CHECK();
-        } else if (!lp) {
-            hipLaunchKernelGGL(drnn_gates_attn_fwd_kernel, dim3(gaa.party_blocks + B, 1, ndir), dim3(DR_AT), 0, st, gaa);
-            GF_LAUNCH_CHECK();
-        } else {
-            hipLaunchKernelGGL(drnn_gates_attn_lfwd_kernel, dim3(gaa.party_blocks + B, 1, ndir), dim3(DR_AT), 0, st, gaa);
-            GF_LAUNCH_CHECK();
-        }
+        launch_gates_attn<StepFwd>(gaa, k, L);
+        GF_LAUNCH_CHECK();
         if (lp) {
-            // ---- listener: GI_l = XL[t] + QSP[t] Wih_l[:, Dm:]^T ; GH_l[p] = Q[t][p] Whh_l^T + bhh_l (p = 0 .. P-1)
+            // ---- listener: GI_l = QSP[t] Wih_l[:, Dm:]^T + XL[t] ; GH_l[p] = Q[t][p] Whh_l^T + bhh_l (p = 0 .. P-1)
             SkinnyProb lpr[2 * (1 + DR_MAXP)];
+            LGateArgs la;
+            step_header(la, k, H, r0);
             for (int z = 0; z < ndir; ++z) {
                 float* sv = saved[z]; float* ws = workspace[z];
-                lpr[(1 + P) * z] = SkinnyProb{sv + sl.QSP + r0 * H, H, lp[z].l_wih + Dm, Dm + H, sv + sl.XL + r0 * 3 * H, 3 * H, nullptr, nullptr,
-                                              ws + wl.GIl, 3 * H, B, 3 * H, H};
+                lpr[(1 + P) * z] = prod(B, 3 * H, H).a(sv + L.QSP + r0 * H, H).w(lp[z].l_wih + Dm, Dm + H).plus(sv + L.XL + r0 * 3 * H, 3 * H).out(ws + L.GIl, 3 * H);
                 for (int pa = 0; pa < P; ++pa)
-                    lpr[(1 + P) * z + 1 + pa] = SkinnyProb{sv + so.Q + r0 * P * H + pa * H, P * H, lp[z].l_whh, H, nullptr, 0, nullptr,
-                                                           lp[z].l_bhh, ws + wl.GHl + pa * 3 * H, P * 3 * H, B, 3 * H, H};
+                    lpr[(1 + P) * z + 1 + pa] = prod(B, 3 * H, H).a(sv + L.Q + r0 * P * H + pa * H, P * H).w(lp[z].l_whh, H).plus_bias(lp[z].l_bhh)
+                                                    .out(ws + L.GHl + pa * 3 * H, P * 3 * H);
+                la.d[z] = LGateDir{ws + L.GIl, ws + L.GHl, sv + L.Q + r0 * P * H, sv + L.QSP + r0 * H, sv + L.Rl + r0 * P * H,
+                                   sv + L.Zl + r0 * P * H, sv + L.Nl + r0 * P * H, sv + L.HNl + r0 * P * H, spk[z] + r0,
+                                   t + 1 < S ? spk[z] + r1 : nullptr, mval[z] + r0, sv + L.Q + r1 * P * H, sv + L.QN + r0 * H,
+                                   sv + L.QS + r1 * H, SITE_DRNN_L + 4u * z};
             }
             GF_TRY(launch_skinny_nt(lpr, (1 + P) * ndir, st));
-            LGateArgs la;
-            la.B = B; la.H = H; la.row0 = (int)r0; la.p = c->p; la.train = c->train; la.P = P; la.rng = rng; la.add = add;
-            for (int z = 0; z < ndir; ++z) {
-                float* sv = saved[z]; float* ws = workspace[z];
-                la.d[z] = LGateDir{ws + wl.GIl, ws + wl.GHl, sv + so.Q + r0 * P * H, sv + sl.QSP + r0 * H, sv + sl.Rl + r0 * P * H,
-                                   sv + sl.Zl + r0 * P * H, sv + sl.Nl + r0 * P * H, sv + sl.HNl + r0 * P * H, spk[z] + r0,
-                                   t + 1 < S ? spk[z] + r1 : nullptr, mval[z] + r0, sv + so.Q + r1 * P * H, sv + so.QN + r0 * H,
-                                   sv + so.QS + r1 * H, SITE_DRNN_L + 4u * z};
-            }
             hipLaunchKernelGGL(drnn_listener_fwd_kernel, dim3((B * P * H + 255) / 256, 1, ndir), dim3(256), 0, st, la);
             GF_LAUNCH_CHECK();
         }
         if (echain) continue;
         // ---- emotion cell: GI = QN[t] Wih_e^T + bih_e ; GH = E[t] Whh_e^T + bhh_e
+        GateArgs ge;
+        step_header(ge, k, He, r0);
         for (int z = 0; z < ndir; ++z) {
             float* sv = saved[z]; float* ws = workspace[z];
-            sg.p[2 * z] = SkinnyProb{sv + so.QN + r0 * H, H, prm[z].e_wih, H, nullptr, 0, nullptr, prm[z].e_bih, ws + wo.GI, 3 * He, B, 3 * He, H};
-            sg.p[2 * z + 1] = SkinnyProb{sv + so.E + r0 * He, He, prm[z].e_whh, He, nullptr, 0, nullptr, prm[z].e_bhh, ws + wo.GH, 3 * He, B, 3 * He, He};
-        }
-        GF_TRY(launch_skinny(sg, 2 * ndir, false, st));
-        ga.H = He;
-        for (int z = 0; z < ndir; ++z) {
-            float* sv = saved[z]; float* ws = workspace[z];
-            ga.d[z] = GateDir{ws + wo.GI, ws + wo.GH, sv + so.E + r0 * He, sv + so.Re + r0 * He, sv + so.Ze + r0 * He, sv + so.Ne + r0 * He,
-                              sv + so.HNe + r0 * He, sv + so.E + r1 * He, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+            sg.p[2 * z] = prod(B, 3 * He, H).a(sv + L.QN + r0 * H, H).w(prm[z].e_wih, H).plus_bias(prm[z].e_bih).out(ws + L.GI, 3 * He);
+            sg.p[2 * z + 1] = prod(B, 3 * He, He).a(sv + L.E + r0 * He, He).w(prm[z].e_whh, He).plus_bias(prm[z].e_bhh).out(ws + L.GH, 3 * He);
+            ge.d[z] = GateDir{ws + L.GI, ws + L.GH, sv + L.E + r0 * He, sv + L.Re + r0 * He, sv + L.Ze + r0 * He, sv + L.Ne + r0 * He,
+                              sv + L.HNe + r0 * He, sv + L.E + r1 * He, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                               SITE_DRNN_E + 4u * z};
         }
-        hipLaunchKernelGGL(gru_gate_fwd_kernel<0>, gHe, dim3(256), 0, st, ga);
+        GF_TRY(launch_skinny(sg, 2 * ndir, false, st));
+        hipLaunchKernelGGL(gru_gate_fwd_kernel<0>, gHe, dim3(256), 0, st, ge);
         GF_LAUNCH_CHECK();
     }
     if (echain) {
         EchainArgs ea;
-        ea.S = S; ea.B = B; ea.He = He; ea.p = c->p; ea.train = c->train; ea.rng = rng; ea.add = add;
+        ea.S = S; ea.B = B; ea.He = He; ea.p = c->p; ea.train = c->train; ea.rng = k.rng; ea.add = k.add;
         for (int z = 0; z < ndir; ++z) {
             float* sv = saved[z]; float* ws = workspace[z];
             EpiArgs e;
             e.bias = prm[z].e_bih;                 // GI_e of every step: one GEMM over all T rows of q_t[spk]
-            GF_TRY(launch_gemm_nt(sv + so.QN, H, prm[z].e_wih, H, ws + wo.GIe, 3 * He, T, 3 * He, H, EPI_NONE, e, st));
-            ea.d[z] = EchainDir{ws + wo.GIe, prm[z].e_whh, prm[z].e_bhh, sv + so.E, sv + so.Re, sv + so.Ze, sv + so.Ne, sv + so.HNe,
+            GF_TRY(launch_gemm_nt(sv + L.QN, H, prm[z].e_wih, H, ws + L.GIe, 3 * He, T, 3 * He, H, EPI_NONE, e, st));
+            ea.d[z] = EchainDir{ws + L.GIe, prm[z].e_whh, prm[z].e_bhh, sv + L.E, sv + L.Re, sv + L.Ze, sv + L.Ne, sv + L.HNe,
                                 SITE_DRNN_E + 4u * z};
         }
         hipLaunchKernelGGL(drnn_echain_fwd_kernel, dim3(B, 1, ndir), dim3(EC_NT), 0, st, ea);
         GF_LAUNCH_CHECK();
     }
     for (int z = 0; z < ndir; ++z) {
-        hipError_t er = hipMemcpyAsync(e_out[z], saved[z] + so.E + (int64_t)B * He, (size_t)T * He * sizeof(float), hipMemcpyDeviceToDevice, st);
+        hipError_t er = hipMemcpyAsync(k.e_out[z], saved[z] + L.E + (int64_t)B * He, (size_t)T * He * sizeof(float), hipMemcpyDeviceToDevice, st);
         if (er != hipSuccess) return fail((int)er, "drnn_fwd: memcpy failed: %s", hipGetErrorString(er));
     }
     return 0;
 }
 
-extern "C" int ganffn_drnn_fwd(const ganffn_drnn_cfg* c, int ndir, const float* const* U, const int32_t* const* spk,
-                               const float* const* mval, const ganffn_drnn_params* prm, float* const* e_out,
-                               float* const* alpha, float* const* saved, float* const* workspace, const uint64_t* rng,
-                               uint64_t add, void* stream) {
-    return drnn_fwd(c, ndir, U, spk, mval, prm, nullptr, e_out, alpha, saved, workspace, rng, add, stream);
-}
-extern "C" int ganffn_drnn_listener_fwd(const ganffn_drnn_cfg* c, int ndir, const float* const* U, const int32_t* const* spk,
-                                        const float* const* mval, const ganffn_drnn_params* prm,
-                                        const ganffn_drnn_listener_params* lprm, float* const* e_out, float* const* alpha,
-                                        float* const* saved, float* const* workspace, const uint64_t* rng, uint64_t add,
-                                        void* stream) {
-    GF_CHECK_ARG(lprm, "drnn_listener_fwd: null listener parameters");
-    return drnn_fwd(c, ndir, U, spk, mval, prm, lprm, e_out, alpha, saved, workspace, rng, add, stream);
-}
-
 // ------------------------------------------------------------------------------------------
 // backward
 // ------------------------------------------------------------------------------------------
-// lp == NULL: listener_state False (ganffn_drnn_bwd); otherwise the listener path (ganffn_drnn_listener_bwd, lg may be NULL)
-static int drnn_bwd(const ganffn_drnn_cfg* c, int ndir, const float* const* d_e, const float* const* U,
-                    const int32_t* const* spk, const float* const* mval, const ganffn_drnn_params* prm,
-                    const ganffn_drnn_listener_params* lp, const ganffn_drnn_grads* grd, const ganffn_drnn_listener_grads* lg,
-                    float* const* dU, const float* const* alpha, const float* const* saved, float* const* workspace,
-                    const uint64_t* rng, uint64_t add, void* stream, const ganffn_drnn_att* at = nullptr,
-                    const ganffn_drnn_att_params* ap = nullptr, const ganffn_drnn_att_grads* ag = nullptr, int P = 2, int maxB = 32) {
-    GF_TRY(check_drnn(c, ndir, maxB));
-    GF_TRY(check_parties(P));
-    const int att = at ? at->type : ATT_GENERAL;
-    if (at) {
-        GF_TRY(check_att(c, at));
-        GF_TRY(check_att_params(at, ap, ndir));
-    }
-    const ganffn_drnn_att gen{ATT_GENERAL, 0};
-    const DrnnASaved sa = drnn_asaved(c, at ? at : &gen, lp != nullptr, P);
-    const DrnnAWs wa = drnn_aws(c, at ? at : &gen, lp != nullptr, P);
-    const int Da = at ? at->Da : 0;
-    GF_CHECK_ARG(d_e && U && spk && mval && prm && grd && dU && alpha && saved && workspace, "drnn_bwd: null pointer");
-    GF_CHECK_ARG(!(c->train && c->p > 0.f) || rng, "drnn_bwd: rng required in train mode");
-    hipStream_t st = (hipStream_t)stream;
-    const int S = c->S, B = c->B, Dm = c->Dm, H = c->H, He = c->He, T = S * B;
-    const DrnnSaved so = drnn_saved(c, P);
-    const DrnnWs wo = drnn_ws(c, P);
-    const DrnnLSaved sl = drnn_lsaved(c, P);
-    const DrnnLWs wl = drnn_lws(c, P);
-    if (lp)
-        for (int z = 0; z < ndir; ++z)
-            GF_CHECK_ARG(lp[z].l_wih && lp[z].l_whh && lp[z].l_bih && lp[z].l_bhh, "drnn_listener_bwd: direction %d: null listener parameter", z);
+static int drnn_bwd(const DrnnCall& k) {
+    const ganffn_drnn_cfg* c = k.c;
+    const ganffn_drnn_params* prm = k.prm;
+    const ganffn_drnn_listener_params* lp = k.lp;
+    const float* const* d_e = k.d_e; const float* const* U = k.U; const int32_t* const* spk = k.spk; const float* const* mval = k.mval;
+    float* const* dU = k.dU; const float* const* alpha = k.alpha; const float* const* saved = k.saved; float* const* workspace = k.workspace;
+    GF_TRY(check_pass(k, "bwd", d_e && U && spk && mval && prm && k.grd && dU && alpha && saved && workspace));
+    const int ndir = k.ndir, P = k.P, att = k.att.type, Da = k.att.Da, S = c->S, B = c->B, Dm = c->Dm, H = c->H, He = c->He, T = S * B;
+    const DrnnLayout L = drnn_layout(c, k.att, lp != nullptr, P);
+    hipStream_t st = k.st;
     for (int z = 0; z < ndir; ++z) {
         GF_CHECK_ARG(d_e[z] && U[z] && dU[z] && saved[z] && workspace[z] && alpha[z], "drnn_bwd: direction %d: null buffer", z);
         float* ws = workspace[z];
-        GF_TRY(memset_f(ws + wo.dG, (int64_t)(S + 1) * B * H, st));
-        GF_TRY(memset_f(ws + wo.dQa, (int64_t)B * P * H, st));
-        GF_TRY(memset_f(ws + wo.dEa, (int64_t)B * He, st));
-        GF_TRY(memset_f(ws + wo.dXA, (int64_t)B * H, st));          // step 0 has no attention: dXA[0] = 0
+        GF_TRY(memset_f(ws + L.dG, (int64_t)(S + 1) * B * H, st));
+        GF_TRY(memset_f(ws + L.dQa, (int64_t)B * P * H, st));
+        GF_TRY(memset_f(ws + L.dEa, (int64_t)B * He, st));
+        GF_TRY(memset_f(ws + L.dXA, (int64_t)B * H, st));          // step 0 has no attention: dXA[0] = 0
         if (att == ATT_CONCAT) {            // dX (row block 0 stays zero), dP (accumulated), v partials (row block 0 stays zero)
-            GF_TRY(memset_f(ws + wa.dXC, (int64_t)T * Da, st));
-            GF_TRY(memset_f(ws + wa.dP, (int64_t)T * Da, st));
-            GF_TRY(memset_f(ws + wa.dVp, (int64_t)T * Da, st));
+            GF_TRY(memset_f(ws + L.dXC, (int64_t)T * Da, st));
+            GF_TRY(memset_f(ws + L.dP, (int64_t)T * Da, st));
+            GF_TRY(memset_f(ws + L.dVp, (int64_t)T * Da, st));
         }
     }
-    const dim3 gH((B * H + 255) / 256, 1, ndir), gHe((B * He + 255) / 256, 1, ndir);
+    const dim3 gHe((B * He + 255) / 256, 1, ndir);
     const bool echain = He <= EC_MAXHE;
-    {
-        // the step products contract over the 3H gate rows: transposed copies [H x 3H] make them row-wise reads (the NT
-        // kernel, 16.6 -> see DESIGN.md) — order per direction: p_wih[:, Dm:], p_whh, g_wih[:, Dm:], g_whh
-        TrGroup tr;
-        tr.rows = 3 * H; tr.cols = H;
+    // the step products contract over the 3H gate rows: transposed copies [H x 3H] make them row-wise reads (the NT
+    // kernel, 16.6 -> see DESIGN.md) — order per direction: p_wih[:, Dm:], p_whh, g_wih[:, Dm:], g_whh
+    const int64_t WM = (int64_t)H * 3 * H;
+    TrGroup tr;
+    tr.rows = 3 * H; tr.cols = H;
+    auto transposed = [&](int i, const float* src, int ld, float* out) { tr.in[i] = src; tr.ld_in[i] = ld; tr.out[i] = out; };
+    for (int z = 0; z < ndir; ++z) {
+        float* wt = workspace[z] + L.WT;
+        transposed(4 * z, prm[z].p_wih + Dm, Dm + H, wt); transposed(4 * z + 1, prm[z].p_whh, H, wt + WM);
+        transposed(4 * z + 2, prm[z].g_wih + Dm, Dm + H, wt + 2 * WM); transposed(4 * z + 3, prm[z].g_whh, H, wt + 3 * WM);
+    }
+    hipLaunchKernelGGL(drnn_transpose_kernel, dim3((H + 31) / 32, (3 * H + 31) / 32, 4 * ndir), dim3(256), 0, st, tr);
+    GF_LAUNCH_CHECK();
+    if (lp) {      // listener: l_wih[:, Dm:], l_whh
         for (int z = 0; z < ndir; ++z) {
-            float* wt = workspace[z] + wo.WT;
-            const float* src[4] = {prm[z].p_wih + Dm, prm[z].p_whh, prm[z].g_wih + Dm, prm[z].g_whh};
-            const int ld[4] = {Dm + H, H, Dm + H, H};
-            for (int i = 0; i < 4; ++i) { tr.in[4 * z + i] = src[i]; tr.ld_in[4 * z + i] = ld[i]; tr.out[4 * z + i] = wt + (int64_t)i * H * 3 * H; }
+            transposed(2 * z, lp[z].l_wih + Dm, Dm + H, workspace[z] + L.WTl); transposed(2 * z + 1, lp[z].l_whh, H, workspace[z] + L.WTl + WM);
         }
-        hipLaunchKernelGGL(drnn_transpose_kernel, dim3((H + 31) / 32, (3 * H + 31) / 32, 4 * ndir), dim3(256), 0, st, tr);
+        hipLaunchKernelGGL(drnn_transpose_kernel, dim3((H + 31) / 32, (3 * H + 31) / 32, 2 * ndir), dim3(256), 0, st, tr);
         GF_LAUNCH_CHECK();
-        if (lp) {      // listener: l_wih[:, Dm:], l_whh
-            for (int z = 0; z < ndir; ++z) {
-                float* wt = workspace[z] + wl.WTl;
-                tr.in[2 * z] = lp[z].l_wih + Dm; tr.ld_in[2 * z] = Dm + H; tr.out[2 * z] = wt;
-                tr.in[2 * z + 1] = lp[z].l_whh; tr.ld_in[2 * z + 1] = H; tr.out[2 * z + 1] = wt + (int64_t)H * 3 * H;
-            }
-            hipLaunchKernelGGL(drnn_transpose_kernel, dim3((H + 31) / 32, (3 * H + 31) / 32, 2 * ndir), dim3(256), 0, st, tr);
-            GF_LAUNCH_CHECK();
-        }
     }
     if (echain) {
         // emotion chain first (it depends on nothing else): gate gradients of all steps, then dQN of all steps in one GEMM
         EchainBwdArgs eb;
-        eb.S = S; eb.B = B; eb.He = He; eb.p = c->p; eb.train = c->train; eb.rng = rng; eb.add = add;
+        eb.S = S; eb.B = B; eb.He = He; eb.p = c->p; eb.train = c->train; eb.rng = k.rng; eb.add = k.add;
         for (int z = 0; z < ndir; ++z) {
             const float* sv = saved[z]; float* ws = workspace[z];
-            eb.d[z] = EchainBwdDir{d_e[z], prm[z].e_whh, sv + so.E, sv + so.Re, sv + so.Ze, sv + so.Ne, sv + so.HNe, ws + wo.dGIe,
-                                   ws + wo.dGHe, SITE_DRNN_E + 4u * z};
+            eb.d[z] = EchainBwdDir{d_e[z], prm[z].e_whh, sv + L.E, sv + L.Re, sv + L.Ze, sv + L.Ne, sv + L.HNe, ws + L.dGIe,
+                                   ws + L.dGHe, SITE_DRNN_E + 4u * z};
         }
         hipLaunchKernelGGL(drnn_echain_bwd_kernel, dim3(B, 1, ndir), dim3(EC_NT), 0, st, eb);
         GF_LAUNCH_CHECK();
-        for (int z = 0; z < ndir; ++z) {
-            float* ws = workspace[z];
-            EpiArgs e0;
-            GF_TRY(launch_gemm_nn(ws + wo.dGIe, 3 * He, prm[z].e_wih, H, ws + wo.dQNall, H, T, H, 3 * He, EPI_NONE, e0, st));
-        }
+        for (int z = 0; z < ndir; ++z)
+            GF_TRY(launch_gemm_nn(workspace[z] + L.dGIe, 3 * He, prm[z].e_wih, H, workspace[z] + L.dQNall, H, T, H, 3 * He, EPI_NONE, EpiArgs(), st));
     }
     for (int t = S - 1; t >= 0; --t) {
         const int64_t r0 = (int64_t)t * B, r1 = (int64_t)(t + 1) * B;
         const bool even = ((S - 1 - t) & 1) == 0;            // ping-pong of the recurrent gradients
-        const int64_t dQin = even ? wo.dQa : wo.dQb;      // gradient wrt Q[t+1] (assembled by the party gate kernel below)
-        const int64_t dEin = even ? wo.dEa : wo.dEb, dEout = even ? wo.dEb : wo.dEa;
+        const int64_t dQin = even ? L.dQa : L.dQb;        // gradient wrt Q[t+1] (assembled by the party gate kernel below)
+        const int64_t dEin = even ? L.dEa : L.dEb, dEout = even ? L.dEb : L.dEa;
+        const int64_t dQNt = echain ? L.dQNall + r0 * H : L.dQN;      // dQN[t]: a row block of the chain's GEMM, or this step's product
         SkinnyGroup sg;
-        GateBwdArgs gb;
-        gb.B = B; gb.row0 = (int)r0; gb.p = c->p; gb.train = c->train; gb.P = P; gb.rng = rng; gb.add = add;
         // ---- emotion cell (per step only when the chain kernels do not apply)
-        gb.H = He;
         if (!echain) {
-        for (int z = 0; z < ndir; ++z) {
-            const float* sv = saved[z]; float* ws = workspace[z];
-            gb.d[z] = GateBwdDir{ws + dEin, d_e[z] + r0 * He, sv + so.Re + r0 * He, sv + so.Ze + r0 * He, sv + so.Ne + r0 * He,
-                                 sv + so.HNe + r0 * He, sv + so.E + r0 * He, ws + wo.dGIe + r0 * 3 * He, ws + wo.dGHe + r0 * 3 * He,
-                                 ws + wo.dhdir, nullptr, nullptr, SITE_DRNN_E + 4u * z};
+            GateBwdArgs ge;
+            step_header(ge, k, He, r0);
+            for (int z = 0; z < ndir; ++z) {
+                const float* sv = saved[z]; float* ws = workspace[z];
+                ge.d[z] = GateBwdDir{ws + dEin, d_e[z] + r0 * He, sv + L.Re + r0 * He, sv + L.Ze + r0 * He, sv + L.Ne + r0 * He,
+                                     sv + L.HNe + r0 * He, sv + L.E + r0 * He, ws + L.dGIe + r0 * 3 * He, ws + L.dGHe + r0 * 3 * He,
+                                     ws + L.dhdir, nullptr, nullptr, SITE_DRNN_E + 4u * z};
+                // dQN[t] = dGI_e Wih_e ; dE_rec = dGH_e Whh_e + dhdir
+                sg.p[2 * z] = prod(B, H, 3 * He).a(ws + L.dGIe + r0 * 3 * He, 3 * He).w(prm[z].e_wih, H).out(ws + L.dQN, H);
+                sg.p[2 * z + 1] = prod(B, He, 3 * He).a(ws + L.dGHe + r0 * 3 * He, 3 * He).w(prm[z].e_whh, He).plus(ws + L.dhdir, He).out(ws + dEout, He);
+            }
+            hipLaunchKernelGGL(gru_gate_bwd_kernel<0>, gHe, dim3(256), 0, st, ge);
+            GF_LAUNCH_CHECK();
+            GF_TRY(launch_skinny(sg, 2 * ndir, true, st));
         }
-        hipLaunchKernelGGL(gru_gate_bwd_kernel<0>, gHe, dim3(256), 0, st, gb);
-        GF_LAUNCH_CHECK();
-        for (int z = 0; z < ndir; ++z) {
-            float* ws = workspace[z];
-            // dQN[t] = dGI_e Wih_e ; dE_rec = dGH_e Whh_e + dhdir
-            sg.p[2 * z] = SkinnyProb{ws + wo.dGIe + r0 * 3 * He, 3 * He, prm[z].e_wih, H, nullptr, 0, nullptr, nullptr, ws + wo.dQN, H, B, H, 3 * He};
-            sg.p[2 * z + 1] = SkinnyProb{ws + wo.dGHe + r0 * 3 * He, 3 * He, prm[z].e_whh, He, ws + wo.dhdir, He, nullptr, nullptr, ws + dEout, He, B, He, 3 * He};
-        }
-        GF_TRY(launch_skinny(sg, 2 * ndir, true, st));
+        if (lp) {
+            // ---- listener + blend backward: dGI_l (party sum), dGH_l, dh' z of both party rows, d qs through the blend
+            // ---- then d ss = dGI_l Wih_l[:, Dm:] ; dQl[p] = dGH_l[p] Whh_l + dh' z (gradient wrt Q[t] through the listener)
+            LGateBwdArgs lb;
+            step_header(lb, k, H, r0);
+            SkinnyProb lpr[2 * (1 + DR_MAXP)];
+            for (int z = 0; z < ndir; ++z) {
+                const float* sv = saved[z]; float* ws = workspace[z];
+                const bool last = t == S - 1;
+                lb.d[z] = LGateBwdDir{last ? nullptr : ws + L.dQl, ws + L.dQSp, ws + L.dQSg, last ? nullptr : spk[z] + r1,
+                                      ws + dQNt, spk[z] + r0, mval[z] + r0,
+                                      sv + L.Rl + r0 * P * H, sv + L.Zl + r0 * P * H, sv + L.Nl + r0 * P * H, sv + L.HNl + r0 * P * H,
+                                      sv + L.Q + r0 * P * H, ws + L.dGIl + r0 * 3 * H, ws + L.dGHl + r0 * P * 3 * H, ws + L.dhdirl,
+                                      ws + L.dqs, SITE_DRNN_L + 4u * z};
+                const float* wt = ws + L.WTl;
+                lpr[(1 + P) * z] = prod(B, H, 3 * H).a(ws + L.dGIl + r0 * 3 * H, 3 * H).w(wt, 3 * H).out(ws + L.dss, H);
+                for (int pa = 0; pa < P; ++pa)
+                    lpr[(1 + P) * z + 1 + pa] = prod(B, H, 3 * H).a(ws + L.dGHl + r0 * P * 3 * H + pa * 3 * H, P * 3 * H).w(wt + WM, 3 * H)
+                                                    .plus(ws + L.dhdirl + pa * H, P * H).out(ws + L.dQl + pa * H, P * H);
+            }
+            hipLaunchKernelGGL(drnn_listener_bwd_kernel, dim3((B * H + 255) / 256, 1, ndir), dim3(256), 0, st, lb);
+            GF_LAUNCH_CHECK();
+            GF_TRY(launch_skinny_nt(lpr, (1 + P) * ndir, st));
         }
         // ---- gate gradients of both cells in one launch.  Party cell: gradient wrt Q[t+1][spk] = dQ[t+1][spk] + dQN (selected
         // inside the kernel).  Global cell: dg_t = dG[t+1] — the attention uses of g_t at later steps and the recurrent path
         // were all added by the steps already done.
-        gb.H = H;
-        if (lp) {
-            // ---- listener + blend backward: dGI_l (party sum), dGH_l, dh' z of both party rows, d qs through the blend
-            LGateBwdArgs lb;
-            lb.B = B; lb.H = H; lb.row0 = (int)r0; lb.p = c->p; lb.train = c->train; lb.P = P; lb.rng = rng; lb.add = add;
-            for (int z = 0; z < ndir; ++z) {
-                const float* sv = saved[z]; float* ws = workspace[z];
-                const bool last = t == S - 1;
-                lb.d[z] = LGateBwdDir{last ? nullptr : ws + wl.dQl, ws + wo.dQSp, ws + wo.dQSg, last ? nullptr : spk[z] + r1,
-                                      echain ? ws + wo.dQNall + r0 * H : ws + wo.dQN, spk[z] + r0, mval[z] + r0,
-                                      sv + sl.Rl + r0 * P * H, sv + sl.Zl + r0 * P * H, sv + sl.Nl + r0 * P * H, sv + sl.HNl + r0 * P * H,
-                                      sv + so.Q + r0 * P * H, ws + wl.dGIl + r0 * 3 * H, ws + wl.dGHl + r0 * P * 3 * H, ws + wl.dhdirl,
-                                      ws + wl.dqs, SITE_DRNN_L + 4u * z};
-            }
-            hipLaunchKernelGGL(drnn_listener_bwd_kernel, dim3((B * H + 255) / 256, 1, ndir), dim3(256), 0, st, lb);
-            GF_LAUNCH_CHECK();
-            // ---- d ss = dGI_l Wih_l[:, Dm:] ; dQl[p] = dGH_l[p] Whh_l + dh' z (gradient wrt Q[t] through the listener)
-            SkinnyProb lpr[2 * (1 + DR_MAXP)];
-            for (int z = 0; z < ndir; ++z) {
-                float* ws = workspace[z];
-                const float* wt = ws + wl.WTl;
-                lpr[(1 + P) * z] = SkinnyProb{ws + wl.dGIl + r0 * 3 * H, 3 * H, wt, 3 * H, nullptr, 0, nullptr, nullptr, ws + wl.dss, H, B, H, 3 * H};
-                for (int pa = 0; pa < P; ++pa)
-                    lpr[(1 + P) * z + 1 + pa] = SkinnyProb{ws + wl.dGHl + r0 * P * 3 * H + pa * 3 * H, P * 3 * H, wt + (int64_t)H * 3 * H, 3 * H,
-                                                           ws + wl.dhdirl + pa * H, P * H, nullptr, nullptr, ws + wl.dQl + pa * H, P * H,
-                                                           B, H, 3 * H};
-            }
-            GF_TRY(launch_skinny_nt(lpr, (1 + P) * ndir, st));
-        }
-        GateBwdArgs gg = gb;
+        GateAttnBwdArgs gab;
+        GateBwdArgs &gg = gab.g, &gb = gab.p;
+        step_header(gg, k, H, r0);
+        step_header(gb, k, H, r0);
+        attn_header(gab, c, t);             // attention backward of step t + 1: needs its dCT (the products of step t + 1)
         for (int z = 0; z < ndir; ++z) {
             const float* sv = saved[z]; float* ws = workspace[z];
-            gb.d[z] = GateBwdDir{ws + dQin, echain ? ws + wo.dQNall + r0 * H : ws + wo.dQN, sv + so.Rp + r0 * H, sv + so.Zp + r0 * H, sv + so.Np + r0 * H, sv + so.HNp + r0 * H,
-                                 sv + so.QS + r0 * H, ws + wo.dGIp + r0 * 3 * H, ws + wo.dGHp + r0 * 3 * H, ws + wo.dhdir, mval[z] + r0,
+            gb.d[z] = GateBwdDir{ws + dQin, ws + dQNt, sv + L.Rp + r0 * H, sv + L.Zp + r0 * H, sv + L.Np + r0 * H, sv + L.HNp + r0 * H,
+                                 sv + L.QS + r0 * H, ws + L.dGIp + r0 * 3 * H, ws + L.dGHp + r0 * 3 * H, ws + L.dhdir, mval[z] + r0,
                                  spk[z] + r0, SITE_DRNN_P + 4u * z};
             if (t < S - 1) {      // assemble dQ[t+1] here (the previous iteration's party-gradient launch is gone)
                 const bool even1 = ((S - 2 - t) & 1) == 0;
-                gb.d[z].pg_dQ = ws + (even1 ? wo.dQa : wo.dQb);
+                gb.d[z].pg_dQ = ws + (even1 ? L.dQa : L.dQb);
                 gb.d[z].pg_out = ws + dQin;
-                gb.d[z].pg_dQSp = ws + wo.dQSp; gb.d[z].pg_dQSg = ws + wo.dQSg; gb.d[z].pg_spk = spk[z] + r1;
+                gb.d[z].pg_dQSp = ws + L.dQSp; gb.d[z].pg_dQSg = ws + L.dQSg; gb.d[z].pg_spk = spk[z] + r1;
             }
             if (lp) {             // listener: the party cell's output qs gets d qs (blend) + d ss (listener input); no pass-through
-                gb.d[z].dh = ws + wl.dqs; gb.d[z].dh2 = ws + wl.dss;
+                gb.d[z].dh = ws + L.dqs; gb.d[z].dh2 = ws + L.dss;
                 gb.d[z].pg_out = nullptr;
             }
-            gg.d[z] = GateBwdDir{ws + wo.dG + r1 * H, nullptr, sv + so.Rg + r0 * H, sv + so.Zg + r0 * H, sv + so.Ng + r0 * H, sv + so.HNg + r0 * H,
-                                 sv + so.G + r0 * H, ws + wo.dGIg + r0 * 3 * H, ws + wo.dGHg + r0 * 3 * H, ws + wo.dhdirG, nullptr,
+            gg.d[z] = GateBwdDir{ws + L.dG + r1 * H, nullptr, sv + L.Rg + r0 * H, sv + L.Zg + r0 * H, sv + L.Ng + r0 * H, sv + L.HNg + r0 * H,
+                                 sv + L.G + r0 * H, ws + L.dGIg + r0 * 3 * H, ws + L.dGHg + r0 * 3 * H, ws + L.dhdirG, nullptr,
                                  nullptr, SITE_DRNN_G + 4u * z};
+            gab.at.d[z] = AttnBwdDir{ws + L.dCT, sv + L.XA + r1 * H, sv + L.G, alpha[z], ws + L.dG, ws + L.dXA + r1 * H};
         }
-        GateAttnBwdArgs gab;
-        gab.g = gg; gab.p = gb;
-        gab.party_blocks = (B * H + DR_AT - 1) / DR_AT;
-        gab.has_attn = t + 1 < S;             // attention backward of step t + 1: needs its dCT (the products of step t + 1)
-        gab.at.B = B; gab.at.H = H; gab.at.S = S; gab.at.t = t + 1;
-        for (int z = 0; z < ndir; ++z)
-            gab.at.d[z] = AttnBwdDir{workspace[z] + wo.dCT, saved[z] + so.XA + r1 * H, saved[z] + so.G, alpha[z], workspace[z] + wo.dG,
-                                     workspace[z] + wo.dXA + r1 * H};
-        if (att == ATT_GENERAL2 || att == ATT_CONCAT) {
-            const dim3 gA(gab.party_blocks + B, 1, ndir);
-            GateAttnXBwdArgs gx;
-            gx.a = gab;
-            gx.x.ldw = H + Dm; gx.x.Da = Da;
-            for (int z = 0; z < ndir; ++z) {
-                float* sv = const_cast<float*>(saved[z]); float* ws = workspace[z];
-                const bool cc = att == ATT_CONCAT;
-                gx.x.d[z] = AttnXDir{cc ? nullptr : sv + sa.TS, cc ? sv + sa.P : nullptr, cc ? sv + sa.XC : nullptr, ap[z].w, ap[z].v,
-                                     cc ? ws + wa.dP : nullptr, cc ? ws + wa.dXC : nullptr, cc ? ws + wa.dVp : nullptr};
-            }
-            if (att == ATT_GENERAL2 && !lp) hipLaunchKernelGGL((drnn_gates_attnx_bwd_kernel<1, ATT_GENERAL2>), gA, dim3(DR_AT), 0, st, gx);
-            else if (att == ATT_GENERAL2) hipLaunchKernelGGL((drnn_gates_attnx_bwd_kernel<2, ATT_GENERAL2>), gA, dim3(DR_AT), 0, st, gx);
-            else if (!lp) hipLaunchKernelGGL((drnn_gates_attnx_bwd_kernel<1, ATT_CONCAT>), gA, dim3(DR_AT), 0, st, gx);
-            else hipLaunchKernelGGL((drnn_gates_attnx_bwd_kernel<2, ATT_CONCAT>), gA, dim3(DR_AT), 0, st, gx);
-        } else if (!lp) hipLaunchKernelGGL(drnn_gates_attn_bwd_kernel, dim3(gab.party_blocks + B, 1, ndir), dim3(DR_AT), 0, st, gab);
-        else hipLaunchKernelGGL(drnn_gates_attn_lbwd_kernel, dim3(gab.party_blocks + B, 1, ndir), dim3(DR_AT), 0, st, gab);
+        launch_gates_attn<StepBwd>(gab, k, L);
         GF_LAUNCH_CHECK();
         // ---- the four dgrad products of the step in one launch
         for (int z = 0; z < ndir; ++z) {
             float* ws = workspace[z];
-            const float* wt = ws + wo.WT;
-            const int64_t WM = (int64_t)H * 3 * H;
+            const float* wt = ws + L.WT;
             // dCT[t] = dGI_p Wih_p[:, Dm:] ; dQS_p = dGH_p Whh_p + dhdir
-            sg.p[4 * z] = SkinnyProb{ws + wo.dGIp + r0 * 3 * H, 3 * H, wt, 3 * H, nullptr, 0, nullptr, nullptr, ws + wo.dCT, H, B, H, 3 * H};
-            sg.p[4 * z + 1] = SkinnyProb{ws + wo.dGHp + r0 * 3 * H, 3 * H, wt + WM, 3 * H, ws + wo.dhdir, H, nullptr, nullptr, ws + wo.dQSp, H, B, H, 3 * H};
-            // dQS_g = dGI_g Wih_g[:, Dm:] ; dG[t] += dGH_g Whh_g + dhdir (in place: second addend = the output block itself)
-            sg.p[4 * z + 2] = SkinnyProb{ws + wo.dGIg + r0 * 3 * H, 3 * H, wt + 2 * WM, 3 * H, nullptr, 0, nullptr, nullptr, ws + wo.dQSg, H, B, H, 3 * H};
-            sg.p[4 * z + 3] = SkinnyProb{ws + wo.dGHg + r0 * 3 * H, 3 * H, wt + 3 * WM, 3 * H, ws + wo.dhdirG, H, ws + wo.dG + r0 * H, nullptr,
-                                         ws + wo.dG + r0 * H, H, B, H, 3 * H};
+            sg.p[4 * z] = prod(B, H, 3 * H).a(ws + L.dGIp + r0 * 3 * H, 3 * H).w(wt, 3 * H).out(ws + L.dCT, H);
+            sg.p[4 * z + 1] = prod(B, H, 3 * H).a(ws + L.dGHp + r0 * 3 * H, 3 * H).w(wt + WM, 3 * H).plus(ws + L.dhdir, H).out(ws + L.dQSp, H);
+            // dQS_g = dGI_g Wih_g[:, Dm:] ; dG[t] += dGH_g Whh_g + dhdir
+            sg.p[4 * z + 2] = prod(B, H, 3 * H).a(ws + L.dGIg + r0 * 3 * H, 3 * H).w(wt + 2 * WM, 3 * H).out(ws + L.dQSg, H);
+            sg.p[4 * z + 3] = prod(B, H, 3 * H).a(ws + L.dGHg + r0 * 3 * H, 3 * H).w(wt + 3 * WM, 3 * H).plus(ws + L.dhdirG, H).out_acc(ws + L.dG + r0 * H, H);
         }
         GF_TRY(launch_skinny(sg, 4 * ndir, false, st));
     }
     // ---- dU and the deferred weight gradients (all steps at once)
     for (int z = 0; z < ndir; ++z) {
         const float* sv = saved[z]; float* ws = workspace[z];
-        const ganffn_drnn_grads& g = grd[z];
+        const ganffn_drnn_grads& g = k.grd[z];
+        const float* aw = k.ap[z].w;
+        float* agw = k.ag[z].w;
         EpiArgs e0, e1;
-        GF_TRY(launch_gemm_nn(ws + wo.dGIg, 3 * H, prm[z].g_wih, Dm + H, dU[z], Dm, T, Dm, 3 * H, EPI_NONE, e0, st));
+        GF_TRY(launch_gemm_nn(ws + L.dGIg, 3 * H, prm[z].g_wih, Dm + H, dU[z], Dm, T, Dm, 3 * H, EPI_NONE, e0, st));
         e1.aux_in = dU[z];
-        GF_TRY(launch_gemm_nn(ws + wo.dGIp, 3 * H, prm[z].p_wih, Dm + H, dU[z], Dm, T, Dm, 3 * H, EPI_NONE, e1, st));
-        const float* aw = at ? (ap ? ap[z].w : nullptr) : prm[z].att_w;
+        GF_TRY(launch_gemm_nn(ws + L.dGIp, 3 * H, prm[z].p_wih, Dm + H, dU[z], Dm, T, Dm, 3 * H, EPI_NONE, e1, st));
         if (att == ATT_GENERAL || att == ATT_GENERAL2) {
-            GF_TRY(launch_gemm_nn(ws + wo.dXA, H, aw, Dm, dU[z], Dm, T, Dm, H, EPI_NONE, e1, st));
+            GF_TRY(launch_gemm_nn(ws + L.dXA, H, aw, Dm, dU[z], Dm, T, Dm, H, EPI_NONE, e1, st));
         } else if (att == ATT_DOT) {
-            hipLaunchKernelGGL(drnn_add_kernel, dim3((unsigned)(((int64_t)T * Dm + 255) / 256)), dim3(256), 0, st, dU[z], ws + wo.dXA, (int64_t)T * Dm);
+            hipLaunchKernelGGL(drnn_add_kernel, dim3((unsigned)(((int64_t)T * Dm + 255) / 256)), dim3(256), 0, st, dU[z], ws + L.dXA, (int64_t)T * Dm);
             GF_LAUNCH_CHECK();
         } else if (att == ATT_CONCAT) {         // dU += dX W_u
-            GF_TRY(launch_gemm_nn(ws + wa.dXC, Da, aw + H, H + Dm, dU[z], Dm, T, Dm, Da, EPI_NONE, e1, st));
+            GF_TRY(launch_gemm_nn(ws + L.dXC, Da, aw + H, H + Dm, dU[z], Dm, T, Dm, Da, EPI_NONE, e1, st));
         }
-        if (lp) GF_TRY(launch_gemm_nn(ws + wl.dGIl, 3 * H, lp[z].l_wih, Dm + H, dU[z], Dm, T, Dm, 3 * H, EPI_NONE, e1, st));
-        float* agw = at ? (ag ? ag[z].w : nullptr) : g.att_w;
-        if (at && agw && att == ATT_SIMPLE) {   // dw = column sum of dXA (the constant query)
-            hipLaunchKernelGGL(drnn_colsum_kernel, dim3((H + 63) / 64), dim3(1024), 0, st, ws + wo.dXA, T, H, agw);
+        if (lp) GF_TRY(launch_gemm_nn(ws + L.dGIl, 3 * H, lp[z].l_wih, Dm + H, dU[z], Dm, T, Dm, 3 * H, EPI_NONE, e1, st));
+        if (agw && att == ATT_SIMPLE) {         // dw = column sum of dXA (the constant query)
+            hipLaunchKernelGGL(drnn_colsum_kernel, dim3((H + 63) / 64), dim3(1024), 0, st, ws + L.dXA, T, H, agw);
             GF_LAUNCH_CHECK();
         }
-        if (at && ag && ag[z].v && att == ATT_CONCAT) {   // dv: the per-step partials in a fixed order
-            hipLaunchKernelGGL(drnn_colsum_kernel, dim3((Da + 63) / 64), dim3(1024), 0, st, ws + wa.dVp, T, Da, ag[z].v);
+        if (k.ag[z].v && att == ATT_CONCAT) {   // dv: the per-step partials in a fixed order
+            hipLaunchKernelGGL(drnn_colsum_kernel, dim3((Da + 63) / 64), dim3(1024), 0, st, ws + L.dVp, T, Da, k.ag[z].v);
             GF_LAUNCH_CHECK();
         }
-        if (g.g_wih || (at && agw)) {
+        if (g.g_wih || agw) {
             TnDesc tn[16];
             int n = 0;
             if (g.g_wih) {
-                tn[n++] = TnDesc{ws + wo.dGIg, 3 * H, U[z], Dm, g.g_wih, Dm + H, g.g_bih, 3 * H, Dm, T};
-                tn[n++] = TnDesc{ws + wo.dGIg, 3 * H, sv + so.QS, H, g.g_wih + Dm, Dm + H, nullptr, 3 * H, H, T};
-                tn[n++] = TnDesc{ws + wo.dGHg, 3 * H, sv + so.G, H, g.g_whh, H, g.g_bhh, 3 * H, H, T};
-                tn[n++] = TnDesc{ws + wo.dGIp, 3 * H, U[z], Dm, g.p_wih, Dm + H, g.p_bih, 3 * H, Dm, T};
-                tn[n++] = TnDesc{ws + wo.dGIp, 3 * H, sv + so.CT, H, g.p_wih + Dm, Dm + H, nullptr, 3 * H, H, T};
-                tn[n++] = TnDesc{ws + wo.dGHp, 3 * H, sv + so.QS, H, g.p_whh, H, g.p_bhh, 3 * H, H, T};
-                tn[n++] = TnDesc{ws + wo.dGIe, 3 * He, sv + so.QN, H, g.e_wih, H, g.e_bih, 3 * He, H, T};
-                tn[n++] = TnDesc{ws + wo.dGHe, 3 * He, sv + so.E, He, g.e_whh, He, g.e_bhh, 3 * He, He, T};
+                tn[n++] = TnDesc{ws + L.dGIg, 3 * H, U[z], Dm, g.g_wih, Dm + H, g.g_bih, 3 * H, Dm, T};
+                tn[n++] = TnDesc{ws + L.dGIg, 3 * H, sv + L.QS, H, g.g_wih + Dm, Dm + H, nullptr, 3 * H, H, T};
+                tn[n++] = TnDesc{ws + L.dGHg, 3 * H, sv + L.G, H, g.g_whh, H, g.g_bhh, 3 * H, H, T};
+                tn[n++] = TnDesc{ws + L.dGIp, 3 * H, U[z], Dm, g.p_wih, Dm + H, g.p_bih, 3 * H, Dm, T};
+                tn[n++] = TnDesc{ws + L.dGIp, 3 * H, sv + L.CT, H, g.p_wih + Dm, Dm + H, nullptr, 3 * H, H, T};
+                tn[n++] = TnDesc{ws + L.dGHp, 3 * H, sv + L.QS, H, g.p_whh, H, g.p_bhh, 3 * H, H, T};
+                tn[n++] = TnDesc{ws + L.dGIe, 3 * He, sv + L.QN, H, g.e_wih, H, g.e_bih, 3 * He, H, T};
+                tn[n++] = TnDesc{ws + L.dGHe, 3 * He, sv + L.E, He, g.e_whh, He, g.e_bhh, 3 * He, He, T};
             }
-            if (att == ATT_GENERAL && (at ? agw != nullptr : g.g_wih != nullptr))
-                tn[n++] = TnDesc{ws + wo.dXA, H, U[z], Dm, agw, Dm, nullptr, H, Dm, T};
+            if (att == ATT_GENERAL && k.general_dw[z])
+                tn[n++] = TnDesc{ws + L.dXA, H, U[z], Dm, agw, Dm, nullptr, H, Dm, T};
             if (att == ATT_GENERAL2 && agw)             // transform.bias: the column sum of dXA
-                tn[n++] = TnDesc{ws + wo.dXA, H, U[z], Dm, agw, Dm, ag[z].b, H, Dm, T};
+                tn[n++] = TnDesc{ws + L.dXA, H, U[z], Dm, agw, Dm, k.ag[z].b, H, Dm, T};
             if (att == ATT_CONCAT && agw) {            // dW_g = sum dP^T g, dW_u = sum dX^T U: the two column blocks of transform.weight
-                tn[n++] = TnDesc{ws + wa.dP, Da, saved[z] + so.G + (int64_t)B * H, H, agw, H + Dm, nullptr, Da, H, T};
-                tn[n++] = TnDesc{ws + wa.dXC, Da, U[z], Dm, agw + H, H + Dm, nullptr, Da, Dm, T};
+                tn[n++] = TnDesc{ws + L.dP, Da, sv + L.G + (int64_t)B * H, H, agw, H + Dm, nullptr, Da, H, T};
+                tn[n++] = TnDesc{ws + L.dXC, Da, U[z], Dm, agw + H, H + Dm, nullptr, Da, Dm, T};
             }
-            if (g.g_wih && lp && lg && lg[z].l_wih) {
+            if (g.g_wih && lp && k.lg && k.lg[z].l_wih) {
                 // listener: input side against [U, qs] (party-summed dGI_l), hidden side against Q[t][p] (P T rows)
-                const ganffn_drnn_listener_grads& l = lg[z];
-                tn[n++] = TnDesc{ws + wl.dGIl, 3 * H, U[z], Dm, l.l_wih, Dm + H, l.l_bih, 3 * H, Dm, T};
-                tn[n++] = TnDesc{ws + wl.dGIl, 3 * H, sv + sl.QSP, H, l.l_wih + Dm, Dm + H, nullptr, 3 * H, H, T};
-                tn[n++] = TnDesc{ws + wl.dGHl, 3 * H, sv + so.Q, H, l.l_whh, H, l.l_bhh, 3 * H, H, P * T};
+                const ganffn_drnn_listener_grads& l = k.lg[z];
+                tn[n++] = TnDesc{ws + L.dGIl, 3 * H, U[z], Dm, l.l_wih, Dm + H, l.l_bih, 3 * H, Dm, T};
+                tn[n++] = TnDesc{ws + L.dGIl, 3 * H, sv + L.QSP, H, l.l_wih + Dm, Dm + H, nullptr, 3 * H, H, T};
+                tn[n++] = TnDesc{ws + L.dGHl, 3 * H, sv + L.Q, H, l.l_whh, H, l.l_bhh, 3 * H, H, P * T};
             }
             if (n) GF_TRY(launch_gemm_tn_grouped(tn, n, st));
         }
@@ -1776,12 +1744,39 @@ static int drnn_bwd(const ganffn_drnn_cfg* c, int ndir, const float* const* d_e,
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------
+// entry points: five families, one DrnnCall each way.  ganffn_drnn_* and ganffn_drnn_listener_* (lprm given): general
+// attention on the 13th cell tensor, two parties; ganffn_drnn_att_*: an attention descriptor, with (lprm != NULL) or without
+// listener state; ganffn_drnn_party_*: and any party count 1 .. GANFFN_DRNN_MAX_PARTIES (att is its parties = 2 case);
+// ganffn_drnn_batch_*: and 1 <= B <= GANFFN_MAX_DIALOGUES dialogues through the skinny products' dialogue-tile axis (B <= 32
+// is the launch sequence of ganffn_drnn_party_*, bit for bit; above it the same number of launches per step).
+// ------------------------------------------------------------------------------------------
+extern "C" int ganffn_drnn_fwd(const ganffn_drnn_cfg* c, int ndir, const float* const* U, const int32_t* const* spk,
+                               const float* const* mval, const ganffn_drnn_params* prm, float* const* e_out,
+                               float* const* alpha, float* const* saved, float* const* workspace, const uint64_t* rng,
+                               uint64_t add, void* stream) {
+    DrnnCall k = drnn_call(c, ndir, rng, add, stream).inputs(U, spk, mval).cells(prm, nullptr).forward(e_out, alpha, saved, workspace);
+    att_of_cell(k);
+    return drnn_fwd(k);
+}
+extern "C" int ganffn_drnn_listener_fwd(const ganffn_drnn_cfg* c, int ndir, const float* const* U, const int32_t* const* spk,
+                                        const float* const* mval, const ganffn_drnn_params* prm,
+                                        const ganffn_drnn_listener_params* lprm, float* const* e_out, float* const* alpha,
+                                        float* const* saved, float* const* workspace, const uint64_t* rng, uint64_t add,
+                                        void* stream) {
+    GF_CHECK_ARG(lprm, "drnn_listener_fwd: null listener parameters");
+    DrnnCall k = drnn_call(c, ndir, rng, add, stream).inputs(U, spk, mval).cells(prm, lprm).forward(e_out, alpha, saved, workspace);
+    att_of_cell(k);
+    return drnn_fwd(k);
+}
 extern "C" int ganffn_drnn_bwd(const ganffn_drnn_cfg* c, int ndir, const float* const* d_e, const float* const* U,
                                const int32_t* const* spk, const float* const* mval, const ganffn_drnn_params* prm,
                                const ganffn_drnn_grads* grd, float* const* dU, const float* const* alpha,
                                const float* const* saved, float* const* workspace, const uint64_t* rng, uint64_t add,
                                void* stream) {
-    return drnn_bwd(c, ndir, d_e, U, spk, mval, prm, nullptr, grd, nullptr, dU, alpha, saved, workspace, rng, add, stream);
+    DrnnCall k = drnn_call(c, ndir, rng, add, stream).inputs(U, spk, mval).cells(prm, nullptr).grads(grd, nullptr).backward(d_e, dU, alpha, saved, workspace);
+    att_of_cell(k);
+    return drnn_bwd(k);
 }
 extern "C" int ganffn_drnn_listener_bwd(const ganffn_drnn_cfg* c, int ndir, const float* const* d_e, const float* const* U,
                                         const int32_t* const* spk, const float* const* mval, const ganffn_drnn_params* prm,
@@ -1790,17 +1785,19 @@ extern "C" int ganffn_drnn_listener_bwd(const ganffn_drnn_cfg* c, int ndir, cons
                                         const float* const* saved, float* const* workspace, const uint64_t* rng, uint64_t add,
                                         void* stream) {
     GF_CHECK_ARG(lprm, "drnn_listener_bwd: null listener parameters");
-    return drnn_bwd(c, ndir, d_e, U, spk, mval, prm, lprm, grd, lgrd, dU, alpha, saved, workspace, rng, add, stream);
+    DrnnCall k = drnn_call(c, ndir, rng, add, stream).inputs(U, spk, mval).cells(prm, lprm).grads(grd, lgrd).backward(d_e, dU, alpha, saved, workspace);
+    att_of_cell(k);
+    return drnn_bwd(k);
 }
-
-// other context attention types (general, simple, dot, general2, concat), with (lprm != NULL) or without listener state
 extern "C" int ganffn_drnn_att_fwd(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int ndir, const float* const* U,
                                    const int32_t* const* spk, const float* const* mval, const ganffn_drnn_params* prm,
                                    const ganffn_drnn_listener_params* lprm, const ganffn_drnn_att_params* aprm,
                                    float* const* e_out, float* const* alpha, float* const* saved, float* const* workspace,
                                    const uint64_t* rng, uint64_t add, void* stream) {
     GF_CHECK_ARG(at, "drnn_att_fwd: null attention descriptor");
-    return drnn_fwd(c, ndir, U, spk, mval, prm, lprm, e_out, alpha, saved, workspace, rng, add, stream, at, aprm);
+    DrnnCall k = drnn_call(c, ndir, rng, add, stream).inputs(U, spk, mval).cells(prm, lprm).forward(e_out, alpha, saved, workspace);
+    GF_TRY(att_of_descriptor(k, at, aprm, nullptr));
+    return drnn_fwd(k);
 }
 extern "C" int ganffn_drnn_att_bwd(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int ndir, const float* const* d_e,
                                    const float* const* U, const int32_t* const* spk, const float* const* mval,
@@ -1810,11 +1807,10 @@ extern "C" int ganffn_drnn_att_bwd(const ganffn_drnn_cfg* c, const ganffn_drnn_a
                                    const float* const* alpha, const float* const* saved, float* const* workspace,
                                    const uint64_t* rng, uint64_t add, void* stream) {
     GF_CHECK_ARG(at, "drnn_att_bwd: null attention descriptor");
-    return drnn_bwd(c, ndir, d_e, U, spk, mval, prm, lprm, grd, lgrd, dU, alpha, saved, workspace, rng, add, stream, at, aprm, agrd);
+    DrnnCall k = drnn_call(c, ndir, rng, add, stream).inputs(U, spk, mval).cells(prm, lprm).grads(grd, lgrd).backward(d_e, dU, alpha, saved, workspace);
+    GF_TRY(att_of_descriptor(k, at, aprm, agrd));
+    return drnn_bwd(k);
 }
-
-// any party count 1 <= parties <= GANFFN_DRNN_MAX_PARTIES, every attention type, with or without listener state: the driver
-// above with P = parties (ganffn_drnn_att_* are its parties = 2 case)
 extern "C" int ganffn_drnn_party_fwd(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int parties, int ndir, const float* const* U,
                                      const int32_t* const* spk, const float* const* mval, const ganffn_drnn_params* prm,
                                      const ganffn_drnn_listener_params* lprm, const ganffn_drnn_att_params* aprm,
@@ -1822,7 +1818,9 @@ extern "C" int ganffn_drnn_party_fwd(const ganffn_drnn_cfg* c, const ganffn_drnn
                                      const uint64_t* rng, uint64_t add, void* stream) {
     GF_CHECK_ARG(at, "drnn_party_fwd: null attention descriptor");
     GF_TRY(check_parties(parties));
-    return drnn_fwd(c, ndir, U, spk, mval, prm, lprm, e_out, alpha, saved, workspace, rng, add, stream, at, aprm, parties);
+    DrnnCall k = drnn_call(c, ndir, rng, add, stream).inputs(U, spk, mval).cells(prm, lprm).forward(e_out, alpha, saved, workspace).limits(parties, 32);
+    GF_TRY(att_of_descriptor(k, at, aprm, nullptr));
+    return drnn_fwd(k);
 }
 extern "C" int ganffn_drnn_party_bwd(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int parties, int ndir, const float* const* d_e,
                                      const float* const* U, const int32_t* const* spk, const float* const* mval,
@@ -1833,17 +1831,10 @@ extern "C" int ganffn_drnn_party_bwd(const ganffn_drnn_cfg* c, const ganffn_drnn
                                      const uint64_t* rng, uint64_t add, void* stream) {
     GF_CHECK_ARG(at, "drnn_party_bwd: null attention descriptor");
     GF_TRY(check_parties(parties));
-    return drnn_bwd(c, ndir, d_e, U, spk, mval, prm, lprm, grd, lgrd, dU, alpha, saved, workspace, rng, add, stream, at, aprm, agrd,
-                    parties);
-}
-
-// 1 <= B <= GANFFN_MAX_DIALOGUES dialogues per call: the driver above with the skinny products' dialogue-tile axis (B <= 32 is
-// the launch sequence of ganffn_drnn_party_*, bit for bit; above it the same number of launches per step)
-extern "C" int64_t ganffn_drnn_batch_saved_floats(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int listener, int parties) {
-    return check_drnn(c, 1, GANFFN_MAX_DIALOGUES) || check_att(c, at) || check_parties(parties) ? -1 : drnn_asaved(c, at, listener != 0, parties).total;
-}
-extern "C" int64_t ganffn_drnn_batch_workspace_floats(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int listener, int parties) {
-    return check_drnn(c, 1, GANFFN_MAX_DIALOGUES) || check_att(c, at) || check_parties(parties) ? -1 : drnn_aws(c, at, listener != 0, parties).total;
+    DrnnCall k = drnn_call(c, ndir, rng, add, stream).inputs(U, spk, mval).cells(prm, lprm).grads(grd, lgrd)
+                     .backward(d_e, dU, alpha, saved, workspace).limits(parties, 32);
+    GF_TRY(att_of_descriptor(k, at, aprm, agrd));
+    return drnn_bwd(k);
 }
 extern "C" int ganffn_drnn_batch_fwd(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int parties, int ndir, const float* const* U,
                                      const int32_t* const* spk, const float* const* mval, const ganffn_drnn_params* prm,
@@ -1852,8 +1843,10 @@ extern "C" int ganffn_drnn_batch_fwd(const ganffn_drnn_cfg* c, const ganffn_drnn
                                      const uint64_t* rng, uint64_t add, void* stream) {
     GF_CHECK_ARG(at, "drnn_batch_fwd: null attention descriptor");
     GF_TRY(check_parties(parties));
-    return drnn_fwd(c, ndir, U, spk, mval, prm, lprm, e_out, alpha, saved, workspace, rng, add, stream, at, aprm, parties,
-                    GANFFN_MAX_DIALOGUES);
+    DrnnCall k = drnn_call(c, ndir, rng, add, stream).inputs(U, spk, mval).cells(prm, lprm).forward(e_out, alpha, saved, workspace)
+                     .limits(parties, GANFFN_MAX_DIALOGUES);
+    GF_TRY(att_of_descriptor(k, at, aprm, nullptr));
+    return drnn_fwd(k);
 }
 extern "C" int ganffn_drnn_batch_bwd(const ganffn_drnn_cfg* c, const ganffn_drnn_att* at, int parties, int ndir, const float* const* d_e,
                                      const float* const* U, const int32_t* const* spk, const float* const* mval,
@@ -1864,6 +1857,8 @@ extern "C" int ganffn_drnn_batch_bwd(const ganffn_drnn_cfg* c, const ganffn_drnn
                                      const uint64_t* rng, uint64_t add, void* stream) {
     GF_CHECK_ARG(at, "drnn_batch_bwd: null attention descriptor");
     GF_TRY(check_parties(parties));
-    return drnn_bwd(c, ndir, d_e, U, spk, mval, prm, lprm, grd, lgrd, dU, alpha, saved, workspace, rng, add, stream, at, aprm, agrd,
-                    parties, GANFFN_MAX_DIALOGUES);
+    DrnnCall k = drnn_call(c, ndir, rng, add, stream).inputs(U, spk, mval).cells(prm, lprm).grads(grd, lgrd)
+                     .backward(d_e, dU, alpha, saved, workspace).limits(parties, GANFFN_MAX_DIALOGUES);
+    GF_TRY(att_of_descriptor(k, at, aprm, agrd));
+    return drnn_bwd(k);
 }

@@ -1332,28 +1332,19 @@ class DrnnEngine(_NetRunner):
         self._net_fwd(self.G[k], self.pass_G[k], self._tune_x[1][k], train=False, save=True, adds=(0, 1))
 
     # ------------------------------------------------------------------------------------------
+    # pointer structs of both directions over the head slab (grad: over its gradient slab), built by the ops helpers
     def _drnn_ptrs(self, grad):
-        out = []
-        for z in range(2):
-            s = _lib.DrnnPtrs()
-            for j, name in enumerate(_lib.DRNN_PARAM_FIELDS[:self.ncell]):       # (other types: att_w stays NULL)
-                setattr(s, name, self._hp(self.ncell * z + j, grad).data_ptr())
-            out.append(s)
-        return (_lib.DrnnPtrs * 2)(*out)
+        # (the first ncell fields; other types than general: att_w stays NULL)
+        return ops._ptr_structs(_lib.DrnnPtrs, [[self._hp(self.ncell * z + j, grad) for j in range(self.ncell)] for z in range(2)])
 
     def _drnn_att_ptrs(self, grad):
         n = len(self.att_keys)
-        return (_lib.DrnnAttPtrs * 2)(*[ops._att_ptrs(self.att, [self._hp(self.ncell * z + 12 + i, grad) for i in range(n)])
-                                        for z in range(2)])
+        return ops._ptr_structs(_lib.DrnnAttPtrs, [[self._hp(self.ncell * z + 12 + i, grad) for i in range(n)] for z in range(2)],
+                                lambda a, _: ops._att_ptrs(self.att, a))
 
     def _drnn_listener_ptrs(self, grad):
-        out = []
-        for z in range(2):
-            s = _lib.DrnnListenerPtrs()
-            for j, name in enumerate(_lib.DRNN_LISTENER_FIELDS):
-                setattr(s, name, self._hp(2 * self.ncell + 6 + 4 * z + j, grad).data_ptr())
-            out.append(s)
-        return (_lib.DrnnListenerPtrs * 2)(*out)
+        return ops._ptr_structs(_lib.DrnnListenerPtrs, [[self._hp(2 * self.ncell + 6 + 4 * z + j, grad) for j in range(4)]
+                                                        for z in range(2)])
 
     def step(self, batch, train=True):
         """batch: acoustic/visual/text (S,B,.), qmask (S,B,P) one-hot (zero rows on padding; 1 <= P <= ops.DRNN_MAX_PARTIES),
