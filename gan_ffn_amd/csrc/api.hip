@@ -3,6 +3,7 @@
 #include "common.h"
 
 #include <string.h>
+#include <algorithm>
 
 namespace ganffn {
 
@@ -134,18 +135,50 @@ static int inproj_dgrad_splits(int T, int E) {
     return s < 1 ? 1 : (int)s;
 }
 
-static int64_t enc_ws_floats(const ganffn_enc_cfg* c) {
-    const int64_t T = (int64_t)c->S * c->B, TE = T * c->E, TF = T * c->F;
-    // L x (dh | dyA dyB d_qkv(3)) | dz2 dz1 d_attn | tmp slabs | L x 2 LayerNorm partial-sum blocks
-    // + the partial-slab workspace of the grouped weight-gradient launch (narrow groups split the token range)
-    // + L transposed {in-proj, out-proj} weight blocks (rowchain backward, d_model 100)
-    const int64_t rcw = rc_supported(c->E) ? (int64_t)c->L * rc_pack_floats() + 8 : 0;
-    const int64_t bwd = (int64_t)c->L * (TF + 5 * TE) + (3 + MAX_SPLITS) * TE + (int64_t)c->L * 2 * ln_part_floats(c) +
-                        gemm_tn_grouped_part_floats() + 8 + rcw;
-    const SavedOff s = saved_off(c);
-    const int64_t fwd_nosave = 2 * TE + s.per_layer + MAX_SPLITS * TE;          // X ping-pong + one layer's saved set + tmp slabs
-    return (bwd > fwd_nosave ? bwd : fwd_nosave) + 64;
+// Slack terms of the size functions, in floats.  REGION_SLACK follows the grouped-wgrad parts and the rowchain weight pack: it paid
+// for re-aligning the next region by address; every offset of BwdLayout is a multiple of 4 floats (E and F are), so it pays for
+// nothing and is kept only so that the sizes do not change.  TAIL_SLACK ends every encoder and head workspace: no region of a
+// layout reaches into it, and it too is kept only so that the sizes do not change.
+constexpr int64_t REGION_SLACK = 8, TAIL_SLACK = 64;
+
+// workspace of a forward segment that keeps nothing, over the T = S B rows of c (a streaming pass: S = 1, B = rows):
+//   X ping-pong [2][T x E] | layer: one layer's saved set (SavedOff), reused by every layer | tmp: slabs [MAX_SPLITS][T x E]
+// slabs: the float count of tmp, and of the second segment's slabs that a two-segment pass keeps behind `total`
+struct UnsavedLayout { int64_t TE, X, layer, tmp, slabs, total; };
+static UnsavedLayout unsaved_layout(const ganffn_enc_cfg* c) {
+    UnsavedLayout u;
+    u.TE = (int64_t)c->S * c->B * c->E;
+    u.X = 0; u.layer = 2 * u.TE; u.tmp = u.layer + saved_off(c).per_layer; u.slabs = MAX_SPLITS * u.TE; u.total = u.tmp + u.slabs;
+    return u;
 }
+
+// workspace of the backward over a layer range; i = l - layer_lo counts the range's layers from its bottom:
+//   L sets of dh [T x F] | dyA [T x E] | dyB [T x E] | d_qkv [T x 3E], what layer i's four weight-gradient GEMMs read |
+//   dz2 | dz1 | d_attn [T x E] each | tmp [MAX_SPLITS][T x E] | lnp: LayerNorm partial-sum blocks [L][2 (LN2, LN1)][LNP] |
+//   tnp: partial slabs of the grouped weight-gradient launch | rcw [L][RCW]: transposed {in-proj, out-proj} weights (d_model 100)
+struct BwdLayout {
+    int64_t TE, TF, SET, LNP, RCW, dz2, dz1, d_attn, tmp, lnp, tnp, rcw, total;
+    int64_t dh(int i) const { return i * SET; }
+    int64_t dyA(int i) const { return dh(i) + TF; }
+    int64_t dyB(int i) const { return dyA(i) + TE; }
+    int64_t d_qkv(int i) const { return dyB(i) + TE; }
+    int64_t d_qkv_above(int i) const { return d_qkv(i + 1); }   // the rowchain LN2 backward runs the in-proj dgrad of the layer above
+    int64_t lnp2(int i) const { return lnp + 2 * i * LNP; }
+    int64_t lnp1(int i) const { return lnp2(i) + LNP; }
+    int64_t rcw_layer(int i) const { return rcw + i * RCW; }
+};
+static BwdLayout bwd_layout(const ganffn_enc_cfg* c) {
+    BwdLayout b;
+    const int64_t T = (int64_t)c->S * c->B, L = c->L;
+    b.TE = T * c->E; b.TF = T * c->F; b.SET = b.TF + 5 * b.TE; b.LNP = ln_part_floats(c); b.RCW = rc_pack_floats();
+    b.dz2 = L * b.SET; b.dz1 = b.dz2 + b.TE; b.d_attn = b.dz1 + b.TE; b.tmp = b.d_attn + b.TE; b.lnp = b.tmp + MAX_SPLITS * b.TE;
+    b.tnp = a4(b.lnp + L * 2 * b.LNP);
+    b.rcw = a4(b.tnp + gemm_tn_grouped_part_floats());
+    b.total = b.rcw + REGION_SLACK + (rc_supported(c->E) ? L * b.RCW + REGION_SLACK : 0);
+    return b;
+}
+// one workspace serves a backward range or a forward that keeps nothing
+static int64_t enc_ws_floats(const ganffn_enc_cfg* c) { return std::max(bwd_layout(c).total, unsaved_layout(c).total) + TAIL_SLACK; }
 
 }  // namespace ganffn
 
@@ -163,19 +196,13 @@ extern "C" int ganffn_layer_param_offsets(int E, int F, int64_t* o) {
     return 0;
 }
 
-extern "C" int64_t ganffn_encoder_saved_floats(const ganffn_enc_cfg* c) {
-    if (check_cfg(c) != 0) return -1;
-    return saved_off(c).total;
-}
+extern "C" int64_t ganffn_encoder_saved_floats(const ganffn_enc_cfg* c) { return check_cfg(c) != 0 ? -1 : saved_off(c).total; }
 extern "C" int64_t ganffn_encoder_saved_hidden_offset(const ganffn_enc_cfg* c, int layer) {
     if (check_cfg(c) != 0 || layer < 0 || layer >= c->L) return -1;
     const SavedOff so = saved_off(c);
     return so.layers + (int64_t)layer * so.per_layer + so.h;
 }
-extern "C" int64_t ganffn_encoder_workspace_floats(const ganffn_enc_cfg* c) {
-    if (check_cfg(c) != 0) return -1;
-    return enc_ws_floats(c);
-}
+extern "C" int64_t ganffn_encoder_workspace_floats(const ganffn_enc_cfg* c) { return check_cfg(c) != 0 ? -1 : enc_ws_floats(c); }
 
 // ------------------------------------------------------------------------------------------
 // encoder stack forward
@@ -193,15 +220,38 @@ struct FwdSeg {
     float* x(int l) const { return l == L ? out : X + (keeps ? l : (l & 1)) * TE; }
     float* layer(int l) const { return layers + (keeps ? l : 0) * per_layer; }
 };
-// nothing kept: X ping-pongs at workspace + 0 / + TE | one layer's saved set, reused by every layer | slabs
-static FwdSeg unsaved_seg(const ganffn_enc_cfg* c, const SavedOff& so, float* workspace, float* out, int train) {
-    const int64_t TE = (int64_t)c->S * c->B * c->E;
-    return FwdSeg{workspace, workspace + 2 * TE, workspace + 2 * TE + so.per_layer, out, TE, so.per_layer, c->L, train, false};
+// nothing kept: the segment lives in the workspace (UnsavedLayout)
+static FwdSeg unsaved_seg(const ganffn_enc_cfg* c, float* workspace, float* out, int train) {
+    const UnsavedLayout u = unsaved_layout(c);
+    return FwdSeg{workspace + u.X, workspace + u.layer, workspace + u.tmp, out, u.TE, saved_off(c).per_layer, c->L, train, false};
 }
 // everything kept in `saved` (SavedOff); the slabs are the caller's
-static FwdSeg saved_seg(const ganffn_enc_cfg* c, const SavedOff& so, float* saved, float* tmp, float* out, int train) {
-    const int64_t TE = (int64_t)c->S * c->B * c->E;
-    return FwdSeg{saved + so.X, saved + so.layers, tmp, out, TE, so.per_layer, c->L, train, true};
+static FwdSeg saved_seg(const ganffn_enc_cfg* c, float* saved, float* tmp, float* out, int train) {
+    const SavedOff so = saved_off(c);
+    return FwdSeg{saved + so.X, saved + so.layers, tmp, out, (int64_t)c->S * c->B * c->E, so.per_layer, c->L, train, true};
+}
+
+// One encoder pass.  Every encoder entry point fills one and runs encoder_fwd, encoder_fwd_pair or encoder_bwd on it (the
+// streaming ones: encoder_fwd_walk); what an entry point does not take stays null / 0.
+struct EncCall {
+    const ganffn_enc_cfg* c; const uint64_t* rng; uint64_t add; hipStream_t st;
+    const int32_t* key_len; uint32_t flags;            // the attention core's per-dialogue key lengths (or null), GANFFN_ATTN_* bits
+    const float* x_in; const float* pe; const float* params; float* workspace;
+    float* out; float* saved; float* out_train;        // forward; saved null: nothing kept.  Pair: out is the eval segment's, out_train
+                                                       // and saved are the train segment's.  (The backward only reads saved.)
+    int layer_lo, layer_hi, need_dx_in; float* dx; float* grads;       // backward over layers [layer_lo, layer_hi)
+    TnSlabs* slabs;                                    // (or null) leave the weight gradients unreduced: ganffn_encoder_bwd_parts*
+    EncCall& forward(const float* x, const float* pe_, const float* P, float* o, float* sv, float* ws) { x_in = x; pe = pe_; params = P; out = o; saved = sv; workspace = ws; return *this; }
+    EncCall& pair(float* o_train) { out_train = o_train; return *this; }
+    EncCall& backward(int lo, int hi, float* dx_, const float* P, float* G, const float* sv, float* ws, int need) {
+        layer_lo = lo; layer_hi = hi; dx = dx_; params = P; grads = G; saved = const_cast<float*>(sv); workspace = ws; need_dx_in = need;
+        return *this;
+    }
+};
+static inline EncCall enc_call(const ganffn_enc_cfg* c, const int32_t* key_len, uint32_t flags, const uint64_t* rng, uint64_t add, void* stream) {
+    EncCall k{};
+    k.c = c; k.key_len = key_len; k.flags = flags; k.rng = rng; k.add = add; k.st = (hipStream_t)stream;
+    return k;
 }
 
 // The launch sequence of the stack, once.  s1 (or null): the second segment; every launcher takes it as its optional trailing
@@ -215,9 +265,10 @@ static FwdSeg saved_seg(const ganffn_enc_cfg* c, const SavedOff& so, float* save
 // layer l's K/V cache (stream.hip).  Every other launch is the one a pass over T = n rows issues; null changes no call.
 // With sa->count (ganffn_encoder_stream_extend) the T = m * n rows are n chunks of up to m rows, time-major, and the two launches
 // are the chunk forms of the same file; without it they are the step's, as before.
-static int encoder_fwd_walk(const ganffn_enc_cfg* c, const int32_t* key_len, uint32_t flags, const Mode md, const FwdSeg& s0,
-                            const FwdSeg* s1, const float* pe, const float* x_in, const float* params, const uint64_t* rng,
-                            uint64_t add, hipStream_t st, const StreamArgs* sa = nullptr) {
+static int encoder_fwd_walk(const EncCall& k, const Mode md, const FwdSeg& s0, const FwdSeg* s1, const StreamArgs* sa) {
+    const ganffn_enc_cfg* c = k.c; const int32_t* key_len = k.key_len; const uint32_t flags = k.flags;
+    const float* pe = k.pe; const float* x_in = k.x_in; const float* params = k.params;
+    const uint64_t* rng = k.rng; const uint64_t add = k.add; hipStream_t st = k.st;
     GF_CHECK_ARG(!s1 || flags == 0, "encoder_fwd_pair: flags 0x%x have no two-segment form", flags);
     GF_CHECK_ARG(!sa || (!s1 && !key_len && flags == 0 && !s0.train), "encoder_stream_step: one eval segment, no lengths, no flags");
     const int S = c->S, B = c->B, E = c->E, H = c->H, F = c->F, L = c->L, T = S * B;
@@ -338,35 +389,38 @@ static int encoder_fwd_walk(const ganffn_enc_cfg* c, const int32_t* key_len, uin
     return 0;
 }
 
-static int encoder_fwd_impl(const ganffn_enc_cfg* c, const int32_t* key_len, uint32_t flags, const float* x_in, const float* pe,
-                            const float* params, float* out, float* saved, float* workspace, const uint64_t* rng, uint64_t add,
-                            void* stream) {
+// what every pass refuses before its first launch, in this order; pass = "fwd" | "fwd_pair" | "bwd" (the one with a dx)
+static int check_pass(const EncCall& k, const char* pass, bool pointers_given, bool all_aligned) {
+    GF_TRY(check_cfg(k.c));
+    GF_CHECK_ARG((k.flags & ~GANFFN_ATTN_CAUSAL) == 0, "encoder_%s: unknown flag bits 0x%x", pass, k.flags & ~GANFFN_ATTN_CAUSAL);
+    GF_CHECK_ARG(pointers_given, "encoder_%s: null pointer", pass);
+    GF_CHECK_ARG(!k.dx || (0 <= k.layer_lo && k.layer_lo < k.layer_hi && k.layer_hi <= k.c->L), "encoder_bwd: bad layer range [%d,%d)",
+                 k.layer_lo, k.layer_hi);
+    GF_CHECK_ARG(all_aligned, "encoder_%s: buffers must be 16-byte aligned", pass);
+    GF_CHECK_ARG(!(k.c->train && (k.c->p_pe > 0.f || k.c->p_enc > 0.f)) || k.rng, "encoder_%s: rng required in train mode", pass);
+    return 0;
+}
+static int encoder_fwd(const EncCall& k) {
     const Mode md = mode();
-    GF_TRY(check_cfg(c));
-    GF_CHECK_ARG((flags & ~GANFFN_ATTN_CAUSAL) == 0, "encoder_fwd: unknown flag bits 0x%x", flags & ~GANFFN_ATTN_CAUSAL);
-    GF_CHECK_ARG(x_in && pe && params && out && workspace, "encoder_fwd: null pointer");
-    GF_CHECK_ARG(aligned16(x_in) && aligned16(params) && aligned16(out) && aligned16(workspace) && (!saved || aligned16(saved)),
-                 "encoder_fwd: buffers must be 16-byte aligned");
-    const bool drop = c->train && (c->p_pe > 0.f || c->p_enc > 0.f);
-    GF_CHECK_ARG(!drop || rng, "encoder_fwd: rng required in train mode");
-    const SavedOff so = saved_off(c);
-    const FwdSeg s0 = saved ? saved_seg(c, so, saved, workspace, out, c->train) : unsaved_seg(c, so, workspace, out, c->train);
-    return encoder_fwd_walk(c, key_len, flags, md, s0, nullptr, pe, x_in, params, rng, add, (hipStream_t)stream);
+    GF_TRY(check_pass(k, "fwd", k.x_in && k.pe && k.params && k.out && k.workspace,
+                      aligned16(k.x_in) && aligned16(k.params) && aligned16(k.out) && aligned16(k.workspace) && aligned16(k.saved)));
+    const FwdSeg s0 = k.saved ? saved_seg(k.c, k.saved, k.workspace, k.out, k.c->train) : unsaved_seg(k.c, k.workspace, k.out, k.c->train);
+    return encoder_fwd_walk(k, md, s0, nullptr, nullptr);
 }
 extern "C" int ganffn_encoder_fwd(const ganffn_enc_cfg* c, const float* x_in, const float* pe, const float* params,
                                   float* out, float* saved, float* workspace, const uint64_t* rng, uint64_t add,
                                   void* stream) {
-    return encoder_fwd_impl(c, nullptr, 0, x_in, pe, params, out, saved, workspace, rng, add, stream);
+    return encoder_fwd(enc_call(c, nullptr, 0, rng, add, stream).forward(x_in, pe, params, out, saved, workspace));
 }
 extern "C" int ganffn_encoder_fwd_len(const ganffn_enc_cfg* c, const int32_t* key_len, const float* x_in, const float* pe,
                                       const float* params, float* out, float* saved, float* workspace, const uint64_t* rng,
                                       uint64_t add, void* stream) {
-    return encoder_fwd_impl(c, key_len, 0, x_in, pe, params, out, saved, workspace, rng, add, stream);
+    return encoder_fwd(enc_call(c, key_len, 0, rng, add, stream).forward(x_in, pe, params, out, saved, workspace));
 }
 extern "C" int ganffn_encoder_fwd_mask(const ganffn_enc_cfg* c, const int32_t* key_len, uint32_t flags, const float* x_in,
                                        const float* pe, const float* params, float* out, float* saved, float* workspace,
                                        const uint64_t* rng, uint64_t add, void* stream) {
-    return encoder_fwd_impl(c, key_len, flags, x_in, pe, params, out, saved, workspace, rng, add, stream);
+    return encoder_fwd(enc_call(c, key_len, flags, rng, add, stream).forward(x_in, pe, params, out, saved, workspace));
 }
 
 // ------------------------------------------------------------------------------------------
@@ -384,21 +438,13 @@ static int check_stream_cfg(const ganffn_enc_cfg* c) {
 static int64_t stream_layer_floats(const ganffn_enc_cfg* c) { return a4((int64_t)c->B * 2 * c->S * c->E); }
 static ganffn_enc_cfg stream_rows_cfg(const ganffn_enc_cfg* c, int n) {
     ganffn_enc_cfg r = *c;
-    r.S = 1;
-    r.B = n;
-    r.train = 0;
+    r.S = 1; r.B = n; r.train = 0;
     return r;
 }
-extern "C" int64_t ganffn_stream_cache_floats(const ganffn_enc_cfg* c) {
-    if (check_stream_cfg(c) != 0) return -1;
-    return (int64_t)c->L * stream_layer_floats(c);
-}
+extern "C" int64_t ganffn_stream_cache_floats(const ganffn_enc_cfg* c) { return check_stream_cfg(c) != 0 ? -1 : c->L * stream_layer_floats(c); }
 extern "C" int64_t ganffn_stream_workspace_floats(const ganffn_enc_cfg* c, int n_max) {
     if (check_stream_cfg(c) != 0) return -1;
-    if (n_max < 1 || n_max > c->B) {
-        fail(-1, "stream_workspace_floats: n_max=%d out of range [1,%d]", n_max, c->B);
-        return -1;
-    }
+    if (n_max < 1 || n_max > c->B) return fail(-1, "stream_workspace_floats: n_max=%d out of range [1,%d]", n_max, c->B);
     const ganffn_enc_cfg r = stream_rows_cfg(c, n_max);
     return enc_ws_floats(&r);
 }
@@ -412,10 +458,9 @@ extern "C" int ganffn_encoder_stream_step(const ganffn_enc_cfg* c, int n, const 
     GF_CHECK_ARG(aligned16(x) && aligned16(pe) && aligned16(params) && aligned16(cache) && aligned16(out) && aligned16(workspace),
                  "encoder_stream_step: buffers must be 16-byte aligned");
     const ganffn_enc_cfg r = stream_rows_cfg(c, n);
-    const SavedOff so = saved_off(&r);
-    const FwdSeg s0 = unsaved_seg(&r, so, workspace, out, 0);
+    const FwdSeg s0 = unsaved_seg(&r, workspace, out, 0);
     const StreamArgs sa{slot, pos, cache, stream_layer_floats(c), c->B, c->S};
-    return encoder_fwd_walk(&r, nullptr, 0, md, s0, nullptr, pe, x, params, nullptr, 0, (hipStream_t)stream, &sa);
+    return encoder_fwd_walk(enc_call(&r, nullptr, 0, nullptr, 0, stream).forward(x, pe, params, out, nullptr, workspace), md, s0, nullptr, &sa);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -424,14 +469,12 @@ extern "C" int ganffn_encoder_stream_step(const ganffn_enc_cfg* c, int n, const 
 // ------------------------------------------------------------------------------------------
 static int64_t stream_extend_ws(const ganffn_enc_cfg* c, int rows) {
     const ganffn_enc_cfg r = stream_rows_cfg(c, rows);
-    return 2 * (int64_t)rows * c->E + saved_off(&r).per_layer + (int64_t)MAX_SPLITS * rows * c->E + 64;
+    return unsaved_layout(&r).total + TAIL_SLACK;
 }
 extern "C" int64_t ganffn_stream_extend_workspace_floats(const ganffn_enc_cfg* c, int rows_max) {
     if (check_stream_cfg(c) != 0) return -1;
-    if (rows_max < 1 || rows_max > c->S * c->B) {
-        fail(-1, "stream_extend_workspace_floats: rows_max=%d out of range [1,%d] (max_len * capacity)", rows_max, c->S * c->B);
-        return -1;
-    }
+    if (rows_max < 1 || rows_max > c->S * c->B)
+        return fail(-1, "stream_extend_workspace_floats: rows_max=%d out of range [1,%d] (max_len * capacity)", rows_max, c->S * c->B);
     return stream_extend_ws(c, rows_max);
 }
 extern "C" int ganffn_encoder_stream_extend(const ganffn_enc_cfg* c, int n, int m, const int32_t* slot, const int32_t* count,
@@ -449,12 +492,11 @@ extern "C" int ganffn_encoder_stream_extend(const ganffn_enc_cfg* c, int n, int 
                  "encoder_stream_extend: m*n=%d rows need a workspace of %lld floats (rows_max >= %d), got %lld", rows,
                  (long long)stream_extend_ws(c, rows), rows, (long long)workspace_floats);
     const ganffn_enc_cfg r = stream_rows_cfg(c, rows);
-    const SavedOff so = saved_off(&r);
-    const FwdSeg s0 = unsaved_seg(&r, so, workspace, out, 0);
+    const FwdSeg s0 = unsaved_seg(&r, workspace, out, 0);
     StreamArgs sa{slot, pos, cache, stream_layer_floats(c), c->B, c->S};
     sa.count = count;
     sa.m = m;
-    return encoder_fwd_walk(&r, nullptr, 0, md, s0, nullptr, pe, x, params, nullptr, 0, (hipStream_t)stream, &sa);
+    return encoder_fwd_walk(enc_call(&r, nullptr, 0, nullptr, 0, stream).forward(x, pe, params, out, nullptr, workspace), md, s0, nullptr, &sa);
 }
 extern "C" int ganffn_stream_attention_chunk(const float* qkv, float* cache_layer, const int32_t* slot, const int32_t* count,
                                              const int32_t* pos, float* o, int n, int m, int capacity, int max_len, int E, int H,
@@ -477,13 +519,7 @@ extern "C" int ganffn_stream_attention(const float* qkv, float* cache_layer, con
 // ------------------------------------------------------------------------------------------
 static bool pair_supported(const ganffn_enc_cfg* c, const Mode md) {
     // every width has its segment forms; of gemm_n100's variants only the product one (eight waves, 4x4x1 tail), not the lab ones
-    if (n100_supported(c->E, c->F) && !md.n100_off() && (md.n100_pad7() || md.n100_force_kw() == 1)) return false;
-    return true;
-}
-// segment 0's part of the workspace (unsaved_seg: X ping-pong | one layer's saved set | slabs); then segment 1's slabs
-static int64_t pair_eval_ws_floats(const ganffn_enc_cfg* c) {
-    const int64_t TE = (int64_t)c->S * c->B * c->E;
-    return 2 * TE + saved_off(c).per_layer + MAX_SPLITS * TE;
+    return !(n100_supported(c->E, c->F) && !md.n100_off() && (md.n100_pad7() || md.n100_force_kw() == 1));
 }
 extern "C" int ganffn_encoder_fwd_pair_supported(const ganffn_enc_cfg* c) {
     if (check_cfg(c) != 0) return 0;
@@ -491,80 +527,66 @@ extern "C" int ganffn_encoder_fwd_pair_supported(const ganffn_enc_cfg* c) {
 }
 extern "C" int64_t ganffn_encoder_fwd_pair_workspace_floats(const ganffn_enc_cfg* c) {
     if (check_cfg(c) != 0) return -1;
-    return pair_eval_ws_floats(c) + (int64_t)MAX_SPLITS * c->S * c->B * c->E + 64;
+    const UnsavedLayout u = unsaved_layout(c);      // segment 0's part of the workspace; then segment 1's slabs
+    return u.total + u.slabs + TAIL_SLACK;
 }
-static int encoder_fwd_pair_impl(const ganffn_enc_cfg* c, const int32_t* key_len, const float* x_in, const float* pe,
-                                 const float* params, float* out_eval, float* out_train, float* saved_train, float* workspace,
-                                 const uint64_t* rng, uint64_t add_train, void* stream) {
+static int encoder_fwd_pair(const EncCall& k) {
     const Mode md = mode();
+    const ganffn_enc_cfg* c = k.c;
     GF_TRY(check_cfg(c));
     GF_CHECK_ARG(pair_supported(c, md), "encoder_fwd_pair: no two-segment form for E=%d H=%d F=%d S=%d (ganffn_encoder_fwd_pair_supported)",
                  c->E, c->H, c->F, c->S);
-    GF_CHECK_ARG(x_in && pe && params && out_eval && out_train && saved_train && workspace, "encoder_fwd_pair: null pointer");
-    GF_CHECK_ARG(aligned16(x_in) && aligned16(params) && aligned16(out_eval) && aligned16(out_train) && aligned16(saved_train) &&
-                     aligned16(workspace), "encoder_fwd_pair: buffers must be 16-byte aligned");
-    GF_CHECK_ARG(!(c->train && (c->p_pe > 0.f || c->p_enc > 0.f)) || rng, "encoder_fwd_pair: rng required in train mode");
-    const SavedOff so = saved_off(c);
-    const FwdSeg s0 = unsaved_seg(c, so, workspace, out_eval, 0);
-    const FwdSeg s1 = saved_seg(c, so, saved_train, workspace + pair_eval_ws_floats(c), out_train, c->train);
-    return encoder_fwd_walk(c, key_len, 0, md, s0, &s1, pe, x_in, params, rng, add_train, (hipStream_t)stream);
+    GF_TRY(check_pass(k, "fwd_pair", k.x_in && k.pe && k.params && k.out && k.out_train && k.saved && k.workspace,
+                      aligned16(k.x_in) && aligned16(k.params) && aligned16(k.out) && aligned16(k.out_train) && aligned16(k.saved) &&
+                          aligned16(k.workspace)));
+    const FwdSeg s0 = unsaved_seg(c, k.workspace, k.out, 0);
+    const FwdSeg s1 = saved_seg(c, k.saved, k.workspace + unsaved_layout(c).total, k.out_train, c->train);
+    return encoder_fwd_walk(k, md, s0, &s1, nullptr);
 }
-
 extern "C" int ganffn_encoder_fwd_pair(const ganffn_enc_cfg* c, const float* x_in, const float* pe, const float* params,
                                        float* out_eval, float* out_train, float* saved_train, float* workspace,
                                        const uint64_t* rng, uint64_t add_train, void* stream) {
-    return encoder_fwd_pair_impl(c, nullptr, x_in, pe, params, out_eval, out_train, saved_train, workspace, rng, add_train, stream);
+    return encoder_fwd_pair(enc_call(c, nullptr, 0, rng, add_train, stream).forward(x_in, pe, params, out_eval, saved_train, workspace).pair(out_train));
 }
 extern "C" int ganffn_encoder_fwd_pair_len(const ganffn_enc_cfg* c, const int32_t* key_len, const float* x_in, const float* pe,
                                            const float* params, float* out_eval, float* out_train, float* saved_train,
                                            float* workspace, const uint64_t* rng, uint64_t add_train, void* stream) {
-    return encoder_fwd_pair_impl(c, key_len, x_in, pe, params, out_eval, out_train, saved_train, workspace, rng, add_train, stream);
+    return encoder_fwd_pair(enc_call(c, key_len, 0, rng, add_train, stream).forward(x_in, pe, params, out_eval, saved_train, workspace).pair(out_train));
 }
 
 // ------------------------------------------------------------------------------------------
 // encoder stack backward over layers [lo_l, hi_l)
 // ------------------------------------------------------------------------------------------
-static int encoder_bwd_impl(const ganffn_enc_cfg* c, int layer_lo, int layer_hi, float* dx, const float* params,
-                            float* grads, const float* saved, float* workspace, const uint64_t* rng, uint64_t add,
-                            int need_dx_in, void* stream, TnSlabs* slabs, const int32_t* key_len = nullptr, uint32_t flags = 0) {
+static int encoder_bwd(const EncCall& k) {
     const Mode md = mode();
-    GF_TRY(check_cfg(c));
-    GF_CHECK_ARG((flags & ~GANFFN_ATTN_CAUSAL) == 0, "encoder_bwd: unknown flag bits 0x%x", flags & ~GANFFN_ATTN_CAUSAL);
-    GF_CHECK_ARG(dx && params && saved && workspace, "encoder_bwd: null pointer");
-    GF_CHECK_ARG(0 <= layer_lo && layer_lo < layer_hi && layer_hi <= c->L, "encoder_bwd: bad layer range [%d,%d)", layer_lo, layer_hi);
-    GF_CHECK_ARG(aligned16(dx) && aligned16(params) && aligned16(saved) && aligned16(workspace) && (!grads || aligned16(grads)),
-                 "encoder_bwd: buffers must be 16-byte aligned");
-    const bool drop = c->train && (c->p_pe > 0.f || c->p_enc > 0.f);
-    GF_CHECK_ARG(!drop || rng, "encoder_bwd: rng required in train mode");
-    hipStream_t st = (hipStream_t)stream;
+    const ganffn_enc_cfg* c = k.c;
+    const int layer_lo = k.layer_lo, layer_hi = k.layer_hi, need_dx_in = k.need_dx_in;
+    TnSlabs* const slabs = k.slabs;
+    float* const dx = k.dx; float* const grads = k.grads; float* const workspace = k.workspace;
+    const float* params = k.params; const float* saved = k.saved;
+    const uint64_t* rng = k.rng; const uint64_t add = k.add; hipStream_t st = k.st;
+    GF_TRY(check_pass(k, "bwd", dx && params && saved && workspace,
+                      aligned16(dx) && aligned16(params) && aligned16(saved) && aligned16(workspace) && aligned16(grads)));
     const int S = c->S, B = c->B, E = c->E, H = c->H, F = c->F, T = S * B;
-    const int64_t TE = (int64_t)T * E, TF = (int64_t)T * F;
+    const int64_t TE = (int64_t)T * E;
     const LayerOff lo = layer_off(E, F);
     const SavedOff so = saved_off(c);
+    const BwdLayout w = bwd_layout(c);
     const int train = c->train;
-    const float pdrop = (train ? c->p_enc : 0.f);
 
     // Weight gradients are DEFERRED: every layer keeps what its 4 wgrad GEMMs read (dh, dyA, dyB, d_qkv) in its own
     // buffer set, and one grouped launch at the end of the range computes all of them (4 x layers problems).  The
     // LayerNorm weight / bias gradients are reduced the same way: per-block partial sums now, one ordered reduce
     // launch for the whole range at the end.  Nothing in here uses atomics: gradients are bit-reproducible.
-    const int64_t SET = TF + 5 * TE;              // dh | dyA | dyB | d_qkv(3)
-    float* set0 = workspace;
-    float* dz2 = set0 + (int64_t)c->L * SET;      // [T x E] LN2 input gradient (residual branch into x1)
-    float* dz1 = dz2 + TE;            // [T x E] LN1 input gradient (residual branch into X[l])
-    float* d_attn = dz1 + TE;         // [T x E]
-    float* tmp = d_attn + TE;         // [MAX_SPLITS][T x E] partial slabs of dh W1
-    float* lnp0 = tmp + (int64_t)MAX_SPLITS * TE;   // [L][2] LayerNorm partial-sum blocks
-    const int64_t LNP = ln_part_floats(c);
-    float* tnp = lnp0 + (int64_t)c->L * 2 * LNP;     // grouped-wgrad partial slabs
-    tnp = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(tnp) + 15) & ~(uintptr_t)15);
+    float* dz2 = workspace + w.dz2;        // [T x E] LN2 input gradient (residual branch into x1)
+    float* dz1 = workspace + w.dz1;        // [T x E] LN1 input gradient (residual branch into X[l])
+    float* d_attn = workspace + w.d_attn;  // [T x E]
+    float* tmp = workspace + w.tmp;        // [MAX_SPLITS][T x E] partial slabs of dh W1
     const bool rc = rc_supported(E) && !md.rc_off();
-    float* rcw = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(tnp + gemm_tn_grouped_part_floats()) + 15) & ~(uintptr_t)15);
-    const int64_t RCW = rc_pack_floats();              // per layer: in_w^T [E x 3E] | out_w^T [E x E]
-    if (rc) GF_TRY(launch_rc_pack(params + (int64_t)layer_lo * lo.total, lo.total, lo.in_w, lo.out_w, rcw, layer_hi - layer_lo, st));
+    // rcw, per layer: in_w^T [E x 3E] | out_w^T [E x E]
+    if (rc) GF_TRY(launch_rc_pack(params + (int64_t)layer_lo * lo.total, lo.total, lo.in_w, lo.out_w, workspace + w.rcw, layer_hi - layer_lo, st));
     const int lnblk = rc ? rc_blocks(T) : ln_bwd_blocks(T);
-    TnDesc tn[40];
-    int ntn = 0;
+    TnDesc tn[40]; int ntn = 0;
     float* r_gw[2 * 64]; float* r_gb[2 * 64]; const float* r_part[2 * 64]; int r_nb[2 * 64];
     int nred = 0;
 
@@ -576,26 +598,23 @@ static int encoder_bwd_impl(const ganffn_enc_cfg* c, int layer_lo, int layer_hi,
         const float* sv = saved + so.layers + (int64_t)l * so.per_layer;
         const float* Xl = saved + so.X + (int64_t)l * TE;
         const uint32_t site = SITE_LAYER0 + 4 * l;
-        float* bs = set0 + (int64_t)(l - layer_lo) * SET;
-        float* dh = bs;               // [T x F]
-        float* dyA = dh + TF;         // [T x E] d(FFN output)
-        float* dyB = dyA + TE;        // [T x E] d(attention block output)
-        float* d_qkv = dyB + TE;      // [T x 3E]
-        float* lnp2 = lnp0 + (int64_t)(2 * (l - layer_lo)) * LNP;
-        float* lnp1 = lnp2 + LNP;
+        const int i = l - layer_lo;
+        float* dh = workspace + w.dh(i);         // [T x F]
+        float* dyA = workspace + w.dyA(i);       // [T x E] d(FFN output)
+        float* dyB = workspace + w.dyB(i);       // [T x E] d(attention block output)
+        float* d_qkv = workspace + w.d_qkv(i);   // [T x 3E]
+        float* lnp2 = workspace + w.lnp2(i);
+        float* lnp1 = workspace + w.lnp1(i);
         EpiArgs none;
         // LN2 backward: dL/dX[l+1] -> dz2 (to x1), dyA (to FFN output).  dL/dX[l+1] is the caller's dx for the top layer
         // of the range and otherwise the in-proj dgrad of the layer above: split-K partial slabs in `tmp`, summed here
         if (rc) {
             // top layer of the range: the caller's dx; below it: the in-proj dgrad of the layer above (its d_qkv is still in
             // that layer's buffer set, its residual-branch gradient in dz1) runs inside this kernel
-            if (l == layer_hi - 1)
-                GF_TRY(launch_rc_ln_bwd(nullptr, nullptr, dx, 1, 0, nullptr, sv + so.xhat2, sv + so.rstd2, P + lo.n2w, dz2, dyA,
-                                        G ? lnp2 : nullptr, nullptr, nullptr, T, c->p_enc, site + 3, rng, add, train, st));
-            else
-                GF_TRY(launch_rc_ln_bwd(bs + SET + TF + 2 * TE, rcw + (int64_t)(l + 1 - layer_lo) * RCW, nullptr, 0, 0, dz1,
-                                        sv + so.xhat2, sv + so.rstd2, P + lo.n2w, dz2, dyA, G ? lnp2 : nullptr, nullptr, nullptr, T,
-                                        c->p_enc, site + 3, rng, add, train, st));
+            const bool top = l == layer_hi - 1;
+            GF_TRY(launch_rc_ln_bwd(top ? nullptr : workspace + w.d_qkv_above(i), top ? nullptr : workspace + w.rcw_layer(i + 1),
+                                    top ? dx : nullptr, top ? 1 : 0, 0, top ? nullptr : dz1, sv + so.xhat2, sv + so.rstd2, P + lo.n2w, dz2,
+                                    dyA, G ? lnp2 : nullptr, nullptr, nullptr, T, c->p_enc, site + 3, rng, add, train, st));
         } else {
             GF_TRY(launch_add_drop_ln_bwd(dxin, sv + so.xhat2, sv + so.rstd2, P + lo.n2w, dz2, dyA, G ? G + lo.n2w : nullptr,
                                           G ? G + lo.n2b : nullptr, T, E, c->p_enc, site + 3, rng, add, train, st, dxin_slabs, TE,
@@ -604,7 +623,7 @@ static int encoder_bwd_impl(const ganffn_enc_cfg* c, int layer_lo, int layer_hi,
         if (G) { r_gw[nred] = G + lo.n2w; r_gb[nred] = G + lo.n2b; r_part[nred] = lnp2; r_nb[nred] = lnblk; ++nred; }
         // linear2 wgrad: gW2[E,F] += dyA^T h ; gb2 += colsum(dyA)
         if (G) tn[ntn++] = TnDesc{dyA, E, sv + so.h, F, G + lo.w2, F, G + lo.b2, E, F, T};
-        const float mscale = (pdrop > 0.f) ? 1.0f / (1.0f - pdrop) : 1.0f;
+        const float pdrop = train ? c->p_enc : 0.f, mscale = (pdrop > 0.f) ? 1.0f / (1.0f - pdrop) : 1.0f;
         int splits = 1;
         {
             EpiArgs em;
@@ -628,7 +647,7 @@ static int encoder_bwd_impl(const ganffn_enc_cfg* c, int layer_lo, int layer_hi,
         if (rc) {
             // LN1 backward + the out-proj dgrad (d_attn = dyB W_o) on the rows while they are in the workgroup
             GF_TRY(launch_rc_ln_bwd(nullptr, nullptr, tmp, splits, TE, dz2, sv + so.xhat1, sv + so.rstd1, P + lo.n1w, dz1, dyB,
-                                    G ? lnp1 : nullptr, rcw + (int64_t)(l - layer_lo) * RCW + 3 * (int64_t)E * E, d_attn, T, c->p_enc,
+                                    G ? lnp1 : nullptr, workspace + w.rcw_layer(i) + 3 * (int64_t)E * E, d_attn, T, c->p_enc,
                                     site + 1, rng, add, train, st));
         } else {
             GF_TRY(launch_add_drop_ln_bwd(tmp, sv + so.xhat1, sv + so.rstd1, P + lo.n1w, dz1, dyB, G ? G + lo.n1w : nullptr,
@@ -641,11 +660,11 @@ static int encoder_bwd_impl(const ganffn_enc_cfg* c, int layer_lo, int layer_hi,
         if (!rc) GF_TRY(launch_gemm_nn(dyB, E, P + lo.out_w, E, d_attn, E, T, E, E, EPI_NONE, none, st));
         // attention core backward
         GF_TRY(launch_attention_bwd(sv + so.qkv, sv + so.attn_o, sv + so.lse, d_attn, reinterpret_cast<const uint32_t*>(sv + so.keep), d_qkv, S, B, E,
-                                    H, c->p_enc, site + 0, rng, add, train, st, key_len, flags));
+                                    H, c->p_enc, site + 0, rng, add, train, st, k.key_len, k.flags));
         // in-proj wgrad + dgrad; dX[l] = d_qkv W_in + dz1
         if (G) tn[ntn++] = TnDesc{d_qkv, 3 * E, Xl, E, G + lo.in_w, E, G + lo.in_b, 3 * E, E, T};
         if (ntn == 40 || (l == layer_lo && ntn > 0)) {
-            GF_TRY(launch_gemm_tn_grouped(tn, ntn, st, tnp, gemm_tn_grouped_part_floats(), slabs));
+            GF_TRY(launch_gemm_tn_grouped(tn, ntn, st, workspace + w.tnp, gemm_tn_grouped_part_floats(), slabs));
             ntn = 0;
         }
         EpiArgs eadd;
@@ -671,7 +690,7 @@ static int encoder_bwd_impl(const ganffn_enc_cfg* c, int layer_lo, int layer_hi,
 extern "C" int ganffn_encoder_bwd2(const ganffn_enc_cfg* c, int layer_lo, int layer_hi, float* dx, const float* params,
                                    float* grads, const float* saved, float* workspace, const uint64_t* rng, uint64_t add,
                                    int need_dx_in, void* stream) {
-    return encoder_bwd_impl(c, layer_lo, layer_hi, dx, params, grads, saved, workspace, rng, add, need_dx_in, stream, nullptr);
+    return encoder_bwd(enc_call(c, nullptr, 0, rng, add, stream).backward(layer_lo, layer_hi, dx, params, grads, saved, workspace, need_dx_in));
 }
 extern "C" int ganffn_encoder_bwd(const ganffn_enc_cfg* c, int layer_lo, int layer_hi, float* dx, const float* params,
                                   float* grads, const float* saved, float* workspace, const uint64_t* rng, uint64_t add,
@@ -681,13 +700,12 @@ extern "C" int ganffn_encoder_bwd(const ganffn_enc_cfg* c, int layer_lo, int lay
 extern "C" int ganffn_encoder_bwd_len(const ganffn_enc_cfg* c, const int32_t* key_len, int layer_lo, int layer_hi, float* dx,
                                       const float* params, float* grads, const float* saved, float* workspace, const uint64_t* rng,
                                       uint64_t add, int need_dx_in, void* stream) {
-    return encoder_bwd_impl(c, layer_lo, layer_hi, dx, params, grads, saved, workspace, rng, add, need_dx_in, stream, nullptr, key_len);
+    return encoder_bwd(enc_call(c, key_len, 0, rng, add, stream).backward(layer_lo, layer_hi, dx, params, grads, saved, workspace, need_dx_in));
 }
 extern "C" int ganffn_encoder_bwd_mask(const ganffn_enc_cfg* c, const int32_t* key_len, uint32_t flags, int layer_lo, int layer_hi,
                                        float* dx, const float* params, float* grads, const float* saved, float* workspace,
                                        const uint64_t* rng, uint64_t add, int need_dx_in, void* stream) {
-    return encoder_bwd_impl(c, layer_lo, layer_hi, dx, params, grads, saved, workspace, rng, add, need_dx_in, stream, nullptr, key_len,
-                            flags);
+    return encoder_bwd(enc_call(c, key_len, flags, rng, add, stream).backward(layer_lo, layer_hi, dx, params, grads, saved, workspace, need_dx_in));
 }
 // does ganffn_encoder_bwd_parts leave the weight gradients of this stack unreduced?  (d_model 100 on the rowchain / tn100 kernels,
 // at most 10 layers: one grouped weight-gradient launch for the whole pass)
@@ -707,7 +725,9 @@ extern "C" int ganffn_encoder_bwd_parts_len(const ganffn_enc_cfg* c, const int32
     GF_CHECK_ARG(grads && part_offset && part_stride && n_parts, "encoder_bwd_parts: null pointer");
     GF_CHECK_ARG(bwd_parts_supported(c, mode()), "encoder_bwd_parts: this stack's weight gradients are reduced in the launch (ask ganffn_encoder_bwd_parts_supported)");
     TnSlabs sl{grads, (long)c->L * layer_off(c->E, c->F).total, 1, nullptr, 0};
-    GF_TRY(encoder_bwd_impl(c, 0, c->L, dx, params, grads, saved, workspace, rng, add, need_dx_in, stream, &sl, key_len));
+    EncCall k = enc_call(c, key_len, 0, rng, add, stream).backward(0, c->L, dx, params, grads, saved, workspace, need_dx_in);
+    k.slabs = &sl;
+    GF_TRY(encoder_bwd(k));
     *n_parts = sl.n_parts;
     *part_offset = sl.part ? sl.part - workspace : 0;
     *part_stride = sl.part_stride;
@@ -734,23 +754,26 @@ static int check_head(const ganffn_head_cfg* c) {
     GF_CHECK_ARG(c->p >= 0.f && c->p < 1.f, "head: p=%g out of [0,1)", (double)c->p);
     return 0;
 }
-extern "C" int64_t ganffn_head_saved_floats(const ganffn_head_cfg* c) {
-    if (check_head(c) != 0) return -1;
-    const int64_t T = c->T, T4 = (T + 3) & ~int64_t(3);
-    int64_t n = T * c->E + 2 * T * c->D1 + T * c->D2;
-    if (c->kind == 1) n += T * c->D2 + T4;
-    return n;
-}
-// workspace of the head backward: d_pre1 [T x D1] | d_pre2 [T x D2] | split-K partial slabs of the two weight-gradient
-// GEMMs | per-block partial sums of the discriminator tail
-static int64_t head_part2(const ganffn_head_cfg* c) { return a4(gemm_tn_part_floats(c->D2, c->D1, c->T)); }
-static int64_t head_part1(const ganffn_head_cfg* c) { return a4(gemm_tn_part_floats(c->D1, c->E, c->T)); }
-extern "C" int64_t ganffn_head_workspace_floats(const ganffn_head_cfg* c) {
-    if (check_head(c) != 0) return -1;
-    const int64_t T = c->T;
+// the saved layout above (a2 and prob: kind 1 only) and the workspace of the head backward: d_pre1 [T x D1] | d_pre2 [T x D2] |
+// part2, part1: split-K partial slabs of the gw2 / gw1 weight-gradient GEMMs (part2_floats, part1_floats) | tailp: per-block
+// partial sums of the discriminator tail (36 floats a block, of the fused kernel's blocks or the tail kernel's)
+struct HeadLayout {
+    int64_t s0, u1, a1, u2, a2, prob, saved_total;
+    int64_t d_pre1, d_pre2, part2, part1, tailp, ws_total, part2_floats, part1_floats;
+};
+static HeadLayout head_layout(const ganffn_head_cfg* c) {
+    const int64_t T = c->T, TD1 = T * c->D1, TD2 = T * c->D2;
+    HeadLayout h;
+    h.s0 = 0; h.u1 = T * c->E; h.a1 = h.u1 + TD1; h.u2 = h.a1 + TD1; h.a2 = h.u2 + TD2; h.prob = h.a2 + TD2;
+    h.saved_total = c->kind == 1 ? h.prob + a4(T) : h.a2;
+    h.part2_floats = a4(gemm_tn_part_floats(c->D2, c->D1, c->T)); h.part1_floats = a4(gemm_tn_part_floats(c->D1, c->E, c->T));
+    h.d_pre1 = 0; h.d_pre2 = a4(TD1); h.part2 = h.d_pre2 + a4(TD2); h.part1 = h.part2 + h.part2_floats; h.tailp = h.part1 + h.part1_floats;
     const int64_t tail_blocks = disc_head_blocks((int)T) > (T + 255) / 256 ? disc_head_blocks((int)T) : (T + 255) / 256;
-    return a4(T * c->D1) + a4(T * c->D2) + head_part2(c) + head_part1(c) + tail_blocks * 36 + 64;
+    h.ws_total = h.tailp + tail_blocks * 36 + TAIL_SLACK;
+    return h;
 }
+extern "C" int64_t ganffn_head_saved_floats(const ganffn_head_cfg* c) { return check_head(c) != 0 ? -1 : head_layout(c).saved_total; }
+extern "C" int64_t ganffn_head_workspace_floats(const ganffn_head_cfg* c) { return check_head(c) != 0 ? -1 : head_layout(c).ws_total; }
 
 extern "C" int ganffn_head_fwd(const ganffn_head_cfg* c, const float* x, const float* w1, const float* b1, const float* w2,
                                const float* b2, const float* w3, const float* b3, float* out, float* saved, float* workspace,
@@ -762,36 +785,24 @@ extern "C" int ganffn_head_fwd(const ganffn_head_cfg* c, const float* x, const f
     GF_CHECK_ARG(!(c->train && c->p > 0.f) || rng, "head_fwd: rng required in train mode");
     hipStream_t st = (hipStream_t)stream;
     const int T = c->T, E = c->E, D1 = c->D1, D2 = c->D2, train = c->train;
-    float* s0 = saved;                      // t0 / g0
-    float* u1 = s0 + (int64_t)T * E;
-    float* a1 = u1 + (int64_t)T * D1;
-    float* u2 = a1 + (int64_t)T * D1;
+    const HeadLayout h = head_layout(c);
+    float *s0 = saved + h.s0, *u1 = saved + h.u1, *a1 = saved + h.a1, *u2 = saved + h.u2;     // s0: t0 / g0
+    float *a2 = saved + h.a2, *prob = saved + h.prob;                                         // (kind 1)
+    if (c->kind == 1 && disc_head_fused_supported(E, D1, D2) && !md.dhead_off())
+        return launch_disc_head_fwd(x, w1, b1, w2, b2, w3, b3, s0, u1, a1, u2, a2, prob, out, T, c->p, rng, add, train, st);
+    // the generator head drops its input and ends after fc2; the discriminator's gets gelu only (model.py:1322) and fc2 goes on to the tail
+    const bool gen = c->kind == 0;
+    GF_TRY(launch_gelu_drop_fwd(x, s0, T, E, gen ? c->p : 0.f, SITE_HEAD0, rng, add, gen ? train : 0, st));
     EpiArgs e;
     e.p = c->p; e.rng = rng; e.rng_add = add; e.train = train;
-    if (c->kind == 0) {
-        GF_TRY(launch_gelu_drop_fwd(x, s0, T, E, c->p, SITE_HEAD0, rng, add, train, st));
-        e.bias = b1; e.site = SITE_HEAD1; e.aux_out = u1;
-        GF_TRY(launch_gemm_nt(s0, E, w1, E, a1, D1, T, D1, E, EPI_DROP_GELU, e, st));
-        e.bias = b2; e.site = SITE_HEAD2; e.aux_out = u2;
-        GF_TRY(launch_gemm_nt(a1, D1, w2, D1, out, D2, T, D2, D1, EPI_DROP_GELU, e, st));
-    } else if (disc_head_fused_supported(E, D1, D2) && !md.dhead_off()) {
-        float* a2 = u2 + (int64_t)T * D2;
-        float* prob = a2 + (int64_t)T * D2;
-        GF_TRY(launch_disc_head_fwd(x, w1, b1, w2, b2, w3, b3, s0, u1, a1, u2, a2, prob, out, T, c->p, rng, add, train, st));
-    } else {
-        float* a2 = u2 + (int64_t)T * D2;
-        float* prob = a2 + (int64_t)T * D2;
-        GF_TRY(launch_gelu_drop_fwd(x, s0, T, E, 0.f, SITE_HEAD0, rng, add, 0, st));  // gelu only (model.py:1322)
-        e.bias = b1; e.site = SITE_HEAD1; e.aux_out = u1;
-        GF_TRY(launch_gemm_nt(s0, E, w1, E, a1, D1, T, D1, E, EPI_DROP_GELU, e, st));
-        e.bias = b2; e.site = SITE_HEAD2; e.aux_out = u2;
-        GF_TRY(launch_gemm_nt(a1, D1, w2, D1, a2, D2, T, D2, D1, EPI_DROP_GELU, e, st));
-        GF_TRY(launch_disc_tail_fwd(a2, w3, b3, prob, T, D2, c->p, rng, add, train, st));
-        hipError_t er = hipMemcpyAsync(out, prob, (size_t)T * sizeof(float), hipMemcpyDeviceToDevice, st);
-        if (er != hipSuccess) return fail((int)er, "head_fwd: memcpy failed");
-    }
-    (void)workspace;
-    return 0;
+    e.bias = b1; e.site = SITE_HEAD1; e.aux_out = u1;
+    GF_TRY(launch_gemm_nt(s0, E, w1, E, a1, D1, T, D1, E, EPI_DROP_GELU, e, st));
+    e.bias = b2; e.site = SITE_HEAD2; e.aux_out = u2;
+    GF_TRY(launch_gemm_nt(a1, D1, w2, D1, gen ? out : a2, D2, T, D2, D1, EPI_DROP_GELU, e, st));
+    if (gen) return 0;
+    GF_TRY(launch_disc_tail_fwd(a2, w3, b3, prob, T, D2, c->p, rng, add, train, st));
+    hipError_t er = hipMemcpyAsync(out, prob, (size_t)T * sizeof(float), hipMemcpyDeviceToDevice, st);
+    return er == hipSuccess ? 0 : fail((int)er, "head_fwd: memcpy failed");
 }
 
 extern "C" int ganffn_head_bwd(const ganffn_head_cfg* c, const float* d_out, const float* x, const float* w1, const float* w2,
@@ -812,40 +823,29 @@ extern "C" int ganffn_head_bwd(const ganffn_head_cfg* c, const float* d_out, con
     GF_CHECK_ARG(!gw3 || gb3, "head_bwd: gw3 given without gb3 (the fc3 gradients are reduced together)");
     hipStream_t st = (hipStream_t)stream;
     const int T = c->T, E = c->E, D1 = c->D1, D2 = c->D2, train = c->train;
-    const float* s0 = saved;
-    const float* u1 = s0 + (int64_t)T * E;
-    const float* a1 = u1 + (int64_t)T * D1;
-    const float* u2 = a1 + (int64_t)T * D1;
-    float* d_pre1 = workspace;                       // [T x D1]
-    float* d_pre2 = d_pre1 + a4((int64_t)T * D1);    // [T x D2]
-    float* part2 = d_pre2 + a4((int64_t)T * D2);     // split-K slabs of gw2
-    float* part1 = part2 + head_part2(c);            // split-K slabs of gw1
-    float* tailp = part1 + head_part1(c);            // discriminator tail: per-block sums
-    if (c->kind == 1 && disc_head_fused_supported(E, D1, D2) && !md.dhead_off()) {
+    const HeadLayout h = head_layout(c);
+    const float *s0 = saved + h.s0, *u1 = saved + h.u1, *a1 = saved + h.a1, *u2 = saved + h.u2;
+    const float *a2 = saved + h.a2, *prob = saved + h.prob;                                    // (kind 1)
+    float *d_pre1 = workspace + h.d_pre1, *d_pre2 = workspace + h.d_pre2;                      // [T x D1], [T x D2]
+    float *part2 = workspace + h.part2, *part1 = workspace + h.part1, *tailp = workspace + h.tailp;
+    const bool fused = c->kind == 1 && disc_head_fused_supported(E, D1, D2) && !md.dhead_off();
+    if (fused) {
         // one kernel: dprob -> d_pre3 -> d_pre2 -> d_pre1 -> dx; the fc1 / fc2 weight gradients (token reductions) stay GEMMs
-        const float* a2 = u2 + (int64_t)T * D2;
-        const float* prob = a2 + (int64_t)T * D2;
         GF_TRY(launch_disc_head_bwd(d_out, x, w1, w2, w3, u1, u2, a2, prob, dx, gw1 ? d_pre1 : nullptr, gw2 ? d_pre2 : nullptr,
                                     gw3 ? tailp : nullptr, T, c->p, rng, add, train, st));
         if (gw3) GF_TRY(launch_disc_tail_reduce(tailp, disc_head_blocks(T), D2, gw3, gb3, st));
-        if (gw2) GF_TRY(launch_gemm_tn_acc(d_pre2, D2, a1, D1, gw2, D1, gb2, D2, D1, T, st, part2, head_part2(c)));
-        if (gw1) GF_TRY(launch_gemm_tn_acc(d_pre1, D1, s0, E, gw1, E, gb1, D1, E, T, st, part1, head_part1(c)));
-        return 0;
-    }
-    if (c->kind == 0) {
-        // d_pre2 = d_out * gelu'(u2) * m2
-        GF_TRY(launch_gelu_bwd_drop(d_out, u2, d_pre2, T, D2, c->p, SITE_HEAD2, rng, add, train, st));
+    } else if (c->kind == 0) {
+        GF_TRY(launch_gelu_bwd_drop(d_out, u2, d_pre2, T, D2, c->p, SITE_HEAD2, rng, add, train, st));   // d_pre2 = d_out * gelu'(u2) * m2
     } else {
-        const float* a2 = u2 + (int64_t)T * D2;
-        const float* prob = a2 + (int64_t)T * D2;
         GF_TRY(launch_disc_tail_bwd(d_out, prob, a2, u2, w3, d_pre2, gw3, gb3, T, D2, c->p, rng, add, train, st, tailp));
     }
-    if (gw2) GF_TRY(launch_gemm_tn_acc(d_pre2, D2, a1, D1, gw2, D1, gb2, D2, D1, T, st, part2, head_part2(c)));
+    if (gw2) GF_TRY(launch_gemm_tn_acc(d_pre2, D2, a1, D1, gw2, D1, gb2, D2, D1, T, st, part2, h.part2_floats));
     EpiArgs e;
     e.p = c->p; e.rng = rng; e.rng_add = add; e.train = train;
     e.aux_in = u1; e.site = SITE_HEAD1;
-    GF_TRY(launch_gemm_nn(d_pre2, D2, w2, D1, d_pre1, D1, T, D1, D2, EPI_GELU_BWD_DROP, e, st));
-    if (gw1) GF_TRY(launch_gemm_tn_acc(d_pre1, D1, s0, E, gw1, E, gb1, D1, E, T, st, part1, head_part1(c)));
+    if (!fused) GF_TRY(launch_gemm_nn(d_pre2, D2, w2, D1, d_pre1, D1, T, D1, D2, EPI_GELU_BWD_DROP, e, st));
+    if (gw1) GF_TRY(launch_gemm_tn_acc(d_pre1, D1, s0, E, gw1, E, gb1, D1, E, T, st, part1, h.part1_floats));
+    if (fused) return 0;
     e.aux_in = x;
     if (c->kind == 0) {
         e.site = SITE_HEAD0;

@@ -164,22 +164,13 @@ ATTN_CAUSAL = 1                    # GANFFN_ATTN_CAUSAL
 
 
 def encoder_fwd_raw(cfg, x, pe, slab, out, saved, ws, rng, add, key_len=None, causal=False):
-    """key_len (int32 device tensor [B], or None): the attention of every layer sees keys j < key_len[b] of dialogue b only
-    (ganffn_encoder_fwd_len); None is the plain call.  causal=True: query i sees keys j <= i as well, with or without lengths
-    (ganffn_encoder_fwd_mask with GANFFN_ATTN_CAUSAL) — row t of the output then depends on rows 0 .. t of x alone."""
-    if causal:
-        if key_len is not None:
-            _check_key_len(key_len, cfg)
-        _lib.call("ganffn_encoder_fwd_mask", C.byref(cfg), _ptr(key_len), C.c_uint32(ATTN_CAUSAL), _ptr(x), _ptr(pe), _ptr(slab),
-                  _ptr(out), _ptr(saved), _ptr(ws), _ptr(rng), C.c_uint64(add), _stream())
-        return
-    if key_len is None:
-        _lib.call("ganffn_encoder_fwd", C.byref(cfg), _ptr(x), _ptr(pe), _ptr(slab), _ptr(out), _ptr(saved), _ptr(ws),
-                  _ptr(rng), C.c_uint64(add), _stream())
-        return
-    _check_key_len(key_len, cfg)
-    _lib.call("ganffn_encoder_fwd_len", C.byref(cfg), _ptr(key_len), _ptr(x), _ptr(pe), _ptr(slab), _ptr(out), _ptr(saved),
-              _ptr(ws), _ptr(rng), C.c_uint64(add), _stream())
+    """ganffn_encoder_fwd_mask.  key_len (int32 device tensor [B], or None): the attention of every layer sees keys
+    j < key_len[b] of dialogue b only; None (a null pointer) is the plain call.  causal=True (the GANFFN_ATTN_CAUSAL flag): query i
+    sees keys j <= i as well, with or without lengths — row t of the output then depends on rows 0 .. t of x alone."""
+    if key_len is not None:
+        _check_key_len(key_len, cfg)
+    _lib.call("ganffn_encoder_fwd_mask", C.byref(cfg), _ptr(key_len), C.c_uint32(ATTN_CAUSAL if causal else 0), _ptr(x), _ptr(pe),
+              _ptr(slab), _ptr(out), _ptr(saved), _ptr(ws), _ptr(rng), C.c_uint64(add), _stream())
 
 
 def stream_sizes(cfg, n_max):
@@ -247,33 +238,22 @@ def encoder_fwd_pair_workspace_floats(cfg):
 
 def encoder_fwd_pair_raw(cfg, x, pe, slab, out_eval, out_train, saved_train, ws, rng, add_train, key_len=None):
     """cfg: the train-mode cfg.  out_eval = the eval-mode forward of x (nothing kept), out_train / saved_train = the
-    train-mode forward with its saved set — one pass, the bits of the two encoder_fwd_raw calls.  key_len (int32 device
-    tensor [B], or None): the lengths of the B dialogues, for both segments (ganffn_encoder_fwd_pair_len)."""
-    if key_len is None:
-        _lib.call("ganffn_encoder_fwd_pair", C.byref(cfg), _ptr(x), _ptr(pe), _ptr(slab), _ptr(out_eval), _ptr(out_train),
-                  _ptr(saved_train), _ptr(ws), _ptr(rng), C.c_uint64(add_train), _stream())
-        return
-    _check_key_len(key_len, cfg)
+    train-mode forward with its saved set — one pass, the bits of the two encoder_fwd_raw calls (ganffn_encoder_fwd_pair_len).
+    key_len (int32 device tensor [B], or None for a null pointer): the lengths of the B dialogues, for both segments."""
+    if key_len is not None:
+        _check_key_len(key_len, cfg)
     _lib.call("ganffn_encoder_fwd_pair_len", C.byref(cfg), _ptr(key_len), _ptr(x), _ptr(pe), _ptr(slab), _ptr(out_eval),
               _ptr(out_train), _ptr(saved_train), _ptr(ws), _ptr(rng), C.c_uint64(add_train), _stream())
 
 
 def encoder_bwd_raw(cfg, lo, hi, dx, slab, gslab, saved, ws, rng, add, need_dx_in=True, key_len=None, causal=False):
     """need_dx_in=False: the stack's input needs no gradient — with lo == 0 the bottom in-proj dgrad and the PE dropout
-    backward are skipped (as autograd skips them) and dx is undefined afterwards.  key_len, causal: what the forward was given."""
-    if causal:
-        if key_len is not None:
-            _check_key_len(key_len, cfg)
-        _lib.call("ganffn_encoder_bwd_mask", C.byref(cfg), _ptr(key_len), C.c_uint32(ATTN_CAUSAL), lo, hi, _ptr(dx), _ptr(slab),
-                  _ptr(gslab), _ptr(saved), _ptr(ws), _ptr(rng), C.c_uint64(add), 1 if need_dx_in else 0, _stream())
-        return
+    backward are skipped (as autograd skips them) and dx is undefined afterwards.  key_len, causal: what the forward was given
+    (ganffn_encoder_bwd_mask: a null pointer for None, the GANFFN_ATTN_CAUSAL flag for causal)."""
     if key_len is not None:
         _check_key_len(key_len, cfg)
-        _lib.call("ganffn_encoder_bwd_len", C.byref(cfg), _ptr(key_len), lo, hi, _ptr(dx), _ptr(slab), _ptr(gslab), _ptr(saved),
-                  _ptr(ws), _ptr(rng), C.c_uint64(add), 1 if need_dx_in else 0, _stream())
-        return
-    _lib.call("ganffn_encoder_bwd2", C.byref(cfg), lo, hi, _ptr(dx), _ptr(slab), _ptr(gslab), _ptr(saved), _ptr(ws),
-              _ptr(rng), C.c_uint64(add), 1 if need_dx_in else 0, _stream())
+    _lib.call("ganffn_encoder_bwd_mask", C.byref(cfg), _ptr(key_len), C.c_uint32(ATTN_CAUSAL if causal else 0), lo, hi, _ptr(dx),
+              _ptr(slab), _ptr(gslab), _ptr(saved), _ptr(ws), _ptr(rng), C.c_uint64(add), 1 if need_dx_in else 0, _stream())
 
 
 def encoder_bwd_parts_supported(cfg):
@@ -284,15 +264,12 @@ def encoder_bwd_parts_supported(cfg):
 def encoder_bwd_parts_raw(cfg, dx, slab, gslab, saved, ws, rng, add, need_dx_in=True, key_len=None):
     """whole-stack backward with unreduced weight gradients -> (parts tensor view into ws or None, part_stride, n_parts, offset
     of the parts in ws): hand them to adam_step_parts_raw before anything else touches ws[offset:].  key_len: the lengths the
-    forward was given (ganffn_encoder_bwd_parts_len)."""
+    forward was given, None for a null pointer (ganffn_encoder_bwd_parts_len)."""
     off, stride, n = C.c_int64(0), C.c_int64(0), C.c_int(0)
     if key_len is not None:
         _check_key_len(key_len, cfg)
-        _lib.call("ganffn_encoder_bwd_parts_len", C.byref(cfg), _ptr(key_len), _ptr(dx), _ptr(slab), _ptr(gslab), _ptr(saved),
-                  _ptr(ws), _ptr(rng), C.c_uint64(add), 1 if need_dx_in else 0, C.byref(off), C.byref(stride), C.byref(n), _stream())
-    else:
-        _lib.call("ganffn_encoder_bwd_parts", C.byref(cfg), _ptr(dx), _ptr(slab), _ptr(gslab), _ptr(saved), _ptr(ws), _ptr(rng),
-                  C.c_uint64(add), 1 if need_dx_in else 0, C.byref(off), C.byref(stride), C.byref(n), _stream())
+    _lib.call("ganffn_encoder_bwd_parts_len", C.byref(cfg), _ptr(key_len), _ptr(dx), _ptr(slab), _ptr(gslab), _ptr(saved), _ptr(ws),
+              _ptr(rng), C.c_uint64(add), 1 if need_dx_in else 0, C.byref(off), C.byref(stride), C.byref(n), _stream())
     return (ws[off.value:] if n.value > 1 else None), stride.value, n.value, off.value
 
 

@@ -1,0 +1,120 @@
+"""The call lists of tests/test_hip_workspace_bounds.py: every encoder and head call on buffers of exactly the size the library
+reports, each followed by GUARD floats of a fixed bit pattern inside the same tensor.  After every call `visit(label, buffers)`
+is handed the full tensors (guards included) the call could have written: the test checks the guards, a comparison of two
+libraries hashes them."""
+import types
+
+import torch
+
+GUARD = 256
+PATTERN = 0x7FA5C3E1                     # a NaN: nothing may read a buffer before writing it either
+WIDTHS = [(100, 10, 2048), (64, 4, 128)]   # (E, H, F): rowchain + n100 + tn100 kernels | the generic path
+SHAPES = [(3, 1), (5, 3)]                  # (S, B): T = 3 takes every round-to-4 | more than one dialogue
+L = 2
+SEED, ADD = 20261018, 5
+# (kind, E, D1, D2): generator head | discriminator head, one kernel per direction | discriminator head, GEMM chain
+HEADS = {"gen": (0, 100, 512, 100), "disc-fused": (1, 100, 64, 16), "disc-unfused": (1, 100, 64, 32)}
+HEAD_T = 3
+
+
+def guarded(n, fill=None):
+    """n floats (fill, or the pattern) followed by GUARD floats of the pattern, as one tensor"""
+    t = torch.full((n + GUARD,), PATTERN, dtype=torch.int32, device="cuda").view(torch.float32)
+    if fill is not None:
+        t[:n] = fill.reshape(-1).to(t.device) if torch.is_tensor(fill) else fill
+    return t
+
+
+def guard_intact(t):
+    return bool((t[-GUARD:].view(torch.int32) == PATTERN).all())
+
+
+def encoder_case(E, H, F, S, B, train, n_layers=L, lengths=None, causal=False):
+    return types.SimpleNamespace(E=E, H=H, F=F, S=S, B=B, L=n_layers, train=train, lengths=lengths, causal=causal)
+
+
+def run_encoder_case(c, visit):
+    """forward unsaved | forward saved | backward [1,L) then [0,1) | backward [0,L) with and without grads | _bwd_parts where
+    supported | _fwd_pair | (eval, no lengths, not causal) one stream step and one stream extend with m = 2"""
+    from gan_ffn_amd import ops
+    import encoder_range_cases as RC
+    slab, x, pe, dout = RC.inputs(c)
+    cfg = ops.enc_cfg(c.S, c.B, c.E, c.H, c.L, F=c.F, train=c.train)
+    n_saved, n_ws = ops.enc_sizes(cfg)
+    n_out = c.S * c.B * c.E
+    slab_d, x_d, pe_d = slab.cuda(), x.cuda(), pe.cuda()
+    rng = torch.tensor([SEED, 0], dtype=torch.int64, device="cuda")
+    key_len = None if c.lengths is None else torch.tensor(c.lengths, dtype=torch.int32, device="cuda")
+    mask = dict(key_len=key_len, causal=c.causal)
+
+    out, ws = guarded(n_out), guarded(n_ws)
+    ops.encoder_fwd_raw(cfg, x_d, pe_d, slab_d, out[:n_out], None, ws[:n_ws], rng, ADD, **mask)
+    visit("fwd unsaved", {"out": out, "ws": ws})
+
+    out, saved, ws = guarded(n_out), guarded(n_saved), guarded(n_ws)
+    ops.encoder_fwd_raw(cfg, x_d, pe_d, slab_d, out[:n_out], saved[:n_saved], ws[:n_ws], rng, ADD, **mask)
+    visit("fwd saved", {"out": out, "saved": saved, "ws": ws})
+
+    def backward(label, ranges, grads=True):
+        dx, g, ws = guarded(n_out, dout), guarded(slab.numel(), 0.5) if grads else None, guarded(n_ws)
+        for lo, hi in ranges:
+            ops.encoder_bwd_raw(cfg, lo, hi, dx[:n_out], slab_d, None if g is None else g[:slab.numel()], saved[:n_saved], ws[:n_ws],
+                                rng, ADD, True, **mask)
+            visit("%s [%d,%d)" % (label, lo, hi), {"dx": dx, "ws": ws, "saved": saved, **({} if g is None else {"grads": g})})
+
+    backward("bwd", [(1, c.L), (0, 1)])
+    backward("bwd", [(0, c.L)])
+    backward("bwd no grads", [(0, c.L)], grads=False)
+
+    if ops.encoder_bwd_parts_supported(cfg) and not c.causal:
+        dx, g, ws = guarded(n_out, dout), guarded(slab.numel(), 0.5), guarded(n_ws)
+        _, stride, n_parts, off = ops.encoder_bwd_parts_raw(cfg, dx[:n_out], slab_d, g[:slab.numel()], saved[:n_saved], ws[:n_ws], rng, ADD,
+                                                            True, key_len=key_len)
+        assert n_parts >= 1 and off >= 0 and stride >= 0 and off + n_parts * stride <= n_ws, (off, n_parts, stride, n_ws)
+        visit("bwd_parts", {"dx": dx, "grads": g, "ws": ws, "saved": saved})
+
+    if ops.encoder_fwd_pair_supported(cfg) and not c.causal:
+        n_pair = ops.encoder_fwd_pair_workspace_floats(cfg)
+        out, out2, saved2, ws = guarded(n_out), guarded(n_out), guarded(n_saved), guarded(n_pair)
+        ops.encoder_fwd_pair_raw(cfg, x_d, pe_d, slab_d, out[:n_out], out2[:n_out], saved2[:n_saved], ws[:n_pair], rng, ADD, key_len=key_len)
+        visit("fwd_pair", {"out_eval": out, "out_train": out2, "saved": saved2, "ws": ws})
+
+    if not c.train and c.lengths is None and not c.causal and c.S >= 3:
+        # the cache is S positions for each of B slots; every slot takes one row, then two more
+        n_cache, n_step = ops.stream_sizes(cfg, c.B)
+        n_ext = ops.stream_extend_sizes(cfg, 2 * c.B)
+        cache, ws, wsx = guarded(n_cache), guarded(n_step), guarded(n_ext)
+        slot = torch.arange(c.B, dtype=torch.int32, device="cuda")
+        pos = torch.zeros(c.B, dtype=torch.int32, device="cuda")
+        out = guarded(c.B * c.E)
+        ops.encoder_stream_step_raw(cfg, c.B, slot, pos, x_d[0].contiguous(), pe_d, slab_d, cache[:n_cache], out[:c.B * c.E], ws[:n_step])
+        visit("stream step", {"out": out, "cache": cache, "ws": ws})
+        pos += 1
+        out = guarded(2 * c.B * c.E)
+        count = torch.full((c.B,), 2, dtype=torch.int32, device="cuda")
+        ops.encoder_stream_extend_raw(cfg, c.B, 2, slot, count, pos, x_d[1:3].contiguous(), pe_d, slab_d, cache[:n_cache],
+                                      out[:2 * c.B * c.E], wsx[:n_ext])
+        visit("stream extend", {"out": out, "cache": cache, "ws": wsx})
+    torch.cuda.synchronize()
+
+
+def run_head_case(name, train, visit, T=HEAD_T):
+    from gan_ffn_amd import ops
+    from head_cases import head_inputs
+    kind, E, D1, D2 = HEADS[name]
+    tensors, d_out, g0 = head_inputs(kind, T, E, D1, D2)
+    cfg = ops.head_cfg(T, E, D1, D2, kind, 0.2, train)
+    n_saved, n_ws = ops.head_sizes(cfg)
+    n_out = T * (D2 if kind == 0 else 1)
+    dt = [None if t is None else t.cuda() for t in tensors]
+    rng = torch.tensor([SEED, 0], dtype=torch.int64, device="cuda")
+    out, saved, ws = guarded(n_out), guarded(n_saved), guarded(n_ws)
+    ops.head_fwd_raw(cfg, *dt, out[:n_out], saved[:n_saved], ws[:n_ws], rng, ADD)
+    visit("head fwd", {"out": out, "saved": saved, "ws": ws})
+    G = {k: guarded(v.numel(), v) for k, v in g0.items()}
+    g = lambda k: G[k][:g0[k].numel()] if k in G else None
+    dx = guarded(T * E)
+    ops.head_bwd_raw(cfg, d_out.cuda(), dt[0], dt[1], dt[3], dt[5], g("w1"), g("b1"), g("w2"), g("b2"), g("w3"), g("b3"), dx[:T * E],
+                     saved[:n_saved], ws[:n_ws], rng, ADD)
+    visit("head bwd", {"dx": dx, "saved": saved, "ws": ws, **{"g" + k: v for k, v in G.items()}})
+    torch.cuda.synchronize()
