@@ -129,20 +129,55 @@ __global__ __launch_bounds__(256) void lstm_colsum2_kernel(const float* __restri
     if (o2) o2[n] += t;
 }
 
-struct LstmOff { int64_t gates, c, total; };             // saved: gates [2][T x 4H] | c [2][T x H]
-LstmOff lstm_saved(const ganffn_lstm_cfg* c) {
-    const int64_t T = (int64_t)c->S * c->B, H = c->H;
-    LstmOff o;
-    o.gates = 0; o.c = 2 * T * 4 * H; o.total = o.c + 2 * T * H;
-    return o;
-}
-// workspace: forward xg [2][T x 4H] | G [2][B x 4H];  backward dG [2][T x 4H] | dh [2][B x H] | dc [2][B x H] | TN partial slabs
-int64_t lstm_ws(const ganffn_lstm_cfg* c) {
-    const int64_t T = (int64_t)c->S * c->B, H = c->H, B = c->B;
-    const int64_t fwd = 2 * T * 4 * H + 2 * B * 4 * H;
-    const int64_t part = gemm_tn_part_floats(4 * c->H, c->In > c->H ? c->In : c->H, (int)T);
-    const int64_t bwd = 2 * T * 4 * H + 4 * B * H + part + 64;
-    return (fwd > bwd ? fwd : bwd) + 64;
+// ------------------------------------------------------------------------------------------
+// Host half.  THE layouts: every region of every buffer is laid out here, once, in floats from the start of its buffer; the
+// eight size functions return the totals and the four drivers take every pointer from the offsets.
+// ------------------------------------------------------------------------------------------
+// Slack terms of a layer's workspace size, in floats.  PART_SLACK follows the TN partial slabs: it paid for re-aligning their
+// start, which is a rounded offset that rounds nothing now (lstm_layout).  TAIL_SLACK ends the workspace: no region reaches into
+// it.  Both are kept only so that no reported size changes.
+constexpr int64_t PART_SLACK = 64, TAIL_SLACK = 64;
+
+// One layer.  [2]: the forward direction's block, then the reverse direction's; T = S B tokens, a time index tm owns B rows.
+struct LstmLayout {
+    int64_t T, B, H;
+    int64_t gates, c, saved_total;                   // saved: gates [2][T x 4H] (activated i | f | g | o) | c [2][T x H]
+    int64_t xg, G;                                   // workspace, forward: xg [2][T x 4H] | G [2][B x 4H] (this step's pre-activations)
+    int64_t dG, dh, dc, part, part_floats;           // workspace, backward: dG [2][T x 4H] | dh [2][B x H] | dc [2][B x H] | TN partial slabs
+    int64_t ws_total;                                // the larger pass + the slack
+    // direction d's rows of time index tm in the per-token regions, direction d's block of the per-step ones
+    int64_t gates_at(int d, int64_t tm) const { return gates + (d * T + tm * B) * 4 * H; }
+    int64_t c_at(int d, int64_t tm) const { return c + (d * T + tm * B) * H; }
+    int64_t xg_at(int d, int64_t tm) const { return xg + (d * T + tm * B) * 4 * H; }
+    int64_t dG_at(int d, int64_t tm) const { return dG + (d * T + tm * B) * 4 * H; }
+    int64_t G_of(int d) const { return G + d * B * 4 * H; }
+    int64_t dh_of(int d) const { return dh + d * B * H; }
+    int64_t dc_of(int d) const { return dc + d * B * H; }
+    // ... and in out / d_out [T x 2H]: direction d's half of time index tm's rows (leading dimension 2H)
+    int64_t h_at(int d, int64_t tm) const { return (tm * B * 2 + d) * H; }
+};
+LstmLayout lstm_layout(const ganffn_lstm_cfg* c) {
+    LstmLayout L;
+    const int64_t T = L.T = (int64_t)c->S * c->B, B = L.B = c->B, H = L.H = c->H;
+    int64_t p = 0;
+    auto take = [&](int64_t n) { int64_t r = p; p += n; return r; };
+    L.gates = take(2 * T * 4 * H); L.c = take(2 * T * H);
+    L.saved_total = p;
+    p = 0;
+    L.xg = take(2 * T * 4 * H); L.G = take(2 * B * 4 * H);
+    const int64_t fwd = p;
+    p = 0;
+    L.dG = take(2 * T * 4 * H); L.dh = take(2 * B * H); L.dc = take(2 * B * H);
+    // the slabs start 16-byte aligned (gemm.hip's launcher refuses them otherwise): H % 4 == 0 (check_lstm) makes every region
+    // above a multiple of 4 floats and the drivers refuse a workspace that is not 16-byte aligned, so this rounds nothing
+    p = (p + 3) & ~(int64_t)3;
+    // one slab region serves both deferred weight-gradient products, [4H x In] and [4H x H]: sized for the wider; the launcher
+    // splits no further than the floats it is given
+    L.part_floats = gemm_tn_part_floats(4 * c->H, c->In > c->H ? c->In : c->H, (int)T);
+    L.part = take(L.part_floats);
+    const int64_t bwd = p + PART_SLACK;
+    L.ws_total = (fwd > bwd ? fwd : bwd) + TAIL_SLACK;
+    return L;
 }
 
 // ---- the whole stack (ganffn_lstm_stack_*): L layers chained, nn.LSTM's inter-layer dropout between them
@@ -151,36 +186,45 @@ constexpr uint32_t SITE_LSTM0 = 64;                      // + layer (ops.SITE_LS
 inline ganffn_lstm_cfg stack_layer_cfg(const ganffn_lstm_stack_cfg* c, int l) {
     return ganffn_lstm_cfg{c->S, c->B, l == 0 ? c->In : 2 * c->H, c->H};
 }
-// saved: per layer the layer's own block (gates | c: 10 T H floats whatever its input width), then per layer but the last
-// its output [T x 2H] and the dropped output [T x 2H] the next layer reads (unused when no dropout is active)
-struct LstmStackOff { int64_t layer_stride, outs, total; };
-LstmStackOff lstm_stack_saved(const ganffn_lstm_stack_cfg* c) {
-    const int64_t T = (int64_t)c->S * c->B, H = c->H;
-    LstmStackOff o;
-    o.layer_stride = 10 * T * H;
-    o.outs = c->L * o.layer_stride;
-    o.total = o.outs + (int64_t)(c->L - 1) * 2 * T * 2 * H;
-    return o;
-}
-// workspace: the widest layer's own workspace (16-byte rounded) | two [T x 2H] gradient buffers the backward alternates between
-int64_t lstm_stack_layer_ws(const ganffn_lstm_stack_cfg* c) {
-    int64_t m = 0;
+struct LstmStackLayout {
+    int64_t TD;                                      // floats of one [T x 2H] block
+    // saved: per layer the layer's own saved block (10 T H floats whatever its input width), then per layer but the last its
+    // output [T x 2H] and the dropped output [T x 2H] the next layer reads (unused when no dropout is active)
+    int64_t layer_stride, between, saved_total;
+    // workspace: the widest layer's own workspace (rounded to 16 bytes) | two [T x 2H] gradient buffers: layer l's input gradient
+    // goes to buffer l & 1, where layer l - 1 reads it as its d_out
+    int64_t layer_ws, dbuf, ws_total;
+    int64_t out(int l) const { return between + l * 2 * TD; }
+    int64_t dropped(int l) const { return out(l) + TD; }
+    int64_t d_in(int l) const { return dbuf + (l & 1) * TD; }
+};
+LstmStackLayout lstm_stack_layout(const ganffn_lstm_stack_cfg* c) {
+    LstmStackLayout L;
+    L.TD = (int64_t)c->S * c->B * 2 * c->H;
+    L.layer_ws = 0;
     for (int l = 0; l < c->L; ++l) {
         const ganffn_lstm_cfg lc = stack_layer_cfg(c, l);
-        const int64_t w = lstm_ws(&lc);
-        m = w > m ? w : m;
+        const LstmLayout ll = lstm_layout(&lc);
+        L.layer_stride = ll.saved_total;                // (the same for every layer: no term of it holds In)
+        L.layer_ws = ll.ws_total > L.layer_ws ? ll.ws_total : L.layer_ws;
     }
-    return (m + 3) & ~(int64_t)3;
+    L.layer_ws = (L.layer_ws + 3) & ~(int64_t)3;
+    L.between = c->L * L.layer_stride;
+    L.saved_total = L.out(c->L - 1);                    // (the last layer has no block there: its output is the call's)
+    L.dbuf = L.layer_ws;
+    L.ws_total = L.dbuf + 2 * L.TD;
+    return L;
 }
 
-int check_lstm(const ganffn_lstm_cfg* c, int maxB = 32) {
+// maxB: 32 behind the entry points that always had that limit, GANFFN_MAX_DIALOGUES behind the _batch_ and _packed_ ones
+int check_lstm(const ganffn_lstm_cfg* c, int maxB) {
     GF_CHECK_ARG(c, "null lstm cfg");
     GF_CHECK_ARG(c->S >= 1 && c->B >= 1 && c->B <= maxB, "lstm: S=%d B=%d (B <= %d per call)", c->S, c->B, maxB);
     GF_CHECK_ARG(c->In >= 4 && (c->In & 3) == 0 && c->H >= 4 && (c->H & 3) == 0, "lstm: In=%d H=%d must be multiples of 4", c->In, c->H);
     return 0;
 }
 
-int check_lstm_stack(const ganffn_lstm_stack_cfg* c, int maxB = 32) {
+int check_lstm_stack(const ganffn_lstm_stack_cfg* c, int maxB) {
     GF_CHECK_ARG(c, "null lstm stack cfg");
     GF_CHECK_ARG(c->L >= 1 && c->L <= 16, "lstm stack: L=%d (1 .. 16 layers)", c->L);
     GF_CHECK_ARG(c->p >= 0.f && c->p < 1.f, "lstm stack: dropout p=%g must be in [0, 1)", (double)c->p);
@@ -188,285 +232,315 @@ int check_lstm_stack(const ganffn_lstm_stack_cfg* c, int maxB = 32) {
     return check_lstm(&l0, maxB);
 }
 
+// What a forward or a backward call needs; the entry-point families differ only in maxB and lengths.  The weight and gradient
+// arrays have one entry per direction ([L][2] in a stack call); a member its pass does not take stays null.
+struct LstmCall {
+    const ganffn_lstm_cfg* c;                  // (a stack call: null here, the stack's beside it in LstmStackCall)
+    int maxB; const int* lengths;              // dialogue limit; real steps per dialogue (int32 [B] on the device) or null: all S
+    hipStream_t st;
+    const float* x; float* out; float* saved; float* workspace;                  // (the backward only reads out and saved)
+    const float* const* w_ih; const float* const* w_hh; const float* const* b_ih; const float* const* b_hh;
+    const float* d_out; float* dx;                                               // backward; dx may be null
+    float* const* gw_ih; float* const* gw_hh; float* const* gb_ih; float* const* gb_hh;      // accumulated into; null arrays / entries: not wanted
+    LstmCall& forward(const float* x_, const float* const* wi, const float* const* wh, const float* const* bi, const float* const* bh,
+                      float* out_, float* saved_, float* ws) {
+        x = x_; w_ih = wi; w_hh = wh; b_ih = bi; b_hh = bh; out = out_; saved = saved_; workspace = ws;
+        return *this;
+    }
+    LstmCall& backward(const float* d_out_, const float* x_, const float* out_, const float* const* wi, const float* const* wh, float* dx_,
+                       float* const* gwi, float* const* gwh, float* const* gbi, float* const* gbh, const float* saved_, float* ws) {
+        d_out = d_out_; x = x_; out = const_cast<float*>(out_); w_ih = wi; w_hh = wh; dx = dx_;
+        gw_ih = gwi; gw_hh = gwh; gb_ih = gbi; gb_hh = gbh; saved = const_cast<float*>(saved_); workspace = ws;
+        return *this;
+    }
+};
+inline LstmCall lstm_call(const ganffn_lstm_cfg* c, int maxB, const int* lengths, void* stream) {
+    LstmCall k{};
+    k.c = c; k.maxB = maxB; k.lengths = lengths; k.st = (hipStream_t)stream;
+    return k;
+}
+struct LstmStackCall {
+    const ganffn_lstm_stack_cfg* c; const uint64_t* rng; uint64_t add;     // add = rng_offset_add: layer l's dropout draws offset add + l
+    LstmCall k;
+    bool drop() const { return c->train && c->p > 0.f && c->L > 1; }
+    // layer l's call: its cfg, its entries of the [L][2] arrays, its saved block; the driver sets x / out / d_out / dx
+    LstmCall layer(const ganffn_lstm_cfg* lc, int l, const LstmStackLayout& L) const {
+        LstmCall q = k;
+        q.c = lc; q.saved = k.saved + l * L.layer_stride;
+        q.w_ih = k.w_ih + 2 * l; q.w_hh = k.w_hh + 2 * l;
+        if (k.b_ih) { q.b_ih = k.b_ih + 2 * l; q.b_hh = k.b_hh + 2 * l; }
+        if (k.gw_ih) q.gw_ih = k.gw_ih + 2 * l;
+        if (k.gw_hh) q.gw_hh = k.gw_hh + 2 * l;
+        if (k.gb_ih) q.gb_ih = k.gb_ih + 2 * l;
+        if (k.gb_hh) q.gb_hh = k.gb_hh + 2 * l;
+        return q;
+    }
+};
+
+// What a driver refuses before its first launch.  A stack driver (s given) checks the stack's cfg, the call's pointers and the
+// rng; the layer drivers it then runs check each layer's buffers and weights themselves, as every layer call does.
+int check_pass(const LstmCall& k, bool bwd, const LstmStackCall* s) {
+    const char* of = s ? "stack" : "layer";
+    const char* pass = bwd ? "bwd" : "fwd";
+    GF_TRY(s ? check_lstm_stack(s->c, k.maxB) : check_lstm(k.c, k.maxB));
+    GF_CHECK_ARG(k.x && k.out && k.saved && k.workspace && k.w_ih && k.w_hh && (bwd ? k.d_out != nullptr : k.b_ih && k.b_hh),
+                 "lstm_%s_%s: null pointer", of, pass);
+    if (s) {
+        GF_CHECK_ARG(!s->drop() || s->rng, "lstm_stack_%s: rng required in train mode", pass);
+        return 0;
+    }
+    // (d_out and dx are null in a forward call, dx may be in a backward one: null counts as aligned)
+    GF_CHECK_ARG(aligned16(k.d_out) && aligned16(k.x) && aligned16(k.out) && aligned16(k.saved) && aligned16(k.workspace) && aligned16(k.dx),
+                 "lstm_layer_%s: buffers must be 16-byte aligned", pass);
+    for (int d = 0; d < 2; ++d)
+        GF_CHECK_ARG(k.w_ih[d] && k.w_hh[d] && (bwd || (k.b_ih[d] && k.b_hh[d])) && aligned16(k.w_ih[d]) && aligned16(k.w_hh[d]),
+                     "lstm_layer_%s: direction %d: null / unaligned weights", pass, d);
+    return 0;
+}
+
+// The gate launch of a step, both directions: THE choice of its kernel, for both passes — the length-aware instantiation
+// behind the _packed_ entry points (the call has lengths), the plain one behind all others.
+template <class Args> void launch_gates(void (*packed)(Args), void (*plain)(Args), const LstmCall& k, Args& a) {
+    a.B = k.c->B; a.H = k.c->H; a.lengths = k.lengths;
+    hipLaunchKernelGGL(k.lengths ? packed : plain, dim3((a.B * a.H + 255) / 256, 2), dim3(256), 0, k.st, a);
+}
+
 }  // namespace
 }  // namespace ganffn
 
 using namespace ganffn;
 
-extern "C" int64_t ganffn_lstm_saved_floats(const ganffn_lstm_cfg* c) { return check_lstm(c) ? -1 : lstm_saved(c).total; }
-extern "C" int64_t ganffn_lstm_workspace_floats(const ganffn_lstm_cfg* c) { return check_lstm(c) ? -1 : lstm_ws(c); }
-
-// maxB: 32 behind the entry points that always had that limit, GANFFN_MAX_DIALOGUES behind the _batch_ and _packed_ ones;
-// lengths: null behind every entry point but the _packed_ ones (which refuse a null one themselves)
-static int lstm_layer_fwd(const ganffn_lstm_cfg* c, const float* x, const float* const* w_ih, const float* const* w_hh,
-                          const float* const* b_ih, const float* const* b_hh, float* out, float* saved, float* workspace,
-                          void* stream, int maxB, const int* lengths = nullptr) {
-    GF_TRY(check_lstm(c, maxB));
-    GF_CHECK_ARG(x && w_ih && w_hh && b_ih && b_hh && out && saved && workspace, "lstm_layer_fwd: null pointer");
-    GF_CHECK_ARG(aligned16(x) && aligned16(out) && aligned16(saved) && aligned16(workspace), "lstm_layer_fwd: buffers must be 16-byte aligned");
-    for (int d = 0; d < 2; ++d)
-        GF_CHECK_ARG(w_ih[d] && w_hh[d] && b_ih[d] && b_hh[d] && aligned16(w_ih[d]) && aligned16(w_hh[d]), "lstm_layer_fwd: direction %d: null / unaligned weights", d);
-    hipStream_t st = (hipStream_t)stream;
-    const int S = c->S, B = c->B, In = c->In, H = c->H;
-    const int64_t T = (int64_t)S * B;
-    const LstmOff so = lstm_saved(c);
-    float* xg = workspace;                          // [2][T x 4H]
-    float* G = xg + 2 * T * 4 * H;                  // [2][B x 4H]
+static int lstm_layer_fwd(const LstmCall& k) {
+    GF_TRY(check_pass(k, false, nullptr));
+    const int S = k.c->S, B = k.c->B, In = k.c->In, H = k.c->H;
+    const LstmLayout L = lstm_layout(k.c);
+    const int T = (int)L.T;
+    float* out = k.out; float* saved = k.saved; float* ws = k.workspace;
     for (int d = 0; d < 2; ++d) {
         EpiArgs e;
-        e.bias = b_ih[d];
-        GF_TRY(launch_gemm_nt(x, In, w_ih[d], In, xg + d * T * 4 * H, 4 * H, (int)T, 4 * H, In, EPI_NONE, e, st));
+        e.bias = k.b_ih[d];
+        GF_TRY(launch_gemm_nt(k.x, In, k.w_ih[d], In, ws + L.xg_at(d, 0), 4 * H, T, 4 * H, In, EPI_NONE, e, k.st));
     }
-    const dim3 ggrid((B * H + 255) / 256, 2);
     for (int t = 0; t < S; ++t) {
         SkinnyGroup sg;
         LstmGateArgs ga;
-        ga.B = B; ga.H = H; ga.lengths = lengths;
         for (int d = 0; d < 2; ++d) {
             const int64_t tm = d == 0 ? t : S - 1 - t, tp = d == 0 ? tm - 1 : tm + 1;      // this step's / the previous step's time index
-            float* Gd = G + (int64_t)d * B * 4 * H;
-            float* cS = saved + so.c + d * T * H;
-            float* gS = saved + so.gates + d * T * 4 * H;
-            const float* xgt = xg + d * T * 4 * H + tm * B * 4 * H;
-            // (first step: h_{-1} = 0 — the product runs on this step's own, still unwritten, c slot, zeroed below)
-            sg.p[d] = SkinnyProb{t == 0 ? cS + tm * B * H : out + tp * B * 2 * H + d * H, t == 0 ? H : 2 * H, w_hh[d], H, xgt, 4 * H, nullptr,
-                                 b_hh[d], Gd, 4 * H, B, 4 * H, H};
-            ga.d[d] = LstmGateDir{Gd, t == 0 ? nullptr : cS + tp * B * H, cS + tm * B * H, out + tm * B * 2 * H + d * H, gS + tm * B * 4 * H, (int)tm};
+            float* c_t = saved + L.c_at(d, tm);
+            float* Gd = ws + L.G_of(d);
+            // first step: h_{-1} = 0 without a special kernel — the product runs on this step's own, not yet written, c slot, zeroed here
+            if (t == 0) GF_HIP(hipMemsetAsync(c_t, 0, (size_t)B * H * sizeof(float), k.st));
+            sg.p[d] = SkinnyProb{t == 0 ? c_t : out + L.h_at(d, tp), t == 0 ? H : 2 * H, k.w_hh[d], H, ws + L.xg_at(d, tm), 4 * H, nullptr,
+                                 k.b_hh[d], Gd, 4 * H, B, 4 * H, H};
+            ga.d[d] = LstmGateDir{Gd, t == 0 ? nullptr : saved + L.c_at(d, tp), c_t, out + L.h_at(d, tm), saved + L.gates_at(d, tm), (int)tm};
         }
-        if (t == 0) {
-            // the first step's h_prev operand: this step's own (not yet written) c slot, zeroed — h_{-1} = 0 without a special kernel
-            for (int d = 0; d < 2; ++d) {
-                const int64_t tm = d == 0 ? 0 : S - 1;
-                GF_HIP(hipMemsetAsync(saved + so.c + d * T * H + tm * B * H, 0, (size_t)B * H * sizeof(float), st));
-            }
-        }
-        GF_TRY(launch_skinny(sg, 2, false, st));
-        if (lengths) hipLaunchKernelGGL(lstm_gate_fwd_kernel<true>, ggrid, dim3(256), 0, st, ga);
-        else hipLaunchKernelGGL(lstm_gate_fwd_kernel<false>, ggrid, dim3(256), 0, st, ga);
+        GF_TRY(launch_skinny(sg, 2, false, k.st));
+        launch_gates(lstm_gate_fwd_kernel<true>, lstm_gate_fwd_kernel<false>, k, ga);
         GF_LAUNCH_CHECK();
     }
     return 0;
 }
 
-extern "C" int ganffn_lstm_layer_fwd(const ganffn_lstm_cfg* c, const float* x, const float* const* w_ih, const float* const* w_hh,
-                                     const float* const* b_ih, const float* const* b_hh, float* out, float* saved, float* workspace,
-                                     void* stream) {
-    return lstm_layer_fwd(c, x, w_ih, w_hh, b_ih, b_hh, out, saved, workspace, stream, 32);
-}
-
-static int lstm_layer_bwd(const ganffn_lstm_cfg* c, const float* d_out, const float* x, const float* out,
-                          const float* const* w_ih, const float* const* w_hh, float* dx, float* const* gw_ih,
-                          float* const* gw_hh, float* const* gb_ih, float* const* gb_hh, const float* saved,
-                          float* workspace, void* stream, int maxB, const int* lengths = nullptr) {
-    GF_TRY(check_lstm(c, maxB));
-    GF_CHECK_ARG(d_out && x && out && w_ih && w_hh && saved && workspace, "lstm_layer_bwd: null pointer");
-    GF_CHECK_ARG(aligned16(d_out) && aligned16(x) && aligned16(out) && aligned16(saved) && aligned16(workspace) && (!dx || aligned16(dx)),
-                 "lstm_layer_bwd: buffers must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const int S = c->S, B = c->B, In = c->In, H = c->H;
-    const int64_t T = (int64_t)S * B;
-    const LstmOff so = lstm_saved(c);
-    float* dG = workspace;                          // [2][T x 4H]
-    float* dh = dG + 2 * T * 4 * H;                 // [2][B x H]
-    float* dc = dh + 2 * B * H;                     // [2][B x H]
-    float* part = reinterpret_cast<float*>((reinterpret_cast<uintptr_t>(dc + 2 * B * H) + 15) & ~(uintptr_t)15);
-    const long part_floats = gemm_tn_part_floats(4 * H, In > H ? In : H, (int)T);
-    const dim3 ggrid((B * H + 255) / 256, 2);
+static int lstm_layer_bwd(const LstmCall& k) {
+    GF_TRY(check_pass(k, true, nullptr));
+    const int S = k.c->S, B = k.c->B, In = k.c->In, H = k.c->H;
+    const LstmLayout L = lstm_layout(k.c);
+    const int T = (int)L.T;
+    const float* d_out = k.d_out; const float* out = k.out; const float* saved = k.saved; float* ws = k.workspace;
     for (int t = S - 1; t >= 0; --t) {              // step index of the forward loop, walked backwards
+        const bool first = t == S - 1;              // first backward step: no later step feeds dh / dc
         LstmGateBwdArgs gb;
-        gb.B = B; gb.H = H; gb.lengths = lengths;
+        SkinnyGroup sg;
         for (int d = 0; d < 2; ++d) {
             const int64_t tm = d == 0 ? t : S - 1 - t, tp = d == 0 ? tm - 1 : tm + 1;
-            const float* cS = saved + so.c + d * T * H;
-            const float* gS = saved + so.gates + d * T * 4 * H;
-            const bool first = t == S - 1;          // first backward step: no later step feeds dh / dc
-            gb.d[d] = LstmGateBwdDir{first ? d_out + tm * B * 2 * H + d * H : dh + (int64_t)d * B * H, first ? 2 * H : H, dc + (int64_t)d * B * H,
-                                     first ? 1 : 0, gS + tm * B * 4 * H, cS + tm * B * H, t == 0 ? nullptr : cS + tp * B * H,
-                                     dG + d * T * 4 * H + tm * B * 4 * H, (int)tm};
-        }
-        if (lengths) hipLaunchKernelGGL(lstm_gate_bwd_kernel<true>, ggrid, dim3(256), 0, st, gb);
-        else hipLaunchKernelGGL(lstm_gate_bwd_kernel<false>, ggrid, dim3(256), 0, st, gb);
-        GF_LAUNCH_CHECK();
-        if (t > 0) {
+            float* dG_t = ws + L.dG_at(d, tm);
+            float* dh = ws + L.dh_of(d);
+            gb.d[d] = LstmGateBwdDir{first ? d_out + L.h_at(d, tm) : dh, first ? 2 * H : H, ws + L.dc_of(d), first ? 1 : 0,
+                                     saved + L.gates_at(d, tm), saved + L.c_at(d, tm), t == 0 ? nullptr : saved + L.c_at(d, tp), dG_t, (int)tm};
             // dh_{t-1} = d_out[t-1]'s half + dG_t W_hh   ([B x 4H] x [4H x H], the weight row-wise as stored)
-            SkinnyGroup sg;
-            for (int d = 0; d < 2; ++d) {
-                const int64_t tm = d == 0 ? t : S - 1 - t, tp = d == 0 ? tm - 1 : tm + 1;
-                sg.p[d] = SkinnyProb{dG + d * T * 4 * H + tm * B * 4 * H, 4 * H, w_hh[d], H, d_out + tp * B * 2 * H + d * H, 2 * H, nullptr, nullptr,
-                                     dh + (int64_t)d * B * H, H, B, H, 4 * H};
-            }
-            GF_TRY(launch_skinny(sg, 2, true, st));
+            if (t > 0) sg.p[d] = SkinnyProb{dG_t, 4 * H, k.w_hh[d], H, d_out + L.h_at(d, tp), 2 * H, nullptr, nullptr, dh, H, B, H, 4 * H};
         }
+        launch_gates(lstm_gate_bwd_kernel<true>, lstm_gate_bwd_kernel<false>, k, gb);
+        GF_LAUNCH_CHECK();
+        if (t > 0) GF_TRY(launch_skinny(sg, 2, true, k.st));
     }
     // deferred weight gradients over all tokens (accumulated: the caller zeroes), bias gradients, input gradient
+    float* part = ws + L.part;
     for (int d = 0; d < 2; ++d) {
-        const float* dGd = dG + d * T * 4 * H;
-        if (gw_ih && gw_ih[d]) GF_TRY(launch_gemm_tn_acc(dGd, 4 * H, x, In, gw_ih[d], In, nullptr, 4 * H, In, (int)T, st, part, part_floats));
-        if (gw_hh && gw_hh[d] && S > 1) {
-            // h_prev of time tm: forward direction out[tm - 1], reverse direction out[tm + 1] (zero at the direction's first step)
-            const float* dGs = d == 0 ? dGd + (int64_t)B * 4 * H : dGd;
-            const float* hp = d == 0 ? out + d * H : out + (int64_t)B * 2 * H + d * H;
-            GF_TRY(launch_gemm_tn_acc(dGs, 4 * H, hp, 2 * H, gw_hh[d], H, nullptr, 4 * H, H, (int)(T - B), st, part, part_floats));
+        const float* dGd = ws + L.dG_at(d, 0);
+        if (k.gw_ih && k.gw_ih[d]) GF_TRY(launch_gemm_tn_acc(dGd, 4 * H, k.x, In, k.gw_ih[d], In, nullptr, 4 * H, In, T, k.st, part, L.part_floats));
+        if (k.gw_hh && k.gw_hh[d] && S > 1) {
+            // h_prev of time tm: forward direction out[tm - 1], reverse direction out[tm + 1] (zero at the direction's first step):
+            // the forward direction pairs dG of times 1 .. S-1 with out of 0 .. S-2, the reverse one dG of 0 .. S-2 with out of 1 .. S-1
+            const int from = d == 0 ? 1 : 0;
+            GF_TRY(launch_gemm_tn_acc(ws + L.dG_at(d, from), 4 * H, out + L.h_at(d, 1 - from), 2 * H, k.gw_hh[d], H, nullptr, 4 * H, H, T - B, k.st,
+                                      part, L.part_floats));
         }
-        float* b1 = gb_ih ? gb_ih[d] : nullptr;
-        float* b2 = gb_hh ? gb_hh[d] : nullptr;
+        float* b1 = k.gb_ih ? k.gb_ih[d] : nullptr;
+        float* b2 = k.gb_hh ? k.gb_hh[d] : nullptr;
         if (b1 || b2) {
-            hipLaunchKernelGGL(lstm_colsum2_kernel, dim3((4 * H + 255) / 256), dim3(256), 0, st, dGd, (int)T, 4 * H, b1, b2);
+            hipLaunchKernelGGL(lstm_colsum2_kernel, dim3((4 * H + 255) / 256), dim3(256), 0, k.st, dGd, T, 4 * H, b1, b2);
             GF_LAUNCH_CHECK();
         }
     }
-    if (dx) {
+    if (k.dx) {
         EpiArgs e0;
-        GF_TRY(launch_gemm_nn(dG, 4 * H, w_ih[0], In, dx, In, (int)T, In, 4 * H, EPI_NONE, e0, st));
+        GF_TRY(launch_gemm_nn(ws + L.dG_at(0, 0), 4 * H, k.w_ih[0], In, k.dx, In, T, In, 4 * H, EPI_NONE, e0, k.st));
         EpiArgs e1;
-        e1.aux_in = dx;                              // + the reverse direction's share (each element read and written by one thread)
-        GF_TRY(launch_gemm_nn(dG + T * 4 * H, 4 * H, w_ih[1], In, dx, In, (int)T, In, 4 * H, EPI_NONE, e1, st));
+        e1.aux_in = k.dx;                            // + the reverse direction's share (each element read and written by one thread)
+        GF_TRY(launch_gemm_nn(ws + L.dG_at(1, 0), 4 * H, k.w_ih[1], In, k.dx, In, T, In, 4 * H, EPI_NONE, e1, k.st));
     }
     return 0;
 }
 
-extern "C" int ganffn_lstm_layer_bwd(const ganffn_lstm_cfg* c, const float* d_out, const float* x, const float* out,
-                                     const float* const* w_ih, const float* const* w_hh, float* dx, float* const* gw_ih,
-                                     float* const* gw_hh, float* const* gb_ih, float* const* gb_hh, const float* saved,
-                                     float* workspace, void* stream) {
-    return lstm_layer_bwd(c, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, workspace, stream, 32);
-}
-
-// ---- L layers in one call -------------------------------------------------------------------------------------------
-extern "C" int64_t ganffn_lstm_stack_saved_floats(const ganffn_lstm_stack_cfg* c) { return check_lstm_stack(c) ? -1 : lstm_stack_saved(c).total; }
-extern "C" int64_t ganffn_lstm_stack_workspace_floats(const ganffn_lstm_stack_cfg* c) {
-    return check_lstm_stack(c) ? -1 : lstm_stack_layer_ws(c) + 2 * (int64_t)c->S * c->B * 2 * c->H;
-}
-
-// The per-layer entry points above, chained (same launches, same bits), with nn.LSTM(dropout = p)'s dropout on the output of every
-// layer but the last: site SITE_LSTM0 + l, offset rng_offset_add + l — what ops.lstm_forward issues as separate calls.
-static int lstm_stack_fwd(const ganffn_lstm_stack_cfg* c, const float* x, const float* const* w_ih, const float* const* w_hh,
-                          const float* const* b_ih, const float* const* b_hh, float* out, float* saved, float* workspace,
-                          const uint64_t* rng, uint64_t rng_offset_add, void* stream, int maxB, const int* lengths = nullptr) {
-    GF_TRY(check_lstm_stack(c, maxB));
-    GF_CHECK_ARG(x && w_ih && w_hh && b_ih && b_hh && out && saved && workspace, "lstm_stack_fwd: null pointer");
-    const bool drop = c->train && c->p > 0.f && c->L > 1;
-    GF_CHECK_ARG(!drop || rng, "lstm_stack_fwd: rng required in train mode");
-    const int64_t T = (int64_t)c->S * c->B, H = c->H;
-    const LstmStackOff so = lstm_stack_saved(c);
-    const float* in = x;
+// The layer driver L times (same launches, same bits as L per-layer calls), with nn.LSTM(dropout = p)'s dropout on the output of
+// every layer but the last: site SITE_LSTM0 + l, offset add + l — what ops.lstm_forward issues as separate calls.
+static int lstm_stack_fwd(const LstmStackCall& s) {
+    GF_TRY(check_pass(s.k, false, &s));
+    const ganffn_lstm_stack_cfg* c = s.c;
+    const LstmStackLayout L = lstm_stack_layout(c);
+    const int T = c->S * c->B;
+    const float* in = s.k.x;
     for (int l = 0; l < c->L; ++l) {
         const ganffn_lstm_cfg lc = stack_layer_cfg(c, l);
         const bool last = l + 1 == c->L;
-        float* o = last ? out : saved + so.outs + (int64_t)l * 2 * T * 2 * H;
-        GF_TRY(lstm_layer_fwd(&lc, in, w_ih + 2 * l, w_hh + 2 * l, b_ih + 2 * l, b_hh + 2 * l, o, saved + l * so.layer_stride,
-                              workspace, stream, maxB, lengths));
-        in = o;
-        if (!last && drop) {
-            float* dr = o + T * 2 * H;
-            GF_TRY(launch_dropout(o, dr, (int)T, 2 * (int)H, c->p, SITE_LSTM0 + l, rng, rng_offset_add + l, 1, (hipStream_t)stream));
+        LstmCall q = s.layer(&lc, l, L);
+        q.x = in; q.out = last ? s.k.out : s.k.saved + L.out(l);
+        GF_TRY(lstm_layer_fwd(q));
+        in = q.out;
+        if (!last && s.drop()) {
+            float* dr = s.k.saved + L.dropped(l);
+            GF_TRY(launch_dropout(q.out, dr, T, 2 * c->H, c->p, SITE_LSTM0 + l, s.rng, s.add + l, 1, s.k.st));
             in = dr;
         }
     }
     return 0;
 }
 
+// x, out: the forward's; the dropout masks are regenerated from {rng, add}
+static int lstm_stack_bwd(const LstmStackCall& s) {
+    GF_TRY(check_pass(s.k, true, &s));
+    const ganffn_lstm_stack_cfg* c = s.c;
+    const LstmStackLayout L = lstm_stack_layout(c);
+    const int T = c->S * c->B;
+    const float* d = s.k.d_out;
+    for (int l = c->L - 1; l >= 0; --l) {
+        const ganffn_lstm_cfg lc = stack_layer_cfg(c, l);
+        LstmCall q = s.layer(&lc, l, L);
+        q.d_out = d;
+        q.x = l == 0 ? s.k.x : s.k.saved + (s.drop() ? L.dropped(l - 1) : L.out(l - 1));
+        q.out = l + 1 == c->L ? s.k.out : s.k.saved + L.out(l);
+        q.dx = l == 0 ? s.k.dx : s.k.workspace + L.d_in(l);
+        GF_TRY(lstm_layer_bwd(q));
+        if (l > 0 && s.drop())
+            GF_TRY(launch_dropout(q.dx, q.dx, T, 2 * c->H, c->p, SITE_LSTM0 + (l - 1), s.rng, s.add + (l - 1), 1, s.k.st));
+        d = q.dx;
+    }
+    return 0;
+}
+
+// ---- the entry points: each states its family — the dialogue limit and whether it takes lengths — fills one call and runs a driver
+constexpr int PLAIN_MAX_DIALOGUES = 32;       // ganffn_lstm_* / ganffn_lstm_stack_*: the limit they always had (they keep refusing 33)
+
+extern "C" int64_t ganffn_lstm_saved_floats(const ganffn_lstm_cfg* c) { return check_lstm(c, PLAIN_MAX_DIALOGUES) ? -1 : lstm_layout(c).saved_total; }
+extern "C" int64_t ganffn_lstm_workspace_floats(const ganffn_lstm_cfg* c) { return check_lstm(c, PLAIN_MAX_DIALOGUES) ? -1 : lstm_layout(c).ws_total; }
+extern "C" int ganffn_lstm_layer_fwd(const ganffn_lstm_cfg* c, const float* x, const float* const* w_ih, const float* const* w_hh,
+                                     const float* const* b_ih, const float* const* b_hh, float* out, float* saved, float* workspace,
+                                     void* stream) {
+    return lstm_layer_fwd(lstm_call(c, PLAIN_MAX_DIALOGUES, nullptr, stream).forward(x, w_ih, w_hh, b_ih, b_hh, out, saved, workspace));
+}
+extern "C" int ganffn_lstm_layer_bwd(const ganffn_lstm_cfg* c, const float* d_out, const float* x, const float* out,
+                                     const float* const* w_ih, const float* const* w_hh, float* dx, float* const* gw_ih,
+                                     float* const* gw_hh, float* const* gb_ih, float* const* gb_hh, const float* saved,
+                                     float* workspace, void* stream) {
+    return lstm_layer_bwd(lstm_call(c, PLAIN_MAX_DIALOGUES, nullptr, stream)
+                              .backward(d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, workspace));
+}
+
+// L layers in one call.  gw_* / gb_*: arrays of [L][2] pointers, ACCUMULATED into like the per-layer backward (NULL arrays or
+// entries: not wanted); dx [S x B x In] may be NULL.
+extern "C" int64_t ganffn_lstm_stack_saved_floats(const ganffn_lstm_stack_cfg* c) {
+    return check_lstm_stack(c, PLAIN_MAX_DIALOGUES) ? -1 : lstm_stack_layout(c).saved_total;
+}
+extern "C" int64_t ganffn_lstm_stack_workspace_floats(const ganffn_lstm_stack_cfg* c) {
+    return check_lstm_stack(c, PLAIN_MAX_DIALOGUES) ? -1 : lstm_stack_layout(c).ws_total;
+}
 extern "C" int ganffn_lstm_stack_fwd(const ganffn_lstm_stack_cfg* c, const float* x, const float* const* w_ih, const float* const* w_hh,
                                      const float* const* b_ih, const float* const* b_hh, float* out, float* saved, float* workspace,
                                      const uint64_t* rng, uint64_t rng_offset_add, void* stream) {
-    return lstm_stack_fwd(c, x, w_ih, w_hh, b_ih, b_hh, out, saved, workspace, rng, rng_offset_add, stream, 32);
-}
-
-// x, out: the forward's; gw_* / gb_*: arrays of [L][2] pointers, ACCUMULATED into like the per-layer backward (NULL arrays or
-// entries: not wanted); dx [S x B x In] may be NULL.  The dropout masks are regenerated from {rng, rng_offset_add}.
-static int lstm_stack_bwd(const ganffn_lstm_stack_cfg* c, const float* d_out, const float* x, const float* out,
-                          const float* const* w_ih, const float* const* w_hh, float* dx, float* const* gw_ih,
-                          float* const* gw_hh, float* const* gb_ih, float* const* gb_hh, const float* saved,
-                          float* workspace, const uint64_t* rng, uint64_t rng_offset_add, void* stream, int maxB,
-                          const int* lengths = nullptr) {
-    GF_TRY(check_lstm_stack(c, maxB));
-    GF_CHECK_ARG(d_out && x && out && w_ih && w_hh && saved && workspace, "lstm_stack_bwd: null pointer");
-    const bool drop = c->train && c->p > 0.f && c->L > 1;
-    GF_CHECK_ARG(!drop || rng, "lstm_stack_bwd: rng required in train mode");
-    const int64_t T = (int64_t)c->S * c->B, H = c->H;
-    const LstmStackOff so = lstm_stack_saved(c);
-    float* dbuf = workspace + lstm_stack_layer_ws(c);          // [2][T x 2H]
-    const float* d = d_out;
-    for (int l = c->L - 1; l >= 0; --l) {
-        const ganffn_lstm_cfg lc = stack_layer_cfg(c, l);
-        const float* o = l + 1 == c->L ? out : saved + so.outs + (int64_t)l * 2 * T * 2 * H;
-        const float* prev = l == 0 ? nullptr : saved + so.outs + (int64_t)(l - 1) * 2 * T * 2 * H;
-        const float* in = l == 0 ? x : drop ? prev + T * 2 * H : prev;
-        float* dxl = l == 0 ? dx : dbuf + (int64_t)(l & 1) * T * 2 * H;
-        GF_TRY(lstm_layer_bwd(&lc, d, in, o, w_ih + 2 * l, w_hh + 2 * l, dxl, gw_ih ? gw_ih + 2 * l : nullptr,
-                              gw_hh ? gw_hh + 2 * l : nullptr, gb_ih ? gb_ih + 2 * l : nullptr, gb_hh ? gb_hh + 2 * l : nullptr,
-                              saved + l * so.layer_stride, workspace, stream, maxB, lengths));
-        if (l > 0 && drop)
-            GF_TRY(launch_dropout(dxl, dxl, (int)T, 2 * (int)H, c->p, SITE_LSTM0 + (l - 1), rng, rng_offset_add + (l - 1), 1, (hipStream_t)stream));
-        d = dxl;
-    }
-    return 0;
+    return lstm_stack_fwd({c, rng, rng_offset_add,
+                           lstm_call(nullptr, PLAIN_MAX_DIALOGUES, nullptr, stream).forward(x, w_ih, w_hh, b_ih, b_hh, out, saved, workspace)});
 }
 extern "C" int ganffn_lstm_stack_bwd(const ganffn_lstm_stack_cfg* c, const float* d_out, const float* x, const float* out,
                                      const float* const* w_ih, const float* const* w_hh, float* dx, float* const* gw_ih,
                                      float* const* gw_hh, float* const* gb_ih, float* const* gb_hh, const float* saved,
                                      float* workspace, const uint64_t* rng, uint64_t rng_offset_add, void* stream) {
-    return lstm_stack_bwd(c, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, workspace, rng, rng_offset_add, stream, 32);
+    return lstm_stack_bwd({c, rng, rng_offset_add, lstm_call(nullptr, PLAIN_MAX_DIALOGUES, nullptr, stream)
+                                                       .backward(d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, workspace)});
 }
 
 // ---- 1 <= B <= GANFFN_MAX_DIALOGUES dialogues per call ---------------------------------------------------------------------
-// The bodies above with the skinny products' dialogue-tile axis (dialogue_rnn.hip): the same layouts and sizes as functions of
+// The same drivers with the skinny products' dialogue-tile axis (dialogue_rnn.hip): the same layouts and sizes as functions of
 // B, the same launches per step; B <= 32 is the launch sequence of the entry points above, bit for bit.
-extern "C" int64_t ganffn_lstm_batch_saved_floats(const ganffn_lstm_cfg* c) { return check_lstm(c, GANFFN_MAX_DIALOGUES) ? -1 : lstm_saved(c).total; }
-extern "C" int64_t ganffn_lstm_batch_workspace_floats(const ganffn_lstm_cfg* c) { return check_lstm(c, GANFFN_MAX_DIALOGUES) ? -1 : lstm_ws(c); }
+extern "C" int64_t ganffn_lstm_batch_saved_floats(const ganffn_lstm_cfg* c) { return check_lstm(c, GANFFN_MAX_DIALOGUES) ? -1 : lstm_layout(c).saved_total; }
+extern "C" int64_t ganffn_lstm_batch_workspace_floats(const ganffn_lstm_cfg* c) { return check_lstm(c, GANFFN_MAX_DIALOGUES) ? -1 : lstm_layout(c).ws_total; }
 extern "C" int ganffn_lstm_batch_layer_fwd(const ganffn_lstm_cfg* c, const float* x, const float* const* w_ih, const float* const* w_hh,
                                            const float* const* b_ih, const float* const* b_hh, float* out, float* saved,
                                            float* workspace, void* stream) {
-    return lstm_layer_fwd(c, x, w_ih, w_hh, b_ih, b_hh, out, saved, workspace, stream, GANFFN_MAX_DIALOGUES);
+    return lstm_layer_fwd(lstm_call(c, GANFFN_MAX_DIALOGUES, nullptr, stream).forward(x, w_ih, w_hh, b_ih, b_hh, out, saved, workspace));
 }
 extern "C" int ganffn_lstm_batch_layer_bwd(const ganffn_lstm_cfg* c, const float* d_out, const float* x, const float* out,
                                            const float* const* w_ih, const float* const* w_hh, float* dx, float* const* gw_ih,
                                            float* const* gw_hh, float* const* gb_ih, float* const* gb_hh, const float* saved,
                                            float* workspace, void* stream) {
-    return lstm_layer_bwd(c, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, workspace, stream, GANFFN_MAX_DIALOGUES);
+    return lstm_layer_bwd(lstm_call(c, GANFFN_MAX_DIALOGUES, nullptr, stream)
+                              .backward(d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, workspace));
 }
 extern "C" int64_t ganffn_lstm_stack_batch_saved_floats(const ganffn_lstm_stack_cfg* c) {
-    return check_lstm_stack(c, GANFFN_MAX_DIALOGUES) ? -1 : lstm_stack_saved(c).total;
+    return check_lstm_stack(c, GANFFN_MAX_DIALOGUES) ? -1 : lstm_stack_layout(c).saved_total;
 }
 extern "C" int64_t ganffn_lstm_stack_batch_workspace_floats(const ganffn_lstm_stack_cfg* c) {
-    return check_lstm_stack(c, GANFFN_MAX_DIALOGUES) ? -1 : lstm_stack_layer_ws(c) + 2 * (int64_t)c->S * c->B * 2 * c->H;
+    return check_lstm_stack(c, GANFFN_MAX_DIALOGUES) ? -1 : lstm_stack_layout(c).ws_total;
 }
 extern "C" int ganffn_lstm_stack_batch_fwd(const ganffn_lstm_stack_cfg* c, const float* x, const float* const* w_ih,
                                            const float* const* w_hh, const float* const* b_ih, const float* const* b_hh, float* out,
                                            float* saved, float* workspace, const uint64_t* rng, uint64_t rng_offset_add, void* stream) {
-    return lstm_stack_fwd(c, x, w_ih, w_hh, b_ih, b_hh, out, saved, workspace, rng, rng_offset_add, stream, GANFFN_MAX_DIALOGUES);
+    return lstm_stack_fwd({c, rng, rng_offset_add,
+                           lstm_call(nullptr, GANFFN_MAX_DIALOGUES, nullptr, stream).forward(x, w_ih, w_hh, b_ih, b_hh, out, saved, workspace)});
 }
 extern "C" int ganffn_lstm_stack_batch_bwd(const ganffn_lstm_stack_cfg* c, const float* d_out, const float* x, const float* out,
                                            const float* const* w_ih, const float* const* w_hh, float* dx, float* const* gw_ih,
                                            float* const* gw_hh, float* const* gb_ih, float* const* gb_hh, const float* saved,
                                            float* workspace, const uint64_t* rng, uint64_t rng_offset_add, void* stream) {
-    return lstm_stack_bwd(c, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, workspace, rng, rng_offset_add, stream,
-                          GANFFN_MAX_DIALOGUES);
+    return lstm_stack_bwd({c, rng, rng_offset_add, lstm_call(nullptr, GANFFN_MAX_DIALOGUES, nullptr, stream)
+                                                       .backward(d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, workspace)});
 }
 
 // ---- packed sequences: lengths[b] real steps per dialogue ------------------------------------------------------------------
-// The _batch_ bodies with the length-aware gate kernels (the rule: top of the file): same layouts, sizes (ganffn_lstm_batch_*_floats /
-// ganffn_lstm_stack_batch_*_floats) and launches.  lengths: int32 [B] on the device, never read by the host.
+// The _batch_ calls with lengths, so with the length-aware gate kernels (the rule: top of the file): same layouts, sizes
+// (ganffn_lstm_batch_*_floats / ganffn_lstm_stack_batch_*_floats) and launches.  lengths: int32 [B] on the device, never read by
+// the host; a null one is refused here, before anything else: behind these entry points it would select the other kernels.
 extern "C" int ganffn_lstm_packed_layer_fwd(const ganffn_lstm_cfg* c, const int32_t* lengths, const float* x, const float* const* w_ih,
                                             const float* const* w_hh, const float* const* b_ih, const float* const* b_hh, float* out,
                                             float* saved, float* workspace, void* stream) {
     GF_CHECK_ARG(lengths, "lstm_packed_layer_fwd: null lengths");
-    return lstm_layer_fwd(c, x, w_ih, w_hh, b_ih, b_hh, out, saved, workspace, stream, GANFFN_MAX_DIALOGUES, lengths);
+    return lstm_layer_fwd(lstm_call(c, GANFFN_MAX_DIALOGUES, lengths, stream).forward(x, w_ih, w_hh, b_ih, b_hh, out, saved, workspace));
 }
 extern "C" int ganffn_lstm_packed_layer_bwd(const ganffn_lstm_cfg* c, const int32_t* lengths, const float* d_out, const float* x,
                                             const float* out, const float* const* w_ih, const float* const* w_hh, float* dx,
                                             float* const* gw_ih, float* const* gw_hh, float* const* gb_ih, float* const* gb_hh,
                                             const float* saved, float* workspace, void* stream) {
     GF_CHECK_ARG(lengths, "lstm_packed_layer_bwd: null lengths");
-    return lstm_layer_bwd(c, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, workspace, stream, GANFFN_MAX_DIALOGUES,
-                          lengths);
+    return lstm_layer_bwd(lstm_call(c, GANFFN_MAX_DIALOGUES, lengths, stream)
+                              .backward(d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, workspace));
 }
 extern "C" int ganffn_lstm_stack_packed_fwd(const ganffn_lstm_stack_cfg* c, const int32_t* lengths, const float* x,
                                             const float* const* w_ih, const float* const* w_hh, const float* const* b_ih,
                                             const float* const* b_hh, float* out, float* saved, float* workspace, const uint64_t* rng,
                                             uint64_t rng_offset_add, void* stream) {
     GF_CHECK_ARG(lengths, "lstm_stack_packed_fwd: null lengths");
-    return lstm_stack_fwd(c, x, w_ih, w_hh, b_ih, b_hh, out, saved, workspace, rng, rng_offset_add, stream, GANFFN_MAX_DIALOGUES, lengths);
+    return lstm_stack_fwd({c, rng, rng_offset_add,
+                           lstm_call(nullptr, GANFFN_MAX_DIALOGUES, lengths, stream).forward(x, w_ih, w_hh, b_ih, b_hh, out, saved, workspace)});
 }
 extern "C" int ganffn_lstm_stack_packed_bwd(const ganffn_lstm_stack_cfg* c, const int32_t* lengths, const float* d_out, const float* x,
                                             const float* out, const float* const* w_ih, const float* const* w_hh, float* dx,
@@ -474,6 +548,7 @@ extern "C" int ganffn_lstm_stack_packed_bwd(const ganffn_lstm_stack_cfg* c, cons
                                             const float* saved, float* workspace, const uint64_t* rng, uint64_t rng_offset_add,
                                             void* stream) {
     GF_CHECK_ARG(lengths, "lstm_stack_packed_bwd: null lengths");
-    return lstm_stack_bwd(c, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, workspace, rng, rng_offset_add, stream,
-                          GANFFN_MAX_DIALOGUES, lengths);
+    return lstm_stack_bwd({c, rng, rng_offset_add, lstm_call(nullptr, GANFFN_MAX_DIALOGUES, lengths, stream)
+                                                       .backward(d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, workspace)});
 }
+

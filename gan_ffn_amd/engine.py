@@ -1583,11 +1583,7 @@ class MeldEngine(_Runner):
         if fit == "grow":
             cS, cB = self._alloc_S, self._alloc_B
             lib = _lib.load()
-            cfgc = _lib.LstmStackCfg(cS, cB, self.Dm, self.He, self.L, self.p_lstm, 1)
-            fam = "ganffn_lstm_stack_batch_" if cB > 32 else "ganffn_lstm_stack_"       # (the same sizes as functions of B)
-            n_saved, n_ws = int(getattr(lib, fam + "saved_floats")(C.byref(cfgc))), int(getattr(lib, fam + "workspace_floats")(C.byref(cfgc)))
-            if n_saved < 0 or n_ws < 0:
-                _lib.check(-1, "ganffn_lstm_stack_*_floats")
+            n_saved, n_ws = ops.lstm_sizes(_lib.LstmStackCfg(cS, cB, self.Dm, self.He, self.L, self.p_lstm, 1), self.packed)
             T, D2, Cn = cS * cB, self.D2, self.n_classes
             z = lambda n: torch.empty(n, device=self.dev, dtype=torch.float32)
             self._f = dict(emotions=z(T * D2), xq=z(T * D2), att=z(T * D2), alpha=z(cB * cS * cS), tanh_s=z(cB * cS * cS),
@@ -1622,13 +1618,9 @@ class MeldEngine(_Runner):
         n_t = 8 * self.L
         w_t, b_t, w_s, b_s = (self._p(n_t + j) for j in range(4))
         # ---- forward: LSTM stack -> transform -> general2 attention -> hardswish head -> loss       (model.py:546-560)
-        if self.packed:
-            lengths = umask.sum(1).to(torch.int32)          # on the device, no host read; alive until the backward is enqueued
-            fam, head = "ganffn_lstm_stack_packed_", (C.byref(cfg), P(lengths))
-        else:
-            fam, head = "ganffn_lstm_stack_batch_" if B > 32 else "ganffn_lstm_stack_", (C.byref(cfg),)
-        _lib.call(fam + "fwd", *head, P(text), w_ih, w_hh, b_ih, b_hh, P(f["emotions"]), P(f["saved"]), P(f["ws"]),
-                  P(rng), C.c_uint64(base), st)
+        # packed: lengths on the device, no host read; alive until the backward is enqueued.  The entry points: ops.lstm_family
+        lengths = umask.sum(1).to(torch.int32) if self.packed else None
+        ops.lstm_stack_fwd_raw(cfg, text, w_ih, w_hh, b_ih, b_hh, f["emotions"], f["saved"], f["ws"], rng, base, lengths=lengths)
         ops.linear_fwd_raw(f["emotions"], w_t, b_t, f["xq"], T, D2, D2)
         _lib.call("ganffn_general2_attention_fwd", P(f["xq"]), P(f["emotions"]), P(umask), P(f["att"]), P(f["alpha"]), P(f["tanh_s"]),
                   S, B, D2, st)
@@ -1649,8 +1641,8 @@ class MeldEngine(_Runner):
         # d emotions = the residual + the attention's memory side + its query side through transform
         _lib.call("ganffn_add3", P(f["d_res"]), P(f["d_mem"]), P(f["d_tr"]), P(f["d_em"]), C.c_int64(T * D2), st)
         g_ih, g_hh, gb_ih, gb_hh = self._g
-        _lib.call(fam + "bwd", *head, P(f["d_em"]), P(text), P(f["emotions"]), w_ih, w_hh, None, g_ih, g_hh, gb_ih,
-                  gb_hh, P(f["saved"]), P(f["ws"]), P(rng), C.c_uint64(base), st)
+        ops.lstm_stack_bwd_raw(cfg, f["d_em"], text, f["emotions"], w_ih, w_hh, None, g_ih, g_hh, gb_ih, gb_hh, f["saved"], f["ws"],
+                               rng, base, lengths=lengths)
         self.params.all_reduce(self.pg)
         self.params.adam(self.lr, self.wd, self.world)
         return self.loss, log_prob

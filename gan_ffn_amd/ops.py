@@ -910,6 +910,68 @@ def dialogue_rnn_run(cells, Us, qmasks, training):
 # ----------------------------------------------------------------------------------------------
 SITE_LSTM = 64          # + layer: the dropout nn.LSTM(dropout=p) applies to the output of every layer but the last
 
+# The entry points of each family (lstm_family).  The naming is irregular — "batch" / "packed" stand before "layer" and behind
+# "stack" — so the heads are written out; the packed family has no size functions of its own and takes the _batch_ ones.
+_LSTM_ENTRY = {
+    "": {"layer": "ganffn_lstm_layer_", "stack": "ganffn_lstm_stack_",
+         "layer_sizes": "ganffn_lstm_", "stack_sizes": "ganffn_lstm_stack_"},
+    "batch": {"layer": "ganffn_lstm_batch_layer_", "stack": "ganffn_lstm_stack_batch_",
+              "layer_sizes": "ganffn_lstm_batch_", "stack_sizes": "ganffn_lstm_stack_batch_"},
+    "packed": {"layer": "ganffn_lstm_packed_layer_", "stack": "ganffn_lstm_stack_packed_",
+               "layer_sizes": "ganffn_lstm_batch_", "stack_sizes": "ganffn_lstm_stack_batch_"},
+}
+
+
+def lstm_family(B, packed):
+    """THE rule for which entry-point family of the LSTM a call takes (every family is a thin wrapper over the one set of
+    drivers in csrc/lstm.hip; the names: _LSTM_ENTRY):
+      "packed"  lengths are given, whatever B (up to MAX_DIALOGUES)      ganffn_lstm_packed_layer_* / ganffn_lstm_stack_packed_*
+      "batch"   otherwise B > 32 dialogues (up to MAX_DIALOGUES)         ganffn_lstm_batch_layer_* / ganffn_lstm_stack_batch_*
+      ""        otherwise                                                ganffn_lstm_layer_* / ganffn_lstm_stack_*"""
+    if packed:
+        return "packed"
+    return "batch" if B > 32 else ""
+
+
+def lstm_sizes(cfg, packed=False):
+    """(n_saved, n_ws) floats of a layer call (_lib.LstmCfg) or a stack call (_lib.LstmStackCfg), from the size functions of
+    the family cfg.B and `packed` select"""
+    head = _LSTM_ENTRY[lstm_family(cfg.B, packed)]["stack_sizes" if isinstance(cfg, _lib.LstmStackCfg) else "layer_sizes"]
+    n_saved, n_ws = (int(getattr(_lib.load(), head + w)(C.byref(cfg))) for w in ("saved_floats", "workspace_floats"))
+    if n_saved < 0 or n_ws < 0:
+        _lib.check(-1, head + "*_floats")
+    return n_saved, n_ws
+
+
+def _lstm_call(kind, what, cfg, lengths, *args):
+    head = (C.byref(cfg),) if lengths is None else (C.byref(cfg), _ptr(lengths))
+    _lib.call(_LSTM_ENTRY[lstm_family(cfg.B, lengths is not None)][kind] + what, *head, *args, _stream())
+
+
+def lstm_layer_fwd_raw(cfg, x, w_ih, w_hh, b_ih, b_hh, out, saved, ws, lengths=None):
+    """one layer forward: ONE call of the family's layer_fwd (lstm_family; lengths given: the packed one, lengths behind cfg).
+    cfg: _lib.LstmCfg; w_* / b_*: arrays of 2 device pointers (forward, reverse), passed as they are; the rest: tensors."""
+    _lstm_call("layer", "fwd", cfg, lengths, _ptr(x), w_ih, w_hh, b_ih, b_hh, _ptr(out), _ptr(saved), _ptr(ws))
+
+
+def lstm_layer_bwd_raw(cfg, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, ws, lengths=None):
+    """lstm_layer_fwd_raw's backward: ONE call of the family's layer_bwd; g*: arrays of 2 gradient pointers (accumulated into;
+    None or a null entry: not wanted), dx may be None"""
+    _lstm_call("layer", "bwd", cfg, lengths, _ptr(d_out), _ptr(x), _ptr(out), w_ih, w_hh, _ptr(dx), gw_ih, gw_hh, gb_ih, gb_hh,
+               _ptr(saved), _ptr(ws))
+
+
+def lstm_stack_fwd_raw(cfg, x, w_ih, w_hh, b_ih, b_hh, out, saved, ws, rng, add, lengths=None):
+    """L layers with the inter-layer dropout forward: ONE call of the family's stack fwd.  cfg: _lib.LstmStackCfg; w_* / b_*:
+    arrays of [L][2] device pointers, passed as they are; rng: the Philox state tensor, add: the offset."""
+    _lstm_call("stack", "fwd", cfg, lengths, _ptr(x), w_ih, w_hh, b_ih, b_hh, _ptr(out), _ptr(saved), _ptr(ws), _ptr(rng), C.c_uint64(add))
+
+
+def lstm_stack_bwd_raw(cfg, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, ws, rng, add, lengths=None):
+    """lstm_stack_fwd_raw's backward: ONE call of the family's stack bwd; g*: arrays of [L][2] gradient pointers"""
+    _lstm_call("stack", "bwd", cfg, lengths, _ptr(d_out), _ptr(x), _ptr(out), w_ih, w_hh, _ptr(dx), gw_ih, gw_hh, gb_ih, gb_hh,
+               _ptr(saved), _ptr(ws), _ptr(rng), C.c_uint64(add))
+
 
 def _lstm_layer_fwd(ctx, x, lengths, params):
     """the forward of LstmLayerFn (lengths None) and LstmPackedLayerFn: chunks of MAX_DIALOGUES, lengths sliced with the batch"""
@@ -929,19 +991,13 @@ def _lstm_layer_fwd(ctx, x, lengths, params):
     for b0 in range(0, B, MAX_DIALOGUES):
         b1 = min(B, b0 + MAX_DIALOGUES)
         cfg = _lib.LstmCfg(S, b1 - b0, In, H)
-        fam = "ganffn_lstm_batch_" if b1 - b0 > 32 or lengths is not None else "ganffn_lstm_"
-        n_saved = int(getattr(_lib.load(), fam + "saved_floats")(C.byref(cfg)))
-        n_ws = int(getattr(_lib.load(), fam + "workspace_floats")(C.byref(cfg)))
-        if n_saved < 0 or n_ws < 0:
-            _lib.check(-1, fam + "*_floats")
+        n_saved, n_ws = lstm_sizes(cfg, lengths is not None)
         xc = x if (b0, b1) == (0, B) else x[:, b0:b1].contiguous()
         oc = out if (b0, b1) == (0, B) else torch.empty(S, b1 - b0, 2 * H, device=x.device, dtype=torch.float32)
         saved = torch.empty(n_saved, device=x.device, dtype=torch.float32)
         ws = torch.empty(n_ws, device=x.device, dtype=torch.float32)
         lc = None if lengths is None else lengths[b0:b1]          # (a slice of a contiguous vector: contiguous, 4-byte aligned)
-        head = (fam + "layer_fwd", C.byref(cfg)) if lc is None else ("ganffn_lstm_packed_layer_fwd", C.byref(cfg), _ptr(lc))
-        _lib.call(*head, _ptr(xc), _ptr_array([p[0], p[4]]), _ptr_array([p[1], p[5]]),
-                  _ptr_array([p[2], p[6]]), _ptr_array([p[3], p[7]]), _ptr(oc), _ptr(saved), _ptr(ws), _stream())
+        lstm_layer_fwd_raw(cfg, xc, *[_ptr_array([p[j], p[4 + j]]) for j in range(4)], oc, saved, ws, lengths=lc)
         if oc is not out:
             out[:, b0:b1] = oc
         chunks.append((b0, b1, xc, oc, saved, lc))
@@ -960,17 +1016,13 @@ def _lstm_layer_bwd(ctx, d_out, i_x, i_p):
     grads = [torch.zeros_like(t) if ctx.needs_input_grad[i_p + i] else None for i, t in enumerate(p)]
     for (b0, b1, xc, oc, saved, lc) in ctx.chunks:
         cfg = _lib.LstmCfg(S, b1 - b0, In, H)
-        fam = "ganffn_lstm_batch_" if b1 - b0 > 32 or lc is not None else "ganffn_lstm_"
-        n_ws = int(getattr(_lib.load(), fam + "workspace_floats")(C.byref(cfg)))
-        ws = torch.empty(n_ws, device=d_out.device, dtype=torch.float32)
+        ws = torch.empty(lstm_sizes(cfg, lc is not None)[1], device=d_out.device, dtype=torch.float32)
         dc = d_out if (b0, b1) == (0, B) else d_out[:, b0:b1].contiguous()
         dxc = None
         if need_dx:
             dxc = dx if (b0, b1) == (0, B) else torch.empty(S, b1 - b0, In, device=d_out.device, dtype=torch.float32)
-        head = (fam + "layer_bwd", C.byref(cfg)) if lc is None else ("ganffn_lstm_packed_layer_bwd", C.byref(cfg), _ptr(lc))
-        _lib.call(*head, _ptr(dc), _ptr(xc), _ptr(oc), _ptr_array([p[0], p[4]]), _ptr_array([p[1], p[5]]),
-                  _ptr(dxc), _ptr_array([grads[0], grads[4]]), _ptr_array([grads[1], grads[5]]), _ptr_array([grads[2], grads[6]]),
-                  _ptr_array([grads[3], grads[7]]), _ptr(saved), _ptr(ws), _stream())
+        lstm_layer_bwd_raw(cfg, dc, xc, oc, _ptr_array([p[0], p[4]]), _ptr_array([p[1], p[5]]), dxc,
+                           *[_ptr_array([grads[j], grads[4 + j]]) for j in range(4)], saved, ws, lengths=lc)
         if need_dx and dxc is not dx:
             dx[:, b0:b1] = dxc
     return dx, grads

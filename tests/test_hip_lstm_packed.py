@@ -189,19 +189,17 @@ def test_four_layer_packed_stack_in_train_mode_matches_the_oracle_with_the_same_
     arr = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
     col = lambda j, src: [src[names[4 * i + j]] for i in range(2 * L)]
     cfg = _lib.LstmStackCfg(S, B, In, H, L, p, 1)
-    lib = _lib.load()
-    n_saved, n_ws = int(lib.ganffn_lstm_stack_batch_saved_floats(C.byref(cfg))), int(lib.ganffn_lstm_stack_batch_workspace_floats(C.byref(cfg)))
+    n_saved, n_ws = ops.lstm_sizes(cfg, packed=True)            # (the _batch_ size functions)
     assert n_saved > 0 and n_ws > 0
     saved, ws = torch.empty(n_saved, device="cuda"), torch.empty(n_ws, device="cuda")
     out_s, dx_s = torch.empty(S, B, 2 * H, device="cuda"), torch.empty(S, B, In, device="cuda")
     xd, dy = x.cuda(), gy.cuda()
     ops.manual_seed(seed)
     rng = ops.DeviceRng.get(xd.device)
-    _lib.call("ganffn_lstm_stack_packed_fwd", C.byref(cfg), ops._ptr(ln), ops._ptr(xd), arr(col(0, Pd)), arr(col(1, Pd)), arr(col(2, Pd)),
-              arr(col(3, Pd)), ops._ptr(out_s), ops._ptr(saved), ops._ptr(ws), ops._ptr(rng.state), C.c_uint64(0), ops._stream())
-    _lib.call("ganffn_lstm_stack_packed_bwd", C.byref(cfg), ops._ptr(ln), ops._ptr(dy), ops._ptr(xd), ops._ptr(out_s), arr(col(0, Pd)),
-              arr(col(1, Pd)), ops._ptr(dx_s), arr(col(0, Gs)), arr(col(1, Gs)), arr(col(2, Gs)), arr(col(3, Gs)), ops._ptr(saved),
-              ops._ptr(ws), ops._ptr(rng.state), C.c_uint64(0), ops._stream())
+    # lengths given: ganffn_lstm_stack_packed_fwd / _bwd
+    weights = [arr(col(j, Pd)) for j in range(4)]
+    ops.lstm_stack_fwd_raw(cfg, xd, *weights, out_s, saved, ws, rng.state, 0, lengths=ln)
+    ops.lstm_stack_bwd_raw(cfg, dy, xd, out_s, *weights[:2], dx_s, *[arr(col(j, Gs)) for j in range(4)], saved, ws, rng.state, 0, lengths=ln)
     torch.cuda.synchronize()
     assert torch.equal(out_s, y) and torch.equal(dx_s, dx)
     for k in names:

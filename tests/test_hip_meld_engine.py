@@ -188,16 +188,15 @@ def test_lstm_stack_entry_points_give_the_bits_of_the_per_layer_chain():
     Pd = {k: v.detach() for k, v in P.items()}
     cfg = _lib.LstmStackCfg(S, B, In, H, L, p, 1)
     lib = _lib.load()
-    n_saved, n_ws = int(lib.ganffn_lstm_stack_saved_floats(C.byref(cfg))), int(lib.ganffn_lstm_stack_workspace_floats(C.byref(cfg)))
+    assert ops.lstm_family(B, False) == ""                      # ganffn_lstm_stack_fwd / _bwd and their size functions
+    n_saved, n_ws = ops.lstm_sizes(cfg)
     assert n_saved > 0 and n_ws > 0
     saved, ws = torch.empty(n_saved, device="cuda"), torch.empty(n_ws, device="cuda")
     out_s, dx_s = torch.empty(S, B, 2 * H, device="cuda"), torch.empty(S, B, In, device="cuda")
     xd = x.detach()
-    _lib.call("ganffn_lstm_stack_fwd", C.byref(cfg), ops._ptr(xd), arr(col(0, Pd)), arr(col(1, Pd)), arr(col(2, Pd)), arr(col(3, Pd)),
-              ops._ptr(out_s), ops._ptr(saved), ops._ptr(ws), ops._ptr(rng.state), C.c_uint64(base), ops._stream())
-    _lib.call("ganffn_lstm_stack_bwd", C.byref(cfg), ops._ptr(dy), ops._ptr(xd), ops._ptr(out_s), arr(col(0, Pd)), arr(col(1, Pd)),
-              ops._ptr(dx_s), arr(col(0, G)), arr(col(1, G)), arr(col(2, G)), arr(col(3, G)), ops._ptr(saved), ops._ptr(ws),
-              ops._ptr(rng.state), C.c_uint64(base), ops._stream())
+    weights = [arr(col(j, Pd)) for j in range(4)]
+    ops.lstm_stack_fwd_raw(cfg, xd, *weights, out_s, saved, ws, rng.state, base)
+    ops.lstm_stack_bwd_raw(cfg, dy, xd, out_s, *weights[:2], dx_s, *[arr(col(j, G)) for j in range(4)], saved, ws, rng.state, base)
     torch.cuda.synchronize()
     assert torch.equal(out_s, out_c.detach())
     assert torch.equal(dx_s, x.grad)
@@ -207,8 +206,7 @@ def test_lstm_stack_entry_points_give_the_bits_of_the_per_layer_chain():
     # eval mode: no dropout, no rng needed
     cfg_e = _lib.LstmStackCfg(S, B, In, H, L, p, 0)
     out_e = torch.empty_like(out_s)
-    _lib.call("ganffn_lstm_stack_fwd", C.byref(cfg_e), ops._ptr(xd), arr(col(0, Pd)), arr(col(1, Pd)), arr(col(2, Pd)), arr(col(3, Pd)),
-              ops._ptr(out_e), ops._ptr(saved), ops._ptr(ws), None, C.c_uint64(0), ops._stream())
+    ops.lstm_stack_fwd_raw(cfg_e, xd, *weights, out_e, saved, ws, None, 0)
     assert torch.equal(out_e, ops.lstm_forward(xd, lstm, False).detach())
     bad = _lib.LstmStackCfg(S, 33, In, H, L, p, 1)
     assert lib.ganffn_lstm_stack_saved_floats(C.byref(bad)) < 0

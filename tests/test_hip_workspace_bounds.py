@@ -1,4 +1,4 @@
-"""No encoder or head call writes past the size its size function reports.
+"""No encoder, head or LSTM call writes past the size its size function reports.
 
 Every buffer a call writes (outputs, saved, workspace, K/V cache, gradients) is a tensor of exactly the reported size plus 256
 guard floats of a fixed bit pattern; the call is handed the front part, and after each call every guard is compared with the
@@ -7,7 +7,11 @@ anything outside a tensor being touched.  The call lists are in workspace_bounds
 
 The sizes are the smallest at which the layouts can go wrong: T = 3 rows (every round-to-4 of a layout rounds) and T = 15 (three
 dialogues), two layers (a layer set above another, the cross-layer reach of the rowchain backward), at d_model 100 (rowchain,
-n100 and tn100 kernels, unreduced weight gradients) and at 64 (the generic path)."""
+n100 and tn100 kernels, unreduced weight gradients) and at 64 (the generic path).  The LSTM's (layer and stack calls of the
+three entry-point families): S = 1 (the first step is the last: no recurrent weight gradient), one and three dialogues, 33 (two
+dialogue tiles) behind the batch and packed entry points, an input wider and narrower than H (the partial slabs are sized for
+the larger), 1 layer (no between-layer region) and 3 (both of the alternating gradient buffers), eval and train with p = 0.5,
+packed lengths (1, 5, 3) and a ragged vector with dialogues of length 1."""
 import pytest
 import torch
 
@@ -36,6 +40,17 @@ def test_encoder_calls_stay_inside_their_buffers(E, H, F, S, B, train):
     want += ["fwd_pair"]
     want += ["stream step", "stream extend"] if not train else []
     assert seen == want
+
+
+@pytest.mark.parametrize("train", [False, True], ids=["eval", "train"])
+@pytest.mark.parametrize("family,S,B", WB.LSTM_CALLS, ids=["%s-%dx%d" % (f or "plain", s, b) for f, s, b in WB.LSTM_CALLS])
+def test_lstm_calls_stay_inside_their_buffers(family, S, B, train):
+    """layer and stack calls of every family (csrc/lstm.hip), at both width orders and at 1 and 3 layers; train: p = 0.5"""
+    seen = []
+    for In, H in WB.LSTM_WIDTHS:
+        for n_layers in WB.LSTM_LAYERS:
+            WB.run_lstm_case(WB.lstm_case(family, S, B, In, H, n_layers, train), _check_guards(seen))
+    assert seen == ["layer fwd", "layer bwd", "stack fwd", "stack bwd"] * (len(WB.LSTM_WIDTHS) * len(WB.LSTM_LAYERS))
 
 
 @pytest.mark.parametrize("train", [False, True], ids=["eval", "train"])

@@ -1,4 +1,4 @@
-"""The call lists of tests/test_hip_workspace_bounds.py: every encoder and head call on buffers of exactly the size the library
+"""The call lists of tests/test_hip_workspace_bounds.py: every encoder, head and LSTM call on buffers of exactly the size the library
 reports, each followed by GUARD floats of a fixed bit pattern inside the same tensor.  After every call `visit(label, buffers)`
 is handed the full tensors (guards included) the call could have written: the test checks the guards, a comparison of two
 libraries hashes them."""
@@ -95,6 +95,66 @@ def run_encoder_case(c, visit):
         ops.encoder_stream_extend_raw(cfg, c.B, 2, slot, count, pos, x_d[1:3].contiguous(), pe_d, slab_d, cache[:n_cache],
                                       out[:2 * c.B * c.E], wsx[:n_ext])
         visit("stream extend", {"out": out, "cache": cache, "ws": wsx})
+    torch.cuda.synchronize()
+
+
+LSTM_FAMILIES = ["", "batch", "packed"]      # ops.lstm_family: each one's entry points are called here whatever B is
+LSTM_SHAPES = [(1, 1), (3, 1), (5, 3), (5, 33)]   # (S, B): the first step is the last | one dialogue | three | two dialogue tiles
+LSTM_CALLS = [(f, s, b) for f in LSTM_FAMILIES for s, b in LSTM_SHAPES if f or b <= 32]      # (the plain family: at most 32 dialogues)
+LSTM_WIDTHS = [(12, 8), (4, 8)]             # (In, H): wider than H, narrower (the partial slabs are sized for the larger)
+LSTM_LAYERS = [1, 3]                         # no between-layer region | both parities of the alternating gradient buffer
+
+
+def lstm_lengths(S, B):
+    """packed lengths: (1, 5, 3) at (5, 3); ragged with dialogues of length 1 (the first among them) otherwise"""
+    return (1, 5, 3) if (S, B) == (5, 3) else tuple(1 + (3 * b) % S for b in range(B))
+
+
+def lstm_case(family, S, B, In, H, n_layers, train, p=0.5, lengths=None):
+    if family == "packed" and lengths is None:
+        lengths = lstm_lengths(S, B)
+    return types.SimpleNamespace(family=family, S=S, B=B, In=In, H=H, L=n_layers, train=train, p=p, lengths=lengths)
+
+
+def run_lstm_case(c, visit):
+    """layer forward | layer backward (layer 0's weights) | stack forward | stack backward, through the entry points and the size
+    functions of c.family"""
+    import ctypes as C
+    from gan_ffn_amd import _lib, ops
+    lib, names = _lib.load(), ops._LSTM_ENTRY[c.family]
+    gen = torch.Generator().manual_seed(SEED)
+    rnd = lambda scale, *shape: ((torch.rand(*shape, generator=gen) - 0.5) * scale).cuda()
+    S, B, In, H = c.S, c.B, c.In, c.H
+    x, d_out = rnd(1.0, S, B, In), rnd(1.0, S, B, 2 * H)
+    # [L][2] rows of w_ih, w_hh, b_ih, b_hh; the gradients start from 0.5 (they accumulate), each in a guarded tensor of its own
+    W = [[rnd(0.6, 4 * H, In if l == 0 else 2 * H), rnd(0.6, 4 * H, H), rnd(0.2, 4 * H), rnd(0.2, 4 * H)] for l in range(c.L) for _ in range(2)]
+    G = [[guarded(t.numel(), 0.5) for t in row] for row in W]
+    arrays = lambda rows, n_rows: [ops._ptr_array([r[j] for r in rows[:n_rows]]) for j in range(4)]
+    grads = lambda n_rows: [ops._ptr_array([g[j][:w[j].numel()] for g, w in zip(G[:n_rows], W)]) for j in range(4)]
+    named = lambda n_rows: {"g%s[%d]" % (k, i): G[i][j] for i in range(n_rows) for j, k in enumerate(("w_ih", "w_hh", "b_ih", "b_hh"))}
+    lengths = None if c.lengths is None else torch.tensor(c.lengths, dtype=torch.int32, device="cuda")
+    P, st = ops._ptr, ops._stream()
+    rng = torch.tensor([SEED, 0], dtype=torch.int64, device="cuda")
+
+    def sizes(kind, cfg):
+        n = tuple(int(getattr(lib, names[kind + "_sizes"] + w)(C.byref(cfg))) for w in ("saved_floats", "workspace_floats"))
+        assert n[0] > 0 and n[1] > 0, (kind, n)
+        return n
+
+    def call(kind, what, cfg, *args):
+        _lib.call(names[kind] + what, C.byref(cfg), *(() if lengths is None else (P(lengths),)), *args)
+
+    n_out, n_dx = S * B * 2 * H, S * B * In
+    for kind, cfg, n_rows, tail in (("layer", _lib.LstmCfg(S, B, In, H), 2, (st,)),
+                                    ("stack", _lib.LstmStackCfg(S, B, In, H, c.L, c.p, int(c.train)), 2 * c.L, (P(rng), C.c_uint64(ADD), st))):
+        n_saved, n_ws = sizes(kind, cfg)
+        out, saved, ws = guarded(n_out), guarded(n_saved), guarded(n_ws)
+        call(kind, "fwd", cfg, P(x), *arrays(W, n_rows), P(out[:n_out]), P(saved[:n_saved]), P(ws[:n_ws]), *tail)
+        visit(kind + " fwd", {"out": out, "saved": saved, "ws": ws})
+        dx, ws = guarded(n_dx), guarded(n_ws)
+        call(kind, "bwd", cfg, P(d_out), P(x), P(out[:n_out]), *arrays(W, n_rows)[:2], P(dx[:n_dx]), *grads(n_rows), P(saved[:n_saved]),
+             P(ws[:n_ws]), *tail)
+        visit(kind + " bwd", {"dx": dx, "ws": ws, "saved": saved, "out": out, **named(n_rows)})
     torch.cuda.synchronize()
 
 
