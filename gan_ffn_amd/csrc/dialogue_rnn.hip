@@ -1161,12 +1161,15 @@ static DrnnLayout drnn_layout(const ganffn_drnn_cfg* c, const ganffn_drnn_att& a
     L.saved_total = p;
 
     p = 0;
-    L.GI = take(B * 3 * H); L.GH = take(B * 3 * H); L.GIp = take(B * 3 * H); L.GHp = take(B * 3 * H);
+    // D_e > EC_MAXHE: the emotion cell runs per step and borrows GI, GH ([B x 3 He]) and dhdir ([B x He]) from the global and
+    // party cells, so those three hold the wider of the two cells (Hs); every other configuration keeps B*3*H / B*H
+    const int64_t Hs = He > EC_MAXHE && He > H ? He : H;
+    L.GI = take(B * 3 * Hs); L.GH = take(B * 3 * Hs); L.GIp = take(B * 3 * H); L.GHp = take(B * 3 * H);
     L.dGIg = take(T * 3 * H); L.dGHg = take(T * 3 * H); L.dGIp = take(T * 3 * H); L.dGHp = take(T * 3 * H);
     L.dGIe = take(T * 3 * He); L.dGHe = take(T * 3 * He);
     L.dXA = take(T * H); L.dCT = take(B * H); L.dG = take(T1 * H);
     L.dQa = take(B * P * H); L.dQb = take(B * P * H); L.dEa = take(B * He); L.dEb = take(B * He);
-    L.dQsel = take(B * H); L.dQSp = take(B * H); L.dQSg = take(B * H); L.dhdir = take(B * H); L.dhdirG = take(B * H); L.dQN = take(B * H);
+    L.dQsel = take(B * H); L.dQSp = take(B * H); L.dQSg = take(B * H); L.dhdir = take(B * Hs); L.dhdirG = take(B * H); L.dQN = take(B * H);
     L.GIe = take(T * 3 * He); L.dQNall = take(T * H);
     L.WT = take(4 * H * 3 * H);
     if (listener) {

@@ -294,6 +294,9 @@ typedef struct ganffn_drnn_grads {   /* accumulated into (+=); all NULL = input 
 } ganffn_drnn_grads;
 int64_t ganffn_drnn_saved_floats(const ganffn_drnn_cfg* cfg);      /* per direction */
 int64_t ganffn_drnn_workspace_floats(const ganffn_drnn_cfg* cfg);  /* per direction; fwd and bwd */
+/* (every ganffn_drnn_*_workspace_floats: with D_e > 128 the emotion cell runs per step and shares three step regions with the
+ * g / p cells — pre-activations 2 x [B x 3 D] and the direct-path gradient [B x D] — which are sized for D = max(D_g, D_e);
+ * for D_e > max(D_g, 128) that is 7 B (D_e - D_g) floats more than the D_g-sized regions.  D_e <= 128 or D_e <= D_g: D = D_g.) */
 /* every array argument has ndir entries */
 int ganffn_drnn_fwd(const ganffn_drnn_cfg* cfg, int ndir, const float* const* U, const int32_t* const* spk,
                     const float* const* mval, const ganffn_drnn_params* params, float* const* e_out,

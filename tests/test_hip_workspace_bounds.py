@@ -1,4 +1,4 @@
-"""No encoder, head or LSTM call writes past the size its size function reports.
+"""No encoder, head, LSTM or DialogueRNN call writes past the size its size function reports.
 
 Every buffer a call writes (outputs, saved, workspace, K/V cache, gradients) is a tensor of exactly the reported size plus 256
 guard floats of a fixed bit pattern; the call is handed the front part, and after each call every guard is compared with the
@@ -11,7 +11,13 @@ n100 and tn100 kernels, unreduced weight gradients) and at 64 (the generic path)
 three entry-point families): S = 1 (the first step is the last: no recurrent weight gradient), one and three dialogues, 33 (two
 dialogue tiles) behind the batch and packed entry points, an input wider and narrower than H (the partial slabs are sized for
 the larger), 1 layer (no between-layer region) and 3 (both of the alternating gradient buffers), eval and train with p = 0.5,
-packed lengths (1, 5, 3) and a ragged vector with dialogues of length 1."""
+packed lengths (1, 5, 3) and a ragged vector with dialogues of length 1.  The DialogueRNN's (forward and backward through
+ops.drnn_fwd_raw / drnn_bwd_raw, about 60 regions that depend on attention type, listener, parties and B): S = 1, one and three
+dialogues with a padded tail, 33 behind the batch entry points, one and two directions, eval and train with p = 0.5, widths
+(12, 8, 4) (emotion chain) and (8, 8, 132) (the per-step emotion cell with D_e > 2 D_g, whose pre-activations and direct-path
+gradient take regions sized for the wider cell), every attention type with and without the listener (general2 at S = 3, B = 1:
+9 tanh scores rounded to 12; concat at D_a = 4), and 1, 2 and 16 parties (16 with the listener: 34 products in one launch);
+saved and workspace start as the NaN pattern, so e, dU and every gradient must come out finite."""
 import pytest
 import torch
 
@@ -51,6 +57,26 @@ def test_lstm_calls_stay_inside_their_buffers(family, S, B, train):
         for n_layers in WB.LSTM_LAYERS:
             WB.run_lstm_case(WB.lstm_case(family, S, B, In, H, n_layers, train), _check_guards(seen))
     assert seen == ["layer fwd", "layer bwd", "stack fwd", "stack bwd"] * (len(WB.LSTM_WIDTHS) * len(WB.LSTM_LAYERS))
+
+
+@pytest.mark.parametrize("case", WB.DRNN_CASES, ids=[WB.drnn_case_id(c) for c in WB.DRNN_CASES])
+def test_drnn_calls_stay_inside_their_buffers(case):
+    """forward and backward of every entry-point family (csrc/dialogue_rnn.hip), on buffers of exactly ops.drnn_floats"""
+    seen = []
+    WB.run_drnn_case(case, _check_guards(seen))
+    assert seen == ["fwd", "bwd"]
+
+
+def test_drnn_cases_cover_every_family_attention_and_party_count():
+    from gan_ffn_amd import ops
+    cases = WB.DRNN_CASES
+    family = lambda c: ops.drnn_family(c[1], c[7], c[5], c[6])
+    for width in WB.DRNN_WIDTHS:
+        assert {family(c) for c in cases if c[4] == width} == {"", "listener", "att", "party", "batch"}, width
+    assert {(c[5], c[6]) for c in cases} == {(a, l) for a in ("general", "simple", "dot", "general2", "concat") for l in (False, True)}
+    assert {c[7] for c in cases} == {1, 2, 16} and {(c[0], c[1]) for c in cases} == {(1, 1), (3, 1), (5, 3), (5, 33)}
+    assert {c[2] for c in cases} == {1, 2} and {c[3] for c in cases} == {False, True}
+    assert (3, 1) in {(c[0], c[1]) for c in cases if c[5] == "general2"}
 
 
 @pytest.mark.parametrize("train", [False, True], ids=["eval", "train"])

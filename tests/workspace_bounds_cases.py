@@ -1,4 +1,4 @@
-"""The call lists of tests/test_hip_workspace_bounds.py: every encoder, head and LSTM call on buffers of exactly the size the library
+"""The call lists of tests/test_hip_workspace_bounds.py: every encoder, head, LSTM and DialogueRNN call on buffers of exactly the size the library
 reports, each followed by GUARD floats of a fixed bit pattern inside the same tensor.  After every call `visit(label, buffers)`
 is handed the full tensors (guards included) the call could have written: the test checks the guards, a comparison of two
 libraries hashes them."""
@@ -155,6 +155,100 @@ def run_lstm_case(c, visit):
         call(kind, "bwd", cfg, P(d_out), P(x), P(out[:n_out]), *arrays(W, n_rows)[:2], P(dx[:n_dx]), *grads(n_rows), P(saved[:n_saved]),
              P(ws[:n_ws]), *tail)
         visit(kind + " bwd", {"dx": dx, "ws": ws, "saved": saved, "out": out, **named(n_rows)})
+    torch.cuda.synchronize()
+
+
+DRNN_WIDTHS = {"chain": (12, 8, 4), "per-step": (8, 8, 132)}      # (D_m, D_g = D_p, D_e): emotion chain | per-step cell, D_e > 2 D_g
+DRNN_DA = 4
+# (S, B, ndir, train, width, attention, listener, parties) — not the full product: every entry-point family (ops.drnn_family),
+# every attention type with and without the listener, 1 / 2 / 16 parties, both width rows, every shape, both ndir, eval and train.
+# dot needs D_m == D_g (the per-step row); general2 at S = 3, B = 1 has TS = 9 floats rounded to 12; 16 parties with the
+# listener is the wide skinny group (34 problems in a launch), with 33 dialogues its tiled form.
+DRNN_CASES = [
+    (1, 1, 1, False, "chain", "general", False, 2), (3, 1, 2, True, "chain", "general", True, 2),
+    (5, 3, 2, True, "chain", "general", False, 2), (5, 3, 1, False, "per-step", "general", False, 2),
+    (5, 3, 2, True, "per-step", "general", True, 2), (1, 1, 2, False, "per-step", "general", False, 2),
+    (3, 1, 1, False, "chain", "general2", False, 2), (3, 1, 2, True, "chain", "general2", True, 2),
+    (5, 3, 1, True, "chain", "simple", False, 2), (5, 3, 2, False, "chain", "simple", True, 2),
+    (5, 3, 1, False, "per-step", "dot", False, 2), (3, 1, 2, True, "per-step", "dot", True, 2),
+    (5, 3, 2, True, "chain", "concat", False, 2), (5, 3, 1, False, "per-step", "concat", True, 2),
+    (5, 3, 1, True, "chain", "general", False, 1), (5, 3, 2, False, "chain", "general", True, 1),
+    (5, 3, 2, True, "per-step", "general", True, 16), (1, 1, 1, True, "per-step", "general2", False, 16),
+    (5, 33, 2, True, "chain", "general", False, 2), (5, 33, 1, False, "per-step", "concat", True, 2),
+    (5, 33, 2, True, "per-step", "general", True, 16)]
+DRNN_LENGTHS = {(5, 3): (5, 3, 1)}            # a padded tail (mval 0, U 0) at (5, 3); full dialogues elsewhere
+
+
+def drnn_case_id(case):
+    S, B, ndir, train, width, att, listener, parties = case
+    return "%dx%d-ndir%d-%s-%s-%s%s-P%d" % (S, B, ndir, "train" if train else "eval", width, att, "-listener" if listener else "", parties)
+
+
+def run_drnn_case(case, visit, p=0.5):
+    """forward | backward of ndir directions through ops.drnn_fwd_raw / drnn_bwd_raw (ops.drnn_family picks the entry points), every
+    written buffer guarded: e, alpha, saved, ws and dU per direction, every gradient tensor on its own (started from 0.5).  The
+    backward gets a fresh workspace: it may read alpha and saved, nothing the forward left in ws."""
+    from gan_ffn_amd import _lib, ops
+    S, B, ndir, train, width, att, listener, P = case
+    Dm, H, He = DRNN_WIDTHS[width]
+    Da = DRNN_DA if att == "concat" else 0
+    gen = torch.Generator().manual_seed(SEED)
+    rnd = lambda scale, *shape: ((torch.rand(*shape, generator=gen) - 0.5) * scale).cuda()
+    lens = torch.tensor(DRNN_LENGTHS.get((S, B), (S,) * B))
+    valid = (torch.arange(S).unsqueeze(1) < lens.unsqueeze(0)).float()               # (S, B)
+    cell = lambda Hc, In: [rnd(0.6, 3 * Hc, In), rnd(0.6, 3 * Hc, Hc), rnd(0.2, 3 * Hc), rnd(0.2, 3 * Hc)]
+    att_shapes = {"general": [(H, Dm)], "simple": [(1, H)], "dot": [], "general2": [(H, Dm), (H,)], "concat": [(Da, H + Dm), (1, Da)]}[att]
+    U, spk, mval, prm, aprm, lprm = [], [], [], [], [], []
+    for z in range(ndir):
+        U.append((rnd(1.0, S, B, Dm) * valid.cuda().unsqueeze(2)).contiguous())
+        spk.append(torch.randint(0, P, (S, B), generator=gen).to(torch.int32).cuda())
+        mval.append(valid.cuda().contiguous())
+        aprm.append([rnd(0.6, *s) for s in att_shapes])
+        # the 13th cell tensor is general's transform.weight (the attention's own parameter); no other type has one
+        prm.append(cell(H, Dm + H) + cell(H, Dm + H) + cell(He, H)[:1] + cell(He, He)[1:] + [aprm[z][0] if att == "general" else None])
+        lprm.append(cell(H, Dm + H))
+    if not listener:
+        lprm = None
+    cfg = _lib.DrnnCfg(S, B, Dm, H, He, p, int(train))
+    acfg = _lib.DrnnAtt(_lib.DRNN_ATT_TYPES[att], Da)
+    n_saved, n_ws = ops.drnn_floats(cfg, acfg, listener, P)
+    n_e, n_al, n_u = S * B * He, B * S * S, S * B * Dm
+    rng = torch.tensor([SEED, 0], dtype=torch.int64, device="cuda")
+    A, att_ptrs = ops._ptr_array, lambda a, _: ops._att_ptrs(att, a)
+    front = lambda ts, n: A([t[:n] for t in ts])
+    structs = lambda cls, rows, fill=ops._drnn_ptrs: ops._ptr_structs(cls, rows, fill)
+    PRM, LP, AP = structs(_lib.DrnnPtrs, prm), structs(_lib.DrnnListenerPtrs, lprm), structs(_lib.DrnnAttPtrs, aprm, att_ptrs)
+
+    e, alpha = [guarded(n_e) for _ in range(ndir)], [guarded(n_al) for _ in range(ndir)]
+    saved, ws = [guarded(n_saved) for _ in range(ndir)], [guarded(n_ws) for _ in range(ndir)]
+    ops.drnn_fwd_raw(cfg, acfg, P, ndir, A(U), A(spk), A(mval), PRM, LP, AP, front(e, n_e), front(alpha, n_al), front(saved, n_saved),
+                     front(ws, n_ws), ops._ptr(rng), ADD)
+    named = lambda **k: {"%s[%d]" % (n, z): t for n, ts in k.items() for z, t in enumerate(ts)}
+    visit("fwd", named(e=e, alpha=alpha, saved=saved, ws=ws))
+    for z in range(ndir):
+        assert bool(torch.isfinite(e[z][:n_e]).all()), "e[%d]" % z
+
+    d_e = [rnd(1.0, S, B, He) for _ in range(ndir)]
+    dU, ws = [guarded(n_u) for _ in range(ndir)], [guarded(n_ws) for _ in range(ndir)]
+    guard_rows = lambda rows: [[None if t is None else guarded(t.numel(), 0.5) for t in r] for r in rows]
+    G, AG, LG = guard_rows(prm), guard_rows(aprm), guard_rows(lprm) if listener else None
+    for z in range(ndir):
+        if att == "general":              # one tensor under both names, as its parameter
+            AG[z][0] = G[z][12]
+    fronts = lambda g_rows, rows: [[None if g is None else g[:t.numel()] for g, t in zip(gr, r)] for gr, r in zip(g_rows, rows)]
+    ops.drnn_bwd_raw(cfg, acfg, P, ndir, A(d_e), A(U), A(spk), A(mval), PRM, LP, AP, structs(_lib.DrnnPtrs, fronts(G, prm)),
+                     structs(_lib.DrnnListenerPtrs, fronts(LG, lprm)) if listener else None,
+                     structs(_lib.DrnnAttPtrs, fronts(AG, aprm), att_ptrs), front(dU, n_u), front(alpha, n_al), front(saved, n_saved),
+                     front(ws, n_ws), ops._ptr(rng), ADD)
+    grads = {}
+    for name, rows, of in (("g", G, prm), ("ag", AG, aprm)) + ((("lg", LG, lprm),) if listener else ()):
+        grads.update({"%s[%d][%d]" % (name, z, j): (g, t.numel()) for z, (gr, r) in enumerate(zip(rows, of)) for j, (g, t) in enumerate(zip(gr, r))
+                      if g is not None})
+    visit("bwd", {**named(dU=dU, ws=ws, saved=saved, alpha=alpha), **{k: g for k, (g, _) in grads.items()}})
+    for z in range(ndir):
+        assert bool(torch.isfinite(dU[z][:n_u]).all()), "dU[%d]" % z
+    for k, (g, n) in grads.items():
+        assert bool(torch.isfinite(g[:n]).all()), k
     torch.cuda.synchronize()
 
 
