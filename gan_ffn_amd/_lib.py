@@ -165,6 +165,8 @@ SIGNATURES = {
     "ganffn_stream_attention_chunk": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ganffn_encoder_fwd_pair_len":(_I, [_PE, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, _P]),
     "ganffn_encoder_bwd_parts_len": (_I, [_PE, _P, _P, _P, _P, _P, _P, _P, _U64, _I, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int), _P]),
+    "ganffn_encoder_fwd_pair_mask": (_I, [_PE, _P, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _U64, _P]),
+    "ganffn_encoder_bwd_parts_mask": (_I, [_PE, _P, _U32, _P, _P, _P, _P, _P, _P, _U64, _I, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int), _P]),
     "ganffn_bce_len_fwd": (_I, [_P, _P, _I, _F, _F, _I, _I, _I, _F, _P, _I, _P]),
     "ganffn_bce_len_bwd": (_I, [_P, _P, _I, _F, _F, _I, _I, _I, _F, _P, _P]),
     "ganffn_add_dropout_layernorm_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _U32, _P, _U64, _P]),

@@ -219,7 +219,7 @@ def _device_epoch(engine, loader, train):
 
 def run_training(dataset_path, g_epochs=150, n_epochs=160, lr=1e-4, l2=0.008, batch_size=32, out_dir="./output/",
                  model_save_path="./GAN_save/", device="cuda", seed=None, log=print, device_corpus=False, mask_padding=False,
-                 mask_padding_gan=False, causal=False):
+                 mask_padding_gan=False, causal=False, causal_gan=False):
     """The reference's __main__ flow on the HIP path: GAN phase (lr 1e-4, betas (0.5, 0.6), batch 32 whatever
     `batch_size` says — train_IEMOCAP.py:595-607) -> GAN_loss.csv + six checkpoints -> GAN_FFN phase for `n_epochs`
     -> test_out_*.txt from the epoch with the best test loss.  Returns (report file, final F1, loss table).
@@ -231,8 +231,10 @@ def run_training(dataset_path, g_epochs=150, n_epochs=160, lr=1e-4, l2=0.008, ba
     only and their losses are means over real utterances (GanEngine `mask_padding`, from every batch's umask).
     causal (an extension, independent of both): in the classifier phase the generators' self-attention never looks ahead, in the
     module and in the engine alike (GAN_FFN / Phase2Engine `causal`), so the trained classifier labels utterance t from utterances
-    0 .. t.  It applies to the classifier phase only: the GAN phase still trains bidirectional generators, which phase 2 then
-    fine-tunes under the causal mask.  A causal GanEngine is the follow-up."""
+    0 .. t.  It applies to the classifier phase only and says nothing about the GAN phase.
+    causal_gan (an extension too, independent of causal, as mask_padding_gan is of mask_padding): the GAN phase trains its three
+    generators under the causal mask (GanEngine `causal`; the discriminators stay bidirectional), so that phase 2 with causal
+    fine-tunes generators that were pre-trained in the regime they will run in, not bidirectional ones."""
     from . import data as D, engine as E, model as M
     gens, discs = E.build_networks(100, 0.2, device, seed)
     if device_corpus:
@@ -242,7 +244,8 @@ def run_training(dataset_path, g_epochs=150, n_epochs=160, lr=1e-4, l2=0.008, ba
     else:
         loaders = lambda bs: D.get_IEMOCAP_loaders(dataset_path, batch_size=bs, valid=0.1)
         batches = _DeviceBatches(loaders(32)[0], device)
-    rows = E.train_GAN(gens, discs, batches, epochs=g_epochs, lr=1e-4, b1=0.5, b2=0.6, reserve_S=110, mask_padding=mask_padding_gan)
+    rows = E.train_GAN(gens, discs, batches, epochs=g_epochs, lr=1e-4, b1=0.5, b2=0.6, reserve_S=110, mask_padding=mask_padding_gan,
+                       causal=causal_gan)
     df = loss_table(rows)
     save_GAN_loss(df, os.path.join(out_dir, "GAN_loss.csv"))
     if not os.path.exists(model_save_path):

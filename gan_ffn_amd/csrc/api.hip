@@ -259,7 +259,7 @@ static inline EncCall enc_call(const ganffn_enc_cfg* c, const int32_t* key_len, 
 // gemm_n100) is evaluated for T = S B, one segment's rows, so a segment has the bits of a pass of its own.
 // key_len (or null): per-dialogue key lengths of the attention core, the one place of a layer where rows of a dialogue meet;
 // both segments are the same B dialogues, so one [B] array serves both
-// flags: GANFFN_ATTN_* bits for the same place (0 = none); the causal kernels have no two-segment form
+// flags: GANFFN_ATTN_* bits for the same place (0 = none), for both segments alike
 // sa (or null): the pass is a streaming step (ganffn_encoder_stream_step) — c is S = 1, B = n, eval; the positional encoding is
 // the gather by per-dialogue position followed by layer 0's in-proj GEMM, and the attention core is the single-query step over
 // layer l's K/V cache (stream.hip).  Every other launch is the one a pass over T = n rows issues; null changes no call.
@@ -269,7 +269,6 @@ static int encoder_fwd_walk(const EncCall& k, const Mode md, const FwdSeg& s0, c
     const ganffn_enc_cfg* c = k.c; const int32_t* key_len = k.key_len; const uint32_t flags = k.flags;
     const float* pe = k.pe; const float* x_in = k.x_in; const float* params = k.params;
     const uint64_t* rng = k.rng; const uint64_t add = k.add; hipStream_t st = k.st;
-    GF_CHECK_ARG(!s1 || flags == 0, "encoder_fwd_pair: flags 0x%x have no two-segment form", flags);
     GF_CHECK_ARG(!sa || (!s1 && !key_len && flags == 0 && !s0.train), "encoder_stream_step: one eval segment, no lengths, no flags");
     const int S = c->S, B = c->B, E = c->E, H = c->H, F = c->F, L = c->L, T = S * B;
     const int64_t TE = (int64_t)T * E;
@@ -553,6 +552,14 @@ extern "C" int ganffn_encoder_fwd_pair_len(const ganffn_enc_cfg* c, const int32_
                                            float* workspace, const uint64_t* rng, uint64_t add_train, void* stream) {
     return encoder_fwd_pair(enc_call(c, key_len, 0, rng, add_train, stream).forward(x_in, pe, params, out_eval, saved_train, workspace).pair(out_train));
 }
+// the same with a flags word: GANFFN_ATTN_CAUSAL puts BOTH segments under the causal mask (0 = the call above; an unknown bit is
+// refused by check_pass before any launch)
+extern "C" int ganffn_encoder_fwd_pair_mask(const ganffn_enc_cfg* c, const int32_t* key_len, uint32_t flags, const float* x_in,
+                                            const float* pe, const float* params, float* out_eval, float* out_train,
+                                            float* saved_train, float* workspace, const uint64_t* rng, uint64_t add_train,
+                                            void* stream) {
+    return encoder_fwd_pair(enc_call(c, key_len, flags, rng, add_train, stream).forward(x_in, pe, params, out_eval, saved_train, workspace).pair(out_train));
+}
 
 // ------------------------------------------------------------------------------------------
 // encoder stack backward over layers [lo_l, hi_l)
@@ -718,20 +725,27 @@ extern "C" int ganffn_encoder_bwd_parts_supported(const ganffn_enc_cfg* c) {
     return bwd_parts_supported(c, mode()) ? 1 : 0;
 }
 extern "C" int64_t ganffn_encoder_bwd_parts_covered(int E, int F) { return layer_off(E, F).n1w; }
-extern "C" int ganffn_encoder_bwd_parts_len(const ganffn_enc_cfg* c, const int32_t* key_len, float* dx, const float* params,
-                                            float* grads, const float* saved, float* workspace, const uint64_t* rng, uint64_t add,
-                                            int need_dx_in, int64_t* part_offset, int64_t* part_stride, int* n_parts, void* stream) {
+extern "C" int ganffn_encoder_bwd_parts_mask(const ganffn_enc_cfg* c, const int32_t* key_len, uint32_t flags, float* dx,
+                                             const float* params, float* grads, const float* saved, float* workspace,
+                                             const uint64_t* rng, uint64_t add, int need_dx_in, int64_t* part_offset,
+                                             int64_t* part_stride, int* n_parts, void* stream) {
     GF_TRY(check_cfg(c));
     GF_CHECK_ARG(grads && part_offset && part_stride && n_parts, "encoder_bwd_parts: null pointer");
     GF_CHECK_ARG(bwd_parts_supported(c, mode()), "encoder_bwd_parts: this stack's weight gradients are reduced in the launch (ask ganffn_encoder_bwd_parts_supported)");
     TnSlabs sl{grads, (long)c->L * layer_off(c->E, c->F).total, 1, nullptr, 0};
-    EncCall k = enc_call(c, key_len, 0, rng, add, stream).backward(0, c->L, dx, params, grads, saved, workspace, need_dx_in);
+    EncCall k = enc_call(c, key_len, flags, rng, add, stream).backward(0, c->L, dx, params, grads, saved, workspace, need_dx_in);
     k.slabs = &sl;
     GF_TRY(encoder_bwd(k));
     *n_parts = sl.n_parts;
     *part_offset = sl.part ? sl.part - workspace : 0;
     *part_stride = sl.part_stride;
     return 0;
+}
+extern "C" int ganffn_encoder_bwd_parts_len(const ganffn_enc_cfg* c, const int32_t* key_len, float* dx, const float* params,
+                                            float* grads, const float* saved, float* workspace, const uint64_t* rng, uint64_t add,
+                                            int need_dx_in, int64_t* part_offset, int64_t* part_stride, int* n_parts, void* stream) {
+    return ganffn_encoder_bwd_parts_mask(c, key_len, 0, dx, params, grads, saved, workspace, rng, add, need_dx_in, part_offset,
+                                         part_stride, n_parts, stream);
 }
 extern "C" int ganffn_encoder_bwd_parts(const ganffn_enc_cfg* c, float* dx, const float* params, float* grads, const float* saved,
                                         float* workspace, const uint64_t* rng, uint64_t add, int need_dx_in, int64_t* part_offset,

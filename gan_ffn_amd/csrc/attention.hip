@@ -320,7 +320,8 @@ __device__ __forceinline__ bool kept(const unsigned long long (&mq)[4], int c, i
 // to the batch, so key_len[b] serves both) — a template flag, so that the
 // instantiations without lengths keep the instructions they had (see attention16.hip)
 // CAUSAL (only with LEN; a null key_len reads as S): the lane's key limit in the softmax is min(n, query + 1).  At most 4 key
-// tiles here, so the mask is all: no tile is skipped.
+// tiles here, so the mask is all: no tile is skipped.  PAIR && CAUSAL: the segment choice first, then the same kernel — both
+// segments of a generator's two-segment pass under the mask, each with the bits of its own causal launch.
 template <int HD, int NT, bool PAIR = false, bool LEN = false, bool CAUSAL = false>
 __global__ __launch_bounds__(64 * NT) void attention_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ o, AttnGeom g,
                                                                 float p, uint32_t site, const uint64_t* __restrict__ rng,
@@ -582,7 +583,11 @@ static int check_attn(int S, int B, int E, int H) {
 template <int HD, int NT>
 static int launch_fwd_t(const float* qkv, float* o, const AttnGeom& g, size_t lds, float p, uint32_t site, const uint64_t* rng,
                         uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1, const int32_t* key_len, bool causal) {
-    if (causal) {      // never with seg1 (refused by the caller); a null key_len reads as S in the kernel
+    if (causal && seg1) {      // both segments under the mask; a null key_len reads as S in the kernel
+        GF_TRY((lds_optin<attention_fwd_kernel<HD, NT, true, true, true>>(lds, "attention_fwd")));
+        hipLaunchKernelGGL((attention_fwd_kernel<HD, NT, true, true, true>), dim3(2 * g.B * g.H), dim3(64 * NT), lds, st, qkv, o, g, p,
+                           site, rng, add, train, seg1->qkv, seg1->o, seg1->train, key_len);
+    } else if (causal) {
         GF_TRY((lds_optin<attention_fwd_kernel<HD, NT, false, true, true>>(lds, "attention_fwd")));
         hipLaunchKernelGGL((attention_fwd_kernel<HD, NT, false, true, true>), dim3(g.B * g.H), dim3(64 * NT), lds, st, qkv, o, g, p, site,
                            rng, add, train, (const float*)nullptr, (float*)nullptr, 0, key_len);
@@ -640,7 +645,6 @@ int launch_attention_fwd(const float* qkv, float* o, float* lse, uint32_t* keep,
     GF_TRY(check_attn(S, B, E, H));
     GF_CHECK_ARG((flags & ~GANFFN_ATTN_CAUSAL) == 0, "attention_fwd: unknown flag bits 0x%x", flags & ~GANFFN_ATTN_CAUSAL);
     const bool causal = (flags & GANFFN_ATTN_CAUSAL) != 0;
-    GF_CHECK_ARG(!(seg1 && causal), "attention_fwd: the two-batch launch has no causal form");
     GF_CHECK_ARG(qkv && o, "attention_fwd: null pointer");
     GF_CHECK_ARG(!seg1 || (seg1->qkv && seg1->o), "attention_fwd: bad second batch");
     GF_CHECK_ARG(!((train || (seg1 && seg1->train)) && p > 0.f) || rng, "attention_fwd: rng required when dropout is active");

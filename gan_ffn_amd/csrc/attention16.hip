@@ -216,6 +216,10 @@ struct Attn16Seg1 {
 // CAUSAL (only with LEN; a null key_len reads as S): query i attends to keys j <= i, i.e. the lane's key limit is
 // min(n, query + 1).  Wave w owns query tile w, so key tiles t > w are dead: the wave runs the tail of the kernel compiled for
 // w + 1 key tiles (tile_dispatch) — no score MFMAs, exp / sum work or P V products for the rest, and no Philox calls.
+// PAIR && CAUSAL (both segments of a generator's two-segment pass under the mask): the segment choice comes first and changes
+// pointers and the train flag only, so everything after it is the single-batch causal kernel — w through readfirstlane, the
+// dispatch over key tiles 0 .. w in both segments, dead tiles skipped in the keep-bit loop, keep words stored by the train
+// segment alone (dc.on) — and each segment has the bits of its own causal launch.
 template <int HD, int NT, int WPB, bool PAIR = false, bool LEN = false, bool CAUSAL = false>
 __global__ __launch_bounds__(64 * WPB) void attn16_fwd_kernel(const float* __restrict__ qkv, float* __restrict__ o,
                                                              float* __restrict__ lse, uint32_t* __restrict__ keepw, int S, int B,
@@ -765,17 +769,21 @@ static int launch16_fwd(const float* qkv, float* o, float* lse, uint32_t* keepw,
                         const int32_t* key_len) {
     const size_t lds = fwd_lds<HD>(NT);
     if (!attn16_use_keep(B, H)) keepw = nullptr;
-#ifndef GANFFN_A16_CAUSAL_TU
     if (seg1) {
         // the workgroup cut and the keep-word rule are those of ONE batch of B dialogues: what a single launch would choose
         Attn16Seg1 s1{seg1->qkv, seg1->o, seg1->lse, attn16_use_keep(B, H) ? seg1->keep : nullptr, seg1->train};
-#define GF_A16_FWD2(W, LEN)                                                                                         \
+#define GF_A16_FWD2(W, LEN, ...)                                                                                    \
     {                                                                                                               \
-        GF_TRY((lds_optin<attn16_fwd_kernel<HD, NT, W, true, LEN>>(lds, "attention_fwd")));                         \
-        hipLaunchKernelGGL((attn16_fwd_kernel<HD, NT, W, true, LEN>), dim3(2 * B * H * (NT / W)), dim3(64 * W), lds, st, qkv, o, lse, keepw, \
+        GF_TRY((lds_optin<attn16_fwd_kernel<HD, NT, W, true, LEN, ##__VA_ARGS__>>(lds, "attention_fwd")));          \
+        hipLaunchKernelGGL((attn16_fwd_kernel<HD, NT, W, true, LEN, ##__VA_ARGS__>), dim3(2 * B * H * (NT / W)), dim3(64 * W), lds, st, qkv, o, lse, keepw, \
                            S, B, E, H, p, site, rng, add, train, s1, B * H * (NT / W), key_len);                     \
     }
         const bool cut2 = (long)B * H < 512 && NT % 2 == 0 && NT > 2;
+#ifdef GANFFN_A16_CAUSAL_TU
+        // both segments causal: after the segment choice the kernel is the single-batch causal one (a null key_len reads as S)
+        if (cut2) GF_A16_FWD2((NT % 2 == 0 ? 2 : NT), true, true)
+        else GF_A16_FWD2(NT, true, true)
+#else
         if (key_len) {
             if (cut2) GF_A16_FWD2((NT % 2 == 0 ? 2 : NT), true)
             else GF_A16_FWD2(NT, true)
@@ -783,11 +791,11 @@ static int launch16_fwd(const float* qkv, float* o, float* lse, uint32_t* keepw,
             if (cut2) GF_A16_FWD2((NT % 2 == 0 ? 2 : NT), false)
             else GF_A16_FWD2(NT, false)
         }
+#endif
 #undef GF_A16_FWD2
         GF_LAUNCH_CHECK();
         return 0;
     }
-#endif
     // query tiles per workgroup: measured at hd = 10, S = 94 (tools/lab/attn_wpb.py, lab build): 320 problems 11.1 us as
     // whole workgroups, 10.1 / 9.9 / 11.5 us cut in 2 / 3 / 6; 640 problems 15.0 us whole, 16.4 / 17.9 / 21.5 us cut —
     // the cut pays while the problems do not fill the chip, then the repeated K / V staging costs more than the balance gains
@@ -866,7 +874,6 @@ int A16_ENTRY(launch_attn16_fwd)(const float* qkv, float* o, float* lse, uint32_
                       const int32_t* key_len, uint32_t flags) {
     const bool causal = (flags & GANFFN_ATTN_CAUSAL) != 0;
     GF_CHECK_ARG(!seg1 || (seg1->qkv && seg1->o), "attn16_fwd: bad second batch");
-    GF_CHECK_ARG(!(seg1 && causal), "attn16_fwd: the two-batch launch has no causal form");
     GF_CHECK_ARG(attn16_supported(E, H, S) && S >= 1 && S <= GANFFN_MAX_SEQ, "attn16_fwd: unsupported E=%d H=%d S=%d", E, H, S);
     GF_CHECK_ARG((long)B * H * 28 * 128 < (1l << 32), "attention: B*H too large for the Philox counter");
 #ifndef GANFFN_A16_CAUSAL_TU

@@ -388,8 +388,12 @@ class _NetRunner(_Runner):
     # outlives the backward that reads it.  GanEngine, whose passes have two batch widths, overrides _pass_key_len instead.
     _key_len = None
     # causal self-attention in every encoder call of _net_fwd / _net_bwd (Phase2Engine(causal=True)); False: the calls without it.
-    # GanEngine has no causal form yet (its paired forward and parts backward have none in the library) and leaves this False.
+    # GanEngine, whose discriminators stay bidirectional, chooses per network instead: it overrides _net_causal.
     _causal = False
+
+    def _net_causal(self, net):
+        """do the encoder calls on this network carry the causal flag?"""
+        return self._causal
 
     def _pass_key_len(self, ps):
         """the key lengths of a forward / backward on the pass buffers ps (None: the plain encoder calls)"""
@@ -417,7 +421,7 @@ class _NetRunner(_Runner):
         else:
             a0, a1 = self._base_add + adds[0], self._base_add + adds[1]
         ops.encoder_fwd_raw(cfg, x, net.pe, net.slab, ps.enc_out, ps.saved if save else None, self.ws, self.rng.state, a0,
-                            key_len=self._pass_key_len(ps), causal=self._causal)
+                            key_len=self._pass_key_len(ps), causal=self._net_causal(net))
         w = net.w
         w3 = w("fc3.weight") if net.kind == 1 else None
         b3 = w("fc3.bias") if net.kind == 1 else None
@@ -444,16 +448,14 @@ class _NetRunner(_Runner):
         # train_gen passes its input gradient on to the generator
         if need_dx is None:
             need_dx = not want_wgrad
-        if parts and self._causal:
-            raise NotImplementedError("the parts backward has no causal form")
         if parts and want_wgrad and reduce_cb is None:
             # single GPU, d_model 100: the weight gradients stay as token-chunk slabs for Adam to add (no reduce launch, and the
             # caller did not zero the encoder region of net.grad) -> (parts view of self.ws, stride, chunks)
             return ops.encoder_bwd_parts_raw(cfg, ps.dx, net.slab, gslab, ps.saved, self.ws, self.rng.state, a0, need_dx,
-                                             key_len=self._pass_key_len(ps))
+                                             key_len=self._pass_key_len(ps), causal=self._net_causal(net))
         if reduce_cb is None or not want_wgrad:
             ops.encoder_bwd_raw(cfg, 0, net.L, ps.dx, net.slab, gslab, ps.saved, self.ws, self.rng.state, a0, need_dx,
-                                key_len=self._pass_key_len(ps), causal=self._causal)
+                                key_len=self._pass_key_len(ps), causal=self._net_causal(net))
         else:
             # bucketed: backward a group of layers, then hand that slice of the grad slab to the all-reduce
             bks = net.buckets(self.n_buckets)
@@ -461,7 +463,7 @@ class _NetRunner(_Runner):
             for i, (lo_f, hi_f) in enumerate(bks[1:]):
                 lo, hi = lo_f // net.layer_floats, hi_f // net.layer_floats
                 ops.encoder_bwd_raw(cfg, lo, hi, ps.dx, net.slab, gslab, ps.saved, self.ws, self.rng.state, a0, need_dx,
-                                    key_len=self._pass_key_len(ps), causal=self._causal)
+                                    key_len=self._pass_key_len(ps), causal=self._net_causal(net))
                 reduce_cb(lo_f, hi_f, last=(i == len(bks) - 2))
 
     def _adam(self, net, parts=None):
@@ -597,11 +599,21 @@ class GanEngine(_NetRunner):
     loss, gradient or updated parameter.  Under a process group each rank divides by its OWN count of real utterances: the
     all-reduced gradient is the mean of the ranks' masked means (as the reference's is the mean of their padded means), not the
     mean over all ranks' utterances.  GANFFN_CHECK_QMASK=1 checks that umask rows are prefixes (one host sync per batch).  Off,
-    the engine issues exactly the calls it issued before the option existed."""
+    the engine issues exactly the calls it issued before the option existed.
+
+    causal (default False: the reference's generators are bidirectional) is an extension too: every GENERATOR pass of every
+    sub-step — the eval-mode forward of a discriminator sub-step, the train-mode forward and backward of a generator sub-step,
+    both segments of a paired forward — runs under the causal mask (query i attends to keys j <= i; with mask_padding
+    j < min(len, i + 1)), so the generators are trained in the regime a streaming classifier runs them in.  The DISCRIMINATORS
+    stay bidirectional: they are training-time critics of whole fused sequences and are never deployed, so every discriminator
+    launch is the one issued without the option.  Dropout offsets, the Philox indexing, the stream map, the pairing rule and the
+    parts rule are unchanged; it composes with mask_padding, graph capture, several streams and a process group.  Off, the
+    engine issues exactly the calls it issued before the option existed."""
 
     def __init__(self, gens, discs, lr=1e-4, b1=0.5, b2=0.6, process_group=None, n_buckets=3, use_graph=False,
-                 n_streams=1, schedule=None, mask_padding=False):
+                 n_streams=1, schedule=None, mask_padding=False, causal=False):
         self.mask_padding = bool(mask_padding)
+        self.causal = bool(causal)
         self._kl1 = self._kl2 = None         # int32 key lengths of the iteration being issued: [B], and [2B] = the same twice
         # optimizers: train_IEMOCAP.py:292-297 (G lr, text-G 1.1*lr, every D lr/2); call site :603-606
         self.G = {k: NetState(m, lr * (1.1 if k == "text" else 1.0), (b1, b2)) for k, m in gens.items()}
@@ -669,6 +681,9 @@ class GanEngine(_NetRunner):
 
     def _communicators(self):
         return self.pgs
+
+    def _net_causal(self, net):
+        return self.causal and net.kind == 0         # the generators; a discriminator (kind 1) judges the whole sequence
 
     def _pass_key_len(self, ps):
         if self._kl1 is None:
@@ -785,7 +800,7 @@ class GanEngine(_NetRunner):
         generator over x: one two-segment encoder pass, then the two heads; -> the train pass's (enc_add, head_add)"""
         a0, a1 = self._base_add + adds_train[0], self._base_add + adds_train[1]
         ops.encoder_fwd_pair_raw(ps_train.cfg_train, x, net.pe, net.slab, ps_eval.enc_out, ps_train.enc_out, ps_train.saved,
-                                 self.ws, self.rng.state, a0, key_len=self._pass_key_len(ps_train))
+                                 self.ws, self.rng.state, a0, key_len=self._pass_key_len(ps_train), causal=self._net_causal(net))
         w = net.w
         w3 = w("fc3.weight") if net.kind == 1 else None
         b3 = w("fc3.bias") if net.kind == 1 else None
@@ -1045,14 +1060,16 @@ def build_networks(D_h=100, dropout=0.2, device="cuda", seed=None):
 
 
 def train_GAN(gens, discs, batches, epochs=1, lr=1e-4, b1=0.5, b2=0.6, process_group=None, use_graph=False, log=None,
-              n_streams=3, reserve_S=None, mask_padding=False):
+              n_streams=3, reserve_S=None, mask_padding=False, causal=False):
     """Counterpart of train_GAN (train_IEMOCAP.py:255-393) over an iterable of batches per epoch.
     Returns rows of the GAN_loss table (columns train_IEMOCAP.py:308-316): last batch of each epoch.
     reserve_S: size the step buffers once for dialogues up to this length (PositionalEncoding allows 110), so that
     batches of varying length never re-allocate.
     The losses are read on the host per batch only when `log` wants them; otherwise once per epoch (the last batch's).
-    mask_padding: every batch carries "umask" [B, S]; attention and losses ignore padded utterances (GanEngine)."""
-    eng = GanEngine(gens, discs, lr, b1, b2, process_group, use_graph=use_graph, n_streams=n_streams, mask_padding=mask_padding)
+    mask_padding: every batch carries "umask" [B, S]; attention and losses ignore padded utterances (GanEngine).
+    causal: the generators' self-attention never looks ahead; the discriminators stay bidirectional (GanEngine)."""
+    eng = GanEngine(gens, discs, lr, b1, b2, process_group, use_graph=use_graph, n_streams=n_streams, mask_padding=mask_padding,
+                    causal=causal)
     rows = []
     for epoch in range(epochs):
         last = kept = None

@@ -236,14 +236,15 @@ def encoder_fwd_pair_workspace_floats(cfg):
     return w
 
 
-def encoder_fwd_pair_raw(cfg, x, pe, slab, out_eval, out_train, saved_train, ws, rng, add_train, key_len=None):
+def encoder_fwd_pair_raw(cfg, x, pe, slab, out_eval, out_train, saved_train, ws, rng, add_train, key_len=None, causal=False):
     """cfg: the train-mode cfg.  out_eval = the eval-mode forward of x (nothing kept), out_train / saved_train = the
-    train-mode forward with its saved set — one pass, the bits of the two encoder_fwd_raw calls (ganffn_encoder_fwd_pair_len).
-    key_len (int32 device tensor [B], or None for a null pointer): the lengths of the B dialogues, for both segments."""
+    train-mode forward with its saved set — one pass, the bits of the two encoder_fwd_raw calls (ganffn_encoder_fwd_pair_mask).
+    key_len (int32 device tensor [B], or None for a null pointer): the lengths of the B dialogues, for both segments.
+    causal=True (the GANFFN_ATTN_CAUSAL flag): both segments under the causal mask, as encoder_fwd_raw(causal=True) twice."""
     if key_len is not None:
         _check_key_len(key_len, cfg)
-    _lib.call("ganffn_encoder_fwd_pair_len", C.byref(cfg), _ptr(key_len), _ptr(x), _ptr(pe), _ptr(slab), _ptr(out_eval),
-              _ptr(out_train), _ptr(saved_train), _ptr(ws), _ptr(rng), C.c_uint64(add_train), _stream())
+    _lib.call("ganffn_encoder_fwd_pair_mask", C.byref(cfg), _ptr(key_len), C.c_uint32(ATTN_CAUSAL if causal else 0), _ptr(x), _ptr(pe),
+              _ptr(slab), _ptr(out_eval), _ptr(out_train), _ptr(saved_train), _ptr(ws), _ptr(rng), C.c_uint64(add_train), _stream())
 
 
 def encoder_bwd_raw(cfg, lo, hi, dx, slab, gslab, saved, ws, rng, add, need_dx_in=True, key_len=None, causal=False):
@@ -261,15 +262,16 @@ def encoder_bwd_parts_supported(cfg):
     return int(_lib.load().ganffn_encoder_bwd_parts_supported(C.byref(cfg))) == 1
 
 
-def encoder_bwd_parts_raw(cfg, dx, slab, gslab, saved, ws, rng, add, need_dx_in=True, key_len=None):
+def encoder_bwd_parts_raw(cfg, dx, slab, gslab, saved, ws, rng, add, need_dx_in=True, key_len=None, causal=False):
     """whole-stack backward with unreduced weight gradients -> (parts tensor view into ws or None, part_stride, n_parts, offset
-    of the parts in ws): hand them to adam_step_parts_raw before anything else touches ws[offset:].  key_len: the lengths the
-    forward was given, None for a null pointer (ganffn_encoder_bwd_parts_len)."""
+    of the parts in ws): hand them to adam_step_parts_raw before anything else touches ws[offset:].  key_len, causal: what the
+    forward was given (ganffn_encoder_bwd_parts_mask: a null pointer for None, the GANFFN_ATTN_CAUSAL flag for causal)."""
     off, stride, n = C.c_int64(0), C.c_int64(0), C.c_int(0)
     if key_len is not None:
         _check_key_len(key_len, cfg)
-    _lib.call("ganffn_encoder_bwd_parts_len", C.byref(cfg), _ptr(key_len), _ptr(dx), _ptr(slab), _ptr(gslab), _ptr(saved), _ptr(ws),
-              _ptr(rng), C.c_uint64(add), 1 if need_dx_in else 0, C.byref(off), C.byref(stride), C.byref(n), _stream())
+    _lib.call("ganffn_encoder_bwd_parts_mask", C.byref(cfg), _ptr(key_len), C.c_uint32(ATTN_CAUSAL if causal else 0), _ptr(dx), _ptr(slab),
+              _ptr(gslab), _ptr(saved), _ptr(ws), _ptr(rng), C.c_uint64(add), 1 if need_dx_in else 0, C.byref(off), C.byref(stride),
+              C.byref(n), _stream())
     return (ws[off.value:] if n.value > 1 else None), stride.value, n.value, off.value
 
 

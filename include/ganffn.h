@@ -579,8 +579,21 @@ int ganffn_encoder_bwd_len(const ganffn_enc_cfg* cfg, const int32_t* key_len, in
  * flags == 0 is exactly the _len call (same launches, same bits); key_len may be NULL with any flags; a bit other than
  * GANFFN_ATTN_CAUSAL is refused with a message and nothing is written.  Saved and workspace sizes and layouts are unchanged.  The
  * forward and the backward of one pass must be given the same flags (and lengths).  The causal kernels are instantiations of
- * their own; in the head_dim 10 / 30 family (and 60 / 64 at S <= 48) they also skip the key tiles above the diagonal. */
+ * their own; in the head_dim 10 / 30 family (and 60 / 64 at S <= 48) they also skip the key tiles above the diagonal.
+ * The GAN step's forms (GanEngine(causal = True): generators under the mask, discriminators not):
+ * ganffn_encoder_fwd_pair_mask: ganffn_encoder_fwd_pair_len with the flags word; GANFFN_ATTN_CAUSAL masks BOTH segments.  The eval
+ * output has the bits of ganffn_encoder_fwd_mask(..., saved = NULL), the train output and the saved block those of
+ * ganffn_encoder_fwd_mask with the same rng_offset_add and flags.
+ * ganffn_encoder_bwd_parts_mask: ganffn_encoder_bwd_parts_len with the flags handed on; followed by ganffn_adam_step_parts the
+ * update has the bits of ganffn_encoder_bwd_mask + ganffn_adam_step. */
 #define GANFFN_ATTN_CAUSAL 1u
+int ganffn_encoder_fwd_pair_mask(const ganffn_enc_cfg* cfg, const int32_t* key_len, uint32_t flags, const float* x_in,
+                                 const float* pe, const float* params, float* out_eval, float* out_train, float* saved_train,
+                                 float* workspace, const uint64_t* rng, uint64_t rng_offset_add_train, void* stream);
+int ganffn_encoder_bwd_parts_mask(const ganffn_enc_cfg* cfg, const int32_t* key_len, uint32_t flags, float* dx,
+                                  const float* params, float* grads, const float* saved, float* workspace, const uint64_t* rng,
+                                  uint64_t rng_offset_add, int need_dx_in, int64_t* part_offset, int64_t* part_stride,
+                                  int* n_parts, void* stream);
 int ganffn_attention_fwd_mask(const float* qkv, float* o, float* lse, uint32_t* keep, const int32_t* key_len, uint32_t flags,
                               int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng,
                               uint64_t rng_offset_add, void* stream);
