@@ -9,6 +9,12 @@
 // s is bounded by tanh, so no max-subtraction is needed; a dialogue with no valid step yields 0/0 = NaN as the
 // reference does.  Fallback kernels (dialogue too large for the LDS): one workgroup per (query step, dialogue); S <= 128, D <= 1024 (D = 2 D_e = 200 in config 5, 600 in the MELD classifier).
 // HBM-bound: M[b] (S x D floats) is re-read by the S workgroups of a dialogue out of L2.
+//
+// CAUSAL (GANFFN_ATTN_CAUSAL through the _mask entry points; a template flag, instantiations of their own): query step t sees
+// memory steps j <= t only, a_tj = e^{s_tj} m_j [j <= t] / sum_{k <= t} e^{s_tk} m_k — MatchingAttention.forward(M[:t+1], M[t],
+// umask[:, :t+1]) for every t.  The causal kernels skip the work above the diagonal (a query block stages, scores and combines
+// memory rows j < min(S, t0 + 16) only; memory step j sums over t >= j only) and still write alpha, tanh_s and du completely:
+// exact zeros above the diagonal.  The non-causal instantiations are the code they were.
 #include "common.h"
 
 namespace ganffn {
@@ -16,6 +22,7 @@ namespace ganffn {
 constexpr int G2_MAXS = 128;
 constexpr int G2_MAXD = 1024;
 
+template <bool CAUSAL>
 __global__ __launch_bounds__(256) void general2_fwd_kernel(const float* __restrict__ x, const float* __restrict__ mem,
                                                            const float* __restrict__ mask, float* __restrict__ att,
                                                            float* __restrict__ alpha, float* __restrict__ tanh_s, int S,
@@ -25,10 +32,11 @@ __global__ __launch_bounds__(256) void general2_fwd_kernel(const float* __restri
     __shared__ float red[4];
     const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const size_t row = (size_t)B * D;                     // stride between time steps
+    const int Sk = CAUSAL ? t + 1 : S;                    // memory steps this query sees
     for (int d = tid; d < D; d += 256) xs[d] = x[(size_t)t * row + (size_t)b * D + d];
     __syncthreads();
     float part = 0.f;                                     // this wave's share of sum_k e^{s_k} m_k
-    for (int j = w; j < S; j += 4) {
+    for (int j = w; j < Sk; j += 4) {
         const float* mj = mem + (size_t)j * row + (size_t)b * D;
         float dot = 0.f;
         for (int d = lane; d < D; d += 64) dot += xs[d] * mj[d];
@@ -45,21 +53,27 @@ __global__ __launch_bounds__(256) void general2_fwd_kernel(const float* __restri
     if (lane == 0) red[w] = part;
     __syncthreads();
     const float inv = 1.0f / (red[0] + red[1] + red[2] + red[3]);
-    for (int j = tid; j < S; j += 256) {
+    for (int j = tid; j < Sk; j += 256) {
         const float a = a_s[j] * inv;
         a_s[j] = a;
         alpha[((size_t)b * S + t) * S + j] = a;
     }
+    if (CAUSAL)
+        for (int j = Sk + tid; j < S; j += 256) {         // above the diagonal: written, with zeros
+            alpha[((size_t)b * S + t) * S + j] = 0.f;
+            tanh_s[((size_t)b * S + t) * S + j] = 0.f;
+        }
     __syncthreads();
     for (int d = tid; d < D; d += 256) {
         float acc = 0.f;
-        for (int j = 0; j < S; ++j) acc += a_s[j] * mem[(size_t)j * row + (size_t)b * D + d];
+        for (int j = 0; j < Sk; ++j) acc += a_s[j] * mem[(size_t)j * row + (size_t)b * D + d];
         att[(size_t)t * row + (size_t)b * D + d] = acc;
     }
 }
 
 // per (query step, dialogue): du_j = a_j (da_j - sum_k a_k da_k) (1 - s_j^2) m_j^2 with da_j = <d_att_t, M_j>;
 // dx_t = sum_j du_j M_j.  du is kept for the memory-gradient kernel.
+template <bool CAUSAL>
 __global__ __launch_bounds__(256) void general2_bwd_q_kernel(const float* __restrict__ d_att, const float* __restrict__ mem,
                                                              const float* __restrict__ mask, const float* __restrict__ alpha,
                                                              const float* __restrict__ tanh_s, float* __restrict__ du,
@@ -70,10 +84,11 @@ __global__ __launch_bounds__(256) void general2_bwd_q_kernel(const float* __rest
     const int t = blockIdx.x, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const size_t row = (size_t)B * D;
     const size_t arow = ((size_t)b * S + t) * S;
+    const int Sk = CAUSAL ? t + 1 : S;
     for (int d = tid; d < D; d += 256) gs[d] = d_att[(size_t)t * row + (size_t)b * D + d];
     __syncthreads();
     float part = 0.f;
-    for (int j = w; j < S; j += 4) {
+    for (int j = w; j < Sk; j += 4) {
         const float* mj = mem + (size_t)j * row + (size_t)b * D;
         float dot = 0.f;
         for (int d = lane; d < D; d += 64) dot += gs[d] * mj[d];
@@ -84,21 +99,24 @@ __global__ __launch_bounds__(256) void general2_bwd_q_kernel(const float* __rest
     if (lane == 0) red[w] = part;
     __syncthreads();
     const float dsum = red[0] + red[1] + red[2] + red[3];
-    for (int j = tid; j < S; j += 256) {
+    for (int j = tid; j < Sk; j += 256) {
         const float a = alpha[arow + j], s = tanh_s[arow + j], m = mask[(size_t)b * S + j];
         const float v = a * (da_s[j] - dsum) * (1.0f - s * s) * (m * m);
         da_s[j] = v;
         du[arow + j] = v;
     }
+    if (CAUSAL)
+        for (int j = Sk + tid; j < S; j += 256) du[arow + j] = 0.f;
     __syncthreads();
     for (int d = tid; d < D; d += 256) {
         float acc = 0.f;
-        for (int j = 0; j < S; ++j) acc += da_s[j] * mem[(size_t)j * row + (size_t)b * D + d];
+        for (int j = 0; j < Sk; ++j) acc += da_s[j] * mem[(size_t)j * row + (size_t)b * D + d];
         dx[(size_t)t * row + (size_t)b * D + d] = acc;
     }
 }
 
-// per (memory step j, dialogue): dM_j = sum_t ( a_tj d_att_t + du_tj x_t )   — no atomics, fixed order
+// per (memory step j, dialogue): dM_j = sum_t ( a_tj d_att_t + du_tj x_t )   — no atomics, fixed order (causal: t >= j)
+template <bool CAUSAL>
 __global__ __launch_bounds__(256) void general2_bwd_m_kernel(const float* __restrict__ d_att, const float* __restrict__ x,
                                                              const float* __restrict__ alpha, const float* __restrict__ du,
                                                              float* __restrict__ dmem, int S, int B, int D) {
@@ -106,14 +124,15 @@ __global__ __launch_bounds__(256) void general2_bwd_m_kernel(const float* __rest
     __shared__ float u_s[G2_MAXS];
     const int j = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
     const size_t row = (size_t)B * D;
-    for (int t = tid; t < S; t += 256) {
+    const int tlo = CAUSAL ? j : 0;                       // first query step that sees memory step j
+    for (int t = tlo + tid; t < S; t += 256) {
         a_s[t] = alpha[((size_t)b * S + t) * S + j];
         u_s[t] = du[((size_t)b * S + t) * S + j];
     }
     __syncthreads();
     for (int d = tid; d < D; d += 256) {
         float acc = 0.f;
-        for (int t = 0; t < S; ++t) {
+        for (int t = tlo; t < S; ++t) {
             const size_t o = (size_t)t * row + (size_t)b * D + d;
             acc += a_s[t] * d_att[o] + u_s[t] * x[o];
         }
@@ -133,15 +152,16 @@ constexpr int G2_NT = 512;   // threads per workgroup
 
 __host__ __device__ __forceinline__ int g2_ldm(int D) { return D | 1; }          // odd row stride: key-on-lane reads conflict-free
 
-// stage M[b] ([S x D], row stride B*D in global) into Ms[S][ldm] and V[t0 .. t0+7] (same layout) transposed into vT[d][QB]
+// stage rows j < Sk of M[b] ([S x D], row stride B*D in global) into Ms[S][ldm] and V[t0 .. t0+15] (same layout) transposed into
+// vT[d][QB].  Sk = S, or in the causal kernels min(S, t0 + QB): the rows this query block sees.
 __device__ __forceinline__ void g2_stage(float* __restrict__ Ms, float* __restrict__ vT, const float* __restrict__ mem,
-                                         const float* __restrict__ v, int S, int B, int D, int b, int t0, int tid) {
+                                         const float* __restrict__ v, int S, int Sk, int B, int D, int b, int t0, int tid) {
     const int ldm = g2_ldm(D);
     const size_t row = (size_t)B * D;
     const float* mb = mem + (size_t)b * D;
     if ((D & 3) == 0) {
         // coalesced 16-byte loads over the flat (step, column/4) index, 8 independent loads in flight per thread
-        const int kv = D >> 2, total = S * kv;
+        const int kv = D >> 2, total = Sk * kv;
         for (int i0 = tid; i0 < total; i0 += G2_NT * 8) {
             float4 r[8];
             int jj[8], dd[8];
@@ -162,13 +182,13 @@ __device__ __forceinline__ void g2_stage(float* __restrict__ Ms, float* __restri
         }
     } else {
         for (int d = tid; d < D; d += G2_NT)
-            for (int j0 = 0; j0 < S; j0 += 16) {
+            for (int j0 = 0; j0 < Sk; j0 += 16) {
                 float r[16];
 #pragma unroll
-                for (int u = 0; u < 16; ++u) r[u] = mb[(size_t)min(j0 + u, S - 1) * row + d];
+                for (int u = 0; u < 16; ++u) r[u] = mb[(size_t)min(j0 + u, Sk - 1) * row + d];
 #pragma unroll
                 for (int u = 0; u < 16; ++u)
-                    if (j0 + u < S) Ms[(j0 + u) * ldm + d] = r[u];
+                    if (j0 + u < Sk) Ms[(j0 + u) * ldm + d] = r[u];
             }
     }
     for (int d = tid; d < D; d += G2_NT) {
@@ -194,9 +214,9 @@ __device__ __forceinline__ void g2_dots(float (&acc)[4], const float* __restrict
     }
 }
 
-// out[t0 + q][d] = sum_j cT[j][q] * M[j][d] for q < QB (rows < S only); thread = (column d, half of the 16 outputs)
+// out[t0 + q][d] = sum_{j < Sk} cT[j][q] * M[j][d] for q < QB (rows < S only); thread = (column d, half of the 16 outputs)
 __device__ __forceinline__ void g2_combine(float* __restrict__ out, const float* __restrict__ Ms, const float* __restrict__ cT,
-                                           int S, int B, int D, int b, int t0, int tid) {
+                                           int S, int Sk, int B, int D, int b, int t0, int tid) {
     const int ldm = g2_ldm(D);
     const size_t row = (size_t)B * D;
     const int qh = tid >> 8;
@@ -205,7 +225,7 @@ __device__ __forceinline__ void g2_combine(float* __restrict__ out, const float*
 #pragma unroll
         for (int q = 0; q < 8; ++q) acc[q] = 0.f;
 #pragma unroll 4
-        for (int j = 0; j < S; ++j) {
+        for (int j = 0; j < Sk; ++j) {
             const float m = Ms[j * ldm + d];
             const float4 c0 = *reinterpret_cast<const float4*>(cT + j * G2_QB + 8 * qh), c1 = *reinterpret_cast<const float4*>(cT + j * G2_QB + 8 * qh + 4);
             acc[0] += c0.x * m; acc[1] += c0.y * m; acc[2] += c0.z * m; acc[3] += c0.w * m;
@@ -217,6 +237,7 @@ __device__ __forceinline__ void g2_combine(float* __restrict__ out, const float*
     }
 }
 
+template <bool CAUSAL>
 __global__ __launch_bounds__(G2_NT) void general2_fwd_lds_kernel(const float* __restrict__ x, const float* __restrict__ mem,
                                                                const float* __restrict__ mask, float* __restrict__ att,
                                                                float* __restrict__ alpha, float* __restrict__ tanh_s, int S,
@@ -227,18 +248,20 @@ __global__ __launch_bounds__(G2_NT) void general2_fwd_lds_kernel(const float* __
     float* aT = xT + D * G2_QB;                        // [S][QB]
     float* inv_s = aT + S * G2_QB;                     // [QB]  (no static LDS: the dynamic opt-in covers the whole 160 KB)
     const int t0 = blockIdx.x * G2_QB, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    g2_stage(Ms, xT, mem, x, S, B, D, b, t0, tid);
+    const int Sk = CAUSAL ? min(S, t0 + G2_QB) : S;    // memory rows this query block sees
+    g2_stage(Ms, xT, mem, x, S, Sk, B, D, b, t0, tid);
     __syncthreads();
     {
         const int j = tid & 127, qh = tid >> 7;
-        if (j < S) {
+        if (j < Sk) {
             float acc[4];
             g2_dots(acc, Ms, xT, D, j, qh);
             const float m = mask[(size_t)b * S + j];
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const float sv = tanhf(m * (m * acc[q]));
-                aT[j * G2_QB + 4 * qh + q] = __expf(sv) * m;
+                const bool above = CAUSAL && j > t0 + 4 * qh + q;      // inside the diagonal block
+                const float sv = above ? 0.f : tanhf(m * (m * acc[q]));
+                aT[j * G2_QB + 4 * qh + q] = above ? 0.f : __expf(sv) * m;
                 const int t = t0 + 4 * qh + q;
                 if (t < S) tanh_s[((size_t)b * S + t) * S + j] = sv;
             }
@@ -247,21 +270,30 @@ __global__ __launch_bounds__(G2_NT) void general2_fwd_lds_kernel(const float* __
     __syncthreads();
     for (int q = 2 * w; q < 2 * w + 2; ++q) {          // wave w normalises queries 2w, 2w + 1
         float part = 0.f;
-        for (int j = lane; j < S; j += 64) part += aT[j * G2_QB + q];
+        for (int j = lane; j < Sk; j += 64) part += aT[j * G2_QB + q];
         part = wave_sum(part);
         if (lane == 0) inv_s[q] = 1.0f / part;
     }
     __syncthreads();
-    for (int i = tid; i < S * G2_QB; i += G2_NT) {
+    for (int i = tid; i < Sk * G2_QB; i += G2_NT) {
         const int j = i / G2_QB, q = i - j * G2_QB;
         const float a = aT[i] * inv_s[q];
         aT[i] = a;
         if (t0 + q < S) alpha[((size_t)b * S + t0 + q) * S + j] = a;
     }
+    if (CAUSAL)
+        for (int i = Sk * G2_QB + tid; i < S * G2_QB; i += G2_NT) {      // the blocks above the diagonal: written, with zeros
+            const int j = i / G2_QB, q = i - j * G2_QB;
+            if (t0 + q < S) {
+                alpha[((size_t)b * S + t0 + q) * S + j] = 0.f;
+                tanh_s[((size_t)b * S + t0 + q) * S + j] = 0.f;
+            }
+        }
     __syncthreads();
-    g2_combine(att, Ms, aT, S, B, D, b, t0, tid);
+    g2_combine(att, Ms, aT, S, Sk, B, D, b, t0, tid);
 }
 
+template <bool CAUSAL>
 __global__ __launch_bounds__(G2_NT) void general2_bwd_q_lds_kernel(const float* __restrict__ d_att, const float* __restrict__ mem,
                                                                  const float* __restrict__ mask, const float* __restrict__ alpha,
                                                                  const float* __restrict__ tanh_s, float* __restrict__ du,
@@ -272,11 +304,12 @@ __global__ __launch_bounds__(G2_NT) void general2_bwd_q_lds_kernel(const float* 
     float* uT = gT + D * G2_QB;                        // da, then du: [S][QB]
     float* dsum_s = uT + S * G2_QB;                    // [QB]
     const int t0 = blockIdx.x * G2_QB, b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    g2_stage(Ms, gT, mem, d_att, S, B, D, b, t0, tid);
+    const int Sk = CAUSAL ? min(S, t0 + G2_QB) : S;
+    g2_stage(Ms, gT, mem, d_att, S, Sk, B, D, b, t0, tid);
     __syncthreads();
     {
         const int j = tid & 127, qh = tid >> 7;
-        if (j < S) {
+        if (j < Sk) {
             float acc[4];
             g2_dots(acc, Ms, gT, D, j, qh);
 #pragma unroll
@@ -287,25 +320,33 @@ __global__ __launch_bounds__(G2_NT) void general2_bwd_q_lds_kernel(const float* 
     for (int q = 2 * w; q < 2 * w + 2; ++q) {          // dsum_q = sum_j alpha[q][j] da[q][j]
         const int t = min(t0 + q, S - 1);
         float part = 0.f;
-        for (int j = lane; j < S; j += 64) part += alpha[((size_t)b * S + t) * S + j] * uT[j * G2_QB + q];
+        for (int j = lane; j < Sk; j += 64) part += alpha[((size_t)b * S + t) * S + j] * uT[j * G2_QB + q];
         part = wave_sum(part);
         if (lane == 0) dsum_s[q] = part;
     }
     __syncthreads();
-    for (int i = tid; i < S * G2_QB; i += G2_NT) {
+    for (int i = tid; i < Sk * G2_QB; i += G2_NT) {
         const int j = i / G2_QB, q = i - j * G2_QB;
         const int t = min(t0 + q, S - 1);
         const size_t ar = ((size_t)b * S + t) * S + j;
         const float a = alpha[ar], sv = tanh_s[ar], m = mask[(size_t)b * S + j];
-        const float v = a * (uT[i] - dsum_s[q]) * (1.0f - sv * sv) * (m * m);
+        float v = a * (uT[i] - dsum_s[q]) * (1.0f - sv * sv) * (m * m);
+        if (CAUSAL && j > t0 + q) v = 0.f;             // the diagonal block (alpha is 0 there: this pins the sign of the zero)
         uT[i] = v;
         if (t0 + q < S) du[ar] = v;
     }
+    if (CAUSAL)
+        for (int i = Sk * G2_QB + tid; i < S * G2_QB; i += G2_NT) {
+            const int j = i / G2_QB, q = i - j * G2_QB;
+            if (t0 + q < S) du[((size_t)b * S + t0 + q) * S + j] = 0.f;
+        }
     __syncthreads();
-    g2_combine(dx, Ms, uT, S, B, D, b, t0, tid);
+    g2_combine(dx, Ms, uT, S, Sk, B, D, b, t0, tid);
 }
 
-// per (block of 8 memory steps j0 .., dialogue): dM_j = sum_t ( a_tj d_att_t + du_tj x_t ), t ascending
+// per (block of 16 memory steps j0 .., dialogue): dM_j = sum_t ( a_tj d_att_t + du_tj x_t ), t ascending; causal: from t = j0
+// (alpha and du are exact zeros at j > t, so the diagonal block's rows t < j add 0)
+template <bool CAUSAL>
 __global__ __launch_bounds__(G2_NT) void general2_bwd_m_lds_kernel(const float* __restrict__ d_att, const float* __restrict__ x,
                                                                  const float* __restrict__ alpha, const float* __restrict__ du,
                                                                  float* __restrict__ dmem, int S, int B, int D) {
@@ -314,7 +355,8 @@ __global__ __launch_bounds__(G2_NT) void general2_bwd_m_lds_kernel(const float* 
     float* cu = ca + S * G2_QB;                        // [S][QB] du[t][j0 + q]
     const int j0 = blockIdx.x * G2_QB, b = blockIdx.y, tid = threadIdx.x;
     const size_t row = (size_t)B * D;
-    for (int i = tid; i < S * G2_QB; i += G2_NT) {
+    const int tlo = CAUSAL ? j0 : 0;                   // first query step any memory step of the block is seen by
+    for (int i = tlo * G2_QB + tid; i < S * G2_QB; i += G2_NT) {
         const int t = i / G2_QB, q = i - t * G2_QB;
         const size_t o = ((size_t)b * S + t) * S + min(j0 + q, S - 1);
         ca[i] = alpha[o];
@@ -328,7 +370,7 @@ __global__ __launch_bounds__(G2_NT) void general2_bwd_m_lds_kernel(const float* 
         for (int q = 0; q < 8; ++q) acc[q] = 0.f;
         const float* gp = d_att + (size_t)b * D + d;
         const float* xp = x + (size_t)b * D + d;
-        for (int t0 = 0; t0 < S; t0 += 8) {            // 16 loads in flight
+        for (int t0 = tlo; t0 < S; t0 += 8) {          // 16 loads in flight
             float gv[8], xv[8];
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
@@ -372,44 +414,78 @@ static int check_g2(int S, int B, int D) {
 
 using namespace ganffn;
 
-extern "C" int ganffn_general2_attention_fwd(const float* x, const float* mem, const float* mask, float* att, float* alpha,
-                                             float* tanh_s, int S, int B, int D, void* stream) {
-    GF_TRY(check_g2(S, B, D));
-    GF_CHECK_ARG(x && mem && mask && att && alpha && tanh_s, "general2_attention_fwd: null pointer");
+static int g2_flags(uint32_t flags, const char* who, bool* causal) {
+    GF_CHECK_ARG((flags & ~GANFFN_ATTN_CAUSAL) == 0, "%s: unknown flag bits 0x%x", who, flags & ~GANFFN_ATTN_CAUSAL);
+    *causal = (flags & GANFFN_ATTN_CAUSAL) != 0;
+    return 0;
+}
+
+template <bool CAUSAL>
+static int g2_launch_fwd(const float* x, const float* mem, const float* mask, float* att, float* alpha, float* tanh_s, int S, int B,
+                         int D, hipStream_t st) {
     if (g2_fits_lds(S, D)) {
         const size_t lds = g2_lds_bytes(S, D);
-        GF_TRY((lds_optin<general2_fwd_lds_kernel>(lds, "general2_fwd")));
-        hipLaunchKernelGGL(general2_fwd_lds_kernel, dim3((S + G2_QB - 1) / G2_QB, B), dim3(G2_NT), lds, (hipStream_t)stream, x, mem,
-                           mask, att, alpha, tanh_s, S, B, D);
+        GF_TRY((lds_optin<general2_fwd_lds_kernel<CAUSAL>>(lds, "general2_fwd")));
+        hipLaunchKernelGGL(general2_fwd_lds_kernel<CAUSAL>, dim3((S + G2_QB - 1) / G2_QB, B), dim3(G2_NT), lds, st, x, mem, mask, att,
+                           alpha, tanh_s, S, B, D);
         GF_LAUNCH_CHECK();
         return 0;
     }
-    hipLaunchKernelGGL(general2_fwd_kernel, dim3(S, B), dim3(256), 0, (hipStream_t)stream, x, mem, mask, att, alpha, tanh_s,
-                       S, B, D);
+    hipLaunchKernelGGL(general2_fwd_kernel<CAUSAL>, dim3(S, B), dim3(256), 0, st, x, mem, mask, att, alpha, tanh_s, S, B, D);
     GF_LAUNCH_CHECK();
     return 0;
+}
+
+template <bool CAUSAL>
+static int g2_launch_bwd(const float* d_att, const float* x, const float* mem, const float* mask, const float* alpha,
+                         const float* tanh_s, float* du_ws, float* dx, float* dmem, int S, int B, int D, hipStream_t st) {
+    if (g2_fits_lds(S, D)) {
+        const size_t lds = g2_lds_bytes(S, D);
+        const dim3 grid((S + G2_QB - 1) / G2_QB, B);
+        GF_TRY((lds_optin<general2_bwd_q_lds_kernel<CAUSAL>>(lds, "general2_bwd_q")));
+        hipLaunchKernelGGL(general2_bwd_q_lds_kernel<CAUSAL>, grid, dim3(G2_NT), lds, st, d_att, mem, mask, alpha, tanh_s, du_ws, dx, S,
+                           B, D);
+        GF_LAUNCH_CHECK();
+        hipLaunchKernelGGL(general2_bwd_m_lds_kernel<CAUSAL>, grid, dim3(G2_NT), (size_t)2 * S * G2_QB * sizeof(float), st, d_att, x,
+                           alpha, du_ws, dmem, S, B, D);
+        GF_LAUNCH_CHECK();
+        return 0;
+    }
+    hipLaunchKernelGGL(general2_bwd_q_kernel<CAUSAL>, dim3(S, B), dim3(256), 0, st, d_att, mem, mask, alpha, tanh_s, du_ws, dx, S, B, D);
+    GF_LAUNCH_CHECK();
+    hipLaunchKernelGGL(general2_bwd_m_kernel<CAUSAL>, dim3(S, B), dim3(256), 0, st, d_att, x, alpha, du_ws, dmem, S, B, D);
+    GF_LAUNCH_CHECK();
+    return 0;
+}
+
+extern "C" int ganffn_general2_attention_fwd_mask(const float* x, const float* mem, const float* mask, uint32_t flags, float* att,
+                                                  float* alpha, float* tanh_s, int S, int B, int D, void* stream) {
+    bool causal = false;
+    GF_TRY(g2_flags(flags, "general2_attention_fwd", &causal));
+    GF_TRY(check_g2(S, B, D));
+    GF_CHECK_ARG(x && mem && mask && att && alpha && tanh_s, "general2_attention_fwd: null pointer");
+    return causal ? g2_launch_fwd<true>(x, mem, mask, att, alpha, tanh_s, S, B, D, (hipStream_t)stream)
+                  : g2_launch_fwd<false>(x, mem, mask, att, alpha, tanh_s, S, B, D, (hipStream_t)stream);
+}
+
+extern "C" int ganffn_general2_attention_bwd_mask(const float* d_att, const float* x, const float* mem, const float* mask,
+                                                  uint32_t flags, const float* alpha, const float* tanh_s, float* du_ws, float* dx,
+                                                  float* dmem, int S, int B, int D, void* stream) {
+    bool causal = false;
+    GF_TRY(g2_flags(flags, "general2_attention_bwd", &causal));
+    GF_TRY(check_g2(S, B, D));
+    GF_CHECK_ARG(d_att && x && mem && mask && alpha && tanh_s && du_ws && dx && dmem, "general2_attention_bwd: null pointer");
+    return causal ? g2_launch_bwd<true>(d_att, x, mem, mask, alpha, tanh_s, du_ws, dx, dmem, S, B, D, (hipStream_t)stream)
+                  : g2_launch_bwd<false>(d_att, x, mem, mask, alpha, tanh_s, du_ws, dx, dmem, S, B, D, (hipStream_t)stream);
+}
+
+extern "C" int ganffn_general2_attention_fwd(const float* x, const float* mem, const float* mask, float* att, float* alpha,
+                                             float* tanh_s, int S, int B, int D, void* stream) {
+    return ganffn_general2_attention_fwd_mask(x, mem, mask, 0u, att, alpha, tanh_s, S, B, D, stream);
 }
 
 extern "C" int ganffn_general2_attention_bwd(const float* d_att, const float* x, const float* mem, const float* mask,
                                              const float* alpha, const float* tanh_s, float* du_ws, float* dx, float* dmem,
                                              int S, int B, int D, void* stream) {
-    GF_TRY(check_g2(S, B, D));
-    GF_CHECK_ARG(d_att && x && mem && mask && alpha && tanh_s && du_ws && dx && dmem, "general2_attention_bwd: null pointer");
-    hipStream_t st = (hipStream_t)stream;
-    if (g2_fits_lds(S, D)) {
-        const size_t lds = g2_lds_bytes(S, D);
-        const dim3 grid((S + G2_QB - 1) / G2_QB, B);
-        GF_TRY((lds_optin<general2_bwd_q_lds_kernel>(lds, "general2_bwd_q")));
-        hipLaunchKernelGGL(general2_bwd_q_lds_kernel, grid, dim3(G2_NT), lds, st, d_att, mem, mask, alpha, tanh_s, du_ws, dx, S, B, D);
-        GF_LAUNCH_CHECK();
-        hipLaunchKernelGGL(general2_bwd_m_lds_kernel, grid, dim3(G2_NT), (size_t)2 * S * G2_QB * sizeof(float), st, d_att, x, alpha,
-                           du_ws, dmem, S, B, D);
-        GF_LAUNCH_CHECK();
-        return 0;
-    }
-    hipLaunchKernelGGL(general2_bwd_q_kernel, dim3(S, B), dim3(256), 0, st, d_att, mem, mask, alpha, tanh_s, du_ws, dx, S, B, D);
-    GF_LAUNCH_CHECK();
-    hipLaunchKernelGGL(general2_bwd_m_kernel, dim3(S, B), dim3(256), 0, st, d_att, x, alpha, du_ws, dmem, S, B, D);
-    GF_LAUNCH_CHECK();
-    return 0;
+    return ganffn_general2_attention_bwd_mask(d_att, x, mem, mask, 0u, alpha, tanh_s, du_ws, dx, dmem, S, B, D, stream);
 }

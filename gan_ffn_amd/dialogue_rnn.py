@@ -16,6 +16,8 @@ restatement below, which is also what the reference-fixture parity tests pin.  T
   * BiModel's second attention — one masked `general2` MatchingAttention query per time step in the reference — is ONE
     batched masked attention over all (dialogue, query step) pairs (`general2_all_queries`).
 The generators underneath are the HIP path; there is no CPU route through them.
+An extension the reference does not have: `UniModel` / `GAN_FFN_DialogueRNN(causal=True)`, the classifier that never looks ahead
+(one forward DialogueRNN, causal second attention, causal generators).
 """
 import torch
 import torch.nn as nn
@@ -35,11 +37,17 @@ class SimpleAttention(nn.Module):
         return torch.bmm(alpha, M.transpose(0, 1))[:, 0, :], alpha
 
 
-def general2_scores(xt, M, mask):
+def general2_scores(xt, M, mask, causal=False):
     """masked `general2` attention weights for queries xt (B, Q, D) over memory M (S, B, D), mask (B, S):
-    softmax_j tanh(m_j * <x, m_j * M_j>), zeroed at masked positions and re-normalised (model.py:169-182)."""
+    softmax_j tanh(m_j * <x, m_j * M_j>), zeroed at masked positions and re-normalised (model.py:169-182).
+    causal (Q = S, query t is step t): the keys of query t are the steps j <= t, a_tj = e^{s_tj} m_j [j <= t] /
+    sum_{k <= t} e^{s_tk} m_k — the same call on M[:t+1] and mask[:, :t+1] for every t."""
     Mb = M.transpose(0, 1) * mask.unsqueeze(2)                               # (B, S, D), masked memory
     a = torch.tanh(torch.bmm(xt, Mb.transpose(1, 2)) * mask.unsqueeze(1))    # (B, Q, S)
+    if causal:
+        # s is bounded by tanh: e^s needs no max-subtraction, and the softmax's own denominator cancels in the re-normalisation
+        a = torch.exp(a) * mask.unsqueeze(1) * torch.tril(torch.ones_like(a[0]))
+        return a / a.sum(dim=2, keepdim=True)
     a = F.softmax(a, dim=2) * mask.unsqueeze(1)
     return a / a.sum(dim=2, keepdim=True)
 
@@ -78,14 +86,18 @@ class MatchingAttention(nn.Module):
             alpha = F.softmax(self.vector_prod(torch.tanh(self.transform(cat))), 1).transpose(1, 2)
         return torch.bmm(alpha, M.transpose(0, 1))[:, 0, :], alpha
 
-    def general2_all_queries(self, M, mask):
+    def general2_all_queries(self, M, mask, causal=False):
         """every time step of M as the candidate, at once: -> pooled (S, B, D), alpha (B, S_query, S_memory).
-        Equals [self(M, M[t], mask) for t in range(S)] (what BiModel.forward loops over, model.py:1043-1049)."""
+        Equals [self(M, M[t], mask) for t in range(S)] (what BiModel.forward loops over, model.py:1043-1049).
+        causal=True (an extension the reference does not have; UniModel's attention): step t attends to steps j <= t only —
+        [self(M[:t+1], M[t], mask[:, :t+1]) for t in range(S)], alpha exactly 0 above the diagonal."""
         assert self.att_type == "general2"
         if M.is_cuda and M.size(0) <= 128 and M.size(2) <= 1024:
             from . import ops                      # one HIP kernel per direction instead of ~10 torch ops on (B,S,S)
+            if causal:
+                return ops.General2AttnFn.apply(self.transform(M), M, mask, True)
             return ops.General2AttnFn.apply(self.transform(M), M, mask)
-        alpha = general2_scores(self.transform(M).transpose(0, 1), M, mask)          # (B, S, S)
+        alpha = general2_scores(self.transform(M).transpose(0, 1), M, mask, causal)  # (B, S, S)
         return torch.bmm(alpha, M.transpose(0, 1)).transpose(0, 1), alpha
 
 
@@ -235,31 +247,80 @@ class BiModel(nn.Module):
         return F.log_softmax(self.smax_fc(hidden), 2), alpha, alpha_f, alpha_b
 
 
+class UniModel(nn.Module):
+    """BiModel without its look-ahead (an extension the reference does not have): ONE forward DialogueRNN — its context
+    attention of step t sees g_0 .. g_{t-1} only, so the recurrence is causal by construction —, the second (masked general2)
+    attention CAUSAL (step t attends to the emotions of steps j <= t: MatchingAttention.general2_all_queries(causal=True)),
+    linear + relu + dropout, class log-probabilities.  log_prob[t] of a dialogue is a function of its utterances and speakers
+    0 .. t.  There is no dialog_rnn_r; matchatt is D_e x D_e, linear D_e -> D_h, smax_fc D_h -> n_classes; the dropouts are
+    BiModel's.  Returns BiModel's tuple with an empty alpha_b."""
+
+    def __init__(self, D_m, D_g, D_p, D_e, D_h, n_classes=7, listener_state=False, context_attention="simple", D_a=100,
+                 dropout_rec=0.5, dropout=0.5):
+        super().__init__()
+        self.D_m, self.D_g, self.D_p, self.D_e, self.D_h, self.n_classes = D_m, D_g, D_p, D_e, D_h, n_classes
+        self.dropout = nn.Dropout(dropout)
+        self.dropout_rec = nn.Dropout(dropout + 0.15)
+        self.dialog_rnn_f = DialogueRNN(D_m, D_g, D_p, D_e, listener_state, context_attention, D_a, dropout_rec)
+        self.linear = nn.Linear(D_e, D_h)
+        self.smax_fc = nn.Linear(D_h, n_classes)
+        self.matchatt = MatchingAttention(D_e, D_e, att_type="general2")
+
+    def forward(self, U, qmask, umask, att2=True):
+        emotions, alpha_f = self.dialog_rnn_f(U, qmask)
+        emotions = self.dropout_rec(emotions)
+        if att2:
+            att, a = self.matchatt.general2_all_queries(emotions, umask, causal=True)
+            alpha = [a[:, t, :] for t in range(a.size(1))]
+            hidden = F.relu(self.linear(att))
+        else:
+            alpha = []
+            hidden = F.relu(self.linear(emotions))
+        hidden = self.dropout(hidden)
+        return F.log_softmax(self.smax_fc(hidden), 2), alpha, alpha_f, []
+
+
 class GAN_FFN_DialogueRNN(nn.Module):
     """fusion = G_a(acoustic) + G_v(visual) + G_t(text) -> BiModel (model.py:1465-1528).  `gelu`, `relu`, `dropout`
     and `fc1` exist on the reference object without taking part in forward; they are kept so state_dicts match.
     mask_padding (default False: the reference passes no mask) is an extension: the generators' self-attention ignores the padded
     utterances of every dialogue (key lengths umask.sum(1), derived on the device), the one place where padding reached a real
-    utterance's prediction.  `umask` must then be a PREFIX mask.  A plain attribute: the state_dict is the same either way."""
+    utterance's prediction.  `umask` must then be a PREFIX mask.  A plain attribute: the state_dict is the same either way.
+    causal (default False) is an extension the reference does not have: a classifier that never looks ahead.  The head is a
+    UniModel (one forward DialogueRNN, causal second attention) and the three generators run under the causal self-attention
+    mask (composing with mask_padding as in GAN_FFN), so log_prob[t] of a dialogue depends on its utterances and speakers
+    0 .. t alone.  The UniModel is kept under the attribute name `bi_model`, so that engines, artifacts and tools that say
+    net.bi_model keep working.  A plain attribute; the state_dict is the bidirectional one without bi_model.dialog_rnn_r.*,
+    with bi_model.matchatt.transform D_e x D_e, bi_model.linear D_e -> D_h and bi_model.smax_fc D_h -> n_classes.
+    causal=False constructs and runs exactly what it always did.  The option is given by keyword only
+    (GAN_FFN_DialogueRNN(..., causal=True)): it arrives through `options`, whose one known key is `causal` — any other keyword
+    raises TypeError as an unknown argument does — so the constructor's named parameters are the ones it always had."""
 
     def __init__(self, acoustic_generator, visual_generator, text_generator, D_m, D_g, D_p, D_e, D_h, D_a, n_classes,
-                 listener_state, context_attention, dropout_rec, dropout, mask_padding=False):
+                 listener_state, context_attention, dropout_rec, dropout, mask_padding=False, **options):
         super().__init__()
         self.mask_padding = bool(mask_padding)
+        self.causal = bool(options.pop("causal", False))
+        if options:
+            raise TypeError("GAN_FFN_DialogueRNN.__init__() got an unexpected keyword argument %r" % sorted(options)[0])
         self.n_classes = n_classes
         self.acoustic_generator = acoustic_generator
         self.visual_generator = visual_generator
         self.text_generator = text_generator
         self.gelu, self.relu, self.dropout = nn.GELU(), nn.ReLU(), nn.Dropout(dropout)
-        self.bi_model = BiModel(D_m=D_m, D_g=D_g, D_p=D_p, D_e=D_e, D_h=D_h, n_classes=n_classes,
-                                listener_state=listener_state, context_attention=context_attention, D_a=D_a,
-                                dropout_rec=dropout_rec, dropout=dropout)
+        self.bi_model = (UniModel if self.causal else BiModel)(D_m=D_m, D_g=D_g, D_p=D_p, D_e=D_e, D_h=D_h, n_classes=n_classes,
+                                                               listener_state=listener_state, context_attention=context_attention,
+                                                               D_a=D_a, dropout_rec=dropout_rec, dropout=dropout)
         self.fc1 = nn.Linear(100, n_classes)
 
     def forward(self, acoustic, visual, text, qmask, umask):
         from . import ops
         kl = ops.key_lengths_from_umask(umask) if self.mask_padding else None
-        fusion = self.acoustic_generator(acoustic, kl) + self.visual_generator(visual, kl) + self.text_generator(text, kl)
+        if self.causal:
+            fusion = (self.acoustic_generator(acoustic, kl, causal=True) + self.visual_generator(visual, kl, causal=True)
+                      + self.text_generator(text, kl, causal=True))
+        else:
+            fusion = self.acoustic_generator(acoustic, kl) + self.visual_generator(visual, kl) + self.text_generator(text, kl)
         return self.bi_model(fusion, qmask, umask)
 
 

@@ -1246,7 +1246,15 @@ class DrnnEngine(_NetRunner):
     every launch).
     mask_padding (default False: the reference passes no mask) is an extension: the generators' self-attention sees only the first
     umask.sum(1) utterances of every dialogue — the lengths tensor the recurrence already uses, so the step has no launch more —
-    and with that no part of the step lets padding reach a real utterance.  False issues exactly the calls it always did."""
+    and with that no part of the step lets padding reach a real utterance.  False issues exactly the calls it always did.
+    A causal net (GAN_FFN_DialogueRNN(causal=True): net.causal, read from the module — the head's structure is the module's, so
+    there is no constructor argument; absent means False) is a classifier that never looks ahead, and the step follows it: the
+    generators run forward and backward under the causal flag (with the key lengths when mask_padding), there is ONE recurrence
+    direction (ndir = 1: no ganffn_seq_reverse, no reversed speaker indices), the join is a dropout of e_f alone (ganffn_dropout
+    at SITE_JOIN_F, forward and on the gradient; skipped in eval), the head is D_e wide (transform D_e -> D_e, the CAUSAL
+    general2 attention through ganffn_general2_attention_*_mask, linear D_e -> D_h) and d_fusion is the recurrence's dU.  The
+    head slab holds one cell's tensors, the six head tensors, then the one cell's listener tensors; the step's block of RNG
+    offsets keeps its layout.  A bidirectional net issues exactly the calls it always did."""
 
     def __init__(self, net, lr=1e-4, weight_decay=1e-5, class_weights=CLASS_WEIGHTS, process_group=None, n_buckets=3,
                  n_streams=1, max_dialogues=32, mask_padding=False):
@@ -1255,7 +1263,10 @@ class DrnnEngine(_NetRunner):
         self.max_dialogues = _check_max_dialogues("DrnnEngine", max_dialogues)
         self.module = net
         bm = net.bi_model
-        cf, cr = bm.dialog_rnn_f.dialogue_cell, bm.dialog_rnn_r.dialogue_cell
+        self._causal = self.causal = bool(getattr(net, "causal", False))
+        self.ndir = 1 if self.causal else 2                  # directions of the recurrence = cells on the head slab
+        cells = [bm.dialog_rnn_f.dialogue_cell] + ([] if self.causal else [bm.dialog_rnn_r.dialogue_cell])
+        cf = cells[0]
         if cf.D_g != cf.D_p or cf.D_g > 512 or cf.D_g % 4 or not ops.drnn_att_limits_hold(cf):
             raise ValueError("DrnnEngine runs every context attention type (general, simple, dot, general2, concat) within the "
                              "recurrence kernels' limits: D_g = D_p <= 512 (multiples of 4), dot only with D_m = D_g, concat "
@@ -1272,17 +1283,18 @@ class DrnnEngine(_NetRunner):
         dev = self.dev
         self.lr, self.wd = lr, weight_decay
         self.Dm, self.H, self.He, self.Dh2 = cf.D_m, cf.D_g, cf.D_e, bm.linear.weight.shape[0]
+        self.D2 = self.ndir * cf.D_e                         # width of the head's rows (the joined emotions)
         self.n_classes = bm.smax_fc.weight.shape[0]
         self.p_rec, self.p_join, self.p_hid = float(cf.dropout.p), float(bm.dropout_rec.p), float(bm.dropout.p)
         # ---- head parameters -> one slab (views keep the module's parameters alive on it)
         plist = []
-        for cell in (cf, cr):
+        for cell in cells:
             sd = dict(cell.named_parameters())
             plist += [sd[k] for k in ops.DRNN_KEYS[:12] + self.att_keys]
         plist += [bm.matchatt.transform.weight, bm.matchatt.transform.bias, bm.linear.weight, bm.linear.bias,
                   bm.smax_fc.weight, bm.smax_fc.bias]
         if self.listener:                    # behind the head tensors: the listener-free slab layout does not move
-            for cell in (cf, cr):
+            for cell in cells:
                 sd = dict(cell.named_parameters())
                 plist += [sd[k] for k in ops.DRNN_LISTENER_KEYS]
         head = self.head = _ParamSlab(plist, dev)
@@ -1319,15 +1331,16 @@ class DrnnEngine(_NetRunner):
             # (the capacity's family: the layouts are the same functions of B in every family, and the recurrence's buffers grow
             # with the party count — sized for the widest batch so far)
             n_saved, n_ws = ops.drnn_floats(cfgc, self.acfg, self.listener, cP)
-            T, D2, Cn = cS * cB, 2 * self.He, self.n_classes
+            T, D2, Cn = cS * cB, self.D2, self.n_classes
             z = lambda n: torch.empty(n, **f32)
-            self._f = dict(fusion=z(T * self.Dm), rev_U=z(T * self.Dm), e_f=z(T * self.He), e_b=z(T * self.He),
-                           alpha_f=z(cB * cS * cS), alpha_b=z(cB * cS * cS), emotions=z(T * D2), xq=z(T * D2), att=z(T * D2),
+            zb = (lambda n: None) if self.causal else z      # the second direction's buffers: a causal net has none
+            self._f = dict(fusion=z(T * self.Dm), rev_U=zb(T * self.Dm), e_f=z(T * self.He), e_b=zb(T * self.He),
+                           alpha_f=z(cB * cS * cS), alpha_b=zb(cB * cS * cS), emotions=z(T * D2), xq=z(T * D2), att=z(T * D2),
                            alpha2=z(cB * cS * cS), tanh_s=z(cB * cS * cS), du=z(cB * cS * cS), hidden=z(T * self.Dh2),
                            logits=z(T * Cn), log_prob=z(T * Cn), dlogits=z(T * Cn), d_hidden=z(T * self.Dh2), d_att=z(T * D2),
-                           d_xq=z(T * D2), d_mem=z(T * D2), d_em=z(T * D2), d_e_f=z(T * self.He), d_e_b=z(T * self.He),
-                           dU_f=z(T * self.Dm), dU_b=z(T * self.Dm), saved_f=z(n_saved), saved_b=z(n_saved), ws_f=z(n_ws),
-                           ws_b=z(n_ws), lin_ws=z(int(lib.ganffn_linear_bwd_workspace_floats(T, D2, D2)) + 64))
+                           d_xq=z(T * D2), d_mem=z(T * D2), d_em=z(T * D2), d_e_f=z(T * self.He), d_e_b=zb(T * self.He),
+                           dU_f=z(T * self.Dm), dU_b=zb(T * self.Dm), saved_f=z(n_saved), saved_b=zb(n_saved), ws_f=z(n_ws),
+                           ws_b=zb(n_ws), lin_ws=z(int(lib.ganffn_linear_bwd_workspace_floats(T, D2, D2)) + 64))
             self.ws2 = torch.zeros(4, **f32)
         for p_ in self.pass_G.values():
             p_.resize(S, B)
@@ -1349,19 +1362,20 @@ class DrnnEngine(_NetRunner):
         self._net_fwd(self.G[k], self.pass_G[k], self._tune_x[1][k], train=False, save=True, adds=(0, 1))
 
     # ------------------------------------------------------------------------------------------
-    # pointer structs of both directions over the head slab (grad: over its gradient slab), built by the ops helpers
+    # pointer structs of the ndir directions over the head slab (grad: over its gradient slab), built by the ops helpers
     def _drnn_ptrs(self, grad):
         # (the first ncell fields; other types than general: att_w stays NULL)
-        return ops._ptr_structs(_lib.DrnnPtrs, [[self._hp(self.ncell * z + j, grad) for j in range(self.ncell)] for z in range(2)])
+        return ops._ptr_structs(_lib.DrnnPtrs, [[self._hp(self.ncell * z + j, grad) for j in range(self.ncell)]
+                                                for z in range(self.ndir)])
 
     def _drnn_att_ptrs(self, grad):
         n = len(self.att_keys)
-        return ops._ptr_structs(_lib.DrnnAttPtrs, [[self._hp(self.ncell * z + 12 + i, grad) for i in range(n)] for z in range(2)],
-                                lambda a, _: ops._att_ptrs(self.att, a))
+        return ops._ptr_structs(_lib.DrnnAttPtrs, [[self._hp(self.ncell * z + 12 + i, grad) for i in range(n)]
+                                                   for z in range(self.ndir)], lambda a, _: ops._att_ptrs(self.att, a))
 
     def _drnn_listener_ptrs(self, grad):
-        return ops._ptr_structs(_lib.DrnnListenerPtrs, [[self._hp(2 * self.ncell + 6 + 4 * z + j, grad) for j in range(4)]
-                                                        for z in range(2)])
+        return ops._ptr_structs(_lib.DrnnListenerPtrs, [[self._hp(self.ndir * self.ncell + 6 + 4 * z + j, grad) for j in range(4)]
+                                                        for z in range(self.ndir)])
 
     def step(self, batch, train=True):
         """batch: acoustic/visual/text (S,B,.), qmask (S,B,P) one-hot (zero rows on padding; 1 <= P <= ops.DRNN_MAX_PARTIES),
@@ -1399,8 +1413,8 @@ class DrnnEngine(_NetRunner):
         if not self.head.in_place():
             raise RuntimeError("the DialogueRNN head was re-allocated after the engine was built: build DrnnEngine after the last .to()")
         P, st_ = ops._ptr, ops._stream
-        T, Dm, He, D2, Cn = S * B, self.Dm, self.He, 2 * self.He, self.n_classes
-        f = self._f
+        T, Dm, He, D2, Cn = S * B, self.Dm, self.He, self.D2, self.n_classes
+        f, nd, causal = self._f, self.ndir, self.causal
         self._adds = 0
         self._base_add = self.rng.next_add(10)          # 3 generators x (encoder, head), the recurrence, the head's dropouts
         a_rec, a_head = self._base_add + 6, self._base_add + 7
@@ -1418,11 +1432,12 @@ class DrnnEngine(_NetRunner):
         self._key_len = lens if self.mask_padding else None
         spk_f = torch.argmax(qmask, 2).to(torch.int32).contiguous()
         mval_f = qmask.max(2).values.contiguous()
-        t_idx = torch.arange(S, device=self.dev).unsqueeze(1)
-        src = (lens.to(torch.long).unsqueeze(0) - 1 - t_idx).clamp(min=0)
-        valid = (t_idx < lens.unsqueeze(0))
-        spk_b = (spk_f.gather(0, src) * valid).to(torch.int32).contiguous()
-        mval_b = (mval_f.gather(0, src) * valid).contiguous()
+        if not causal:
+            t_idx = torch.arange(S, device=self.dev).unsqueeze(1)
+            src = (lens.to(torch.long).unsqueeze(0) - 1 - t_idx).clamp(min=0)
+            valid = (t_idx < lens.unsqueeze(0))
+            spk_b = (spk_f.gather(0, src) * valid).to(torch.int32).contiguous()
+            mval_b = (mval_f.gather(0, src) * valid).contiguous()
 
         # ---- three generators, concurrently
         keys = ("acoustic", "visual", "text")                        # model.py:1521-1523
@@ -1450,24 +1465,37 @@ class DrnnEngine(_NetRunner):
         st = st_()
         _lib.call("ganffn_add3", P(self.pass_G["acoustic"].out), P(self.pass_G["visual"].out), P(self.pass_G["text"].out),
                   P(f["fusion"]), C.c_int64(T * Dm), st)
-        _lib.call("ganffn_seq_reverse", P(f["fusion"]), P(lens), P(f["rev_U"]), S, B, Dm, 0, st)
-        # ---- the recurrence, both directions
+        if not causal:
+            _lib.call("ganffn_seq_reverse", P(f["fusion"]), P(lens), P(f["rev_U"]), S, B, Dm, 0, st)
+        # ---- the recurrence, both directions (a causal net: the forward one alone)
         cfg = self.cfg_train if train else self.cfg_eval
-        arr = lambda ts: (C.c_void_p * 2)(*[t.data_ptr() for t in ts])
-        U_, spk_, mval_ = arr([f["fusion"], f["rev_U"]]), arr([spk_f, spk_b]), arr([mval_f, mval_b])
+        arr = lambda ts: (C.c_void_p * nd)(*[t.data_ptr() for t in ts[:nd]])
+        U_, spk_, mval_ = arr([f["fusion"], f["rev_U"]]), arr([spk_f, None if causal else spk_b]), arr([mval_f, None if causal else mval_b])
         e_, al_, sv_, ws_ = arr([f["e_f"], f["e_b"]]), arr([f["alpha_f"], f["alpha_b"]]), arr([f["saved_f"], f["saved_b"]]), arr([f["ws_f"], f["ws_b"]])
         Pp, APp = self._drnn_ptrs(False), self._drnn_att_ptrs(False)
         LPp = self._drnn_listener_ptrs(False) if self.listener else None
         parties = self._shape[2]
-        ops.drnn_fwd_raw(cfg, self.acfg, parties, 2, U_, spk_, mval_, Pp, LPp, APp, e_, al_, sv_, ws_, P(rng), a_rec)
+        ops.drnn_fwd_raw(cfg, self.acfg, parties, nd, U_, spk_, mval_, Pp, LPp, APp, e_, al_, sv_, ws_, P(rng), a_rec)
         # ---- head: emotions -> matching attention -> linear/relu/dropout -> classes -> loss
         tr = 1 if train else 0
-        _lib.call("ganffn_drnn_join_fwd", P(f["e_f"]), P(f["e_b"]), P(lens), P(f["emotions"]), S, B, He, C.c_float(self.p_join),
-                  C.c_uint32(SITE_JOIN_F), C.c_uint32(SITE_JOIN_B), P(rng), C.c_uint64(a_head), tr, st)
-        w_t, b_t, w_l, b_l, w_s, b_s = (self._hp(2 * self.ncell + j) for j in range(6))
-        ops.linear_fwd_raw(f["emotions"], w_t, b_t, f["xq"], T, D2, D2)
-        _lib.call("ganffn_general2_attention_fwd", P(f["xq"]), P(f["emotions"]), P(umask), P(f["att"]), P(f["alpha2"]), P(f["tanh_s"]),
-                  S, B, D2, st)
+        w_t, b_t, w_l, b_l, w_s, b_s = (self._hp(nd * self.ncell + j) for j in range(6))
+        if causal:
+            # the join of one direction is dropout_rec on e_f alone (SITE_JOIN_F); eval: the emotions are e_f itself
+            em = f["emotions"] if train else f["e_f"]
+            if train:
+                _lib.call("ganffn_dropout", P(f["e_f"]), P(em), T, He, C.c_float(self.p_join), C.c_uint32(SITE_JOIN_F), P(rng),
+                          C.c_uint64(a_head), st)
+        else:
+            em = f["emotions"]
+            _lib.call("ganffn_drnn_join_fwd", P(f["e_f"]), P(f["e_b"]), P(lens), P(em), S, B, He, C.c_float(self.p_join),
+                      C.c_uint32(SITE_JOIN_F), C.c_uint32(SITE_JOIN_B), P(rng), C.c_uint64(a_head), tr, st)
+        ops.linear_fwd_raw(em, w_t, b_t, f["xq"], T, D2, D2)
+        if causal:
+            _lib.call("ganffn_general2_attention_fwd_mask", P(f["xq"]), P(em), P(umask), C.c_uint32(ops.ATTN_CAUSAL), P(f["att"]),
+                      P(f["alpha2"]), P(f["tanh_s"]), S, B, D2, st)
+        else:
+            _lib.call("ganffn_general2_attention_fwd", P(f["xq"]), P(em), P(umask), P(f["att"]), P(f["alpha2"]), P(f["tanh_s"]),
+                      S, B, D2, st)
         _lib.call("ganffn_ffn_linear1_fwd", P(f["att"]), P(w_l), P(b_l), P(f["hidden"]), T, D2, self.Dh2, C.c_float(self.p_hid),
                   C.c_uint32(SITE_HIDDEN), P(rng), C.c_uint64(a_head), tr, st)
         ops.linear_fwd_raw(f["hidden"], w_s, b_s, f["logits"], T, self.Dh2, Cn)
@@ -1478,25 +1506,34 @@ class DrnnEngine(_NetRunner):
             return self.loss, log_prob
         # ---- backward through the head
         self.h_grad.zero_()
-        g_t, gb_t, g_l, gb_l, g_s, gb_s = (self._hp(2 * self.ncell + j, True) for j in range(6))
+        g_t, gb_t, g_l, gb_l, g_s, gb_s = (self._hp(nd * self.ncell + j, True) for j in range(6))
         ops.linear_bwd_raw(f["dlogits"], f["hidden"], w_s, f["d_hidden"], g_s, gb_s, T, self.Dh2, Cn, f["lin_ws"])
         mscale = 1.0 / (1.0 - self.p_hid) if self.p_hid > 0 else 1.0
         _lib.call("ganffn_mask_pos_inplace", P(f["d_hidden"]), P(f["hidden"]), C.c_float(mscale), C.c_int64(T * self.Dh2), st)
         ops.linear_bwd_raw(f["d_hidden"], f["att"], w_l, f["d_att"], g_l, gb_l, T, D2, self.Dh2, f["lin_ws"])
-        _lib.call("ganffn_general2_attention_bwd", P(f["d_att"]), P(f["xq"]), P(f["emotions"]), P(umask), P(f["alpha2"]), P(f["tanh_s"]),
-                  P(f["du"]), P(f["d_xq"]), P(f["d_mem"]), S, B, D2, st)
-        ops.linear_bwd_raw(f["d_xq"], f["emotions"], w_t, f["d_em"], g_t, gb_t, T, D2, D2, f["lin_ws"])
+        if causal:
+            _lib.call("ganffn_general2_attention_bwd_mask", P(f["d_att"]), P(f["xq"]), P(em), P(umask), C.c_uint32(ops.ATTN_CAUSAL),
+                      P(f["alpha2"]), P(f["tanh_s"]), P(f["du"]), P(f["d_xq"]), P(f["d_mem"]), S, B, D2, st)
+        else:
+            _lib.call("ganffn_general2_attention_bwd", P(f["d_att"]), P(f["xq"]), P(em), P(umask), P(f["alpha2"]), P(f["tanh_s"]),
+                      P(f["du"]), P(f["d_xq"]), P(f["d_mem"]), S, B, D2, st)
+        ops.linear_bwd_raw(f["d_xq"], em, w_t, f["d_em"], g_t, gb_t, T, D2, D2, f["lin_ws"])
         f["d_em"][:T * D2].add_(f["d_mem"][:T * D2])          # memory path of the attention + its transform(mem) path
-        _lib.call("ganffn_drnn_join_bwd", P(f["d_em"]), P(lens), P(f["d_e_f"]), P(f["d_e_b"]), S, B, He, C.c_float(self.p_join),
-                  C.c_uint32(SITE_JOIN_F), C.c_uint32(SITE_JOIN_B), P(rng), C.c_uint64(a_head), tr, st)
+        if causal:
+            _lib.call("ganffn_dropout", P(f["d_em"]), P(f["d_e_f"]), T, He, C.c_float(self.p_join), C.c_uint32(SITE_JOIN_F), P(rng),
+                      C.c_uint64(a_head), st)
+        else:
+            _lib.call("ganffn_drnn_join_bwd", P(f["d_em"]), P(lens), P(f["d_e_f"]), P(f["d_e_b"]), S, B, He, C.c_float(self.p_join),
+                      C.c_uint32(SITE_JOIN_F), C.c_uint32(SITE_JOIN_B), P(rng), C.c_uint64(a_head), tr, st)
         # ---- the recurrence backward (weight gradients accumulate into the zeroed head slab)
         Gp = self._drnn_ptrs(True)
         de_, dU_ = arr([f["d_e_f"], f["d_e_b"]]), arr([f["dU_f"], f["dU_b"]])
-        ops.drnn_bwd_raw(cfg, self.acfg, parties, 2, de_, U_, spk_, mval_, Pp, LPp, APp, Gp,
+        ops.drnn_bwd_raw(cfg, self.acfg, parties, nd, de_, U_, spk_, mval_, Pp, LPp, APp, Gp,
                          self._drnn_listener_ptrs(True) if self.listener else None, self._drnn_att_ptrs(True), dU_, al_, sv_, ws_,
                          P(rng), a_rec)
-        # d fusion = dU_f + reverse(dU_b)
-        _lib.call("ganffn_seq_reverse", P(f["dU_b"]), P(lens), P(f["dU_f"]), S, B, Dm, 1, st)
+        # d fusion = dU_f + reverse(dU_b); a causal net: dU_f itself
+        if not causal:
+            _lib.call("ganffn_seq_reverse", P(f["dU_b"]), P(lens), P(f["dU_f"]), S, B, Dm, 1, st)
         d_fusion = f["dU_f"][:T * Dm].view(S, B, Dm)
         # ---- head optimizer step (its all-reduce, when data-parallel, runs beside the generators' backward)
         # (in-line mode: on this stream — a communicator never carries two collectives at once, and the generators' all-reduces

@@ -570,18 +570,21 @@ class LogSoftmaxFn(torch.autograd.Function):
 class General2AttnFn(torch.autograd.Function):
     """masked general2 matching attention with every time step as the query (include/ganffn.h, N2):
     (x = transform(mem) (S,B,D), mem (S,B,D), mask (B,S)) -> (att (S,B,D), alpha (B,S,S)); alpha is an inspection
-    output (the reference returns it to the caller, nothing differentiates through it)."""
+    output (the reference returns it to the caller, nothing differentiates through it).  causal=True (the GANFFN_ATTN_CAUSAL
+    flag of ganffn_general2_attention_*_mask): query step t attends to memory steps j <= t only, alpha is exactly 0 above the
+    diagonal."""
 
     @staticmethod
-    def forward(ctx, x, mem, mask):
+    def forward(ctx, x, mem, mask, causal=False):
         _need_gpu(x, mem)
         xc, mc, kc = _f32c(x), _f32c(mem), _f32c(mask)
         S, B, D = mc.shape
         att = torch.empty_like(mc)
         alpha = torch.empty(B, S, S, device=mc.device, dtype=torch.float32)
         ts = torch.empty(B, S, S, device=mc.device, dtype=torch.float32)
-        _lib.call("ganffn_general2_attention_fwd", _ptr(xc), _ptr(mc), _ptr(kc), _ptr(att), _ptr(alpha), _ptr(ts), S, B, D,
-                  _stream())
+        ctx.flags = ATTN_CAUSAL if causal else 0
+        _lib.call("ganffn_general2_attention_fwd_mask", _ptr(xc), _ptr(mc), _ptr(kc), C.c_uint32(ctx.flags), _ptr(att), _ptr(alpha),
+                  _ptr(ts), S, B, D, _stream())
         ctx.save_for_backward(xc, mc, kc, alpha, ts)
         ctx.mark_non_differentiable(alpha)
         return att, alpha
@@ -593,9 +596,9 @@ class General2AttnFn(torch.autograd.Function):
         g = _f32c(d_att)
         du = torch.empty_like(alpha)
         dx, dm = torch.empty_like(mc), torch.empty_like(mc)
-        _lib.call("ganffn_general2_attention_bwd", _ptr(g), _ptr(xc), _ptr(mc), _ptr(kc), _ptr(alpha), _ptr(ts), _ptr(du),
-                  _ptr(dx), _ptr(dm), S, B, D, _stream())
-        return dx, dm, None
+        _lib.call("ganffn_general2_attention_bwd_mask", _ptr(g), _ptr(xc), _ptr(mc), _ptr(kc), C.c_uint32(ctx.flags), _ptr(alpha),
+                  _ptr(ts), _ptr(du), _ptr(dx), _ptr(dm), S, B, D, _stream())
+        return dx, dm, None, None
 
 
 # ----------------------------------------------------------------------------------------------

@@ -600,6 +600,20 @@ int ganffn_attention_fwd_mask(const float* qkv, float* o, float* lse, uint32_t* 
 int ganffn_attention_bwd_mask(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keep,
                               const int32_t* key_len, uint32_t flags, float* d_qkv, int S, int B, int E, int H, float p,
                               uint32_t site, const uint64_t* rng, uint64_t rng_offset_add, void* stream);
+/* The general2 matching attention (N2 above) with a flags word after mask.  GANFFN_ATTN_CAUSAL: query step t attends to memory
+ * steps j <= t only, a_tj = e^{s_tj} m_j [j <= t] / sum_{k <= t} e^{s_tk} m_k — MatchingAttention.forward(M[:t+1], M[t],
+ * umask[:, :t+1]) for every t, the second attention of dialogue_rnn.UniModel.  alpha, tanh_s and du_ws are written completely on
+ * every call, exact zeros at j > t (and alpha and du_ws at masked j); a query row at or past its dialogue's end attends over the
+ * dialogue's real steps.  The causal kernels skip the work above the diagonal: a block of 16 query steps reads memory rows
+ * j < min(S, t0 + 16) only, memory step j sums over t >= j only; every output element keeps a fixed summation order, no atomics.
+ * flags == 0 is exactly the call above (same launches, same bits: the two entry points above forward here with 0); a bit other
+ * than GANFFN_ATTN_CAUSAL, or a null pointer, is refused with a message before any launch.  The forward and the backward of one
+ * pass must be given the same flags. */
+int ganffn_general2_attention_fwd_mask(const float* x, const float* mem, const float* mask, uint32_t flags, float* att,
+                                       float* alpha, float* tanh_s, int S, int B, int D, void* stream);
+int ganffn_general2_attention_bwd_mask(const float* d_att, const float* x, const float* mem, const float* mask, uint32_t flags,
+                                       const float* alpha, const float* tanh_s, float* du_ws, float* dx, float* dmem, int S,
+                                       int B, int D, void* stream);
 int ganffn_encoder_fwd_mask(const ganffn_enc_cfg* cfg, const int32_t* key_len, uint32_t flags, const float* x_in,
                             const float* pe, const float* params, float* out, float* saved, float* workspace,
                             const uint64_t* rng, uint64_t rng_offset_add, void* stream);
