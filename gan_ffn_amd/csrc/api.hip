@@ -331,9 +331,10 @@ static int encoder_fwd_walk(const EncCall& k, const Mode md, const FwdSeg& s0, c
             GF_TRY(launch_stream_attention(v0 + so.qkv, sa->cache + (int64_t)l * sa->layer_stride, sa->slot, sa->pos, v0 + so.attn_o, T,
                                            sa->capacity, sa->max_len, E, H, st));
         } else {
-            const AttnFwdSeg1 a1{v1 + so.qkv, v1 + so.attn_o, v1 + so.lse, keep_words(t1, v1), train1};
-            GF_TRY(launch_attention_fwd(v0 + so.qkv, v0 + so.attn_o, v0 + so.lse, keep_words(s0, v0), S, B, E, H, c->p_enc, site + 0, rng,
-                                        add, train0, st, s1 ? &a1 : nullptr, key_len, flags));
+            AttnCall a = attn_call(S, B, E, H, c->p_enc, site + 0, rng, add, st).mask(key_len, flags);
+            a.forward(AttnSeg{v0 + so.qkv, v0 + so.attn_o, v0 + so.lse, keep_words(s0, v0), train0});
+            if (s1) a.pair(AttnSeg{v1 + so.qkv, v1 + so.attn_o, v1 + so.lse, keep_words(t1, v1), train1});
+            GF_TRY(attention_fwd(a));
         }
         // out-proj, residual + dropout + LN1
         if (rc) {
@@ -666,8 +667,8 @@ static int encoder_bwd(const EncCall& k) {
         if (G) tn[ntn++] = TnDesc{dyB, E, sv + so.attn_o, E, G + lo.out_w, E, G + lo.out_b, E, E, T};
         if (!rc) GF_TRY(launch_gemm_nn(dyB, E, P + lo.out_w, E, d_attn, E, T, E, E, EPI_NONE, none, st));
         // attention core backward
-        GF_TRY(launch_attention_bwd(sv + so.qkv, sv + so.attn_o, sv + so.lse, d_attn, reinterpret_cast<const uint32_t*>(sv + so.keep), d_qkv, S, B, E,
-                                    H, c->p_enc, site + 0, rng, add, train, st, k.key_len, k.flags));
+        GF_TRY(attention_bwd(attn_call(S, B, E, H, c->p_enc, site + 0, rng, add, st).mask(k.key_len, k.flags)
+                                 .backward(sv + so.qkv, sv + so.attn_o, sv + so.lse, reinterpret_cast<const uint32_t*>(sv + so.keep), d_attn, d_qkv, train)));
         // in-proj wgrad + dgrad; dX[l] = d_qkv W_in + dz1
         if (G) tn[ntn++] = TnDesc{d_qkv, 3 * E, Xl, E, G + lo.in_w, E, G + lo.in_b, 3 * E, E, T};
         if (ntn == 40 || (l == layer_lo && ntn > 0)) {
@@ -1003,41 +1004,41 @@ extern "C" int ganffn_gemm_tn_grouped(int n, const float* const* At, const float
 }
 extern "C" int ganffn_attention_fwd(const float* qkv, float* o, float* lse, int S, int B, int E, int H, float p, uint32_t site,
                                     const uint64_t* rng, uint64_t add, void* stream) {
-    return launch_attention_fwd(qkv, o, lse, nullptr, S, B, E, H, p, site, rng, add, 1, (hipStream_t)stream);
+    return attention_fwd(attn_call(S, B, E, H, p, site, rng, add, (hipStream_t)stream).forward(AttnSeg{qkv, o, lse, nullptr, 1}));
 }
 extern "C" int64_t ganffn_attention_keep_words(int B, int H) { return (int64_t)B * H * ATTN_KEEP_WORDS; }
 extern "C" int ganffn_attention_fwd_keep(const float* qkv, float* o, float* lse, uint32_t* keep, int S, int B, int E, int H, float p,
                                          uint32_t site, const uint64_t* rng, uint64_t add, void* stream) {
-    return launch_attention_fwd(qkv, o, lse, keep, S, B, E, H, p, site, rng, add, 1, (hipStream_t)stream);
+    return attention_fwd(attn_call(S, B, E, H, p, site, rng, add, (hipStream_t)stream).forward(AttnSeg{qkv, o, lse, keep, 1}));
 }
 extern "C" int ganffn_attention_bwd_keep(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keep,
                                          float* d_qkv, int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng,
                                          uint64_t add, void* stream) {
-    return launch_attention_bwd(qkv, o, lse, d_o, keep, d_qkv, S, B, E, H, p, site, rng, add, 1, (hipStream_t)stream);
+    return attention_bwd(attn_call(S, B, E, H, p, site, rng, add, (hipStream_t)stream).backward(qkv, o, lse, keep, d_o, d_qkv, 1));
 }
 extern "C" int ganffn_attention_bwd(const float* qkv, const float* o, const float* lse, const float* d_o, float* d_qkv, int S,
                                     int B, int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add,
                                     void* stream) {
-    return launch_attention_bwd(qkv, o, lse, d_o, nullptr, d_qkv, S, B, E, H, p, site, rng, add, 1, (hipStream_t)stream);
+    return attention_bwd(attn_call(S, B, E, H, p, site, rng, add, (hipStream_t)stream).backward(qkv, o, lse, nullptr, d_o, d_qkv, 1));
 }
 // the attention pair with per-dialogue key lengths (keep may be NULL; key_len NULL = the pairs above)
 extern "C" int ganffn_attention_fwd_len(const float* qkv, float* o, float* lse, uint32_t* keep, const int32_t* key_len, int S, int B,
                                         int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add, void* stream) {
-    return launch_attention_fwd(qkv, o, lse, keep, S, B, E, H, p, site, rng, add, 1, (hipStream_t)stream, nullptr, key_len);
+    return attention_fwd(attn_call(S, B, E, H, p, site, rng, add, (hipStream_t)stream).mask(key_len, 0).forward(AttnSeg{qkv, o, lse, keep, 1}));
 }
 extern "C" int ganffn_attention_bwd_len(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keep,
                                         const int32_t* key_len, float* d_qkv, int S, int B, int E, int H, float p, uint32_t site,
                                         const uint64_t* rng, uint64_t add, void* stream) {
-    return launch_attention_bwd(qkv, o, lse, d_o, keep, d_qkv, S, B, E, H, p, site, rng, add, 1, (hipStream_t)stream, key_len);
+    return attention_bwd(attn_call(S, B, E, H, p, site, rng, add, (hipStream_t)stream).mask(key_len, 0).backward(qkv, o, lse, keep, d_o, d_qkv, 1));
 }
 // the same pair with a flags word (GANFFN_ATTN_CAUSAL; 0 = the _len pair, an unknown bit is refused before any launch)
 extern "C" int ganffn_attention_fwd_mask(const float* qkv, float* o, float* lse, uint32_t* keep, const int32_t* key_len, uint32_t flags,
                                          int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add,
                                          void* stream) {
-    return launch_attention_fwd(qkv, o, lse, keep, S, B, E, H, p, site, rng, add, 1, (hipStream_t)stream, nullptr, key_len, flags);
+    return attention_fwd(attn_call(S, B, E, H, p, site, rng, add, (hipStream_t)stream).mask(key_len, flags).forward(AttnSeg{qkv, o, lse, keep, 1}));
 }
 extern "C" int ganffn_attention_bwd_mask(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keep,
                                          const int32_t* key_len, uint32_t flags, float* d_qkv, int S, int B, int E, int H, float p,
                                          uint32_t site, const uint64_t* rng, uint64_t add, void* stream) {
-    return launch_attention_bwd(qkv, o, lse, d_o, keep, d_qkv, S, B, E, H, p, site, rng, add, 1, (hipStream_t)stream, key_len, flags);
+    return attention_bwd(attn_call(S, B, E, H, p, site, rng, add, (hipStream_t)stream).mask(key_len, flags).backward(qkv, o, lse, keep, d_o, d_qkv, 1));
 }

@@ -410,7 +410,7 @@ __global__ __launch_bounds__(64 * NT) void attention_bwd_kernel(const float* __r
     const int n = LEN ? attn_key_len(key_len, b, g.S) : g.S;
     const size_t HM = (size_t)g.ROWS * g.LDH + 64;
     // All four operand matrices stay resident in LDS when they fit (one global-load round trip, one barrier fewer);
-    // otherwise dO overwrites Q and the re-loaded Q overwrites V (ALIAS).  Same rule on the host: launch_attention_bwd().
+    // otherwise dO overwrites Q and the re-loaded Q overwrites V (ALIAS).  Same rule on the host: attention_bwd().
     constexpr bool ALIAS = (HD == 0) || (HD * NT > 192);
     float* RA = smem;                        // scaled Q   (ALIAS: later dO)
     float* RB = RA + HM;                     // K
@@ -571,64 +571,63 @@ __global__ __launch_bounds__(64 * NT) void attention_bwd_kernel(const float* __r
     }
 }
 
-static int check_attn(int S, int B, int E, int H) {
-    GF_CHECK_ARG(S >= 1 && S <= GANFFN_MAX_SEQ, "attention: S=%d out of range [1,%d]", S, GANFFN_MAX_SEQ);
-    GF_CHECK_ARG(B >= 1 && H >= 1 && E % H == 0, "attention: bad B=%d E=%d H=%d", B, E, H);
-    const int hd = E / H;
+// ------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------
+// Every refusal of the attention family, both kernel families and both directions: once per call, before dispatch, so that a
+// refused call launches and writes nothing.
+static int check_attn(const AttnCall& k, bool bwd) {
+    const char* what = bwd ? "attention_bwd" : "attention_fwd";
+    GF_CHECK_ARG(k.S >= 1 && k.S <= GANFFN_MAX_SEQ, "attention: S=%d out of range [1,%d]", k.S, GANFFN_MAX_SEQ);
+    GF_CHECK_ARG(k.B >= 1 && k.H >= 1 && k.E % k.H == 0, "attention: bad B=%d E=%d H=%d", k.B, k.E, k.H);
+    const int hd = k.E / k.H;
     GF_CHECK_ARG((hd & 1) == 0 && hd <= 64, "attention: head_dim=%d must be even and <= 64", hd);
-    GF_CHECK_ARG((long)B * H * 28 * 128 < (1l << 32), "attention: B*H too large for the Philox counter");
+    GF_CHECK_ARG((long)k.B * k.H * 28 * 128 < (1l << 32), "attention: B*H too large for the Philox counter");
+    GF_CHECK_ARG((k.flags & ~GANFFN_ATTN_CAUSAL) == 0, "%s: unknown flag bits 0x%x", what, k.flags & ~GANFFN_ATTN_CAUSAL);
+    if (bwd) {
+        GF_CHECK_ARG(k.qkv && k.d_o && k.d_qkv, "attention_bwd: null pointer");
+        GF_CHECK_ARG(!(k.train && k.p > 0.f) || k.rng, "attention_bwd: rng required when dropout is active");
+        GF_CHECK_ARG(!attn16_supported(k.E, k.H, k.S) || (k.o && k.lse),
+                     "attention_bwd: head_dim %d needs the forward's output and log-sum-exp", hd);
+    } else {
+        GF_CHECK_ARG(k.seg[0].qkv && k.seg[0].o, "attention_fwd: null pointer");
+        GF_CHECK_ARG(k.nseg != 2 || (k.seg[1].qkv && k.seg[1].o), "attention_fwd: bad second batch");
+        GF_CHECK_ARG(!((k.seg[0].train || k.seg[1].train) && k.p > 0.f) || k.rng, "attention_fwd: rng required when dropout is active");
+    }
     return 0;
 }
 
+// The template flags of the 32-row kernels from the call: f(LEN, CAUSAL).  The causal kernels are instantiated only in the form
+// with lengths (a null key_len reads as S in the kernel).
+template <class F>
+static int with_mask(const AttnCall& k, F&& f) {
+    if (k.causal()) return f(std::true_type{}, std::true_type{});
+    return with_flag(k.key_len != nullptr, [&](auto len) { return f(len, std::false_type{}); });
+}
+
 template <int HD, int NT>
-static int launch_fwd_t(const float* qkv, float* o, const AttnGeom& g, size_t lds, float p, uint32_t site, const uint64_t* rng,
-                        uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1, const int32_t* key_len, bool causal) {
-    if (causal && seg1) {      // both segments under the mask; a null key_len reads as S in the kernel
-        GF_TRY((lds_optin<attention_fwd_kernel<HD, NT, true, true, true>>(lds, "attention_fwd")));
-        hipLaunchKernelGGL((attention_fwd_kernel<HD, NT, true, true, true>), dim3(2 * g.B * g.H), dim3(64 * NT), lds, st, qkv, o, g, p,
-                           site, rng, add, train, seg1->qkv, seg1->o, seg1->train, key_len);
-    } else if (causal) {
-        GF_TRY((lds_optin<attention_fwd_kernel<HD, NT, false, true, true>>(lds, "attention_fwd")));
-        hipLaunchKernelGGL((attention_fwd_kernel<HD, NT, false, true, true>), dim3(g.B * g.H), dim3(64 * NT), lds, st, qkv, o, g, p, site,
-                           rng, add, train, (const float*)nullptr, (float*)nullptr, 0, key_len);
-    } else if (seg1 && key_len) {
-        GF_TRY((lds_optin<attention_fwd_kernel<HD, NT, true, true>>(lds, "attention_fwd")));
-        hipLaunchKernelGGL((attention_fwd_kernel<HD, NT, true, true>), dim3(2 * g.B * g.H), dim3(64 * NT), lds, st, qkv, o, g, p, site,
-                           rng, add, train, seg1->qkv, seg1->o, seg1->train, key_len);
-    } else if (seg1) {
-        GF_TRY((lds_optin<attention_fwd_kernel<HD, NT, true>>(lds, "attention_fwd")));
-        hipLaunchKernelGGL((attention_fwd_kernel<HD, NT, true>), dim3(2 * g.B * g.H), dim3(64 * NT), lds, st, qkv, o, g, p, site, rng,
-                           add, train, seg1->qkv, seg1->o, seg1->train, (const int32_t*)nullptr);
-    } else if (key_len) {
-        GF_TRY((lds_optin<attention_fwd_kernel<HD, NT, false, true>>(lds, "attention_fwd")));
-        hipLaunchKernelGGL((attention_fwd_kernel<HD, NT, false, true>), dim3(g.B * g.H), dim3(64 * NT), lds, st, qkv, o, g, p, site, rng,
-                           add, train, (const float*)nullptr, (float*)nullptr, 0, key_len);
-    } else {
-        GF_TRY((lds_optin<attention_fwd_kernel<HD, NT>>(lds, "attention_fwd")));
-        hipLaunchKernelGGL((attention_fwd_kernel<HD, NT>), dim3(g.B * g.H), dim3(64 * NT), lds, st, qkv, o, g, p, site, rng, add, train,
-                           (const float*)nullptr, (float*)nullptr, 0, key_len);
-    }
-    GF_LAUNCH_CHECK();
-    return 0;
+static int launch_fwd_t(const AttnCall& k, const AttnGeom& g, size_t lds) {
+    auto launch = [&](auto pair, auto len, auto causal) -> int {
+        constexpr bool PAIR = decltype(pair)::value, LEN = decltype(len)::value, CAUSAL = decltype(causal)::value;
+        const AttnSeg &s0 = k.seg[0], &s1 = k.seg[1];      // without a second segment s1 is null / 0
+        GF_TRY((lds_optin<attention_fwd_kernel<HD, NT, PAIR, LEN, CAUSAL>>(lds, "attention_fwd")));
+        hipLaunchKernelGGL((attention_fwd_kernel<HD, NT, PAIR, LEN, CAUSAL>), dim3((PAIR ? 2 : 1) * g.B * g.H), dim3(64 * NT), lds, k.st,
+                           s0.qkv, s0.o, g, k.p, k.site, k.rng, k.add, s0.train, s1.qkv, s1.o, s1.train, k.key_len);
+        GF_LAUNCH_CHECK();
+        return 0;
+    };
+    return with_flag(k.nseg == 2, [&](auto pair) { return with_mask(k, [&](auto len, auto causal) { return launch(pair, len, causal); }); });
 }
 template <int HD, int NT>
-static int launch_bwd_t(const float* qkv, const float* d_o, float* d_qkv, const AttnGeom& g, size_t lds, float p, uint32_t site,
-                        const uint64_t* rng, uint64_t add, int train, hipStream_t st, const int32_t* key_len, bool causal) {
-    if (causal) {
-        GF_TRY((lds_optin<attention_bwd_kernel<HD, NT, true, true>>(lds, "attention_bwd")));
-        hipLaunchKernelGGL((attention_bwd_kernel<HD, NT, true, true>), dim3(g.B * g.H), dim3(64 * NT), lds, st, qkv, d_o, d_qkv, g, p,
-                           site, rng, add, train, key_len);
-    } else if (key_len) {
-        GF_TRY((lds_optin<attention_bwd_kernel<HD, NT, true>>(lds, "attention_bwd")));
-        hipLaunchKernelGGL((attention_bwd_kernel<HD, NT, true>), dim3(g.B * g.H), dim3(64 * NT), lds, st, qkv, d_o, d_qkv, g, p, site,
-                           rng, add, train, key_len);
-    } else {
-        GF_TRY((lds_optin<attention_bwd_kernel<HD, NT>>(lds, "attention_bwd")));
-        hipLaunchKernelGGL((attention_bwd_kernel<HD, NT>), dim3(g.B * g.H), dim3(64 * NT), lds, st, qkv, d_o, d_qkv, g, p, site, rng,
-                           add, train, key_len);
-    }
-    GF_LAUNCH_CHECK();
-    return 0;
+static int launch_bwd_t(const AttnCall& k, const AttnGeom& g, size_t lds) {
+    return with_mask(k, [&](auto len, auto causal) -> int {
+        constexpr bool LEN = decltype(len)::value, CAUSAL = decltype(causal)::value;
+        GF_TRY((lds_optin<attention_bwd_kernel<HD, NT, LEN, CAUSAL>>(lds, "attention_bwd")));
+        hipLaunchKernelGGL((attention_bwd_kernel<HD, NT, LEN, CAUSAL>), dim3(g.B * g.H), dim3(64 * NT), lds, k.st, k.qkv, k.d_o, k.d_qkv, g,
+                           k.p, k.site, k.rng, k.add, k.train, k.key_len);
+        GF_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 #define NT_SWITCH(FN, HD, ...)                                  \
@@ -639,41 +638,28 @@ static int launch_bwd_t(const float* qkv, const float* d_o, float* d_qkv, const 
         default: return FN<HD, 4>(__VA_ARGS__);                 \
     }
 
-int launch_attention_fwd(const float* qkv, float* o, float* lse, uint32_t* keep, int S, int B, int E, int H, float p, uint32_t site,
-                         const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1,
-                         const int32_t* key_len, uint32_t flags) {
-    GF_TRY(check_attn(S, B, E, H));
-    GF_CHECK_ARG((flags & ~GANFFN_ATTN_CAUSAL) == 0, "attention_fwd: unknown flag bits 0x%x", flags & ~GANFFN_ATTN_CAUSAL);
-    const bool causal = (flags & GANFFN_ATTN_CAUSAL) != 0;
-    GF_CHECK_ARG(qkv && o, "attention_fwd: null pointer");
-    GF_CHECK_ARG(!seg1 || (seg1->qkv && seg1->o), "attention_fwd: bad second batch");
-    GF_CHECK_ARG(!((train || (seg1 && seg1->train)) && p > 0.f) || rng, "attention_fwd: rng required when dropout is active");
-    if (attn16_supported(E, H, S)) return launch_attn16_fwd(qkv, o, lse, keep, S, B, E, H, p, site, rng, add, train, st, seg1, key_len, flags);
-    const AttnGeom g = make_geom(S, B, E, H);
+int attention_fwd(const AttnCall& k) {
+    GF_TRY(check_attn(k, false));
+    if (attn16_supported(k.E, k.H, k.S)) return k.causal() ? attn16_fwd<true>(k) : attn16_fwd<false>(k);
+    const AttnGeom g = make_geom(k.S, k.B, k.E, k.H);
     const size_t lds = 3 * hd_mat_floats(g) * sizeof(float);
     GF_CHECK_ARG(lds <= 160 * 1024, "attention_fwd: LDS need %zu > 160 KiB", lds);
-    if (g.hd == 64) { NT_SWITCH(launch_fwd_t, 64, qkv, o, g, lds, p, site, rng, add, train, st, seg1, key_len, causal) }
-    if (g.hd == 60) { NT_SWITCH(launch_fwd_t, 60, qkv, o, g, lds, p, site, rng, add, train, st, seg1, key_len, causal) }
-    NT_SWITCH(launch_fwd_t, 0, qkv, o, g, lds, p, site, rng, add, train, st, seg1, key_len, causal)
+    if (g.hd == 64) { NT_SWITCH(launch_fwd_t, 64, k, g, lds) }
+    if (g.hd == 60) { NT_SWITCH(launch_fwd_t, 60, k, g, lds) }
+    NT_SWITCH(launch_fwd_t, 0, k, g, lds)
 }
 
-int launch_attention_bwd(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keep, float* d_qkv,
-                         int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train,
-                         hipStream_t st, const int32_t* key_len, uint32_t flags) {
-    GF_TRY(check_attn(S, B, E, H));
-    GF_CHECK_ARG((flags & ~GANFFN_ATTN_CAUSAL) == 0, "attention_bwd: unknown flag bits 0x%x", flags & ~GANFFN_ATTN_CAUSAL);
-    const bool causal = (flags & GANFFN_ATTN_CAUSAL) != 0;
-    GF_CHECK_ARG(qkv && d_o && d_qkv, "attention_bwd: null pointer");
-    GF_CHECK_ARG(!(train && p > 0.f) || rng, "attention_bwd: rng required when dropout is active");
-    if (attn16_supported(E, H, S)) return launch_attn16_bwd(qkv, o, lse, d_o, keep, d_qkv, S, B, E, H, p, site, rng, add, train, st, key_len, flags);
-    const AttnGeom g = make_geom(S, B, E, H);
+int attention_bwd(const AttnCall& k) {
+    GF_TRY(check_attn(k, true));
+    if (attn16_supported(k.E, k.H, k.S)) return k.causal() ? attn16_bwd<true>(k) : attn16_bwd<false>(k);
+    const AttnGeom g = make_geom(k.S, k.B, k.E, k.H);
     const int hdt = (g.hd == 60 || g.hd == 64) ? g.hd : 0;      // kernel template head_dim (0 = generic)
     const bool alias = hdt == 0 || hdt * g.NT > 192;            // == attention_bwd_kernel::ALIAS
     const size_t lds = ((alias ? 3 : 4) * hd_mat_floats(g) + ss_mat_floats(g)) * sizeof(float);
     GF_CHECK_ARG(lds <= 160 * 1024, "attention_bwd: LDS need %zu > 160 KiB", lds);
-    if (g.hd == 64) { NT_SWITCH(launch_bwd_t, 64, qkv, d_o, d_qkv, g, lds, p, site, rng, add, train, st, key_len, causal) }
-    if (g.hd == 60) { NT_SWITCH(launch_bwd_t, 60, qkv, d_o, d_qkv, g, lds, p, site, rng, add, train, st, key_len, causal) }
-    NT_SWITCH(launch_bwd_t, 0, qkv, d_o, d_qkv, g, lds, p, site, rng, add, train, st, key_len, causal)
+    if (g.hd == 64) { NT_SWITCH(launch_bwd_t, 64, k, g, lds) }
+    if (g.hd == 60) { NT_SWITCH(launch_bwd_t, 60, k, g, lds) }
+    NT_SWITCH(launch_bwd_t, 0, k, g, lds)
 }
 
 }  // namespace ganffn

@@ -26,7 +26,6 @@
 //     no reduction across waves, no atomics);  only dS crosses LDS once, for dQ = dS K.
 // Layout: qkv [T x 3E] packed q|k|v per token (t = s*B + b), head h = columns h*hd .. h*hd+hd-1; lse [B*H x S].
 #include "common.h"
-#include <type_traits>
 
 namespace ganffn {
 
@@ -725,7 +724,7 @@ __global__ __launch_bounds__(64 * NT) void attn16_bwd_kernel(const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------
-// host side
+// host side: the launches for a call that attention.hip has checked (check_attn) and attn16_supported() accepts
 // ------------------------------------------------------------------------------------------
 // head_dim 10 / 30: always.  head_dim 60 / 64: short sequences only — measured against attention.hip (tools/lab/attn_big.py,
 // B = 32): S = 33, hd 60: forward 17.1 -> 9.6 us, backward 30.4 -> 19.4 us; S = 94, hd 64: forward 17.2 -> 36.9 us
@@ -739,15 +738,21 @@ bool attn16_supported(int E, int H, int S) {
 }
 #endif
 // The CAUSAL instantiations live in a translation unit of their own: attention16_causal.hip is this file compiled with
-// GANFFN_A16_CAUSAL_TU, which keeps the causal launches (as launch_attn16_fwd_causal / _bwd_causal) and nothing else, and this
+// GANFFN_A16_CAUSAL_TU, which keeps the causal launches (attn16_fwd<true> / attn16_bwd<true>) and nothing else, and this
 // file without it keeps everything else.  Measured, not a matter of taste: with both in one module 52 of the 176 kernels without
 // the flag (the head_dim 10 backward among them) came out of hipcc with another schedule and register assignment than the
 // parent's, although their source had not changed; apart, all 176 are the parent's instruction for instruction.
 #ifdef GANFFN_A16_CAUSAL_TU
-#define A16_ENTRY(name) name##_causal
+constexpr bool A16_CAUSAL = true;
 #else
-#define A16_ENTRY(name) name
+constexpr bool A16_CAUSAL = false;
 #endif
+// The LEN flag of this unit's kernels: f(LEN).  The causal instantiations are LEN ones (a null key_len reads as S in the kernel).
+template <class F>
+static int with_len(const AttnCall& k, F&& f) {
+    if constexpr (A16_CAUSAL) return f(std::true_type{});
+    else return with_flag(k.key_len != nullptr, f);
+}
 
 // Hand the dropout keep bits from the forward to the backward (instead of re-evaluating the Philox calls there) only while
 // the launch leaves most CUs with ONE backward workgroup: measured (tools/lab/attn_ab.py, S = 94, head_dim 10, p = 0.1)
@@ -764,102 +769,60 @@ static size_t bwd_lds(int nt) {
 }
 
 template <int HD, int NT>
-static int launch16_fwd(const float* qkv, float* o, float* lse, uint32_t* keepw, int S, int B, int E, int H, float p, uint32_t site,
-                        const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1,
-                        const int32_t* key_len) {
+static int launch16_fwd(const AttnCall& k) {
     const size_t lds = fwd_lds<HD>(NT);
-    if (!attn16_use_keep(B, H)) keepw = nullptr;
-    if (seg1) {
-        // the workgroup cut and the keep-word rule are those of ONE batch of B dialogues: what a single launch would choose
-        Attn16Seg1 s1{seg1->qkv, seg1->o, seg1->lse, attn16_use_keep(B, H) ? seg1->keep : nullptr, seg1->train};
-#define GF_A16_FWD2(W, LEN, ...)                                                                                    \
-    {                                                                                                               \
-        GF_TRY((lds_optin<attn16_fwd_kernel<HD, NT, W, true, LEN, ##__VA_ARGS__>>(lds, "attention_fwd")));          \
-        hipLaunchKernelGGL((attn16_fwd_kernel<HD, NT, W, true, LEN, ##__VA_ARGS__>), dim3(2 * B * H * (NT / W)), dim3(64 * W), lds, st, qkv, o, lse, keepw, \
-                           S, B, E, H, p, site, rng, add, train, s1, B * H * (NT / W), key_len);                     \
-    }
-        const bool cut2 = (long)B * H < 512 && NT % 2 == 0 && NT > 2;
-#ifdef GANFFN_A16_CAUSAL_TU
-        // both segments causal: after the segment choice the kernel is the single-batch causal one (a null key_len reads as S)
-        if (cut2) GF_A16_FWD2((NT % 2 == 0 ? 2 : NT), true, true)
-        else GF_A16_FWD2(NT, true, true)
-#else
-        if (key_len) {
-            if (cut2) GF_A16_FWD2((NT % 2 == 0 ? 2 : NT), true)
-            else GF_A16_FWD2(NT, true)
-        } else {
-            if (cut2) GF_A16_FWD2((NT % 2 == 0 ? 2 : NT), false)
-            else GF_A16_FWD2(NT, false)
-        }
-#endif
-#undef GF_A16_FWD2
-        GF_LAUNCH_CHECK();
-        return 0;
-    }
+    // the workgroup cut and the keep-word rule are those of ONE batch of B dialogues: what a single launch would choose
+    const bool keep = attn16_use_keep(k.B, k.H);
     // query tiles per workgroup: measured at hd = 10, S = 94 (tools/lab/attn_wpb.py, lab build): 320 problems 11.1 us as
     // whole workgroups, 10.1 / 9.9 / 11.5 us cut in 2 / 3 / 6; 640 problems 15.0 us whole, 16.4 / 17.9 / 21.5 us cut —
     // the cut pays while the problems do not fill the chip, then the repeated K / V staging costs more than the balance gains
-#define GF_A16_FWD(W, LEN, ...)                                                                                     \
-    {                                                                                                               \
-        GF_TRY((lds_optin<attn16_fwd_kernel<HD, NT, W, false, LEN, ##__VA_ARGS__>>(lds, "attention_fwd")));         \
-        hipLaunchKernelGGL((attn16_fwd_kernel<HD, NT, W, false, LEN, ##__VA_ARGS__>), dim3(B * H * (NT / W)), dim3(64 * W), lds, st, qkv, o, lse, keepw, S, \
-                           B, E, H, p, site, rng, add, train, Attn16Seg1{}, 0, key_len);                                \
-    }
-    const bool cut = (long)B * H < 512 && NT % 2 == 0 && NT > 2;
-#ifdef GANFFN_A16_CAUSAL_TU
-    // the causal instantiations are LEN ones; a null key_len reads as S in the kernel
-    if (cut) GF_A16_FWD((NT % 2 == 0 ? 2 : NT), true, true)
-    else GF_A16_FWD(NT, true, true)
-#else
-    if (key_len) {
-        if (cut) GF_A16_FWD((NT % 2 == 0 ? 2 : NT), true)
-        else GF_A16_FWD(NT, true)
-    } else {
-        if (cut) GF_A16_FWD((NT % 2 == 0 ? 2 : NT), false)
-        else GF_A16_FWD(NT, false)
-    }
-#endif
-#undef GF_A16_FWD
-    GF_LAUNCH_CHECK();
-    return 0;
+    constexpr bool CUTTABLE = NT % 2 == 0 && NT > 2;
+    const bool cut = (long)k.B * k.H < 512 && CUTTABLE;
+    auto launch = [&](auto wpb, auto pair, auto len) -> int {
+        constexpr int WPB = decltype(wpb)::value;
+        constexpr bool PAIR = decltype(pair)::value, LEN = decltype(len)::value;
+        const AttnSeg &s0 = k.seg[0], &t1 = k.seg[1];      // without a second segment t1 is null / 0
+        const Attn16Seg1 s1{t1.qkv, t1.o, t1.lse, keep ? t1.keep : nullptr, t1.train};
+        const int nb0 = k.B * k.H * (NT / WPB);            // workgroups of one batch
+        GF_TRY((lds_optin<attn16_fwd_kernel<HD, NT, WPB, PAIR, LEN, A16_CAUSAL>>(lds, "attention_fwd")));
+        hipLaunchKernelGGL((attn16_fwd_kernel<HD, NT, WPB, PAIR, LEN, A16_CAUSAL>), dim3((PAIR ? 2 : 1) * nb0), dim3(64 * WPB), lds, k.st,
+                           s0.qkv, s0.o, s0.lse, keep ? s0.keep : nullptr, k.S, k.B, k.E, k.H, k.p, k.site, k.rng, k.add, s0.train, s1,
+                           PAIR ? nb0 : 0, k.key_len);
+        GF_LAUNCH_CHECK();
+        return 0;
+    };
+    return with_flag(k.nseg == 2, [&](auto pair) {
+        return with_len(k, [&](auto len) {
+            if constexpr (CUTTABLE)
+                if (cut) return launch(std::integral_constant<int, 2>{}, pair, len);
+            return launch(std::integral_constant<int, NT>{}, pair, len);
+        });
+    });
 }
 template <int HD, int NT>
-static int launch16_bwd(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keepw, float* d_qkv,
-                        int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train,
-                        hipStream_t st, const int32_t* key_len) {
+static int launch16_bwd(const AttnCall& k) {
     const size_t lds = bwd_lds<HD>(NT);
-#define GF_A16_BWD(SAVED, LEN, ...)                                                                                 \
-    {                                                                                                               \
-        GF_TRY((lds_optin<attn16_bwd_kernel<HD, NT, SAVED, LEN, ##__VA_ARGS__>>(lds, "attention_bwd")));            \
-        hipLaunchKernelGGL((attn16_bwd_kernel<HD, NT, SAVED, LEN, ##__VA_ARGS__>), dim3(B * H), dim3(64 * NT), lds, st, qkv, o, lse, d_o, keepw, d_qkv, \
-                           S, B, E, H, p, site, rng, add, train, key_len);                                              \
-    }
-    const bool saved = keepw != nullptr && train && p > 0.f && attn16_use_keep(B, H);      // the forward of this pass stored its keep words
-#ifdef GANFFN_A16_CAUSAL_TU
-    if (saved) GF_A16_BWD(true, true, true)
-    else GF_A16_BWD(false, true, true)
-#else
-    if (key_len) {
-        if (saved) GF_A16_BWD(true, true)
-        else GF_A16_BWD(false, true)
-    } else {
-        if (saved) GF_A16_BWD(true, false)
-        else GF_A16_BWD(false, false)
-    }
-#endif
-#undef GF_A16_BWD
-    GF_LAUNCH_CHECK();
-    return 0;
+    const bool saved = k.keep != nullptr && k.train && k.p > 0.f && attn16_use_keep(k.B, k.H);      // the forward of this pass stored its keep words
+    return with_flag(saved, [&](auto sv) {
+        return with_len(k, [&](auto len) -> int {
+            constexpr bool SAVED = decltype(sv)::value, LEN = decltype(len)::value;
+            GF_TRY((lds_optin<attn16_bwd_kernel<HD, NT, SAVED, LEN, A16_CAUSAL>>(lds, "attention_bwd")));
+            hipLaunchKernelGGL((attn16_bwd_kernel<HD, NT, SAVED, LEN, A16_CAUSAL>), dim3(k.B * k.H), dim3(64 * NT), lds, k.st, k.qkv, k.o, k.lse,
+                               k.d_o, k.keep, k.d_qkv, k.S, k.B, k.E, k.H, k.p, k.site, k.rng, k.add, k.train, k.key_len);
+            GF_LAUNCH_CHECK();
+            return 0;
+        });
+    });
 }
 
 #define NT16_SWITCH3(FN, HD, ...)                           \
-    switch ((S + 15) / 16) {                                \
+    switch ((k.S + 15) / 16) {                              \
         case 1: return FN<HD, 1>(__VA_ARGS__);              \
         case 2: return FN<HD, 2>(__VA_ARGS__);              \
         default: return FN<HD, 3>(__VA_ARGS__);             \
     }
 #define NT16_SWITCH(FN, HD, ...)                            \
-    switch ((S + 15) / 16) {                                \
+    switch ((k.S + 15) / 16) {                              \
         case 1: return FN<HD, 1>(__VA_ARGS__);              \
         case 2: return FN<HD, 2>(__VA_ARGS__);              \
         case 3: return FN<HD, 3>(__VA_ARGS__);              \
@@ -869,36 +832,23 @@ static int launch16_bwd(const float* qkv, const float* o, const float* lse, cons
         default: return FN<HD, 7>(__VA_ARGS__);             \
     }
 
-int A16_ENTRY(launch_attn16_fwd)(const float* qkv, float* o, float* lse, uint32_t* keepw, int S, int B, int E, int H, float p, uint32_t site,
-                      const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1,
-                      const int32_t* key_len, uint32_t flags) {
-    const bool causal = (flags & GANFFN_ATTN_CAUSAL) != 0;
-    GF_CHECK_ARG(!seg1 || (seg1->qkv && seg1->o), "attn16_fwd: bad second batch");
-    GF_CHECK_ARG(attn16_supported(E, H, S) && S >= 1 && S <= GANFFN_MAX_SEQ, "attn16_fwd: unsupported E=%d H=%d S=%d", E, H, S);
-    GF_CHECK_ARG((long)B * H * 28 * 128 < (1l << 32), "attention: B*H too large for the Philox counter");
-#ifndef GANFFN_A16_CAUSAL_TU
-    if (causal) return launch_attn16_fwd_causal(qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st, seg1, key_len, flags);
-#endif
-    if (E / H == 64) { NT16_SWITCH3(launch16_fwd, 64, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st, seg1, key_len) }
-    if (E / H == 60) { NT16_SWITCH3(launch16_fwd, 60, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st, seg1, key_len) }
-    if (E / H == 10) { NT16_SWITCH(launch16_fwd, 10, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st, seg1, key_len) }
-    NT16_SWITCH(launch16_fwd, 30, qkv, o, lse, keepw, S, B, E, H, p, site, rng, add, train, st, seg1, key_len)
+template <bool CAUSAL>
+int attn16_fwd(const AttnCall& k) {
+    static_assert(CAUSAL == A16_CAUSAL, "each unit launches its own kernels only");
+    if (k.E / k.H == 64) { NT16_SWITCH3(launch16_fwd, 64, k) }
+    if (k.E / k.H == 60) { NT16_SWITCH3(launch16_fwd, 60, k) }
+    if (k.E / k.H == 10) { NT16_SWITCH(launch16_fwd, 10, k) }
+    NT16_SWITCH(launch16_fwd, 30, k)
 }
-
-int A16_ENTRY(launch_attn16_bwd)(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keepw, float* d_qkv,
-                      int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train,
-                      hipStream_t st, const int32_t* key_len, uint32_t flags) {
-    [[maybe_unused]] const bool causal = (flags & GANFFN_ATTN_CAUSAL) != 0;
-    GF_CHECK_ARG(attn16_supported(E, H, S) && S >= 1 && S <= GANFFN_MAX_SEQ, "attn16_bwd: unsupported E=%d H=%d S=%d", E, H, S);
-    GF_CHECK_ARG(o && lse, "attention_bwd: head_dim %d needs the forward's output and log-sum-exp", E / H);
-    GF_CHECK_ARG((long)B * H * 28 * 128 < (1l << 32), "attention: B*H too large for the Philox counter");
-#ifndef GANFFN_A16_CAUSAL_TU
-    if (causal) return launch_attn16_bwd_causal(qkv, o, lse, d_o, keepw, d_qkv, S, B, E, H, p, site, rng, add, train, st, key_len, flags);
-#endif
-    if (E / H == 64) { NT16_SWITCH3(launch16_bwd, 64, qkv, o, lse, d_o, keepw, d_qkv, S, B, E, H, p, site, rng, add, train, st, key_len) }
-    if (E / H == 60) { NT16_SWITCH3(launch16_bwd, 60, qkv, o, lse, d_o, keepw, d_qkv, S, B, E, H, p, site, rng, add, train, st, key_len) }
-    if (E / H == 10) { NT16_SWITCH(launch16_bwd, 10, qkv, o, lse, d_o, keepw, d_qkv, S, B, E, H, p, site, rng, add, train, st, key_len) }
-    NT16_SWITCH(launch16_bwd, 30, qkv, o, lse, d_o, keepw, d_qkv, S, B, E, H, p, site, rng, add, train, st, key_len)
+template <bool CAUSAL>
+int attn16_bwd(const AttnCall& k) {
+    static_assert(CAUSAL == A16_CAUSAL, "each unit launches its own kernels only");
+    if (k.E / k.H == 64) { NT16_SWITCH3(launch16_bwd, 64, k) }
+    if (k.E / k.H == 60) { NT16_SWITCH3(launch16_bwd, 60, k) }
+    if (k.E / k.H == 10) { NT16_SWITCH(launch16_bwd, 10, k) }
+    NT16_SWITCH(launch16_bwd, 30, k)
 }
+template int attn16_fwd<A16_CAUSAL>(const AttnCall& k);
+template int attn16_bwd<A16_CAUSAL>(const AttnCall& k);
 
 }  // namespace ganffn

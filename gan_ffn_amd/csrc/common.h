@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdarg.h>
 #include <atomic>
+#include <type_traits>
 
 #include "../../include/ganffn.h"
 
@@ -334,39 +335,54 @@ long gemm_tn_grouped_part_floats();
 // small-head forward and read back by its backward instead of recomputing the Philox calls (attention16.hip; the
 // head_dim 60/64 kernels ignore it).  Same bits either way.
 constexpr int ATTN_KEEP_WORDS = 28 * 16;
-// seg1 (optional): a second batch of the same shape in the same launch, with its own buffers and train flag
-struct AttnFwdSeg1 {
+// one batch of a forward pass: its buffers and train flag
+struct AttnSeg {
     const float* qkv; float* o; float* lse; uint32_t* keep; int train;
 };
+// One call of the attention core.  Every caller (the ganffn_attention_* entry points, encoder_fwd_walk and encoder_bwd in api.hip)
+// fills one and runs attention_fwd or attention_bwd on it; what a caller does not have stays null / 0.
 // key_len (optional, device int32 [B]): dialogue b attends over keys j < clamp(key_len[b], 1, S) only (probability 0 past it,
-// dK and dV rows written as zeros); null = all S keys, today's bits.  With seg1 the lengths serve both batches (the same B dialogues).
+// dK and dV rows written as zeros); null = all S keys, today's bits.  With a second segment the lengths serve both batches (the
+// same B dialogues).
 // flags: GANFFN_ATTN_CAUSAL = query i attends to keys j <= i as well (key limit min(n, i + 1)); kernels of their own, instantiated
-// only in the form with lengths (a null key_len reads as S there) and not for seg1.  0 = the launches and bits without it.
-int launch_attention_fwd(const float* qkv, float* o, float* lse, uint32_t* keep, int S, int B, int E, int H, float p, uint32_t site,
-                         const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1 = nullptr,
-                         const int32_t* key_len = nullptr, uint32_t flags = 0);
-int launch_attention_bwd(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keep, float* d_qkv,
-                         int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train,
-                         hipStream_t st, const int32_t* key_len = nullptr, uint32_t flags = 0);
+// only in the form with lengths (a null key_len reads as S there), for one segment and for two.  0 = the launches and bits without it.
+struct AttnCall {
+    int S, B, E, H; float p; uint32_t site; const uint64_t* rng; uint64_t add; hipStream_t st;
+    const int32_t* key_len; uint32_t flags;
+    AttnSeg seg[2]; int nseg;                          // forward; nseg 2: a second batch of the same shape in the same launch
+    const float* qkv; const float* o; const float* lse; const uint32_t* keep; const float* d_o; float* d_qkv; int train;   // backward
+    bool causal() const { return (flags & GANFFN_ATTN_CAUSAL) != 0; }
+    AttnCall& mask(const int32_t* key_len_, uint32_t flags_) { key_len = key_len_; flags = flags_; return *this; }
+    AttnCall& forward(const AttnSeg& s) { seg[0] = s; nseg = 1; return *this; }
+    AttnCall& pair(const AttnSeg& s) { seg[1] = s; nseg = 2; return *this; }
+    AttnCall& backward(const float* qkv_, const float* o_, const float* lse_, const uint32_t* keep_, const float* d_o_, float* d_qkv_, int train_) {
+        qkv = qkv_; o = o_; lse = lse_; keep = keep_; d_o = d_o_; d_qkv = d_qkv_; train = train_;
+        return *this;
+    }
+};
+static inline AttnCall attn_call(int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add, hipStream_t st) {
+    AttnCall k{};
+    k.S = S; k.B = B; k.E = E; k.H = H; k.p = p; k.site = site; k.rng = rng; k.add = add; k.st = st;
+    return k;
+}
+// attention.hip: check the call (every refusal of the family is there, before any launch), then the 16-row kernels where
+// attn16_supported() says so, else the 32-row ones
+int attention_fwd(const AttnCall& k);
+int attention_bwd(const AttnCall& k);
+// f(std::true_type{}) or f(std::false_type{}): a run-time fact as a template flag of the kernel that f launches
+template <class F>
+static inline int with_flag(bool on, F&& f) { return on ? f(std::true_type{}) : f(std::false_type{}); }
 // the key length of dialogue b inside a kernel instantiated for lengths: one scalar load per workgroup (b is workgroup-uniform),
 // clamped here so that a bad length can neither empty a softmax nor move a read out of range
 __device__ __forceinline__ int attn_key_len(const int32_t* __restrict__ key_len, int b, int S) {
     return key_len ? min(max(key_len[b], 1), S) : S;
 }
+// attention16.hip: which shapes the 16-row kernels take, and their launches for a call that attention_fwd / attention_bwd has
+// checked and attn16_supported() accepts: CAUSAL = k.causal(), defined in attention16_causal.hip for true and in attention16.hip
+// for false
 bool attn16_supported(int E, int H, int S);
-// the causal launches of the same family (attention16_causal.hip); reached through launch_attn16_fwd / _bwd with the flag set
-int launch_attn16_fwd_causal(const float* qkv, float* o, float* lse, uint32_t* keepw, int S, int B, int E, int H, float p,
-                             uint32_t site, const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1,
-                             const int32_t* key_len, uint32_t flags);
-int launch_attn16_bwd_causal(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keepw,
-                             float* d_qkv, int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add,
-                             int train, hipStream_t st, const int32_t* key_len, uint32_t flags);
-int launch_attn16_fwd(const float* qkv, float* o, float* lse, uint32_t* keepw, int S, int B, int E, int H, float p, uint32_t site,
-                      const uint64_t* rng, uint64_t add, int train, hipStream_t st, const AttnFwdSeg1* seg1 = nullptr,
-                      const int32_t* key_len = nullptr, uint32_t flags = 0);
-int launch_attn16_bwd(const float* qkv, const float* o, const float* lse, const float* d_o, const uint32_t* keepw, float* d_qkv,
-                      int S, int B, int E, int H, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train,
-                      hipStream_t st, const int32_t* key_len = nullptr, uint32_t flags = 0);
+template <bool CAUSAL> int attn16_fwd(const AttnCall& k);
+template <bool CAUSAL> int attn16_bwd(const AttnCall& k);
 
 // stream.hip — streaming causal attention over per-layer K/V caches (layout: include/ganffn.h, "streaming"): per row i, slot
 // s = slot[i] at position t = pos[s], append the row's K / V at t and attend with its Q over keys 0 .. t; a row with s outside

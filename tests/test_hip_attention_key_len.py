@@ -22,9 +22,13 @@ CASES = {
     "hd10_110": (110, 2, 20, 2, [110, 97]),
     "hd10_94_10heads": (94, 2, 100, 10, [94, 48]),
     "hd10_400_problems": (17, 200, 20, 2, [1 + b % 17 for b in range(200)]),      # the path without keep words
+    # four query tiles at B H >= 512: whole workgroups (fewer problems are cut in two: hd10_94_10heads, hd30_50)
+    "hd10_520_problems": (50, 52, 100, 10, [50, 1] + [1 + (7 * b) % 50 for b in range(50)]),
     # 16-row, head_dim 30
     "hd30_17": (17, 3, 60, 2, [17, 1, 16]),
     "hd30_33": (33, 2, 60, 2, [33, 20]),
+    "hd30_50": (50, 2, 60, 2, [50, 33]),
+    "hd30_512_problems": (50, 128, 120, 4, [50, 1] + [1 + (7 * b) % 50 for b in range(126)]),
     # 16-row, head_dim 64 / 60 (S <= 48)
     "hd64_40": (40, 2, 128, 2, [40, 17]),
     "hd60_48": (48, 2, 120, 2, [48, 33]),

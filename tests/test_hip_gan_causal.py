@@ -39,7 +39,7 @@ import test_hip_gan_mask_padding as MP
 from key_len_oracle import valid_rows
 from test_hip_classifier_engines_train_oracle import _batch
 from test_hip_engine import build_all
-from test_hip_gen_pair import SHAPES, WIDTHS, _case
+from test_hip_gen_pair import SHAPES, _case, pair_cases
 from util import DIN
 
 pytestmark = pytest.mark.gpu
@@ -61,8 +61,7 @@ def _pair_buffers(cfg, S, B, E):
             torch.zeros(ops.encoder_fwd_pair_workspace_floats(cfg), **f32))
 
 
-@pytest.mark.parametrize("E,H", WIDTHS)
-@pytest.mark.parametrize("S,B", SHAPES + [(33, 5), (50, 2)])
+@pytest.mark.parametrize("S,B,E,H", pair_cases(SHAPES + [(33, 5), (50, 2)]))
 def test_causal_pair_pass_equals_the_two_causal_single_passes(S, B, E, H):
     from gan_ffn_amd import ops
     cfg, cfg_eval, params, x, pe = _case(S, B, E, H)

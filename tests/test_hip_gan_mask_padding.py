@@ -39,7 +39,7 @@ from bce_cases import UNDERFLOW
 from key_len_oracle import masked_attention, valid_rows
 from test_hip_classifier_engines_train_oracle import _batch
 from test_hip_engine import build_all
-from test_hip_gen_pair import SHAPES, WIDTHS, _case
+from test_hip_gen_pair import SHAPES, _case, pair_cases
 from util import DISC, GEN
 
 pytestmark = pytest.mark.gpu
@@ -65,8 +65,7 @@ def _bits(t):
 # ================================================================================================================
 # 1. the two-segment forward with key lengths
 # ================================================================================================================
-@pytest.mark.parametrize("E,H", WIDTHS)
-@pytest.mark.parametrize("S,B", SHAPES + [(50, 2)])
+@pytest.mark.parametrize("S,B,E,H", pair_cases(SHAPES + [(50, 2)]))
 def test_pair_pass_with_key_lengths_equals_the_two_single_passes(S, B, E, H):
     from gan_ffn_amd import ops
     cfg, cfg_eval, params, x, pe = _case(S, B, E, H)

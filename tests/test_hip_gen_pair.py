@@ -14,6 +14,14 @@ SHAPES = [(7, 2), (9, 4), (16, 4), (94, 3)]
 # GEMM path (the 16-row attention kernels' third head shape); (64, 4) and (248, 4): head_dim 16 and 62 on the 32-row attention
 # kernel's run-time head_dim form, whose two-segment instantiation no workload width reaches
 WIDTHS = [(100, 10), (512, 8), (120, 4), (64, 4), (248, 4)]
+# (S, B, E, H): four query tiles at B H >= 512 — the 16-row attention forward (head_dim 10 and 30) runs a batch as whole workgroups
+# where the smaller launches above are cut in two, and the rule is that of ONE batch of B dialogues in the two-segment launch too
+UNCUT = [(50, 52, 100, 10), (50, 128, 120, 4)]
+
+
+def pair_cases(shapes):
+    """every shape at every width, then UNCUT"""
+    return [(S, B, E, H) for E, H in WIDTHS for S, B in shapes] + UNCUT
 
 
 def _case(S, B, E, H, L=2):
@@ -62,8 +70,7 @@ def _pair_against_the_two_single_passes(S, B, E, H, mode=0, key_len=None):
     assert torch.equal(p_saved.view(torch.int32), saved.view(torch.int32))
 
 
-@pytest.mark.parametrize("E,H", WIDTHS)
-@pytest.mark.parametrize("S,B", SHAPES)
+@pytest.mark.parametrize("S,B,E,H", pair_cases(SHAPES))
 def test_pair_pass_equals_the_two_single_passes(S, B, E, H):
     _pair_against_the_two_single_passes(S, B, E, H)
 

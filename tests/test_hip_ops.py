@@ -173,7 +173,10 @@ ATTN_CASES = [(7, 2, 100, 10), (110, 3, 100, 10), (94, 4, 512, 8), (33, 2, 100, 
               # MELD-dimension stacks (BASELINE.json configs[2]): text E = 600 (head_dim 60), audio E = 300 (head_dim 30)
               (94, 2, 600, 10), (33, 3, 600, 10), (110, 2, 600, 10), (94, 3, 300, 10), (7, 2, 300, 10), (110, 2, 300, 10),
               # head_dim 60 / 64 at S <= 48 run on the 16x16x4 kernels, longer sequences on attention.hip
-              (48, 2, 600, 10), (49, 2, 600, 10), (40, 3, 512, 8), (16, 2, 512, 8), (5, 1, 600, 10)]
+              (48, 2, 600, 10), (49, 2, 600, 10), (40, 3, 512, 8), (16, 2, 512, 8), (5, 1, 600, 10),
+              # head_dim 30 at 520 problems and four query tiles: whole workgroups where fewer than 512 problems are cut in two
+              # (head_dim 10: (94, 64, 100, 10) above)
+              (50, 52, 300, 10)]
 
 
 ATTN_SEED, ATTN_OFF, ATTN_ADD, ATTN_LAYER = 777, 11, 4, 2

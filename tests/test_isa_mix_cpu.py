@@ -55,6 +55,67 @@ def test_weight_resident_epilogues_stay_lean(gemm):
     assert max(c["valu"] for c in lin1) <= 130 and max(c["valu"] for c in dgrad) <= 64, (lin1, dgrad)
 
 
+_LISTING_A = """\t.text
+\t.globl\t_Z1aPf
+_Z1aPf:                                 ; @_Z1aPf
+; %bb.0:
+\ts_load_dwordx2 s[0:1], s[0:1], 0x0
+\ts_cbranch_execz .LBB0_2
+
+.LBB0_2:                                ; %exit
+\ts_endpgm
+\t.amdhsa_kernel _Z1aPf
+\t\t.amdhsa_next_free_vgpr 2
+\t.end_amdhsa_kernel
+.Lfunc_end0:
+\t.globl\t_Z1bPf
+_Z1bPf:                                 ; @_Z1bPf
+\tv_mov_b32_e32 v0, 0
+.LBB1_1:
+\ts_endpgm
+\t.amdhsa_kernel _Z1bPf
+\t\t.amdhsa_next_free_vgpr 1
+\t.end_amdhsa_kernel
+.Lfunc_end1:
+"""
+# the same two kernels emitted in the other order (so each has the other's function index), other comments, other blank lines
+_LISTING_B = """\t.text
+_Z1bPf:                                 ; @_Z1bPf another comment
+\tv_mov_b32_e32 v0, 0
+
+.LBB0_1:
+\ts_endpgm
+\t.amdhsa_kernel _Z1bPf
+\t\t.amdhsa_next_free_vgpr 1 ; Occupancy: 8
+\t.end_amdhsa_kernel
+.Lfunc_end0:
+_Z1aPf:
+\ts_load_dwordx2 s[0:1], s[0:1], 0x0
+\ts_cbranch_execz .LBB1_2
+.LBB1_2:
+\ts_endpgm
+\t.amdhsa_kernel _Z1aPf
+\t\t.amdhsa_next_free_vgpr 2
+\t.end_amdhsa_kernel
+.Lfunc_end1:
+"""
+
+
+def test_digest_ignores_emission_order_comments_and_blank_lines_and_nothing_else():
+    """--digest compares two commits' device code: per kernel, the text from its label to .Lfunc_end and its .amdhsa_kernel block,
+    without the function index of .LBB labels, comments and blank lines.  No compile: two canned listings."""
+    a, b = isa_mix.kernel_digests(_LISTING_A), isa_mix.kernel_digests(_LISTING_B)
+    assert set(a) == {"_Z1aPf", "_Z1bPf"} and a == b
+    assert isa_mix.unit_digest(a) == isa_mix.unit_digest(b)
+    assert a["_Z1aPf"] != a["_Z1bPf"]
+    for old, new in (("v_mov_b32_e32 v0, 0", "v_mov_b32_e32 v0, 1"),                 # an instruction
+                     (".LBB1_2\n", ".LBB1_3\n"),                                     # a branch target (the label's own number)
+                     ("next_free_vgpr 2", "next_free_vgpr 3")):                      # the kernel descriptor
+        assert old in _LISTING_B
+        c = isa_mix.kernel_digests(_LISTING_B.replace(old, new))
+        assert set(c) == set(a) and c != a and isa_mix.unit_digest(c) != isa_mix.unit_digest(a), (old, new)
+
+
 def test_d100_kernels_k_loops():
     n100, _ = _kernels("gemm_n100.hip")
     for name, rows in n100.items():

@@ -1,13 +1,17 @@
 """Instruction mix of the MFMA-carrying basic blocks of the hot kernels, from hipcc's own assembly listing.
 
     python tools/isa_mix.py [file.hip ...]        (default: the K-loop kernels of gan_ffn_amd/csrc)
+    python tools/isa_mix.py --digest [file.hip ...]   (default: every translation unit of csrc/Makefile's SRCS)
 
 For every kernel of a translation unit and every basic block with at least four MFMAs: instructions, MFMAs, accumulator moves
 (v_accvgpr_read / write / mov), other vector-ALU instructions, LDS and global / buffer memory instructions.  fp32 MFMAs execute on
 the SIMD's vector ALU, so the "valu" and "accmov" columns are paid in MFMA time: this listing is how round 5
 found the accumulator shuffling of tn100_kernel, the per-lane 64-bit addresses in every K loop and the select chains of the
-K = 100 epilogues.  Compiles with the flags of csrc/Makefile; no GPU needed."""
-import os, re, subprocess, sys, tempfile
+K = 100 epilogues.  Compiles with the flags of csrc/Makefile; no GPU needed.
+
+--digest: per translation unit, the number of kernels and one sha256 over the sorted per-kernel digests of the listing
+(kernel_digests) — two commits whose lines are equal compile to the same device code, whatever their host code looks like."""
+import hashlib, os, re, subprocess, sys, tempfile
 from collections import Counter
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -56,6 +60,38 @@ def blocks_of(text):
             yield name, rows
 
 
+def normalise(body):
+    """A kernel's listing without what moves when other functions of the unit do: the function index in .LBB<n>_ labels,
+    comments (from ';' to the end of the line) and blank lines."""
+    lines = (re.sub(r"\.LBB\d+_", ".LBB_", line.split(";")[0]).rstrip() for line in body.split("\n"))
+    return "\n".join(line for line in lines if line.strip())
+
+
+def kernel_digests(text):
+    """{kernel symbol: sha256 over its normalised text from the label to .Lfunc_end and its .amdhsa_kernel block}"""
+    out = {}
+    for m in re.finditer(r"^\s*\.amdhsa_kernel\s+(\S+)\n.*?^\s*\.end_amdhsa_kernel", text, re.M | re.S):
+        name = m.group(1)
+        i = re.search(r"^%s:" % re.escape(name), text, re.M).end()
+        body = normalise(text[i:text.index(".Lfunc_end", i)])
+        out[name] = hashlib.sha256((body + "\n--\n" + normalise(m.group(0))).encode()).hexdigest()
+    return out
+
+
+def unit_digest(digests):
+    return hashlib.sha256("\n".join(sorted("%s %s" % kv for kv in digests.items())).encode()).hexdigest()
+
+
+def srcs():
+    return re.search(r"^SRCS\s*:=\s*(.*)$", open(os.path.join(CSRC, "Makefile")).read(), re.M).group(1).split()
+
+
+def digest_main(files):
+    for f in files or srcs():
+        d = kernel_digests(listing(f if os.path.isabs(f) else os.path.join(CSRC, f)))
+        print("%-24s kernels %4d  sha256 %s" % (os.path.basename(f), len(d), unit_digest(d)), flush=True)
+
+
 def main(files):
     for f in files:
         path = f if os.path.isabs(f) else os.path.join(CSRC, f)
@@ -70,4 +106,7 @@ def main(files):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:] or DEFAULT)
+    if sys.argv[1:2] == ["--digest"]:
+        digest_main(sys.argv[2:])
+    else:
+        main(sys.argv[1:] or DEFAULT)
