@@ -122,19 +122,6 @@ static int64_t ln_part_floats(const ganffn_enc_cfg* c) {
     return (int64_t)nb * 2 * c->E;
 }
 
-// K splits of the in-proj dgrad [T x 3E] x [3E x E]: its T/64 x E/64 output tiles are far fewer than the chip's workgroup
-// slots (94 at d_model 100, T = 3008), so K is cut into ~128-wide chunks (at most 8) whose partial outputs the consuming
-// LayerNorm backward adds in order
-static int inproj_dgrad_splits(int T, int E) {
-    const long tiles = (long)((T + 63) / 64) * ((E + 63) / 64);
-    if (tiles >= 768) return 1;
-    long s = (768 + tiles - 1) / tiles;
-    const long maxs = (3L * E) / 128;
-    if (s > maxs) s = maxs;
-    if (s > 8) s = 8;
-    return s < 1 ? 1 : (int)s;
-}
-
 // Slack terms of the size functions, in floats.  REGION_SLACK follows the grouped-wgrad parts and the rowchain weight pack: it paid
 // for re-aligning the next region by address; every offset of BwdLayout is a multiple of 4 floats (E and F are), so it pays for
 // nothing and is kept only so that the sizes do not change.  TAIL_SLACK ends every encoder and head workspace: no region of a
@@ -278,11 +265,14 @@ static int encoder_fwd_walk(const EncCall& k, const Mode md, const FwdSeg& s0, c
     const FwdSeg& t1 = s1 ? *s1 : s0;
     const int train0 = s0.train, train1 = s1 ? s1->train : 0;
     auto keep_words = [&](const FwdSeg& s, float* sv) { return s.keeps ? reinterpret_cast<uint32_t*>(sv + so.keep) : nullptr; };
-    // [T x K] x W[N x K]^T of both segments in one launch; splits (or null): split-K slabs TE apart, summed by the LayerNorm kernel
+    // [T x K] x W[N x K]^T of both segments in one launch; slab_cap (or 0): at most so many K slabs TE apart, summed by the
+    // LayerNorm kernel, *splits of them written (gemm_plan picks the kernel and the count)
     auto nt = [&](const float* A0, const float* A1, int K, const float* W, float* C0, float* C1, int N, int epi, const EpiArgs& ea,
-                  uint16_t* mask1 = nullptr, int* splits = nullptr) {
-        const GemmSeg1 g1{A1, C1, mask1, train1};
-        return launch_gemm_nt(A0, K, W, K, C0, N, T, N, K, epi, ea, st, splits, splits ? TE : 0, s1 ? &g1 : nullptr);
+                  uint16_t* mask1 = nullptr, int slab_cap = 0, int* splits = nullptr) {
+        GemmCall g = gemm_nt(A0, W, C0, T, N, K).epilogue(epi, ea).on(st);
+        if (slab_cap) g.slabs(slab_cap, TE, splits);
+        if (s1) g.pair(GemmSeg1{A1, C1, mask1, train1});
+        return gemm(g);
     };
     auto ln = [&](const float* x0, const float* x1, const float* w, const float* b, float* out0, float* out1, float* xhat0,
                   float* xhat1, float* rstd0, float* rstd1, uint32_t site, int nslab) {
@@ -347,8 +337,9 @@ static int encoder_fwd_walk(const EncCall& k, const Mode md, const FwdSeg& s0, c
         } else {
             ea.bias = P + lo.out_b;
             // (the 512-wide out-proj is 376 output tiles on 256 CUs: K in two halves, summed by the LayerNorm kernel)
-            int osplits = md.outproj_nosplit() ? 1 : gemm_splitk_factor(T, E, E);
-            GF_TRY(nt(v0 + so.attn_o, v1 + so.attn_o, E, P + lo.out_w, s0.tmp, t1.tmp, E, EPI_NONE, ea, nullptr, &osplits));
+            int osplits = 1;
+            GF_TRY(nt(v0 + so.attn_o, v1 + so.attn_o, E, P + lo.out_w, s0.tmp, t1.tmp, E, EPI_NONE, ea, nullptr,
+                      md.outproj_nosplit() ? 1 : MAX_SPLITS, &osplits));
             GF_TRY(ln(s0.x(l), t1.x(l), P + lo.n1w, P + lo.n1b, v0 + so.x1, v1 + so.x1, v0 + so.xhat1, v1 + so.xhat1, v0 + so.rstd1,
                       v1 + so.rstd1, site + 1, osplits));
         }
@@ -361,15 +352,9 @@ static int encoder_fwd_walk(const EncCall& k, const Mode md, const FwdSeg& s0, c
             if (s0.keeps) e1.mask_out = reinterpret_cast<uint16_t*>(v0 + so.hmask);
             uint16_t* const mask1 = t1.keeps ? reinterpret_cast<uint16_t*>(v1 + so.hmask) : nullptr;
             GF_TRY(nt(v0 + so.x1, v1 + so.x1, E, P + lo.w1, v0 + so.h, v1 + so.h, F, EPI_RELU_DROP, e1, mask1));
-            if (n100_supported(E, F) && !md.n100_off()) {
-                splits = MAX_SPLITS;                   // K chunks = output slabs, summed by the LayerNorm kernel
-                GF_TRY(launch_gemm_n100(v0 + so.h, F, P + lo.w2, F, 0, P + lo.b2, s0.tmp, TE, T, F, &splits, st,
-                                        s1 ? v1 + so.h : nullptr, s1 ? s1->tmp : nullptr));
-            } else {
-                ea.bias = P + lo.b2;
-                splits = gemm_splitk_factor(T, E, F);      // few output tiles, K = 2048: split K, LN sums the slabs
-                GF_TRY(nt(v0 + so.h, v1 + so.h, F, P + lo.w2, s0.tmp, t1.tmp, E, EPI_NONE, ea, nullptr, &splits));
-            }
+            // few output tiles, K = 2048: K chunks = output slabs, summed by the LayerNorm kernel (gemm_n100.hip at d_model 100)
+            ea.bias = P + lo.b2;
+            GF_TRY(nt(v0 + so.h, v1 + so.h, F, P + lo.w2, s0.tmp, t1.tmp, E, EPI_NONE, ea, nullptr, MAX_SPLITS, &splits));
         }
         if (rc) {
             // LN2, then (all but the last layer) qkv of layer l + 1 from the fresh rows while they are in the workgroup
@@ -613,7 +598,6 @@ static int encoder_bwd(const EncCall& k) {
         float* d_qkv = workspace + w.d_qkv(i);   // [T x 3E]
         float* lnp2 = workspace + w.lnp2(i);
         float* lnp1 = workspace + w.lnp1(i);
-        EpiArgs none;
         // LN2 backward: dL/dX[l+1] -> dz2 (to x1), dyA (to FFN output).  dL/dX[l+1] is the caller's dx for the top layer
         // of the range and otherwise the in-proj dgrad of the layer above: split-K partial slabs in `tmp`, summed here
         if (rc) {
@@ -638,19 +622,13 @@ static int encoder_bwd(const EncCall& k) {
             em.aux_in = sv + so.h;
             em.mscale = mscale;
             if (!md.mask_float()) em.mask_in = reinterpret_cast<const uint16_t*>(sv + so.hmask);     // linear1's epilogue left the pattern as bits
-            GF_TRY(launch_gemm_nn(dyA, E, P + lo.w2, F, dh, F, T, F, E, EPI_MASK_POS, em, st));
+            GF_TRY(gemm(gemm_nn(dyA, P + lo.w2, dh, T, F, E).epilogue(EPI_MASK_POS, em).on(st)));
         }
         // linear1 wgrad: gW1[F,E] += dh^T x1 ; gb1 += colsum(dh)
         if (G) tn[ntn++] = TnDesc{dh, F, sv + so.x1, E, G + lo.w1, E, G + lo.b1, F, E, T};
         {
             // d x1 = dh W1 (split-K slabs) + dz2, consumed directly by the LN1 backward
-            if (n100_supported(E, F) && !md.n100_off()) {
-                splits = MAX_SPLITS;
-                GF_TRY(launch_gemm_n100(dh, F, P + lo.w1, E, 1, nullptr, tmp, TE, T, F, &splits, st));
-            } else {
-                splits = gemm_splitk_factor(T, E, F);
-                GF_TRY(launch_gemm_nn(dh, F, P + lo.w1, E, tmp, E, T, E, F, EPI_NONE, none, st, &splits, TE));
-            }
+            GF_TRY(gemm(gemm_nn(dh, P + lo.w1, tmp, T, E, F).slabs(MAX_SPLITS, TE, &splits).on(st)));
         }
         if (rc) {
             // LN1 backward + the out-proj dgrad (d_attn = dyB W_o) on the rows while they are in the workgroup
@@ -665,7 +643,7 @@ static int encoder_bwd(const EncCall& k) {
         if (G) { r_gw[nred] = G + lo.n1w; r_gb[nred] = G + lo.n1b; r_part[nred] = lnp1; r_nb[nred] = lnblk; ++nred; }
         // out-proj wgrad + dgrad
         if (G) tn[ntn++] = TnDesc{dyB, E, sv + so.attn_o, E, G + lo.out_w, E, G + lo.out_b, E, E, T};
-        if (!rc) GF_TRY(launch_gemm_nn(dyB, E, P + lo.out_w, E, d_attn, E, T, E, E, EPI_NONE, none, st));
+        if (!rc) GF_TRY(gemm(gemm_nn(dyB, P + lo.out_w, d_attn, T, E, E).on(st)));
         // attention core backward
         GF_TRY(attention_bwd(attn_call(S, B, E, H, c->p_enc, site + 0, rng, add, st).mask(k.key_len, k.flags)
                                  .backward(sv + so.qkv, sv + so.attn_o, sv + so.lse, reinterpret_cast<const uint32_t*>(sv + so.keep), d_attn, d_qkv, train)));
@@ -675,19 +653,18 @@ static int encoder_bwd(const EncCall& k) {
             GF_TRY(launch_gemm_tn_grouped(tn, ntn, st, workspace + w.tnp, gemm_tn_grouped_part_floats(), slabs));
             ntn = 0;
         }
-        EpiArgs eadd;
-        eadd.aux_in = dz1;            // dX[l] = d_qkv W_in + dz1 (residual, added by split 0) in the GEMM epilogue
+        // dX[l] = d_qkv W_in + dz1 (.residual: added by split 0 in the GEMM epilogue)
         if (l > layer_lo && rc) {
             // (the in-proj dgrad of this layer runs inside the LN2 backward kernel of layer l - 1)
         } else if (l > layer_lo) {
             // few output tiles (T/64 x E/64): split K into slabs that the next layer's LN2 backward sums on the fly
             // (`tmp` is free here: its previous content, this layer's dh W1 slabs, went into the LN1 backward above)
-            int sp = inproj_dgrad_splits(T, E);
-            GF_TRY(launch_gemm_nn(d_qkv, 3 * E, P + lo.in_w, E, tmp, E, T, E, 3 * E, EPI_NONE, eadd, st, &sp, TE));
+            int sp = 1;
+            GF_TRY(gemm(gemm_nn(d_qkv, P + lo.in_w, tmp, T, E, 3 * E).residual(dz1).slabs(MAX_SPLITS, TE, &sp, SLABS_INPROJ_DGRAD).on(st)));
             dxin = tmp;
             dxin_slabs = sp;
         } else if (layer_lo > 0 || need_dx_in) {
-            GF_TRY(launch_gemm_nn(d_qkv, 3 * E, P + lo.in_w, E, dx, E, T, E, 3 * E, EPI_NONE, eadd, st));
+            GF_TRY(gemm(gemm_nn(d_qkv, P + lo.in_w, dx, T, E, 3 * E).residual(dz1).on(st)));
         }   // (else: the stack's input needs no gradient — autograd would not compute this product either)
     }
     // (unreduced mode: nobody zeroed the gradient slab's encoder region — the LayerNorm parameter gradients are WRITTEN too)
@@ -811,9 +788,9 @@ extern "C" int ganffn_head_fwd(const ganffn_head_cfg* c, const float* x, const f
     EpiArgs e;
     e.p = c->p; e.rng = rng; e.rng_add = add; e.train = train;
     e.bias = b1; e.site = SITE_HEAD1; e.aux_out = u1;
-    GF_TRY(launch_gemm_nt(s0, E, w1, E, a1, D1, T, D1, E, EPI_DROP_GELU, e, st));
+    GF_TRY(gemm(gemm_nt(s0, w1, a1, T, D1, E).epilogue(EPI_DROP_GELU, e).on(st)));
     e.bias = b2; e.site = SITE_HEAD2; e.aux_out = u2;
-    GF_TRY(launch_gemm_nt(a1, D1, w2, D1, gen ? out : a2, D2, T, D2, D1, EPI_DROP_GELU, e, st));
+    GF_TRY(gemm(gemm_nt(a1, w2, gen ? out : a2, T, D2, D1).epilogue(EPI_DROP_GELU, e).on(st)));
     if (gen) return 0;
     GF_TRY(launch_disc_tail_fwd(a2, w3, b3, prob, T, D2, c->p, rng, add, train, st));
     hipError_t er = hipMemcpyAsync(out, prob, (size_t)T * sizeof(float), hipMemcpyDeviceToDevice, st);
@@ -854,19 +831,19 @@ extern "C" int ganffn_head_bwd(const ganffn_head_cfg* c, const float* d_out, con
     } else {
         GF_TRY(launch_disc_tail_bwd(d_out, prob, a2, u2, w3, d_pre2, gw3, gb3, T, D2, c->p, rng, add, train, st, tailp));
     }
-    if (gw2) GF_TRY(launch_gemm_tn_acc(d_pre2, D2, a1, D1, gw2, D1, gb2, D2, D1, T, st, part2, h.part2_floats));
+    if (gw2) GF_TRY(gemm(gemm_tn(d_pre2, a1, gw2, D2, D1, T).sums(gb2).tn_workspace(part2, h.part2_floats).on(st)));
     EpiArgs e;
     e.p = c->p; e.rng = rng; e.rng_add = add; e.train = train;
     e.aux_in = u1; e.site = SITE_HEAD1;
-    if (!fused) GF_TRY(launch_gemm_nn(d_pre2, D2, w2, D1, d_pre1, D1, T, D1, D2, EPI_GELU_BWD_DROP, e, st));
-    if (gw1) GF_TRY(launch_gemm_tn_acc(d_pre1, D1, s0, E, gw1, E, gb1, D1, E, T, st, part1, h.part1_floats));
+    if (!fused) GF_TRY(gemm(gemm_nn(d_pre2, w2, d_pre1, T, D1, D2).epilogue(EPI_GELU_BWD_DROP, e).on(st)));
+    if (gw1) GF_TRY(gemm(gemm_tn(d_pre1, s0, gw1, D1, E, T).sums(gb1).tn_workspace(part1, h.part1_floats).on(st)));
     if (fused) return 0;
     e.aux_in = x;
     if (c->kind == 0) {
         e.site = SITE_HEAD0;
-        GF_TRY(launch_gemm_nn(d_pre1, D1, w1, E, dx, E, T, E, D1, EPI_GELU_BWD_DROP, e, st));
+        GF_TRY(gemm(gemm_nn(d_pre1, w1, dx, T, E, D1).epilogue(EPI_GELU_BWD_DROP, e).on(st)));
     } else {
-        GF_TRY(launch_gemm_nn(d_pre1, D1, w1, E, dx, E, T, E, D1, EPI_GELU_BWD, e, st));
+        GF_TRY(gemm(gemm_nn(d_pre1, w1, dx, T, E, D1).epilogue(EPI_GELU_BWD, e).on(st)));
     }
     return 0;
 }
@@ -880,9 +857,7 @@ extern "C" int ganffn_linear_fwd(const float* x, const float* w, const float* b,
     GF_CHECK_ARG(x && w && y && T > 0 && K > 0 && N > 0, "linear_fwd: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     if ((K & 3) == 0 && aligned16(x) && aligned16(w)) {
-        EpiArgs e;
-        e.bias = b;
-        return launch_gemm_nt(x, K, w, K, y, N, T, N, K, EPI_NONE, e, st);
+        return gemm(gemm_nt(x, w, y, T, N, K).bias(b).on(st));
     }
     return launch_small_linear_fwd(x, w, b, y, T, K, N, st);
 }
@@ -896,12 +871,11 @@ extern "C" int ganffn_linear_bwd(const float* dy, const float* x, const float* w
     GF_CHECK_ARG(dy && x && w && T > 0 && K > 0 && N > 0, "linear_bwd: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     if (mfma_ok(K, N) && aligned16(dy) && aligned16(x) && aligned16(w)) {
-        EpiArgs e;
-        if (dx) GF_TRY(launch_gemm_nn(dy, N, w, K, dx, K, T, K, N, EPI_NONE, e, st));
+        if (dx) GF_TRY(gemm(gemm_nn(dy, w, dx, T, K, N).on(st)));
         // weight gradient: split over tokens into partial slabs when the caller lends a workspace (deterministic
         // ordered reduce), one workgroup per tile over the whole token range otherwise
         const bool ws_ok = workspace != nullptr && aligned16(workspace);
-        if (gw) GF_TRY(launch_gemm_tn_acc(dy, N, x, K, gw, K, gb, N, K, T, st, ws_ok ? workspace : nullptr, ws_ok ? (long)workspace_floats : 0));
+        if (gw) GF_TRY(gemm(gemm_tn(dy, x, gw, N, K, T).sums(gb).tn_workspace(ws_ok ? workspace : nullptr, ws_ok ? (long)workspace_floats : 0).on(st)));
         return 0;
     }
     return launch_small_linear_bwd(dy, x, w, dx, gw, gb, T, K, N, st);
@@ -911,16 +885,13 @@ extern "C" int ganffn_linear_bwd(const float* dy, const float* x, const float* w
 // building blocks for unit tests
 // ------------------------------------------------------------------------------------------
 extern "C" int ganffn_gemm_nt(const float* A, const float* W, const float* bias, float* C, int M, int N, int K, void* stream) {
-    EpiArgs e;
-    e.bias = bias;
-    return launch_gemm_nt(A, K, W, K, C, N, M, N, K, EPI_NONE, e, (hipStream_t)stream);
+    return gemm(gemm_nt(A, W, C, M, N, K).bias(bias).on((hipStream_t)stream));
 }
 extern "C" int ganffn_gemm_nn(const float* A, const float* Bm, float* C, int M, int N, int K, void* stream) {
-    EpiArgs e;
-    return launch_gemm_nn(A, K, Bm, N, C, N, M, N, K, EPI_NONE, e, (hipStream_t)stream);
+    return gemm(gemm_nn(A, Bm, C, M, N, K).on((hipStream_t)stream));
 }
 extern "C" int ganffn_gemm_tn_acc(const float* At, const float* Bm, float* C, float* colsum, int M, int N, int K, void* stream) {
-    return launch_gemm_tn_acc(At, M, Bm, N, C, N, colsum, M, N, K, (hipStream_t)stream);
+    return gemm(gemm_tn(At, Bm, C, M, N, K).sums(colsum).on((hipStream_t)stream));
 }
 extern "C" int ganffn_ffn_linear1_fwd(const float* x, const float* w1, const float* b1, float* h, int T, int E, int F, float p,
                                       uint32_t site, const uint64_t* rng, uint64_t add, int train, void* stream) {
@@ -928,7 +899,7 @@ extern "C" int ganffn_ffn_linear1_fwd(const float* x, const float* w1, const flo
     GF_CHECK_ARG(!(train && p > 0.f) || rng, "ffn_linear1_fwd: rng required when dropout is active");
     EpiArgs e;
     e.bias = b1; e.p = p; e.site = site; e.rng = rng; e.rng_add = add; e.train = train;
-    return launch_gemm_nt(x, E, w1, E, h, F, T, F, E, EPI_RELU_DROP, e, (hipStream_t)stream);
+    return gemm(gemm_nt(x, w1, h, T, F, E).epilogue(EPI_RELU_DROP, e).on((hipStream_t)stream));
 }
 // test / measurement hook: the generic 64 x 64 GEMM kernel as the encoder stack launches it (bench.py replays the d_model-512
 // generator's launch mix through this)
@@ -943,13 +914,9 @@ extern "C" int ganffn_gemm_hook(int mode, int epi, const float* A, const float* 
     e.bias = bias; e.aux_in = aux; e.mscale = (train && p > 0.f && epi == EPI_MASK_POS) ? 1.f / (1.f - p) : 1.f;
     e.p = p; e.site = site; e.rng = rng; e.rng_add = add; e.train = train;
     int splits = 1;
-    if (max_slabs > 1 && epi == EPI_NONE) {
-        splits = gemm_splitk_factor(M, N, K);
-        if (splits > max_slabs) splits = max_slabs;
-    }
-    int* sp = (max_slabs > 1 && epi == EPI_NONE) ? &splits : nullptr;
-    if (mode == 0) GF_TRY(launch_gemm_nt(A, K, W, K, C, N, M, N, K, epi, e, (hipStream_t)stream, sp, (long)slab_stride));
-    else GF_TRY(launch_gemm_nn(A, K, W, N, C, N, M, N, K, epi, e, (hipStream_t)stream, sp, (long)slab_stride));
+    GemmCall g = (mode == 0 ? gemm_nt(A, W, C, M, N, K) : gemm_nn(A, W, C, M, N, K)).epilogue(epi, e).on((hipStream_t)stream);
+    if (max_slabs > 1 && epi == EPI_NONE) g.slabs(max_slabs, (long)slab_stride, &splits, SLABS_GENERIC);
+    GF_TRY(gemm(g));
     if (n_slabs) *n_slabs = splits;
     return 0;
 }
@@ -966,22 +933,20 @@ extern "C" int ganffn_ffn_k100_hook(int which, const float* a, const float* w, c
         GF_CHECK_ARG(!(train && p > 0.f) || rng, "ffn_k100_hook: rng required when dropout is active");
         e.bias = bias; e.p = p; e.site = site; e.rng = rng; e.rng_add = add; e.train = train;
         e.mask_out = reinterpret_cast<uint16_t*>(hmask);
-        return launch_gemm_nt(a, E, w, E, out, F, T, F, E, EPI_RELU_DROP, e, (hipStream_t)stream);
+        return gemm(gemm_nt(a, w, out, T, F, E).epilogue(EPI_RELU_DROP, e).on((hipStream_t)stream));
     }
     GF_CHECK_ARG(hmask || h_saved, "ffn_k100_hook: the linear2 dgrad needs the pattern bits or the saved activation");
     e.aux_in = h_saved;
     e.mask_in = reinterpret_cast<const uint16_t*>(hmask);
     e.mscale = (train && p > 0.f) ? 1.f / (1.f - p) : 1.f;
-    return launch_gemm_nn(a, E, w, F, out, F, T, F, E, EPI_MASK_POS, e, (hipStream_t)stream);
+    return gemm(gemm_nn(a, w, out, T, F, E).epilogue(EPI_MASK_POS, e).on((hipStream_t)stream));
 }
 extern "C" int ganffn_gemm_n100(const float* A, const float* W, int w_kmajor, const float* bias, float* slabs, int64_t slab_stride,
                                 int T, int K, int max_slabs, int* n_slabs, void* stream) {
     GF_CHECK_ARG(n_slabs && max_slabs >= 1 && max_slabs <= MAX_SPLITS, "gemm_n100: max_slabs=%d out of [1,%d]", max_slabs, MAX_SPLITS);
     GF_CHECK_ARG(n100_supported(100, K), "gemm_n100: K=%d must be a multiple of 32, >= 256", K);
-    int s = max_slabs;
-    GF_TRY(launch_gemm_n100(A, K, W, w_kmajor ? 100 : K, w_kmajor, bias, slabs, (long)slab_stride, T, K, &s, (hipStream_t)stream));
-    *n_slabs = s;
-    return 0;
+    return gemm((w_kmajor ? gemm_nn(A, W, slabs, T, 100, K) : gemm_nt(A, W, slabs, T, 100, K))
+                    .bias(bias).slabs(max_slabs, (long)slab_stride, n_slabs, SLABS_N100).on((hipStream_t)stream));
 }
 #ifdef GANFFN_LAB
 // lab builds only (make LAB=1 -> lib/libganffn_lab.so; never in the product library, not declared in include/ganffn.h):

@@ -265,25 +265,83 @@ struct EpiArgs {
 
 inline long epi_mask_words(long M, long N) { return ((M + 31) / 32) * N * 2; }
 
-// second row segment of a two-segment launch_gemm_nt (EPI_NONE, also split-K, or EPI_RELU_DROP): its input rows, output (slabs
-// at the same stride), pattern words (may be null) and train flag
+// second row segment of a two-segment NT product (EPI_NONE, also split-K, or EPI_RELU_DROP): its input rows, output (slabs
+// at the same stride), pattern words (may be null) and train flag.  The n100 kernel reads A and C only.
 struct GemmSeg1 {
     const float* A; float* C; uint16_t* mask_out; int train;
 };
-// C[MxN] = A[MxK] * W[NxK]^T (NT); s1 (optional): the same product for a second row segment in the same launch
-int launch_gemm_nt(const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N, int K,
-                   int epi, const EpiArgs& ea, hipStream_t st, int* splits_io = nullptr, long slab_stride = 0,
-                   const GemmSeg1* s1 = nullptr);
-int gemm_splitk_factor(int M, int N, int K);
-// C[MxN] = A[MxK] * B[KxN] (NN)
-int launch_gemm_nn(const float* A, int lda, const float* Bm, int ldb, float* C, int ldc, int M, int N, int K,
-                   int epi, const EpiArgs& ea, hipStream_t st, int* splits_io = nullptr, long slab_stride = 0);
-// C[MxN] += At[KxM]^T * B[KxN]  (TN); colsum[M] += sum_k At[k][m].  Deterministic: with a partial-slab workspace
-// (gemm_tn_part_floats floats) the token range is split over workgroups and reduced in split order, without one a
-// single workgroup per output tile runs the whole range.  No atomics.
+//   NT  C[MxN]  = A[MxK] * W[NxK]^T   NN  C[MxN] = A[MxK] * B[KxN]   TN  C[MxN] += At[KxM]^T * B[KxN], colsum[M] += sum_k At[k][m]
+enum GemmLayout : int { GEMM_NT = 0, GEMM_NN = 1, GEMM_TN = 2 };
+// who decides how many K slabs an EPI_NONE product writes (gemm.hip, "split policies"); the caller gives the cap and the stride
+enum GemmSlabRule : int {
+    SLABS_AUTO = 0,      // the [T x K] x [K x 100] kernel (gemm_n100.hip) with its own chunk rule where it takes the shape and
+                         // Mode::n100_off() is clear, else the generic kernel split by gemm_splitk_factor
+    SLABS_GENERIC,       // the generic kernel split by gemm_splitk_factor, whatever the shape (ganffn_gemm_hook)
+    SLABS_INPROJ_DGRAD,  // the generic kernel split by gemm_inproj_dgrad_splits
+    SLABS_N100,          // gemm_n100.hip whatever the mode word says; a shape it does not take is refused (ganffn_gemm_n100)
+};
+// One dense product.  Every caller fills one and runs gemm() on it; what a caller does not have stays null / 0.  The struct lives
+// on the caller's stack.  Deterministic in every form: split products write slabs that the consumer (NT / NN) or an ordered
+// reduce launch (TN) adds in split order; no atomics.
+struct GemmCall {
+    GemmLayout layout;
+    const float* A; int lda;       // NT / NN: [M x K];  TN: At [K x M]
+    const float* B; int ldb;       // NT: W [N x K];  NN / TN: [K x N]
+    float* C; int ldc;
+    int M, N, K;
+    int epi; EpiArgs ea;           // NT / NN
+    hipStream_t st;
+    // K slabs (EPI_NONE, NT / NN): slab z = the partial product of K chunk z at C + z * slab_stride, at most slab_cap of them, the
+    // count written goes to *n_slabs.  slab_cap 0 = not asked for: one product at C.
+    GemmSlabRule slab_rule; int slab_cap; long slab_stride; int* n_slabs;
+    bool has_seg1; GemmSeg1 seg1;  // NT: the same product for a second segment of M rows in the same launch
+    float* colsum; float* part_ws; long part_floats;   // TN: column sums of At (or null), partial-slab workspace (or null)
+    GemmCall& ld(int lda_, int ldb_, int ldc_) { lda = lda_; ldb = ldb_; ldc = ldc_; return *this; }
+    GemmCall& epilogue(int epi_, const EpiArgs& ea_) { epi = epi_; ea = ea_; return *this; }
+    // EPI_NONE's two operands, for the callers that have nothing else to say about the epilogue: C = acc + bias[N] + residual[M x N]
+    GemmCall& bias(const float* b) { ea.bias = b; return *this; }
+    GemmCall& residual(const float* r) { ea.aux_in = r; return *this; }         // leading dimension ldc; may be C itself
+    GemmCall& slabs(int cap, long stride, int* n, GemmSlabRule rule = SLABS_AUTO) {
+        slab_cap = cap; slab_stride = stride; n_slabs = n; slab_rule = rule;
+        return *this;
+    }
+    GemmCall& pair(const GemmSeg1& s) { seg1 = s; has_seg1 = true; return *this; }
+    GemmCall& sums(float* colsum_) { colsum = colsum_; return *this; }
+    GemmCall& tn_workspace(float* ws, long floats) { part_ws = ws; part_floats = floats; return *this; }
+    GemmCall& on(hipStream_t st_) { st = st_; return *this; }
+};
+// the three layouts with the dense leading dimensions almost every caller has; .ld() for the rest
+static inline GemmCall gemm_call(GemmLayout layout, const float* A, int lda, const float* B, int ldb, float* C, int ldc, int M, int N, int K) {
+    GemmCall k{};
+    k.layout = layout; k.A = A; k.lda = lda; k.B = B; k.ldb = ldb; k.C = C; k.ldc = ldc; k.M = M; k.N = N; k.K = K; k.epi = EPI_NONE;
+    return k;
+}
+static inline GemmCall gemm_nt(const float* A, const float* W, float* C, int M, int N, int K) { return gemm_call(GEMM_NT, A, K, W, K, C, N, M, N, K); }
+static inline GemmCall gemm_nn(const float* A, const float* B, float* C, int M, int N, int K) { return gemm_call(GEMM_NN, A, K, B, N, C, N, M, N, K); }
+static inline GemmCall gemm_tn(const float* At, const float* B, float* C, int M, int N, int K) { return gemm_call(GEMM_TN, At, M, B, N, C, N, M, N, K); }
+// What gemm_plan (gemm.hip) decides for a call: a pure host function of the call and the mode word, no HIP call inside.
+enum GemmFamily : int {
+    GEMM_GENERIC = 0,    // gemm_kernel / gemm_pair_kernel, 64 x 64 x 16 tiles
+    GEMM_SHORTK,         // the same code under its K <= 128 symbol
+    GEMM_WRES,           // gemm_wres_kernel / gemm_wres_pair_kernel: K = 100, N >= 1024, weight fragments resident in registers
+    GEMM_N100,           // gemm_n100.hip
+    GEMM_TN_ACC,         // gemm_kernel<MODE_TN>: owner-adds-in-place, or (splits > 1) partial slabs + tn_reduce_kernel
+};
+enum N100Variant : int { N100_KW2_TAIL4 = 0, N100_KW2_PAD7, N100_KW1_PAD7 };   // waves per token group along K; features 96..99
+constexpr int N100_BM = 64, N100_BK = 32;       // gemm_n100.hip's token tile and K tile
+struct GemmPlan {
+    GemmFamily family; bool pair;
+    int epi;             // the kernel's epilogue (EPI_GELU_BWD_DROP0 runs EPI_GELU_BWD_DROP's code)
+    int splits, kchunk;  // K chunks (= slabs written) and the chunk length; 1 and K when not split
+    long slab_stride;    // what the kernel gets: the call's when split, 0 when not;  TN: floats per partial slab
+    dim3 grid;           // GEMM_WRES: (column panels, token tiles of all segments); its launcher cuts the tiles down to what is resident
+    N100Variant n100;
+};
+// gemm.hip: check the call (every refusal of the dense paths, before any launch), plan it (kernel family and variant, K split,
+// grid), launch
+int gemm(const GemmCall& k);
+// floats of partial-slab workspace a split TN product of this shape can use (0: it will not split)
 long gemm_tn_part_floats(int M, int N, int K);
-int launch_gemm_tn_acc(const float* At, int lda, const float* Bm, int ldb, float* C, int ldc, float* colsum,
-                       int M, int N, int K, hipStream_t st, float* part_ws = nullptr, long part_floats = 0);
 
 // skinny products (dialogue_rnn.hip): M <= 32 rows of A (dialogues) against a weight matrix, up to 8 problems per launch — one
 // link of a recurrence's launch chain (DialogueRNN cells, lstm.hip's recurrent products)
@@ -439,12 +497,11 @@ int launch_ln_param_reduce(int n, float* const* gw, float* const* gb, const floa
                            hipStream_t st, bool overwrite = false);
 int launch_add_inplace(float* a, const float* b, int64_t n, hipStream_t st);
 
-// gemm_n100.hip — [T x K] x [K x 100] with a long K on 16x16x4 MFMAs (112-wide feature tile), K cut into output slabs
+// gemm_n100.hip — [T x K] x [K x 100] with a long K on 16x16x4 MFMAs (112-wide feature tile), K cut into output slabs.  Reached
+// through gemm(): gemm.hip's check and plan decide (its chunk rule, n100_splits, stands there beside the other split rules),
+// launch_gemm_n100 launches what the plan says.
 bool n100_supported(int N, int K);
-int n100_splits(int T, int K, int max_splits, int w_kmajor);
-// A1 / C1 (optional, both or neither; rows-of-K weights only): a second row segment [T x K] -> slabs at C1 in the same launch
-int launch_gemm_n100(const float* A, int lda, const float* W, int ldw, int w_kmajor, const float* bias, float* C, long slab_stride,
-                     int T, int K, int* splits_io, hipStream_t st, const float* A1 = nullptr, float* C1 = nullptr);
+int launch_gemm_n100(const GemmCall& k, const GemmPlan& p);
 
 // rowchain.hip — d_model 100: out-proj + residual + dropout + LayerNorm1, LayerNorm2 + the next layer's in-proj, and the
 // mirror-image backward chains, one kernel each (16 token rows per workgroup)

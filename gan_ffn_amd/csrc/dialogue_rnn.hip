@@ -1413,9 +1413,7 @@ static int drnn_fwd(const DrnnCall& k) {
         const float* aw = k.ap[z].w;
         // U-only terms for all steps, out[T x N] = U W[:, :Dm]^T (+ bias): XG (with bih_g), XP likewise, XA = the attention's query
         auto u_term = [&](const float* W, int ldw, const float* bias, float* out, int N) {
-            EpiArgs e;
-            e.bias = bias;
-            return launch_gemm_nt(U[z], Dm, W, ldw, out, N, T, N, Dm, EPI_NONE, e, st);
+            return gemm(gemm_nt(U[z], W, out, T, N, Dm).ld(Dm, ldw, N).bias(bias).on(st));
         };
         GF_TRY(u_term(prm[z].g_wih, Dm + H, prm[z].g_bih, sv + L.XG, 3 * H));
         GF_TRY(u_term(prm[z].p_wih, Dm + H, prm[z].p_bih, sv + L.XP, 3 * H));
@@ -1517,9 +1515,8 @@ static int drnn_fwd(const DrnnCall& k) {
         ea.S = S; ea.B = B; ea.He = He; ea.p = c->p; ea.train = c->train; ea.rng = k.rng; ea.add = k.add;
         for (int z = 0; z < ndir; ++z) {
             float* sv = saved[z]; float* ws = workspace[z];
-            EpiArgs e;
-            e.bias = prm[z].e_bih;                 // GI_e of every step: one GEMM over all T rows of q_t[spk]
-            GF_TRY(launch_gemm_nt(sv + L.QN, H, prm[z].e_wih, H, ws + L.GIe, 3 * He, T, 3 * He, H, EPI_NONE, e, st));
+            // GI_e of every step: one GEMM over all T rows of q_t[spk]
+            GF_TRY(gemm(gemm_nt(sv + L.QN, prm[z].e_wih, ws + L.GIe, T, 3 * He, H).bias(prm[z].e_bih).on(st)));
             ea.d[z] = EchainDir{ws + L.GIe, prm[z].e_whh, prm[z].e_bhh, sv + L.E, sv + L.Re, sv + L.Ze, sv + L.Ne, sv + L.HNe,
                                 SITE_DRNN_E + 4u * z};
         }
@@ -1593,7 +1590,7 @@ static int drnn_bwd(const DrnnCall& k) {
         hipLaunchKernelGGL(drnn_echain_bwd_kernel, dim3(B, 1, ndir), dim3(EC_NT), 0, st, eb);
         GF_LAUNCH_CHECK();
         for (int z = 0; z < ndir; ++z)
-            GF_TRY(launch_gemm_nn(workspace[z] + L.dGIe, 3 * He, prm[z].e_wih, H, workspace[z] + L.dQNall, H, T, H, 3 * He, EPI_NONE, EpiArgs(), st));
+            GF_TRY(gemm(gemm_nn(workspace[z] + L.dGIe, prm[z].e_wih, workspace[z] + L.dQNall, T, H, 3 * He).on(st)));
     }
     for (int t = S - 1; t >= 0; --t) {
         const int64_t r0 = (int64_t)t * B, r1 = (int64_t)(t + 1) * B;
@@ -1692,19 +1689,18 @@ static int drnn_bwd(const DrnnCall& k) {
         const ganffn_drnn_grads& g = k.grd[z];
         const float* aw = k.ap[z].w;
         float* agw = k.ag[z].w;
-        EpiArgs e0, e1;
-        GF_TRY(launch_gemm_nn(ws + L.dGIg, 3 * H, prm[z].g_wih, Dm + H, dU[z], Dm, T, Dm, 3 * H, EPI_NONE, e0, st));
-        e1.aux_in = dU[z];
-        GF_TRY(launch_gemm_nn(ws + L.dGIp, 3 * H, prm[z].p_wih, Dm + H, dU[z], Dm, T, Dm, 3 * H, EPI_NONE, e1, st));
+        // dU = the first product, += every later one (.residual(dU): each element read and written by one thread)
+        GF_TRY(gemm(gemm_nn(ws + L.dGIg, prm[z].g_wih, dU[z], T, Dm, 3 * H).ld(3 * H, Dm + H, Dm).on(st)));
+        GF_TRY(gemm(gemm_nn(ws + L.dGIp, prm[z].p_wih, dU[z], T, Dm, 3 * H).ld(3 * H, Dm + H, Dm).residual(dU[z]).on(st)));
         if (att == ATT_GENERAL || att == ATT_GENERAL2) {
-            GF_TRY(launch_gemm_nn(ws + L.dXA, H, aw, Dm, dU[z], Dm, T, Dm, H, EPI_NONE, e1, st));
+            GF_TRY(gemm(gemm_nn(ws + L.dXA, aw, dU[z], T, Dm, H).residual(dU[z]).on(st)));
         } else if (att == ATT_DOT) {
             hipLaunchKernelGGL(drnn_add_kernel, dim3((unsigned)(((int64_t)T * Dm + 255) / 256)), dim3(256), 0, st, dU[z], ws + L.dXA, (int64_t)T * Dm);
             GF_LAUNCH_CHECK();
         } else if (att == ATT_CONCAT) {         // dU += dX W_u
-            GF_TRY(launch_gemm_nn(ws + L.dXC, Da, aw + H, H + Dm, dU[z], Dm, T, Dm, Da, EPI_NONE, e1, st));
+            GF_TRY(gemm(gemm_nn(ws + L.dXC, aw + H, dU[z], T, Dm, Da).ld(Da, H + Dm, Dm).residual(dU[z]).on(st)));
         }
-        if (lp) GF_TRY(launch_gemm_nn(ws + L.dGIl, 3 * H, lp[z].l_wih, Dm + H, dU[z], Dm, T, Dm, 3 * H, EPI_NONE, e1, st));
+        if (lp) GF_TRY(gemm(gemm_nn(ws + L.dGIl, lp[z].l_wih, dU[z], T, Dm, 3 * H).ld(3 * H, Dm + H, Dm).residual(dU[z]).on(st)));
         if (agw && att == ATT_SIMPLE) {         // dw = column sum of dXA (the constant query)
             hipLaunchKernelGGL(drnn_colsum_kernel, dim3((H + 63) / 64), dim3(1024), 0, st, ws + L.dXA, T, H, agw);
             GF_LAUNCH_CHECK();

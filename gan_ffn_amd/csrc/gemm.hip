@@ -1016,12 +1016,14 @@ __global__ __launch_bounds__(256) void gemm_wres_pair_kernel(GemmArgs g, GemmSeg
     gemm_wres_body<MODE, EPI, KC, true>(g, mtiles, wg_per_panel, s1 GF_LAB_ONLY(, nullptr));
 }
 
-// PAIR (with s1): the two-segment launch (gemm_wres_pair_kernel) over 2 * mtiles token tiles
-template <int MODE, int EPI, bool PAIR = false>
-static int launch_wres(const GemmArgs& g, hipStream_t st, const GemmSeg1* s1 = nullptr) {
+// The launch block of the weight-resident kernel.  PAIR (with s1): the two-segment launch (gemm_wres_pair_kernel) over
+// 2 * mtiles token tiles.  grid: gemm_plan's (column panels, token tiles of all segments); the workgroups per panel are cut down
+// here to what the device holds at once — the one decision of the family that needs a HIP call.
+template <int MODE, int EPI, bool PAIR>
+static int launch_wres(const GemmArgs& g, const dim3 grid, hipStream_t st, const GemmSeg1* s1) {
     constexpr int KC = 100;
     constexpr size_t lds = 2 * 64 * 4 * ((KC / 4) | 1) * sizeof(float);
-    const int panels = (g.N + 63) / 64, mtiles = (g.M + 63) / 64;
+    const int panels = (int)grid.x, mtiles = (int)grid.y / (PAIR ? 2 : 1);
     if constexpr (PAIR) GF_TRY((lds_optin<gemm_wres_pair_kernel<MODE, EPI, KC>>(lds, "gemm_wres")));
     GF_TRY((lds_optin<gemm_wres_kernel<MODE, EPI, KC>>(lds, "gemm_wres")));
     // persistent grid = exactly the workgroups the device holds at once (queried once per kernel and device)
@@ -1135,52 +1137,192 @@ __global__ __launch_bounds__(256) void gemm_tn_grouped_kernel(TnGroup grp) {
     gemm_body<MODE_TN, 64, BN, 16, EPI_NONE, 2, 2>(g, nt, mt, bz);
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// Driver.  gemm(call) = check_gemm (every refusal, before any launch) -> gemm_plan (family, variant, K split, grid: pure host
+// code) -> one launch block per kernel template.  The grouped weight-gradient launcher below it has the same three parts.
+// ------------------------------------------------------------------------------------------------------------------
+
+// ---- split policies: one function per rule, side by side.  They differ because they were measured separately. ----
+
+// (1) a plain (EPI_NONE) NT / NN product whose output has too few tiles to fill 256 CUs
+static int gemm_splitk_factor(int M, int N, int K) {
+    const long tiles = (long)((M + 63) / 64) * ((N + 63) / 64);
+    if (tiles >= 384 || K < 512) return 1;
+    long s = (768 + tiles - 1) / tiles;
+    const long maxs = K / 256;
+    if (s > maxs) s = maxs;
+    if (s > 8) s = 8;
+    return s < 1 ? 1 : (int)s;
+}
+
+// (2) the in-proj dgrad [T x 3E] x [3E x E] (M = T, N = E, K = 3E): its T/64 x E/64 output tiles are far fewer than the chip's
+// workgroup slots (94 at d_model 100, T = 3008), so K is cut into ~128-wide chunks (at most 8) whose partial outputs the
+// consuming LayerNorm backward adds in order
+static int gemm_inproj_dgrad_splits(int M, int N, int K) {
+    const long tiles = (long)((M + 63) / 64) * ((N + 63) / 64);
+    if (tiles >= 768) return 1;
+    long s = (768 + tiles - 1) / tiles;
+    const long maxs = K / 128;
+    if (s > maxs) s = maxs;
+    if (s > 8) s = 8;
+    return s < 1 ? 1 : (int)s;
+}
+
+// what (1) and (2) ask for becomes chunks that are multiples of 64 (of every BK); the count follows from the chunk
+static void split_chunks(int K, int want, int& splits, int& kchunk) {
+    if (want <= 1) { splits = 1; kchunk = K; return; }
+    kchunk = ((K + want - 1) / want + 63) / 64 * 64;
+    splits = (K + kchunk - 1) / kchunk;
+}
+
+// (3) a TN product (weight gradient) with a partial-slab workspace.  A one- or two-tile gradient (the discriminator head's fc1
+// [64 x 100] / fc2 [16 x 64]) used to be cut into K / 64 = 94 slabs: the 6 us GEMM was followed by a 40 us reduce launch whose 2-7
+// workgroups walk 94 slabs one batch of loads after the other (profiles/r02_*: tn_reduce_kernel 1.4 % of the step).  16 slabs keep
+// the GEMM as short and the reduce at its floor.
+constexpr long TN_ACC_MAXSPLIT = 16;
+static long tn_acc_wanted_splits(int M, int N, int K) {
+    const long tiles = (long)((M + 63) / 64) * ((N + 63) / 64);
+    long splits = (768 + tiles - 1) / tiles;             // ~3 blocks per CU measured best (tools/gemm_bench.py)
+    const long maxsplits = (K + 63) / 64;                // at least 64 k per block
+    if (splits > maxsplits) splits = maxsplits;
+    if (splits > TN_ACC_MAXSPLIT) splits = TN_ACC_MAXSPLIT;
+    return splits;
+}
+static inline long tn_acc_slab_floats(int M, int N) { return (long)M * N + M; }     // [M x N] partial product, then [M] column sums
+// the workspace a split launch of this shape can use, and what a launch makes of the workspace it gets: both from the rule above
+long gemm_tn_part_floats(int M, int N, int K) {
+    const long splits = tn_acc_wanted_splits(M, N, K);
+    return splits <= 1 ? 0 : splits * tn_acc_slab_floats(M, N);
+}
+static void tn_acc_split(const GemmCall& k, GemmPlan& p) {
+    const long per = tn_acc_slab_floats(k.M, k.N);
+    long splits = tn_acc_wanted_splits(k.M, k.N, k.K);
+    if (k.part_ws == nullptr) splits = 1;
+    else if (splits * per > k.part_floats) splits = k.part_floats / per;
+    if (splits < 1) splits = 1;
+    p.kchunk = (int)(((k.K + splits - 1) / splits + 63) / 64 * 64);   // multiple of every BK
+    splits = (k.K + p.kchunk - 1) / p.kchunk;
+    p.splits = (int)splits;
+    // (M and N are multiples of 4 — check_gemm — so a slab is its own 16-byte stride, and the slabs that fit densely fit;
+    //  the launcher this came from had a fallback to one owner per tile for strides that did not: no call could reach it)
+    p.slab_stride = splits > 1 ? per : 0;
+}
+
+// (4) a grouped TN launch with fewer than TN_GROUP_MIN_TILES output tiles (4 per CU) splits the token range of every tile so that
+// about TN_GROUP_TILES workgroups exist.  Measured at 1136 tiles (a whole d_model-100 backward pass, T = 6016): unsplit
+// 446 us; split in 3: 424 us + 20 us for the reduce launch — no gain, so such groups stay on the owner-only path; the
+// narrow groups this is for are the 1-4-layer gradient buckets of the data-parallel path (142-568 tiles).
+constexpr int TN_GROUP_MIN_TILES = 1024;
+constexpr int TN_GROUP_TILES = 2560;
+constexpr int TN_GROUP_MAXSPLIT = 8;
+static int tn_grouped_splits(long tiles, int kmax, long per_split, bool have_ws, long part_floats) {
+    if (!have_ws || tiles >= TN_GROUP_MIN_TILES) return 1;
+    int splits = (int)((TN_GROUP_TILES + tiles - 1) / tiles);
+    if (splits > TN_GROUP_MAXSPLIT) splits = TN_GROUP_MAXSPLIT;
+    if (splits > kmax / 256) splits = kmax / 256;             // >= 256 tokens per workgroup of the longest problem
+    if ((long)splits * per_split > part_floats) splits = (int)(part_floats / per_split);
+    return splits < 2 ? 1 : splits;
+}
+long gemm_tn_grouped_part_floats() { return (long)(TN_GROUP_TILES + 256) * (64 * 64 + 64) + 4 * MAXP; }
+
+// (5) gemm_n100.hip: K chunks (= output slabs, <= max_splits).  Measured on MI355X (tools/lab/n100_lab.py, K = 2048,
+// gpurun_out/r4_n100_lab.txt; round 3's 4-wave numbers in brackets):
+//  * 8 waves (two per 16-token group, one 16-wide half of every K tile each): rows-of-K weights T = 3008: 4 / 5 / 8 / 10 / 16
+//    chunks 20.8 / 18.1 / 20.1 / 19.2 / 22.9 us [22.0 / 19.1 / 20.4 / 19.0 / 19.0]; T = 6016: 4 / 5 / 6 / 8 chunks
+//    34.0 / 29.2 / 41.2 / 36.1 us [35.4 / 30.5 / 35.1 / 29.9];
+//  * K-major weights (58 LDS reads per tile instead of 16): T = 3008: 5 / 8 / 16 chunks 19.3 / 20.3 / 18.1 us
+//    [22.9 / 21.6 / 18.5]; T = 6016: 5 / 6 / 8 chunks 29.9 / 34.0 / 29.1 us [32.4 / 35.0 / 29.9] — with the second wave per
+//    SIMD inside the workgroup the K-major layout no longer needs the extra chunks (and their slabs) for co-residency.
+// Rule (8 waves, both weight layouts): a CU runs its workgroups' MFMA work back to back, so the launch costs
+// ceil(workgroups / 256 CUs) x the chunk's K tiles, plus the slab traffic: every slab is written here and read again by the
+// LayerNorm-side consumer (~0.8 tile-times per slab at T = 3008; the consumer at T = 6016 with 8 slabs is bandwidth-bound on
+// them: 19 MB).  Lab knob: bits 8..15 of the mode word force the count.
+static int n100_splits(int T, int K, int max_splits, const Mode md) {
+    if (const int fs = md.n100_force_splits(); fs > 0) return fs < max_splits ? fs : max_splits;
+    const int tiles_m = (T + N100_BM - 1) / N100_BM, ksteps = K / N100_BK;
+    int best = 1;
+    double best_cost = 1e30;
+    for (int s = 1; s <= max_splits && s <= ksteps; ++s) {
+        const int per = (ksteps + s - 1) / s;
+        if ((s - 1) * per >= ksteps) continue;                       // an empty last chunk
+        const long wgs = (long)tiles_m * s;
+        const long rounds = (wgs + 255) / 256;
+        const double cost = (double)rounds * per + 0.8 * ((double)T / 3008.0) * s;
+        if (cost < best_cost) { best_cost = cost; best = s; }
+    }
+    return best;
+}
+
+// ---- the plan ----
+
 // the kernels with a two-segment form (gemm_pair_kernel; of the weight-resident kernel, linear1's epilogue only)
 template <int MODE, int EPI>
 constexpr bool HAS_PAIR = MODE == MODE_NT && (EPI == EPI_NONE || EPI == EPI_RELU_DROP);
 
-// s1 (or null): the second row segment — the same tiles again along grid y, for s1's operands
-template <int MODE, int BM, int BN, int BK, int EPI, int WGM = 2, int WGN = 2, int SHORTK = 0>
-static int launch_cfg(const GemmArgs& g, int splits, hipStream_t st, const GemmSeg1* s1 = nullptr) {
-    const int gy0 = (g.M + BM - 1) / BM;
-    dim3 grid((g.N + BN - 1) / BN, gy0, splits);
-    constexpr size_t lds = Smem<MODE, BM, BN, BK>::TOTAL * sizeof(float);
-    if constexpr (HAS_PAIR<MODE, EPI>) {
-        if (s1) {
-            grid.y = 2 * gy0;
-            GF_TRY((lds_optin<gemm_pair_kernel<MODE, BM, BN, BK, EPI, WGM, WGN, SHORTK>>(lds, "gemm")));
-            hipLaunchKernelGGL((gemm_pair_kernel<MODE, BM, BN, BK, EPI, WGM, WGN, SHORTK>), grid, dim3(64 * WGM * WGN), lds, st, g, *s1, gy0);
-            GF_LAUNCH_CHECK();
-            return 0;
-        }
-    }
-    GF_TRY((lds_optin<gemm_kernel<MODE, BM, BN, BK, EPI, WGM, WGN, SHORTK>>(lds, "gemm")));
-    hipLaunchKernelGGL((gemm_kernel<MODE, BM, BN, BK, EPI, WGM, WGN, SHORTK>), grid, dim3(64 * WGM * WGN), lds, st, g);
-    GF_LAUNCH_CHECK();
-    return 0;
+// gemm_n100.hip serves the call: asked for by name, or a slab product of its shape that leaves the choice open
+static bool gemm_takes_n100(const GemmCall& k, const Mode md) {
+    if (k.layout == GEMM_TN || k.slab_cap <= 0) return false;
+    if (k.slab_rule == SLABS_N100) return true;
+    return k.slab_rule == SLABS_AUTO && k.epi == EPI_NONE && k.ea.aux_in == nullptr && n100_supported(k.N, k.K) && !md.n100_off();
 }
 
-// s1 (or null): the second segment goes to the two-segment form of the kernel that one segment's shape takes
-template <int MODE, int EPI>
-static int launch_pick(const GemmArgs& g, int splits, hipStream_t st, const GemmSeg1* s1 = nullptr) {
-    if constexpr (!HAS_PAIR<MODE, EPI>)
-        if (s1) return fail(-1, "gemm_nt_pair: epilogue %d has no two-segment form", EPI);
+// A pure function of the call and the mode word: no HIP call, nothing written.  The call has passed check_gemm's argument checks.
+static GemmPlan gemm_plan(const GemmCall& k, const Mode md) {
+    GemmPlan p{};
+    p.pair = k.has_seg1;
+    p.epi = k.epi == EPI_GELU_BWD_DROP0 ? EPI_GELU_BWD_DROP : k.epi;
+    p.splits = 1; p.kchunk = k.K;
+    const int tiles_m = (k.M + 63) / 64, tiles_n = (k.N + 63) / 64;
+    if (k.layout == GEMM_TN) {
+        p.family = GEMM_TN_ACC;
+        tn_acc_split(k, p);
+        p.grid = dim3(tiles_n, tiles_m, p.splits);
+        return p;
+    }
+    if (gemm_takes_n100(k, md)) {
+        p.family = GEMM_N100;
+        // (the chunk count is one segment's, T rows, also with a second one: the slab order is part of the result)
+        const int ksteps = k.K / N100_BK;
+        const int s = n100_splits(k.M, k.K, k.slab_cap, md);
+        const int per = (ksteps + s - 1) / s;
+        p.splits = (ksteps + per - 1) / per;
+        p.kchunk = per * N100_BK;
+        p.slab_stride = k.slab_stride;
+        // waves per 16-token group along K: two (8-wave workgroups) — faster at every chunk count the rule picks; the 4-wave form
+        // and the padded seventh tile (round 3's form) stay behind the lab knobs (bits 20..21, bit 23) for A/B
+        const int kw = md.n100_force_kw() ? md.n100_force_kw() : 2;
+        p.n100 = kw == 2 ? (md.n100_pad7() ? N100_KW2_PAD7 : N100_KW2_TAIL4) : N100_KW1_PAD7;
+        p.grid = dim3((k.M + N100_BM - 1) / N100_BM * (p.pair ? 2 : 1), p.splits);
+        return p;
+    }
+    if (k.slab_cap > 0 && k.epi == EPI_NONE) {
+        int want = k.slab_rule == SLABS_INPROJ_DGRAD ? gemm_inproj_dgrad_splits(k.M, k.N, k.K) : gemm_splitk_factor(k.M, k.N, k.K);
+        if (want > k.slab_cap) want = k.slab_cap;
+        split_chunks(k.K, want, p.splits, p.kchunk);
+    }
+    p.slab_stride = p.splits > 1 ? k.slab_stride : 0;
     // measured on MI355X (tools/gemm_bench.py, M = 3008 / 6016, N = 100 .. 2048, K = 100 .. 2048): with the
     // straight-line K loop the 4-wave 64x64x16 block is the fastest or within 2 % of the fastest of every block /
     // wave-tile shape tried (64x64x32, 128x64, 64x128, 128x128 with 2, 4, 8 or 16 waves), so it is the only one used.
-    if constexpr (MODE != MODE_TN)
-        if (g.K == 100 && g.N >= 1024 && splits == 1 && (g.lda & 3) == 0 && ((MODE == MODE_NT) ? (g.ldb & 3) == 0 : true) &&
-            (size_t)g.M * g.lda * 4 < (size_t(1) << 31) && (size_t)g.M * g.ldc * 4 < (size_t(1) << 31)) {   // 32-bit buffer offsets
-            if (!s1) return launch_wres<MODE, EPI>(g, st);
-            if constexpr (MODE == MODE_NT && EPI == EPI_RELU_DROP) return launch_wres<MODE, EPI, true>(g, st, s1);
-            else return fail(-1, "gemm_nt_pair: no two-segment form of the weight-resident kernel for epilogue %d", EPI);
-        }
-    if (g.K <= 128) return launch_cfg<MODE, 64, 64, 16, EPI, 2, 2, 1>(g, splits, st, s1);
     // (64 x 128 tiles for the N = 2048, K = 512 products: 5-9 % faster in isolation, round 2; in the 3-stream step 35.9 against
     // 35.7 ms with 64 x 64 — fewer, fatter workgroups co-run worse — so they are not used; round 3, tools/lab/mode_ab.py;
     // re-measured in round 4 with tuned streams and the XCD-aware tile order: 34.71 against 34.43 ms, three interleaved runs each)
-    return launch_cfg<MODE, 64, 64, 16, EPI>(g, splits, st, s1);
+    //
+    // The weight-resident kernel takes K = 100, N >= 1024 unsplit when A and C each span less than 2 GiB.  That bound is a CHOICE
+    // of kernel, not a refusal (larger operands run on the generic kernel, whose own limit is check_gemm's 4 GiB): the kernel
+    // puts a token tile's row offset into the range-checked LANE offset of its buffer loads and the output row into a 32-bit
+    // scalar offset beside a lane offset, both handed to the buffer builtins as int; under 2 GiB neither sum can wrap or turn
+    // negative.  (gemm_store_epilogue makes the same `span < 1 << 31` test in device code before it takes the straight-line
+    // epilogue the two kernels share.)
+    const bool wres = k.K == 100 && k.N >= 1024 && p.splits == 1 && (size_t)k.M * k.lda * 4 < (size_t(1) << 31) &&
+                      (size_t)k.M * k.ldc * 4 < (size_t(1) << 31);
+    p.family = wres ? GEMM_WRES : k.K <= 128 ? GEMM_SHORTK : GEMM_GENERIC;
+    const int segs = p.pair ? 2 : 1;
+    p.grid = wres ? dim3(tiles_n, segs * tiles_m) : dim3(tiles_n, segs * tiles_m, p.splits);
+    return p;
 }
+
+// ---- the checks ----
 
 // the K loop reads its operands through buffer descriptors with 32-bit byte offsets (round 5): an operand must span < 4 GiB
 static inline bool fits32(long rows, long ld) { return (unsigned long long)rows * (unsigned long long)ld * 4ull < (1ull << 32); }
@@ -1193,81 +1335,67 @@ static int check_common(const float* A, int lda, const float* B, int ldb, const 
     return 0;
 }
 
-#define EPI_SWITCH(MODE, g, st, s1)                                                        \
-    switch (epi) {                                                                         \
-        case EPI_NONE: return launch_pick<MODE, EPI_NONE>(g, splits, st, s1);              \
-        case EPI_RELU_DROP: return launch_pick<MODE, EPI_RELU_DROP>(g, 1, st, s1);         \
-        case EPI_DROP_GELU: return launch_pick<MODE, EPI_DROP_GELU>(g, 1, st, s1);         \
-        case EPI_MASK_POS: return launch_pick<MODE, EPI_MASK_POS>(g, 1, st, s1);           \
-        case EPI_GELU_BWD_DROP:                                                            \
-        case EPI_GELU_BWD_DROP0: return launch_pick<MODE, EPI_GELU_BWD_DROP>(g, 1, st, s1);\
-        case EPI_GELU_BWD: return launch_pick<MODE, EPI_GELU_BWD>(g, 1, st, s1);           \
-        default: return fail(-1, "gemm: unknown epilogue %d", epi);                        \
+// Every refusal of the dense paths, in the order the launchers used to make them; nothing has been launched or written when one
+// fires.  The plan is made here, as the last step but two: a misaligned TN workspace matters only where the plan would split,
+// and the weight-resident kernel has a two-segment form for linear1's epilogue only.
+static int check_gemm(const GemmCall& k, const Mode md, GemmPlan& p) {
+    const bool nt = k.layout == GEMM_NT, nn = k.layout == GEMM_NN;
+    if (gemm_takes_n100(k, md)) {
+        GF_CHECK_ARG(k.A && k.B && k.C && k.n_slabs && k.M > 0 && n100_supported(k.N, k.K) && k.epi == EPI_NONE && !k.ea.aux_in && k.ldc == k.N,
+                     "gemm_n100: bad arguments (K=%d)", k.K);
+        GF_CHECK_ARG(!k.has_seg1 || (k.seg1.A && k.seg1.C && aligned16(k.seg1.A) && aligned16(k.seg1.C)), "gemm_n100: bad second segment");
+        GF_CHECK_ARG(aligned16(k.A) && aligned16(k.B) && aligned16(k.C) && (k.lda & 3) == 0 && (k.ldb & 3) == 0 && (k.slab_stride & 3) == 0 &&
+                         (!k.ea.bias || aligned16(k.ea.bias)), "gemm_n100: operands must be 16-byte aligned");
+        GF_CHECK_ARG(fits32(k.M, k.lda) && fits32(nn ? k.K : k.N, k.ldb), "gemm_n100: an operand of 4 GiB or more is not supported");
+        p = gemm_plan(k, md);
+        GF_CHECK_ARG(!p.pair || (p.n100 == N100_KW2_TAIL4 && nt), "gemm_n100: no two-segment form of this variant");
+        return 0;
     }
-
-// number of K splits for a plain (EPI_NONE) GEMM whose output has too few tiles to fill 256 CUs
-int gemm_splitk_factor(int M, int N, int K) {
-    const long tiles = (long)((M + 63) / 64) * ((N + 63) / 64);
-    if (tiles >= 384 || K < 512) return 1;
-    long s = (768 + tiles - 1) / tiles;
-    const long maxs = K / 256;
-    if (s > maxs) s = maxs;
-    if (s > 8) s = 8;
-    return s < 1 ? 1 : (int)s;
+    GF_CHECK_ARG(!k.has_seg1 || (nt && (k.epi == EPI_RELU_DROP || k.epi == EPI_NONE)), "gemm_nt_pair: epilogue %d has no two-segment form", k.epi);
+    GF_TRY(check_common(k.A, k.lda, k.B, k.ldb, k.C, k.M, k.N, k.K));
+    GF_CHECK_ARG(!k.has_seg1 || (k.seg1.A && k.seg1.C && aligned16(k.seg1.A) && k.ea.aux_in == nullptr), "gemm_nt_pair: bad second segment");
+    if (nt) GF_CHECK_ARG((k.K & 3) == 0, "gemm_nt: K=%d must be a multiple of 4", k.K);
+    else if (nn) GF_CHECK_ARG((k.K & 3) == 0 && (k.N & 3) == 0, "gemm_nn: K=%d and N=%d must be multiples of 4", k.K, k.N);
+    else GF_CHECK_ARG((k.M & 3) == 0 && (k.N & 3) == 0, "gemm_tn: M=%d and N=%d must be multiples of 4", k.M, k.N);
+    if (nt) GF_CHECK_ARG(fits32(k.M, k.lda) && fits32(k.N, k.ldb), "gemm_nt: an operand of 4 GiB or more is not supported");
+    else if (nn) GF_CHECK_ARG(fits32(k.M, k.lda) && fits32(k.K, k.ldb), "gemm_nn: an operand of 4 GiB or more is not supported");
+    else GF_CHECK_ARG(fits32(k.K, k.lda) && fits32(k.K, k.ldb), "gemm_tn: an operand of 4 GiB or more is not supported");
+    GF_CHECK_ARG(k.layout == GEMM_TN ? k.epi == EPI_NONE : (k.epi >= EPI_NONE && k.epi <= EPI_GELU_BWD_DROP0), "gemm: unknown epilogue %d", k.epi);
+    p = gemm_plan(k, md);
+    GF_CHECK_ARG(p.family != GEMM_TN_ACC || p.splits == 1 || aligned16(k.part_ws), "gemm_tn: partial-slab workspace must be 16-byte aligned");
+    GF_CHECK_ARG(!(p.family == GEMM_WRES && p.pair) || k.epi == EPI_RELU_DROP,
+                 "gemm_nt_pair: no two-segment form of the weight-resident kernel for epilogue %d", k.epi);
+    return 0;
 }
 
-static void set_split(GemmArgs& g, int& splits, long slab_stride) {
-    if (splits <= 1) { splits = 1; g.kchunk = g.K; g.slab_stride = 0; return; }
-    int kchunk = ((g.K + splits - 1) / splits + 63) / 64 * 64;
-    splits = (g.K + kchunk - 1) / kchunk;
-    g.kchunk = kchunk;
-    g.slab_stride = slab_stride;
+// ---- the launch blocks: one per kernel template ----
+
+// f(integral_constant<int, EPI>) for the epilogue the plan names; check_gemm has refused every other value
+template <class F>
+static inline int with_epi(int epi, F&& f) {
+    switch (epi) {
+        case EPI_RELU_DROP: return f(std::integral_constant<int, EPI_RELU_DROP>{});
+        case EPI_DROP_GELU: return f(std::integral_constant<int, EPI_DROP_GELU>{});
+        case EPI_MASK_POS: return f(std::integral_constant<int, EPI_MASK_POS>{});
+        case EPI_GELU_BWD_DROP: return f(std::integral_constant<int, EPI_GELU_BWD_DROP>{});
+        case EPI_GELU_BWD: return f(std::integral_constant<int, EPI_GELU_BWD>{});
+        default: return f(std::integral_constant<int, EPI_NONE>{});
+    }
 }
 
-// splits > 1 (EPI_NONE only): split z writes its partial to C + z*slab_stride; the consumer sums the slabs.
-// *splits_io returns the number of slabs actually written.
-// s1 (or null): a second row segment [M x K] against the same weight in the same launch (plain / split-K product and linear1's
-// epilogue): segment 0 as given, segment 1 with s1's operands; the same kernel, K split and slab layout as for one segment
-int launch_gemm_nt(const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N, int K,
-                   int epi, const EpiArgs& ea, hipStream_t st, int* splits_io, long slab_stride, const GemmSeg1* s1) {
-    GF_CHECK_ARG(!s1 || epi == EPI_RELU_DROP || epi == EPI_NONE, "gemm_nt_pair: epilogue %d has no two-segment form", epi);
-    GF_TRY(check_common(A, lda, W, ldw, C, M, N, K));
-    GF_CHECK_ARG(!s1 || (s1->A && s1->C && aligned16(s1->A) && ea.aux_in == nullptr), "gemm_nt_pair: bad second segment");
-    GF_CHECK_ARG((K & 3) == 0, "gemm_nt: K=%d must be a multiple of 4", K);
-    GF_CHECK_ARG(fits32(M, lda) && fits32(N, ldw), "gemm_nt: an operand of 4 GiB or more is not supported");
-    GemmArgs g{A, lda, W, ldw, C, ldc, nullptr, M, N, K, K, 0, ea};
-    int splits = (splits_io && epi == EPI_NONE) ? *splits_io : 1;
-    set_split(g, splits, slab_stride);
-    if (splits_io) *splits_io = splits;
-    EPI_SWITCH(MODE_NT, g, st, s1)
-}
-
-int launch_gemm_nn(const float* A, int lda, const float* Bm, int ldb, float* C, int ldc, int M, int N, int K,
-                   int epi, const EpiArgs& ea, hipStream_t st, int* splits_io, long slab_stride) {
-    GF_TRY(check_common(A, lda, Bm, ldb, C, M, N, K));
-    GF_CHECK_ARG((K & 3) == 0 && (N & 3) == 0, "gemm_nn: K=%d and N=%d must be multiples of 4", K, N);
-    GF_CHECK_ARG(fits32(M, lda) && fits32(K, ldb), "gemm_nn: an operand of 4 GiB or more is not supported");
-    GemmArgs g{A, lda, Bm, ldb, C, ldc, nullptr, M, N, K, K, 0, ea};
-    int splits = (splits_io && epi == EPI_NONE) ? *splits_io : 1;
-    set_split(g, splits, slab_stride);
-    if (splits_io) *splits_io = splits;
-    EPI_SWITCH(MODE_NN, g, st, nullptr)
-}
-
-// A one- or two-tile gradient (the discriminator head's fc1 [64 x 100] / fc2 [16 x 64]) used to be cut into K / 64 = 94
-// slabs: the 6 us GEMM was followed by a 40 us reduce launch whose 2-7 workgroups walk 94 slabs one batch of loads after
-// the other (profiles/r02_*: tn_reduce_kernel 1.4 % of the step).  16 slabs keep the GEMM as short and the reduce at its floor.
-constexpr long TN_ACC_MAXSPLIT = 16;
-
-// floats of partial-slab workspace a split TN launch of this shape can use (0: it will not split)
-long gemm_tn_part_floats(int M, int N, int K) {
-    const long tiles = (long)((M + 63) / 64) * ((N + 63) / 64);
-    long splits = (768 + tiles - 1) / tiles;             // ~3 blocks per CU measured best (tools/gemm_bench.py)
-    const long maxsplits = (K + 63) / 64;                // at least 64 k per block
-    if (splits > maxsplits) splits = maxsplits;
-    if (splits > TN_ACC_MAXSPLIT) splits = TN_ACC_MAXSPLIT;
-    if (splits <= 1) return 0;
-    return splits * ((long)M * N + M);
+// gemm_kernel / gemm_pair_kernel on 64 x 64 x 16 tiles.  s1 (PAIR): the second row segment — the same tiles again along grid y
+template <int MODE, int EPI, int SHORTK, bool PAIR>
+static int launch_tiles(const GemmArgs& g, const dim3 grid, hipStream_t st, const GemmSeg1* s1) {
+    constexpr size_t lds = Smem<MODE, 64, 64, 16>::TOTAL * sizeof(float);
+    if constexpr (PAIR) {
+        GF_TRY((lds_optin<gemm_pair_kernel<MODE, 64, 64, 16, EPI, 2, 2, SHORTK>>(lds, "gemm")));
+        hipLaunchKernelGGL((gemm_pair_kernel<MODE, 64, 64, 16, EPI, 2, 2, SHORTK>), grid, dim3(256), lds, st, g, *s1, (int)grid.y / 2);
+    } else {
+        GF_TRY((lds_optin<gemm_kernel<MODE, 64, 64, 16, EPI, 2, 2, SHORTK>>(lds, "gemm")));
+        hipLaunchKernelGGL((gemm_kernel<MODE, 64, 64, 16, EPI, 2, 2, SHORTK>), grid, dim3(256), lds, st, g);
+    }
+    GF_LAUNCH_CHECK();
+    return 0;
 }
 
 static int launch_tn_reduce(float* C, int ldc, float* colsum, const float* part, long part_stride, int splits, int M, int N,
@@ -1280,45 +1408,44 @@ static int launch_tn_reduce(float* C, int ldc, float* colsum, const float* part,
     return 0;
 }
 
-// C[M x N] += At^T B (+ column sums of At).  With a partial-slab workspace (part_ws, part_floats) the K range is split
-// over workgroups (slabs + ordered reduce: deterministic); without one a single workgroup per tile runs the whole K.
-int launch_gemm_tn_acc(const float* At, int lda, const float* Bm, int ldb, float* C, int ldc, float* colsum,
-                       int M, int N, int K, hipStream_t st, float* part_ws, long part_floats) {
-    GF_TRY(check_common(At, lda, Bm, ldb, C, M, N, K));
-    GF_CHECK_ARG((M & 3) == 0 && (N & 3) == 0, "gemm_tn: M=%d and N=%d must be multiples of 4", M, N);
-    GF_CHECK_ARG(fits32(K, lda) && fits32(K, ldb), "gemm_tn: an operand of 4 GiB or more is not supported");
-    EpiArgs ea;
-    GemmArgs g{At, lda, Bm, ldb, C, ldc, colsum, M, N, K, K, 0, ea};
-    const long tiles = (long)((M + 63) / 64) * ((N + 63) / 64);
-    const long per = (long)M * N + M;
-    long splits = (768 + tiles - 1) / tiles;
-    const long maxsplits = (K + 63) / 64;
-    if (splits > maxsplits) splits = maxsplits;
-    if (splits > TN_ACC_MAXSPLIT) splits = TN_ACC_MAXSPLIT;
-    if (part_ws == nullptr) splits = 1;
-    else if (splits * per > part_floats) splits = part_floats / per;
-    if (splits < 1) splits = 1;
-    int kchunk = (int)(((K + splits - 1) / splits + 63) / 64 * 64);   // multiple of every BK
-    splits = (K + kchunk - 1) / kchunk;
-    g.kchunk = kchunk;
-    if (splits > 1) {
-        GF_CHECK_ARG(aligned16(part_ws), "gemm_tn: partial-slab workspace must be 16-byte aligned");
-        g.part = part_ws;
-        g.part_stride = (per + 3) & ~3L;
-        if (splits * g.part_stride > part_floats) { splits = 1; g.part = nullptr; g.kchunk = K; }
+int gemm(const GemmCall& k) {
+    GemmPlan p;
+    GF_TRY(check_gemm(k, mode(), p));
+    if (k.n_slabs) *k.n_slabs = p.splits;
+    if (p.family == GEMM_N100) return launch_gemm_n100(k, p);
+    GemmArgs g{k.A, k.lda, k.B, k.ldb, k.C, k.ldc, k.colsum, k.M, k.N, k.K, p.kchunk, 0, k.ea};
+    if (p.family == GEMM_TN_ACC) {
+        // C += At^T B (+ column sums of At): split, the workgroups store partial slabs and an ordered reduce adds them; unsplit,
+        // the single owner workgroup of a tile runs the whole K and adds in place
+        if (p.splits > 1) { g.part = k.part_ws; g.part_stride = p.slab_stride; }
+        GF_TRY((launch_tiles<MODE_TN, EPI_NONE, 0, false>(g, p.grid, k.st, nullptr)));
+        if (p.splits > 1) GF_TRY(launch_tn_reduce(k.C, k.ldc, k.colsum, g.part, g.part_stride, p.splits, k.M, k.N, k.st));
+        return 0;
     }
-    GF_TRY((launch_cfg<MODE_TN, 64, 64, 16, EPI_NONE>(g, (int)splits, st)));
-    if (splits > 1) GF_TRY(launch_tn_reduce(C, ldc, colsum, g.part, g.part_stride, (int)splits, M, N, st));
-    return 0;
+    g.slab_stride = p.slab_stride;
+    const GemmSeg1* const s1 = p.pair ? &k.seg1 : nullptr;
+    return with_flag(k.layout == GEMM_NN, [&](auto is_nn) {
+        return with_epi(p.epi, [&](auto epi) {
+            return with_flag(p.pair, [&](auto pair) {
+                constexpr int MODE = decltype(is_nn)::value ? MODE_NN : MODE_NT, EPI = decltype(epi)::value;
+                constexpr bool PAIR = decltype(pair)::value;
+                // (the two-segment kernels that do not exist are not instantiated; check_gemm has refused the calls that would name them)
+                constexpr bool TILES = !PAIR || HAS_PAIR<MODE, EPI>, WRES = !PAIR || (MODE == MODE_NT && EPI == EPI_RELU_DROP);
+                if constexpr (WRES)
+                    if (p.family == GEMM_WRES) return launch_wres<MODE, EPI, PAIR>(g, p.grid, k.st, s1);
+                if constexpr (TILES) {
+                    if (p.family == GEMM_SHORTK) return launch_tiles<MODE, EPI, 1, PAIR>(g, p.grid, k.st, s1);
+                    if (p.family == GEMM_GENERIC) return launch_tiles<MODE, EPI, 0, PAIR>(g, p.grid, k.st, s1);
+                }
+                return fail(-1, "gemm: no kernel for layout %d, epilogue %d, family %d%s", MODE, EPI, (int)p.family, PAIR ? ", two segments" : "");
+            });
+        });
+    });
 }
 
-// A grouped launch with fewer than TN_GROUP_MIN_TILES output tiles (4 per CU) splits the token range of every tile so that
-// about TN_GROUP_TILES workgroups exist.  Measured at 1136 tiles (a whole d_model-100 backward pass, T = 6016): unsplit
-// 446 us; split in 3: 424 us + 20 us for the reduce launch — no gain, so such groups stay on the owner-only path; the
-// narrow groups this is for are the 1-4-layer gradient buckets of the data-parallel path (142-568 tiles).
-constexpr int TN_GROUP_MIN_TILES = 1024;
-constexpr int TN_GROUP_TILES = 2560;
-constexpr int TN_GROUP_MAXSPLIT = 8;
+// ------------------------------------------------------------------------------------------------------------------
+// Grouped weight-gradient launch: dW_i[M_i x N_i] += At_i^T B_i for n problems in one launch (see gemm_tn_grouped_kernel).
+// ------------------------------------------------------------------------------------------------------------------
 
 // C_i += sum_z part[z][i], colsum_i += sum_z part[z][M N + i] for every problem of a split grouped launch, slabs in split
 // order; blockIdx.y = problem, blockIdx.x strides over its elements
@@ -1348,57 +1475,65 @@ __global__ __launch_bounds__(256) void tn_reduce_grouped_kernel(TnGroup grp) {
         }
 }
 
-long gemm_tn_grouped_part_floats() { return (long)(TN_GROUP_TILES + 256) * (64 * 64 + 64) + 4 * MAXP; }
+// one problem of a grouped launch, for the generic kernels and for gemm_tn100.hip alike (who: the launcher named in the messages)
+static int check_tn_desc(const TnDesc& d, const char* who) {
+    GF_CHECK_ARG(fits32(d.K, d.lda) && fits32(d.K, d.ldb), "%s: an operand of 4 GiB or more is not supported", who);
+    GF_TRY(check_common(d.At, d.lda, d.B, d.ldb, d.C, d.M, d.N, d.K));
+    GF_CHECK_ARG((d.M & 3) == 0 && (d.N & 3) == 0, "%s: M, N must be multiples of 4", who);
+    return 0;
+}
 
-// dW_i[M_i x N_i] += At_i^T B_i for n problems in one launch (see gemm_tn_grouped_kernel).  Groups of >= 1024 tiles (one
-// encoder backward pass: 6144 tiles at d_model 512, 1136 at 100): every output tile has one owner workgroup that runs the
-// whole token range and adds its result in place.  Narrower groups (a 2-layer gradient bucket: 284 tiles on 256 CUs) with
-// a workspace: the token range is split, the partial tiles go to per-split slabs and one reduce launch adds them in split
-// order.  Deterministic either way.
+// every problem 100-wide on one side (a d_model-100 encoder pass) and a usable workspace: 112-wide 16x16x4 tiles (gemm_tn100.hip)
+static bool tn_grouped_takes_tn100(const TnDesc* d, int n, const float* part_ws, const Mode md) {
+    return !md.tn100_off() && part_ws != nullptr && aligned16(part_ws) && tn100_supported(d, n);
+}
+// what a group that gemm_tn100.hip does not take runs on
+enum TnGroupedForm : int {
+    TNG_WIDE,        // 64 x 128 tiles, one owner workgroup per tile
+    TNG_OWNER,       // 64 x 64 tiles, one owner workgroup per tile over the whole token range, adds in place
+    TNG_SPLIT,       // 64 x 64 tiles, token range split: partial tiles to per-split slabs, one reduce launch adds them in order
+};
+struct TnGroupedPlan { TnGroupedForm form; int BN, splits; long per_split; };
+
+// Groups of >= 1024 tiles (one encoder backward pass: 6144 tiles at d_model 512, 1136 at 100): every output tile has one owner.
+// Narrower groups (a 2-layer gradient bucket: 284 tiles on 256 CUs) with a workspace: split.  Deterministic either way.
+// 64 x 128 tiles (two accumulators per wave sharing the A fragment: the single-accumulator MFMA chain of the 64 x 64
+// tile is issue-limited) when every problem's N is a multiple of 128 and the group keeps >= 4 such tiles per CU.
+// Measured (tools/lab/tn_wide.py, same bits): the d_model-512 group 1270 -> 1212 us; the d_model-100 group would drop
+// to 568 tiles (N = 100 -> one 128-wide tile) and gets slower (543 -> 639 us), so it stays on 64 x 64.
+// (pure host code; the problems have passed check_tn_desc)
+static TnGroupedPlan tn_grouped_plan(const TnDesc* d, int n, const float* part_ws, long part_floats) {
+    TnGroupedPlan p{TNG_OWNER, 64, 1, 0};
+    bool wide = true, reducible = true;
+    long wtiles = 0, tiles = 0;
+    int kmax = 0;
+    for (int i = 0; i < n; ++i) {
+        wide = wide && (d[i].N % 128 == 0);
+        wtiles += (long)((d[i].M + 63) / 64) * ((d[i].N + 127) / 128);
+        tiles += (long)((d[i].M + 63) / 64) * ((d[i].N + 63) / 64);
+        p.per_split += (tn_acc_slab_floats(d[i].M, d[i].N) + 3) & ~3L;
+        kmax = d[i].K > kmax ? d[i].K : kmax;
+        if (!aligned16(d[i].C) || (d[i].ldc & 3) != 0) reducible = false;     // the reduce adds 16-byte vectors in place
+    }
+    if (wide && wtiles >= TN_GROUP_MIN_TILES) { p.form = TNG_WIDE; p.BN = 128; return p; }    // (>= the split rule's threshold: unsplit)
+    p.splits = tn_grouped_splits(tiles, kmax, p.per_split, part_ws != nullptr && reducible, part_floats);
+    if (p.splits > 1) p.form = TNG_SPLIT;
+    return p;
+}
 
 int launch_gemm_tn_grouped(const TnDesc* d, int n, hipStream_t st, float* part_ws, long part_floats, TnSlabs* slabs) {
     GF_CHECK_ARG(d && n >= 1 && n <= MAXP, "gemm_tn_grouped: n=%d out of [1,%d]", n, MAXP);
-    // every problem 100-wide on one side (a d_model-100 encoder pass): 112-wide 16x16x4 tiles (gemm_tn100.hip)
-    if (!mode().tn100_off() && part_ws != nullptr && aligned16(part_ws) && tn100_supported(d, n))
-        return launch_gemm_tn100_grouped(d, n, st, part_ws, part_floats, slabs);
-    GF_CHECK_ARG(slabs == nullptr, "gemm_tn_grouped: unreduced gradient slabs exist only for the d_model-100 kernel");
+    const bool tn100 = tn_grouped_takes_tn100(d, n, part_ws, mode());
+    GF_CHECK_ARG(tn100 || slabs == nullptr, "gemm_tn_grouped: unreduced gradient slabs exist only for the d_model-100 kernel");
+    for (int i = 0; i < n; ++i) GF_TRY(check_tn_desc(d[i], tn100 ? "gemm_tn100_grouped" : "gemm_tn_grouped"));
+    if (tn100) return launch_gemm_tn100_grouped(d, n, st, part_ws, part_floats, slabs);
+    const TnGroupedPlan p = tn_grouped_plan(d, n, part_ws, part_floats);
+    GF_CHECK_ARG(p.splits == 1 || aligned16(part_ws), "gemm_tn_grouped: partial-slab workspace must be 16-byte aligned");
     TnGroup grp;
     grp.n = n;
-    // 64 x 128 tiles (two accumulators per wave sharing the A fragment: the single-accumulator MFMA chain of the 64 x 64
-    // tile is issue-limited) when every problem's N is a multiple of 128 and the group keeps >= 4 such tiles per CU.
-    // Measured (tools/lab/tn_wide.py, same bits): the d_model-512 group 1270 -> 1212 us; the d_model-100 group would drop
-    // to 568 tiles (N = 100 -> one 128-wide tile) and gets slower (543 -> 639 us), so it stays on 64 x 64.
-    bool wide = true;
-    long wtiles = 0;
-    for (int i = 0; i < n; ++i) {
-        GF_CHECK_ARG(fits32(d[i].K, d[i].lda) && fits32(d[i].K, d[i].ldb), "gemm_tn_grouped: an operand of 4 GiB or more is not supported");
-        wide = wide && (d[i].N % 128 == 0);
-        wtiles += (long)((d[i].M + 63) / 64) * ((d[i].N + 127) / 128);
-    }
-    wide = wide && wtiles >= TN_GROUP_MIN_TILES;
-    const int BNs = wide ? 128 : 64;
-    long tiles = 0, per_split = 0;
-    int kmax = 0;
-    for (int i = 0; i < n; ++i) {
-        GF_TRY(check_common(d[i].At, d[i].lda, d[i].B, d[i].ldb, d[i].C, d[i].M, d[i].N, d[i].K));
-        GF_CHECK_ARG((d[i].M & 3) == 0 && (d[i].N & 3) == 0, "gemm_tn_grouped: M, N must be multiples of 4");
-        tiles += (long)((d[i].M + 63) / 64) * ((d[i].N + BNs - 1) / BNs);
-        per_split += (((long)d[i].M * d[i].N + d[i].M) + 3) & ~3L;
-        kmax = d[i].K > kmax ? d[i].K : kmax;
-        if (!aligned16(d[i].C) || (d[i].ldc & 3) != 0) part_ws = nullptr;     // the reduce adds 16-byte vectors in place
-    }
-    int splits = 1;
-    if (part_ws != nullptr && tiles < TN_GROUP_MIN_TILES) {
-        splits = (int)((TN_GROUP_TILES + tiles - 1) / tiles);
-        if (splits > TN_GROUP_MAXSPLIT) splits = TN_GROUP_MAXSPLIT;
-        if (splits > kmax / 256) splits = kmax / 256;             // >= 256 tokens per workgroup of the longest problem
-        if ((long)splits * per_split > part_floats) splits = (int)(part_floats / per_split);
-        if (splits < 2) splits = 1;
-    }
-    grp.splits = splits;
-    grp.part = splits > 1 ? part_ws : nullptr;
-    grp.part_stride = per_split;
-    GF_CHECK_ARG(splits == 1 || aligned16(part_ws), "gemm_tn_grouped: partial-slab workspace must be 16-byte aligned");
+    grp.splits = p.splits;
+    grp.part = p.splits > 1 ? part_ws : nullptr;
+    grp.part_stride = p.per_split;
     int total = 0;
     long off = 0;
     for (int i = 0; i < n; ++i) {
@@ -1406,26 +1541,28 @@ int launch_gemm_tn_grouped(const TnDesc* d, int n, hipStream_t st, float* part_w
         q.A = d[i].At; q.B = d[i].B; q.C = d[i].C; q.colsum = d[i].colsum;
         q.lda = d[i].lda; q.ldb = d[i].ldb; q.ldc = d[i].ldc; q.M = d[i].M; q.N = d[i].N; q.K = d[i].K;
         // chunk: a multiple of 64 tokens; problems with different K in one group simply get fewer non-empty splits
-        q.kchunk = splits > 1 ? (int)((((long)d[i].K + splits - 1) / splits + 63) / 64 * 64) : d[i].K;
+        q.kchunk = p.splits > 1 ? (int)((((long)d[i].K + p.splits - 1) / p.splits + 63) / 64 * 64) : d[i].K;
         const int tm = (d[i].M + 63) / 64;
-        q.tiles_n = (d[i].N + BNs - 1) / BNs;
+        q.tiles_n = (d[i].N + p.BN - 1) / p.BN;
         q.tiles_mn = tm * q.tiles_n;
         q.block0 = total;
         q.part_off = off;
-        off += (((long)d[i].M * d[i].N + d[i].M) + 3) & ~3L;
-        total += q.tiles_mn * splits;
+        off += (tn_acc_slab_floats(d[i].M, d[i].N) + 3) & ~3L;
+        total += q.tiles_mn * p.splits;
     }
-    if (wide && splits == 1) {
-        constexpr size_t ldsw = Smem<MODE_TN, 64, 128, 16>::TOTAL * sizeof(float);
-        hipLaunchKernelGGL((gemm_tn_grouped_kernel<false, 128>), dim3(total), dim3(256), ldsw, st, grp);
+    // SPLIT = false: no partial-slab code in the kernel at all (gemm_tn_grouped_kernel)
+    auto launch = [&](auto split, auto bn) {
+        constexpr bool SPLIT = decltype(split)::value;
+        constexpr int BN = decltype(bn)::value;
+        constexpr size_t lds = Smem<MODE_TN, 64, BN, 16>::TOTAL * sizeof(float);
+        hipLaunchKernelGGL((gemm_tn_grouped_kernel<SPLIT, BN>), dim3(total), dim3(256), lds, st, grp);
         GF_LAUNCH_CHECK();
         return 0;
-    }
-    constexpr size_t lds = Smem<MODE_TN, 64, 64, 16>::TOTAL * sizeof(float);
-    if (splits > 1) hipLaunchKernelGGL(gemm_tn_grouped_kernel<true>, dim3(total), dim3(256), lds, st, grp);
-    else hipLaunchKernelGGL(gemm_tn_grouped_kernel<false>, dim3(total), dim3(256), lds, st, grp);
-    GF_LAUNCH_CHECK();
-    if (splits > 1) {
+    };
+    using BN64 = std::integral_constant<int, 64>;
+    GF_TRY(p.form == TNG_WIDE ? launch(std::false_type{}, std::integral_constant<int, 128>{})
+                              : p.form == TNG_SPLIT ? launch(std::true_type{}, BN64{}) : launch(std::false_type{}, BN64{}));
+    if (p.form == TNG_SPLIT) {
         hipLaunchKernelGGL(tn_reduce_grouped_kernel, dim3(64, n), dim3(256), 0, st, grp);
         GF_LAUNCH_CHECK();
     }

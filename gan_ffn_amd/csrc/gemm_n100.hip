@@ -30,7 +30,7 @@ typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-constexpr int NE = 100, NT7 = 7, NBK = 32, NBM = 64;
+constexpr int NE = 100, NT7 = 7, NBK = N100_BK, NBM = N100_BM;
 constexpr int LDWK = 116;          // K-major weight tile [32][116]: rows 4 apart sit 16 banks apart (116 = 4 mod 8)
 
 // K-contiguous LDS tile [rows][32]: 16-byte slot s of row r at slot s ^ ((r / 2) % 8) (gemm.hip kc_off<32>)
@@ -271,83 +271,40 @@ __global__ __launch_bounds__(256 * KW) void gemm_n100_pair_kernel(N100Args a, co
 
 }  // namespace
 
-// lab knobs of the mode word (common.h `Mode`): bits 8..15 force the K-chunk count, bit 23 = features 96..99 on a padded seventh
-// 16-wide tile (round 3's form), bits 20..21 force four (1) or eight (2) waves per workgroup
+// ------------------------------------------------------------------------------------------------------------------
+// driver: gemm.hip's check_gemm has refused what this kernel does not take, gemm_plan has chosen the K chunks, the variant
+// and the grid (its chunk rule, n100_splits, stands beside gemm.hip's other split rules)
+// ------------------------------------------------------------------------------------------------------------------
 GF_LAB_ONLY(unsigned long long* g_n100_stamps = nullptr;)   // lab builds only: device buffer for in-kernel time stamps
 
 bool n100_supported(int N, int K) { return N == NE && K >= 256 && (K % NBK) == 0; }
 
-// K chunks (= output slabs, <= max_splits) and waves per workgroup.  Measured on MI355X (tools/lab/n100_lab.py, K = 2048,
-// gpurun_out/r4_n100_lab.txt; round 3's 4-wave numbers in brackets):
-//  * 8 waves (two per 16-token group, one 16-wide half of every K tile each): rows-of-K weights T = 3008: 4 / 5 / 8 / 10 / 16
-//    chunks 20.8 / 18.1 / 20.1 / 19.2 / 22.9 us [22.0 / 19.1 / 20.4 / 19.0 / 19.0]; T = 6016: 4 / 5 / 6 / 8 chunks
-//    34.0 / 29.2 / 41.2 / 36.1 us [35.4 / 30.5 / 35.1 / 29.9];
-//  * K-major weights (58 LDS reads per tile instead of 16): T = 3008: 5 / 8 / 16 chunks 19.3 / 20.3 / 18.1 us
-//    [22.9 / 21.6 / 18.5]; T = 6016: 5 / 6 / 8 chunks 29.9 / 34.0 / 29.1 us [32.4 / 35.0 / 29.9] — with the second wave per
-//    SIMD inside the workgroup the K-major layout no longer needs the extra chunks (and their slabs) for co-residency.
-// Rule (8 waves): a CU runs its workgroups' MFMA work back to back, so the launch costs ceil(workgroups / 256 CUs) x the
-// chunk's K tiles, plus the slab traffic: every slab is written here and read again by the LayerNorm-side consumer
-// (~0.8 tile-times per slab at T = 3008; the consumer at T = 6016 with 8 slabs is bandwidth-bound on them: 19 MB).
-int n100_splits(int T, int K, int max_splits, int w_kmajor) {
-    if (const int fs = mode().n100_force_splits(); fs > 0) return fs < max_splits ? fs : max_splits;
-    const int tiles_m = (T + NBM - 1) / NBM, ksteps = K / NBK;
-    int best = 1;
-    double best_cost = 1e30;
-    for (int s = 1; s <= max_splits && s <= ksteps; ++s) {
-        const int per = (ksteps + s - 1) / s;
-        if ((s - 1) * per >= ksteps) continue;                       // an empty last chunk
-        const long wgs = (long)tiles_m * s;
-        const long rounds = (wgs + 255) / 256;
-        const double cost = (double)rounds * per + 0.8 * ((double)T / 3008.0) * s;
-        if (cost < best_cost) { best_cost = cost; best = s; }
-    }
-    (void)w_kmajor;
-    return best;
-}
-
-// waves per 16-token group along K: two (8-wave workgroups) — faster at every chunk count the rule above picks; the 4-wave
-// form stays behind the lab knob for A/B
-static int n100_kw(int T, int splits) {
-    (void)T; (void)splits;
-    return 2;
-}
-
-// C slabs = A[T x K] . W^T (w_kmajor == 0: W [100 x K]) or A . W (w_kmajor == 1: W [K x 100]); *splits_io: in = cap, out = slabs written
-int launch_gemm_n100(const float* A, int lda, const float* W, int ldw, int w_kmajor, const float* bias, float* C, long slab_stride,
-                     int T, int K, int* splits_io, hipStream_t st, const float* A1, float* C1) {
-    GF_CHECK_ARG(A && W && C && splits_io && T > 0 && n100_supported(NE, K), "gemm_n100: bad arguments (K=%d)", K);
-    GF_CHECK_ARG((A1 == nullptr) == (C1 == nullptr) && aligned16(A1) && aligned16(C1), "gemm_n100: bad second segment");
-    GF_CHECK_ARG(aligned16(A) && aligned16(W) && aligned16(C) && (lda & 3) == 0 && (ldw & 3) == 0 && (slab_stride & 3) == 0 &&
-                     (!bias || aligned16(bias)), "gemm_n100: operands must be 16-byte aligned");
-    GF_CHECK_ARG((unsigned long long)T * (unsigned long long)lda * 4ull < (1ull << 32) &&
-                     (unsigned long long)(w_kmajor ? K : NE) * (unsigned long long)ldw * 4ull < (1ull << 32),
-                 "gemm_n100: an operand of 4 GiB or more is not supported");
-    const int ksteps = K / NBK;
-    int s = n100_splits(T, K, *splits_io < 1 ? 1 : *splits_io, w_kmajor);
-    const int per = (ksteps + s - 1) / s;
-    s = (ksteps + per - 1) / per;
-    *splits_io = s;
-    N100Args a{A, lda, W, ldw, bias, C, slab_stride, T, K, per * NBK GF_LAB_ONLY(, g_n100_stamps)};
-    const dim3 grid((T + NBM - 1) / NBM, s);
-    const Mode md = mode();
-    const int kw = md.n100_force_kw() ? md.n100_force_kw() : n100_kw(T, s);
-    if (A1) {
-        // second segment: the product form only (eight waves, 4x4x1 tail, weight as rows of K); the chunk count above is the
-        // single-segment launch's (T, not 2 T: the slab order is part of the result)
-        GF_CHECK_ARG(kw == 2 && !md.n100_pad7() && !w_kmajor, "gemm_n100: no two-segment form of this variant");
-        hipLaunchKernelGGL((gemm_n100_pair_kernel<false, 2, true>), dim3(2 * grid.x, s), dim3(512), 0, st, a, A1, C1, (int)grid.x);
-    } else if (kw == 2 && !md.n100_pad7()) {
-        if (w_kmajor) hipLaunchKernelGGL((gemm_n100_kernel<true, 2, true>), grid, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((gemm_n100_kernel<false, 2, true>), grid, dim3(512), 0, st, a);
-    } else if (kw == 2) {
-        if (w_kmajor) hipLaunchKernelGGL((gemm_n100_kernel<true, 2, false>), grid, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((gemm_n100_kernel<false, 2, false>), grid, dim3(512), 0, st, a);
-    } else {
-        if (w_kmajor) hipLaunchKernelGGL((gemm_n100_kernel<true, 1, false>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((gemm_n100_kernel<false, 1, false>), grid, dim3(256), 0, st, a);
-    }
-    GF_LAUNCH_CHECK();
-    return 0;
+// C slabs = A[T x K] . W^T (GEMM_NT: W [100 x K]) or A . W (GEMM_NN: W [K x 100]); the second segment (A, C of k.seg1) runs as
+// the product form only: eight waves, 4x4x1 tail, weight as rows of K — check_gemm has refused every other variant with one
+int launch_gemm_n100(const GemmCall& k, const GemmPlan& p) {
+    const N100Args a{k.A, k.lda, k.B, k.ldb, k.ea.bias, k.C, k.slab_stride, k.M, k.K, p.kchunk GF_LAB_ONLY(, g_n100_stamps)};
+    return with_flag(k.layout == GEMM_NN, [&](auto wkmajor) {
+        auto variant = [&](auto v) {
+            constexpr bool WK = decltype(wkmajor)::value;
+            constexpr int KW = decltype(v)::value == N100_KW1_PAD7 ? 1 : 2;
+            constexpr bool TAIL4 = decltype(v)::value == N100_KW2_TAIL4;
+            if constexpr (!WK && KW == 2 && TAIL4) {
+                if (p.pair) {
+                    hipLaunchKernelGGL((gemm_n100_pair_kernel<false, 2, true>), p.grid, dim3(512), 0, k.st, a, k.seg1.A, k.seg1.C, (int)p.grid.x / 2);
+                    GF_LAUNCH_CHECK();
+                    return 0;
+                }
+            }
+            hipLaunchKernelGGL((gemm_n100_kernel<WK, KW, TAIL4>), p.grid, dim3(256 * KW), 0, k.st, a);
+            GF_LAUNCH_CHECK();
+            return 0;
+        };
+        switch (p.n100) {
+            case N100_KW2_TAIL4: return variant(std::integral_constant<int, N100_KW2_TAIL4>{});
+            case N100_KW2_PAD7: return variant(std::integral_constant<int, N100_KW2_PAD7>{});
+            default: return variant(std::integral_constant<int, N100_KW1_PAD7>{});
+        }
+    });
 }
 
 }  // namespace ganffn

@@ -474,12 +474,10 @@ long tn100_part_floats(const TnDesc* d, int n) {
 }
 
 // slabs (optional): the caller wants the weight gradients UNREDUCED (TnSlabs, common.h): no reduce launch, chunk 0 overwrites the
-// gradient slab, chunks 1.. go to gradient-shaped slabs at the head of part_ws
+// gradient slab, chunks 1.. go to gradient-shaped slabs at the head of part_ws.
+// Its one caller, launch_gemm_tn_grouped (gemm.hip), has found the group tn100_supported and put every problem through
+// check_tn_desc (pointers, shapes, operands under 4 GiB).
 int launch_gemm_tn100_grouped(const TnDesc* d, int n, hipStream_t st, float* part_ws, long part_floats, TnSlabs* slabs) {
-    GF_CHECK_ARG(tn100_supported(d, n), "gemm_tn100_grouped: unsupported group");
-    for (int i = 0; i < n; ++i)
-        GF_CHECK_ARG((unsigned long long)d[i].K * (unsigned long long)(d[i].lda > d[i].ldb ? d[i].lda : d[i].ldb) * 4ull < (1ull << 32),
-                     "gemm_tn100_grouped: an operand of 4 GiB or more is not supported");
     const Mode md = mode();
     W100Group grp;
     grp.n = n;

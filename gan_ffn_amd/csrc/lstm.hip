@@ -317,9 +317,7 @@ static int lstm_layer_fwd(const LstmCall& k) {
     const int T = (int)L.T;
     float* out = k.out; float* saved = k.saved; float* ws = k.workspace;
     for (int d = 0; d < 2; ++d) {
-        EpiArgs e;
-        e.bias = k.b_ih[d];
-        GF_TRY(launch_gemm_nt(k.x, In, k.w_ih[d], In, ws + L.xg_at(d, 0), 4 * H, T, 4 * H, In, EPI_NONE, e, k.st));
+        GF_TRY(gemm(gemm_nt(k.x, k.w_ih[d], ws + L.xg_at(d, 0), T, 4 * H, In).bias(k.b_ih[d]).on(k.st)));
     }
     for (int t = 0; t < S; ++t) {
         SkinnyGroup sg;
@@ -368,13 +366,13 @@ static int lstm_layer_bwd(const LstmCall& k) {
     float* part = ws + L.part;
     for (int d = 0; d < 2; ++d) {
         const float* dGd = ws + L.dG_at(d, 0);
-        if (k.gw_ih && k.gw_ih[d]) GF_TRY(launch_gemm_tn_acc(dGd, 4 * H, k.x, In, k.gw_ih[d], In, nullptr, 4 * H, In, T, k.st, part, L.part_floats));
+        if (k.gw_ih && k.gw_ih[d]) GF_TRY(gemm(gemm_tn(dGd, k.x, k.gw_ih[d], 4 * H, In, T).tn_workspace(part, L.part_floats).on(k.st)));
         if (k.gw_hh && k.gw_hh[d] && S > 1) {
             // h_prev of time tm: forward direction out[tm - 1], reverse direction out[tm + 1] (zero at the direction's first step):
             // the forward direction pairs dG of times 1 .. S-1 with out of 0 .. S-2, the reverse one dG of 0 .. S-2 with out of 1 .. S-1
             const int from = d == 0 ? 1 : 0;
-            GF_TRY(launch_gemm_tn_acc(ws + L.dG_at(d, from), 4 * H, out + L.h_at(d, 1 - from), 2 * H, k.gw_hh[d], H, nullptr, 4 * H, H, T - B, k.st,
-                                      part, L.part_floats));
+            GF_TRY(gemm(gemm_tn(ws + L.dG_at(d, from), out + L.h_at(d, 1 - from), k.gw_hh[d], 4 * H, H, T - B).ld(4 * H, 2 * H, H)
+                            .tn_workspace(part, L.part_floats).on(k.st)));
         }
         float* b1 = k.gb_ih ? k.gb_ih[d] : nullptr;
         float* b2 = k.gb_hh ? k.gb_hh[d] : nullptr;
@@ -384,11 +382,9 @@ static int lstm_layer_bwd(const LstmCall& k) {
         }
     }
     if (k.dx) {
-        EpiArgs e0;
-        GF_TRY(launch_gemm_nn(ws + L.dG_at(0, 0), 4 * H, k.w_ih[0], In, k.dx, In, T, In, 4 * H, EPI_NONE, e0, k.st));
-        EpiArgs e1;
-        e1.aux_in = k.dx;                            // + the reverse direction's share (each element read and written by one thread)
-        GF_TRY(launch_gemm_nn(ws + L.dG_at(1, 0), 4 * H, k.w_ih[1], In, k.dx, In, T, In, 4 * H, EPI_NONE, e1, k.st));
+        GF_TRY(gemm(gemm_nn(ws + L.dG_at(0, 0), k.w_ih[0], k.dx, T, In, 4 * H).on(k.st)));
+        // + the reverse direction's share (each element read and written by one thread)
+        GF_TRY(gemm(gemm_nn(ws + L.dG_at(1, 0), k.w_ih[1], k.dx, T, In, 4 * H).residual(k.dx).on(k.st)));
     }
     return 0;
 }

@@ -22,6 +22,11 @@ KINK = 1e-5                                           # |pre-activation| <= KINK
 # K <= 128 instantiation (68: K % 16 != 0), 132, 516 on the long-K one.
 SHAPES = [(1, 64, 4), (33, 36, 68), (64, 64, 128), (97, 132, 132), (130, 100, 516), (97, 4, 68), (130, 132, 128), (33, 100, 132),
           (64, 36, 516), (97, 64, 4), (1, 132, 132), (130, 64, 68), (64, 100, 132)]
+# the smallest shape the weight-resident kernel takes (K = 100, N >= 1024): M = 70 is two token tiles, the second with 6 rows.
+# With the tables above that is every family of gemm_plan (csrc/gemm.hip) under the three epilogues in both operand modes:
+# K = 128 is the last K of the short-K class, K = 132 the first of the generic one
+WRES_SHAPE = (70, 1024, 100)
+SHAPES = SHAPES + [WRES_SHAPE]
 EPI0_CASES = [(0, s) for s in SHAPES] + [(1, s) for s in SHAPES if s[1] != 4]
 # K = 100: N >= 1024 runs on the weight-resident kernel, N < 1024 on the generic K <= 128 instantiation; the last two: the
 # shapes of the d_model-512 stack's linear1 / a long K

@@ -9,6 +9,10 @@ GEN_SHAPES = [(14, 100, 512, 100), (1, 100, 512, 100), (5, 100, 512, 100), (69, 
               (70, 68, 132, 36), (9, 128, 60, 200)]
 DISC_FUSED_SHAPES = [(T, 100, 64, 16) for T in (1, 3, 4, 5, 15, 16, 17, 63, 330, 1029)]
 DISC_UNFUSED_SHAPES = [(5, 100, 64, 32), (257, 64, 16, 4), (70, 512, 64, 16), (33, 100, 128, 16), (16389, 4, 4, 4)]
+# the dx product of the discriminator head (EPI_GELU_BWD, K = D1) past the short-K class (D1 = 132) and on the weight-resident
+# kernel (D1 = 100, E = 1024: two token tiles, the second with 6 rows) — csrc/gemm.hip gemm_plan.  (Not part of WIDTHS: the
+# recorded size tables are over the widths above.)
+DISC_PLAN_SHAPES = [(33, 100, 132, 16), (70, 1024, 100, 16)]
 WIDTHS = sorted({s[1:] for s in GEN_SHAPES + DISC_FUSED_SHAPES + DISC_UNFUSED_SHAPES})
 
 

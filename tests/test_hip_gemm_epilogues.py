@@ -239,6 +239,21 @@ def test_epi1_relu_dropout(lib, shape, train, p):
     assert not fails, fails
 
 
+@pytest.mark.parametrize("shape", [(97, 132, 132), (64, 64, 128), GC.WRES_SHAPE], ids=lambda s: "x".join(map(str, s)))
+def test_epi1_relu_dropout_on_a_k_major_weight(lib, shape):
+    """mode 1 (C = A W, W [K x N]) under linear1's epilogue, which no network runs: the generic, the short-K and the
+    weight-resident kernel, train mode with p = 0.2, held to test_epi1_relu_dropout's bounds"""
+    M, N, K = shape
+    x, w, bias, _ = GC.inputs(M, N, K)
+    xd, wd, bd, rng = x.cuda(), _weight(w, 1), bias.cuda(), _rng()
+    tag, fails = "mode 1 %s" % (shape,), []
+    Cb = _sent(M * N + GUARD)
+    _hook(lib, 1, 1, xd, wd, bd, None, Cb, 0, M, N, K, 0.2, 1, 1, rng)
+    _expect(fails, _untouched(Cb[M * N:]), "guard", tag)
+    _check_epi1(fails, "epi1 mode 1", tag, Cb[:M * N].view(M, N), x, w, bias, 0.2, 1, K)
+    assert not fails, fails
+
+
 @pytest.mark.parametrize("train,p", GC.MODES, ids=GC.MODE_IDS)
 def test_epi1_generic_short_k_kernel_gives_the_weight_resident_kernels_bits(lib, train, p):
     """K = 100: N = 2048 runs on the weight-resident kernel, the first 132 / 1000 columns alone on the generic K <= 128

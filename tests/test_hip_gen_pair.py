@@ -24,22 +24,24 @@ def pair_cases(shapes):
     return [(S, B, E, H) for E, H in WIDTHS for S, B in shapes] + UNCUT
 
 
-def _case(S, B, E, H, L=2):
+def _case(S, B, E, H, L=2, F=None):
     from gan_ffn_amd import ops
+    F = ops.FF if F is None else F
     g = torch.Generator().manual_seed(1000 * S + 10 * B + E)
-    cfg = ops.enc_cfg(S, B, E, H, L, train=True)
-    cfg_eval = ops.enc_cfg(S, B, E, H, L, train=False)
-    per, _ = ops.layer_layout(E)
+    cfg = ops.enc_cfg(S, B, E, H, L, F=F, train=True)
+    cfg_eval = ops.enc_cfg(S, B, E, H, L, F=F, train=False)
+    per, _ = ops.layer_layout(E, F)
     params = ((torch.rand(L * per, generator=g) - 0.5) * 0.2).cuda()
     x = torch.rand(S, B, E, generator=g).cuda()
     pe = torch.rand(S, E, generator=g).cuda()
     return cfg, cfg_eval, params, x, pe
 
 
-def _pair_against_the_two_single_passes(S, B, E, H, mode=0, key_len=None):
-    """mode: the debug mode word (ganffn_debug_set_ffn_mode) all three calls run under; key_len: handed to all three"""
+def _pair_against_the_two_single_passes(S, B, E, H, mode=0, key_len=None, F=None):
+    """mode: the debug mode word (ganffn_debug_set_ffn_mode) all three calls run under; key_len: handed to all three;
+    F: the feed-forward width (None: the networks' 2048)"""
     from gan_ffn_amd import _lib, ops
-    cfg, cfg_eval, params, x, pe = _case(S, B, E, H)
+    cfg, cfg_eval, params, x, pe = _case(S, B, E, H, F=F)
     n_saved, n_ws = ops.enc_sizes(cfg)
     ops.manual_seed(4321)
     rng, add = ops.DeviceRng.get("cuda").state, 17
@@ -73,6 +75,18 @@ def _pair_against_the_two_single_passes(S, B, E, H, mode=0, key_len=None):
 @pytest.mark.parametrize("S,B,E,H", pair_cases(SHAPES))
 def test_pair_pass_equals_the_two_single_passes(S, B, E, H):
     _pair_against_the_two_single_passes(S, B, E, H)
+
+
+# the smallest shapes that select the two-segment forms of the GEMM driver's special kernels (csrc/gemm.hip gemm_plan), d_model 100:
+#   T = 70, F = 1024: linear1 [70 x 100] -> 1024 on the weight-resident kernel's pair form (K = 100, N >= 1024; two token tiles
+#     per segment, the second with 6 rows), linear2 (K = 1024) on gemm_n100's pair form
+#   T = 17, F = 256: linear2 at gemm_n100's smallest K, one ragged token tile per segment; linear1 (N = 256 < 1024) on the
+#     short-K pair form of the generic kernel
+#   d_model 64, F = 128 / 132: linear1's K = 64 on the short-K pair forms of both epilogues, linear2's K on either side of the
+#     short-K threshold of the plain pair form
+@pytest.mark.parametrize("S,B,E,H,F", [(35, 2, 100, 10, 1024), (17, 1, 100, 10, 256), (17, 1, 64, 4, 128), (17, 1, 64, 4, 132)])
+def test_pair_pass_equals_the_two_single_passes_at_the_thresholds_of_the_gemm_plan(S, B, E, H, F):
+    _pair_against_the_two_single_passes(S, B, E, H, F=F)
 
 
 # the older launch sequences of the mode word (include/ganffn.h: bit 1 separate GEMM + LayerNorm launches, bit 2 generic tiles

@@ -188,6 +188,13 @@ def test_discriminator_head_unfused_by_width(shape, train, p):
     _head_case(HO.DISC, shape, train, p)
 
 
+# dx = d_pre1 W1 under EPI_GELU_BWD on the generic kernel (K = D1 = 132) and on the weight-resident one (K = 100, N = E = 1024)
+@pytest.mark.parametrize("train,p", MODES, ids=MODE_IDS)
+@pytest.mark.parametrize("shape", HC.DISC_PLAN_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_discriminator_head_dx_past_the_short_k_class(shape, train, p):
+    _head_case(HO.DISC, shape, train, p)
+
+
 @pytest.mark.parametrize("train,p", MODES, ids=MODE_IDS)
 def test_discriminator_head_unfused_by_mode_bit_at_the_fused_widths(train, p):
     """bit 5 of the debug mode word: the separate launches at (100, 64, 16), held to the same fp64 bounds as the fused kernel

@@ -39,7 +39,7 @@ def rel_err(a, b):
 
 GEMM_SHAPES = [(3008, 300, 100), (3008, 2048, 100), (3008, 100, 2048), (282, 1536, 512), (14, 300, 100),
                (5, 4, 4), (65, 68, 20), (3008, 64, 100), (3008, 16, 64), (330, 100, 512), (6016, 2048, 512),
-               (3025, 1100, 100), (6016, 2048, 100), (40, 1024, 100)]
+               (3025, 1100, 100), (6016, 2048, 100), (40, 1024, 100), (70, 1024, 100)]
 
 
 @pytest.mark.parametrize("M,N,K", GEMM_SHAPES)
@@ -55,7 +55,7 @@ def test_gemm_nt(lib, M, N, K):
 
 @pytest.mark.parametrize("M,N,K", [(3008, 100, 300), (3008, 2048, 100), (3008, 100, 2048), (282, 512, 1536),
                                    (14, 100, 300), (5, 4, 4), (65, 68, 20), (3008, 64, 16), (3008, 512, 100),
-                                   (3025, 1100, 100), (6016, 2048, 100), (40, 1024, 100)])
+                                   (3025, 1100, 100), (6016, 2048, 100), (40, 1024, 100), (70, 1024, 100)])
 def test_gemm_nn(lib, M, N, K):
     g = torch.Generator().manual_seed(M + N * 5 + K * 11)
     A, Bm = torch.randn(M, K, generator=g), torch.randn(K, N, generator=g)
@@ -405,7 +405,8 @@ def test_logsoftmax_nll_matches_reference_fixture(lib):
 
 
 @pytest.mark.parametrize("T,K,kmajor,cap", [(3008, 2048, 0, 16), (6016, 2048, 1, 16), (6016, 2048, 0, 8), (3008, 2048, 1, 5),
-                                            (21, 256, 0, 16), (70, 2048, 1, 1), (1, 320, 1, 16), (2112, 2048, 0, 16)])
+                                            (21, 256, 0, 16), (70, 2048, 1, 1), (1, 320, 1, 16), (2112, 2048, 0, 16),
+                                            (17, 256, 0, 16), (17, 256, 1, 16)])
 @pytest.mark.parametrize("kw", [0, 1, 2, 2 | 8])
 def test_gemm_n100_slabs_sum_to_the_product(lib, T, K, kmajor, cap, kw):
     """[T x K] x [K x 100] on the 112-wide 16x16x4 kernel (csrc/gemm_n100.hip): the sum of its K-chunk slabs against fp64
@@ -539,3 +540,74 @@ def test_gemm_tn_grouped(lib, use_ws):
         Sd2 = [torch.zeros(m, device="cuda") for (m, n, k) in probs]
         lib.call("ganffn_gemm_tn_grouped", n, arr(At), arr(Bm), arr(Cd2), arr(Sd2), ints(0), ints(1), ints(2), ptr(ws), nws, stream())
         assert all(torch.equal(a, b) for a, b in zip(Cd, Cd2)) and all(torch.equal(a, b) for a, b in zip(Sd, Sd2))
+
+
+# (N, K, T) of ganffn_linear_bwd: the gradient is [N x K] over T tokens.  Then: the slabs the size function makes room for, the
+# slabs of [N x K | N] floats the workspace handed over holds (None: no workspace), the slabs written.  From the rule (csrc/gemm.hip,
+# split policy 3): ceil(768 / tiles) slabs, at most 16 and at most ceil(T / 64), then what fits; chunks are multiples of 64 tokens.
+TN_ACC_WS_CASES = [((64, 100, 330), 6, 6, 6),           # 2 tiles, 330 tokens: 6 chunks of 64
+                   ((64, 100, 330), 6, None, 1),        # unsplit for want of a workspace
+                   ((64, 100, 330), 6, 5, 3),           # a workspace one slab too small: 5 chunks would be 66 -> 128 tokens, so 3
+                   ((64, 100, 330), 6, 1, 1),           # room for one slab: unsplit
+                   ((132, 68, 1100), 16, 16, 9)]        # 6 tiles, 1100 tokens: the cap of 16 -> chunks of 128: 9
+
+
+@pytest.mark.parametrize("shape,wanted,room,slabs", TN_ACC_WS_CASES, ids=["split", "no-workspace", "one-slab-short", "room-for-one", "cap-16"])
+def test_linear_bwd_weight_gradient_split_and_unsplit(lib, shape, wanted, room, slabs):
+    """the TN product of ganffn_linear_bwd (gW [N x K] += dy^T x, gb += column sums of dy) on its split path (partial slabs in the
+    workspace + the ordered reduce), unsplit without a workspace, and with a workspace that holds fewer slabs than the rule asks
+    for: gW, gb (+=, into non-zero gradients) and dx against fp64 at test_gemm_tn_acc's tolerance; a second launch gives the
+    same bits; nothing is written past the workspace handed over, and the size function names the room the rule wants"""
+    N, K, T = shape                                         # the gradient is [N x K], reduced over T tokens
+    g = torch.Generator().manual_seed(N * 13 + K + T)
+    x, w, dy = torch.randn(T, K, generator=g), torch.randn(N, K, generator=g), torch.randn(T, N, generator=g)
+    gw0, gb0 = torch.randn(N, K, generator=g), torch.randn(N, generator=g)
+    xd, wd, dyd = dev(x), dev(w), dev(dy)
+    per = N * K + N
+    assert int(lib.load().ganffn_linear_bwd_workspace_floats(T, K, N)) == wanted * per
+    floats = 0 if room is None else room * per
+    ws = torch.full((floats + 256,), float("nan"), device="cuda") if room is not None else None
+
+    def run():
+        dx, gw, gb = torch.empty(T, K, device="cuda"), dev(gw0.clone()), dev(gb0.clone())
+        lib.call("ganffn_linear_bwd", ptr(dyd), ptr(xd), ptr(wd), ptr(dx), ptr(gw), ptr(gb), T, K, N, ptr(ws), C.c_int64(floats), stream())
+        torch.cuda.synchronize()
+        return dx, gw, gb
+    dx, gw, gb = run()
+    assert rel_err(dx, dy.double() @ w.double()) < 2e-6 * max(1, N ** 0.5)
+    assert rel_err(gw, gw0.double() + dy.double().T @ x.double()) < 3e-6 * max(1, T ** 0.5)
+    assert rel_err(gb, gb0.double() + dy.double().sum(0)) < 3e-6 * max(1, T ** 0.5)
+    if ws is not None:
+        assert bool(torch.isnan(ws[floats:]).all())                       # nothing past the workspace handed over
+        written = int(torch.isfinite(ws[:floats]).view(-1, per).all(1).sum()) if floats else 0
+        print("%s room %s: %d slabs written (expected %d)" % (shape, room, written, slabs))
+        assert written == (slabs if slabs > 1 else 0)
+    dx2, gw2, gb2 = run()
+    assert torch.equal(gw, gw2) and torch.equal(gb, gb2) and torch.equal(dx, dx2)
+
+
+def test_gemm_tn_grouped_wide_and_owner_forms(lib):
+    """the two unsplit forms of the grouped weight-gradient launch on the generic tiles (csrc/gemm.hip tn_grouped_plan): one
+    2048 x 4096 gradient over 64 tokens is 32 x 32 = 1024 tiles of 64 x 128, the threshold of the 128-wide form; 2048 x 4032
+    (N % 128 != 0, 2016 tiles of 64 x 64) stays on the 64-wide form with one owner per tile, with a workspace and without.
+    Gradients and bias gradients (+=) against fp64 at test_gemm_tn_grouped's tolerance; a second launch gives the same bits"""
+    K = 64
+    nws = int(lib.load().ganffn_gemm_tn_grouped_workspace_floats())
+    ws = torch.full((nws,), float("nan"), device="cuda")
+    for M, N, use_ws in ((2048, 4096, True), (2048, 4032, True), (2048, 4032, False)):
+        g = torch.Generator().manual_seed(M + N)
+        At, Bm = dev(torch.randn(K, M, generator=g)), dev(torch.randn(K, N, generator=g))
+        C0, S0 = torch.randn(M, N, generator=g), torch.randn(M, generator=g)
+        one = lambda t: (C.c_void_p * 1)(t.data_ptr())
+        outs = []
+        for _ in range(2):
+            Cd, Sd = dev(C0.clone()), dev(S0.clone())
+            lib.call("ganffn_gemm_tn_grouped", 1, one(At), one(Bm), one(Cd), one(Sd), (C.c_int * 1)(M), (C.c_int * 1)(N), (C.c_int * 1)(K),
+                     ptr(ws) if use_ws else None, nws if use_ws else 0, stream())
+            torch.cuda.synchronize()
+            outs.append((Cd, Sd))
+        ref = C0.double() + At.double().cpu().T @ Bm.double().cpu()
+        assert rel_err(outs[0][0], ref) < 3e-6 * max(1, K ** 0.5), (M, N, use_ws)
+        assert rel_err(outs[0][1], S0.double() + At.double().cpu().sum(0)) < 3e-6 * max(1, K ** 0.5), (M, N, use_ws)
+        assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+        assert bool(torch.isnan(ws).all())                   # unsplit: the workspace is not touched
