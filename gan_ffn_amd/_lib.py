@@ -64,6 +64,11 @@ class DrnnAttPtrs(C.Structure):     # ganffn_drnn_att_params / ganffn_drnn_att_g
     _fields_ = [(n, C.c_void_p) for n in DRNN_ATT_FIELDS]
 
 
+class DrnnStreamCfg(C.Structure):  # ganffn_drnn_stream_cfg: the streamed head's state and cell description
+    _fields_ = [("capacity", C.c_int32), ("max_len", C.c_int32), ("parties", C.c_int32), ("Dm", C.c_int32), ("H", C.c_int32),
+                ("He", C.c_int32), ("listener", C.c_int32), ("att", DrnnAtt)]
+
+
 BATCH_MAX_COLS = 4                 # GANFFN_BATCH_MAX_COLS
 
 
@@ -163,6 +168,11 @@ SIGNATURES = {
     "ganffn_stream_extend_workspace_floats": (_L, [_PE, _I]),
     "ganffn_encoder_stream_extend": (_I, [_PE, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
     "ganffn_stream_attention_chunk": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "ganffn_drnn_stream_state_floats": (_L, [C.POINTER(DrnnStreamCfg)]),
+    "ganffn_drnn_stream_workspace_floats": (_L, [C.POINTER(DrnnStreamCfg), _I]),
+    "ganffn_drnn_stream_step": (_I, [C.POINTER(DrnnStreamCfg), _I, _P, _P, _I] + [_P] * 10),
+    "ganffn_drnn_stream_extend": (_I, [C.POINTER(DrnnStreamCfg), _I, _I] + [_P] * 12),
+    "ganffn_general2_stream_attention": (_I, [_P] * 7 + [_I] * 5 + [_P]),
     "ganffn_encoder_fwd_pair_len":(_I, [_PE, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, _P]),
     "ganffn_encoder_bwd_parts_len": (_I, [_PE, _P, _P, _P, _P, _P, _P, _P, _U64, _I, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int), _P]),
     "ganffn_encoder_fwd_pair_mask": (_I, [_PE, _P, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _U64, _P]),

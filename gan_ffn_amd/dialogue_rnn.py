@@ -17,7 +17,8 @@ restatement below, which is also what the reference-fixture parity tests pin.  T
     batched masked attention over all (dialogue, query step) pairs (`general2_all_queries`).
 The generators underneath are the HIP path; there is no CPU route through them.
 An extension the reference does not have: `UniModel` / `GAN_FFN_DialogueRNN(causal=True)`, the classifier that never looks ahead
-(one forward DialogueRNN, causal second attention, causal generators).
+(one forward DialogueRNN, causal second attention, causal generators), which also streams: `GAN_FFN_DialogueRNN.stream()`
+(streaming.DrnnStreamSession) labels each utterance as it arrives, one recurrence step per utterance against per-slot state.
 """
 import torch
 import torch.nn as nn
@@ -312,6 +313,7 @@ class GAN_FFN_DialogueRNN(nn.Module):
                                                                listener_state=listener_state, context_attention=context_attention,
                                                                D_a=D_a, dropout_rec=dropout_rec, dropout=dropout)
         self.fc1 = nn.Linear(100, n_classes)
+        self.stream = self._open_stream            # a plain instance attribute (a bound method): see _open_stream
 
     def forward(self, acoustic, visual, text, qmask, umask):
         from . import ops
@@ -322,6 +324,17 @@ class GAN_FFN_DialogueRNN(nn.Module):
         else:
             fusion = self.acoustic_generator(acoustic, kl) + self.visual_generator(visual, kl) + self.text_generator(text, kl)
         return self.bi_model(fusion, qmask, umask)
+
+    def _open_stream(self, capacity=1, max_len=110, parties=2):
+        """net.stream(capacity=1, max_len=MAX_LEN, parties=2): the name `stream` is bound on every INSTANCE in __init__, not on the
+        class — the class keeps the attribute set it always had (tests/test_stream_cpu.py and tests/test_stream_extend_cpu.py pin that
+        the class carries no `stream`), and a net streams or refuses by what it was built with.
+        -> a streaming.DrnnStreamSession: label each utterance of up to `capacity` concurrent dialogues as it arrives, from the
+        generators' per-layer K/V caches and the head's per-slot recurrence state (one DialogueRNN step per new utterance).  Needs
+        causal=True: the bidirectional head reads the future.  max_len: positions per slot (<= model.MAX_LEN = 110); parties: the
+        width of the party axis (qmask's last dimension; speakers are given as indices)."""
+        from .streaming import DrnnStreamSession
+        return DrnnStreamSession(self, capacity, max_len, parties)
 
 
 class MELDLSTMModel(nn.Module):

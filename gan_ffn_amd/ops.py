@@ -706,6 +706,73 @@ def drnn_bwd_raw(cfg, acfg, parties, ndir, d_e, U, spk, mval, P, LP, AP, G, LG, 
                        ("alpha", alpha), ("saved", saved), ("ws", ws)], rng, add)
 
 
+# ---- the streamed head (csrc/drnn_stream.hip): one recurrence step per new utterance against per-slot state -----------------
+def drnn_stream_cfg(capacity, max_len, parties, Dm, H, He, listener, att, Da=0):
+    """_lib.DrnnStreamCfg: the state's shape (capacity slots of max_len positions, `parties` party rows) and the cell's widths,
+    listener state and context attention type (a DRNN_ATT_TYPES name; Da: concat's D_a)"""
+    return _lib.DrnnStreamCfg(int(capacity), int(max_len), int(parties), int(Dm), int(H), int(He), 1 if listener else 0,
+                              _lib.DrnnAtt(_lib.DRNN_ATT_TYPES[att], int(Da)))
+
+
+def drnn_stream_sizes(cfg, n_max):
+    """(state floats, workspace floats for calls of up to n_max rows) of a streamed head (ganffn_drnn_stream_*_floats)"""
+    lib = _lib.load()
+    s = int(lib.ganffn_drnn_stream_state_floats(C.byref(cfg)))
+    w = int(lib.ganffn_drnn_stream_workspace_floats(C.byref(cfg), int(n_max))) if s >= 0 else -1
+    if s < 0 or w < 0:
+        _lib.check(-1, "ganffn_drnn_stream_*_floats")
+    return s, w
+
+
+def drnn_stream_cell_ptrs(cell):
+    """(ganffn_drnn_params, ganffn_drnn_listener_params or None, ganffn_drnn_att_params or None) of a DialogueRNNCell, read from
+    its parameter tensors now: pointer structs for ganffn_drnn_stream_step / _extend.  The attention's parameters go in their own
+    struct for every type (general's transform.weight too); att_w of the first stays null."""
+    sd = dict(cell.named_parameters())
+    att = drnn_att_type(cell)
+    tensors = [sd[k] for k in DRNN_KEYS[:12] + DRNN_ATT_KEYS[att] + (DRNN_LISTENER_KEYS if cell.listener_state else [])]
+    for t in tensors:
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise GanffnError("the streamed DialogueRNN step reads the cell's parameters in place: float32 and contiguous")
+    _need_gpu(*tensors)
+    prm = _drnn_ptrs(tensors[:12] + [None])
+    n_att = len(DRNN_ATT_KEYS[att])
+    aprm = _att_ptrs(att, tensors[12:12 + n_att]) if att != "dot" else None
+    lprm = _drnn_ptrs(tensors[12 + n_att:], _lib.DrnnListenerPtrs) if cell.listener_state else None
+    return prm, lprm, aprm
+
+
+def _byref(s):
+    return C.byref(s) if s is not None else None
+
+
+def drnn_stream_step_raw(cfg, n, slot, pos, spk, U, ptrs, state, e_out, ws, off=0, count=None):
+    """one recurrence step of n rows (ganffn_drnn_stream_step; eval math): row i of U [n x Dm], speaker spk[i], is utterance
+    pos[slot[i]] + off of the dialogue in slot slot[i]; writes the state and e_out [n x He].  pos is not advanced.
+    ptrs: drnn_stream_cell_ptrs(cell)."""
+    _need_gpu(slot, pos, spk, U, state, e_out, ws)
+    prm, lprm, aprm = ptrs
+    _lib.call("ganffn_drnn_stream_step", C.byref(cfg), n, _ptr(slot), _ptr(pos), int(off), _ptr(count), _ptr(spk), _ptr(U),
+              C.byref(prm), _byref(lprm), _byref(aprm), _ptr(state), _ptr(e_out), _ptr(ws), _stream())
+
+
+def drnn_stream_extend_raw(cfg, n, m, slot, count, pos, spk, U, ptrs, state, e_out, ws):
+    """count[i] consecutive recurrence steps of n dialogues in one native call (ganffn_drnn_stream_extend): spk [m][n],
+    U [m][n][Dm] and e_out [m][n][He] time-major.  pos is not advanced."""
+    _need_gpu(slot, count, pos, spk, U, state, e_out, ws)
+    prm, lprm, aprm = ptrs
+    _lib.call("ganffn_drnn_stream_extend", C.byref(cfg), n, m, _ptr(slot), _ptr(count), _ptr(pos), _ptr(spk), _ptr(U),
+              C.byref(prm), _byref(lprm), _byref(aprm), _ptr(state), _ptr(e_out), _ptr(ws), _stream())
+
+
+def general2_stream_attention_raw(x, e_hist, slot, count, pos, att, alpha, n, m, capacity, max_len, D):
+    """the second attention of new rows (ganffn_general2_stream_attention): x, att [m][n][D]; e_hist: the state's E region, which
+    already holds the new rows; count None = one row each; alpha [m][n][max_len] or None"""
+    _need_gpu(x, e_hist, slot, pos, att)
+    _lib.call("ganffn_general2_stream_attention", _ptr(x), _ptr(e_hist), _ptr(slot), _ptr(count), _ptr(pos), _ptr(att), _ptr(alpha),
+              n, m, capacity, max_len, D, _stream())
+
+
 class DialogueRNNFn(torch.autograd.Function):
     """ndir (1 or 2) DialogueRNNs through one chain of launches (drnn_fwd_raw / drnn_bwd_raw; which entry points they reach:
     drnn_family).

@@ -8,6 +8,10 @@ values agree with the matching rows of the full causal forward to rounding, not 
 rules are evaluated for n rows).  `extend` ingests several utterances per dialogue in one call (ganffn_encoder_stream_extend: one
 causal pass over the new rows against the same caches) — a dialogue joined under way, caches rebuilt after the weights changed,
 utterances that arrive in bursts.
+
+`GAN_FFN_DialogueRNN(causal=True).stream(capacity, max_len, parties)` returns a DrnnStreamSession: the same generator caches plus
+the DialogueRNN head's per-slot state (global history, party states, emotion history; csrc/drnn_stream.hip), one recurrence step
+per new utterance.
 """
 import torch
 
@@ -36,7 +40,7 @@ class _Bufs:
             self.head_saved.append(torch.empty(n_saved, **f32))
             self.head_ws.append(torch.empty(n_ws, **f32))
             self.head_out.append(torch.empty(n, g.fc2.weight.shape[0], **f32))
-        self.fusion = torch.empty(n, sess.net.fc.weight.shape[1], **f32)
+        self.fusion = torch.empty(n, sess._fusion_width(), **f32)
         self.logits = torch.empty(n, sess.net.n_classes, **f32)
         self.log_prob = torch.empty(n, sess.net.n_classes, **f32)
         self.graph = None
@@ -63,33 +67,17 @@ class _ExtBufs:
                          torch.empty(m, n, sess.net.n_classes, device=dev, dtype=torch.float32))
 
 
-class StreamSession:
-    """Per-dialogue K/V caches of a causal GAN_FFN and the step that labels one new utterance of up to `capacity` concurrent
-    dialogues.  Slot s holds one dialogue; `positions[s]` (device int32) is the number of its utterances seen so far.
+class _GeneratorStream:
+    """What the streaming sessions share: the three causal generators' per-layer K/V caches, stack configurations and workspaces,
+    the slots' positions (device int32 + host mirror), slot validation and reset."""
 
-    Always eval math under no_grad (no dropout), whatever net.training says; the weights are read from the generators' slabs at
-    call time.  CHANGED WEIGHTS: after a training step (or load_state_dict) the cached K / V are stale — call reset() and `extend`
-    with the dialogues' utterances so far (one causal pass over them instead of one step per utterance); the session does not
-    notice.  mask_padding is irrelevant to a stream: at real utterances lengths add nothing
-    to a causal mask."""
-
-    def __init__(self, net, capacity=1, max_len=None, use_graph=False):
-        from .model import MAX_LEN
-        max_len = MAX_LEN if max_len is None else int(max_len)
-        if not getattr(net, "causal", False):
-            raise ValueError("GAN_FFN.stream() needs a classifier built with causal=True: row t of a bidirectional classifier "
-                             "depends on the utterances after it, so it cannot be labelled as it arrives")
-        if not 1 <= int(capacity) <= MAX_DIALOGUES:
-            raise ValueError("capacity=%r out of range [1, %d]" % (capacity, MAX_DIALOGUES))
-        if not 1 <= max_len <= MAX_LEN:
-            raise ValueError("max_len=%r out of range [1, %d] (PositionalEncoding max_len)" % (max_len, MAX_LEN))
-        self.net, self.capacity, self.max_len, self.use_graph = net, int(capacity), max_len, bool(use_graph)
+    def _init_generators(self, net, capacity, max_len, dev, what):
+        self.net, self.capacity, self.max_len = net, int(capacity), int(max_len)
         self.gens = [getattr(net, k) for k in GEN_NAMES]
-        dev = net.fc.weight.device
         for p in net.parameters():
             if not p.is_cuda or p.device != dev:
-                raise ops.GanffnError("GAN_FFN.stream(): every parameter must be on one GPU (got %s and %s); there is no CPU "
-                                      "fallback" % (dev, p.device))
+                raise ops.GanffnError("%s: every parameter must be on one GPU (got %s and %s); there is no CPU "
+                                      "fallback" % (what, dev, p.device))
         self.device = dev
         self.cfgs, self.caches, self.ws, self.pes = [], [], [], []
         for g in self.gens:
@@ -126,6 +114,95 @@ class StreamSession:
             for s in slots:
                 self._host_pos[s] = 0
 
+    def _heads_sum(self, b):
+        """the generators' heads over the stack outputs b.enc and their sum -> b.fusion"""
+        for i, g in enumerate(self.gens):
+            ops.head_fwd_raw(b.head_cfg[i], b.enc[i], g.fc1.weight, g.fc1.bias, g.fc2.weight, g.fc2.bias, None, None,
+                             b.head_out[i], b.head_saved[i], b.head_ws[i], None, 0)
+        ops._lib.call("ganffn_add3", ops._ptr(b.head_out[0]), ops._ptr(b.head_out[1]), ops._ptr(b.head_out[2]), ops._ptr(b.fusion),
+                      ops.C.c_int64(b.fusion.numel()), ops._stream())
+
+    def _check_rows(self, xs, slots, what):
+        """shapes of a step's inputs and its slot list -> (n, slots as a tuple); nothing full, nothing launched"""
+        n = int(xs[0].shape[0])
+        for x, g in zip(xs, self.gens):
+            if x.dim() != 2 or x.shape[0] != n or x.shape[1] != g.d_model:
+                raise ValueError("%s: inputs must be [n, 100], [n, 512], [n, 100]; got %s" % (what, [tuple(t.shape) for t in xs]))
+        if slots is None:
+            if n != self.capacity:
+                raise ValueError("%s: slots=None means every slot: n must be the capacity %d, got %d" % (what, self.capacity, n))
+            slots = range(self.capacity)
+        slots = tuple(self._check_slots(slots.tolist() if torch.is_tensor(slots) else slots, what))
+        if len(slots) != n or n < 1:
+            raise ValueError("%s: %d rows for %d slots" % (what, n, len(slots)))
+        for s in slots:
+            if self._host_pos[s] >= self.max_len:
+                raise ValueError("%s: slot %d is full (%d utterances); reset() it before its next dialogue" % (what, s, self.max_len))
+        return n, slots
+
+    def _check_chunks(self, xs, lengths, slots, what):
+        """shapes of an extend's inputs, its slot list and lengths -> (m, n, slots, lengths as tuples); nothing launched"""
+        if xs[0].dim() != 3:
+            raise ValueError("%s: inputs must be [m, n, 100], [m, n, 512], [m, n, 100]; got %s" % (what, [tuple(t.shape) for t in xs]))
+        m, n = int(xs[0].shape[0]), int(xs[0].shape[1])
+        for x, g in zip(xs, self.gens):
+            if x.dim() != 3 or x.shape[0] != m or x.shape[1] != n or x.shape[2] != g.d_model:
+                raise ValueError("%s: inputs must be [m, n, 100], [m, n, 512], [m, n, 100]; got %s" % (what, [tuple(t.shape) for t in xs]))
+        if not 1 <= m <= self.max_len:
+            raise ValueError("%s: m=%d utterances per call outside [1, max_len=%d]" % (what, m, self.max_len))
+        if slots is None:
+            if n != self.capacity:
+                raise ValueError("%s: slots=None means every slot: n must be the capacity %d, got %d" % (what, self.capacity, n))
+            slots = range(self.capacity)
+        slots = tuple(self._check_slots(slots.tolist() if torch.is_tensor(slots) else slots, what))
+        if len(slots) != n or n < 1:
+            raise ValueError("%s: %d columns for %d slots" % (what, n, len(slots)))
+        lengths = tuple(int(c) for c in (lengths.tolist() if torch.is_tensor(lengths) else lengths))
+        if len(lengths) != n:
+            raise ValueError("%s: %d lengths for %d columns" % (what, len(lengths), n))
+        for s, c in zip(slots, lengths):
+            if not 1 <= c <= m:
+                raise ValueError("%s: length %d of slot %d outside [1, m=%d]" % (what, c, s, m))
+        for s, c in zip(slots, lengths):
+            if self._host_pos[s] + c > self.max_len:
+                raise ValueError("%s: slot %d holds %d of max_len=%d utterances: %d more fit, not %d; reset() it before its next "
+                                 "dialogue" % (what, s, self._host_pos[s], self.max_len, self.max_len - self._host_pos[s], c))
+        return m, n, slots, lengths
+
+    @staticmethod
+    def _upload_slots(b, slots):
+        if b.slots_host != slots:
+            b.slot.copy_(torch.tensor(slots, dtype=torch.int32))
+            b.slot64.copy_(b.slot)
+            b.slots_host = slots
+
+
+class StreamSession(_GeneratorStream):
+    """Per-dialogue K/V caches of a causal GAN_FFN and the step that labels one new utterance of up to `capacity` concurrent
+    dialogues.  Slot s holds one dialogue; `positions[s]` (device int32) is the number of its utterances seen so far.
+
+    Always eval math under no_grad (no dropout), whatever net.training says; the weights are read from the generators' slabs at
+    call time.  CHANGED WEIGHTS: after a training step (or load_state_dict) the cached K / V are stale — call reset() and `extend`
+    with the dialogues' utterances so far (one causal pass over them instead of one step per utterance); the session does not
+    notice.  mask_padding is irrelevant to a stream: at real utterances lengths add nothing
+    to a causal mask."""
+
+    def __init__(self, net, capacity=1, max_len=None, use_graph=False):
+        from .model import MAX_LEN
+        max_len = MAX_LEN if max_len is None else int(max_len)
+        if not getattr(net, "causal", False):
+            raise ValueError("GAN_FFN.stream() needs a classifier built with causal=True: row t of a bidirectional classifier "
+                             "depends on the utterances after it, so it cannot be labelled as it arrives")
+        if not 1 <= int(capacity) <= MAX_DIALOGUES:
+            raise ValueError("capacity=%r out of range [1, %d]" % (capacity, MAX_DIALOGUES))
+        if not 1 <= max_len <= MAX_LEN:
+            raise ValueError("max_len=%r out of range [1, %d] (PositionalEncoding max_len)" % (max_len, MAX_LEN))
+        self.use_graph = bool(use_graph)
+        self._init_generators(net, capacity, max_len, net.fc.weight.device, "GAN_FFN.stream()")
+
+    def _fusion_width(self):
+        return self.net.fc.weight.shape[1]
+
     # ---- one utterance per active dialogue ---------------------------------------------------------------------------
     def _body(self, b, n):
         """the launches of a step, on the current stream: one stack step and one head per generator, sum, fc, log_softmax,
@@ -139,11 +216,7 @@ class StreamSession:
     def _tail(self, b, n):
         """the row-wise rest of the classifier over n rows of stack outputs b.enc: the generators' heads, sum, fc, log_softmax"""
         net = self.net
-        for i, g in enumerate(self.gens):
-            ops.head_fwd_raw(b.head_cfg[i], b.enc[i], g.fc1.weight, g.fc1.bias, g.fc2.weight, g.fc2.bias, None, None,
-                             b.head_out[i], b.head_saved[i], b.head_ws[i], None, 0)
-        ops._lib.call("ganffn_add3", ops._ptr(b.head_out[0]), ops._ptr(b.head_out[1]), ops._ptr(b.head_out[2]), ops._ptr(b.fusion),
-                      ops.C.c_int64(b.fusion.numel()), ops._stream())
+        self._heads_sum(b)
         ops.linear_fwd_raw(b.fusion, net.fc.weight, net.fc.bias, b.logits, n, net.fc.weight.shape[1], net.n_classes)
         ops.logsoftmax_nll_raw(b.logits, None, None, None, b.log_prob, None, None, None, 1, n, net.n_classes)
 
@@ -160,27 +233,11 @@ class StreamSession:
         validated, which for a device tensor is a read); allocates only on the first step at a given n.  The returned tensor is
         the session's buffer for that n: the next step with the same n overwrites it."""
         xs = (acoustic, visual, text)
-        n = int(acoustic.shape[0])
-        for x, g in zip(xs, self.gens):
-            if x.dim() != 2 or x.shape[0] != n or x.shape[1] != g.d_model:
-                raise ValueError("step: inputs must be [n, 100], [n, 512], [n, 100]; got %s" % [tuple(t.shape) for t in xs])
-        if slots is None:
-            if n != self.capacity:
-                raise ValueError("step: slots=None means every slot: n must be the capacity %d, got %d" % (self.capacity, n))
-            slots = range(self.capacity)
-        slots = tuple(self._check_slots(slots.tolist() if torch.is_tensor(slots) else slots, "step"))
-        if len(slots) != n or n < 1:
-            raise ValueError("step: %d rows for %d slots" % (n, len(slots)))
-        for s in slots:
-            if self._host_pos[s] >= self.max_len:
-                raise ValueError("step: slot %d is full (%d utterances); reset() it before its next dialogue" % (s, self.max_len))
+        n, slots = self._check_rows(xs, slots, "step")
         b = self._bufs.get(n)
         if b is None:
             b = self._bufs[n] = _Bufs(self, n)
-        if b.slots_host != slots:
-            b.slot.copy_(torch.tensor(slots, dtype=torch.int32))
-            b.slot64.copy_(b.slot)
-            b.slots_host = slots
+        self._upload_slots(b, slots)
         for dst, x in zip(b.x, xs):
             dst.copy_(x)
         if not self.use_graph:
@@ -218,38 +275,11 @@ class StreamSession:
         for its n).  Values agree with `step` by `step` and with the full causal forward to rounding, not bit for bit.  The returned
         tensor is the session's buffer for that (m, n): the next extend at the same (m, n) overwrites it."""
         xs = (acoustic, visual, text)
-        if acoustic.dim() != 3:
-            raise ValueError("extend: inputs must be [m, n, 100], [m, n, 512], [m, n, 100]; got %s" % [tuple(t.shape) for t in xs])
-        m, n = int(acoustic.shape[0]), int(acoustic.shape[1])
-        for x, g in zip(xs, self.gens):
-            if x.dim() != 3 or x.shape[0] != m or x.shape[1] != n or x.shape[2] != g.d_model:
-                raise ValueError("extend: inputs must be [m, n, 100], [m, n, 512], [m, n, 100]; got %s" % [tuple(t.shape) for t in xs])
-        if not 1 <= m <= self.max_len:
-            raise ValueError("extend: m=%d utterances per call outside [1, max_len=%d]" % (m, self.max_len))
-        if slots is None:
-            if n != self.capacity:
-                raise ValueError("extend: slots=None means every slot: n must be the capacity %d, got %d" % (self.capacity, n))
-            slots = range(self.capacity)
-        slots = tuple(self._check_slots(slots.tolist() if torch.is_tensor(slots) else slots, "extend"))
-        if len(slots) != n or n < 1:
-            raise ValueError("extend: %d columns for %d slots" % (n, len(slots)))
-        lengths = tuple(int(c) for c in (lengths.tolist() if torch.is_tensor(lengths) else lengths))
-        if len(lengths) != n:
-            raise ValueError("extend: %d lengths for %d columns" % (len(lengths), n))
-        for s, c in zip(slots, lengths):
-            if not 1 <= c <= m:
-                raise ValueError("extend: length %d of slot %d outside [1, m=%d]" % (c, s, m))
-        for s, c in zip(slots, lengths):
-            if self._host_pos[s] + c > self.max_len:
-                raise ValueError("extend: slot %d holds %d of max_len=%d utterances: %d more fit, not %d; reset() it before its next "
-                                 "dialogue" % (s, self._host_pos[s], self.max_len, self.max_len - self._host_pos[s], c))
+        m, n, slots, lengths = self._check_chunks(xs, lengths, slots, "extend")
         b = self._ext_bufs.get((m, n))
         if b is None:
             b = self._ext_bufs[(m, n)] = _ExtBufs(self, m, n)
-        if b.slots_host != slots:
-            b.slot.copy_(torch.tensor(slots, dtype=torch.int32))
-            b.slot64.copy_(b.slot)
-            b.slots_host = slots
+        self._upload_slots(b, slots)
         if b.counts_host != lengths:
             b.count.copy_(torch.tensor(lengths, dtype=torch.int32))
             b.counts_host = lengths
@@ -269,3 +299,191 @@ class StreamSession:
         for s, c in zip(slots, lengths):
             self._host_pos[s] += c
         return b.log_prob
+
+
+# ---- configuration 5: the causal DialogueRNN classifier ------------------------------------------------------------------------
+class _HeadBufs:
+    """what the streamed head of a call over `rows` rows (n of a step, m * n of an extend) touches besides the generators' buffers"""
+
+    def __init__(self, sess, rows, spk_shape):
+        um = sess.net.bi_model
+        f32 = dict(device=sess.device, dtype=torch.float32)
+        self.spk = torch.zeros(spk_shape, device=sess.device, dtype=torch.int32)
+        self.spk_host = None
+        self.e = torch.empty(rows, um.D_e, **f32)
+        self.xt = torch.empty(rows, um.D_e, **f32)
+        self.att = torch.empty(rows, um.D_e, **f32)
+        self.hidden = torch.empty(rows, um.linear.weight.shape[0], **f32)
+        self.logits = torch.empty(rows, sess.net.n_classes, **f32)
+        self.log_prob = torch.empty(rows, sess.net.n_classes, **f32)
+
+    def upload_speakers(self, spk):
+        if self.spk_host != spk:
+            self.spk.copy_(torch.tensor(spk, dtype=torch.int32).view(self.spk.shape))
+            self.spk_host = spk
+
+
+class DrnnStreamSession(_GeneratorStream):
+    """The streaming form of GAN_FFN_DialogueRNN(causal=True): per-dialogue K/V caches of the three causal generators (as
+    StreamSession keeps them) and, next to them, the head's per-slot state — the global history g_0 .. g_{t-1}, the party states and
+    the emotion history e_0 .. e_{t-1}, which is also the memory of the second attention (csrc/drnn_stream.hip; layout in
+    include/ganffn.h).  `step` runs ONE recurrence step per new utterance instead of the whole prefix: log_prob[t] of the causal
+    classifier depends on utterances and speakers 0 .. t only, so each row is final when it is returned.
+
+    Always eval math under no_grad (no dropout), whatever net.training says; the weights are read from the net's parameter tensors
+    at call time.  CHANGED WEIGHTS: the caches and the state are stale after a training step — reset() and `extend` with the
+    dialogues so far.  Values agree with the rows of the net's full causal forward to rounding, not bit for bit."""
+
+    def __init__(self, net, capacity=1, max_len=None, parties=2):
+        from .model import MAX_LEN
+        max_len = MAX_LEN if max_len is None else int(max_len)
+        if not getattr(net, "causal", False):
+            raise ValueError("GAN_FFN_DialogueRNN.stream() needs a classifier built with causal=True: the bidirectional head reads "
+                             "the future (its reverse DialogueRNN starts at the dialogue's last utterance), so no row can be "
+                             "labelled as it arrives")
+        if not 1 <= int(capacity) <= MAX_DIALOGUES:
+            raise ValueError("capacity=%r out of range [1, %d]" % (capacity, MAX_DIALOGUES))
+        if not 1 <= max_len <= MAX_LEN:
+            raise ValueError("max_len=%r out of range [1, %d] (PositionalEncoding max_len)" % (max_len, MAX_LEN))
+        if not 1 <= int(parties) <= ops.DRNN_MAX_PARTIES:
+            raise ValueError("parties=%r out of range [1, %d]" % (parties, ops.DRNN_MAX_PARTIES))
+        um = net.bi_model
+        cell = um.dialog_rnn_f.dialogue_cell
+        self._init_generators(net, capacity, max_len, um.linear.weight.device, "GAN_FFN_DialogueRNN.stream()")
+        self.parties = int(parties)
+        att = ops.drnn_att_type(cell)
+        if cell.D_g != cell.D_p:
+            raise ValueError("stream(): the step kernels need D_g == D_p, got D_g=%d D_p=%d" % (cell.D_g, cell.D_p))
+        if cell.D_g > 512:
+            raise ValueError("stream(): D_g = D_p = %d > 512 (the step kernels hold one state column per thread)" % cell.D_g)
+        if cell.D_m % 4 or cell.D_g % 4 or cell.D_e % 4 or cell.D_e > 1024:
+            raise ValueError("stream(): D_m=%d, D_g=%d, D_e=%d must be multiples of 4, D_e <= 1024" % (cell.D_m, cell.D_g, cell.D_e))
+        if att == "dot" and cell.D_m != cell.D_g:
+            raise ValueError("stream(): dot attention needs D_m == D_g, got D_m=%d D_g=%d" % (cell.D_m, cell.D_g))
+        Da = cell.attention.transform.weight.shape[0] if att == "concat" else 0
+        if att == "concat" and (Da % 4 or not 4 <= Da <= 512):
+            raise ValueError("stream(): concat attention needs D_a a multiple of 4 in [4, 512], got D_a=%d" % Da)
+        for g in self.gens:
+            if g.fc2.weight.shape[0] != cell.D_m:
+                raise ValueError("stream(): the generators' output width %d is not D_m=%d" % (g.fc2.weight.shape[0], cell.D_m))
+        self.cell, self.um = cell, um
+        self.head_cfg = ops.drnn_stream_cfg(self.capacity, self.max_len, self.parties, cell.D_m, cell.D_g, cell.D_e,
+                                            cell.listener_state, att, Da)
+        n_state, n_ws = ops.drnn_stream_sizes(self.head_cfg, self.capacity)
+        self.state = torch.empty(n_state, device=self.device, dtype=torch.float32)      # never read at or above a position
+        self.head_ws = torch.empty(n_ws, device=self.device, dtype=torch.float32)
+        a4 = lambda k: (k + 3) & ~3                                                     # noqa: E731  (the header's region rule)
+        e_off = a4(self.capacity * self.max_len * cell.D_g) + a4(self.capacity * self.parties * cell.D_g)
+        self.e_hist = self.state[e_off:e_off + self.capacity * self.max_len * cell.D_e]  # the E region: the second attention's memory
+
+    def _fusion_width(self):
+        return self.cell.D_m
+
+    def _check_speakers(self, speakers, shape, lengths, what):
+        """speakers as host ints of the given shape, validated against the party count (entries past a length: ignored, sent as 0)"""
+        spk = speakers.tolist() if torch.is_tensor(speakers) else speakers
+        if len(shape) == 1:
+            spk = tuple(int(v) for v in spk)
+            if len(spk) != shape[0]:
+                raise ValueError("%s: %d speakers for %d rows" % (what, len(spk), shape[0]))
+            live = spk
+        else:
+            m, n = shape
+            if len(spk) != m or any(len(r) != n for r in spk):
+                raise ValueError("%s: speakers must be [m=%d][n=%d] ints" % (what, m, n))
+            spk = tuple(int(spk[j][i]) if j < lengths[i] else 0 for j in range(m) for i in range(n))
+            live = spk
+        for v in live:
+            if not 0 <= v < self.parties:
+                raise ValueError("%s: speaker %d outside [0, parties=%d)" % (what, v, self.parties))
+        return spk
+
+    def _head_tail(self, h, fusion, b, n, m, count):
+        """the head over m * n time-major rows of fusion: recurrence (one step, or the native extend), transform, the second
+        attention over the slot's emotion history, linear + ReLU, smax_fc, log_softmax"""
+        um, rows = self.um, m * n
+        De, Dh, Cn = um.D_e, um.linear.weight.shape[0], self.net.n_classes
+        ptrs = ops.drnn_stream_cell_ptrs(self.cell)
+        if count is None:
+            ops.drnn_stream_step_raw(self.head_cfg, n, b.slot, self.positions, h.spk, fusion, ptrs, self.state, h.e, self.head_ws)
+        else:
+            ops.drnn_stream_extend_raw(self.head_cfg, n, m, b.slot, count, self.positions, h.spk, fusion, ptrs, self.state, h.e,
+                                       self.head_ws)
+        tr = um.matchatt.transform
+        ops.linear_fwd_raw(h.e, tr.weight, tr.bias, h.xt, rows, De, De)
+        ops.general2_stream_attention_raw(h.xt, self.e_hist, b.slot, count, self.positions, h.att, None, n, m, self.capacity,
+                                          self.max_len, De)
+        ops._lib.call("ganffn_ffn_linear1_fwd", ops._ptr(h.att), ops._ptr(um.linear.weight), ops._ptr(um.linear.bias), ops._ptr(h.hidden),
+                      rows, De, Dh, ops.C.c_float(0.0), ops.C.c_uint32(0), None, ops.C.c_uint64(0), 0, ops._stream())
+        ops.linear_fwd_raw(h.hidden, um.smax_fc.weight, um.smax_fc.bias, h.logits, rows, Dh, Cn)
+        ops.logsoftmax_nll_raw(h.logits, None, None, None, h.log_prob, None, None, None, 1, rows, Cn)
+
+    # ---- one utterance per active dialogue ---------------------------------------------------------------------------
+    @torch.no_grad()
+    def step(self, acoustic, visual, text, speakers, slots=None):
+        """acoustic [n, 100], visual [n, 512], text [n, 100]: the next utterance of n dialogues; speakers: n host ints in
+        [0, parties) (or an int tensor, which is brought to the host to be validated) — the party index, not a one-hot.
+        -> log_prob [n, n_classes].  slots: as in StreamSession.step.  Everything — shapes, slots, a full slot, a speaker out of
+        range — is validated before any launch and with no position moved.  Never reads from the device, allocates only on the
+        first step at a given n; the returned tensor is the session's buffer for that n."""
+        xs = (acoustic, visual, text)
+        n, slots = self._check_rows(xs, slots, "step")
+        spk = self._check_speakers(speakers, (n,), None, "step")
+        b = self._bufs.get(n)
+        if b is None:
+            b = self._bufs[n] = _Bufs(self, n)
+            b.head = _HeadBufs(self, n, (n,))
+        self._upload_slots(b, slots)
+        b.head.upload_speakers(spk)
+        for dst, x in zip(b.x, xs):
+            dst.copy_(x)
+        for i, g in enumerate(self.gens):
+            ops.encoder_stream_step_raw(self.cfgs[i], n, b.slot, self.positions, b.x[i], self.pes[i], g.slab, self.caches[i],
+                                        b.enc[i], self.ws[i])
+        self._heads_sum(b)
+        self._head_tail(b.head, b.fusion, b, n, 1, None)
+        self.positions.index_add_(0, b.slot64, b.ones)
+        for s in slots:
+            self._host_pos[s] += 1
+        return b.head.log_prob
+
+    # ---- several utterances per active dialogue --------------------------------------------------------------------------
+    @torch.no_grad()
+    def extend(self, acoustic, visual, text, speakers, lengths, slots=None):
+        """acoustic [m, n, 100], visual [m, n, 512], text [m, n, 100], time-major; speakers [m][n] host ints (entries at
+        j >= lengths[i] are ignored); lengths: n host ints in [1, m] -> log_prob [m, n, n_classes], rows past a length unspecified.
+        One generator extend per group of at most ops.STREAM_EXTEND_MAX_ROWS rows, then ONE native head extend (the recurrence is
+        serial in t: lengths[i] steps per dialogue with no host synchronisation), then the row-wise tail.  Raises ValueError before
+        any launch and with no position moved, as StreamSession.extend does, and for a speaker out of range.  Rows past a length
+        must be finite."""
+        xs = (acoustic, visual, text)
+        m, n, slots, lengths = self._check_chunks(xs, lengths, slots, "extend")
+        spk = self._check_speakers(speakers, (m, n), lengths, "extend")
+        b = self._ext_bufs.get((m, n))
+        if b is None:
+            b = self._ext_bufs[(m, n)] = _ExtBufs(self, m, n)
+            b.head = _HeadBufs(self, m * n, (m, n))
+            b.fusion = (b.rows[n].fusion.view(m, n, -1) if len(b.groups) == 1 else
+                        torch.empty(m, n, self.cell.D_m, device=self.device, dtype=torch.float32))
+        self._upload_slots(b, slots)
+        if b.counts_host != lengths:
+            b.count.copy_(torch.tensor(lengths, dtype=torch.int32))
+            b.counts_host = lengths
+        b.head.upload_speakers(spk)
+        single = len(b.groups) == 1
+        for lo, hi in b.groups:
+            ng = hi - lo
+            r = b.rows[ng]
+            for i, g in enumerate(self.gens):
+                xg = r.x[i].view(m, ng, g.d_model)
+                xg.copy_(xs[i] if single else xs[i][:, lo:hi])
+                ops.encoder_stream_extend_raw(self.cfgs[i], ng, m, b.slot[lo:hi], b.count[lo:hi], self.positions, xg, self.pes[i],
+                                              g.slab, self.caches[i], r.enc[i], b.ws[i])
+            self._heads_sum(r)
+            if not single:
+                b.fusion[:, lo:hi].copy_(r.fusion.view(m, ng, -1))
+        self._head_tail(b.head, b.fusion, b, n, m, b.count)
+        self.positions.index_add_(0, b.slot64, b.count)
+        for s, c in zip(slots, lengths):
+            self._host_pos[s] += c
+        return b.head.log_prob.view(m, n, -1)

@@ -676,6 +676,59 @@ int ganffn_encoder_stream_extend(const ganffn_enc_cfg* cfg, int n, int m, const 
 int ganffn_stream_attention_chunk(const float* qkv, float* cache_layer, const int32_t* slot, const int32_t* count,
                                   const int32_t* pos, float* o, int n, int m, int capacity, int max_len, int E, int H,
                                   void* stream);
+/* ---- streaming: the causal DialogueRNN classifier head one utterance at a time (csrc/drnn_stream.hip) ---------------------------
+ * The head of GAN_FFN_DialogueRNN(causal=True) (dialogue_rnn.UniModel) next to the streamed generators above: everything a
+ * recurrence step needs from the past is the global history, the party states and the emotion history, kept as per-slot STATE.
+ * slot [n], pos [capacity], count [n], spk int32 on the device, with the meaning they have above; pos is READ ONLY (the caller
+ * advances it after the last consumer of a step); the slots of one call must be distinct.
+ * State layout (the caller owns it; tests fill it directly): three regions back to back, each rounded up to a multiple of 4 floats:
+ *   G [capacity][max_len][H]    global history: g_j of slot s is the H floats at (s * max_len + j) * H
+ *   Q [capacity][parties][H]    party states
+ *   E [capacity][max_len][He]   emotion history; E[s][t-1] is the emotion cell's recurrent state
+ * Words of G and E at or above a slot's position are never read, and at position 0 the step takes g_prev, every party row and
+ * e_prev as zeros WITHOUT reading the state: it needs no initialisation and a slot is reset by setting its position to 0.
+ * ganffn_drnn_stream_step: row i (U [n x Dm], spk[i] in [0, parties)) is utterance t = pos[slot[i]] + off of the dialogue in slot
+ * slot[i]; a plain step passes off = 0, count = NULL; with count given row i takes part only if off < count[i].  It computes
+ * DialogueRNNCell.forward for one real utterance (m = 1) in eval mode — the g cell on [U, q[spk]] and g_{t-1}; the context
+ * attention of the configured type over G[s][0 .. t-1] (c = 0 at t = 0); the party cell for the speaker's row; with `listener` the
+ * listener cell for every party row, then the blend; the e cell — and writes G[s][t], all `parties` rows of Q[s], E[s][t] and
+ * e_out[i] = e_t ([n x He]).  prm->att_w is ignored: the attention's parameters are aprm (ONE struct; NULL for dot), lprm is the
+ * listener's (NULL without).  Inference only: no dropout, nothing saved, no atomics, every summation order fixed; the bits of a
+ * row depend on no other row of the call.  7 launches (more product launches with listener state and more than 2 parties).
+ * SKIP: a row whose slot is outside [0, capacity), whose position is negative, whose t is outside [0, max_len), whose spk is
+ * outside [0, parties) or that count masks: the state is untouched and e_out[i] is a zero row; nothing is accessed out of range
+ * whatever the index arrays hold.
+ * Refused with a message before any launch: null or misaligned pointers, n outside [1, capacity], widths outside the limits, dot
+ * with Dm != H, concat D_a outside its limits, missing attention or listener tensors.
+ * ganffn_drnn_stream_extend: the step m times with off = 0 .. m-1 on time-major rows (spk [m][n], U [m][n][Dm], e_out [m][n][He]),
+ * count [n] required, no host synchronisation: 7 launches per chunk step.
+ * workspace: ganffn_drnn_stream_workspace_floats(cfg, n_max >= n), n_max <= capacity. */
+typedef struct ganffn_drnn_stream_cfg {
+    int32_t capacity, max_len;   /* slots (1 .. GANFFN_MAX_DIALOGUES), positions per slot (1 .. 110) */
+    int32_t parties;             /* 1 .. GANFFN_DRNN_MAX_PARTIES */
+    int32_t Dm, H, He;           /* as ganffn_drnn_cfg: multiples of 4, H <= 512 */
+    int32_t listener;            /* 0 / 1 */
+    ganffn_drnn_att att;         /* every GANFFN_DRNN_ATT_* type, under the rules of ganffn_drnn_att_* */
+} ganffn_drnn_stream_cfg;
+int64_t ganffn_drnn_stream_state_floats(const ganffn_drnn_stream_cfg* cfg);
+int64_t ganffn_drnn_stream_workspace_floats(const ganffn_drnn_stream_cfg* cfg, int n_max);
+int ganffn_drnn_stream_step(const ganffn_drnn_stream_cfg* cfg, int n, const int32_t* slot, const int32_t* pos, int off,
+                            const int32_t* count, const int32_t* spk, const float* U, const ganffn_drnn_params* prm,
+                            const ganffn_drnn_listener_params* lprm, const ganffn_drnn_att_params* aprm, float* state,
+                            float* e_out, float* workspace, void* stream);
+int ganffn_drnn_stream_extend(const ganffn_drnn_stream_cfg* cfg, int n, int m, const int32_t* slot, const int32_t* count,
+                              const int32_t* pos, const int32_t* spk, const float* U, const ganffn_drnn_params* prm,
+                              const ganffn_drnn_listener_params* lprm, const ganffn_drnn_att_params* aprm, float* state,
+                              float* e_out, float* workspace, void* stream);
+/* The second (general2) attention of new rows over a slot's emotion history.  x, att [m][n][D] time-major; x is the caller's
+ * transform(e) of the new rows; e_hist is the state's E region, which ALREADY HOLDS the new rows.  Row (j, i) with j < count[i]
+ * (count = NULL: 1 each) attends over E[s][0 .. pos[s] + j], s = slot[i]: alpha_k = softmax_k(tanh(<x, e_k>)), att = sum_k alpha_k
+ * e_k — the causal row of ganffn_general2_attention_fwd_mask with an all-ones mask.  alpha [m][n][max_len] may be NULL; it is exact
+ * zeros past the row's last memory step.  D a multiple of 4, <= 1024.  A row whose slot is outside [0, capacity), whose position is
+ * negative, whose pos + j is at or above max_len, or with j >= count[i] is skipped: zero rows; nothing is read out of range. */
+int ganffn_general2_stream_attention(const float* x, const float* e_hist, const int32_t* slot, const int32_t* count,
+                                     const int32_t* pos, float* att, float* alpha, int n, int m, int capacity, int max_len, int D,
+                                     void* stream);
 /* z = x + drop(y); xhat = (z-mean)*rstd; out = xhat*w + b   (norm1/norm2 of the encoder layer).  Accepted: T >= 1 and
  * 1 <= E <= 640, a multiple of 4 or not; a wider row is refused with a message.  The variance is the two-pass one (mean
  * of the squared deviations), so a row mean far above the row's spread costs no more than fp32 rounding of z itself. */
