@@ -112,14 +112,14 @@ static int check_cfg(const ganffn_enc_cfg* c) {
 std::atomic<uint32_t> g_mode_word{0};
 GF_LAB_ONLY(extern unsigned long long* g_n100_stamps; extern unsigned long long* g_wres_stamps;)
 constexpr int MAX_SPLITS = 16;  // partial-output slabs: K chunks of gemm_n100 (<= 16) / split-K GEMMs (<= 8)
+static_assert(MAX_SPLITS <= LN_MAXSLAB, "the LayerNorm kernels sum every slab a split rule may write");
 
 static int64_t a4(int64_t n) { return (n + 3) & ~int64_t(3); }
 
 // per LayerNorm backward launch: per-block partial sums of the weight / bias gradient
 static int64_t ln_part_floats(const ganffn_enc_cfg* c) {
     const int T = c->S * c->B;
-    const int nb = ln_bwd_blocks(T) > rc_blocks(T) ? ln_bwd_blocks(T) : rc_blocks(T);
-    return (int64_t)nb * 2 * c->E;
+    return (int64_t)row_blocks_any_plan(T) * 2 * c->E;
 }
 
 // Slack terms of the size functions, in floats.  REGION_SLACK follows the grouped-wgrad parts and the rowchain weight pack: it paid
@@ -261,7 +261,7 @@ static int encoder_fwd_walk(const EncCall& k, const Mode md, const FwdSeg& s0, c
     const int64_t TE = (int64_t)T * E;
     const LayerOff lo = layer_off(E, F);
     const SavedOff so = saved_off(c);
-    // t1's addresses are only handed on where s1 is: without a second segment the adapters below give the launchers null
+    // t1's addresses are only handed on where s1 is: without a second segment the adapters below (nt, run) leave it out of the call
     const FwdSeg& t1 = s1 ? *s1 : s0;
     const int train0 = s0.train, train1 = s1 ? s1->train : 0;
     auto keep_words = [&](const FwdSeg& s, float* sv) { return s.keeps ? reinterpret_cast<uint32_t*>(sv + so.keep) : nullptr; };
@@ -274,45 +274,45 @@ static int encoder_fwd_walk(const EncCall& k, const Mode md, const FwdSeg& s0, c
         if (s1) g.pair(GemmSeg1{A1, C1, mask1, train1});
         return gemm(g);
     };
-    auto ln = [&](const float* x0, const float* x1, const float* w, const float* b, float* out0, float* out1, float* xhat0,
-                  float* xhat1, float* rstd0, float* rstd1, uint32_t site, int nslab) {
-        const LnFwdSeg1 n1{x1, t1.tmp, out1, xhat1, rstd1, train1};
-        return launch_add_drop_ln_fwd(x0, s0.tmp, w, b, out0, xhat0, rstd0, T, E, c->ln_eps, c->p_enc, site, rng, add, train0, st,
-                                      nslab, TE, s1 ? &n1 : nullptr);
+    // A row stage (common.h RowCall) over both segments.  d_model 100: the stage with its GEMMs is one kernel (rowchain.hip) — out-proj
+    // + residual + dropout + LN1, LN2 + the NEXT layer's in-proj, and the positional encoding + dropout at the head of the stack with
+    // layer 0's; every other width, or the mode word: the same launches one by one.  row_plan says which, row_fwd does it.
+    const RowPlan rp = row_plan(E, md, sa != nullptr);
+    // (a RowCall is filled where it stands and each segment built once: some 600 stages a step are issued from one host thread)
+    auto stage = [&](RowKind kind, float p, uint32_t site) {
+        RowCall r = row_call(kind, T, B, E, c->ln_eps, p, site, rng, add, st);
+        r.plan = rp;
+        return r;
+    };
+    // seg(s, v): the stage's operands for segment s, whose saved set of the layer is v
+    auto run = [&](RowCall& r, float* v0, float* v1, auto&& seg) {
+        r.forward(seg(s0, v0));
+        if (s1) r.pair(seg(*s1, v1));
+        return row_fwd(r);
     };
 
-    // d_model 100: out-proj + residual + dropout + LN1 is one kernel, and LN2 carries the NEXT layer's in-proj (rowchain.hip);
-    // the positional encoding + dropout at the head of the stack carries layer 0's
-    const bool rc = rc_supported(E) && !md.rc_off();
-    if (rc && !md.pe_off() && !sa) {
-        RcFwdSeg1 r1{};
-        r1.y = pe; r1.x = x_in; r1.out = t1.x(0); r1.post_out = t1.layer(0) + so.qkv; r1.train = train1;
-        GF_TRY(launch_rc_pe_inproj_fwd(x_in, pe, s0.x(0), params + lo.in_w, params + lo.in_b, s0.layer(0) + so.qkv, T, B, c->p_pe, rng,
-                                       add, train0, st, s1 ? &r1 : nullptr));
-    } else {
-        if (sa && sa->count)
+    // X[0] = dropout(x_in + pe), then qkv of layer 0 = X[0] W_in^T + b_in
+    if (sa) {
+        if (sa->count)
             GF_TRY(launch_stream_pe_chunk(x_in, pe, sa->slot, sa->count, sa->pos, s0.x(0), T / sa->m, sa->m, sa->capacity, sa->max_len,
                                           E, st));
-        else if (sa)
-            GF_TRY(launch_stream_pe(x_in, pe, sa->slot, sa->pos, s0.x(0), T, sa->capacity, sa->max_len, E, st));
         else
-            GF_TRY(launch_pe_dropout(x_in, pe, s0.x(0), S, B, E, c->p_pe, rng, add, train0, st, s1 ? s1->x(0) : nullptr, train1));
-        if (rc) {
-            EpiArgs e0;
-            e0.bias = params + lo.in_b;
-            GF_TRY(nt(s0.x(0), t1.x(0), E, params + lo.in_w, s0.layer(0) + so.qkv, t1.layer(0) + so.qkv, 3 * E, EPI_NONE, e0));
-        }
+            GF_TRY(launch_stream_pe(x_in, pe, sa->slot, sa->pos, s0.x(0), T, sa->capacity, sa->max_len, E, st));
+        EpiArgs e0;
+        e0.bias = params + lo.in_b;
+        GF_TRY(nt(s0.x(0), t1.x(0), E, params + lo.in_w, s0.layer(0) + so.qkv, t1.layer(0) + so.qkv, 3 * E, EPI_NONE, e0));
+    } else {
+        RowCall r = stage(ROW_PE, c->p_pe, SITE_PE);
+        r.inproj(params + lo.in_w, params + lo.in_b);
+        GF_TRY(run(r, nullptr, nullptr, [&](const FwdSeg& s, float*) { return pe_seg(x_in, pe, s.x(0), s.layer(0) + so.qkv, s.train); }));
     }
 
     for (int l = 0; l < L; ++l) {
         const float* P = params + (int64_t)l * lo.total;
+        const float* Pn = (l + 1 < L) ? P + lo.total : nullptr;      // the next layer's parameters
         float* const v0 = s0.layer(l);
         float* const v1 = t1.layer(l);
         const uint32_t site = SITE_LAYER0 + 4 * l;
-        EpiArgs ea;
-        // qkv = X W_in^T + b_in
-        ea.bias = P + lo.in_b;
-        if (!rc) GF_TRY(nt(s0.x(l), t1.x(l), E, P + lo.in_w, v0 + so.qkv, v1 + so.qkv, 3 * E, EPI_NONE, ea));
         // attention core (keep words only when a backward will follow)
         if (sa && sa->count) {
             GF_TRY(launch_stream_attention_chunk(v0 + so.qkv, sa->cache + (int64_t)l * sa->layer_stride, sa->slot, sa->count, sa->pos,
@@ -326,49 +326,36 @@ static int encoder_fwd_walk(const EncCall& k, const Mode md, const FwdSeg& s0, c
             if (s1) a.pair(AttnSeg{v1 + so.qkv, v1 + so.attn_o, v1 + so.lse, keep_words(t1, v1), train1});
             GF_TRY(attention_fwd(a));
         }
-        // out-proj, residual + dropout + LN1
-        if (rc) {
-            RcFwdSeg1 r1{};
-            r1.pre_a = v1 + so.attn_o; r1.x = t1.x(l); r1.out = v1 + so.x1; r1.xhat = v1 + so.xhat1; r1.rstd = v1 + so.rstd1;
-            r1.train = train1;
-            GF_TRY(launch_rc_outproj_ln_fwd(v0 + so.attn_o, P + lo.out_w, P + lo.out_b, s0.x(l), P + lo.n1w, P + lo.n1b, v0 + so.x1,
-                                            v0 + so.xhat1, v0 + so.rstd1, T, c->ln_eps, c->p_enc, site + 1, rng, add, train0, st,
-                                            s1 ? &r1 : nullptr));
-        } else {
-            ea.bias = P + lo.out_b;
-            // (the 512-wide out-proj is 376 output tiles on 256 CUs: K in two halves, summed by the LayerNorm kernel)
-            int osplits = 1;
-            GF_TRY(nt(v0 + so.attn_o, v1 + so.attn_o, E, P + lo.out_w, s0.tmp, t1.tmp, E, EPI_NONE, ea, nullptr,
-                      md.outproj_nosplit() ? 1 : MAX_SPLITS, &osplits));
-            GF_TRY(ln(s0.x(l), t1.x(l), P + lo.n1w, P + lo.n1b, v0 + so.x1, v1 + so.x1, v0 + so.xhat1, v1 + so.xhat1, v0 + so.rstd1,
-                      v1 + so.rstd1, site + 1, osplits));
+        // stage A: out-proj, residual + dropout + LN1
+        // (as separate launches the 512-wide out-proj is 376 output tiles on 256 CUs: K in two halves, summed by the LayerNorm kernel)
+        {
+            RowCall r = stage(ROW_LN, c->p_enc, site + 1);
+            r.norm(P + lo.n1w, P + lo.n1b).front(P + lo.out_w, P + lo.out_b, md.outproj_nosplit() ? 1 : MAX_SPLITS, TE);
+            GF_TRY(run(r, v0, v1, [&](const FwdSeg& s, float* v) {
+                return ln_front_seg(v + so.attn_o, s.tmp, s.x(l), v + so.x1, v + so.xhat1, v + so.rstd1, s.train);
+            }));
         }
         // FFN: h = drop(relu(x1 W1^T + b1)); y = h W2^T + b2
         int splits = 1;
         {
-            EpiArgs e1;
+            EpiArgs e1, e2;
             e1.bias = P + lo.b1; e1.p = c->p_enc; e1.site = site + 2; e1.rng = rng; e1.rng_add = add; e1.train = train0;
             // hmask: the pattern the linear2 dgrad will ask for
             if (s0.keeps) e1.mask_out = reinterpret_cast<uint16_t*>(v0 + so.hmask);
             uint16_t* const mask1 = t1.keeps ? reinterpret_cast<uint16_t*>(v1 + so.hmask) : nullptr;
             GF_TRY(nt(v0 + so.x1, v1 + so.x1, E, P + lo.w1, v0 + so.h, v1 + so.h, F, EPI_RELU_DROP, e1, mask1));
             // few output tiles, K = 2048: K chunks = output slabs, summed by the LayerNorm kernel (gemm_n100.hip at d_model 100)
-            ea.bias = P + lo.b2;
-            GF_TRY(nt(v0 + so.h, v1 + so.h, F, P + lo.w2, s0.tmp, t1.tmp, E, EPI_NONE, ea, nullptr, MAX_SPLITS, &splits));
+            e2.bias = P + lo.b2;
+            GF_TRY(nt(v0 + so.h, v1 + so.h, F, P + lo.w2, s0.tmp, t1.tmp, E, EPI_NONE, e2, nullptr, MAX_SPLITS, &splits));
         }
-        if (rc) {
-            // LN2, then (all but the last layer) qkv of layer l + 1 from the fresh rows while they are in the workgroup
-            const float* Pn = (l + 1 < L) ? P + lo.total : nullptr;
-            RcFwdSeg1 r1{};
-            r1.y = t1.tmp; r1.x = v1 + so.x1; r1.out = t1.x(l + 1); r1.xhat = v1 + so.xhat2; r1.rstd = v1 + so.rstd2;
-            r1.post_out = Pn ? t1.layer(l + 1) + so.qkv : nullptr; r1.train = train1;
-            GF_TRY(launch_rc_ln_inproj_fwd(s0.tmp, splits, TE, v0 + so.x1, P + lo.n2w, P + lo.n2b, s0.x(l + 1), v0 + so.xhat2,
-                                           v0 + so.rstd2, Pn ? Pn + lo.in_w : nullptr, Pn ? Pn + lo.in_b : nullptr,
-                                           Pn ? s0.layer(l + 1) + so.qkv : nullptr, T, c->ln_eps, c->p_enc, site + 3, rng, add, train0,
-                                           st, s1 ? &r1 : nullptr));
-        } else {
-            GF_TRY(ln(v0 + so.x1, v1 + so.x1, P + lo.n2w, P + lo.n2b, s0.x(l + 1), t1.x(l + 1), v0 + so.xhat2, v1 + so.xhat2,
-                      v0 + so.rstd2, v1 + so.rstd2, site + 3, splits));
+        // stage B: the slabs, residual + dropout + LN2, then (all but the last layer) qkv of layer l + 1 from the fresh rows
+        {
+            RowCall r = stage(ROW_LN, c->p_enc, site + 3);
+            r.norm(P + lo.n2w, P + lo.n2b).slabs(splits, TE);
+            if (Pn) r.inproj(Pn + lo.in_w, Pn + lo.in_b);
+            GF_TRY(run(r, v0, v1, [&](const FwdSeg& s, float* v) {
+                return ln_slab_seg(s.tmp, v + so.x1, s.x(l + 1), v + so.xhat2, v + so.rstd2, Pn ? s.layer(l + 1) + so.qkv : nullptr, s.train);
+            }));
         }
     }
     return 0;
@@ -575,16 +562,22 @@ static int encoder_bwd(const EncCall& k) {
     float* dz1 = workspace + w.dz1;        // [T x E] LN1 input gradient (residual branch into X[l])
     float* d_attn = workspace + w.d_attn;  // [T x E]
     float* tmp = workspace + w.tmp;        // [MAX_SPLITS][T x E] partial slabs of dh W1
-    const bool rc = rc_supported(E) && !md.rc_off();
-    // rcw, per layer: in_w^T [E x 3E] | out_w^T [E x E]
-    if (rc) GF_TRY(launch_rc_pack(params + (int64_t)layer_lo * lo.total, lo.total, lo.in_w, lo.out_w, workspace + w.rcw, layer_hi - layer_lo, st));
-    const int lnblk = rc ? rc_blocks(T) : ln_bwd_blocks(T);
+    // The two LayerNorm backward stages are row stages (common.h RowCall).  Under the rowchain plan (d_model 100) the in-proj dgrad of
+    // the layer above runs inside the LN2 stage and the out-proj dgrad inside the LN1 stage, on transposed weights packed here;
+    // otherwise both are GEMMs of this walk.  rcw, per layer: in_w^T [E x 3E] | out_w^T [E x E]
+    const RowPlan rp = row_plan(E, md);
+    if (rp.rowchain) GF_TRY(launch_rc_pack(params + (int64_t)layer_lo * lo.total, lo.total, lo.in_w, lo.out_w, workspace + w.rcw, layer_hi - layer_lo, st));
+    auto stage = [&](uint32_t site) {
+        RowCall r = row_call(ROW_LN, T, B, E, c->ln_eps, c->p_enc, site, rng, add, st);
+        r.plan = rp;
+        return r;
+    };
     TnDesc tn[40]; int ntn = 0;
-    float* r_gw[2 * 64]; float* r_gb[2 * 64]; const float* r_part[2 * 64]; int r_nb[2 * 64];
-    int nred = 0;
+    LnRedList red;
 
     const float* dxin = dx;       // gradient wrt the current layer's output: the caller's dx, then in-proj dgrad slabs
     int dxin_slabs = 1;
+    int64_t dxin_stride = rp.rowchain ? 0 : TE;   // of one tensor no kernel reads it; each plan keeps the value its launches always got
     for (int l = layer_hi - 1; l >= layer_lo; --l) {
         const float* P = params + (int64_t)l * lo.total;
         float* G = grads ? grads + (int64_t)l * lo.total : nullptr;
@@ -600,19 +593,16 @@ static int encoder_bwd(const EncCall& k) {
         float* lnp1 = workspace + w.lnp1(i);
         // LN2 backward: dL/dX[l+1] -> dz2 (to x1), dyA (to FFN output).  dL/dX[l+1] is the caller's dx for the top layer
         // of the range and otherwise the in-proj dgrad of the layer above: split-K partial slabs in `tmp`, summed here
-        if (rc) {
-            // top layer of the range: the caller's dx; below it: the in-proj dgrad of the layer above (its d_qkv is still in
-            // that layer's buffer set, its residual-branch gradient in dz1) runs inside this kernel
-            const bool top = l == layer_hi - 1;
-            GF_TRY(launch_rc_ln_bwd(top ? nullptr : workspace + w.d_qkv_above(i), top ? nullptr : workspace + w.rcw_layer(i + 1),
-                                    top ? dx : nullptr, top ? 1 : 0, 0, top ? nullptr : dz1, sv + so.xhat2, sv + so.rstd2, P + lo.n2w, dz2,
-                                    dyA, G ? lnp2 : nullptr, nullptr, nullptr, T, c->p_enc, site + 3, rng, add, train, st));
-        } else {
-            GF_TRY(launch_add_drop_ln_bwd(dxin, sv + so.xhat2, sv + so.rstd2, P + lo.n2w, dz2, dyA, G ? G + lo.n2w : nullptr,
-                                          G ? G + lo.n2b : nullptr, T, E, c->p_enc, site + 3, rng, add, train, st, dxin_slabs, TE,
-                                          nullptr, G ? lnp2 : nullptr));
+        {
+            RowCall r = stage(site + 3);
+            r.backward(sv + so.xhat2, sv + so.rstd2, P + lo.n2w, dz2, dyA, train);
+            // rowchain, below the top layer of the range: the in-proj dgrad of the layer above (its d_qkv is still in that layer's
+            // buffer set, its residual-branch gradient in dz1) runs inside this kernel
+            if (rp.rowchain && l < layer_hi - 1) r.from_inproj(workspace + w.d_qkv_above(i), workspace + w.rcw_layer(i + 1), dz1);
+            else r.from(dxin, dxin_slabs, dxin_stride, nullptr);
+            if (G) r.param_grads(G + lo.n2w, G + lo.n2b, lnp2, &red);
+            GF_TRY(row_bwd(r));
         }
-        if (G) { r_gw[nred] = G + lo.n2w; r_gb[nred] = G + lo.n2b; r_part[nred] = lnp2; r_nb[nred] = lnblk; ++nred; }
         // linear2 wgrad: gW2[E,F] += dyA^T h ; gb2 += colsum(dyA)
         if (G) tn[ntn++] = TnDesc{dyA, E, sv + so.h, F, G + lo.w2, F, G + lo.b2, E, F, T};
         const float pdrop = train ? c->p_enc : 0.f, mscale = (pdrop > 0.f) ? 1.0f / (1.0f - pdrop) : 1.0f;
@@ -630,20 +620,17 @@ static int encoder_bwd(const EncCall& k) {
             // d x1 = dh W1 (split-K slabs) + dz2, consumed directly by the LN1 backward
             GF_TRY(gemm(gemm_nn(dh, P + lo.w1, tmp, T, E, F).slabs(MAX_SPLITS, TE, &splits).on(st)));
         }
-        if (rc) {
-            // LN1 backward + the out-proj dgrad (d_attn = dyB W_o) on the rows while they are in the workgroup
-            GF_TRY(launch_rc_ln_bwd(nullptr, nullptr, tmp, splits, TE, dz2, sv + so.xhat1, sv + so.rstd1, P + lo.n1w, dz1, dyB,
-                                    G ? lnp1 : nullptr, workspace + w.rcw_layer(i) + 3 * (int64_t)E * E, d_attn, T, c->p_enc,
-                                    site + 1, rng, add, train, st));
-        } else {
-            GF_TRY(launch_add_drop_ln_bwd(tmp, sv + so.xhat1, sv + so.rstd1, P + lo.n1w, dz1, dyB, G ? G + lo.n1w : nullptr,
-                                          G ? G + lo.n1b : nullptr, T, E, c->p_enc, site + 1, rng, add, train, st, splits, TE, dz2,
-                                          G ? lnp1 : nullptr));
+        {
+            // LN1 backward; rowchain: + the out-proj dgrad (d_attn = dyB W_o) on the rows while they are in the workgroup
+            RowCall r = stage(site + 1);
+            r.backward(sv + so.xhat1, sv + so.rstd1, P + lo.n1w, dz1, dyB, train).from(tmp, splits, TE, dz2);
+            if (rp.rowchain) r.outproj_dgrad(workspace + w.rcw_layer(i) + 3 * (int64_t)E * E, d_attn);
+            if (G) r.param_grads(G + lo.n1w, G + lo.n1b, lnp1, &red);
+            GF_TRY(row_bwd(r));
         }
-        if (G) { r_gw[nred] = G + lo.n1w; r_gb[nred] = G + lo.n1b; r_part[nred] = lnp1; r_nb[nred] = lnblk; ++nred; }
         // out-proj wgrad + dgrad
         if (G) tn[ntn++] = TnDesc{dyB, E, sv + so.attn_o, E, G + lo.out_w, E, G + lo.out_b, E, E, T};
-        if (!rc) GF_TRY(gemm(gemm_nn(dyB, P + lo.out_w, d_attn, T, E, E).on(st)));
+        if (!rp.rowchain) GF_TRY(gemm(gemm_nn(dyB, P + lo.out_w, d_attn, T, E, E).on(st)));
         // attention core backward
         GF_TRY(attention_bwd(attn_call(S, B, E, H, c->p_enc, site + 0, rng, add, st).mask(k.key_len, k.flags)
                                  .backward(sv + so.qkv, sv + so.attn_o, sv + so.lse, reinterpret_cast<const uint32_t*>(sv + so.keep), d_attn, d_qkv, train)));
@@ -654,7 +641,7 @@ static int encoder_bwd(const EncCall& k) {
             ntn = 0;
         }
         // dX[l] = d_qkv W_in + dz1 (.residual: added by split 0 in the GEMM epilogue)
-        if (l > layer_lo && rc) {
+        if (l > layer_lo && rp.rowchain) {
             // (the in-proj dgrad of this layer runs inside the LN2 backward kernel of layer l - 1)
         } else if (l > layer_lo) {
             // few output tiles (T/64 x E/64): split K into slabs that the next layer's LN2 backward sums on the fly
@@ -663,12 +650,13 @@ static int encoder_bwd(const EncCall& k) {
             GF_TRY(gemm(gemm_nn(d_qkv, P + lo.in_w, tmp, T, E, 3 * E).residual(dz1).slabs(MAX_SPLITS, TE, &sp, SLABS_INPROJ_DGRAD).on(st)));
             dxin = tmp;
             dxin_slabs = sp;
+            dxin_stride = TE;
         } else if (layer_lo > 0 || need_dx_in) {
             GF_TRY(gemm(gemm_nn(d_qkv, P + lo.in_w, dx, T, E, 3 * E).residual(dz1).on(st)));
         }   // (else: the stack's input needs no gradient — autograd would not compute this product either)
     }
     // (unreduced mode: nobody zeroed the gradient slab's encoder region — the LayerNorm parameter gradients are WRITTEN too)
-    if (nred > 0) GF_TRY(launch_ln_param_reduce(nred, r_gw, r_gb, r_part, r_nb, E, st, slabs != nullptr));
+    if (red.n > 0) GF_TRY(launch_ln_param_reduce(red, E, st, slabs != nullptr));
     if (layer_lo == 0 && need_dx_in) GF_TRY(launch_dropout_bwd_inplace(dx, T, E, c->p_pe, SITE_PE, rng, add, train, st));
     return 0;
 }
@@ -695,7 +683,7 @@ extern "C" int ganffn_encoder_bwd_mask(const ganffn_enc_cfg* c, const int32_t* k
 // does ganffn_encoder_bwd_parts leave the weight gradients of this stack unreduced?  (d_model 100 on the rowchain / tn100 kernels,
 // at most 10 layers: one grouped weight-gradient launch for the whole pass)
 static bool bwd_parts_supported(const ganffn_enc_cfg* c, const Mode md) {
-    return rc_supported(c->E) && !md.rc_off() && !md.tn100_off() && !md.tn100_in_kernel_sum() && !md.adam_slabs_off() && c->F == 2048 &&
+    return row_plan(c->E, md).rowchain && !md.tn100_off() && !md.tn100_in_kernel_sum() && !md.adam_slabs_off() && c->F == 2048 &&
            4 * c->L <= 40;
 }
 extern "C" int ganffn_encoder_bwd_parts_supported(const ganffn_enc_cfg* c) {

@@ -467,34 +467,14 @@ struct StreamArgs {
     const int32_t* count = nullptr; int m = 1;
 };
 
-// out1 (optional): a second segment over the same x in the same launch, with its own output and train flag
-int launch_pe_dropout(const float* x, const float* pe, float* out, int S, int B, int E, float p,
-                      const uint64_t* rng, uint64_t add, int train, hipStream_t st, float* out1 = nullptr, int train1 = 0);
 int launch_dropout_bwd_inplace(float* dx, int R, int C, float p, uint32_t site, const uint64_t* rng, uint64_t add,
                                int train, hipStream_t st);
 int launch_dropout(const float* x, float* out, int R, int C, float p, uint32_t site, const uint64_t* rng,
                    uint64_t add, int train, hipStream_t st);
-// y / d_out may be given as `nslab` partial slabs `slab_stride` floats apart (split-K GEMM output): they are summed
-// on the fly; d_out additionally takes an optional addend (the residual-branch gradient).
-// s1 (optional): a second row segment of T rows in the same launch (same parameters, nslab and slab_stride), with its own
-// operands and train flag
+// kernel argument of the two-segment LayerNorm forward (elementwise.hip): the second row segment's operands and train flag
 struct LnFwdSeg1 {
     const float* x; const float* y; float* out; float* xhat; float* rstd; int train;
 };
-int launch_add_drop_ln_fwd(const float* x, const float* y, const float* w, const float* b, float* out, float* xhat,
-                           float* rstd, int T, int E, float eps, float p, uint32_t site, const uint64_t* rng,
-                           uint64_t add, int train, hipStream_t st, int nslab = 1, long slab_stride = 0,
-                           const LnFwdSeg1* s1 = nullptr);
-// gw / gb: per-block partial sums go to gpart (ln_bwd_blocks(T) * 2 * E floats), to be added by launch_ln_param_reduce;
-// gpart == NULL runs one workgroup that adds its sums directly.  No atomics either way.
-int ln_bwd_blocks(int T);
-int launch_add_drop_ln_bwd(const float* d_out, const float* xhat, const float* rstd, const float* w, float* dz,
-                           float* dy, float* gw, float* gb, int T, int E, float p, uint32_t site,
-                           const uint64_t* rng, uint64_t add, int train, hipStream_t st, int nslab = 1,
-                           long slab_stride = 0, const float* addend = nullptr, float* gpart = nullptr);
-// overwrite: gw / gb = the sums (the caller did not zero them) instead of +=
-int launch_ln_param_reduce(int n, float* const* gw, float* const* gb, const float* const* part, const int* nblk, int E,
-                           hipStream_t st, bool overwrite = false);
 int launch_add_inplace(float* a, const float* b, int64_t n, hipStream_t st);
 
 // gemm_n100.hip — [T x K] x [K x 100] with a long K on 16x16x4 MFMAs (112-wide feature tile), K cut into output slabs.  Reached
@@ -509,28 +489,115 @@ bool rc_supported(int E);
 long rc_pack_floats();          // floats of one layer's transposed {in-proj, out-proj} weights (backward)
 int rc_blocks(int T);           // workgroups = partial rows of the LayerNorm parameter gradients per launch
 int launch_rc_pack(const float* params, long layer_stride, long off_in, long off_out, float* wt, int nl, hipStream_t st);
-// s1 (forward launchers, optional): a SECOND row segment of the same T rows with the same weights in the same launch — its
-// per-segment operands (named as in the kernel: pre_a = attn_o, y = slabs / PE table, x = residual, post_out = qkv) and its
-// train flag; the arguments proper describe segment 0.  Each segment gets the bits of its own single-segment launch.
+// kernel argument of the two-segment rowchain forward: the second row segment's operands (named as in the kernel: pre_a = attn_o,
+// y = slabs / PE table, x = residual, post_out = qkv) and train flag
 struct RcFwdSeg1 {
     const float* pre_a; const float* y; const float* x;
     float* out; float* xhat; float* rstd; float* post_out;
     int train;
 };
-int launch_rc_outproj_ln_fwd(const float* attn_o, const float* wo, const float* bo, const float* x, const float* gamma,
-                             const float* beta, float* out, float* xhat, float* rstd, int T, float eps, float p, uint32_t site,
-                             const uint64_t* rng, uint64_t add, int train, hipStream_t st, const RcFwdSeg1* s1 = nullptr);
-int launch_rc_pe_inproj_fwd(const float* x_in, const float* pe, float* out, const float* w_in, const float* b_in, float* qkv, int T,
-                            int B, float p, const uint64_t* rng, uint64_t add, int train, hipStream_t st,
-                            const RcFwdSeg1* s1 = nullptr);
-int launch_rc_ln_inproj_fwd(const float* y, int nslab, long slab_stride, const float* x, const float* gamma, const float* beta,
-                            float* out, float* xhat, float* rstd, const float* w_in, const float* b_in, float* qkv, int T,
-                            float eps, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train, hipStream_t st,
-                            const RcFwdSeg1* s1 = nullptr);
-int launch_rc_ln_bwd(const float* d_qkv, const float* w_in_t, const float* d_out, int nslab, long slab_stride, const float* addend,
-                     const float* xhat, const float* rstd, const float* gamma, float* dz, float* dy, float* gpart,
-                     const float* wo_t, float* d_attn, int T, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train,
-                     hipStream_t st);
+int ln_bwd_blocks(int T);       // the same for the plain LayerNorm backward (elementwise.hip)
+
+// ---------------------------------------------------------------------------------------
+// Row stages: the token-local steps of an encoder pass around the two LayerNorms and the positional encoding.
+//   forward   [front GEMM: y = attn_o . pre_w^T + pre_b]  ->  ROW_LN: out = LayerNorm(x + dropout(y)) | ROW_PE: out = dropout(x + pe[s])
+//             ->  [trailing in-proj: post_out = out . post_w^T + post_b]
+//   backward  (ROW_LN) d = (sum of the slabs of d_out | d_qkv . w_in_t^T) + addend  ->  dz, dy = dz * dropout multiplier, the parameter
+//             gradients  ->  [d_attn = dy . wo_t^T]
+// Every caller fills a RowCall and runs row_fwd or row_bwd on it (elementwise.hip); what a caller does not have stays null / 0.
+// ---------------------------------------------------------------------------------------
+// Which kernels run a stage: a pure function of the width and the mode word.
+struct RowPlan {
+    bool rowchain;       // the stage with its GEMMs is one rowchain.hip kernel (d_model 100) instead of separate launches
+    bool head_fused;     // ... and so is the ROW_PE stage at the head of a stack
+    // partial-sum blocks (rows of gpart, 2 E floats each) a backward launch writes
+    int blocks(int T) const { return rowchain ? rc_blocks(T) : ln_bwd_blocks(T); }
+};
+// streaming: the head of the stack is the streaming step's own gather (stream.hip), never a row stage
+static inline RowPlan row_plan(int E, const Mode md, bool streaming = false) {
+    const bool rc = rc_supported(E) && !md.rc_off();
+    return RowPlan{rc, rc && !md.pe_off() && !streaming};
+}
+// what a workspace must hold per backward launch, whichever mode word the pass will run under
+static inline int row_blocks_any_plan(int T) {
+    const int a = RowPlan{false, false}.blocks(T), b = RowPlan{true, true}.blocks(T);
+    return a > b ? a : b;
+}
+enum RowKind : int { ROW_LN = 0, ROW_PE = 1 };
+constexpr int LN_MAXSLAB = 16;   // slabs a LayerNorm kernel sums on the fly: the cap of every split rule that feeds one (api.hip MAX_SPLITS)
+// one row segment of a forward stage: T rows with their own buffers and train flag
+struct RowSeg {
+    const float* attn_o;                      // the front GEMM's input rows [T x E]
+    const float* y;                           // ROW_LN without a front GEMM: the slabs;  ROW_PE: the positional-encoding table
+    const float* x;                           // residual input [T x E] (ROW_PE: the stack's input)
+    float* out; float* xhat; float* rstd;     // xhat / rstd may be null (nothing kept for a backward)
+    float* post_out;                          // the trailing in-proj's output [T x 3E]
+    float* tmp;                               // slab scratch: where the separate-launch plan writes the front GEMM's slabs
+    int train;
+};
+// the three forms a forward segment takes; what a form does not have stays null
+static inline RowSeg pe_seg(const float* x_in, const float* pe, float* out, float* qkv, int train) {
+    RowSeg s{};
+    s.x = x_in; s.y = pe; s.out = out; s.post_out = qkv; s.train = train;
+    return s;
+}
+static inline RowSeg ln_front_seg(const float* attn_o, float* tmp, const float* x, float* out, float* xhat, float* rstd, int train) {
+    RowSeg s{};
+    s.attn_o = attn_o; s.tmp = tmp; s.x = x; s.out = out; s.xhat = xhat; s.rstd = rstd; s.train = train;
+    return s;
+}
+static inline RowSeg ln_slab_seg(const float* y, const float* x, float* out, float* xhat, float* rstd, float* qkv, int train) {
+    RowSeg s{};
+    s.y = y; s.x = x; s.out = out; s.xhat = xhat; s.rstd = rstd; s.post_out = qkv; s.train = train;
+    return s;
+}
+// the LayerNorm parameter gradients still to be summed from per-block partial rows: row_bwd appends, launch_ln_param_reduce adds
+struct LnRedRec { float* gw; float* gb; const float* part; int nblk; };
+struct LnRedList { LnRedRec r[2 * 64]; int n = 0; };
+struct RowCall {
+    RowKind kind; int T, B, E; float eps, p; uint32_t site; const uint64_t* rng; uint64_t add; hipStream_t st;
+    RowPlan plan;                                               // default: separate launches
+    const float* gamma; const float* beta;                      // ROW_LN
+    const float* pre_w; const float* pre_b; int pre_slab_cap;   // front GEMM (or null): W [E x E], bias, at most so many K slabs
+    int nslab; long slab_stride;                                // slabs of y / d_out, summed on the fly (a front GEMM reports its own count)
+    const float* post_w; const float* post_b;                   // trailing in-proj (or null): W [3E x E], bias
+    RowSeg seg[2]; int nseg;                                    // forward; nseg 2: a second segment of T rows in the same launches
+    // backward
+    const float* d_out; const float* addend; const float* xhat; const float* rstd; float* dz; float* dy; int train;
+    float* gw; float* gb; float* gpart; LnRedList* red;         // gpart null: one workgroup adds its sums to gw / gb itself
+    const float* d_qkv; const float* w_in_t;                    // rowchain only: d_out is d_qkv . w_in_t^T (in-proj weight packed by rc_pack)
+    const float* wo_t; float* d_attn;                           // rowchain only: d_attn = dy . wo_t^T (out-proj weight packed by rc_pack)
+    RowCall& under(const RowPlan& p_) { plan = p_; return *this; }
+    RowCall& norm(const float* gamma_, const float* beta_) { gamma = gamma_; beta = beta_; return *this; }
+    RowCall& front(const float* w, const float* b, int slab_cap, long stride) { pre_w = w; pre_b = b; pre_slab_cap = slab_cap; slab_stride = stride; return *this; }
+    RowCall& slabs(int n, long stride) { nslab = n; slab_stride = stride; return *this; }
+    RowCall& inproj(const float* w, const float* b) { post_w = w; post_b = b; return *this; }
+    RowCall& forward(const RowSeg& s) { seg[0] = s; nseg = 1; return *this; }
+    RowCall& pair(const RowSeg& s) { seg[1] = s; nseg = 2; return *this; }
+    RowCall& backward(const float* xhat_, const float* rstd_, const float* gamma_, float* dz_, float* dy_, int train_) {
+        xhat = xhat_; rstd = rstd_; gamma = gamma_; dz = dz_; dy = dy_; train = train_;
+        return *this;
+    }
+    RowCall& from(const float* d_out_, int n, long stride, const float* addend_) { d_out = d_out_; nslab = n; slab_stride = stride; addend = addend_; return *this; }
+    RowCall& from_inproj(const float* d_qkv_, const float* w_in_t_, const float* addend_) { d_qkv = d_qkv_; w_in_t = w_in_t_; addend = addend_; d_out = nullptr; nslab = 0; return *this; }
+    RowCall& outproj_dgrad(const float* wo_t_, float* d_attn_) { wo_t = wo_t_; d_attn = d_attn_; return *this; }
+    RowCall& param_grads(float* gw_, float* gb_, float* gpart_, LnRedList* red_) { gw = gw_; gb = gb_; gpart = gpart_; red = red_; return *this; }
+};
+static inline RowCall row_call(RowKind kind, int T, int B, int E, float eps, float p, uint32_t site, const uint64_t* rng, uint64_t add, hipStream_t st) {
+    RowCall k{};
+    k.kind = kind; k.T = T; k.B = B; k.E = E; k.eps = eps; k.p = p; k.site = site; k.rng = rng; k.add = add; k.st = st; k.nslab = 1;
+    return k;
+}
+// elementwise.hip: check the call (check_row_fwd / check_row_bwd: every refusal of the family, before any launch), then what the plan says — one
+// rowchain launch (launch_rc_fwd / launch_rc_bwd, rowchain.hip), or the separate launches: gemm() into the segment's slab scratch,
+// the LayerNorm or PE kernel over the slab count gemm() reported, gemm() for the in-proj.  row_bwd composes no GEMM: the products
+// around a backward stage read other buffers and sit elsewhere in the launch order under the two plans (api.hip encoder_bwd).
+int row_fwd(const RowCall& k);
+int row_bwd(const RowCall& k);
+int launch_rc_fwd(const RowCall& k);
+int launch_rc_bwd(const RowCall& k);
+// gw / gb += (overwrite: =, the caller did not zero them) the sums of every record's partial rows, in block order
+int launch_ln_param_reduce(const LnRedList& list, int E, hipStream_t st, bool overwrite = false);
 int launch_gelu_drop_fwd(const float* x, float* out, int R, int C, float p, uint32_t site, const uint64_t* rng,
                          uint64_t add, int train, hipStream_t st);
 

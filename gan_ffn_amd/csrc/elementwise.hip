@@ -90,7 +90,6 @@ __global__ void add3_kernel(const float* __restrict__ a, const float* __restrict
 // one wave per group of 4 rows; lane covers columns lane, lane+64, ...  (E <= 64*MAXC)
 // ------------------------------------------------------------------------------------------
 constexpr int LN_MAXC = 10;  // E <= 640 (d_model 600 of the MELD-dimension text stack)
-constexpr int LN_MAXSLAB = 16;  // split-K / split-F slabs summed on the fly (api.hip MAX_SPLITS)
 
 // NC = column chunks of 64 per lane (E <= 64 NC); NSB = slabs loaded per batch.  Every global load is issued from a
 // clamped (always valid) address and masked afterwards by a select: a load under a branch makes hipcc wait for it
@@ -758,17 +757,6 @@ __global__ __launch_bounds__(1024) void small_linear_dw_kernel(const float* __re
 // ------------------------------------------------------------------------------------------
 static inline int nblk(long n, int bs) { return (int)((n + bs - 1) / bs); }
 
-int launch_pe_dropout(const float* x, const float* pe, float* out, int S, int B, int E, float p,
-                      const uint64_t* rng, uint64_t add, int train, hipStream_t st, float* out1, int train1) {
-    const int T = S * B;
-    const long n = (long)((T + 3) / 4) * E;
-    const int nb = nblk(n, 256);
-    if (out1) hipLaunchKernelGGL(pe_dropout_kernel<true>, dim3(2 * nb), dim3(256), 0, st, x, pe, out, T, B, E, p, rng, add, train, out1, train1, nb);
-    else hipLaunchKernelGGL(pe_dropout_kernel<false>, dim3(nb), dim3(256), 0, st, x, pe, out, T, B, E, p, rng, add, train, (float*)nullptr, 0, 0);
-    GF_LAUNCH_CHECK();
-    return 0;
-}
-
 int launch_dropout(const float* x, float* out, int R, int C, float p, uint32_t site, const uint64_t* rng,
                    uint64_t add, int train, hipStream_t st) {
     const long n = (long)((R + 3) / 4) * C;
@@ -803,72 +791,175 @@ int launch_add_inplace(float* a, const float* b, int64_t n, hipStream_t st) {
     return 0;
 }
 
-int launch_add_drop_ln_fwd(const float* x, const float* y, const float* w, const float* b, float* out, float* xhat,
-                           float* rstd, int T, int E, float eps, float p, uint32_t site, const uint64_t* rng,
-                           uint64_t add, int train, hipStream_t st, int nslab, long slab_stride, const LnFwdSeg1* s1) {
-    GF_CHECK_ARG(E <= 64 * LN_MAXC, "layernorm: E=%d > %d", E, 64 * LN_MAXC);
-    GF_CHECK_ARG(nslab >= 1 && nslab <= LN_MAXSLAB, "layernorm: nslab=%d out of [1,%d]", nslab, LN_MAXSLAB);
-    GF_CHECK_ARG(!s1 || (s1->x && s1->y && s1->out), "layernorm: bad second segment");
-    const int G = (T + 3) / 4;
-    const dim3 grid((G + 3) / 4), grid2(2 * ((G + 3) / 4)), blk(256);
-#define GF_LN_FWD(NC, NSB)                                                                                              \
-    do {                                                                                                                \
-        if (s1) hipLaunchKernelGGL((add_drop_ln_fwd_kernel<NC, NSB, true>), grid2, blk, 0, st, x, y, w, b, out, xhat, rstd, T, E, eps, \
-                                   p, site, rng, add, train, nslab, slab_stride, *s1, (int)grid.x);                      \
-        else hipLaunchKernelGGL((add_drop_ln_fwd_kernel<NC, NSB>), grid, blk, 0, st, x, y, w, b, out, xhat, rstd, T, E, eps, p, \
-                                site, rng, add, train, nslab, slab_stride, LnFwdSeg1{}, 0);                              \
-    } while (0)
-    if (E <= 64) GF_LN_FWD(1, 8);
-    else if (E <= 128) GF_LN_FWD(2, 8);
-    else if (E <= 256) GF_LN_FWD(4, 4);
-    else if (E <= 320) GF_LN_FWD(5, 4);
-    else if (E <= 512) GF_LN_FWD(8, 2);
-    else GF_LN_FWD(10, 2);
-#undef GF_LN_FWD
-    GF_LAUNCH_CHECK();
-    return 0;
-}
-
+// ------------------------------------------------------------------------------------------
+// row stages (common.h RowCall): check, then one rowchain launch or the separate launches
+// ------------------------------------------------------------------------------------------
 int ln_bwd_blocks(int T) {
     int blocks = ((T + 3) / 4 + 3) / 4;
     return blocks > 256 ? 256 : blocks;
 }
 
-// gw / gb (when non-NULL): with a partial buffer gpart (>= ln_bwd_blocks(T) * 2 * E floats) the launch is full-width and
-// the caller must run launch_ln_param_reduce afterwards; without one a single workgroup does the whole tensor and adds
-// its sums directly (unit-test hook; still deterministic).
-int launch_add_drop_ln_bwd(const float* d_out, const float* xhat, const float* rstd, const float* w, float* dz,
-                           float* dy, float* gw, float* gb, int T, int E, float p, uint32_t site,
-                           const uint64_t* rng, uint64_t add, int train, hipStream_t st, int nslab, long slab_stride,
-                           const float* addend, float* gpart) {
-    GF_CHECK_ARG(E <= 64 * LN_MAXC, "layernorm: E=%d > %d", E, 64 * LN_MAXC);
+static bool row_fused(const RowCall& k) { return k.kind == ROW_PE ? k.plan.head_fused : k.plan.rowchain; }
+
+// Every refusal of the family, before any launch.  The texts carry the name of the launch the call would become.
+static int check_row_fwd(const RowCall& k) {
+    const RowSeg& s = k.seg[0];
+    const RowSeg& t = k.seg[1];
+    const bool pair = k.nseg == 2;
+    GF_CHECK_ARG(k.nseg == 1 || k.nseg == 2, "row stage: %d segments", k.nseg);
+    GF_CHECK_ARG(!(k.kind == ROW_PE && k.pre_w), "row stage: the positional encoding has no GEMM in front");
+    if (row_fused(k) && k.kind == ROW_PE) {
+        GF_CHECK_ARG(s.x && s.y && s.out && k.post_w && k.post_b && s.post_out && k.T > 0 && k.B > 0, "rc_pe_inproj_fwd: bad arguments");
+        GF_CHECK_ARG(!pair || (t.y && t.x && t.out && t.post_out && aligned16(t.y) && aligned16(t.x) && aligned16(t.out) && aligned16(t.post_out)),
+                     "rc_pe_inproj_fwd: bad second segment");
+        GF_CHECK_ARG(aligned16(s.x) && aligned16(s.y) && aligned16(s.out) && aligned16(k.post_w) && aligned16(k.post_b) && aligned16(s.post_out),
+                     "rc_pe_inproj_fwd: operands must be 16-byte aligned");
+        return 0;
+    }
+    if (row_fused(k)) {
+        // the rows that enter: the front GEMM's input, or the slabs
+        const char* name = k.pre_w ? "rc_outproj_ln_fwd" : "rc_ln_inproj_fwd";
+        const float* in0 = k.pre_w ? s.attn_o : s.y;
+        const float* in1 = k.pre_w ? t.attn_o : t.y;
+        GF_CHECK_ARG(!(k.pre_w && k.post_w), "%s: no rowchain kernel has a GEMM on both sides", name);
+        GF_CHECK_ARG(in0 && (k.pre_w ? k.pre_b != nullptr : k.nslab >= 1) && s.x && k.gamma && k.beta && s.out && k.T > 0, "%s: bad arguments", name);
+        GF_CHECK_ARG(!pair || (in1 && t.x && t.out && aligned16(in1) && aligned16(t.x) && aligned16(t.out) && (!t.xhat || aligned16(t.xhat)) &&
+                               (!k.post_w || (t.post_out && aligned16(t.post_out)))), "%s: bad second segment", name);
+        GF_CHECK_ARG(aligned16(in0) && (k.pre_w ? aligned16(k.pre_w) && aligned16(k.pre_b) : (k.slab_stride & 3) == 0) && aligned16(s.x) &&
+                         aligned16(k.gamma) && aligned16(k.beta) && aligned16(s.out) && (!s.xhat || aligned16(s.xhat)),
+                     "%s: operands must be 16-byte aligned", name);
+        GF_CHECK_ARG(!k.post_w || (k.post_b && s.post_out && aligned16(k.post_w) && aligned16(k.post_b) && aligned16(s.post_out)),
+                     "%s: in-proj needs bias, output and 16-byte aligned operands", name);
+        return 0;
+    }
+    // separate launches; the two GEMMs are checked by gemm() (check_gemm) when their turn comes
+    if (k.kind == ROW_PE) {
+        GF_CHECK_ARG(s.x && s.y && s.out && k.T > 0 && k.B > 0 && k.E > 0, "pe_dropout: bad arguments");
+        // (the two-segment kernel reads one input and one table for both segments)
+        GF_CHECK_ARG(!pair || (t.out && t.x == s.x && t.y == s.y), "pe_dropout: bad second segment");
+        return 0;
+    }
+    const int nslab = k.pre_w ? k.pre_slab_cap : k.nslab;     // a front GEMM writes at most its cap
+    GF_CHECK_ARG(k.E <= 64 * LN_MAXC, "layernorm: E=%d > %d", k.E, 64 * LN_MAXC);
     GF_CHECK_ARG(nslab >= 1 && nslab <= LN_MAXSLAB, "layernorm: nslab=%d out of [1,%d]", nslab, LN_MAXSLAB);
-    int blocks = ln_bwd_blocks(T);
-    if (gw != nullptr && gpart == nullptr) blocks = 1;
-    if (gw == nullptr) gpart = nullptr;
-    const dim3 grid(blocks), blk(256);
-#define GF_LN_BWD(NC, NSB)                                                                                            \
-    hipLaunchKernelGGL((add_drop_ln_bwd_kernel<NC, NSB>), grid, blk, 0, st, d_out, xhat, rstd, w, dz, dy, gw, gb, T, \
-                       E, p, site, rng, add, train, nslab, slab_stride, addend, gpart)
-    if (E <= 64) GF_LN_BWD(1, 8);
-    else if (E <= 128) GF_LN_BWD(2, 8);
-    else if (E <= 256) GF_LN_BWD(4, 4);
-    else if (E <= 320) GF_LN_BWD(5, 4);
-    else if (E <= 512) GF_LN_BWD(8, 2);
-    else GF_LN_BWD(10, 2);
-#undef GF_LN_BWD
-    GF_LAUNCH_CHECK();
+    GF_CHECK_ARG(!pair || (t.x && (k.pre_w ? t.tmp : t.y) && t.out), "layernorm: bad second segment");
+    GF_CHECK_ARG(s.x && (k.pre_w ? s.tmp : s.y) && k.gamma && k.beta && s.out && k.T > 0 && k.E > 0, "layernorm: bad arguments");
     return 0;
 }
 
-// add the per-block partial sums of n LayerNorm backward launches (gw[i], gb[i] += sum over nblk[i] blocks of part[i])
-int launch_ln_param_reduce(int n, float* const* gw, float* const* gb, const float* const* part, const int* nblk, int E,
-                           hipStream_t st, bool overwrite) {
-    for (int i0 = 0; i0 < n; i0 += LN_RED_MAX) {
+static int check_row_bwd(const RowCall& k) {
+    GF_CHECK_ARG(k.kind == ROW_LN, "row stage: the positional encoding's backward is a dropout launch");
+    if (k.plan.rowchain) {
+        GF_CHECK_ARG((k.d_qkv || k.d_out) && k.xhat && k.rstd && k.gamma && k.dz && k.T > 0, "rc_ln_bwd: bad arguments");
+        GF_CHECK_ARG(!k.d_qkv || (k.w_in_t && aligned16(k.d_qkv) && aligned16(k.w_in_t)), "rc_ln_bwd: in-proj dgrad needs the transposed weight");
+        GF_CHECK_ARG(!k.wo_t || (k.d_attn && k.dy && aligned16(k.wo_t) && aligned16(k.d_attn)), "rc_ln_bwd: out-proj dgrad needs dy and an output");
+        GF_CHECK_ARG((!k.d_out || (aligned16(k.d_out) && (k.slab_stride & 3) == 0)) && (!k.addend || aligned16(k.addend)) && aligned16(k.xhat) &&
+                         aligned16(k.gamma) && aligned16(k.dz) && (!k.dy || aligned16(k.dy)), "rc_ln_bwd: operands must be 16-byte aligned");
+    } else {
+        GF_CHECK_ARG(k.E <= 64 * LN_MAXC, "layernorm: E=%d > %d", k.E, 64 * LN_MAXC);
+        GF_CHECK_ARG(k.nslab >= 1 && k.nslab <= LN_MAXSLAB, "layernorm: nslab=%d out of [1,%d]", k.nslab, LN_MAXSLAB);
+        GF_CHECK_ARG(!k.d_qkv && !k.wo_t, "layernorm: the in-proj and out-proj dgrads run inside the rowchain kernels only");
+        GF_CHECK_ARG(k.d_out && k.xhat && k.rstd && k.gamma && k.dz && k.T > 0 && k.E > 0, "layernorm: bad arguments");
+    }
+    GF_CHECK_ARG(!(k.red && k.gw && k.gpart) || k.red->n < (int)(sizeof(k.red->r) / sizeof(k.red->r[0])), "layernorm: reduce list is full");
+    return 0;
+}
+
+// f(NC, NSB) for the width: NC column chunks of 64 per lane, NSB slabs loaded per batch
+template <class F>
+static inline int with_ln_width(int E, F&& f) {
+    using std::integral_constant;
+    if (E <= 64) return f(integral_constant<int, 1>{}, integral_constant<int, 8>{});
+    if (E <= 128) return f(integral_constant<int, 2>{}, integral_constant<int, 8>{});
+    if (E <= 256) return f(integral_constant<int, 4>{}, integral_constant<int, 4>{});
+    if (E <= 320) return f(integral_constant<int, 5>{}, integral_constant<int, 4>{});
+    if (E <= 512) return f(integral_constant<int, 8>{}, integral_constant<int, 2>{});
+    return f(integral_constant<int, 10>{}, integral_constant<int, 2>{});
+}
+
+// out = dropout(x + pe[s]); a second segment writes its own output from the same input
+static int launch_pe_dropout(const RowCall& k) {
+    const RowSeg& s = k.seg[0];
+    const int nb = nblk((long)((k.T + 3) / 4) * k.E, 256);
+    return with_flag(k.nseg == 2, [&](auto pair) {
+        constexpr bool PAIR = decltype(pair)::value;
+        hipLaunchKernelGGL(pe_dropout_kernel<PAIR>, dim3(PAIR ? 2 * nb : nb), dim3(256), 0, k.st, s.x, s.y, s.out, k.T, k.B, k.E, k.p, k.rng, k.add,
+                           s.train, PAIR ? k.seg[1].out : (float*)nullptr, PAIR ? k.seg[1].train : 0, PAIR ? nb : 0);
+        GF_LAUNCH_CHECK();
+        return 0;
+    });
+}
+
+// out = LayerNorm(x + dropout(sum of the nslab slabs of y)), y per segment
+static int launch_ln_fwd(const RowCall& k, const float* y0, const float* y1, int nslab) {
+    const RowSeg& s = k.seg[0];
+    const int nb = (((k.T + 3) / 4) + 3) / 4;
+    return with_ln_width(k.E, [&](auto nc, auto nsb) {
+        return with_flag(k.nseg == 2, [&](auto pair) {
+            constexpr bool PAIR = decltype(pair)::value;
+            const RowSeg& t = k.seg[1];
+            const LnFwdSeg1 s1 = PAIR ? LnFwdSeg1{t.x, y1, t.out, t.xhat, t.rstd, t.train} : LnFwdSeg1{};
+            hipLaunchKernelGGL((add_drop_ln_fwd_kernel<decltype(nc)::value, decltype(nsb)::value, PAIR>), dim3(PAIR ? 2 * nb : nb), dim3(256), 0,
+                               k.st, s.x, y0, k.gamma, k.beta, s.out, s.xhat, s.rstd, k.T, k.E, k.eps, k.p, k.site, k.rng, k.add, s.train,
+                               nslab, k.slab_stride, s1, PAIR ? nb : 0);
+            GF_LAUNCH_CHECK();
+            return 0;
+        });
+    });
+}
+
+int row_fwd(const RowCall& k) {
+    GF_TRY(check_row_fwd(k));
+    if (row_fused(k)) return launch_rc_fwd(k);
+    const RowSeg& s = k.seg[0];
+    const RowSeg& t = k.seg[1];
+    const bool pair = k.nseg == 2;
+    int nslab = k.nslab;
+    if (k.pre_w) {
+        GemmCall g = gemm_nt(s.attn_o, k.pre_w, s.tmp, k.T, k.E, k.E).bias(k.pre_b).slabs(k.pre_slab_cap, k.slab_stride, &nslab).on(k.st);
+        if (pair) g.pair(GemmSeg1{t.attn_o, t.tmp, nullptr, t.train});
+        GF_TRY(gemm(g));
+    }
+    if (k.kind == ROW_PE) GF_TRY(launch_pe_dropout(k));
+    else GF_TRY(launch_ln_fwd(k, k.pre_w ? s.tmp : s.y, k.pre_w ? t.tmp : t.y, nslab));
+    if (k.post_w) {
+        GemmCall g = gemm_nt(s.out, k.post_w, s.post_out, k.T, 3 * k.E, k.E).bias(k.post_b).on(k.st);
+        if (pair) g.pair(GemmSeg1{t.out, t.post_out, nullptr, t.train});
+        GF_TRY(gemm(g));
+    }
+    return 0;
+}
+
+// gw / gb with a partial buffer gpart (>= plan.blocks(T) * 2 * E floats): the launch is full-width and the sums are added by
+// launch_ln_param_reduce over the list the call names; without one a single workgroup does the whole tensor and adds its sums
+// directly (unit-test hook; still deterministic).  No atomics either way.
+int row_bwd(const RowCall& k) {
+    GF_TRY(check_row_bwd(k));
+    if (k.plan.rowchain) {
+        GF_TRY(launch_rc_bwd(k));
+    } else {
+        const int blocks = (k.gw != nullptr && k.gpart == nullptr) ? 1 : k.plan.blocks(k.T);
+        float* const gpart = k.gw ? k.gpart : nullptr;
+        GF_TRY(with_ln_width(k.E, [&](auto nc, auto nsb) {
+            hipLaunchKernelGGL((add_drop_ln_bwd_kernel<decltype(nc)::value, decltype(nsb)::value>), dim3(blocks), dim3(256), 0, k.st, k.d_out, k.xhat,
+                               k.rstd, k.gamma, k.dz, k.dy, k.gw, k.gb, k.T, k.E, k.p, k.site, k.rng, k.add, k.train, k.nslab, k.slab_stride,
+                               k.addend, gpart);
+            GF_LAUNCH_CHECK();
+            return 0;
+        }));
+    }
+    if (k.red && k.gw && k.gpart) k.red->r[k.red->n++] = LnRedRec{k.gw, k.gb, k.gpart, k.plan.blocks(k.T)};
+    return 0;
+}
+
+// add the per-block partial sums of the listed LayerNorm backward launches (gw, gb += sum over nblk blocks of part)
+int launch_ln_param_reduce(const LnRedList& list, int E, hipStream_t st, bool overwrite) {
+    for (int i0 = 0; i0 < list.n; i0 += LN_RED_MAX) {
         LnRedGroup grp;
-        const int m = n - i0 < LN_RED_MAX ? n - i0 : LN_RED_MAX;
+        const int m = list.n - i0 < LN_RED_MAX ? list.n - i0 : LN_RED_MAX;
         for (int i = 0; i < m; ++i) {
-            grp.gw[i] = gw[i0 + i]; grp.gb[i] = gb[i0 + i]; grp.part[i] = part[i0 + i]; grp.nblk[i] = nblk[i0 + i];
+            const LnRedRec& r = list.r[i0 + i];
+            grp.gw[i] = r.gw; grp.gb[i] = r.gb; grp.part[i] = r.part; grp.nblk[i] = r.nblk;
         }
         hipLaunchKernelGGL(ln_param_reduce_kernel, dim3((E + 63) / 64, m), dim3(1024), 0, st, grp, E, overwrite ? 1 : 0);
         GF_LAUNCH_CHECK();
@@ -1095,7 +1186,8 @@ extern "C" int ganffn_add_dropout_layernorm_fwd(const float* x, const float* y, 
                                                 const uint64_t* rng, uint64_t rng_offset_add, void* stream) {
     GF_CHECK_ARG(x && y && w && b && out && T > 0 && E > 0, "add_dropout_layernorm_fwd: bad arguments");
     GF_CHECK_ARG(p <= 0.f || rng, "add_dropout_layernorm_fwd: rng required");
-    return launch_add_drop_ln_fwd(x, y, w, b, out, xhat, rstd, T, E, eps, p, site, rng, rng_offset_add, 1, (hipStream_t)stream);
+    return row_fwd(row_call(ROW_LN, T, 1, E, eps, p, site, rng, rng_offset_add, (hipStream_t)stream).norm(w, b)
+                       .forward(ln_slab_seg(y, x, out, xhat, rstd, nullptr, 1)));
 }
 
 extern "C" int ganffn_add_dropout_layernorm_bwd(const float* d_out, const float* xhat, const float* rstd, const float* w,
@@ -1103,6 +1195,6 @@ extern "C" int ganffn_add_dropout_layernorm_bwd(const float* d_out, const float*
                                                 uint32_t site, const uint64_t* rng, uint64_t rng_offset_add, void* stream) {
     GF_CHECK_ARG(d_out && xhat && rstd && w && dz && T > 0 && E > 0, "add_dropout_layernorm_bwd: bad arguments");
     GF_CHECK_ARG(p <= 0.f || rng, "add_dropout_layernorm_bwd: rng required");
-    return launch_add_drop_ln_bwd(d_out, xhat, rstd, w, dz, dy, gw, gb, T, E, p, site, rng, rng_offset_add, 1,
-                                  (hipStream_t)stream, 1, 0, nullptr, nullptr);
+    return row_bwd(row_call(ROW_LN, T, 1, E, 0.f, p, site, rng, rng_offset_add, (hipStream_t)stream).backward(xhat, rstd, w, dz, dy, 1)
+                       .from(d_out, 1, 0, nullptr).param_grads(gw, gb, nullptr, nullptr));
 }

@@ -554,97 +554,70 @@ int launch_rc_pack(const float* params, long layer_stride, long off_in, long off
     return 0;
 }
 
-// forward A: x1 = LayerNorm1(x + dropout(attn_o . Wo^T + bo))
-int launch_rc_outproj_ln_fwd(const float* attn_o, const float* wo, const float* bo, const float* x, const float* gamma,
-                             const float* beta, float* out, float* xhat, float* rstd, int T, float eps, float p, uint32_t site,
-                             const uint64_t* rng, uint64_t add, int train, hipStream_t st, const RcFwdSeg1* s1) {
-    GF_CHECK_ARG(attn_o && wo && bo && x && gamma && beta && out && T > 0, "rc_outproj_ln_fwd: bad arguments");
-    GF_CHECK_ARG(!s1 || (s1->pre_a && s1->x && s1->out && aligned16(s1->pre_a) && aligned16(s1->x) && aligned16(s1->out) &&
-                         (!s1->xhat || aligned16(s1->xhat))), "rc_outproj_ln_fwd: bad second segment");
-    GF_CHECK_ARG(aligned16(attn_o) && aligned16(wo) && aligned16(bo) && aligned16(x) && aligned16(gamma) && aligned16(beta) &&
-                     aligned16(out) && (!xhat || aligned16(xhat)), "rc_outproj_ln_fwd: operands must be 16-byte aligned");
-    RcFwdArgs a{};
-    a.pre_a = attn_o; a.pre_w = wo; a.pre_b = bo; a.x = x; a.gamma = gamma; a.beta = beta; a.out = out; a.xhat = xhat; a.rstd = rstd;
-    a.T = T; a.eps = eps; a.p = p; a.site = site; a.rng = rng; a.add = add; a.train = train;
-    if (s1) hipLaunchKernelGGL((rc_fwd_pair_kernel<1, false>), dim3(2 * rc_blocks(T)), dim3(256), 0, st, a, *s1, rc_blocks(T));
-    else hipLaunchKernelGGL((rc_fwd_kernel<1, false>), dim3(rc_blocks(T)), dim3(256), 0, st, a);
-    GF_LAUNCH_CHECK();
-    return 0;
+// The launches below trust check_row_fwd / check_row_bwd (elementwise.hip): row_fwd / row_bwd have run it on the call.
+
+// f(PRE, POST_GEMM) over the four forward forms that exist:
+//   ROW_PE            <2, true>   x0 = dropout(x_in + pe[s]) and qkv of layer 0 — the head of an encoder stack
+//   ROW_LN, front     <1, false>  x1 = LayerNorm1(x + dropout(attn_o . Wo^T + bo))
+//   ROW_LN, slabs     <0, post>   out = LayerNorm2(x + dropout(sum of slabs)); post: qkv = out . w_in^T + b_in (the next layer's in-proj)
+template <class F>
+static inline int with_rc_fwd_form(const RowCall& k, F&& f) {
+    if (k.kind == ROW_PE) return f(std::integral_constant<int, 2>{}, std::true_type{});
+    if (k.pre_w) return f(std::integral_constant<int, 1>{}, std::false_type{});
+    return with_flag(k.post_w != nullptr, [&](auto post) { return f(std::integral_constant<int, 0>{}, post); });
 }
 
-// forward B: out = LayerNorm2(x + dropout(sum of slabs)); with w_in: qkv = out . w_in^T + b_in (the next layer's in-proj)
-int launch_rc_ln_inproj_fwd(const float* y, int nslab, long slab_stride, const float* x, const float* gamma, const float* beta,
-                            float* out, float* xhat, float* rstd, const float* w_in, const float* b_in, float* qkv, int T,
-                            float eps, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train, hipStream_t st,
-                            const RcFwdSeg1* s1) {
-    GF_CHECK_ARG(y && x && gamma && beta && out && T > 0 && nslab >= 1, "rc_ln_inproj_fwd: bad arguments");
-    GF_CHECK_ARG(!s1 || (s1->y && s1->x && s1->out && aligned16(s1->y) && aligned16(s1->x) && aligned16(s1->out) &&
-                         (!s1->xhat || aligned16(s1->xhat)) && (!w_in || (s1->post_out && aligned16(s1->post_out)))),
-                 "rc_ln_inproj_fwd: bad second segment");
-    GF_CHECK_ARG(aligned16(y) && (slab_stride & 3) == 0 && aligned16(x) && aligned16(gamma) && aligned16(beta) && aligned16(out) &&
-                     (!xhat || aligned16(xhat)), "rc_ln_inproj_fwd: operands must be 16-byte aligned");
-    GF_CHECK_ARG(!w_in || (b_in && qkv && aligned16(w_in) && aligned16(b_in) && aligned16(qkv)),
-                 "rc_ln_inproj_fwd: in-proj needs bias, output and 16-byte aligned operands");
+int launch_rc_fwd(const RowCall& k) {
+    const RowSeg& s = k.seg[0];
+    // what a form does not read stays zero
     RcFwdArgs a{};
-    a.y = y; a.nslab = nslab; a.slab_stride = slab_stride; a.x = x; a.gamma = gamma; a.beta = beta; a.out = out; a.xhat = xhat;
-    a.rstd = rstd; a.post_w = w_in; a.post_b = b_in; a.post_out = qkv;
-    a.T = T; a.eps = eps; a.p = p; a.site = site; a.rng = rng; a.add = add; a.train = train;
-    const int nb = rc_blocks(T);
-    if (s1 && w_in) hipLaunchKernelGGL((rc_fwd_pair_kernel<0, true>), dim3(2 * nb), dim3(256), 0, st, a, *s1, nb);
-    else if (s1) hipLaunchKernelGGL((rc_fwd_pair_kernel<0, false>), dim3(2 * nb), dim3(256), 0, st, a, *s1, nb);
-    else if (w_in) hipLaunchKernelGGL((rc_fwd_kernel<0, true>), dim3(nb), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((rc_fwd_kernel<0, false>), dim3(nb), dim3(256), 0, st, a);
-    GF_LAUNCH_CHECK();
-    return 0;
-}
-
-// forward 0: x0 = dropout(x_in + pe[s]) and qkv of layer 0 = x0 . w_in^T + b_in — the head of an encoder stack as one launch
-int launch_rc_pe_inproj_fwd(const float* x_in, const float* pe, float* out, const float* w_in, const float* b_in, float* qkv, int T,
-                            int B, float p, const uint64_t* rng, uint64_t add, int train, hipStream_t st, const RcFwdSeg1* s1) {
-    GF_CHECK_ARG(x_in && pe && out && w_in && b_in && qkv && T > 0 && B > 0, "rc_pe_inproj_fwd: bad arguments");
-    GF_CHECK_ARG(!s1 || (s1->y && s1->x && s1->out && s1->post_out && aligned16(s1->y) && aligned16(s1->x) && aligned16(s1->out) &&
-                         aligned16(s1->post_out)), "rc_pe_inproj_fwd: bad second segment");
-    GF_CHECK_ARG(aligned16(x_in) && aligned16(pe) && aligned16(out) && aligned16(w_in) && aligned16(b_in) && aligned16(qkv),
-                 "rc_pe_inproj_fwd: operands must be 16-byte aligned");
-    RcFwdArgs a{};
-    a.y = pe; a.x = x_in; a.out = out; a.post_w = w_in; a.post_b = b_in; a.post_out = qkv;
-    a.T = T; a.B = B; a.p = p; a.site = SITE_PE; a.rng = rng; a.add = add; a.train = train;
-    if (s1) hipLaunchKernelGGL((rc_fwd_pair_kernel<2, true>), dim3(2 * rc_blocks(T)), dim3(256), 0, st, a, *s1, rc_blocks(T));
-    else hipLaunchKernelGGL((rc_fwd_kernel<2, true>), dim3(rc_blocks(T)), dim3(256), 0, st, a);
-    GF_LAUNCH_CHECK();
-    return 0;
+    a.x = s.x; a.out = s.out; a.post_w = k.post_w; a.post_b = k.post_b; a.post_out = s.post_out;
+    a.T = k.T; a.p = k.p; a.rng = k.rng; a.add = k.add; a.train = s.train;
+    if (k.kind == ROW_PE) {
+        a.y = s.y; a.B = k.B; a.site = SITE_PE;
+    } else {
+        a.gamma = k.gamma; a.beta = k.beta; a.xhat = s.xhat; a.rstd = s.rstd; a.eps = k.eps; a.site = k.site;
+        if (k.pre_w) { a.pre_a = s.attn_o; a.pre_w = k.pre_w; a.pre_b = k.pre_b; }
+        else { a.y = s.y; a.nslab = k.nslab; a.slab_stride = k.slab_stride; }
+    }
+    const int nb = rc_blocks(k.T);
+    return with_rc_fwd_form(k, [&](auto pre, auto post) {
+        constexpr int PRE = decltype(pre)::value;
+        constexpr bool POST = decltype(post)::value;
+        if (k.nseg == 2) {
+            const RowSeg& t = k.seg[1];
+            const RcFwdSeg1 s1{t.attn_o, t.y, t.x, t.out, t.xhat, t.rstd, t.post_out, t.train};
+            hipLaunchKernelGGL((rc_fwd_pair_kernel<PRE, POST>), dim3(2 * nb), dim3(256), 0, k.st, a, s1, nb);
+        } else {
+            hipLaunchKernelGGL((rc_fwd_kernel<PRE, POST>), dim3(nb), dim3(256), 0, k.st, a);
+        }
+        GF_LAUNCH_CHECK();
+        return 0;
+    });
 }
 
 // backward of a LayerNorm with its surroundings.  Incoming gradient: d_qkv . w_in_t^T (w_in_t = in-proj weight transposed,
 // [E x 3E]) when d_qkv is given, else the nslab slabs of d_out; + addend.  Outgoing: dz, dy = dz * dropout multiplier, the
 // per-workgroup partial sums of the LayerNorm parameter gradients (gpart: rc_blocks(T) * 2 * E floats), and with wo_t
 // (out-proj weight transposed) d_attn = dy . wo_t^T.
-int launch_rc_ln_bwd(const float* d_qkv, const float* w_in_t, const float* d_out, int nslab, long slab_stride, const float* addend,
-                     const float* xhat, const float* rstd, const float* gamma, float* dz, float* dy, float* gpart,
-                     const float* wo_t, float* d_attn, int T, float p, uint32_t site, const uint64_t* rng, uint64_t add, int train,
-                     hipStream_t st) {
-    GF_CHECK_ARG((d_qkv || d_out) && xhat && rstd && gamma && dz && T > 0, "rc_ln_bwd: bad arguments");
-    GF_CHECK_ARG(!d_qkv || (w_in_t && aligned16(d_qkv) && aligned16(w_in_t)), "rc_ln_bwd: in-proj dgrad needs the transposed weight");
-    GF_CHECK_ARG(!wo_t || (d_attn && dy && aligned16(wo_t) && aligned16(d_attn)), "rc_ln_bwd: out-proj dgrad needs dy and an output");
-    GF_CHECK_ARG((!d_out || (aligned16(d_out) && (slab_stride & 3) == 0)) && (!addend || aligned16(addend)) && aligned16(xhat) &&
-                     aligned16(gamma) && aligned16(dz) && (!dy || aligned16(dy)), "rc_ln_bwd: operands must be 16-byte aligned");
+int launch_rc_bwd(const RowCall& k) {
     RcBwdArgs a{};
-    a.pre_a = d_qkv; a.pre_wt = w_in_t; a.d_out = d_out; a.nslab = nslab; a.slab_stride = slab_stride; a.addend = addend;
-    a.xhat = xhat; a.rstd = rstd; a.gamma = gamma; a.dz = dz; a.dy = dy; a.gpart = gpart; a.post_wt = wo_t; a.post_out = d_attn;
-    a.T = T; a.p = p; a.site = site; a.rng = rng; a.add = add; a.train = train;
-    const dim3 grid(rc_blocks(T)), blk(256);
-    if (d_qkv) {
-        if (wo_t) hipLaunchKernelGGL((rc_bwd_kernel<2, true>), grid, blk, 0, st, a);
-        else hipLaunchKernelGGL((rc_bwd_kernel<2, false>), grid, blk, 0, st, a);
-    } else if (nslab > 1) {
-        if (wo_t) hipLaunchKernelGGL((rc_bwd_kernel<1, true>), grid, blk, 0, st, a);
-        else hipLaunchKernelGGL((rc_bwd_kernel<1, false>), grid, blk, 0, st, a);
-    } else {
-        if (wo_t) hipLaunchKernelGGL((rc_bwd_kernel<0, true>), grid, blk, 0, st, a);
-        else hipLaunchKernelGGL((rc_bwd_kernel<0, false>), grid, blk, 0, st, a);
-    }
-    GF_LAUNCH_CHECK();
-    return 0;
+    a.pre_a = k.d_qkv; a.pre_wt = k.w_in_t; a.d_out = k.d_out; a.nslab = k.nslab; a.slab_stride = k.slab_stride; a.addend = k.addend;
+    a.xhat = k.xhat; a.rstd = k.rstd; a.gamma = k.gamma; a.dz = k.dz; a.dy = k.dy; a.gpart = k.gpart; a.post_wt = k.wo_t; a.post_out = k.d_attn;
+    a.T = k.T; a.p = k.p; a.site = k.site; a.rng = k.rng; a.add = k.add; a.train = k.train;
+    const int pre = k.d_qkv ? 2 : k.nslab > 1 ? 1 : 0;
+    auto launch = [&](auto pre_c, auto post) {
+        hipLaunchKernelGGL((rc_bwd_kernel<decltype(pre_c)::value, decltype(post)::value>), dim3(rc_blocks(k.T)), dim3(256), 0, k.st, a);
+        GF_LAUNCH_CHECK();
+        return 0;
+    };
+    return with_flag(k.wo_t != nullptr, [&](auto post) {
+        switch (pre) {
+            case 2: return launch(std::integral_constant<int, 2>{}, post);
+            case 1: return launch(std::integral_constant<int, 1>{}, post);
+            default: return launch(std::integral_constant<int, 0>{}, post);
+        }
+    });
 }
 
 }  // namespace ganffn
