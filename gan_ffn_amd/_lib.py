@@ -129,6 +129,14 @@ SIGNATURES = {
     "ganffn_lstm_packed_layer_bwd": (_I, [C.POINTER(LstmCfg)] + [_P] * 14),
     "ganffn_lstm_stack_packed_fwd": (_I, [C.POINTER(LstmStackCfg)] + [_P] * 10 + [_U64, _P]),
     "ganffn_lstm_stack_packed_bwd": (_I, [C.POINTER(LstmStackCfg)] + [_P] * 14 + [_U64, _P]),
+    "ganffn_unilstm_saved_floats": (_L, [C.POINTER(LstmCfg)]),
+    "ganffn_unilstm_workspace_floats": (_L, [C.POINTER(LstmCfg)]),
+    "ganffn_unilstm_layer_fwd": (_I, [C.POINTER(LstmCfg)] + [_P] * 10),
+    "ganffn_unilstm_layer_bwd": (_I, [C.POINTER(LstmCfg)] + [_P] * 14),
+    "ganffn_unilstm_stack_saved_floats": (_L, [C.POINTER(LstmStackCfg)]),
+    "ganffn_unilstm_stack_workspace_floats": (_L, [C.POINTER(LstmStackCfg)]),
+    "ganffn_unilstm_stack_fwd": (_I, [C.POINTER(LstmStackCfg)] + [_P] * 10 + [_U64, _P]),
+    "ganffn_unilstm_stack_bwd": (_I, [C.POINTER(LstmStackCfg)] + [_P] * 14 + [_U64, _P]),
     "ganffn_meld_head_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ganffn_meld_head_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ganffn_zero_floats": (_I, [_P, _L, _P]),

@@ -274,17 +274,22 @@ def run_training(dataset_path, g_epochs=150, n_epochs=160, lr=1e-4, l2=0.008, ba
 
 
 def run_meld_training(pickle_path, n_epochs=50, lr=3e-4, l2=1e-4, dropout=0.6, batch_size=32, classify="emotion", device="cuda",
-                      seed=None, log=print, device_corpus=False, packed=False):
+                      seed=None, log=print, device_corpus=False, packed=False, causal=False):
     """The __main__ flow of train_MELD.py:143-195 on the HIP path: MELDLSTMModel(600, 300, 600) through engine.MeldEngine,
     MaskedNLLLoss without class weights, Adam(lr, weight_decay = l2), loaders with valid = 0.0, the per-epoch line, and the
     test epoch with the best F-score kept.  Returns (best_loss, best_fscore, labels, preds, masks, attentions).
     device_corpus: as in run_training.  packed (an extension the reference does not have): the LSTM on packed sequences, in the
-    model and in the engine alike (MELDLSTMModel / MeldEngine `packed`)."""
+    model and in the engine alike (MELDLSTMModel / MeldEngine `packed`).  causal (an extension the reference does not have): the
+    classifier that never looks ahead, MELDLSTMModel(600, 300, 300, causal=True) — forward-only LSTM, causal general2 attention —
+    and the engine built from it."""
     from . import data as D, engine as E, dialogue_rnn as DR
     if seed is not None:
         torch.manual_seed(seed)
     n_classes = 7 if classify == "emotion" else 3                                 # train_MELD.py:138-141
-    model = DR.MELDLSTMModel(600, 300, 600, n_classes=n_classes, dropout=dropout, packed=packed).to(device)
+    if causal:
+        model = DR.MELDLSTMModel(600, 300, 300, n_classes=n_classes, dropout=dropout, packed=packed, causal=True).to(device)
+    else:
+        model = DR.MELDLSTMModel(600, 300, 600, n_classes=n_classes, dropout=dropout, packed=packed).to(device)
     eng = E.MeldEngine(model, lr=lr, weight_decay=l2, max_dialogues=max(32, batch_size), packed=packed)      # train_MELD.py:114 --batch-size
     if device_corpus:
         train_loader, valid_loader, test_loader = D.get_device_loaders(D.MELDDataset(pickle_path, classify, True),

@@ -33,6 +33,14 @@
 // there.  That is pack_padded_sequence -> nn.LSTM -> pad_packed_sequence(total_length = S): the reverse direction enters step
 // len - 1 with zero state (out[tm + 1] and c[tm + 1] are zero), the outputs past the end are zero, and the deferred GEMMs see
 // zero dG rows at padded tokens, so nothing else changes — the same launches as the unpacked step, no host read of lengths.
+//
+// ONE direction (ganffn_unilstm_* at the end of the file; an extension: the reference's LSTM is bidirectional): the direction
+// count ndir, 2 or 1, is a property of the call (LstmCall::ndir).  The layouts take it — every region [ndir][...], h_at's leading
+// dimension ndir H, layer l > 0's input ndir H wide, the stack's blocks [T x ndir H]; with ndir = 2 every offset and size is what
+// it was —, the gate kernels read the leading dimension of h from their arguments (LstmGateArgs::ldh) and run grid.y = ndir,
+// the skinny launches carry ndir problems, and the hoisted, deferred and dx GEMMs loop d < ndir (one direction: dx is the single
+// NN product, no residual pass).  nn.LSTM(bidirectional=False): out[t] is a function of x[0 .. t]; a step stays 2 + 2 launches,
+// and with the same weights out is bit for bit the forward half of the two-direction layer's (the same products, the same K split).
 #include "common.h"
 
 namespace ganffn {
@@ -45,11 +53,11 @@ struct LstmGateDir {
     const float* G;        // [B x 4H] pre-activations of this step (everything added: xg, recurrent product, both biases)
     const float* c_prev;   // [B x H] (null at the first step: zeros)
     float* c;              // [B x H]
-    float* h_out;          // h_t into out[t][:, d H .. (d + 1) H): leading dimension 2H
+    float* h_out;          // h_t into out[t][:, d H .. (d + 1) H): leading dimension ldh = ndir H
     float* gates;          // [B x 4H] activated i | f | g | o, kept for the backward
     int tm;                // this step's time index (read by the packed form only)
 };
-struct LstmGateArgs { LstmGateDir d[2]; int B, H; const int* lengths; };
+struct LstmGateArgs { LstmGateDir d[2]; int B, H, ldh; const int* lengths; };      // d[0 .. ndir): the launch's grid.y
 
 // PACKED: dialogue b at a time index tm >= lengths[b] gets c = h = gates = 0 by a select (the row's products are discarded)
 template <bool PACKED>
@@ -67,17 +75,17 @@ __global__ __launch_bounds__(256) void lstm_gate_fwd_kernel(LstmGateArgs a) {
     if (PACKED) {
         const bool valid = q.tm < a.lengths[b];
         q.c[(size_t)b * H + j] = valid ? c : 0.f;
-        q.h_out[(size_t)b * 2 * H + j] = valid ? h : 0.f;
+        q.h_out[(size_t)b * a.ldh + j] = valid ? h : 0.f;
         S[j] = valid ? i : 0.f; S[H + j] = valid ? f : 0.f; S[2 * H + j] = valid ? g : 0.f; S[3 * H + j] = valid ? o : 0.f;
     } else {
         q.c[(size_t)b * H + j] = c;
-        q.h_out[(size_t)b * 2 * H + j] = h;
+        q.h_out[(size_t)b * a.ldh + j] = h;
         S[j] = i; S[H + j] = f; S[2 * H + j] = g; S[3 * H + j] = o;
     }
 }
 
 struct LstmGateBwdDir {
-    const float* dh; int ld_dh;   // gradient wrt h_t: d_out[t]'s half (ld 2H) at the first backward step, else the product's output (ld H)
+    const float* dh; int ld_dh;   // gradient wrt h_t: d_out[t]'s part (ld ndir H) at the first backward step, else the product's output (ld H)
     float* dc;                    // [B x H] in: dL/dc_t from the later step (zeros at the first backward step: dc_zero), out: dL/dc_{t-1}
     int dc_zero;
     const float* gates;           // activated i | f | g | o of this step
@@ -85,7 +93,7 @@ struct LstmGateBwdDir {
     float* dG;                    // [B x 4H] gradient wrt the pre-activations of this step
     int tm;                       // this step's time index (read by the packed form only)
 };
-struct LstmGateBwdArgs { LstmGateBwdDir d[2]; int B, H; const int* lengths; };
+struct LstmGateBwdArgs { LstmGateBwdDir d[2]; int B, H, ldh; const int* lengths; };   // (ldh: unread — dh carries its own ld_dh)
 
 // PACKED: dialogue b at a time index tm >= lengths[b] gets dG = 0 and hands dc = 0 to the earlier step, by a select and not a
 // product with 0: whatever d_out / dh hold at a padded position (NaN included) cannot spread
@@ -138,12 +146,13 @@ __global__ __launch_bounds__(256) void lstm_colsum2_kernel(const float* __restri
 // it.  Both are kept only so that no reported size changes.
 constexpr int64_t PART_SLACK = 64, TAIL_SLACK = 64;
 
-// One layer.  [2]: the forward direction's block, then the reverse direction's; T = S B tokens, a time index tm owns B rows.
+// One layer of ndir directions (2: nn.LSTM(bidirectional=True), 1: forward only — ganffn_unilstm_*).  [ndir]: the forward
+// direction's block, then (ndir == 2) the reverse direction's; T = S B tokens, a time index tm owns B rows.
 struct LstmLayout {
-    int64_t T, B, H;
-    int64_t gates, c, saved_total;                   // saved: gates [2][T x 4H] (activated i | f | g | o) | c [2][T x H]
-    int64_t xg, G;                                   // workspace, forward: xg [2][T x 4H] | G [2][B x 4H] (this step's pre-activations)
-    int64_t dG, dh, dc, part, part_floats;           // workspace, backward: dG [2][T x 4H] | dh [2][B x H] | dc [2][B x H] | TN partial slabs
+    int64_t T, B, H, ndir;
+    int64_t gates, c, saved_total;                   // saved: gates [ndir][T x 4H] (activated i | f | g | o) | c [ndir][T x H]
+    int64_t xg, G;                                   // workspace, forward: xg [ndir][T x 4H] | G [ndir][B x 4H] (this step's pre-activations)
+    int64_t dG, dh, dc, part, part_floats;           // workspace, backward: dG [ndir][T x 4H] | dh [ndir][B x H] | dc [ndir][B x H] | TN partial slabs
     int64_t ws_total;                                // the larger pass + the slack
     // direction d's rows of time index tm in the per-token regions, direction d's block of the per-step ones
     int64_t gates_at(int d, int64_t tm) const { return gates + (d * T + tm * B) * 4 * H; }
@@ -153,21 +162,22 @@ struct LstmLayout {
     int64_t G_of(int d) const { return G + d * B * 4 * H; }
     int64_t dh_of(int d) const { return dh + d * B * H; }
     int64_t dc_of(int d) const { return dc + d * B * H; }
-    // ... and in out / d_out [T x 2H]: direction d's half of time index tm's rows (leading dimension 2H)
-    int64_t h_at(int d, int64_t tm) const { return (tm * B * 2 + d) * H; }
+    // ... and in out / d_out [T x ndir H]: direction d's part of time index tm's rows (leading dimension ldh)
+    int64_t ldh() const { return ndir * H; }
+    int64_t h_at(int d, int64_t tm) const { return (tm * B * ndir + d) * H; }
 };
-LstmLayout lstm_layout(const ganffn_lstm_cfg* c) {
+LstmLayout lstm_layout(const ganffn_lstm_cfg* c, int ndir) {
     LstmLayout L;
-    const int64_t T = L.T = (int64_t)c->S * c->B, B = L.B = c->B, H = L.H = c->H;
+    const int64_t T = L.T = (int64_t)c->S * c->B, B = L.B = c->B, H = L.H = c->H, D = L.ndir = ndir;
     int64_t p = 0;
     auto take = [&](int64_t n) { int64_t r = p; p += n; return r; };
-    L.gates = take(2 * T * 4 * H); L.c = take(2 * T * H);
+    L.gates = take(D * T * 4 * H); L.c = take(D * T * H);
     L.saved_total = p;
     p = 0;
-    L.xg = take(2 * T * 4 * H); L.G = take(2 * B * 4 * H);
+    L.xg = take(D * T * 4 * H); L.G = take(D * B * 4 * H);
     const int64_t fwd = p;
     p = 0;
-    L.dG = take(2 * T * 4 * H); L.dh = take(2 * B * H); L.dc = take(2 * B * H);
+    L.dG = take(D * T * 4 * H); L.dh = take(D * B * H); L.dc = take(D * B * H);
     // the slabs start 16-byte aligned (gemm.hip's launcher refuses them otherwise): H % 4 == 0 (check_lstm) makes every region
     // above a multiple of 4 floats and the drivers refuse a workspace that is not 16-byte aligned, so this rounds nothing
     p = (p + 3) & ~(int64_t)3;
@@ -183,28 +193,28 @@ LstmLayout lstm_layout(const ganffn_lstm_cfg* c) {
 // ---- the whole stack (ganffn_lstm_stack_*): L layers chained, nn.LSTM's inter-layer dropout between them
 constexpr uint32_t SITE_LSTM0 = 64;                      // + layer (ops.SITE_LSTM): the dropout behind every layer but the last
 
-inline ganffn_lstm_cfg stack_layer_cfg(const ganffn_lstm_stack_cfg* c, int l) {
-    return ganffn_lstm_cfg{c->S, c->B, l == 0 ? c->In : 2 * c->H, c->H};
+inline ganffn_lstm_cfg stack_layer_cfg(const ganffn_lstm_stack_cfg* c, int l, int ndir) {
+    return ganffn_lstm_cfg{c->S, c->B, l == 0 ? c->In : ndir * c->H, c->H};
 }
 struct LstmStackLayout {
-    int64_t TD;                                      // floats of one [T x 2H] block
-    // saved: per layer the layer's own saved block (10 T H floats whatever its input width), then per layer but the last its
-    // output [T x 2H] and the dropped output [T x 2H] the next layer reads (unused when no dropout is active)
+    int64_t TD;                                      // floats of one [T x ndir H] block
+    // saved: per layer the layer's own saved block (5 ndir T H floats whatever its input width), then per layer but the last its
+    // output [T x ndir H] and the dropped output [T x ndir H] the next layer reads (unused when no dropout is active)
     int64_t layer_stride, between, saved_total;
-    // workspace: the widest layer's own workspace (rounded to 16 bytes) | two [T x 2H] gradient buffers: layer l's input gradient
+    // workspace: the widest layer's own workspace (rounded to 16 bytes) | two [T x ndir H] gradient buffers: layer l's input gradient
     // goes to buffer l & 1, where layer l - 1 reads it as its d_out
     int64_t layer_ws, dbuf, ws_total;
     int64_t out(int l) const { return between + l * 2 * TD; }
     int64_t dropped(int l) const { return out(l) + TD; }
     int64_t d_in(int l) const { return dbuf + (l & 1) * TD; }
 };
-LstmStackLayout lstm_stack_layout(const ganffn_lstm_stack_cfg* c) {
+LstmStackLayout lstm_stack_layout(const ganffn_lstm_stack_cfg* c, int ndir) {
     LstmStackLayout L;
-    L.TD = (int64_t)c->S * c->B * 2 * c->H;
+    L.TD = (int64_t)c->S * c->B * ndir * c->H;
     L.layer_ws = 0;
     for (int l = 0; l < c->L; ++l) {
-        const ganffn_lstm_cfg lc = stack_layer_cfg(c, l);
-        const LstmLayout ll = lstm_layout(&lc);
+        const ganffn_lstm_cfg lc = stack_layer_cfg(c, l, ndir);
+        const LstmLayout ll = lstm_layout(&lc, ndir);
         L.layer_stride = ll.saved_total;                // (the same for every layer: no term of it holds In)
         L.layer_ws = ll.ws_total > L.layer_ws ? ll.ws_total : L.layer_ws;
     }
@@ -228,14 +238,15 @@ int check_lstm_stack(const ganffn_lstm_stack_cfg* c, int maxB) {
     GF_CHECK_ARG(c, "null lstm stack cfg");
     GF_CHECK_ARG(c->L >= 1 && c->L <= 16, "lstm stack: L=%d (1 .. 16 layers)", c->L);
     GF_CHECK_ARG(c->p >= 0.f && c->p < 1.f, "lstm stack: dropout p=%g must be in [0, 1)", (double)c->p);
-    const ganffn_lstm_cfg l0 = stack_layer_cfg(c, 0);
+    const ganffn_lstm_cfg l0 = stack_layer_cfg(c, 0, 2);     // (layer 0's cfg holds no direction count)
     return check_lstm(&l0, maxB);
 }
 
-// What a forward or a backward call needs; the entry-point families differ only in maxB and lengths.  The weight and gradient
-// arrays have one entry per direction ([L][2] in a stack call); a member its pass does not take stays null.
+// What a forward or a backward call needs; the entry-point families differ only in ndir, maxB and lengths.  The weight and
+// gradient arrays have one entry per direction ([L][ndir] in a stack call); a member its pass does not take stays null.
 struct LstmCall {
     const ganffn_lstm_cfg* c;                  // (a stack call: null here, the stack's beside it in LstmStackCall)
+    int ndir;                                  // directions: 2 (forward | reverse) or 1 (forward only)
     int maxB; const int* lengths;              // dialogue limit; real steps per dialogue (int32 [B] on the device) or null: all S
     hipStream_t st;
     const float* x; float* out; float* saved; float* workspace;                  // (the backward only reads out and saved)
@@ -254,25 +265,25 @@ struct LstmCall {
         return *this;
     }
 };
-inline LstmCall lstm_call(const ganffn_lstm_cfg* c, int maxB, const int* lengths, void* stream) {
+inline LstmCall lstm_call(const ganffn_lstm_cfg* c, int maxB, const int* lengths, void* stream, int ndir = 2) {
     LstmCall k{};
-    k.c = c; k.maxB = maxB; k.lengths = lengths; k.st = (hipStream_t)stream;
+    k.c = c; k.ndir = ndir; k.maxB = maxB; k.lengths = lengths; k.st = (hipStream_t)stream;
     return k;
 }
 struct LstmStackCall {
     const ganffn_lstm_stack_cfg* c; const uint64_t* rng; uint64_t add;     // add = rng_offset_add: layer l's dropout draws offset add + l
     LstmCall k;
     bool drop() const { return c->train && c->p > 0.f && c->L > 1; }
-    // layer l's call: its cfg, its entries of the [L][2] arrays, its saved block; the driver sets x / out / d_out / dx
+    // layer l's call: its cfg, its entries of the [L][ndir] arrays, its saved block; the driver sets x / out / d_out / dx
     LstmCall layer(const ganffn_lstm_cfg* lc, int l, const LstmStackLayout& L) const {
         LstmCall q = k;
         q.c = lc; q.saved = k.saved + l * L.layer_stride;
-        q.w_ih = k.w_ih + 2 * l; q.w_hh = k.w_hh + 2 * l;
-        if (k.b_ih) { q.b_ih = k.b_ih + 2 * l; q.b_hh = k.b_hh + 2 * l; }
-        if (k.gw_ih) q.gw_ih = k.gw_ih + 2 * l;
-        if (k.gw_hh) q.gw_hh = k.gw_hh + 2 * l;
-        if (k.gb_ih) q.gb_ih = k.gb_ih + 2 * l;
-        if (k.gb_hh) q.gb_hh = k.gb_hh + 2 * l;
+        q.w_ih = k.w_ih + k.ndir * l; q.w_hh = k.w_hh + k.ndir * l;
+        if (k.b_ih) { q.b_ih = k.b_ih + k.ndir * l; q.b_hh = k.b_hh + k.ndir * l; }
+        if (k.gw_ih) q.gw_ih = k.gw_ih + k.ndir * l;
+        if (k.gw_hh) q.gw_hh = k.gw_hh + k.ndir * l;
+        if (k.gb_ih) q.gb_ih = k.gb_ih + k.ndir * l;
+        if (k.gb_hh) q.gb_hh = k.gb_hh + k.ndir * l;
         return q;
     }
 };
@@ -281,6 +292,7 @@ struct LstmStackCall {
 // rng; the layer drivers it then runs check each layer's buffers and weights themselves, as every layer call does.
 int check_pass(const LstmCall& k, bool bwd, const LstmStackCall* s) {
     const char* of = s ? "stack" : "layer";
+    GF_CHECK_ARG(k.ndir == 1 || k.ndir == 2, "lstm: %d directions", k.ndir);
     const char* pass = bwd ? "bwd" : "fwd";
     GF_TRY(s ? check_lstm_stack(s->c, k.maxB) : check_lstm(k.c, k.maxB));
     GF_CHECK_ARG(k.x && k.out && k.saved && k.workspace && k.w_ih && k.w_hh && (bwd ? k.d_out != nullptr : k.b_ih && k.b_hh),
@@ -292,17 +304,17 @@ int check_pass(const LstmCall& k, bool bwd, const LstmStackCall* s) {
     // (d_out and dx are null in a forward call, dx may be in a backward one: null counts as aligned)
     GF_CHECK_ARG(aligned16(k.d_out) && aligned16(k.x) && aligned16(k.out) && aligned16(k.saved) && aligned16(k.workspace) && aligned16(k.dx),
                  "lstm_layer_%s: buffers must be 16-byte aligned", pass);
-    for (int d = 0; d < 2; ++d)
+    for (int d = 0; d < k.ndir; ++d)
         GF_CHECK_ARG(k.w_ih[d] && k.w_hh[d] && (bwd || (k.b_ih[d] && k.b_hh[d])) && aligned16(k.w_ih[d]) && aligned16(k.w_hh[d]),
                      "lstm_layer_%s: direction %d: null / unaligned weights", pass, d);
     return 0;
 }
 
-// The gate launch of a step, both directions: THE choice of its kernel, for both passes — the length-aware instantiation
+// The gate launch of a step, all ndir directions on grid.y: THE choice of its kernel, for both passes — the length-aware instantiation
 // behind the _packed_ entry points (the call has lengths), the plain one behind all others.
 template <class Args> void launch_gates(void (*packed)(Args), void (*plain)(Args), const LstmCall& k, Args& a) {
-    a.B = k.c->B; a.H = k.c->H; a.lengths = k.lengths;
-    hipLaunchKernelGGL(k.lengths ? packed : plain, dim3((a.B * a.H + 255) / 256, 2), dim3(256), 0, k.st, a);
+    a.B = k.c->B; a.H = k.c->H; a.ldh = k.ndir * k.c->H; a.lengths = k.lengths;
+    hipLaunchKernelGGL(k.lengths ? packed : plain, dim3((a.B * a.H + 255) / 256, k.ndir), dim3(256), 0, k.st, a);
 }
 
 }  // namespace
@@ -312,27 +324,27 @@ using namespace ganffn;
 
 static int lstm_layer_fwd(const LstmCall& k) {
     GF_TRY(check_pass(k, false, nullptr));
-    const int S = k.c->S, B = k.c->B, In = k.c->In, H = k.c->H;
-    const LstmLayout L = lstm_layout(k.c);
-    const int T = (int)L.T;
+    const int S = k.c->S, B = k.c->B, In = k.c->In, H = k.c->H, ND = k.ndir;
+    const LstmLayout L = lstm_layout(k.c, ND);
+    const int T = (int)L.T, ldh = (int)L.ldh();
     float* out = k.out; float* saved = k.saved; float* ws = k.workspace;
-    for (int d = 0; d < 2; ++d) {
+    for (int d = 0; d < ND; ++d) {
         GF_TRY(gemm(gemm_nt(k.x, k.w_ih[d], ws + L.xg_at(d, 0), T, 4 * H, In).bias(k.b_ih[d]).on(k.st)));
     }
     for (int t = 0; t < S; ++t) {
         SkinnyGroup sg;
-        LstmGateArgs ga;
-        for (int d = 0; d < 2; ++d) {
+        LstmGateArgs ga{};
+        for (int d = 0; d < ND; ++d) {
             const int64_t tm = d == 0 ? t : S - 1 - t, tp = d == 0 ? tm - 1 : tm + 1;      // this step's / the previous step's time index
             float* c_t = saved + L.c_at(d, tm);
             float* Gd = ws + L.G_of(d);
             // first step: h_{-1} = 0 without a special kernel — the product runs on this step's own, not yet written, c slot, zeroed here
             if (t == 0) GF_HIP(hipMemsetAsync(c_t, 0, (size_t)B * H * sizeof(float), k.st));
-            sg.p[d] = SkinnyProb{t == 0 ? c_t : out + L.h_at(d, tp), t == 0 ? H : 2 * H, k.w_hh[d], H, ws + L.xg_at(d, tm), 4 * H, nullptr,
+            sg.p[d] = SkinnyProb{t == 0 ? c_t : out + L.h_at(d, tp), t == 0 ? H : ldh, k.w_hh[d], H, ws + L.xg_at(d, tm), 4 * H, nullptr,
                                  k.b_hh[d], Gd, 4 * H, B, 4 * H, H};
             ga.d[d] = LstmGateDir{Gd, t == 0 ? nullptr : saved + L.c_at(d, tp), c_t, out + L.h_at(d, tm), saved + L.gates_at(d, tm), (int)tm};
         }
-        GF_TRY(launch_skinny(sg, 2, false, k.st));
+        GF_TRY(launch_skinny(sg, ND, false, k.st));
         launch_gates(lstm_gate_fwd_kernel<true>, lstm_gate_fwd_kernel<false>, k, ga);
         GF_LAUNCH_CHECK();
     }
@@ -341,37 +353,37 @@ static int lstm_layer_fwd(const LstmCall& k) {
 
 static int lstm_layer_bwd(const LstmCall& k) {
     GF_TRY(check_pass(k, true, nullptr));
-    const int S = k.c->S, B = k.c->B, In = k.c->In, H = k.c->H;
-    const LstmLayout L = lstm_layout(k.c);
-    const int T = (int)L.T;
+    const int S = k.c->S, B = k.c->B, In = k.c->In, H = k.c->H, ND = k.ndir;
+    const LstmLayout L = lstm_layout(k.c, ND);
+    const int T = (int)L.T, ldh = (int)L.ldh();
     const float* d_out = k.d_out; const float* out = k.out; const float* saved = k.saved; float* ws = k.workspace;
     for (int t = S - 1; t >= 0; --t) {              // step index of the forward loop, walked backwards
         const bool first = t == S - 1;              // first backward step: no later step feeds dh / dc
-        LstmGateBwdArgs gb;
+        LstmGateBwdArgs gb{};
         SkinnyGroup sg;
-        for (int d = 0; d < 2; ++d) {
+        for (int d = 0; d < ND; ++d) {
             const int64_t tm = d == 0 ? t : S - 1 - t, tp = d == 0 ? tm - 1 : tm + 1;
             float* dG_t = ws + L.dG_at(d, tm);
             float* dh = ws + L.dh_of(d);
-            gb.d[d] = LstmGateBwdDir{first ? d_out + L.h_at(d, tm) : dh, first ? 2 * H : H, ws + L.dc_of(d), first ? 1 : 0,
+            gb.d[d] = LstmGateBwdDir{first ? d_out + L.h_at(d, tm) : dh, first ? ldh : H, ws + L.dc_of(d), first ? 1 : 0,
                                      saved + L.gates_at(d, tm), saved + L.c_at(d, tm), t == 0 ? nullptr : saved + L.c_at(d, tp), dG_t, (int)tm};
-            // dh_{t-1} = d_out[t-1]'s half + dG_t W_hh   ([B x 4H] x [4H x H], the weight row-wise as stored)
-            if (t > 0) sg.p[d] = SkinnyProb{dG_t, 4 * H, k.w_hh[d], H, d_out + L.h_at(d, tp), 2 * H, nullptr, nullptr, dh, H, B, H, 4 * H};
+            // dh_{t-1} = d_out[t-1]'s part + dG_t W_hh   ([B x 4H] x [4H x H], the weight row-wise as stored)
+            if (t > 0) sg.p[d] = SkinnyProb{dG_t, 4 * H, k.w_hh[d], H, d_out + L.h_at(d, tp), ldh, nullptr, nullptr, dh, H, B, H, 4 * H};
         }
         launch_gates(lstm_gate_bwd_kernel<true>, lstm_gate_bwd_kernel<false>, k, gb);
         GF_LAUNCH_CHECK();
-        if (t > 0) GF_TRY(launch_skinny(sg, 2, true, k.st));
+        if (t > 0) GF_TRY(launch_skinny(sg, ND, true, k.st));
     }
     // deferred weight gradients over all tokens (accumulated: the caller zeroes), bias gradients, input gradient
     float* part = ws + L.part;
-    for (int d = 0; d < 2; ++d) {
+    for (int d = 0; d < ND; ++d) {
         const float* dGd = ws + L.dG_at(d, 0);
         if (k.gw_ih && k.gw_ih[d]) GF_TRY(gemm(gemm_tn(dGd, k.x, k.gw_ih[d], 4 * H, In, T).tn_workspace(part, L.part_floats).on(k.st)));
         if (k.gw_hh && k.gw_hh[d] && S > 1) {
             // h_prev of time tm: forward direction out[tm - 1], reverse direction out[tm + 1] (zero at the direction's first step):
             // the forward direction pairs dG of times 1 .. S-1 with out of 0 .. S-2, the reverse one dG of 0 .. S-2 with out of 1 .. S-1
             const int from = d == 0 ? 1 : 0;
-            GF_TRY(gemm(gemm_tn(ws + L.dG_at(d, from), out + L.h_at(d, 1 - from), k.gw_hh[d], 4 * H, H, T - B).ld(4 * H, 2 * H, H)
+            GF_TRY(gemm(gemm_tn(ws + L.dG_at(d, from), out + L.h_at(d, 1 - from), k.gw_hh[d], 4 * H, H, T - B).ld(4 * H, ldh, H)
                             .tn_workspace(part, L.part_floats).on(k.st)));
         }
         float* b1 = k.gb_ih ? k.gb_ih[d] : nullptr;
@@ -383,8 +395,8 @@ static int lstm_layer_bwd(const LstmCall& k) {
     }
     if (k.dx) {
         GF_TRY(gemm(gemm_nn(ws + L.dG_at(0, 0), k.w_ih[0], k.dx, T, In, 4 * H).on(k.st)));
-        // + the reverse direction's share (each element read and written by one thread)
-        GF_TRY(gemm(gemm_nn(ws + L.dG_at(1, 0), k.w_ih[1], k.dx, T, In, 4 * H).residual(k.dx).on(k.st)));
+        // + the reverse direction's share (each element read and written by one thread); one direction: no residual pass
+        if (ND == 2) GF_TRY(gemm(gemm_nn(ws + L.dG_at(1, 0), k.w_ih[1], k.dx, T, In, 4 * H).residual(k.dx).on(k.st)));
     }
     return 0;
 }
@@ -394,11 +406,12 @@ static int lstm_layer_bwd(const LstmCall& k) {
 static int lstm_stack_fwd(const LstmStackCall& s) {
     GF_TRY(check_pass(s.k, false, &s));
     const ganffn_lstm_stack_cfg* c = s.c;
-    const LstmStackLayout L = lstm_stack_layout(c);
+    const int ND = s.k.ndir;
+    const LstmStackLayout L = lstm_stack_layout(c, ND);
     const int T = c->S * c->B;
     const float* in = s.k.x;
     for (int l = 0; l < c->L; ++l) {
-        const ganffn_lstm_cfg lc = stack_layer_cfg(c, l);
+        const ganffn_lstm_cfg lc = stack_layer_cfg(c, l, ND);
         const bool last = l + 1 == c->L;
         LstmCall q = s.layer(&lc, l, L);
         q.x = in; q.out = last ? s.k.out : s.k.saved + L.out(l);
@@ -406,7 +419,7 @@ static int lstm_stack_fwd(const LstmStackCall& s) {
         in = q.out;
         if (!last && s.drop()) {
             float* dr = s.k.saved + L.dropped(l);
-            GF_TRY(launch_dropout(q.out, dr, T, 2 * c->H, c->p, SITE_LSTM0 + l, s.rng, s.add + l, 1, s.k.st));
+            GF_TRY(launch_dropout(q.out, dr, T, ND * c->H, c->p, SITE_LSTM0 + l, s.rng, s.add + l, 1, s.k.st));
             in = dr;
         }
     }
@@ -417,11 +430,12 @@ static int lstm_stack_fwd(const LstmStackCall& s) {
 static int lstm_stack_bwd(const LstmStackCall& s) {
     GF_TRY(check_pass(s.k, true, &s));
     const ganffn_lstm_stack_cfg* c = s.c;
-    const LstmStackLayout L = lstm_stack_layout(c);
+    const int ND = s.k.ndir;
+    const LstmStackLayout L = lstm_stack_layout(c, ND);
     const int T = c->S * c->B;
     const float* d = s.k.d_out;
     for (int l = c->L - 1; l >= 0; --l) {
-        const ganffn_lstm_cfg lc = stack_layer_cfg(c, l);
+        const ganffn_lstm_cfg lc = stack_layer_cfg(c, l, ND);
         LstmCall q = s.layer(&lc, l, L);
         q.d_out = d;
         q.x = l == 0 ? s.k.x : s.k.saved + (s.drop() ? L.dropped(l - 1) : L.out(l - 1));
@@ -429,7 +443,7 @@ static int lstm_stack_bwd(const LstmStackCall& s) {
         q.dx = l == 0 ? s.k.dx : s.k.workspace + L.d_in(l);
         GF_TRY(lstm_layer_bwd(q));
         if (l > 0 && s.drop())
-            GF_TRY(launch_dropout(q.dx, q.dx, T, 2 * c->H, c->p, SITE_LSTM0 + (l - 1), s.rng, s.add + (l - 1), 1, s.k.st));
+            GF_TRY(launch_dropout(q.dx, q.dx, T, ND * c->H, c->p, SITE_LSTM0 + (l - 1), s.rng, s.add + (l - 1), 1, s.k.st));
         d = q.dx;
     }
     return 0;
@@ -438,8 +452,8 @@ static int lstm_stack_bwd(const LstmStackCall& s) {
 // ---- the entry points: each states its family — the dialogue limit and whether it takes lengths — fills one call and runs a driver
 constexpr int PLAIN_MAX_DIALOGUES = 32;       // ganffn_lstm_* / ganffn_lstm_stack_*: the limit they always had (they keep refusing 33)
 
-extern "C" int64_t ganffn_lstm_saved_floats(const ganffn_lstm_cfg* c) { return check_lstm(c, PLAIN_MAX_DIALOGUES) ? -1 : lstm_layout(c).saved_total; }
-extern "C" int64_t ganffn_lstm_workspace_floats(const ganffn_lstm_cfg* c) { return check_lstm(c, PLAIN_MAX_DIALOGUES) ? -1 : lstm_layout(c).ws_total; }
+extern "C" int64_t ganffn_lstm_saved_floats(const ganffn_lstm_cfg* c) { return check_lstm(c, PLAIN_MAX_DIALOGUES) ? -1 : lstm_layout(c, 2).saved_total; }
+extern "C" int64_t ganffn_lstm_workspace_floats(const ganffn_lstm_cfg* c) { return check_lstm(c, PLAIN_MAX_DIALOGUES) ? -1 : lstm_layout(c, 2).ws_total; }
 extern "C" int ganffn_lstm_layer_fwd(const ganffn_lstm_cfg* c, const float* x, const float* const* w_ih, const float* const* w_hh,
                                      const float* const* b_ih, const float* const* b_hh, float* out, float* saved, float* workspace,
                                      void* stream) {
@@ -456,10 +470,10 @@ extern "C" int ganffn_lstm_layer_bwd(const ganffn_lstm_cfg* c, const float* d_ou
 // L layers in one call.  gw_* / gb_*: arrays of [L][2] pointers, ACCUMULATED into like the per-layer backward (NULL arrays or
 // entries: not wanted); dx [S x B x In] may be NULL.
 extern "C" int64_t ganffn_lstm_stack_saved_floats(const ganffn_lstm_stack_cfg* c) {
-    return check_lstm_stack(c, PLAIN_MAX_DIALOGUES) ? -1 : lstm_stack_layout(c).saved_total;
+    return check_lstm_stack(c, PLAIN_MAX_DIALOGUES) ? -1 : lstm_stack_layout(c, 2).saved_total;
 }
 extern "C" int64_t ganffn_lstm_stack_workspace_floats(const ganffn_lstm_stack_cfg* c) {
-    return check_lstm_stack(c, PLAIN_MAX_DIALOGUES) ? -1 : lstm_stack_layout(c).ws_total;
+    return check_lstm_stack(c, PLAIN_MAX_DIALOGUES) ? -1 : lstm_stack_layout(c, 2).ws_total;
 }
 extern "C" int ganffn_lstm_stack_fwd(const ganffn_lstm_stack_cfg* c, const float* x, const float* const* w_ih, const float* const* w_hh,
                                      const float* const* b_ih, const float* const* b_hh, float* out, float* saved, float* workspace,
@@ -478,8 +492,8 @@ extern "C" int ganffn_lstm_stack_bwd(const ganffn_lstm_stack_cfg* c, const float
 // ---- 1 <= B <= GANFFN_MAX_DIALOGUES dialogues per call ---------------------------------------------------------------------
 // The same drivers with the skinny products' dialogue-tile axis (dialogue_rnn.hip): the same layouts and sizes as functions of
 // B, the same launches per step; B <= 32 is the launch sequence of the entry points above, bit for bit.
-extern "C" int64_t ganffn_lstm_batch_saved_floats(const ganffn_lstm_cfg* c) { return check_lstm(c, GANFFN_MAX_DIALOGUES) ? -1 : lstm_layout(c).saved_total; }
-extern "C" int64_t ganffn_lstm_batch_workspace_floats(const ganffn_lstm_cfg* c) { return check_lstm(c, GANFFN_MAX_DIALOGUES) ? -1 : lstm_layout(c).ws_total; }
+extern "C" int64_t ganffn_lstm_batch_saved_floats(const ganffn_lstm_cfg* c) { return check_lstm(c, GANFFN_MAX_DIALOGUES) ? -1 : lstm_layout(c, 2).saved_total; }
+extern "C" int64_t ganffn_lstm_batch_workspace_floats(const ganffn_lstm_cfg* c) { return check_lstm(c, GANFFN_MAX_DIALOGUES) ? -1 : lstm_layout(c, 2).ws_total; }
 extern "C" int ganffn_lstm_batch_layer_fwd(const ganffn_lstm_cfg* c, const float* x, const float* const* w_ih, const float* const* w_hh,
                                            const float* const* b_ih, const float* const* b_hh, float* out, float* saved,
                                            float* workspace, void* stream) {
@@ -493,10 +507,10 @@ extern "C" int ganffn_lstm_batch_layer_bwd(const ganffn_lstm_cfg* c, const float
                               .backward(d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, workspace));
 }
 extern "C" int64_t ganffn_lstm_stack_batch_saved_floats(const ganffn_lstm_stack_cfg* c) {
-    return check_lstm_stack(c, GANFFN_MAX_DIALOGUES) ? -1 : lstm_stack_layout(c).saved_total;
+    return check_lstm_stack(c, GANFFN_MAX_DIALOGUES) ? -1 : lstm_stack_layout(c, 2).saved_total;
 }
 extern "C" int64_t ganffn_lstm_stack_batch_workspace_floats(const ganffn_lstm_stack_cfg* c) {
-    return check_lstm_stack(c, GANFFN_MAX_DIALOGUES) ? -1 : lstm_stack_layout(c).ws_total;
+    return check_lstm_stack(c, GANFFN_MAX_DIALOGUES) ? -1 : lstm_stack_layout(c, 2).ws_total;
 }
 extern "C" int ganffn_lstm_stack_batch_fwd(const ganffn_lstm_stack_cfg* c, const float* x, const float* const* w_ih,
                                            const float* const* w_hh, const float* const* b_ih, const float* const* b_hh, float* out,
@@ -548,3 +562,44 @@ extern "C" int ganffn_lstm_stack_packed_bwd(const ganffn_lstm_stack_cfg* c, cons
                                                        .backward(d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, workspace)});
 }
 
+// ---- one direction: nn.LSTM(bidirectional=False) ----------------------------------------------------------------------------
+// The same drivers with ndir = 1 (an extension: the reference's LSTM is bidirectional): every region [1][...], out / d_out
+// [S x B x H], layer l > 0's input H wide, weight and gradient arrays [L][1]; one problem per skinny launch, one hoisted input
+// product, one dx product — still 2 launches per step, forward and backward.  ONE family for the padded and the packed run:
+// lengths (int32 [B] on the device) may be NULL = every dialogue runs all S steps; 1 <= B <= GANFFN_MAX_DIALOGUES.
+constexpr int UNI = 1;
+
+extern "C" int64_t ganffn_unilstm_saved_floats(const ganffn_lstm_cfg* c) { return check_lstm(c, GANFFN_MAX_DIALOGUES) ? -1 : lstm_layout(c, UNI).saved_total; }
+extern "C" int64_t ganffn_unilstm_workspace_floats(const ganffn_lstm_cfg* c) { return check_lstm(c, GANFFN_MAX_DIALOGUES) ? -1 : lstm_layout(c, UNI).ws_total; }
+extern "C" int ganffn_unilstm_layer_fwd(const ganffn_lstm_cfg* c, const int32_t* lengths, const float* x, const float* const* w_ih,
+                                        const float* const* w_hh, const float* const* b_ih, const float* const* b_hh, float* out,
+                                        float* saved, float* workspace, void* stream) {
+    return lstm_layer_fwd(lstm_call(c, GANFFN_MAX_DIALOGUES, lengths, stream, UNI).forward(x, w_ih, w_hh, b_ih, b_hh, out, saved, workspace));
+}
+extern "C" int ganffn_unilstm_layer_bwd(const ganffn_lstm_cfg* c, const int32_t* lengths, const float* d_out, const float* x,
+                                        const float* out, const float* const* w_ih, const float* const* w_hh, float* dx,
+                                        float* const* gw_ih, float* const* gw_hh, float* const* gb_ih, float* const* gb_hh,
+                                        const float* saved, float* workspace, void* stream) {
+    return lstm_layer_bwd(lstm_call(c, GANFFN_MAX_DIALOGUES, lengths, stream, UNI)
+                              .backward(d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, workspace));
+}
+extern "C" int64_t ganffn_unilstm_stack_saved_floats(const ganffn_lstm_stack_cfg* c) {
+    return check_lstm_stack(c, GANFFN_MAX_DIALOGUES) ? -1 : lstm_stack_layout(c, UNI).saved_total;
+}
+extern "C" int64_t ganffn_unilstm_stack_workspace_floats(const ganffn_lstm_stack_cfg* c) {
+    return check_lstm_stack(c, GANFFN_MAX_DIALOGUES) ? -1 : lstm_stack_layout(c, UNI).ws_total;
+}
+extern "C" int ganffn_unilstm_stack_fwd(const ganffn_lstm_stack_cfg* c, const int32_t* lengths, const float* x, const float* const* w_ih,
+                                        const float* const* w_hh, const float* const* b_ih, const float* const* b_hh, float* out,
+                                        float* saved, float* workspace, const uint64_t* rng, uint64_t rng_offset_add, void* stream) {
+    return lstm_stack_fwd({c, rng, rng_offset_add, lstm_call(nullptr, GANFFN_MAX_DIALOGUES, lengths, stream, UNI)
+                                                       .forward(x, w_ih, w_hh, b_ih, b_hh, out, saved, workspace)});
+}
+extern "C" int ganffn_unilstm_stack_bwd(const ganffn_lstm_stack_cfg* c, const int32_t* lengths, const float* d_out, const float* x,
+                                        const float* out, const float* const* w_ih, const float* const* w_hh, float* dx,
+                                        float* const* gw_ih, float* const* gw_hh, float* const* gb_ih, float* const* gb_hh,
+                                        const float* saved, float* workspace, const uint64_t* rng, uint64_t rng_offset_add,
+                                        void* stream) {
+    return lstm_stack_bwd({c, rng, rng_offset_add, lstm_call(nullptr, GANFFN_MAX_DIALOGUES, lengths, stream, UNI)
+                                                       .backward(d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, workspace)});
+}

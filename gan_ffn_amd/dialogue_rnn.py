@@ -349,19 +349,32 @@ class MELDLSTMModel(nn.Module):
     on packed sequences — every dialogue for its own umask.sum(1) steps, zero output past its end, the reverse direction starting
     at its last real utterance — so a dialogue's prediction no longer depends on how far its batch is padded.  `umask` must then be
     a PREFIX mask (ones for the real utterances, then zeros: what every loader of the project produces).  A plain attribute, not a
-    parameter or buffer: the state_dict is the same either way."""
+    parameter or buffer: the state_dict is the same either way.
+    causal (default False) is an extension the reference does not have: a classifier that never looks ahead.  The LSTM is
+    forward-only (nn.LSTM(bidirectional=False): no *_reverse parameters; csrc/lstm.hip with one direction, ops.UniLstmLayerFn) and
+    the general2 attention is CAUSAL (step t attends to the emotions of steps j <= t:
+    MatchingAttention.general2_all_queries(causal=True)), so log_prob[t] of a dialogue is a function of its utterances 0 .. t
+    alone.  matchatt is D_e x D_e, linear D_e -> D_h, smax_fc D_h -> n_classes; the att2=True branch feeds the D_e-wide hidden
+    to smax_fc, so it needs D_h == D_e just as the reference's needs D_h == 2 D_e.  Composes with packed.  causal=False
+    constructs and runs exactly what it always did."""
 
-    def __init__(self, D_m, D_e, D_h, n_classes=7, dropout=0.5, packed=False):
+    def __init__(self, D_m, D_e, D_h, n_classes=7, dropout=0.5, packed=False, causal=False):
         super().__init__()
         self.n_classes = n_classes
         self.packed = bool(packed)
+        self.causal = bool(causal)
+        self.D_e, self.D_h = D_e, D_h
+        D = D_e if self.causal else 2 * D_e          # width of the LSTM's output
         self.dropout = nn.Dropout(dropout)
-        self.lstm = nn.LSTM(input_size=D_m, hidden_size=D_e, num_layers=4, bidirectional=True, dropout=dropout)
-        self.matchatt = MatchingAttention(2 * D_e, 2 * D_e, att_type="general2")
-        self.linear = nn.Linear(2 * D_e, D_h)
+        self.lstm = nn.LSTM(input_size=D_m, hidden_size=D_e, num_layers=4, bidirectional=not self.causal, dropout=dropout)
+        self.matchatt = MatchingAttention(D, D, att_type="general2")
+        self.linear = nn.Linear(D, D_h)
         self.smax_fc = nn.Linear(D_h, n_classes)
 
     def forward(self, U, qmask, umask, visuf=None, att2=True):
+        if self.causal and att2 and self.D_h != self.D_e:
+            raise ValueError("MELDLSTMModel(causal=True): the att2=True branch hands the D_e-wide hidden to smax_fc, so it needs "
+                             "D_h == D_e; got D_e=%d D_h=%d" % (self.D_e, self.D_h))
         if U.is_cuda:
             # the recurrence on the HIP kernels (csrc/lstm.hip), with self.lstm's own parameters (same state_dict keys)
             from . import ops
@@ -375,7 +388,10 @@ class MELDLSTMModel(nn.Module):
             emotions, _ = self.lstm(U)      # CPU tensors: stock torch (the fixtures' CPU check; the product path is the GPU one)
         alpha, alpha_f, alpha_b = [], [], []
         if att2:
-            att, a = self.matchatt.general2_all_queries(emotions, umask)
+            if self.causal:
+                att, a = self.matchatt.general2_all_queries(emotions, umask, causal=True)
+            else:
+                att, a = self.matchatt.general2_all_queries(emotions, umask)
             alpha = [a[:, t, :] for t in range(a.size(1))]
             hidden = F.hardswish(emotions + F.hardswish(att))
         else:

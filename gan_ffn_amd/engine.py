@@ -1580,6 +1580,12 @@ class MeldEngine(_Runner):
     packed = True (default False; an extension the reference does not have, MELDLSTMModel(packed=True)'s step): the LSTM runs on
     packed sequences — lengths = umask.sum(1) as int32, derived on the device every step (umask must be a prefix mask), through
     ganffn_lstm_stack_packed_* for any B <= max_dialogues: the same launches; everything else in the step is unchanged.
+    A model built with causal=True (MELDLSTMModel(causal=True); an extension the reference does not have; read from the model,
+    and refused when it contradicts lstm.bidirectional) steps the classifier that never looks ahead: one direction (D = D_e
+    instead of 2 D_e everywhere above), the LSTM's 4 L tensors on the slab, pointer arrays [L][1], the stack through
+    ganffn_unilstm_stack_* for any B <= max_dialogues (with lengths when packed, NULL otherwise) and the attention through
+    ganffn_general2_attention_fwd_mask / _bwd_mask with GANFFN_ATTN_CAUSAL; the rest of the step is the same calls.  Its limits:
+    D_e <= 1024, D_m and D_e multiples of 4, smax_fc and matchatt D_e wide.  A default model issues the calls it always did.
     Data-parallel over dialogues like Phase2Engine: the gradient slab is all-reduced in-line on the step's stream (through
     GradReducer under GANFFN_DP_MODE=buckets), Adam divides by the world size."""
 
@@ -1588,22 +1594,33 @@ class MeldEngine(_Runner):
         self.packed = bool(packed)
         self.module = model
         lstm = model.lstm
-        if not (lstm.bidirectional and not lstm.batch_first and lstm.proj_size == 0 and lstm.bias):
+        self.causal = bool(getattr(model, "causal", False))
+        if hasattr(model, "causal") and self.causal == bool(lstm.bidirectional):
+            raise ValueError("MeldEngine: model.causal = %s contradicts lstm.bidirectional = %s (MELDLSTMModel(causal=True) builds a "
+                             "forward-only LSTM, the default a bidirectional one) — run the module path (MELDLSTMModel under "
+                             "autograd) for anything else" % (self.causal, bool(lstm.bidirectional)))
+        if not (lstm.bidirectional != self.causal and not lstm.batch_first and lstm.proj_size == 0 and lstm.bias):
             raise ValueError("MeldEngine: MELDLSTMModel's LSTM configuration only (bidirectional, sequence-first, biases, no "
                              "projection) — run the module path for anything else")
         self.Dm, self.He, self.L = int(lstm.input_size), int(lstm.hidden_size), int(lstm.num_layers)
-        self.D2 = 2 * self.He
+        self.ndir = 1 if self.causal else 2
+        self.D2 = self.ndir * self.He             # the width of the LSTM's output: 2 D_e, or D_e for the causal model
         self.n_classes = int(model.smax_fc.weight.shape[0])
         self.p_lstm = float(lstm.dropout)
         if (self.Dm % 4 or self.He % 4 or self.D2 > 1024 or self.n_classes > 16 or model.smax_fc.weight.shape[1] != self.D2
                 or model.matchatt.att_type != "general2" or tuple(model.matchatt.transform.weight.shape) != (self.D2, self.D2)):
+            if self.causal:
+                raise ValueError("MeldEngine: a causal model's D_m and D_e must be multiples of 4, D_e <= 1024 (the general2 attention "
+                                 "kernel), at most 16 classes, smax_fc and matchatt D_e wide; got D_m = %d, D_e = %d, %d classes, "
+                                 "smax_fc over %d — use the module path (MELDLSTMModel under autograd) for the rest"
+                                 % (self.Dm, self.He, self.n_classes, model.smax_fc.weight.shape[1]))
             raise ValueError("MeldEngine: D_m and D_e must be multiples of 4, 2 D_e <= 1024 (the general2 attention kernel), at most "
                              "16 classes, smax_fc and matchatt 2 D_e wide; got D_m = %d, D_e = %d, %d classes, smax_fc over %d — use "
                              "the module path (MELDLSTMModel under autograd) for the rest"
                              % (self.Dm, self.He, self.n_classes, model.smax_fc.weight.shape[1]))
         names = dict(lstm.named_parameters())
         plist = [names[k] for k in names]                     # weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0, *_l0_reverse, ...
-        assert len(plist) == 8 * self.L and list(names)[4] == "weight_ih_l0_reverse", list(names)[:8]
+        assert len(plist) == 4 * self.ndir * self.L and (self.causal or list(names)[4] == "weight_ih_l0_reverse"), list(names)[:8]
         plist += [model.matchatt.transform.weight, model.matchatt.transform.bias, model.smax_fc.weight, model.smax_fc.bias]
         self._init_common(plist[0].device, process_group, 1)
         dev = self.dev
@@ -1614,10 +1631,10 @@ class MeldEngine(_Runner):
         offs = ps.offs
         self.lr, self.wd = lr, weight_decay
         self.class_w = torch.tensor(class_weights, device=dev, dtype=torch.float32) if class_weights is not None else None
-        # the stack entry points' pointer arrays [L][2] (the slabs never move: built once)
+        # the stack entry points' pointer arrays [L][ndir] (the slabs never move: built once)
         def arrays(slab):
-            base = slab.data_ptr()
-            return [(C.c_void_p * (2 * self.L))(*[base + 4 * offs[4 * i + j] for i in range(2 * self.L)]) for j in range(4)]
+            base, n = slab.data_ptr(), self.ndir * self.L
+            return [(C.c_void_p * n)(*[base + 4 * offs[4 * i + j] for i in range(n)]) for j in range(4)]
         self._w, self._g = arrays(self.slab), arrays(self.grad)
         self.n_adds = max(1, self.L - 1)                      # one Philox offset per inter-layer dropout call
         self.loss = torch.zeros(1, device=dev)
@@ -1637,7 +1654,8 @@ class MeldEngine(_Runner):
         if fit == "grow":
             cS, cB = self._alloc_S, self._alloc_B
             lib = _lib.load()
-            n_saved, n_ws = ops.lstm_sizes(_lib.LstmStackCfg(cS, cB, self.Dm, self.He, self.L, self.p_lstm, 1), self.packed)
+            cfg = _lib.LstmStackCfg(cS, cB, self.Dm, self.He, self.L, self.p_lstm, 1)
+            n_saved, n_ws = ops.unilstm_sizes(cfg) if self.causal else ops.lstm_sizes(cfg, self.packed)
             T, D2, Cn = cS * cB, self.D2, self.n_classes
             z = lambda n: torch.empty(n, device=self.dev, dtype=torch.float32)
             self._f = dict(emotions=z(T * D2), xq=z(T * D2), att=z(T * D2), alpha=z(cB * cS * cS), tanh_s=z(cB * cS * cS),
@@ -1669,15 +1687,21 @@ class MeldEngine(_Runner):
         rng = self.rng.state
         cfg = self.cfg_train if train else self.cfg_eval
         w_ih, w_hh, b_ih, b_hh = self._w
-        n_t = 8 * self.L
+        n_t = 4 * self.ndir * self.L
         w_t, b_t, w_s, b_s = (self._p(n_t + j) for j in range(4))
         # ---- forward: LSTM stack -> transform -> general2 attention -> hardswish head -> loss       (model.py:546-560)
         # packed: lengths on the device, no host read; alive until the backward is enqueued.  The entry points: ops.lstm_family
         lengths = umask.sum(1).to(torch.int32) if self.packed else None
-        ops.lstm_stack_fwd_raw(cfg, text, w_ih, w_hh, b_ih, b_hh, f["emotions"], f["saved"], f["ws"], rng, base, lengths=lengths)
+        stack_fwd, stack_bwd = ((ops.unilstm_stack_fwd_raw, ops.unilstm_stack_bwd_raw) if self.causal
+                                else (ops.lstm_stack_fwd_raw, ops.lstm_stack_bwd_raw))
+        stack_fwd(cfg, text, w_ih, w_hh, b_ih, b_hh, f["emotions"], f["saved"], f["ws"], rng, base, lengths=lengths)
         ops.linear_fwd_raw(f["emotions"], w_t, b_t, f["xq"], T, D2, D2)
-        _lib.call("ganffn_general2_attention_fwd", P(f["xq"]), P(f["emotions"]), P(umask), P(f["att"]), P(f["alpha"]), P(f["tanh_s"]),
-                  S, B, D2, st)
+        if self.causal:        # step t attends to the emotions of steps j <= t
+            _lib.call("ganffn_general2_attention_fwd_mask", P(f["xq"]), P(f["emotions"]), P(umask), C.c_uint32(ops.ATTN_CAUSAL),
+                      P(f["att"]), P(f["alpha"]), P(f["tanh_s"]), S, B, D2, st)
+        else:
+            _lib.call("ganffn_general2_attention_fwd", P(f["xq"]), P(f["emotions"]), P(umask), P(f["att"]), P(f["alpha"]), P(f["tanh_s"]),
+                      S, B, D2, st)
         _lib.call("ganffn_meld_head_fwd", P(f["emotions"]), P(f["att"]), P(w_s), P(b_s), P(f["hidden"]), P(f["logits"]), T, D2, Cn, st)
         log_prob = f["log_prob"][:T * Cn].view(S, B, Cn)
         ops.logsoftmax_nll_raw(f["logits"], label, umask, self.class_w, log_prob, self.loss, f["dlogits"] if train else None,
@@ -1689,14 +1713,18 @@ class MeldEngine(_Runner):
         g_t, gb_t, g_s, gb_s = (self._p(n_t + j, True) for j in range(4))
         _lib.call("ganffn_meld_head_bwd", P(f["dlogits"]), P(f["emotions"]), P(f["att"]), P(f["hidden"]), P(w_s), P(f["d_res"]),
                   P(f["d_att"]), P(g_s), P(gb_s), T, D2, Cn, st)
-        _lib.call("ganffn_general2_attention_bwd", P(f["d_att"]), P(f["xq"]), P(f["emotions"]), P(umask), P(f["alpha"]), P(f["tanh_s"]),
-                  P(f["du"]), P(f["d_xq"]), P(f["d_mem"]), S, B, D2, st)
+        if self.causal:
+            _lib.call("ganffn_general2_attention_bwd_mask", P(f["d_att"]), P(f["xq"]), P(f["emotions"]), P(umask),
+                      C.c_uint32(ops.ATTN_CAUSAL), P(f["alpha"]), P(f["tanh_s"]), P(f["du"]), P(f["d_xq"]), P(f["d_mem"]), S, B, D2, st)
+        else:
+            _lib.call("ganffn_general2_attention_bwd", P(f["d_att"]), P(f["xq"]), P(f["emotions"]), P(umask), P(f["alpha"]), P(f["tanh_s"]),
+                      P(f["du"]), P(f["d_xq"]), P(f["d_mem"]), S, B, D2, st)
         ops.linear_bwd_raw(f["d_xq"], f["emotions"], w_t, f["d_tr"], g_t, gb_t, T, D2, D2, f["lin_ws"])
         # d emotions = the residual + the attention's memory side + its query side through transform
         _lib.call("ganffn_add3", P(f["d_res"]), P(f["d_mem"]), P(f["d_tr"]), P(f["d_em"]), C.c_int64(T * D2), st)
         g_ih, g_hh, gb_ih, gb_hh = self._g
-        ops.lstm_stack_bwd_raw(cfg, f["d_em"], text, f["emotions"], w_ih, w_hh, None, g_ih, g_hh, gb_ih, gb_hh, f["saved"], f["ws"],
-                               rng, base, lengths=lengths)
+        stack_bwd(cfg, f["d_em"], text, f["emotions"], w_ih, w_hh, None, g_ih, g_hh, gb_ih, gb_hh, f["saved"], f["ws"], rng, base,
+                  lengths=lengths)
         self.params.all_reduce(self.pg)
         self.params.adam(self.lr, self.wd, self.world)
         return self.loss, log_prob

@@ -1133,18 +1133,133 @@ class LstmPackedLayerFn(torch.autograd.Function):
         return (dx, None, *grads)
 
 
+# ---- one direction (include/ganffn.h "the LSTM recurrence with ONE direction"): ganffn_unilstm_*, an extension the reference
+# does not have.  ONE family whatever B (up to MAX_DIALOGUES) and whether lengths are given: lengths stands behind cfg, NULL for
+# the padded run.
+def unilstm_sizes(cfg):
+    """(n_saved, n_ws) floats of a one-direction layer call (_lib.LstmCfg) or stack call (_lib.LstmStackCfg)"""
+    head = "ganffn_unilstm_stack_" if isinstance(cfg, _lib.LstmStackCfg) else "ganffn_unilstm_"
+    n_saved, n_ws = (int(getattr(_lib.load(), head + w)(C.byref(cfg))) for w in ("saved_floats", "workspace_floats"))
+    if n_saved < 0 or n_ws < 0:
+        _lib.check(-1, head + "*_floats")
+    return n_saved, n_ws
+
+
+def unilstm_layer_fwd_raw(cfg, x, w_ih, w_hh, b_ih, b_hh, out, saved, ws, lengths=None):
+    """one forward-only layer forward: ONE call of ganffn_unilstm_layer_fwd.  cfg: _lib.LstmCfg; lengths: int32 (B,) on the device
+    or None (NULL: the padded run); w_* / b_*: arrays of 1 device pointer, passed as they are; the rest: tensors."""
+    _lib.call("ganffn_unilstm_layer_fwd", C.byref(cfg), _ptr(lengths), _ptr(x), w_ih, w_hh, b_ih, b_hh, _ptr(out), _ptr(saved),
+              _ptr(ws), _stream())
+
+
+def unilstm_layer_bwd_raw(cfg, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, ws, lengths=None):
+    """unilstm_layer_fwd_raw's backward: ONE call of ganffn_unilstm_layer_bwd; g*: arrays of 1 gradient pointer (accumulated into;
+    None or a null entry: not wanted), dx may be None"""
+    _lib.call("ganffn_unilstm_layer_bwd", C.byref(cfg), _ptr(lengths), _ptr(d_out), _ptr(x), _ptr(out), w_ih, w_hh, _ptr(dx),
+              gw_ih, gw_hh, gb_ih, gb_hh, _ptr(saved), _ptr(ws), _stream())
+
+
+def unilstm_stack_fwd_raw(cfg, x, w_ih, w_hh, b_ih, b_hh, out, saved, ws, rng, add, lengths=None):
+    """L forward-only layers with the inter-layer dropout: ONE call of ganffn_unilstm_stack_fwd.  cfg: _lib.LstmStackCfg; w_* / b_*:
+    arrays of [L][1] device pointers, passed as they are; rng: the Philox state tensor, add: the offset."""
+    _lib.call("ganffn_unilstm_stack_fwd", C.byref(cfg), _ptr(lengths), _ptr(x), w_ih, w_hh, b_ih, b_hh, _ptr(out), _ptr(saved),
+              _ptr(ws), _ptr(rng), C.c_uint64(add), _stream())
+
+
+def unilstm_stack_bwd_raw(cfg, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, ws, rng, add, lengths=None):
+    """unilstm_stack_fwd_raw's backward: ONE call of ganffn_unilstm_stack_bwd; g*: arrays of [L][1] gradient pointers"""
+    _lib.call("ganffn_unilstm_stack_bwd", C.byref(cfg), _ptr(lengths), _ptr(d_out), _ptr(x), _ptr(out), w_ih, w_hh, _ptr(dx),
+              gw_ih, gw_hh, gb_ih, gb_hh, _ptr(saved), _ptr(ws), _ptr(rng), C.c_uint64(add), _stream())
+
+
+class UniLstmLayerFn(torch.autograd.Function):
+    """one forward-only LSTM layer (nn.LSTM(bidirectional=False); ganffn_unilstm_layer_*): x (S, B, In) -> (S, B, H), out[t] a
+    function of x[0 .. t] alone; torch's parameters weight_ih [4H x In], weight_hh [4H x H], bias_ih, bias_hh [4H].  lengths: None
+    (the padded run) or int32 (B,) on the device with LstmPackedLayerFn's rule (zero output and zero dx past a dialogue's end;
+    x finite there).  One native call for B <= MAX_DIALOGUES; bigger batches run in chunks of MAX_DIALOGUES, lengths sliced
+    alongside the batch."""
+
+    @staticmethod
+    def forward(ctx, x, lengths, *params):
+        _need_gpu(x, lengths, *params)
+        x = _f32c(x)
+        p = [_f32c(t.detach()) for t in params]          # w_ih, w_hh, b_ih, b_hh
+        S, B, In = x.shape
+        H = p[1].shape[1]
+        if lengths is not None:
+            if lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,):
+                raise ValueError("lstm: lengths must be an int32 tensor of shape (%d,) on the device; got %s %s"
+                                 % (B, lengths.dtype, tuple(lengths.shape)))
+            lengths = lengths.contiguous()
+        out = torch.empty(S, B, H, device=x.device, dtype=torch.float32)
+        chunks = []
+        for b0 in range(0, B, MAX_DIALOGUES):
+            b1 = min(B, b0 + MAX_DIALOGUES)
+            whole = (b0, b1) == (0, B)
+            cfg = _lib.LstmCfg(S, b1 - b0, In, H)
+            n_saved, n_ws = unilstm_sizes(cfg)
+            xc = x if whole else x[:, b0:b1].contiguous()
+            oc = out if whole else torch.empty(S, b1 - b0, H, device=x.device, dtype=torch.float32)
+            saved = torch.empty(n_saved, device=x.device, dtype=torch.float32)
+            ws = torch.empty(n_ws, device=x.device, dtype=torch.float32)
+            lc = None if lengths is None else lengths[b0:b1]
+            unilstm_layer_fwd_raw(cfg, xc, *[_ptr_array([t]) for t in p], oc, saved, ws, lengths=lc)
+            if not whole:
+                out[:, b0:b1] = oc
+            chunks.append((b0, b1, xc, oc, saved, lc))
+        ctx.chunks, ctx.p, ctx.shape = chunks, p, (S, B, In, H)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        S, B, In, H = ctx.shape
+        p = ctx.p
+        d_out = _f32c(d_out)
+        need_dx = ctx.needs_input_grad[0]
+        dx = torch.empty(S, B, In, device=d_out.device, dtype=torch.float32) if need_dx else None
+        grads = [torch.zeros_like(t) if ctx.needs_input_grad[2 + i] else None for i, t in enumerate(p)]
+        for (b0, b1, xc, oc, saved, lc) in ctx.chunks:
+            whole = (b0, b1) == (0, B)
+            cfg = _lib.LstmCfg(S, b1 - b0, In, H)
+            ws = torch.empty(unilstm_sizes(cfg)[1], device=d_out.device, dtype=torch.float32)
+            dc = d_out if whole else d_out[:, b0:b1].contiguous()
+            dxc = None
+            if need_dx:
+                dxc = dx if whole else torch.empty(S, b1 - b0, In, device=d_out.device, dtype=torch.float32)
+            unilstm_layer_bwd_raw(cfg, dc, xc, oc, _ptr_array([p[0]]), _ptr_array([p[1]]), dxc,
+                                  *[_ptr_array([g]) for g in grads], saved, ws, lengths=lc)
+            if need_dx and not whole:
+                dx[:, b0:b1] = dxc
+        return (dx, None, *grads)
+
+
+def lstm_supported(lstm):
+    """whether lstm_forward runs this nn.LSTM on the HIP kernels: any input_size and hidden_size that are multiples of 4, any
+    num_layers, any dropout, bidirectional OR NOT — with the default (seq, batch, feature) layout, biases and no projection.
+    batch_first=True, bias=False and proj_size > 0 are not supported."""
+    return (not lstm.batch_first and lstm.proj_size == 0 and bool(lstm.bias)
+            and lstm.input_size % 4 == 0 and lstm.hidden_size % 4 == 0)
+
+
 def lstm_forward(x, lstm, training, lengths=None):
-    """nn.LSTM(..., bidirectional=True, dropout=p).forward(x)[0] for a padded (S, B, In) CUDA batch, on the HIP kernels, with the
-    module's own parameters (state_dict keys unchanged: lstm.weight_ih_l{k}[_reverse], ...).  Inter-layer dropout (every layer but
-    the last, train mode only) follows the Philox contract (site SITE_LSTM + layer).
+    """nn.LSTM(..., dropout=p).forward(x)[0] for a padded (S, B, In) CUDA batch, on the HIP kernels, with the module's own
+    parameters (state_dict keys unchanged: lstm.weight_ih_l{k}[_reverse], ...).  Inter-layer dropout (every layer but the last,
+    train mode only) follows the Philox contract (site SITE_LSTM + layer).
+    Supported configurations (lstm_supported): bidirectional=True — the MELDLSTMModel configuration, LstmLayerFn /
+    LstmPackedLayerFn — and bidirectional=False — the forward direction alone, parameters weight_ih_l{k}, ... with no _reverse,
+    UniLstmLayerFn, an extension the reference does not have; input and hidden sizes multiples of 4, any num_layers and dropout;
+    not batch_first, bias=False or proj_size > 0.
     lengths (int32 (B,) on the device; default None: the padded run above, as the reference): the packed run —
-    pack_padded_sequence(x, lengths, enforce_sorted=False) -> lstm -> pad_packed_sequence(total_length=S)[0] (LstmPackedLayerFn)."""
-    assert lstm.bidirectional and not lstm.batch_first and lstm.proj_size == 0 and lstm.bias, "lstm_forward: the MELDLSTMModel configuration only"
+    pack_padded_sequence(x, lengths, enforce_sorted=False) -> lstm -> pad_packed_sequence(total_length=S)[0]."""
+    assert not lstm.batch_first and lstm.proj_size == 0 and lstm.bias, "lstm_forward: (seq, batch, feature) layout, biases, no projection"
     h = x
     for l in range(lstm.num_layers):
         names = ["weight_ih_l%d", "weight_hh_l%d", "bias_ih_l%d", "bias_hh_l%d"]
-        params = [getattr(lstm, n % l) for n in names] + [getattr(lstm, (n % l) + "_reverse") for n in names]
-        h = LstmLayerFn.apply(h, *params) if lengths is None else LstmPackedLayerFn.apply(h, lengths, *params)
+        if lstm.bidirectional:
+            params = [getattr(lstm, n % l) for n in names] + [getattr(lstm, (n % l) + "_reverse") for n in names]
+            h = LstmLayerFn.apply(h, *params) if lengths is None else LstmPackedLayerFn.apply(h, lengths, *params)
+        else:
+            h = UniLstmLayerFn.apply(h, lengths, *[getattr(lstm, n % l) for n in names])
         if l + 1 < lstm.num_layers and lstm.dropout > 0.0:
             h = DropoutFn.apply(h, float(lstm.dropout), training, SITE_LSTM + l)
     return h

@@ -873,6 +873,38 @@ int ganffn_lstm_stack_packed_bwd(const ganffn_lstm_stack_cfg* cfg, const int32_t
                                  const float* saved, float* workspace, const uint64_t* rng, uint64_t rng_offset_add,
                                  void* stream);
 
+/* ---- N4: the LSTM recurrence with ONE direction (csrc/lstm.hip) ------------------------------------------------------------
+ * An extension the reference does not have (its LSTM is bidirectional: model.py:531): `nn.LSTM(In, H, num_layers = L,
+ * bidirectional = False, dropout = p)` — the forward direction alone, so out[t] depends on x[0 .. t] only; what the causal MELD
+ * classifier (MELDLSTMModel(causal=True)) is built on.  The same drivers, kernels and layouts as the entry points above with a
+ * direction count of 1 instead of 2: out / d_out [S x B x H], layer l > 0 reads an H-wide input, the inter-layer dropout draws
+ * over [S B x H] (site 64 + l, offset rng_offset_add + l), the weight and gradient pointers are arrays of [1] (layer calls) or
+ * [L][1] (stack calls: entry l = layer l), and a step stays one skinny product launch (one problem) + one gate launch in either
+ * pass.  With the same forward-direction weights, out is bit for bit the forward half of the bidirectional layer's out.
+ * ONE family for the padded and the packed run: `lengths` after cfg is int32 [B] on the device with the packed entry points'
+ * rule (above) or NULL: every dialogue runs all S steps.  1 <= cfg->B <= GANFFN_MAX_DIALOGUES; the refusals are those of the
+ * other families (In, H multiples of 4; L in 1 .. 16; p in [0, 1); no null pointer; 16-byte alignment; rng in train mode with
+ * dropout).  saved / workspace sizes from the four *_floats functions below (-1 for a refused cfg). */
+int64_t ganffn_unilstm_saved_floats(const ganffn_lstm_cfg* cfg);
+int64_t ganffn_unilstm_workspace_floats(const ganffn_lstm_cfg* cfg);
+int ganffn_unilstm_layer_fwd(const ganffn_lstm_cfg* cfg, const int32_t* lengths, const float* x, const float* const* w_ih,
+                             const float* const* w_hh, const float* const* b_ih, const float* const* b_hh, float* out,
+                             float* saved, float* workspace, void* stream);
+int ganffn_unilstm_layer_bwd(const ganffn_lstm_cfg* cfg, const int32_t* lengths, const float* d_out, const float* x,
+                             const float* out, const float* const* w_ih, const float* const* w_hh, float* dx,
+                             float* const* gw_ih, float* const* gw_hh, float* const* gb_ih, float* const* gb_hh,
+                             const float* saved, float* workspace, void* stream);
+int64_t ganffn_unilstm_stack_saved_floats(const ganffn_lstm_stack_cfg* cfg);
+int64_t ganffn_unilstm_stack_workspace_floats(const ganffn_lstm_stack_cfg* cfg);
+int ganffn_unilstm_stack_fwd(const ganffn_lstm_stack_cfg* cfg, const int32_t* lengths, const float* x, const float* const* w_ih,
+                             const float* const* w_hh, const float* const* b_ih, const float* const* b_hh, float* out,
+                             float* saved, float* workspace, const uint64_t* rng, uint64_t rng_offset_add, void* stream);
+int ganffn_unilstm_stack_bwd(const ganffn_lstm_stack_cfg* cfg, const int32_t* lengths, const float* d_out, const float* x,
+                             const float* out, const float* const* w_ih, const float* const* w_hh, float* dx,
+                             float* const* gw_ih, float* const* gw_hh, float* const* gb_ih, float* const* gb_hh,
+                             const float* saved, float* workspace, const uint64_t* rng, uint64_t rng_offset_add,
+                             void* stream);
+
 /* ---- N4: the MELD classifier's head (csrc/meld_head.hip) ------------------------------------------------------------------
  * Replaces `hidden = F.hardswish(emotions + F.hardswish(att_emotions))` and `self.smax_fc(hidden)` of MELDLSTMModel.forward
  * (/root/reference/model.py:553-560, the att2 branch /root/reference/train_MELD.py:71 runs) and autograd's backward of them.
