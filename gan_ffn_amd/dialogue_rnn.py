@@ -95,9 +95,7 @@ class MatchingAttention(nn.Module):
         assert self.att_type == "general2"
         if M.is_cuda and M.size(0) <= 128 and M.size(2) <= 1024:
             from . import ops                      # one HIP kernel per direction instead of ~10 torch ops on (B,S,S)
-            if causal:
-                return ops.General2AttnFn.apply(self.transform(M), M, mask, True)
-            return ops.General2AttnFn.apply(self.transform(M), M, mask)
+            return ops.General2AttnFn.apply(self.transform(M), M, mask, causal)
         alpha = general2_scores(self.transform(M).transpose(0, 1), M, mask, causal)  # (B, S, S)
         return torch.bmm(alpha, M.transpose(0, 1)).transpose(0, 1), alpha
 
@@ -203,6 +201,17 @@ def reverse_valid_prefix(X, mask):
     return X.gather(0, idx) * valid
 
 
+def _classify(m, emotions, umask, att2, causal):
+    """the tail BiModel and UniModel share: the second (masked general2; causal for UniModel) attention over the emotion sequence,
+    linear + relu + dropout, class log-probabilities -> (log_prob, alpha)"""
+    alpha = []
+    if att2:
+        emotions, a = m.matchatt.general2_all_queries(emotions, umask, causal)
+        alpha = [a[:, t, :] for t in range(a.size(1))]
+    hidden = m.dropout(F.relu(m.linear(emotions)))
+    return F.log_softmax(m.smax_fc(hidden), 2), alpha
+
+
 class BiModel(nn.Module):
     """forward and backward DialogueRNN, concatenated, second (masked general2) attention over the emotion sequence,
     linear + relu + dropout, class log-probabilities (model.py:975-1062)"""
@@ -236,16 +245,7 @@ class BiModel(nn.Module):
             emotions_b, alpha_b = self.dialog_rnn_r(rev_U, rev_qmask)
         emotions_f = self.dropout_rec(emotions_f)
         emotions_b = self.dropout_rec(self._reverse_seq(emotions_b, umask))
-        emotions = torch.cat([emotions_f, emotions_b], dim=-1)
-        if att2:
-            att, a = self.matchatt.general2_all_queries(emotions, umask)
-            alpha = [a[:, t, :] for t in range(a.size(1))]
-            hidden = F.relu(self.linear(att))
-        else:
-            alpha = []
-            hidden = F.relu(self.linear(emotions))
-        hidden = self.dropout(hidden)
-        return F.log_softmax(self.smax_fc(hidden), 2), alpha, alpha_f, alpha_b
+        return (*_classify(self, torch.cat([emotions_f, emotions_b], dim=-1), umask, att2, False), alpha_f, alpha_b)
 
 
 class UniModel(nn.Module):
@@ -269,16 +269,7 @@ class UniModel(nn.Module):
 
     def forward(self, U, qmask, umask, att2=True):
         emotions, alpha_f = self.dialog_rnn_f(U, qmask)
-        emotions = self.dropout_rec(emotions)
-        if att2:
-            att, a = self.matchatt.general2_all_queries(emotions, umask, causal=True)
-            alpha = [a[:, t, :] for t in range(a.size(1))]
-            hidden = F.relu(self.linear(att))
-        else:
-            alpha = []
-            hidden = F.relu(self.linear(emotions))
-        hidden = self.dropout(hidden)
-        return F.log_softmax(self.smax_fc(hidden), 2), alpha, alpha_f, []
+        return (*_classify(self, self.dropout_rec(emotions), umask, att2, True), alpha_f, [])
 
 
 class GAN_FFN_DialogueRNN(nn.Module):
@@ -318,11 +309,8 @@ class GAN_FFN_DialogueRNN(nn.Module):
     def forward(self, acoustic, visual, text, qmask, umask):
         from . import ops
         kl = ops.key_lengths_from_umask(umask) if self.mask_padding else None
-        if self.causal:
-            fusion = (self.acoustic_generator(acoustic, kl, causal=True) + self.visual_generator(visual, kl, causal=True)
-                      + self.text_generator(text, kl, causal=True))
-        else:
-            fusion = self.acoustic_generator(acoustic, kl) + self.visual_generator(visual, kl) + self.text_generator(text, kl)
+        c = self.causal
+        fusion = self.acoustic_generator(acoustic, kl, c) + self.visual_generator(visual, kl, c) + self.text_generator(text, kl, c)
         return self.bi_model(fusion, qmask, umask)
 
     def _open_stream(self, capacity=1, max_len=110, parties=2):
@@ -351,7 +339,7 @@ class MELDLSTMModel(nn.Module):
     a PREFIX mask (ones for the real utterances, then zeros: what every loader of the project produces).  A plain attribute, not a
     parameter or buffer: the state_dict is the same either way.
     causal (default False) is an extension the reference does not have: a classifier that never looks ahead.  The LSTM is
-    forward-only (nn.LSTM(bidirectional=False): no *_reverse parameters; csrc/lstm.hip with one direction, ops.UniLstmLayerFn) and
+    forward-only (nn.LSTM(bidirectional=False): no *_reverse parameters; the same ops.lstm_forward call path with one direction) and
     the general2 attention is CAUSAL (step t attends to the emotions of steps j <= t:
     MatchingAttention.general2_all_queries(causal=True)), so log_prob[t] of a dialogue is a function of its utterances 0 .. t
     alone.  matchatt is D_e x D_e, linear D_e -> D_h, smax_fc D_h -> n_classes; the att2=True branch feeds the D_e-wide hidden
@@ -388,10 +376,7 @@ class MELDLSTMModel(nn.Module):
             emotions, _ = self.lstm(U)      # CPU tensors: stock torch (the fixtures' CPU check; the product path is the GPU one)
         alpha, alpha_f, alpha_b = [], [], []
         if att2:
-            if self.causal:
-                att, a = self.matchatt.general2_all_queries(emotions, umask, causal=True)
-            else:
-                att, a = self.matchatt.general2_all_queries(emotions, umask)
+            att, a = self.matchatt.general2_all_queries(emotions, umask, self.causal)
             alpha = [a[:, t, :] for t in range(a.size(1))]
             hidden = F.hardswish(emotions + F.hardswish(att))
         else:

@@ -1186,8 +1186,7 @@ class Phase2Engine(_NetRunner):
         adds = {}
         for k in ("acoustic", "visual", "text"):                    # model.py:1441-1443
             adds[k] = self._net_fwd(self.G[k], self.pass_G[k], batch[k], train=train, save=train)
-        ops._lib.call("ganffn_add3", ops._ptr(self.pass_G["acoustic"].out), ops._ptr(self.pass_G["visual"].out),
-                      ops._ptr(self.pass_G["text"].out), ops._ptr(self.fusion), C.c_int64(T * 100), ops._stream())
+        ops.add3_raw(self.pass_G["acoustic"].out, self.pass_G["visual"].out, self.pass_G["text"].out, self.fusion, T * 100)
         ops.linear_fwd_raw(self.fusion, self.fc_w, self.fc_b, self.logits, T, 100, C_)          # model.py:1448
         ops.logsoftmax_nll_raw(self.logits, batch["label"], batch["umask"], self.class_w, self.log_prob, self.loss,
                                self.dlogits if train else None, self.ws2, S, B, C_)                # model.py:1449, :74-81
@@ -1463,8 +1462,7 @@ class DrnnEngine(_NetRunner):
                 if s_.cuda_stream != cur.cuda_stream:
                     cur.wait_stream(s_)
         st = st_()
-        _lib.call("ganffn_add3", P(self.pass_G["acoustic"].out), P(self.pass_G["visual"].out), P(self.pass_G["text"].out),
-                  P(f["fusion"]), C.c_int64(T * Dm), st)
+        ops.add3_raw(self.pass_G["acoustic"].out, self.pass_G["visual"].out, self.pass_G["text"].out, f["fusion"], T * Dm)
         if not causal:
             _lib.call("ganffn_seq_reverse", P(f["fusion"]), P(lens), P(f["rev_U"]), S, B, Dm, 0, st)
         # ---- the recurrence, both directions (a causal net: the forward one alone)
@@ -1477,27 +1475,20 @@ class DrnnEngine(_NetRunner):
         parties = self._shape[2]
         ops.drnn_fwd_raw(cfg, self.acfg, parties, nd, U_, spk_, mval_, Pp, LPp, APp, e_, al_, sv_, ws_, P(rng), a_rec)
         # ---- head: emotions -> matching attention -> linear/relu/dropout -> classes -> loss
-        tr = 1 if train else 0
+        tr, a_flags = 1 if train else 0, ops.ATTN_CAUSAL if causal else None
         w_t, b_t, w_l, b_l, w_s, b_s = (self._hp(nd * self.ncell + j) for j in range(6))
         if causal:
             # the join of one direction is dropout_rec on e_f alone (SITE_JOIN_F); eval: the emotions are e_f itself
             em = f["emotions"] if train else f["e_f"]
             if train:
-                _lib.call("ganffn_dropout", P(f["e_f"]), P(em), T, He, C.c_float(self.p_join), C.c_uint32(SITE_JOIN_F), P(rng),
-                          C.c_uint64(a_head), st)
+                ops.dropout_raw(f["e_f"], em, T, He, self.p_join, SITE_JOIN_F, rng, a_head)
         else:
             em = f["emotions"]
             _lib.call("ganffn_drnn_join_fwd", P(f["e_f"]), P(f["e_b"]), P(lens), P(em), S, B, He, C.c_float(self.p_join),
                       C.c_uint32(SITE_JOIN_F), C.c_uint32(SITE_JOIN_B), P(rng), C.c_uint64(a_head), tr, st)
         ops.linear_fwd_raw(em, w_t, b_t, f["xq"], T, D2, D2)
-        if causal:
-            _lib.call("ganffn_general2_attention_fwd_mask", P(f["xq"]), P(em), P(umask), C.c_uint32(ops.ATTN_CAUSAL), P(f["att"]),
-                      P(f["alpha2"]), P(f["tanh_s"]), S, B, D2, st)
-        else:
-            _lib.call("ganffn_general2_attention_fwd", P(f["xq"]), P(em), P(umask), P(f["att"]), P(f["alpha2"]), P(f["tanh_s"]),
-                      S, B, D2, st)
-        _lib.call("ganffn_ffn_linear1_fwd", P(f["att"]), P(w_l), P(b_l), P(f["hidden"]), T, D2, self.Dh2, C.c_float(self.p_hid),
-                  C.c_uint32(SITE_HIDDEN), P(rng), C.c_uint64(a_head), tr, st)
+        ops.general2_attention_fwd_raw(f["xq"], em, umask, f["att"], f["alpha2"], f["tanh_s"], S, B, D2, a_flags)
+        ops.linear1_fwd_raw(f["att"], w_l, b_l, f["hidden"], T, D2, self.Dh2, self.p_hid, SITE_HIDDEN, rng, a_head, train)
         ops.linear_fwd_raw(f["hidden"], w_s, b_s, f["logits"], T, self.Dh2, Cn)
         log_prob = f["log_prob"][:T * Cn].view(S, B, Cn)
         ops.logsoftmax_nll_raw(f["logits"], batch["label"], umask, self.class_w, log_prob, self.loss,
@@ -1511,17 +1502,12 @@ class DrnnEngine(_NetRunner):
         mscale = 1.0 / (1.0 - self.p_hid) if self.p_hid > 0 else 1.0
         _lib.call("ganffn_mask_pos_inplace", P(f["d_hidden"]), P(f["hidden"]), C.c_float(mscale), C.c_int64(T * self.Dh2), st)
         ops.linear_bwd_raw(f["d_hidden"], f["att"], w_l, f["d_att"], g_l, gb_l, T, D2, self.Dh2, f["lin_ws"])
-        if causal:
-            _lib.call("ganffn_general2_attention_bwd_mask", P(f["d_att"]), P(f["xq"]), P(em), P(umask), C.c_uint32(ops.ATTN_CAUSAL),
-                      P(f["alpha2"]), P(f["tanh_s"]), P(f["du"]), P(f["d_xq"]), P(f["d_mem"]), S, B, D2, st)
-        else:
-            _lib.call("ganffn_general2_attention_bwd", P(f["d_att"]), P(f["xq"]), P(em), P(umask), P(f["alpha2"]), P(f["tanh_s"]),
-                      P(f["du"]), P(f["d_xq"]), P(f["d_mem"]), S, B, D2, st)
+        ops.general2_attention_bwd_raw(f["d_att"], f["xq"], em, umask, f["alpha2"], f["tanh_s"], f["du"], f["d_xq"], f["d_mem"], S, B, D2,
+                                       a_flags)
         ops.linear_bwd_raw(f["d_xq"], em, w_t, f["d_em"], g_t, gb_t, T, D2, D2, f["lin_ws"])
         f["d_em"][:T * D2].add_(f["d_mem"][:T * D2])          # memory path of the attention + its transform(mem) path
         if causal:
-            _lib.call("ganffn_dropout", P(f["d_em"]), P(f["d_e_f"]), T, He, C.c_float(self.p_join), C.c_uint32(SITE_JOIN_F), P(rng),
-                      C.c_uint64(a_head), st)
+            ops.dropout_raw(f["d_em"], f["d_e_f"], T, He, self.p_join, SITE_JOIN_F, rng, a_head)
         else:
             _lib.call("ganffn_drnn_join_bwd", P(f["d_em"]), P(lens), P(f["d_e_f"]), P(f["d_e_b"]), S, B, He, C.c_float(self.p_join),
                       C.c_uint32(SITE_JOIN_F), C.c_uint32(SITE_JOIN_B), P(rng), C.c_uint64(a_head), tr, st)
@@ -1582,8 +1568,8 @@ class MeldEngine(_Runner):
     ganffn_lstm_stack_packed_* for any B <= max_dialogues: the same launches; everything else in the step is unchanged.
     A model built with causal=True (MELDLSTMModel(causal=True); an extension the reference does not have; read from the model,
     and refused when it contradicts lstm.bidirectional) steps the classifier that never looks ahead: one direction (D = D_e
-    instead of 2 D_e everywhere above), the LSTM's 4 L tensors on the slab, pointer arrays [L][1], the stack through
-    ganffn_unilstm_stack_* for any B <= max_dialogues (with lengths when packed, NULL otherwise) and the attention through
+    instead of 2 D_e everywhere above), the LSTM's 4 L tensors on the slab, pointer arrays [L][1], the same ops.lstm_stack_*_raw
+    calls with ndir=1 (ops.lstm_family: ganffn_unilstm_stack_* for any B <= max_dialogues, lengths or NULL) and the attention through
     ganffn_general2_attention_fwd_mask / _bwd_mask with GANFFN_ATTN_CAUSAL; the rest of the step is the same calls.  Its limits:
     D_e <= 1024, D_m and D_e multiples of 4, smax_fc and matchatt D_e wide.  A default model issues the calls it always did.
     Data-parallel over dialogues like Phase2Engine: the gradient slab is all-reduced in-line on the step's stream (through
@@ -1655,7 +1641,7 @@ class MeldEngine(_Runner):
             cS, cB = self._alloc_S, self._alloc_B
             lib = _lib.load()
             cfg = _lib.LstmStackCfg(cS, cB, self.Dm, self.He, self.L, self.p_lstm, 1)
-            n_saved, n_ws = ops.unilstm_sizes(cfg) if self.causal else ops.lstm_sizes(cfg, self.packed)
+            n_saved, n_ws = ops.lstm_sizes(cfg, self.packed, self.ndir)
             T, D2, Cn = cS * cB, self.D2, self.n_classes
             z = lambda n: torch.empty(n, device=self.dev, dtype=torch.float32)
             self._f = dict(emotions=z(T * D2), xq=z(T * D2), att=z(T * D2), alpha=z(cB * cS * cS), tanh_s=z(cB * cS * cS),
@@ -1692,16 +1678,11 @@ class MeldEngine(_Runner):
         # ---- forward: LSTM stack -> transform -> general2 attention -> hardswish head -> loss       (model.py:546-560)
         # packed: lengths on the device, no host read; alive until the backward is enqueued.  The entry points: ops.lstm_family
         lengths = umask.sum(1).to(torch.int32) if self.packed else None
-        stack_fwd, stack_bwd = ((ops.unilstm_stack_fwd_raw, ops.unilstm_stack_bwd_raw) if self.causal
-                                else (ops.lstm_stack_fwd_raw, ops.lstm_stack_bwd_raw))
-        stack_fwd(cfg, text, w_ih, w_hh, b_ih, b_hh, f["emotions"], f["saved"], f["ws"], rng, base, lengths=lengths)
+        ops.lstm_stack_fwd_raw(cfg, text, w_ih, w_hh, b_ih, b_hh, f["emotions"], f["saved"], f["ws"], rng, base, lengths=lengths,
+                               ndir=self.ndir)
         ops.linear_fwd_raw(f["emotions"], w_t, b_t, f["xq"], T, D2, D2)
-        if self.causal:        # step t attends to the emotions of steps j <= t
-            _lib.call("ganffn_general2_attention_fwd_mask", P(f["xq"]), P(f["emotions"]), P(umask), C.c_uint32(ops.ATTN_CAUSAL),
-                      P(f["att"]), P(f["alpha"]), P(f["tanh_s"]), S, B, D2, st)
-        else:
-            _lib.call("ganffn_general2_attention_fwd", P(f["xq"]), P(f["emotions"]), P(umask), P(f["att"]), P(f["alpha"]), P(f["tanh_s"]),
-                      S, B, D2, st)
+        a_flags = ops.ATTN_CAUSAL if self.causal else None        # causal: step t attends to the emotions of steps j <= t
+        ops.general2_attention_fwd_raw(f["xq"], f["emotions"], umask, f["att"], f["alpha"], f["tanh_s"], S, B, D2, a_flags)
         _lib.call("ganffn_meld_head_fwd", P(f["emotions"]), P(f["att"]), P(w_s), P(b_s), P(f["hidden"]), P(f["logits"]), T, D2, Cn, st)
         log_prob = f["log_prob"][:T * Cn].view(S, B, Cn)
         ops.logsoftmax_nll_raw(f["logits"], label, umask, self.class_w, log_prob, self.loss, f["dlogits"] if train else None,
@@ -1713,18 +1694,14 @@ class MeldEngine(_Runner):
         g_t, gb_t, g_s, gb_s = (self._p(n_t + j, True) for j in range(4))
         _lib.call("ganffn_meld_head_bwd", P(f["dlogits"]), P(f["emotions"]), P(f["att"]), P(f["hidden"]), P(w_s), P(f["d_res"]),
                   P(f["d_att"]), P(g_s), P(gb_s), T, D2, Cn, st)
-        if self.causal:
-            _lib.call("ganffn_general2_attention_bwd_mask", P(f["d_att"]), P(f["xq"]), P(f["emotions"]), P(umask),
-                      C.c_uint32(ops.ATTN_CAUSAL), P(f["alpha"]), P(f["tanh_s"]), P(f["du"]), P(f["d_xq"]), P(f["d_mem"]), S, B, D2, st)
-        else:
-            _lib.call("ganffn_general2_attention_bwd", P(f["d_att"]), P(f["xq"]), P(f["emotions"]), P(umask), P(f["alpha"]), P(f["tanh_s"]),
-                      P(f["du"]), P(f["d_xq"]), P(f["d_mem"]), S, B, D2, st)
+        ops.general2_attention_bwd_raw(f["d_att"], f["xq"], f["emotions"], umask, f["alpha"], f["tanh_s"], f["du"], f["d_xq"], f["d_mem"],
+                                       S, B, D2, a_flags)
         ops.linear_bwd_raw(f["d_xq"], f["emotions"], w_t, f["d_tr"], g_t, gb_t, T, D2, D2, f["lin_ws"])
         # d emotions = the residual + the attention's memory side + its query side through transform
-        _lib.call("ganffn_add3", P(f["d_res"]), P(f["d_mem"]), P(f["d_tr"]), P(f["d_em"]), C.c_int64(T * D2), st)
+        ops.add3_raw(f["d_res"], f["d_mem"], f["d_tr"], f["d_em"], T * D2)
         g_ih, g_hh, gb_ih, gb_hh = self._g
-        stack_bwd(cfg, f["d_em"], text, f["emotions"], w_ih, w_hh, None, g_ih, g_hh, gb_ih, gb_hh, f["saved"], f["ws"], rng, base,
-                  lengths=lengths)
+        ops.lstm_stack_bwd_raw(cfg, f["d_em"], text, f["emotions"], w_ih, w_hh, None, g_ih, g_hh, gb_ih, gb_hh, f["saved"], f["ws"], rng,
+                               base, lengths=lengths, ndir=self.ndir)
         self.params.all_reduce(self.pg)
         self.params.adam(self.lr, self.wd, self.world)
         return self.loss, log_prob

@@ -352,6 +352,41 @@ def rng_advance_raw(rng, delta):
     _lib.call("ganffn_rng_advance", _ptr(rng), C.c_uint64(delta), _stream())
 
 
+def add3_raw(a, b, c, out, n):
+    _lib.call("ganffn_add3", _ptr(a), _ptr(b), _ptr(c), _ptr(out), C.c_int64(n), _stream())
+
+
+def dropout_raw(x, out, R, C_, p, site, rng_state, add):
+    """out = dropout(x [R x C_]) with the mask of (site, rng_state + add); the same call on dy is its backward"""
+    _lib.call("ganffn_dropout", _ptr(x), _ptr(out), R, C_, C.c_float(p), C.c_uint32(site), _ptr(rng_state), C.c_uint64(add), _stream())
+
+
+def linear1_fwd_raw(x, w, b, out, T, K, N, p, site, rng_state, add, train):
+    """out [T x N] = dropout(relu(x [T x K] W^T + b)); train false (or p 0): no dropout, rng_state may be None"""
+    _lib.call("ganffn_ffn_linear1_fwd", _ptr(x), _ptr(w), _ptr(b), _ptr(out), T, K, N, C.c_float(p), C.c_uint32(site), _ptr(rng_state),
+              C.c_uint64(add), 1 if train else 0, _stream())
+
+
+def general2_attention_fwd_raw(x, mem, mask, att, alpha, tanh_s, S, B, D, flags=None):
+    """masked general2 attention, every step the query: flags None: ganffn_general2_attention_fwd; an int (ATTN_CAUSAL or 0):
+    ganffn_general2_attention_fwd_mask with the flags behind the mask"""
+    if flags is None:
+        _lib.call("ganffn_general2_attention_fwd", _ptr(x), _ptr(mem), _ptr(mask), _ptr(att), _ptr(alpha), _ptr(tanh_s), S, B, D, _stream())
+    else:
+        _lib.call("ganffn_general2_attention_fwd_mask", _ptr(x), _ptr(mem), _ptr(mask), C.c_uint32(flags), _ptr(att), _ptr(alpha),
+                  _ptr(tanh_s), S, B, D, _stream())
+
+
+def general2_attention_bwd_raw(d_att, x, mem, mask, alpha, tanh_s, du, dx, dmem, S, B, D, flags=None):
+    """general2_attention_fwd_raw's backward, flags as the forward was given"""
+    if flags is None:
+        _lib.call("ganffn_general2_attention_bwd", _ptr(d_att), _ptr(x), _ptr(mem), _ptr(mask), _ptr(alpha), _ptr(tanh_s), _ptr(du),
+                  _ptr(dx), _ptr(dmem), S, B, D, _stream())
+    else:
+        _lib.call("ganffn_general2_attention_bwd_mask", _ptr(d_att), _ptr(x), _ptr(mem), _ptr(mask), C.c_uint32(flags), _ptr(alpha),
+                  _ptr(tanh_s), _ptr(du), _ptr(dx), _ptr(dmem), S, B, D, _stream())
+
+
 # ----------------------------------------------------------------------------------------------
 # autograd Functions
 # ----------------------------------------------------------------------------------------------
@@ -510,8 +545,7 @@ class DropoutFn(torch.autograd.Function):
         rng = DeviceRng.get(x.device)
         add = rng.next_add()
         out = torch.empty_like(xc)
-        _lib.call("ganffn_dropout", _ptr(xc), _ptr(out), R, C_, C.c_float(p), C.c_uint32(site), _ptr(rng.state),
-                  C.c_uint64(add), _stream())
+        dropout_raw(xc, out, R, C_, p, site, rng.state, add)
         ctx.args = (R, C_, p, site, rng.state, add)
         return out
 
@@ -519,11 +553,9 @@ class DropoutFn(torch.autograd.Function):
     def backward(ctx, dy):
         if not ctx.active:
             return dy, None, None, None
-        R, C_, p, site, state, add = ctx.args
         dy = _f32c(dy)
         dx = torch.empty_like(dy)
-        _lib.call("ganffn_dropout", _ptr(dy), _ptr(dx), R, C_, C.c_float(p), C.c_uint32(site), _ptr(state),
-                  C.c_uint64(add), _stream())
+        dropout_raw(dy, dx, *ctx.args)
         return dx, None, None, None
 
 
@@ -535,7 +567,7 @@ class Add3Fn(torch.autograd.Function):
         _need_gpu(a, b, c)
         a, b, c = _f32c(a), _f32c(b), _f32c(c)
         out = torch.empty_like(a)
-        _lib.call("ganffn_add3", _ptr(a), _ptr(b), _ptr(c), _ptr(out), C.c_int64(a.numel()), _stream())
+        add3_raw(a, b, c, out, a.numel())
         return out
 
     @staticmethod
@@ -583,8 +615,7 @@ class General2AttnFn(torch.autograd.Function):
         alpha = torch.empty(B, S, S, device=mc.device, dtype=torch.float32)
         ts = torch.empty(B, S, S, device=mc.device, dtype=torch.float32)
         ctx.flags = ATTN_CAUSAL if causal else 0
-        _lib.call("ganffn_general2_attention_fwd_mask", _ptr(xc), _ptr(mc), _ptr(kc), C.c_uint32(ctx.flags), _ptr(att), _ptr(alpha),
-                  _ptr(ts), S, B, D, _stream())
+        general2_attention_fwd_raw(xc, mc, kc, att, alpha, ts, S, B, D, ctx.flags)
         ctx.save_for_backward(xc, mc, kc, alpha, ts)
         ctx.mark_non_differentiable(alpha)
         return att, alpha
@@ -596,8 +627,7 @@ class General2AttnFn(torch.autograd.Function):
         g = _f32c(d_att)
         du = torch.empty_like(alpha)
         dx, dm = torch.empty_like(mc), torch.empty_like(mc)
-        _lib.call("ganffn_general2_attention_bwd_mask", _ptr(g), _ptr(xc), _ptr(mc), _ptr(kc), C.c_uint32(ctx.flags), _ptr(alpha),
-                  _ptr(ts), _ptr(du), _ptr(dx), _ptr(dm), S, B, D, _stream())
+        general2_attention_bwd_raw(g, xc, mc, kc, alpha, ts, du, dx, dm, S, B, D, ctx.flags)
         return dx, dm, None, None
 
 
@@ -983,7 +1013,8 @@ def dialogue_rnn_run(cells, Us, qmasks, training):
 SITE_LSTM = 64          # + layer: the dropout nn.LSTM(dropout=p) applies to the output of every layer but the last
 
 # The entry points of each family (lstm_family).  The naming is irregular — "batch" / "packed" stand before "layer" and behind
-# "stack" — so the heads are written out; the packed family has no size functions of its own and takes the _batch_ ones.
+# "stack" — so the heads are written out; the packed family has no size functions of its own and takes the _batch_ ones.  "uni" is
+# the one-direction family (include/ganffn.h "the LSTM recurrence with ONE direction"; an extension the reference does not have).
 _LSTM_ENTRY = {
     "": {"layer": "ganffn_lstm_layer_", "stack": "ganffn_lstm_stack_",
          "layer_sizes": "ganffn_lstm_", "stack_sizes": "ganffn_lstm_stack_"},
@@ -991,65 +1022,96 @@ _LSTM_ENTRY = {
               "layer_sizes": "ganffn_lstm_batch_", "stack_sizes": "ganffn_lstm_stack_batch_"},
     "packed": {"layer": "ganffn_lstm_packed_layer_", "stack": "ganffn_lstm_stack_packed_",
                "layer_sizes": "ganffn_lstm_batch_", "stack_sizes": "ganffn_lstm_stack_batch_"},
+    "uni": {"layer": "ganffn_unilstm_layer_", "stack": "ganffn_unilstm_stack_",
+            "layer_sizes": "ganffn_unilstm_", "stack_sizes": "ganffn_unilstm_stack_"},
 }
 
 
-def lstm_family(B, packed):
+def lstm_family(B, packed, ndir=2):
     """THE rule for which entry-point family of the LSTM a call takes (every family is a thin wrapper over the one set of
-    drivers in csrc/lstm.hip; the names: _LSTM_ENTRY):
-      "packed"  lengths are given, whatever B (up to MAX_DIALOGUES)      ganffn_lstm_packed_layer_* / ganffn_lstm_stack_packed_*
-      "batch"   otherwise B > 32 dialogues (up to MAX_DIALOGUES)         ganffn_lstm_batch_layer_* / ganffn_lstm_stack_batch_*
-      ""        otherwise                                                ganffn_lstm_layer_* / ganffn_lstm_stack_*"""
+    drivers in csrc/lstm.hip, which take a direction count; the names: _LSTM_ENTRY):
+      "uni"     one direction, whatever B (up to MAX_DIALOGUES) and packed   ganffn_unilstm_layer_* / ganffn_unilstm_stack_*
+      "packed"  otherwise lengths are given, whatever B                      ganffn_lstm_packed_layer_* / ganffn_lstm_stack_packed_*
+      "batch"   otherwise B > 32 dialogues (up to MAX_DIALOGUES)             ganffn_lstm_batch_layer_* / ganffn_lstm_stack_batch_*
+      ""        otherwise                                                    ganffn_lstm_layer_* / ganffn_lstm_stack_*
+    lengths stand behind cfg in "packed" and in "uni" (there always: NULL for the padded run)."""
+    if ndir == 1:
+        return "uni"
     if packed:
         return "packed"
     return "batch" if B > 32 else ""
 
 
-def lstm_sizes(cfg, packed=False):
+def lstm_sizes(cfg, packed=False, ndir=2):
     """(n_saved, n_ws) floats of a layer call (_lib.LstmCfg) or a stack call (_lib.LstmStackCfg), from the size functions of
-    the family cfg.B and `packed` select"""
-    head = _LSTM_ENTRY[lstm_family(cfg.B, packed)]["stack_sizes" if isinstance(cfg, _lib.LstmStackCfg) else "layer_sizes"]
+    the family cfg.B, `packed` and ndir select"""
+    head = _LSTM_ENTRY[lstm_family(cfg.B, packed, ndir)]["stack_sizes" if isinstance(cfg, _lib.LstmStackCfg) else "layer_sizes"]
     n_saved, n_ws = (int(getattr(_lib.load(), head + w)(C.byref(cfg))) for w in ("saved_floats", "workspace_floats"))
     if n_saved < 0 or n_ws < 0:
         _lib.check(-1, head + "*_floats")
     return n_saved, n_ws
 
 
-def _lstm_call(kind, what, cfg, lengths, *args):
-    head = (C.byref(cfg),) if lengths is None else (C.byref(cfg), _ptr(lengths))
-    _lib.call(_LSTM_ENTRY[lstm_family(cfg.B, lengths is not None)][kind] + what, *head, *args, _stream())
+def _lstm_call(kind, what, cfg, lengths, ndir, *args):
+    fam = lstm_family(cfg.B, lengths is not None, ndir)
+    head = (C.byref(cfg),) if lengths is None and ndir == 2 else (C.byref(cfg), _ptr(lengths))
+    _lib.call(_LSTM_ENTRY[fam][kind] + what, *head, *args, _stream())
 
 
-def lstm_layer_fwd_raw(cfg, x, w_ih, w_hh, b_ih, b_hh, out, saved, ws, lengths=None):
-    """one layer forward: ONE call of the family's layer_fwd (lstm_family; lengths given: the packed one, lengths behind cfg).
-    cfg: _lib.LstmCfg; w_* / b_*: arrays of 2 device pointers (forward, reverse), passed as they are; the rest: tensors."""
-    _lstm_call("layer", "fwd", cfg, lengths, _ptr(x), w_ih, w_hh, b_ih, b_hh, _ptr(out), _ptr(saved), _ptr(ws))
+def lstm_layer_fwd_raw(cfg, x, w_ih, w_hh, b_ih, b_hh, out, saved, ws, lengths=None, ndir=2):
+    """one layer forward: ONE call of the family's layer_fwd (lstm_family; lengths behind cfg where the family takes them).
+    cfg: _lib.LstmCfg; w_* / b_*: arrays of ndir device pointers (forward, reverse), passed as they are; the rest: tensors."""
+    _lstm_call("layer", "fwd", cfg, lengths, ndir, _ptr(x), w_ih, w_hh, b_ih, b_hh, _ptr(out), _ptr(saved), _ptr(ws))
 
 
-def lstm_layer_bwd_raw(cfg, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, ws, lengths=None):
-    """lstm_layer_fwd_raw's backward: ONE call of the family's layer_bwd; g*: arrays of 2 gradient pointers (accumulated into;
+def lstm_layer_bwd_raw(cfg, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, ws, lengths=None, ndir=2):
+    """lstm_layer_fwd_raw's backward: ONE call of the family's layer_bwd; g*: arrays of ndir gradient pointers (accumulated into;
     None or a null entry: not wanted), dx may be None"""
-    _lstm_call("layer", "bwd", cfg, lengths, _ptr(d_out), _ptr(x), _ptr(out), w_ih, w_hh, _ptr(dx), gw_ih, gw_hh, gb_ih, gb_hh,
+    _lstm_call("layer", "bwd", cfg, lengths, ndir, _ptr(d_out), _ptr(x), _ptr(out), w_ih, w_hh, _ptr(dx), gw_ih, gw_hh, gb_ih, gb_hh,
                _ptr(saved), _ptr(ws))
 
 
-def lstm_stack_fwd_raw(cfg, x, w_ih, w_hh, b_ih, b_hh, out, saved, ws, rng, add, lengths=None):
+def lstm_stack_fwd_raw(cfg, x, w_ih, w_hh, b_ih, b_hh, out, saved, ws, rng, add, lengths=None, ndir=2):
     """L layers with the inter-layer dropout forward: ONE call of the family's stack fwd.  cfg: _lib.LstmStackCfg; w_* / b_*:
-    arrays of [L][2] device pointers, passed as they are; rng: the Philox state tensor, add: the offset."""
-    _lstm_call("stack", "fwd", cfg, lengths, _ptr(x), w_ih, w_hh, b_ih, b_hh, _ptr(out), _ptr(saved), _ptr(ws), _ptr(rng), C.c_uint64(add))
+    arrays of [L][ndir] device pointers, passed as they are; rng: the Philox state tensor, add: the offset."""
+    _lstm_call("stack", "fwd", cfg, lengths, ndir, _ptr(x), w_ih, w_hh, b_ih, b_hh, _ptr(out), _ptr(saved), _ptr(ws), _ptr(rng),
+               C.c_uint64(add))
 
 
-def lstm_stack_bwd_raw(cfg, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, ws, rng, add, lengths=None):
-    """lstm_stack_fwd_raw's backward: ONE call of the family's stack bwd; g*: arrays of [L][2] gradient pointers"""
-    _lstm_call("stack", "bwd", cfg, lengths, _ptr(d_out), _ptr(x), _ptr(out), w_ih, w_hh, _ptr(dx), gw_ih, gw_hh, gb_ih, gb_hh,
+def lstm_stack_bwd_raw(cfg, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, ws, rng, add, lengths=None, ndir=2):
+    """lstm_stack_fwd_raw's backward: ONE call of the family's stack bwd; g*: arrays of [L][ndir] gradient pointers"""
+    _lstm_call("stack", "bwd", cfg, lengths, ndir, _ptr(d_out), _ptr(x), _ptr(out), w_ih, w_hh, _ptr(dx), gw_ih, gw_hh, gb_ih, gb_hh,
                _ptr(saved), _ptr(ws), _ptr(rng), C.c_uint64(add))
 
 
+# the one-direction forms under their own names (ndir=1 of the above: same arguments, arrays of 1 / [L][1] pointers)
+def unilstm_sizes(cfg):
+    return lstm_sizes(cfg, False, 1)
+
+
+def unilstm_layer_fwd_raw(cfg, x, w_ih, w_hh, b_ih, b_hh, out, saved, ws, lengths=None):
+    lstm_layer_fwd_raw(cfg, x, w_ih, w_hh, b_ih, b_hh, out, saved, ws, lengths, 1)
+
+
+def unilstm_layer_bwd_raw(cfg, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, ws, lengths=None):
+    lstm_layer_bwd_raw(cfg, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, ws, lengths, 1)
+
+
+def unilstm_stack_fwd_raw(cfg, x, w_ih, w_hh, b_ih, b_hh, out, saved, ws, rng, add, lengths=None):
+    lstm_stack_fwd_raw(cfg, x, w_ih, w_hh, b_ih, b_hh, out, saved, ws, rng, add, lengths, 1)
+
+
+def unilstm_stack_bwd_raw(cfg, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, ws, rng, add, lengths=None):
+    lstm_stack_bwd_raw(cfg, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, ws, rng, add, lengths, 1)
+
+
 def _lstm_layer_fwd(ctx, x, lengths, params):
-    """the forward of LstmLayerFn (lengths None) and LstmPackedLayerFn: chunks of MAX_DIALOGUES, lengths sliced with the batch"""
+    """the forward of LstmLayerFn (lengths None), LstmPackedLayerFn and UniLstmLayerFn (4 parameter tensors: one direction):
+    chunks of MAX_DIALOGUES, lengths sliced with the batch"""
     _need_gpu(x, *params)
     x = _f32c(x)
-    p = [_f32c(t.detach()) for t in params]          # w_ih0, w_hh0, b_ih0, b_hh0, w_ih1, w_hh1, b_ih1, b_hh1
+    p = [_f32c(t.detach()) for t in params]          # w_ih, w_hh, b_ih, b_hh of the forward direction, then of the reverse one
+    ndir = len(p) // 4
     S, B, In = x.shape
     H = p[1].shape[1]
     if lengths is not None:
@@ -1058,23 +1120,22 @@ def _lstm_layer_fwd(ctx, x, lengths, params):
             raise ValueError("lstm: lengths must be an int32 tensor of shape (%d,) on the device; got %s %s"
                              % (B, lengths.dtype, tuple(lengths.shape)))
         lengths = lengths.contiguous()
-    out = torch.empty(S, B, 2 * H, device=x.device, dtype=torch.float32)
+    out = torch.empty(S, B, ndir * H, device=x.device, dtype=torch.float32)
     chunks = []
     for b0 in range(0, B, MAX_DIALOGUES):
         b1 = min(B, b0 + MAX_DIALOGUES)
         cfg = _lib.LstmCfg(S, b1 - b0, In, H)
-        n_saved, n_ws = lstm_sizes(cfg, lengths is not None)
+        n_saved, n_ws = lstm_sizes(cfg, lengths is not None, ndir)
         xc = x if (b0, b1) == (0, B) else x[:, b0:b1].contiguous()
-        oc = out if (b0, b1) == (0, B) else torch.empty(S, b1 - b0, 2 * H, device=x.device, dtype=torch.float32)
+        oc = out if (b0, b1) == (0, B) else torch.empty(S, b1 - b0, ndir * H, device=x.device, dtype=torch.float32)
         saved = torch.empty(n_saved, device=x.device, dtype=torch.float32)
         ws = torch.empty(n_ws, device=x.device, dtype=torch.float32)
         lc = None if lengths is None else lengths[b0:b1]          # (a slice of a contiguous vector: contiguous, 4-byte aligned)
-        lstm_layer_fwd_raw(cfg, xc, *[_ptr_array([p[j], p[4 + j]]) for j in range(4)], oc, saved, ws, lengths=lc)
+        lstm_layer_fwd_raw(cfg, xc, *[_ptr_array(p[j::4]) for j in range(4)], oc, saved, ws, lengths=lc, ndir=ndir)
         if oc is not out:
             out[:, b0:b1] = oc
         chunks.append((b0, b1, xc, oc, saved, lc))
     ctx.chunks, ctx.p, ctx.shape = chunks, p, (S, B, In, H)
-    ctx.need_x = x.requires_grad if hasattr(x, "requires_grad") else False
     return out
 
 
@@ -1082,19 +1143,20 @@ def _lstm_layer_bwd(ctx, d_out, i_x, i_p):
     """-> (dx, parameter gradients); i_x / i_p: where x / the first parameter sit among the Function's inputs"""
     S, B, In, H = ctx.shape
     p = ctx.p
+    ndir = len(p) // 4
     d_out = _f32c(d_out)
     need_dx = ctx.needs_input_grad[i_x]
     dx = torch.empty(S, B, In, device=d_out.device, dtype=torch.float32) if need_dx else None
     grads = [torch.zeros_like(t) if ctx.needs_input_grad[i_p + i] else None for i, t in enumerate(p)]
     for (b0, b1, xc, oc, saved, lc) in ctx.chunks:
         cfg = _lib.LstmCfg(S, b1 - b0, In, H)
-        ws = torch.empty(lstm_sizes(cfg, lc is not None)[1], device=d_out.device, dtype=torch.float32)
+        ws = torch.empty(lstm_sizes(cfg, lc is not None, ndir)[1], device=d_out.device, dtype=torch.float32)
         dc = d_out if (b0, b1) == (0, B) else d_out[:, b0:b1].contiguous()
         dxc = None
         if need_dx:
             dxc = dx if (b0, b1) == (0, B) else torch.empty(S, b1 - b0, In, device=d_out.device, dtype=torch.float32)
-        lstm_layer_bwd_raw(cfg, dc, xc, oc, _ptr_array([p[0], p[4]]), _ptr_array([p[1], p[5]]), dxc,
-                           *[_ptr_array([grads[j], grads[4 + j]]) for j in range(4)], saved, ws, lengths=lc)
+        lstm_layer_bwd_raw(cfg, dc, xc, oc, _ptr_array(p[0::4]), _ptr_array(p[1::4]), dxc,
+                           *[_ptr_array(grads[j::4]) for j in range(4)], saved, ws, lengths=lc, ndir=ndir)
         if need_dx and dxc is not dx:
             dx[:, b0:b1] = dxc
     return dx, grads
@@ -1133,103 +1195,19 @@ class LstmPackedLayerFn(torch.autograd.Function):
         return (dx, None, *grads)
 
 
-# ---- one direction (include/ganffn.h "the LSTM recurrence with ONE direction"): ganffn_unilstm_*, an extension the reference
-# does not have.  ONE family whatever B (up to MAX_DIALOGUES) and whether lengths are given: lengths stands behind cfg, NULL for
-# the padded run.
-def unilstm_sizes(cfg):
-    """(n_saved, n_ws) floats of a one-direction layer call (_lib.LstmCfg) or stack call (_lib.LstmStackCfg)"""
-    head = "ganffn_unilstm_stack_" if isinstance(cfg, _lib.LstmStackCfg) else "ganffn_unilstm_"
-    n_saved, n_ws = (int(getattr(_lib.load(), head + w)(C.byref(cfg))) for w in ("saved_floats", "workspace_floats"))
-    if n_saved < 0 or n_ws < 0:
-        _lib.check(-1, head + "*_floats")
-    return n_saved, n_ws
-
-
-def unilstm_layer_fwd_raw(cfg, x, w_ih, w_hh, b_ih, b_hh, out, saved, ws, lengths=None):
-    """one forward-only layer forward: ONE call of ganffn_unilstm_layer_fwd.  cfg: _lib.LstmCfg; lengths: int32 (B,) on the device
-    or None (NULL: the padded run); w_* / b_*: arrays of 1 device pointer, passed as they are; the rest: tensors."""
-    _lib.call("ganffn_unilstm_layer_fwd", C.byref(cfg), _ptr(lengths), _ptr(x), w_ih, w_hh, b_ih, b_hh, _ptr(out), _ptr(saved),
-              _ptr(ws), _stream())
-
-
-def unilstm_layer_bwd_raw(cfg, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, ws, lengths=None):
-    """unilstm_layer_fwd_raw's backward: ONE call of ganffn_unilstm_layer_bwd; g*: arrays of 1 gradient pointer (accumulated into;
-    None or a null entry: not wanted), dx may be None"""
-    _lib.call("ganffn_unilstm_layer_bwd", C.byref(cfg), _ptr(lengths), _ptr(d_out), _ptr(x), _ptr(out), w_ih, w_hh, _ptr(dx),
-              gw_ih, gw_hh, gb_ih, gb_hh, _ptr(saved), _ptr(ws), _stream())
-
-
-def unilstm_stack_fwd_raw(cfg, x, w_ih, w_hh, b_ih, b_hh, out, saved, ws, rng, add, lengths=None):
-    """L forward-only layers with the inter-layer dropout: ONE call of ganffn_unilstm_stack_fwd.  cfg: _lib.LstmStackCfg; w_* / b_*:
-    arrays of [L][1] device pointers, passed as they are; rng: the Philox state tensor, add: the offset."""
-    _lib.call("ganffn_unilstm_stack_fwd", C.byref(cfg), _ptr(lengths), _ptr(x), w_ih, w_hh, b_ih, b_hh, _ptr(out), _ptr(saved),
-              _ptr(ws), _ptr(rng), C.c_uint64(add), _stream())
-
-
-def unilstm_stack_bwd_raw(cfg, d_out, x, out, w_ih, w_hh, dx, gw_ih, gw_hh, gb_ih, gb_hh, saved, ws, rng, add, lengths=None):
-    """unilstm_stack_fwd_raw's backward: ONE call of ganffn_unilstm_stack_bwd; g*: arrays of [L][1] gradient pointers"""
-    _lib.call("ganffn_unilstm_stack_bwd", C.byref(cfg), _ptr(lengths), _ptr(d_out), _ptr(x), _ptr(out), w_ih, w_hh, _ptr(dx),
-              gw_ih, gw_hh, gb_ih, gb_hh, _ptr(saved), _ptr(ws), _ptr(rng), C.c_uint64(add), _stream())
-
-
 class UniLstmLayerFn(torch.autograd.Function):
-    """one forward-only LSTM layer (nn.LSTM(bidirectional=False); ganffn_unilstm_layer_*): x (S, B, In) -> (S, B, H), out[t] a
+    """one forward-only LSTM layer (nn.LSTM(bidirectional=False); the "uni" family): x (S, B, In) -> (S, B, H), out[t] a
     function of x[0 .. t] alone; torch's parameters weight_ih [4H x In], weight_hh [4H x H], bias_ih, bias_hh [4H].  lengths: None
     (the padded run) or int32 (B,) on the device with LstmPackedLayerFn's rule (zero output and zero dx past a dialogue's end;
-    x finite there).  One native call for B <= MAX_DIALOGUES; bigger batches run in chunks of MAX_DIALOGUES, lengths sliced
-    alongside the batch."""
+    x finite there).  The same call path as the two above: the direction count is the number of parameter tensors / 4."""
 
     @staticmethod
     def forward(ctx, x, lengths, *params):
-        _need_gpu(x, lengths, *params)
-        x = _f32c(x)
-        p = [_f32c(t.detach()) for t in params]          # w_ih, w_hh, b_ih, b_hh
-        S, B, In = x.shape
-        H = p[1].shape[1]
-        if lengths is not None:
-            if lengths.dtype != torch.int32 or tuple(lengths.shape) != (B,):
-                raise ValueError("lstm: lengths must be an int32 tensor of shape (%d,) on the device; got %s %s"
-                                 % (B, lengths.dtype, tuple(lengths.shape)))
-            lengths = lengths.contiguous()
-        out = torch.empty(S, B, H, device=x.device, dtype=torch.float32)
-        chunks = []
-        for b0 in range(0, B, MAX_DIALOGUES):
-            b1 = min(B, b0 + MAX_DIALOGUES)
-            whole = (b0, b1) == (0, B)
-            cfg = _lib.LstmCfg(S, b1 - b0, In, H)
-            n_saved, n_ws = unilstm_sizes(cfg)
-            xc = x if whole else x[:, b0:b1].contiguous()
-            oc = out if whole else torch.empty(S, b1 - b0, H, device=x.device, dtype=torch.float32)
-            saved = torch.empty(n_saved, device=x.device, dtype=torch.float32)
-            ws = torch.empty(n_ws, device=x.device, dtype=torch.float32)
-            lc = None if lengths is None else lengths[b0:b1]
-            unilstm_layer_fwd_raw(cfg, xc, *[_ptr_array([t]) for t in p], oc, saved, ws, lengths=lc)
-            if not whole:
-                out[:, b0:b1] = oc
-            chunks.append((b0, b1, xc, oc, saved, lc))
-        ctx.chunks, ctx.p, ctx.shape = chunks, p, (S, B, In, H)
-        return out
+        return _lstm_layer_fwd(ctx, x, lengths, params)
 
     @staticmethod
     def backward(ctx, d_out):
-        S, B, In, H = ctx.shape
-        p = ctx.p
-        d_out = _f32c(d_out)
-        need_dx = ctx.needs_input_grad[0]
-        dx = torch.empty(S, B, In, device=d_out.device, dtype=torch.float32) if need_dx else None
-        grads = [torch.zeros_like(t) if ctx.needs_input_grad[2 + i] else None for i, t in enumerate(p)]
-        for (b0, b1, xc, oc, saved, lc) in ctx.chunks:
-            whole = (b0, b1) == (0, B)
-            cfg = _lib.LstmCfg(S, b1 - b0, In, H)
-            ws = torch.empty(unilstm_sizes(cfg)[1], device=d_out.device, dtype=torch.float32)
-            dc = d_out if whole else d_out[:, b0:b1].contiguous()
-            dxc = None
-            if need_dx:
-                dxc = dx if whole else torch.empty(S, b1 - b0, In, device=d_out.device, dtype=torch.float32)
-            unilstm_layer_bwd_raw(cfg, dc, xc, oc, _ptr_array([p[0]]), _ptr_array([p[1]]), dxc,
-                                  *[_ptr_array([g]) for g in grads], saved, ws, lengths=lc)
-            if need_dx and not whole:
-                dx[:, b0:b1] = dxc
+        dx, grads = _lstm_layer_bwd(ctx, d_out, 0, 2)
         return (dx, None, *grads)
 
 

@@ -69,10 +69,19 @@ class _ExtBufs:
 
 class _GeneratorStream:
     """What the streaming sessions share: the three causal generators' per-layer K/V caches, stack configurations and workspaces,
-    the slots' positions (device int32 + host mirror), slot validation and reset."""
+    the slots' positions (device int32 + host mirror), slot validation and reset, and the body of a step and of an extend up to
+    the generators' stack outputs: a session is its __init__ and what it runs on those outputs."""
 
-    def _init_generators(self, net, capacity, max_len, dev, what):
-        self.net, self.capacity, self.max_len = net, int(capacity), int(max_len)
+    def _init_generators(self, net, capacity, max_len, dev, what, parties=None):
+        from .model import MAX_LEN
+        max_len = MAX_LEN if max_len is None else int(max_len)
+        if not 1 <= int(capacity) <= MAX_DIALOGUES:
+            raise ValueError("capacity=%r out of range [1, %d]" % (capacity, MAX_DIALOGUES))
+        if not 1 <= max_len <= MAX_LEN:
+            raise ValueError("max_len=%r out of range [1, %d] (PositionalEncoding max_len)" % (max_len, MAX_LEN))
+        if parties is not None and not 1 <= int(parties) <= ops.DRNN_MAX_PARTIES:
+            raise ValueError("parties=%r out of range [1, %d]" % (parties, ops.DRNN_MAX_PARTIES))
+        self.net, self.capacity, self.max_len = net, int(capacity), max_len
         self.gens = [getattr(net, k) for k in GEN_NAMES]
         for p in net.parameters():
             if not p.is_cuda or p.device != dev:
@@ -93,14 +102,24 @@ class _GeneratorStream:
         self._ext_bufs = {}
 
     # ---- state ----------------------------------------------------------------------------------------------------
-    def _check_slots(self, slots, what):
-        slots = [int(s) for s in slots]
+    def _check_slots(self, slots, what, n=None, unit=None):
+        """a slot list (ints or an int tensor) as distinct ints in [0, capacity).  With n, a call's slot list for its n rows or
+        columns (`unit`: what the message calls them), None meaning every slot -> a tuple of n"""
+        if slots is None:
+            if n != self.capacity:
+                raise ValueError("%s: slots=None means every slot: n must be the capacity %d, got %d" % (what, self.capacity, n))
+            slots = range(self.capacity)
+        slots = [int(s) for s in (slots.tolist() if torch.is_tensor(slots) else slots)]
         for s in slots:
             if not 0 <= s < self.capacity:
                 raise ValueError("%s: slot %d outside [0, %d)" % (what, s, self.capacity))
         if len(set(slots)) != len(slots):
             raise ValueError("%s: slots must be distinct, got %r" % (what, slots))
-        return slots
+        if n is None:
+            return slots
+        if len(slots) != n or n < 1:
+            raise ValueError("%s: %d %s for %d slots" % (what, n, unit, len(slots)))
+        return tuple(slots)
 
     def reset(self, slots=None):
         """positions of the given slots (all by default) back to 0; the stale cache behind them is never read"""
@@ -108,19 +127,19 @@ class _GeneratorStream:
             self.positions.zero_()
             self._host_pos = [0] * self.capacity
             return
-        slots = self._check_slots(slots.tolist() if torch.is_tensor(slots) else slots, "reset")
+        slots = self._check_slots(slots, "reset")
         if slots:
             self.positions.index_fill_(0, torch.tensor(slots, dtype=torch.int64, device=self.device), 0)
             for s in slots:
                 self._host_pos[s] = 0
 
     def _heads_sum(self, b):
-        """the generators' heads over the stack outputs b.enc and their sum -> b.fusion"""
+        """the generators' heads over the stack outputs b.enc and their sum -> b.fusion (returned)"""
         for i, g in enumerate(self.gens):
             ops.head_fwd_raw(b.head_cfg[i], b.enc[i], g.fc1.weight, g.fc1.bias, g.fc2.weight, g.fc2.bias, None, None,
                              b.head_out[i], b.head_saved[i], b.head_ws[i], None, 0)
-        ops._lib.call("ganffn_add3", ops._ptr(b.head_out[0]), ops._ptr(b.head_out[1]), ops._ptr(b.head_out[2]), ops._ptr(b.fusion),
-                      ops.C.c_int64(b.fusion.numel()), ops._stream())
+        ops.add3_raw(b.head_out[0], b.head_out[1], b.head_out[2], b.fusion, b.fusion.numel())
+        return b.fusion
 
     def _check_rows(self, xs, slots, what):
         """shapes of a step's inputs and its slot list -> (n, slots as a tuple); nothing full, nothing launched"""
@@ -128,13 +147,7 @@ class _GeneratorStream:
         for x, g in zip(xs, self.gens):
             if x.dim() != 2 or x.shape[0] != n or x.shape[1] != g.d_model:
                 raise ValueError("%s: inputs must be [n, 100], [n, 512], [n, 100]; got %s" % (what, [tuple(t.shape) for t in xs]))
-        if slots is None:
-            if n != self.capacity:
-                raise ValueError("%s: slots=None means every slot: n must be the capacity %d, got %d" % (what, self.capacity, n))
-            slots = range(self.capacity)
-        slots = tuple(self._check_slots(slots.tolist() if torch.is_tensor(slots) else slots, what))
-        if len(slots) != n or n < 1:
-            raise ValueError("%s: %d rows for %d slots" % (what, n, len(slots)))
+        slots = self._check_slots(slots, what, n, "rows")
         for s in slots:
             if self._host_pos[s] >= self.max_len:
                 raise ValueError("%s: slot %d is full (%d utterances); reset() it before its next dialogue" % (what, s, self.max_len))
@@ -150,13 +163,7 @@ class _GeneratorStream:
                 raise ValueError("%s: inputs must be [m, n, 100], [m, n, 512], [m, n, 100]; got %s" % (what, [tuple(t.shape) for t in xs]))
         if not 1 <= m <= self.max_len:
             raise ValueError("%s: m=%d utterances per call outside [1, max_len=%d]" % (what, m, self.max_len))
-        if slots is None:
-            if n != self.capacity:
-                raise ValueError("%s: slots=None means every slot: n must be the capacity %d, got %d" % (what, self.capacity, n))
-            slots = range(self.capacity)
-        slots = tuple(self._check_slots(slots.tolist() if torch.is_tensor(slots) else slots, what))
-        if len(slots) != n or n < 1:
-            raise ValueError("%s: %d columns for %d slots" % (what, n, len(slots)))
+        slots = self._check_slots(slots, what, n, "columns")
         lengths = tuple(int(c) for c in (lengths.tolist() if torch.is_tensor(lengths) else lengths))
         if len(lengths) != n:
             raise ValueError("%s: %d lengths for %d columns" % (what, len(lengths), n))
@@ -176,6 +183,60 @@ class _GeneratorStream:
             b.slot64.copy_(b.slot)
             b.slots_host = slots
 
+    def _new_bufs(self, m, n):
+        """the buffers of a step over n rows (m None) or of an extend over [m, n]; a session with a head of its own adds its buffers"""
+        return _Bufs(self, n) if m is None else _ExtBufs(self, m, n)
+
+    def _prepare_step(self, xs, n, slots):
+        """the buffers of a step at n (made on the first one), with this call's slots and inputs in them"""
+        b = self._bufs.get(n)
+        if b is None:
+            b = self._bufs[n] = self._new_bufs(None, n)
+        if b.slots_host != slots:
+            self._upload_slots(b, slots)
+        for dst, x in zip(b.x, xs):
+            dst.copy_(x)
+        return b
+
+    def _generator_steps(self, b, n):
+        """one stack step per generator over the n new rows b.x -> b.enc"""
+        for i, g in enumerate(self.gens):
+            ops.encoder_stream_step_raw(self.cfgs[i], n, b.slot, self.positions, b.x[i], self.pes[i], g.slab, self.caches[i],
+                                        b.enc[i], self.ws[i])
+
+    def _prepare_extend(self, m, n, slots, lengths):
+        """the buffers of an extend at (m, n) (made on the first one), with this call's slots and lengths in them"""
+        b = self._ext_bufs.get((m, n))
+        if b is None:
+            b = self._ext_bufs[(m, n)] = self._new_bufs(m, n)
+        self._upload_slots(b, slots)
+        if b.counts_host != lengths:
+            b.count.copy_(torch.tensor(lengths, dtype=torch.int32))
+            b.counts_host = lengths
+        return b
+
+    def _extend_groups(self, b, xs, m, tail, out):
+        """the generators' extend over each group of dialogues, then tail(r) on the group's row buffers r; what it returns
+        ([m * ng, W]) is the group's columns of out [m, n, W] (one group: out is that buffer itself)"""
+        single = len(b.groups) == 1
+        for lo, hi in b.groups:
+            ng = hi - lo
+            r = b.rows[ng]
+            for i, g in enumerate(self.gens):
+                xg = r.x[i].view(m, ng, g.d_model)
+                xg.copy_(xs[i] if single else xs[i][:, lo:hi])
+                ops.encoder_stream_extend_raw(self.cfgs[i], ng, m, b.slot[lo:hi], b.count[lo:hi], self.positions, xg, self.pes[i],
+                                              g.slab, self.caches[i], r.enc[i], b.ws[i])
+            res = tail(r)
+            if not single:
+                out[:, lo:hi].copy_(res.view(m, ng, -1))
+
+    def _advance(self, b, count, slots, lengths):
+        """the slots' positions += lengths (count: the same on the device), on the device and in the host mirror"""
+        self.positions.index_add_(0, b.slot64, count)
+        for s, c in zip(slots, lengths):
+            self._host_pos[s] += c
+
 
 class StreamSession(_GeneratorStream):
     """Per-dialogue K/V caches of a causal GAN_FFN and the step that labels one new utterance of up to `capacity` concurrent
@@ -188,15 +249,9 @@ class StreamSession(_GeneratorStream):
     to a causal mask."""
 
     def __init__(self, net, capacity=1, max_len=None, use_graph=False):
-        from .model import MAX_LEN
-        max_len = MAX_LEN if max_len is None else int(max_len)
         if not getattr(net, "causal", False):
             raise ValueError("GAN_FFN.stream() needs a classifier built with causal=True: row t of a bidirectional classifier "
                              "depends on the utterances after it, so it cannot be labelled as it arrives")
-        if not 1 <= int(capacity) <= MAX_DIALOGUES:
-            raise ValueError("capacity=%r out of range [1, %d]" % (capacity, MAX_DIALOGUES))
-        if not 1 <= max_len <= MAX_LEN:
-            raise ValueError("max_len=%r out of range [1, %d] (PositionalEncoding max_len)" % (max_len, MAX_LEN))
         self.use_graph = bool(use_graph)
         self._init_generators(net, capacity, max_len, net.fc.weight.device, "GAN_FFN.stream()")
 
@@ -207,18 +262,18 @@ class StreamSession(_GeneratorStream):
     def _body(self, b, n):
         """the launches of a step, on the current stream: one stack step and one head per generator, sum, fc, log_softmax,
         then the position advance"""
-        for i, g in enumerate(self.gens):
-            ops.encoder_stream_step_raw(self.cfgs[i], n, b.slot, self.positions, b.x[i], self.pes[i], g.slab, self.caches[i],
-                                        b.enc[i], self.ws[i])
-        self._tail(b, n)
+        self._generator_steps(b, n)
+        self._tail(b)
         self.positions.index_add_(0, b.slot64, b.ones)
 
-    def _tail(self, b, n):
-        """the row-wise rest of the classifier over n rows of stack outputs b.enc: the generators' heads, sum, fc, log_softmax"""
-        net = self.net
+    def _tail(self, b):
+        """the row-wise rest of the classifier over the rows of stack outputs b.enc: the generators' heads, sum, fc, log_softmax
+        -> b.log_prob"""
+        net, n = self.net, b.fusion.shape[0]
         self._heads_sum(b)
         ops.linear_fwd_raw(b.fusion, net.fc.weight, net.fc.bias, b.logits, n, net.fc.weight.shape[1], net.n_classes)
         ops.logsoftmax_nll_raw(b.logits, None, None, None, b.log_prob, None, None, None, 1, n, net.n_classes)
+        return b.log_prob
 
     def _graph_key(self):
         """the addresses a captured graph froze: a re-packed slab (a .to() that moved the module) asks for a new capture"""
@@ -234,12 +289,7 @@ class StreamSession(_GeneratorStream):
         the session's buffer for that n: the next step with the same n overwrites it."""
         xs = (acoustic, visual, text)
         n, slots = self._check_rows(xs, slots, "step")
-        b = self._bufs.get(n)
-        if b is None:
-            b = self._bufs[n] = _Bufs(self, n)
-        self._upload_slots(b, slots)
-        for dst, x in zip(b.x, xs):
-            dst.copy_(x)
+        b = self._prepare_step(xs, n, slots)
         if not self.use_graph:
             self._body(b, n)
         else:
@@ -255,7 +305,7 @@ class StreamSession(_GeneratorStream):
                 with torch.cuda.graph(b.graph):
                     self._body(b, n)
                 b.graph_key = key
-        for s in slots:
+        for s in slots:                     # (the device side of the advance: in _body, for the graph)
             self._host_pos[s] += 1
         return b.log_prob
 
@@ -276,28 +326,9 @@ class StreamSession(_GeneratorStream):
         tensor is the session's buffer for that (m, n): the next extend at the same (m, n) overwrites it."""
         xs = (acoustic, visual, text)
         m, n, slots, lengths = self._check_chunks(xs, lengths, slots, "extend")
-        b = self._ext_bufs.get((m, n))
-        if b is None:
-            b = self._ext_bufs[(m, n)] = _ExtBufs(self, m, n)
-        self._upload_slots(b, slots)
-        if b.counts_host != lengths:
-            b.count.copy_(torch.tensor(lengths, dtype=torch.int32))
-            b.counts_host = lengths
-        single = len(b.groups) == 1
-        for lo, hi in b.groups:
-            ng = hi - lo
-            r = b.rows[ng]
-            for i, g in enumerate(self.gens):
-                xg = r.x[i].view(m, ng, g.d_model)
-                xg.copy_(xs[i] if single else xs[i][:, lo:hi])
-                ops.encoder_stream_extend_raw(self.cfgs[i], ng, m, b.slot[lo:hi], b.count[lo:hi], self.positions, xg, self.pes[i],
-                                              g.slab, self.caches[i], r.enc[i], b.ws[i])
-            self._tail(r, m * ng)
-            if not single:
-                b.log_prob[:, lo:hi].copy_(r.log_prob.view(m, ng, -1))
-        self.positions.index_add_(0, b.slot64, b.count)
-        for s, c in zip(slots, lengths):
-            self._host_pos[s] += c
+        b = self._prepare_extend(m, n, slots, lengths)
+        self._extend_groups(b, xs, m, self._tail, b.log_prob)
+        self._advance(b, b.count, slots, lengths)
         return b.log_prob
 
 
@@ -335,21 +366,13 @@ class DrnnStreamSession(_GeneratorStream):
     dialogues so far.  Values agree with the rows of the net's full causal forward to rounding, not bit for bit."""
 
     def __init__(self, net, capacity=1, max_len=None, parties=2):
-        from .model import MAX_LEN
-        max_len = MAX_LEN if max_len is None else int(max_len)
         if not getattr(net, "causal", False):
             raise ValueError("GAN_FFN_DialogueRNN.stream() needs a classifier built with causal=True: the bidirectional head reads "
                              "the future (its reverse DialogueRNN starts at the dialogue's last utterance), so no row can be "
                              "labelled as it arrives")
-        if not 1 <= int(capacity) <= MAX_DIALOGUES:
-            raise ValueError("capacity=%r out of range [1, %d]" % (capacity, MAX_DIALOGUES))
-        if not 1 <= max_len <= MAX_LEN:
-            raise ValueError("max_len=%r out of range [1, %d] (PositionalEncoding max_len)" % (max_len, MAX_LEN))
-        if not 1 <= int(parties) <= ops.DRNN_MAX_PARTIES:
-            raise ValueError("parties=%r out of range [1, %d]" % (parties, ops.DRNN_MAX_PARTIES))
         um = net.bi_model
         cell = um.dialog_rnn_f.dialogue_cell
-        self._init_generators(net, capacity, max_len, um.linear.weight.device, "GAN_FFN_DialogueRNN.stream()")
+        self._init_generators(net, capacity, max_len, um.linear.weight.device, "GAN_FFN_DialogueRNN.stream()", parties)
         self.parties = int(parties)
         att = ops.drnn_att_type(cell)
         if cell.D_g != cell.D_p:
@@ -378,6 +401,14 @@ class DrnnStreamSession(_GeneratorStream):
 
     def _fusion_width(self):
         return self.cell.D_m
+
+    def _new_bufs(self, m, n):
+        b = super()._new_bufs(m, n)
+        b.head = _HeadBufs(self, (m or 1) * n, (n,) if m is None else (m, n))
+        if m is not None:
+            b.fusion = (b.rows[n].fusion.view(m, n, -1) if len(b.groups) == 1 else
+                        torch.empty(m, n, self.cell.D_m, device=self.device, dtype=torch.float32))
+        return b
 
     def _check_speakers(self, speakers, shape, lengths, what):
         """speakers as host ints of the given shape, validated against the party count (entries past a length: ignored, sent as 0)"""
@@ -413,8 +444,7 @@ class DrnnStreamSession(_GeneratorStream):
         ops.linear_fwd_raw(h.e, tr.weight, tr.bias, h.xt, rows, De, De)
         ops.general2_stream_attention_raw(h.xt, self.e_hist, b.slot, count, self.positions, h.att, None, n, m, self.capacity,
                                           self.max_len, De)
-        ops._lib.call("ganffn_ffn_linear1_fwd", ops._ptr(h.att), ops._ptr(um.linear.weight), ops._ptr(um.linear.bias), ops._ptr(h.hidden),
-                      rows, De, Dh, ops.C.c_float(0.0), ops.C.c_uint32(0), None, ops.C.c_uint64(0), 0, ops._stream())
+        ops.linear1_fwd_raw(h.att, um.linear.weight, um.linear.bias, h.hidden, rows, De, Dh, 0.0, 0, None, 0, False)
         ops.linear_fwd_raw(h.hidden, um.smax_fc.weight, um.smax_fc.bias, h.logits, rows, Dh, Cn)
         ops.logsoftmax_nll_raw(h.logits, None, None, None, h.log_prob, None, None, None, 1, rows, Cn)
 
@@ -429,22 +459,12 @@ class DrnnStreamSession(_GeneratorStream):
         xs = (acoustic, visual, text)
         n, slots = self._check_rows(xs, slots, "step")
         spk = self._check_speakers(speakers, (n,), None, "step")
-        b = self._bufs.get(n)
-        if b is None:
-            b = self._bufs[n] = _Bufs(self, n)
-            b.head = _HeadBufs(self, n, (n,))
-        self._upload_slots(b, slots)
+        b = self._prepare_step(xs, n, slots)
         b.head.upload_speakers(spk)
-        for dst, x in zip(b.x, xs):
-            dst.copy_(x)
-        for i, g in enumerate(self.gens):
-            ops.encoder_stream_step_raw(self.cfgs[i], n, b.slot, self.positions, b.x[i], self.pes[i], g.slab, self.caches[i],
-                                        b.enc[i], self.ws[i])
+        self._generator_steps(b, n)
         self._heads_sum(b)
         self._head_tail(b.head, b.fusion, b, n, 1, None)
-        self.positions.index_add_(0, b.slot64, b.ones)
-        for s in slots:
-            self._host_pos[s] += 1
+        self._advance(b, b.ones, slots, (1,) * n)
         return b.head.log_prob
 
     # ---- several utterances per active dialogue --------------------------------------------------------------------------
@@ -459,31 +479,9 @@ class DrnnStreamSession(_GeneratorStream):
         xs = (acoustic, visual, text)
         m, n, slots, lengths = self._check_chunks(xs, lengths, slots, "extend")
         spk = self._check_speakers(speakers, (m, n), lengths, "extend")
-        b = self._ext_bufs.get((m, n))
-        if b is None:
-            b = self._ext_bufs[(m, n)] = _ExtBufs(self, m, n)
-            b.head = _HeadBufs(self, m * n, (m, n))
-            b.fusion = (b.rows[n].fusion.view(m, n, -1) if len(b.groups) == 1 else
-                        torch.empty(m, n, self.cell.D_m, device=self.device, dtype=torch.float32))
-        self._upload_slots(b, slots)
-        if b.counts_host != lengths:
-            b.count.copy_(torch.tensor(lengths, dtype=torch.int32))
-            b.counts_host = lengths
+        b = self._prepare_extend(m, n, slots, lengths)
         b.head.upload_speakers(spk)
-        single = len(b.groups) == 1
-        for lo, hi in b.groups:
-            ng = hi - lo
-            r = b.rows[ng]
-            for i, g in enumerate(self.gens):
-                xg = r.x[i].view(m, ng, g.d_model)
-                xg.copy_(xs[i] if single else xs[i][:, lo:hi])
-                ops.encoder_stream_extend_raw(self.cfgs[i], ng, m, b.slot[lo:hi], b.count[lo:hi], self.positions, xg, self.pes[i],
-                                              g.slab, self.caches[i], r.enc[i], b.ws[i])
-            self._heads_sum(r)
-            if not single:
-                b.fusion[:, lo:hi].copy_(r.fusion.view(m, ng, -1))
+        self._extend_groups(b, xs, m, self._heads_sum, b.fusion)
         self._head_tail(b.head, b.fusion, b, n, m, b.count)
-        self.positions.index_add_(0, b.slot64, b.count)
-        for s, c in zip(slots, lengths):
-            self._host_pos[s] += c
+        self._advance(b, b.count, slots, lengths)
         return b.head.log_prob.view(m, n, -1)

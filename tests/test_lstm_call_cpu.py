@@ -1,7 +1,7 @@
 """The one place that decides which entry-point family of the LSTM a call takes, without a GPU: ops.lstm_family against the
-rule written out here, the argument list the four ops.lstm_*_raw helpers hand to _lib.call for every family (name, count against
-_lib.SIGNATURES, order, lengths in second place), ops.lstm_sizes against the size functions the table names, and the twenty
-ganffn_lstm_* signatures against a literal copy."""
+rule written out here, the argument list the four ops.lstm_*_raw helpers hand to _lib.call for every family — the one-direction
+family (ndir=1) among them — (name, count against _lib.SIGNATURES, order, lengths in second place), ops.lstm_sizes against the size
+functions the table names, and the twenty ganffn_lstm_* signatures against a literal copy."""
 import ctypes as C
 
 import pytest
@@ -10,9 +10,10 @@ import torch
 # family -> what its layer calls, stack calls, layer size functions and stack size functions are called
 NAMES = {"": ("ganffn_lstm_layer_%s", "ganffn_lstm_stack_%s", "ganffn_lstm_%s_floats", "ganffn_lstm_stack_%s_floats"),
          "batch": ("ganffn_lstm_batch_layer_%s", "ganffn_lstm_stack_batch_%s", "ganffn_lstm_batch_%s_floats", "ganffn_lstm_stack_batch_%s_floats"),
-         "packed": ("ganffn_lstm_packed_layer_%s", "ganffn_lstm_stack_packed_%s", "ganffn_lstm_batch_%s_floats", "ganffn_lstm_stack_batch_%s_floats")}
-# (B, packed) of a call that takes the family
-TAKES = {"": (3, False), "batch": (33, False), "packed": (3, True)}
+         "packed": ("ganffn_lstm_packed_layer_%s", "ganffn_lstm_stack_packed_%s", "ganffn_lstm_batch_%s_floats", "ganffn_lstm_stack_batch_%s_floats"),
+         "uni": ("ganffn_unilstm_layer_%s", "ganffn_unilstm_stack_%s", "ganffn_unilstm_%s_floats", "ganffn_unilstm_stack_%s_floats")}
+# (B, packed, ndir) of a call that takes the family; the one-direction family takes lengths (here NULL) behind cfg whatever B
+TAKES = {"": (3, False, 2), "batch": (33, False, 2), "packed": (3, True, 2), "uni": (40, False, 1)}
 
 
 def test_family_rule():
@@ -20,6 +21,8 @@ def test_family_rule():
     for B, want in ((1, ""), (32, ""), (33, "batch"), (256, "batch")):
         assert ops.lstm_family(B, False) == want, B
         assert ops.lstm_family(B, True) == "packed", B
+        assert ops.lstm_family(B, False, 2) == want and ops.lstm_family(B, True, 2) == "packed", B
+        assert ops.lstm_family(B, False, 1) == ops.lstm_family(B, True, 1) == "uni", B
 
 
 LAYER_FWD = "x w_ih w_hh b_ih b_hh out saved ws"
@@ -33,15 +36,16 @@ def test_raw_calls_pass_the_familys_argument_list(family, monkeypatch):
     calls = []
     monkeypatch.setattr(_lib, "call", lambda name, *a: calls.append((name, a)))
     monkeypatch.setattr(ops, "_stream", lambda: "the stream")
-    B, packed = TAKES[family]
+    B, packed, ndir = TAKES[family]
+    kw = {} if ndir == 2 else {"ndir": ndir}                    # two directions: the default
     s = {k: torch.zeros(4) for k in "x out saved ws d_out dx rng".split()}
     s.update({k: "<%s>" % k for k in ARRAYS})                   # the pointer arrays go through as they are
     lengths = torch.zeros(B, dtype=torch.int32) if packed else None
     layer, stack = _lib.LstmCfg(5, B, 12, 8), _lib.LstmStackCfg(5, B, 12, 8, 3, 0.5, 1)
-    ops.lstm_layer_fwd_raw(layer, *[s[k] for k in LAYER_FWD.split()], lengths=lengths)
-    ops.lstm_layer_bwd_raw(layer, *[s[k] for k in LAYER_BWD.split()], lengths=lengths)
-    ops.lstm_stack_fwd_raw(stack, *[s[k] for k in LAYER_FWD.split()], s["rng"], 77, lengths=lengths)
-    ops.lstm_stack_bwd_raw(stack, *[s[k] for k in LAYER_BWD.split()], s["rng"], 78, lengths=lengths)
+    ops.lstm_layer_fwd_raw(layer, *[s[k] for k in LAYER_FWD.split()], lengths=lengths, **kw)
+    ops.lstm_layer_bwd_raw(layer, *[s[k] for k in LAYER_BWD.split()], lengths=lengths, **kw)
+    ops.lstm_stack_fwd_raw(stack, *[s[k] for k in LAYER_FWD.split()], s["rng"], 77, lengths=lengths, **kw)
+    ops.lstm_stack_bwd_raw(stack, *[s[k] for k in LAYER_BWD.split()], s["rng"], 78, lengths=lengths, **kw)
     assert len(calls) == 4
     want = [(NAMES[family][0] % "fwd", layer, LAYER_FWD, None), (NAMES[family][0] % "bwd", layer, LAYER_BWD, None),
             (NAMES[family][1] % "fwd", stack, LAYER_FWD + " rng", 77), (NAMES[family][1] % "bwd", stack, LAYER_BWD + " rng", 78)]
@@ -53,6 +57,8 @@ def test_raw_calls_pass_the_familys_argument_list(family, monkeypatch):
         if packed:
             got = a.pop(0)                                                           # then lengths, when given
             assert isinstance(got, C.c_void_p) and got.value == lengths.data_ptr(), name
+        elif ndir == 1:
+            assert a.pop(0) is None, name                                            # one direction: always there, NULL for the padded run
         assert a.pop() == "the stream"
         if add is not None:
             got = a.pop()
@@ -66,20 +72,23 @@ def test_raw_calls_pass_the_familys_argument_list(family, monkeypatch):
     # what may be left out is: dx and the gradient arrays go through as null
     calls.clear()
     ops.lstm_stack_bwd_raw(stack, s["d_out"], s["x"], s["out"], s["w_ih"], s["w_hh"], None, None, None, None, None, s["saved"],
-                           s["ws"], s["rng"], 0, lengths=lengths)
+                           s["ws"], s["rng"], 0, lengths=lengths, **kw)
     (name, a), = calls
-    assert list(a[6 + packed:11 + packed]) == [None] * 5 and len(a) == len(_lib.SIGNATURES[name][1])
+    k = 6 + (packed or ndir == 1)
+    assert list(a[k:k + 5]) == [None] * 5 and len(a) == len(_lib.SIGNATURES[name][1])
 
 
 @pytest.mark.parametrize("family", list(TAKES))
 def test_sizes_come_from_the_size_functions_the_table_names(family):
     from gan_ffn_amd import _lib, ops
     lib = _lib.load()
-    B, packed = TAKES[family]
+    B, packed, ndir = TAKES[family]
     for cfg, names in ((_lib.LstmCfg(5, B, 12, 8), NAMES[family][2]), (_lib.LstmStackCfg(5, B, 12, 8, 3, 0.5, 1), NAMES[family][3])):
         want = tuple(int(getattr(lib, names % w)(C.byref(cfg))) for w in ("saved", "workspace"))
         assert want[0] > 0 and want[1] > 0
-        assert ops.lstm_sizes(cfg, packed) == want
+        assert ops.lstm_sizes(cfg, packed, ndir) == want
+        if ndir == 2:
+            assert ops.lstm_sizes(cfg, packed) == want
     assert ops.lstm_sizes(_lib.LstmCfg(5, B, 12, 8)) == ops.lstm_sizes(_lib.LstmCfg(5, B, 12, 8), False)
 
 
