@@ -69,6 +69,10 @@ class DrnnStreamCfg(C.Structure):  # ganffn_drnn_stream_cfg: the streamed head's
                 ("He", C.c_int32), ("listener", C.c_int32), ("att", DrnnAtt)]
 
 
+class LstmStreamCfg(C.Structure):  # ganffn_stream_lstm_cfg: the streamed LSTM's state and widths
+    _fields_ = [("capacity", C.c_int32), ("max_len", C.c_int32), ("In", C.c_int32), ("H", C.c_int32), ("L", C.c_int32)]
+
+
 BATCH_MAX_COLS = 4                 # GANFFN_BATCH_MAX_COLS
 
 
@@ -181,6 +185,10 @@ SIGNATURES = {
     "ganffn_drnn_stream_step": (_I, [C.POINTER(DrnnStreamCfg), _I, _P, _P, _I] + [_P] * 10),
     "ganffn_drnn_stream_extend": (_I, [C.POINTER(DrnnStreamCfg), _I, _I] + [_P] * 12),
     "ganffn_general2_stream_attention": (_I, [_P] * 7 + [_I] * 5 + [_P]),
+    "ganffn_stream_lstm_state_floats": (_L, [C.POINTER(LstmStreamCfg)]),
+    "ganffn_stream_lstm_workspace_floats": (_L, [C.POINTER(LstmStreamCfg), _I]),
+    "ganffn_stream_lstm_step": (_I, [C.POINTER(LstmStreamCfg), _I, _P, _P, _I] + [_P] * 10),
+    "ganffn_stream_lstm_extend": (_I, [C.POINTER(LstmStreamCfg), _I, _I] + [_P] * 12),
     "ganffn_encoder_fwd_pair_len":(_I, [_PE, _P, _P, _P, _P, _P, _P, _P, _P, _P, _U64, _P]),
     "ganffn_encoder_bwd_parts_len": (_I, [_PE, _P, _P, _P, _P, _P, _P, _P, _U64, _I, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int), _P]),
     "ganffn_encoder_fwd_pair_mask": (_I, [_PE, _P, _U32, _P, _P, _P, _P, _P, _P, _P, _P, _U64, _P]),

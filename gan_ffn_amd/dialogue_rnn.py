@@ -358,6 +358,18 @@ class MELDLSTMModel(nn.Module):
         self.matchatt = MatchingAttention(D, D, att_type="general2")
         self.linear = nn.Linear(D, D_h)
         self.smax_fc = nn.Linear(D_h, n_classes)
+        self.stream = self._open_stream            # a plain instance attribute (a bound method): see _open_stream
+
+    def _open_stream(self, capacity=1, max_len=110):
+        """model.stream(capacity=1, max_len=MAX_LEN): the name `stream` is bound on every INSTANCE in __init__, not on the class, as
+        GAN_FFN_DialogueRNN binds its own (tests/test_stream_cpu.py and tests/test_stream_extend_cpu.py pin that the class carries no
+        `stream`).  -> a streaming.MeldStreamSession: label each utterance of up to `capacity` concurrent dialogues as it arrives,
+        from per-slot (h, c) of every LSTM layer and the slot's emotion history (one LSTM step per new utterance instead of the
+        whole prefix).  Needs causal=True — the bidirectional LSTM's reverse direction starts at the dialogue's end — and D_h == D_e
+        (the att2=True branch).  max_len: positions per slot (<= model.MAX_LEN = 110).  `packed` is irrelevant: a stream has no
+        padding."""
+        from .streaming import MeldStreamSession
+        return MeldStreamSession(self, capacity, max_len)
 
     def forward(self, U, qmask, umask, visuf=None, att2=True):
         if self.causal and att2 and self.D_h != self.D_e:

@@ -803,6 +803,62 @@ def general2_stream_attention_raw(x, e_hist, slot, count, pos, att, alpha, n, m,
               n, m, capacity, max_len, D, _stream())
 
 
+# ---- the streamed LSTM (csrc/lstm_stream.hip): one step of the L layers per new utterance against per-slot state ---------------
+LSTM_STREAM_MAX_H = 1024       # the emotion history is the memory of ganffn_general2_stream_attention (D <= 1024)
+LSTM_STREAM_MAX_LAYERS = 16
+MELD_HEAD_MAX_CLASSES = 16     # ganffn_meld_head_*: smax_fc's rows are held per thread
+
+
+def lstm_stream_cfg(capacity, max_len, In, H, L):
+    """_lib.LstmStreamCfg: the state's shape (capacity slots of max_len positions, L layers) and the LSTM's widths"""
+    return _lib.LstmStreamCfg(int(capacity), int(max_len), int(In), int(H), int(L))
+
+
+def lstm_stream_sizes(cfg, n_max):
+    """(state floats, workspace floats for calls of up to n_max rows) of a streamed LSTM (ganffn_stream_lstm_*_floats)"""
+    lib = _lib.load()
+    s = int(lib.ganffn_stream_lstm_state_floats(C.byref(cfg)))
+    w = int(lib.ganffn_stream_lstm_workspace_floats(C.byref(cfg), int(n_max))) if s >= 0 else -1
+    if s < 0 or w < 0:
+        _lib.check(-1, "ganffn_stream_lstm_*_floats")
+    return s, w
+
+
+def lstm_stream_ptrs(lstm):
+    """(w_ih, w_hh, b_ih, b_hh): arrays of num_layers device pointers of a forward-only nn.LSTM, read from lstm.weight_ih_l{k}, ...
+    now — the streamed step reads the parameters in place, wherever they live at call time (a step runner's slab included)"""
+    names = ("weight_ih_l%d", "weight_hh_l%d", "bias_ih_l%d", "bias_hh_l%d")
+    tensors = [[getattr(lstm, n % l) for l in range(lstm.num_layers)] for n in names]
+    for t in (t for row in tensors for t in row):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise GanffnError("the streamed LSTM step reads the LSTM's parameters in place: float32 and contiguous")
+    _need_gpu(*[t for row in tensors for t in row])
+    return tuple(_ptr_array(row) for row in tensors)
+
+
+def lstm_stream_step_raw(cfg, n, slot, pos, x, ptrs, state, e_out, ws, off=0, count=None):
+    """one step of the L layers over n rows (ganffn_stream_lstm_step; eval math): row i of x [n x In] is utterance
+    pos[slot[i]] + off of the dialogue in slot slot[i]; writes the state and e_out [n x H].  pos is not advanced.
+    ptrs: lstm_stream_ptrs(lstm)."""
+    _need_gpu(slot, pos, count, x, state, e_out, ws)
+    _lib.call("ganffn_stream_lstm_step", C.byref(cfg), n, _ptr(slot), _ptr(pos), int(off), _ptr(count), _ptr(x), *ptrs, _ptr(state),
+              _ptr(e_out), _ptr(ws), _stream())
+
+
+def lstm_stream_extend_raw(cfg, n, m, slot, count, pos, x, ptrs, state, e_out, ws):
+    """count[i] consecutive steps of n dialogues in one native call (ganffn_stream_lstm_extend): x [m][n][In] and e_out [m][n][H]
+    time-major.  pos is not advanced."""
+    _need_gpu(slot, count, pos, x, state, e_out, ws)
+    _lib.call("ganffn_stream_lstm_extend", C.byref(cfg), n, m, _ptr(slot), _ptr(count), _ptr(pos), _ptr(x), *ptrs, _ptr(state),
+              _ptr(e_out), _ptr(ws), _stream())
+
+
+def meld_head_fwd_raw(emotions, att, w_fc, b_fc, hidden, logits, T, D, Cn):
+    """hidden = hardswish(emotions + hardswish(att)), logits = hidden w_fc^T + b_fc over T rows (ganffn_meld_head_fwd)"""
+    _need_gpu(emotions, att, w_fc, b_fc, hidden, logits)
+    _lib.call("ganffn_meld_head_fwd", _ptr(emotions), _ptr(att), _ptr(w_fc), _ptr(b_fc), _ptr(hidden), _ptr(logits), T, D, Cn, _stream())
+
+
 class DialogueRNNFn(torch.autograd.Function):
     """ndir (1 or 2) DialogueRNNs through one chain of launches (drnn_fwd_raw / drnn_bwd_raw; which entry points they reach:
     drnn_family).

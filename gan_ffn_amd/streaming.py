@@ -12,6 +12,9 @@ utterances that arrive in bursts.
 `GAN_FFN_DialogueRNN(causal=True).stream(capacity, max_len, parties)` returns a DrnnStreamSession: the same generator caches plus
 the DialogueRNN head's per-slot state (global history, party states, emotion history; csrc/drnn_stream.hip), one recurrence step
 per new utterance.
+
+`MELDLSTMModel(causal=True).stream(capacity, max_len)` returns a MeldStreamSession: no generators, the forward-only LSTM's per-slot
+(h, c) of every layer and the emotion history (csrc/lstm_stream.hip), one LSTM step per new utterance.
 """
 import torch
 
@@ -67,35 +70,31 @@ class _ExtBufs:
                          torch.empty(m, n, sess.net.n_classes, device=dev, dtype=torch.float32))
 
 
-class _GeneratorStream:
-    """What the streaming sessions share: the three causal generators' per-layer K/V caches, stack configurations and workspaces,
-    the slots' positions (device int32 + host mirror), slot validation and reset, and the body of a step and of an extend up to
-    the generators' stack outputs: a session is its __init__ and what it runs on those outputs."""
+class _SlotStream:
+    """The slot and position bookkeeping every streaming session shares: `capacity` slots of up to `max_len` positions, the
+    positions on the device (int32) with a host mirror that only step, extend and reset change, slot-list validation, reset, the
+    slot upload of a call's buffers and the position advance."""
 
-    def _init_generators(self, net, capacity, max_len, dev, what, parties=None):
+    @staticmethod
+    def _check_capacity(capacity, max_len):
+        """-> (capacity, max_len) as ints in range (max_len None: model.MAX_LEN), else ValueError"""
         from .model import MAX_LEN
         max_len = MAX_LEN if max_len is None else int(max_len)
         if not 1 <= int(capacity) <= MAX_DIALOGUES:
             raise ValueError("capacity=%r out of range [1, %d]" % (capacity, MAX_DIALOGUES))
         if not 1 <= max_len <= MAX_LEN:
             raise ValueError("max_len=%r out of range [1, %d] (PositionalEncoding max_len)" % (max_len, MAX_LEN))
-        if parties is not None and not 1 <= int(parties) <= ops.DRNN_MAX_PARTIES:
-            raise ValueError("parties=%r out of range [1, %d]" % (parties, ops.DRNN_MAX_PARTIES))
-        self.net, self.capacity, self.max_len = net, int(capacity), max_len
-        self.gens = [getattr(net, k) for k in GEN_NAMES]
+        return int(capacity), max_len
+
+    @staticmethod
+    def _check_one_gpu(net, dev, what):
         for p in net.parameters():
             if not p.is_cuda or p.device != dev:
                 raise ops.GanffnError("%s: every parameter must be on one GPU (got %s and %s); there is no CPU "
                                       "fallback" % (what, dev, p.device))
+
+    def _init_positions(self, dev):
         self.device = dev
-        self.cfgs, self.caches, self.ws, self.pes = [], [], [], []
-        for g in self.gens:
-            cfg = ops.enc_cfg(self.max_len, self.capacity, g.d_model, g.nhead, g.num_layers, train=False)
-            n_cache, n_ws = ops.stream_sizes(cfg, self.capacity)
-            self.cfgs.append(cfg)
-            self.caches.append(torch.empty(n_cache, device=dev, dtype=torch.float32))     # never read at or above a position
-            self.ws.append(torch.empty(n_ws, device=dev, dtype=torch.float32))
-            self.pes.append(g.position_encoding.pe)
         self.positions = torch.zeros(self.capacity, device=dev, dtype=torch.int32)
         self._host_pos = [0] * self.capacity      # host mirror: only step, extend and reset change the positions
         self._bufs = {}
@@ -133,6 +132,70 @@ class _GeneratorStream:
             for s in slots:
                 self._host_pos[s] = 0
 
+    def _check_not_full(self, slots, what):
+        for s in slots:
+            if self._host_pos[s] >= self.max_len:
+                raise ValueError("%s: slot %d is full (%d utterances); reset() it before its next dialogue" % (what, s, self.max_len))
+
+    def _check_lengths(self, m, n, lengths, slots, what):
+        """an extend's m, its slot list and lengths -> (slots, lengths) as tuples; nothing launched"""
+        if not 1 <= m <= self.max_len:
+            raise ValueError("%s: m=%d utterances per call outside [1, max_len=%d]" % (what, m, self.max_len))
+        slots = self._check_slots(slots, what, n, "columns")
+        lengths = tuple(int(c) for c in (lengths.tolist() if torch.is_tensor(lengths) else lengths))
+        if len(lengths) != n:
+            raise ValueError("%s: %d lengths for %d columns" % (what, len(lengths), n))
+        for s, c in zip(slots, lengths):
+            if not 1 <= c <= m:
+                raise ValueError("%s: length %d of slot %d outside [1, m=%d]" % (what, c, s, m))
+        for s, c in zip(slots, lengths):
+            if self._host_pos[s] + c > self.max_len:
+                raise ValueError("%s: slot %d holds %d of max_len=%d utterances: %d more fit, not %d; reset() it before its next "
+                                 "dialogue" % (what, s, self._host_pos[s], self.max_len, self.max_len - self._host_pos[s], c))
+        return slots, lengths
+
+    @staticmethod
+    def _upload_slots(b, slots):
+        if b.slots_host != slots:
+            b.slot.copy_(torch.tensor(slots, dtype=torch.int32))
+            b.slot64.copy_(b.slot)
+            b.slots_host = slots
+
+    @staticmethod
+    def _upload_counts(b, lengths):
+        if b.counts_host != lengths:
+            b.count.copy_(torch.tensor(lengths, dtype=torch.int32))
+            b.counts_host = lengths
+
+    def _advance(self, b, count, slots, lengths):
+        """the slots' positions += lengths (count: the same on the device), on the device and in the host mirror"""
+        self.positions.index_add_(0, b.slot64, count)
+        for s, c in zip(slots, lengths):
+            self._host_pos[s] += c
+
+
+class _GeneratorStream(_SlotStream):
+    """What the generator-backed streaming sessions share besides the slots (_SlotStream): the three causal generators' per-layer
+    K/V caches, stack configurations and workspaces, and the body of a step and of an extend up to the generators' stack outputs:
+    a session is its __init__ and what it runs on those outputs."""
+
+    def _init_generators(self, net, capacity, max_len, dev, what, parties=None):
+        capacity, max_len = self._check_capacity(capacity, max_len)
+        if parties is not None and not 1 <= int(parties) <= ops.DRNN_MAX_PARTIES:
+            raise ValueError("parties=%r out of range [1, %d]" % (parties, ops.DRNN_MAX_PARTIES))
+        self.net, self.capacity, self.max_len = net, capacity, max_len
+        self.gens = [getattr(net, k) for k in GEN_NAMES]
+        self._check_one_gpu(net, dev, what)
+        self.cfgs, self.caches, self.ws, self.pes = [], [], [], []
+        for g in self.gens:
+            cfg = ops.enc_cfg(self.max_len, self.capacity, g.d_model, g.nhead, g.num_layers, train=False)
+            n_cache, n_ws = ops.stream_sizes(cfg, self.capacity)
+            self.cfgs.append(cfg)
+            self.caches.append(torch.empty(n_cache, device=dev, dtype=torch.float32))     # never read at or above a position
+            self.ws.append(torch.empty(n_ws, device=dev, dtype=torch.float32))
+            self.pes.append(g.position_encoding.pe)
+        self._init_positions(dev)
+
     def _heads_sum(self, b):
         """the generators' heads over the stack outputs b.enc and their sum -> b.fusion (returned)"""
         for i, g in enumerate(self.gens):
@@ -148,9 +211,7 @@ class _GeneratorStream:
             if x.dim() != 2 or x.shape[0] != n or x.shape[1] != g.d_model:
                 raise ValueError("%s: inputs must be [n, 100], [n, 512], [n, 100]; got %s" % (what, [tuple(t.shape) for t in xs]))
         slots = self._check_slots(slots, what, n, "rows")
-        for s in slots:
-            if self._host_pos[s] >= self.max_len:
-                raise ValueError("%s: slot %d is full (%d utterances); reset() it before its next dialogue" % (what, s, self.max_len))
+        self._check_not_full(slots, what)
         return n, slots
 
     def _check_chunks(self, xs, lengths, slots, what):
@@ -161,27 +222,8 @@ class _GeneratorStream:
         for x, g in zip(xs, self.gens):
             if x.dim() != 3 or x.shape[0] != m or x.shape[1] != n or x.shape[2] != g.d_model:
                 raise ValueError("%s: inputs must be [m, n, 100], [m, n, 512], [m, n, 100]; got %s" % (what, [tuple(t.shape) for t in xs]))
-        if not 1 <= m <= self.max_len:
-            raise ValueError("%s: m=%d utterances per call outside [1, max_len=%d]" % (what, m, self.max_len))
-        slots = self._check_slots(slots, what, n, "columns")
-        lengths = tuple(int(c) for c in (lengths.tolist() if torch.is_tensor(lengths) else lengths))
-        if len(lengths) != n:
-            raise ValueError("%s: %d lengths for %d columns" % (what, len(lengths), n))
-        for s, c in zip(slots, lengths):
-            if not 1 <= c <= m:
-                raise ValueError("%s: length %d of slot %d outside [1, m=%d]" % (what, c, s, m))
-        for s, c in zip(slots, lengths):
-            if self._host_pos[s] + c > self.max_len:
-                raise ValueError("%s: slot %d holds %d of max_len=%d utterances: %d more fit, not %d; reset() it before its next "
-                                 "dialogue" % (what, s, self._host_pos[s], self.max_len, self.max_len - self._host_pos[s], c))
+        slots, lengths = self._check_lengths(m, n, lengths, slots, what)
         return m, n, slots, lengths
-
-    @staticmethod
-    def _upload_slots(b, slots):
-        if b.slots_host != slots:
-            b.slot.copy_(torch.tensor(slots, dtype=torch.int32))
-            b.slot64.copy_(b.slot)
-            b.slots_host = slots
 
     def _new_bufs(self, m, n):
         """the buffers of a step over n rows (m None) or of an extend over [m, n]; a session with a head of its own adds its buffers"""
@@ -210,9 +252,7 @@ class _GeneratorStream:
         if b is None:
             b = self._ext_bufs[(m, n)] = self._new_bufs(m, n)
         self._upload_slots(b, slots)
-        if b.counts_host != lengths:
-            b.count.copy_(torch.tensor(lengths, dtype=torch.int32))
-            b.counts_host = lengths
+        self._upload_counts(b, lengths)
         return b
 
     def _extend_groups(self, b, xs, m, tail, out):
@@ -230,12 +270,6 @@ class _GeneratorStream:
             res = tail(r)
             if not single:
                 out[:, lo:hi].copy_(res.view(m, ng, -1))
-
-    def _advance(self, b, count, slots, lengths):
-        """the slots' positions += lengths (count: the same on the device), on the device and in the host mirror"""
-        self.positions.index_add_(0, b.slot64, count)
-        for s, c in zip(slots, lengths):
-            self._host_pos[s] += c
 
 
 class StreamSession(_GeneratorStream):
@@ -485,3 +519,135 @@ class DrnnStreamSession(_GeneratorStream):
         self._head_tail(b.head, b.fusion, b, n, m, b.count)
         self._advance(b, b.count, slots, lengths)
         return b.head.log_prob.view(m, n, -1)
+
+
+# ---- the causal MELD classifier -----------------------------------------------------------------------------------------------
+class _MeldBufs:
+    """everything a MELD step over n rows (m None) or an extend over [m, n] touches: allocated on the first call at that n or
+    (m, n), never again"""
+
+    def __init__(self, sess, m, n):
+        dev, f32 = sess.device, dict(device=sess.device, dtype=torch.float32)
+        rows, De, Cn = (m or 1) * n, sess.D_e, sess.model.n_classes
+        self.slot = torch.zeros(n, device=dev, dtype=torch.int32)
+        self.slot64 = torch.zeros(n, device=dev, dtype=torch.int64)
+        self.ones = torch.ones(n, device=dev, dtype=torch.int32)
+        self.count = torch.zeros(n, device=dev, dtype=torch.int32) if m is not None else None
+        self.slots_host = self.counts_host = None                       # what the device copies hold, to skip equal uploads
+        self.x = torch.zeros(rows, sess.D_m, **f32)
+        self.e = torch.empty(rows, De, **f32)
+        self.xt = torch.empty(rows, De, **f32)
+        self.att = torch.empty(rows, De, **f32)
+        self.hidden = torch.empty(rows, De, **f32)
+        self.logits = torch.empty(rows, Cn, **f32)
+        self.log_prob = torch.empty(rows, Cn, **f32)
+
+
+class MeldStreamSession(_SlotStream):
+    """The streaming form of MELDLSTMModel(causal=True): per slot, (h, c) of every LSTM layer after the dialogue's last utterance
+    and the emotion history e_0 .. e_{t-1}, which is the memory of the causal general2 attention (csrc/lstm_stream.hip; layout in
+    include/ganffn.h).  `step` runs ONE LSTM step per new utterance instead of the whole prefix: log_prob[t] of the causal
+    classifier depends on utterances 0 .. t only, so each row is final when it is returned.  A step is 13 launches of the library
+    at four layers: the LSTM step's 9, then matchatt.transform, the single-query general2 attention over the slot's history,
+    hardswish(e + hardswish(att)) with smax_fc, log_softmax.
+
+    Always eval math under no_grad (no dropout), whatever model.training says; the weights are read from the model's parameter
+    tensors at call time.  CHANGED WEIGHTS: the state is stale after a training step — reset() and `extend` with the dialogues so
+    far.  `packed` is irrelevant to a stream, which has no padding.  Values agree with the rows of the model's full causal
+    forward to rounding, not bit for bit."""
+
+    def __init__(self, model, capacity=1, max_len=None):
+        if not getattr(model, "causal", False):
+            raise ValueError("MELDLSTMModel.stream() needs a classifier built with causal=True: the bidirectional LSTM reads the "
+                             "future (its reverse direction starts at the dialogue's end), so no row can be labelled as it arrives")
+        lstm = model.lstm
+        if model.D_h != model.D_e:
+            raise ValueError("MELDLSTMModel.stream(): the att2=True branch hands the D_e-wide hidden to smax_fc, so it needs "
+                             "D_h == D_e; got D_e=%d D_h=%d" % (model.D_e, model.D_h))
+        if lstm.bidirectional or not ops.lstm_supported(lstm):
+            raise ValueError("MELDLSTMModel.stream(): the LSTM must be forward-only with the layout ops.lstm_supported accepts "
+                             "((seq, batch, feature), biases, no projection, input and hidden sizes multiples of 4)")
+        if lstm.hidden_size > ops.LSTM_STREAM_MAX_H or not 1 <= lstm.num_layers <= ops.LSTM_STREAM_MAX_LAYERS:
+            raise ValueError("MELDLSTMModel.stream(): D_e=%d, num_layers=%d outside the step kernels' limits (D_e <= %d, 1 .. %d "
+                             "layers)" % (lstm.hidden_size, lstm.num_layers, ops.LSTM_STREAM_MAX_H, ops.LSTM_STREAM_MAX_LAYERS))
+        if not 1 <= model.n_classes <= ops.MELD_HEAD_MAX_CLASSES:
+            raise ValueError("MELDLSTMModel.stream(): n_classes=%d outside [1, %d]" % (model.n_classes, ops.MELD_HEAD_MAX_CLASSES))
+        self.capacity, self.max_len = self._check_capacity(capacity, max_len)
+        self.model, self.lstm = model, lstm
+        self.D_m, self.D_e, self.L = lstm.input_size, lstm.hidden_size, lstm.num_layers
+        dev = model.smax_fc.weight.device
+        self._check_one_gpu(model, dev, "MELDLSTMModel.stream()")
+        self.cfg = ops.lstm_stream_cfg(self.capacity, self.max_len, self.D_m, self.D_e, self.L)
+        n_state, n_ws = ops.lstm_stream_sizes(self.cfg, self.capacity)
+        self.state = torch.empty(n_state, device=dev, dtype=torch.float32)            # never read at or above a position
+        self.ws = torch.empty(n_ws, device=dev, dtype=torch.float32)
+        a4 = lambda k: (k + 3) & ~3                                                   # noqa: E731  (the header's region rule)
+        e_off = 2 * a4(self.capacity * self.L * self.D_e)
+        self.e_hist = self.state[e_off:e_off + self.capacity * self.max_len * self.D_e]  # the E region: the attention's memory
+        self._init_positions(dev)
+
+    def _buffers(self, m, n):
+        cache, key = (self._bufs, n) if m is None else (self._ext_bufs, (m, n))
+        b = cache.get(key)
+        if b is None:
+            b = cache[key] = _MeldBufs(self, m, n)
+        return b
+
+    def _run(self, b, n, m, count):
+        """the launches of a call over m * n time-major rows b.x: the LSTM (one step, or the native extend), transform, the
+        attention over the slot's emotion history, the hardswish head with smax_fc, log_softmax -> b.log_prob"""
+        mod, rows, De, Cn = self.model, m * n, self.D_e, self.model.n_classes
+        ptrs = ops.lstm_stream_ptrs(self.lstm)                 # (refuses parameters that left the GPU: before any launch)
+        if count is None:
+            ops.lstm_stream_step_raw(self.cfg, n, b.slot, self.positions, b.x, ptrs, self.state, b.e, self.ws)
+        else:
+            ops.lstm_stream_extend_raw(self.cfg, n, m, b.slot, count, self.positions, b.x, ptrs, self.state, b.e, self.ws)
+        tr = mod.matchatt.transform
+        ops.linear_fwd_raw(b.e, tr.weight, tr.bias, b.xt, rows, De, De)
+        ops.general2_stream_attention_raw(b.xt, self.e_hist, b.slot, count, self.positions, b.att, None, n, m, self.capacity,
+                                          self.max_len, De)
+        ops.meld_head_fwd_raw(b.e, b.att, mod.smax_fc.weight, mod.smax_fc.bias, b.hidden, b.logits, rows, De, Cn)
+        ops.logsoftmax_nll_raw(b.logits, None, None, None, b.log_prob, None, None, None, 1, rows, Cn)
+
+    # ---- one utterance per active dialogue ---------------------------------------------------------------------------
+    @torch.no_grad()
+    def step(self, text, slots=None):
+        """text [n, D_m]: the next utterance of n dialogues -> log_prob [n, n_classes].  slots: None = slots 0 .. capacity-1 (then
+        n == capacity), or n distinct ints in [0, capacity) (list or int tensor): row i belongs to the dialogue in slot slots[i].
+        Everything — the shape, the slots, a full slot (max_len utterances) — is validated before any launch and with no position
+        moved (ValueError).  Never reads from the device (pass slots as a list), allocates only on the first step at a given n;
+        the returned tensor is the session's buffer for that n: the next step with the same n overwrites it."""
+        if text.dim() != 2 or text.shape[1] != self.D_m:
+            raise ValueError("step: text must be [n, %d]; got %s" % (self.D_m, tuple(text.shape)))
+        n = int(text.shape[0])
+        slots = self._check_slots(slots, "step", n, "rows")
+        self._check_not_full(slots, "step")
+        b = self._buffers(None, n)
+        self._upload_slots(b, slots)
+        b.x.copy_(text)
+        self._run(b, n, 1, None)
+        self._advance(b, b.ones, slots, (1,) * n)
+        return b.log_prob
+
+    # ---- several utterances per active dialogue --------------------------------------------------------------------------
+    @torch.no_grad()
+    def extend(self, text, lengths, slots=None):
+        """text [m, n, D_m], time-major (a padded batch of dialogue pieces passes straight in): the next lengths[i] utterances
+        (n host ints, 1 <= lengths[i] <= m) of n dialogues -> log_prob [m, n, n_classes], rows past a length unspecified.  ONE
+        native LSTM extend (the recurrence is serial in t: lengths[i] steps per dialogue with no host synchronisation), then the
+        row-wise tail over all rows; the positions advance by `lengths`, on the device and in the host mirror.  Rows j >=
+        lengths[i] of text must be finite; their values change no bit of a valid row or of the state.  Raises ValueError before
+        any launch and with no position moved for a wrong shape, slots that repeat or lie outside the capacity, a length outside
+        [1, m] and a dialogue that would pass max_len.  Never reads from the device, allocates only on the first call at a given
+        (m, n); the returned tensor is the session's buffer for that (m, n)."""
+        if text.dim() != 3 or text.shape[2] != self.D_m:
+            raise ValueError("extend: text must be [m, n, %d]; got %s" % (self.D_m, tuple(text.shape)))
+        m, n = int(text.shape[0]), int(text.shape[1])
+        slots, lengths = self._check_lengths(m, n, lengths, slots, "extend")
+        b = self._buffers(m, n)
+        self._upload_slots(b, slots)
+        self._upload_counts(b, lengths)
+        b.x.view(m, n, self.D_m).copy_(text)
+        self._run(b, n, m, b.count)
+        self._advance(b, b.count, slots, lengths)
+        return b.log_prob.view(m, n, -1)

@@ -729,6 +729,46 @@ int ganffn_drnn_stream_extend(const ganffn_drnn_stream_cfg* cfg, int n, int m, c
 int ganffn_general2_stream_attention(const float* x, const float* e_hist, const int32_t* slot, const int32_t* count,
                                      const int32_t* pos, float* att, float* alpha, int n, int m, int capacity, int max_len, int D,
                                      void* stream);
+/* ---- streaming: the causal MELD classifier's LSTM one utterance at a time (csrc/lstm_stream.hip) -------------------------------
+ * nn.LSTM(In, H, num_layers = L, bidirectional = False) in eval mode (the recurrence of MELDLSTMModel(causal=True)): everything a
+ * step needs from the past is (h, c) of every layer, kept as per-slot STATE next to the emotion history that
+ * ganffn_general2_stream_attention reads.  slot [n], pos [capacity], count [n] int32 on the device, with the meaning they have
+ * above; pos is READ ONLY (the caller advances it after the last consumer of a step); the slots of one call must be distinct.
+ * State layout (the caller owns it; tests fill it directly): three regions back to back, each rounded up to a multiple of 4 floats:
+ *   Hs [capacity][L][H]         h of every layer after the slot's last step: layer l of slot s at (s * L + l) * H
+ *   Cs [capacity][L][H]         c of every layer
+ *   E  [capacity][max_len][H]   emotion history: E[s][t] = the last layer's h_t (the same bits as Hs[s][L-1] after step t)
+ * Words of E at or above a slot's position are never read, and at t = 0 every layer's h_prev and c_prev are taken as zeros WITHOUT
+ * reading the state: it needs no initialisation and a slot is reset by setting its position to 0.
+ * ganffn_stream_lstm_step: row i of x [n x In] is utterance t = pos[slot[i]] + off of the dialogue in slot slot[i]; a plain step
+ * passes off = 0, count = NULL; with count given row i takes part only if off < count[i].  It computes torch's LSTM cell (gate
+ * order i, f, g, o) for the L layers in turn with w_ih[l] [4H x In or H], w_hh[l] [4H x H], b_ih[l], b_hh[l] [4H] (host arrays of
+ * L device pointers, weights 16-byte aligned) and writes Hs[s], Cs[s], E[s][t] and e_out[i] = the last layer's h_t ([n x H]).
+ * Inference only: nothing saved, no atomics, every summation order fixed; the bits of a row depend on no other row of the call.
+ * 2 L + 1 launches at L <= 7: gather, the L recurrent products and layer 0's input product in one launch, then per layer a gate
+ * launch and (but for the last) the next layer's input product.
+ * SKIP: a row whose slot is outside [0, capacity), whose position is negative, whose t is outside [0, max_len) or that count
+ * masks: the state is untouched and e_out[i] is a zero row; nothing is accessed out of range whatever the index arrays hold.
+ * Refused with a message before any launch (the size functions return a negative value): null or misaligned pointers, n outside
+ * [1, capacity], m outside [1, max_len], capacity outside [1, GANFFN_MAX_DIALOGUES], max_len outside [1, 110], In or H not a
+ * multiple of 4, H > 1024, L outside [1, 16], n_max > capacity.
+ * ganffn_stream_lstm_extend: the step m times with off = 0 .. m-1 on time-major rows (x [m][n][In], e_out [m][n][H]), count [n]
+ * required, no host synchronisation; the state it leaves is bit for bit that of the m step calls.
+ * workspace: ganffn_stream_lstm_workspace_floats(cfg, n_max >= n), n_max <= capacity. */
+typedef struct ganffn_stream_lstm_cfg {
+    int32_t capacity, max_len;   /* slots (1 .. GANFFN_MAX_DIALOGUES), positions per slot (1 .. 110) */
+    int32_t In, H, L;            /* input and hidden widths (multiples of 4, H <= 1024), layers (1 .. 16) */
+} ganffn_stream_lstm_cfg;
+int64_t ganffn_stream_lstm_state_floats(const ganffn_stream_lstm_cfg* cfg);
+int64_t ganffn_stream_lstm_workspace_floats(const ganffn_stream_lstm_cfg* cfg, int n_max);
+int ganffn_stream_lstm_step(const ganffn_stream_lstm_cfg* cfg, int n, const int32_t* slot, const int32_t* pos, int off,
+                            const int32_t* count, const float* x, const float* const* w_ih, const float* const* w_hh,
+                            const float* const* b_ih, const float* const* b_hh, float* state, float* e_out, float* workspace,
+                            void* stream);
+int ganffn_stream_lstm_extend(const ganffn_stream_lstm_cfg* cfg, int n, int m, const int32_t* slot, const int32_t* count,
+                              const int32_t* pos, const float* x, const float* const* w_ih, const float* const* w_hh,
+                              const float* const* b_ih, const float* const* b_hh, float* state, float* e_out, float* workspace,
+                              void* stream);
 /* z = x + drop(y); xhat = (z-mean)*rstd; out = xhat*w + b   (norm1/norm2 of the encoder layer).  Accepted: T >= 1 and
  * 1 <= E <= 640, a multiple of 4 or not; a wider row is refused with a message.  The variance is the two-pass one (mean
  * of the squared deviations), so a row mean far above the row's spread costs no more than fp32 rounding of z itself. */
